@@ -8,14 +8,20 @@ step was accepted), damped LDL^T solve, retraction, cost-only evaluation, accept
 damping_iter run ends (<= 10 iterations or the 1e-6 relative-decrease test) the next one restarts from
 the same perturbed poses, so the timed steps are the iteration mix a real refinement executes.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3|C2|NxV]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3|C2|NxV] [--dump-outputs DIR] [--full]
 N > 1 is launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`:
 one rank per GPU, voxels sharded by contiguous range (bavoxel.hpp:621-624 with thread -> GPU), the
 pose-block Hessian / gradient / cost all-reduced over RCCL inside liblvba_hip.so; the two ends of the band
 factorisation run on ranks 0 and 1 (the middle block is exchanged), the rest of the solve is replicated.  Total work is
 fixed as N grows -> "scaling": "strong".
 
-Rank 0 prints ONE JSON line.  `roofline` is the H/g/cost evaluation ("Jacobian") pass against HBM, from
+Rank 0 prints ONE JSON line.  A plain run sets up, runs W warm-up steps, times exactly K steps (`value`, `ms_per_step`) and
+prints the line; --dump-outputs DIR also writes what the last timed step left to a caller (the LM run's poses, poses.npy
+[N, 12] float64, and that step's trace row, lm_step.npy: LM_STEP_FIELDS as float64) -- the inputs are seeded, so two builds can
+be compared file by file.  Everything else below is --full only (the --no-* switches choose among its legs): further timed
+regions for the spread, the profiled pass and what is derived from it, the side legs, the CPU baselines and the parity gate.
+
+`roofline` is the H/g/cost evaluation ("Jacobian") pass against HBM, from
 HIP-event durations recorded on the library's stream around its kernels during the timed steps and the
 algorithmic bytes of SURVEY.md section 8(d); `cpu_baseline` is the C restatement (oracle/balm_oracle.c)
 timed on this host on ONE full LM iteration of the same problem, and `parity` holds the HIP path against it at that
@@ -37,7 +43,8 @@ import numpy as np
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8 TB/s spec (6.3 TB/s measured achievable)
 FP64_PEAK_TFLOPS = 78.6    # MI355X fp64 vector == fp64 MFMA peak (256 CU x 128 flop/clk x 2.4 GHz)
 L2_PEAK_TBS = 34.5         # MI355X_MICROARCH.md: aggregate L2 -> CU bandwidth, 8 XCDs
-REGIONS = 5                 # timed regions of --steps steps each; the line carries the median region and the spread
+REGIONS = 5                 # --full: timed regions of --steps steps each (the first is the headline's), their spread in `timing`
+LM_STEP_FIELDS = ("iter", "accepted", "evaluated", "status", "residual1", "residual2", "u", "v", "q", "q1")   # lm_step.npy
 
 
 def parse_config(name, synth):
@@ -148,6 +155,14 @@ def cpu_model():
     return None
 
 
+def dump_outputs(dirname, poses, row):
+    """--dump-outputs: what a caller of the timed path holds after its last step -- the LM run's poses [N, 12] as lvba_balm_lm_end
+    returns them, and that step's trace row (LM_STEP_FIELDS, lvba_lm_trace) -- as float64 .npy files in `dirname`."""
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "poses.npy"), np.ascontiguousarray(poses, np.float64))
+    np.save(os.path.join(dirname, "lm_step.npy"), np.array([row[k] for k in LM_STEP_FIELDS], np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -165,7 +180,13 @@ def main():
                          "transport entry point with a host-staged torch.distributed all-reduce: a REHEARSAL of the torchrun path on "
                          "a box with fewer GPUs than ranks (with --same-device); its rate is not a result")
     ap.add_argument("--same-device", action="store_true", help="all ranks on GPU 0 (rehearsal with --transport gloo)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed (poses.npy, lm_step.npy) to DIR")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the timing spread over further regions, the profiled pass (stage times, roofline, "
+                         "scaling model), the y32 / visual / front-end legs, the CPU baselines and the parity gate")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the ranks ourselves, exactly as the documented command does
@@ -218,8 +239,9 @@ def main():
         torch.cuda.synchronize()
 
     state = {"active": False, "runs": 0, "evals": 0, "accepts": 0, "evals_on_records": 0}
+    ended = {"poses": None}     # what lm_end handed back when a run ended on a step that asked for the poses
 
-    def step():
+    def step(want_poses=False):
         if not state["active"]:
             prob.lm_begin(x0)
             state["active"] = True
@@ -230,39 +252,77 @@ def main():
         # an evaluation after an accepted step starts from the voxel records the trial-point cost pass left (lvba_api.hip)
         state["evals_on_records"] += int(bool(row["evaluated"]) and row["iter"] > 0 and bool(info["trial_linearised"]))
         if done or rc != 0:
-            prob.lm_end(want_poses=False)
+            ended["poses"] = prob.lm_end(want_poses=want_poses)
             state["active"] = False
         return row
 
-    for _ in range(args.warmup):
-        step()
-    # ---- the timed regions: REGIONS x [exactly K steps between barrier + synchronize, MAX over ranks], the library's event
-    # profiling OFF (it costs ~1 % of a step).  `value` / `ms_per_step` are the MEDIAN region's; min / max are printed beside
-    # them (a single 0.12-s region moved by +-1.5 % from run to run in round 4).
-    prob.set_profiling(False)
-    region_s, region_state = [], []
-    last = None
-    for _ in range(REGIONS):
+    def timed_region(want_poses=False):
+        """exactly K steps between barrier + synchronize, MAX over ranks: (seconds, trace row of the last step, counters)"""
         state.update(runs=int(state["active"]), evals=0, accepts=0, evals_on_records=0)
         barrier()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
-            last = step()
+        for i in range(args.steps):
+            row = step(want_poses and i == args.steps - 1)
         barrier()
         el = time.perf_counter() - t0
         if dist is not None:
             tt = torch.tensor([el], dtype=torch.float64)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             el = float(tt[0])
+        return el, row, {k: state[k] for k in ("runs", "evals", "accepts", "evals_on_records")}
+
+    def finish(out, parity_ok=True):
+        if out is not None:
+            print(json.dumps(out), flush=True)
+        prob.close()
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        if not parity_ok:
+            raise SystemExit("bench.py: the HIP path disagrees with the oracle beyond 1e-7 at the benchmark size (see \"parity\")")
+
+    for _ in range(args.warmup):
+        step()
+    # ---- the timed steps: exactly K steps, the library's event profiling OFF (it costs ~1 % of a step); `value` /
+    # `ms_per_step` are theirs.  --full times REGIONS - 1 further regions of K steps after them (they continue the LM runs) and
+    # prints the spread in `timing` (a single 0.12-s region moved by +-1.5 % from run to run in round 4).
+    prob.set_profiling(False)
+    elapsed, last, timed = timed_region(want_poses=args.dump_outputs is not None)
+    if args.dump_outputs is not None:
+        if state["active"]:         # the LM run goes on past the last timed step: its poses as they stand
+            ended["poses"] = prob.lm_end(want_poses=True)
+            state["active"] = False
+        if rank == 0:
+            dump_outputs(args.dump_outputs, ended["poses"], last)
+    region_s, region_state = [elapsed], [timed]
+    for _ in range(REGIONS - 1 if args.full else 0):
+        el, last, counts = timed_region()
         region_s.append(el)
-        region_state.append({k: state[k] for k in ("runs", "evals", "accepts", "evals_on_records")})
-    mid = sorted(range(REGIONS), key=lambda r: region_s[r])[REGIONS // 2]
-    elapsed = region_s[mid]
-    state.update(region_state[mid])
+        region_state.append(counts)
     if state["active"]:
         prob.lm_end(want_poses=False)
         state["active"] = False
-    timed = dict(state)
+
+    def headline():
+        n, bw = 6 * N, 6 * info["band_blocks"] + 5
+        return {
+            "metric": "LM iterations/sec, 2k poses x 10M LiDAR factors (BALM damping_iter)",
+            "value": args.steps / elapsed, "unit": "iterations/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "strong",
+            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": f"{args.config}: BALM LiDAR BA, {N} poses x {V} voxels x {F_total} LiDAR factors "
+                                   f"(plane-eigenvalue factors, exact Hessian, Nielsen LM)",
+                       "n_poses": N, "n_voxels": V, "n_factors": F_total, "n_pairs_local": info["n_pairs"],
+                       "sharding": (f"voxel ranges over {world} rank(s), {'RCCL' if args.transport == 'rccl' else 'HOST-STAGED gloo (rehearsal)'} all-reduce of pose-block H/g/cost, "
+                                    f"{info['allreduce_bytes'] / 1e6:.0f} MB per evaluation") if world > 1 else "single GPU",
+                       "solver": ("band" if info["use_band"] else "dense") + f" LDL^T, half-bandwidth {bw} of n={n}",
+                       "lm_runs": timed["runs"], "evals_in_timed_steps": timed["evals"],
+                       "accepted_in_timed_steps": timed["accepts"], "last_cost": last["residual2"]}}
+
+    if not args.full:
+        finish(headline() if rank == 0 else None)
+        return
+    mid = sorted(range(REGIONS), key=lambda r: region_s[r])[REGIONS // 2]
     # ---- a second, UNTIMED pass over the same K steps with HIP events on the library's stream around its kernels: the stage
     # times and the kernel durations of the `roofline` objects come from here (same problem, same start, same iteration mix)
     state.update(runs=0, evals=0, accepts=0, evals_on_records=0)
@@ -301,8 +361,8 @@ def main():
                                  "process drives several GPUs through lvba_window_ba_multi"}
 
     parity_ok = True
+    out = None
     if rank == 0:
-        ms = 1e3 * elapsed / args.steps
         # algorithmic bytes of one H/g/cost evaluation of THIS rank's shard:
         #   84 B/factor (80 B cluster + 4 B pose index) + 4 B/voxel offsets + 96 B/pose + 8 B cost
         #   + upper pose blocks written once: 8 * (36 * nnzb + 6 N)
@@ -375,28 +435,18 @@ def main():
                                    "single panels): the matrix pipe and the serial chain of panel factorisations "
                                    "bound the solve, not HBM"}})
         others.append(solve_roof)
-        out = {
-            "metric": "LM iterations/sec, 2k poses x 10M LiDAR factors (BALM damping_iter)",
-            "value": args.steps / elapsed, "unit": "iterations/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": ms, "higher_is_better": True, "scaling": "strong",
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": f"{args.config}: BALM LiDAR BA, {N} poses x {V} voxels x {F_total} LiDAR factors "
-                                   f"(plane-eigenvalue factors, exact Hessian, Nielsen LM)",
-                       "n_poses": N, "n_voxels": V, "n_factors": F_total, "n_pairs_local": info["n_pairs"],
-                       "sharding": (f"voxel ranges over {world} rank(s), {'RCCL' if args.transport == 'rccl' else 'HOST-STAGED gloo (rehearsal)'} all-reduce of pose-block H/g/cost, "
-                                    f"{info['allreduce_bytes'] / 1e6:.0f} MB per evaluation") if world > 1 else "single GPU",
-                       "solver": ("band" if info["use_band"] else "dense") + f" LDL^T, half-bandwidth {bw} of n={n}",
-                       "lm_runs": timed["runs"], "evals_in_timed_steps": timed["evals"],
-                       "accepted_in_timed_steps": timed["accepts"], "last_cost": last["residual2"] if last else None},
+        out = headline()
+        out.update({
             "stage_ms": {"eval": p["eval_ms"] / max(1, p["eval_calls"]), "solve": sv_ms,
                          "cost": p["cost_ms"] / max(1, p["cost_calls"]),
                          "allreduce": p["reduce_ms"] / max(1, p["reduce_calls"]) if p["reduce_calls"] else 0.0},
             "stage_ms_source": {"pass": "second, untimed pass over the same K steps with the library's HIP-event profiling on "
                                         "(the timed region runs with it off)", "ms_per_step": 1e3 * elapsed_profiled / args.steps,
                                 "evals": state["evals"], "accepted": state["accepts"]},
-            "timing": {"regions": REGIONS, "steps_per_region": args.steps, "value_is": "median region",
+            "timing": {"regions": REGIONS, "steps_per_region": args.steps, "value_is": "first region (the timed steps of a plain run)",
                        "ms_per_step_by_region": [1e3 * t / args.steps for t in region_s],
                        "ms_per_step_min": 1e3 * min(region_s) / args.steps, "ms_per_step_max": 1e3 * max(region_s) / args.steps,
+                       "ms_per_step_median": 1e3 * region_s[mid] / args.steps,
                        "value_min": args.steps / max(region_s), "value_max": args.steps / min(region_s),
                        "median_region": mid,
                        # (the regions continue one another's LM runs: their iteration mix differs, deterministically)
@@ -410,7 +460,7 @@ def main():
             "roofline_cost_pass_in_loop": others[0],
             "roofline_other_kernels": others,
             "scaling_model": scaling_model(p, sv_ms, info, world, prob),
-        }
+        })
         if windows_multi is not None:
             out["window_stage_all_ranks"] = windows_multi
         if world == 1 and not args.no_y32:
@@ -445,13 +495,7 @@ def main():
             except Exception as e:  # the baseline is a reported number, not part of the measured path
                 out["cpu_baseline"] = {"value": None, "unit": "iterations/s", "cores": 0, "kind": "port",
                                        "sample": f"failed: {e!r}"}
-        print(json.dumps(out), flush=True)
-    prob.close()
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
-    if not parity_ok:
-        raise SystemExit("bench.py: the HIP path disagrees with the oracle beyond 1e-7 at the benchmark size (see \"parity\")")
+    finish(out, parity_ok)
 
 
 def relaunch_under_torchrun(n):

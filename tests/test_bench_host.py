@@ -3,6 +3,8 @@ import importlib.util
 import os
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -43,3 +45,13 @@ def test_ldlt_chain_length():
     b = _bench()
     assert b.ldlt_chain(12000, 2597) == 73 + 42
     assert b.ldlt_chain(640, 600) == 10          # too short for the two-ended form
+
+
+def test_dump_outputs_writes_float64_arrays(tmp_path):
+    b = _bench()
+    poses = np.arange(36.0).reshape(3, 12)
+    row = {k: float(i) for i, k in enumerate(b.LM_STEP_FIELDS)}
+    b.dump_outputs(str(tmp_path / "out"), poses, row)
+    p, r = np.load(tmp_path / "out" / "poses.npy"), np.load(tmp_path / "out" / "lm_step.npy")
+    assert p.dtype == np.float64 and np.array_equal(p, poses)
+    assert r.dtype == np.float64 and np.array_equal(r, np.arange(len(b.LM_STEP_FIELDS), dtype=np.float64))

@@ -17,8 +17,8 @@ for cfg in C3 C4; do
     extra="--no-visual --no-front-end --no-y32 --no-reference-baseline"
     [ "$n" -gt 1 ] && extra="$extra --no-cpu-baseline"
     [ "$cfg" = C4 ] && extra="$extra --steps 10 --warmup 2 --no-cpu-baseline"
-    if [ "$n" -eq 1 ]; then python bench.py --gpus 1 --config $cfg $extra > profiles/first_node_${cfg}_${n}gpu.json 2> profiles/first_node_${cfg}_${n}gpu.err
-    else python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29540 + n)) bench.py --gpus $n --config $cfg $extra > profiles/first_node_${cfg}_${n}gpu.json 2> profiles/first_node_${cfg}_${n}gpu.err; fi
+    if [ "$n" -eq 1 ]; then python bench.py --full --gpus 1 --config $cfg $extra > profiles/first_node_${cfg}_${n}gpu.json 2> profiles/first_node_${cfg}_${n}gpu.err
+    else python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29540 + n)) bench.py --full --gpus $n --config $cfg $extra > profiles/first_node_${cfg}_${n}gpu.json 2> profiles/first_node_${cfg}_${n}gpu.err; fi
     echo "$cfg on $n GPU(s): $(grep -o '"value": [0-9.]*' profiles/first_node_${cfg}_${n}gpu.json | head -1) $(grep -o '"ms_per_step": [0-9.]*' profiles/first_node_${cfg}_${n}gpu.json | head -1)"
   done
 done

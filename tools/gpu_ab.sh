@@ -5,6 +5,6 @@ cd $R
 i=0
 for e in "$@"; do
   i=$((i+1))
-  env $e python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-visual --no-front-end --no-y32 > $O/b_$i.json 2> $O/b_$i.err
+  env $e python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-visual --no-front-end --no-y32 > $O/b_$i.json 2> $O/b_$i.err
   echo "$e: $(grep -o '"ms_per_step": [0-9.]*' $O/b_$i.json | head -1) $(grep -o '"stage_ms": {[^}]*}' $O/b_$i.json)"
 done

@@ -6,7 +6,7 @@ export TMPDIR=/tmp; cd /tmp
 i=0
 for e in "$@"; do
   i=$((i+1)); rm -rf /tmp/ks_$i
-  e2=$(echo "$e" | sed "s#=ab/#=$R/ab/#"); env $e2 rocprofv3 --kernel-trace --stats -d /tmp/ks_$i -o s -- python $R/bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-visual --no-front-end --no-y32 > $O/bench_$i.json 2> $O/bench_$i.err
+  e2=$(echo "$e" | sed "s#=ab/#=$R/ab/#"); env $e2 rocprofv3 --kernel-trace --stats -d $TMPDIR/ks_$i -o s -- python $R/bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-visual --no-front-end --no-y32 > $O/bench_$i.json 2> $O/bench_$i.err
   python $R/tools/rocpd_stats.py /tmp/ks_$i/s_results.db $O/stats_$i.csv > /dev/null
   echo "== $e"
   python - <<PY

@@ -5,7 +5,7 @@ TAG=${1:-trace}; shift
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O
 export TMPDIR=/tmp
 cd /tmp; rm -rf /tmp/tr1
-env "$@" timeout 600 rocprofv3 --kernel-trace -d /tmp/tr1 -o t -- python $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-visual --no-front-end --no-y32 > $O/bench_under_trace.json 2> $O/bench_under_trace.err
+env "$@" timeout 600 rocprofv3 --kernel-trace -d $TMPDIR/tr1 -o t -- python $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-visual --no-front-end --no-y32 > $O/bench_under_trace.json 2> $O/bench_under_trace.err
 python $R/tools/rocpd_timeline.py /tmp/tr1/t_results.db $O/timeline.csv 700 > /dev/null
 python - <<PY
 import csv
