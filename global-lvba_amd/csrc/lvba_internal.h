@@ -74,6 +74,9 @@ struct VisDev {
     // used -- camsum [12 M] = diag(Jc^T Jc) | Jc^T r (LM diagonal, gradient max), colsum [6 M] (Jacobi scaling)
     int32_t dist, count_cams;      // dist: 1 when sharded; count_cams: this rank counts the (replicated) cameras in the step norms
     double *camsum, *colsum;
+    // robust losses (visual_loss.h), [0] reprojection blocks, [1] plane blocks; robust = 0: both TRIVIAL, the ROBUST=false kernels run
+    int32_t robust, loss_kind[2];
+    double loss_scale[2];
 };
 
 
@@ -192,6 +195,7 @@ void vis_launch_colnorm_finish(const VisDev &d, hipStream_t s);    //          (
 void vis_launch_cam_finish(const VisDev &d, double radius, double min_diag, double max_diag, double *Hblk, const double *qc, unsigned long long *gmax,
                            hipStream_t s);                         // sharded, after the all-reduces: LM diagonal, gradient max
 void vis_launch_gather_uv(const VisDev &d, double *uv_cm, hipStream_t s);
+void vis_launch_residual_sq(const VisDev &d, const double *qc, const double *tc, const double *Xp, double *out, hipStream_t s); // [O + Ta]
 void vis_launch_reduced_system(const VisDev &d, const PairDev &pd, const double *qc, const double *tc, const double *Xp, double radius, double min_diag, double max_diag, double *Hblk,
                                int64_t hblk_doubles, double *g, unsigned long long *gmax, bool zero_first, hipStream_t s);
 void vis_launch_step_and_trial(const VisDev &d, const double *step_c, const double *qc, const double *tc, const double *Xp, double *qc2,

@@ -5,6 +5,8 @@
 // Jacobi scaling fixed at iteration 0, LM diagonal sqrt(clamp(diag J^T J)/radius),
 // parameter/function tolerance checks before the accept test, radius /= max(1/3, 1-(2 rho-1)^3) on success and
 // /= 2,4,8.. on failure.  Host logic only; arithmetic runs in visual_kernels.hip, balm_pair_kernel and ldlt.hip.
+// Robust losses (lvba_visual_set_loss) follow Ceres 2.1's ResidualBlock::Evaluate + Corrector, restated in visual_loss.h: a
+// block contributes 1/2 rho(s) to every cost this driver compares, and (r~, J~) to everything built from the linearisation.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -27,6 +29,10 @@ struct lvba_visual_s {
     lvba::hvec<int64_t> act;      // active landmark -> caller track index
     lvba::hvec<int64_t> h_off;    // CSR of the active landmarks (host, kept until finalize)
     lvba::hvec<int32_t> h_cam;    // caller camera index per kept observation
+    lvba::hvec<int64_t> obs_src;  // caller observation index (relative to obs_off[0]) per kept observation
+    int64_t O_all = 0;            // caller observations, kept or not
+    int32_t loss_kind[2] = {0, 0}; // [0] reprojection, [1] plane: LVBA_LOSS_*; scale 0 on TRIVIAL
+    double loss_scale[2] = {0.0, 0.0};
     bool finalized = false;
     double intr[8] = {}, sig_px = 0.5, sig_pl = 0.01;
     // device
@@ -57,6 +63,8 @@ struct lvba_visual_s {
         d.csc_off = bs.d_csc_off; d.csc_f = bs.d_csc_f; d.group_of_pos = bs.d_group_of_pos; d.pos_of = bs.d_pos_of;
         d.Y = bs.d_Y; d.part = d_part;
         d.dist = bs.distributed() ? 1 : 0; d.count_cams = bs.rank == 0 ? 1 : 0; d.camsum = d_camsum; d.colsum = d_colsum;
+        d.robust = (loss_kind[0] != LVBA_LOSS_TRIVIAL || loss_kind[1] != LVBA_LOSS_TRIVIAL) ? 1 : 0;
+        for (int f = 0; f < 2; ++f) { d.loss_kind[f] = loss_kind[f]; d.loss_scale[f] = loss_scale[f]; }
         return d;
     }
 };
@@ -114,6 +122,7 @@ extern "C" int32_t lvba_visual_create(int32_t n_cams, int64_t n_tracks, const in
         for (int64_t o = obs_off[i] - base; o < obs_off[i + 1] - base; ++o) {
             if (obs_cam[o] < 0 || obs_cam[o] >= n_cams) { delete h; return fail(LVBA_ERR_ARG, "obs_cam[%lld] = %d out of range", (long long)o, obs_cam[o]); }
             h->h_cam.push_back(obs_cam[o]);
+            h->obs_src.push_back(o);
             uv.push_back(obs_uv[2 * o]);
             uv.push_back(obs_uv[2 * o + 1]);
         }
@@ -123,6 +132,7 @@ extern "C" int32_t lvba_visual_create(int32_t n_cams, int64_t n_tracks, const in
     }
     h->Ta = (int64_t)h->act.size();
     h->O = (int64_t)h->h_cam.size();
+    h->O_all = Oall;
     auto bail = [&](int32_t rc) { lvba_visual_destroy(h); return rc; };
 #define CTRY(expr) do { int32_t rc_ = (expr); if (rc_ != LVBA_OK) return bail(rc_); } while (0)
 #define CHIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return bail(fail(e_ == hipErrorOutOfMemory ? LVBA_ERR_NOMEM : LVBA_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_))); } while (0)
@@ -253,6 +263,54 @@ static int32_t allreduce_scalars(lvba_visual_s *h, int first, int count)
     return bs_allreduce(h->bs, h->d_scal + first, (size_t)count);
 }
 
+// Sharded handles: every rank must use the same losses.  One MAX all-reduce of (kinds, scale bits) and their negations: the
+// maxima of v and of -v agree with every rank's own v only when all ranks hold the same v, and every rank sees the same maxima,
+// so all of them fail together (nothing diverges, nothing waits).  Run at every sharded cost / linearize / refine call: the call
+// is collective anyway, and a check only "after a change" would leave a rank that changed nothing out of the all-reduce.
+static int32_t check_loss_agreement(lvba_visual_s *h)
+{
+    BlockSys &bs = h->bs;
+    if (!bs.distributed()) return LVBA_OK;
+    int64_t v[8];
+    for (int f = 0; f < 2; ++f) {
+        int64_t bits;
+        memcpy(&bits, &h->loss_scale[f], sizeof bits); // scale >= 0: bits < 2^63, their negation does not overflow
+        v[f] = h->loss_kind[f]; v[2 + f] = bits;
+    }
+    for (int e = 0; e < 4; ++e) v[4 + e] = -v[e];
+    DevBuf buf(bs.stream);
+    HIPCHK(buf.alloc(sizeof v));
+    HIPCHK(hipMemcpyAsync(buf.p, v, sizeof v, hipMemcpyHostToDevice, bs.stream));
+    TRY(bs_comm_allreduce(bs, buf.p, 8, ncclInt64, ncclMax));
+    int64_t m[8];
+    HIPCHK(hipMemcpyAsync(m, buf.p, sizeof m, hipMemcpyDeviceToHost, bs.stream));
+    HIPCHK(hipStreamSynchronize(bs.stream));
+    for (int e = 0; e < 4; ++e)
+        if (m[e] != -m[4 + e]) return fail(LVBA_ERR_ARG, "the ranks of a sharded visual handle set different losses");
+    return LVBA_OK;
+}
+
+static bool loss_ok(const lvba_loss *l)
+{
+    if (!l || l->kind == LVBA_LOSS_TRIVIAL) return true;
+    if (l->kind < LVBA_LOSS_TRIVIAL || l->kind > LVBA_LOSS_TUKEY) return false;
+    return isfinite(l->scale) && l->scale > 0.0;
+}
+
+extern "C" int32_t lvba_visual_set_loss(lvba_visual_t h, const lvba_loss *reproj, const lvba_loss *plane)
+{
+    if (!h) return fail(LVBA_ERR_ARG, "NULL handle");
+    if (!loss_ok(reproj)) return fail(LVBA_ERR_ARG, "reprojection loss: unknown kind %d or scale not finite and > 0", reproj->kind);
+    if (!loss_ok(plane)) return fail(LVBA_ERR_ARG, "plane loss: unknown kind %d or scale not finite and > 0", plane->kind);
+    const lvba_loss *ls[2] = {reproj, plane};
+    for (int f = 0; f < 2; ++f) {
+        const bool trivial = !ls[f] || ls[f]->kind == LVBA_LOSS_TRIVIAL;
+        h->loss_kind[f] = trivial ? LVBA_LOSS_TRIVIAL : ls[f]->kind;
+        h->loss_scale[f] = trivial ? 0.0 : ls[f]->scale;
+    }
+    return LVBA_OK;
+}
+
 extern "C" int32_t lvba_visual_dist_init(lvba_visual_t h, int32_t n_ranks, int32_t rank, const char uid[128])
 {
     if (!h || !uid) return fail(LVBA_ERR_ARG, "NULL argument");
@@ -273,6 +331,7 @@ extern "C" int32_t lvba_visual_cost(lvba_visual_t h, const double *q, const doub
     TRY(finalize(h));
     BlockSys &bs = h->bs;
     HIPCHK(hipSetDevice(bs.device));
+    TRY(check_loss_agreement(h));
     TRY(import_state(h, q, t, X));
     vis_launch_residuals(h->dev(), false, h->d_q, h->d_t, h->d_X, h->d_blkpart, h->d_scal, bs.stream);
     TRY(allreduce_scalars(h, 0, 1));
@@ -294,6 +353,31 @@ extern "C" int32_t lvba_visual_info(lvba_visual_t h, lvba_balm_info_t *info)
     return LVBA_OK;
 }
 
+extern "C" int32_t lvba_visual_residual_sq(lvba_visual_t h, const double *q, const double *t, const double *X, double *obs_sq,
+                                           double *plane_sq)
+{
+    if (!h || !q || !t || !X || !obs_sq || !plane_sq) return fail(LVBA_ERR_ARG, "NULL argument");
+    if (!h->finalized && h->bs.distributed()) // finalize is collective there; this call is not
+        return fail(LVBA_ERR_STATE, "residual_sq on a sharded handle must follow its first cost / linearize / refine call");
+    TRY(finalize(h));
+    BlockSys &bs = h->bs;
+    HIPCHK(hipSetDevice(bs.device));
+    TRY(import_state(h, q, t, X));
+    const int64_t n = h->O + h->Ta;
+    lvba::hvec<double> hs((size_t)std::max<int64_t>(1, n));
+    DevBuf ds(bs.stream);
+    HIPCHK(ds.alloc((size_t)std::max<int64_t>(1, n) * sizeof(double)));
+    vis_launch_residual_sq(h->dev(), h->d_q, h->d_t, h->d_X, ds.as<double>(), bs.stream);
+    if (n) HIPCHK(hipMemcpyAsync(hs.data(), ds.as<double>(), (size_t)n * sizeof(double), hipMemcpyDeviceToHost, bs.stream));
+    HIPCHK(hipStreamSynchronize(bs.stream));
+    HIPCHK(hipGetLastError());
+    for (int64_t o = 0; o < h->O_all; ++o) obs_sq[o] = NAN;     // observations of inactive landmarks
+    for (int64_t i = 0; i < h->T; ++i) plane_sq[i] = NAN;
+    for (int64_t o = 0; o < h->O; ++o) obs_sq[h->obs_src[o]] = hs[o];
+    for (int64_t i = 0; i < h->Ta; ++i) plane_sq[h->act[i]] = hs[h->O + i];
+    return LVBA_OK;
+}
+
 extern "C" int32_t lvba_visual_linearize(lvba_visual_t h, const double *q, const double *t, const double *X, double radius,
                                          double *S, double *rhs, double *cost)
 {
@@ -302,6 +386,7 @@ extern "C" int32_t lvba_visual_linearize(lvba_visual_t h, const double *q, const
     TRY(finalize(h));
     BlockSys &bs = h->bs;
     HIPCHK(hipSetDevice(bs.device));
+    TRY(check_loss_agreement(h));
     TRY(import_state(h, q, t, X));
     lvba_visual_opts o;
     lvba_visual_default_opts(&o);
@@ -336,6 +421,7 @@ extern "C" int32_t lvba_visual_refine(lvba_visual_t h, double *q, double *t, dou
     TRY(finalize(h));
     BlockSys &bs = h->bs;
     HIPCHK(hipSetDevice(bs.device));
+    TRY(check_loss_agreement(h));
     lvba_visual_opts o;
     if (opts) o = *opts; else lvba_visual_default_opts(&o);
     auto wall_us = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };

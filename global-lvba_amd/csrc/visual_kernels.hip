@@ -15,12 +15,17 @@
 //   vis_back_kernel       lane = landmark : landmark step by back-substitution + model cost change
 //   vis_apply_kernel      candidate point x (+) step on the manifold, step / parameter norms
 // Camera order everywhere is the solver's (RCM) order; camera `fixed_cam` is constant (zero Jacobian columns).
+// Robust losses (lvba_visual_set_loss): the kernels that evaluate a residual block are templated on ROBUST.  ROBUST = false (both
+// families TRIVIAL) is the plain 1/2 sum r^2 code; ROBUST = true replaces a block's r^2 by rho(s) in the cost and scales its
+// residual and Jacobian by sqrt(rho'(s)) (Ceres' Corrector, visual_loss.h) right after reproj_eval / plane_eval, so everything
+// downstream (Jacobi scaling, LM diagonal, Schur complement, pair pass, LDL^T, model cost change) sees (r~, J~) unchanged.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
 #include "lvba_internal.h"
 #include "visual_math.h"
+#include "visual_loss.h"
 
 namespace lvba {
 
@@ -40,6 +45,16 @@ __device__ __forceinline__ double v_block_sum(double x, double *red) // 256 thre
     return t;
 }
 
+// Corrector of one residual block with squared norm s (family f: 0 reprojection, 1 plane): returns sqrt(rho'(s)), rho(s) -> *rho0.
+// The kind is a kernel argument: the branch is uniform over the wavefront.
+__device__ __forceinline__ double v_loss_weight(const VisDev &d, int f, double s, double *rho0)
+{
+    double rho[3];
+    loss_eval(d.loss_kind[f], d.loss_scale[f], s, rho);
+    if (rho0) *rho0 = rho[0];
+    return sqrt(rho[1]);
+}
+
 // sum over the four lanes of a DPP quad; every lane of the quad gets the total (quad_perm [1,0,3,2], then [2,3,0,1])
 __device__ __forceinline__ double v_quad_sum(double x)
 {
@@ -55,8 +70,9 @@ __device__ __forceinline__ double v_quad_sum(double x)
     return x;
 }
 
-// residuals at (qc, tc, Xp); threads [0,O) observations, [O, O+Ta) plane priors.  part[blockIdx] = sum r^2.
-template <bool JAC>
+// residuals at (qc, tc, Xp); threads [0,O) observations, [O, O+Ta) plane priors.  part[blockIdx] = sum r^2 (ROBUST: sum rho(s),
+// and with JAC the corrected r~, J~ are stored).
+template <bool JAC, bool ROBUST>
 __global__ __launch_bounds__(256) void vis_residual_kernel(VisDev d, const double *__restrict__ qc, const double *__restrict__ tc,
                                                            const double *__restrict__ Xp, double *__restrict__ part)
 {
@@ -72,6 +88,18 @@ __global__ __launch_bounds__(256) void vis_residual_kernel(VisDev d, const doubl
 #pragma unroll
         for (int e = 0; e < 3; ++e) { t[e] = tc[3 * (int64_t)cam + e]; X[e] = Xp[3 * i + e]; }
         reproj_eval<JAC>(q, t, X, d.uv[2 * gid], d.uv[2 * gid + 1], d.intr, d.inv_sig_px, r, Jc, Jp);
+        if (ROBUST) {
+            double rho0;
+            const double w = v_loss_weight(d, 0, r[0] * r[0] + r[1] * r[1], &rho0);
+            ss = rho0;
+            if (JAC) {
+                r[0] *= w; r[1] *= w;
+#pragma unroll
+                for (int e = 0; e < 12; ++e) Jc[e] *= w;
+#pragma unroll
+                for (int e = 0; e < 6; ++e) Jp[e] *= w;
+            }
+        }
         if (JAC) {
             // r, Jc, Jp describe the linearisation point: a cost-only evaluation (a trial point, which may be rejected) must not
             // touch them -- the next iteration linearises at the SAME point with a smaller radius
@@ -83,7 +111,7 @@ __global__ __launch_bounds__(256) void vis_residual_kernel(VisDev d, const doubl
 #pragma unroll
             for (int e = 0; e < 6; ++e) d.Jp[6 * gid + e] = Jp[e];
         }
-        ss = r[0] * r[0] + r[1] * r[1];
+        if (!ROBUST) ss = r[0] * r[0] + r[1] * r[1];
     } else if (gid < d.O + d.Ta) {
         const int64_t i = gid - d.O;
         double X[3], pl[4], J[3];
@@ -91,13 +119,23 @@ __global__ __launch_bounds__(256) void vis_residual_kernel(VisDev d, const doubl
         for (int e = 0; e < 3; ++e) X[e] = Xp[3 * i + e];
 #pragma unroll
         for (int e = 0; e < 4; ++e) pl[e] = d.plane[4 * i + e];
-        const double rp = plane_eval(X, pl, d.inv_sig_pl, JAC ? J : nullptr);
+        double rp = plane_eval(X, pl, d.inv_sig_pl, JAC ? J : nullptr);
+        if (ROBUST) {
+            double rho0;
+            const double w = v_loss_weight(d, 1, rp * rp, &rho0);
+            ss = rho0;
+            if (JAC) {
+                rp *= w;
+#pragma unroll
+                for (int e = 0; e < 3; ++e) J[e] *= w;
+            }
+        }
         if (JAC) {
             d.rpl[i] = rp;
 #pragma unroll
             for (int e = 0; e < 3; ++e) d.Jpl[3 * i + e] = J[e];
         }
-        ss = rp * rp;
+        if (!ROBUST) ss = rp * rp;
     }
     const double tot = v_block_sum(ss, red);
     if (threadIdx.x == 0) part[blockIdx.x] = tot;
@@ -162,6 +200,7 @@ __global__ void vis_colnorm_cam_finish_kernel(VisDev d)
 // the scaled variables, LM diagonal D^2 = clamp(diag C)/radius, Cholesky of C + D^2, z = L^-1 g.  gmax: max |unscaled gradient
 // entry| (bit pattern of a non-negative double).  (One lane per landmark left 125 k lanes walking four dependent gathers each:
 // 31 us of latency for 12 MB.)
+template <bool ROBUST>
 __global__ __launch_bounds__(256) void vis_point_kernel(VisDev d, const double *__restrict__ qc, const double *__restrict__ tc,
                                                         const double *__restrict__ Xp, double radius, double min_diag, double max_diag,
                                                         unsigned long long *gmax)
@@ -182,7 +221,11 @@ __global__ __launch_bounds__(256) void vis_point_kernel(VisDev d, const double *
             double pl[4], Jl[3];
 #pragma unroll
             for (int e = 0; e < 4; ++e) pl[e] = d.plane[4 * i + e];
-            const double rp = plane_eval(X, pl, d.inv_sig_pl, Jl);
+            double rp = plane_eval(X, pl, d.inv_sig_pl, Jl);
+            if (ROBUST) {
+                const double w = v_loss_weight(d, 1, rp * rp, nullptr);
+                rp *= w; Jl[0] *= w; Jl[1] *= w; Jl[2] *= w;
+            }
             const double j[3] = {Jl[0] * sp[0], Jl[1] * sp[1], Jl[2] * sp[2]};
             C[0] += j[0] * j[0]; C[1] += j[1] * j[0]; C[2] += j[1] * j[1]; C[3] += j[2] * j[0]; C[4] += j[2] * j[1]; C[5] += j[2] * j[2];
             g[0] += j[0] * rp; g[1] += j[1] * rp; g[2] += j[2] * rp;
@@ -195,6 +238,12 @@ __global__ __launch_bounds__(256) void vis_point_kernel(VisDev d, const double *
             const double2 uv = *reinterpret_cast<const double2 *>(d.uv + 2 * o);
             double rr[2], Jc[12], P[6];
             reproj_eval<true>(q, t, X, uv.x, uv.y, d.intr, d.inv_sig_px, rr, Jc, P);
+            if (ROBUST) {
+                const double w = v_loss_weight(d, 0, rr[0] * rr[0] + rr[1] * rr[1], nullptr);
+                rr[0] *= w; rr[1] *= w;
+#pragma unroll
+                for (int e = 0; e < 6; ++e) P[e] *= w;
+            }
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
                 const double j[3] = {P[3 * k] * sp[0], P[3 * k + 1] * sp[1], P[3 * k + 2] * sp[2]};
@@ -233,6 +282,8 @@ __global__ __launch_bounds__(256) void vis_point_kernel(VisDev d, const double *
 // workgroup (I, s): slice s of camera I's observations in camera-major order.  Per observation Y = (Jc^T Jp) L^-T
 // (stored for the pair pass and the back-substitution); per camera the sums of
 //   D = Jc^T Jc - Y Y^T (lower 21) | reduced rhs Jc^T r - Y z (6) | diag(Jc^T Jc) (6) | Jc^T r (6)   -> part[.][40]
+// (ROBUST: of the corrected r~, Jc~, Jp~; the weight is applied before the Jacobi scaling, while Y and its operands are not live yet)
+template <bool ROBUST>
 __global__ __launch_bounds__(256) void vis_cam_kernel(VisDev d, const double *__restrict__ qc, const double *__restrict__ tc,
                                                       const double *__restrict__ Xp, int wave_units)
 {
@@ -269,6 +320,14 @@ __global__ __launch_bounds__(256) void vis_cam_kernel(VisDev d, const double *__
             const double2 uv = *reinterpret_cast<const double2 *>(d.uv_cm + 2 * t);
             const double X[3] = {Xp[3 * i], Xp[3 * i + 1], Xp[3 * i + 2]};
             reproj_eval<true>(qI, tI, X, uv.x, uv.y, d.intr, d.inv_sig_px, rr, J, P);
+            if (ROBUST) {
+                const double w = v_loss_weight(d, 0, rr[0] * rr[0] + rr[1] * rr[1], nullptr);
+                rr[0] *= w; rr[1] *= w;
+#pragma unroll
+                for (int e = 0; e < 12; ++e) J[e] *= w;
+#pragma unroll
+                for (int e = 0; e < 6; ++e) P[e] *= w;
+            }
             const double sp[3] = {d.sc_pt[3 * i], d.sc_pt[3 * i + 1], d.sc_pt[3 * i + 2]};
 #pragma unroll
             for (int e = 0; e < 12; ++e) J[e] = fixed ? 0.0 : J[e] * sc[e % 6];
@@ -403,6 +462,8 @@ __global__ void vis_cam_finish_kernel(VisDev d, double radius, double min_diag, 
 
 // four lanes (one DPP quad) per landmark, as in vis_point_kernel: step_p = -L^-T (z + sum_obs Y^T step_c), and the model cost
 // change -sum_rows m (r + m/2), m = J step (scaled variables).  part[blockIdx] = partial of the model cost change.
+// ROBUST: of m~ = sqrt(rho') m and r~ = sqrt(rho') r.
+template <bool ROBUST>
 __global__ __launch_bounds__(256) void vis_back_kernel(VisDev d, const double *__restrict__ step_c, const double *__restrict__ qc,
                                                        const double *__restrict__ tc, const double *__restrict__ Xp, double *__restrict__ part)
 {
@@ -439,8 +500,12 @@ __global__ __launch_bounds__(256) void vis_back_kernel(VisDev d, const double *_
             double pl[4], Jl[3];
 #pragma unroll
             for (int e = 0; e < 4; ++e) pl[e] = d.plane[4 * i + e];
-            const double rp = plane_eval(X, pl, d.inv_sig_pl, Jl);
-            const double m = Jl[0] * sp[0] * st[0] + Jl[1] * sp[1] * st[1] + Jl[2] * sp[2] * st[2];
+            double rp = plane_eval(X, pl, d.inv_sig_pl, Jl);
+            double m = Jl[0] * sp[0] * st[0] + Jl[1] * sp[1] * st[1] + Jl[2] * sp[2] * st[2];
+            if (ROBUST) {
+                const double w = v_loss_weight(d, 1, rp * rp, nullptr);
+                rp *= w; m *= w;
+            }
             mc -= m * (rp + 0.5 * m);
         }
         for (int64_t o = o0; o < o1; o += 4) {
@@ -455,6 +520,8 @@ __global__ __launch_bounds__(256) void vis_back_kernel(VisDev d, const double *_
             const double2 uv = *reinterpret_cast<const double2 *>(d.uv + 2 * o);
             double rr[2], J[12], P[6];
             reproj_eval<true>(q, t, X, uv.x, uv.y, d.intr, d.inv_sig_px, rr, J, P);
+            double wl = 1.0;
+            if (ROBUST) wl = v_loss_weight(d, 0, rr[0] * rr[0] + rr[1] * rr[1], nullptr);
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
                 double m = 0.0;
@@ -462,12 +529,40 @@ __global__ __launch_bounds__(256) void vis_back_kernel(VisDev d, const double *_
                 for (int e = 0; e < 6; ++e) m += J[6 * k + e] * w[e];
 #pragma unroll
                 for (int e = 0; e < 3; ++e) m += P[3 * k + e] * sp[e] * st[e];
+                if (ROBUST) { m *= wl; rr[k] *= wl; }
                 mc -= m * (rr[k] + 0.5 * m);
             }
         }
     }
     const double tot = v_block_sum(mc, red);
     if (threadIdx.x == 0) part[blockIdx.x] = tot;
+}
+
+// squared norms s of the residual blocks at (qc, tc, Xp), before any loss: out[0,O) observations, out[O, O+Ta) plane priors
+__global__ __launch_bounds__(256) void vis_residual_sq_kernel(VisDev d, const double *__restrict__ qc, const double *__restrict__ tc,
+                                                              const double *__restrict__ Xp, double *__restrict__ out)
+{
+    const int64_t gid = blockIdx.x * (int64_t)256 + threadIdx.x;
+    if (gid < d.O) {
+        const int cam = d.cam[gid];
+        const int64_t i = d.track_of_obs[gid];
+        double q[4], t[3], X[3], r[2];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) q[e] = qc[4 * (int64_t)cam + e];
+#pragma unroll
+        for (int e = 0; e < 3; ++e) { t[e] = tc[3 * (int64_t)cam + e]; X[e] = Xp[3 * i + e]; }
+        reproj_eval<false>(q, t, X, d.uv[2 * gid], d.uv[2 * gid + 1], d.intr, d.inv_sig_px, r, nullptr, nullptr);
+        out[gid] = r[0] * r[0] + r[1] * r[1];
+    } else if (gid < d.O + d.Ta) {
+        const int64_t i = gid - d.O;
+        double X[3], pl[4];
+#pragma unroll
+        for (int e = 0; e < 3; ++e) X[e] = Xp[3 * i + e];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) pl[e] = d.plane[4 * i + e];
+        const double rp = plane_eval(X, pl, d.inv_sig_pl, nullptr);
+        out[gid] = rp * rp;
+    }
 }
 
 // candidate = x (+) step (unscaled): threads [0,M) cameras, [M, M+Ta) landmarks.  part[2*blk] = |cand - x|^2,
@@ -598,8 +693,11 @@ void vis_launch_residuals(const VisDev &d, bool jac, const double *qc, const dou
                           double *cost_out, hipStream_t s)
 {
     const unsigned nb = nblk(d.O + d.Ta, 256);
-    if (jac) hipLaunchKernelGGL(vis_residual_kernel<true>, dim3(nb), dim3(256), 0, s, d, qc, tc, Xp, part);
-    else hipLaunchKernelGGL(vis_residual_kernel<false>, dim3(nb), dim3(256), 0, s, d, qc, tc, Xp, part);
+    if (d.robust) {
+        if (jac) hipLaunchKernelGGL((vis_residual_kernel<true, true>), dim3(nb), dim3(256), 0, s, d, qc, tc, Xp, part);
+        else hipLaunchKernelGGL((vis_residual_kernel<false, true>), dim3(nb), dim3(256), 0, s, d, qc, tc, Xp, part);
+    } else if (jac) hipLaunchKernelGGL((vis_residual_kernel<true, false>), dim3(nb), dim3(256), 0, s, d, qc, tc, Xp, part);
+    else hipLaunchKernelGGL((vis_residual_kernel<false, false>), dim3(nb), dim3(256), 0, s, d, qc, tc, Xp, part);
     if (cost_out) hipLaunchKernelGGL(vis_reduce_kernel, dim3(1), dim3(1024), 0, s, part, (int64_t)nb, 1, cost_out);
 }
 
@@ -610,9 +708,11 @@ void vis_launch_step_and_trial(const VisDev &d, const double *step_c, const doub
 {
     const unsigned nb_back = vis_back_grid(d.Ta), nb_apply = nblk(d.M + d.Ta, 256), nb_res = nblk(d.O + d.Ta, 256);
     double *pa = part + nb_back, *pr = pa + 2 * (int64_t)nb_apply;
-    hipLaunchKernelGGL(vis_back_kernel, dim3(nb_back), dim3(256), 0, s, d, step_c, qc, tc, Xp, part);
+    if (d.robust) hipLaunchKernelGGL(vis_back_kernel<true>, dim3(nb_back), dim3(256), 0, s, d, step_c, qc, tc, Xp, part);
+    else hipLaunchKernelGGL(vis_back_kernel<false>, dim3(nb_back), dim3(256), 0, s, d, step_c, qc, tc, Xp, part);
     hipLaunchKernelGGL(vis_apply_kernel, dim3(nb_apply), dim3(256), 0, s, d, step_c, qc, tc, Xp, qc2, tc2, Xp2, pa);
-    hipLaunchKernelGGL(vis_residual_kernel<false>, dim3(nb_res), dim3(256), 0, s, d, qc2, tc2, Xp2, pr);
+    if (d.robust) hipLaunchKernelGGL((vis_residual_kernel<false, true>), dim3(nb_res), dim3(256), 0, s, d, qc2, tc2, Xp2, pr);
+    else hipLaunchKernelGGL((vis_residual_kernel<false, false>), dim3(nb_res), dim3(256), 0, s, d, qc2, tc2, Xp2, pr);
     hipLaunchKernelGGL(vis_finish_kernel, dim3(1), dim3(1024), 0, s, part, (int64_t)nb_back, (int64_t)nb_apply, (int64_t)nb_res, scal,
                        gmax, status, host_pin);
 }
@@ -638,6 +738,11 @@ void vis_launch_cam_finish(const VisDev &d, double radius, double min_diag, doub
     hipLaunchKernelGGL(vis_cam_finish_kernel, dim3(nblk(d.M, 64)), dim3(64), 0, s, d, radius, min_diag, max_diag, Hblk, qc, gmax);
 }
 
+void vis_launch_residual_sq(const VisDev &d, const double *qc, const double *tc, const double *Xp, double *out, hipStream_t s)
+{
+    if (d.O + d.Ta > 0) hipLaunchKernelGGL(vis_residual_sq_kernel, dim3(nblk(d.O + d.Ta, 256)), dim3(256), 0, s, d, qc, tc, Xp, out);
+}
+
 void vis_launch_gather_uv(const VisDev &d, double *uv_cm, hipStream_t s)
 {
     if (d.O > 0) hipLaunchKernelGGL(vis_gather_uv_kernel, dim3(nblk(d.O, 256)), dim3(256), 0, s, d, uv_cm);
@@ -648,12 +753,15 @@ void vis_launch_reduced_system(const VisDev &d, const PairDev &pd, const double 
 {
     if (zero_first) hipMemsetAsync(Hblk, 0, (size_t)hblk_doubles * sizeof(double), s);
     hipMemsetAsync(gmax, 0, sizeof(unsigned long long), s);
-    hipLaunchKernelGGL(vis_point_kernel, dim3(vis_quad_grid(d.Ta)), dim3(256), 0, s, d, qc, tc, Xp, radius, min_diag, max_diag, gmax);
+    if (d.robust) hipLaunchKernelGGL(vis_point_kernel<true>, dim3(vis_quad_grid(d.Ta)), dim3(256), 0, s, d, qc, tc, Xp, radius, min_diag, max_diag, gmax);
+    else hipLaunchKernelGGL(vis_point_kernel<false>, dim3(vis_quad_grid(d.Ta)), dim3(256), 0, s, d, qc, tc, Xp, radius, min_diag, max_diag, gmax);
     // one wavefront per (camera, slice) while a slice is short: its 39 sums cost one 64-lane reduction per WAVEFRONT, which at ~250
     // observations per camera was most of the kernel with four wavefronts of one observation per lane each
     const int64_t per_slice = d.O / ((int64_t)d.M * d.S > 0 ? (int64_t)d.M * d.S : 1);
-    if (per_slice <= 1024) hipLaunchKernelGGL(vis_cam_kernel, dim3((unsigned)((d.M * d.S + 3) / 4)), dim3(256), 0, s, d, qc, tc, Xp, 1);
-    else hipLaunchKernelGGL(vis_cam_kernel, dim3((unsigned)(d.M * d.S)), dim3(256), 0, s, d, qc, tc, Xp, 0);
+    const int wave_units = per_slice <= 1024 ? 1 : 0;
+    const unsigned ncam_wg = (unsigned)(wave_units ? (d.M * d.S + 3) / 4 : d.M * d.S);
+    if (d.robust) hipLaunchKernelGGL(vis_cam_kernel<true>, dim3(ncam_wg), dim3(256), 0, s, d, qc, tc, Xp, wave_units);
+    else hipLaunchKernelGGL(vis_cam_kernel<false>, dim3(ncam_wg), dim3(256), 0, s, d, qc, tc, Xp, wave_units);
     hipLaunchKernelGGL(vis_cam_reduce_kernel, dim3(nblk(d.M, 64)), dim3(64), 0, s, d, radius, min_diag, max_diag, Hblk, g, qc, gmax);
     launch_pairs(pd, Hblk, s);
 }
@@ -662,7 +770,8 @@ void vis_launch_back(const VisDev &d, const double *step_c, const double *qc, co
                      double *model_out, hipStream_t s)
 {
     const unsigned nb = vis_back_grid(d.Ta);
-    hipLaunchKernelGGL(vis_back_kernel, dim3(nb), dim3(256), 0, s, d, step_c, qc, tc, Xp, part);
+    if (d.robust) hipLaunchKernelGGL(vis_back_kernel<true>, dim3(nb), dim3(256), 0, s, d, step_c, qc, tc, Xp, part);
+    else hipLaunchKernelGGL(vis_back_kernel<false>, dim3(nb), dim3(256), 0, s, d, step_c, qc, tc, Xp, part);
     hipLaunchKernelGGL(vis_reduce_kernel, dim3(1), dim3(1024), 0, s, part, (int64_t)nb, 1, model_out);
 }
 

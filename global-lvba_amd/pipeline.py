@@ -25,7 +25,11 @@ DEFAULTS = dict(                                   # config/config.yaml of the r
     window_enable=True, window_size=20, anchor_leaf=0.01, use_rel=True,
     stage1_enable=True, stage_voxel_size=(1.0, 0.5), stage_eigen_ratio=((0.2,) * 4, (0.08,) * 4),
     obser_thr=3, min_view_angle_deg=8.0, reproj_mean_thr_px=3.0, depth_half_window_s=0.5, depth_voxel=0.5,
-    sigma_px=0.5, sigma_plane=0.01)
+    sigma_px=0.5, sigma_plane=0.01,
+    # robust losses of the visual stage: None (the reference's nullptr at src/lvba_system.cpp:1630, :1639) or a pair
+    # (reprojection, plane) of VisualProblem.set_loss arguments -- REFERENCE_HUBER is the pair the reference builds at :1585-1586
+    visual_loss=None)
+REFERENCE_HUBER = (("huber", 1.0), ("huber", 0.1))
 
 
 def _mat(T):
@@ -188,7 +192,8 @@ def run_visual_ba_with_lidar_assist(scans, x_opt, x_orig, scan_times, image_time
                                     keypoints, pairs, matches, **cfg):
     """LvbaSystem::runVisualBAWithLidarAssist (src/lvba_system.cpp:144-154) from the refined LiDAR poses to the refined
     cameras.  scans: a voxel.Scans holding the raw clouds; keypoints[i] = [n_i, 2] float pixel coordinates; pairs / matches as
-    build_tracks takes them.  Returns a dict (cameras before / after, tracks, landmarks, planes, traces)."""
+    build_tracks takes them.  cfg["visual_loss"]: see DEFAULTS.  Returns a dict (cameras before / after, tracks, landmarks, planes,
+    traces)."""
     c = dict(DEFAULTS); c.update(cfg)
     cam_new = update_camera_poses_from_lidar(x_opt, x_orig, scan_times, image_times, image_poses)      # poses_
     Rcw, tcw = camera_from_imu(cam_new, Rci, tci)                                                      # Rcw_all_optimized_
@@ -227,9 +232,10 @@ def run_visual_ba_with_lidar_assist(scans, x_opt, x_orig, scan_times, image_time
         o_cam.extend(img[sel].tolist()); o_uv.extend(uv[sel].astype(np.float64).tolist())
         o_off.append(len(o_cam))
     q0 = rot_to_quat_wxyz(Rcw)
+    loss_r, loss_p = c["visual_loss"] if c["visual_loss"] is not None else (None, None)
     (q, t, Xn), trace, term, rc, valid = V.optimize_camera_poses(
         q0, tcw, X[tr], np.asarray(o_off, np.int64), np.asarray(o_cam, np.int32), np.asarray(o_uv, np.float64).reshape(-1, 2),
-        plane[:, :3], plane[:, 3], intr, c["sigma_px"], c["sigma_plane"])
+        plane[:, :3], plane[:, 3], intr, c["sigma_px"], c["sigma_plane"], loss_reproj=loss_r, loss_plane=loss_p)
     out.update(Rcw=quat_wxyz_to_rot(q), tcw=np.asarray(t), q=q, landmarks=np.asarray(Xn), landmarks_before=X[tr],
                landmark_valid=valid, track_ids=tr, plane=plane, plane_valid=pvalid, obs_off=np.asarray(o_off), obs_cam=np.asarray(o_cam),
                obs_uv=np.asarray(o_uv).reshape(-1, 2), trace=trace, termination=term, status=rc, mean_reproj=err[tr])
@@ -239,7 +245,8 @@ def run_visual_ba_with_lidar_assist(scans, x_opt, x_orig, scan_times, image_time
 def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, tci, intr, width, height, keypoints, pairs,
                       matches, enable_lidar_ba=True, enable_visual_ba=True, device=0, **cfg):
     """LvbaSystem::runFullPipeline (src/lvba_system.cpp:136-142) on in-memory data: clouds = body-frame [n_i, >=3] float32
-    arrays, poses [n,12] = x_buf_ (T_world<-imu), image_poses [m,12] the image poses from the odometry."""
+    arrays, poses [n,12] = x_buf_ (T_world<-imu), image_poses [m,12] the image poses from the odometry.  cfg: DEFAULTS' keys
+    (visual_loss among them)."""
     c = dict(DEFAULTS); c.update(cfg)
     x_orig = np.asarray(poses, np.float64).reshape(-1, 12).copy()
     out = dict(poses_before=x_orig)
@@ -293,7 +300,8 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
     text files images.txt / points3D.txt the reference writes (src/lvba_system.cpp:2018-2137) are saved there.  images.txt is
     the reference's, character for character (tests/test_ref_system.py); points3D.txt has the reference's format but holds
     the refined visual landmarks in white -- the reference fills it with its LiDAR map coloured from the images
-    (VisualizeOptComparison), which needs an image codec and is visualisation, outside the scope contract."""
+    (VisualizeOptComparison), which needs an image codec and is visualisation, outside the scope contract.  cfg as for
+    run_full_pipeline, e.g. visual_loss=REFERENCE_HUBER."""
     import os
     from . import dataset as D
     ds = D.load_dataset(data_path)

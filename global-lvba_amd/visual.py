@@ -33,6 +33,7 @@ class VisualProblem:
                                             plane.reshape(-1), valid, intr, float(sigma_px), float(sigma_plane), int(device),
                                             C.byref(self._h)))
         self._keep = (obs_cam, obs_uv)
+        self.n_obs = int(obs_off[-1] - obs_off[0])
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -57,6 +58,21 @@ class VisualProblem:
         out = C.c_double()
         L.check(self.lib.lvba_visual_cost(self._h, *self._state(q, t, X), C.byref(out)))
         return out.value
+
+    def set_loss(self, reproj=None, plane=None):
+        """Robust losses of the reprojection and the plane residual blocks (lvba_visual_set_loss): None (the reference's nullptr)
+        or a (kind, scale) tuple, kind one of "huber", "softlone", "cauchy", "arctan", "tukey" (or "trivial"), scale in whitened
+        residual units -- ("huber", 1.0) / ("huber", 0.1) are the reference's constants (src/lvba_system.cpp:1585-1586)."""
+        L.check(self.lib.lvba_visual_set_loss(self._h, *(loss_struct(x) for x in (reproj, plane))))
+
+    def residual_sq(self, q, t, X):
+        """Whitened squared norms s of every observation's reprojection block [O] (caller order) and of every landmark's plane
+        block [n_tracks], before any loss; NaN on landmarks without a valid plane and on their observations."""
+        q, t, X = self._state(q, t, X)
+        obs = np.empty(self.n_obs)
+        pl = np.empty(self.n_tracks)
+        L.check(self.lib.lvba_visual_residual_sq(self._h, q, t, X, obs.ctypes.data, pl.ctypes.data))
+        return obs, pl
 
     def linearize(self, q, t, X, radius=1e4):
         n = 6 * self.n_cams
@@ -105,16 +121,30 @@ class VisualProblem:
             L.TERMINATION.get(term.value, str(term.value)), rc
 
 
+def loss_struct(loss):
+    """None -> NULL (TRIVIAL); (kind, scale) -> a pointer to an lvba_loss."""
+    if loss is None:
+        return None
+    kind, scale = loss
+    k = L.LOSS_KINDS.get(str(kind).lower()) if isinstance(kind, str) else int(kind)
+    if k is None:
+        raise ValueError(f"unknown loss kind {kind!r}; one of {sorted(L.LOSS_KINDS)}")
+    return C.pointer(L.Loss(k, 0, float(scale)))
+
+
 def optimize_camera_poses(qs, ts, Xs, obs_off, obs_cam, obs_uv, plane_n, plane_d, intr, sigma_px=0.5, sigma_plane=0.01,
-                          device=0):
+                          device=0, loss_reproj=None, loss_plane=None):
     """The ceres::Problem / ceres::Solve region of LvbaSystem::optimizeCameraPoses (src/lvba_system.cpp:1571-1665).
-    A landmark has a valid plane iff its normal is finite and non-zero (has_valid_plane, :1596)."""
+    A landmark has a valid plane iff its normal is finite and non-zero (has_valid_plane, :1596).  loss_reproj / loss_plane:
+    VisualProblem.set_loss arguments (None: the reference's nullptr at :1630, :1639)."""
     plane_n = np.asarray(plane_n, np.float64).reshape(-1, 3)
     plane_d = np.asarray(plane_d, np.float64).reshape(-1)
     valid = (np.isfinite(plane_n).all(1) & np.isfinite(plane_d) & ~(np.abs(plane_n) <= 1e-6).all(1)).astype(np.uint8)
     prob = VisualProblem(len(qs), obs_off, obs_cam, obs_uv, np.concatenate([plane_n, plane_d[:, None]], 1), valid, intr,
                          sigma_px, sigma_plane, device)
     try:
+        if loss_reproj is not None or loss_plane is not None:
+            prob.set_loss(loss_reproj, loss_plane)
         return prob.refine(qs, ts, Xs) + (valid,)
     finally:
         prob.close()

@@ -476,13 +476,23 @@ void build_tracks_and_fuse(const KeypointTable &all_keypoints, const MatchTable 
 // reference's `summary.termination_type == ceres::FAILURE` early return at :1646-1649 tests).  Usage:
 //       const int term = lvba::optimize_camera_poses_hip(qs, ts, Xs, obs_off, obs_cam, obs_uv, plane_nd, valid, intr, 0.5, 0.01);
 //       if (term == LVBA_TERM_FAILURE) { std::cerr << "[optimizeCamPoses] Solver failed!\n"; return; }
-// and the write-back block at :1651-1665 runs unchanged afterwards.
+// and the write-back block at :1651-1665 runs unchanged afterwards.  loss_reproj / loss_plane: the robust losses the reference
+// builds at :1585-1586 and leaves unused (nullptr at :1630, :1639, the default here); to use them --
+//       const lvba_loss hr = lvba::loss_huber(1.0), hp = lvba::loss_huber(0.1);
+//       lvba::optimize_camera_poses_hip(qs, ts, Xs, obs_off, obs_cam, obs_uv, plane_nd, valid, intr, 0.5, 0.01, nullptr, 0, &hr, &hp);
+inline lvba_loss make_loss(int32_t kind, double a) { lvba_loss l; l.kind = kind; l.reserved = 0; l.scale = a; return l; }
+inline lvba_loss loss_huber(double a) { return make_loss(LVBA_LOSS_HUBER, a); }
+inline lvba_loss loss_softlone(double a) { return make_loss(LVBA_LOSS_SOFTLONE, a); }
+inline lvba_loss loss_cauchy(double a) { return make_loss(LVBA_LOSS_CAUCHY, a); }
+inline lvba_loss loss_arctan(double a) { return make_loss(LVBA_LOSS_ARCTAN, a); }
+inline lvba_loss loss_tukey(double a) { return make_loss(LVBA_LOSS_TUKEY, a); }
+
 template <class QVec, class TVec, class XVec>
 int32_t optimize_camera_poses_hip(QVec &qs, TVec &ts, XVec &Xs, const std::vector<int64_t> &obs_off,
                                   const std::vector<int32_t> &obs_cam, const std::vector<double> &obs_uv,
                                   const std::vector<double> &plane_nd, const std::vector<uint8_t> &valid, const double intr[8],
                                   double sigma_px, double sigma_plane, std::vector<lvba_visual_trace> *trace = nullptr,
-                                  int device = 0)
+                                  int device = 0, const lvba_loss *loss_reproj = nullptr, const lvba_loss *loss_plane = nullptr)
 {
     const int32_t M = static_cast<int32_t>(qs.size());
     const int64_t P = static_cast<int64_t>(Xs.size());
@@ -500,6 +510,11 @@ int32_t optimize_camera_poses_hip(QVec &qs, TVec &ts, XVec &Xs, const std::vecto
     if (lvba_visual_create(M, P, obs_off.data(), obs_cam.data(), obs_uv.data(), plane_nd.data(), valid.data(), intr, sigma_px,
                            sigma_plane, device, &vh) != LVBA_OK)
         throw std::runtime_error(std::string("lvba_visual_create: ") + lvba_last_error());
+    if ((loss_reproj || loss_plane) && lvba_visual_set_loss(vh, loss_reproj, loss_plane) != LVBA_OK) {
+        const std::string msg = std::string("lvba_visual_set_loss: ") + lvba_last_error();
+        lvba_visual_destroy(vh);
+        throw std::runtime_error(msg);
+    }
     lvba_visual_opts o;
     lvba_visual_default_opts(&o);                        // 50 iterations, Ceres 2.1 defaults (:1572-1576)
     std::vector<lvba_visual_trace> tr(static_cast<size_t>(o.max_iter) + 2);

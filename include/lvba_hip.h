@@ -239,7 +239,8 @@ int32_t lvba_balm_dist_init_external(lvba_balm_t h, int32_t n_ranks, int32_t ran
  *   landmark = X_w [3]; a landmark whose `valid` flag is 0 (no plane found, :1598-1603) is dropped together with
  *              its reprojection observations and is returned unchanged
  *   residuals: per observation the whitened Brown-Conrady reprojection error (2), per landmark the whitened
- *              point-to-plane distance sqrt(s^2+1e-12)/sigma (1); no loss function (:1630,1639)
+ *              point-to-plane distance sqrt(s^2+1e-12)/sigma (1); by default no loss function (:1630,1639), each
+ *              family may take a robust loss (lvba_visual_set_loss).  cost = 1/2 sum rho(s), s = |r|^2 of a block
  *   solver:    Levenberg-Marquardt trust region with Ceres 2.1 defaults restated (Jacobi scaling, LM diagonal
  *              clamp(diag)/radius, radius schedule, tolerances), landmark blocks eliminated (Schur), reduced
  *              camera system solved by the same LDL^T as the LiDAR stage.
@@ -273,7 +274,7 @@ typedef struct {
     int32_t accepted;     /* step successful (always 1 for iteration 0) */
     int32_t valid;        /* linear solve produced a finite step with positive model decrease */
     int32_t reserved;
-    double cost;          /* 1/2 sum r^2: the new cost if accepted, the rejected candidate's cost otherwise */
+    double cost;          /* 1/2 sum rho(s): the new cost if accepted, the rejected candidate's cost otherwise */
     double cost_change;
     double step_norm;
     double radius;        /* trust-region radius after this iteration's update */
@@ -305,7 +306,7 @@ int32_t lvba_visual_info(lvba_visual_t h, lvba_balm_info_t *info);
 int32_t lvba_visual_dist_init(lvba_visual_t h, int32_t n_ranks, int32_t rank, const char uid[128]);
 int32_t lvba_visual_dist_init_external(lvba_visual_t h, int32_t n_ranks, int32_t rank, lvba_allreduce_fn fn, void *ctx);
 
-/* 1/2 sum r^2 over the residuals of the active landmarks at (q [M][4], t [M][3], X [n_tracks][3]). */
+/* 1/2 sum rho(s) over the residual blocks of the active landmarks at (q [M][4], t [M][3], X [n_tracks][3]). */
 int32_t lvba_visual_cost(lvba_visual_t h, const double *q, const double *t, const double *X, double *cost);
 
 /* Linearise at the given point with trust-region radius `radius` (Jacobi scaling taken from THIS Jacobian, as at
@@ -313,6 +314,41 @@ int32_t lvba_visual_cost(lvba_visual_t h, const double *q, const double *t, cons
  * right-hand side rhs [6M] in the scaled tangent variables, caller camera order.  For tests / inspection. */
 int32_t lvba_visual_linearize(lvba_visual_t h, const double *q, const double *t, const double *X, double radius,
                               double *S, double *rhs, double *cost);
+
+/* Robust losses, Ceres 2.1 semantics (loss_function.cc, corrector.cc): a residual block with squared norm s = |f|^2
+ * contributes 1/2 rho(s) to the cost, and its residual and Jacobian enter the linearisation as sqrt(rho'(s)) f,
+ * sqrt(rho'(s)) J (every kind here has rho'' <= 0).  `scale` = a, in whitened residual units:
+ *   TRIVIAL   rho = s (default: the reference's nullptr)
+ *   HUBER     s <= a^2: s, else 2 a sqrt(s) - a^2         SOFTLONE  2 a^2 (sqrt(1 + s/a^2) - 1)
+ *   CAUCHY    a^2 log(1 + s/a^2)                          ARCTAN    a atan2(s, a)
+ *   TUKEY     s <= a^2: a^2/3 (1 - (1 - s/a^2)^3), else a^2/3
+ * The reference's own (unused) constants, :1585-1586: HUBER 1.0 on the reprojection blocks (0.5 px at sigma_px 0.5), HUBER 0.1
+ * on the plane blocks (1 mm at sigma_plane 0.01). */
+#define LVBA_LOSS_TRIVIAL 0
+#define LVBA_LOSS_HUBER 1
+#define LVBA_LOSS_SOFTLONE 2
+#define LVBA_LOSS_CAUCHY 3
+#define LVBA_LOSS_ARCTAN 4
+#define LVBA_LOSS_TUKEY 5
+typedef struct {
+    int32_t kind;         /* LVBA_LOSS_* */
+    int32_t reserved;
+    double scale;         /* a > 0, finite; ignored for TRIVIAL */
+} lvba_loss;
+
+/* Loss of the reprojection blocks (one 2-vector per observation) and of the plane blocks (one per active landmark); NULL =
+ * TRIVIAL.  Kept on the handle for every later cost / linearize / refine call.  An unknown kind, or a non-trivial kind with a
+ * scale that is not finite and > 0, returns LVBA_ERR_ARG and leaves the handle unchanged.  Sharded handles: every rank must set
+ * the same losses; each cost / linearize / refine call checks this with one small all-reduce and fails with LVBA_ERR_ARG on
+ * every rank otherwise. */
+int32_t lvba_visual_set_loss(lvba_visual_t h, const lvba_loss *reproj, const lvba_loss *plane);
+
+/* Whitened squared norms s of the residual blocks at (q, t, X), before any loss: obs_sq [O] per caller observation
+ * (O = obs_off[n_tracks] - obs_off[0], caller order), plane_sq [n_tracks] per landmark; NaN for landmarks with valid == 0 and
+ * their observations.  Which blocks a loss down-weights: s > a^2.  Rank-local on a sharded handle (its own tracks; call it
+ * after the first cost / linearize / refine call there). */
+int32_t lvba_visual_residual_sq(lvba_visual_t h, const double *q, const double *t, const double *X, double *obs_sq,
+                                double *plane_sq);
 
 /* The solve: refines q, t, X in place (quaternions re-normalised on write-back, :1651-1657). */
 int32_t lvba_visual_refine(lvba_visual_t h, double *q, double *t, double *X, const lvba_visual_opts *opts,
