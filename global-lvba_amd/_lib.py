@@ -24,6 +24,8 @@ SYMBOLS = [
     "lvba_lidar_ba_default_opts", "lvba_lidar_ba", "lvba_lidar_ba_multi", "lvba_triangulate_tracks",
     "lvba_depth_render", "lvba_depth_upload", "lvba_depth_info", "lvba_depth_download", "lvba_depth_destroy",
     "lvba_fuse_default_opts", "lvba_fuse_tracks",
+    "lvba_colorize_default_opts", "lvba_colorize_create", "lvba_colorize_add_images", "lvba_colorize_count",
+    "lvba_colorize_download", "lvba_colorize_profile", "lvba_colorize_destroy",
 ]
 
 OK, ERR_ARG, ERR_DEVICE, ERR_NOMEM, ERR_UNSUPPORTED, ERR_DIST, ERR_STATE = 0, -1, -2, -3, -4, -5, -6
@@ -93,6 +95,11 @@ class Loss(C.Structure):
 class FuseOpts(C.Structure):
     _fields_ = [("obser_thr", C.c_int32), ("reserved", C.c_int32), ("min_view_angle_deg", C.c_double),
                 ("reproj_mean_thr_px", C.c_double)]
+
+
+class ColorizeOpts(C.Structure):
+    _fields_ = [("half_window_s", C.c_double), ("leaf_size", C.c_double), ("max_batch_images", C.c_int32),
+                ("reserved", C.c_int32)]
 
 
 class VoxelOpts(C.Structure):
@@ -250,6 +257,16 @@ def load():
     lib.lvba_fuse_default_opts.restype = None
     lib.lvba_fuse_tracks.argtypes = [C.c_int32, C.c_void_p, C.c_int32, f64p, f64p, f64p, C.c_int64, i64p, C.c_void_p, C.c_void_p,
                                      C.POINTER(FuseOpts), C.c_void_p, f64p, f64p, C.c_void_p]
+    lib.lvba_colorize_default_opts.argtypes = [C.POINTER(ColorizeOpts)]
+    lib.lvba_colorize_default_opts.restype = None
+    lib.lvba_colorize_create.argtypes = [C.c_void_p, f64p, f64p, f64p, C.c_int32, C.c_int32, C.POINTER(ColorizeOpts),
+                                         C.POINTER(C.c_void_p)]
+    lib.lvba_colorize_add_images.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.lvba_colorize_count.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    lib.lvba_colorize_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.lvba_colorize_profile.argtypes = [C.c_void_p, C.c_void_p]
+    lib.lvba_colorize_destroy.argtypes = [C.c_void_p]
+    lib.lvba_colorize_destroy.restype = None
     lib.lvba_scans_info.argtypes = [H, C.POINTER(C.c_int32), C.c_void_p]
     lib.lvba_scans_download.argtypes = [H, C.c_int32, np.ctypeslib.ndpointer(np.float32, flags="C")]
     for name in SYMBOLS:

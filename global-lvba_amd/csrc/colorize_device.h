@@ -1,0 +1,115 @@
+// colorize_device.h -- the per-point rules of the LiDAR map colouriser (colorize.hip) as host/device-neutral functions, so that
+// the very code the kernels run is also compiled for the CPU (tests/colorize_check.cpp, tests/test_colorize_host.py).
+// Of the reference (src/lvba_system.cpp, LvbaSystem::VisualizeOptComparison, :1932-2144):
+//   scan window           :1974       |t_scan - t_image| <= 0.5 (the difference is rounded first: not t0 <= t <= t1)
+//   world point           :1980-1987  R p + t in double, stored as float
+//   projection            :2034-2045  projectWorldToPixel (include/utils.hpp:183-205), std::round, [0,W) x [0,H)
+//   depth buffer          :2046-2058  replace when zc + 1e-6f < zbuf, zbuf = (float)zc; pixel kept when zbuf is finite
+//   down_sampling_voxel2  include/BALM/tools.hpp:300-359 (key and squared distance to the leaf centre)
+// Files that include this one are built with -ffp-contract=off (build.py NO_CONTRACT): every expression rounds as written.
+#pragma once
+#include "tracks_device.h"
+
+namespace lvba {
+
+constexpr int COL_KEY_BIAS = 1 << 20; // leaf key components must lie in [-2^20, 2^20) (the packing of voxel_internal.h)
+
+// :1974 -- the image at t_img uses the scan at t_scan unless |t_scan - t_img| > half.  For ascending scan times the rounded
+// difference is non-decreasing, so the scans used form one contiguous range (found by col_window_range).
+LVBA_TRK_FN bool col_in_window(double t_scan, double t_img, double half) { return !(fabs(t_scan - t_img) > half); }
+// [lo, hi): the scans of t[0..n) (ascending) inside the window of t_img
+LVBA_TRK_FN void col_window_range(const double *t, int n, double t_img, double half, int &lo, int &hi)
+{
+    int a = 0, b = n; // first index with t - t_img >= -half
+    while (a < b) {
+        const int m = (a + b) >> 1;
+        if (t[m] - t_img >= -half) b = m; else a = m + 1;
+    }
+    lo = a;
+    b = n; // first index with t - t_img > half
+    while (a < b) {
+        const int m = (a + b) >> 1;
+        if (t[m] - t_img > half) b = m; else a = m + 1;
+    }
+    hi = a;
+}
+
+// :1980-1987 -- pose T = R (row-major) | t; the world point in double, stored as float
+LVBA_TRK_FN void col_world_point(const double *T, float x, float y, float z, float out[3])
+{
+    const double p0 = x, p1 = y, p2 = z;
+    out[0] = (float)(T[0] * p0 + T[1] * p1 + T[2] * p2 + T[9]);
+    out[1] = (float)(T[3] * p0 + T[4] * p1 + T[5] * p2 + T[10]);
+    out[2] = (float)(T[6] * p0 + T[7] * p1 + T[8] * p2 + T[11]);
+}
+
+// :2034-2045 -- projectWorldToPixel of the float point (widened back to double), std::round (half away from zero),
+// bounds [0, W) x [0, H).  Returns false when the reference skips the point; else the row-major pixel and the depth zc.
+LVBA_TRK_FN bool col_project(const TrkIntr &cam, const double *R, const double *t, const float pw[3], int W, int H, int64_t &pix,
+                             double &zc)
+{
+    const double X[3] = {(double)pw[0], (double)pw[1], (double)pw[2]};
+    const double X0 = R[0] * X[0] + R[1] * X[1] + R[2] * X[2] + t[0];
+    const double X1 = R[3] * X[0] + R[4] * X[1] + R[5] * X[2] + t[1];
+    const double Z = R[6] * X[0] + R[7] * X[1] + R[8] * X[2] + t[2];
+    double u, v;
+    if (!trk_project_cam(cam, X0, X1, Z, u, v)) return false; // non-finite, Z <= 1e-12
+    const double ru = round(u), rv = round(v);
+    // static_cast<int> of anything this large is undefined upstream (x86-64 gives INT_MIN, out of bounds): skip it here
+    if (!(fabs(ru) < 2.0e9 && fabs(rv) < 2.0e9)) return false;
+    const int uu = (int)ru, vv = (int)rv;
+    if (uu < 0 || uu >= W || vv < 0 || vv >= H) return false;
+    pix = (int64_t)vv * W + uu;
+    zc = Z;
+    return true;
+}
+
+// :2046-2058 -- one step of the depth buffer: the point replaces the stored one when zc + 1e-6f < zbuf (in double, zbuf
+// widened); zbuf then holds (float)zc.  Not a minimum: with the epsilon and the float store, the survivor is the end of a
+// chain of first improvements in point order.
+LVBA_TRK_FN bool col_depth_step(double zc, float &zbuf)
+{
+    const float eps = 1e-6f;
+    if (zc + eps < zbuf) {
+        zbuf = (float)zc;
+        return true;
+    }
+    return false;
+}
+// The whole walk over one pixel's points, in point order: zc_at(q) = depth of the q-th of n.  Returns true when the pixel
+// is kept (its final zbuf is finite, :2063-2067); winner = index q of the point stored last.
+template <class ZAt>
+LVBA_TRK_FN bool col_walk(int64_t n, ZAt zc_at, int64_t &winner)
+{
+    float zbuf = INFINITY;
+    winner = -1;
+    for (int64_t q = 0; q < n; ++q)
+        if (col_depth_step(zc_at(q), zbuf)) winner = q;
+    return winner >= 0 && isfinite(zbuf);
+}
+
+// down_sampling_voxel2 (tools.hpp:318-341) for a float point q and the double leaf: key = (int64)(float)(q / leaf), minus 1
+// when negative (in float); d2 = squared distance to the leaf centre, dx*dx + dy*dy + dz*dz from left to right.  Returns
+// false when a component falls outside the packable range (or q is not finite).
+LVBA_TRK_FN bool col_leaf_key(const float q[3], double leaf, int64_t k[3], double &d2)
+{
+    bool ok = true;
+    double dd = 0.0;
+    for (int j = 0; j < 3; ++j) {
+        float loc = (float)((double)q[j] / leaf);
+        if (loc < 0.f) loc -= 1.f;
+        ok = ok && (fabsf(loc) < (float)COL_KEY_BIAS);
+        k[j] = ok ? (int64_t)loc : 0;
+        const double c = ((double)k[j] + 0.5) * leaf;
+        const double d = (double)q[j] - c;
+        dd = dd + d * d;
+    }
+    d2 = dd;
+    return ok;
+}
+LVBA_TRK_FN uint64_t col_pack_key(const int64_t k[3])
+{
+    return ((uint64_t)(k[0] + COL_KEY_BIAS) << 42) | ((uint64_t)(k[1] + COL_KEY_BIAS) << 21) | (uint64_t)(k[2] + COL_KEY_BIAS);
+}
+
+} // namespace lvba

@@ -77,7 +77,7 @@ struct lvba_balm_s {
 };
 
 // ------------------------------------------------------------------------------------------ misc API
-extern "C" int32_t lvba_version(void) { return 111; }
+extern "C" int32_t lvba_version(void) { return 112; }
 extern "C" int32_t lvba_device_count(void)
 {
     int n = 0;

@@ -233,6 +233,53 @@ def write_points3d_txt(path, xyz, rgb):
             f.write(f"{i} {p[0]:.6f} {p[1]:.6f} {p[2]:.6f} {int(c[0])} {int(c[1])} {int(c[2])} 0\n")
 
 
+def pack_rgb(rgb):
+    """PCL's packed colour of a pcl::PointXYZRGB (b, g, r, a bytes in memory, a = 255 as its constructor sets it) as uint32."""
+    c = np.asarray(rgb, np.uint8).reshape(-1, 3).astype(np.uint32)
+    return np.uint32(0xFF000000) | (c[:, 0] << 16) | (c[:, 1] << 8) | c[:, 2]
+
+
+def save_pcd_xyzrgb(path, xyz, rgb):
+    """pcl::io::savePCDFileBinary of a pcl::PointCloud<pcl::PointXYZRGB>: fields x y z rgb, 16 bytes per point, the colour
+    packed as PCL packs it (pack_rgb) and stored under TYPE F."""
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    n = len(xyz)
+    rec = np.zeros(n, np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("rgb", "<u4")]))
+    rec["x"], rec["y"], rec["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    rec["rgb"] = pack_rgb(rgb) if n else np.zeros(0, np.uint32)
+    hdr = ("# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z rgb\nSIZE 4 4 4 4\nTYPE F F F F\n"
+           f"COUNT 1 1 1 1\nWIDTH {n}\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS {n}\nDATA binary\n")
+    with open(path, "wb") as f:
+        f.write(hdr.encode("ascii"))
+        f.write(rec.tobytes())
+
+
+def load_pcd_xyzrgb(path):
+    """(xyz [n,3] float32, rgb [n,3] uint8) of a PCD with fields x y z rgb (save_pcd_xyzrgb's inverse)."""
+    a, found = load_pcd(path, ("x", "y", "z", "rgb"))
+    if found != ["x", "y", "z", "rgb"]:
+        raise ValueError(f"{path}: fields {found}")
+    c = np.ascontiguousarray(a[:, 3]).view(np.uint32)
+    rgb = np.stack([(c >> 16) & 255, (c >> 8) & 255, c & 255], 1).astype(np.uint8)
+    return np.ascontiguousarray(a[:, :3]), rgb
+
+
+def read_image_bgr(path, width=None, height=None):
+    """An 8-bit image as cv::imread(path, IMREAD_COLOR) hands it out: [h, w, 3] uint8 in B, G, R order (grey replicated,
+    alpha dropped).  Decoded with Pillow.  With width / height given and a different size, the image is resized with
+    Pillow's bilinear filter -- close to, but not bit for bit, OpenCV's INTER_LINEAR (src/lvba_system.cpp:1963-1966)."""
+    from PIL import Image
+    with Image.open(path) as im:
+        if im.mode == "LA":
+            im = im.convert("L")
+        if im.mode != "RGB":
+            im = im.convert("RGB")                                     # L replicated, RGBA's alpha dropped, P expanded
+        if width is not None and height is not None and im.size != (int(width), int(height)):
+            im = im.resize((int(width), int(height)), Image.BILINEAR)
+        rgb = np.asarray(im, np.uint8)
+    return np.ascontiguousarray(rgb[:, :, ::-1])
+
+
 # ------------------------------------------------------------------------------------------------------------- COLMAP database
 COLMAP_MAX_NUM_IMAGES = (1 << 31) - 1
 

@@ -10,9 +10,12 @@ LiDAR poses, camera poses and landmarks", with every compute step in liblvba_hip
     camera extrinsics                         src/lvba_system.cpp:860-869   Rcw = Rci Rwi^T, tcw = -Rcw Pwi + tci
     anchor clouds + plane map of the visual stage  src/lvba_system.cpp:1453-1507
 
+    LvbaSystem::VisualizeOptComparison        src/lvba_system.cpp:1932-2144 the LiDAR map coloured from the images, after and
+                                                                            before the refinement (colorize_maps)
+
 Out of scope, as in DESIGN.md: SIFT extraction / matching (SiftGPU, `extractAndMatchFeaturesGPU`) -- keypoints and inlier
 matches are inputs here, e.g. from a COLMAP database through dataset.load_colmap_db, which is the reference's own alternative
-(`loadFromColmapDB`); ROS publishing and the OpenCV visualisations.
+(`loadFromColmapDB`); ROS publishing and the OpenCV overlays.
 """
 from __future__ import annotations
 
@@ -28,7 +31,8 @@ DEFAULTS = dict(                                   # config/config.yaml of the r
     sigma_px=0.5, sigma_plane=0.01,
     # robust losses of the visual stage: None (the reference's nullptr at src/lvba_system.cpp:1630, :1639) or a pair
     # (reprojection, plane) of VisualProblem.set_loss arguments -- REFERENCE_HUBER is the pair the reference builds at :1585-1586
-    visual_loss=None)
+    visual_loss=None,
+    colorize_half_window_s=0.5, colorize_leaf=0.01)       # VisualizeOptComparison: :1974, filter_size_points3D
 REFERENCE_HUBER = (("huber", 1.0), ("huber", 0.1))
 
 
@@ -242,11 +246,44 @@ def run_visual_ba_with_lidar_assist(scans, x_opt, x_orig, scan_times, image_time
     return out
 
 
+def colorize_maps(scans, image_times, images, intr, width, height, after, before=None, scan_times=None, half_window_s=0.5,
+                  leaf_size=0.01, max_batch_images=0, chunk=16):
+    """LvbaSystem::VisualizeOptComparison (src/lvba_system.cpp:1932-2144): the LiDAR map coloured from the images, thinned
+    by down_sampling_voxel2(leaf_size).  scans: a voxel.Scans; images: [m,H,W,3] BGR uint8 or a callable k -> [H,W,3] (read in
+    chunks of `chunk` images, each fed to both clouds); after / before = (scan_poses [n,12], Rcw [m,3,3], tcw [m,3]): the
+    refined scan poses and cameras, and the original ones (x_buf_before_, Rcw_all_); before may be None.
+    Returns {"after": (xyz, rgb), "before": (xyz, rgb)} (float32 [k,3], uint8 [k,3]), sorted by leaf key when thinned."""
+    from .colorize import ColorMap
+    if scan_times is None:
+        raise ValueError("scan_times are required")
+    sets = {"after": after} if before is None else {"after": after, "before": before}
+    maps = {}
+    try:
+        for name, (x, _, _) in sets.items():
+            maps[name] = ColorMap(scans, x, scan_times, intr, width, height, half_window_s=half_window_s, leaf_size=leaf_size,
+                                  max_batch_images=max_batch_images)
+        t = np.asarray(image_times, np.float64).reshape(-1)
+        for a in range(0, len(t), max(1, int(chunk))):
+            ks = range(a, min(len(t), a + max(1, int(chunk))))
+            bgr = np.stack([np.asarray(images(k) if callable(images) else images[k], np.uint8) for k in ks])
+            for name, (_, Rcw, tcw) in sets.items():
+                Rcw, tcw = np.asarray(Rcw, np.float64).reshape(-1, 3, 3), np.asarray(tcw, np.float64).reshape(-1, 3)
+                maps[name].add_images(t[a:a + len(ks)], Rcw[a:a + len(ks)], tcw[a:a + len(ks)], bgr)
+        return {name: m.download() for name, m in maps.items()}
+    finally:
+        for m in maps.values():
+            m.close()
+
+
 def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, tci, intr, width, height, keypoints, pairs,
-                      matches, enable_lidar_ba=True, enable_visual_ba=True, device=0, **cfg):
+                      matches, enable_lidar_ba=True, enable_visual_ba=True, device=0, images=None, **cfg):
     """LvbaSystem::runFullPipeline (src/lvba_system.cpp:136-142) on in-memory data: clouds = body-frame [n_i, >=3] float32
     arrays, poses [n,12] = x_buf_ (T_world<-imu), image_poses [m,12] the image poses from the odometry.  cfg: DEFAULTS' keys
-    (visual_loss among them)."""
+    (visual_loss, colorize_leaf among them).  images: None, or the images ([m,H,W,3] BGR uint8 or a callable k -> [H,W,3]):
+    then the output also holds colored_after / colored_before = (xyz, rgb), the LiDAR map coloured from them
+    (colorize_maps) with the refined poses and cameras and with the original ones; this needs the visual stage."""
+    if images is not None and not enable_visual_ba:
+        raise ValueError("colouring the map needs the cameras of the visual stage (enable_visual_ba=True)")
     c = dict(DEFAULTS); c.update(cfg)
     x_orig = np.asarray(poses, np.float64).reshape(-1, 12).copy()
     out = dict(poses_before=x_orig)
@@ -261,6 +298,12 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
         if enable_visual_ba:
             out["visual"] = run_visual_ba_with_lidar_assist(scans, out["poses"], x_orig, scan_times, image_times, image_poses, Rci,
                                                             tci, intr, width, height, keypoints, pairs, matches, **c)
+        if images is not None:
+            v = out["visual"]
+            col = colorize_maps(scans, image_times, images, intr, width, height, after=(out["poses"], v["Rcw"], v["tcw"]),
+                                before=(x_orig, v["Rcw_before"], v["tcw_before"]), scan_times=scan_times,
+                                half_window_s=c["colorize_half_window_s"], leaf_size=c["colorize_leaf"])
+            out["colored_after"], out["colored_before"] = col["after"], col["before"]
     return out
 
 
@@ -295,13 +338,17 @@ def extrinsics_from_config(Rcl, Pcl, extrinsic_R, extrinsic_T):
 
 
 def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrinsic_R=np.eye(3), extrinsic_T=np.zeros(3),
-                image_sample_step=1, out_dir=None, device=0, **cfg):
+                image_sample_step=1, out_dir=None, device=0, colorize=False, **cfg):
     """initFromDatasetIO + runFullPipeline on a dataset directory; with out_dir, the refined LiDAR poses (TUM) and the COLMAP
     text files images.txt / points3D.txt the reference writes (src/lvba_system.cpp:2018-2137) are saved there.  images.txt is
-    the reference's, character for character (tests/test_ref_system.py); points3D.txt has the reference's format but holds
-    the refined visual landmarks in white -- the reference fills it with its LiDAR map coloured from the images
-    (VisualizeOptComparison), which needs an image codec and is visualisation, outside the scope contract.  cfg as for
-    run_full_pipeline, e.g. visual_loss=REFERENCE_HUBER."""
+    the reference's, character for character (tests/test_ref_system.py).
+    colorize=False (default): points3D.txt has the reference's format but holds the refined visual landmarks in white.
+    colorize=True: the LiDAR map is coloured from the images as VisualizeOptComparison does (colorize_maps): all_image/<t>.png
+    are decoded with Pillow into BGR as cv::imread(IMREAD_COLOR) would (8-bit RGB, RGBA and grey); an image whose size is not
+    the camera's is resized with Pillow's bilinear filter, which is not OpenCV's INTER_LINEAR bit for bit.  The output gains
+    colored_after / colored_before, and out_dir gets colored_merged_after.pcd / colored_merged_before.pcd (binary PCD, PCL's
+    XYZRGB layout) and a points3D.txt holding the coloured after-cloud, as the reference writes them.
+    cfg as for run_full_pipeline, e.g. visual_loss=REFERENCE_HUBER."""
     import os
     from . import dataset as D
     ds = D.load_dataset(data_path)
@@ -318,7 +365,8 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
     Rci, tci = extrinsics_from_config(Rcl, Pcl, extrinsic_R, extrinsic_T)
     out = run_full_pipeline([c[:, :3] for c in ds["clouds"]], ds["poses"], ds["timestamps"], image_ids, image_poses, Rci, tci, intr,
                             width, height, [k[:, :2] for k in kps], [pairs[k] for k in keep], [matches[k] for k in keep],
-                            device=device, **cfg)
+                            device=device, images=(lambda k: D.read_image_bgr(os.path.join(img_dir, names[k]), width, height))
+                            if colorize else None, **cfg)
     out.update(image_ids=image_ids, scan_times=ds["timestamps"])
     if out_dir is not None:
         os.makedirs(out_dir, exist_ok=True)
@@ -326,6 +374,11 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
         v = out.get("visual")
         if v is not None and len(v.get("landmarks", [])):
             D.write_images_txt(os.path.join(out_dir, "images.txt"), rot_to_quat_wxyz(v["Rcw"]), v["tcw"])
-            ok = v["landmark_valid"] > 0
-            D.write_points3d_txt(os.path.join(out_dir, "points3D.txt"), v["landmarks"][ok], np.full((int(ok.sum()), 3), 255))
+            if not colorize:
+                ok = v["landmark_valid"] > 0
+                D.write_points3d_txt(os.path.join(out_dir, "points3D.txt"), v["landmarks"][ok], np.full((int(ok.sum()), 3), 255))
+        if colorize:
+            D.save_pcd_xyzrgb(os.path.join(out_dir, "colored_merged_after.pcd"), *out["colored_after"])
+            D.save_pcd_xyzrgb(os.path.join(out_dir, "colored_merged_before.pcd"), *out["colored_before"])
+            D.write_points3d_txt(os.path.join(out_dir, "points3D.txt"), *out["colored_after"])
     return out

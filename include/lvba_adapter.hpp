@@ -533,4 +533,84 @@ int32_t optimize_camera_poses_hip(QVec &qs, TVec &ts, XVec &Xs, const std::vecto
     return term;
 }
 
+// VisualizeOptComparison's two depth-buffer loops and both down_sampling_voxel2 calls (src/lvba_system.cpp:1932-2144) on the
+// device: the LiDAR map coloured from the images with the refined poses (x_after = x_buf_, Rcw_all_optimized_) and with the
+// original ones (x_before = x_buf_before_, Rcw_all_).  clouds = pl_fulls_ (x, y, z the first three floats of a point), poses
+// with `.R(r,c)`, `.p[r]`, `.t`; rotations `(r,c)`, translations `[r]`.  image(k, bgr) fills bgr with image k as width x height
+// BGR bytes (cv::imread + the reference's resize) and returns false when it cannot be read (the reference skips it).  The
+// outputs (pcl::PointCloud<pcl::PointXYZRGB> or anything with PointType / push_back / clear) get the thinned clouds, sorted by
+// leaf key.  leaf = filter_size_points3D_.
+template <class CloudPtrVec, class PoseVec, class RotVec, class TransVec, class ImageFn, class CloudOut>
+void colorize_maps(const CloudPtrVec &clouds, const PoseVec &x_after, const PoseVec &x_before, const std::vector<double> &image_ids,
+                   const RotVec &Rcw_after, const TransVec &tcw_after, const RotVec &Rcw_before, const TransVec &tcw_before,
+                   const double intr[8], int32_t width, int32_t height, ImageFn image, CloudOut &out_after, CloudOut &out_before,
+                   double leaf = 0.01, int device = 0)
+{
+    const int32_t n = static_cast<int32_t>(std::min(x_after.size(), static_cast<size_t>(clouds.size())));
+    std::vector<const void *> ptr(n);
+    std::vector<int64_t> cnt(n);
+    std::vector<double> times(n);
+    int32_t stride = 12;
+    for (int32_t j = 0; j < n; ++j) {
+        const auto &pts = clouds[j]->points;
+        ptr[j] = pts.data();
+        cnt[j] = static_cast<int64_t>(pts.size());
+        if (!pts.empty()) stride = static_cast<int32_t>(sizeof(pts[0]));
+        times[j] = x_after[j].t;
+    }
+    struct Handles {
+        lvba_scans_t scans = nullptr;
+        lvba_colorize_t h[2] = {nullptr, nullptr};
+        ~Handles() { lvba_colorize_destroy(h[0]); lvba_colorize_destroy(h[1]); lvba_scans_destroy(scans); }
+    } hd;
+    auto check = [](int32_t rc, const char *what) {
+        if (rc != LVBA_OK) throw std::runtime_error(std::string(what) + ": " + lvba_last_error());
+    };
+    check(lvba_scans_create(device, n, ptr.data(), cnt.data(), stride, &hd.scans), "lvba_scans_create");
+    lvba_colorize_opts o;
+    lvba_colorize_default_opts(&o);
+    o.leaf_size = leaf;
+    std::vector<double> poses(12 * static_cast<size_t>(n));
+    for (int s = 0; s < 2; ++s) {
+        const PoseVec &x = s ? x_before : x_after;
+        for (int32_t j = 0; j < n; ++j)
+            for (int r = 0; r < 3; ++r) {
+                for (int c = 0; c < 3; ++c) poses[12 * j + 3 * r + c] = x[j].R(r, c);
+                poses[12 * j + 9 + r] = x[j].p[r];
+            }
+        check(lvba_colorize_create(hd.scans, poses.data(), times.data(), intr, width, height, &o, &hd.h[s]), "lvba_colorize_create");
+    }
+    std::vector<uint8_t> bgr;
+    for (size_t k = 0; k < image_ids.size(); ++k) {
+        bgr.clear();
+        if (!image(k, bgr)) continue;                                          // :1959-1962
+        if (bgr.size() != 3 * static_cast<size_t>(width) * height) throw std::runtime_error("colorize_maps: image of the wrong size");
+        for (int s = 0; s < 2; ++s) {
+            const RotVec &Rv = s ? Rcw_before : Rcw_after;
+            const TransVec &tv = s ? tcw_before : tcw_after;
+            double R[9], t[3];
+            for (int r = 0; r < 3; ++r) {
+                for (int c = 0; c < 3; ++c) R[3 * r + c] = Rv[k](r, c);
+                t[r] = tv[k][r];
+            }
+            check(lvba_colorize_add_images(hd.h[s], 1, &image_ids[k], R, t, bgr.data()), "lvba_colorize_add_images");
+        }
+    }
+    for (int s = 0; s < 2; ++s) {
+        CloudOut &out = s ? out_before : out_after;
+        int64_t m = 0;
+        check(lvba_colorize_count(hd.h[s], &m), "lvba_colorize_count");
+        std::vector<float> xyz(3 * static_cast<size_t>(m));
+        std::vector<uint8_t> rgb(3 * static_cast<size_t>(m));
+        check(lvba_colorize_download(hd.h[s], xyz.data(), rgb.data()), "lvba_colorize_download");
+        out.clear();
+        for (int64_t i = 0; i < m; ++i) {
+            typename CloudOut::PointType p;
+            p.x = xyz[3 * i]; p.y = xyz[3 * i + 1]; p.z = xyz[3 * i + 2];
+            p.r = rgb[3 * i]; p.g = rgb[3 * i + 1]; p.b = rgb[3 * i + 2];
+            out.push_back(p);
+        }
+    }
+}
+
 } // namespace lvba

@@ -549,6 +549,42 @@ int32_t lvba_lidar_ba_multi(int32_t n_shares, const lvba_scans_t *scans, const d
 int32_t lvba_scans_info(lvba_scans_t scans, int32_t *n_frames, int64_t *frame_count);
 int32_t lvba_scans_download(lvba_scans_t scans, int32_t frame, float *xyz);
 
+/* ---- The LiDAR map coloured from the camera images (version 112) ----------------------------------------------------------
+ *   <- LvbaSystem::VisualizeOptComparison (src/lvba_system.cpp:1932-2144) for one pose set: the after cloud with the refined
+ *   scan poses (x_buf_) and cameras (Rcw_all_optimized_), the before cloud with x_buf_before_ and Rcw_all_.
+ *   lvba_colorize_create: the handle computes every point of `scans` in the world frame (scan_poses [n_frames][12], R
+ *   row-major | t, T_world<-body), stored as float.  scan_times [n_frames] ascending; intr = fx fy cx cy k1 k2 p1 p2; the images
+ *   are width x height (the reference's camera size: images of another size are the caller's to resize).
+ *   lvba_colorize_add_images: image k (time image_times[k], camera Rcw [k][9] row-major / tcw [k][3] = T_cam<-world, bgr
+ *   [k][height][width][3] bytes as cv::imread gives them) takes every point of the scans with |t_scan - t_k| <= half_window_s,
+ *   in scan order; an image without points is skipped.  Each point is projected (projectWorldToPixel, std::round, [0,W) x
+ *   [0,H)) and a pixel keeps the point the reference's depth buffer keeps (replace when zc + 1e-6f < zbuf, zbuf = (float)zc:
+ *   not the nearest one in general), coloured r g b from the pixel.  Kept pixels are merged in row-major order, images in
+ *   call order, calls in order.  With leaf_size >= 0.001 the merged cloud is thinned as down_sampling_voxel2 does (per leaf
+ *   voxel the first point at the smallest distance to its centre) and comes out sorted by leaf key (x, y, z); otherwise in
+ *   merged order.  Images are processed in batches of at most max_batch_images (0: as free device memory allows); the result
+ *   does not depend on the batching.
+ *   lvba_colorize_count / lvba_colorize_download: the current cloud, xyz [n][3] float and rgb [n][3] bytes.
+ *   lvba_colorize_profile: accumulated device time in ms of upload, projection, sort, walk, compaction and thinning.
+ *   LVBA_ERR_ARG: null pointers, width or height < 2, scan times not ascending, non-finite poses, times or intrinsics, or (when
+ *   thinning) a finite world point more than 2^20 leaves from the origin; the handle stays valid / destroyable. */
+typedef struct lvba_colorize_s *lvba_colorize_t;
+typedef struct lvba_colorize_opts {
+    double half_window_s;     /* scan window around an image time (reference: 0.5 s) */
+    double leaf_size;         /* down_sampling_voxel2 leaf (reference: filter_size_points3D = 0.01); < 0.001: no thinning */
+    int32_t max_batch_images; /* 0: by free device memory */
+    int32_t reserved;
+} lvba_colorize_opts;
+void lvba_colorize_default_opts(lvba_colorize_opts *o);
+int32_t lvba_colorize_create(lvba_scans_t scans, const double *scan_poses, const double *scan_times, const double intr[8],
+                             int32_t width, int32_t height, const lvba_colorize_opts *o, lvba_colorize_t *out);
+int32_t lvba_colorize_add_images(lvba_colorize_t h, int32_t n, const double *image_times, const double *Rcw, const double *tcw,
+                                 const uint8_t *bgr);
+int32_t lvba_colorize_count(lvba_colorize_t h, int64_t *n_points);
+int32_t lvba_colorize_download(lvba_colorize_t h, float *xyz, uint8_t *rgb);
+int32_t lvba_colorize_profile(lvba_colorize_t h, double ms[6]);
+void lvba_colorize_destroy(lvba_colorize_t h);
+
 #ifdef __cplusplus
 }
 #endif
