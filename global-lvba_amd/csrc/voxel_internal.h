@@ -19,6 +19,16 @@ struct lvba_scans_s {
     int64_t *d_frame_off = nullptr;
 };
 
+namespace lvba {
+struct DevCloud { float *d; int64_t n; }; // n points [n][3] on a device
+// A scan set of n_frames frames of count[f] points on `device`, allocated with hipMalloc as lvba_scans_destroy frees it
+// (window_ba.hip).  Its points: `adopt`, a hipMalloc'd array on `device` that already holds them all (the set owns it from here
+// on, also when this fails); else the clouds src[0 .. n_src) copied in back to back (from any device: hipMemcpyDefault); else
+// (n_src = 0) left to the caller.
+int32_t scans_build(int32_t device, int32_t n_frames, const int64_t *count, float *adopt, const DevCloud *src, int n_src,
+                    lvba_scans_s **out);
+} // namespace lvba
+
 struct lvba_voxmap_s;
 // the admitted voxels' clusters of a map, [n_factors][10] on the device (voxelize.hip; for the window driver's joint problem)
 const double *lvba_voxmap_clusters(const lvba_voxmap_s *h);

@@ -723,26 +723,17 @@ extern "C" int32_t lvba_scans_create(int32_t device, int32_t n_frames, const voi
         return lvba_fail(LVBA_ERR_DEVICE, "no HIP device available (this library has no CPU fallback)");
     if (device < 0 || device >= ndev) return lvba_fail(LVBA_ERR_ARG, "device %d out of range [0,%d)", device, ndev);
     HIPCHK(hipSetDevice(device));
-    lvba_scans_s *sc = new (std::nothrow) lvba_scans_s();
-    if (!sc) return lvba_fail(LVBA_ERR_NOMEM, "host allocation failed");
-    sc->device = device;
-    sc->n_frames = n_frames;
-    sc->frame_off.assign(n_frames + 1, 0);
-    for (int f = 0; f < n_frames; ++f) {
-        if (frame_count[f] < 0 || (frame_count[f] > 0 && !frame_points[f])) {
-            delete sc;
+    for (int f = 0; f < n_frames; ++f)
+        if (frame_count[f] < 0 || (frame_count[f] > 0 && !frame_points[f]))
             return lvba_fail(LVBA_ERR_ARG, "frame %d: bad point count / null cloud", f);
-        }
-        sc->frame_off[f + 1] = sc->frame_off[f] + frame_count[f];
-    }
+    lvba_scans_s *sc = nullptr;
+    TRY(lvba::scans_build(device, n_frames, frame_count, nullptr, nullptr, 0, &sc));
     const int64_t P = sc->frame_off[n_frames];
     auto fail = [&](hipError_t e, const char *what) {
         lvba_scans_destroy(sc);
         return lvba_fail(e == hipErrorOutOfMemory ? LVBA_ERR_NOMEM : LVBA_ERR_DEVICE, "%s: %s", what, hipGetErrorString(e));
     };
-    hipError_t e;
-    if ((e = hipMalloc((void **)&sc->d_pts, P ? 12 * (size_t)P : 8)) != hipSuccess) return fail(e, "hipMalloc(points)");
-    if ((e = hipMalloc((void **)&sc->d_frame_off, 8 * ((size_t)n_frames + 1))) != hipSuccess) return fail(e, "hipMalloc(frame_off)");
+    hipError_t e = hipSuccess;
     // xyz packed out of the caller's point stride (e.g. sizeof(pcl::PointXYZINormal) = 48).  hipMemcpy2D of 12-byte rows out of
     // pageable memory ran at 3.3 GB/s (57.8 ms for 16 M points: 18 x the map build it feeds).  Now the host packs the
     // coordinates itself -- a few threads, each a slice of a chunk of <= 1 M points -- into one of two pinned buffers, and the
@@ -825,8 +816,6 @@ extern "C" int32_t lvba_scans_create(int32_t device, int32_t n_frames, const voi
                                       hipMemcpyHostToDevice);
                 if (e != hipSuccess) return fail(e, "hipMemcpy(points)");
             }
-    if ((e = lvba::copy_h2d(sc->d_frame_off, sc->frame_off.data(), 8 * ((size_t)n_frames + 1))) != hipSuccess)
-        return fail(e, "hipMemcpy(frame_off)");
     *out = sc;
     return LVBA_OK;
 }

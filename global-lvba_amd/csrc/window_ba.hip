@@ -12,7 +12,6 @@
 // global stages' lvba_voxmap_build_scans directly.
 // down_sampling_voxel2 emits survivors in unordered_map order (unspecified); here: sorted by voxel key (x, y, z).
 #include <atomic>
-#include <functional>
 #include <string>
 #include <thread>
 #include "host_arena.h"
@@ -144,6 +143,482 @@ inline void mat3T_mul(const double *A, const double *B, double *C) // A^T * B
         for (int c = 0; c < 3; ++c) C[3 * r + c] = A[r] * B[c] + A[3 + r] * B[3 + c] + A[6 + r] * B[6 + c];
 }
 
+// damping_iter on the problem of a voxel map, which it consumes (:264, :386): poses x refined in place; the LM status, the
+// iterations, the first and last cost of the trace, and the time of the problem's set-up
+struct Refined { int32_t status = 0, n_iter = 0; double cost_first = 0.0, cost_last = 0.0, setup_ms = 0.0; };
+int32_t refine_map(lvba_voxmap_t map, double *x, const lvba_balm_opts &lm, Refined &r)
+{
+    const double t0 = now_ms();
+    lvba_balm_t b = nullptr;
+    int32_t rc = lvba_voxmap_to_balm(map, &b);
+    lvba_voxmap_destroy(map);
+    if (rc != LVBA_OK) return rc;
+    lvba::hvec<lvba_lm_trace> trace((size_t)std::max(1, lm.max_iter));
+    int32_t nt = 0;
+    lvba_balm_info_t bi;
+    lvba_balm_info(b, &bi); // forces the one-off problem set-up (ordering, pair lists) so that it is timed apart
+    r.setup_ms = now_ms() - t0;
+    rc = lvba_balm_refine(b, x, &lm, trace.data(), &nt);
+    lvba_balm_destroy(b);
+    if (rc < 0) return rc;
+    r.status = rc; r.n_iter = nt;
+    if (nt > 0) {
+        r.cost_first = trace[0].residual1;
+        r.cost_last = trace[nt - 1].accepted ? trace[nt - 1].residual2 : trace[nt - 1].residual1;
+    }
+    return LVBA_OK;
+}
+
+// ---- lvba_window_ba.  One window = map -> problem -> LM -> anchor cloud; windows are independent (src/lvba_system.cpp:232-302
+// runs them one after the other).  The stages, each over all windows:
+//   1. voxel map of every window: ONE map of all windows (stage_map_joint), or one per window on a few host threads, each with
+//      its own stream (a single map build leaves the GPU idle most of the time -- launch and synchronisation latency);
+//   2. the LM refinements of ALL windows in lock-step as one grouped problem (lvba_balm_set_groups / lvba_balm_refine_groups: one
+//      evaluation, one band factorisation with a damping value per window, one cost pass per iteration for all windows; every
+//      window keeps its own LM state).  lm_mode = 1, a single window, or a broken pivot in the joint factorisation: one window at
+//      a time, on the host threads;
+//   3. alignment, relative poses, anchor merge + down-sampling: all windows in one pass (merge_run over all windows), or one
+//      pass per window on the host threads.
+// The results are assembled in window order into the caller's arrays and a scan set of the anchor clouds.
+struct WinResult {
+    int32_t rc = LVBA_OK;
+    std::string err;
+    lvba_window_info info{};
+    lvba::hvec<double> x; // the window's poses: odometry, refined by stage 2
+    lvba_voxmap_t map = nullptr;
+    bool refined = false;
+};
+// one lvba_window_ba call; it owns what the stages make until the call returns and frees it on every path
+struct WindowCall {
+    lvba_scans_s *sc = nullptr;
+    const double *poses = nullptr;
+    lvba_window_opts o{};
+    int n = 0, w = 1, n_win = 0, n_thr = 1;
+    hipStream_t s = nullptr;          // the calling thread's
+    lvba::hvec<hipStream_t> wstreams; // the worker threads' (n_thr > 1); they live until the call returns: the maps work on them
+    lvba::hvec<WinResult> res;
+    lvba::hvec<double> rel;           // [n][12] relative poses to the anchor: identity (:338), then the merged windows' (:284-299)
+    lvba_voxmap_t joint_map = nullptr; // stage 1 as ONE map of all windows; the windows' maps are views into it
+    lvba::hvec<DevCloud> clouds;      // [n_win] stage 3's hipMalloc'd anchor points: [w0] those of the run starting at window w0
+
+    int start(int wi) const { return wi * w; }
+    int frames(int wi) const { return std::min(w, n - wi * w); }
+    void free_maps()
+    {
+        for (auto &R : res) if (R.map) { lvba_voxmap_destroy(R.map); R.map = nullptr; }
+        if (joint_map) { lvba_voxmap_destroy(joint_map); joint_map = nullptr; }
+    }
+    ~WindowCall()
+    {
+        free_maps();
+        for (auto &c : clouds) if (c.d) (void)hipFree(c.d);
+        for (hipStream_t q : wstreams) if (q) lvba::StreamCache::get().release(q);
+        if (s) lvba::StreamCache::get().release(s);
+    }
+};
+
+// The joint passes (stage 1 and stage 3 over all windows at once) hold keys, records, indices and sort temporaries of ALL frames
+// at once (~90 bytes per point, where a per-window pass needs one window's worth): they are only tried when that fits the device's
+// free memory with room to spare -- a long sequence goes window by window instead of running into hipErrorOutOfMemory first.
+// LVBA_WINDOW_JOINT_MAP=0: always window by window.
+bool joint_fits(const WindowCall &c)
+{
+    static const bool on = [] { const char *e = getenv("LVBA_WINDOW_JOINT_MAP"); return !(e && !strcmp(e, "0")); }();
+    if (!on || c.n_win < 2) return false;
+    size_t free_b = 0, total_b = 0;
+    const int64_t P = c.sc->frame_off[(size_t)c.n] - c.sc->frame_off[0];
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return false; }
+    if ((double)P * 96.0 > 0.5 * (double)free_b) {
+        if (timing_on("window"))
+            fprintf(stderr, "[window_ba] joint pass skipped: %lld points x ~96 B against %.1f GB free -> one pass per window\n",
+                    (long long)P, (double)free_b / 1e9);
+        return false;
+    }
+    return true;
+}
+
+// the window's info and starting poses (odometry) and, given its voxel map (none with merge_only), the skip rule (:258-262)
+void window_init(WindowCall &c, int wi, lvba_voxmap_t map, double map_ms)
+{
+    WinResult &R = c.res[(size_t)wi];
+    const int start = c.start(wi), cw = c.frames(wi);
+    R.info = lvba_window_info{};
+    R.info.start = start; R.info.n_frames = cw; R.info.anchor = -1;
+    R.x.assign(c.poses + 12 * (int64_t)start, c.poses + 12 * (int64_t)(start + cw));
+    R.map = map;
+    if (!map) return;
+    lvba_voxmap_info_t mi;
+    lvba_voxmap_info(map, &mi);
+    R.info.n_voxels = mi.n_voxels; R.info.n_factors = mi.n_factors;
+    R.info.map_ms = map_ms;
+    if (mi.n_voxels < 3 * (int64_t)cw) { // :258-262
+        R.info.skipped = 1;
+        lvba_voxmap_destroy(R.map);
+        R.map = nullptr;
+    }
+}
+
+// ---- stage 1: the voxel map at the odometry poses (:247-257), one window
+int32_t stage_map(WindowCall &c, int wi, hipStream_t ws)
+{
+    lvba_voxmap_t map = nullptr;
+    const double tw = now_ms();
+    if (!c.o.merge_only) // on the worker's stream, which outlives the map
+        TRY(lvba_voxmap_build_scans_on(c.sc, c.start(wi), c.frames(wi), c.poses + 12 * (int64_t)c.start(wi), &c.o.voxel, ws, &map));
+    window_init(c, wi, map, now_ms() - tw);
+    return LVBA_OK;
+}
+// ---- stage 1 for all windows at once: a root voxel is (window, key), so one sort and one pass of every kernel of the map build
+// serve every window (the per-window builds are dozens of dependent launches and a dozen host round trips EACH); a window's
+// part of the joint map is bit for bit what its own build gives (tests/test_gpu_window.py).  False: build them one by one.
+bool stage_map_joint(WindowCall &c)
+{
+    const double tw = now_ms();
+    if (lvba_voxmap_build_scans_joint(c.sc, 0, c.n, c.w, c.poses, &c.o.voxel, c.s, &c.joint_map) != LVBA_OK) {
+        c.joint_map = nullptr; // (too many key + window bits, a bad point, ...: the per-window builds say what it is)
+        return false;
+    }
+    const double per = (now_ms() - tw) / c.n_win;
+    for (int wi = 0; wi < c.n_win; ++wi) {
+        WinResult &R = c.res[(size_t)wi];
+        lvba_voxmap_t view = nullptr;
+        R.rc = lvba_voxmap_window_view(c.joint_map, wi, &view);
+        if (R.rc != LVBA_OK) { R.err = lvba_last_error(); continue; }
+        window_init(c, wi, view, per);
+    }
+    return true;
+}
+
+// ---- stage 2, one window at a time: damping_iter on the window's own problem (:264)
+int32_t stage_lm_single(WindowCall &c, int wi, hipStream_t)
+{
+    WinResult &R = c.res[(size_t)wi];
+    if (!R.map || R.refined) return LVBA_OK;
+    const double tw = now_ms();
+    lvba_voxmap_t map = R.map;
+    R.map = nullptr;
+    Refined r;
+    TRY(refine_map(map, R.x.data(), c.o.lm, r));
+    R.info.lm_status = r.status; R.info.n_iter = r.n_iter;
+    R.info.cost_first = r.cost_first; R.info.cost_last = r.cost_last;
+    R.info.setup_ms = r.setup_ms;
+    R.info.solve_ms = now_ms() - tw;
+    R.refined = true;
+    return LVBA_OK;
+}
+// ---- stage 2, all windows at once.  Returns LVBA_OK with `done` = false when the windows have to go one by one.
+int32_t stage_lm_batched(WindowCall &c, bool &done)
+{
+    done = false;
+    lvba::hvec<int> live;
+    for (int wi = 0; wi < c.n_win; ++wi)
+        if (c.res[(size_t)wi].map) live.push_back(wi);
+    if (live.size() < 2) return LVBA_OK;
+    const double t0 = now_ms();
+    const int G = (int)live.size();
+    lvba::hvec<int32_t> pose_off((size_t)G + 1, 0);
+    lvba::hvec<int64_t> vox_off((size_t)G + 1, 0), fac_off((size_t)G + 1, 0);
+    for (int k = 0; k < G; ++k) {
+        const WinResult &R = c.res[(size_t)live[(size_t)k]];
+        pose_off[(size_t)k + 1] = pose_off[(size_t)k] + R.info.n_frames;
+        vox_off[(size_t)k + 1] = vox_off[(size_t)k] + R.info.n_voxels;
+        fac_off[(size_t)k + 1] = fac_off[(size_t)k] + R.info.n_factors;
+    }
+    const int64_t V = vox_off[(size_t)G], F = fac_off[(size_t)G];
+    if (F >= ((int64_t)1 << 31)) return LVBA_OK; // too large for one handle: one by one
+    lvba::hvec<int64_t> off((size_t)V + 1, 0);
+    lvba::hvec<int32_t> idx((size_t)F);
+    lvba::hvec<double> x(12 * (size_t)pose_off[(size_t)G]);
+    DevBuf d_clu(c.s);
+    HIPCHK(d_clu.alloc(80 * (size_t)F));
+    lvba::hvec<int64_t> joff; // with a joint map: its whole CSR structure in ONE pair of copies instead of two per window
+    lvba::hvec<int32_t> jidx;
+    if (c.joint_map) {
+        lvba_voxmap_info_t ji;
+        lvba_voxmap_info(c.joint_map, &ji);
+        joff.resize((size_t)ji.n_voxels + 1); jidx.resize((size_t)std::max<int64_t>(ji.n_factors, 1));
+        TRY(lvba_voxmap_export(c.joint_map, joff.data(), jidx.data(), nullptr, nullptr));
+    }
+    for (int k = 0; k < G; ++k) {
+        const WinResult &R = c.res[(size_t)live[(size_t)k]];
+        const int64_t v0 = vox_off[(size_t)k], f0 = fac_off[(size_t)k], nv = R.info.n_voxels, nf = R.info.n_factors;
+        lvba::hvec<int64_t> o1((size_t)nv + 1);
+        if (c.joint_map) {
+            int64_t jv0, jv1, jf0, jf1;
+            TRY(lvba_voxmap_window_range(c.joint_map, live[(size_t)k], &jv0, &jv1, &jf0, &jf1));
+            memcpy(o1.data(), joff.data() + jv0, 8 * ((size_t)nv + 1));
+            memcpy(idx.data() + f0, jidx.data() + jf0, 4 * (size_t)nf);
+        } else
+            TRY(lvba_voxmap_export(R.map, o1.data(), idx.data() + f0, nullptr, nullptr)); // CSR structure to the host, clusters stay in HBM
+        for (int64_t a = 0; a <= nv; ++a) off[(size_t)(v0 + a)] = f0 + (o1[(size_t)a] - o1[0]);
+        for (int64_t f = f0; f < f0 + nf; ++f) idx[(size_t)f] += pose_off[(size_t)k];
+        HIPCHK(hipMemcpyAsync(d_clu.as<double>() + 10 * f0, lvba_voxmap_clusters(R.map), 80 * (size_t)nf, hipMemcpyDeviceToDevice, c.s));
+        memcpy(x.data() + 12 * (size_t)pose_off[(size_t)k], R.x.data(), 96 * (size_t)R.info.n_frames);
+    }
+    HIPCHK(hipStreamSynchronize(c.s));
+    const bool tm = timing_on("window");
+    double tk = now_ms();
+    auto mk = [&](const char *what) { if (tm) { const double t = now_ms(); fprintf(stderr, "[window_ba LM] %-16s %.3f ms\n", what, t - tk); tk = t; } };
+    if (tm) fprintf(stderr, "[window_ba LM] %-16s %.3f ms\n", "export + concat", tk - t0);
+    lvba_balm_t b = nullptr;
+    TRY(balm_create_dev_trusted(pose_off[(size_t)G], V, off.data(), idx.data(), d_clu.as<double>(), c.sc->device, &b));
+    struct Guard { lvba_balm_t b; ~Guard() { if (b) lvba_balm_destroy(b); } } guard{b};
+    mk("create");
+    TRY(lvba_balm_set_groups(b, G, pose_off.data(), vox_off.data()));
+    mk("set_groups");
+    lvba_balm_info_t bi;
+    TRY(lvba_balm_info(b, &bi)); // the one-off set-up, timed apart
+    mk("set-up");
+    const double t1 = now_ms();
+    lvba::hvec<int32_t> n_iter((size_t)G), status((size_t)G);
+    lvba::hvec<double> first((size_t)G), last((size_t)G);
+    const int32_t rc = lvba_balm_refine_groups(b, x.data(), &c.o.lm, n_iter.data(), status.data(), first.data(), last.data());
+    if (rc == LVBA_NUM_FACTORIZATION) return LVBA_OK; // the windows are not independent in a broken factorisation: one by one
+    if (rc < 0) return rc;
+    const double t2 = now_ms();
+    mk("refine_groups");
+    for (int k = 0; k < G; ++k) {
+        WinResult &R = c.res[(size_t)live[(size_t)k]];
+        memcpy(R.x.data(), x.data() + 12 * (size_t)pose_off[(size_t)k], 96 * (size_t)R.info.n_frames);
+        R.info.n_iter = n_iter[(size_t)k]; R.info.lm_status = status[(size_t)k];
+        R.info.cost_first = first[(size_t)k]; R.info.cost_last = last[(size_t)k];
+        R.info.setup_ms = (t1 - t0) / G; R.info.solve_ms = (t2 - t0) / G; // the joint problem's times, shared out evenly
+        R.refined = true;
+        lvba_voxmap_destroy(R.map);
+        R.map = nullptr;
+    }
+    mk("results, maps freed");
+    lvba_balm_destroy(guard.b);
+    guard.b = nullptr;
+    mk("handle destroyed");
+    done = true;
+    return LVBA_OK;
+}
+
+// ---- stage 3: alignment to the odometry pose of the window's first frame (:268-279) and relative poses (:284-299) into c.rel
+void align_window(WindowCall &c, int wi)
+{
+    const int start = c.start(wi), cw = c.frames(wi);
+    const double *x_odom = c.poses + 12 * (int64_t)start;
+    const lvba::hvec<double> &x = c.res[(size_t)wi].x;
+    const double *Ro0 = x_odom, *po0 = x_odom + 9;
+    double R_align[9], p_align[3] = {0, 0, 0};
+    if (c.o.use_rel) {
+        mat3_mulT(Ro0, x.data(), R_align);
+        for (int r = 0; r < 3; ++r)
+            p_align[r] = po0[r] - (R_align[3 * r] * x[9] + R_align[3 * r + 1] * x[10] + R_align[3 * r + 2] * x[11]);
+    }
+    for (int j = 0; j < cw; ++j) {
+        double Ra[9], pa[3];
+        if (c.o.use_rel) {
+            const double *Rj = x.data() + 12 * j, *pj = Rj + 9;
+            mat3_mul(R_align, Rj, Ra);
+            for (int r = 0; r < 3; ++r)
+                pa[r] = R_align[3 * r] * pj[0] + R_align[3 * r + 1] * pj[1] + R_align[3 * r + 2] * pj[2] + p_align[r];
+        } else {
+            memcpy(Ra, x_odom + 12 * j, 72);
+            memcpy(pa, x_odom + 12 * j + 9, 24);
+        }
+        double *rj = c.rel.data() + 12 * (size_t)(start + j);
+        mat3T_mul(Ro0, Ra, rj);
+        const double d[3] = {pa[0] - po0[0], pa[1] - po0[1], pa[2] - po0[2]};
+        for (int r = 0; r < 3; ++r) rj[9 + r] = Ro0[r] * d[0] + Ro0[3 + r] * d[1] + Ro0[6 + r] * d[2];
+    }
+}
+// Merge + down_sampling_voxel2 (tools.hpp:300-359) of the run of windows [w0, w1) in one pass: the points of every frame moved by
+// its relative pose in one launch, ONE stable sort by (window, leaf key), one pick / scan / compaction into the anchor points.  A
+// window's cloud is bit for bit what a run of that window alone gives: the same fp32 points, the same leaf keys, the same order
+// inside a leaf (the sort is stable and a window's points keep their order), the leaves in key order.  The points of skipped
+// windows (relative poses: identity) sort behind all others and are dropped.  anchor_leaf < 0.001 (tools.hpp:303): the merged
+// points as they are.  *out: the clouds of the run's merged windows back to back (hipMalloc'd, as a scan set's d_pts; left empty
+// when they hold no point); count[wi - w0]: window wi's points (0 when skipped).
+int32_t merge_run(const WindowCall &c, int w0, int w1, hipStream_t s, DevCloud *out, int64_t *count)
+{
+    const lvba_scans_s *sc = c.sc;
+    const int nw = w1 - w0, f0 = c.start(w0), nf = c.start(w1 - 1) + c.frames(w1 - 1) - f0;
+    const int64_t p_begin = sc->frame_off[(size_t)f0], P = sc->frame_off[(size_t)(f0 + nf)] - p_begin;
+    // code[window]: its rank among the run's merged windows; the skipped ones' get the code above all of those.  at: the merged
+    // windows' bounds in the sorted sequence (their raw point counts: known on the host)
+    lvba::hvec<uint32_t> code((size_t)nw);
+    lvba::hvec<int64_t> at(1, 0);
+    int G = 0;
+    for (int wi = w0; wi < w1; ++wi) G += !c.res[(size_t)wi].info.skipped;
+    for (int wi = w0; wi < w1; ++wi) {
+        const bool skip = c.res[(size_t)wi].info.skipped;
+        const int64_t np = sc->frame_off[(size_t)(c.start(wi) + c.frames(wi))] - sc->frame_off[(size_t)c.start(wi)];
+        code[(size_t)(wi - w0)] = skip ? (uint32_t)G : (uint32_t)(at.size() - 1);
+        count[wi - w0] = skip ? 0 : np;
+        if (!skip) at.push_back(at.back() + np);
+    }
+    const int64_t P_live = at.back();
+    if (P_live == 0) return LVBA_OK;
+    const bool down = c.o.anchor_leaf >= 0.001;
+    if (down && P >= ((int64_t)1 << 32)) return lvba_fail(LVBA_ERR_UNSUPPORTED, "windows [%d,%d): %lld points for 32-bit sort indices", w0, w1, (long long)P);
+    const bool tm = nw > 1 && timing_on("window"); // (the per-window runs go on several host threads at once: not timed apart)
+    double tj = now_ms();
+    auto mark = [&](const char *what) { // (waits for the stream at every mark)
+        if (!tm) return;
+        (void)hipStreamSynchronize(s);
+        const double t = now_ms();
+        fprintf(stderr, "[window_ba merge] %-18s %.3f ms\n", what, t - tj);
+        tj = t;
+    };
+    DevBuf d_rel(s), d_code(s), d_at(s), d_cnt(s), merged(s), d_err(s), key(s), d2(s), idx(s), d_part(s);
+    DevBuf key_s(s), order(s), flag(s), excl(s), pick(s);
+    const int64_t n_slots = key_range_slots(P, 256);
+    HIPCHK(d_rel.alloc(96 * (size_t)nf)); HIPCHK(merged.alloc(12 * (size_t)P));
+    HIPCHK(lvba::copy_h2d(d_rel.p, c.rel.data() + 12 * (size_t)f0, 96 * (size_t)nf)); // (pageable sources: synchronous copies)
+    if (down) {
+        HIPCHK(d_code.alloc(4 * (size_t)nw)); HIPCHK(d_at.alloc(8 * ((size_t)G + 1))); HIPCHK(d_cnt.alloc(4 * ((size_t)G + 1)));
+        HIPCHK(d_err.alloc(28)); HIPCHK(key.alloc(8 * (size_t)P)); HIPCHK(d2.alloc(8 * (size_t)P)); HIPCHK(idx.alloc(4 * (size_t)P));
+        HIPCHK(d_part.alloc(24 * (size_t)n_slots));
+        HIPCHK(lvba::copy_h2d(d_code.p, code.data(), 4 * (size_t)nw));
+        HIPCHK(lvba::copy_h2d(d_at.p, at.data(), 8 * ((size_t)G + 1)));
+        HIPCHK(hipMemsetAsync(d_err.p, 0, 28, s));
+    }
+    mark("alloc + tables");
+    wba_merge_kernel<<<grid_for(P, 256), 256, 0, s>>>(P, sc->d_pts + 3 * p_begin, sc->d_frame_off + f0, nf, d_rel.as<double>(),
+                                                      c.o.anchor_leaf, merged.as<float>(), down ? key.as<uint64_t>() : nullptr,
+                                                      d2.as<double>(), idx.as<uint32_t>(), d_err.as<int>(), d_part.as<int>());
+    HIPCHK(hipGetLastError());
+    int64_t n_all = P_live;
+    if (down) {
+        key_range_reduce_kernel<<<key_range_reduce_grid(n_slots), 256, 0, s>>>(n_slots, d_part.as<int>(), d_err.as<int>() + 1);
+        HIPCHK(hipGetLastError());
+        int h_err[7] = {0}; // [0] error flag, [1..6] range of the biased key components
+        HIPCHK(hipStreamSynchronize(s));
+        HIPCHK(lvba::copy_d2h(h_err, d_err.p, 28));
+        if (h_err[0]) // (a run of several windows is retried one window at a time, so that the message names the window)
+            return lvba_fail(LVBA_ERR_ARG, "window %d: a merged point is non-finite or outside +-2^20 anchor leaves", w0);
+        mark("merge + range");
+        // the sort runs on the bits of the leaf key that vary (voxel_internal.h) below the window's code; run leaders only
+        // compare sorted keys for equality, so the re-packed ones serve as they are
+        const KeyPack kp = key_pack_of(h_err + 1);
+        const int cbits = G < nw ? 32 - __builtin_clz((unsigned)G) : (G > 1 ? 32 - __builtin_clz((unsigned)(G - 1)) : 0);
+        const unsigned bits = (unsigned)(kp.total + cbits);
+        if (bits > 64) return lvba_fail(LVBA_ERR_UNSUPPORTED, "windows [%d,%d): %u key + window bits", w0, w1, bits);
+        HIPCHK(key_s.alloc(8 * (size_t)P)); HIPCHK(order.alloc(4 * (size_t)P)); HIPCHK(flag.alloc(4 * ((size_t)P_live + 1)));
+        HIPCHK(excl.alloc(4 * ((size_t)P_live + 1))); HIPCHK(pick.alloc(4 * (size_t)P_live));
+        if (bits <= 32) {
+            DevBuf k32(s);
+            HIPCHK(k32.alloc(4 * (size_t)P));
+            wba_compress_win_kernel<uint32_t><<<grid_for(P, 256), 256, 0, s>>>(P, key.as<uint64_t>(), sc->d_frame_off + f0, nf, c.w,
+                                                                               d_code.as<uint32_t>(), kp, k32.as<uint32_t>());
+            HIPCHK(hipGetLastError());
+            TRY(sort_pairs(s, k32.as<uint32_t>(), key_s.as<uint32_t>(), idx.as<uint32_t>(), order.as<uint32_t>(), (size_t)P, bits));
+            wba_pick_kernel<uint32_t><<<grid_for(P_live, 256), 256, 0, s>>>(P_live, key_s.as<uint32_t>(), order.as<uint32_t>(), d2.as<double>(),
+                                                                            flag.as<uint32_t>(), pick.as<uint32_t>());
+        } else {
+            wba_compress_win_kernel<uint64_t><<<grid_for(P, 256), 256, 0, s>>>(P, key.as<uint64_t>(), sc->d_frame_off + f0, nf, c.w,
+                                                                               d_code.as<uint32_t>(), kp, key.as<uint64_t>());
+            HIPCHK(hipGetLastError());
+            TRY(sort_pairs(s, key.as<uint64_t>(), key_s.as<uint64_t>(), idx.as<uint32_t>(), order.as<uint32_t>(), (size_t)P, bits));
+            wba_pick_kernel<uint64_t><<<grid_for(P_live, 256), 256, 0, s>>>(P_live, key_s.as<uint64_t>(), order.as<uint32_t>(), d2.as<double>(),
+                                                                            flag.as<uint32_t>(), pick.as<uint32_t>());
+        }
+        HIPCHK(hipGetLastError());
+        mark("sort + pick");
+        HIPCHK(hipMemsetAsync(flag.as<uint32_t>() + P_live, 0, 4, s));
+        TRY(scan_excl<uint32_t>(s, flag.as<uint32_t>(), excl.as<uint32_t>(), (size_t)P_live + 1));
+        wba_bounds_kernel<<<grid_for(G + 1, 256), 256, 0, s>>>(G + 1, d_at.as<int64_t>(), excl.as<uint32_t>(), d_cnt.as<uint32_t>());
+        HIPCHK(hipGetLastError());
+        lvba::hvec<uint32_t> cnt((size_t)G + 1);
+        HIPCHK(hipStreamSynchronize(s));
+        HIPCHK(lvba::copy_d2h(cnt.data(), d_cnt.p, 4 * ((size_t)G + 1)));
+        mark("scan + counts");
+        n_all = cnt[(size_t)G];
+        for (int wi = w0, g = 0; wi < w1; ++wi)
+            if (!c.res[(size_t)wi].info.skipped) { count[wi - w0] = (int64_t)cnt[(size_t)g + 1] - (int64_t)cnt[(size_t)g]; ++g; }
+    }
+    float *pts = nullptr;
+    HIPCHK(hipMalloc((void **)&pts, 12 * (size_t)n_all));
+    mark("hipMalloc (cloud)");
+    hipError_t e = hipSuccess;
+    if (down) {
+        wba_compact_kernel<<<grid_for(P_live, 256), 256, 0, s>>>(P_live, flag.as<uint32_t>(), excl.as<uint32_t>(), pick.as<uint32_t>(),
+                                                                 merged.as<float>(), pts);
+        e = hipGetLastError();
+    } else
+        for (int wi = w0, g = 0; wi < w1 && e == hipSuccess; ++wi)
+            if (!c.res[(size_t)wi].info.skipped) {
+                const int64_t src = sc->frame_off[(size_t)c.start(wi)] - p_begin;
+                e = hipMemcpyAsync(pts + 3 * at[(size_t)g], merged.as<float>() + 3 * src, 12 * (size_t)count[wi - w0], hipMemcpyDeviceToDevice, s);
+                ++g;
+            }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        (void)hipFree(pts);
+        return lvba_fail(e == hipErrorOutOfMemory ? LVBA_ERR_NOMEM : LVBA_ERR_DEVICE, "anchor clouds: %s", hipGetErrorString(e));
+    }
+    mark("compact");
+    *out = DevCloud{pts, n_all};
+    return LVBA_OK;
+}
+// alignment and merge of the run of windows [w0, w1): the anchor points into c.clouds[w0], the counts into the windows' infos
+int32_t stage_merge(WindowCall &c, int w0, int w1, hipStream_t s)
+{
+    const double tw = now_ms();
+    int G = 0;
+    for (int wi = w0; wi < w1; ++wi)
+        if (!c.res[(size_t)wi].info.skipped) { align_window(c, wi); ++G; }
+    if (G == 0) return LVBA_OK;
+    lvba::hvec<int64_t> count((size_t)(w1 - w0));
+    TRY(merge_run(c, w0, w1, s, &c.clouds[(size_t)w0], count.data()));
+    const double per = (now_ms() - tw) / G;
+    for (int wi = w0; wi < w1; ++wi) {
+        lvba_window_info &info = c.res[(size_t)wi].info;
+        if (info.skipped) continue;
+        info.n_anchor_points = count[(size_t)(wi - w0)];
+        info.merge_ms = per;
+    }
+    return LVBA_OK;
+}
+int32_t stage_merge_window(WindowCall &c, int wi, hipStream_t ws) { return stage_merge(c, wi, wi + 1, ws); }
+// ---- stage 3 for all windows at once, as stage 1.  False: one pass per window.
+bool stage_merge_joint(WindowCall &c)
+{
+    if (!joint_fits(c)) return false;
+    const int32_t rc = stage_merge(c, 0, c.n_win, c.s);
+    if (rc != LVBA_OK && timing_on("window")) fprintf(stderr, "[window_ba] joint merge not taken (rc %d): one pass per window\n", rc);
+    return rc == LVBA_OK;
+}
+
+// a stage over all windows, on a small pool of host threads (LVBA_WINDOW_THREADS, default 4; 1 = in the calling thread), each
+// with a stream of its own
+void run_stage(WindowCall &c, int32_t (*stage)(WindowCall &, int, hipStream_t))
+{
+    std::atomic<int> next{0};
+    lvba::hvec<char> visited((size_t)c.n_win, 0);
+    auto worker = [&](hipStream_t ws) {
+        for (int wi = next.fetch_add(1); wi < c.n_win; wi = next.fetch_add(1)) {
+            WinResult &R = c.res[(size_t)wi];
+            visited[(size_t)wi] = 1;
+            if (R.rc < 0) continue;
+            R.rc = stage(c, wi, ws);
+            if (R.rc < 0) R.err = lvba_last_error();
+        }
+    };
+    if (c.n_thr == 1) {
+        worker(c.s);
+        return;
+    }
+    struct Inhibit { Inhibit() { bs_graph_inhibit(+1); } ~Inhibit() { bs_graph_inhibit(-1); } } inhibit;
+    lvba::hvec<std::thread> pool;
+    for (int t = 0; t < c.n_thr; ++t)
+        pool.emplace_back([&, t]() {
+            if (!c.wstreams[(size_t)t] || hipSetDevice(c.sc->device) != hipSuccess) return;
+            worker(c.wstreams[(size_t)t]);
+            (void)hipStreamSynchronize(c.wstreams[(size_t)t]);
+        });
+    for (auto &th : pool) th.join();
+    for (int wi = 0; wi < c.n_win; ++wi) // a thread that could not get a stream leaves its windows untouched
+        if (!visited[(size_t)wi] && c.res[(size_t)wi].rc >= 0) {
+            WinResult &R = c.res[(size_t)wi];
+            R.rc = stage(c, wi, c.s);
+            if (R.rc < 0) R.err = lvba_last_error();
+        }
+}
+
 } // namespace
 
 extern "C" void lvba_window_default_opts(lvba_window_opts *o)
@@ -157,6 +632,35 @@ extern "C" void lvba_window_default_opts(lvba_window_opts *o)
     lvba_voxel_default_opts(&o->voxel);
     o->voxel.voxel_size = 0.5; // stage1_root_voxel_size_, include/dataset_io.h:76
     lvba_balm_default_opts(&o->lm);
+}
+
+int32_t lvba::scans_build(int32_t device, int32_t n_frames, const int64_t *count, float *adopt, const DevCloud *src, int n_src,
+                          lvba_scans_s **out)
+{
+    *out = nullptr;
+    lvba_scans_s *sc = new (std::nothrow) lvba_scans_s();
+    hipError_t e = hipSetDevice(device);
+    if (!sc) {
+        if (adopt && e == hipSuccess) (void)hipFree(adopt);
+        return lvba_fail(LVBA_ERR_NOMEM, "host allocation failed");
+    }
+    sc->device = device;
+    sc->n_frames = n_frames;
+    sc->d_pts = adopt;
+    sc->frame_off.assign((size_t)n_frames + 1, 0);
+    for (int f = 0; f < n_frames; ++f) sc->frame_off[(size_t)f + 1] = sc->frame_off[(size_t)f] + count[f];
+    const int64_t P = sc->frame_off[(size_t)n_frames];
+    if (e == hipSuccess && !adopt) e = hipMalloc((void **)&sc->d_pts, P ? 12 * (size_t)P : 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&sc->d_frame_off, 8 * ((size_t)n_frames + 1));
+    for (int64_t k = 0, at = 0; k < n_src && e == hipSuccess; at += src[k++].n)
+        if (src[k].n > 0) e = hipMemcpy(sc->d_pts + 3 * at, src[k].d, 12 * (size_t)src[k].n, hipMemcpyDefault); // (across devices: UVA)
+    if (e == hipSuccess) e = lvba::copy_h2d(sc->d_frame_off, sc->frame_off.data(), 8 * ((size_t)n_frames + 1));
+    if (e != hipSuccess) {
+        lvba_scans_destroy(sc);
+        return lvba_fail(e == hipErrorOutOfMemory ? LVBA_ERR_NOMEM : LVBA_ERR_DEVICE, "scan set: %s", hipGetErrorString(e));
+    }
+    *out = sc;
+    return LVBA_OK;
 }
 
 extern "C" int32_t lvba_scans_info(lvba_scans_t sc, int32_t *n_frames, int64_t *frame_count)
@@ -185,530 +689,35 @@ extern "C" int32_t lvba_window_ba(lvba_scans_t sc, const double *poses, const lv
     if (anchor_scans) *anchor_scans = nullptr;
     if (!sc || !poses || !rel_poses || !anchor_index || !anchor_poses || !n_anchors || !anchor_scans)
         return lvba_fail(LVBA_ERR_ARG, "null argument");
-    lvba_window_opts o;
-    lvba_window_default_opts(&o);
-    if (opts) o = *opts;
-    if (o.window_size < 1) return lvba_fail(LVBA_ERR_ARG, "window_size must be >= 1");
+    WindowCall c;
+    lvba_window_default_opts(&c.o);
+    if (opts) c.o = *opts;
+    if (c.o.window_size < 1) return lvba_fail(LVBA_ERR_ARG, "window_size must be >= 1");
     HIPCHK(hipSetDevice(sc->device));
-    const int n = sc->n_frames, w = o.window_size;
+    c.sc = sc; c.poses = poses;
+    c.n = sc->n_frames; c.w = c.o.window_size; c.n_win = (c.n + c.w - 1) / c.w;
     hipStream_t s = nullptr;
     HIPCHK(lvba::StreamCache::get().acquire(&s));
-    struct StreamGuard { hipStream_t s; ~StreamGuard() { lvba::StreamCache::get().release(s); } } sguard{s};
+    c.s = s;
 
     static const double I12[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
-    for (int i = 0; i < n; ++i) { // rel_poses_to_anchor_.assign(total, IMUST()), anchor_index -1 (:338-339)
+    for (int i = 0; i < c.n; ++i) { // rel_poses_to_anchor_.assign(total, IMUST()), anchor_index -1 (:338-339)
         memcpy(rel_poses + 12 * i, I12, sizeof I12);
         anchor_index[i] = -1;
     }
-    if (window_poses) memcpy(window_poses, poses, 96 * (size_t)n);
-
-    struct AnchorCloud { float *d; int64_t n; };
-    lvba::hvec<AnchorCloud> clouds;
-    auto free_clouds = [&]() { for (auto &c : clouds) DevicePool::get().free(c.d); clouds.clear(); };
-    // One window = map -> problem -> LM -> anchor cloud; windows are independent (src/lvba_system.cpp:232-302 runs them one
-    // after the other).  Three stages:
-    //   1. voxel map of every window (a few host threads, each with its own stream: a single map build leaves the GPU idle
-    //      most of the time -- launch and synchronisation latency);
-    //   2. the LM refinements of ALL windows in lock-step as one grouped problem (lvba_balm_set_groups /
-    //      lvba_balm_refine_groups: one evaluation, one band factorisation with a damping value per window, one cost pass per
-    //      iteration for all windows; every window keeps its own LM state).  lm_mode = 1, a single
-    //      window, or a broken pivot in the joint factorisation: one window at a time, as before;
-    //   3. alignment, relative poses, anchor merge + down-sampling: all windows in one pass (stage_finish_joint), or per window
-    //      on the host threads again.
-    // Results are assembled in window order below.
-    struct WinResult { int32_t rc = LVBA_OK; std::string err; lvba_window_info info{}; lvba::hvec<double> x, rel; float *d_out = nullptr; int64_t n_out = 0;
-                       lvba_voxmap_t map = nullptr; bool refined = false; };
-    const int n_win = (n + w - 1) / w;
-    lvba::hvec<WinResult> results((size_t)n_win);
-    auto win_range = [&](int wi, int &start, int &cw) { start = wi * w; cw = std::min(w, n - start); };
-    lvba_voxmap_t joint_map = nullptr; // stage 1 as ONE map of all windows (stage_map_joint); the windows' maps are views into it
-    // ---- stage 1: the voxel map at the odometry poses (:247-257) and the skip rule (:258-262)
-    auto stage_map = [&](int wi, hipStream_t ws, WinResult &R) -> int32_t {
-        int start, cw;
-        win_range(wi, start, cw);
-        lvba_window_info &info = R.info;
-        info = lvba_window_info{};
-        info.start = start; info.n_frames = cw; info.anchor = -1;
-        const double *x_odom = poses + 12 * (int64_t)start;
-        R.x.assign(x_odom, x_odom + 12 * (size_t)cw);
-        if (o.merge_only) return LVBA_OK;
-        const double tw = now_ms();
-        int32_t rc = lvba_voxmap_build_scans_on(sc, start, cw, x_odom, &o.voxel, ws, &R.map); // on the worker's stream, which outlives the map
-        if (rc != LVBA_OK) return rc;
-        lvba_voxmap_info_t mi;
-        lvba_voxmap_info(R.map, &mi);
-        info.n_voxels = mi.n_voxels; info.n_factors = mi.n_factors;
-        info.map_ms = now_ms() - tw;
-        if (mi.n_voxels < 3 * (int64_t)cw) { // :258-262
-            info.skipped = 1;
-            lvba_voxmap_destroy(R.map);
-            R.map = nullptr;
-        }
-        return LVBA_OK;
-    };
-    // ---- stage 2, one window at a time: damping_iter on the window's own problem (:264)
-    auto stage_lm_single = [&](int wi, hipStream_t, WinResult &R) -> int32_t {
-        if (!R.map || R.refined) return LVBA_OK;
-        lvba_window_info &info = R.info;
-        double tw = now_ms();
-        lvba_balm_t b = nullptr;
-        int32_t rc = lvba_voxmap_to_balm(R.map, &b);
-        lvba_voxmap_destroy(R.map);
-        R.map = nullptr;
-        if (rc != LVBA_OK) return rc;
-        lvba::hvec<lvba_lm_trace> trace((size_t)std::max(1, o.lm.max_iter));
-        int32_t nt = 0;
-        lvba_balm_info_t bi;
-        lvba_balm_info(b, &bi); // forces the one-off problem set-up (ordering, pair lists) so that it is timed apart
-        info.setup_ms = now_ms() - tw;
-        rc = lvba_balm_refine(b, R.x.data(), &o.lm, trace.data(), &nt);
-        lvba_balm_destroy(b);
-        if (rc < 0) return rc;
-        info.lm_status = rc; info.n_iter = nt;
-        if (nt > 0) {
-            info.cost_first = trace[0].residual1;
-            info.cost_last = trace[nt - 1].accepted ? trace[nt - 1].residual2 : trace[nt - 1].residual1;
-        }
-        info.solve_ms = now_ms() - tw;
-        R.refined = true;
-        (void)wi;
-        return LVBA_OK;
-    };
-    // ---- stage 2, all windows at once.  Returns LVBA_OK with `done` = false when the windows have to go one by one.
-    auto stage_lm_batched = [&](bool &done) -> int32_t {
-        done = false;
-        lvba::hvec<int> live;
-        for (int wi = 0; wi < n_win; ++wi)
-            if (results[(size_t)wi].map) live.push_back(wi);
-        if (live.size() < 2) return LVBA_OK;
-        const double t0 = now_ms();
-        const int G = (int)live.size();
-        lvba::hvec<int32_t> pose_off((size_t)G + 1, 0);
-        lvba::hvec<int64_t> vox_off((size_t)G + 1, 0), fac_off((size_t)G + 1, 0);
-        for (int k = 0; k < G; ++k) {
-            const WinResult &R = results[(size_t)live[(size_t)k]];
-            pose_off[(size_t)k + 1] = pose_off[(size_t)k] + R.info.n_frames;
-            vox_off[(size_t)k + 1] = vox_off[(size_t)k] + R.info.n_voxels;
-            fac_off[(size_t)k + 1] = fac_off[(size_t)k] + R.info.n_factors;
-        }
-        const int64_t V = vox_off[(size_t)G], F = fac_off[(size_t)G];
-        if (F >= ((int64_t)1 << 31)) return LVBA_OK; // too large for one handle: one by one
-        lvba::hvec<int64_t> off((size_t)V + 1, 0);
-        lvba::hvec<int32_t> idx((size_t)F);
-        lvba::hvec<double> x(12 * (size_t)pose_off[(size_t)G]);
-        DevBuf d_clu(s);
-        HIPCHK(d_clu.alloc(80 * (size_t)F));
-        lvba::hvec<int64_t> joff; // with a joint map: its whole CSR structure in ONE pair of copies instead of two per window
-        lvba::hvec<int32_t> jidx;
-        if (joint_map) {
-            lvba_voxmap_info_t ji;
-            lvba_voxmap_info(joint_map, &ji);
-            joff.resize((size_t)ji.n_voxels + 1); jidx.resize((size_t)std::max<int64_t>(ji.n_factors, 1));
-            TRY(lvba_voxmap_export(joint_map, joff.data(), jidx.data(), nullptr, nullptr));
-        }
-        for (int k = 0; k < G; ++k) {
-            const WinResult &R = results[(size_t)live[(size_t)k]];
-            const int64_t v0 = vox_off[(size_t)k], f0 = fac_off[(size_t)k], nv = R.info.n_voxels, nf = R.info.n_factors;
-            lvba::hvec<int64_t> o1((size_t)nv + 1);
-            if (joint_map) {
-                int64_t jv0, jv1, jf0, jf1;
-                TRY(lvba_voxmap_window_range(joint_map, live[(size_t)k], &jv0, &jv1, &jf0, &jf1));
-                memcpy(o1.data(), joff.data() + jv0, 8 * ((size_t)nv + 1));
-                memcpy(idx.data() + f0, jidx.data() + jf0, 4 * (size_t)nf);
-            } else
-                TRY(lvba_voxmap_export(R.map, o1.data(), idx.data() + f0, nullptr, nullptr)); // CSR structure to the host, clusters stay in HBM
-            for (int64_t a = 0; a <= nv; ++a) off[(size_t)(v0 + a)] = f0 + (o1[(size_t)a] - o1[0]);
-            for (int64_t f = f0; f < f0 + nf; ++f) idx[(size_t)f] += pose_off[(size_t)k];
-            HIPCHK(hipMemcpyAsync(d_clu.as<double>() + 10 * f0, lvba_voxmap_clusters(R.map), 80 * (size_t)nf, hipMemcpyDeviceToDevice, s));
-            memcpy(x.data() + 12 * (size_t)pose_off[(size_t)k], R.x.data(), 96 * (size_t)R.info.n_frames);
-        }
-        HIPCHK(hipStreamSynchronize(s));
-        const bool tm = timing_on("window");
-        double tk = now_ms();
-        auto mk = [&](const char *what) { if (tm) { const double t = now_ms(); fprintf(stderr, "[window_ba LM] %-16s %.3f ms\n", what, t - tk); tk = t; } };
-        if (tm) fprintf(stderr, "[window_ba LM] %-16s %.3f ms\n", "export + concat", tk - t0);
-        lvba_balm_t b = nullptr;
-        TRY(balm_create_dev_trusted(pose_off[(size_t)G], V, off.data(), idx.data(), d_clu.as<double>(), sc->device, &b));
-        struct Guard { lvba_balm_t b; ~Guard() { if (b) lvba_balm_destroy(b); } } guard{b};
-        mk("create");
-        TRY(lvba_balm_set_groups(b, G, pose_off.data(), vox_off.data()));
-        mk("set_groups");
-        lvba_balm_info_t bi;
-        TRY(lvba_balm_info(b, &bi)); // the one-off set-up, timed apart
-        mk("set-up");
-        const double t1 = now_ms();
-        lvba::hvec<int32_t> n_iter((size_t)G), status((size_t)G);
-        lvba::hvec<double> first((size_t)G), last((size_t)G);
-        const int32_t rc = lvba_balm_refine_groups(b, x.data(), &o.lm, n_iter.data(), status.data(), first.data(), last.data());
-        if (rc == LVBA_NUM_FACTORIZATION) return LVBA_OK; // the windows are not independent in a broken factorisation: one by one
-        if (rc < 0) return rc;
-        const double t2 = now_ms();
-        mk("refine_groups");
-        for (int k = 0; k < G; ++k) {
-            WinResult &R = results[(size_t)live[(size_t)k]];
-            memcpy(R.x.data(), x.data() + 12 * (size_t)pose_off[(size_t)k], 96 * (size_t)R.info.n_frames);
-            R.info.n_iter = n_iter[(size_t)k]; R.info.lm_status = status[(size_t)k];
-            R.info.cost_first = first[(size_t)k]; R.info.cost_last = last[(size_t)k];
-            R.info.setup_ms = (t1 - t0) / G; R.info.solve_ms = (t2 - t0) / G; // the joint problem's times, shared out evenly
-            R.refined = true;
-            lvba_voxmap_destroy(R.map);
-            R.map = nullptr;
-        }
-        mk("results, maps freed");
-        lvba_balm_destroy(guard.b);
-        guard.b = nullptr;
-        mk("handle destroyed");
-        done = true;
-        return LVBA_OK;
-    };
-    // ---- stage 3: alignment (:268-279), relative poses (:284-299), merge + down_sampling_voxel2 on the device
-    auto align_window = [&](int wi, WinResult &R) {
-        int start, cw;
-        win_range(wi, start, cw);
-        const double *x_odom = poses + 12 * (int64_t)start;
-        lvba::hvec<double> &x = R.x;
-        lvba::hvec<double> &rel = R.rel;
-        rel.assign(12 * (size_t)cw, 0.0);
-        const double *Ro0 = x_odom, *po0 = x_odom + 9;
-        double R_align[9], p_align[3] = {0, 0, 0};
-        if (o.use_rel) {
-            mat3_mulT(Ro0, x.data(), R_align);
-            for (int r = 0; r < 3; ++r)
-                p_align[r] = po0[r] - (R_align[3 * r] * x[9] + R_align[3 * r + 1] * x[10] + R_align[3 * r + 2] * x[11]);
-        }
-        for (int j = 0; j < cw; ++j) {
-            double Ra[9], pa[3];
-            if (o.use_rel) {
-                const double *Rj = x.data() + 12 * j, *pj = Rj + 9;
-                mat3_mul(R_align, Rj, Ra);
-                for (int r = 0; r < 3; ++r)
-                    pa[r] = R_align[3 * r] * pj[0] + R_align[3 * r + 1] * pj[1] + R_align[3 * r + 2] * pj[2] + p_align[r];
-            } else {
-                memcpy(Ra, x_odom + 12 * j, 72);
-                memcpy(pa, x_odom + 12 * j + 9, 24);
-            }
-            double *rj = rel.data() + 12 * j;
-            mat3T_mul(Ro0, Ra, rj);
-            const double d[3] = {pa[0] - po0[0], pa[1] - po0[1], pa[2] - po0[2]};
-            for (int r = 0; r < 3; ++r) rj[9 + r] = Ro0[r] * d[0] + Ro0[3 + r] * d[1] + Ro0[6 + r] * d[2];
-        }
-    };
-    auto stage_finish = [&](int wi, hipStream_t s, WinResult &R) -> int32_t {
-        int start, cw;
-        win_range(wi, start, cw);
-        lvba_window_info &info = R.info;
-        if (info.skipped) return LVBA_OK;
-        double tw = now_ms();
-        align_window(wi, R);
-        lvba::hvec<double> &rel = R.rel;
-        // merge + down_sampling_voxel2 on the device
-        const int64_t p_begin = sc->frame_off[start], P = sc->frame_off[start + cw] - p_begin;
-        const bool down = o.anchor_leaf >= 0.001 && P > 0; // tools.hpp:303
-        float *d_out = nullptr;
-        int64_t n_out = P;
-        if (P > 0) {
-            DevBuf d_rel(s), merged(s), key(s), d2(s), idx(s), d_err(s);
-            HIPCHK(d_rel.alloc(96 * (size_t)cw)); HIPCHK(merged.alloc(12 * (size_t)P)); HIPCHK(d_err.alloc(28));
-            HIPCHK(lvba::copy_h2d(d_rel.p, rel.data(), 96 * (size_t)cw)); // (pageable source: synchronous copy, voxelize.hip)
-            int h_err[7] = {0}; // [0] error flag, [1..6] range of the biased key components
-            DevBuf d_part(s);
-            const int64_t n_slots = key_range_slots(P, 256);
-            if (down) HIPCHK(d_part.alloc(24 * (size_t)n_slots));
-            HIPCHK(hipMemsetAsync(d_err.p, 0, 28, s));
-            if (down) { HIPCHK(key.alloc(8 * (size_t)P)); HIPCHK(d2.alloc(8 * (size_t)P)); HIPCHK(idx.alloc(4 * (size_t)P)); }
-            wba_merge_kernel<<<grid_for(P, 256), 256, 0, s>>>(P, sc->d_pts + 3 * p_begin, sc->d_frame_off + start, cw, d_rel.as<double>(),
-                                                              o.anchor_leaf, merged.as<float>(), down ? key.as<uint64_t>() : nullptr,
-                                                              d2.as<double>(), idx.as<uint32_t>(), d_err.as<int>(), d_part.as<int>());
-            HIPCHK(hipGetLastError());
-            if (down) {
-                key_range_reduce_kernel<<<key_range_reduce_grid(n_slots), 256, 0, s>>>(n_slots, d_part.as<int>(), d_err.as<int>() + 1);
-                HIPCHK(hipGetLastError());
-            }
-            if (!down) {
-                HIPCHK(hipStreamSynchronize(s));
-                d_out = (float *)merged.release();
-            } else {
-                HIPCHK(hipStreamSynchronize(s));
-                HIPCHK(lvba::copy_d2h(h_err, d_err.p, 28));
-                if (h_err[0]) { return lvba_fail(LVBA_ERR_ARG, "window %d: a merged point is non-finite or outside +-2^20 anchor leaves", wi); }
-                DevBuf key_s(s), order(s), flag(s), excl(s), pick(s);
-                HIPCHK(key_s.alloc(8 * (size_t)P)); HIPCHK(order.alloc(4 * (size_t)P)); HIPCHK(flag.alloc(4 * ((size_t)P + 1)));
-                HIPCHK(excl.alloc(4 * ((size_t)P + 1))); HIPCHK(pick.alloc(4 * (size_t)P));
-                // the sort runs on the bits of the leaf key that vary (voxel_internal.h); run leaders only compare sorted keys for
-                // equality, so the re-packed ones serve as they are
-                const KeyPack kp = key_pack_of(h_err + 1);
-                if (kp.total <= 32) {
-                    DevBuf k32(s);
-                    HIPCHK(k32.alloc(4 * (size_t)P));
-                    key_compress_kernel<uint32_t><<<grid_for(P, 256), 256, 0, s>>>(P, key.as<uint64_t>(), kp, k32.as<uint32_t>());
-                    HIPCHK(hipGetLastError());
-                    TRY(sort_pairs(s, k32.as<uint32_t>(), key_s.as<uint32_t>(), idx.as<uint32_t>(), order.as<uint32_t>(), (size_t)P, (unsigned)kp.total));
-                    wba_pick_kernel<uint32_t><<<grid_for(P, 256), 256, 0, s>>>(P, key_s.as<uint32_t>(), order.as<uint32_t>(), d2.as<double>(),
-                                                                               flag.as<uint32_t>(), pick.as<uint32_t>());
-                } else {
-                    key_compress_kernel<uint64_t><<<grid_for(P, 256), 256, 0, s>>>(P, key.as<uint64_t>(), kp, key.as<uint64_t>());
-                    HIPCHK(hipGetLastError());
-                    const unsigned bits = (unsigned)kp.total;
-                    TRY(sort_pairs(s, key.as<uint64_t>(), key_s.as<uint64_t>(), idx.as<uint32_t>(), order.as<uint32_t>(), (size_t)P, bits));
-                    wba_pick_kernel<uint64_t><<<grid_for(P, 256), 256, 0, s>>>(P, key_s.as<uint64_t>(), order.as<uint32_t>(), d2.as<double>(),
-                                                                               flag.as<uint32_t>(), pick.as<uint32_t>());
-                }
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipMemsetAsync(flag.as<uint32_t>() + P, 0, 4, s));
-                TRY(scan_excl<uint32_t>(s, flag.as<uint32_t>(), excl.as<uint32_t>(), (size_t)P + 1));
-                uint32_t cnt = 0;
-                HIPCHK(lvba::copy_d2h(&cnt, excl.as<uint32_t>() + P, 4));
-                n_out = cnt;
-                void *raw = nullptr;
-                HIPCHK(DevicePool::get().alloc(&raw, 12 * (size_t)std::max<int64_t>(n_out, 1)));
-                d_out = (float *)raw;
-                wba_compact_kernel<<<grid_for(P, 256), 256, 0, s>>>(P, flag.as<uint32_t>(), excl.as<uint32_t>(), pick.as<uint32_t>(),
-                                                                    merged.as<float>(), d_out);
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipStreamSynchronize(s));
-            }
-        }
-        info.merge_ms = now_ms() - tw;
-        info.n_anchor_points = n_out;
-        R.d_out = d_out; R.n_out = n_out;
-        return LVBA_OK;
-    };
-    // a stage over all windows, on a small pool of host threads (LVBA_WINDOW_THREADS, default 4; 1 = in the calling thread), each
-    // with a stream of its own; the streams live until the call returns (the maps of stage 1 work on them)
-    int n_thr = 4;
-    if (const char *e = getenv("LVBA_WINDOW_THREADS")) n_thr = atoi(e);
-    n_thr = std::max(1, std::min(n_thr, n_win));
-    lvba::hvec<hipStream_t> wstreams;
-    struct StreamsGuard { lvba::hvec<hipStream_t> &v; ~StreamsGuard() { for (hipStream_t q : v) if (q) lvba::StreamCache::get().release(q); } } wguard{wstreams};
-    if (n_thr > 1) {
-        wstreams.assign((size_t)n_thr, nullptr);
-        for (auto &q : wstreams)
+    if (window_poses) memcpy(window_poses, poses, 96 * (size_t)c.n);
+    c.rel.assign(rel_poses, rel_poses + 12 * (size_t)c.n);
+    c.res.resize((size_t)c.n_win);
+    c.clouds.assign((size_t)c.n_win, DevCloud{nullptr, 0});
+    c.n_thr = 4;
+    if (const char *e = getenv("LVBA_WINDOW_THREADS")) c.n_thr = atoi(e);
+    c.n_thr = std::max(1, std::min(c.n_thr, c.n_win));
+    if (c.n_thr > 1) {
+        c.wstreams.assign((size_t)c.n_thr, nullptr);
+        for (auto &q : c.wstreams)
             if (lvba::StreamCache::get().acquire(&q) != hipSuccess) { (void)hipGetLastError(); q = nullptr; }
     }
-    auto run_stage = [&](const std::function<int32_t(int, hipStream_t, WinResult &)> &stage) {
-        std::atomic<int> next{0};
-        lvba::hvec<char> visited((size_t)n_win, 0);
-        auto worker = [&](hipStream_t ws) {
-            for (int wi = next.fetch_add(1); wi < n_win; wi = next.fetch_add(1)) {
-                WinResult &R = results[(size_t)wi];
-                visited[(size_t)wi] = 1;
-                if (R.rc < 0) continue;
-                R.rc = stage(wi, ws, R);
-                if (R.rc < 0) R.err = lvba_last_error();
-            }
-        };
-        if (n_thr == 1) {
-            worker(s);
-            return;
-        }
-        struct Inhibit { Inhibit() { bs_graph_inhibit(+1); } ~Inhibit() { bs_graph_inhibit(-1); } } inhibit;
-        lvba::hvec<std::thread> pool;
-        for (int t = 0; t < n_thr; ++t)
-            pool.emplace_back([&, t]() {
-                if (!wstreams[(size_t)t] || hipSetDevice(sc->device) != hipSuccess) return;
-                worker(wstreams[(size_t)t]);
-                (void)hipStreamSynchronize(wstreams[(size_t)t]);
-            });
-        for (auto &th : pool) th.join();
-        for (int wi = 0; wi < n_win; ++wi) // a thread that could not get a stream leaves its windows untouched
-            if (!visited[(size_t)wi] && results[(size_t)wi].rc >= 0) {
-                WinResult &R = results[(size_t)wi];
-                R.rc = stage(wi, s, R);
-                if (R.rc < 0) R.err = lvba_last_error();
-            }
-    };
-    auto free_maps = [&]() {
-        for (auto &q : results) if (q.map) { lvba_voxmap_destroy(q.map); q.map = nullptr; }
-        if (joint_map) { lvba_voxmap_destroy(joint_map); joint_map = nullptr; }
-    };
-    // ---- stage 1 for all windows at once: a root voxel is (window, key), so one sort and one pass of every kernel of the map build
-    // serve every window (the per-window builds are dozens of dependent launches and a dozen host round trips EACH); a window's
-    // part of the joint map is bit for bit what its own build gives (tests/test_gpu_window.py).  LVBA_WINDOW_JOINT_MAP=0: off.
-    // The joint build holds keys, records, indices and sort temporaries of ALL frames at once (~90 bytes per point, where a
-    // per-window build needs one window's worth): it is only tried when that fits the device's free memory with room to spare --
-    // a long sequence goes window by window instead of running into hipErrorOutOfMemory first.
-    auto stage_map_joint = [&]() -> bool {
-        static const bool on = [] { const char *e = getenv("LVBA_WINDOW_JOINT_MAP"); return !(e && !strcmp(e, "0")); }();
-        if (!on || o.merge_only || n_win < 2) return false;
-        {
-            size_t free_b = 0, total_b = 0;
-            const int64_t P_all = sc->frame_off[(size_t)n] - sc->frame_off[0];
-            if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return false; }
-            if ((double)P_all * 96.0 > 0.5 * (double)free_b) {
-                if (timing_on("window"))
-                    fprintf(stderr, "[window_ba] joint voxel map skipped: %lld points x ~96 B against %.1f GB free -> one map per window\n",
-                            (long long)P_all, (double)free_b / 1e9);
-                return false;
-            }
-        }
-        const double tw = now_ms();
-        if (lvba_voxmap_build_scans_joint(sc, 0, n, w, poses, &o.voxel, s, &joint_map) != LVBA_OK) {
-            joint_map = nullptr; // (too many key + window bits, a bad point, ...: the per-window builds say what it is)
-            return false;
-        }
-        const double per = (now_ms() - tw) / n_win;
-        for (int wi = 0; wi < n_win; ++wi) {
-            WinResult &R = results[(size_t)wi];
-            int start, cw;
-            win_range(wi, start, cw);
-            R.info = lvba_window_info{};
-            R.info.start = start; R.info.n_frames = cw; R.info.anchor = -1;
-            R.x.assign(poses + 12 * (int64_t)start, poses + 12 * (int64_t)(start + cw));
-            R.rc = lvba_voxmap_window_view(joint_map, wi, &R.map);
-            if (R.rc != LVBA_OK) { R.err = lvba_last_error(); continue; }
-            lvba_voxmap_info_t mi;
-            lvba_voxmap_info(R.map, &mi);
-            R.info.n_voxels = mi.n_voxels; R.info.n_factors = mi.n_factors;
-            R.info.map_ms = per;
-            if (mi.n_voxels < 3 * (int64_t)cw) { // :258-262
-                R.info.skipped = 1;
-                lvba_voxmap_destroy(R.map);
-                R.map = nullptr;
-            }
-        }
-        return true;
-    };
-    // ---- stage 3 for all windows at once, as stage 1: the points of every window moved by their frames' relative poses in one
-    // launch, ONE sort by (window, leaf key), one pick / scan / compaction -- straight into the anchor scan set's point array, whose
-    // frames are the windows' runs of the compacted sequence (their bounds in the SORTED sequence are the windows' point counts:
-    // known on the host).  A window's anchor cloud is bit for bit what its own pass gives: the same fp32 points, the same leaf keys,
-    // the same order inside a leaf (the sort is stable and a window's points keep their order), the leaves in key order.  Per window
-    // the stage was seventeen launches and five waits on the host.  Same switch and the same memory rule as the joint map.
-    float *joint_pts = nullptr; // [anchor points of all windows][3], allocated like a scan set's d_pts
-    auto stage_finish_joint = [&]() -> bool {
-        static const bool on = [] { const char *e = getenv("LVBA_WINDOW_JOINT_MAP"); return !(e && !strcmp(e, "0")); }();
-        const int64_t p_begin = sc->frame_off[0], P = sc->frame_off[(size_t)n] - p_begin;
-        if (!on || n_win < 2 || !(o.anchor_leaf >= 0.001) || P <= 0 || P >= ((int64_t)1 << 32)) return false;
-        {
-            size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return false; }
-            if ((double)P * 96.0 > 0.5 * (double)free_b) return false;
-        }
-        const double tw = now_ms();
-        // codes, relative poses of all frames, the windows' bounds in the sorted sequence
-        lvba::hvec<uint32_t> code((size_t)n_win);
-        lvba::hvec<int64_t> at;
-        lvba::hvec<double> rel_all(12 * (size_t)n);
-        int G = 0;
-        for (int wi = 0; wi < n_win; ++wi)
-            if (!results[(size_t)wi].info.skipped) ++G;
-        if (G == 0) return false;
-        at.push_back(0);
-        for (int wi = 0, g = 0; wi < n_win; ++wi) {
-            WinResult &R = results[(size_t)wi];
-            int start, cw;
-            win_range(wi, start, cw);
-            if (R.info.skipped) {
-                code[(size_t)wi] = (uint32_t)G;
-                for (int j = 0; j < cw; ++j) memcpy(rel_all.data() + 12 * (size_t)(start + j), I12, sizeof I12);
-                continue;
-            }
-            code[(size_t)wi] = (uint32_t)g++;
-            align_window(wi, R);
-            memcpy(rel_all.data() + 12 * (size_t)start, R.rel.data(), 96 * (size_t)cw);
-            at.push_back(at.back() + (sc->frame_off[(size_t)(start + cw)] - sc->frame_off[(size_t)start]));
-        }
-        const int64_t P_live = at.back();
-        const int cbits = G < n_win ? 32 - __builtin_clz((unsigned)G) : (G > 1 ? 32 - __builtin_clz((unsigned)(G - 1)) : 0);
-        const bool jt = timing_on("window");
-        double tj = now_ms();
-        auto jm = [&](const char *what) { // (LVBA_TIMING: waits for the stream at every mark)
-            if (!jt) return;
-            (void)hipStreamSynchronize(s);
-            const double t = now_ms();
-            fprintf(stderr, "[window_ba merge] %-18s %.3f ms\n", what, t - tj);
-            tj = t;
-        };
-        auto body = [&]() -> int32_t {
-            jm("align (host)");
-            DevBuf d_rel(s), d_code(s), d_at(s), d_cnt(s), merged(s), key(s), d2(s), idx(s), d_err(s), d_part(s);
-            HIPCHK(d_rel.alloc(96 * (size_t)n)); HIPCHK(d_code.alloc(4 * (size_t)n_win)); HIPCHK(d_at.alloc(8 * ((size_t)G + 1)));
-            HIPCHK(d_cnt.alloc(4 * ((size_t)G + 1))); HIPCHK(merged.alloc(12 * (size_t)P)); HIPCHK(d_err.alloc(28));
-            HIPCHK(key.alloc(8 * (size_t)P)); HIPCHK(d2.alloc(8 * (size_t)P)); HIPCHK(idx.alloc(4 * (size_t)P));
-            const int64_t n_slots = key_range_slots(P, 256);
-            HIPCHK(d_part.alloc(24 * (size_t)n_slots));
-            HIPCHK(lvba::copy_h2d(d_rel.p, rel_all.data(), 96 * (size_t)n)); // (pageable sources: synchronous copies)
-            HIPCHK(lvba::copy_h2d(d_code.p, code.data(), 4 * (size_t)n_win));
-            HIPCHK(lvba::copy_h2d(d_at.p, at.data(), 8 * ((size_t)G + 1)));
-            HIPCHK(hipMemsetAsync(d_err.p, 0, 28, s));
-            jm("alloc + tables");
-            wba_merge_kernel<<<grid_for(P, 256), 256, 0, s>>>(P, sc->d_pts + 3 * p_begin, sc->d_frame_off, n, d_rel.as<double>(), o.anchor_leaf,
-                                                              merged.as<float>(), key.as<uint64_t>(), d2.as<double>(), idx.as<uint32_t>(),
-                                                              d_err.as<int>(), d_part.as<int>());
-            HIPCHK(hipGetLastError());
-            key_range_reduce_kernel<<<key_range_reduce_grid(n_slots), 256, 0, s>>>(n_slots, d_part.as<int>(), d_err.as<int>() + 1);
-            HIPCHK(hipGetLastError());
-            int h_err[7] = {0};
-            HIPCHK(hipStreamSynchronize(s));
-            HIPCHK(lvba::copy_d2h(h_err, d_err.p, 28));
-            if (h_err[0]) return LVBA_ERR_ARG; // (the per-window passes name the window)
-            jm("merge + range");
-            const KeyPack kp = key_pack_of(h_err + 1);
-            const unsigned bits = (unsigned)(kp.total + cbits);
-            if (bits > 64) return LVBA_ERR_UNSUPPORTED;
-            DevBuf key_s(s), order(s), flag(s), excl(s), pick(s);
-            HIPCHK(key_s.alloc(8 * (size_t)P)); HIPCHK(order.alloc(4 * (size_t)P)); HIPCHK(flag.alloc(4 * ((size_t)P_live + 1)));
-            HIPCHK(excl.alloc(4 * ((size_t)P_live + 1))); HIPCHK(pick.alloc(4 * (size_t)std::max<int64_t>(P_live, 1)));
-            if (bits <= 32) {
-                DevBuf k32(s);
-                HIPCHK(k32.alloc(4 * (size_t)P));
-                wba_compress_win_kernel<uint32_t><<<grid_for(P, 256), 256, 0, s>>>(P, key.as<uint64_t>(), sc->d_frame_off, n, w, d_code.as<uint32_t>(),
-                                                                                   kp, k32.as<uint32_t>());
-                HIPCHK(hipGetLastError());
-                TRY(sort_pairs(s, k32.as<uint32_t>(), key_s.as<uint32_t>(), idx.as<uint32_t>(), order.as<uint32_t>(), (size_t)P, bits));
-                if (P_live > 0)
-                    wba_pick_kernel<uint32_t><<<grid_for(P_live, 256), 256, 0, s>>>(P_live, key_s.as<uint32_t>(), order.as<uint32_t>(), d2.as<double>(),
-                                                                                    flag.as<uint32_t>(), pick.as<uint32_t>());
-            } else {
-                wba_compress_win_kernel<uint64_t><<<grid_for(P, 256), 256, 0, s>>>(P, key.as<uint64_t>(), sc->d_frame_off, n, w, d_code.as<uint32_t>(),
-                                                                                   kp, key.as<uint64_t>());
-                HIPCHK(hipGetLastError());
-                TRY(sort_pairs(s, key.as<uint64_t>(), key_s.as<uint64_t>(), idx.as<uint32_t>(), order.as<uint32_t>(), (size_t)P, bits));
-                if (P_live > 0)
-                    wba_pick_kernel<uint64_t><<<grid_for(P_live, 256), 256, 0, s>>>(P_live, key_s.as<uint64_t>(), order.as<uint32_t>(), d2.as<double>(),
-                                                                                    flag.as<uint32_t>(), pick.as<uint32_t>());
-            }
-            HIPCHK(hipGetLastError());
-            jm("sort + pick");
-            HIPCHK(hipMemsetAsync(flag.as<uint32_t>() + P_live, 0, 4, s));
-            TRY(scan_excl<uint32_t>(s, flag.as<uint32_t>(), excl.as<uint32_t>(), (size_t)P_live + 1));
-            wba_bounds_kernel<<<grid_for(G + 1, 256), 256, 0, s>>>(G + 1, d_at.as<int64_t>(), excl.as<uint32_t>(), d_cnt.as<uint32_t>());
-            HIPCHK(hipGetLastError());
-            lvba::hvec<uint32_t> cnt((size_t)G + 1);
-            HIPCHK(hipStreamSynchronize(s));
-            HIPCHK(lvba::copy_d2h(cnt.data(), d_cnt.p, 4 * ((size_t)G + 1)));
-            const int64_t n_all = cnt[(size_t)G];
-            jm("scan + counts");
-            hipError_t e = hipMalloc((void **)&joint_pts, n_all ? 12 * (size_t)n_all : 8);
-            if (e != hipSuccess) { (void)hipGetLastError(); joint_pts = nullptr; return LVBA_ERR_NOMEM; }
-            jm("hipMalloc (cloud)");
-            if (P_live > 0) {
-                wba_compact_kernel<<<grid_for(P_live, 256), 256, 0, s>>>(P_live, flag.as<uint32_t>(), excl.as<uint32_t>(), pick.as<uint32_t>(),
-                                                                         merged.as<float>(), joint_pts);
-                HIPCHK(hipGetLastError());
-            }
-            HIPCHK(hipStreamSynchronize(s));
-            jm("compact");
-            const double per = (now_ms() - tw) / G;
-            for (int wi = 0; wi < n_win; ++wi) {
-                WinResult &R = results[(size_t)wi];
-                if (R.info.skipped) continue;
-                const uint32_t g = code[(size_t)wi];
-                R.d_out = nullptr;
-                R.n_out = (int64_t)cnt[(size_t)g + 1] - (int64_t)cnt[(size_t)g];
-                R.info.n_anchor_points = R.n_out;
-                R.info.merge_ms = per;
-            }
-            return LVBA_OK;
-        };
-        const int32_t rc = body();
-        if (rc != LVBA_OK) {
-            if (joint_pts) { (void)hipFree(joint_pts); joint_pts = nullptr; }
-            if (timing_on("window")) fprintf(stderr, "[window_ba] joint merge not taken (rc %d): one pass per window\n", rc);
-            return false;
-        }
-        return true;
-    };
+
     const bool timing = timing_on("window"); // stage times of the whole call to stderr
     double tmark = now_ms();
     auto mark = [&](const char *what) {
@@ -717,68 +726,45 @@ extern "C" int32_t lvba_window_ba(lvba_scans_t sc, const double *poses, const lv
         fprintf(stderr, "[window_ba] %-18s %.3f ms\n", what, t - tmark);
         tmark = t;
     };
-    if (!stage_map_joint()) run_stage(stage_map);
+    auto any_failed = [&]() { for (auto &R : c.res) if (R.rc < 0) return true; return false; };
+    if (c.o.merge_only || !joint_fits(c) || !stage_map_joint(c)) run_stage(c, stage_map);
     mark("voxel maps");
-    bool any_failed = false;
-    for (auto &q : results) any_failed = any_failed || q.rc < 0;
-    if (!any_failed && !o.merge_only) {
-        const bool batch = o.lm_mode == 0;
+    if (!any_failed() && !c.o.merge_only) {
         bool done = false;
-        if (batch) {
-            const int32_t rc = stage_lm_batched(done);
-            if (rc < 0) { free_maps(); return rc; }
-        }
-        if (!done) run_stage(stage_lm_single);
-        for (auto &q : results) any_failed = any_failed || q.rc < 0;
+        if (c.o.lm_mode == 0) TRY(stage_lm_batched(c, done));
+        if (!done) run_stage(c, stage_lm_single);
         mark(done ? "LM, all windows" : "LM, one by one");
     }
-    if (!any_failed && !stage_finish_joint()) run_stage(stage_finish);
-    free_maps();
+    if (!any_failed() && !stage_merge_joint(c)) run_stage(c, stage_merge_window);
+    c.free_maps();
     mark("align + merge");
-    for (int wi = 0; wi < n_win; ++wi) { // assemble in window order
-        WinResult &R = results[(size_t)wi];
-        if (R.rc < 0) {
-            for (auto &q : results) if (q.d_out) DevicePool::get().free(q.d_out);
-            clouds.clear();
-            if (joint_pts) (void)hipFree(joint_pts);
-            return lvba_fail(R.rc, "%s", R.err.c_str());
-        }
-    }
-    for (int wi = 0; wi < n_win; ++wi) {
-        WinResult &R = results[(size_t)wi];
-        const int start = wi * w, cw = std::min(w, n - start);
+    for (auto &R : c.res)
+        if (R.rc < 0) return lvba_fail(R.rc, "%s", R.err.c_str());
+    lvba::hvec<int64_t> count; // assembled in window order
+    for (int wi = 0; wi < c.n_win; ++wi) {
+        WinResult &R = c.res[(size_t)wi];
+        const int start = c.start(wi), cw = c.frames(wi);
         if (!R.info.skipped) {
             if (window_poses) memcpy(window_poses + 12 * (int64_t)start, R.x.data(), 96 * (size_t)cw);
-            memcpy(rel_poses + 12 * (int64_t)start, R.rel.data(), 96 * (size_t)cw);
-            for (int j = 0; j < cw; ++j) anchor_index[start + j] = (int32_t)clouds.size();
-            R.info.anchor = (int32_t)clouds.size();
-            memcpy(anchor_poses + 12 * clouds.size(), poses + 12 * (int64_t)start, 96);
-            clouds.push_back({R.d_out, R.n_out});
+            for (int j = 0; j < cw; ++j) anchor_index[start + j] = (int32_t)count.size();
+            R.info.anchor = (int32_t)count.size();
+            memcpy(anchor_poses + 12 * count.size(), poses + 12 * (int64_t)start, 96);
+            count.push_back(R.info.n_anchor_points);
         }
         if (win_info) win_info[wi] = R.info;
     }
-    // the anchor clouds as a scan set of their own
-    lvba_scans_s *out = new (std::nothrow) lvba_scans_s();
-    if (!out) { free_clouds(); if (joint_pts) (void)hipFree(joint_pts); return lvba_fail(LVBA_ERR_NOMEM, "host allocation failed"); }
-    out->device = sc->device;
-    out->n_frames = (int)clouds.size();
-    out->frame_off.assign(clouds.size() + 1, 0);
-    for (size_t a = 0; a < clouds.size(); ++a) out->frame_off[a + 1] = out->frame_off[a] + clouds[a].n;
-    const int64_t PT = out->frame_off.back();
-    hipError_t e = hipSuccess;
-    if (joint_pts) out->d_pts = joint_pts; // (stage_finish_joint: the windows' clouds already lie one after the other)
-    else e = hipMalloc((void **)&out->d_pts, PT ? 12 * (size_t)PT : 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&out->d_frame_off, 8 * (clouds.size() + 1));
-    for (size_t a = 0; a < clouds.size() && e == hipSuccess && !joint_pts; ++a)
-        if (clouds[a].n > 0)
-            e = hipMemcpy(out->d_pts + 3 * out->frame_off[a], clouds[a].d, 12 * (size_t)clouds[a].n, hipMemcpyDeviceToDevice);
-    if (e == hipSuccess)
-        e = lvba::copy_h2d(out->d_frame_off, out->frame_off.data(), 8 * (clouds.size() + 1));
-    free_clouds();
-    if (e != hipSuccess) {
-        lvba_scans_destroy(out);
-        return lvba_fail(e == hipErrorOutOfMemory ? LVBA_ERR_NOMEM : LVBA_ERR_DEVICE, "anchor scan set: %s", hipGetErrorString(e));
+    memcpy(rel_poses, c.rel.data(), 96 * (size_t)c.n);
+    // the anchor clouds as a scan set of their own; a single cloud (the joint pass's, or one window's) becomes its point array
+    lvba::hvec<DevCloud> src;
+    for (const DevCloud &cl : c.clouds) if (cl.d) src.push_back(cl);
+    float *adopt = nullptr;
+    if (src.size() == 1) {
+        adopt = src[0].d;
+        src.clear();
+        for (DevCloud &cl : c.clouds) if (cl.d == adopt) cl.d = nullptr;
     }
+    lvba_scans_s *out = nullptr;
+    TRY(scans_build(sc->device, (int32_t)count.size(), count.data(), adopt, src.data(), (int)src.size(), &out));
     *n_anchors = out->n_frames;
     *anchor_scans = out;
     mark("anchor scan set");
@@ -829,13 +815,12 @@ extern "C" int32_t lvba_window_ba_multi(int32_t n_shares, const lvba_scans_t *sc
     struct Inhibit { Inhibit() { bs_graph_inhibit(+1); } ~Inhibit() { bs_graph_inhibit(-1); } } inhibit;
     auto run = [&](int k) {
         Share &S = sh[(size_t)k];
-        const int64_t nf = scans[k]->n_frames, nw = wb[(size_t)k + 1] - wb[(size_t)k];
+        const int64_t nw = wb[(size_t)k + 1] - wb[(size_t)k];
         S.ap.assign(12 * (size_t)std::max<int64_t>(nw, 1), 0.0);
         S.rc = lvba_window_ba(scans[k], poses + 12 * fb[(size_t)k], &o, window_poses ? window_poses + 12 * fb[(size_t)k] : nullptr,
                               rel_poses + 12 * fb[(size_t)k], anchor_index + fb[(size_t)k], S.ap.data(), &S.na, &S.anchors,
                               win_info ? win_info + wb[(size_t)k] : nullptr);
         if (S.rc < 0) S.err = lvba_last_error();
-        (void)nf;
     };
     {
         std::vector<std::thread> th;
@@ -866,36 +851,16 @@ extern "C" int32_t lvba_window_ba_multi(int32_t n_shares, const lvba_scans_t *sc
         base += S.na;
     }
     // the anchor clouds as ONE scan set on the first share's device
-    lvba_scans_s *out = new (std::nothrow) lvba_scans_s();
-    if (!out) { drop(); return lvba_fail(LVBA_ERR_NOMEM, "host allocation failed"); }
-    out->device = scans[0]->device;
-    out->n_frames = base;
-    out->frame_off.assign((size_t)base + 1, 0);
-    {
-        size_t a = 0;
-        for (int k = 0; k < n_shares; ++k)
-            for (int f = 0; f < sh[(size_t)k].na; ++f, ++a)
-                out->frame_off[a + 1] = out->frame_off[a] + (sh[(size_t)k].anchors->frame_off[(size_t)f + 1] - sh[(size_t)k].anchors->frame_off[(size_t)f]);
+    lvba::hvec<int64_t> count;
+    lvba::hvec<DevCloud> src;
+    for (const Share &S : sh) {
+        for (int f = 0; f < S.na; ++f) count.push_back(S.anchors->frame_off[(size_t)f + 1] - S.anchors->frame_off[(size_t)f]);
+        src.push_back({S.anchors->d_pts, S.anchors->frame_off[(size_t)S.na]});
     }
-    hipError_t e = hipSetDevice(out->device);
-    const int64_t PT = out->frame_off.back();
-    if (e == hipSuccess) e = hipMalloc((void **)&out->d_pts, PT ? 12 * (size_t)PT : 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&out->d_frame_off, 8 * ((size_t)base + 1));
-    {
-        size_t a = 0;
-        for (int k = 0; k < n_shares && e == hipSuccess; ++k) {
-            const lvba_scans_s *A = sh[(size_t)k].anchors;
-            const int64_t np = A->frame_off[(size_t)sh[(size_t)k].na];
-            if (np > 0) e = hipMemcpy(out->d_pts + 3 * out->frame_off[a], A->d_pts, 12 * (size_t)np, hipMemcpyDefault); // (across devices: UVA)
-            a += (size_t)sh[(size_t)k].na;
-        }
-    }
-    if (e == hipSuccess) e = lvba::copy_h2d(out->d_frame_off, out->frame_off.data(), 8 * ((size_t)base + 1));
+    lvba_scans_s *out = nullptr;
+    const int32_t rc = scans_build(scans[0]->device, base, count.data(), nullptr, src.data(), n_shares, &out);
     drop();
-    if (e != hipSuccess) {
-        lvba_scans_destroy(out);
-        return lvba_fail(e == hipErrorOutOfMemory ? LVBA_ERR_NOMEM : LVBA_ERR_DEVICE, "anchor scan set: %s", hipGetErrorString(e));
-    }
+    if (rc != LVBA_OK) return rc;
     *n_anchors = base;
     *anchor_scans = out;
     return LVBA_OK;
@@ -979,20 +944,10 @@ static int32_t lidar_ba_impl(int32_t n_shares, const lvba_scans_t *scs, const do
                 r.stage_ms[idx] = now_ms() - t0;
                 continue;
             }
-            lvba_balm_t b = nullptr;
-            int32_t rc = lvba_voxmap_to_balm(map, &b);
-            lvba_voxmap_destroy(map);
-            if (rc != LVBA_OK) return rc;
-            lvba::hvec<lvba_lm_trace> trace((size_t)std::max(1, o.lm.max_iter));
-            int32_t nt = 0;
-            rc = lvba_balm_refine(b, anchor_poses.data(), &o.lm, trace.data(), &nt);
-            lvba_balm_destroy(b);
-            if (rc < 0) return rc;
-            r.stage_status[idx] = rc; r.stage_iters[idx] = nt;
-            if (nt > 0) {
-                r.stage_cost_first[idx] = trace[0].residual1;
-                r.stage_cost_last[idx] = trace[nt - 1].accepted ? trace[nt - 1].residual2 : trace[nt - 1].residual1;
-            }
+            Refined rr;
+            TRY(refine_map(map, anchor_poses.data(), o.lm, rr));
+            r.stage_status[idx] = rr.status; r.stage_iters[idx] = rr.n_iter;
+            r.stage_cost_first[idx] = rr.cost_first; r.stage_cost_last[idx] = rr.cost_last;
             r.stage_ms[idx] = now_ms() - t0;
         }
     memcpy(poses_out, poses_in, 96 * (size_t)n); // optimized_x_buf_ = x_buf_full (:393)
