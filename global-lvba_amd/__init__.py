@@ -4,8 +4,8 @@ The directory name (with a hyphen) is fixed by the build contract; import it wit
 `importlib.import_module("global-lvba_amd")` or through the `lvba_amd` alias module at the repo root.
 """
 from . import _lib
-from .balm import BALM2, IMUST, VOX_HESS, BalmProblem, shard_range
+from .balm import BALM2, IMUST, VOX_HESS, BalmProblem, Prior, shard_range
 from .visual import DepthImages, VisualProblem, fuse_tracks, optimize_camera_poses
 from .voxel import Scans, VoxelMap
 
-__all__ = ["BALM2", "IMUST", "VOX_HESS", "BalmProblem", "shard_range", "VisualProblem", "optimize_camera_poses", "VoxelMap", "Scans", "_lib"]
+__all__ = ["BALM2", "IMUST", "VOX_HESS", "BalmProblem", "Prior", "shard_range", "VisualProblem", "optimize_camera_poses", "VoxelMap", "Scans", "_lib"]

@@ -15,13 +15,14 @@ SYMBOLS = [
     "lvba_balm_create", "lvba_balm_create_dev", "lvba_balm_destroy", "lvba_balm_configure", "lvba_balm_info", "lvba_balm_cost",
     "lvba_balm_eval", "lvba_balm_eval_blocks", "lvba_balm_solve", "lvba_balm_refine", "lvba_balm_lm_begin", "lvba_balm_lm_step",
     "lvba_balm_lm_end", "lvba_balm_set_groups", "lvba_balm_refine_groups", "lvba_balm_set_profiling", "lvba_balm_get_profile", "lvba_balm_get_ordering", "lvba_balm_nd_model",
+    "lvba_balm_set_priors", "lvba_balm_prior_residuals",
     "lvba_dist_unique_id", "lvba_balm_dist_init", "lvba_balm_dist_init_external", "lvba_visual_dist_init_external",
     "lvba_visual_default_opts", "lvba_visual_create", "lvba_visual_destroy", "lvba_visual_cost", "lvba_visual_linearize", "lvba_visual_info", "lvba_visual_dist_init",
     "lvba_visual_refine", "lvba_visual_set_loss", "lvba_visual_residual_sq",
     "lvba_voxel_default_opts", "lvba_voxmap_build", "lvba_voxmap_destroy", "lvba_voxmap_info", "lvba_voxmap_export",
     "lvba_voxmap_to_balm", "lvba_voxmap_find_planes", "lvba_scans_create", "lvba_scans_destroy", "lvba_voxmap_build_scans",
     "lvba_release_cached_memory", "lvba_window_default_opts", "lvba_window_ba", "lvba_window_split", "lvba_window_ba_multi", "lvba_scans_info", "lvba_scans_download",
-    "lvba_lidar_ba_default_opts", "lvba_lidar_ba", "lvba_lidar_ba_multi", "lvba_triangulate_tracks",
+    "lvba_lidar_ba_default_opts", "lvba_lidar_ba", "lvba_lidar_ba_multi", "lvba_lidar_ba_priors", "lvba_lidar_ba_multi_priors", "lvba_triangulate_tracks",
     "lvba_depth_render", "lvba_depth_upload", "lvba_depth_info", "lvba_depth_download", "lvba_depth_destroy",
     "lvba_fuse_default_opts", "lvba_fuse_tracks",
     "lvba_colorize_default_opts", "lvba_colorize_create", "lvba_colorize_add_images", "lvba_colorize_count",
@@ -82,6 +83,15 @@ class VisualTrace(C.Structure):
 
     def as_dict(self):
         return {f: getattr(self, f) for f, _ in self._fields_ if f != "reserved"}
+
+
+PRIOR_KINDS = {"pose": 0, "position": 1, "relative": 2}
+
+
+class Prior(C.Structure):
+    """lvba_prior: one pose prior (see balm.Prior for the constructors)"""
+    _fields_ = [("kind", C.c_int32), ("i", C.c_int32), ("j", C.c_int32), ("reserved", C.c_int32), ("meas", C.c_double * 12),
+                ("offset_i", C.c_double * 12), ("offset_j", C.c_double * 12), ("sqrt_info", C.c_double * 36)]
 
 
 LOSS_KINDS = {"trivial": 0, "huber": 1, "softlone": 2, "cauchy": 3, "arctan": 4, "tukey": 5}
@@ -201,6 +211,8 @@ def load():
     lib.lvba_balm_get_profile.argtypes = [H, C.POINTER(Prof), C.c_int32]
     lib.lvba_balm_get_ordering.argtypes = [H, i32p]
     lib.lvba_balm_nd_model.argtypes = [H, C.c_int32, C.POINTER(NdModel)]
+    lib.lvba_balm_set_priors.argtypes = [H, C.c_int32, C.c_void_p]
+    lib.lvba_balm_prior_residuals.argtypes = [H, f64p, C.c_void_p, C.POINTER(C.c_double)]
     lib.lvba_dist_unique_id.argtypes = [C.c_char_p]
     lib.lvba_balm_dist_init_external.argtypes = [H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.lvba_visual_dist_init_external.argtypes = [H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
@@ -243,6 +255,10 @@ def load():
     lib.lvba_lidar_ba_default_opts.restype = None
     lib.lvba_lidar_ba.argtypes = [H, f64p, C.POINTER(LidarBaOpts), f64p, C.POINTER(LidarBaReport)]
     lib.lvba_lidar_ba_multi.argtypes = [C.c_int32, C.POINTER(H), f64p, C.POINTER(LidarBaOpts), f64p, C.POINTER(LidarBaReport)]
+    lib.lvba_lidar_ba_priors.argtypes = [H, f64p, C.POINTER(LidarBaOpts), C.c_int32, C.c_void_p, f64p, C.POINTER(LidarBaReport),
+                                         C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.lvba_lidar_ba_multi_priors.argtypes = [C.c_int32, C.POINTER(H), f64p, C.POINTER(LidarBaOpts), C.c_int32, C.c_void_p, f64p,
+                                               C.POINTER(LidarBaReport), C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.lvba_triangulate_tracks.argtypes = [C.c_int32, C.c_int32, C.c_int64, i64p, C.c_void_p, C.c_void_p, f64p, f64p, f64p, f64p,
                                             f64p, i32p, u8p]
     lib.lvba_depth_render.argtypes = [C.c_void_p, f64p, f64p, C.c_int32, f64p, f64p, f64p, f64p, C.c_int32, C.c_int32, C.c_double,

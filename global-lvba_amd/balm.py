@@ -25,6 +25,69 @@ def shard_range(n_voxels, rank, n_ranks):
     return a.value, b.value
 
 
+def _pose12(T):
+    """a pose as 12 doubles R row-major | p, from 12 numbers, a 4 x 4 / 3 x 4 matrix or an (R, p) pair"""
+    if isinstance(T, (tuple, list)) and len(T) == 2:
+        return np.r_[np.asarray(T[0], np.float64).reshape(9), np.asarray(T[1], np.float64).reshape(3)]
+    a = np.asarray(T, np.float64)
+    if a.shape in ((4, 4), (3, 4)):
+        return np.r_[a[:3, :3].reshape(9), a[:3, 3]]
+    return a.reshape(12)
+
+
+def _sqrt_info(sqrt_info, sigma_rot, sigma_pos):
+    if sqrt_info is not None:
+        return np.asarray(sqrt_info, np.float64).reshape(6, 6)
+    if sigma_rot is None or sigma_pos is None:
+        raise ValueError("give sigma_rot and sigma_pos, or sqrt_info")
+    sr = np.broadcast_to(np.asarray(sigma_rot, np.float64), (3,))
+    sp = np.broadcast_to(np.asarray(sigma_pos, np.float64), (3,))
+    return np.diag(1.0 / np.r_[sr, sp])
+
+
+class Prior:
+    """Pose priors of the LiDAR bundle adjustment (lvba_balm_set_priors; model in include/lvba_hip.h).  Poses and offsets are 12
+    numbers (R row-major | p), a 4 x 4 matrix or an (R, p) pair; sigma_rot [rad] / sigma_pos [m] are scalars or 3-vectors and make a
+    diagonal square-root information diag(1 / sigma), or sqrt_info gives the 6 x 6 matrix itself (row-major).  Offsets are body-frame
+    transforms O: the prior constrains T_i O (identity by default)."""
+
+    @staticmethod
+    def _make(kind, i, j, meas, L6, oi, oj):
+        p = L.Prior()
+        p.kind, p.i, p.j, p.reserved = L.PRIOR_KINDS[kind], int(i), int(j), 0
+        p.meas[:] = [float(v) for v in meas]
+        p.offset_i[:] = [float(v) for v in (np.zeros(12) if oi is None else _pose12(oi))]
+        p.offset_j[:] = [float(v) for v in (np.zeros(12) if oj is None else _pose12(oj))]
+        p.sqrt_info[:] = [float(v) for v in np.asarray(L6, np.float64).reshape(36)]
+        return p
+
+    @staticmethod
+    def pose(i, T, sigma_rot=None, sigma_pos=None, sqrt_info=None, offset=None):
+        """r = [Log(R^T R_A); p_A - p] with A = T_i offset"""
+        return Prior._make("pose", i, 0, _pose12(T), _sqrt_info(sqrt_info, sigma_rot, sigma_pos), offset, None)
+
+    @staticmethod
+    def position(i, z, sigma=None, sqrt_info=None, lever_arm=None):
+        """r = R_i lever_arm + p_i - z (a GNSS fix of the antenna at `lever_arm` in the body frame); sqrt_info: 3 x 3 (or 6 x 6,
+        of which the top-left 3 x 3 is read)"""
+        L6 = np.zeros((6, 6))
+        if sqrt_info is not None:
+            a = np.asarray(sqrt_info, np.float64)
+            L6[:3, :3] = a[:3, :3] if a.shape == (6, 6) else a.reshape(3, 3)
+        elif sigma is not None:
+            L6[:3, :3] = np.diag(1.0 / np.broadcast_to(np.asarray(sigma, np.float64), (3,)))
+        else:
+            raise ValueError("give sigma or sqrt_info")
+        meas = np.r_[np.eye(3).reshape(9), np.asarray(z, np.float64).reshape(3)]
+        off = None if lever_arm is None else np.r_[np.eye(3).reshape(9), np.asarray(lever_arm, np.float64).reshape(3)]
+        return Prior._make("position", i, 0, meas, L6, off, None)
+
+    @staticmethod
+    def relative(i, j, T_ij, sigma_rot=None, sigma_pos=None, sqrt_info=None, offset_i=None, offset_j=None):
+        """r = [Log(R_ij^T R_A^T R_B); R_A^T (p_B - p_A) - p_ij] with A = T_i offset_i, B = T_j offset_j"""
+        return Prior._make("relative", i, j, _pose12(T_ij), _sqrt_info(sqrt_info, sigma_rot, sigma_pos), offset_i, offset_j)
+
+
 class BalmProblem:
     """One packed LiDAR-BA problem (or one rank's voxel shard) resident on a GPU."""
 
@@ -168,6 +231,23 @@ class BalmProblem:
         nt = C.c_int32()
         rc = L.check(self.lib.lvba_balm_refine(self._h, x, C.byref(o), trace, C.byref(nt)), allow_numeric=True)
         return x.reshape(-1, 12), [trace[i].as_dict() for i in range(nt.value)], rc
+
+    def set_priors(self, priors):
+        """Pose priors (lvba_balm_set_priors): a sequence of Prior.pose / .position / .relative; empty or None clears them.
+        Relative priors that join new pairs of poses must come before the first cost / eval / refine call."""
+        priors = list(priors or [])
+        arr = (L.Prior * max(1, len(priors)))(*priors)
+        L.check(self.lib.lvba_balm_set_priors(self._h, len(priors), C.cast(arr, C.c_void_p) if priors else None))
+        self.n_priors = len(priors)
+
+    def prior_residuals(self, poses):
+        """(e [n, 6] whitened residuals L r in the order given to set_priors -- position priors fill e[k, :3] --, their cost
+        sum 1/2 |e|^2)"""
+        n = getattr(self, "n_priors", 0)
+        e = np.zeros((max(n, 1), 6))
+        c = C.c_double()
+        L.check(self.lib.lvba_balm_prior_residuals(self._h, self._poses(poses), e.ctypes.data, C.byref(c)))
+        return e[:n], c.value
 
     def set_groups(self, pose_off, voxel_off):
         """Independent groups of poses / voxels (lvba_balm_set_groups); before the first cost / eval / refine call."""

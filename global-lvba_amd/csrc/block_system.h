@@ -60,6 +60,10 @@ struct BlockSys {
     // grouped refinement: d_u holds one damping value per group, d_grp_of_pose [N] (owned by the caller) maps pose blocks to them
     int32_t n_groups = 0;
     const int32_t *d_grp_of_pose = nullptr;
+    // pose-graph edges that are not voxels (relative pose priors, lvba_balm_set_priors), caller indices: bs_build takes them into the
+    // band, the ordering, the dissection plan and the packed all-reduce; extra_slots: their blocks, for bs_pattern_slots
+    lvba::hvec<int32_t> edge_i, edge_j;
+    lvba::hvec<int64_t> extra_slots;
     int32_t bb_hint = -1; // >= 0: an upper bound of the block half-bandwidth in the caller's pose order (a grouped problem: the
                           // largest group's pose count - 1; the voxels were checked against the groups) -- no host pass over the factors
     int *d_status = nullptr;

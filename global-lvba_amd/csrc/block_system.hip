@@ -227,6 +227,7 @@ int32_t bs_pattern_slots(BlockSys &bs, lvba::hvec<int64_t> &slots)
     if (bs.n_multi) HIPCHK(hipMemcpy(slots.data() + bs.n_items, bs.d_multi_slot, (size_t)bs.n_multi * sizeof(int64_t), hipMemcpyDeviceToHost));
     slots.erase(std::remove_if(slots.begin(), slots.end(), [](int64_t v) { return v < 0; }), slots.end());
     for (int64_t J = 0; J < bs.N; ++J) slots.push_back(J * Bb1);
+    slots.insert(slots.end(), bs.extra_slots.begin(), bs.extra_slots.end()); // blocks that only pose priors fill
     std::sort(slots.begin(), slots.end());
     slots.erase(std::unique(slots.begin(), slots.end()), slots.end());
     return LVBA_OK;
@@ -362,6 +363,7 @@ int32_t bs_build(BlockSys &bs, int32_t N, int64_t G, const int64_t *voff, const 
             }
             if (hi >= 0) Bb = std::max(Bb, hi - lo);
         }
+        for (size_t e = 0; e < bs.edge_i.size(); ++e) Bb = std::max(Bb, std::abs(iperm[bs.edge_i[e]] - iperm[bs.edge_j[e]]));
         return Bb;
     };
     int32_t Bb_nat = (bs.bb_hint >= 0 && !bs.distributed()) ? std::min<int32_t>(bs.bb_hint, std::max(N - 1, 0)) : band_of(bs.iperm);
@@ -395,6 +397,8 @@ int32_t bs_build(BlockSys &bs, int32_t N, int64_t G, const int64_t *voff, const 
             HIPCHK(lvba::copy_d2h(adj.data(), dadj, adj.size()));
             hipFree(dadj);
         }
+        for (size_t e = 0; e < bs.edge_i.size(); ++e) // relative pose priors: edges of the same graph (the same on every rank)
+            adj[(size_t)bs.edge_i[e] * N + bs.edge_j[e]] = adj[(size_t)bs.edge_j[e] * N + bs.edge_i[e]] = 1;
         lvba::hvec<int32_t> perm, iperm(N);
         rcm_order(adj, N, perm);
         for (int i = 0; i < N; ++i) iperm[perm[i]] = i;

@@ -80,6 +80,28 @@ struct VisDev {
 };
 
 
+// One pose prior (lvba_balm_set_priors) bound to the solver order: I, J solver pose indices; flip: I < J (the cross block is stored
+// transposed); offsets and measurement as R row-major | t, L the 6 x 6 square-root information, row-major (prior_device.h)
+struct PriorRec {
+    int32_t kind, I, J, flip;
+    double meas[12], oi[12], oj[12], L[36];
+};
+// Device view of a handle's priors and the scatter tables of priors.hip.  Target blocks of the store: slot, mode (bit 0: the slot
+// holds nothing else, it is written rather than added to; bit 1: a diagonal block), contributions hsrc[hoff[b] .. hoff[b+1]) as
+// (prior << 2 | piece), piece 0: J_i^T J_i, 1: J_j^T J_j, 2: the cross block.  g: the same per pose, piece 0: J_i^T e, 1: J_j^T e.
+struct PriorDev {
+    int32_t n = 0;
+    const PriorRec *pr = nullptr;
+    double *lin = nullptr;     // [n][128] linearisation records
+    double *part = nullptr;    // [(n + 63) / 64] per-workgroup shares of the cost
+    unsigned *ticket = nullptr; // workgroups done (0 between launches)
+    int64_t n_hblk = 0;
+    const int64_t *hslot = nullptr;
+    const int32_t *hmode = nullptr, *hoff = nullptr, *hsrc = nullptr;
+    int32_t n_g = 0;
+    const int32_t *gpose = nullptr, *goff = nullptr, *gsrc = nullptr;
+};
+
 // Working matrix of the damped system, lower triangle, column-major with leading dimension ld:
 // A(r,c) = a[r + c*ld].  Dense: ld = n.  Band: LAPACK lower-band storage with ldab = ld+1, i.e.
 // A(r,c) = ab[(r-c) + c*ldab]; valid offsets 0 <= r-c <= ld.  bw = half bandwidth in scalars.
@@ -185,6 +207,11 @@ void launch_export_dense(const double *Hblk, int band_blocks, int n_poses, const
 void launch_export_vec(const double *v, const int *perm, int n_poses, double *out, hipStream_t s);
 void launch_import_poses(const double *in, const int *perm, int n_poses, double *out, hipStream_t s);
 void launch_export_poses(const double *in, const int *perm, int n_poses, double *out, hipStream_t s);
+
+// priors.hip: nothing is launched when d.n == 0
+void launch_prior_eval(const PriorDev &d, const double *poses, double *Hblk, double *g, double *scal, hipStream_t s); // scal[0] += cost
+void launch_prior_cost(const PriorDev &d, const double *poses, double *out, double *e_out, hipStream_t s);             // out[0] += cost
+void launch_prior_zero_slots(double *Hblk, const int64_t *slot, int64_t n, hipStream_t s);
 
 // visual_kernels.hip
 void vis_launch_residuals(const VisDev &d, bool jac, const double *qc, const double *tc, const double *Xp, double *part,

@@ -1,0 +1,208 @@
+// priors.hip -- the pose priors of the LiDAR bundle adjustment (lvba_balm_set_priors; the model is in prior_device.h).
+//   prior_lin_kernel      one lane per prior: e = L r and the whitened Jacobian blocks at the solver-order poses; writes per prior
+//                         J_i^T e, J_j^T e and the 6 x 6 products J_i^T J_i, J_j^T J_j, J_i^T J_j (the last oriented for the lower
+//                         block store: transposed when the solver puts i before j), and adds the prior cost to the evaluation's
+//   prior_scatter_kernel  every target element of the block store and of g sums its contributions in the fixed order of a CSR table
+//                         built on the host.  No atomics on data: the bytes do not change run to run.
+//   prior_cost_kernel     the cost alone (the LM's trial point), one lane per prior, summed like the evaluation's
+// Both sums run in a fixed order: a tree over the 64 lanes of each workgroup, then the workgroup that finishes last (a ticket
+// counter, the only atomic) sums the workgroups' shares in index order.
+// An evaluation is 2 launches, a trial cost 1; a handle without priors launches none of them.
+#include <hip/hip_runtime.h>
+
+#include "lvba_internal.h"
+#include "prior_device.h"
+
+namespace lvba {
+
+#define PRIOR_WG 256
+
+// lin record of prior k: [0] unused, [1..6] J_i^T e, [7..12] J_j^T e, [13..48] J_i^T J_i, [49..84] J_j^T J_j, [85..120] cross block,
+// 6 x 6 blocks in the store's element order (column-major: [c * 6 + r])
+enum { PL_GI = 1, PL_GJ = 7, PL_HII = 13, PL_HJJ = 49, PL_HX = 85 };
+
+// Fixed-order sum of one value per lane over the whole grid (64-lane workgroups); the last workgroup to finish adds the total to
+// out[0] and resets the ticket for the next launch on the stream.
+__device__ void prior_grid_sum(double v, double *__restrict__ part, unsigned *__restrict__ ticket, double *__restrict__ out)
+{
+    __shared__ double red[64];
+    __shared__ int last;
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int w = 32; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        part[blockIdx.x] = red[0];
+        __threadfence();
+        last = atomicAdd(ticket, 1u) == gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!last) return;
+    __threadfence();
+    double s = 0.0;
+    for (unsigned b = threadIdx.x; b < gridDim.x; b += 64) s += __builtin_nontemporal_load(part + b);
+    __syncthreads();
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 32; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        if (out) out[0] += red[0];
+        *ticket = 0u;
+    }
+}
+
+// (kind is a constant at each call site: every array stays in registers)
+__device__ __forceinline__ double prior_lin_one(const int kind, const PriorRec &p, const double *__restrict__ poses, double *__restrict__ o)
+{
+    double Ti[12], Tj[12], r[6], Ji[36], Jj[36], e[6], Wi[36], Wj[36];
+#pragma unroll
+    for (int a = 0; a < 12; ++a) Ti[a] = poses[12 * (int64_t)p.I + a];
+    if (kind == PRIOR_RELATIVE) {
+#pragma unroll
+        for (int a = 0; a < 12; ++a) Tj[a] = poses[12 * (int64_t)p.J + a];
+    }
+    prior_raw(kind, p.meas, Ti, p.oi, Tj, p.oj, r, true, Ji, Jj);
+    const double cost = prior_whiten(kind, p.L, r, e);
+    prior_whiten_jac(kind, p.L, Ji, Wi);
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+        double s = 0.0;
+#pragma unroll
+        for (int a = 0; a < 6; ++a) s += Wi[6 * a + c] * e[a];
+        o[PL_GI + c] = s;
+    }
+#pragma unroll
+    for (int c = 0; c < 6; ++c)
+#pragma unroll
+        for (int rr = 0; rr < 6; ++rr) {
+            double s = 0.0;
+#pragma unroll
+            for (int a = 0; a < 6; ++a) s += Wi[6 * a + rr] * Wi[6 * a + c];
+            o[PL_HII + 6 * c + rr] = s;
+        }
+    if (kind != PRIOR_RELATIVE) return cost;
+    prior_whiten_jac(kind, p.L, Jj, Wj);
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+        double s = 0.0;
+#pragma unroll
+        for (int a = 0; a < 6; ++a) s += Wj[6 * a + c] * e[a];
+        o[PL_GJ + c] = s;
+    }
+#pragma unroll
+    for (int c = 0; c < 6; ++c)
+#pragma unroll
+        for (int rr = 0; rr < 6; ++rr) {
+            double s = 0.0, x = 0.0;
+#pragma unroll
+            for (int a = 0; a < 6; ++a) { s += Wj[6 * a + rr] * Wj[6 * a + c]; x += Wi[6 * a + rr] * Wj[6 * a + c]; }
+            o[PL_HJJ + 6 * c + rr] = s;
+            // x = (J_i^T J_j)(rr, c): block (i, j).  The store keeps (max, min) in solver order; flip: j comes after i, block (j, i)
+            o[PL_HX + (p.flip ? 6 * rr + c : 6 * c + rr)] = x;
+        }
+    return cost;
+}
+
+__global__ __launch_bounds__(64) void prior_lin_kernel(const PriorRec *__restrict__ pr, int32_t n, const double *__restrict__ poses,
+                                                       double *__restrict__ lin, double *__restrict__ part, unsigned *__restrict__ ticket,
+                                                       double *__restrict__ scal)
+{
+    const int k = blockIdx.x * 64 + threadIdx.x;
+    double c = 0.0;
+    if (k < n) {
+        const PriorRec &p = pr[k];
+        double *o = lin + 128 * (int64_t)k;
+        if (p.kind == PRIOR_POSE) c = prior_lin_one(PRIOR_POSE, p, poses, o);
+        else if (p.kind == PRIOR_POSITION) c = prior_lin_one(PRIOR_POSITION, p, poses, o);
+        else c = prior_lin_one(PRIOR_RELATIVE, p, poses, o);
+    }
+    prior_grid_sum(c, part, ticket, scal);
+}
+
+__global__ __launch_bounds__(64) void prior_cost_kernel(const PriorRec *__restrict__ pr, int32_t n, const double *__restrict__ poses,
+                                                        double *__restrict__ part, unsigned *__restrict__ ticket, double *__restrict__ out,
+                                                        double *__restrict__ e_out)
+{
+    const int k = blockIdx.x * 64 + threadIdx.x;
+    double c = 0.0;
+    if (k < n) {
+        const PriorRec &p = pr[k];
+        double Ti[12], Tj[12], r[6], e[6];
+LVBA_PRIOR_UNROLL
+        for (int a = 0; a < 12; ++a) Ti[a] = poses[12 * (int64_t)p.I + a];
+        if (p.kind == PRIOR_RELATIVE) {
+LVBA_PRIOR_UNROLL
+            for (int a = 0; a < 12; ++a) Tj[a] = poses[12 * (int64_t)p.J + a];
+        }
+        prior_raw(p.kind, p.meas, Ti, p.oi, Tj, p.oj, r, false, nullptr, nullptr);
+        c = prior_whiten(p.kind, p.L, r, e);
+        if (e_out) {
+LVBA_PRIOR_UNROLL
+            for (int a = 0; a < 6; ++a) e_out[6 * (int64_t)k + a] = e[a];
+        }
+    }
+    prior_grid_sum(c, part, ticket, out);
+}
+
+__global__ __launch_bounds__(PRIOR_WG) void prior_scatter_kernel(PriorDev d, double *__restrict__ Hblk, double *__restrict__ g)
+{
+    const int64_t t = (int64_t)blockIdx.x * PRIOR_WG + threadIdx.x;
+    if (t < 36 * d.n_hblk) {
+        const int64_t b = t / 36;
+        const int el = (int)(t - 36 * b);
+        const int mode = d.hmode[b];
+        if ((mode & 2) && (el % 6) < (el / 6)) return; // diagonal block: only the lower triangle is stored
+        double *dst = Hblk + d.hslot[b] * 36 + el;
+        double s = (mode & 1) ? 0.0 : *dst;
+        for (int32_t q = d.hoff[b]; q < d.hoff[b + 1]; ++q) {
+            const int32_t src = d.hsrc[q], k = src >> 2, piece = src & 3;
+            s += d.lin[128 * (int64_t)k + (piece == 0 ? PL_HII : piece == 1 ? PL_HJJ : PL_HX) + el];
+        }
+        *dst = s;
+        return;
+    }
+    const int64_t u = t - 36 * d.n_hblk;
+    if (u >= 6 * (int64_t)d.n_g) return;
+    const int64_t b = u / 6;
+    const int el = (int)(u - 6 * b);
+    double *dst = g + 6 * (int64_t)d.gpose[b] + el;
+    double s = *dst;
+    for (int32_t q = d.goff[b]; q < d.goff[b + 1]; ++q) {
+        const int32_t src = d.gsrc[q], k = src >> 2, piece = src & 3;
+        s += d.lin[128 * (int64_t)k + (piece == 0 ? PL_GI : PL_GJ) + el];
+    }
+    *dst = s;
+}
+
+__global__ void prior_zero_slots_kernel(double *__restrict__ Hblk, const int64_t *__restrict__ slot, int64_t n)
+{
+    const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (t < 36 * n) Hblk[slot[t / 36] * 36 + t % 36] = 0.0;
+}
+
+void launch_prior_eval(const PriorDev &d, const double *poses, double *Hblk, double *g, double *scal, hipStream_t s)
+{
+    if (d.n <= 0) return;
+    hipLaunchKernelGGL(prior_lin_kernel, dim3((unsigned)((d.n + 63) / 64)), dim3(64), 0, s, d.pr, d.n, poses, d.lin, d.part, d.ticket, scal);
+    const int64_t work = 36 * d.n_hblk + 6 * (int64_t)d.n_g;
+    hipLaunchKernelGGL(prior_scatter_kernel, dim3((unsigned)((work + PRIOR_WG - 1) / PRIOR_WG)), dim3(PRIOR_WG), 0, s, d, Hblk, g);
+}
+
+void launch_prior_cost(const PriorDev &d, const double *poses, double *out, double *e_out, hipStream_t s)
+{
+    if (d.n <= 0) return;
+    hipLaunchKernelGGL(prior_cost_kernel, dim3((unsigned)((d.n + 63) / 64)), dim3(64), 0, s, d.pr, d.n, poses, d.part, d.ticket, out, e_out);
+}
+
+void launch_prior_zero_slots(double *Hblk, const int64_t *slot, int64_t n, hipStream_t s)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL(prior_zero_slots_kernel, dim3((unsigned)((36 * n + 255) / 256)), dim3(256), 0, s, Hblk, slot, n);
+}
+
+} // namespace lvba

@@ -146,13 +146,18 @@ inline void mat3T_mul(const double *A, const double *B, double *C) // A^T * B
 // damping_iter on the problem of a voxel map, which it consumes (:264, :386): poses x refined in place; the LM status, the
 // iterations, the first and last cost of the trace, and the time of the problem's set-up
 struct Refined { int32_t status = 0, n_iter = 0; double cost_first = 0.0, cost_last = 0.0, setup_ms = 0.0; };
-int32_t refine_map(lvba_voxmap_t map, double *x, const lvba_balm_opts &lm, Refined &r)
+int32_t refine_map(lvba_voxmap_t map, double *x, const lvba_balm_opts &lm, Refined &r, int32_t n_priors = 0,
+                   const lvba_prior *priors = nullptr)
 {
     const double t0 = now_ms();
     lvba_balm_t b = nullptr;
     int32_t rc = lvba_voxmap_to_balm(map, &b);
     lvba_voxmap_destroy(map);
     if (rc != LVBA_OK) return rc;
+    if (n_priors > 0 && (rc = lvba_balm_set_priors(b, n_priors, priors)) != LVBA_OK) {
+        lvba_balm_destroy(b);
+        return rc;
+    }
     lvba::hvec<lvba_lm_trace> trace((size_t)std::max(1, lm.max_iter));
     int32_t nt = 0;
     lvba_balm_info_t bi;
@@ -884,8 +889,42 @@ extern "C" void lvba_lidar_ba_default_opts(lvba_lidar_ba_opts *o)
 
 // n_shares == 1: the whole sequence on scs[0]'s device; > 1: the window stage over the shares (lvba_window_ba_multi), the global
 // stages -- single problems over all anchors -- on the first share's device, where the anchor clouds are gathered
+namespace lvba {
+int32_t prior_validate(int32_t n, const lvba_prior *priors, int32_t n_poses); // lvba_api.hip
+void prior_offset_or_identity(const double *o, double *out);
+}
+// frame priors -> priors on the anchors of the global stages: frame f = anchor a(f) o rel_f, so T_f O = T_a (rel_f o O) exactly.
+// Frames of skipped windows (anchor -1) and relative priors inside one anchor (constant at this stage) are dropped.
+static void priors_to_anchors(int32_t n, const lvba_prior *fp, const int32_t *aidx, const double *rel, std::vector<lvba_prior> &out)
+{
+    out.clear();
+    auto compose = [](const double *A, const double *B, double *C) { // C = A o B
+        double O[12];
+        mat3_mul(A, B, O);
+        for (int q = 0; q < 3; ++q) O[9 + q] = A[3 * q] * B[9] + A[3 * q + 1] * B[10] + A[3 * q + 2] * B[11] + A[9 + q];
+        memcpy(C, O, sizeof O);
+    };
+    for (int32_t k = 0; k < n; ++k) {
+        lvba_prior q = fp[k];
+        const bool relk = q.kind == LVBA_PRIOR_RELATIVE;
+        const int32_t ai = aidx[q.i], aj = relk ? aidx[q.j] : ai;
+        if (ai < 0 || aj < 0 || (relk && ai == aj)) continue;
+        double o[12];
+        lvba::prior_offset_or_identity(fp[k].offset_i, o);
+        compose(rel + 12 * (size_t)q.i, o, q.offset_i);
+        q.i = ai;
+        if (relk) {
+            lvba::prior_offset_or_identity(fp[k].offset_j, o);
+            compose(rel + 12 * (size_t)fp[k].j, o, q.offset_j);
+            q.j = aj;
+        }
+        out.push_back(q);
+    }
+}
+
 static int32_t lidar_ba_impl(int32_t n_shares, const lvba_scans_t *scs, const double *poses_in, const lvba_lidar_ba_opts *opts,
-                             double *poses_out, lvba_lidar_ba_report *rep)
+                             double *poses_out, lvba_lidar_ba_report *rep, int32_t n_priors = 0, const lvba_prior *priors = nullptr,
+                             lvba_prior *anchor_priors = nullptr, int32_t *n_used = nullptr, int32_t *n_dropped = nullptr)
 {
     if (n_shares < 1 || !scs || !scs[0] || !poses_in || !poses_out) return lvba_fail(LVBA_ERR_ARG, "null argument");
     lvba_lidar_ba_opts o;
@@ -899,6 +938,7 @@ static int32_t lidar_ba_impl(int32_t n_shares, const lvba_scans_t *scs, const do
     }
     if (n_shares > 1 && !o.window_enable)
         return lvba_fail(LVBA_ERR_ARG, "several shares need the window stage (window_enable = 0 cuts the RAW scans in the global stages: one device)");
+    TRY(lvba::prior_validate(n_priors, priors, n));
     lvba_lidar_ba_report r{};
     r.n_frames = n;
     lvba::hvec<double> rel(12 * (size_t)n), anchor_poses;
@@ -922,6 +962,11 @@ static int32_t lidar_ba_impl(int32_t n_shares, const lvba_scans_t *scs, const do
     }
     r.n_anchors = na;
     r.window_ms = now_ms() - t0;
+    std::vector<lvba_prior> ap;
+    priors_to_anchors(n_priors, priors, aidx.data(), rel.data(), ap);
+    if (n_used) *n_used = (int32_t)ap.size();
+    if (n_dropped) *n_dropped = n_priors - (int32_t)ap.size();
+    if (anchor_priors && !ap.empty()) memcpy(anchor_priors, ap.data(), ap.size() * sizeof(lvba_prior));
     struct AnchorGuard { lvba_scans_t a; ~AnchorGuard() { lvba_scans_destroy(a); } } guard{anchors};
     lvba_scans_t cut = o.window_enable ? anchors : sc;
     if (na > 0)
@@ -945,7 +990,7 @@ static int32_t lidar_ba_impl(int32_t n_shares, const lvba_scans_t *scs, const do
                 continue;
             }
             Refined rr;
-            TRY(refine_map(map, anchor_poses.data(), o.lm, rr));
+            TRY(refine_map(map, anchor_poses.data(), o.lm, rr, (int32_t)ap.size(), ap.data()));
             r.stage_status[idx] = rr.status; r.stage_iters[idx] = rr.n_iter;
             r.stage_cost_first[idx] = rr.cost_first; r.stage_cost_last[idx] = rr.cost_last;
             r.stage_ms[idx] = now_ms() - t0;
@@ -973,4 +1018,18 @@ extern "C" int32_t lvba_lidar_ba_multi(int32_t n_shares, const lvba_scans_t *sca
                                        const lvba_lidar_ba_opts *opts, double *poses_out, lvba_lidar_ba_report *rep)
 {
     return lidar_ba_impl(n_shares, scans, poses_in, opts, poses_out, rep);
+}
+
+extern "C" int32_t lvba_lidar_ba_priors(lvba_scans_t sc, const double *poses_in, const lvba_lidar_ba_opts *opts, int32_t n_priors,
+                                        const lvba_prior *priors, double *poses_out, lvba_lidar_ba_report *rep, lvba_prior *anchor_priors,
+                                        int32_t *n_used, int32_t *n_dropped)
+{
+    return lidar_ba_impl(1, &sc, poses_in, opts, poses_out, rep, n_priors, priors, anchor_priors, n_used, n_dropped);
+}
+
+extern "C" int32_t lvba_lidar_ba_multi_priors(int32_t n_shares, const lvba_scans_t *scans, const double *poses_in,
+                                              const lvba_lidar_ba_opts *opts, int32_t n_priors, const lvba_prior *priors, double *poses_out,
+                                              lvba_lidar_ba_report *rep, lvba_prior *anchor_priors, int32_t *n_used, int32_t *n_dropped)
+{
+    return lidar_ba_impl(n_shares, scans, poses_in, opts, poses_out, rep, n_priors, priors, anchor_priors, n_used, n_dropped);
 }

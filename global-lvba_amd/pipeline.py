@@ -276,12 +276,14 @@ def colorize_maps(scans, image_times, images, intr, width, height, after, before
 
 
 def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, tci, intr, width, height, keypoints, pairs,
-                      matches, enable_lidar_ba=True, enable_visual_ba=True, device=0, images=None, **cfg):
+                      matches, enable_lidar_ba=True, enable_visual_ba=True, device=0, images=None, lidar_priors=None, **cfg):
     """LvbaSystem::runFullPipeline (src/lvba_system.cpp:136-142) on in-memory data: clouds = body-frame [n_i, >=3] float32
     arrays, poses [n,12] = x_buf_ (T_world<-imu), image_poses [m,12] the image poses from the odometry.  cfg: DEFAULTS' keys
     (visual_loss, colorize_leaf among them).  images: None, or the images ([m,H,W,3] BGR uint8 or a callable k -> [H,W,3]):
     then the output also holds colored_after / colored_before = (xyz, rgb), the LiDAR map coloured from them
-    (colorize_maps) with the refined poses and cameras and with the original ones; this needs the visual stage."""
+    (colorize_maps) with the refined poses and cameras and with the original ones; this needs the visual stage.
+    lidar_priors: balm.Prior objects on frames (GNSS fixes, loop closures, ...) for the global stages of the LiDAR BA
+    (Scans.lidar_ba(priors=...))."""
     if images is not None and not enable_visual_ba:
         raise ValueError("colouring the map needs the cameras of the visual stage (enable_visual_ba=True)")
     c = dict(DEFAULTS); c.update(cfg)
@@ -292,7 +294,8 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
         if enable_lidar_ba:
             x_opt, report = scans.lidar_ba(x_orig, window_enable=c["window_enable"], window_size=c["window_size"],
                                            anchor_leaf=c["anchor_leaf"], use_rel=c["use_rel"], stage1_enable=c["stage1_enable"],
-                                           stage_voxel_size=c["stage_voxel_size"], stage_eigen_ratio=c["stage_eigen_ratio"])
+                                           stage_voxel_size=c["stage_voxel_size"], stage_eigen_ratio=c["stage_eigen_ratio"],
+                                           priors=lidar_priors)
             out["lidar_report"] = report
         out["poses"] = np.asarray(x_opt).reshape(-1, 12)
         if enable_visual_ba:

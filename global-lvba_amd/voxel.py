@@ -36,6 +36,19 @@ def _opts(voxel_size, eigen_ratio_array, min_points):
     return o
 
 
+def _prior_arrays(priors):
+    priors = list(priors)
+    pa = (L.Prior * max(1, len(priors)))(*priors)
+    ap = (L.Prior * max(1, len(priors)))()
+    return C.cast(pa, C.c_void_p), ap, C.c_int32(), C.c_int32()
+
+
+def _prior_report(rep, ap, used, dropped):
+    d = rep.as_dict()
+    d.update(priors_used=used.value, priors_dropped=dropped.value, anchor_priors=[ap[k] for k in range(used.value)])
+    return d
+
+
 class Scans:
     """A set of LiDAR clouds resident on a GPU (fp32 x, y, z per point)."""
 
@@ -174,9 +187,10 @@ class Scans:
 
     def lidar_ba(self, poses, window_enable=True, window_size=10, anchor_leaf=0.1, use_rel=True, stage1_enable=True,
                  stage_voxel_size=(0.5, 0.5), stage_eigen_ratio=((0.3, 0.1, 0.06, 0.03), (0.08, 0.08, 0.08, 0.08)),
-                 window_eigen_ratio=None):
+                 window_eigen_ratio=None, priors=None):
         """LvbaSystem::runLidarBA (src/lvba_system.cpp:312-410): window BA, global stage 1 / stage 2, pose composition.
-        Returns (poses [n,12], report dict)."""
+        Returns (poses [n,12], report dict).  priors: balm.Prior objects on FRAMES, applied to the anchors of both global stages
+        (lvba_lidar_ba_priors); the report then also holds priors_used, priors_dropped and anchor_priors (the applied priors)."""
         n = self.n_frames
         poses = np.ascontiguousarray(poses, np.float64).reshape(-1)
         if poses.size != 12 * n:
@@ -192,14 +206,20 @@ class Scans:
                 o.stage_eigen_ratio[i][k] = float(stage_eigen_ratio[i][k])
         out = np.zeros(12 * n)
         rep = L.LidarBaReport()
-        L.check(self.lib.lvba_lidar_ba(self._h, poses, C.byref(o), out, C.byref(rep)))
-        return out.reshape(n, 12), rep.as_dict()
+        if priors is None:
+            L.check(self.lib.lvba_lidar_ba(self._h, poses, C.byref(o), out, C.byref(rep)))
+            return out.reshape(n, 12), rep.as_dict()
+        pa, ap, used, dropped = _prior_arrays(priors)
+        L.check(self.lib.lvba_lidar_ba_priors(self._h, poses, C.byref(o), len(priors), pa, out, C.byref(rep), ap, C.byref(used),
+                                              C.byref(dropped)))
+        return out.reshape(n, 12), _prior_report(rep, ap, used, dropped)
 
     @staticmethod
     def lidar_ba_multi(clouds, poses, devices, window_size=10, anchor_leaf=0.1, use_rel=True, stage1_enable=True,
                        stage_voxel_size=(0.5, 0.5), stage_eigen_ratio=((0.3, 0.1, 0.06, 0.03), (0.08, 0.08, 0.08, 0.08)),
-                       window_eigen_ratio=None):
-        """runLidarBA with the window stage over several GPUs (lvba_lidar_ba_multi): returns (poses [n,12], report dict)."""
+                       window_eigen_ratio=None, priors=None):
+        """runLidarBA with the window stage over several GPUs (lvba_lidar_ba_multi): returns (poses [n,12], report dict).
+        priors: as in lidar_ba (lvba_lidar_ba_multi_priors)."""
         lib = L.load()
         n, D = len(clouds), len(devices)
         poses = np.ascontiguousarray(poses, np.float64).reshape(-1)
@@ -221,11 +241,16 @@ class Scans:
         rep = L.LidarBaReport()
         hs = (C.c_void_p * len(shares))(*[sc._h.value for sc in shares])
         try:
-            L.check(lib.lvba_lidar_ba_multi(len(shares), hs, poses, C.byref(o), out, C.byref(rep)))
+            if priors is None:
+                L.check(lib.lvba_lidar_ba_multi(len(shares), hs, poses, C.byref(o), out, C.byref(rep)))
+                return out.reshape(n, 12), rep.as_dict()
+            pa, ap, used, dropped = _prior_arrays(priors)
+            L.check(lib.lvba_lidar_ba_multi_priors(len(shares), hs, poses, C.byref(o), len(priors), pa, out, C.byref(rep), ap,
+                                                   C.byref(used), C.byref(dropped)))
+            return out.reshape(n, 12), _prior_report(rep, ap, used, dropped)
         finally:
             for sc in shares:
                 sc.close()
-        return out.reshape(n, 12), rep.as_dict()
 
     def voxel_map(self, poses, voxel_size=1.0, eigen_ratio_array=None, min_points=None, frame_begin=0, n_frames=None):
         """Map of frames [frame_begin, frame_begin + n_frames) at `poses` [n_frames, 12]."""

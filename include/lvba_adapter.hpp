@@ -15,6 +15,7 @@
 #pragma once
 #include <algorithm>
 #include <cstdint>
+#include <cstring>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -45,10 +46,84 @@ void pack_voxhess(const VoxHess &vh, std::vector<int64_t> &voxel_off, std::vecto
     }
 }
 
+// Pose priors (lvba_balm_set_priors) from IMUST-like poses (`.R(r,c)`, `.p[r]`): a fixed / known pose, a position fix with a
+// lever arm (GNSS antenna in the body frame), a relative transform T_ij between two poses (odometry, loop closure).  sigma_rot
+// [rad] and sigma_pos [m] make a diagonal square-root information; the sqrt_info forms take the 6 x 6 (3 x 3 for a position)
+// row-major matrix.  Offsets stay identity (twelve zeros).
+template <class Pose>
+inline void prior_pack_pose(const Pose &T, double *out)
+{
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) out[3 * r + c] = T.R(r, c);
+    for (int r = 0; r < 3; ++r) out[9 + r] = T.p[r];
+}
+inline lvba_prior prior_blank(int32_t kind, int32_t i, int32_t j)
+{
+    lvba_prior q;
+    std::memset(&q, 0, sizeof q);
+    q.kind = kind; q.i = i; q.j = j;
+    return q;
+}
+inline void prior_diag(lvba_prior &q, double sigma_rot, double sigma_pos)
+{
+    for (int a = 0; a < 6; ++a) q.sqrt_info[7 * a] = 1.0 / (a < 3 ? sigma_rot : sigma_pos);
+}
+template <class Pose>
+lvba_prior prior_pose(int32_t i, const Pose &T, const double sqrt_info[36])
+{
+    lvba_prior q = prior_blank(LVBA_PRIOR_POSE, i, 0);
+    prior_pack_pose(T, q.meas);
+    std::memcpy(q.sqrt_info, sqrt_info, sizeof q.sqrt_info);
+    return q;
+}
+template <class Pose>
+lvba_prior prior_pose(int32_t i, const Pose &T, double sigma_rot, double sigma_pos)
+{
+    lvba_prior q = prior_blank(LVBA_PRIOR_POSE, i, 0);
+    prior_pack_pose(T, q.meas);
+    prior_diag(q, sigma_rot, sigma_pos);
+    return q;
+}
+inline lvba_prior prior_position(int32_t i, const double z[3], const double sqrt_info3[9], const double lever_arm[3] = nullptr)
+{
+    lvba_prior q = prior_blank(LVBA_PRIOR_POSITION, i, 0);
+    for (int r = 0; r < 3; ++r) q.meas[9 + r] = z[r];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) q.sqrt_info[6 * r + c] = sqrt_info3[3 * r + c];
+    if (lever_arm) {
+        q.offset_i[0] = q.offset_i[4] = q.offset_i[8] = 1.0;
+        for (int r = 0; r < 3; ++r) q.offset_i[9 + r] = lever_arm[r];
+    }
+    return q;
+}
+inline lvba_prior prior_position(int32_t i, const double z[3], double sigma, const double lever_arm[3] = nullptr)
+{
+    const double L3[9] = {1.0 / sigma, 0, 0, 0, 1.0 / sigma, 0, 0, 0, 1.0 / sigma};
+    return prior_position(i, z, L3, lever_arm);
+}
+template <class Pose>
+lvba_prior prior_relative(int32_t i, int32_t j, const Pose &T_ij, const double sqrt_info[36])
+{
+    lvba_prior q = prior_blank(LVBA_PRIOR_RELATIVE, i, j);
+    prior_pack_pose(T_ij, q.meas);
+    std::memcpy(q.sqrt_info, sqrt_info, sizeof q.sqrt_info);
+    return q;
+}
+template <class Pose>
+lvba_prior prior_relative(int32_t i, int32_t j, const Pose &T_ij, double sigma_rot, double sigma_pos)
+{
+    lvba_prior q = prior_blank(LVBA_PRIOR_RELATIVE, i, j);
+    prior_pack_pose(T_ij, q.meas);
+    prior_diag(q, sigma_rot, sigma_pos);
+    return q;
+}
+
 // Drop-in for BALM2::damping_iter(x_stats, voxhess)  (bavoxel.hpp:662).  Refines x_stats in place.
-// Returns the LM trace (the quantities of the commented printf at bavoxel.hpp:737).
+// Returns the LM trace (the quantities of the commented printf at bavoxel.hpp:737).  The overload with `priors` adds pose priors
+// (indices into x_stats) to the cost.
 template <class PoseVec, class VoxHess>
-std::vector<lvba_lm_trace> damping_iter_hip(PoseVec &x_stats, const VoxHess &voxhess, int device = 0)
+std::vector<lvba_lm_trace> damping_iter_hip(PoseVec &x_stats, const VoxHess &voxhess, const std::vector<lvba_prior> &priors,
+                                            int device = 0)
 {
     std::vector<int64_t> off;
     std::vector<int32_t> idx;
@@ -64,6 +139,11 @@ std::vector<lvba_lm_trace> damping_iter_hip(PoseVec &x_stats, const VoxHess &vox
     lvba_balm_t h = nullptr;
     int32_t rc = lvba_balm_create(N, static_cast<int64_t>(off.size()) - 1, off.data(), idx.data(), clu.data(), device, &h);
     if (rc != LVBA_OK) throw std::runtime_error(std::string("lvba_balm_create: ") + lvba_last_error());
+    if (!priors.empty() && (rc = lvba_balm_set_priors(h, static_cast<int32_t>(priors.size()), priors.data())) != LVBA_OK) {
+        const std::string msg = lvba_last_error();
+        lvba_balm_destroy(h);
+        throw std::runtime_error("lvba_balm_set_priors: " + msg);
+    }
     lvba_balm_opts opts;
     lvba_balm_default_opts(&opts);                       // 10 iterations, u=0.01, v=2 (bavoxel.hpp:664,686)
     std::vector<lvba_lm_trace> trace(opts.max_iter);
@@ -80,6 +160,11 @@ std::vector<lvba_lm_trace> damping_iter_hip(PoseVec &x_stats, const VoxHess &vox
         for (int r = 0; r < 3; ++r) x_stats[j].p[r] = poses[12 * j + 9 + r];
     }
     return trace;
+}
+template <class PoseVec, class VoxHess>
+std::vector<lvba_lm_trace> damping_iter_hip(PoseVec &x_stats, const VoxHess &voxhess, int device = 0)
+{
+    return damping_iter_hip(x_stats, voxhess, std::vector<lvba_prior>(), device);
 }
 
 // RAII wrapper of the device-resident voxel map.  CloudPtrVec: sequence of (smart) pointers to clouds with
@@ -177,7 +262,20 @@ class VoxelMap {
 //       lvba_lidar_ba_opts o; lvba_lidar_ba_default_opts(&o);   // then copy window_ba_size_, anchor_leaf_size_, stage sizes ...
 //       lvba::lidar_ba(dataset_io_->pl_fulls_, dataset_io_->x_buf_, o);
 template <class CloudPtrVec, class PoseVec>
+lvba_lidar_ba_report lidar_ba(const CloudPtrVec &clouds, PoseVec &x_buf, const lvba_lidar_ba_opts &opts,
+                              const std::vector<lvba_prior> &frame_priors, int device = 0, int32_t *n_used = nullptr,
+                              int32_t *n_dropped = nullptr);
+template <class CloudPtrVec, class PoseVec>
 lvba_lidar_ba_report lidar_ba(const CloudPtrVec &clouds, PoseVec &x_buf, const lvba_lidar_ba_opts &opts, int device = 0)
+{
+    return lidar_ba(clouds, x_buf, opts, std::vector<lvba_prior>(), device);
+}
+
+// lidar_ba with pose priors on FRAMES (indices into x_buf): both global stages apply them to the anchors (lvba_lidar_ba_priors).
+// n_used / n_dropped (may be NULL): priors applied, and dropped (frames of skipped windows, relative priors inside one anchor).
+template <class CloudPtrVec, class PoseVec>
+lvba_lidar_ba_report lidar_ba(const CloudPtrVec &clouds, PoseVec &x_buf, const lvba_lidar_ba_opts &opts,
+                              const std::vector<lvba_prior> &frame_priors, int device, int32_t *n_used, int32_t *n_dropped)
 {
     const int32_t n = static_cast<int32_t>(x_buf.size());
     std::vector<const void *> ptr(n);
@@ -199,7 +297,9 @@ lvba_lidar_ba_report lidar_ba(const CloudPtrVec &clouds, PoseVec &x_buf, const l
     if (lvba_scans_create(device, n, ptr.data(), cnt.data(), stride, &scans) != LVBA_OK)
         throw std::runtime_error(std::string("lvba_scans_create: ") + lvba_last_error());
     lvba_lidar_ba_report rep;
-    const int32_t rc = lvba_lidar_ba(scans, poses.data(), &opts, poses.data(), &rep);
+    const int32_t rc = frame_priors.empty() ? lvba_lidar_ba(scans, poses.data(), &opts, poses.data(), &rep)
+                                            : lvba_lidar_ba_priors(scans, poses.data(), &opts, static_cast<int32_t>(frame_priors.size()),
+                                                                   frame_priors.data(), poses.data(), &rep, nullptr, n_used, n_dropped);
     lvba_scans_destroy(scans);
     if (rc != LVBA_OK) throw std::runtime_error(std::string("lvba_lidar_ba: ") + lvba_last_error());
     for (int32_t j = 0; j < n; ++j) {

@@ -193,6 +193,39 @@ int32_t lvba_balm_set_groups(lvba_balm_t h, int32_t n_groups, const int32_t *pos
 int32_t lvba_balm_refine_groups(lvba_balm_t h, double *poses_inout, const lvba_balm_opts *opts, int32_t *n_iter,
                                 int32_t *status, double *cost_first, double *cost_last);
 
+/* Pose priors (opt-in; none by default).  The LM then minimises
+ *     C(x) = sum_voxels lambda_min + sum_k 1/2 |L_k r_k(x)|^2
+ * with H, g the exact gradient and the Gauss-Newton Hessian of C; the averaged costs (is_avg, the trace's residual1/2,
+ * cost_avg) divide the whole sum by the voxel count.  With A = T_i O_i, B = T_j O_j (O = body-frame offset, R row-major | t like a
+ * pose; twelve zeros mean identity) and the residual order [rotation; position] of the tangent:
+ *   LVBA_PRIOR_POSE      r = [Log(Rm^T R_A); p_A - pm]                       meas = (Rm | pm)
+ *   LVBA_PRIOR_POSITION  r = p_A - z, 3 rows, top-left 3 x 3 of sqrt_info    meas[9..11] = z (meas[0..8] not read); p_O = lever arm
+ *   LVBA_PRIOR_RELATIVE  r = [Log(Rm^T R_A^T R_B); R_A^T (p_B - p_A) - pm]   meas = T_ij measured, i != j
+ * sqrt_info is the 6 x 6 square-root information matrix L, row-major.  Indices are caller pose indices.
+ *   lvba_balm_set_priors       n = 0 clears.  Before the first cost / eval / solve / refine call any pairs may be joined (a
+ *                              relative prior is an edge of the pose graph: ordering, band and dissection take it in); after it the
+ *                              priors may only be replaced if every relative pair is already a block of the store, else
+ *                              LVBA_ERR_STATE.  LVBA_ERR_ARG: unknown kind, index out of range, i == j for RELATIVE, a non-finite
+ *                              value, a measurement / offset rotation that is not orthonormal within 1e-6.  A refused call leaves
+ *                              the handle as it was.  A grouped handle (lvba_balm_set_groups) refuses priors (LVBA_ERR_STATE).
+ *                              Sharded handles: a collective call like cost / eval / refine -- every rank makes it, with the
+ *                              same priors; the next collective call checks that (one small all-reduce, also made once at the
+ *                              set-up of every sharded handle) and returns LVBA_ERR_ARG on every rank if they differ.
+ *                              At most 2^22 priors.
+ *   lvba_balm_prior_residuals  e [n][6] the whitened residuals L r (POSITION: e[k][0..2], e[k][3..5] = 0), cost = sum 1/2 |e|^2;
+ *                              either may be NULL. */
+#define LVBA_PRIOR_POSE 0
+#define LVBA_PRIOR_POSITION 1
+#define LVBA_PRIOR_RELATIVE 2
+typedef struct {
+    int32_t kind, i, j, reserved;
+    double meas[12];
+    double offset_i[12], offset_j[12];
+    double sqrt_info[36];
+} lvba_prior;
+int32_t lvba_balm_set_priors(lvba_balm_t h, int32_t n, const lvba_prior *priors);
+int32_t lvba_balm_prior_residuals(lvba_balm_t h, const double *poses, double *e, double *cost);
+
 /* Profiling (HIP events around the stages, on the stream the kernels are launched on). */
 int32_t lvba_balm_set_profiling(lvba_balm_t h, int32_t enable);
 int32_t lvba_balm_get_profile(lvba_balm_t h, lvba_prof_t *out, int32_t reset);
@@ -544,6 +577,18 @@ int32_t lvba_lidar_ba(lvba_scans_t scans, const double *poses_in, const lvba_lid
  * device, where the anchor clouds are gathered.  Needs window_enable = 1. */
 int32_t lvba_lidar_ba_multi(int32_t n_shares, const lvba_scans_t *scans, const double *poses_in, const lvba_lidar_ba_opts *opts,
                             double *poses_out, lvba_lidar_ba_report *report);
+
+/* The same two calls with pose priors on FRAMES (lvba_balm_set_priors; indices are frame indices of poses_in).  Both global
+ * stages apply them to the anchor problem: a frame f of anchor a with rel_f becomes a prior on a with offset rel_f o O, exactly.
+ * Priors on frames of skipped windows and relative priors whose two frames share one anchor (constant at this stage) are
+ * dropped.  anchor_priors [n_priors] (may be NULL) receives the n_used priors applied, in input order; n_used / n_dropped may be
+ * NULL.  The window stage takes no priors.  n_priors = 0: exactly lvba_lidar_ba / lvba_lidar_ba_multi. */
+int32_t lvba_lidar_ba_priors(lvba_scans_t scans, const double *poses_in, const lvba_lidar_ba_opts *opts, int32_t n_priors,
+                             const lvba_prior *priors, double *poses_out, lvba_lidar_ba_report *report, lvba_prior *anchor_priors,
+                             int32_t *n_used, int32_t *n_dropped);
+int32_t lvba_lidar_ba_multi_priors(int32_t n_shares, const lvba_scans_t *scans, const double *poses_in, const lvba_lidar_ba_opts *opts,
+                                   int32_t n_priors, const lvba_prior *priors, double *poses_out, lvba_lidar_ba_report *report,
+                                   lvba_prior *anchor_priors, int32_t *n_used, int32_t *n_dropped);
 
 /* Frame count and per-frame point counts of a scan set; host copy of one frame's xyz [count][3]. */
 int32_t lvba_scans_info(lvba_scans_t scans, int32_t *n_frames, int64_t *frame_count);
