@@ -15,7 +15,7 @@ SYMBOLS = [
     "lvba_balm_create", "lvba_balm_create_dev", "lvba_balm_destroy", "lvba_balm_configure", "lvba_balm_info", "lvba_balm_cost",
     "lvba_balm_eval", "lvba_balm_eval_blocks", "lvba_balm_solve", "lvba_balm_refine", "lvba_balm_lm_begin", "lvba_balm_lm_step",
     "lvba_balm_lm_end", "lvba_balm_set_groups", "lvba_balm_refine_groups", "lvba_balm_set_profiling", "lvba_balm_get_profile", "lvba_balm_get_ordering", "lvba_balm_nd_model",
-    "lvba_balm_set_priors", "lvba_balm_prior_residuals",
+    "lvba_balm_set_priors", "lvba_balm_prior_residuals", "lvba_cov_default_opts", "lvba_balm_covariance",
     "lvba_dist_unique_id", "lvba_balm_dist_init", "lvba_balm_dist_init_external", "lvba_visual_dist_init_external",
     "lvba_visual_default_opts", "lvba_visual_create", "lvba_visual_destroy", "lvba_visual_cost", "lvba_visual_linearize", "lvba_visual_info", "lvba_visual_dist_init",
     "lvba_visual_refine", "lvba_visual_set_loss", "lvba_visual_residual_sq",
@@ -31,6 +31,10 @@ SYMBOLS = [
 
 OK, ERR_ARG, ERR_DEVICE, ERR_NOMEM, ERR_UNSUPPORTED, ERR_DIST, ERR_STATE = 0, -1, -2, -3, -4, -5, -6
 NUM_FACTORIZATION, NUM_NONFINITE = 1, 2
+
+
+class CovOpts(C.Structure):
+    _fields_ = [("anchor", C.c_int32), ("reserved", C.c_int32), ("min_pivot_ratio", C.c_double)]
 
 
 class BalmOpts(C.Structure):
@@ -213,6 +217,10 @@ def load():
     lib.lvba_balm_nd_model.argtypes = [H, C.c_int32, C.POINTER(NdModel)]
     lib.lvba_balm_set_priors.argtypes = [H, C.c_int32, C.c_void_p]
     lib.lvba_balm_prior_residuals.argtypes = [H, f64p, C.c_void_p, C.POINTER(C.c_double)]
+    lib.lvba_cov_default_opts.argtypes = [C.POINTER(CovOpts)]
+    lib.lvba_cov_default_opts.restype = None
+    lib.lvba_balm_covariance.argtypes = [H, f64p, C.POINTER(CovOpts), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]
     lib.lvba_dist_unique_id.argtypes = [C.c_char_p]
     lib.lvba_balm_dist_init_external.argtypes = [H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.lvba_visual_dist_init_external.argtypes = [H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]

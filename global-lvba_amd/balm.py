@@ -249,6 +249,31 @@ class BalmProblem:
         L.check(self.lib.lvba_balm_prior_residuals(self._h, self._poses(poses), e.ctypes.data, C.byref(c)))
         return e[:n], c.value
 
+    def covariance(self, poses, anchor=None, pairs=None, min_pivot_ratio=1e-10, scale=1.0):
+        """Marginal pose covariance Sigma = H(poses)^-1 (lvba_balm_covariance): the inverse Hessian of the cost the LM minimises,
+        in the tangent [dphi; dp] of each pose, caller order.  anchor: a pose held fixed (its blocks come back as zeros), or None
+        when priors fix the frame.  pairs: (K, 2) caller indices i != j.  scale multiplies every block (Sigma is in the cost's
+        units; a noise variance turns it into a metric covariance).  Returns (diag [N, 6, 6], pair_blocks [K, 6, 6], avail [K]):
+        avail[k] is False for a pair outside the solver's band, whose block is NaN."""
+        x = self._poses(poses)
+        o = L.CovOpts()
+        self.lib.lvba_cov_default_opts(C.byref(o))
+        o.anchor = -1 if anchor is None else int(anchor)
+        o.min_pivot_ratio = float(min_pivot_ratio)
+        pr = np.ascontiguousarray(np.zeros((0, 2)) if pairs is None else pairs, np.int32).reshape(-1, 2)
+        K = pr.shape[0]
+        pi, pj = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+        diag = np.empty((self.n_poses, 6, 6))
+        blocks = np.empty((K, 6, 6))
+        avail = np.zeros(K, np.uint8)
+        L.check(self.lib.lvba_balm_covariance(self._h, x, C.byref(o), diag.ctypes.data, K, pi.ctypes.data if K else None,
+                                              pj.ctypes.data if K else None, blocks.ctypes.data if K else None,
+                                              avail.ctypes.data if K else None))
+        if scale != 1.0:
+            diag *= scale
+            blocks *= scale
+        return diag, blocks, avail.astype(bool)
+
     def set_groups(self, pose_off, voxel_off):
         """Independent groups of poses / voxels (lvba_balm_set_groups); before the first cost / eval / refine call."""
         po = np.ascontiguousarray(pose_off, dtype=np.int32)

@@ -42,6 +42,7 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 #include "ldlt_tiles.h"
 #include "ldlt_lookahead.h"
 #include "ldlt_back.h"
+#include "ldlt_selinv.h"
 
 // ------------------------------------------------------------------------------------------- driver
 static inline int64_t ldz_for(int64_t n, int64_t bw)
@@ -86,11 +87,12 @@ int64_t ldlt_twist_panels(int64_t n, int64_t ld, int64_t bw)
 // single-GPU one but moves one window per launch instead of two; what is replicated is the S phase only.
 int32_t ldlt_solve(const LdltMat &A, const double *Hblk, int band_blocks, int n_poses, const double *g,
                    const double *u_dev, double *x, double *work, int *status, hipStream_t s, const LdltDist *dist, const int32_t *grp,
-                   int phase, const LdltBorder *border)
+                   int phase, const LdltBorder *border, int64_t anchor_col)
 {
     const int64_t n = A.n, bw = A.bw;
     const int64_t P1 = twist_panels_of(A);
     if (phase != LDLT_ALL && (P1 > 0 || dist)) return LVBA_ERR_STATE; // the halves exist for plain single-rank factorisations
+    if (anchor_col >= 0 && P1 > 0) return LVBA_ERR_STATE;
     LdltTwist tw;
     tw.m = P1 * LVBA_NB; tw.n1 = n - tw.m;
     tw.sA = (A.ld + 1) * (n + 1); tw.sW = ldlt_ws_one(n, bw);
@@ -140,6 +142,8 @@ int32_t ldlt_solve(const LdltMat &A, const double *Hblk, int band_blocks, int n_
         hipMemsetAsync(A.a, 0, P1 > 0 ? (size_t)tw.sA * sizeof(double) + abytes : abytes, s);
     hipLaunchKernelGGL(ldlt_prepare_kernel, dim3(fill ? 64 : 2048), dim3(256), 0, s, A, Hblk, band_blocks, n_poses, g, u_dev, b,
                        reinterpret_cast<unsigned long long *>(x), (unsigned long long)LVBA_X_SENTINEL, tw, grp, fill ? 1 : 0, status);
+    if (anchor_col >= 0)
+        hipLaunchKernelGGL(ldlt_anchor_kernel, dim3((unsigned)((12 * (A.ld + 1) + 255) / 256)), dim3(256), 0, s, A, anchor_col);
     struct Geo { int64_t k, w0, rend, T; int nbe; };
     auto geom = [&](int64_t st) {
         Geo q;
@@ -323,6 +327,58 @@ int32_t ldlt_solve(const LdltMat &A, const double *Hblk, int band_blocks, int n_
         if (dist->allreduce_max_i32(dist->ctx, status)) return LVBA_ERR_DIST;
     }
     return LVBA_OK;
+}
+
+// ---- the covariance (lvba_balm_covariance): pivot test, selected inversion, gather (ldlt_selinv.h)
+static inline int64_t selinv_tiles(int64_t n, int64_t bw) { return (std::min(bw, n) + 63) / 64 + 1; }
+int64_t ldlt_selinv_scratch_doubles(int64_t n, int64_t bw)
+{
+    return selinv_tiles(n, bw) * (LVBA_SI_KSMAX + 1) * 4096 + 64;
+}
+void ldlt_cov_pivot_check(const LdltMat &A, const double *Hblk, int band_blocks, const double *work, int64_t anchor_col, double ratio,
+                          const int *status, int *flag, hipStream_t s)
+{
+    hipLaunchKernelGGL(ldlt_cov_pivot_kernel, dim3((unsigned)((A.n + 255) / 256)), dim3(256), 0, s, Hblk, band_blocks, A.n,
+                       (const double *)ldlt_work_d(A.n, const_cast<double *>(work)), anchor_col, ratio, status, flag);
+}
+// Three launches per panel, last panel to first (each panel reads the Z entries of the panels after it).
+void ldlt_selinv(const LdltMat &A, double *z, const double *work, double *scratch, hipStream_t s)
+{
+    const int64_t n = A.n, bw = A.bw, nsteps = (n + LVBA_NB - 1) / LVBA_NB, Tm = selinv_tiles(n, bw);
+    SelinvPanel p{};
+    p.z = z; p.a = A.a; p.ld = A.ld; p.n = n;
+    p.xpart = scratch; p.qpart = scratch + Tm * LVBA_SI_KSMAX * 4096;
+    const double *G = ldlt_work_G(const_cast<double *>(work)), *d = ldlt_work_d(n, const_cast<double *>(work));
+    for (int64_t st = nsteps - 1; st >= 0; --st) {
+        p.k = st * LVBA_NB;
+        p.nbe = (int)std::min<int64_t>(LVBA_NB, n - p.k);
+        p.w0 = p.k + p.nbe;
+        p.rend = std::min<int64_t>(p.k + p.nbe + bw, n);
+        const int64_t nw = p.rend > p.w0 ? p.rend - p.w0 : 0;
+        p.T = (int)((nw + 63) / 64);
+        p.KS = 1; p.ksz = nw;
+        if (p.T > 0) { // enough workgroups to fill the device, slices of >= 128 inner indices (whole steps of 64)
+            int64_t ks = std::max<int64_t>(1, std::min<int64_t>({(int64_t)LVBA_SI_KSMAX, nw / 128, 256 / p.T}));
+            p.ksz = ((nw + ks - 1) / ks + 63) / 64 * 64;
+            p.KS = (int)((nw + p.ksz - 1) / p.ksz);
+        }
+        p.G = G + st * 4096; p.d = d + p.k;
+        if (p.T > 0) {
+            p.stage = 0;
+            hipLaunchKernelGGL(ldlt_selinv_panel_kernel, dim3((unsigned)(p.T * p.KS)), dim3(256), 0, s, p);
+            p.stage = 1;
+            hipLaunchKernelGGL(ldlt_selinv_panel_kernel, dim3((unsigned)p.T), dim3(256), 0, s, p);
+        }
+        p.stage = 2;
+        hipLaunchKernelGGL(ldlt_selinv_panel_kernel, dim3(1), dim3(256), 0, s, p);
+    }
+}
+void ldlt_cov_gather(const double *z, int64_t ld, int band_blocks, const int32_t *iperm, int N, int anchor, int64_t n_pairs,
+                     const int32_t *pi, const int32_t *pj, double *diag, double *blk, uint8_t *avail, hipStream_t s)
+{
+    const int64_t tot = ((int64_t)N + n_pairs) * 36;
+    hipLaunchKernelGGL(ldlt_cov_gather_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, z, ld, band_blocks, iperm, N, anchor,
+                       n_pairs, pi, pj, diag, blk, avail);
 }
 
 #include "ldlt_nd.h"

@@ -663,6 +663,124 @@ extern "C" int32_t lvba_balm_solve(lvba_balm_t h, double u, double *dx)
     return LVBA_OK;
 }
 
+// ------------------------------------------------------------------------------------------ marginal covariance
+extern "C" void lvba_cov_default_opts(lvba_cov_opts *o)
+{
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    o->anchor = -1;
+    o->min_pivot_ratio = 1e-10;
+}
+
+// Sigma = H^-1 at `poses` (include/lvba_hip.h): the evaluation, the band fill with u = 0 and the anchor, a one-ended LDL^T, its pivot
+// test, the selected inversion on the band of the factor and the gather (ldlt_selinv.h).  Sharded handles all-reduce H in the
+// evaluation and then run the rest on their own copy: every rank computes the same bits.
+extern "C" int32_t lvba_balm_covariance(lvba_balm_t h, const double *poses, const lvba_cov_opts *opts, double *diag, int64_t n_pairs,
+                                        const int32_t *pi, const int32_t *pj, double *blocks, uint8_t *avail)
+{
+    if (!h || !poses) return fail(LVBA_ERR_ARG, "NULL argument");
+    if (n_pairs < 0 || (n_pairs > 0 && (!pi || !pj || !blocks || !avail))) return fail(LVBA_ERR_ARG, "NULL pair arrays");
+    lvba_cov_opts o;
+    lvba_cov_default_opts(&o);
+    if (opts) o = *opts;
+    const int32_t N = h->N;
+    if (o.anchor < -1 || o.anchor >= N) return fail(LVBA_ERR_ARG, "anchor %d out of range [-1, %d)", o.anchor, N);
+    if (!(o.min_pivot_ratio >= 0.0) || !isfinite(o.min_pivot_ratio)) return fail(LVBA_ERR_ARG, "min_pivot_ratio must be finite and >= 0");
+    for (int64_t k = 0; k < n_pairs; ++k)
+        if (pi[k] < 0 || pi[k] >= N || pj[k] < 0 || pj[k] >= N || pi[k] == pj[k])
+            return fail(LVBA_ERR_ARG, "pair %lld (%d, %d): indices out of range or equal", (long long)k, pi[k], pj[k]);
+    if (h->lm_active) return fail(LVBA_ERR_STATE, "lvba_balm_covariance between lm_begin and lm_end");
+    if (h->n_groups > 0) return fail(LVBA_ERR_UNSUPPORTED, "lvba_balm_covariance: grouped handles are not supported");
+    TRY(finalize(h));
+    BlockSys &bs = h->bs;
+    if (bs.nd.active) return fail(LVBA_ERR_UNSUPPORTED, "lvba_balm_covariance: dissected handles (nd_kind != 0) are not supported");
+    if (bs.d_bcr || !bs.d_A || !bs.d_work) return fail(LVBA_ERR_UNSUPPORTED, "lvba_balm_covariance: no LDL^T store on this handle");
+    TRY(prior_sync(h));
+    HIPCHK(hipSetDevice(bs.device));
+    const bool timing = timing_on("cov", true);
+    hipEvent_t tev[5] = {};
+    if (timing)
+        for (hipEvent_t &e : tev) HIPCHK(hipEventCreate(&e));
+    struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int i = 0; i < 5; ++i) if (e[i]) hipEventDestroy(e[i]); } } evg{tev};
+    auto mark = [&](int i) { if (timing) hipEventRecord(tev[i], bs.stream); };
+    const int64_t n = 6 * (int64_t)N;
+    LdltMat A = bs.A;
+    A.no_twist = 1;
+    const bool band = A.ld != n;
+    const int64_t anchor_col = o.anchor >= 0 ? 6 * (int64_t)bs.iperm[(size_t)o.anchor] : -1;
+    // device scratch: the selected inversion's partial products | u = 0 | pivot flag | iperm | pair indices | outputs
+    const int64_t ns = ldlt_selinv_scratch_doubles(n, A.bw);
+    const int64_t nout = ((int64_t)N + n_pairs) * 36;
+    const int64_t nint = (int64_t)N + 2 * n_pairs + 2 * 64, nbytes8 = (n_pairs + 7) / 8 + 8;
+    DevBuf scr(bs.stream), zd(bs.stream);
+    HIPCHK(scr.alloc((size_t)(ns + 8 + nout + nbytes8) * sizeof(double) + (size_t)nint * sizeof(int32_t)));
+    double *d_sc = scr.as<double>(), *d_zero = d_sc + ns, *d_out = d_zero + 8;
+    uint8_t *d_av = reinterpret_cast<uint8_t *>(d_out + nout);
+    int32_t *d_i32 = reinterpret_cast<int32_t *>(d_out + nout + nbytes8);
+    int *d_flag = d_i32, *d_iperm = d_i32 + 64, *d_pi = d_iperm + N + 64, *d_pj = d_pi + n_pairs;
+    HIPCHK(hipMemsetAsync(d_zero, 0, 8 * sizeof(double), bs.stream)); // u = 0
+    HIPCHK(hipMemsetAsync(d_flag, 0, sizeof(int), bs.stream));
+    HIPCHK(hipMemcpyAsync(d_iperm, bs.iperm.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, bs.stream));
+    if (n_pairs > 0) {
+        HIPCHK(hipMemcpyAsync(d_pi, pi, (size_t)n_pairs * sizeof(int32_t), hipMemcpyHostToDevice, bs.stream));
+        HIPCHK(hipMemcpyAsync(d_pj, pj, (size_t)n_pairs * sizeof(int32_t), hipMemcpyHostToDevice, bs.stream));
+    }
+    // Z: the second-matrix slot of the band store (unused by a one-ended factorisation); its own buffer for dense storage
+    double *z = nullptr;
+    if (band) z = bs.d_A + (A.ld + 1) * (n + 1);
+    else {
+        HIPCHK(zd.alloc((size_t)(n * n + 64) * sizeof(double)));
+        z = zd.as<double>();
+    }
+    // the band store must read as zero outside what the damped solve rewrites (block_system.hip): zeroed again on every way out
+    const size_t band_bytes = band ? (size_t)(2 * ((A.ld + 1) * (n + 1)) + 65 * (A.ld + 1)) * sizeof(double) : 0;
+    struct BandGuard { double *p; size_t b; hipStream_t s; ~BandGuard() { if (p) (void)hipMemsetAsync(p, 0, b, s); } } bandg{band ? bs.d_A : nullptr, band_bytes, bs.stream};
+    mark(0);
+    TRY(upload_poses(h, poses, h->d_pose_cur));
+    h->lin_at_cur = false;
+    TRY(enqueue_eval(h, h->d_pose_cur));
+    h->have_eval = false; // the solver's workspace now holds the covariance's factor: a later solve needs a fresh evaluation
+    mark(1);
+    TRY(ldlt_solve(A, bs.Hblk(), bs.Bb, N, bs.g(), d_zero, bs.d_dx, bs.d_work, bs.d_status, bs.stream, nullptr, nullptr, LDLT_FACTOR,
+                   nullptr, anchor_col));
+    ldlt_cov_pivot_check(A, bs.Hblk(), bs.Bb, bs.d_work, anchor_col, o.min_pivot_ratio, bs.d_status, d_flag, bs.stream);
+    mark(2);
+    int *h_flag = reinterpret_cast<int *>(h->h_pin);
+    HIPCHK(hipMemcpyAsync(h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, bs.stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(bs.stream));
+    ev_collect(h);
+    if (*h_flag) return fail(LVBA_NUM_FACTORIZATION, "lvba_balm_covariance: H is not positive definite at these poses (pivot test "
+                                                     "failed; no anchor and no priors that fix the frame, or not at a minimum)");
+    mark(3);
+    ldlt_selinv(A, z, bs.d_work, d_sc, bs.stream);
+    mark(4);
+    ldlt_cov_gather(z, A.ld, band ? bs.Bb : -1, d_iperm, N, o.anchor, n_pairs, d_pi, d_pj, d_out, d_out + (int64_t)N * 36, d_av, bs.stream);
+    HIPCHK(hipGetLastError());
+    if (diag) HIPCHK(hipMemcpyAsync(diag, d_out, (size_t)N * 36 * sizeof(double), hipMemcpyDeviceToHost, bs.stream));
+    if (n_pairs > 0) {
+        HIPCHK(hipMemcpyAsync(blocks, d_out + (int64_t)N * 36, (size_t)n_pairs * 36 * sizeof(double), hipMemcpyDeviceToHost, bs.stream));
+        HIPCHK(hipMemcpyAsync(avail, d_av, (size_t)n_pairs, hipMemcpyDeviceToHost, bs.stream));
+    }
+    HIPCHK(hipStreamSynchronize(bs.stream));
+    if (timing) {
+        // (the gather's time includes the download of the blocks)
+        hipEvent_t e5 = nullptr;
+        HIPCHK(hipEventCreate(&e5));
+        hipEventRecord(e5, bs.stream);
+        hipEventSynchronize(e5);
+        float t[4] = {};
+        hipEventElapsedTime(&t[0], tev[0], tev[1]);
+        hipEventElapsedTime(&t[1], tev[1], tev[2]);
+        hipEventElapsedTime(&t[2], tev[3], tev[4]);
+        hipEventElapsedTime(&t[3], tev[4], e5);
+        hipEventDestroy(e5);
+        fprintf(stderr, "lvba cov: eval %.3f ms factor %.3f ms selinv %.3f ms gather %.3f ms (n %lld, bw %lld, %s)\n", t[0], t[1], t[2],
+                t[3], (long long)n, (long long)A.bw, band ? "band" : "dense");
+    }
+    return LVBA_OK;
+}
+
 // ------------------------------------------------------------------------------------------ a8: LM
 extern "C" int32_t lvba_balm_lm_begin(lvba_balm_t h, const double *poses, const lvba_balm_opts *opts)
 {

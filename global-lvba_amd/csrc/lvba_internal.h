@@ -131,7 +131,7 @@ inline bool solver_form(const char *name)
 }
 
 // LVBA_TIMING = comma-separated parts whose stage times go to stderr: build (bs_build, finalize, create), window (window_ba.hip),
-// vis (the visual refinement's phases); "1" or "all": every part.
+// vis (the visual refinement's phases); "1" or "all": every part.  cov (lvba_balm_covariance's stages) only when named.
 inline bool timing_on(const char *part, bool named_only = false) // named_only: the part must be listed itself ("1" / "all" do not count)
 {
     const char *e = getenv("LVBA_TIMING");
@@ -272,7 +272,18 @@ int32_t ldlt_solve(const LdltMat &A, const double *Hblk, int band_blocks, int n_
                    const double *u_dev, double *x, double *work, int *status, hipStream_t s, const LdltDist *dist = nullptr,
                    const int32_t *grp = nullptr, // grp: pose block -> entry of u_dev (grouped refinement)
                    int phase = LDLT_ALL,         // LDLT_FACTOR / LDLT_BACKWARD: the two halves of a solve (single rank, A.no_twist)
-                   const LdltBorder *border = nullptr);
+                   const LdltBorder *border = nullptr,
+                   int64_t anchor_col = -1);      // >= 0: after the fill, the six columns from anchor_col become the identity's
+                                                  // (lvba_balm_covariance; plain top-down factorisations only)
+// lvba_balm_covariance (ldlt_selinv.h): after ldlt_solve(no_twist A, u = 0, LDLT_FACTOR, anchor_col) -- the pivot test (flag[0] |= 1 on
+// a failure; flag zeroed by the caller), the selected inverse Z of the factor into z (a store of A's shape; scratch of
+// ldlt_selinv_scratch_doubles), and the blocks of the caller's pose pairs from it
+int64_t ldlt_selinv_scratch_doubles(int64_t n, int64_t bw);
+void ldlt_cov_pivot_check(const LdltMat &A, const double *Hblk, int band_blocks, const double *work, int64_t anchor_col, double ratio,
+                          const int *status, int *flag, hipStream_t s);
+void ldlt_selinv(const LdltMat &A, double *z, const double *work, double *scratch, hipStream_t s);
+void ldlt_cov_gather(const double *z, int64_t ld, int band_blocks, const int32_t *iperm, int N, int anchor, int64_t n_pairs,
+                     const int32_t *pi, const int32_t *pj, double *diag, double *blk, uint8_t *avail, hipStream_t s);
 
 // bcr.hip: block cyclic reduction for narrow-band SPD systems (the visual stage's reduced camera system)
 bool bcr_applicable(int n_poses, int band_blocks);

@@ -226,6 +226,41 @@ typedef struct {
 int32_t lvba_balm_set_priors(lvba_balm_t h, int32_t n, const lvba_prior *priors);
 int32_t lvba_balm_prior_residuals(lvba_balm_t h, const double *poses, double *e, double *cost);
 
+/* Marginal pose covariance (opt-in).
+ *   C(x) = sum_voxels lambda_min + sum_k 1/2 |L_k r_k(x)|^2 is the cost the LM minimises (the priors above).  H(x) is its Hessian
+ *   exactly as lvba_balm_eval forms it: the exact second-order voxel part plus the Gauss-Newton prior part, undamped (u = 0), not
+ *   averaged.
+ *   The covariance returned is Sigma = H(x)^-1 in the tangent of BALM's retraction (R <- R Exp(dphi), p <- p + dp, order
+ *   [dphi; dp], bavoxel.hpp:723-727), in the caller's pose order.
+ *   The gauge is fixed in one of two ways:
+ *     anchor >= 0  that caller pose is held fixed: its rows and columns are removed, which is equivalent to replacing them by the
+ *                  identity and zero couplings before factorising.  The anchor's own block (and its pair blocks) are returned
+ *                  as zeros.
+ *     anchor = -1  H itself must be positive definite, for example because priors fix the frame.
+ *   The result is the inverse Hessian of C in C's units.  Turning it into a metric covariance needs a noise model: lambda_min is a
+ *   mean squared point-to-plane distance per voxel, not a whitened residual, so Sigma is not a covariance in metres / radians
+ *   until the caller scales it by the noise variance it believes in.
+ * diag [n_poses][36] row-major (may be NULL); for each requested pair k (i != j, caller indices) blocks[k][6r+c] =
+ * Cov(delta_i[r], delta_j[c]) and avail[k] = 1 if the pair lies in the handle's band (every pair that shares a voxel or a relative
+ * prior does), else avail[k] = 0 and the block is NaN.  Collective on sharded handles (every rank makes the call; results are
+ * bitwise equal on all ranks).
+ *   LVBA_NUM_FACTORIZATION  a pivot d_i <= min_pivot_ratio * A_ii or non-finite: H is not positive definite at these poses (free
+ *                           gauge, or not at a minimum).  Nothing is written to the outputs.
+ *   LVBA_ERR_ARG            anchor or a pair index out of range, or i == j.
+ *   LVBA_ERR_STATE          between lvba_balm_lm_begin and lvba_balm_lm_end.
+ *   LVBA_ERR_UNSUPPORTED    grouped (lvba_balm_set_groups) or dissected (nd_kind != 0) handles.
+ * Like lvba_balm_eval the call replaces the handle's last evaluation; a later lvba_balm_solve needs a fresh lvba_balm_eval.
+ * Nothing else changes: a refinement after a covariance call gives bitwise the poses it gives without one. */
+typedef struct {
+    int32_t anchor;            /* caller pose held fixed, or -1: H must be positive definite (priors fix the frame) */
+    int32_t reserved;
+    double  min_pivot_ratio;   /* refuse if a pivot d_i <= min_pivot_ratio * A_ii or is non-finite; default 1e-10 */
+} lvba_cov_opts;
+void lvba_cov_default_opts(lvba_cov_opts *o);
+int32_t lvba_balm_covariance(lvba_balm_t h, const double *poses, const lvba_cov_opts *opts,
+                             double *diag, int64_t n_pairs, const int32_t *pi, const int32_t *pj,
+                             double *blocks, uint8_t *avail);
+
 /* Profiling (HIP events around the stages, on the stream the kernels are launched on). */
 int32_t lvba_balm_set_profiling(lvba_balm_t h, int32_t enable);
 int32_t lvba_balm_get_profile(lvba_balm_t h, lvba_prof_t *out, int32_t reset);
