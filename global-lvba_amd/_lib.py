@@ -16,13 +16,14 @@ SYMBOLS = [
     "lvba_balm_eval", "lvba_balm_eval_blocks", "lvba_balm_solve", "lvba_balm_refine", "lvba_balm_lm_begin", "lvba_balm_lm_step",
     "lvba_balm_lm_end", "lvba_balm_set_groups", "lvba_balm_refine_groups", "lvba_balm_set_profiling", "lvba_balm_get_profile", "lvba_balm_get_ordering", "lvba_balm_nd_model",
     "lvba_balm_set_priors", "lvba_balm_prior_residuals", "lvba_cov_default_opts", "lvba_balm_covariance",
+    "lvba_balm_set_loss", "lvba_balm_voxel_residuals",
     "lvba_dist_unique_id", "lvba_balm_dist_init", "lvba_balm_dist_init_external", "lvba_visual_dist_init_external",
     "lvba_visual_default_opts", "lvba_visual_create", "lvba_visual_destroy", "lvba_visual_cost", "lvba_visual_linearize", "lvba_visual_info", "lvba_visual_dist_init",
     "lvba_visual_refine", "lvba_visual_set_loss", "lvba_visual_residual_sq",
     "lvba_voxel_default_opts", "lvba_voxmap_build", "lvba_voxmap_destroy", "lvba_voxmap_info", "lvba_voxmap_export",
     "lvba_voxmap_to_balm", "lvba_voxmap_find_planes", "lvba_scans_create", "lvba_scans_destroy", "lvba_voxmap_build_scans",
     "lvba_release_cached_memory", "lvba_window_default_opts", "lvba_window_ba", "lvba_window_split", "lvba_window_ba_multi", "lvba_scans_info", "lvba_scans_download",
-    "lvba_lidar_ba_default_opts", "lvba_lidar_ba", "lvba_lidar_ba_multi", "lvba_lidar_ba_priors", "lvba_lidar_ba_multi_priors", "lvba_triangulate_tracks",
+    "lvba_lidar_ba_default_opts", "lvba_lidar_ba", "lvba_lidar_ba_multi", "lvba_lidar_ba_priors", "lvba_lidar_ba_multi_priors", "lvba_lidar_ba_robust", "lvba_triangulate_tracks",
     "lvba_depth_render", "lvba_depth_upload", "lvba_depth_info", "lvba_depth_download", "lvba_depth_destroy",
     "lvba_fuse_default_opts", "lvba_fuse_tracks",
     "lvba_colorize_default_opts", "lvba_colorize_create", "lvba_colorize_add_images", "lvba_colorize_count",
@@ -102,8 +103,20 @@ LOSS_KINDS = {"trivial": 0, "huber": 1, "softlone": 2, "cauchy": 3, "arctan": 4,
 
 
 class Loss(C.Structure):
-    """lvba_loss: kind (LVBA_LOSS_*), scale a in whitened residual units."""
+    """lvba_loss: kind (LVBA_LOSS_*), scale a (visual stage: whitened residual units; LiDAR stage: metres)."""
     _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("scale", C.c_double)]
+
+
+def loss_struct(loss):
+    """None -> NULL (TRIVIAL); (kind, scale) -> a pointer to an lvba_loss.  Shared by VisualProblem.set_loss, BalmProblem.set_loss
+    and the pipeline's LiDAR losses."""
+    if loss is None:
+        return None
+    kind, scale = loss
+    k = LOSS_KINDS.get(str(kind).lower()) if isinstance(kind, str) else int(kind)
+    if k is None:
+        raise ValueError(f"unknown loss kind {kind!r}; one of {sorted(LOSS_KINDS)}")
+    return C.pointer(Loss(k, 0, float(scale)))
 
 
 class FuseOpts(C.Structure):
@@ -221,6 +234,8 @@ def load():
     lib.lvba_cov_default_opts.restype = None
     lib.lvba_balm_covariance.argtypes = [H, f64p, C.POINTER(CovOpts), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p]
+    lib.lvba_balm_set_loss.argtypes = [H, C.POINTER(Loss)]
+    lib.lvba_balm_voxel_residuals.argtypes = [H, f64p, C.c_void_p, C.c_void_p]
     lib.lvba_dist_unique_id.argtypes = [C.c_char_p]
     lib.lvba_balm_dist_init_external.argtypes = [H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.lvba_visual_dist_init_external.argtypes = [H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
@@ -267,6 +282,8 @@ def load():
                                          C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.lvba_lidar_ba_multi_priors.argtypes = [C.c_int32, C.POINTER(H), f64p, C.POINTER(LidarBaOpts), C.c_int32, C.c_void_p, f64p,
                                                C.POINTER(LidarBaReport), C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.lvba_lidar_ba_robust.argtypes = [C.c_int32, C.POINTER(H), f64p, C.POINTER(LidarBaOpts), C.POINTER(Loss), C.POINTER(Loss), C.c_int32,
+                                         C.c_void_p, f64p, C.POINTER(LidarBaReport), C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.lvba_triangulate_tracks.argtypes = [C.c_int32, C.c_int32, C.c_int64, i64p, C.c_void_p, C.c_void_p, f64p, f64p, f64p, f64p,
                                             f64p, i32p, u8p]
     lib.lvba_depth_render.argtypes = [C.c_void_p, f64p, f64p, C.c_int32, f64p, f64p, f64p, f64p, C.c_int32, C.c_int32, C.c_double,

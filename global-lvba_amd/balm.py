@@ -249,6 +249,19 @@ class BalmProblem:
         L.check(self.lib.lvba_balm_prior_residuals(self._h, self._poses(poses), e.ctypes.data, C.byref(c)))
         return e[:n], c.value
 
+    def set_loss(self, loss=None):
+        """Robust loss on the voxel costs (lvba_balm_set_loss): None (the default, plain sum of lambda_min) or (kind, scale) with
+        kind one of "trivial", "huber", "softlone", "cauchy", "arctan", "tukey" (or an LVBA_LOSS_* integer) and the scale a in
+        metres -- a voxel is down-weighted when its RMS plane distance exceeds a (not "arctan": see include/lvba_hip.h).  Not between lm_begin and lm_end."""
+        L.check(self.lib.lvba_balm_set_loss(self._h, L.loss_struct(loss)))
+
+    def voxel_residuals(self, poses):
+        """(lambda_min [n_voxels], weight [n_voxels] = rho'(lambda_min)) at `poses`, in the order the voxels were given to the
+        constructor (lvba_balm_voxel_residuals); every weight is 1 without a loss."""
+        lam, w = np.empty(self.n_voxels), np.empty(self.n_voxels)
+        L.check(self.lib.lvba_balm_voxel_residuals(self._h, self._poses(poses), lam.ctypes.data, w.ctypes.data))
+        return lam, w
+
     def covariance(self, poses, anchor=None, pairs=None, min_pivot_ratio=1e-10, scale=1.0):
         """Marginal pose covariance Sigma = H(poses)^-1 (lvba_balm_covariance): the inverse Hessian of the cost the LM minimises,
         in the tangent [dphi; dp] of each pose, caller order.  anchor: a pose held fixed (its blocks come back as zeros), or None

@@ -23,6 +23,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "balm_math.h"
+#include "visual_loss.h"
 #include "lvba_internal.h"
 
 namespace lvba {
@@ -42,6 +43,16 @@ __device__ __forceinline__ double block_sum_256(double x, double *red)
     if (lane == 0) red[wv] = x;
     __syncthreads();
     return red[0] + red[1] + red[2] + red[3];
+}
+
+// Robust voxel cost (lvba_balm_set_loss): rho(lambda_min) of the handle's loss, w = rho'(lambda_min).  Only the ROBUST instantiations
+// of the kernels below call it: a handle without a loss runs the kernels it always ran, with no loss arithmetic in them.
+__device__ __forceinline__ double voxel_loss(const BalmDev &d, double lam, double &w)
+{
+    double rho[3];
+    loss_eval(d.loss_kind, d.loss_scale, lam, rho);
+    w = rho[1];
+    return rho[0];
 }
 
 // A voxel observed by more poses than a workgroup has lanes sits alone in its chunk and is merged in tiles of LVBA_CF
@@ -87,6 +98,7 @@ __device__ __forceinline__ void merge_big_voxel(const BalmDev &d, const double *
 // cost only: sum of lambda_min per chunk.  Algorithmic traffic 84 B/factor (80 B cluster + 4 B pose
 // index) -> HBM-bound.  LDS: transformed statistics SoA T[10][CF].
 // ------------------------------------------------------------------------------------------------
+template <bool ROBUST>
 __global__ __launch_bounds__(LVBA_CF) void balm_cost_kernel(BalmDev d, const double *__restrict__ poses,
                                                            double *__restrict__ chunk_cost)
 {
@@ -101,7 +113,11 @@ __global__ __launch_bounds__(LVBA_CF) void balm_cost_kernel(BalmDev d, const dou
     if (nf > LVBA_CF) { // one voxel with more observers than lanes (uniform branch)
         double S[10];
         merge_big_voxel(d, poses, f0, nf, T, S);
-        if (tid == 0) chunk_cost[ch] = voxel_lambda_min(S);
+        if (tid == 0) {
+            double lam = voxel_lambda_min(S), w;
+            if constexpr (ROBUST) lam = voxel_loss(d, lam, w);
+            chunk_cost[ch] = lam;
+        }
         return;
     }
     if (tid <= nv) lvoff[tid] = (int)(d.voff[v0 + tid] - f0);
@@ -133,9 +149,65 @@ __global__ __launch_bounds__(LVBA_CF) void balm_cost_kernel(BalmDev d, const dou
             for (int e = 0; e < 10; ++e) S[e] += T[e * LVBA_CF + f];
         }
         lam0 = voxel_lambda_min(S);
+        if constexpr (ROBUST) { double w; lam0 = voxel_loss(d, lam0, w); }
     }
     const double tot = block_sum_256(lam0, red);
     if (tid == 0) chunk_cost[ch] = tot;
+}
+
+// lvba_balm_voxel_residuals: lambda_min and the weight rho'(lambda_min) of every voxel (the loads of balm_cost_kernel; not on the LM
+// path).  order != nullptr: voxel v of the handle's layout is voxel order[v] of the caller's (the re-layout of balm_create_impl).
+__global__ __launch_bounds__(LVBA_CF) void balm_voxel_resid_kernel(BalmDev d, const double *__restrict__ poses, const int64_t *__restrict__ order,
+                                                                  double *__restrict__ lam_out, double *__restrict__ w_out)
+{
+    __shared__ double T[10 * LVBA_CF];
+    __shared__ int lvoff[LVBA_CV + 1];
+    const int tid = threadIdx.x;
+    const int ch = blockIdx.x;
+    const int64_t v0 = d.chunk_v0[ch], v1 = d.chunk_v0[ch + 1];
+    const int64_t f0 = d.voff[v0];
+    const int nf = (int)(d.voff[v1] - f0), nv = (int)(v1 - v0);
+    double lam = 0.0;
+    bool have = false;
+    if (nf > LVBA_CF) { // one voxel with more observers than lanes (uniform branch)
+        double S[10];
+        merge_big_voxel(d, poses, f0, nf, T, S);
+        if (tid == 0) { lam = voxel_lambda_min(S); have = true; }
+    } else {
+        if (tid <= nv) lvoff[tid] = (int)(d.voff[v0 + tid] - f0);
+        if (tid < nf) {
+            const int64_t f = f0 + tid;
+            double c[10], x[12], t[10];
+#pragma unroll
+            for (int e = 0; e < 10; ++e) c[e] = d.clu[(int64_t)e * d.F + f];
+            const double2 *xp = reinterpret_cast<const double2 *>(poses + 12 * (int64_t)d.pidx[f]);
+#pragma unroll
+            for (int e = 0; e < 6; ++e) {
+                const double2 v2 = xp[e];
+                x[2 * e] = v2.x; x[2 * e + 1] = v2.y;
+            }
+            transform_cluster(c, x, x + 9, t);
+#pragma unroll
+            for (int e = 0; e < 10; ++e) T[e * LVBA_CF + tid] = t[e];
+        }
+        __syncthreads();
+        if (tid < nv) {
+            double S[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+            for (int f = lvoff[tid]; f < lvoff[tid + 1]; ++f) {
+#pragma unroll
+                for (int e = 0; e < 10; ++e) S[e] += T[e * LVBA_CF + f];
+            }
+            lam = voxel_lambda_min(S);
+            have = true;
+        }
+    }
+    if (have) {
+        double w;
+        (void)voxel_loss(d, lam, w); // (TRIVIAL: w = 1)
+        const int64_t v = v0 + tid, o = order ? order[v] : v;
+        if (lam_out) lam_out[o] = lam;
+        if (w_out) w_out[o] = w;
+    }
 }
 
 // Deterministic final sum of per-chunk partials (single workgroup); out[0] = sum.
@@ -168,6 +240,9 @@ __global__ __launch_bounds__(1024) void reduce_chunks_kernel(const double *__res
 // ------------------------------------------------------------------------------------------------
 // full evaluation, pass 1 (voxel-major): cost + per-voxel records.  Same loads as balm_cost_kernel.
 // ------------------------------------------------------------------------------------------------
+// ROBUST: the chunk cost is the sum of rho(lambda_min), and slot 13 of a voxel's record carries w = rho'(lambda_min) to the factor pass
+// (inside the seven 16-byte loads it makes of the record anyway).
+template <bool ROBUST>
 __global__ __launch_bounds__(LVBA_CF, 6) void balm_voxel_kernel(BalmDev d, const double *__restrict__ poses,
                                                             double *__restrict__ chunk_cost)
 {
@@ -184,8 +259,10 @@ __global__ __launch_bounds__(LVBA_CF, 6) void balm_voxel_kernel(BalmDev d, const
         merge_big_voxel(d, poses, f0, nf, T, S);
         if (tid == 0) {
             VoxRec vr;
-            chunk_cost[ch] = voxel_finish(S, vr);
+            double lam = voxel_finish(S, vr);
             double *o = d.vrec + 16 * v0;
+            if constexpr (ROBUST) { double w; lam = voxel_loss(d, lam, w); o[13] = w; }
+            chunk_cost[ch] = lam;
             o[0] = vr.NN;
             for (int e = 0; e < 3; ++e) {
                 o[1 + e] = vr.vb[e];
@@ -214,7 +291,7 @@ __global__ __launch_bounds__(LVBA_CF, 6) void balm_voxel_kernel(BalmDev d, const
         for (int e = 0; e < 10; ++e) T[e * LVBA_CF + tid] = t[e];
     }
     __syncthreads();
-    double lam0 = 0.0;
+    double lam0 = 0.0, wv0 = 0.0;
     VoxRec vr;
     const int vt = (tid + 256 - 64 * (ch & 3)) & 255; // as in balm_cost_kernel (same voxel -> lane map: the same cost, bit for bit)
     if (vt < nv) {
@@ -224,6 +301,7 @@ __global__ __launch_bounds__(LVBA_CF, 6) void balm_voxel_kernel(BalmDev d, const
             for (int e = 0; e < 10; ++e) S[e] += T[e * LVBA_CF + f];
         }
         lam0 = voxel_finish(S, vr);
+        if constexpr (ROBUST) lam0 = voxel_loss(d, lam0, wv0);
     }
     // the records leave through LDS (T is dead once every lane has its sums): lane-per-record stores would put 8 bytes into
     // each of up to 128 cache lines per instruction; staged, the chunk's records go out as contiguous 2-KB stores
@@ -238,7 +316,8 @@ __global__ __launch_bounds__(LVBA_CF, 6) void balm_voxel_kernel(BalmDev d, const
             o[7 + e] = vr.s1[e];
             o[10 + e] = vr.s2[e];
         }
-        o[13] = o[14] = o[15] = 0.0;
+        o[13] = wv0; // (0 without a loss: not read)
+        o[14] = o[15] = 0.0;
     }
     __syncthreads();
     {
@@ -257,7 +336,10 @@ __global__ __launch_bounds__(LVBA_CF, 6) void balm_voxel_kernel(BalmDev d, const
 // Y32 (LVBA_Y32=1, an experiment of round 4): the Y records are stored as fp32, 20 floats = 80 bytes per factor (18 used) instead
 // of 144 -- half of the write traffic here and of the pair pass's gathers; the diagonal blocks and the gradient are formed from
 // the fp64 values in registers either way, the off-diagonal blocks then carry ~1e-7 relative rounding (fp64 accumulation).
-template <bool Y32>
+// ROBUST (lvba_balm_set_loss): the voxel's weight w = rho'(lambda_min) rides in slot 13 of its record; Y_i <- sqrt(w) Y_i, so that the
+// pair pass forms w Y_I Y_J^T from unchanged records, D <- w D, g_i <- w g_i.  The rank-1 term rho'' g_v g_v^T is left out (<= 0 for
+// every kind: the kept matrix majorises the true Hessian; it would need a fourth column in every Y record).
+template <bool Y32, bool ROBUST>
 __global__ __launch_bounds__(256) void balm_factor_kernel(BalmDev d, const double *__restrict__ poses)
 {
     __shared__ double red[4 * 27];
@@ -300,10 +382,20 @@ __global__ __launch_bounds__(256) void balm_factor_kernel(BalmDev d, const doubl
             }
             double D[21], gi[6];
             factor_derivs(c, x, x + 9, vr, Y, D, gi);
+            if constexpr (ROBUST) {
+                const double w = vp[13], sw = sqrt(w);
 #pragma unroll
-            for (int e = 0; e < 21; ++e) acc[e] += D[e];
+                for (int e = 0; e < 18; ++e) Y[e] *= sw;
 #pragma unroll
-            for (int e = 0; e < 6; ++e) acc[21 + e] += gi[e];
+                for (int e = 0; e < 21; ++e) acc[e] += w * D[e];
+#pragma unroll
+                for (int e = 0; e < 6; ++e) acc[21 + e] += w * gi[e];
+            } else {
+#pragma unroll
+                for (int e = 0; e < 21; ++e) acc[e] += D[e];
+#pragma unroll
+                for (int e = 0; e < 6; ++e) acc[21 + e] += gi[e];
+            }
         }
         // Y records leave through LDS: a lane-per-record store puts 16 bytes into each of 72 cache lines per instruction
         // (stride 144 B); transposed, the wavefront's 64 records go out as 9 contiguous 1-KB stores -- NON-TEMPORAL ones: 1.44 GB
@@ -863,12 +955,19 @@ __global__ void export_poses_kernel(const double *__restrict__ in, const int *__
 // with_records: the voxel pass of the full evaluation instead of the cost-only kernel -- the same per-chunk cost sums, plus the
 // voxel records at `poses`.  The LM loop costs its trial point like that: if the step is accepted, the next evaluation is AT that
 // point and starts from the records already there (launch_eval, skip_voxel_pass) instead of reading every cluster again.
+// (a handle with a loss -- d.loss_kind != 0 -- gets the ROBUST instantiations, every other handle the plain ones)
+static void launch_voxel_pass(const BalmDev &d, const double *poses, double *chunk_cost, hipStream_t s)
+{
+    if (d.loss_kind) hipLaunchKernelGGL(balm_voxel_kernel<true>, dim3((unsigned)d.n_chunks), dim3(LVBA_CF), 0, s, d, poses, chunk_cost);
+    else hipLaunchKernelGGL(balm_voxel_kernel<false>, dim3((unsigned)d.n_chunks), dim3(LVBA_CF), 0, s, d, poses, chunk_cost);
+}
+
 void launch_cost(const BalmDev &d, const double *poses, double *chunk_cost, double *out, hipStream_t s,
                  hipEvent_t k0, hipEvent_t k1, bool with_records)
 {
     if (k0) hipEventRecord(k0, s);
-    if (with_records) hipLaunchKernelGGL(balm_voxel_kernel, dim3((unsigned)d.n_chunks), dim3(LVBA_CF), 0, s, d, poses, chunk_cost);
-    else hipLaunchKernelGGL(balm_cost_kernel, dim3((unsigned)d.n_chunks), dim3(LVBA_CF), 0, s, d, poses, chunk_cost);
+    if (with_records) launch_voxel_pass(d, poses, chunk_cost, s);
+    else launch_cost_chunks(d, poses, chunk_cost, s);
     if (k1) hipEventRecord(k1, s);
     hipLaunchKernelGGL(reduce_chunks_kernel, dim3(1), dim3(1024), 0, s, chunk_cost, d.n_chunks, out);
 }
@@ -895,9 +994,15 @@ void launch_eval(const BalmDev &d, const PairDev &pd, const double *poses, doubl
 {
     if (zero_first) hipMemsetAsync(Hblk, 0, (size_t)hblk_doubles * sizeof(double), s);
     if (k0) hipEventRecord(k0, s);
-    if (!skip_voxel_pass) hipLaunchKernelGGL(balm_voxel_kernel, dim3((unsigned)d.n_chunks), dim3(LVBA_CF), 0, s, d, poses, chunk_cost);
-    if (pd.col_form == 2) hipLaunchKernelGGL(balm_factor_kernel<true>, dim3((unsigned)(d.n_poses * d.S)), dim3(256), 0, s, d, poses);
-    else hipLaunchKernelGGL(balm_factor_kernel<false>, dim3((unsigned)(d.n_poses * d.S)), dim3(256), 0, s, d, poses);
+    if (!skip_voxel_pass) launch_voxel_pass(d, poses, chunk_cost, s);
+    const dim3 fgrid((unsigned)(d.n_poses * d.S));
+    if (d.loss_kind) {
+        if (pd.col_form == 2) hipLaunchKernelGGL((balm_factor_kernel<true, true>), fgrid, dim3(256), 0, s, d, poses);
+        else hipLaunchKernelGGL((balm_factor_kernel<false, true>), fgrid, dim3(256), 0, s, d, poses);
+    } else {
+        if (pd.col_form == 2) hipLaunchKernelGGL((balm_factor_kernel<true, false>), fgrid, dim3(256), 0, s, d, poses);
+        else hipLaunchKernelGGL((balm_factor_kernel<false, false>), fgrid, dim3(256), 0, s, d, poses);
+    }
     hipLaunchKernelGGL(balm_diag_reduce_kernel, dim3((unsigned)((32 * (int64_t)d.n_poses + 255) / 256)), dim3(256), 0, s, d, Hblk, g);
     launch_pairs(pd, Hblk, s);
     if (k1) hipEventRecord(k1, s);
@@ -968,7 +1073,13 @@ void launch_reduce_chunks_groups(const double *chunk_cost, const int64_t *gco, i
 
 void launch_cost_chunks(const BalmDev &d, const double *poses, double *chunk_cost, hipStream_t s)
 {
-    hipLaunchKernelGGL(balm_cost_kernel, dim3((unsigned)d.n_chunks), dim3(LVBA_CF), 0, s, d, poses, chunk_cost);
+    if (d.loss_kind) hipLaunchKernelGGL(balm_cost_kernel<true>, dim3((unsigned)d.n_chunks), dim3(LVBA_CF), 0, s, d, poses, chunk_cost);
+    else hipLaunchKernelGGL(balm_cost_kernel<false>, dim3((unsigned)d.n_chunks), dim3(LVBA_CF), 0, s, d, poses, chunk_cost);
+}
+
+void launch_voxel_residuals(const BalmDev &d, const double *poses, const int64_t *order, double *lam, double *w, hipStream_t s)
+{
+    hipLaunchKernelGGL(balm_voxel_resid_kernel, dim3((unsigned)d.n_chunks), dim3(LVBA_CF), 0, s, d, poses, order, lam, w);
 }
 
 void launch_predicted_decrease_groups(const double *Hblk, int band_blocks, const double *g, const double *dx, const double *u,

@@ -31,6 +31,10 @@ struct lvba_balm_s {
     lvba::hvec<int32_t> h_pidx;
     bool finalized = false;
     bool voxels_sorted = false; // the voxels were re-laid in the order of the first pose that sees them (balm_create_impl)
+    int64_t *d_vox_order = nullptr; // then: voxel v of the handle's layout is voxel d_vox_order[v] of the caller's (lvba_balm_voxel_residuals)
+    // robust loss on the voxel costs (lvba_balm_set_loss); TRIVIAL: none, the plain kernels run
+    lvba_loss loss{LVBA_LOSS_TRIVIAL, 0, 0.0};
+    bool loss_check = true;             // a sharded handle checks on its next collective call that every rank set the same loss
     // device data (voxel-major)
     int64_t *d_voff = nullptr, *d_chunk_v0 = nullptr;
     int32_t *d_pidx = nullptr;
@@ -83,6 +87,7 @@ struct lvba_balm_s {
         d.voff = d_voff; d.pidx = d_pidx; d.clu = d_clu; d.chunk_v0 = d_chunk_v0;
         d.S = bs.S; d.csc_off = bs.d_csc_off; d.clu_csc = d_clu_csc; d.vox_of_pos = bs.d_group_of_pos; d.vrec = d_vrec;
         d.Y = bs.d_Y; d.part = d_part;
+        d.loss_kind = loss.kind; d.loss_scale = loss.scale;
         return d;
     }
 };
@@ -187,10 +192,12 @@ static int32_t balm_create_impl(int32_t n_poses, int64_t n_voxels, const int64_t
     // voxel records the factor pass gathers and above all the windows of the pair lists draw on a compact slice of memory then.
     // The reference hands its voxels over in the iteration order of an unordered_map (src/lvba_system.cpp:254-262 -> tras_opt),
     // i.e. in no order at all: at C3 that costs 17 % of the evaluation (2.71 vs 2.32 ms, tools/gpu_shuffled.sh).  So a large
-    // problem whose voxels jump about is re-laid internally, voxels sorted (stably) by the first pose that sees them.  Nothing
-    // the caller gets back is indexed by voxel; sums over voxels change in the last bits only.
+    // problem whose voxels jump about is re-laid internally, voxels sorted (stably) by the first pose that sees them.  The
+    // one output indexed by voxel, lvba_balm_voxel_residuals, goes back through the permutation kept for it (d_vox_order); sums
+    // over voxels change in the last bits only.
     lvba::hvec<int64_t> voff_s;
     lvba::hvec<int32_t> pidx_s, fmap;
+    lvba::hvec<int64_t> vox_order; // [new] = old, kept for the per-voxel outputs (lvba_balm_voxel_residuals)
     {
         const bool sort_voxels = want_key && jump / (double)(n_voxels - 1) > std::max(64.0, 0.125 * n_poses);
         if (sort_voxels) { // stable counting sort by the first pose
@@ -214,6 +221,7 @@ static int32_t balm_create_impl(int32_t n_poses, int64_t n_voxels, const int64_t
             }
             voxel_off = voff_s.data();
             pose_idx = pidx_s.data();
+            vox_order.swap(order);
         }
     }
     const int64_t base2 = voxel_off[0]; // 0 after a re-layout
@@ -253,6 +261,10 @@ static int32_t balm_create_impl(int32_t n_poses, int64_t n_voxels, const int64_t
     CTRY(bs_dmalloc(bs, &h->d_chunk_cost, h->n_chunks));
     CHIP(lvba::copy_h2d(h->d_voff, h->h_voff.data(), (size_t)(n_voxels + 1) * sizeof(int64_t)));
     CHIP(lvba::copy_h2d(h->d_chunk_v0, chunk_v0.data(), (size_t)(h->n_chunks + 1) * sizeof(int64_t)));
+    if (!vox_order.empty()) {
+        CTRY(bs_dmalloc(bs, &h->d_vox_order, n_voxels));
+        CHIP(lvba::copy_h2d(h->d_vox_order, vox_order.data(), (size_t)n_voxels * sizeof(int64_t)));
+    }
     { // AoS [F][10] -> SoA [10][F] on the device (a host array is staged in a temporary device buffer), through the factor map of
       // a re-layout
         const double *src = d_clusters; // like the host array: indexed relative to voxel_off[0]
@@ -291,7 +303,7 @@ extern "C" int32_t lvba_balm_destroy(lvba_balm_t h)
     if (h->bs.stream) hipStreamSynchronize(h->bs.stream);
     void *ptrs[] = {h->d_voff, h->d_chunk_v0, h->d_pidx, h->d_clu, h->d_chunk_cost, h->d_clu_csc, h->d_vrec, h->d_part,
                     h->d_pose_in, h->d_pose_cur, h->d_pose_trial, h->d_out, h->d_scal2, h->d_q1part, h->d_grp_of_pose, h->d_gpo, h->d_gaccept, h->d_gco,
-                    h->d_gscal};
+                    h->d_gscal, h->d_vox_order};
     for (void *p : ptrs)
         if (p) lvba::DevicePool::get().free(p);
     for (void *p : h->prior_mem)
@@ -321,6 +333,7 @@ extern "C" int32_t lvba_balm_configure(lvba_balm_t h, int32_t ordering, double b
 }
 
 static int32_t prior_sync(lvba_balm_s *h);
+static int32_t loss_sync(lvba_balm_s *h);
 static int32_t bind_priors(lvba_balm_s *h);
 
 static int32_t finalize(lvba_balm_s *h)
@@ -551,6 +564,7 @@ extern "C" int32_t lvba_balm_cost(lvba_balm_t h, const double *poses, int32_t is
     if (!h || !poses || !cost) return fail(LVBA_ERR_ARG, "NULL argument");
     TRY(finalize(h));
     TRY(prior_sync(h));
+    TRY(loss_sync(h));
     HIPCHK(hipSetDevice(h->bs.device));
     TRY(upload_poses(h, poses, h->d_pose_trial));
     h->lin_at_cur = false; // the chunk costs are overwritten
@@ -568,6 +582,7 @@ extern "C" int32_t lvba_balm_eval(lvba_balm_t h, const double *poses, double *H,
     if (!h || !poses) return fail(LVBA_ERR_ARG, "NULL argument");
     TRY(finalize(h));
     TRY(prior_sync(h));
+    TRY(loss_sync(h));
     BlockSys &bs = h->bs;
     HIPCHK(hipSetDevice(bs.device));
     TRY(upload_poses(h, poses, h->d_pose_cur));
@@ -599,6 +614,7 @@ extern "C" int32_t lvba_balm_eval_blocks(lvba_balm_t h, const double *poses, int
     if (capacity > 0 && (!bi || !bj || !blocks)) return fail(LVBA_ERR_ARG, "NULL block arrays");
     TRY(finalize(h));
     TRY(prior_sync(h));
+    TRY(loss_sync(h));
     BlockSys &bs = h->bs;
     HIPCHK(hipSetDevice(bs.device));
     // The block set is STRUCTURAL (the pair lists' destinations + the diagonal; the union pattern in a multi-rank job): it is
@@ -696,6 +712,7 @@ extern "C" int32_t lvba_balm_covariance(lvba_balm_t h, const double *poses, cons
     if (bs.nd.active) return fail(LVBA_ERR_UNSUPPORTED, "lvba_balm_covariance: dissected handles (nd_kind != 0) are not supported");
     if (bs.d_bcr || !bs.d_A || !bs.d_work) return fail(LVBA_ERR_UNSUPPORTED, "lvba_balm_covariance: no LDL^T store on this handle");
     TRY(prior_sync(h));
+    TRY(loss_sync(h));
     HIPCHK(hipSetDevice(bs.device));
     const bool timing = timing_on("cov", true);
     hipEvent_t tev[5] = {};
@@ -787,6 +804,7 @@ extern "C" int32_t lvba_balm_lm_begin(lvba_balm_t h, const double *poses, const 
     if (!h || !poses) return fail(LVBA_ERR_ARG, "NULL argument");
     TRY(finalize(h));
     TRY(prior_sync(h));
+    TRY(loss_sync(h));
     HIPCHK(hipSetDevice(h->bs.device));
     if (opts) h->lm_opts = *opts; else lvba_balm_default_opts(&h->lm_opts);
     if (h->lm_opts.max_iter < 0) return fail(LVBA_ERR_ARG, "max_iter < 0");
@@ -1320,6 +1338,75 @@ extern "C" int32_t lvba_balm_prior_residuals(lvba_balm_t h, const double *poses,
     HIPCHK(hipMemcpyAsync(&c, de + 6 * n, sizeof(double), hipMemcpyDeviceToHost, bs.stream));
     HIPCHK(hipStreamSynchronize(bs.stream));
     if (cost) *cost = c;
+    return LVBA_OK;
+}
+
+// ------------------------------------------------------------------------------------------ robust loss
+// C(x) = sum_v rho(lambda_min(v)) + priors; g = sum_v rho' g_v, H = sum_v rho' H_v (the rho'' g_v g_v^T term is left out, see
+// include/lvba_hip.h).  The loss lives on the handle and reaches the kernels through BalmDev (dev()): the voxel pass turns lambda_min
+// into rho and leaves rho' in the voxel record, the factor pass scales with it; nothing else in the LM loop knows about it.
+namespace lvba {
+int32_t loss_validate(const lvba_loss *loss, const char *what)
+{
+    if (!loss || loss->kind == LVBA_LOSS_TRIVIAL) return LVBA_OK;
+    if (loss->kind < LVBA_LOSS_TRIVIAL || loss->kind > LVBA_LOSS_TUKEY) return fail(LVBA_ERR_ARG, "%s: unknown loss kind %d", what, loss->kind);
+    if (!isfinite(loss->scale) || !(loss->scale > 0.0)) return fail(LVBA_ERR_ARG, "%s: the loss scale must be finite and > 0", what);
+    return LVBA_OK;
+}
+} // namespace lvba
+
+extern "C" int32_t lvba_balm_set_loss(lvba_balm_t h, const lvba_loss *loss)
+{
+    if (!h) return fail(LVBA_ERR_ARG, "handle is NULL");
+    TRY(lvba::loss_validate(loss, "lvba_balm_set_loss"));
+    if (h->lm_active) return fail(LVBA_ERR_STATE, "set_loss between lvba_balm_lm_begin and lvba_balm_lm_end");
+    if (!loss || loss->kind == LVBA_LOSS_TRIVIAL) h->loss = lvba_loss{LVBA_LOSS_TRIVIAL, 0, 0.0};
+    else h->loss = lvba_loss{loss->kind, 0, loss->scale};
+    h->loss_check = true;
+    h->have_eval = false; // H, g and the voxel records belong to the old cost
+    h->lin_at_cur = false;
+    return LVBA_OK;
+}
+
+// Sharded handles: like prior_sync, one MAX all-reduce of (kind, scale bits, -kind, -scale bits)
+static int32_t loss_sync(lvba_balm_s *h)
+{
+    if (!h->loss_check) return LVBA_OK;
+    BlockSys &bs = h->bs;
+    if (!bs.distributed()) { h->loss_check = false; return LVBA_OK; }
+    int64_t bits = 0;
+    memcpy(&bits, &h->loss.scale, sizeof bits); // (a valid scale is >= 0: the sign bit is clear)
+    const int64_t k = h->loss.kind;
+    int64_t buf[4] = {k, bits, -k, -bits};
+    HIPCHK(hipSetDevice(bs.device));
+    DevBuf d(bs.stream);
+    HIPCHK(d.alloc(sizeof buf));
+    HIPCHK(hipMemcpyAsync(d.as<int64_t>(), buf, sizeof buf, hipMemcpyHostToDevice, bs.stream));
+    TRY(bs_comm_allreduce(bs, d.as<int64_t>(), 4, ncclInt64, ncclMax));
+    HIPCHK(hipMemcpyAsync(buf, d.as<int64_t>(), sizeof buf, hipMemcpyDeviceToHost, bs.stream));
+    HIPCHK(hipStreamSynchronize(bs.stream));
+    if (buf[0] != -buf[2] || buf[1] != -buf[3]) return fail(LVBA_ERR_ARG, "the ranks of this job set different losses (lvba_balm_set_loss)");
+    h->loss_check = false;
+    return LVBA_OK;
+}
+
+extern "C" int32_t lvba_balm_voxel_residuals(lvba_balm_t h, const double *poses, double *lambda_min, double *weight)
+{
+    if (!h || !poses) return fail(LVBA_ERR_ARG, "NULL argument");
+    TRY(finalize(h));
+    BlockSys &bs = h->bs;
+    HIPCHK(hipSetDevice(bs.device));
+    if (!lambda_min && !weight) return LVBA_OK;
+    TRY(upload_poses(h, poses, h->d_pose_trial));
+    const int64_t V = h->V;
+    DevBuf d(bs.stream);
+    HIPCHK(d.alloc((size_t)((lambda_min ? V : 0) + (weight ? V : 0)) * sizeof(double)));
+    double *dl = d.as<double>(), *dw = dl + (lambda_min ? V : 0);
+    launch_voxel_residuals(h->dev(), h->d_pose_trial, h->d_vox_order, lambda_min ? dl : nullptr, weight ? dw : nullptr, bs.stream);
+    HIPCHK(hipGetLastError());
+    if (lambda_min) HIPCHK(hipMemcpyAsync(lambda_min, dl, (size_t)V * sizeof(double), hipMemcpyDeviceToHost, bs.stream));
+    if (weight) HIPCHK(hipMemcpyAsync(weight, dw, (size_t)V * sizeof(double), hipMemcpyDeviceToHost, bs.stream));
+    HIPCHK(hipStreamSynchronize(bs.stream));
     return LVBA_OK;
 }
 

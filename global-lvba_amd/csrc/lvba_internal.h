@@ -27,9 +27,12 @@ struct BalmDev {
     const int64_t *csc_off;    // [N+1] factor positions of each pose (solver order), sorted by voxel
     const double *clu_csc;     // [10][F] cluster statistics in pose-major order
     const int32_t *vox_of_pos; // [F] voxel of the factor at each pose-major position
-    double *vrec;              // [V][16] per-voxel records (13 used; 128-byte stride)
+    double *vrec;              // [V][16] per-voxel records (128-byte stride): 13 used, and under a loss slot 13 = the weight rho'
     double *Y;                 // [F][18] per-factor Y_i, pose-major positions
     double *part;              // [N*S][32] per-workgroup partial sums of (D[21], g[6])
+    // robust loss on the voxel costs (lvba_balm_set_loss, visual_loss.h); loss_kind = 0: none, the plain kernels run
+    int32_t loss_kind;
+    double loss_scale;
 };
 
 // Per-block contributor lists of the atomic-free assembly of  -sum Y_I Y_J^T  (shared by both stages).
@@ -192,6 +195,8 @@ void launch_aos_to_soa(const double *aos, const int32_t *fmap, int64_t F, double
 // grouped refinement (lvba_balm_refine_groups)
 void launch_reduce_chunks_groups(const double *chunk_cost, const int64_t *gco, int n_groups, double *out, hipStream_t s);
 void launch_cost_chunks(const BalmDev &d, const double *poses, double *chunk_cost, hipStream_t s);
+// lvba_balm_voxel_residuals: lambda_min / rho'(lambda_min) per voxel; order (may be NULL): handle voxel -> caller voxel; lam, w may be NULL
+void launch_voxel_residuals(const BalmDev &d, const double *poses, const int64_t *order, double *lam, double *w, hipStream_t s);
 void launch_predicted_decrease_groups(const double *Hblk, int band_blocks, const double *g, const double *dx, const double *u,
                                       const int32_t *gpo, int n_groups, double *out, hipStream_t s);
 void launch_select_poses(double *cur, const double *trial, const int32_t *accept, const int32_t *grp_of_pose, int n_poses, hipStream_t s);

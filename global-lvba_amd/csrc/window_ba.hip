@@ -146,8 +146,9 @@ inline void mat3T_mul(const double *A, const double *B, double *C) // A^T * B
 // damping_iter on the problem of a voxel map, which it consumes (:264, :386): poses x refined in place; the LM status, the
 // iterations, the first and last cost of the trace, and the time of the problem's set-up
 struct Refined { int32_t status = 0, n_iter = 0; double cost_first = 0.0, cost_last = 0.0, setup_ms = 0.0; };
+// loss: the robust loss of the problem's voxel costs (lvba_balm_set_loss), NULL: none
 int32_t refine_map(lvba_voxmap_t map, double *x, const lvba_balm_opts &lm, Refined &r, int32_t n_priors = 0,
-                   const lvba_prior *priors = nullptr)
+                   const lvba_prior *priors = nullptr, const lvba_loss *loss = nullptr)
 {
     const double t0 = now_ms();
     lvba_balm_t b = nullptr;
@@ -155,6 +156,10 @@ int32_t refine_map(lvba_voxmap_t map, double *x, const lvba_balm_opts &lm, Refin
     lvba_voxmap_destroy(map);
     if (rc != LVBA_OK) return rc;
     if (n_priors > 0 && (rc = lvba_balm_set_priors(b, n_priors, priors)) != LVBA_OK) {
+        lvba_balm_destroy(b);
+        return rc;
+    }
+    if (loss && (rc = lvba_balm_set_loss(b, loss)) != LVBA_OK) {
         lvba_balm_destroy(b);
         return rc;
     }
@@ -198,6 +203,7 @@ struct WindowCall {
     lvba_scans_s *sc = nullptr;
     const double *poses = nullptr;
     lvba_window_opts o{};
+    const lvba_loss *loss = nullptr;  // robust loss of every window problem (lvba_lidar_ba_robust), NULL: none
     int n = 0, w = 1, n_win = 0, n_thr = 1;
     hipStream_t s = nullptr;          // the calling thread's
     lvba::hvec<hipStream_t> wstreams; // the worker threads' (n_thr > 1); they live until the call returns: the maps work on them
@@ -303,7 +309,7 @@ int32_t stage_lm_single(WindowCall &c, int wi, hipStream_t)
     lvba_voxmap_t map = R.map;
     R.map = nullptr;
     Refined r;
-    TRY(refine_map(map, R.x.data(), c.o.lm, r));
+    TRY(refine_map(map, R.x.data(), c.o.lm, r, 0, nullptr, c.loss));
     R.info.lm_status = r.status; R.info.n_iter = r.n_iter;
     R.info.cost_first = r.cost_first; R.info.cost_last = r.cost_last;
     R.info.setup_ms = r.setup_ms;
@@ -370,6 +376,7 @@ int32_t stage_lm_batched(WindowCall &c, bool &done)
     struct Guard { lvba_balm_t b; ~Guard() { if (b) lvba_balm_destroy(b); } } guard{b};
     mk("create");
     TRY(lvba_balm_set_groups(b, G, pose_off.data(), vox_off.data()));
+    if (c.loss) TRY(lvba_balm_set_loss(b, c.loss));
     mk("set_groups");
     lvba_balm_info_t bi;
     TRY(lvba_balm_info(b, &bi)); // the one-off set-up, timed apart
@@ -687,9 +694,10 @@ extern "C" int32_t lvba_scans_download(lvba_scans_t sc, int32_t frame, float *xy
     return LVBA_OK;
 }
 
-extern "C" int32_t lvba_window_ba(lvba_scans_t sc, const double *poses, const lvba_window_opts *opts, double *window_poses,
-                                  double *rel_poses, int32_t *anchor_index, double *anchor_poses, int32_t *n_anchors,
-                                  lvba_scans_t *anchor_scans, lvba_window_info *win_info)
+// loss: the robust loss of every window problem (lvba_lidar_ba_robust), NULL: none
+static int32_t window_ba_impl(lvba_scans_t sc, const double *poses, const lvba_window_opts *opts, double *window_poses,
+                              double *rel_poses, int32_t *anchor_index, double *anchor_poses, int32_t *n_anchors,
+                              lvba_scans_t *anchor_scans, lvba_window_info *win_info, const lvba_loss *loss)
 {
     if (anchor_scans) *anchor_scans = nullptr;
     if (!sc || !poses || !rel_poses || !anchor_index || !anchor_poses || !n_anchors || !anchor_scans)
@@ -699,7 +707,7 @@ extern "C" int32_t lvba_window_ba(lvba_scans_t sc, const double *poses, const lv
     if (opts) c.o = *opts;
     if (c.o.window_size < 1) return lvba_fail(LVBA_ERR_ARG, "window_size must be >= 1");
     HIPCHK(hipSetDevice(sc->device));
-    c.sc = sc; c.poses = poses;
+    c.sc = sc; c.poses = poses; c.loss = loss;
     c.n = sc->n_frames; c.w = c.o.window_size; c.n_win = (c.n + c.w - 1) / c.w;
     hipStream_t s = nullptr;
     HIPCHK(lvba::StreamCache::get().acquire(&s));
@@ -776,6 +784,13 @@ extern "C" int32_t lvba_window_ba(lvba_scans_t sc, const double *poses, const lv
     return LVBA_OK;
 }
 
+extern "C" int32_t lvba_window_ba(lvba_scans_t sc, const double *poses, const lvba_window_opts *opts, double *window_poses,
+                                  double *rel_poses, int32_t *anchor_index, double *anchor_poses, int32_t *n_anchors,
+                                  lvba_scans_t *anchor_scans, lvba_window_info *win_info)
+{
+    return window_ba_impl(sc, poses, opts, window_poses, rel_poses, anchor_index, anchor_poses, n_anchors, anchor_scans, win_info, nullptr);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // The window stage over SEVERAL GPUs of one node.  The windows are independent problems (the reference solves them one after
 // the other, src/lvba_system.cpp:232-302), so this is where the GPUs of a node all have work: device k takes a contiguous run
@@ -793,9 +808,9 @@ extern "C" int32_t lvba_window_split(int32_t n_frames, int32_t window_size, int3
     return LVBA_OK;
 }
 
-extern "C" int32_t lvba_window_ba_multi(int32_t n_shares, const lvba_scans_t *scans, const double *poses, const lvba_window_opts *opts,
-                                        double *window_poses, double *rel_poses, int32_t *anchor_index, double *anchor_poses,
-                                        int32_t *n_anchors, lvba_scans_t *anchor_scans, lvba_window_info *win_info)
+static int32_t window_ba_multi_impl(int32_t n_shares, const lvba_scans_t *scans, const double *poses, const lvba_window_opts *opts,
+                                    double *window_poses, double *rel_poses, int32_t *anchor_index, double *anchor_poses,
+                                    int32_t *n_anchors, lvba_scans_t *anchor_scans, lvba_window_info *win_info, const lvba_loss *loss)
 {
     if (anchor_scans) *anchor_scans = nullptr;
     if (n_shares < 1 || !scans || !poses || !rel_poses || !anchor_index || !anchor_poses || !n_anchors || !anchor_scans)
@@ -822,9 +837,9 @@ extern "C" int32_t lvba_window_ba_multi(int32_t n_shares, const lvba_scans_t *sc
         Share &S = sh[(size_t)k];
         const int64_t nw = wb[(size_t)k + 1] - wb[(size_t)k];
         S.ap.assign(12 * (size_t)std::max<int64_t>(nw, 1), 0.0);
-        S.rc = lvba_window_ba(scans[k], poses + 12 * fb[(size_t)k], &o, window_poses ? window_poses + 12 * fb[(size_t)k] : nullptr,
+        S.rc = window_ba_impl(scans[k], poses + 12 * fb[(size_t)k], &o, window_poses ? window_poses + 12 * fb[(size_t)k] : nullptr,
                               rel_poses + 12 * fb[(size_t)k], anchor_index + fb[(size_t)k], S.ap.data(), &S.na, &S.anchors,
-                              win_info ? win_info + wb[(size_t)k] : nullptr);
+                              win_info ? win_info + wb[(size_t)k] : nullptr, loss);
         if (S.rc < 0) S.err = lvba_last_error();
     };
     {
@@ -871,6 +886,14 @@ extern "C" int32_t lvba_window_ba_multi(int32_t n_shares, const lvba_scans_t *sc
     return LVBA_OK;
 }
 
+extern "C" int32_t lvba_window_ba_multi(int32_t n_shares, const lvba_scans_t *scans, const double *poses, const lvba_window_opts *opts,
+                                        double *window_poses, double *rel_poses, int32_t *anchor_index, double *anchor_poses,
+                                        int32_t *n_anchors, lvba_scans_t *anchor_scans, lvba_window_info *win_info)
+{
+    return window_ba_multi_impl(n_shares, scans, poses, opts, window_poses, rel_poses, anchor_index, anchor_poses, n_anchors, anchor_scans,
+                                win_info, nullptr);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // LvbaSystem::runLidarBA (src/lvba_system.cpp:312-410) without the ROS/visualisation calls: window BA -> anchors, then the
 // global stages (stage 1 optional, stage 2) each re-cutting the anchor clouds at the current anchor poses with that stage's
@@ -892,6 +915,7 @@ extern "C" void lvba_lidar_ba_default_opts(lvba_lidar_ba_opts *o)
 namespace lvba {
 int32_t prior_validate(int32_t n, const lvba_prior *priors, int32_t n_poses); // lvba_api.hip
 void prior_offset_or_identity(const double *o, double *out);
+int32_t loss_validate(const lvba_loss *loss, const char *what);
 }
 // frame priors -> priors on the anchors of the global stages: frame f = anchor a(f) o rel_f, so T_f O = T_a (rel_f o O) exactly.
 // Frames of skipped windows (anchor -1) and relative priors inside one anchor (constant at this stage) are dropped.
@@ -924,7 +948,8 @@ static void priors_to_anchors(int32_t n, const lvba_prior *fp, const int32_t *ai
 
 static int32_t lidar_ba_impl(int32_t n_shares, const lvba_scans_t *scs, const double *poses_in, const lvba_lidar_ba_opts *opts,
                              double *poses_out, lvba_lidar_ba_report *rep, int32_t n_priors = 0, const lvba_prior *priors = nullptr,
-                             lvba_prior *anchor_priors = nullptr, int32_t *n_used = nullptr, int32_t *n_dropped = nullptr)
+                             lvba_prior *anchor_priors = nullptr, int32_t *n_used = nullptr, int32_t *n_dropped = nullptr,
+                             const lvba_loss *window_loss = nullptr, const lvba_loss *stage_loss = nullptr)
 {
     if (n_shares < 1 || !scs || !scs[0] || !poses_in || !poses_out) return lvba_fail(LVBA_ERR_ARG, "null argument");
     lvba_lidar_ba_opts o;
@@ -939,6 +964,8 @@ static int32_t lidar_ba_impl(int32_t n_shares, const lvba_scans_t *scs, const do
     if (n_shares > 1 && !o.window_enable)
         return lvba_fail(LVBA_ERR_ARG, "several shares need the window stage (window_enable = 0 cuts the RAW scans in the global stages: one device)");
     TRY(lvba::prior_validate(n_priors, priors, n));
+    TRY(lvba::loss_validate(window_loss, "window_loss"));
+    TRY(lvba::loss_validate(stage_loss, "stage_loss"));
     lvba_lidar_ba_report r{};
     r.n_frames = n;
     lvba::hvec<double> rel(12 * (size_t)n), anchor_poses;
@@ -950,8 +977,8 @@ static int32_t lidar_ba_impl(int32_t n_shares, const lvba_scans_t *scs, const do
         const int nw = (n + o.window.window_size - 1) / std::max(1, o.window.window_size);
         anchor_poses.resize(12 * (size_t)std::max(nw, 1));
         lvba::hvec<lvba_window_info> wi((size_t)std::max(nw, 1));
-        if (n_shares == 1) TRY(lvba_window_ba(sc, poses_in, &o.window, nullptr, rel.data(), aidx.data(), anchor_poses.data(), &na, &anchors, wi.data()));
-        else TRY(lvba_window_ba_multi(n_shares, scs, poses_in, &o.window, nullptr, rel.data(), aidx.data(), anchor_poses.data(), &na, &anchors, wi.data()));
+        if (n_shares == 1) TRY(window_ba_impl(sc, poses_in, &o.window, nullptr, rel.data(), aidx.data(), anchor_poses.data(), &na, &anchors, wi.data(), window_loss));
+        else TRY(window_ba_multi_impl(n_shares, scs, poses_in, &o.window, nullptr, rel.data(), aidx.data(), anchor_poses.data(), &na, &anchors, wi.data(), window_loss));
         r.n_windows = nw;
         for (int k = 0; k < nw; ++k) r.n_windows_skipped += wi[k].skipped;
     } else { // :221-229: every frame is its own anchor
@@ -990,7 +1017,7 @@ static int32_t lidar_ba_impl(int32_t n_shares, const lvba_scans_t *scs, const do
                 continue;
             }
             Refined rr;
-            TRY(refine_map(map, anchor_poses.data(), o.lm, rr, (int32_t)ap.size(), ap.data()));
+            TRY(refine_map(map, anchor_poses.data(), o.lm, rr, (int32_t)ap.size(), ap.data(), stage_loss));
             r.stage_status[idx] = rr.status; r.stage_iters[idx] = rr.n_iter;
             r.stage_cost_first[idx] = rr.cost_first; r.stage_cost_last[idx] = rr.cost_last;
             r.stage_ms[idx] = now_ms() - t0;
@@ -1032,4 +1059,13 @@ extern "C" int32_t lvba_lidar_ba_multi_priors(int32_t n_shares, const lvba_scans
                                               lvba_lidar_ba_report *rep, lvba_prior *anchor_priors, int32_t *n_used, int32_t *n_dropped)
 {
     return lidar_ba_impl(n_shares, scans, poses_in, opts, poses_out, rep, n_priors, priors, anchor_priors, n_used, n_dropped);
+}
+
+extern "C" int32_t lvba_lidar_ba_robust(int32_t n_shares, const lvba_scans_t *scans, const double *poses_in, const lvba_lidar_ba_opts *opts,
+                                        const lvba_loss *window_loss, const lvba_loss *stage_loss, int32_t n_priors, const lvba_prior *priors,
+                                        double *poses_out, lvba_lidar_ba_report *rep, lvba_prior *anchor_priors, int32_t *n_used,
+                                        int32_t *n_dropped)
+{
+    return lidar_ba_impl(n_shares, scans, poses_in, opts, poses_out, rep, n_priors, priors, anchor_priors, n_used, n_dropped, window_loss,
+                         stage_loss);
 }

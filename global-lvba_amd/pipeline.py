@@ -275,15 +275,64 @@ def colorize_maps(scans, image_times, images, intr, width, height, after, before
             m.close()
 
 
+def _lidar_cfg(cfg):
+    c = dict(DEFAULTS); c.update(cfg)
+    return dict(window_enable=c["window_enable"], window_size=c["window_size"], anchor_leaf=c["anchor_leaf"], use_rel=c["use_rel"],
+                stage1_enable=c["stage1_enable"], stage_voxel_size=c["stage_voxel_size"], stage_eigen_ratio=c["stage_eigen_ratio"])
+
+
+def run_lidar_ba(scans, poses, priors=None, window_loss=None, stage_loss=None, host_driven=False, **cfg):
+    """LvbaSystem::runLidarBA (src/lvba_system.cpp:312-410) on resident scans: (poses [n,12], report dict).  cfg: the LiDAR keys of
+    DEFAULTS.  window_loss / stage_loss: robust losses (BalmProblem.set_loss arguments) of every window problem / of both global
+    stages; None: the plain sum of lambda_min.
+    host_driven=False: the library's whole-stage entry (Scans.lidar_ba -> lvba_lidar_ba / _priors / _robust).
+    host_driven=True: the same flow driven from here, stage by stage -- window BA, then per global stage a voxel map of the anchor
+    clouds at the current anchor poses, its problem (tras_opt), set_loss, refine -- and the composition anchor o rel.  It takes a
+    stage loss only (the window stage is one library call) and no priors."""
+    k = _lidar_cfg(cfg)
+    if not host_driven:
+        return scans.lidar_ba(poses, priors=priors, window_loss=window_loss, stage_loss=stage_loss, **k)
+    if priors or window_loss is not None or not k["window_enable"]:
+        raise ValueError("the host-driven flow takes a stage loss only, and needs the window stage")
+    x = np.asarray(poses, np.float64).reshape(-1, 12)
+    w = scans.window_ba(x, window_size=k["window_size"], voxel_size=k["stage_voxel_size"][0], anchor_leaf=k["anchor_leaf"],
+                        use_rel=k["use_rel"])
+    anchors, ax = w["anchor_scans"], w["anchor_poses"].copy()
+    report = dict(n_anchors=len(ax), stage_ran=[0, 0], stage_iters=[0, 0])
+    try:
+        for s in range(0 if k["stage1_enable"] else 1, 2):
+            if not len(ax):
+                break
+            with anchors.voxel_map(ax, k["stage_voxel_size"][s], k["stage_eigen_ratio"][s]) as m:
+                if m.info["n_voxels"] == 0:
+                    continue
+                with m.tras_opt() as prob:
+                    prob.set_loss(stage_loss)
+                    ax, trace, _ = prob.refine(ax)
+                    report["stage_ran"][s], report["stage_iters"][s] = 1, len(trace)
+    finally:
+        anchors.close()
+    out = x.copy()
+    for i, a in enumerate(w["anchor_index"]):
+        if a < 0:
+            continue
+        A, Lr = ax[a], w["rel_poses"][i]
+        R = A[:9].reshape(3, 3)
+        out[i, :9] = (R @ Lr[:9].reshape(3, 3)).reshape(9)
+        out[i, 9:] = R @ Lr[9:] + A[9:]
+    return out, report
+
+
 def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, tci, intr, width, height, keypoints, pairs,
-                      matches, enable_lidar_ba=True, enable_visual_ba=True, device=0, images=None, lidar_priors=None, **cfg):
+                      matches, enable_lidar_ba=True, enable_visual_ba=True, device=0, images=None, lidar_priors=None,
+                      window_loss=None, stage_loss=None, **cfg):
     """LvbaSystem::runFullPipeline (src/lvba_system.cpp:136-142) on in-memory data: clouds = body-frame [n_i, >=3] float32
     arrays, poses [n,12] = x_buf_ (T_world<-imu), image_poses [m,12] the image poses from the odometry.  cfg: DEFAULTS' keys
     (visual_loss, colorize_leaf among them).  images: None, or the images ([m,H,W,3] BGR uint8 or a callable k -> [H,W,3]):
     then the output also holds colored_after / colored_before = (xyz, rgb), the LiDAR map coloured from them
     (colorize_maps) with the refined poses and cameras and with the original ones; this needs the visual stage.
     lidar_priors: balm.Prior objects on frames (GNSS fixes, loop closures, ...) for the global stages of the LiDAR BA
-    (Scans.lidar_ba(priors=...))."""
+    (Scans.lidar_ba(priors=...)).  window_loss / stage_loss: robust losses of the LiDAR BA (run_lidar_ba)."""
     if images is not None and not enable_visual_ba:
         raise ValueError("colouring the map needs the cameras of the visual stage (enable_visual_ba=True)")
     c = dict(DEFAULTS); c.update(cfg)
@@ -292,10 +341,7 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
     with Scans(clouds, device=device) as scans:
         x_opt = x_orig
         if enable_lidar_ba:
-            x_opt, report = scans.lidar_ba(x_orig, window_enable=c["window_enable"], window_size=c["window_size"],
-                                           anchor_leaf=c["anchor_leaf"], use_rel=c["use_rel"], stage1_enable=c["stage1_enable"],
-                                           stage_voxel_size=c["stage_voxel_size"], stage_eigen_ratio=c["stage_eigen_ratio"],
-                                           priors=lidar_priors)
+            x_opt, report = run_lidar_ba(scans, x_orig, priors=lidar_priors, window_loss=window_loss, stage_loss=stage_loss, **c)
             out["lidar_report"] = report
         out["poses"] = np.asarray(x_opt).reshape(-1, 12)
         if enable_visual_ba:
@@ -351,7 +397,7 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
     the camera's is resized with Pillow's bilinear filter, which is not OpenCV's INTER_LINEAR bit for bit.  The output gains
     colored_after / colored_before, and out_dir gets colored_merged_after.pcd / colored_merged_before.pcd (binary PCD, PCL's
     XYZRGB layout) and a points3D.txt holding the coloured after-cloud, as the reference writes them.
-    cfg as for run_full_pipeline, e.g. visual_loss=REFERENCE_HUBER."""
+    cfg as for run_full_pipeline, e.g. visual_loss=REFERENCE_HUBER, window_loss=("cauchy", 0.1), stage_loss=("huber", 0.05)."""
     import os
     from . import dataset as D
     ds = D.load_dataset(data_path)

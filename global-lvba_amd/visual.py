@@ -121,15 +121,7 @@ class VisualProblem:
             L.TERMINATION.get(term.value, str(term.value)), rc
 
 
-def loss_struct(loss):
-    """None -> NULL (TRIVIAL); (kind, scale) -> a pointer to an lvba_loss."""
-    if loss is None:
-        return None
-    kind, scale = loss
-    k = L.LOSS_KINDS.get(str(kind).lower()) if isinstance(kind, str) else int(kind)
-    if k is None:
-        raise ValueError(f"unknown loss kind {kind!r}; one of {sorted(L.LOSS_KINDS)}")
-    return C.pointer(L.Loss(k, 0, float(scale)))
+loss_struct = L.loss_struct  # (kind, scale) / None -> lvba_loss pointer: shared with the LiDAR stage (_lib.py)
 
 
 def optimize_camera_poses(qs, ts, Xs, obs_off, obs_cam, obs_uv, plane_n, plane_d, intr, sigma_px=0.5, sigma_plane=0.01,

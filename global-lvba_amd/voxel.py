@@ -187,10 +187,12 @@ class Scans:
 
     def lidar_ba(self, poses, window_enable=True, window_size=10, anchor_leaf=0.1, use_rel=True, stage1_enable=True,
                  stage_voxel_size=(0.5, 0.5), stage_eigen_ratio=((0.3, 0.1, 0.06, 0.03), (0.08, 0.08, 0.08, 0.08)),
-                 window_eigen_ratio=None, priors=None):
+                 window_eigen_ratio=None, priors=None, window_loss=None, stage_loss=None):
         """LvbaSystem::runLidarBA (src/lvba_system.cpp:312-410): window BA, global stage 1 / stage 2, pose composition.
         Returns (poses [n,12], report dict).  priors: balm.Prior objects on FRAMES, applied to the anchors of both global stages
-        (lvba_lidar_ba_priors); the report then also holds priors_used, priors_dropped and anchor_priors (the applied priors)."""
+        (lvba_lidar_ba_priors); the report then also holds priors_used, priors_dropped and anchor_priors (the applied priors).
+        window_loss / stage_loss: BalmProblem.set_loss arguments for every window problem / both global stages
+        (lvba_lidar_ba_robust); None: no loss."""
         n = self.n_frames
         poses = np.ascontiguousarray(poses, np.float64).reshape(-1)
         if poses.size != 12 * n:
@@ -206,6 +208,15 @@ class Scans:
                 o.stage_eigen_ratio[i][k] = float(stage_eigen_ratio[i][k])
         out = np.zeros(12 * n)
         rep = L.LidarBaReport()
+        if window_loss is not None or stage_loss is not None:
+            with_priors = priors is not None
+            priors = list(priors or [])
+            pa, ap, used, dropped = _prior_arrays(priors)
+            hs = (C.c_void_p * 1)(self._h.value)
+            L.check(self.lib.lvba_lidar_ba_robust(1, hs, poses, C.byref(o), L.loss_struct(window_loss), L.loss_struct(stage_loss),
+                                                  len(priors), pa if priors else None, out, C.byref(rep), ap, C.byref(used),
+                                                  C.byref(dropped)))
+            return out.reshape(n, 12), (_prior_report(rep, ap, used, dropped) if with_priors else rep.as_dict())
         if priors is None:
             L.check(self.lib.lvba_lidar_ba(self._h, poses, C.byref(o), out, C.byref(rep)))
             return out.reshape(n, 12), rep.as_dict()
@@ -217,9 +228,9 @@ class Scans:
     @staticmethod
     def lidar_ba_multi(clouds, poses, devices, window_size=10, anchor_leaf=0.1, use_rel=True, stage1_enable=True,
                        stage_voxel_size=(0.5, 0.5), stage_eigen_ratio=((0.3, 0.1, 0.06, 0.03), (0.08, 0.08, 0.08, 0.08)),
-                       window_eigen_ratio=None, priors=None):
+                       window_eigen_ratio=None, priors=None, window_loss=None, stage_loss=None):
         """runLidarBA with the window stage over several GPUs (lvba_lidar_ba_multi): returns (poses [n,12], report dict).
-        priors: as in lidar_ba (lvba_lidar_ba_multi_priors)."""
+        priors: as in lidar_ba (lvba_lidar_ba_multi_priors); window_loss / stage_loss: as in lidar_ba (lvba_lidar_ba_robust)."""
         lib = L.load()
         n, D = len(clouds), len(devices)
         poses = np.ascontiguousarray(poses, np.float64).reshape(-1)
@@ -241,6 +252,14 @@ class Scans:
         rep = L.LidarBaReport()
         hs = (C.c_void_p * len(shares))(*[sc._h.value for sc in shares])
         try:
+            if window_loss is not None or stage_loss is not None:
+                with_priors = priors is not None
+                priors = list(priors or [])
+                pa, ap, used, dropped = _prior_arrays(priors)
+                L.check(lib.lvba_lidar_ba_robust(len(shares), hs, poses, C.byref(o), L.loss_struct(window_loss), L.loss_struct(stage_loss),
+                                                 len(priors), pa if priors else None, out, C.byref(rep), ap, C.byref(used),
+                                                 C.byref(dropped)))
+                return out.reshape(n, 12), (_prior_report(rep, ap, used, dropped) if with_priors else rep.as_dict())
             if priors is None:
                 L.check(lib.lvba_lidar_ba_multi(len(shares), hs, poses, C.byref(o), out, C.byref(rep)))
                 return out.reshape(n, 12), rep.as_dict()

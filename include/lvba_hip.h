@@ -261,6 +261,46 @@ int32_t lvba_balm_covariance(lvba_balm_t h, const double *poses, const lvba_cov_
                              double *diag, int64_t n_pairs, const int32_t *pi, const int32_t *pj,
                              double *blocks, uint8_t *avail);
 
+/* Robust loss on the voxel costs (opt-in; none by default).  With a loss rho of kind LVBA_LOSS_* and scale a in metres (the kinds and
+ * formulas of lvba_visual_set_loss below, b = a^2) and s_v = lambda_min(v), a mean squared point-to-plane distance in m^2:
+ *     C(x) = sum_v rho(s_v) + sum_k 1/2 |L_k r_k(x)|^2        the priors are never under the loss
+ *     g    = sum_v rho'(s_v) g_v                              the exact gradient of C
+ *     H    = sum_v rho'(s_v) H_v                              H_v: the exact second-order voxel Hessian
+ * A voxel is down-weighted when its RMS plane distance exceeds a: exactly so for HUBER and TUKEY, as the knee of SOFTLONE and
+ * CAUCHY.  Not for ARCTAN: that kind (as Ceres defines it) weighs with 1 / (1 + s^2 / a^2), comparing s with a rather than with
+ * a^2, so with s in m^2 and a in m only voxels with lambda_min near a lose weight -- at a ~ 0.1 m hardly any.
+ * There is no factor 1/2 on the voxel sum: TRIVIAL is exactly the cost without a loss.  The term rho''(s_v) g_v g_v^T is left out of H on purpose: every kind has rho'' <= 0, so the term is negative
+ * semidefinite and the kept matrix majorises the true Hessian -- the choice the visual stage makes (Ceres' corrector takes only its
+ * scaling branch for rho'' <= 0); keeping it would need a fourth column in every per-factor record of the Hessian assembly.
+ * lvba_balm_covariance returns the inverse of this H.  The LM loop is damping_iter unchanged on the robust quantities: residual1/2,
+ * the averaged costs, q, q1 and the exit test all use C.
+ *   lvba_balm_set_loss         NULL or TRIVIAL restores the default.  LVBA_ERR_ARG (handle unchanged): unknown kind, or a non-trivial
+ *                              kind with a scale that is not finite and > 0.  LVBA_ERR_STATE: between lvba_balm_lm_begin and
+ *                              lvba_balm_lm_end; allowed at any other time, on plain, grouped and dissected handles, with priors.
+ *                              Like lvba_balm_eval it replaces the handle's last evaluation (a later lvba_balm_solve needs a fresh
+ *                              one).  Sharded handles: a collective call like lvba_balm_set_priors -- every rank makes it, with the same
+ *                              loss; the next collective call checks that and returns LVBA_ERR_ARG on every rank if they differ.
+ *   lvba_balm_voxel_residuals  lambda_min [n_voxels] and weight [n_voxels] = rho'(lambda_min) at `poses`, in the CALLER's voxel order
+ *                              (whatever order the handle keeps its voxels in); either may be NULL.  Without a loss every weight is 1.
+ *                              Rank-local on a sharded handle (its own voxels) -- but the handle's set-up is collective: make
+ *                              the first cost / eval / refine call (on every rank) before this one.
+ * lvba_version() is unchanged by these calls (112); a client detects them by looking the symbols up.
+ * A TUKEY loss can leave a pose whose voxels all have weight zero: a rank-deficient problem, reported as any other
+ * (LVBA_NUM_FACTORIZATION from the solve / the LM row); there is no fallback. */
+#define LVBA_LOSS_TRIVIAL 0
+#define LVBA_LOSS_HUBER 1
+#define LVBA_LOSS_SOFTLONE 2
+#define LVBA_LOSS_CAUCHY 3
+#define LVBA_LOSS_ARCTAN 4
+#define LVBA_LOSS_TUKEY 5
+typedef struct {
+    int32_t kind;         /* LVBA_LOSS_* */
+    int32_t reserved;
+    double scale;         /* a > 0, finite; ignored for TRIVIAL */
+} lvba_loss;
+int32_t lvba_balm_set_loss(lvba_balm_t h, const lvba_loss *loss);
+int32_t lvba_balm_voxel_residuals(lvba_balm_t h, const double *poses, double *lambda_min, double *weight);
+
 /* Profiling (HIP events around the stages, on the stream the kernels are launched on). */
 int32_t lvba_balm_set_profiling(lvba_balm_t h, int32_t enable);
 int32_t lvba_balm_get_profile(lvba_balm_t h, lvba_prof_t *out, int32_t reset);
@@ -392,17 +432,7 @@ int32_t lvba_visual_linearize(lvba_visual_t h, const double *q, const double *t,
  *   TUKEY     s <= a^2: a^2/3 (1 - (1 - s/a^2)^3), else a^2/3
  * The reference's own (unused) constants, :1585-1586: HUBER 1.0 on the reprojection blocks (0.5 px at sigma_px 0.5), HUBER 0.1
  * on the plane blocks (1 mm at sigma_plane 0.01). */
-#define LVBA_LOSS_TRIVIAL 0
-#define LVBA_LOSS_HUBER 1
-#define LVBA_LOSS_SOFTLONE 2
-#define LVBA_LOSS_CAUCHY 3
-#define LVBA_LOSS_ARCTAN 4
-#define LVBA_LOSS_TUKEY 5
-typedef struct {
-    int32_t kind;         /* LVBA_LOSS_* */
-    int32_t reserved;
-    double scale;         /* a > 0, finite; ignored for TRIVIAL */
-} lvba_loss;
+/* (LVBA_LOSS_* and lvba_loss are defined above, with lvba_balm_set_loss: both stages share them) */
 
 /* Loss of the reprojection blocks (one 2-vector per observation) and of the plane blocks (one per active landmark); NULL =
  * TRIVIAL.  Kept on the handle for every later cost / linearize / refine call.  An unknown kind, or a non-trivial kind with a
@@ -624,6 +654,14 @@ int32_t lvba_lidar_ba_priors(lvba_scans_t scans, const double *poses_in, const l
 int32_t lvba_lidar_ba_multi_priors(int32_t n_shares, const lvba_scans_t *scans, const double *poses_in, const lvba_lidar_ba_opts *opts,
                                    int32_t n_priors, const lvba_prior *priors, double *poses_out, lvba_lidar_ba_report *report,
                                    lvba_prior *anchor_priors, int32_t *n_used, int32_t *n_dropped);
+
+/* lvba_lidar_ba_multi_priors with robust losses (lvba_balm_set_loss): window_loss on every window problem, stage_loss on both global
+ * stages; either may be NULL (none).  The priors stay outside the loss.  Both NULL: exactly lvba_lidar_ba_multi_priors (and with
+ * n_shares = 1, n_priors = 0 exactly lvba_lidar_ba).  LVBA_ERR_ARG for an invalid loss, before any work is done. */
+int32_t lvba_lidar_ba_robust(int32_t n_shares, const lvba_scans_t *scans, const double *poses_in, const lvba_lidar_ba_opts *opts,
+                             const lvba_loss *window_loss, const lvba_loss *stage_loss, int32_t n_priors, const lvba_prior *priors,
+                             double *poses_out, lvba_lidar_ba_report *report, lvba_prior *anchor_priors, int32_t *n_used,
+                             int32_t *n_dropped);
 
 /* Frame count and per-frame point counts of a scan set; host copy of one frame's xyz [count][3]. */
 int32_t lvba_scans_info(lvba_scans_t scans, int32_t *n_frames, int64_t *frame_count);
