@@ -19,7 +19,7 @@ SYMBOLS = [
     "lvba_balm_set_loss", "lvba_balm_voxel_residuals",
     "lvba_dist_unique_id", "lvba_balm_dist_init", "lvba_balm_dist_init_external", "lvba_visual_dist_init_external",
     "lvba_visual_default_opts", "lvba_visual_create", "lvba_visual_destroy", "lvba_visual_cost", "lvba_visual_linearize", "lvba_visual_info", "lvba_visual_dist_init",
-    "lvba_visual_refine", "lvba_visual_set_loss", "lvba_visual_residual_sq",
+    "lvba_visual_refine", "lvba_visual_set_loss", "lvba_visual_residual_sq", "lvba_visual_set_priors", "lvba_visual_prior_residuals",
     "lvba_voxel_default_opts", "lvba_voxmap_build", "lvba_voxmap_destroy", "lvba_voxmap_info", "lvba_voxmap_export",
     "lvba_voxmap_to_balm", "lvba_voxmap_find_planes", "lvba_scans_create", "lvba_scans_destroy", "lvba_voxmap_build_scans",
     "lvba_release_cached_memory", "lvba_window_default_opts", "lvba_window_ba", "lvba_window_split", "lvba_window_ba_multi", "lvba_scans_info", "lvba_scans_download",
@@ -254,6 +254,8 @@ def load():
                                        C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.lvba_visual_set_loss.argtypes = [H, C.POINTER(Loss), C.POINTER(Loss)]
     lib.lvba_visual_residual_sq.argtypes = [H, f64p, f64p, f64p, C.c_void_p, C.c_void_p]
+    lib.lvba_visual_set_priors.argtypes = [H, C.c_int32, C.c_void_p]
+    lib.lvba_visual_prior_residuals.argtypes = [H, f64p, f64p, C.c_void_p, C.POINTER(C.c_double)]
     lib.lvba_voxel_default_opts.argtypes = [C.POINTER(VoxelOpts)]
     lib.lvba_voxel_default_opts.restype = None
     lib.lvba_voxmap_build.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_void_p), i64p, C.c_int32, f64p,

@@ -105,6 +105,19 @@ struct PriorDev {
     const int32_t *gpose = nullptr, *goff = nullptr, *gsrc = nullptr;
 };
 
+// lin record of prior k (priors.hip, visual_priors.hip): [0] unused, [1..6] J_i^T e, [7..12] J_j^T e, [13..48] J_i^T J_i,
+// [49..84] J_j^T J_j, [85..120] cross block, 6 x 6 blocks in the store's element order (column-major: [c * 6 + r])
+enum { PL_GI = 1, PL_GJ = 7, PL_HII = 13, PL_HJJ = 49, PL_HX = 85 };
+
+// Device view of a visual handle's camera priors (lvba_visual_set_priors; visual_priors.hip).  Records and scatter tables are
+// those of the LiDAR stage (tab: pr, lin, part, ticket, tables), cameras in solver order; `active`: this rank adds them (rank 0
+// of a sharded handle; the cameras are replicated).  pscal [2]: trial-point sum |e|^2 | model cost change of one LM iteration.
+struct VisPriorDev {
+    PriorDev tab;
+    int32_t active = 0, fixed_cam = 0;
+    double *pscal = nullptr;
+};
+
 // Working matrix of the damped system, lower triangle, column-major with leading dimension ld:
 // A(r,c) = a[r + c*ld].  Dense: ld = n.  Band: LAPACK lower-band storage with ldab = ld+1, i.e.
 // A(r,c) = ab[(r-c) + c*ldab]; valid offsets 0 <= r-c <= ld.  bw = half bandwidth in scalars.
@@ -217,6 +230,20 @@ void launch_export_poses(const double *in, const int *perm, int n_poses, double 
 void launch_prior_eval(const PriorDev &d, const double *poses, double *Hblk, double *g, double *scal, hipStream_t s); // scal[0] += cost
 void launch_prior_cost(const PriorDev &d, const double *poses, double *out, double *e_out, hipStream_t s);             // out[0] += cost
 void launch_prior_zero_slots(double *Hblk, const int64_t *slot, int64_t n, hipStream_t s);
+void launch_prior_scatter(const PriorDev &d, double *Hblk, double *g, hipStream_t s); // the lin records into the store and g
+
+// visual_priors.hip: nothing is launched when the handle has no priors or another rank adds them
+// iteration 0: records at (qc, tc) without the Jacobi scaling, scal0[0] += sum |e|^2; then colsum [M][6] += their squared column norms
+void vprior_launch_lin0(const VisPriorDev &d, const double *qc, const double *tc, double *scal0, hipStream_t s);
+void vprior_launch_colsum_add(const VisPriorDev &d, double *colsum, hipStream_t s);
+// records with the scaling sc_cam applied, scattered into the store, the reduced rhs g and camsum = diag(Jc^T Jc) [6 M] | Jc^T r [6 M]
+void vprior_launch_eval(const VisPriorDev &d, const double *qc, const double *tc, const double *sc_cam, int32_t M, double *Hblk,
+                        double *g, double *camsum, hipStream_t s);
+// trial point (qc2, tc2): sum |e|^2 -> out_cost[0]; model cost change of the scaled camera step step_c at (qc, tc) -> out_model[0]
+// (step_c NULL: none).  add: += instead of =.  e_out (may be NULL) [n][6]: the whitened residuals at (qc2, tc2).
+void vprior_launch_trial(const VisPriorDev &d, const double *qc, const double *tc, const double *step_c, const double *sc_cam,
+                         const double *qc2, const double *tc2, double *out_cost, double *out_model, bool add, double *e_out,
+                         hipStream_t s);
 
 // visual_kernels.hip
 void vis_launch_residuals(const VisDev &d, bool jac, const double *qc, const double *tc, const double *Xp, double *part,
@@ -232,7 +259,7 @@ void vis_launch_reduced_system(const VisDev &d, const PairDev &pd, const double 
                                int64_t hblk_doubles, double *g, unsigned long long *gmax, bool zero_first, hipStream_t s);
 void vis_launch_step_and_trial(const VisDev &d, const double *step_c, const double *qc, const double *tc, const double *Xp, double *qc2,
                                double *tc2, double *Xp2, double *part, double *scal, const unsigned long long *gmax, const int *status,
-                               double *host_pin, hipStream_t s);
+                               double *host_pin, hipStream_t s, const VisPriorDev *vp = nullptr); // vp: the camera priors' share
 void vis_launch_back(const VisDev &d, const double *step_c, const double *qc, const double *tc, const double *Xp, double *part,
                      double *model_out, hipStream_t s);
 void vis_launch_apply(const VisDev &d, const double *step_c, const double *qc, const double *tc, const double *Xp, double *qc2,

@@ -17,9 +17,7 @@ namespace lvba {
 
 #define PRIOR_WG 256
 
-// lin record of prior k: [0] unused, [1..6] J_i^T e, [7..12] J_j^T e, [13..48] J_i^T J_i, [49..84] J_j^T J_j, [85..120] cross block,
-// 6 x 6 blocks in the store's element order (column-major: [c * 6 + r])
-enum { PL_GI = 1, PL_GJ = 7, PL_HII = 13, PL_HJJ = 49, PL_HX = 85 };
+// (the lin record of prior k: PL_* in lvba_internal.h)
 
 // Fixed-order sum of one value per lane over the whole grid (64-lane workgroups); the last workgroup to finish adds the total to
 // out[0] and resets the ticket for the next launch on the stream.
@@ -185,12 +183,18 @@ __global__ void prior_zero_slots_kernel(double *__restrict__ Hblk, const int64_t
     if (t < 36 * n) Hblk[slot[t / 36] * 36 + t % 36] = 0.0;
 }
 
+void launch_prior_scatter(const PriorDev &d, double *Hblk, double *g, hipStream_t s)
+{
+    if (d.n <= 0) return;
+    const int64_t work = 36 * d.n_hblk + 6 * (int64_t)d.n_g;
+    hipLaunchKernelGGL(prior_scatter_kernel, dim3((unsigned)((work + PRIOR_WG - 1) / PRIOR_WG)), dim3(PRIOR_WG), 0, s, d, Hblk, g);
+}
+
 void launch_prior_eval(const PriorDev &d, const double *poses, double *Hblk, double *g, double *scal, hipStream_t s)
 {
     if (d.n <= 0) return;
     hipLaunchKernelGGL(prior_lin_kernel, dim3((unsigned)((d.n + 63) / 64)), dim3(64), 0, s, d.pr, d.n, poses, d.lin, d.part, d.ticket, scal);
-    const int64_t work = 36 * d.n_hblk + 6 * (int64_t)d.n_g;
-    hipLaunchKernelGGL(prior_scatter_kernel, dim3((unsigned)((work + PRIOR_WG - 1) / PRIOR_WG)), dim3(PRIOR_WG), 0, s, d, Hblk, g);
+    launch_prior_scatter(d, Hblk, g, s);
 }
 
 void launch_prior_cost(const PriorDev &d, const double *poses, double *out, double *e_out, hipStream_t s)

@@ -7,12 +7,17 @@
 // /= 2,4,8.. on failure.  Host logic only; arithmetic runs in visual_kernels.hip, balm_pair_kernel and ldlt.hip.
 // Robust losses (lvba_visual_set_loss) follow Ceres 2.1's ResidualBlock::Evaluate + Corrector, restated in visual_loss.h: a
 // block contributes 1/2 rho(s) to every cost this driver compares, and (r~, J~) to everything built from the linearisation.
+// Camera pose priors (lvba_visual_set_priors; visual_prior_device.h, visual_priors.hip) are further residual blocks with a
+// trivial loss on one or two cameras: their rows count in the Jacobi scaling, the LM diagonal, the gradient max, the reduced
+// system, the model cost change and every cost.  A handle with priors runs the sharded form of the camera kernels (per-camera
+// sums first, LM diagonal and gradient max after the priors have been added to them); one without launches nothing new.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
 #include <chrono>
+#include <map>
 #include <new>
 #include <vector>
 
@@ -21,6 +26,11 @@
 
 using namespace lvba;
 #define fail lvba_fail
+
+namespace lvba { // lvba_api.hip: the argument checks of lvba_balm_set_priors
+int32_t prior_validate(int32_t n, const lvba_prior *priors, int32_t n_poses);
+void prior_offset_or_identity(const double *o, double *out);
+} // namespace lvba
 
 struct lvba_visual_s {
     BlockSys bs;
@@ -35,6 +45,15 @@ struct lvba_visual_s {
     double loss_scale[2] = {0.0, 0.0};
     bool finalized = false;
     double intr[8] = {}, sig_px = 0.5, sig_pl = 0.01;
+    // camera pose priors (lvba_visual_set_priors): as the caller gave them, and bound to the solver order (bind_priors)
+    std::vector<lvba_prior> priors;
+    VisPriorDev vp;
+    std::vector<void *> prior_mem;      // device allocations behind vp.tab
+    int64_t *d_prior_wslot = nullptr;   // blocks that only priors fill: zeroed when the priors are replaced
+    int64_t n_prior_wslot = 0;
+    lvba::hvec<int64_t> pat_slots;      // blocks the pair pass writes or the packed all-reduce carries (sorted; bind_priors)
+    bool pat_known = false;
+    double *d_pscal = nullptr;          // [2] the priors' trial cost and model cost change of one LM iteration
     // device
     int64_t *d_off = nullptr;
     int32_t *d_cam = nullptr, *d_track_of_obs = nullptr;
@@ -62,7 +81,7 @@ struct lvba_visual_s {
         d.Lp = d_Lp; d.zp = d_zp; d.step_p = d_step_p;
         d.csc_off = bs.d_csc_off; d.csc_f = bs.d_csc_f; d.group_of_pos = bs.d_group_of_pos; d.pos_of = bs.d_pos_of;
         d.Y = bs.d_Y; d.part = d_part;
-        d.dist = bs.distributed() ? 1 : 0; d.count_cams = bs.rank == 0 ? 1 : 0; d.camsum = d_camsum; d.colsum = d_colsum;
+        d.dist = (bs.distributed() || vp.tab.n > 0) ? 1 : 0; d.count_cams = bs.rank == 0 ? 1 : 0; d.camsum = d_camsum; d.colsum = d_colsum;
         d.robust = (loss_kind[0] != LVBA_LOSS_TRIVIAL || loss_kind[1] != LVBA_LOSS_TRIVIAL) ? 1 : 0;
         for (int f = 0; f < 2; ++f) { d.loss_kind[f] = loss_kind[f]; d.loss_scale[f] = loss_scale[f]; }
         return d;
@@ -84,9 +103,10 @@ extern "C" int32_t lvba_visual_destroy(lvba_visual_t h)
     if (h->bs.stream) hipStreamSynchronize(h->bs.stream);
     void *ptrs[] = {h->d_off, h->d_cam, h->d_track_of_obs, h->d_uv, h->d_uv_cm, h->d_plane, h->d_Jc, h->d_Jp, h->d_r, h->d_rpl, h->d_Jpl,
                     h->d_sc_cam, h->d_sc_pt, h->d_Lp, h->d_zp, h->d_step_p, h->d_part, h->d_q, h->d_t, h->d_X, h->d_q2,
-                    h->d_t2, h->d_X2, h->d_blkpart, h->d_scal, h->d_gmax, h->d_out, h->d_camsum, h->d_colsum};
+                    h->d_t2, h->d_X2, h->d_blkpart, h->d_scal, h->d_gmax, h->d_out, h->d_camsum, h->d_colsum, h->d_pscal};
     for (void *p : ptrs)
         if (p) lvba::DevicePool::get().free(p);
+    for (void *p : h->prior_mem) lvba::DevicePool::get().free(p);
     if (h->h_pin) hipHostFree(h->h_pin);
     if (h->h_stage) hipHostFree(h->h_stage);
     bs_destroy(h->bs);
@@ -165,12 +185,15 @@ extern "C" int32_t lvba_visual_create(int32_t n_cams, int64_t n_tracks, const in
     CTRY(bs_dmalloc(bs, &h->d_out, 36 * (int64_t)M + 16));
     CTRY(bs_dmalloc(bs, &h->d_camsum, 12 * (int64_t)M));
     CTRY(bs_dmalloc(bs, &h->d_colsum, 6 * (int64_t)M));
+    CTRY(bs_dmalloc(bs, &h->d_pscal, 2));
     CHIP(hipHostMalloc((void **)&h->h_pin, 16 * sizeof(double), hipHostMallocDefault));
 #undef CTRY
 #undef CHIP
     *out = h;
     return LVBA_OK;
 }
+
+static int32_t bind_priors(lvba_visual_s *h);
 
 static int32_t finalize(lvba_visual_s *h)
 {
@@ -189,6 +212,7 @@ static int32_t finalize(lvba_visual_s *h)
     vis_launch_gather_uv(h->dev(), h->d_uv_cm, bs.stream);
     lvba::hvec<int32_t>().swap(h->h_cam);
     h->finalized = true;
+    if (!h->priors.empty()) TRY(bind_priors(h));
     return LVBA_OK;
 }
 
@@ -238,8 +262,9 @@ static int32_t enqueue_colnorms(lvba_visual_s *h)
 {
     BlockSys &bs = h->bs;
     const VisDev d = h->dev();
-    if (!bs.distributed()) { vis_launch_colnorms(d, bs.stream); return LVBA_OK; }
+    if (!d.dist) { vis_launch_colnorms(d, bs.stream); return LVBA_OK; }
     vis_launch_colsums(d, bs.stream);
+    vprior_launch_colsum_add(h->vp, h->d_colsum, bs.stream); // the prior rows' columns (vprior_launch_lin0 has run)
     TRY(bs_allreduce(bs, h->d_colsum, 6 * (size_t)h->M));
     vis_launch_colnorm_finish(d, bs.stream);
     return LVBA_OK;
@@ -250,11 +275,13 @@ static int32_t enqueue_reduced_system(lvba_visual_s *h, double radius, const lvb
     const VisDev d = h->dev();
     vis_launch_reduced_system(d, bs.pair_dev(), h->d_q, h->d_t, h->d_X, radius, o.min_lm_diagonal, o.max_lm_diagonal, bs.Hblk(), bs.hblk_doubles, bs.g(),
                               h->d_gmax, bs.distributed(), bs.stream);
-    if (!bs.distributed()) return LVBA_OK;
+    if (!d.dist) return LVBA_OK;
+    // camera priors: after the Schur elimination, into the blocks of S, the reduced rhs and the per-camera sums (one rank adds them)
+    vprior_launch_eval(h->vp, h->d_q, h->d_t, h->d_sc_cam, h->M, bs.Hblk(), bs.g(), h->d_camsum, bs.stream);
     TRY(bs_allreduce_hg(bs));                                   // [S blocks | reduced rhs]: sums over the track shards
     TRY(bs_allreduce(bs, h->d_camsum, 12 * (size_t)h->M));      // diag(Jc^T Jc), Jc^T r
     vis_launch_cam_finish(d, radius, o.min_lm_diagonal, o.max_lm_diagonal, bs.Hblk(), h->d_q, h->d_gmax, bs.stream);
-    TRY(bs_comm_allreduce(bs, h->d_gmax, 1, ncclInt64, ncclMax)); // bit patterns of non-negative doubles order like integers
+    if (bs.distributed()) TRY(bs_comm_allreduce(bs, h->d_gmax, 1, ncclInt64, ncclMax)); // bit patterns of non-negative doubles order like integers
     return LVBA_OK;
 }
 static int32_t allreduce_scalars(lvba_visual_s *h, int first, int count)
@@ -271,22 +298,29 @@ static int32_t check_loss_agreement(lvba_visual_s *h)
 {
     BlockSys &bs = h->bs;
     if (!bs.distributed()) return LVBA_OK;
-    int64_t v[8];
+    int64_t v[12];
     for (int f = 0; f < 2; ++f) {
         int64_t bits;
         memcpy(&bits, &h->loss_scale[f], sizeof bits); // scale >= 0: bits < 2^63, their negation does not overflow
         v[f] = h->loss_kind[f]; v[2 + f] = bits;
     }
-    for (int e = 0; e < 4; ++e) v[4 + e] = -v[e];
+    // the camera priors: their count and an FNV-1a hash of the records (reserved fields are stored as zero)
+    uint64_t hs = 1469598103934665603ull;
+    const unsigned char *b = reinterpret_cast<const unsigned char *>(h->priors.data());
+    for (size_t a = 0; a < h->priors.size() * sizeof(lvba_prior); ++a) { hs ^= b[a]; hs *= 1099511628211ull; }
+    v[4] = (int64_t)h->priors.size(); v[5] = (int64_t)(hs >> 2);
+    for (int e = 0; e < 6; ++e) v[6 + e] = -v[e];
     DevBuf buf(bs.stream);
     HIPCHK(buf.alloc(sizeof v));
     HIPCHK(hipMemcpyAsync(buf.p, v, sizeof v, hipMemcpyHostToDevice, bs.stream));
-    TRY(bs_comm_allreduce(bs, buf.p, 8, ncclInt64, ncclMax));
-    int64_t m[8];
+    TRY(bs_comm_allreduce(bs, buf.p, 12, ncclInt64, ncclMax));
+    int64_t m[12];
     HIPCHK(hipMemcpyAsync(m, buf.p, sizeof m, hipMemcpyDeviceToHost, bs.stream));
     HIPCHK(hipStreamSynchronize(bs.stream));
     for (int e = 0; e < 4; ++e)
-        if (m[e] != -m[4 + e]) return fail(LVBA_ERR_ARG, "the ranks of a sharded visual handle set different losses");
+        if (m[e] != -m[6 + e]) return fail(LVBA_ERR_ARG, "the ranks of a sharded visual handle set different losses");
+    for (int e = 4; e < 6; ++e)
+        if (m[e] != -m[6 + e]) return fail(LVBA_ERR_ARG, "the ranks of a sharded visual handle set different camera priors");
     return LVBA_OK;
 }
 
@@ -308,6 +342,186 @@ extern "C" int32_t lvba_visual_set_loss(lvba_visual_t h, const lvba_loss *reproj
         h->loss_kind[f] = trivial ? LVBA_LOSS_TRIVIAL : ls[f]->kind;
         h->loss_scale[f] = trivial ? 0.0 : ls[f]->scale;
     }
+    return LVBA_OK;
+}
+
+// ------------------------------------------------------------------------------------------ camera pose priors
+template <typename T>
+static int32_t prior_upload(lvba_visual_s *h, T **p, size_t n, const T *src)
+{
+    TRY(bs_dmalloc(h->bs, p, (int64_t)n));
+    h->prior_mem.push_back(*p);
+    if (src && n) HIPCHK(lvba::copy_h2d(*p, src, n * sizeof(T)));
+    return LVBA_OK;
+}
+
+// The blocks that hold something besides priors: what the pair pass writes on one rank (a prior adds to those and writes the
+// others); on a sharded handle the whole store is cleared before every linearisation, so every block is added to -- there the
+// list is the union pattern the packed all-reduce carries (empty: the whole store travels).
+static int32_t prior_pattern(lvba_visual_s *h)
+{
+    if (h->pat_known) return LVBA_OK;
+    BlockSys &bs = h->bs;
+    if (!bs.distributed() || bs.d_ar_slot) TRY(bs_pattern_slots(bs, h->pat_slots));
+    h->pat_known = true;
+    return LVBA_OK;
+}
+
+// h->priors -> the solver order, the scatter tables (those of the LiDAR stage, priors.hip) and their device copies
+static int32_t bind_priors(lvba_visual_s *h)
+{
+    BlockSys &bs = h->bs;
+    HIPCHK(hipSetDevice(bs.device));
+    launch_prior_zero_slots(bs.Hblk(), h->d_prior_wslot, h->n_prior_wslot, bs.stream); // what only the old priors filled
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(bs.stream));
+    for (void *p : h->prior_mem) lvba::DevicePool::get().free(p);
+    h->prior_mem.clear();
+    h->vp = VisPriorDev{};
+    h->d_prior_wslot = nullptr;
+    h->n_prior_wslot = 0;
+    const int32_t n = (int32_t)h->priors.size();
+    if (n == 0) return LVBA_OK;
+    TRY(prior_pattern(h));
+    const int64_t Bb1 = (int64_t)bs.Bb + 1;
+    std::vector<PriorRec> rec((size_t)n);
+    std::map<int64_t, std::vector<int32_t>> hb; // slot -> contributions, ascending prior index
+    std::map<int32_t, std::vector<int32_t>> gb; // solver camera -> contributions
+    for (int32_t k = 0; k < n; ++k) {
+        const lvba_prior &q = h->priors[(size_t)k];
+        PriorRec &r = rec[(size_t)k];
+        const bool rel = q.kind == LVBA_PRIOR_RELATIVE;
+        r.kind = q.kind;
+        r.I = bs.iperm[(size_t)q.i];
+        r.J = rel ? bs.iperm[(size_t)q.j] : r.I;
+        r.flip = r.I < r.J ? 1 : 0;
+        memcpy(r.meas, q.meas, sizeof r.meas);
+        prior_offset_or_identity(q.offset_i, r.oi);
+        prior_offset_or_identity(q.offset_j, r.oj);
+        memcpy(r.L, q.sqrt_info, sizeof r.L);
+        hb[(int64_t)r.I * Bb1].push_back(k << 2);
+        gb[r.I].push_back(k << 2);
+        if (rel) {
+            hb[(int64_t)r.J * Bb1].push_back(k << 2 | 1);
+            gb[r.J].push_back(k << 2 | 1);
+            const int32_t lo = std::min(r.I, r.J), hi = std::max(r.I, r.J);
+            hb[(int64_t)lo * Bb1 + (hi - lo)].push_back(k << 2 | 2);
+        }
+    }
+    lvba::hvec<int64_t> hslot, wslot;
+    lvba::hvec<int32_t> hmode, hoff(1, 0), hsrc, gpose, goff(1, 0), gsrc;
+    for (const auto &t : hb) {
+        const bool diag = t.first % Bb1 == 0;
+        const bool add = diag || bs.distributed() || std::binary_search(h->pat_slots.begin(), h->pat_slots.end(), t.first);
+        hslot.push_back(t.first);
+        hmode.push_back((add ? 0 : 1) | (diag ? 2 : 0));
+        if (!add) wslot.push_back(t.first);
+        hsrc.insert(hsrc.end(), t.second.begin(), t.second.end());
+        hoff.push_back((int32_t)hsrc.size());
+    }
+    for (const auto &t : gb) {
+        gpose.push_back(t.first);
+        gsrc.insert(gsrc.end(), t.second.begin(), t.second.end());
+        goff.push_back((int32_t)gsrc.size());
+    }
+    PriorRec *d_rec = nullptr;
+    double *d_lin = nullptr, *d_part = nullptr;
+    unsigned *d_ticket = nullptr;
+    int64_t *d_hslot = nullptr;
+    int32_t *d_hmode = nullptr, *d_hoff = nullptr, *d_hsrc = nullptr, *d_gpose = nullptr, *d_goff = nullptr, *d_gsrc = nullptr;
+    TRY(prior_upload(h, &d_rec, rec.size(), rec.data()));
+    TRY(prior_upload<double>(h, &d_lin, 128 * (size_t)n, nullptr));
+    TRY(prior_upload<double>(h, &d_part, 2 * ((size_t)(n + 63) / 64), nullptr));
+    const unsigned zero = 0;
+    TRY(prior_upload(h, &d_ticket, 1, &zero));
+    TRY(prior_upload(h, &d_hslot, hslot.size(), hslot.data()));
+    TRY(prior_upload(h, &d_hmode, hmode.size(), hmode.data()));
+    TRY(prior_upload(h, &d_hoff, hoff.size(), hoff.data()));
+    TRY(prior_upload(h, &d_hsrc, hsrc.size(), hsrc.data()));
+    TRY(prior_upload(h, &d_gpose, gpose.size(), gpose.data()));
+    TRY(prior_upload(h, &d_goff, goff.size(), goff.data()));
+    TRY(prior_upload(h, &d_gsrc, gsrc.size(), gsrc.data()));
+    if (!wslot.empty()) TRY(prior_upload(h, &h->d_prior_wslot, wslot.size(), wslot.data()));
+    h->n_prior_wslot = (int64_t)wslot.size();
+    PriorDev &d = h->vp.tab;
+    d.pr = d_rec; d.lin = d_lin; d.part = d_part; d.ticket = d_ticket;
+    d.n_hblk = (int64_t)hslot.size(); d.hslot = d_hslot; d.hmode = d_hmode; d.hoff = d_hoff; d.hsrc = d_hsrc;
+    d.n_g = (int32_t)gpose.size(); d.gpose = d_gpose; d.goff = d_goff; d.gsrc = d_gsrc;
+    h->vp.active = bs.rank == 0 ? 1 : 0; // the cameras are replicated over the ranks: one of them adds their priors
+    h->vp.fixed_cam = bs.iperm[0];
+    h->vp.pscal = h->d_pscal;
+    d.n = n; // (last: a failed upload above leaves a handle without priors)
+    return LVBA_OK;
+}
+
+extern "C" int32_t lvba_visual_set_priors(lvba_visual_t h, int32_t n, const lvba_prior *priors)
+{
+    if (!h) return fail(LVBA_ERR_ARG, "handle is NULL");
+    if (n > (1 << 22)) return fail(LVBA_ERR_ARG, "more than 2^22 priors");
+    TRY(lvba::prior_validate(n, priors, h->M));
+    BlockSys &bs = h->bs;
+    if (h->finalized) { // the store is laid out: every relative pair must be one of its blocks
+        TRY(prior_pattern(h));
+        for (int32_t k = 0; k < n; ++k) {
+            if (priors[k].kind != LVBA_PRIOR_RELATIVE) continue;
+            const int32_t I = bs.iperm[(size_t)priors[k].i], J = bs.iperm[(size_t)priors[k].j];
+            const int32_t lo = std::min(I, J), hi = std::max(I, J);
+            bool ok = hi - lo <= bs.Bb;
+            if (ok && bs.d_ar_slot) // sharded: only the blocks of the union pattern travel
+                ok = std::binary_search(h->pat_slots.begin(), h->pat_slots.end(), (int64_t)lo * (bs.Bb + 1) + (hi - lo));
+            if (!ok) return fail(LVBA_ERR_STATE, "prior %d joins cameras %d and %d, which are no block of the store laid out at the first "
+                                 "cost / linearize / refine call: set such priors before it", k, priors[k].i, priors[k].j);
+        }
+    }
+    std::vector<lvba_prior> old(priors, priors + n);
+    old.swap(h->priors); // (old: what the handle held)
+    for (lvba_prior &q : h->priors) {
+        q.reserved = 0;
+        if (q.kind != LVBA_PRIOR_RELATIVE) { q.j = 0; memset(q.offset_j, 0, sizeof q.offset_j); }
+    }
+    if (!h->finalized) {
+        bs.edge_i.clear(); bs.edge_j.clear();
+        for (const lvba_prior &q : h->priors)
+            if (q.kind == LVBA_PRIOR_RELATIVE) { bs.edge_i.push_back(q.i); bs.edge_j.push_back(q.j); }
+        return LVBA_OK;
+    }
+    const int32_t rc = bind_priors(h);
+    if (rc != LVBA_OK) { // out of memory / a failed upload: the handle keeps the priors it had (their pairs are blocks of the store)
+        h->priors.swap(old);
+        bind_priors(h);
+    }
+    return rc;
+}
+
+extern "C" int32_t lvba_visual_prior_residuals(lvba_visual_t h, const double *q, const double *t, double *e, double *cost)
+{
+    if (!h || !q || !t) return fail(LVBA_ERR_ARG, "NULL argument");
+    if (!h->finalized && h->bs.distributed()) // finalize is collective there; this call is not
+        return fail(LVBA_ERR_STATE, "prior_residuals on a sharded handle must follow its first cost / linearize / refine call");
+    TRY(finalize(h));
+    BlockSys &bs = h->bs;
+    HIPCHK(hipSetDevice(bs.device));
+    const int64_t n = h->vp.tab.n;
+    if (n == 0) { if (cost) *cost = 0.0; return LVBA_OK; }
+    DevBuf d(bs.stream);
+    HIPCHK(d.alloc((size_t)(6 * n + 1 + 7 * (int64_t)h->M) * sizeof(double)));
+    double *de = d.as<double>(), *dq = de + 6 * n + 1, *dt = dq + 4 * (int64_t)h->M;
+    lvba::hvec<double> st(7 * (size_t)h->M);
+    for (int c = 0; c < h->M; ++c) {
+        const int I = bs.iperm[c];
+        for (int a = 0; a < 4; ++a) st[4 * (size_t)I + a] = q[4 * c + a];
+        for (int a = 0; a < 3; ++a) st[4 * (size_t)h->M + 3 * (size_t)I + a] = t[3 * c + a];
+    }
+    HIPCHK(lvba::copy_h2d(dq, st.data(), st.size() * sizeof(double)));
+    VisPriorDev vp = h->vp;
+    vp.active = 1; // rank-local: every rank holds the cameras and the priors
+    vprior_launch_trial(vp, nullptr, nullptr, nullptr, nullptr, dq, dt, de + 6 * n, nullptr, false, de, bs.stream);
+    HIPCHK(hipGetLastError());
+    double c2 = 0.0;
+    if (e) HIPCHK(hipMemcpyAsync(e, de, (size_t)(6 * n) * sizeof(double), hipMemcpyDeviceToHost, bs.stream));
+    HIPCHK(hipMemcpyAsync(&c2, de + 6 * n, sizeof(double), hipMemcpyDeviceToHost, bs.stream));
+    HIPCHK(hipStreamSynchronize(bs.stream));
+    if (cost) *cost = 0.5 * c2;
     return LVBA_OK;
 }
 
@@ -334,6 +548,7 @@ extern "C" int32_t lvba_visual_cost(lvba_visual_t h, const double *q, const doub
     TRY(check_loss_agreement(h));
     TRY(import_state(h, q, t, X));
     vis_launch_residuals(h->dev(), false, h->d_q, h->d_t, h->d_X, h->d_blkpart, h->d_scal, bs.stream);
+    vprior_launch_trial(h->vp, nullptr, nullptr, nullptr, nullptr, h->d_q, h->d_t, h->d_scal, nullptr, true, nullptr, bs.stream);
     TRY(allreduce_scalars(h, 0, 1));
     HIPCHK(hipMemcpyAsync(h->h_pin, h->d_scal, sizeof(double), hipMemcpyDeviceToHost, bs.stream));
     HIPCHK(hipStreamSynchronize(bs.stream));
@@ -392,6 +607,7 @@ extern "C" int32_t lvba_visual_linearize(lvba_visual_t h, const double *q, const
     lvba_visual_default_opts(&o);
     const VisDev d = h->dev();
     vis_launch_residuals(d, true, h->d_q, h->d_t, h->d_X, h->d_blkpart, h->d_scal, bs.stream);
+    vprior_launch_lin0(h->vp, h->d_q, h->d_t, h->d_scal, bs.stream);
     TRY(allreduce_scalars(h, 0, 1));
     TRY(enqueue_colnorms(h));
     TRY(enqueue_reduced_system(h, radius, o));
@@ -440,6 +656,7 @@ extern "C" int32_t lvba_visual_refine(lvba_visual_t h, double *q, double *t, dou
     VisDev d = h->dev();
     // iteration 0: evaluate, fix the Jacobi scaling
     vis_launch_residuals(d, true, h->d_q, h->d_t, h->d_X, h->d_blkpart, h->d_scal, bs.stream);
+    vprior_launch_lin0(h->vp, h->d_q, h->d_t, h->d_scal, bs.stream);
     TRY(allreduce_scalars(h, 0, 1));
     TRY(enqueue_colnorms(h));
     HIPCHK(hipMemcpyAsync(h->h_pin, h->d_scal, sizeof(double), hipMemcpyDeviceToHost, bs.stream));
@@ -472,13 +689,15 @@ extern "C" int32_t lvba_visual_refine(lvba_visual_t h, double *q, double *t, dou
             // the host reads below into the pinned buffer (no reductions of their own, no device-to-host copies)
             mark(3);
             vis_launch_step_and_trial(d, bs.d_dx, h->d_q, h->d_t, h->d_X, h->d_q2, h->d_t2, h->d_X2, h->d_blkpart, h->d_scal, h->d_gmax,
-                                      bs.d_status, h->h_pin, bs.stream);
+                                      bs.d_status, h->h_pin, bs.stream, &h->vp);
             mark(4);
         } else {
             vis_launch_back(d, bs.d_dx, h->d_q, h->d_t, h->d_X, h->d_blkpart, h->d_scal + 2, bs.stream);
             mark(3);
             vis_launch_apply(d, bs.d_dx, h->d_q, h->d_t, h->d_X, h->d_q2, h->d_t2, h->d_X2, h->d_blkpart, h->d_scal + 3, bs.stream);
             vis_launch_residuals(d, false, h->d_q2, h->d_t2, h->d_X2, h->d_blkpart, h->d_scal + 1, bs.stream);
+            vprior_launch_trial(h->vp, h->d_q, h->d_t, bs.d_dx, h->d_sc_cam, h->d_q2, h->d_t2, h->d_scal + 1, h->d_scal + 2, true, nullptr,
+                                bs.stream); // (one rank adds the priors' trial cost and model cost change)
             mark(4);
             TRY(allreduce_scalars(h, 1, 4)); // candidate cost, model cost change, |step|^2, |x|^2: sums over the track shards
             HIPCHK(hipMemcpyAsync(h->h_pin, h->d_scal, 5 * sizeof(double), hipMemcpyDeviceToHost, bs.stream));

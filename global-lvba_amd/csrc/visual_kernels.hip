@@ -645,10 +645,12 @@ __global__ void vis_gather_uv_kernel(VisDev d, double *__restrict__ uv_cm)
 // parameter norms | cost at the trial point) summed in a fixed order, and everything the host's accept / reject logic reads
 // written straight into its pinned buffer: host[0..4] = scal[0..4], host[8] = gradient max (bits), host[9] = solver status.
 // Replaces three single-workgroup reductions and three device-to-host copies (six stream operations of ~5 us each).
+// pscal (NULL without camera priors): their sum |e|^2 at the trial point and their share of the model cost change
+// (visual_priors.hip), added last.
 __global__ __launch_bounds__(1024) void vis_finish_kernel(const double *__restrict__ part, int64_t nb_back, int64_t nb_apply,
                                                           int64_t nb_res, double *__restrict__ scal,
                                                           const unsigned long long *__restrict__ gmax, const int *__restrict__ status,
-                                                          double *__restrict__ host)
+                                                          double *__restrict__ host, const double *__restrict__ pscal)
 {
     __shared__ double red[4][16];
     const double *pb = part, *pa = part + nb_back, *pr = part + nb_back + 2 * nb_apply;
@@ -666,6 +668,7 @@ __global__ __launch_bounds__(1024) void vis_finish_kernel(const double *__restri
         double t[4] = {0.0, 0.0, 0.0, 0.0};
         for (int k = 0; k < 4; ++k)
             for (int w = 0; w < 16; ++w) t[k] += red[k][w];
+        if (pscal) { t[3] += pscal[0]; t[0] += pscal[1]; }
         scal[2] = t[0]; scal[3] = t[1]; scal[4] = t[2]; scal[1] = t[3];
         host[0] = scal[0]; host[1] = t[3]; host[2] = t[0]; host[3] = t[1]; host[4] = t[2];
         host[8] = __longlong_as_double((long long)gmax[0]);
@@ -704,7 +707,7 @@ void vis_launch_residuals(const VisDev &d, bool jac, const double *qc, const dou
 // back-substitution, candidate point and its cost with ONE closing kernel (vis_finish_kernel) instead of a reduction each
 void vis_launch_step_and_trial(const VisDev &d, const double *step_c, const double *qc, const double *tc, const double *Xp, double *qc2,
                                double *tc2, double *Xp2, double *part, double *scal, const unsigned long long *gmax, const int *status,
-                               double *host_pin, hipStream_t s)
+                               double *host_pin, hipStream_t s, const VisPriorDev *vp)
 {
     const unsigned nb_back = vis_back_grid(d.Ta), nb_apply = nblk(d.M + d.Ta, 256), nb_res = nblk(d.O + d.Ta, 256);
     double *pa = part + nb_back, *pr = pa + 2 * (int64_t)nb_apply;
@@ -713,8 +716,10 @@ void vis_launch_step_and_trial(const VisDev &d, const double *step_c, const doub
     hipLaunchKernelGGL(vis_apply_kernel, dim3(nb_apply), dim3(256), 0, s, d, step_c, qc, tc, Xp, qc2, tc2, Xp2, pa);
     if (d.robust) hipLaunchKernelGGL((vis_residual_kernel<false, true>), dim3(nb_res), dim3(256), 0, s, d, qc2, tc2, Xp2, pr);
     else hipLaunchKernelGGL((vis_residual_kernel<false, false>), dim3(nb_res), dim3(256), 0, s, d, qc2, tc2, Xp2, pr);
+    const bool pri = vp && vp->tab.n > 0;
+    if (pri) vprior_launch_trial(*vp, qc, tc, step_c, d.sc_cam, qc2, tc2, vp->pscal, vp->pscal + 1, false, nullptr, s);
     hipLaunchKernelGGL(vis_finish_kernel, dim3(1), dim3(1024), 0, s, part, (int64_t)nb_back, (int64_t)nb_apply, (int64_t)nb_res, scal,
-                       gmax, status, host_pin);
+                       gmax, status, host_pin, pri ? (const double *)vp->pscal : (const double *)nullptr);
 }
 
 void vis_launch_colnorms(const VisDev &d, hipStream_t s)

@@ -74,6 +74,26 @@ def camera_from_imu(T_wi, Rci, tci):
     return Rcw, tcw
 
 
+def lidar_camera_priors(cam_poses, Rci, tci, sigma_rot, sigma_pos, relative=False):
+    """Camera pose priors (VisualProblem.set_priors) that tie the visual stage to the LiDAR trajectory.  cam_poses [m,12]: the
+    pose T_world<-imu the LiDAR trajectory gives every image (update_camera_poses_from_lidar).  relative=False: one POSE prior
+    per camera; relative=True: one RELATIVE prior per pair of consecutive cameras (the trajectory's shape, free to move as a
+    whole).  Every prior carries the extrinsic O = T_cam<-imu = (Rci, tci) as offset, so that what it constrains,
+    T_world<-cam O, is the IMU pose and the measurement is the LiDAR pose itself (or the relative pose of two of them).
+    sigma_rot [rad] / sigma_pos [m]: scalars or 3-vectors."""
+    from .balm import Prior
+    R, p = _mat(cam_poses)
+    O = np.r_[np.asarray(Rci, np.float64).reshape(9), np.asarray(tci, np.float64).reshape(3)]
+    if not relative:
+        return [Prior.pose(k, np.r_[R[k].reshape(9), p[k]], sigma_rot, sigma_pos, offset=O) for k in range(len(R))]
+    out = []
+    for k in range(len(R) - 1):
+        Rij = R[k].T @ R[k + 1]
+        out.append(Prior.relative(k, k + 1, np.r_[Rij.reshape(9), R[k].T @ (p[k + 1] - p[k])], sigma_rot, sigma_pos, offset_i=O,
+                                  offset_j=O))
+    return out
+
+
 def rot_to_quat_wxyz(R):
     """Eigen::Quaterniond(R).normalize() as [w, x, y, z] (src/lvba_system.cpp:1514-1517)."""
     from .dataset import rot_to_quat
@@ -193,11 +213,13 @@ def build_tracks_and_fuse(keypoints, pairs, matches, fuse_fn, obser_thr=3):
 
 
 def run_visual_ba_with_lidar_assist(scans, x_opt, x_orig, scan_times, image_times, image_poses, Rci, tci, intr, width, height,
-                                    keypoints, pairs, matches, **cfg):
+                                    keypoints, pairs, matches, camera_priors=None, **cfg):
     """LvbaSystem::runVisualBAWithLidarAssist (src/lvba_system.cpp:144-154) from the refined LiDAR poses to the refined
     cameras.  scans: a voxel.Scans holding the raw clouds; keypoints[i] = [n_i, 2] float pixel coordinates; pairs / matches as
-    build_tracks takes them.  cfg["visual_loss"]: see DEFAULTS.  Returns a dict (cameras before / after, tracks, landmarks, planes,
-    traces)."""
+    build_tracks takes them.  cfg["visual_loss"]: see DEFAULTS.  camera_priors: None (the reference's problem), a list of
+    balm.Prior objects on cameras, or a callable cam_poses -> list, called with the LiDAR-derived image poses [m,12]
+    (T_world<-imu) that only exist inside this call (e.g. lambda cams: lidar_camera_priors(cams, Rci, tci, 1e-3, 0.02)).
+    Returns a dict (cameras before / after, tracks, landmarks, planes, traces)."""
     c = dict(DEFAULTS); c.update(cfg)
     cam_new = update_camera_poses_from_lidar(x_opt, x_orig, scan_times, image_times, image_poses)      # poses_
     Rcw, tcw = camera_from_imu(cam_new, Rci, tci)                                                      # Rcw_all_optimized_
@@ -237,9 +259,11 @@ def run_visual_ba_with_lidar_assist(scans, x_opt, x_orig, scan_times, image_time
         o_off.append(len(o_cam))
     q0 = rot_to_quat_wxyz(Rcw)
     loss_r, loss_p = c["visual_loss"] if c["visual_loss"] is not None else (None, None)
+    priors = camera_priors(cam_new) if callable(camera_priors) else camera_priors
     (q, t, Xn), trace, term, rc, valid = V.optimize_camera_poses(
         q0, tcw, X[tr], np.asarray(o_off, np.int64), np.asarray(o_cam, np.int32), np.asarray(o_uv, np.float64).reshape(-1, 2),
-        plane[:, :3], plane[:, 3], intr, c["sigma_px"], c["sigma_plane"], loss_reproj=loss_r, loss_plane=loss_p)
+        plane[:, :3], plane[:, 3], intr, c["sigma_px"], c["sigma_plane"], loss_reproj=loss_r, loss_plane=loss_p,
+        priors=priors)
     out.update(Rcw=quat_wxyz_to_rot(q), tcw=np.asarray(t), q=q, landmarks=np.asarray(Xn), landmarks_before=X[tr],
                landmark_valid=valid, track_ids=tr, plane=plane, plane_valid=pvalid, obs_off=np.asarray(o_off), obs_cam=np.asarray(o_cam),
                obs_uv=np.asarray(o_uv).reshape(-1, 2), trace=trace, termination=term, status=rc, mean_reproj=err[tr])
@@ -325,14 +349,15 @@ def run_lidar_ba(scans, poses, priors=None, window_loss=None, stage_loss=None, h
 
 def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, tci, intr, width, height, keypoints, pairs,
                       matches, enable_lidar_ba=True, enable_visual_ba=True, device=0, images=None, lidar_priors=None,
-                      window_loss=None, stage_loss=None, **cfg):
+                      window_loss=None, stage_loss=None, camera_priors=None, **cfg):
     """LvbaSystem::runFullPipeline (src/lvba_system.cpp:136-142) on in-memory data: clouds = body-frame [n_i, >=3] float32
     arrays, poses [n,12] = x_buf_ (T_world<-imu), image_poses [m,12] the image poses from the odometry.  cfg: DEFAULTS' keys
     (visual_loss, colorize_leaf among them).  images: None, or the images ([m,H,W,3] BGR uint8 or a callable k -> [H,W,3]):
     then the output also holds colored_after / colored_before = (xyz, rgb), the LiDAR map coloured from them
     (colorize_maps) with the refined poses and cameras and with the original ones; this needs the visual stage.
     lidar_priors: balm.Prior objects on frames (GNSS fixes, loop closures, ...) for the global stages of the LiDAR BA
-    (Scans.lidar_ba(priors=...)).  window_loss / stage_loss: robust losses of the LiDAR BA (run_lidar_ba)."""
+    (Scans.lidar_ba(priors=...)).  window_loss / stage_loss: robust losses of the LiDAR BA (run_lidar_ba).  camera_priors:
+    priors on the cameras of the visual stage (run_visual_ba_with_lidar_assist; None: none)."""
     if images is not None and not enable_visual_ba:
         raise ValueError("colouring the map needs the cameras of the visual stage (enable_visual_ba=True)")
     c = dict(DEFAULTS); c.update(cfg)
@@ -346,7 +371,8 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
         out["poses"] = np.asarray(x_opt).reshape(-1, 12)
         if enable_visual_ba:
             out["visual"] = run_visual_ba_with_lidar_assist(scans, out["poses"], x_orig, scan_times, image_times, image_poses, Rci,
-                                                            tci, intr, width, height, keypoints, pairs, matches, **c)
+                                                            tci, intr, width, height, keypoints, pairs, matches,
+                                                            camera_priors=camera_priors, **c)
         if images is not None:
             v = out["visual"]
             col = colorize_maps(scans, image_times, images, intr, width, height, after=(out["poses"], v["Rcw"], v["tcw"]),
@@ -397,7 +423,8 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
     the camera's is resized with Pillow's bilinear filter, which is not OpenCV's INTER_LINEAR bit for bit.  The output gains
     colored_after / colored_before, and out_dir gets colored_merged_after.pcd / colored_merged_before.pcd (binary PCD, PCL's
     XYZRGB layout) and a points3D.txt holding the coloured after-cloud, as the reference writes them.
-    cfg as for run_full_pipeline, e.g. visual_loss=REFERENCE_HUBER, window_loss=("cauchy", 0.1), stage_loss=("huber", 0.05)."""
+    cfg as for run_full_pipeline, e.g. visual_loss=REFERENCE_HUBER, window_loss=("cauchy", 0.1), stage_loss=("huber", 0.05),
+    camera_priors=lambda cams: lidar_camera_priors(cams, Rci, tci, 1e-3, 0.02)."""
     import os
     from . import dataset as D
     ds = D.load_dataset(data_path)

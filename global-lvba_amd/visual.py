@@ -65,6 +65,29 @@ class VisualProblem:
         residual units -- ("huber", 1.0) / ("huber", 0.1) are the reference's constants (src/lvba_system.cpp:1585-1586)."""
         L.check(self.lib.lvba_visual_set_loss(self._h, *(loss_struct(x) for x in (reproj, plane))))
 
+    def set_priors(self, priors):
+        """Camera pose priors (lvba_visual_set_priors): a sequence of balm.Prior.pose / .position / .relative with camera indices;
+        the pose they constrain is T_world<-cam (times the prior's offset, e.g. T_cam<-imu for a prior on the body pose).  Empty
+        or None clears them.  Relative priors that join new pairs of cameras must come before the first cost / linearize /
+        refine / prior_residuals call."""
+        priors = list(priors or [])
+        arr = (L.Prior * max(1, len(priors)))(*priors)
+        L.check(self.lib.lvba_visual_set_priors(self._h, len(priors), C.cast(arr, C.c_void_p) if priors else None))
+        self.n_priors = len(priors)
+
+    def prior_residuals(self, q, t):
+        """(e [n, 6] whitened residuals L r in the order given to set_priors -- position priors fill e[k, :3] --, their cost
+        sum 1/2 |e|^2) at the cameras q [M,4], t [M,3]"""
+        n = getattr(self, "n_priors", 0)
+        q = np.ascontiguousarray(q, np.float64).reshape(-1)
+        t = np.ascontiguousarray(t, np.float64).reshape(-1)
+        if q.size != 4 * self.n_cams or t.size != 3 * self.n_cams:
+            raise ValueError("q [M,4], t [M,3] expected")
+        e = np.zeros((max(n, 1), 6))
+        c = C.c_double()
+        L.check(self.lib.lvba_visual_prior_residuals(self._h, q, t, e.ctypes.data, C.byref(c)))
+        return e[:n], c.value
+
     def residual_sq(self, q, t, X):
         """Whitened squared norms s of every observation's reprojection block [O] (caller order) and of every landmark's plane
         block [n_tracks], before any loss; NaN on landmarks without a valid plane and on their observations."""
@@ -125,10 +148,11 @@ loss_struct = L.loss_struct  # (kind, scale) / None -> lvba_loss pointer: shared
 
 
 def optimize_camera_poses(qs, ts, Xs, obs_off, obs_cam, obs_uv, plane_n, plane_d, intr, sigma_px=0.5, sigma_plane=0.01,
-                          device=0, loss_reproj=None, loss_plane=None):
+                          device=0, loss_reproj=None, loss_plane=None, priors=None):
     """The ceres::Problem / ceres::Solve region of LvbaSystem::optimizeCameraPoses (src/lvba_system.cpp:1571-1665).
     A landmark has a valid plane iff its normal is finite and non-zero (has_valid_plane, :1596).  loss_reproj / loss_plane:
-    VisualProblem.set_loss arguments (None: the reference's nullptr at :1630, :1639)."""
+    VisualProblem.set_loss arguments (None: the reference's nullptr at :1630, :1639).  priors: VisualProblem.set_priors
+    argument (None: no camera priors, the reference's problem)."""
     plane_n = np.asarray(plane_n, np.float64).reshape(-1, 3)
     plane_d = np.asarray(plane_d, np.float64).reshape(-1)
     valid = (np.isfinite(plane_n).all(1) & np.isfinite(plane_d) & ~(np.abs(plane_n) <= 1e-6).all(1)).astype(np.uint8)
@@ -137,6 +161,8 @@ def optimize_camera_poses(qs, ts, Xs, obs_off, obs_cam, obs_uv, plane_n, plane_d
     try:
         if loss_reproj is not None or loss_plane is not None:
             prob.set_loss(loss_reproj, loss_plane)
+        if priors:
+            prob.set_priors(priors)
         return prob.refine(qs, ts, Xs) + (valid,)
     finally:
         prob.close()

@@ -441,6 +441,33 @@ int32_t lvba_visual_linearize(lvba_visual_t h, const double *q, const double *t,
  * every rank otherwise. */
 int32_t lvba_visual_set_loss(lvba_visual_t h, const lvba_loss *reproj, const lvba_loss *plane);
 
+/* Camera pose priors (opt-in; none by default).  The refinement then minimises
+ *     cost = 1/2 sum_blocks rho(s)  +  1/2 sum_k |L_k r_k|^2            the priors are never under a loss
+ * The pose a prior sees is the camera's pose in the world, T_k = T_world<-cam_k = (R(q_k)^T, -R(q_k)^T t_k) (q normalised as
+ * everywhere in this stage); with A = T_i O_i, B = T_j O_j the three kinds, the residual order [rotation; position], the
+ * offsets (twelve zeros = identity; p_O of a POSITION prior = lever arm) and the 6 x 6 row-major sqrt_info are exactly those of
+ * lvba_balm_set_priors above -- lvba_prior is reused as it is, i / j are caller camera indices.  An offset O = T_cam<-imu states
+ * a prior on the body pose T_world<-imu directly.  Each prior is one more residual block with a trivial loss on the cameras
+ * (i[, j]): its whitened Jacobian in the visual tangent (EigenQuaternionManifold on the [w,x,y,z] memory, t additive) counts in
+ * the Jacobi scaling, the LM diagonal, the gradient max, the reduced camera system, the model cost change and every cost of the
+ * trace.  Camera 0 stays constant: a prior on it contributes its cost only, a RELATIVE prior with it the other camera's side.
+ *   lvba_visual_set_priors       n = 0 clears.  Before the first cost / linearize / refine / prior_residuals call any pairs may be joined (a
+ *                                relative prior is an edge of the camera graph: ordering, band and solver choice take it in); after
+ *                                it the priors may only be replaced if every relative pair is already a block of the store, else
+ *                                LVBA_ERR_STATE.  LVBA_ERR_ARG for an unknown kind, an index out of [0, n_cams), i == j for
+ *                                RELATIVE, a non-finite value, a measurement / offset rotation that is not orthonormal within
+ *                                1e-6: the handle as it was.  Sharded handles: every rank sets the same priors (the cameras are
+ *                                replicated, rank 0 adds them); each cost / linearize / refine call checks this together with the
+ *                                losses and fails with LVBA_ERR_ARG on every rank otherwise.  At most 2^22 priors.
+ *   lvba_visual_prior_residuals  e [n][6] the whitened residuals L r (POSITION: e[k][0..2], e[k][3..5] = 0), cost = sum 1/2 |e|^2;
+ *                                either may be NULL.  Rank-local on a sharded handle (call it after the first cost / linearize /
+ *                                refine call there).  Like those calls it lays out the store on its first use: relative priors
+ *                                that join new pairs of cameras go in before it as well.
+ * A handle without priors launches no kernel of this part and returns bitwise what it returned before they existed.
+ * lvba_visual_residual_sq is unchanged. */
+int32_t lvba_visual_set_priors(lvba_visual_t h, int32_t n, const lvba_prior *priors);
+int32_t lvba_visual_prior_residuals(lvba_visual_t h, const double *q, const double *t, double *e, double *cost);
+
 /* Whitened squared norms s of the residual blocks at (q, t, X), before any loss: obs_sq [O] per caller observation
  * (O = obs_off[n_tracks] - obs_off[0], caller order), plane_sq [n_tracks] per landmark; NaN for landmarks with valid == 0 and
  * their observations.  Which blocks a loss down-weights: s > a^2.  Rank-local on a sharded handle (its own tracks; call it
