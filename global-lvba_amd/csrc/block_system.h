@@ -120,6 +120,11 @@ int32_t bs_allreduce_hg(BlockSys &bs);
 int32_t bs_clear_reduced(BlockSys &bs);
 // all-reduce `count` elements of a device buffer in place (sum or max; double / int64 / int32 / uint8) over the ranks
 int32_t bs_comm_allreduce(BlockSys &bs, void *dbuf, size_t count, ncclDataType_t dt, ncclRedOp_t op);
+// Do all ranks hold the same v [n] (n <= 8; values whose negation does not overflow)?  One MAX all-reduce of (v, -v): the maxima
+// of v and of -v agree with a rank's own v only when every rank holds the same v, and every rank sees the same maxima, so
+// same[e] is the same on all of them (they fail together: nothing diverges, nothing waits).  Synchronises bs.stream.  Not
+// distributed: every same[e] = true, nothing runs.
+int32_t bs_ranks_agree(BlockSys &bs, const int64_t *v, int n, bool *same);
 // slots of the structurally non-zero blocks of the block-band store (ascending, diagonal included); their download [n][36]
 int32_t bs_pattern_slots(BlockSys &bs, lvba::hvec<int64_t> &slots);
 int32_t bs_download_blocks(BlockSys &bs, const int64_t *slots, int64_t n, double *out);

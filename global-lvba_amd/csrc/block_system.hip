@@ -87,6 +87,24 @@ int32_t bs_comm_allreduce(BlockSys &bs, void *dbuf, size_t count, ncclDataType_t
     return LVBA_OK;
 }
 
+int32_t bs_ranks_agree(BlockSys &bs, const int64_t *v, int n, bool *same)
+{
+    for (int e = 0; e < n; ++e) same[e] = true;
+    if (!bs.distributed()) return LVBA_OK;
+    if (n > 8) return lvba_fail(LVBA_ERR_ARG, "bs_ranks_agree: more than 8 values");
+    int64_t buf[16];
+    for (int e = 0; e < n; ++e) { buf[e] = v[e]; buf[n + e] = -v[e]; }
+    const size_t bytes = 2 * (size_t)n * sizeof(int64_t);
+    DevBuf d(bs.stream);
+    HIPCHK(d.alloc(bytes));
+    HIPCHK(hipMemcpyAsync(d.p, buf, bytes, hipMemcpyHostToDevice, bs.stream));
+    TRY(bs_comm_allreduce(bs, d.p, 2 * (size_t)n, ncclInt64, ncclMax));
+    HIPCHK(hipMemcpyAsync(buf, d.p, bytes, hipMemcpyDeviceToHost, bs.stream));
+    HIPCHK(hipStreamSynchronize(bs.stream));
+    for (int e = 0; e < n; ++e) same[e] = buf[e] == -buf[n + e];
+    return LVBA_OK;
+}
+
 int32_t bs_init(BlockSys &bs, int device)
 {
     bs.device = device;

@@ -7,13 +7,13 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
-#include <map>
 #include <new>
 #include <vector>
 
 #include "host_arena.h"
 #include "block_system.h"
 #include "host_tables.h"
+#include "prior_tables.h"
 
 using namespace lvba;
 
@@ -66,10 +66,7 @@ struct lvba_balm_s {
     // pose priors (lvba_balm_set_priors): as the caller gave them, and bound to the solver order (bind_priors)
     std::vector<lvba_prior> priors;
     bool prior_check = true;            // a sharded handle checks on its next collective call that every rank set the same priors
-    PriorDev pd;
-    std::vector<void *> prior_mem;      // device allocations behind pd
-    int64_t *d_prior_wslot = nullptr;   // blocks that only priors fill: zeroed when the priors are replaced
-    int64_t n_prior_wslot = 0;
+    PriorTables pt;                     // their records and scatter tables on the device (pt.dev.n == 0: none bound)
     lvba::hvec<int64_t> vox_slots;      // blocks the voxel evaluation writes (sorted; bind_priors)
     bool vox_slots_known = false, vox_all_add = false;
     lvba::hvec<int64_t> build_slots;    // blocks of relative priors bound when the store was laid out (sorted)
@@ -306,8 +303,7 @@ extern "C" int32_t lvba_balm_destroy(lvba_balm_t h)
                     h->d_gscal, h->d_vox_order};
     for (void *p : ptrs)
         if (p) lvba::DevicePool::get().free(p);
-    for (void *p : h->prior_mem)
-        if (p) lvba::DevicePool::get().free(p);
+    h->pt.free_mem();
     lvba::PinnedCache::get().release(h->h_pin);
     lvba::PinnedCache::get().release(h->h_gpin);
     lvba::PinnedCache::get().release(h->h_gacc);
@@ -339,7 +335,7 @@ static int32_t bind_priors(lvba_balm_s *h);
 static int32_t finalize(lvba_balm_s *h)
 {
     // priors whose binding failed (out of memory) are bound again on the next call, never silently left out
-    if (h->finalized) return h->pd.n == (int32_t)h->priors.size() ? LVBA_OK : bind_priors(h);
+    if (h->finalized) return h->pt.dev.n == (int32_t)h->priors.size() ? LVBA_OK : bind_priors(h);
     TRY(prior_sync(h)); // (before bs_build: the relative priors shape the store on every rank)
     BlockSys &bs = h->bs;
     HIPCHK(hipSetDevice(bs.device));
@@ -483,7 +479,7 @@ static int32_t enqueue_cost(lvba_balm_s *h, const double *d_poses, double *dst, 
         TRY(bs_allreduce(h->bs, dst, 1));
         ev_end(h, EV_REDUCE);
     }
-    launch_prior_cost(h->pd, d_poses, dst, nullptr, h->stream()); // after the all-reduce: every rank adds them once
+    launch_prior_cost(h->pt.dev, d_poses, dst, nullptr, h->stream()); // after the all-reduce: every rank adds them once
     HIPCHK(hipGetLastError());
     return LVBA_OK;
 }
@@ -505,7 +501,7 @@ static int32_t enqueue_eval(lvba_balm_s *h, const double *d_poses, bool lin_in_p
         TRY(bs_allreduce_hg(bs));
         ev_end(h, EV_REDUCE);
     }
-    launch_prior_eval(h->pd, d_poses, bs.Hblk(), bs.g(), bs.scal(), bs.stream); // after the all-reduce: every rank adds them once
+    launch_prior_eval(h->pt.dev, d_poses, bs.Hblk(), bs.g(), bs.scal(), bs.stream); // after the all-reduce: every rank adds them once
     HIPCHK(hipGetLastError());
     h->have_eval = true;
     return LVBA_OK;
@@ -1087,62 +1083,6 @@ extern "C" int32_t lvba_balm_refine_groups(lvba_balm_t h, double *poses_inout, c
 // ------------------------------------------------------------------------------------------ pose priors
 // The model is in prior_device.h, the passes in priors.hip.  A prior adds its terms to the store after the voxel evaluation (and
 // after its all-reduce: every rank adds them once, to the same reduced buffer, so the ranks stay bitwise equal).
-static bool prior_rot_ok(const double *R)
-{
-    for (int a = 0; a < 9; ++a)
-        if (!isfinite(R[a])) return false;
-    for (int a = 0; a < 3; ++a)
-        for (int b = 0; b < 3; ++b) {
-            const double d = R[a] * R[b] + R[3 + a] * R[3 + b] + R[6 + a] * R[6 + b] - (a == b ? 1.0 : 0.0);
-            if (!(fabs(d) <= 1e-6)) return false;
-        }
-    const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
-    return det > 0.0;
-}
-static bool prior_is_zero(const double *o)
-{
-    for (int a = 0; a < 12; ++a)
-        if (o[a] != 0.0) return false;
-    return true;
-}
-static void prior_offset(const double *o, double *out) // twelve zeros: the identity
-{
-    static const double I[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
-    memcpy(out, prior_is_zero(o) ? I : o, 12 * sizeof(double));
-}
-static int32_t prior_check_one(const lvba_prior &q, int32_t N, int32_t k)
-{
-    if (q.kind < LVBA_PRIOR_POSE || q.kind > LVBA_PRIOR_RELATIVE) return fail(LVBA_ERR_ARG, "prior %d: unknown kind %d", k, q.kind);
-    const bool rel = q.kind == LVBA_PRIOR_RELATIVE;
-    if (q.i < 0 || q.i >= N || (rel && (q.j < 0 || q.j >= N))) return fail(LVBA_ERR_ARG, "prior %d: pose index out of range [0,%d)", k, N);
-    if (rel && q.i == q.j) return fail(LVBA_ERR_ARG, "prior %d: a relative prior needs two different poses", k);
-    const int m = q.kind == LVBA_PRIOR_POSITION ? 3 : 6;
-    for (int a = 0; a < m; ++a)
-        for (int b = 0; b < m; ++b)
-            if (!isfinite(q.sqrt_info[6 * a + b])) return fail(LVBA_ERR_ARG, "prior %d: non-finite sqrt_info", k);
-    for (int a = q.kind == LVBA_PRIOR_POSITION ? 9 : 0; a < 12; ++a)
-        if (!isfinite(q.meas[a])) return fail(LVBA_ERR_ARG, "prior %d: non-finite measurement", k);
-    if (q.kind != LVBA_PRIOR_POSITION && !prior_rot_ok(q.meas)) return fail(LVBA_ERR_ARG, "prior %d: the measured rotation is not orthonormal", k);
-    for (int s = 0; s < (rel ? 2 : 1); ++s) {
-        const double *o = s ? q.offset_j : q.offset_i;
-        if (prior_is_zero(o)) continue;
-        for (int a = 9; a < 12; ++a)
-            if (!isfinite(o[a])) return fail(LVBA_ERR_ARG, "prior %d: non-finite offset", k);
-        if (!prior_rot_ok(o)) return fail(LVBA_ERR_ARG, "prior %d: an offset rotation is not orthonormal", k);
-    }
-    return LVBA_OK;
-}
-
-namespace lvba { // (window_ba.hip: priors on frames mapped onto the anchors of the global stages)
-int32_t prior_validate(int32_t n, const lvba_prior *priors, int32_t n_poses)
-{
-    if (n < 0 || (n > 0 && !priors)) return fail(LVBA_ERR_ARG, "n must be >= 0 and priors non-NULL");
-    for (int32_t k = 0; k < n; ++k) TRY(prior_check_one(priors[k], n_poses, k));
-    return LVBA_OK;
-}
-void prior_offset_or_identity(const double *o, double *out) { prior_offset(o, out); }
-} // namespace lvba
-
 // the blocks the voxel evaluation writes (diagonal included): a prior adds to those and writes the others, which hold nothing else
 static int32_t prior_vox_slots(lvba_balm_s *h)
 {
@@ -1158,122 +1098,30 @@ static int32_t prior_vox_slots(lvba_balm_s *h)
     return LVBA_OK;
 }
 
-template <typename T>
-static int32_t prior_upload(lvba_balm_s *h, T **p, size_t n, const T *src)
-{
-    TRY(bs_dmalloc(h->bs, p, (int64_t)n));
-    h->prior_mem.push_back(*p);
-    if (src && n) HIPCHK(lvba::copy_h2d(*p, src, n * sizeof(T)));
-    return LVBA_OK;
-}
-
 // h->priors -> the solver order, the scatter tables and their device copies (the handle is finalised)
 static int32_t bind_priors(lvba_balm_s *h)
 {
     BlockSys &bs = h->bs;
-    HIPCHK(hipSetDevice(bs.device));
-    launch_prior_zero_slots(bs.Hblk(), h->d_prior_wslot, h->n_prior_wslot, bs.stream); // what only the old priors filled
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(bs.stream));
-    for (void *p : h->prior_mem) lvba::DevicePool::get().free(p);
-    h->prior_mem.clear();
-    h->pd = PriorDev{};
-    h->d_prior_wslot = nullptr;
-    h->n_prior_wslot = 0;
+    TRY(h->pt.release(bs));
     bs.extra_slots.clear();
-    const int32_t n = (int32_t)h->priors.size();
-    if (n == 0) return LVBA_OK;
+    if (h->priors.empty()) return LVBA_OK;
     TRY(prior_vox_slots(h));
-    const int64_t Bb1 = (int64_t)bs.Bb + 1;
-    std::vector<PriorRec> rec((size_t)n);
-    std::map<int64_t, std::vector<int32_t>> hb; // slot -> contributions, ascending prior index
-    std::map<int32_t, std::vector<int32_t>> gb; // solver pose -> contributions
-    for (int32_t k = 0; k < n; ++k) {
-        const lvba_prior &q = h->priors[(size_t)k];
-        PriorRec &r = rec[(size_t)k];
-        const bool rel = q.kind == LVBA_PRIOR_RELATIVE;
-        r.kind = q.kind;
-        r.I = bs.iperm[(size_t)q.i];
-        r.J = rel ? bs.iperm[(size_t)q.j] : r.I;
-        r.flip = r.I < r.J ? 1 : 0;
-        memcpy(r.meas, q.meas, sizeof r.meas);
-        prior_offset(q.offset_i, r.oi);
-        prior_offset(q.offset_j, r.oj);
-        memcpy(r.L, q.sqrt_info, sizeof r.L);
-        hb[(int64_t)r.I * Bb1].push_back(k << 2);
-        gb[r.I].push_back(k << 2);
-        if (rel) {
-            hb[(int64_t)r.J * Bb1].push_back(k << 2 | 1);
-            gb[r.J].push_back(k << 2 | 1);
-            const int32_t lo = std::min(r.I, r.J), hi = std::max(r.I, r.J);
-            hb[(int64_t)lo * Bb1 + (hi - lo)].push_back(k << 2 | 2);
-        }
-    }
-    lvba::hvec<int64_t> hslot, wslot;
-    lvba::hvec<int32_t> hmode, hoff(1, 0), hsrc, gpose, goff(1, 0), gsrc;
-    for (const auto &t : hb) {
-        const bool diag = t.first % Bb1 == 0;
-        const bool add = diag || h->vox_all_add || std::binary_search(h->vox_slots.begin(), h->vox_slots.end(), t.first);
-        hslot.push_back(t.first);
-        hmode.push_back((add ? 0 : 1) | (diag ? 2 : 0));
-        if (!add) wslot.push_back(t.first);
-        if (!diag) bs.extra_slots.push_back(t.first);
-        hsrc.insert(hsrc.end(), t.second.begin(), t.second.end());
-        hoff.push_back((int32_t)hsrc.size());
-    }
-    for (const auto &t : gb) {
-        gpose.push_back(t.first);
-        gsrc.insert(gsrc.end(), t.second.begin(), t.second.end());
-        goff.push_back((int32_t)gsrc.size());
-    }
-    PriorRec *d_rec = nullptr;
-    double *d_lin = nullptr;
-    int64_t *d_hslot = nullptr;
-    int32_t *d_hmode = nullptr, *d_hoff = nullptr, *d_hsrc = nullptr, *d_gpose = nullptr, *d_goff = nullptr, *d_gsrc = nullptr;
-    TRY(prior_upload(h, &d_rec, rec.size(), rec.data()));
-    TRY(prior_upload<double>(h, &d_lin, 128 * (size_t)n, nullptr));
-    double *d_part = nullptr;
-    unsigned *d_ticket = nullptr;
-    TRY(prior_upload<double>(h, &d_part, (size_t)(n + 63) / 64, nullptr));
-    const unsigned zero = 0;
-    TRY(prior_upload(h, &d_ticket, 1, &zero));
-    TRY(prior_upload(h, &d_hslot, hslot.size(), hslot.data()));
-    TRY(prior_upload(h, &d_hmode, hmode.size(), hmode.data()));
-    TRY(prior_upload(h, &d_hoff, hoff.size(), hoff.data()));
-    TRY(prior_upload(h, &d_hsrc, hsrc.size(), hsrc.data()));
-    TRY(prior_upload(h, &d_gpose, gpose.size(), gpose.data()));
-    TRY(prior_upload(h, &d_goff, goff.size(), goff.data()));
-    TRY(prior_upload(h, &d_gsrc, gsrc.size(), gsrc.data()));
-    if (!wslot.empty()) TRY(prior_upload(h, &h->d_prior_wslot, wslot.size(), wslot.data()));
-    h->n_prior_wslot = (int64_t)wslot.size();
-    PriorDev &d = h->pd;
-    d.pr = d_rec; d.lin = d_lin; d.part = d_part; d.ticket = d_ticket;
-    d.n_hblk = (int64_t)hslot.size(); d.hslot = d_hslot; d.hmode = d_hmode; d.hoff = d_hoff; d.hsrc = d_hsrc;
-    d.n_g = (int32_t)gpose.size(); d.gpose = d_gpose; d.goff = d_goff; d.gsrc = d_gsrc;
-    d.n = n; // (last: a failed upload above leaves a handle without priors)
-    return LVBA_OK;
+    return h->pt.bind(bs, h->priors, h->vox_slots, h->vox_all_add, 1, &bs.extra_slots);
 }
 
 // Sharded handles: the first collective call after lvba_balm_set_priors (or the set-up) checks with one MAX all-reduce of
-// (count, hash, -count, -hash) that every rank holds the same priors.
+// (count, hash) and their negations that every rank holds the same priors (reserved fields are stored as zero).
 static int32_t prior_sync(lvba_balm_s *h)
 {
     if (!h->prior_check) return LVBA_OK;
     BlockSys &bs = h->bs;
-    if (!bs.distributed()) { h->prior_check = false; return LVBA_OK; }
-    uint64_t hs = 1469598103934665603ull; // FNV-1a over the priors' bytes (reserved fields are stored as zero)
-    const unsigned char *b = reinterpret_cast<const unsigned char *>(h->priors.data());
-    for (size_t a = 0; a < h->priors.size() * sizeof(lvba_prior); ++a) { hs ^= b[a]; hs *= 1099511628211ull; }
-    const int64_t n = (int64_t)h->priors.size(), v = (int64_t)(hs >> 2);
-    int64_t buf[4] = {n, v, -n, -v};
-    HIPCHK(hipSetDevice(bs.device));
-    DevBuf d(bs.stream);
-    HIPCHK(d.alloc(sizeof buf));
-    HIPCHK(hipMemcpyAsync(d.as<int64_t>(), buf, sizeof buf, hipMemcpyHostToDevice, bs.stream));
-    TRY(bs_comm_allreduce(bs, d.as<int64_t>(), 4, ncclInt64, ncclMax));
-    HIPCHK(hipMemcpyAsync(buf, d.as<int64_t>(), sizeof buf, hipMemcpyDeviceToHost, bs.stream));
-    HIPCHK(hipStreamSynchronize(bs.stream));
-    if (buf[0] != -buf[2] || buf[1] != -buf[3]) return fail(LVBA_ERR_ARG, "the ranks of this job set different pose priors");
+    if (bs.distributed()) {
+        const int64_t v[2] = {(int64_t)h->priors.size(), prior_hash(h->priors)};
+        bool same[2];
+        HIPCHK(hipSetDevice(bs.device));
+        TRY(bs_ranks_agree(bs, v, 2, same));
+        if (!same[0] || !same[1]) return fail(LVBA_ERR_ARG, "the ranks of this job set different pose priors");
+    }
     h->prior_check = false;
     return LVBA_OK;
 }
@@ -1282,40 +1130,19 @@ extern "C" int32_t lvba_balm_set_priors(lvba_balm_t h, int32_t n, const lvba_pri
 {
     if (!h) return fail(LVBA_ERR_ARG, "handle is NULL");
     if (n < 0 || (n > 0 && !priors)) return fail(LVBA_ERR_ARG, "n must be >= 0 and priors non-NULL");
-    if (n > (1 << 22)) return fail(LVBA_ERR_ARG, "more than 2^22 priors");
+    TRY(prior_cap(n));
     if (n > 0 && h->n_groups > 0) return fail(LVBA_ERR_STATE, "a grouped handle (lvba_balm_set_groups) takes no pose priors");
     if (h->lm_active) return fail(LVBA_ERR_STATE, "set_priors between lvba_balm_lm_begin and lvba_balm_lm_end");
-    for (int32_t k = 0; k < n; ++k) TRY(prior_check_one(priors[k], h->N, k));
+    TRY(prior_validate(n, priors, h->N));
     BlockSys &bs = h->bs;
     if (h->finalized) { // the store is laid out: every relative pair must be one of its blocks
-        for (int32_t k = 0; k < n; ++k) {
-            if (priors[k].kind != LVBA_PRIOR_RELATIVE) continue;
-            const int32_t I = bs.iperm[(size_t)priors[k].i], J = bs.iperm[(size_t)priors[k].j];
-            const int32_t lo = std::min(I, J), hi = std::max(I, J);
-            bool ok = hi - lo <= bs.Bb;
-            if (ok && bs.nd.active) { // a dissected system couples only the pairs its plan was made from
-                TRY(prior_vox_slots(h));
-                const int64_t slot = (int64_t)lo * (bs.Bb + 1) + (hi - lo);
-                ok = std::binary_search(h->vox_slots.begin(), h->vox_slots.end(), slot) ||
-                     std::binary_search(h->build_slots.begin(), h->build_slots.end(), slot);
-            }
-            if (!ok) return fail(LVBA_ERR_STATE, "prior %d joins poses %d and %d, which are no block of the store laid out at the first "
-                                 "cost / eval / refine call: set such priors before it", k, priors[k].i, priors[k].j);
-        }
+        const bool nd = bs.nd.active; // a dissected system couples only the pairs its plan was made from
+        if (nd && n > 0) TRY(prior_vox_slots(h));
+        TRY(prior_pairs_in_store(bs, n, priors, nd ? &h->vox_slots : nullptr, nd ? &h->build_slots : nullptr, "poses", "eval"));
     }
-    h->priors.assign(priors, priors + n);
-    for (lvba_prior &q : h->priors) {
-        q.reserved = 0;
-        if (q.kind != LVBA_PRIOR_RELATIVE) { q.j = 0; memset(q.offset_j, 0, sizeof q.offset_j); }
-    }
+    prior_store(bs, h->finalized, n, priors, h->priors);
     h->prior_check = true;
-    if (!h->finalized) {
-        bs.edge_i.clear(); bs.edge_j.clear();
-        for (const lvba_prior &q : h->priors)
-            if (q.kind == LVBA_PRIOR_RELATIVE) { bs.edge_i.push_back(q.i); bs.edge_j.push_back(q.j); }
-        return LVBA_OK;
-    }
-    return bind_priors(h);
+    return h->finalized ? bind_priors(h) : LVBA_OK;
 }
 
 extern "C" int32_t lvba_balm_prior_residuals(lvba_balm_t h, const double *poses, double *e, double *cost)
@@ -1324,14 +1151,14 @@ extern "C" int32_t lvba_balm_prior_residuals(lvba_balm_t h, const double *poses,
     TRY(finalize(h));
     BlockSys &bs = h->bs;
     HIPCHK(hipSetDevice(bs.device));
-    const int64_t n = h->pd.n;
+    const int64_t n = h->pt.dev.n;
     if (n == 0) { if (cost) *cost = 0.0; return LVBA_OK; }
     TRY(upload_poses(h, poses, h->d_pose_trial));
     DevBuf d(bs.stream);
     HIPCHK(d.alloc((size_t)(6 * n + 1) * sizeof(double)));
     double *de = d.as<double>();
     HIPCHK(hipMemsetAsync(de + 6 * n, 0, sizeof(double), bs.stream));
-    launch_prior_cost(h->pd, h->d_pose_trial, de + 6 * n, de, bs.stream);
+    launch_prior_cost(h->pt.dev, h->d_pose_trial, de + 6 * n, de, bs.stream);
     HIPCHK(hipGetLastError());
     double c = 0.0;
     if (e) HIPCHK(hipMemcpyAsync(e, de, (size_t)(6 * n) * sizeof(double), hipMemcpyDeviceToHost, bs.stream));
@@ -1368,24 +1195,19 @@ extern "C" int32_t lvba_balm_set_loss(lvba_balm_t h, const lvba_loss *loss)
     return LVBA_OK;
 }
 
-// Sharded handles: like prior_sync, one MAX all-reduce of (kind, scale bits, -kind, -scale bits)
+// Sharded handles: like prior_sync, one MAX all-reduce of (kind, scale bits) and their negations
 static int32_t loss_sync(lvba_balm_s *h)
 {
     if (!h->loss_check) return LVBA_OK;
     BlockSys &bs = h->bs;
-    if (!bs.distributed()) { h->loss_check = false; return LVBA_OK; }
-    int64_t bits = 0;
-    memcpy(&bits, &h->loss.scale, sizeof bits); // (a valid scale is >= 0: the sign bit is clear)
-    const int64_t k = h->loss.kind;
-    int64_t buf[4] = {k, bits, -k, -bits};
-    HIPCHK(hipSetDevice(bs.device));
-    DevBuf d(bs.stream);
-    HIPCHK(d.alloc(sizeof buf));
-    HIPCHK(hipMemcpyAsync(d.as<int64_t>(), buf, sizeof buf, hipMemcpyHostToDevice, bs.stream));
-    TRY(bs_comm_allreduce(bs, d.as<int64_t>(), 4, ncclInt64, ncclMax));
-    HIPCHK(hipMemcpyAsync(buf, d.as<int64_t>(), sizeof buf, hipMemcpyDeviceToHost, bs.stream));
-    HIPCHK(hipStreamSynchronize(bs.stream));
-    if (buf[0] != -buf[2] || buf[1] != -buf[3]) return fail(LVBA_ERR_ARG, "the ranks of this job set different losses (lvba_balm_set_loss)");
+    if (bs.distributed()) {
+        int64_t v[2] = {h->loss.kind, 0};
+        memcpy(&v[1], &h->loss.scale, sizeof v[1]); // (a valid scale is >= 0: the sign bit is clear)
+        bool same[2];
+        HIPCHK(hipSetDevice(bs.device));
+        TRY(bs_ranks_agree(bs, v, 2, same));
+        if (!same[0] || !same[1]) return fail(LVBA_ERR_ARG, "the ranks of this job set different losses (lvba_balm_set_loss)");
+    }
     h->loss_check = false;
     return LVBA_OK;
 }

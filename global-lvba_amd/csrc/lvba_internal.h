@@ -5,6 +5,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
+#include "../../include/lvba_hip.h"
 
 #define LVBA_CF 256   // max factors per chunk == workgroup size of the BALM kernels
 #define LVBA_CV 128   // max voxels per chunk (every voxel has >= 2 factors)
@@ -225,6 +226,12 @@ void launch_export_dense(const double *Hblk, int band_blocks, int n_poses, const
 void launch_export_vec(const double *v, const int *perm, int n_poses, double *out, hipStream_t s);
 void launch_import_poses(const double *in, const int *perm, int n_poses, double *out, hipStream_t s);
 void launch_export_poses(const double *in, const int *perm, int n_poses, double *out, hipStream_t s);
+
+// prior_tables.hip: the argument checks of lvba_*_set_priors (n_poses: poses or cameras); an offset of twelve zeros is the identity
+int32_t prior_validate(int32_t n, const lvba_prior *priors, int32_t n_poses);
+void prior_offset_or_identity(const double *o, double *out);
+// lvba_api.hip: NULL and TRIVIAL pass; `what` names the argument in the message
+int32_t loss_validate(const lvba_loss *loss, const char *what);
 
 // priors.hip: nothing is launched when d.n == 0
 void launch_prior_eval(const PriorDev &d, const double *poses, double *Hblk, double *g, double *scal, hipStream_t s); // scal[0] += cost

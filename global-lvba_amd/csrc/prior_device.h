@@ -7,6 +7,8 @@
 //     RELATIVE  r = [Log(Rm^T R_A^T R_B); R_A^T (p_B - p_A) - pm]          (6 rows)
 //   and adds 1/2 |L r|^2 to the cost.  prior_raw gives r and the Jacobian blocks dr/dd_i, dr/dd_j (row-major 6 x 6; POSITION:
 //   rows 3..5 zero); prior_whiten / prior_whiten_jac apply L.
+//   Shared with the visual stage's priors (visual_prior_device.h, visual_priors.hip): the model above, the products of a whitened
+//   block that a lin record keeps (prior_products, prior_cross) and, device only, the fixed-order grid sum (prior_grid_sum).
 #pragma once
 #include <math.h>
 
@@ -275,5 +277,95 @@ LVBA_PRIOR_UNROLL
             W[6 * a + c] = v;
         }
 }
+
+// The products of a whitened block W (row-major 6 x 6) that a lin record keeps (PL_* in lvba_internal.h):
+// o[g0 + c] = (W^T e)(c), o[h0 + 6 c + r] = (W^T W)(r, c).  Every element is its own sum over a = 0..5, from 0.0.
+LVBA_HD void prior_products(const double *W, const double *e, double *o, int g0, int h0)
+{
+LVBA_PRIOR_UNROLL
+    for (int c = 0; c < 6; ++c) {
+        double s = 0.0;
+LVBA_PRIOR_UNROLL
+        for (int a = 0; a < 6; ++a) s += W[6 * a + c] * e[a];
+        o[g0 + c] = s;
+    }
+LVBA_PRIOR_UNROLL
+    for (int c = 0; c < 6; ++c)
+LVBA_PRIOR_UNROLL
+        for (int r = 0; r < 6; ++r) {
+            double s = 0.0;
+LVBA_PRIOR_UNROLL
+            for (int a = 0; a < 6; ++a) s += W[6 * a + r] * W[6 * a + c];
+            o[h0 + 6 * c + r] = s;
+        }
+}
+
+// The cross block (W_i^T W_j)(r, c) of a RELATIVE prior, block (i, j), into o[x0 ..].  The store keeps (max, min) in solver order;
+// flip: j comes after i, the block kept is (j, i), the transpose.
+LVBA_HD void prior_cross(const double *Wi, const double *Wj, bool flip, double *o, int x0)
+{
+LVBA_PRIOR_UNROLL
+    for (int c = 0; c < 6; ++c)
+LVBA_PRIOR_UNROLL
+        for (int r = 0; r < 6; ++r) {
+            double x = 0.0;
+LVBA_PRIOR_UNROLL
+            for (int a = 0; a < 6; ++a) x += Wi[6 * a + r] * Wj[6 * a + c];
+            o[x0 + (flip ? 6 * r + c : 6 * c + r)] = x;
+        }
+}
+
+#if defined(__HIPCC__)
+// Fixed-order sums of NV values per lane over the whole grid (64-lane workgroups, part [gridDim.x][NV]): a tree over the lanes of
+// each workgroup, then the workgroup that finishes last (a ticket counter, the only atomic) sums the workgroups' shares in index
+// order, writes (or, add, adds) the totals to out[i][0] (an out[i] may be NULL) and resets the ticket for the next launch on the
+// stream.  The bytes do not change run to run.
+template <int NV>
+__device__ void prior_grid_sum(const double (&v)[NV], double *__restrict__ part, unsigned *__restrict__ ticket, double *const (&out)[NV],
+                               bool add)
+{
+    __shared__ double red[NV][64];
+    __shared__ int last;
+    auto tree = [&]() {
+        __syncthreads();
+        for (int w = 32; w > 0; w >>= 1) {
+            if ((int)threadIdx.x < w) {
+#pragma unroll
+                for (int i = 0; i < NV; ++i) red[i][threadIdx.x] += red[i][threadIdx.x + w];
+            }
+            __syncthreads();
+        }
+    };
+#pragma unroll
+    for (int i = 0; i < NV; ++i) red[i][threadIdx.x] = v[i];
+    tree();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) part[NV * blockIdx.x + i] = red[i][0];
+        __threadfence();
+        last = atomicAdd(ticket, 1u) == gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!last) return;
+    __threadfence();
+    double s[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) s[i] = 0.0;
+    for (unsigned b = threadIdx.x; b < gridDim.x; b += 64) {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) s[i] += __builtin_nontemporal_load(part + NV * b + i);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < NV; ++i) red[i][threadIdx.x] = s[i];
+    tree();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int i = 0; i < NV; ++i)
+            if (out[i]) out[i][0] = add ? out[i][0] + red[i][0] : red[i][0];
+        *ticket = 0u;
+    }
+}
+#endif
 
 } // namespace lvba

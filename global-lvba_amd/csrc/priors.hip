@@ -5,8 +5,7 @@
 //   prior_scatter_kernel  every target element of the block store and of g sums its contributions in the fixed order of a CSR table
 //                         built on the host.  No atomics on data: the bytes do not change run to run.
 //   prior_cost_kernel     the cost alone (the LM's trial point), one lane per prior, summed like the evaluation's
-// Both sums run in a fixed order: a tree over the 64 lanes of each workgroup, then the workgroup that finishes last (a ticket
-// counter, the only atomic) sums the workgroups' shares in index order.
+// Both sums run in the fixed order of prior_grid_sum (prior_device.h).
 // An evaluation is 2 launches, a trial cost 1; a handle without priors launches none of them.
 #include <hip/hip_runtime.h>
 
@@ -18,41 +17,6 @@ namespace lvba {
 #define PRIOR_WG 256
 
 // (the lin record of prior k: PL_* in lvba_internal.h)
-
-// Fixed-order sum of one value per lane over the whole grid (64-lane workgroups); the last workgroup to finish adds the total to
-// out[0] and resets the ticket for the next launch on the stream.
-__device__ void prior_grid_sum(double v, double *__restrict__ part, unsigned *__restrict__ ticket, double *__restrict__ out)
-{
-    __shared__ double red[64];
-    __shared__ int last;
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int w = 32; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        part[blockIdx.x] = red[0];
-        __threadfence();
-        last = atomicAdd(ticket, 1u) == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!last) return;
-    __threadfence();
-    double s = 0.0;
-    for (unsigned b = threadIdx.x; b < gridDim.x; b += 64) s += __builtin_nontemporal_load(part + b);
-    __syncthreads();
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 32; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        if (out) out[0] += red[0];
-        *ticket = 0u;
-    }
-}
 
 // (kind is a constant at each call site: every array stays in registers)
 __device__ __forceinline__ double prior_lin_one(const int kind, const PriorRec &p, const double *__restrict__ poses, double *__restrict__ o)
@@ -67,42 +31,11 @@ __device__ __forceinline__ double prior_lin_one(const int kind, const PriorRec &
     prior_raw(kind, p.meas, Ti, p.oi, Tj, p.oj, r, true, Ji, Jj);
     const double cost = prior_whiten(kind, p.L, r, e);
     prior_whiten_jac(kind, p.L, Ji, Wi);
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {
-        double s = 0.0;
-#pragma unroll
-        for (int a = 0; a < 6; ++a) s += Wi[6 * a + c] * e[a];
-        o[PL_GI + c] = s;
-    }
-#pragma unroll
-    for (int c = 0; c < 6; ++c)
-#pragma unroll
-        for (int rr = 0; rr < 6; ++rr) {
-            double s = 0.0;
-#pragma unroll
-            for (int a = 0; a < 6; ++a) s += Wi[6 * a + rr] * Wi[6 * a + c];
-            o[PL_HII + 6 * c + rr] = s;
-        }
+    prior_products(Wi, e, o, PL_GI, PL_HII);
     if (kind != PRIOR_RELATIVE) return cost;
     prior_whiten_jac(kind, p.L, Jj, Wj);
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {
-        double s = 0.0;
-#pragma unroll
-        for (int a = 0; a < 6; ++a) s += Wj[6 * a + c] * e[a];
-        o[PL_GJ + c] = s;
-    }
-#pragma unroll
-    for (int c = 0; c < 6; ++c)
-#pragma unroll
-        for (int rr = 0; rr < 6; ++rr) {
-            double s = 0.0, x = 0.0;
-#pragma unroll
-            for (int a = 0; a < 6; ++a) { s += Wj[6 * a + rr] * Wj[6 * a + c]; x += Wi[6 * a + rr] * Wj[6 * a + c]; }
-            o[PL_HJJ + 6 * c + rr] = s;
-            // x = (J_i^T J_j)(rr, c): block (i, j).  The store keeps (max, min) in solver order; flip: j comes after i, block (j, i)
-            o[PL_HX + (p.flip ? 6 * rr + c : 6 * c + rr)] = x;
-        }
+    prior_products(Wj, e, o, PL_GJ, PL_HJJ);
+    prior_cross(Wi, Wj, p.flip, o, PL_HX);
     return cost;
 }
 
@@ -119,7 +52,7 @@ __global__ __launch_bounds__(64) void prior_lin_kernel(const PriorRec *__restric
         else if (p.kind == PRIOR_POSITION) c = prior_lin_one(PRIOR_POSITION, p, poses, o);
         else c = prior_lin_one(PRIOR_RELATIVE, p, poses, o);
     }
-    prior_grid_sum(c, part, ticket, scal);
+    prior_grid_sum<1>({c}, part, ticket, {scal}, true);
 }
 
 __global__ __launch_bounds__(64) void prior_cost_kernel(const PriorRec *__restrict__ pr, int32_t n, const double *__restrict__ poses,
@@ -144,7 +77,7 @@ LVBA_PRIOR_UNROLL
             for (int a = 0; a < 6; ++a) e_out[6 * (int64_t)k + a] = e[a];
         }
     }
-    prior_grid_sum(c, part, ticket, out);
+    prior_grid_sum<1>({c}, part, ticket, {out}, true);
 }
 
 __global__ __launch_bounds__(PRIOR_WG) void prior_scatter_kernel(PriorDev d, double *__restrict__ Hblk, double *__restrict__ g)

@@ -17,20 +17,15 @@
 #include <string.h>
 #include <algorithm>
 #include <chrono>
-#include <map>
 #include <new>
 #include <vector>
 
 #include "host_arena.h"
 #include "block_system.h"
+#include "prior_tables.h"
 
 using namespace lvba;
 #define fail lvba_fail
-
-namespace lvba { // lvba_api.hip: the argument checks of lvba_balm_set_priors
-int32_t prior_validate(int32_t n, const lvba_prior *priors, int32_t n_poses);
-void prior_offset_or_identity(const double *o, double *out);
-} // namespace lvba
 
 struct lvba_visual_s {
     BlockSys bs;
@@ -47,10 +42,8 @@ struct lvba_visual_s {
     double intr[8] = {}, sig_px = 0.5, sig_pl = 0.01;
     // camera pose priors (lvba_visual_set_priors): as the caller gave them, and bound to the solver order (bind_priors)
     std::vector<lvba_prior> priors;
-    VisPriorDev vp;
-    std::vector<void *> prior_mem;      // device allocations behind vp.tab
-    int64_t *d_prior_wslot = nullptr;   // blocks that only priors fill: zeroed when the priors are replaced
-    int64_t n_prior_wslot = 0;
+    PriorTables pt;                     // their records and scatter tables on the device
+    VisPriorDev vp;                     // what the kernels take: tab = pt.dev
     lvba::hvec<int64_t> pat_slots;      // blocks the pair pass writes or the packed all-reduce carries (sorted; bind_priors)
     bool pat_known = false;
     double *d_pscal = nullptr;          // [2] the priors' trial cost and model cost change of one LM iteration
@@ -106,7 +99,7 @@ extern "C" int32_t lvba_visual_destroy(lvba_visual_t h)
                     h->d_t2, h->d_X2, h->d_blkpart, h->d_scal, h->d_gmax, h->d_out, h->d_camsum, h->d_colsum, h->d_pscal};
     for (void *p : ptrs)
         if (p) lvba::DevicePool::get().free(p);
-    for (void *p : h->prior_mem) lvba::DevicePool::get().free(p);
+    h->pt.free_mem();
     if (h->h_pin) hipHostFree(h->h_pin);
     if (h->h_stage) hipHostFree(h->h_stage);
     bs_destroy(h->bs);
@@ -290,37 +283,26 @@ static int32_t allreduce_scalars(lvba_visual_s *h, int first, int count)
     return bs_allreduce(h->bs, h->d_scal + first, (size_t)count);
 }
 
-// Sharded handles: every rank must use the same losses.  One MAX all-reduce of (kinds, scale bits) and their negations: the
-// maxima of v and of -v agree with every rank's own v only when all ranks hold the same v, and every rank sees the same maxima,
-// so all of them fail together (nothing diverges, nothing waits).  Run at every sharded cost / linearize / refine call: the call
-// is collective anyway, and a check only "after a change" would leave a rank that changed nothing out of the all-reduce.
+// Sharded handles: every rank must use the same losses and the same camera priors: one MAX all-reduce (bs_ranks_agree) of the
+// kinds, the scale bits, the priors' count and the hash of their records (reserved fields are stored as zero).  Run at every
+// sharded cost / linearize / refine call: the call is collective anyway, and a check only "after a change" would leave a rank
+// that changed nothing out of the all-reduce.
 static int32_t check_loss_agreement(lvba_visual_s *h)
 {
     BlockSys &bs = h->bs;
     if (!bs.distributed()) return LVBA_OK;
-    int64_t v[12];
+    int64_t v[6];
     for (int f = 0; f < 2; ++f) {
-        int64_t bits;
-        memcpy(&bits, &h->loss_scale[f], sizeof bits); // scale >= 0: bits < 2^63, their negation does not overflow
-        v[f] = h->loss_kind[f]; v[2 + f] = bits;
+        v[f] = h->loss_kind[f];
+        memcpy(&v[2 + f], &h->loss_scale[f], sizeof v[0]); // scale >= 0: bits < 2^63, their negation does not overflow
     }
-    // the camera priors: their count and an FNV-1a hash of the records (reserved fields are stored as zero)
-    uint64_t hs = 1469598103934665603ull;
-    const unsigned char *b = reinterpret_cast<const unsigned char *>(h->priors.data());
-    for (size_t a = 0; a < h->priors.size() * sizeof(lvba_prior); ++a) { hs ^= b[a]; hs *= 1099511628211ull; }
-    v[4] = (int64_t)h->priors.size(); v[5] = (int64_t)(hs >> 2);
-    for (int e = 0; e < 6; ++e) v[6 + e] = -v[e];
-    DevBuf buf(bs.stream);
-    HIPCHK(buf.alloc(sizeof v));
-    HIPCHK(hipMemcpyAsync(buf.p, v, sizeof v, hipMemcpyHostToDevice, bs.stream));
-    TRY(bs_comm_allreduce(bs, buf.p, 12, ncclInt64, ncclMax));
-    int64_t m[12];
-    HIPCHK(hipMemcpyAsync(m, buf.p, sizeof m, hipMemcpyDeviceToHost, bs.stream));
-    HIPCHK(hipStreamSynchronize(bs.stream));
+    v[4] = (int64_t)h->priors.size(); v[5] = prior_hash(h->priors);
+    bool same[6];
+    TRY(bs_ranks_agree(bs, v, 6, same));
     for (int e = 0; e < 4; ++e)
-        if (m[e] != -m[6 + e]) return fail(LVBA_ERR_ARG, "the ranks of a sharded visual handle set different losses");
+        if (!same[e]) return fail(LVBA_ERR_ARG, "the ranks of a sharded visual handle set different losses");
     for (int e = 4; e < 6; ++e)
-        if (m[e] != -m[6 + e]) return fail(LVBA_ERR_ARG, "the ranks of a sharded visual handle set different camera priors");
+        if (!same[e]) return fail(LVBA_ERR_ARG, "the ranks of a sharded visual handle set different camera priors");
     return LVBA_OK;
 }
 
@@ -346,15 +328,6 @@ extern "C" int32_t lvba_visual_set_loss(lvba_visual_t h, const lvba_loss *reproj
 }
 
 // ------------------------------------------------------------------------------------------ camera pose priors
-template <typename T>
-static int32_t prior_upload(lvba_visual_s *h, T **p, size_t n, const T *src)
-{
-    TRY(bs_dmalloc(h->bs, p, (int64_t)n));
-    h->prior_mem.push_back(*p);
-    if (src && n) HIPCHK(lvba::copy_h2d(*p, src, n * sizeof(T)));
-    return LVBA_OK;
-}
-
 // The blocks that hold something besides priors: what the pair pass writes on one rank (a prior adds to those and writes the
 // others); on a sharded handle the whole store is cleared before every linearisation, so every block is added to -- there the
 // list is the union pattern the packed all-reduce carries (empty: the whole store travels).
@@ -367,124 +340,37 @@ static int32_t prior_pattern(lvba_visual_s *h)
     return LVBA_OK;
 }
 
-// h->priors -> the solver order, the scatter tables (those of the LiDAR stage, priors.hip) and their device copies
+// h->priors -> the solver order, the scatter tables (those of the LiDAR stage, prior_tables.h) and their device copies
 static int32_t bind_priors(lvba_visual_s *h)
 {
     BlockSys &bs = h->bs;
-    HIPCHK(hipSetDevice(bs.device));
-    launch_prior_zero_slots(bs.Hblk(), h->d_prior_wslot, h->n_prior_wslot, bs.stream); // what only the old priors filled
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(bs.stream));
-    for (void *p : h->prior_mem) lvba::DevicePool::get().free(p);
-    h->prior_mem.clear();
+    TRY(h->pt.release(bs));
     h->vp = VisPriorDev{};
-    h->d_prior_wslot = nullptr;
-    h->n_prior_wslot = 0;
-    const int32_t n = (int32_t)h->priors.size();
-    if (n == 0) return LVBA_OK;
+    if (h->priors.empty()) return LVBA_OK;
     TRY(prior_pattern(h));
-    const int64_t Bb1 = (int64_t)bs.Bb + 1;
-    std::vector<PriorRec> rec((size_t)n);
-    std::map<int64_t, std::vector<int32_t>> hb; // slot -> contributions, ascending prior index
-    std::map<int32_t, std::vector<int32_t>> gb; // solver camera -> contributions
-    for (int32_t k = 0; k < n; ++k) {
-        const lvba_prior &q = h->priors[(size_t)k];
-        PriorRec &r = rec[(size_t)k];
-        const bool rel = q.kind == LVBA_PRIOR_RELATIVE;
-        r.kind = q.kind;
-        r.I = bs.iperm[(size_t)q.i];
-        r.J = rel ? bs.iperm[(size_t)q.j] : r.I;
-        r.flip = r.I < r.J ? 1 : 0;
-        memcpy(r.meas, q.meas, sizeof r.meas);
-        prior_offset_or_identity(q.offset_i, r.oi);
-        prior_offset_or_identity(q.offset_j, r.oj);
-        memcpy(r.L, q.sqrt_info, sizeof r.L);
-        hb[(int64_t)r.I * Bb1].push_back(k << 2);
-        gb[r.I].push_back(k << 2);
-        if (rel) {
-            hb[(int64_t)r.J * Bb1].push_back(k << 2 | 1);
-            gb[r.J].push_back(k << 2 | 1);
-            const int32_t lo = std::min(r.I, r.J), hi = std::max(r.I, r.J);
-            hb[(int64_t)lo * Bb1 + (hi - lo)].push_back(k << 2 | 2);
-        }
-    }
-    lvba::hvec<int64_t> hslot, wslot;
-    lvba::hvec<int32_t> hmode, hoff(1, 0), hsrc, gpose, goff(1, 0), gsrc;
-    for (const auto &t : hb) {
-        const bool diag = t.first % Bb1 == 0;
-        const bool add = diag || bs.distributed() || std::binary_search(h->pat_slots.begin(), h->pat_slots.end(), t.first);
-        hslot.push_back(t.first);
-        hmode.push_back((add ? 0 : 1) | (diag ? 2 : 0));
-        if (!add) wslot.push_back(t.first);
-        hsrc.insert(hsrc.end(), t.second.begin(), t.second.end());
-        hoff.push_back((int32_t)hsrc.size());
-    }
-    for (const auto &t : gb) {
-        gpose.push_back(t.first);
-        gsrc.insert(gsrc.end(), t.second.begin(), t.second.end());
-        goff.push_back((int32_t)gsrc.size());
-    }
-    PriorRec *d_rec = nullptr;
-    double *d_lin = nullptr, *d_part = nullptr;
-    unsigned *d_ticket = nullptr;
-    int64_t *d_hslot = nullptr;
-    int32_t *d_hmode = nullptr, *d_hoff = nullptr, *d_hsrc = nullptr, *d_gpose = nullptr, *d_goff = nullptr, *d_gsrc = nullptr;
-    TRY(prior_upload(h, &d_rec, rec.size(), rec.data()));
-    TRY(prior_upload<double>(h, &d_lin, 128 * (size_t)n, nullptr));
-    TRY(prior_upload<double>(h, &d_part, 2 * ((size_t)(n + 63) / 64), nullptr));
-    const unsigned zero = 0;
-    TRY(prior_upload(h, &d_ticket, 1, &zero));
-    TRY(prior_upload(h, &d_hslot, hslot.size(), hslot.data()));
-    TRY(prior_upload(h, &d_hmode, hmode.size(), hmode.data()));
-    TRY(prior_upload(h, &d_hoff, hoff.size(), hoff.data()));
-    TRY(prior_upload(h, &d_hsrc, hsrc.size(), hsrc.data()));
-    TRY(prior_upload(h, &d_gpose, gpose.size(), gpose.data()));
-    TRY(prior_upload(h, &d_goff, goff.size(), goff.data()));
-    TRY(prior_upload(h, &d_gsrc, gsrc.size(), gsrc.data()));
-    if (!wslot.empty()) TRY(prior_upload(h, &h->d_prior_wslot, wslot.size(), wslot.data()));
-    h->n_prior_wslot = (int64_t)wslot.size();
-    PriorDev &d = h->vp.tab;
-    d.pr = d_rec; d.lin = d_lin; d.part = d_part; d.ticket = d_ticket;
-    d.n_hblk = (int64_t)hslot.size(); d.hslot = d_hslot; d.hmode = d_hmode; d.hoff = d_hoff; d.hsrc = d_hsrc;
-    d.n_g = (int32_t)gpose.size(); d.gpose = d_gpose; d.goff = d_goff; d.gsrc = d_gsrc;
+    TRY(h->pt.bind(bs, h->priors, h->pat_slots, bs.distributed(), 2, nullptr));
+    h->vp.tab = h->pt.dev;
     h->vp.active = bs.rank == 0 ? 1 : 0; // the cameras are replicated over the ranks: one of them adds their priors
     h->vp.fixed_cam = bs.iperm[0];
     h->vp.pscal = h->d_pscal;
-    d.n = n; // (last: a failed upload above leaves a handle without priors)
     return LVBA_OK;
 }
 
 extern "C" int32_t lvba_visual_set_priors(lvba_visual_t h, int32_t n, const lvba_prior *priors)
 {
     if (!h) return fail(LVBA_ERR_ARG, "handle is NULL");
-    if (n > (1 << 22)) return fail(LVBA_ERR_ARG, "more than 2^22 priors");
-    TRY(lvba::prior_validate(n, priors, h->M));
+    TRY(prior_cap(n));
+    TRY(prior_validate(n, priors, h->M));
     BlockSys &bs = h->bs;
     if (h->finalized) { // the store is laid out: every relative pair must be one of its blocks
         TRY(prior_pattern(h));
-        for (int32_t k = 0; k < n; ++k) {
-            if (priors[k].kind != LVBA_PRIOR_RELATIVE) continue;
-            const int32_t I = bs.iperm[(size_t)priors[k].i], J = bs.iperm[(size_t)priors[k].j];
-            const int32_t lo = std::min(I, J), hi = std::max(I, J);
-            bool ok = hi - lo <= bs.Bb;
-            if (ok && bs.d_ar_slot) // sharded: only the blocks of the union pattern travel
-                ok = std::binary_search(h->pat_slots.begin(), h->pat_slots.end(), (int64_t)lo * (bs.Bb + 1) + (hi - lo));
-            if (!ok) return fail(LVBA_ERR_STATE, "prior %d joins cameras %d and %d, which are no block of the store laid out at the first "
-                                 "cost / linearize / refine call: set such priors before it", k, priors[k].i, priors[k].j);
-        }
+        // sharded: only the blocks of the union pattern travel
+        TRY(prior_pairs_in_store(bs, n, priors, bs.d_ar_slot ? &h->pat_slots : nullptr, nullptr, "cameras", "linearize"));
     }
-    std::vector<lvba_prior> old(priors, priors + n);
+    std::vector<lvba_prior> old;
     old.swap(h->priors); // (old: what the handle held)
-    for (lvba_prior &q : h->priors) {
-        q.reserved = 0;
-        if (q.kind != LVBA_PRIOR_RELATIVE) { q.j = 0; memset(q.offset_j, 0, sizeof q.offset_j); }
-    }
-    if (!h->finalized) {
-        bs.edge_i.clear(); bs.edge_j.clear();
-        for (const lvba_prior &q : h->priors)
-            if (q.kind == LVBA_PRIOR_RELATIVE) { bs.edge_i.push_back(q.i); bs.edge_j.push_back(q.j); }
-        return LVBA_OK;
-    }
+    prior_store(bs, h->finalized, n, priors, h->priors);
+    if (!h->finalized) return LVBA_OK;
     const int32_t rc = bind_priors(h);
     if (rc != LVBA_OK) { // out of memory / a failed upload: the handle keeps the priors it had (their pairs are blocks of the store)
         h->priors.swap(old);

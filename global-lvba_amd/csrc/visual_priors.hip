@@ -10,63 +10,13 @@
 //                         derived from, in the fixed order of the same host-built CSR table
 //   vprior_trial_kernel   one launch per LM iteration: sum |e|^2 at the trial point and the priors' share -(W d).(e + W d / 2)
 //                         of the model cost change for the camera step d
-// The grid-wide sums run in a fixed order: a tree over the 64 lanes of each workgroup, then the workgroup that finishes last (a
-// ticket counter, the only atomic) sums the workgroups' shares in index order.  The bytes do not change run to run.
+// The grid-wide sums (two values per lane) run in the fixed order of prior_grid_sum (prior_device.h).
 #include <hip/hip_runtime.h>
 
 #include "lvba_internal.h"
 #include "visual_prior_device.h"
 
 namespace lvba {
-
-// Fixed-order sums of two values per lane over the whole grid (64-lane workgroups, part [gridDim.x][2]); the last workgroup to
-// finish writes (or adds) the totals to out0[0], out1[0] (either may be NULL) and resets the ticket for the next launch.
-__device__ void vprior_grid_sum2(double v0, double v1, double *__restrict__ part, unsigned *__restrict__ ticket, double *__restrict__ out0,
-                                 double *__restrict__ out1, bool add)
-{
-    __shared__ double red[2][64];
-    __shared__ int last;
-    red[0][threadIdx.x] = v0;
-    red[1][threadIdx.x] = v1;
-    __syncthreads();
-    for (int w = 32; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + w];
-            red[1][threadIdx.x] += red[1][threadIdx.x + w];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        part[2 * blockIdx.x] = red[0][0];
-        part[2 * blockIdx.x + 1] = red[1][0];
-        __threadfence();
-        last = atomicAdd(ticket, 1u) == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!last) return;
-    __threadfence();
-    double s0 = 0.0, s1 = 0.0;
-    for (unsigned b = threadIdx.x; b < gridDim.x; b += 64) {
-        s0 += __builtin_nontemporal_load(part + 2 * b);
-        s1 += __builtin_nontemporal_load(part + 2 * b + 1);
-    }
-    __syncthreads();
-    red[0][threadIdx.x] = s0;
-    red[1][threadIdx.x] = s1;
-    __syncthreads();
-    for (int w = 32; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + w];
-            red[1][threadIdx.x] += red[1][threadIdx.x + w];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        if (out0) out0[0] = add ? out0[0] + red[0][0] : red[0][0];
-        if (out1) out1[0] = add ? out1[0] + red[1][0] : red[1][0];
-        *ticket = 0u;
-    }
-}
 
 __device__ __forceinline__ void vprior_load_cam(const double *__restrict__ qc, const double *__restrict__ tc, int32_t I, double *q, double *t)
 {
@@ -83,27 +33,6 @@ __device__ __forceinline__ void vprior_scales(const double *__restrict__ sc_cam,
     for (int c = 0; c < 6; ++c) sc[c] = I == fixed_cam ? 0.0 : (sc_cam ? sc_cam[6 * (int64_t)I + c] : 1.0);
 }
 
-// o[g0 + c] = W^T e, o[h0 + 6 c + r] = (W^T W)(r, c)
-__device__ __forceinline__ void vprior_products(const double *W, const double *e, double *__restrict__ o, int g0, int h0)
-{
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {
-        double s = 0.0;
-#pragma unroll
-        for (int a = 0; a < 6; ++a) s += W[6 * a + c] * e[a];
-        o[g0 + c] = s;
-    }
-#pragma unroll
-    for (int c = 0; c < 6; ++c)
-#pragma unroll
-        for (int r = 0; r < 6; ++r) {
-            double s = 0.0;
-#pragma unroll
-            for (int a = 0; a < 6; ++a) s += W[6 * a + r] * W[6 * a + c];
-            o[h0 + 6 * c + r] = s;
-        }
-}
-
 // one prior's lin record; returns |e|^2.  (kind is a constant at each call site, as in priors.hip: every array stays in registers)
 __device__ __forceinline__ double vprior_lin_one(const int kind, const PriorRec &p, int32_t fixed_cam, const double *__restrict__ qc,
                                                  const double *__restrict__ tc, const double *__restrict__ sc_cam, double *__restrict__ o)
@@ -115,22 +44,13 @@ __device__ __forceinline__ double vprior_lin_one(const int kind, const PriorRec 
     vprior_scales(sc_cam, p.I, fixed_cam, sc);
 #pragma unroll
     for (int a = 0; a < 36; ++a) Wi[a] *= sc[a % 6];
-    vprior_products(Wi, e, o, PL_GI, PL_HII);
+    prior_products(Wi, e, o, PL_GI, PL_HII);
     if (kind != PRIOR_RELATIVE) return c2;
     vprior_scales(sc_cam, p.J, fixed_cam, sc);
 #pragma unroll
     for (int a = 0; a < 36; ++a) Wj[a] *= sc[a % 6];
-    vprior_products(Wj, e, o, PL_GJ, PL_HJJ);
-#pragma unroll
-    for (int c = 0; c < 6; ++c)
-#pragma unroll
-        for (int r = 0; r < 6; ++r) {
-            // (W_i^T W_j)(r, c): block (i, j).  The store keeps (max, min) in solver order; flip: j comes after i, block (j, i)
-            double x = 0.0;
-#pragma unroll
-            for (int a = 0; a < 6; ++a) x += Wi[6 * a + r] * Wj[6 * a + c];
-            o[PL_HX + (p.flip ? 6 * r + c : 6 * c + r)] = x;
-        }
+    prior_products(Wj, e, o, PL_GJ, PL_HJJ);
+    prior_cross(Wi, Wj, p.flip, o, PL_HX);
     return c2;
 }
 
@@ -148,7 +68,7 @@ __global__ __launch_bounds__(64) void vprior_lin_kernel(const PriorRec *__restri
         else if (p.kind == PRIOR_POSITION) c2 = vprior_lin_one(PRIOR_POSITION, p, fixed_cam, qc, tc, sc_cam, o);
         else c2 = vprior_lin_one(PRIOR_RELATIVE, p, fixed_cam, qc, tc, sc_cam, o);
     }
-    vprior_grid_sum2(c2, 0.0, part, ticket, scal0, nullptr, true);
+    prior_grid_sum<2>({c2, 0.0}, part, ticket, {scal0, nullptr}, true);
 }
 
 // per camera with priors (the g table: piece 0 = the prior's camera i, 1 = its camera j): diag [6 I + el] += sum of the squared
@@ -233,7 +153,7 @@ __global__ __launch_bounds__(64) void vprior_trial_kernel(const PriorRec *__rest
             for (int a = 0; a < 6; ++a) e_out[6 * (int64_t)k + a] = e[a];
         }
     }
-    vprior_grid_sum2(c2, mc, part, ticket, out_cost, out_model, add);
+    prior_grid_sum<2>({c2, mc}, part, ticket, {out_cost, out_model}, add);
 }
 
 static inline unsigned vprior_grid(int32_t n) { return (unsigned)((n + 63) / 64); }

@@ -912,11 +912,7 @@ extern "C" void lvba_lidar_ba_default_opts(lvba_lidar_ba_opts *o)
 
 // n_shares == 1: the whole sequence on scs[0]'s device; > 1: the window stage over the shares (lvba_window_ba_multi), the global
 // stages -- single problems over all anchors -- on the first share's device, where the anchor clouds are gathered
-namespace lvba {
-int32_t prior_validate(int32_t n, const lvba_prior *priors, int32_t n_poses); // lvba_api.hip
-void prior_offset_or_identity(const double *o, double *out);
-int32_t loss_validate(const lvba_loss *loss, const char *what);
-}
+
 // frame priors -> priors on the anchors of the global stages: frame f = anchor a(f) o rel_f, so T_f O = T_a (rel_f o O) exactly.
 // Frames of skipped windows (anchor -1) and relative priors inside one anchor (constant at this stage) are dropped.
 static void priors_to_anchors(int32_t n, const lvba_prior *fp, const int32_t *aidx, const double *rel, std::vector<lvba_prior> &out)
