@@ -435,24 +435,30 @@ synth = importlib.import_module("global-lvba_amd.synth")
 d = synth.make_balm_problem(700, 30000, band=12, loop_frac=0.0, seed=5)
 prob = pkg.BalmProblem(700, d["voxel_off"], d["pose_idx"], d["clusters"])
 import os
-prob.eval(d["poses_init"], want_H=False, want_g=False)
+_, g, _ = prob.eval(d["poses_init"], want_H=False)
 info = prob.info()
 dx = prob.solve(0.01)
 if os.environ.get("LVBA_CHECK_BAND") == "1":      # the check runs at the START of a solve, on what the solves before it left
     for _ in range(2):
         assert np.array_equal(prob.solve(0.01), dx)
 np.save(sys.argv[2], np.concatenate([dx.ravel(), [info["use_band"], info["twist_panels"]]]))
+np.save(sys.argv[2][:-4] + "_g.npy", g)
 """
 
 
-def test_solver_schedules(tmp_path):
+_SCHEDULE_SPREAD = 1.7e-14   # ten times the largest spread measured on the MI355X (1.66e-15; four of the six forms: the same bits)
+
+
+def test_solver_schedules(pkg, oracle_mod, tmp_path):
     """The band LDL^T (look-ahead schedule: one launch per panel; both ends at once, paired panels, 128 x 64 update tiles) has two
     forms a problem can end up in by its size and shape -- 64 x 64 update tiles with 64-bit addressing (matrices of 4 GB and
     more; LVBA_SOLVER=bulk64 forces it) and the plain top-down factorisation (bands too short for two ends; LVBA_SOLVER=notwist);
     the two ends run the row roles' deferred form, everything else their full form (LVBA_SOLVER=nodefer: the full form everywhere).
     Every form must give the same solution of the same damped system (they differ in summation order only): 4200 unknowns,
     half-bandwidth ~150, enough panels for the two-ended form and the pairing to be active.  (Environment switches are read
-    once per process: one subprocess per form.)"""
+    once per process: one subprocess per form.)
+    The default form is also held to the bars of tests/test_gpu_band_solver.py against the refined reference of the system the
+    parent evaluates (every child's g must be the parent's bits: then the children solved that system)."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -463,18 +469,36 @@ def test_solver_schedules(tmp_path):
                 {"LVBA_SOLVER": "nodefer"}, {"LVBA_SOLVER": "bulk64,nodefer"},
                 # debugging switch: the never-rewritten part of the band store stays zero over repeated solves (no graph)
                 {"LVBA_CHECK_BAND": "1", "LVBA_NO_GRAPH": "1"}]
-    out = []
+    out, gs = [], []
     for i, v in enumerate(variants):
         f = tmp_path / f"dx_{i}.npy"
         env = dict(os.environ, **v)
         r = subprocess.run([sys.executable, str(script), root, str(f)], env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, (v, r.stderr[-2000:])
         out.append(np.load(f))
+        gs.append(np.load(tmp_path / f"dx_{i}_g.npy"))
     ref = out[0]
     assert ref[-2] == 1 and ref[-1] >= 4, ref[-2:]          # band storage, factorised from both ends
     assert np.isfinite(ref).all()
-    for v, o in zip(variants[1:], out[1:]):
-        assert np.abs(o[:-2] - ref[:-2]).max() <= 1e-9 * np.abs(ref[:-2]).max(), (v, np.abs(o[:-2] - ref[:-2]).max() / np.abs(ref[:-2]).max())
+    spread = [np.abs(o[:-2] - ref[:-2]).max() / np.abs(ref[:-2]).max() for o in out[1:]]
+    print("solver_schedules: variant - default, relative:", ["%.2e" % s for s in spread])
+    for v, s in zip(variants[1:], spread):
+        assert s <= _SCHEDULE_SPREAD, (v, s)
+    # the default form against the refined reference of the system it was given
+    import band_solve_reference as R
+    d = make_problem(700, 30000, band=12, loop_frac=0.0, seed=5)
+    prob = pkg.BalmProblem(700, d["voxel_off"], d["pose_idx"], d["clusters"])
+    H, g, _ = prob.eval(d["poses_init"])
+    prob.close()
+    for v, gv in zip(variants, gs):
+        assert np.array_equal(gv, g), v
+    A, b = H + 0.01 * np.diag(np.diag(H)), -g
+    x_ref = R.reference_solve(A, b, R.bandwidth(H))
+    x_o, rc = oracle_mod.ldlt_solve_dense(A, b)
+    assert rc == 0
+    yard, got = R.errors(A, b, x_o, x_ref), R.errors(A, b, ref[:-2], x_ref)
+    print(f"solver_schedules: default form backward {got[0]:.3e} (oracle {yard[0]:.3e})  forward {got[1]:.3e} (oracle {yard[1]:.3e})")
+    assert R.within_bars(got[0], yard[0]) and R.within_bars(got[1], yard[1]), (got, yard)
 
 
 def test_grouped_refinement_equals_one_by_one(pkg):
