@@ -28,6 +28,7 @@ SYMBOLS = [
     "lvba_fuse_default_opts", "lvba_fuse_tracks",
     "lvba_colorize_default_opts", "lvba_colorize_create", "lvba_colorize_add_images", "lvba_colorize_count",
     "lvba_colorize_download", "lvba_colorize_profile", "lvba_colorize_destroy",
+    "lvba_mapq_default_opts", "lvba_mapq_scans", "lvba_mapq_points",
 ]
 
 OK, ERR_ARG, ERR_DEVICE, ERR_NOMEM, ERR_UNSUPPORTED, ERR_DIST, ERR_STATE = 0, -1, -2, -3, -4, -5, -6
@@ -127,6 +128,15 @@ class FuseOpts(C.Structure):
 class ColorizeOpts(C.Structure):
     _fields_ = [("half_window_s", C.c_double), ("leaf_size", C.c_double), ("max_batch_images", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+class MapqOpts(C.Structure):
+    _fields_ = [("radius", C.c_double), ("min_neighbors", C.c_int32), ("query_stride", C.c_int32)]
+
+
+class MapqSummary(C.Structure):
+    _fields_ = [("n_points", C.c_int64), ("n_queries", C.c_int64), ("n_valid", C.c_int64), ("mme", C.c_double), ("mpv", C.c_double),
+                ("mean_neighbors", C.c_double), ("ms", C.c_double * 4)]
 
 
 class VoxelOpts(C.Structure):
@@ -310,6 +320,12 @@ def load():
     lib.lvba_colorize_profile.argtypes = [C.c_void_p, C.c_void_p]
     lib.lvba_colorize_destroy.argtypes = [C.c_void_p]
     lib.lvba_colorize_destroy.restype = None
+    lib.lvba_mapq_default_opts.argtypes = [C.POINTER(MapqOpts)]
+    lib.lvba_mapq_default_opts.restype = None
+    lib.lvba_mapq_scans.argtypes = [C.c_void_p, f64p, C.c_int32, C.c_int32, C.POINTER(MapqOpts), C.POINTER(MapqSummary), C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.lvba_mapq_points.argtypes = [C.c_int32, C.c_int64, C.c_void_p, C.POINTER(MapqOpts), C.POINTER(MapqSummary), C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]
     lib.lvba_scans_info.argtypes = [H, C.POINTER(C.c_int32), C.c_void_p]
     lib.lvba_scans_download.argtypes = [H, C.c_int32, np.ctypeslib.ndpointer(np.float32, flags="C")]
     for name in SYMBOLS:

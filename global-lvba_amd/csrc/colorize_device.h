@@ -112,4 +112,30 @@ LVBA_TRK_FN uint64_t col_pack_key(const int64_t k[3])
     return ((uint64_t)(k[0] + COL_KEY_BIAS) << 42) | ((uint64_t)(k[1] + COL_KEY_BIAS) << 21) | (uint64_t)(k[2] + COL_KEY_BIAS);
 }
 
+#if defined(__HIPCC__)
+// One lane per point i of P points in frames frame_off[0 .. n_frames] (offsets relative to pts): the world point of
+// col_world_point at the frame's pose, stored as float.  thin: a finite point whose leaf key cannot be packed sets *err.
+// Shared by the coloured map (colorize.hip) and the map-quality metrics (map_quality.hip: thin = 0, err unused).
+static __global__ void col_world_kernel(int64_t P, const float *__restrict__ pts, const int64_t *__restrict__ frame_off, int n_frames,
+                                 const double *__restrict__ poses, double leaf, int thin, float *__restrict__ world,
+                                 int *__restrict__ err)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= P) return;
+    int lo = 0, hi = n_frames;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (frame_off[mid] <= i) lo = mid; else hi = mid;
+    }
+    float q[3];
+    col_world_point(poses + 12 * (int64_t)lo, pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], q);
+    world[3 * i] = q[0]; world[3 * i + 1] = q[1]; world[3 * i + 2] = q[2];
+    if (thin && isfinite(q[0]) && isfinite(q[1]) && isfinite(q[2])) { // only finite points can ever be projected
+        int64_t k[3];
+        double dd;
+        if (!col_leaf_key(q, leaf, k, dd)) atomicOr(err, 1);
+    }
+}
+#endif
+
 } // namespace lvba

@@ -299,6 +299,18 @@ def colorize_maps(scans, image_times, images, intr, width, height, after, before
             m.close()
 
 
+def map_quality(scans, after, before=None, **kw):
+    """Mean map entropy / mean plane variance (mapq.map_quality_scans) of the scans at the refined poses `after` [n,12] and, when
+    given, at the original ones `before`: {"after": summary, "before": summary or None}.  kw: radius, min_neighbors,
+    query_stride, per_point.  A sharper map has the lower mme."""
+    from .mapq import map_quality_scans
+    return {"after": map_quality_scans(scans, after, **kw),
+            "before": None if before is None else map_quality_scans(scans, before, **kw)}
+
+
+_map_quality = map_quality   # run_full_pipeline / run_dataset have a keyword of that name
+
+
 def _lidar_cfg(cfg):
     c = dict(DEFAULTS); c.update(cfg)
     return dict(window_enable=c["window_enable"], window_size=c["window_size"], anchor_leaf=c["anchor_leaf"], use_rel=c["use_rel"],
@@ -349,7 +361,7 @@ def run_lidar_ba(scans, poses, priors=None, window_loss=None, stage_loss=None, h
 
 def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, tci, intr, width, height, keypoints, pairs,
                       matches, enable_lidar_ba=True, enable_visual_ba=True, device=0, images=None, lidar_priors=None,
-                      window_loss=None, stage_loss=None, camera_priors=None, **cfg):
+                      window_loss=None, stage_loss=None, camera_priors=None, map_quality=False, **cfg):
     """LvbaSystem::runFullPipeline (src/lvba_system.cpp:136-142) on in-memory data: clouds = body-frame [n_i, >=3] float32
     arrays, poses [n,12] = x_buf_ (T_world<-imu), image_poses [m,12] the image poses from the odometry.  cfg: DEFAULTS' keys
     (visual_loss, colorize_leaf among them).  images: None, or the images ([m,H,W,3] BGR uint8 or a callable k -> [H,W,3]):
@@ -357,7 +369,9 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
     (colorize_maps) with the refined poses and cameras and with the original ones; this needs the visual stage.
     lidar_priors: balm.Prior objects on frames (GNSS fixes, loop closures, ...) for the global stages of the LiDAR BA
     (Scans.lidar_ba(priors=...)).  window_loss / stage_loss: robust losses of the LiDAR BA (run_lidar_ba).  camera_priors:
-    priors on the cameras of the visual stage (run_visual_ba_with_lidar_assist; None: none)."""
+    priors on the cameras of the visual stage (run_visual_ba_with_lidar_assist; None: none).  map_quality: True, or a dict of
+    mapq.map_quality_scans' keywords: the output also holds map_quality = {"after": ..., "before": ...}, the mean map entropy and
+    mean plane variance of the scans at the refined and at the original poses (off by default: nothing is launched)."""
     if images is not None and not enable_visual_ba:
         raise ValueError("colouring the map needs the cameras of the visual stage (enable_visual_ba=True)")
     c = dict(DEFAULTS); c.update(cfg)
@@ -379,6 +393,9 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
                                 before=(x_orig, v["Rcw_before"], v["tcw_before"]), scan_times=scan_times,
                                 half_window_s=c["colorize_half_window_s"], leaf_size=c["colorize_leaf"])
             out["colored_after"], out["colored_before"] = col["after"], col["before"]
+        if map_quality:
+            kw = dict(map_quality) if isinstance(map_quality, dict) else {}
+            out["map_quality"] = _map_quality(scans, out["poses"], x_orig, **kw)
     return out
 
 
@@ -413,7 +430,7 @@ def extrinsics_from_config(Rcl, Pcl, extrinsic_R, extrinsic_T):
 
 
 def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrinsic_R=np.eye(3), extrinsic_T=np.zeros(3),
-                image_sample_step=1, out_dir=None, device=0, colorize=False, **cfg):
+                image_sample_step=1, out_dir=None, device=0, colorize=False, map_quality=False, **cfg):
     """initFromDatasetIO + runFullPipeline on a dataset directory; with out_dir, the refined LiDAR poses (TUM) and the COLMAP
     text files images.txt / points3D.txt the reference writes (src/lvba_system.cpp:2018-2137) are saved there.  images.txt is
     the reference's, character for character (tests/test_ref_system.py).
@@ -423,6 +440,8 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
     the camera's is resized with Pillow's bilinear filter, which is not OpenCV's INTER_LINEAR bit for bit.  The output gains
     colored_after / colored_before, and out_dir gets colored_merged_after.pcd / colored_merged_before.pcd (binary PCD, PCL's
     XYZRGB layout) and a points3D.txt holding the coloured after-cloud, as the reference writes them.
+    map_quality (True or a dict of keywords, as for run_full_pipeline): the output gains map_quality and out_dir gets
+    map_quality.json, the two summaries.
     cfg as for run_full_pipeline, e.g. visual_loss=REFERENCE_HUBER, window_loss=("cauchy", 0.1), stage_loss=("huber", 0.05),
     camera_priors=lambda cams: lidar_camera_priors(cams, Rci, tci, 1e-3, 0.02)."""
     import os
@@ -442,7 +461,7 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
     out = run_full_pipeline([c[:, :3] for c in ds["clouds"]], ds["poses"], ds["timestamps"], image_ids, image_poses, Rci, tci, intr,
                             width, height, [k[:, :2] for k in kps], [pairs[k] for k in keep], [matches[k] for k in keep],
                             device=device, images=(lambda k: D.read_image_bgr(os.path.join(img_dir, names[k]), width, height))
-                            if colorize else None, **cfg)
+                            if colorize else None, **({"map_quality": map_quality} if map_quality else {}), **cfg)
     out.update(image_ids=image_ids, scan_times=ds["timestamps"])
     if out_dir is not None:
         os.makedirs(out_dir, exist_ok=True)
@@ -457,4 +476,9 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
             D.save_pcd_xyzrgb(os.path.join(out_dir, "colored_merged_after.pcd"), *out["colored_after"])
             D.save_pcd_xyzrgb(os.path.join(out_dir, "colored_merged_before.pcd"), *out["colored_before"])
             D.write_points3d_txt(os.path.join(out_dir, "points3D.txt"), *out["colored_after"])
+        if map_quality:
+            import json
+            with open(os.path.join(out_dir, "map_quality.json"), "w") as f:
+                json.dump({k: None if q is None else {a: b for a, b in q.items() if not isinstance(b, np.ndarray)}
+                           for k, q in out["map_quality"].items()}, f, indent=1)
     return out

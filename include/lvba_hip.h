@@ -730,6 +730,45 @@ int32_t lvba_colorize_download(lvba_colorize_t h, float *xyz, uint8_t *rgb);
 int32_t lvba_colorize_profile(lvba_colorize_t h, double ms[6]);
 void lvba_colorize_destroy(lvba_colorize_t h);
 
+/* ---- Map quality without ground truth: mean map entropy, mean plane variance, normals (version 112) ----------------------
+ *   The measures of Razlaw et al. 2015 on the aggregated cloud, plus what the same reduction gives per point.
+ *   Cloud: from scans, frames [frame_begin, frame_begin + n_frames) at scan_poses [n_frames][12] (R row-major | t,
+ *   T_world<-body; relative to frame_begin as for the voxel maps), every point w = (float)(R (double)p + t) in cloud order (frames
+ *   in order, points in scan order) -- the world points of the coloured map --; or n caller-supplied points xyz [n][3] float
+ *   (host memory) on `device`.  A non-finite point keeps its index, is nobody's neighbour and, as a query, has count 0.
+ *   Queries: the points with index k * query_stride, n_queries = ceil(n_points / query_stride); neighbours: all points.
+ *   Neighbourhood of query k: the points j with d2 <= radius * radius, d = (double)w_j - (double)w_k,
+ *   d2 = (dx dx + dy dy) + dz dz rounded as written (no fused multiply-add), k itself included; count = their number.
+ *   Moments about the query, in fp64: m = sum d / count, S = sum d d^T / count - m m^T.  A query is valid when
+ *   count >= min_neighbors and det S (the product of the eigenvalues of S) is finite and > 0; then
+ *   entropy = 1/2 ln((2 pi e)^3 det S), plane_var = the smallest eigenvalue, normal = its unit eigenvector, signed so that its
+ *   largest component in magnitude is positive; otherwise the three are NaN.
+ *   Summary: mme / mpv = the mean entropy / plane_var over the valid queries (NaN without any), mean_neighbors = the mean count
+ *   over the queries with a finite point; every sum runs in a fixed order, two calls give the same bytes.  ms = device time of
+ *   the world points (or the upload), sort + cell table, reduction, download.
+ *   Per-query outputs, each may be NULL: entropy, plane_var, count [n_queries], normal [n_queries][3].
+ *   Options: NULL takes the defaults.
+ *   LVBA_ERR_ARG: a null scans, scan_poses, xyz (with n > 0) or summary pointer; radius <= 0 or non-finite;
+ *   min_neighbors < 4; query_stride < 1; n < 0 or n >= 2^32; a frame range outside the scans or n_frames < 1; a non-finite
+ *   pose; a finite point 2^20 - 1 or more cells (of edge radius (1 + 2^-20)) from the origin on any axis.
+ *   LVBA_ERR_NOMEM: the cloud does not fit into the free device memory (about 120 bytes per point). */
+typedef struct lvba_mapq_opts {
+    double radius;         /* neighbourhood radius in metres (default 0.3) */
+    int32_t min_neighbors; /* a query with fewer neighbours is invalid (default 8; at least 4) */
+    int32_t query_stride;  /* every query_stride-th point is a query (default 1) */
+} lvba_mapq_opts;
+typedef struct lvba_mapq_summary {
+    int64_t n_points, n_queries, n_valid;
+    double mme, mpv, mean_neighbors;
+    double ms[4];
+} lvba_mapq_summary;
+void lvba_mapq_default_opts(lvba_mapq_opts *o);
+int32_t lvba_mapq_scans(lvba_scans_t scans, const double *scan_poses, int32_t frame_begin, int32_t n_frames,
+                        const lvba_mapq_opts *o, lvba_mapq_summary *summary, double *entropy, double *plane_var, float *normal,
+                        int32_t *count);
+int32_t lvba_mapq_points(int32_t device, int64_t n, const float *xyz, const lvba_mapq_opts *o, lvba_mapq_summary *summary,
+                         double *entropy, double *plane_var, float *normal, int32_t *count);
+
 #ifdef __cplusplus
 }
 #endif
