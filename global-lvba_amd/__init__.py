@@ -8,6 +8,7 @@ from .balm import BALM2, IMUST, VOX_HESS, BalmProblem, Prior, shard_range
 from .visual import DepthImages, VisualProblem, fuse_tracks, optimize_camera_poses
 from .voxel import Scans, VoxelMap
 from .mapq import map_quality_points, map_quality_scans
+from . import register
 
 __all__ = ["BALM2", "IMUST", "VOX_HESS", "BalmProblem", "Prior", "shard_range", "VisualProblem", "optimize_camera_poses", "VoxelMap", "Scans",
-           "map_quality_scans", "map_quality_points", "_lib"]
+           "map_quality_scans", "map_quality_points", "register", "_lib"]

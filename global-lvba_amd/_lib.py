@@ -29,6 +29,7 @@ SYMBOLS = [
     "lvba_colorize_default_opts", "lvba_colorize_create", "lvba_colorize_add_images", "lvba_colorize_count",
     "lvba_colorize_download", "lvba_colorize_profile", "lvba_colorize_destroy",
     "lvba_mapq_default_opts", "lvba_mapq_scans", "lvba_mapq_points",
+    "lvba_register_default_opts", "lvba_register_linearize", "lvba_register_scans",
 ]
 
 OK, ERR_ARG, ERR_DEVICE, ERR_NOMEM, ERR_UNSUPPORTED, ERR_DIST, ERR_STATE = 0, -1, -2, -3, -4, -5, -6
@@ -137,6 +138,22 @@ class MapqOpts(C.Structure):
 class MapqSummary(C.Structure):
     _fields_ = [("n_points", C.c_int64), ("n_queries", C.c_int64), ("n_valid", C.c_int64), ("mme", C.c_double), ("mpv", C.c_double),
                 ("mean_neighbors", C.c_double), ("ms", C.c_double * 4)]
+
+
+REG_STATUS = {0: "converged", 1: "max_iterations", 2: "too_few_inliers", 3: "degenerate"}
+
+
+class RegisterOpts(C.Structure):
+    _fields_ = [("max_iterations", C.c_int32), ("max_distance", C.c_double), ("min_inliers", C.c_int64), ("min_eigenvalue", C.c_double),
+                ("tol_rot", C.c_double), ("tol_pos", C.c_double), ("loss", Loss)]
+
+
+class RegisterResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("inliers", C.c_int64), ("points", C.c_int64),
+                ("cost_first", C.c_double), ("cost_last", C.c_double), ("rmse", C.c_double), ("min_eigenvalue", C.c_double)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
 
 
 class VoxelOpts(C.Structure):
@@ -326,6 +343,12 @@ def load():
                                     C.c_void_p, C.c_void_p, C.c_void_p]
     lib.lvba_mapq_points.argtypes = [C.c_int32, C.c_int64, C.c_void_p, C.POINTER(MapqOpts), C.POINTER(MapqSummary), C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.lvba_register_default_opts.argtypes = [C.POINTER(RegisterOpts)]
+    lib.lvba_register_default_opts.restype = None
+    lib.lvba_register_linearize.argtypes = [H, H, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(RegisterOpts), C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p]
+    lib.lvba_register_scans.argtypes = [H, H, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(RegisterOpts), C.c_void_p, C.c_void_p,
+                                        C.c_void_p]
     lib.lvba_scans_info.argtypes = [H, C.POINTER(C.c_int32), C.c_void_p]
     lib.lvba_scans_download.argtypes = [H, C.c_int32, np.ctypeslib.ndpointer(np.float32, flags="C")]
     for name in SYMBOLS:

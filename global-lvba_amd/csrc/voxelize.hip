@@ -36,28 +36,11 @@
 #include "mempool.h"
 #include "lvba_internal.h"
 #include "voxel_internal.h"
+#include "voxel_lookup.h"
 
 using namespace lvba;
 
 namespace {
-
-enum : int { ST_NONE = 0, ST_DROP = 1, ST_PLANE = 2, ST_SPLIT = 3 };
-
-// ---- shared per-point arithmetic (cut_voxel :809-815, root centre :826-829, cut_func :368-381) ------------------
-__device__ __forceinline__ void octants_of(const double pw[3], const int64_t k[3], double vs, int &o1, int &o2)
-{
-    const float quater = (float)(vs / 4.0);
-    o1 = 0; o2 = 0;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const float c0 = (float)((0.5 + (double)k[j]) * vs);
-        const int b1 = pw[j] > (double)c0 ? 1 : 0;
-        const float c1 = c0 + (float)(2 * b1 - 1) * quater;
-        const int b2 = pw[j] > (double)c1 ? 1 : 0;
-        o1 |= b1 << (2 - j);
-        o2 |= b2 << (2 - j);
-    }
-}
 
 // ---- 1. keys + records --------------------------------------------------------------------------------------------
 // frame_off: the window's slice of the scan set's frame offsets; pts already points at the window's first point
@@ -623,36 +606,12 @@ __global__ void vox_lookup_kernel(int64_t n, const double *__restrict__ X, doubl
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     double *o = out + 4 * i;
-    o[0] = o[1] = o[2] = o[3] = 0.0;
-    valid[i] = 0;
     const double pw[3] = {X[3 * i], X[3 * i + 1], X[3 * i + 2]};
-    if (!(isfinite(pw[0]) && isfinite(pw[1]) && isfinite(pw[2]))) return;
-    int64_t k[3];
-    if (!root_key_of(pw, vs, k)) return;
-    const uint64_t key = pack_key(k);
-    int64_t lo = 0, hi = R;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (root_key[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    if (lo >= R || root_key[lo] != key) return;
-    const uint32_t info = rootinfo[lo];
-    const int st0 = info & 0xff;
-    int o1, o2;
-    octants_of(pw, k, vs, o1, o2);
-    int lane;
-    if (st0 == ST_PLANE) lane = 0;
-    else if (st0 == ST_SPLIT) lane = ((info >> (8 + o1)) & 1u) ? (o1 << 3 | o2) : (o1 << 3);
-    else return;
-    const uint64_t m = mask[lo];
-    if (!((m >> lane) & 1ull)) return;
-    const double *pl = plane + 6 * ((int64_t)plane_first[lo] + __popcll(lane ? (m & (~0ull >> (64 - lane))) : 0ull));
-    const double nn = sqrt(pl[3] * pl[3] + pl[4] * pl[4] + pl[5] * pl[5]);
-    if (!(isfinite(nn) && nn >= 1e-6 && isfinite(pl[0]) && isfinite(pl[1]) && isfinite(pl[2]))) return;
-    const double n0 = pl[3] / nn, n1 = pl[4] / nn, n2 = pl[5] / nn;
-    o[0] = n0; o[1] = n1; o[2] = n2;
-    o[3] = -(n0 * pl[0] + n1 * pl[1] + n2 * pl[2]);
-    valid[i] = 1;
+    double pl[4];
+    const bool found = vox_find_plane(pw, vs, R, root_key, mask, rootinfo, plane_first, plane, pl); // voxel_lookup.h
+#pragma unroll
+    for (int q = 0; q < 4; ++q) o[q] = found ? pl[q] : 0.0;
+    valid[i] = found ? 1 : 0;
 }
 
 } // namespace
@@ -683,6 +642,18 @@ struct lvba_voxmap_s {
 };
 
 const double *lvba_voxmap_clusters(const lvba_voxmap_s *h) { return h ? h->d_clusters : nullptr; }
+
+int32_t lvba_voxmap_lookup_tables(const lvba_voxmap_s *h, lvba::VoxLookup *out, int *device)
+{
+    if (!h || !out || !device) return lvba_fail(LVBA_ERR_ARG, "null argument");
+    if (h->is_view || h->window_size > 0)
+        return lvba_fail(LVBA_ERR_UNSUPPORTED, "a joint map of several windows (or a view into one) has no key lookup");
+    out->vs = h->opts.voxel_size; out->R = h->info.n_roots;
+    out->root_key = h->d_root_key; out->mask = h->d_mask; out->rootinfo = h->d_rootinfo;
+    out->plane_first = h->d_plane_first; out->plane = h->d_plane;
+    *device = h->device;
+    return LVBA_OK;
+}
 
 extern "C" int64_t lvba_release_cached_memory(void)
 {

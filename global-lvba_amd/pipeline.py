@@ -308,6 +308,46 @@ def map_quality(scans, after, before=None, **kw):
             "before": None if before is None else map_quality_scans(scans, before, **kw)}
 
 
+def loop_closure_prior(scans, poses, map_frames, query_frame, ref_frame=None, voxel_size=1.0, eigen_ratio_array=None, sigma=None,
+                       **opts):
+    """A relative pose constraint from a revisit: the map of the frames `map_frames` (a contiguous ascending run of frame
+    indices) of `scans` at their current `poses` [n,12] is built, frame `query_frame` is registered against it from its current
+    pose (VoxelMap.register, opts: its options) and the result becomes a balm.Prior.relative between `ref_frame` (a map frame;
+    default the first) and the query frame.  Returns (prior, registration dict); the caller decides on status / rmse / inliers
+    whether to use it.
+    The measurement is T_ref^-1 T_query(registered).  The registration's information H is in the tangent (theta, t) of
+    R <- R Exp(theta), t <- t + delta, which is the LiDAR BA's own retraction (prior_device.h:3); the prior's residual is
+    r = [Log(Rm^T R_i^T R_j); R_i^T (p_j - p_i) - pm] (prior_device.h:7) and at r = 0, with identity offsets, its Jacobian to the
+    query pose is dr / dd_j = M = diag(I, R_i^T) (prior_device.h:230-245), so the information of r is M H M^T.  It is divided by
+    sigma^2, the variance of a point-to-plane distance in m^2 (default: the registration's rmse^2), to make 1/2 |L r|^2 the
+    negative log-likelihood; sqrt_info is the upper Cholesky factor L, L^T L = M H M^T / sigma^2.
+    eigen_ratio_array: default register.STRICT_RATIO (the reason is DESIGN.md §10c)."""
+    from .balm import Prior
+    from .register import STRICT_RATIO
+    mf = [int(f) for f in map_frames]
+    if not mf or mf != list(range(mf[0], mf[0] + len(mf))):
+        raise ValueError("map_frames must be a contiguous ascending run of frame indices")
+    i, j = (mf[0] if ref_frame is None else int(ref_frame)), int(query_frame)
+    if i not in mf or j == i:
+        raise ValueError("ref_frame must be one of map_frames and differ from query_frame")
+    x = np.asarray(poses, np.float64).reshape(-1, 12)
+    with scans.voxel_map(x[mf[0]:mf[0] + len(mf)], voxel_size, STRICT_RATIO if eigen_ratio_array is None else eigen_ratio_array,
+                         frame_begin=mf[0], n_frames=len(mf)) as m:
+        reg = m.register(scans, [j], x[j:j + 1], **opts)
+    Ri, pi = x[i, :9].reshape(3, 3), x[i, 9:]
+    Tj = reg["poses"][0]
+    meas = np.r_[(Ri.T @ Tj[:9].reshape(3, 3)).reshape(9), Ri.T @ (Tj[9:] - pi)]
+    s2 = float(reg["rmse"][0]) ** 2 if sigma is None else float(sigma) ** 2
+    M = np.zeros((6, 6))
+    M[:3, :3], M[3:, 3:] = np.eye(3), Ri.T
+    info = M @ reg["information"][0] @ M.T / s2 if s2 > 0 and reg["status"][0] in (0, 1) else np.zeros((6, 6))
+    try:
+        sqrt_info = np.linalg.cholesky(info).T
+    except np.linalg.LinAlgError:
+        sqrt_info = np.zeros((6, 6))   # a failed registration constrains nothing
+    return Prior.relative(i, j, meas, sqrt_info=sqrt_info), reg
+
+
 _map_quality = map_quality   # run_full_pipeline / run_dataset have a keyword of that name
 
 

@@ -1,0 +1,79 @@
+"""Scan-to-map registration (lvba_register_*): point-to-plane Gauss-Newton of scans against a voxel plane map.
+
+    with scans.voxel_map(poses[:5], 1.0, STRICT_RATIO, n_frames=5) as m:
+        r = m.register(scans, [5], poses[5:6])           # {"poses", "information", "status", "rmse", ...}
+
+Every point of a scan is taken to the world by the job's pose, associated with the map's plane exactly as
+VoxelMap.find_planes does it, and contributes its point-to-plane distance r if |r| <= max_distance; the pose is refined by
+Gauss-Newton under the retraction R <- R Exp(theta), t <- t + delta (include/lvba_hip.h has the exact definitions).  Build the
+map with strict eigen ratios (STRICT_RATIO) or set a loss: a map cut with the optimiser's stage-1 ratios admits planes fitted
+through clutter, and plain Gauss-Newton walks away from the true pose on it.  Everything runs in liblvba_hip.so
+on the GPU; this file packs arrays."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib as L
+
+STRICT_RATIO = (0.02, 0.02, 0.02, 0.02)   # eigen ratios of a registration map
+OPTS = ("max_iterations", "max_distance", "min_inliers", "min_eigenvalue", "tol_rot", "tol_pos")
+
+
+def default_opts():
+    o = L.RegisterOpts()
+    L.load().lvba_register_default_opts(C.byref(o))
+    return o
+
+
+def _opts(kw):
+    o = default_opts()
+    kw = dict(kw)
+    loss = kw.pop("loss", None)
+    for k, v in kw.items():
+        if k not in OPTS:
+            raise TypeError(f"unknown registration option {k!r}; one of {OPTS + ('loss',)}")
+        setattr(o, k, type(getattr(o, k))(v))
+    if loss is not None:
+        o.loss = L.loss_struct(loss).contents
+    return o
+
+
+def _jobs(frames, poses):
+    fr = np.ascontiguousarray(frames, np.int32).reshape(-1)
+    x = np.ascontiguousarray(poses, np.float64).reshape(-1)
+    if x.size != 12 * len(fr):
+        raise ValueError(f"{x.size // 12} poses for {len(fr)} frames")
+    return fr, x
+
+
+def linearize(vmap, scans, frames, poses, **opts):
+    """The sums of one linearisation per job (lvba_register_linearize): dict(H [n,6,6], g [n,6], cost [n], inliers [n])."""
+    fr, x = _jobs(frames, poses)
+    n = len(fr)
+    H, g, cost, inl = np.zeros((n, 6, 6)), np.zeros((n, 6)), np.zeros(n), np.zeros(n, np.int64)
+    o = _opts(opts)
+    L.check(L.load().lvba_register_linearize(vmap._h, scans._h, n, fr.ctypes.data, x.ctypes.data, C.byref(o), H.ctypes.data,
+                                             g.ctypes.data, cost.ctypes.data, inl.ctypes.data))
+    return dict(H=H, g=g, cost=cost, inliers=inl)
+
+
+def register(vmap, scans, frames, poses, **opts):
+    """Register frame frames[k] of `scans` (a voxel.Scans) from poses[k] against `vmap` (a voxel.VoxelMap), all jobs at once
+    (lvba_register_scans).  opts: max_iterations, max_distance [m], min_inliers, min_eigenvalue, tol_rot [rad], tol_pos [m],
+    loss=(kind, scale [m]).  Returns dict(poses [n,12], information [n,6,6] (H of the last linearisation, tangent order
+    (theta, t)), status [n] (a _lib.REG_STATUS key), status_name, iterations, inliers, points, cost_first, cost_last, rmse,
+    min_eigenvalue)."""
+    fr, x = _jobs(frames, poses)
+    n = len(fr)
+    out, info = np.zeros((n, 12)), np.zeros((n, 6, 6))
+    res = (L.RegisterResult * max(n, 1))()
+    o = _opts(opts)
+    L.check(L.load().lvba_register_scans(vmap._h, scans._h, n, fr.ctypes.data, x.ctypes.data, C.byref(o), out.ctypes.data,
+                                         info.ctypes.data, C.cast(res, C.c_void_p)))
+    d = dict(poses=out, information=info)
+    for f, t in L.RegisterResult._fields_:
+        d[f] = np.array([getattr(res[k], f) for k in range(n)], np.float64 if t is C.c_double else np.int64)
+    d["status_name"] = [L.REG_STATUS.get(int(s), "?") for s in d["status"]]
+    return d

@@ -359,3 +359,14 @@ class VoxelMap:
         valid = np.zeros(len(X), np.uint8)
         L.check(self.lib.lvba_voxmap_find_planes(self._h, len(X), X.reshape(-1), plane.reshape(-1), valid))
         return plane, valid
+
+    def register(self, scans, frames, poses, **opts):
+        """Scan-to-map registration of frames of `scans` from `poses` against this map (register.register): the refined poses, the
+        6 x 6 information of each fit and its statistics."""
+        from .register import register
+        return register(self, scans, frames, poses, **opts)
+
+    def register_linearize(self, scans, frames, poses, **opts):
+        """The point-to-plane sums H, g, cost, inliers of frames of `scans` at `poses` against this map (register.linearize)."""
+        from .register import linearize
+        return linearize(self, scans, frames, poses, **opts)

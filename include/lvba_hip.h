@@ -769,6 +769,57 @@ int32_t lvba_mapq_scans(lvba_scans_t scans, const double *scan_poses, int32_t fr
 int32_t lvba_mapq_points(int32_t device, int64_t n, const float *xyz, const lvba_mapq_opts *o, lvba_mapq_summary *summary,
                          double *entropy, double *plane_var, float *normal, int32_t *count);
 
+/* ---- scan-to-map registration: point-to-plane Gauss-Newton of scans against a voxel plane map -------------
+ *   A batch of n independent jobs; job k registers frame frames[k] of `scans` from the pose poses[k] (R row-major | t,
+ *   T_world<-body) against `map`.  The map and the scans may come from different scan sets (relocalisation) but lie on one device.
+ *   Per point p of the frame (fp32, promoted once), all in fp64 and rounded as written (no fused multiply-add):
+ *     w = (R00 px + R01 py) + R02 pz + tx, ...     the world point
+ *     (n, d)                                        its plane, exactly as lvba_voxmap_find_planes associates it
+ *     r = (n0 w0 + n1 w1) + n2 w2 + d               inlier iff a plane was found and |r| <= max_distance
+ *     J = [ p x (R^T n) ; n ]                       d r / d(theta, t) under the retraction R <- R Exp(theta), t <- t + delta
+ *     H += rho' J J^T, g += rho' J r, cost += rho   with (rho, rho') = loss(r^2), scale in metres (first-order IRLS weights);
+ *                                                   no loss: rho = r^2, rho' = 1
+ *   lvba_register_linearize returns these sums at the given poses: H [n][36] (full, symmetric, tangent order (theta, t)),
+ *   g [n][6], cost [n], inliers [n].
+ *   lvba_register_scans iterates every job, in lock-step on the device, until each has a status:
+ *     LVBA_REG_TOO_FEW_INLIERS   inliers < max(min_inliers, 1); the pose stays as it is
+ *     LVBA_REG_DEGENERATE        the smallest eigenvalue of H / inliers is below min_eigenvalue (or H has no LDL^T with positive
+ *                                pivots); the pose stays as it is
+ *     LVBA_REG_CONVERGED         delta = -H^-1 g has |dtheta| <= tol_rot and |dt| <= tol_pos; this last step is not applied, so
+ *                                the information and the statistics belong to the returned pose
+ *     LVBA_REG_MAX_ITERATIONS    max_iterations linearisations were taken, each followed by its step
+ *   poses_out [n][12]; information [n][36] = H at the job's last linearisation; results[k]: status, iterations (linearisations
+ *   taken), inliers / cost_last / rmse = sqrt(cost_last / inliers) / min_eigenvalue of the last linearisation, cost_first of the
+ *   first, points = the frame's point count.  Every sum runs in a fixed order that depends on the job's point count alone: two
+ *   calls give the same bytes, and a job gives the same bytes whatever else is in the batch.
+ *   An empty map is not an error: every job ends LVBA_REG_TOO_FEW_INLIERS.  Options: NULL takes the defaults.
+ *   LVBA_ERR_ARG: a null pointer (with n > 0), n < 0, a frame outside the scans, a non-finite pose, map and scans on different
+ *   devices, max_iterations outside 1 .. 1000, max_distance not finite and > 0, a negative min_inliers, min_eigenvalue or tolerance,
+ *   an unknown loss kind or a non-trivial loss whose scale is not finite and > 0.
+ *   LVBA_ERR_UNSUPPORTED: a joint map of several windows or a view into one (as lvba_voxmap_find_planes). */
+#define LVBA_REG_CONVERGED 0
+#define LVBA_REG_MAX_ITERATIONS 1
+#define LVBA_REG_TOO_FEW_INLIERS 2
+#define LVBA_REG_DEGENERATE 3
+typedef struct lvba_register_opts {
+    int32_t max_iterations; /* default 30 */
+    double max_distance;    /* inlier gate on |r| in metres (default 0.1) */
+    int64_t min_inliers;    /* default 100 */
+    double min_eigenvalue;  /* of H / inliers (default 1e-3) */
+    double tol_rot, tol_pos; /* rad, m (default 1e-6 each) */
+    lvba_loss loss;         /* default LVBA_LOSS_TRIVIAL */
+} lvba_register_opts;
+typedef struct lvba_register_result {
+    int32_t status, iterations;
+    int64_t inliers, points;
+    double cost_first, cost_last, rmse, min_eigenvalue;
+} lvba_register_result;
+void lvba_register_default_opts(lvba_register_opts *o);
+int32_t lvba_register_linearize(lvba_voxmap_t map, lvba_scans_t scans, int32_t n, const int32_t *frames, const double *poses,
+                                const lvba_register_opts *o, double *H, double *g, double *cost, int64_t *inliers);
+int32_t lvba_register_scans(lvba_voxmap_t map, lvba_scans_t scans, int32_t n, const int32_t *frames, const double *poses_init,
+                            const lvba_register_opts *o, double *poses_out, double *information, lvba_register_result *results);
+
 #ifdef __cplusplus
 }
 #endif
