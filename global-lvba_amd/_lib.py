@@ -30,6 +30,8 @@ SYMBOLS = [
     "lvba_colorize_download", "lvba_colorize_profile", "lvba_colorize_destroy",
     "lvba_mapq_default_opts", "lvba_mapq_scans", "lvba_mapq_points",
     "lvba_register_default_opts", "lvba_register_linearize", "lvba_register_scans",
+    "lvba_submaps_build", "lvba_submaps_count", "lvba_submaps_find_planes", "lvba_register_linearize_submaps",
+    "lvba_register_scans_submaps", "lvba_loop_default_opts", "lvba_loop_candidates",
 ]
 
 OK, ERR_ARG, ERR_DEVICE, ERR_NOMEM, ERR_UNSUPPORTED, ERR_DIST, ERR_STATE = 0, -1, -2, -3, -4, -5, -6
@@ -154,6 +156,15 @@ class RegisterResult(C.Structure):
 
     def as_dict(self):
         return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class LoopOpts(C.Structure):
+    _fields_ = [("submap_size", C.c_int32), ("min_gap", C.c_int32), ("max_per_frame", C.c_int32), ("query_stride", C.c_int32),
+                ("radius", C.c_double)]
+
+
+class LoopCandidate(C.Structure):
+    _fields_ = [("query", C.c_int32), ("submap", C.c_int32), ("ref", C.c_int32), ("pad", C.c_int32), ("distance", C.c_double)]
 
 
 class VoxelOpts(C.Structure):
@@ -349,6 +360,17 @@ def load():
                                             C.c_void_p, C.c_void_p]
     lib.lvba_register_scans.argtypes = [H, H, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(RegisterOpts), C.c_void_p, C.c_void_p,
                                         C.c_void_p]
+    lib.lvba_submaps_build.argtypes = [H, C.c_int32, C.c_int32, C.c_int32, f64p, C.POINTER(VoxelOpts), C.POINTER(H)]
+    lib.lvba_submaps_count.argtypes = [H, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.lvba_submaps_find_planes.argtypes = [H, C.c_int64, C.c_void_p, f64p, f64p, u8p]
+    lib.lvba_register_linearize_submaps.argtypes = [H, H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RegisterOpts), C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.lvba_register_scans_submaps.argtypes = [H, H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RegisterOpts), C.c_void_p,
+                                                C.c_void_p, C.c_void_p]
+    lib.lvba_loop_default_opts.argtypes = [C.POINTER(LoopOpts)]
+    lib.lvba_loop_default_opts.restype = None
+    lib.lvba_loop_candidates.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.POINTER(LoopOpts), C.c_int64, C.c_void_p,
+                                         C.POINTER(C.c_int64)]
     lib.lvba_scans_info.argtypes = [H, C.POINTER(C.c_int32), C.c_void_p]
     lib.lvba_scans_download.argtypes = [H, C.c_int32, np.ctypeslib.ndpointer(np.float32, flags="C")]
     for name in SYMBOLS:

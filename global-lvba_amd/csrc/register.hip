@@ -1,5 +1,5 @@
 // register.hip -- scan-to-map registration: point-to-plane Gauss-Newton of a batch of (scan, initial pose) jobs against a voxel
-// plane map, in lock-step over the batch.  The per-point rule and the per-job step are register_device.h (also compiled for the
+// plane map -- or, job by job, against one submap of a submap set (lvba_register_*_submaps) --, in lock-step over the batch.  The per-point rule and the per-job step are register_device.h (also compiled for the
 // host by the tests); the plane association is the map's own lookup (voxel_lookup.h); definitions in include/lvba_hip.h and
 // DESIGN.md §10c.
 //
@@ -64,10 +64,13 @@ __device__ __forceinline__ double wave_sum_to_lane63(double v)
     return v;
 }
 
-// part [jobs][gridDim.x][REG_NS]
+// part [jobs][gridDim.x][REG_NS].  SUBMAPS = false: every job against the whole root table (submap unused; the single-map code
+// as it was).  SUBMAPS = true: job k against submap[k] of a submap set: the job's root range is read once, from two uniform
+// addresses, and stays in scalar registers.
+template <bool SUBMAPS>
 __global__ __launch_bounds__(REG_BLOCK) void reg_linearize_kernel(const VoxLookup map, const float *__restrict__ pts,
                                                                   const int64_t *__restrict__ frame_off, const int32_t *__restrict__ frames,
-                                                                  const double *__restrict__ poses,
+                                                                  const int32_t *__restrict__ submap, const double *__restrict__ poses,
                                                                   const lvba_register_result *__restrict__ res, const RegParams o,
                                                                   double *__restrict__ part)
 {
@@ -78,6 +81,12 @@ __global__ __launch_bounds__(REG_BLOCK) void reg_linearize_kernel(const VoxLooku
     const int64_t p0 = frame_off[f], m = frame_off[f + 1] - p0;
     const int nb = reg_blocks(m);
     if ((int)blockIdx.x >= nb) return;
+    int64_t r0 = 0, r1 = map.R;
+    if (SUBMAPS && map.win_r0) {
+        const int w = submap[job];
+        r0 = map.win_r0[w];
+        r1 = map.win_r0[w + 1];
+    }
     double T[12];
 #pragma unroll
     for (int a = 0; a < 12; ++a) T[a] = poses[12 * (int64_t)job + a];
@@ -89,7 +98,7 @@ __global__ __launch_bounds__(REG_BLOCK) void reg_linearize_kernel(const VoxLooku
         const double p[3] = {(double)P[3 * i], (double)P[3 * i + 1], (double)P[3 * i + 2]};
         double w[3], pl[4];
         reg_world(T, p, w);
-        if (vox_find_plane(w, map.vs, map.R, map.root_key, map.mask, map.rootinfo, map.plane_first, map.plane, pl))
+        if (vox_find_plane(w, map.vs, r0, r1, map.root_key, map.mask, map.rootinfo, map.plane_first, map.plane, pl))
             reg_point(T, p, w, pl, o, s);
     }
 #pragma unroll
@@ -162,10 +171,10 @@ struct PinnedWords { // the iteration words in the host's pinned memory
     ~PinnedWords() { if (p) PinnedCache::get().release(p); }
 };
 
-// Both entry points.  sums_only: one linearisation, H / g / cost / inliers out; else the iteration, poses_out / information /
-// results out.
-int32_t reg_run(lvba_voxmap_t map, lvba_scans_t sc, int32_t n, const int32_t *frames, const double *poses, const lvba_register_opts *opts,
-                bool sums_only, double *H, double *g, double *cost, int64_t *inliers, double *poses_out, lvba_register_result *results)
+// All entry points.  sums_only: one linearisation, H / g / cost / inliers out; else the iteration, poses_out / information /
+// results out.  submaps: the map is a submap set and job k works against submap[k] (else a map of one window, submap unused).
+int32_t reg_run(lvba_voxmap_t map, lvba_scans_t sc, int32_t n, const int32_t *frames, const int32_t *submap, bool submaps,
+                const double *poses, const lvba_register_opts *opts, bool sums_only, double *H, double *g, double *cost, int64_t *inliers, double *poses_out, lvba_register_result *results)
 {
     if (!map || !sc || n < 0) return lvba_fail(LVBA_ERR_ARG, "null map or scans, or n < 0");
     lvba_register_opts o;
@@ -173,14 +182,16 @@ int32_t reg_run(lvba_voxmap_t map, lvba_scans_t sc, int32_t n, const int32_t *fr
     TRY(check_opts(opts, o, par));
     VoxLookup tab;
     int device = 0;
-    TRY(lvba_voxmap_lookup_tables(map, &tab, &device));
+    TRY(submaps ? lvba_voxmap_lookup_tables_windows(map, &tab, &device) : lvba_voxmap_lookup_tables(map, &tab, &device));
     if (device != sc->device) return lvba_fail(LVBA_ERR_ARG, "the map is on device %d, the scans on device %d", device, sc->device);
     if (n == 0) return LVBA_OK;
-    if (!frames || !poses || (sums_only ? !(H && g && cost && inliers) : !(poses_out && results)))
+    if (!frames || !poses || (submaps && !submap) || (sums_only ? !(H && g && cost && inliers) : !(poses_out && results)))
         return lvba_fail(LVBA_ERR_ARG, "null argument");
     int max_blocks = 1;
     for (int32_t k = 0; k < n; ++k) {
         if (frames[k] < 0 || frames[k] >= sc->n_frames) return lvba_fail(LVBA_ERR_ARG, "job %d: frame %d of %d", k, frames[k], sc->n_frames);
+        if (submaps && (submap[k] < 0 || submap[k] >= tab.n_windows))
+            return lvba_fail(LVBA_ERR_ARG, "job %d: submap %d of %d", k, submap[k], tab.n_windows);
         for (int a = 0; a < 12; ++a)
             if (!std::isfinite(poses[12 * (size_t)k + a])) return lvba_fail(LVBA_ERR_ARG, "job %d: non-finite pose", k);
         max_blocks = std::max(max_blocks, reg_blocks(sc->frame_off[frames[k] + 1] - sc->frame_off[frames[k]]));
@@ -201,7 +212,11 @@ int32_t reg_run(lvba_voxmap_t map, lvba_scans_t sc, int32_t n, const int32_t *fr
         hres[k].status = REG_RUNNING;
         hres[k].points = sc->frame_off[frames[k] + 1] - sc->frame_off[frames[k]];
     }
-    DevBuf d_frames(s), d_poses(s), d_res(s), d_part(s), d_sums(s);
+    DevBuf d_frames(s), d_poses(s), d_res(s), d_part(s), d_sums(s), d_submap(s);
+    if (submaps) {
+        HIPCHK(d_submap.alloc(4 * (size_t)n));
+        HIPCHK(hipMemcpyAsync(d_submap.p, submap, 4 * (size_t)n, hipMemcpyHostToDevice, s));
+    }
     HIPCHK(d_frames.alloc(4 * (size_t)n)); HIPCHK(d_poses.alloc(96 * (size_t)n)); HIPCHK(d_res.alloc(sizeof(lvba_register_result) * (size_t)n));
     HIPCHK(d_part.alloc(8 * (size_t)REG_NS * (size_t)max_blocks * (size_t)n)); HIPCHK(d_sums.alloc(8 * (size_t)REG_NS * (size_t)n));
     HIPCHK(hipMemcpyAsync(d_frames.p, frames, 4 * (size_t)n, hipMemcpyHostToDevice, s));
@@ -209,8 +224,8 @@ int32_t reg_run(lvba_voxmap_t map, lvba_scans_t sc, int32_t n, const int32_t *fr
     HIPCHK(hipMemcpyAsync(d_res.p, hres.data(), sizeof(lvba_register_result) * (size_t)n, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemsetAsync(d_sums.p, 0, 8 * (size_t)REG_NS * (size_t)n, s));
     for (int it = 0; it < max_it; ++it) {
-        reg_linearize_kernel<<<dim3((unsigned)max_blocks, (unsigned)n), REG_BLOCK, 0, s>>>(
-            tab, sc->d_pts, sc->d_frame_off, d_frames.as<int32_t>(), d_poses.as<double>(), d_res.as<lvba_register_result>(), par,
+        (submaps ? reg_linearize_kernel<true> : reg_linearize_kernel<false>)<<<dim3((unsigned)max_blocks, (unsigned)n), REG_BLOCK, 0, s>>>(
+            tab, sc->d_pts, sc->d_frame_off, d_frames.as<int32_t>(), d_submap.as<int32_t>(), d_poses.as<double>(), d_res.as<lvba_register_result>(), par,
             d_part.as<double>());
         HIPCHK(hipGetLastError());
         reg_step_kernel<<<(unsigned)n, 64, 0, s>>>(max_blocks, sc->d_frame_off, d_frames.as<int32_t>(), d_part.as<double>(), par,
@@ -258,7 +273,7 @@ extern "C" void lvba_register_default_opts(lvba_register_opts *o)
 extern "C" int32_t lvba_register_linearize(lvba_voxmap_t map, lvba_scans_t scans, int32_t n, const int32_t *frames, const double *poses,
                                            const lvba_register_opts *opts, double *H, double *g, double *cost, int64_t *inliers)
 {
-    return reg_run(map, scans, n, frames, poses, opts, true, H, g, cost, inliers, nullptr, nullptr);
+    return reg_run(map, scans, n, frames, nullptr, false, poses, opts, true, H, g, cost, inliers, nullptr, nullptr);
 }
 
 extern "C" int32_t lvba_register_scans(lvba_voxmap_t map, lvba_scans_t scans, int32_t n, const int32_t *frames, const double *poses_init,
@@ -266,5 +281,21 @@ extern "C" int32_t lvba_register_scans(lvba_voxmap_t map, lvba_scans_t scans, in
                                        lvba_register_result *results)
 {
     if (n > 0 && !information) return lvba_fail(LVBA_ERR_ARG, "null argument");
-    return reg_run(map, scans, n, frames, poses_init, opts, false, information, nullptr, nullptr, nullptr, poses_out, results);
+    return reg_run(map, scans, n, frames, nullptr, false, poses_init, opts, false, information, nullptr, nullptr, nullptr, poses_out, results);
+}
+
+extern "C" int32_t lvba_register_linearize_submaps(lvba_voxmap_t submaps, lvba_scans_t scans, int32_t n, const int32_t *frames,
+                                                   const int32_t *submap, const double *poses, const lvba_register_opts *opts, double *H,
+                                                   double *g, double *cost, int64_t *inliers)
+{
+    return reg_run(submaps, scans, n, frames, submap, true, poses, opts, true, H, g, cost, inliers, nullptr, nullptr);
+}
+
+extern "C" int32_t lvba_register_scans_submaps(lvba_voxmap_t submaps, lvba_scans_t scans, int32_t n, const int32_t *frames,
+                                               const int32_t *submap, const double *poses_init, const lvba_register_opts *opts,
+                                               double *poses_out, double *information, lvba_register_result *results)
+{
+    if (n > 0 && !information) return lvba_fail(LVBA_ERR_ARG, "null argument");
+    return reg_run(submaps, scans, n, frames, submap, true, poses_init, opts, false, information, nullptr, nullptr, nullptr, poses_out,
+                   results);
 }

@@ -25,9 +25,11 @@ __device__ __forceinline__ void octants_of(const double pw[3], const int64_t k[3
     }
 }
 
-// The searchable part of a map of ONE window (a joint map of several windows holds a key once per window and has no lookup):
-// R roots sorted by packed key; per root its state and split bits, the mask of octant slots that hold a plane and the index of
-// its first plane; per plane node centre (3) and normal (3).
+// The searchable part of a map: R roots; per root its state and split bits, the mask of octant slots that hold a plane and the
+// index of its first plane; per plane node centre (3) and normal (3).  A map of ONE window has its roots sorted by packed key
+// (win_r0 = nullptr, n_windows = 1: the range to search is [0, R)).  A joint map of several windows (a submap set) holds a key
+// once per window, window-major: window w's roots are [win_r0[w], win_r0[w + 1]) (device array of n_windows + 1 entries),
+// sorted by key inside the range; plane indices stay those of the whole map.
 struct VoxLookup {
     double vs = 0.0;
     int64_t R = 0;
@@ -35,11 +37,13 @@ struct VoxLookup {
     const uint32_t *rootinfo = nullptr;
     const int32_t *plane_first = nullptr;
     const double *plane = nullptr;
+    const int64_t *win_r0 = nullptr;
+    int32_t n_windows = 1;
 };
 
-// The plane (unit normal n, offset d: n . x + d = 0) the world point pw falls on; false: none (no root, a dropped or empty
-// octant, a degenerate normal, a non-finite or out-of-range point).
-__device__ __forceinline__ bool vox_find_plane(const double pw[3], double vs, int64_t R, const uint64_t *__restrict__ root_key,
+// The plane (unit normal n, offset d: n . x + d = 0) the world point pw falls on, among the roots [r0, r1) (a map of one
+// window: [0, R)); false: none (no root, a dropped or empty octant, a degenerate normal, a non-finite or out-of-range point).
+__device__ __forceinline__ bool vox_find_plane(const double pw[3], double vs, int64_t r0, int64_t r1, const uint64_t *__restrict__ root_key,
                                                const uint64_t *__restrict__ mask, const uint32_t *__restrict__ rootinfo,
                                                const int32_t *__restrict__ plane_first, const double *__restrict__ plane, double o[4])
 {
@@ -47,12 +51,12 @@ __device__ __forceinline__ bool vox_find_plane(const double pw[3], double vs, in
     int64_t k[3];
     if (!root_key_of(pw, vs, k)) return false;
     const uint64_t key = pack_key(k);
-    int64_t lo = 0, hi = R;
+    int64_t lo = r0, hi = r1;
     while (lo < hi) {
         const int64_t mid = (lo + hi) >> 1;
         if (root_key[mid] < key) lo = mid + 1; else hi = mid;
     }
-    if (lo >= R || root_key[lo] != key) return false;
+    if (lo >= r1 || root_key[lo] != key) return false;
     const uint32_t info = rootinfo[lo];
     const int st0 = info & 0xff;
     int o1, o2;
@@ -78,3 +82,6 @@ struct lvba_voxmap_s;
 // The tables of a map and its device and stream (voxelize.hip).  LVBA_ERR_UNSUPPORTED for a joint map of several windows or a
 // view into one.  An empty map gives R = 0.
 int32_t lvba_voxmap_lookup_tables(const lvba_voxmap_s *h, lvba::VoxLookup *out, int *device);
+// The same for a submap set: a joint map of several windows comes with its window table (win_r0, n_windows); a map of one
+// window is a set of one submap (win_r0 = nullptr).  LVBA_ERR_UNSUPPORTED for a view.
+int32_t lvba_voxmap_lookup_tables_windows(const lvba_voxmap_s *h, lvba::VoxLookup *out, int *device);

@@ -133,6 +133,20 @@ __global__ void vox_win_first_kernel(int64_t R, const uint32_t *__restrict__ roo
     const int w = seg_frame[root_seg[r]] / ws;
     if (r == 0 || seg_frame[root_seg[r - 1]] / ws != w) { win_v0[w] = vox_first[r]; win_f0[w] = fac_first[r]; }
 }
+// first root of every window, win_r0[w] for w = 0 .. n_win: the first root whose window is >= w (a window without roots begins
+// where the next one begins; win_r0[n_win] = R).  The roots are window-major, so this is a search per entry.
+__global__ void vox_win_roots_kernel(int64_t R, int n_win, const uint32_t *__restrict__ root_seg, const int32_t *__restrict__ seg_frame,
+                                     int ws, int64_t *__restrict__ win_r0)
+{
+    const int w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w > n_win) return;
+    int64_t lo = 0, hi = R;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (seg_frame[root_seg[mid]] / ws < w) lo = mid + 1; else hi = mid;
+    }
+    win_r0[w] = lo;
+}
 // The build sizes its next buffers and launches from counts the device has just formed.  Every such read used to be a
 // synchronous copy of its own (sixteen blocking calls per map); now one single-workgroup kernel writes the words of up to six
 // device locations into a slot of the process-wide pinned stage (mempool.h) and the host waits for the stream ONCE per decision
@@ -598,17 +612,26 @@ __global__ void vox_root_emit_kernel(int64_t NS, const uint32_t *__restrict__ se
 }
 
 // ---- landmark -> plane lookup (src/lvba_system.cpp:1531-1565) ------------------------------------------------------
+// submap: nullptr (a map of one window: every point searches [0, R)), or the window of every point of a submap set (win_r0,
+// n_win: its window table; an index outside 0 .. n_win - 1 finds nothing)
 __global__ void vox_lookup_kernel(int64_t n, const double *__restrict__ X, double vs, int64_t R,
                                   const uint64_t *__restrict__ root_key, const uint64_t *__restrict__ mask,
                                   const uint32_t *__restrict__ rootinfo, const int32_t *__restrict__ plane_first,
-                                  const double *__restrict__ plane, double *__restrict__ out, uint8_t *__restrict__ valid)
+                                  const double *__restrict__ plane, const int32_t *__restrict__ submap,
+                                  const int64_t *__restrict__ win_r0, int n_win, double *__restrict__ out, uint8_t *__restrict__ valid)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     double *o = out + 4 * i;
     const double pw[3] = {X[3 * i], X[3 * i + 1], X[3 * i + 2]};
     double pl[4];
-    const bool found = vox_find_plane(pw, vs, R, root_key, mask, rootinfo, plane_first, plane, pl); // voxel_lookup.h
+    int64_t r0 = 0, r1 = R;
+    if (submap) {
+        const int w = submap[i];
+        if (w < 0 || w >= n_win) r1 = 0;
+        else if (win_r0) { r0 = win_r0[w]; r1 = win_r0[w + 1]; }
+    }
+    const bool found = vox_find_plane(pw, vs, r0, r1, root_key, mask, rootinfo, plane_first, plane, pl); // voxel_lookup.h
 #pragma unroll
     for (int q = 0; q < 4; ++q) o[q] = found ? pl[q] : 0.0;
     valid[i] = found ? 1 : 0;
@@ -636,8 +659,11 @@ struct lvba_voxmap_s {
     // the range win_v0[w] .. win_v0[w + 1], its factors win_f0[w] .. win_f0[w + 1], pose indices relative to the window's first
     // frame) and the per-window VIEWS into one (lvba_voxmap_window_view: they own nothing).  Neither has a key lookup: the root
     // table of a joint map holds a key once per window.
+    // win_r0[w] .. win_r0[w + 1] are window w's roots in the joint root table, sorted by key: the key lookup of a SUBMAP SET
+    // (lvba_submaps_*, lvba_register_*_submaps) searches that range; d_win_r0 is the device copy.
     int window_size = 0, n_windows = 1;
-    lvba::hvec<int64_t> win_v0, win_f0;
+    lvba::hvec<int64_t> win_v0, win_f0, win_r0;
+    int64_t *d_win_r0 = nullptr;
     bool is_view = false;
 };
 
@@ -651,6 +677,20 @@ int32_t lvba_voxmap_lookup_tables(const lvba_voxmap_s *h, lvba::VoxLookup *out, 
     out->vs = h->opts.voxel_size; out->R = h->info.n_roots;
     out->root_key = h->d_root_key; out->mask = h->d_mask; out->rootinfo = h->d_rootinfo;
     out->plane_first = h->d_plane_first; out->plane = h->d_plane;
+    *device = h->device;
+    return LVBA_OK;
+}
+
+int32_t lvba_voxmap_lookup_tables_windows(const lvba_voxmap_s *h, lvba::VoxLookup *out, int *device)
+{
+    if (!h || !out || !device) return lvba_fail(LVBA_ERR_ARG, "null argument");
+    if (h->is_view) return lvba_fail(LVBA_ERR_UNSUPPORTED, "a view into a joint map is not a submap set");
+    if (h->window_size > 0 && h->info.n_roots > 0 && !h->d_win_r0) return lvba_fail(LVBA_ERR_STATE, "joint map without its window table");
+    out->vs = h->opts.voxel_size; out->R = h->info.n_roots;
+    out->root_key = h->d_root_key; out->mask = h->d_mask; out->rootinfo = h->d_rootinfo;
+    out->plane_first = h->d_plane_first; out->plane = h->d_plane;
+    out->win_r0 = h->window_size > 0 ? h->d_win_r0 : nullptr;
+    out->n_windows = h->n_windows;
     *device = h->device;
     return LVBA_OK;
 }
@@ -797,7 +837,7 @@ extern "C" int32_t lvba_voxmap_destroy(lvba_voxmap_t h)
     if (h->is_view) { delete h; return LVBA_OK; } // a window view of a joint map: the arrays are the joint map's
     (void)hipSetDevice(h->device);
     void *ptrs[] = {h->d_root_key, h->d_mask, h->d_rootinfo, h->d_plane_first, h->d_plane,
-                    h->d_vox_off, h->d_pose_idx, h->d_vox_label, h->d_clusters};
+                    h->d_vox_off, h->d_pose_idx, h->d_vox_label, h->d_clusters, h->d_win_r0};
     for (void *p : ptrs) DevicePool::get().free(p);
     if (h->stream && h->owns_stream) lvba::StreamCache::get().release(h->stream);
     delete h;
@@ -976,8 +1016,8 @@ int32_t voxmap_build_impl(lvba_voxmap_s *h, const lvba_scans_s *sc, int frame_be
     fc.add(&n_planes, plane_first.as<int32_t>() + R, 4);
     fc.add(&V, vox_first.as<int32_t>() + R, 4);
     fc.add(&F, fac_first.as<int64_t>() + R, 8);
-    DevBuf wv(s), wf(s);
-    if (ws) { // where every window's voxels and factors begin
+    DevBuf wv(s), wf(s), wr(s);
+    if (ws) { // where every window's voxels, factors and roots begin
         HIPCHK(wv.alloc(8 * (size_t)n_win)); HIPCHK(wf.alloc(8 * (size_t)n_win));
         HIPCHK(hipMemsetAsync(wv.p, 0xFF, 8 * (size_t)n_win, s)); HIPCHK(hipMemsetAsync(wf.p, 0xFF, 8 * (size_t)n_win, s));
         vox_win_first_kernel<<<grid_for(R, 256), 256, 0, s>>>(R, root_seg.as<uint32_t>(), seg_frame.as<int32_t>(), ws, vox_first.as<int32_t>(),
@@ -986,6 +1026,12 @@ int32_t voxmap_build_impl(lvba_voxmap_s *h, const lvba_scans_s *sc, int frame_be
         h->win_v0.assign((size_t)n_win + 1, 0); h->win_f0.assign((size_t)n_win + 1, 0);
         fc.add(h->win_v0.data(), wv.p, 8 * (size_t)n_win);
         fc.add(h->win_f0.data(), wf.p, 8 * (size_t)n_win);
+        HIPCHK(wr.alloc(8 * ((size_t)n_win + 1)));
+        vox_win_roots_kernel<<<grid_for((int64_t)n_win + 1, 256), 256, 0, s>>>(R, n_win, root_seg.as<uint32_t>(), seg_frame.as<int32_t>(), ws,
+                                                                               wr.as<int64_t>());
+        HIPCHK(hipGetLastError());
+        h->win_r0.assign((size_t)n_win + 1, 0);
+        fc.add(h->win_r0.data(), wr.p, 8 * ((size_t)n_win + 1));
     }
     HIPCHK(fc.run(s)); // the totals and the windows' first voxels / factors in one round trip
     h->info.n_planes = n_planes; h->info.n_voxels = V; h->info.n_factors = F;
@@ -1031,6 +1077,7 @@ int32_t voxmap_build_impl(lvba_voxmap_s *h, const lvba_scans_s *sc, int frame_be
     h->d_pose_idx = (int32_t *)pose_idx.release();
     h->d_vox_label = (int32_t *)vox_label.release();
     h->d_clusters = (double *)clusters.release();
+    h->d_win_r0 = (int64_t *)wr.release();
     return LVBA_OK;
 }
 
@@ -1188,27 +1235,65 @@ extern "C" int32_t lvba_voxmap_to_balm(lvba_voxmap_t h, lvba_balm_t *out)
     return lvba_balm_create_dev(h->n_frames, V, off.data(), idx.data(), h->d_clusters, h->device, out);
 }
 
-extern "C" int32_t lvba_voxmap_find_planes(lvba_voxmap_t h, int64_t n, const double *X, double *plane, uint8_t *valid)
+// submap: nullptr (lvba_voxmap_find_planes), or a window per point (lvba_submaps_find_planes)
+static int32_t find_planes_impl(lvba_voxmap_t h, int64_t n, const int32_t *submap, const double *X, double *plane, uint8_t *valid)
 {
     if (!h || n < 0 || (n > 0 && (!X || !plane || !valid))) return lvba_fail(LVBA_ERR_ARG, "null argument");
     if (n == 0) return LVBA_OK;
-    if (h->is_view || h->window_size > 0)
-        return lvba_fail(LVBA_ERR_UNSUPPORTED, "a joint map of several windows (or a view into one) has no key lookup");
     if (h->info.n_roots == 0) {
         memset(plane, 0, 32 * (size_t)n);
         memset(valid, 0, (size_t)n);
         return LVBA_OK;
     }
     HIPCHK(hipSetDevice(h->device));
-    DevBuf dX(h->stream), dpl(h->stream), dval(h->stream);
+    DevBuf dX(h->stream), dpl(h->stream), dval(h->stream), dsub(h->stream);
     HIPCHK(dX.alloc(24 * (size_t)n)); HIPCHK(dpl.alloc(32 * (size_t)n)); HIPCHK(dval.alloc((size_t)n));
     HIPCHK(hipMemcpyAsync(dX.p, X, 24 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    if (submap) {
+        HIPCHK(dsub.alloc(4 * (size_t)n));
+        HIPCHK(hipMemcpyAsync(dsub.p, submap, 4 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    }
     vox_lookup_kernel<<<grid_for(n, 256), 256, 0, h->stream>>>(n, dX.as<double>(), h->opts.voxel_size, h->info.n_roots,
                                                                h->d_root_key, h->d_mask, h->d_rootinfo, h->d_plane_first,
-                                                               h->d_plane, dpl.as<double>(), dval.as<uint8_t>());
+                                                               h->d_plane, submap ? dsub.as<int32_t>() : nullptr,
+                                                               h->window_size > 0 ? h->d_win_r0 : nullptr, h->n_windows,
+                                                               dpl.as<double>(), dval.as<uint8_t>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(plane, dpl.p, 32 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(valid, dval.p, (size_t)n, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return LVBA_OK;
+}
+
+extern "C" int32_t lvba_voxmap_find_planes(lvba_voxmap_t h, int64_t n, const double *X, double *plane, uint8_t *valid)
+{
+    if (!h || n < 0 || (n > 0 && (!X || !plane || !valid))) return lvba_fail(LVBA_ERR_ARG, "null argument");
+    if (n == 0) return LVBA_OK;
+    if (h->is_view || h->window_size > 0)
+        return lvba_fail(LVBA_ERR_UNSUPPORTED, "a joint map of several windows (or a view into one) has no key lookup");
+    return find_planes_impl(h, n, nullptr, X, plane, valid);
+}
+
+// ---- submap sets: the joint map of the submaps of submap_size frames, with a key lookup per submap ------------------
+extern "C" int32_t lvba_submaps_build(lvba_scans_t scans, int32_t frame_begin, int32_t n_frames, int32_t submap_size, const double *poses,
+                                      const lvba_voxel_opts *opts, lvba_voxmap_t *out)
+{
+    return lvba_voxmap_build_scans_joint(scans, frame_begin, n_frames, submap_size, poses, opts, nullptr, out);
+}
+
+extern "C" int32_t lvba_submaps_count(lvba_voxmap_t submaps, int32_t *n_submaps, int32_t *submap_size)
+{
+    if (!submaps) return lvba_fail(LVBA_ERR_ARG, "null handle");
+    if (submaps->is_view) return lvba_fail(LVBA_ERR_UNSUPPORTED, "a view into a joint map is not a submap set");
+    if (n_submaps) *n_submaps = submaps->n_windows;
+    if (submap_size) *submap_size = submaps->window_size > 0 ? submaps->window_size : submaps->n_frames;
+    return LVBA_OK;
+}
+
+extern "C" int32_t lvba_submaps_find_planes(lvba_voxmap_t submaps, int64_t n, const int32_t *submap, const double *X, double *plane,
+                                            uint8_t *valid)
+{
+    if (submaps && submaps->is_view) return lvba_fail(LVBA_ERR_UNSUPPORTED, "a view into a joint map is not a submap set");
+    if (n > 0 && !submap) return lvba_fail(LVBA_ERR_ARG, "null argument");
+    return find_planes_impl(submaps, n, submap, X, plane, valid);
 }

@@ -308,6 +308,26 @@ def map_quality(scans, after, before=None, **kw):
             "before": None if before is None else map_quality_scans(scans, before, **kw)}
 
 
+def registration_prior(i, j, pose_i, pose_j, information, rmse, status, sigma=None):
+    """The balm.Prior.relative(i, j) a registration of frame j gives against reference frame i (loop_closure_prior has the
+    derivation): measurement T_i^-1 T_j(registered), sqrt_info the upper Cholesky factor of M H M^T / sigma^2 with
+    M = diag(I, R_i^T) and sigma = rmse unless given; a registration that ended neither converged nor at max_iterations, or whose
+    information is not positive definite, constrains nothing (sqrt_info = 0)."""
+    from .balm import Prior
+    pose_i, Tj = np.asarray(pose_i, np.float64).reshape(12), np.asarray(pose_j, np.float64).reshape(12)
+    Ri, pi = pose_i[:9].reshape(3, 3), pose_i[9:]
+    meas = np.r_[(Ri.T @ Tj[:9].reshape(3, 3)).reshape(9), Ri.T @ (Tj[9:] - pi)]
+    s2 = float(rmse) ** 2 if sigma is None else float(sigma) ** 2
+    M = np.zeros((6, 6))
+    M[:3, :3], M[3:, 3:] = np.eye(3), Ri.T
+    info = M @ np.asarray(information, np.float64).reshape(6, 6) @ M.T / s2 if s2 > 0 and status in (0, 1) else np.zeros((6, 6))
+    try:
+        sqrt_info = np.linalg.cholesky(info).T
+    except np.linalg.LinAlgError:
+        sqrt_info = np.zeros((6, 6))   # a failed registration constrains nothing
+    return Prior.relative(int(i), int(j), meas, sqrt_info=sqrt_info)
+
+
 def loop_closure_prior(scans, poses, map_frames, query_frame, ref_frame=None, voxel_size=1.0, eigen_ratio_array=None, sigma=None,
                        **opts):
     """A relative pose constraint from a revisit: the map of the frames `map_frames` (a contiguous ascending run of frame
@@ -322,7 +342,6 @@ def loop_closure_prior(scans, poses, map_frames, query_frame, ref_frame=None, vo
     sigma^2, the variance of a point-to-plane distance in m^2 (default: the registration's rmse^2), to make 1/2 |L r|^2 the
     negative log-likelihood; sqrt_info is the upper Cholesky factor L, L^T L = M H M^T / sigma^2.
     eigen_ratio_array: default register.STRICT_RATIO (the reason is DESIGN.md §10c)."""
-    from .balm import Prior
     from .register import STRICT_RATIO
     mf = [int(f) for f in map_frames]
     if not mf or mf != list(range(mf[0], mf[0] + len(mf))):
@@ -334,18 +353,68 @@ def loop_closure_prior(scans, poses, map_frames, query_frame, ref_frame=None, vo
     with scans.voxel_map(x[mf[0]:mf[0] + len(mf)], voxel_size, STRICT_RATIO if eigen_ratio_array is None else eigen_ratio_array,
                          frame_begin=mf[0], n_frames=len(mf)) as m:
         reg = m.register(scans, [j], x[j:j + 1], **opts)
-    Ri, pi = x[i, :9].reshape(3, 3), x[i, 9:]
-    Tj = reg["poses"][0]
-    meas = np.r_[(Ri.T @ Tj[:9].reshape(3, 3)).reshape(9), Ri.T @ (Tj[9:] - pi)]
-    s2 = float(reg["rmse"][0]) ** 2 if sigma is None else float(sigma) ** 2
-    M = np.zeros((6, 6))
-    M[:3, :3], M[3:, 3:] = np.eye(3), Ri.T
-    info = M @ reg["information"][0] @ M.T / s2 if s2 > 0 and reg["status"][0] in (0, 1) else np.zeros((6, 6))
-    try:
-        sqrt_info = np.linalg.cholesky(info).T
-    except np.linalg.LinAlgError:
-        sqrt_info = np.zeros((6, 6))   # a failed registration constrains nothing
-    return Prior.relative(i, j, meas, sqrt_info=sqrt_info), reg
+    return registration_prior(i, j, x[i], reg["poses"][0], reg["information"][0], reg["rmse"][0], reg["status"][0], sigma), reg
+
+
+def pose_correction(T0, T):
+    """(rotation angle of R0^T R [rad], |t - t0| [m]) between a start pose and a registered one."""
+    T0, T = np.asarray(T0, np.float64).reshape(12), np.asarray(T, np.float64).reshape(12)
+    dR = T0[:9].reshape(3, 3).T @ T[:9].reshape(3, 3)
+    return float(np.arccos(np.clip((np.trace(dR) - 1.0) / 2.0, -1.0, 1.0))), float(np.linalg.norm(T[9:] - T0[9:]))
+
+
+def loop_acceptance(status, inliers, points, rmse, rot, trans, min_inlier_frac=0.3, max_rmse=None, max_rot=None, max_trans=None):
+    """The acceptance rule of find_loop_closures on one registered candidate: (accepted, reason).  Accepted iff the registration
+    converged, inliers >= min_inlier_frac * points, rmse <= max_rmse, and the correction from the start to the registered pose is
+    within max_rot [rad] / max_trans [m] (each bound only when given).  reason: None, or the first clause that failed --
+    "status", "inliers", "rmse", "correction"."""
+    if int(status) != 0:
+        return False, "status"
+    if not inliers >= min_inlier_frac * points:
+        return False, "inliers"
+    if max_rmse is not None and not rmse <= max_rmse:
+        return False, "rmse"
+    if (max_rot is not None and not rot <= max_rot) or (max_trans is not None and not trans <= max_trans):
+        return False, "correction"
+    return True, None
+
+
+def find_loop_closures(scans, poses, submap_size=10, voxel_size=1.0, eigen_ratio_array=None, radius=5.0, min_gap=50, max_per_frame=2,
+                       query_stride=1, min_inlier_frac=0.3, max_rmse=None, max_rot=None, max_trans=None, sigma=None, **register_opts):
+    """Loop closures of a trajectory, found and verified on the GPU: the submap set of all frames of `scans` at their current
+    `poses` [n,12] is built in one pass (Scans.submaps, eigen ratios register.STRICT_RATIO by default: DESIGN.md §10c), the
+    candidates (query frame, submap, nearest frame ref) come from the poses alone (register.loop_candidates: radius, min_gap,
+    max_per_frame, query_stride), and ALL candidates are registered in one call, each query frame from its current pose against
+    its submap (SubmapSet.register, register_opts: its options).  A candidate is accepted by loop_acceptance.
+    Returns (priors, report): priors = a balm.Prior.relative(ref, query) per accepted candidate, measurement and sqrt_info as
+    loop_closure_prior builds them (registration_prior; sigma as there); report = one dict per candidate: query, submap, ref,
+    distance, the registration's fields (pose, information, status, status_name, iterations, inliers, points, cost_first,
+    cost_last, rmse, min_eigenvalue), rot / trans (the correction), accepted and reason (None when accepted)."""
+    from .register import STRICT_RATIO, loop_candidates
+    x = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
+    cand = loop_candidates(x, submap_size=submap_size, min_gap=min_gap, max_per_frame=max_per_frame, query_stride=query_stride,
+                           radius=radius)
+    priors, report = [], []
+    if cand["count"] == 0:
+        return priors, report
+    q = cand["query"]
+    with scans.submaps(x, submap_size, voxel_size, STRICT_RATIO if eigen_ratio_array is None else eigen_ratio_array) as sm:
+        reg = sm.register(scans, q, cand["submap"], x[q], **register_opts)
+    for k in range(len(q)):
+        rot, trans = pose_correction(x[q[k]], reg["poses"][k])
+        ok, why = loop_acceptance(reg["status"][k], reg["inliers"][k], reg["points"][k], reg["rmse"][k], rot, trans, min_inlier_frac,
+                                  max_rmse, max_rot, max_trans)
+        r = dict(query=int(q[k]), submap=int(cand["submap"][k]), ref=int(cand["ref"][k]), distance=float(cand["distance"][k]),
+                 pose=reg["poses"][k].copy(), information=reg["information"][k].copy(), status_name=reg["status_name"][k],
+                 rot=rot, trans=trans, accepted=ok, reason=why)
+        for f in ("status", "iterations", "inliers", "points"):
+            r[f] = int(reg[f][k])
+        for f in ("cost_first", "cost_last", "rmse", "min_eigenvalue"):
+            r[f] = float(reg[f][k])
+        report.append(r)
+        if ok:
+            priors.append(registration_prior(r["ref"], r["query"], x[r["ref"]], r["pose"], r["information"], r["rmse"], r["status"], sigma))
+    return priors, report
 
 
 _map_quality = map_quality   # run_full_pipeline / run_dataset have a keyword of that name
@@ -401,7 +470,7 @@ def run_lidar_ba(scans, poses, priors=None, window_loss=None, stage_loss=None, h
 
 def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, tci, intr, width, height, keypoints, pairs,
                       matches, enable_lidar_ba=True, enable_visual_ba=True, device=0, images=None, lidar_priors=None,
-                      window_loss=None, stage_loss=None, camera_priors=None, map_quality=False, **cfg):
+                      window_loss=None, stage_loss=None, camera_priors=None, map_quality=False, loop_closures=None, **cfg):
     """LvbaSystem::runFullPipeline (src/lvba_system.cpp:136-142) on in-memory data: clouds = body-frame [n_i, >=3] float32
     arrays, poses [n,12] = x_buf_ (T_world<-imu), image_poses [m,12] the image poses from the odometry.  cfg: DEFAULTS' keys
     (visual_loss, colorize_leaf among them).  images: None, or the images ([m,H,W,3] BGR uint8 or a callable k -> [H,W,3]):
@@ -411,7 +480,10 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
     (Scans.lidar_ba(priors=...)).  window_loss / stage_loss: robust losses of the LiDAR BA (run_lidar_ba).  camera_priors:
     priors on the cameras of the visual stage (run_visual_ba_with_lidar_assist; None: none).  map_quality: True, or a dict of
     mapq.map_quality_scans' keywords: the output also holds map_quality = {"after": ..., "before": ...}, the mean map entropy and
-    mean plane variance of the scans at the refined and at the original poses (off by default: nothing is launched)."""
+    mean plane variance of the scans at the refined and at the original poses (off by default: nothing is launched).
+    loop_closures: None (off: nothing is launched), True, or a dict of find_loop_closures' keywords: loop closures are detected on
+    the input poses before the LiDAR stage, the accepted priors are appended to lidar_priors and the output holds
+    loop_closures = the report."""
     if images is not None and not enable_visual_ba:
         raise ValueError("colouring the map needs the cameras of the visual stage (enable_visual_ba=True)")
     c = dict(DEFAULTS); c.update(cfg)
@@ -419,6 +491,9 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
     out = dict(poses_before=x_orig)
     with Scans(clouds, device=device) as scans:
         x_opt = x_orig
+        if loop_closures:
+            found, out["loop_closures"] = find_loop_closures(scans, x_orig, **(dict(loop_closures) if isinstance(loop_closures, dict) else {}))
+            lidar_priors = list(lidar_priors or []) + found if found or lidar_priors is not None else None
         if enable_lidar_ba:
             x_opt, report = run_lidar_ba(scans, x_orig, priors=lidar_priors, window_loss=window_loss, stage_loss=stage_loss, **c)
             out["lidar_report"] = report
@@ -470,7 +545,7 @@ def extrinsics_from_config(Rcl, Pcl, extrinsic_R, extrinsic_T):
 
 
 def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrinsic_R=np.eye(3), extrinsic_T=np.zeros(3),
-                image_sample_step=1, out_dir=None, device=0, colorize=False, map_quality=False, **cfg):
+                image_sample_step=1, out_dir=None, device=0, colorize=False, map_quality=False, loop_closures=None, **cfg):
     """initFromDatasetIO + runFullPipeline on a dataset directory; with out_dir, the refined LiDAR poses (TUM) and the COLMAP
     text files images.txt / points3D.txt the reference writes (src/lvba_system.cpp:2018-2137) are saved there.  images.txt is
     the reference's, character for character (tests/test_ref_system.py).
@@ -482,6 +557,8 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
     XYZRGB layout) and a points3D.txt holding the coloured after-cloud, as the reference writes them.
     map_quality (True or a dict of keywords, as for run_full_pipeline): the output gains map_quality and out_dir gets
     map_quality.json, the two summaries.
+    loop_closures (True or a dict of keywords, as for run_full_pipeline): the output gains loop_closures and out_dir gets
+    loop_closures.json, the report without its arrays.
     cfg as for run_full_pipeline, e.g. visual_loss=REFERENCE_HUBER, window_loss=("cauchy", 0.1), stage_loss=("huber", 0.05),
     camera_priors=lambda cams: lidar_camera_priors(cams, Rci, tci, 1e-3, 0.02)."""
     import os
@@ -501,7 +578,8 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
     out = run_full_pipeline([c[:, :3] for c in ds["clouds"]], ds["poses"], ds["timestamps"], image_ids, image_poses, Rci, tci, intr,
                             width, height, [k[:, :2] for k in kps], [pairs[k] for k in keep], [matches[k] for k in keep],
                             device=device, images=(lambda k: D.read_image_bgr(os.path.join(img_dir, names[k]), width, height))
-                            if colorize else None, **({"map_quality": map_quality} if map_quality else {}), **cfg)
+                            if colorize else None, **({"map_quality": map_quality} if map_quality else {}),
+                            **({"loop_closures": loop_closures} if loop_closures else {}), **cfg)
     out.update(image_ids=image_ids, scan_times=ds["timestamps"])
     if out_dir is not None:
         os.makedirs(out_dir, exist_ok=True)
@@ -521,4 +599,8 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
             with open(os.path.join(out_dir, "map_quality.json"), "w") as f:
                 json.dump({k: None if q is None else {a: b for a, b in q.items() if not isinstance(b, np.ndarray)}
                            for k, q in out["map_quality"].items()}, f, indent=1)
+        if loop_closures:
+            import json
+            with open(os.path.join(out_dir, "loop_closures.json"), "w") as f:
+                json.dump([{a: b for a, b in r.items() if not isinstance(b, np.ndarray)} for r in out["loop_closures"]], f, indent=1)
     return out

@@ -7,8 +7,9 @@ Every point of a scan is taken to the world by the job's pose, associated with t
 VoxelMap.find_planes does it, and contributes its point-to-plane distance r if |r| <= max_distance; the pose is refined by
 Gauss-Newton under the retraction R <- R Exp(theta), t <- t + delta (include/lvba_hip.h has the exact definitions).  Build the
 map with strict eigen ratios (STRICT_RATIO) or set a loss: a map cut with the optimiser's stage-1 ratios admits planes fitted
-through clutter, and plain Gauss-Newton walks away from the true pose on it.  Everything runs in liblvba_hip.so
-on the GPU; this file packs arrays."""
+through clutter, and plain Gauss-Newton walks away from the true pose on it.  A submap set (voxel.SubmapSet, Scans.submaps) holds many
+submaps in one map: its register / linearize take a submap index per job.  loop_candidates finds which frame revisits which
+submap from the poses alone.  Everything runs in liblvba_hip.so on the GPU; this file packs arrays."""
 from __future__ import annotations
 
 import ctypes as C
@@ -48,32 +49,76 @@ def _jobs(frames, poses):
     return fr, x
 
 
-def linearize(vmap, scans, frames, poses, **opts):
-    """The sums of one linearisation per job (lvba_register_linearize): dict(H [n,6,6], g [n,6], cost [n], inliers [n])."""
+def _submap(submap, n):
+    sm = np.ascontiguousarray(submap, np.int32).reshape(-1)
+    if len(sm) != n:
+        raise ValueError(f"{len(sm)} submap indices for {n} frames")
+    return sm
+
+
+def linearize(vmap, scans, frames, poses, submap=None, **opts):
+    """The sums of one linearisation per job (lvba_register_linearize): dict(H [n,6,6], g [n,6], cost [n], inliers [n]).
+    submap: None, or one submap index per job for a submap set (lvba_register_linearize_submaps)."""
     fr, x = _jobs(frames, poses)
     n = len(fr)
     H, g, cost, inl = np.zeros((n, 6, 6)), np.zeros((n, 6)), np.zeros(n), np.zeros(n, np.int64)
     o = _opts(opts)
-    L.check(L.load().lvba_register_linearize(vmap._h, scans._h, n, fr.ctypes.data, x.ctypes.data, C.byref(o), H.ctypes.data,
-                                             g.ctypes.data, cost.ctypes.data, inl.ctypes.data))
+    if submap is None:
+        L.check(L.load().lvba_register_linearize(vmap._h, scans._h, n, fr.ctypes.data, x.ctypes.data, C.byref(o), H.ctypes.data,
+                                                 g.ctypes.data, cost.ctypes.data, inl.ctypes.data))
+    else:
+        sm = _submap(submap, n)
+        L.check(L.load().lvba_register_linearize_submaps(vmap._h, scans._h, n, fr.ctypes.data, sm.ctypes.data, x.ctypes.data, C.byref(o),
+                                                         H.ctypes.data, g.ctypes.data, cost.ctypes.data, inl.ctypes.data))
     return dict(H=H, g=g, cost=cost, inliers=inl)
 
 
-def register(vmap, scans, frames, poses, **opts):
+def register(vmap, scans, frames, poses, submap=None, **opts):
     """Register frame frames[k] of `scans` (a voxel.Scans) from poses[k] against `vmap` (a voxel.VoxelMap), all jobs at once
     (lvba_register_scans).  opts: max_iterations, max_distance [m], min_inliers, min_eigenvalue, tol_rot [rad], tol_pos [m],
     loss=(kind, scale [m]).  Returns dict(poses [n,12], information [n,6,6] (H of the last linearisation, tangent order
     (theta, t)), status [n] (a _lib.REG_STATUS key), status_name, iterations, inliers, points, cost_first, cost_last, rmse,
-    min_eigenvalue)."""
+    min_eigenvalue).  submap: None, or one submap index per job for a submap set (lvba_register_scans_submaps)."""
     fr, x = _jobs(frames, poses)
     n = len(fr)
     out, info = np.zeros((n, 12)), np.zeros((n, 6, 6))
     res = (L.RegisterResult * max(n, 1))()
     o = _opts(opts)
-    L.check(L.load().lvba_register_scans(vmap._h, scans._h, n, fr.ctypes.data, x.ctypes.data, C.byref(o), out.ctypes.data,
-                                         info.ctypes.data, C.cast(res, C.c_void_p)))
+    if submap is None:
+        L.check(L.load().lvba_register_scans(vmap._h, scans._h, n, fr.ctypes.data, x.ctypes.data, C.byref(o), out.ctypes.data,
+                                             info.ctypes.data, C.cast(res, C.c_void_p)))
+    else:
+        sm = _submap(submap, n)
+        L.check(L.load().lvba_register_scans_submaps(vmap._h, scans._h, n, fr.ctypes.data, sm.ctypes.data, x.ctypes.data, C.byref(o),
+                                                     out.ctypes.data, info.ctypes.data, C.cast(res, C.c_void_p)))
     d = dict(poses=out, information=info)
     for f, t in L.RegisterResult._fields_:
         d[f] = np.array([getattr(res[k], f) for k in range(n)], np.float64 if t is C.c_double else np.int64)
     d["status_name"] = [L.REG_STATUS.get(int(s), "?") for s in d["status"]]
     return d
+
+
+LOOP_OPTS = ("submap_size", "min_gap", "max_per_frame", "query_stride", "radius")
+
+
+def loop_candidates(poses, device=0, capacity=None, **opts):
+    """Loop-closure candidates from the poses [n,12] alone (lvba_loop_candidates; include/lvba_hip.h has the exact rule): every
+    query frame (a multiple of query_stride) against every submap of submap_size frames that lies at least min_gap frames away
+    and comes within radius [m]; the max_per_frame nearest per query.  Returns dict(query, submap, ref (the submap's nearest
+    frame), distance [m], count), sorted by (query, submap).  capacity: None (all of them), or the number of entries to fetch;
+    count is the true number either way."""
+    x = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
+    o = L.LoopOpts()
+    lib = L.load()
+    lib.lvba_loop_default_opts(C.byref(o))
+    for k, v in opts.items():
+        if k not in LOOP_OPTS:
+            raise TypeError(f"unknown candidate option {k!r}; one of {LOOP_OPTS}")
+        setattr(o, k, type(getattr(o, k))(v))
+    count = C.c_int64()
+    cap = len(x) * max(1, min(32, o.max_per_frame)) if capacity is None else int(capacity)
+    buf = np.zeros(max(cap, 1), np.dtype([("query", "<i4"), ("submap", "<i4"), ("ref", "<i4"), ("pad", "<i4"), ("distance", "<f8")]))
+    L.check(lib.lvba_loop_candidates(int(device), len(x), x.ctypes.data, C.byref(o), cap, buf.ctypes.data, C.byref(count)))
+    got = buf[:min(cap, count.value)]
+    return dict(query=got["query"].copy(), submap=got["submap"].copy(), ref=got["ref"].copy(), distance=got["distance"].copy(),
+                count=count.value, raw=got.copy())

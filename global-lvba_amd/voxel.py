@@ -276,6 +276,12 @@ class Scans:
         n = self.n_frames - frame_begin if n_frames is None else int(n_frames)
         return VoxelMap(None, poses, voxel_size, eigen_ratio_array, min_points, _scans=(self, int(frame_begin), n))
 
+    def submaps(self, poses, submap_size, voxel_size=1.0, eigen_ratio_array=None, frame_begin=0, n_frames=None, min_points=None):
+        """Submap set of frames [frame_begin, frame_begin + n_frames) at `poses` [n_frames, 12]: submaps of submap_size frames
+        (the last may be shorter), all built in one pass (lvba_submaps_build)."""
+        n = self.n_frames - frame_begin if n_frames is None else int(n_frames)
+        return SubmapSet(self, poses, submap_size, voxel_size, eigen_ratio_array, min_points, int(frame_begin), n)
+
 
 class VoxelMap:
     """Adaptive-voxel plane map of a window of scans, resident on a GPU."""
@@ -370,3 +376,50 @@ class VoxelMap:
         """The point-to-plane sums H, g, cost, inliers of frames of `scans` at `poses` against this map (register.linearize)."""
         from .register import linearize
         return linearize(self, scans, frames, poses, **opts)
+
+
+class SubmapSet(VoxelMap):
+    """Many submaps in one map, resident on a GPU, with a key lookup per submap (lvba_submaps_*).  A context manager like
+    VoxelMap; its find_planes / register / linearize take a submap index per point / per job."""
+
+    def __init__(self, scans, poses, submap_size, voxel_size=1.0, eigen_ratio_array=None, min_points=None, frame_begin=0, n_frames=None):
+        self.lib = L.load()
+        o = _opts(voxel_size, eigen_ratio_array, min_points)
+        self.voxel_size = float(voxel_size)
+        self._h = C.c_void_p()
+        n = scans.n_frames - frame_begin if n_frames is None else int(n_frames)
+        poses = np.ascontiguousarray(poses, np.float64).reshape(-1)
+        if poses.size != 12 * n:
+            raise ValueError(f"poses must hold {n} x 12 doubles")
+        L.check(self.lib.lvba_submaps_build(scans._h, int(frame_begin), n, int(submap_size), poses, C.byref(o), C.byref(self._h)))
+        self.n_frames = n
+        info = L.VoxmapInfo()
+        L.check(self.lib.lvba_voxmap_info(self._h, C.byref(info)))
+        self.info = {f: getattr(info, f) for f, _ in info._fields_}
+        ns, ss = C.c_int32(), C.c_int32()
+        L.check(self.lib.lvba_submaps_count(self._h, C.byref(ns), C.byref(ss)))
+        self.n_submaps, self.submap_size = ns.value, ss.value
+
+    def tras_opt(self, *a, **k):
+        raise TypeError("a submap set is not one optimisation problem")
+
+    def find_planes(self, X, submap):
+        """(plane [n,4], valid [n]) for world points X [n,3], point i among the planes of submap[i] (a scalar: all points)."""
+        X = np.ascontiguousarray(X, np.float64).reshape(-1, 3)
+        sm = np.ascontiguousarray(np.broadcast_to(np.asarray(submap, np.int32), (len(X),)))
+        plane = np.zeros((len(X), 4))
+        valid = np.zeros(len(X), np.uint8)
+        L.check(self.lib.lvba_submaps_find_planes(self._h, len(X), sm.ctypes.data, X.reshape(-1), plane.reshape(-1), valid))
+        return plane, valid
+
+    def register(self, scans, frames, submap, poses, **opts):
+        """register.register with job k against submap[k]."""
+        from .register import register
+        return register(self, scans, frames, poses, submap=submap, **opts)
+
+    def linearize(self, scans, frames, submap, poses, **opts):
+        """register.linearize with job k against submap[k]."""
+        from .register import linearize
+        return linearize(self, scans, frames, poses, submap=submap, **opts)
+
+    register_linearize = linearize

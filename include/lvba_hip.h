@@ -820,6 +820,63 @@ int32_t lvba_register_linearize(lvba_voxmap_t map, lvba_scans_t scans, int32_t n
 int32_t lvba_register_scans(lvba_voxmap_t map, lvba_scans_t scans, int32_t n, const int32_t *frames, const double *poses_init,
                             const lvba_register_opts *o, double *poses_out, double *information, lvba_register_result *results);
 
+/* ---- submap sets: many submaps in one map, a key lookup per submap ------------------------------------------
+ *   lvba_submaps_build cuts frames [frame_begin, frame_begin + n_frames) of `scans` into submaps of submap_size frames -- submap
+ *   w holds frames [frame_begin + w S, min(frame_begin + (w + 1) S, frame_begin + n_frames)); the last one may be ragged -- and
+ *   builds all of them in ONE pass at poses [n_frames][12]: every submap's roots and planes are, bit for bit, those of
+ *   lvba_voxmap_build_scans on its own frames.  The handle is a voxel map on a stream of its own: lvba_voxmap_info gives the
+ *   totals, lvba_voxmap_destroy frees it.  submap_size >= n_frames gives one submap (a plain map); a plain map built by
+ *   lvba_voxmap_build* is accepted wherever a submap set is, as a set of one submap.
+ *   lvba_submaps_count: the number of submaps and their size in frames.
+ *   lvba_submaps_find_planes: lvba_voxmap_find_planes with one submap index per point; point i is looked up among the planes of
+ *   submap[i] only.  An index outside 0 .. n_submaps - 1 gives valid = 0 (and a zero plane), not an error.
+ *   lvba_register_linearize_submaps / lvba_register_scans_submaps: lvba_register_linearize / lvba_register_scans where job k
+ *   associates its points with the planes of submap submap[k] only.  Arithmetic, statuses and summation order are those of the
+ *   single-map calls: a job gives the bytes lvba_register_scans gives on the submap's own map, whatever else is in the batch.  A
+ *   submap without planes ends its jobs LVBA_REG_TOO_FEW_INLIERS.
+ *   LVBA_ERR_ARG: as the single-map calls, and a submap index outside 0 .. n_submaps - 1 in a registration job, submap_size < 1.
+ *   LVBA_ERR_UNSUPPORTED: a view into a joint map.  lvba_voxmap_find_planes, lvba_register_linearize and lvba_register_scans
+ *   keep refusing a set of several submaps (LVBA_ERR_UNSUPPORTED): they have no submap to search. */
+int32_t lvba_submaps_build(lvba_scans_t scans, int32_t frame_begin, int32_t n_frames, int32_t submap_size, const double *poses,
+                           const lvba_voxel_opts *opts, lvba_voxmap_t *out);
+int32_t lvba_submaps_count(lvba_voxmap_t submaps, int32_t *n_submaps, int32_t *submap_size);
+int32_t lvba_submaps_find_planes(lvba_voxmap_t submaps, int64_t n, const int32_t *submap, const double *X, double *plane,
+                                 uint8_t *valid);
+int32_t lvba_register_linearize_submaps(lvba_voxmap_t submaps, lvba_scans_t scans, int32_t n, const int32_t *frames,
+                                        const int32_t *submap, const double *poses, const lvba_register_opts *o, double *H, double *g,
+                                        double *cost, int64_t *inliers);
+int32_t lvba_register_scans_submaps(lvba_voxmap_t submaps, lvba_scans_t scans, int32_t n, const int32_t *frames,
+                                    const int32_t *submap, const double *poses_init, const lvba_register_opts *o, double *poses_out,
+                                    double *information, lvba_register_result *results);
+
+/* ---- loop-closure candidates: which frame revisits which submap, from the poses alone -----------------------
+ *   poses [n_frames][12] (R row-major | t); only t is read.  With S = submap_size, submap w holds frames
+ *   F_w = [w S, min((w + 1) S, n_frames)).  A query frame j is a multiple of query_stride.  Every squared distance is
+ *     d2(j, f) = ((dx dx + dy dy) + dz dz),  dx = tx_j - tx_f, ...       in fp64, rounded as written (no fused multiply-add)
+ *   (j, w) is eligible iff |j - f| >= min_gap for EVERY f in F_w, and min over F_w of d2(j, f) <= radius * radius.
+ *   ref is the f in F_w with the smallest d2; on a tie the lowest f.  Per query the max_per_frame eligible submaps with the
+ *   smallest d2 are kept; on a tie the lower w.  The output is sorted by (query, submap); distance = sqrt(d2).
+ *   *count is the true number of candidates even when it exceeds capacity; only the first `capacity` are written.
+ *   No atomics: two calls give the same bytes.  n_frames = 0 gives *count = 0.  Options: NULL takes the defaults with
+ *   submap_size 10.
+ *   LVBA_ERR_ARG: a null pointer, n_frames < 0, capacity < 0, a non-finite pose, submap_size < 1, min_gap < 0, max_per_frame
+ *   outside 1 .. 32, query_stride < 1, radius not finite and > 0. */
+typedef struct lvba_loop_opts {
+    int32_t submap_size;     /* S >= 1 (default 10) */
+    int32_t min_gap;         /* frames (default 50) */
+    int32_t max_per_frame;   /* 1 .. 32 (default 2) */
+    int32_t query_stride;    /* >= 1 (default 1) */
+    double radius;           /* metres, finite and > 0 (default 5) */
+} lvba_loop_opts;
+typedef struct lvba_loop_candidate {
+    int32_t query, submap, ref;
+    int32_t pad;
+    double distance;
+} lvba_loop_candidate;
+void lvba_loop_default_opts(lvba_loop_opts *o);
+int32_t lvba_loop_candidates(int32_t device, int32_t n_frames, const double *poses, const lvba_loop_opts *o, int64_t capacity,
+                             lvba_loop_candidate *out, int64_t *count);
+
 #ifdef __cplusplus
 }
 #endif
