@@ -25,25 +25,9 @@
 #include "balm_math.h"
 #include "visual_loss.h"
 #include "lvba_internal.h"
+#include "wave_ops.h"
 
 namespace lvba {
-
-__device__ __forceinline__ double wave_sum(double x)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-    return x;
-}
-
-// Sum over the 256 threads of a workgroup; result valid in thread 0.  red: >= 4 doubles of LDS.
-__device__ __forceinline__ double block_sum_256(double x, double *red)
-{
-    x = wave_sum(x);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) red[wv] = x;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
 
 // Robust voxel cost (lvba_balm_set_loss): rho(lambda_min) of the handle's loss, w = rho'(lambda_min).  Only the ROBUST instantiations
 // of the kernels below call it: a handle without a loss runs the kernels it always ran, with no loss arithmetic in them.
@@ -151,7 +135,7 @@ __global__ __launch_bounds__(LVBA_CF) void balm_cost_kernel(BalmDev d, const dou
         lam0 = voxel_lambda_min(S);
         if constexpr (ROBUST) { double w; lam0 = voxel_loss(d, lam0, w); }
     }
-    const double tot = block_sum_256(lam0, red);
+    const double tot = block_sum<4>(lam0, red);
     if (tid == 0) chunk_cost[ch] = tot;
 }
 
@@ -227,14 +211,8 @@ __global__ __launch_bounds__(1024) void reduce_chunks_kernel(const double *__res
     }
     for (int64_t i = 4 * n4 + threadIdx.x; i < n; i += 1024) s0 += part[i];
     double s = (s0 + s1) + (s2 + s3);
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int i = 0; i < 16; ++i) t += red[i];
-        out[0] = t;
-    }
+    const double t = block_sum<16>(s, red);
+    if (threadIdx.x == 0) out[0] = t;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -324,7 +302,7 @@ __global__ __launch_bounds__(LVBA_CF, 6) void balm_voxel_kernel(BalmDev d, const
         double *o = d.vrec + 16 * v0;
         for (int f = tid; f < 16 * nv; f += LVBA_CF) o[f] = T[17 * (f >> 4) + (f & 15)];
     }
-    const double tot = block_sum_256(lam0, red);
+    const double tot = block_sum<4>(lam0, red);
     if (tid == 0) chunk_cost[ch] = tot;
 }
 
@@ -465,17 +443,10 @@ __global__ void balm_diag_reduce_kernel(BalmDev d, double *__restrict__ Hblk, do
 // sum over the 16 lanes of a DPP row; every lane of the row gets the total
 __device__ __forceinline__ double row16_sum(double x)
 {
-#define LVBA_ROR_ADD(n)                                                                                \
-    do {                                                                                               \
-        const int lo_ = __builtin_amdgcn_update_dpp(0, __double2loint(x), 0x120 + (n), 0xF, 0xF, false); \
-        const int hi_ = __builtin_amdgcn_update_dpp(0, __double2hiint(x), 0x120 + (n), 0xF, 0xF, false); \
-        x += __hiloint2double(hi_, lo_);                                                               \
-    } while (0)
-    LVBA_ROR_ADD(1);
-    LVBA_ROR_ADD(2);
-    LVBA_ROR_ADD(4);
-    LVBA_ROR_ADD(8);
-#undef LVBA_ROR_ADD
+    x += dpp_f64<0x121, 0xf>(0.0, x); // row_ror:1
+    x += dpp_f64<0x122, 0xf>(0.0, x); // row_ror:2
+    x += dpp_f64<0x124, 0xf>(0.0, x); // row_ror:4
+    x += dpp_f64<0x128, 0xf>(0.0, x); // row_ror:8
     return x;
 }
 
@@ -811,10 +782,8 @@ __global__ __launch_bounds__(128) void retract_q1_kernel(const double *__restric
 #pragma unroll
         for (int r = 0; r < 6; ++r) s += dd[r] * (u * hd[r * 6 + r] * dd[r] - g[6 * (int64_t)j + r]);
     }
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) q1_part[blockIdx.x] = red[0] + red[1];
+    const double t = block_sum<2>(s, red);
+    if (threadIdx.x == 0) q1_part[blockIdx.x] = t;
 }
 
 // q1 numerator: 0.5 * dx . (u * diag(H) .* dx - g)   (bavoxel.hpp:729); out[0] = value
@@ -832,14 +801,8 @@ __global__ __launch_bounds__(1024) void predicted_decrease_kernel(const double *
         const double dgl = Hblk[blk * Bb1 * 36 + r * 6 + r];
         s += dx[a] * (u * dgl * dx[a] - g[a]);
     }
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int i = 0; i < 16; ++i) t += red[i];
-        out[0] = 0.5 * t;
-    }
+    const double t = block_sum<16>(s, red);
+    if (threadIdx.x == 0) out[0] = 0.5 * t;
 }
 
 // The five numbers the LM driver reads after an iteration, written straight into pinned host memory (zero-copy): trial cost,
@@ -868,7 +831,7 @@ __global__ __launch_bounds__(256) void reduce_chunks_groups_kernel(const double 
     const int64_t c0 = gco[blockIdx.x], c1 = gco[blockIdx.x + 1];
     double s = 0.0;
     for (int64_t i = c0 + threadIdx.x; i < c1; i += 256) s += part[i];
-    const double t = block_sum_256(s, red);
+    const double t = block_sum<4>(s, red);
     if (threadIdx.x == 0) out[blockIdx.x] = t;
 }
 // per group: 0.5 * dx . (u_g * diag(H) .* dx - g) over the group's poses (bavoxel.hpp:729)
@@ -887,7 +850,7 @@ __global__ __launch_bounds__(256) void predicted_decrease_groups_kernel(const do
         const double dgl = Hblk[blk * Bb1 * 36 + r * 6 + r];
         s += dx[a] * (ug * dgl * dx[a] - g[a]);
     }
-    const double t = block_sum_256(s, red);
+    const double t = block_sum<4>(s, red);
     if (threadIdx.x == 0) out[blockIdx.x] = 0.5 * t;
 }
 // cur[j] <- trial[j] for the poses of groups whose step was accepted

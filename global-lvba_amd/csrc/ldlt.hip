@@ -30,6 +30,7 @@
 #include <thread>
 #include "lvba_internal.h"
 #include "ldlt_schedule.h"
+#include "wave_ops.h"
 #include "../../include/lvba_hip.h" // status codes
 
 namespace lvba {

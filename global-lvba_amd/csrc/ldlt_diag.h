@@ -33,12 +33,6 @@ __device__ __forceinline__ double fast_rcp(double d)
 // the symmetric sweep operator 22 us (a barrier per pivot); this form: see DESIGN.md 5.2.
 #define LVBA_W1S 130 // column stride of W (doubles)
 #define LVBA_Z1S 50  // column stride of the Z^T tile (doubles)
-__device__ __forceinline__ double readlane_f64(double v, int lane)
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-    return __hiloint2double(hi, lo);
-}
 // lane L of every 16-lane row to all lanes of that row (v_mov_b64_dpp row_newbcast)
 template <int L>
 __device__ __forceinline__ double bcast16(double v)

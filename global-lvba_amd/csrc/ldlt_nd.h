@@ -193,8 +193,7 @@ __global__ __launch_bounds__(256) void nd_zstep_kernel(const double *__restrict_
     if (r >= n) return;
     double s = 0.0;
     for (int64_t jj = lane; jj < 6 * (int64_t)nsep; jj += 64) s += B[r * ldb + jj] * xS[6 * (int64_t)sep[jj / 6] + jj % 6];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    s = wave_sum(s);
     if (lane == 0) b[r] -= s;
 }
 

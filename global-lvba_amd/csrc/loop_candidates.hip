@@ -6,8 +6,8 @@
 //   loop_search_kernel   one wavefront per query frame j, four to a workgroup.  The wavefront walks the submaps in index order; a
 //                        submap that fails the gap clause costs two scalar compares.  Otherwise the lanes stride over the submap's
 //                        frames, each keeps its smallest (d2, f) pair; if no lane is inside the radius the submap is done (one
-//                        ballot), else the pairs are reduced in a fixed order -- the DPP row steps of wave_max_to_lane63
-//                        (voxel_internal.h) on the pair, compared lexicographically -- and lane 0 files the result among the
+//                        ballot), else the pairs are reduced in a fixed order -- the DPP tree of wave_ops.h
+//                        (wave_fold_to_lane63) on the pair, compared lexicographically -- and lane 0 files the result among the
 //                        query's max_per_frame best in LDS.  At the end lane 0 puts them in submap order into the query's slot of a
 //                        staging array and writes their number.
 //   scan_excl            where every query's entries begin; the last element is the total.
@@ -23,6 +23,7 @@
 #include "mempool.h"
 #include "voxel_internal.h"
 #include "loop_device.h"
+#include "wave_ops.h"
 #include "../../include/lvba_hip.h"
 
 using namespace lvba;
@@ -32,28 +33,17 @@ namespace {
 constexpr int LOOP_BLOCK = 256; // four wavefronts, a query each
 
 // min over the 64 lanes of a wavefront of the (d2, idx) pairs, result in lane 63.  A lane without a source sees loop_none().
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ LoopBest dpp_min_pair(LoopBest v)
-{
-    const LoopBest id = loop_none();
-    const long long b = __double_as_longlong(v.d2), ib = __double_as_longlong(id.d2);
-    const int lo = dpp_i32<CTRL, ROW_MASK>((int)(ib & 0xffffffffll), (int)(b & 0xffffffffll));
-    const int hi = dpp_i32<CTRL, ROW_MASK>((int)(ib >> 32), (int)(b >> 32));
-    LoopBest o;
-    o.d2 = __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
-    o.idx = dpp_i32<CTRL, ROW_MASK>(id.idx, v.idx);
-    return loop_less(o.d2, o.idx, v.d2, v.idx) ? o : v;
-}
-__device__ __forceinline__ LoopBest wave_min_pair_to_lane63(LoopBest v)
-{
-    v = dpp_min_pair<0x111, 0xf>(v); // row_shr:1
-    v = dpp_min_pair<0x112, 0xf>(v); // row_shr:2
-    v = dpp_min_pair<0x114, 0xf>(v); // row_shr:4
-    v = dpp_min_pair<0x118, 0xf>(v); // row_shr:8   -> lane 15 of every row of 16: the row
-    v = dpp_min_pair<0x142, 0xa>(v); // row_bcast:15 -> rows 1 and 3 take in rows 0 and 2
-    v = dpp_min_pair<0x143, 0xc>(v); // row_bcast:31 -> rows 2 and 3 take in rows 0 + 1
-    return v;
-}
+struct MinPairStep {
+    template <int CTRL, int ROW_MASK>
+    static __device__ __forceinline__ LoopBest step(LoopBest v)
+    {
+        const LoopBest id = loop_none();
+        LoopBest o;
+        o.d2 = dpp_f64<CTRL, ROW_MASK>(id.d2, v.d2);
+        o.idx = dpp_i32<CTRL, ROW_MASK>(id.idx, v.idx);
+        return loop_less(o.d2, o.idx, v.d2, v.idx) ? o : v;
+    }
+};
 
 // count [nq], stage [nq][max_per_frame]
 __global__ __launch_bounds__(LOOP_BLOCK) void loop_search_kernel(int n, int nq, const double *__restrict__ pos, const LoopParams o,
@@ -77,10 +67,8 @@ __global__ __launch_bounds__(LOOP_BLOCK) void loop_search_kernel(int n, int nq, 
             if (loop_less(d2, f, b.d2, b.idx)) { b.d2 = d2; b.idx = f; }
         }
         if (!__any(loop_in_radius(b.d2, o.radius2) ? 1 : 0)) continue;
-        b = wave_min_pair_to_lane63(b);
-        const long long bits = __double_as_longlong(b.d2);
-        const int lo = __builtin_amdgcn_readlane((int)(bits & 0xffffffffll), 63), hi = __builtin_amdgcn_readlane((int)(bits >> 32), 63);
-        const double d2 = __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
+        b = wave_fold_to_lane63<MinPairStep>(b);
+        const double d2 = readlane_f64(b.d2, 63);
         const int f = __builtin_amdgcn_readlane(b.idx, 63);
         if (lane == 0) loop_keep(top[wv], ref[wv], &kept, o.max_per_frame, d2, w, f);
     }

@@ -24,6 +24,7 @@
 #include "mempool.h"
 #include "voxel_internal.h"
 #include "voxel_lookup.h"
+#include "wave_ops.h"
 #include "register_device.h"
 #include "../../include/lvba_hip.h"
 
@@ -42,26 +43,6 @@ __host__ __device__ inline int reg_blocks(int64_t m)
 {
     const int64_t nb = (m + (int64_t)REG_BLOCK * REG_RUN - 1) / ((int64_t)REG_BLOCK * REG_RUN);
     return (int)(nb < 1 ? 1 : nb > REG_MAX_BLOCKS ? REG_MAX_BLOCKS : nb);
-}
-
-// sum over the 64 lanes of a wavefront, result in lane 63 (the steps of wave_max_to_lane63, voxel_internal.h, on the two halves
-// of a double; a lane without a source adds 0.0)
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_f64(double v)
-{
-    const long long b = __double_as_longlong(v);
-    const int lo = dpp_i32<CTRL, ROW_MASK>(0, (int)(b & 0xffffffffll)), hi = dpp_i32<CTRL, ROW_MASK>(0, (int)(b >> 32));
-    return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
-}
-__device__ __forceinline__ double wave_sum_to_lane63(double v)
-{
-    v += dpp_f64<0x111, 0xf>(v); // row_shr:1
-    v += dpp_f64<0x112, 0xf>(v); // row_shr:2
-    v += dpp_f64<0x114, 0xf>(v); // row_shr:4
-    v += dpp_f64<0x118, 0xf>(v); // row_shr:8   -> lane 15 of every row of 16: the row
-    v += dpp_f64<0x142, 0xa>(v); // row_bcast:15 -> rows 1 and 3 take in rows 0 and 2
-    v += dpp_f64<0x143, 0xc>(v); // row_bcast:31 -> rows 2 and 3 take in rows 0 + 1
-    return v;
 }
 
 // part [jobs][gridDim.x][REG_NS].  SUBMAPS = false: every job against the whole root table (submap unused; the single-map code
@@ -102,7 +83,8 @@ __global__ __launch_bounds__(REG_BLOCK) void reg_linearize_kernel(const VoxLooku
             reg_point(T, p, w, pl, o, s);
     }
 #pragma unroll
-    for (int q = 0; q < REG_NS; ++q) s[q] = wave_sum_to_lane63(s[q]);
+    for (int q = 0; q < REG_NS; ++q) s[q] = wave_sum_to_lane63(s[q]); // (a lane without a source adds 0.0)
+    // per component, from lane 63, for REG_NS threads to finish: not block_sum (wave_ops.h), which sums one value through lane 0
     if ((threadIdx.x & 63) == 63) {
 #pragma unroll
         for (int q = 0; q < REG_NS; ++q) red[threadIdx.x >> 6][q] = s[q];

@@ -26,24 +26,9 @@
 #include "lvba_internal.h"
 #include "visual_math.h"
 #include "visual_loss.h"
+#include "wave_ops.h"
 
 namespace lvba {
-
-__device__ __forceinline__ double v_wave_sum(double x)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-    return x;
-}
-__device__ __forceinline__ double v_block_sum(double x, double *red) // 256 threads; valid in every thread
-{
-    x = v_wave_sum(x);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
-    __syncthreads();
-    const double t = red[0] + red[1] + red[2] + red[3];
-    __syncthreads();
-    return t;
-}
 
 // Corrector of one residual block with squared norm s (family f: 0 reprojection, 1 plane): returns sqrt(rho'(s)), rho(s) -> *rho0.
 // The kind is a kernel argument: the branch is uniform over the wavefront.
@@ -58,15 +43,8 @@ __device__ __forceinline__ double v_loss_weight(const VisDev &d, int f, double s
 // sum over the four lanes of a DPP quad; every lane of the quad gets the total (quad_perm [1,0,3,2], then [2,3,0,1])
 __device__ __forceinline__ double v_quad_sum(double x)
 {
-#define LVBA_QUAD_ADD(ctrl)                                                                          \
-    do {                                                                                             \
-        const int lo_ = __builtin_amdgcn_update_dpp(0, __double2loint(x), (ctrl), 0xF, 0xF, false);  \
-        const int hi_ = __builtin_amdgcn_update_dpp(0, __double2hiint(x), (ctrl), 0xF, 0xF, false);  \
-        x += __hiloint2double(hi_, lo_);                                                             \
-    } while (0)
-    LVBA_QUAD_ADD(0xB1);
-    LVBA_QUAD_ADD(0x4E);
-#undef LVBA_QUAD_ADD
+    x += dpp_f64<0xB1, 0xf>(0.0, x);
+    x += dpp_f64<0x4E, 0xf>(0.0, x);
     return x;
 }
 
@@ -137,7 +115,7 @@ __global__ __launch_bounds__(256) void vis_residual_kernel(VisDev d, const doubl
         }
         if (!ROBUST) ss = rp * rp;
     }
-    const double tot = v_block_sum(ss, red);
+    const double tot = block_sum_all<4>(ss, red);
     if (threadIdx.x == 0) part[blockIdx.x] = tot;
 }
 
@@ -170,7 +148,7 @@ __device__ __forceinline__ void colsq_cam(const VisDev &d, int64_t I, double (&s
         }
     }
 #pragma unroll
-    for (int e = 0; e < 6; ++e) s[e] = v_wave_sum(s[e]);
+    for (int e = 0; e < 6; ++e) s[e] = wave_sum(s[e]);
 }
 __global__ __launch_bounds__(64) void vis_colnorm_cam_kernel(VisDev d)
 {
@@ -271,8 +249,7 @@ __global__ __launch_bounds__(256) void vis_point_kernel(VisDev d, const double *
         }
     }
     // one atomic per workgroup: atomics on ONE address are serialised (one per wavefront of 16 landmarks cost 60 us here)
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) gm = fmax(gm, __shfl_down(gm, off, 64));
+    gm = wave_reduce_down(gm, [](double a, double b) { return fmax(a, b); });
     if ((threadIdx.x & 63) == 0) redm[threadIdx.x >> 6] = gm;
     __syncthreads();
     if (threadIdx.x == 0)
@@ -371,7 +348,7 @@ __global__ __launch_bounds__(256) void vis_cam_kernel(VisDev d, const double *__
     }
 #pragma unroll
     for (int e = 0; e < 39; ++e) {
-        const double v = v_wave_sum(acc[e]);
+        const double v = wave_sum(acc[e]);
         if (lane == 0) red[wv * 39 + e] = v;
     }
     if (wave_units) {
@@ -534,7 +511,7 @@ __global__ __launch_bounds__(256) void vis_back_kernel(VisDev d, const double *_
             }
         }
     }
-    const double tot = v_block_sum(mc, red);
+    const double tot = block_sum_all<4>(mc, red);
     if (threadIdx.x == 0) part[blockIdx.x] = tot;
 }
 
@@ -607,8 +584,8 @@ __global__ __launch_bounds__(256) void vis_apply_kernel(VisDev d, const double *
             xn += x * x;
         }
     }
-    const double t0 = v_block_sum(dn, red);
-    const double t1 = v_block_sum(xn, red);
+    const double t0 = block_sum_all<4>(dn, red);
+    const double t1 = block_sum_all<4>(xn, red);
     if (threadIdx.x == 0) { part[2 * blockIdx.x] = t0; part[2 * blockIdx.x + 1] = t1; }
 }
 
@@ -619,14 +596,8 @@ __global__ __launch_bounds__(1024) void vis_reduce_kernel(const double *__restri
     for (int k = 0; k < stride; ++k) {
         double s = 0.0;
         for (int64_t i = threadIdx.x; i < n; i += 1024) s += part[stride * i + k];
-        s = v_wave_sum(s);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double t = 0.0;
-            for (int i = 0; i < 16; ++i) t += red[i];
-            out[k] = t;
-        }
+        const double t = block_sum<16>(s, red);
+        if (threadIdx.x == 0) out[k] = t;
         __syncthreads();
     }
 }
@@ -658,7 +629,7 @@ __global__ __launch_bounds__(1024) void vis_finish_kernel(const double *__restri
     for (int64_t i = threadIdx.x; i < nb_back; i += 1024) s0 += pb[i];
     for (int64_t i = threadIdx.x; i < nb_apply; i += 1024) { s1 += pa[2 * i]; s2 += pa[2 * i + 1]; }
     for (int64_t i = threadIdx.x; i < nb_res; i += 1024) s3 += pr[i];
-    s0 = v_wave_sum(s0); s1 = v_wave_sum(s1); s2 = v_wave_sum(s2); s3 = v_wave_sum(s3);
+    s0 = wave_sum(s0); s1 = wave_sum(s1); s2 = wave_sum(s2); s3 = wave_sum(s3);
     if ((threadIdx.x & 63) == 0) {
         const int w = threadIdx.x >> 6;
         red[0][w] = s0; red[1][w] = s1; red[2][w] = s2; red[3][w] = s3;

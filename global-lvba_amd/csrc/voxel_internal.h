@@ -10,6 +10,7 @@
 #include "lvba_common.h"
 #include "mempool.h"
 #include "key_pack.h"
+#include "wave_ops.h"
 
 struct lvba_scans_s {
     int device = 0;
@@ -122,22 +123,7 @@ __device__ __forceinline__ uint64_t pack_key(const int64_t k[3])
 // error flag it waits for anyway, and the keys are re-packed as  (x - x0) << (by + bz) | (y - y0) << bz | (z - z0):
 // the same lexicographic order, hence the same stable sort, in 32 bits whenever bx + by + bz <= 32.
 // (KeyPack, key_pack_of, key_compress, key_expand: key_pack.h -- plain arithmetic, also compiled by tests/key_pack_check.cpp)
-// max over the 64 lanes of a wavefront, result in lane 63: four row shifts and two row broadcasts on the DPP path of the
-// vector ALU (as ds_bpermute shuffles the six reductions cost the key kernel 0.2 ms per 16 M points)
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ int dpp_i32(int old, int v) { return __builtin_amdgcn_update_dpp(old, v, CTRL, ROW_MASK, 0xf, false); }
-__device__ __forceinline__ int wave_max_to_lane63(int v) // v >= 0
-{
-    constexpr int id = 0; // what a lane without a source sees
-    auto op = [](int a, int b) { return max(a, b); };
-    v = op(v, dpp_i32<0x111, 0xf>(id, v)); // row_shr:1
-    v = op(v, dpp_i32<0x112, 0xf>(id, v)); // row_shr:2
-    v = op(v, dpp_i32<0x114, 0xf>(id, v)); // row_shr:4
-    v = op(v, dpp_i32<0x118, 0xf>(id, v)); // row_shr:8   -> lane 15 of every row of 16: the row
-    v = op(v, dpp_i32<0x142, 0xa>(id, v)); // row_bcast:15 -> rows 1 and 3 take in rows 0 and 2
-    v = op(v, dpp_i32<0x143, 0xc>(id, v)); // row_bcast:31 -> rows 2 and 3 take in rows 0 + 1
-    return v;
-}
+// The maxima over a wavefront are wave_max_to_lane63 (wave_ops.h): the DPP tree, result in lane 63.
 // every lane of the wavefront calls this (lanes without a point: valid = false); kb = biased components.  The wavefront's six
 // maxima go to its own slot of `partial` ([wavefronts of the launch][6]) -- no atomics, nothing read back: conditional atomics on
 // the global range cost 0.25 ms per 16 M points in the round trip of the read alone (and 16 ms unconditionally) --,

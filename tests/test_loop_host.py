@@ -49,6 +49,9 @@ def search_cases():
            ("min_gap=8", P, dict(lc.SEARCH, min_gap=8)), ("min_gap=9", P, dict(lc.SEARCH, min_gap=9)),
            ("n < submap_size", P[:2], dict(lc.SEARCH, submap_size=3, min_gap=1, radius=10.0)),
            ("n = 0", P[:0], lc.SEARCH)]
+    # a submap of exactly one wavefront of frames, and of one frame more, each followed by a last submap of a single frame
+    ragged = dict(submap_size=64, min_gap=0, max_per_frame=2, query_stride=1, radius=3.0)
+    out += [("64 + 1 frames", lc.laps()[:65], ragged), ("65 + 1 frames", lc.laps()[:66], dict(ragged, submap_size=65))]
     return out + [(f"laps {k}", lc.laps(), o) for k, o in enumerate(lc.LAPS_CASES)]
 
 
@@ -84,6 +87,10 @@ def test_fixture_candidates_cover_every_clause():
     for p in el:
         per_query.setdefault(p["query"], []).append(p["d2"])
     assert any(len(v) > L0["max_per_frame"] for v in per_query.values()) and any(len(set(v)) < len(v) for v in per_query.values())
+    # the ragged cases have candidates in the full submap and in the last one of a single frame
+    for name, P, o in search_cases():
+        if name.endswith("+ 1 frames"):
+            assert {c[1] for c in lo.candidates(P, **o)} == {0, 1} and len(P) == o["submap_size"] + 1
 
 
 def test_fixture_registrations_meet_their_conditions():
