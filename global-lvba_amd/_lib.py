@@ -32,6 +32,7 @@ SYMBOLS = [
     "lvba_register_default_opts", "lvba_register_linearize", "lvba_register_scans",
     "lvba_submaps_build", "lvba_submaps_count", "lvba_submaps_find_planes", "lvba_register_linearize_submaps",
     "lvba_register_scans_submaps", "lvba_loop_default_opts", "lvba_loop_candidates",
+    "lvba_place_default_opts", "lvba_place_descriptors", "lvba_place_search", "lvba_place_candidates",
 ]
 
 OK, ERR_ARG, ERR_DEVICE, ERR_NOMEM, ERR_UNSUPPORTED, ERR_DIST, ERR_STATE = 0, -1, -2, -3, -4, -5, -6
@@ -165,6 +166,17 @@ class LoopOpts(C.Structure):
 
 class LoopCandidate(C.Structure):
     _fields_ = [("query", C.c_int32), ("submap", C.c_int32), ("ref", C.c_int32), ("pad", C.c_int32), ("distance", C.c_double)]
+
+
+class PlaceOpts(C.Structure):
+    _fields_ = [("n_rings", C.c_int32), ("n_sectors", C.c_int32), ("min_range", C.c_double), ("max_range", C.c_double),
+                ("z_offset", C.c_double), ("submap_size", C.c_int32), ("min_gap", C.c_int32), ("n_key_candidates", C.c_int32),
+                ("max_per_frame", C.c_int32), ("query_stride", C.c_int32), ("pad", C.c_int32), ("max_distance", C.c_double)]
+
+
+class PlaceCandidate(C.Structure):
+    _fields_ = [("query", C.c_int32), ("submap", C.c_int32), ("ref", C.c_int32), ("shift", C.c_int32), ("distance", C.c_double),
+                ("yaw", C.c_double)]
 
 
 class VoxelOpts(C.Structure):
@@ -371,6 +383,11 @@ def load():
     lib.lvba_loop_default_opts.restype = None
     lib.lvba_loop_candidates.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.POINTER(LoopOpts), C.c_int64, C.c_void_p,
                                          C.POINTER(C.c_int64)]
+    lib.lvba_place_default_opts.argtypes = [C.POINTER(PlaceOpts)]
+    lib.lvba_place_default_opts.restype = None
+    lib.lvba_place_descriptors.argtypes = [H, C.c_int32, C.c_int32, C.POINTER(PlaceOpts), C.c_void_p, C.c_void_p]
+    lib.lvba_place_search.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.POINTER(PlaceOpts), C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]
+    lib.lvba_place_candidates.argtypes = [H, C.POINTER(PlaceOpts), C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]
     lib.lvba_scans_info.argtypes = [H, C.POINTER(C.c_int32), C.c_void_p]
     lib.lvba_scans_download.argtypes = [H, C.c_int32, np.ctypeslib.ndpointer(np.float32, flags="C")]
     for name in SYMBOLS:

@@ -7,11 +7,12 @@
 //                        submap that fails the gap clause costs two scalar compares.  Otherwise the lanes stride over the submap's
 //                        frames, each keeps its smallest (d2, f) pair; if no lane is inside the radius the submap is done (one
 //                        ballot), else the pairs are reduced in a fixed order -- the DPP tree of wave_ops.h
-//                        (wave_fold_to_lane63) on the pair, compared lexicographically -- and lane 0 files the result among the
+//                        (wave_fold_to_lane63 with MinPairStep) on the pair, compared lexicographically -- and lane 0 files the result among the
 //                        query's max_per_frame best in LDS.  At the end lane 0 puts them in submap order into the query's slot of a
 //                        staging array and writes their number.
 //   scan_excl            where every query's entries begin; the last element is the total.
-//   loop_write_kernel    one lane per query copies its entries to their place, up to `capacity`.
+//   loop_write_kernel    one lane per query copies its entries to their place, up to `capacity` (loop_device.h; shared with
+//                        place.hip).
 // No atomics anywhere, every minimum in a fixed order: two calls give the same bytes.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -31,19 +32,6 @@ using namespace lvba;
 namespace {
 
 constexpr int LOOP_BLOCK = 256; // four wavefronts, a query each
-
-// min over the 64 lanes of a wavefront of the (d2, idx) pairs, result in lane 63.  A lane without a source sees loop_none().
-struct MinPairStep {
-    template <int CTRL, int ROW_MASK>
-    static __device__ __forceinline__ LoopBest step(LoopBest v)
-    {
-        const LoopBest id = loop_none();
-        LoopBest o;
-        o.d2 = dpp_f64<CTRL, ROW_MASK>(id.d2, v.d2);
-        o.idx = dpp_i32<CTRL, ROW_MASK>(id.idx, v.idx);
-        return loop_less(o.d2, o.idx, v.d2, v.idx) ? o : v;
-    }
-};
 
 // count [nq], stage [nq][max_per_frame]
 __global__ __launch_bounds__(LOOP_BLOCK) void loop_search_kernel(int n, int nq, const double *__restrict__ pos, const LoopParams o,
@@ -67,7 +55,7 @@ __global__ __launch_bounds__(LOOP_BLOCK) void loop_search_kernel(int n, int nq, 
             if (loop_less(d2, f, b.d2, b.idx)) { b.d2 = d2; b.idx = f; }
         }
         if (!__any(loop_in_radius(b.d2, o.radius2) ? 1 : 0)) continue;
-        b = wave_fold_to_lane63<MinPairStep>(b);
+        b = wave_fold_to_lane63<MinPairStep<LoopBest>>(b);
         const double d2 = readlane_f64(b.d2, 63);
         const int f = __builtin_amdgcn_readlane(b.idx, 63);
         if (lane == 0) loop_keep(top[wv], ref[wv], &kept, o.max_per_frame, d2, w, f);
@@ -81,15 +69,6 @@ __global__ __launch_bounds__(LOOP_BLOCK) void loop_search_kernel(int n, int nq, 
         c.distance = sqrt(top[wv][a].d2);
         stage[(int64_t)q * o.max_per_frame + a] = c;
     }
-}
-
-__global__ void loop_write_kernel(int nq, int k, const int64_t *__restrict__ count, const int64_t *__restrict__ first,
-                                  const lvba_loop_candidate *__restrict__ stage, int64_t capacity, lvba_loop_candidate *__restrict__ out)
-{
-    const int q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= nq) return;
-    const int64_t c = count[q], d0 = first[q];
-    for (int64_t a = 0; a < c && d0 + a < capacity; ++a) out[d0 + a] = stage[(int64_t)q * k + a];
 }
 
 } // namespace

@@ -79,4 +79,18 @@ LVBA_HD void loop_sort_by_submap(LoopBest *top, int32_t *ref, int n)
     }
 }
 
+#ifdef __HIPCC__
+// One lane per query copies its count[q] staged entries (stage [nq][k]) to out[first[q] ..], up to `capacity` (the candidate
+// searches: loop_candidates.hip, place.hip).
+template <class Cand>
+__global__ void loop_write_kernel(int nq, int k, const int64_t *__restrict__ count, const int64_t *__restrict__ first,
+                                  const Cand *__restrict__ stage, int64_t capacity, Cand *__restrict__ out)
+{
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nq) return;
+    const int64_t c = count[q], d0 = first[q];
+    for (int64_t a = 0; a < c && d0 + a < capacity; ++a) out[d0 + a] = stage[(int64_t)q * k + a];
+}
+#endif
+
 } // namespace lvba

@@ -3,6 +3,8 @@
 // reduction is stated here and nowhere else; DESIGN.md, "Wavefront reductions", says which tree to use when.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
 
 namespace lvba {
 
@@ -51,6 +53,27 @@ struct MaxStepI32 { // of values >= 0
 struct SumStepF64 {
     template <int CTRL, int ROW_MASK>
     static __device__ __forceinline__ double step(double v) { return v + dpp_f64<CTRL, ROW_MASK>(0.0, v); }
+};
+// min of (d2, idx) pairs in lexicographic order -- the lower idx wins a tie, so the result does not depend on which lane held
+// what.  Pair: any struct with a float or double `d2` and an int32_t `idx`.  A lane without a source sees (inf, INT32_MAX), which
+// loses against every real pair (the candidate searches: loop_candidates.hip, place.hip).
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ float dpp_val(float old, float v)
+{
+    return __int_as_float(dpp_i32<CTRL, ROW_MASK>(__float_as_int(old), __float_as_int(v)));
+}
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ double dpp_val(double old, double v) { return dpp_f64<CTRL, ROW_MASK>(old, v); }
+template <class Pair>
+struct MinPairStep {
+    template <int CTRL, int ROW_MASK>
+    static __device__ __forceinline__ Pair step(Pair v)
+    {
+        Pair o = v;
+        o.d2 = dpp_val<CTRL, ROW_MASK>((decltype(v.d2))INFINITY, v.d2);
+        o.idx = dpp_i32<CTRL, ROW_MASK>(INT32_MAX, v.idx);
+        return (o.d2 < v.d2 || (o.d2 == v.d2 && o.idx < v.idx)) ? o : v;
+    }
 };
 __device__ __forceinline__ int wave_max_to_lane63(int v) { return wave_fold_to_lane63<MaxStepI32>(v); } // v >= 0
 __device__ __forceinline__ double wave_sum_to_lane63(double v) { return wave_fold_to_lane63<SumStepF64>(v); }

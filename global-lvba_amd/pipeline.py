@@ -380,33 +380,74 @@ def loop_acceptance(status, inliers, points, rmse, rot, trans, min_inlier_frac=0
 
 
 def find_loop_closures(scans, poses, submap_size=10, voxel_size=1.0, eigen_ratio_array=None, radius=5.0, min_gap=50, max_per_frame=2,
-                       query_stride=1, min_inlier_frac=0.3, max_rmse=None, max_rot=None, max_trans=None, sigma=None, **register_opts):
+                       query_stride=1, min_inlier_frac=0.3, max_rmse=None, max_rot=None, max_trans=None, sigma=None, method="pose",
+                       place=None, **register_opts):
     """Loop closures of a trajectory, found and verified on the GPU: the submap set of all frames of `scans` at their current
     `poses` [n,12] is built in one pass (Scans.submaps, eigen ratios register.STRICT_RATIO by default: DESIGN.md §10c), the
-    candidates (query frame, submap, nearest frame ref) come from the poses alone (register.loop_candidates: radius, min_gap,
-    max_per_frame, query_stride), and ALL candidates are registered in one call, each query frame from its current pose against
-    its submap (SubmapSet.register, register_opts: its options).  A candidate is accepted by loop_acceptance.
+    candidates (query frame, submap, reference frame ref) are found, and ALL candidates are registered in one call, each query
+    frame from its start pose against its submap (SubmapSet.register, register_opts: its options).  A candidate is accepted by
+    loop_acceptance.
+    method: where the candidates and their start poses come from.
+      "pose"        from the poses alone (register.loop_candidates: radius, min_gap, max_per_frame, query_stride); ref is the
+                    submap's nearest frame and the start is the query's current pose.  Finds a revisit only while the drift is
+                    below radius.
+      "descriptor"  from the clouds alone (register.place_candidates: Scan Context descriptors; `place` is a dict
+                    of its options, submap_size / min_gap / max_per_frame / query_stride are this function's own); ref is the
+                    submap's most similar frame and the start is poses[ref] o (Rz(yaw), 0), the reference pose turned by the
+                    yaw the descriptors give.  It does not depend on the query's current pose, however far that has drifted.
+      "both"        the union; a (query, submap) found by both is kept once, with the pose-based ref and start.
+    rot / trans, and hence the max_rot / max_trans bounds, are measured from the START pose to the registered one: for a
+    descriptor candidate the jump from the query's drifted pose to the registered pose is the finding, not an error, while a
+    large correction of the start says the registration wandered off.
     Returns (priors, report): priors = a balm.Prior.relative(ref, query) per accepted candidate, measurement and sqrt_info as
-    loop_closure_prior builds them (registration_prior; sigma as there); report = one dict per candidate: query, submap, ref,
-    distance, the registration's fields (pose, information, status, status_name, iterations, inliers, points, cost_first,
+    loop_closure_prior builds them (registration_prior; sigma as there) -- a relative constraint from ref to the REGISTERED pose
+    of the query, valid whatever the query's current pose; report = one dict per candidate, by (query, submap): query, submap,
+    ref, method ("pose", "descriptor", or "both" for a pair that both found), distance and distance_kind ("metres" between the
+    positions for a pose candidate, "descriptor" for the shift distance in [0, 1]), shift and yaw (None for a pose candidate),
+    start, the registration's fields (pose, information, status, status_name, iterations, inliers, points, cost_first,
     cost_last, rmse, min_eigenvalue), rot / trans (the correction), accepted and reason (None when accepted)."""
-    from .register import STRICT_RATIO, loop_candidates
+    from .register import STRICT_RATIO, loop_candidates, place_candidates
+    if method not in ("pose", "descriptor", "both"):
+        raise ValueError(f"method {method!r}: one of 'pose', 'descriptor', 'both'")
+    if place is not None and method == "pose":
+        raise TypeError("place options are for method='descriptor' or 'both'")
     x = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
-    cand = loop_candidates(x, submap_size=submap_size, min_gap=min_gap, max_per_frame=max_per_frame, query_stride=query_stride,
-                           radius=radius)
+    shared = dict(submap_size=submap_size, min_gap=min_gap, max_per_frame=max_per_frame, query_stride=query_stride)
+    found = {}
+    if method in ("descriptor", "both"):
+        clash = set(place or {}) & set(shared)
+        if clash:
+            raise TypeError(f"place options {sorted(clash)} are arguments of find_loop_closures itself")
+        if scans.n_frames != len(x):
+            raise ValueError(f"{len(x)} poses for {scans.n_frames} frames")
+        cand = place_candidates(scans, **shared, **(place or {}))
+        for k in range(len(cand["query"])):
+            ref, yaw = int(cand["ref"][k]), float(cand["yaw"][k])
+            c, s = np.cos(yaw), np.sin(yaw)
+            start = np.r_[(x[ref, :9].reshape(3, 3) @ np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])).reshape(9), x[ref, 9:]]
+            found[(int(cand["query"][k]), int(cand["submap"][k]))] = dict(
+                ref=ref, method="descriptor", distance=float(cand["distance"][k]), distance_kind="descriptor", shift=int(cand["shift"][k]),
+                yaw=yaw, start=start)
+    if method in ("pose", "both"):
+        cand = loop_candidates(x, radius=radius, **shared)
+        for k in range(len(cand["query"])):
+            key = (int(cand["query"][k]), int(cand["submap"][k]))
+            found[key] = dict(ref=int(cand["ref"][k]), method="both" if key in found else "pose", distance=float(cand["distance"][k]),
+                              distance_kind="metres", shift=None, yaw=None, start=x[key[0]].copy())
     priors, report = [], []
-    if cand["count"] == 0:
+    if not found:
         return priors, report
-    q = cand["query"]
+    keys = sorted(found)
+    q, w = np.array([k[0] for k in keys], np.int32), np.array([k[1] for k in keys], np.int32)
+    starts = np.stack([found[k]["start"] for k in keys])
     with scans.submaps(x, submap_size, voxel_size, STRICT_RATIO if eigen_ratio_array is None else eigen_ratio_array) as sm:
-        reg = sm.register(scans, q, cand["submap"], x[q], **register_opts)
-    for k in range(len(q)):
-        rot, trans = pose_correction(x[q[k]], reg["poses"][k])
+        reg = sm.register(scans, q, w, starts, **register_opts)
+    for k, key in enumerate(keys):
+        rot, trans = pose_correction(starts[k], reg["poses"][k])
         ok, why = loop_acceptance(reg["status"][k], reg["inliers"][k], reg["points"][k], reg["rmse"][k], rot, trans, min_inlier_frac,
                                   max_rmse, max_rot, max_trans)
-        r = dict(query=int(q[k]), submap=int(cand["submap"][k]), ref=int(cand["ref"][k]), distance=float(cand["distance"][k]),
-                 pose=reg["poses"][k].copy(), information=reg["information"][k].copy(), status_name=reg["status_name"][k],
-                 rot=rot, trans=trans, accepted=ok, reason=why)
+        r = dict(query=key[0], submap=key[1], **found[key], pose=reg["poses"][k].copy(), information=reg["information"][k].copy(),
+                 status_name=reg["status_name"][k], rot=rot, trans=trans, accepted=ok, reason=why)
         for f in ("status", "iterations", "inliers", "points"):
             r[f] = int(reg[f][k])
         for f in ("cost_first", "cost_last", "rmse", "min_eigenvalue"):

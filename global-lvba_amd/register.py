@@ -9,7 +9,8 @@ Gauss-Newton under the retraction R <- R Exp(theta), t <- t + delta (include/lvb
 map with strict eigen ratios (STRICT_RATIO) or set a loss: a map cut with the optimiser's stage-1 ratios admits planes fitted
 through clutter, and plain Gauss-Newton walks away from the true pose on it.  A submap set (voxel.SubmapSet, Scans.submaps) holds many
 submaps in one map: its register / linearize take a submap index per job.  loop_candidates finds which frame revisits which
-submap from the poses alone.  Everything runs in liblvba_hip.so on the GPU; this file packs arrays."""
+submap from the poses alone; scan_descriptors / place_search / place_candidates find it from the clouds alone (Scan Context
+descriptors: DESIGN.md §10e), with the relative yaw.  Everything runs in liblvba_hip.so on the GPU; this file packs arrays."""
 from __future__ import annotations
 
 import ctypes as C
@@ -122,3 +123,65 @@ def loop_candidates(poses, device=0, capacity=None, **opts):
     got = buf[:min(cap, count.value)]
     return dict(query=got["query"].copy(), submap=got["submap"].copy(), ref=got["ref"].copy(), distance=got["distance"].copy(),
                 count=count.value, raw=got.copy())
+
+
+PLACE_OPTS = ("n_rings", "n_sectors", "min_range", "max_range", "z_offset", "submap_size", "min_gap", "n_key_candidates", "max_per_frame",
+              "query_stride", "max_distance")
+PLACE_DTYPE = np.dtype([("query", "<i4"), ("submap", "<i4"), ("ref", "<i4"), ("shift", "<i4"), ("distance", "<f8"), ("yaw", "<f8")])
+
+
+def _place_opts(opts):
+    o = L.PlaceOpts()
+    L.load().lvba_place_default_opts(C.byref(o))
+    for k, v in opts.items():
+        if k not in PLACE_OPTS:
+            raise TypeError(f"unknown place option {k!r}; one of {PLACE_OPTS}")
+        setattr(o, k, type(getattr(o, k))(v))
+    return o
+
+
+def _place_result(call, n, o, capacity):
+    count = C.c_int64()
+    cap = n * max(1, min(32, o.max_per_frame)) if capacity is None else int(capacity)
+    buf = np.zeros(max(cap, 1), PLACE_DTYPE)
+    L.check(call(C.byref(o), cap, buf.ctypes.data, C.byref(count)))
+    got = buf[:min(cap, count.value)]
+    d = {k: got[k].copy() for k in PLACE_DTYPE.names}
+    d.update(count=count.value, raw=got.copy())
+    return d
+
+
+def scan_descriptors(scans, frame_begin=0, n_frames=None, **opts):
+    """Scan Context descriptors of frames [frame_begin, frame_begin + n_frames) of `scans` (a voxel.Scans; default: to the last
+    frame): (desc [n, n_rings, n_sectors] float32, ring_key [n, n_rings] float32) -- lvba_place_descriptors; include/lvba_hip.h
+    has the exact rule.  opts: n_rings, n_sectors, min_range, max_range, z_offset (the others of PLACE_OPTS are accepted and
+    have no bearing on a descriptor)."""
+    o = _place_opts(opts)
+    n = scans.n_frames - int(frame_begin) if n_frames is None else int(n_frames)
+    desc, key = np.zeros((max(n, 0), o.n_rings, o.n_sectors), np.float32), np.zeros((max(n, 0), o.n_rings), np.float32)
+    L.check(L.load().lvba_place_descriptors(scans._h, int(frame_begin), n, C.byref(o), desc.ctypes.data, key.ctypes.data))
+    return desc, key
+
+
+def place_search(desc, device=0, capacity=None, **opts):
+    """Place-recognition candidates among descriptors desc [n, n_rings, n_sectors] from anywhere (lvba_place_search): per query
+    frame the n_key_candidates frames of the nearest ring keys, at least min_gap frames away, get the column-shift distance; per
+    submap the best frame is ref; the max_per_frame submaps within max_distance are kept.  Returns dict(query, submap, ref,
+    shift, distance, yaw [rad, the query's body is ref's turned by yaw about z], count, raw), sorted by (query, submap).
+    n_rings / n_sectors default to desc's shape.  capacity: as loop_candidates."""
+    d = np.ascontiguousarray(desc, np.float32)
+    if d.ndim != 3:
+        raise ValueError("desc must be [n, n_rings, n_sectors]")
+    o = _place_opts(dict(dict(n_rings=d.shape[1], n_sectors=d.shape[2]), **opts))
+    if (o.n_rings, o.n_sectors) != d.shape[1:]:
+        raise ValueError(f"desc is {d.shape[1]} x {d.shape[2]}, the options say {o.n_rings} x {o.n_sectors}")
+    lib = L.load()
+    return _place_result(lambda po, cap, out, cnt: lib.lvba_place_search(int(device), len(d), d.ctypes.data, po, cap, out, cnt), len(d), o, capacity)
+
+
+def place_candidates(scans, capacity=None, **opts):
+    """place_search over the descriptors of all frames of `scans`, the descriptors never leaving the device
+    (lvba_place_candidates): the same bytes as scan_descriptors followed by place_search."""
+    o = _place_opts(opts)
+    lib = L.load()
+    return _place_result(lambda po, cap, out, cnt: lib.lvba_place_candidates(scans._h, po, cap, out, cnt), scans.n_frames, o, capacity)

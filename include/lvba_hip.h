@@ -877,6 +877,65 @@ void lvba_loop_default_opts(lvba_loop_opts *o);
 int32_t lvba_loop_candidates(int32_t device, int32_t n_frames, const double *poses, const lvba_loop_opts *o, int64_t capacity,
                              lvba_loop_candidate *out, int64_t *count);
 
+/* ---- place recognition: which frame revisits which submap, from the clouds alone (Scan Context) ---------------
+ *   Descriptor of a frame, Nr = n_rings, Ns = n_sectors.  Every body-frame point (x, y, z), fp32 promoted once to fp64:
+ *     r = sqrt(x x + y y); the point is dropped unless min_range <= r < max_range (a non-finite x or y drops it)
+ *     ring   = min(floor((r Nr) / max_range), Nr - 1)
+ *     sector = min(floor(((atan2(y, x) + pi) Ns) / (2 pi)), Ns - 1)      atan2 in fp64, pi = 3.14159265358979323846; a point within
+ *                                                                          an ulp or two of a sector boundary may fall either side
+ *     h = (float)(z + z_offset); a point whose h is not finite is dropped
+ *     D[ring][sector] = max(0, max of h over the cell's points)         fp32; an empty cell is 0.  A maximum: the same bytes
+ *                                                                          however it is reduced
+ *   Ring key: key[ring] = (float)((double)(number of sectors with D > 0) / (double)Ns); it does not change when the body turns
+ *   about z.  Normalised columns: U[:, j] = D[:, j] / sqrt(sum over ring of D[ring][j]^2), fp64, the sum in ring order; a zero
+ *   column stays zero and is "empty".
+ *   Shift distance of query q against frame c, for s = 0 .. Ns - 1:
+ *     sim(s) = sum over j, then ring, of U_q[ring][(j - s) mod Ns] U_c[ring][j]   over the columns j where neither side is empty, in
+ *              (j, ring) order, fp64, rounded as written (no fused multiply-add); n(s) = the number of such columns
+ *     dist(s) = 1 - sim(s) / n(s), or 1 when n(s) = 0;   distance = min over s, shift = the smallest s that attains it
+ *     yaw = (2 pi shift) / Ns, minus 2 pi when above pi
+ *   T_c o (Rz(yaw), 0) is then the initial T_world<-body of q: the body of q is the body of c turned by yaw about its own z.
+ *   Candidates, with S = submap_size and submap w = frames F_w = [w S, min((w + 1) S, n)): a query j (a multiple of query_stride)
+ *   considers the frames f of the submaps with |j - f'| >= min_gap for EVERY f' in F_w.  Among them the K = n_key_candidates
+ *   smallest (sum over ring of (key_j - key_f)^2, f) pairs -- the sum in fp32, in ring order, rounded as written; the order
+ *   lexicographic -- are kept and the shift distance is computed for exactly these.  Per submap with at least one of the K, ref
+ *   is the frame of the smallest (distance, f); the submap is eligible iff that distance <= max_distance.  Per query the
+ *   max_per_frame eligible submaps of the smallest (distance, w) are kept.  The output is sorted by (query, submap).
+ *   *count is the true number of candidates even when it exceeds capacity; only the first `capacity` are written.  No
+ *   floating-point atomics, every sum and minimum in a fixed order: two calls give the same bytes.
+ *   lvba_place_descriptors: desc [n_frames][Nr][Ns] and ring_key [n_frames][Nr] of frames [frame_begin, frame_begin + n_frames).
+ *   lvba_place_search: the candidates among n_frames descriptors from anywhere (the ring keys are derived from desc).
+ *   lvba_place_candidates: both over all frames of `scans`, the descriptors staying on the device; the bytes of the composition.
+ *   A frame without points has an all-zero descriptor; its distance to anything is 1.  n_frames = 0 gives *count = 0.  Options:
+ *   NULL takes the defaults.
+ *   LVBA_ERR_ARG: a null pointer, a frame range outside the scans, n_frames < 0, capacity < 0, an option outside its range below,
+ *   a descriptor value given to lvba_place_search that is not finite and >= 0. */
+typedef struct lvba_place_opts {
+    int32_t n_rings;          /* Nr, 1 .. 32 (default 20) */
+    int32_t n_sectors;        /* Ns, 1 .. 128 (default 60) */
+    double min_range;         /* metres, finite and >= 0 (default 0.5) */
+    double max_range;         /* metres, finite and > min_range (default 80) */
+    double z_offset;          /* metres, finite (default 2) */
+    int32_t submap_size;      /* S >= 1 (default 10) */
+    int32_t min_gap;          /* frames, >= 0 (default 50) */
+    int32_t n_key_candidates; /* K, 1 .. 32 (default 10) */
+    int32_t max_per_frame;    /* 1 .. 32 (default 2) */
+    int32_t query_stride;     /* >= 1 (default 1) */
+    int32_t pad;
+    double max_distance;      /* in (0, 1] (default 0.4) */
+} lvba_place_opts;
+typedef struct lvba_place_candidate {
+    int32_t query, submap, ref, shift;
+    double distance, yaw;
+} lvba_place_candidate;
+void lvba_place_default_opts(lvba_place_opts *o);
+int32_t lvba_place_descriptors(lvba_scans_t scans, int32_t frame_begin, int32_t n_frames, const lvba_place_opts *o,
+                               float *desc, float *ring_key);
+int32_t lvba_place_search(int32_t device, int32_t n_frames, const float *desc, const lvba_place_opts *o, int64_t capacity,
+                          lvba_place_candidate *out, int64_t *count);
+int32_t lvba_place_candidates(lvba_scans_t scans, const lvba_place_opts *o, int64_t capacity, lvba_place_candidate *out,
+                              int64_t *count);
+
 #ifdef __cplusplus
 }
 #endif
