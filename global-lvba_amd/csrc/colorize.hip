@@ -134,8 +134,8 @@ __global__ void col_emit_kernel(int64_t M, const uint32_t *__restrict__ flag, co
     if (thin) {
         int64_t k[3];
         double dd;
-        col_leaf_key(q, leaf, k, dd); // in range: every finite world point was checked at creation
-        okey[o] = col_pack_key(k);
+        leaf_key_of(q, leaf, k, dd); // in range: every finite world point was checked at creation
+        okey[o] = pack_key(k);
         od2[o] = dd;
     }
 }
@@ -215,12 +215,8 @@ int32_t thin_running(lvba_colorize_s *h, hipStream_t s)
     col_pick_kernel<<<grid_for(n, 256), 256, 0, s>>>(n, key_s.as<uint64_t>(), idx_s.as<uint32_t>(), h->d2.as<double>(),
                                                      h->pos.as<int64_t>(), flag.as<uint32_t>(), pick.as<uint32_t>());
     HIPCHK(hipGetLastError());
-    TRY(scan_excl<uint32_t>(s, flag.as<uint32_t>(), excl.as<uint32_t>(), (size_t)n));
-    uint32_t last[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(&last[0], excl.as<uint32_t>() + (n - 1), 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(&last[1], flag.as<uint32_t>() + (n - 1), 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    const int64_t N = (int64_t)last[0] + last[1];
+    int64_t N = 0;
+    TRY(count_flags(s, flag.as<uint32_t>(), excl.as<uint32_t>(), (size_t)n, &N));
     Owned a[5];
     const size_t sz[5] = {12, 3, 8, 8, 8};
     const int64_t cap = std::max<int64_t>(N, 1);
@@ -244,26 +240,13 @@ int32_t thin_running(lvba_colorize_s *h, hipStream_t s)
     return LVBA_OK;
 }
 
-struct EventTimer { // elapsed ms between events recorded on one stream
-    hipEvent_t e[7] = {};
-    bool ok = true;
-    EventTimer() { for (auto &x : e) ok = ok && hipEventCreate(&x) == hipSuccess; }
-    ~EventTimer() { for (auto &x : e) if (x) (void)hipEventDestroy(x); }
-    void rec(int i, hipStream_t s) { if (ok) (void)hipEventRecord(e[i], s); }
-    double ms(int a, int b) const
-    {
-        float t = 0.f;
-        return ok && hipEventElapsedTime(&t, e[a], e[b]) == hipSuccess ? (double)t : 0.0;
-    }
-};
-
 // one batch: images [b0, b1) of the call, all with a non-empty window (tab[] filled by the caller)
 int32_t run_batch(lvba_colorize_s *h, hipStream_t s, const std::vector<BatchImage> &tab, const std::vector<int32_t> &img_of,
                   const double *Rcw, const double *tcw, const uint8_t *bgr, int64_t M)
 {
     const int B = (int)tab.size();
     const int64_t npix = (int64_t)h->width * h->height;
-    EventTimer ev;
+    EventTimer<7> ev;
     ev.rec(0, s);
     DevBuf d_tab(s), d_R(s), d_t(s), d_img(s), key(s), val(s), key_s(s), val_s(s), zc(s), flag(s), excl(s), win(s);
     HIPCHK(d_tab.alloc(sizeof(BatchImage) * B)); HIPCHK(d_R.alloc(72 * (size_t)B)); HIPCHK(d_t.alloc(24 * (size_t)B));
@@ -297,12 +280,8 @@ int32_t run_batch(lvba_colorize_s *h, hipStream_t s, const std::vector<BatchImag
                                                      win.as<uint32_t>());
     HIPCHK(hipGetLastError());
     ev.rec(4, s);
-    TRY(scan_excl<uint32_t>(s, flag.as<uint32_t>(), excl.as<uint32_t>(), (size_t)M));
-    uint32_t last[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(&last[0], excl.as<uint32_t>() + (M - 1), 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(&last[1], flag.as<uint32_t>() + (M - 1), 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    const int64_t S = (int64_t)last[0] + last[1];
+    int64_t S = 0;
+    TRY(count_flags(s, flag.as<uint32_t>(), excl.as<uint32_t>(), (size_t)M, &S));
     if (S > 0) {
         TRY(ensure_capacity(h, h->n + S, s));
         col_emit_kernel<<<grid_for(M, 256), 256, 0, s>>>(M, flag.as<uint32_t>(), excl.as<uint32_t>(), key_s.as<uint32_t>(),
@@ -372,9 +351,9 @@ extern "C" int32_t lvba_colorize_create(lvba_scans_t sc, const double *scan_pose
     if (P >= ((int64_t)1 << 32)) return lvba_fail(LVBA_ERR_ARG, "%lld points (at most 2^32 - 1)", (long long)P);
     HIPCHK(h->world.alloc(12 * (size_t)std::max<int64_t>(P, 1)));
     if (P > 0) {
-        hipStream_t s = nullptr;
-        HIPCHK(lvba::StreamCache::get().acquire(&s));
-        struct SG { hipStream_t s; ~SG() { lvba::StreamCache::get().release(s); } } sg{s};
+        ScopedStream sg;
+        HIPCHK(sg.acquire());
+        const hipStream_t s = sg.s;
         DevBuf d_poses(s), d_err(s);
         HIPCHK(d_poses.alloc(96 * (size_t)nf)); HIPCHK(d_err.alloc(4));
         HIPCHK(hipMemcpyAsync(d_poses.p, scan_poses, 96 * (size_t)nf, hipMemcpyHostToDevice, s));
@@ -406,9 +385,9 @@ extern "C" int32_t lvba_colorize_add_images(lvba_colorize_t h, int32_t n, const 
     HIPCHK(hipMemGetInfo(&free_b, &total_b));
     const double budget = std::min(0.4 * (double)free_b, 8.0 * (1 << 30));
     const int64_t max_b = std::max<int64_t>(1, std::min<int64_t>(h->max_batch > 0 ? h->max_batch : INT32_MAX, (((int64_t)1 << 31) - 1) / npix));
-    hipStream_t s = nullptr;
-    HIPCHK(lvba::StreamCache::get().acquire(&s));
-    struct SG { hipStream_t s; ~SG() { lvba::StreamCache::get().release(s); } } sg{s};
+    ScopedStream sg;
+    HIPCHK(sg.acquire());
+    const hipStream_t s = sg.s;
     std::vector<BatchImage> tab;
     std::vector<int32_t> img_of;
     int64_t M = 0;

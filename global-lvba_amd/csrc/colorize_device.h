@@ -2,17 +2,16 @@
 // the very code the kernels run is also compiled for the CPU (tests/colorize_check.cpp, tests/test_colorize_host.py).
 // Of the reference (src/lvba_system.cpp, LvbaSystem::VisualizeOptComparison, :1932-2144):
 //   scan window           :1974       |t_scan - t_image| <= 0.5 (the difference is rounded first: not t0 <= t <= t1)
-//   world point           :1980-1987  R p + t in double, stored as float
+//   world point           :1980-1987  R p + t in double, stored as float (pose_apply_f32, scan_points.h)
 //   projection            :2034-2045  projectWorldToPixel (include/utils.hpp:183-205), std::round, [0,W) x [0,H)
 //   depth buffer          :2046-2058  replace when zc + 1e-6f < zbuf, zbuf = (float)zc; pixel kept when zbuf is finite
-//   down_sampling_voxel2  include/BALM/tools.hpp:300-359 (key and squared distance to the leaf centre)
+//   down_sampling_voxel2  include/BALM/tools.hpp:300-359 (key and squared distance to the leaf centre: leaf_key_of, scan_points.h)
 // Files that include this one are built with -ffp-contract=off (build.py NO_CONTRACT): every expression rounds as written.
 #pragma once
 #include "tracks_device.h"
+#include "scan_points.h"
 
 namespace lvba {
-
-constexpr int COL_KEY_BIAS = 1 << 20; // leaf key components must lie in [-2^20, 2^20) (the packing of voxel_internal.h)
 
 // :1974 -- the image at t_img uses the scan at t_scan unless |t_scan - t_img| > half.  For ascending scan times the rounded
 // difference is non-decreasing, so the scans used form one contiguous range (found by col_window_range).
@@ -34,14 +33,10 @@ LVBA_TRK_FN void col_window_range(const double *t, int n, double t_img, double h
     hi = a;
 }
 
-// :1980-1987 -- pose T = R (row-major) | t; the world point in double, stored as float
-LVBA_TRK_FN void col_world_point(const double *T, float x, float y, float z, float out[3])
-{
-    const double p0 = x, p1 = y, p2 = z;
-    out[0] = (float)(T[0] * p0 + T[1] * p1 + T[2] * p2 + T[9]);
-    out[1] = (float)(T[3] * p0 + T[4] * p1 + T[5] * p2 + T[10]);
-    out[2] = (float)(T[6] * p0 + T[7] * p1 + T[8] * p2 + T[11]);
-}
+// :1980-1987 -- the world point in double, stored as float; the leaf key of down_sampling_voxel2: the shared rules under the
+// names tests/colorize_check.cpp binds.  New code calls pose_apply_f32 and leaf_key_of (scan_points.h).
+LVBA_TRK_FN void col_world_point(const double *T, float x, float y, float z, float out[3]) { pose_apply_f32(T, x, y, z, out); }
+LVBA_TRK_FN bool col_leaf_key(const float q[3], double leaf, int64_t k[3], double &d2) { return leaf_key_of(q, leaf, k, d2); }
 
 // :2034-2045 -- projectWorldToPixel of the float point (widened back to double), std::round (half away from zero),
 // bounds [0, W) x [0, H).  Returns false when the reference skips the point; else the row-major pixel and the depth zc.
@@ -88,33 +83,9 @@ LVBA_TRK_FN bool col_walk(int64_t n, ZAt zc_at, int64_t &winner)
     return winner >= 0 && isfinite(zbuf);
 }
 
-// down_sampling_voxel2 (tools.hpp:318-341) for a float point q and the double leaf: key = (int64)(float)(q / leaf), minus 1
-// when negative (in float); d2 = squared distance to the leaf centre, dx*dx + dy*dy + dz*dz from left to right.  Returns
-// false when a component falls outside the packable range (or q is not finite).
-LVBA_TRK_FN bool col_leaf_key(const float q[3], double leaf, int64_t k[3], double &d2)
-{
-    bool ok = true;
-    double dd = 0.0;
-    for (int j = 0; j < 3; ++j) {
-        float loc = (float)((double)q[j] / leaf);
-        if (loc < 0.f) loc -= 1.f;
-        ok = ok && (fabsf(loc) < (float)COL_KEY_BIAS);
-        k[j] = ok ? (int64_t)loc : 0;
-        const double c = ((double)k[j] + 0.5) * leaf;
-        const double d = (double)q[j] - c;
-        dd = dd + d * d;
-    }
-    d2 = dd;
-    return ok;
-}
-LVBA_TRK_FN uint64_t col_pack_key(const int64_t k[3])
-{
-    return ((uint64_t)(k[0] + COL_KEY_BIAS) << 42) | ((uint64_t)(k[1] + COL_KEY_BIAS) << 21) | (uint64_t)(k[2] + COL_KEY_BIAS);
-}
-
 #if defined(__HIPCC__)
-// One lane per point i of P points in frames frame_off[0 .. n_frames] (offsets relative to pts): the world point of
-// col_world_point at the frame's pose, stored as float.  thin: a finite point whose leaf key cannot be packed sets *err.
+// One lane per point i of P points in frames frame_off[0 .. n_frames] (a slice of the set's offsets; pts points at its first
+// point): the world point at the frame's pose, stored as float.  thin: a finite point whose leaf key cannot be packed sets *err.
 // Shared by the coloured map (colorize.hip) and the map-quality metrics (map_quality.hip: thin = 0, err unused).
 static __global__ void col_world_kernel(int64_t P, const float *__restrict__ pts, const int64_t *__restrict__ frame_off, int n_frames,
                                  const double *__restrict__ poses, double leaf, int thin, float *__restrict__ world,
@@ -122,18 +93,13 @@ static __global__ void col_world_kernel(int64_t P, const float *__restrict__ pts
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= P) return;
-    int lo = 0, hi = n_frames;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (frame_off[mid] <= i) lo = mid; else hi = mid;
-    }
     float q[3];
-    col_world_point(poses + 12 * (int64_t)lo, pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], q);
+    pose_apply_f32(poses + 12 * (int64_t)frame_of_point(frame_off, n_frames, i), pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], q);
     world[3 * i] = q[0]; world[3 * i + 1] = q[1]; world[3 * i + 2] = q[2];
     if (thin && isfinite(q[0]) && isfinite(q[1]) && isfinite(q[2])) { // only finite points can ever be projected
         int64_t k[3];
         double dd;
-        if (!col_leaf_key(q, leaf, k, dd)) atomicOr(err, 1);
+        if (!leaf_key_of(q, leaf, k, dd)) atomicOr(err, 1);
     }
 }
 #endif

@@ -47,17 +47,8 @@ __global__ void gm_world_kernel(int64_t P, const float *__restrict__ pts, const 
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= P) return;
-    int lo = 0, hi = n_frames;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (frame_off[mid] <= i) lo = mid; else hi = mid;
-    }
-    const double *T = poses + 12 * (int64_t)lo;
-    const double p0 = pts[3 * i], p1 = pts[3 * i + 1], p2 = pts[3 * i + 2];
     double pw[3];
-    pw[0] = T[0] * p0 + T[1] * p1 + T[2] * p2 + T[9];
-    pw[1] = T[3] * p0 + T[4] * p1 + T[5] * p2 + T[10];
-    pw[2] = T[6] * p0 + T[7] * p1 + T[8] * p2 + T[11];
+    pose_apply(poses + 12 * (int64_t)frame_of_point(frame_off, n_frames, i), pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], pw);
     int64_t k[3];
     if (!root_key_of(pw, vox, k)) { *err = 1; k[0] = k[1] = k[2] = 0; }
     world[3 * i] = pw[0]; world[3 * i + 1] = pw[1]; world[3 * i + 2] = pw[2];
@@ -140,15 +131,6 @@ __global__ void fuse_kernel(int64_t n_tracks, const int64_t *__restrict__ obs_of
                flag, idx, status, Xout, err_out, kept_out);
 }
 
-int32_t check_device(int32_t device)
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return lvba_fail(LVBA_ERR_DEVICE, "no HIP device available (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return lvba_fail(LVBA_ERR_ARG, "device %d out of range [0,%d)", device, ndev);
-    return LVBA_OK;
-}
-
 } // namespace
 
 extern "C" int32_t lvba_depth_render(lvba_scans_t sc, const double *scan_poses, const double *scan_times, int32_t n_images,
@@ -173,9 +155,9 @@ extern "C" int32_t lvba_depth_render(lvba_scans_t sc, const double *scan_poses, 
         h->d_depth = (float *)raw;
     }
     struct Guard { lvba_depth_s *h; ~Guard() { if (h) { (void)hipFree(h->d_depth); delete h; } } } guard{h};
-    hipStream_t s = nullptr;
-    HIPCHK(lvba::StreamCache::get().acquire(&s));
-    struct SG { hipStream_t s; ~SG() { lvba::StreamCache::get().release(s); } } sg{s};
+    ScopedStream sg;
+    HIPCHK(sg.acquire());
+    const hipStream_t s = sg.s;
     if (n_images == 0) { *out = h; guard.h = nullptr; return LVBA_OK; }
     // every pixel starts at +inf
     HIPCHK(hipMemsetD32Async((hipDeviceptr_t)h->d_depth, 0x7f800000, (size_t)(n_images * npix), s));
@@ -316,9 +298,9 @@ extern "C" int32_t lvba_fuse_tracks(int32_t device, lvba_depth_t depth, int32_t 
     }
     TRY(check_device(device));
     HIPCHK(hipSetDevice(device));
-    hipStream_t s = nullptr;
-    HIPCHK(lvba::StreamCache::get().acquire(&s));
-    struct SG { hipStream_t s; ~SG() { lvba::StreamCache::get().release(s); } } sg{s};
+    ScopedStream sg;
+    HIPCHK(sg.acquire());
+    const hipStream_t s = sg.s;
     DevBuf d_off(s), d_img(s), d_uv(s), d_R(s), d_t(s), d_pts(s), d_dirs(s), d_flag(s), d_idx(s), d_st(s), d_X(s), d_err(s), d_kept(s);
     const size_t O1 = (size_t)std::max<int64_t>(O, 1);
     HIPCHK(d_off.alloc(8 * ((size_t)n_tracks + 1))); HIPCHK(d_img.alloc(4 * O1)); HIPCHK(d_uv.alloc(8 * O1));

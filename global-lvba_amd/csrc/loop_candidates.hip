@@ -111,9 +111,9 @@ extern "C" int32_t lvba_loop_candidates(int32_t device, int32_t n_frames, const 
     par.radius2 = o.radius * o.radius;
     const int nq = (int)(((int64_t)n + o.query_stride - 1) / o.query_stride);
     HIPCHK(hipSetDevice(device));
-    hipStream_t s = nullptr;
-    HIPCHK(StreamCache::get().acquire(&s));
-    struct SG { hipStream_t s; ~SG() { StreamCache::get().release(s); } } sg{s};
+    ScopedStream sg;
+    HIPCHK(sg.acquire());
+    const hipStream_t s = sg.s;
     DevBuf d_pos(s), d_count(s), d_first(s), d_stage(s), d_out(s);
     HIPCHK(d_pos.alloc(24 * (size_t)n)); HIPCHK(d_count.alloc(8 * ((size_t)nq + 1))); HIPCHK(d_first.alloc(8 * ((size_t)nq + 1)));
     HIPCHK(d_stage.alloc(sizeof(lvba_loop_candidate) * (size_t)nq * (size_t)o.max_per_frame));

@@ -149,10 +149,7 @@ static int32_t balm_create_impl(int32_t n_poses, int64_t n_voxels, const int64_t
     const int64_t F = voxel_off[n_voxels] - base;
     if (F < 2 * n_voxels) return fail(LVBA_ERR_ARG, "every voxel needs >= 2 factors (push_voxel, bavoxel.hpp:52)");
     if (F >= (int64_t)1 << 31) return fail(LVBA_ERR_UNSUPPORTED, "more than 2^31 factors per shard");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return fail(LVBA_ERR_DEVICE, "no HIP device available (liblvba_hip has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(LVBA_ERR_ARG, "device %d out of range [0,%d)", device, ndev);
+    TRY(lvba::check_device(device));
 
     const bool timing = timing_on("build");
     auto nowc = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };

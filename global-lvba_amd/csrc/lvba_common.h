@@ -17,6 +17,18 @@ int32_t lvba_fail(int32_t code, const char *fmt, ...);
     } while (0)
 #define TRY(expr) do { int32_t rc_ = (expr); if (rc_ != LVBA_OK) return rc_; } while (0)
 
+namespace lvba {
+// LVBA_ERR_DEVICE without a HIP device, LVBA_ERR_ARG for a device index out of range
+inline int32_t check_device(int32_t device)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        return lvba_fail(LVBA_ERR_DEVICE, "no HIP device available (this library has no CPU fallback)");
+    if (device < 0 || device >= ndev) return lvba_fail(LVBA_ERR_ARG, "device %d out of range [0,%d)", device, ndev);
+    return LVBA_OK;
+}
+} // namespace lvba
+
 struct RcclApi {
     void *lib = nullptr;
     ncclResult_t (*GetUniqueId)(ncclUniqueId *) = nullptr;

@@ -56,8 +56,8 @@ __global__ __launch_bounds__(256) void mapq_key_kernel(int64_t n, const float *_
             int64_t c[3];
             if (mapq_cell_of(w, edge, c)) {
                 valid = true;
-                k = mapq_pack(c[0], c[1], c[2]);
-                for (int j = 0; j < 3; ++j) kb[j] = (int)(c[j] + MAPQ_KEY_BIAS);
+                k = pack_key(c);
+                for (int j = 0; j < 3; ++j) kb[j] = (int)(c[j] + KEY_BIAS);
             } else {
                 atomicOr(err, 1);
             }
@@ -138,7 +138,7 @@ __global__ __launch_bounds__(64) void mapq_reduce_kernel(int64_t nq, const uint3
     const bool fin = active && mapq_finite(wf);
     int64_t c[3] = {0, 0, 0};
     if (fin) mapq_cell_of(wf, edge, c); // in range: the key kernel checked every finite point
-    const int bx = (int)c[0] + MAPQ_KEY_BIAS, by = (int)c[1] + MAPQ_KEY_BIAS, bz = (int)c[2] + MAPQ_KEY_BIAS; // biased
+    const int bx = (int)c[0] + KEY_BIAS, by = (int)c[1] + KEY_BIAS, bz = (int)c[2] + KEY_BIAS; // biased
     MapqAcc acc;
     mapq_clear(acc);
     bool todo = fin;
@@ -190,19 +190,6 @@ __global__ __launch_bounds__(64) void mapq_reduce_kernel(int64_t nq, const uint3
     prior_grid_sum<5>(v, part, ticket, out, false);
 }
 
-struct MapqTimer { // elapsed ms between events recorded on one stream
-    hipEvent_t e[4] = {};
-    bool ok = true;
-    MapqTimer() { for (auto &x : e) ok = ok && hipEventCreate(&x) == hipSuccess; }
-    ~MapqTimer() { for (auto &x : e) if (x) (void)hipEventDestroy(x); }
-    void rec(int i, hipStream_t s) { if (ok) (void)hipEventRecord(e[i], s); }
-    double ms(int a, int b) const
-    {
-        float t = 0.f;
-        return ok && hipEventElapsedTime(&t, e[a], e[b]) == hipSuccess ? (double)t : 0.0;
-    }
-};
-
 int32_t check_opts(const lvba_mapq_opts *opts, lvba_mapq_opts &o)
 {
     lvba_mapq_default_opts(&o);
@@ -230,7 +217,7 @@ int32_t fits(int64_t n, int64_t nq, double extra)
 
 // the metrics of n world points on the device (stream s, the current device); ms[0] is the caller's
 int32_t mapq_run(hipStream_t s, const float *d_world, int64_t n, const lvba_mapq_opts &o, lvba_mapq_summary *sum, double *entropy,
-                 double *plane_var, float *normal, int32_t *count, MapqTimer &ev)
+                 double *plane_var, float *normal, int32_t *count, EventTimer<4> &ev)
 {
     const int64_t stride = o.query_stride;
     const int64_t nq = (n + stride - 1) / stride;
@@ -266,13 +253,9 @@ int32_t mapq_run(hipStream_t s, const float *d_world, int64_t n, const lvba_mapq
     mapq_gather_kernel<<<grid_for(n, 256), 256, 0, s>>>(n, ckey_s.as<uint64_t>(), idx_s.as<uint32_t>(), d_world, (uint32_t)stride,
                                                         rec.as<float4>(), head.as<uint32_t>(), qflag.as<uint32_t>());
     HIPCHK(hipGetLastError());
-    TRY(scan_excl<uint32_t>(s, head.as<uint32_t>(), head_x.as<uint32_t>(), (size_t)n));
     TRY(scan_excl<uint32_t>(s, qflag.as<uint32_t>(), q_x.as<uint32_t>(), (size_t)n));
-    uint32_t last[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(&last[0], head_x.as<uint32_t>() + (n - 1), 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(&last[1], head.as<uint32_t>() + (n - 1), 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    const int64_t n_cells = (int64_t)last[0] + last[1];
+    int64_t n_cells = 0;
+    TRY(count_flags(s, head.as<uint32_t>(), head_x.as<uint32_t>(), (size_t)n, &n_cells));
     HIPCHK(ukey.alloc(8 * (size_t)n_cells)); HIPCHK(ustart.alloc(4 * (size_t)(n_cells + 1))); HIPCHK(qlist.alloc(4 * (size_t)nq));
     mapq_table_kernel<<<grid_for(n, 256), 256, 0, s>>>(n, ckey_s.as<uint64_t>(), head.as<uint32_t>(), head_x.as<uint32_t>(),
                                                        qflag.as<uint32_t>(), q_x.as<uint32_t>(), kp, n_cells, ukey.as<uint64_t>(),
@@ -329,30 +312,26 @@ extern "C" int32_t lvba_mapq_scans(lvba_scans_t sc, const double *scan_poses, in
     for (int64_t i = 0; i < 12 * (int64_t)n_frames; ++i)
         if (!std::isfinite(scan_poses[i])) return lvba_fail(LVBA_ERR_ARG, "non-finite scan pose");
     *summary = lvba_mapq_summary{};
-    std::vector<int64_t> off((size_t)n_frames + 1);
-    for (int f = 0; f <= n_frames; ++f) off[f] = sc->frame_off[frame_begin + f] - sc->frame_off[frame_begin];
-    const int64_t P = off[n_frames];
+    const int64_t P = sc->frame_off[frame_begin + n_frames] - sc->frame_off[frame_begin];
     if (P >= ((int64_t)1 << 32)) return lvba_fail(LVBA_ERR_ARG, "%lld points (at most 2^32 - 1)", (long long)P);
     HIPCHK(hipSetDevice(sc->device));
     TRY(fits(P, (P + o.query_stride - 1) / o.query_stride, 12.0 * (double)P));
-    hipStream_t s = nullptr;
-    HIPCHK(StreamCache::get().acquire(&s));
-    struct SG { hipStream_t s; ~SG() { StreamCache::get().release(s); } } sg{s};
-    MapqTimer ev;
-    DevBuf world(s), d_poses(s), d_off(s);
+    ScopedStream sg;
+    HIPCHK(sg.acquire());
+    const hipStream_t s = sg.s;
+    EventTimer<4> ev;
+    DevBuf world(s), d_poses(s);
     HIPCHK(world.alloc(12 * (size_t)std::max<int64_t>(P, 1))); HIPCHK(d_poses.alloc(96 * (size_t)n_frames));
-    HIPCHK(d_off.alloc(8 * (size_t)(n_frames + 1)));
     HIPCHK(hipMemcpyAsync(d_poses.p, scan_poses, 96 * (size_t)n_frames, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_off.p, off.data(), 8 * (size_t)(n_frames + 1), hipMemcpyHostToDevice, s));
     ev.rec(0, s);
     if (P > 0) {
-        col_world_kernel<<<grid_for(P, 256), 256, 0, s>>>(P, sc->d_pts + 3 * sc->frame_off[frame_begin], d_off.as<int64_t>(), n_frames,
+        col_world_kernel<<<grid_for(P, 256), 256, 0, s>>>(P, sc->d_pts + 3 * sc->frame_off[frame_begin], sc->d_frame_off + frame_begin, n_frames,
                                                           d_poses.as<double>(), 0.0, 0, world.as<float>(), nullptr);
         HIPCHK(hipGetLastError());
     }
     ev.rec(1, s);
     const int32_t rc = mapq_run(s, world.as<float>(), P, o, summary, entropy, plane_var, normal, count, ev);
-    HIPCHK(hipStreamSynchronize(s)); // off and scan_poses were read by now
+    HIPCHK(hipStreamSynchronize(s)); // scan_poses was read by now
     if (rc == LVBA_OK) summary->ms[0] = ev.ms(0, 1);
     return rc;
 }
@@ -367,10 +346,10 @@ extern "C" int32_t lvba_mapq_points(int32_t device, int64_t n, const float *xyz,
     *summary = lvba_mapq_summary{};
     HIPCHK(hipSetDevice(device));
     TRY(fits(n, (n + o.query_stride - 1) / o.query_stride, 12.0 * (double)n));
-    hipStream_t s = nullptr;
-    HIPCHK(StreamCache::get().acquire(&s));
-    struct SG { hipStream_t s; ~SG() { StreamCache::get().release(s); } } sg{s};
-    MapqTimer ev;
+    ScopedStream sg;
+    HIPCHK(sg.acquire());
+    const hipStream_t s = sg.s;
+    EventTimer<4> ev;
     DevBuf world(s);
     HIPCHK(world.alloc(12 * (size_t)std::max<int64_t>(n, 1)));
     const double t0 = now_ms();

@@ -13,11 +13,11 @@
 #include <math.h>
 #include <stdint.h>
 #include "balm_math.h"
+#include "scan_points.h"
 
 namespace lvba {
 
-constexpr int MAPQ_KEY_BIAS = 1 << 20;             // the packing of voxel_internal.h (pack_key)
-constexpr int MAPQ_CELL_LIMIT = (1 << 20) - 1;     // |cell| < this: the neighbour cells c +- 1 stay packable
+constexpr int MAPQ_CELL_LIMIT = KEY_BIAS - 1;      // |cell| < this: the neighbour cells c +- 1 stay packable (pack_key, scan_points.h)
 
 LVBA_HD double mapq_cell_edge(double radius) { return radius * (1.0 + 1.0 / 1048576.0); }
 LVBA_HD bool mapq_finite(const float w[3]) { return isfinite(w[0]) && isfinite(w[1]) && isfinite(w[2]); }
@@ -32,9 +32,11 @@ LVBA_HD bool mapq_cell_of(const float w[3], double edge, int64_t c[3])
     }
     return ok;
 }
-LVBA_HD uint64_t mapq_pack(int64_t x, int64_t y, int64_t z) // pack_key's layout
+// pack_key (scan_points.h) of a cell, under the name tests/mapq_check.cpp binds; new code calls pack_key
+LVBA_HD uint64_t mapq_pack(int64_t x, int64_t y, int64_t z)
 {
-    return ((uint64_t)(x + MAPQ_KEY_BIAS) << 42) | ((uint64_t)(y + MAPQ_KEY_BIAS) << 21) | (uint64_t)(z + MAPQ_KEY_BIAS);
+    const int64_t c[3] = {x, y, z};
+    return pack_key(c);
 }
 
 struct MapqAcc {

@@ -158,6 +158,33 @@ class StreamCache {
     std::map<hipStream_t, int> owner_;
 };
 
+// A cached stream of the current device for one scope: acquire() takes it, the destructor gives it back.  Declare it before the
+// DevBufs bound to the stream (they drain it when they go).
+struct ScopedStream {
+    hipStream_t s = nullptr;
+    ScopedStream() {}
+    ScopedStream(const ScopedStream &) = delete;
+    ScopedStream &operator=(const ScopedStream &) = delete;
+    ~ScopedStream() { StreamCache::get().release(s); }
+    hipError_t acquire() { return StreamCache::get().acquire(&s); }
+};
+
+// elapsed ms between N events recorded on one stream (0 when an event could not be created)
+template <int N> struct EventTimer {
+    hipEvent_t e[N] = {};
+    bool ok = true;
+    EventTimer() { for (auto &x : e) ok = ok && hipEventCreate(&x) == hipSuccess; }
+    EventTimer(const EventTimer &) = delete;
+    EventTimer &operator=(const EventTimer &) = delete;
+    ~EventTimer() { for (auto &x : e) if (x) (void)hipEventDestroy(x); }
+    void rec(int i, hipStream_t s) { if (ok) (void)hipEventRecord(e[i], s); }
+    double ms(int a, int b) const
+    {
+        float t = 0.f;
+        return ok && hipEventElapsedTime(&t, e[a], e[b]) == hipSuccess ? (double)t : 0.0;
+    }
+};
+
 // Pinned staging memory for the scan upload (voxelize.hip: 24 MB per call): hipHostMalloc / hipHostFree of that size cost
 // milliseconds and the unpinning stalls the device's queues (host_arena.h); a refinement handle's three small zero-copy blocks come
 // from here too.  Blocks are allocated portable + mapped: a block pinned under one device is reused as zero-copy / staging memory

@@ -262,11 +262,6 @@ int32_t search_dev(hipStream_t s, int n, const float *d_desc, const PlaceParams 
     return LVBA_OK;
 }
 
-struct StreamGuard {
-    hipStream_t s = nullptr;
-    ~StreamGuard() { StreamCache::get().release(s); }
-};
-
 } // namespace
 
 extern "C" void lvba_place_default_opts(lvba_place_opts *o)
@@ -291,8 +286,8 @@ extern "C" int32_t lvba_place_descriptors(lvba_scans_t sc, int32_t frame_begin, 
     if (n_frames == 0) return LVBA_OK;
     const size_t cells = (size_t)p.n_rings * p.n_sectors, n = (size_t)n_frames;
     HIPCHK(hipSetDevice(sc->device));
-    StreamGuard sg;
-    HIPCHK(StreamCache::get().acquire(&sg.s));
+    ScopedStream sg;
+    HIPCHK(sg.acquire());
     DevBuf d_desc(sg.s), d_key(sg.s);
     HIPCHK(d_desc.alloc(4 * n * cells)); HIPCHK(d_key.alloc(4 * n * p.n_rings));
     TRY(describe_dev(sg.s, sc, frame_begin, n_frames, p, d_desc.as<float>()));
@@ -319,8 +314,8 @@ extern "C" int32_t lvba_place_search(int32_t device, int32_t n_frames, const flo
             return lvba_fail(LVBA_ERR_ARG, "frame %d: descriptor value %g (finite and >= 0)", (int)(i / cells), (double)desc[i]);
     if (n == 0) return LVBA_OK;
     HIPCHK(hipSetDevice(device));
-    StreamGuard sg;
-    HIPCHK(StreamCache::get().acquire(&sg.s));
+    ScopedStream sg;
+    HIPCHK(sg.acquire());
     DevBuf d_desc(sg.s);
     HIPCHK(d_desc.alloc(4 * n * cells));
     HIPCHK(lvba::copy_h2d(d_desc.p, desc, 4 * n * cells));
@@ -338,8 +333,8 @@ extern "C" int32_t lvba_place_candidates(lvba_scans_t sc, const lvba_place_opts 
     const int n = sc->n_frames;
     if (n == 0) return LVBA_OK;
     HIPCHK(hipSetDevice(sc->device));
-    StreamGuard sg;
-    HIPCHK(StreamCache::get().acquire(&sg.s));
+    ScopedStream sg;
+    HIPCHK(sg.acquire());
     DevBuf d_desc(sg.s);
     HIPCHK(d_desc.alloc(4 * (size_t)n * p.n_rings * p.n_sectors));
     TRY(describe_dev(sg.s, sc, 0, n, p, d_desc.as<float>()));

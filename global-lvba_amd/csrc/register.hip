@@ -78,7 +78,7 @@ __global__ __launch_bounds__(REG_BLOCK) void reg_linearize_kernel(const VoxLooku
     for (int64_t i = (int64_t)blockIdx.x * REG_BLOCK + threadIdx.x; i < m; i += (int64_t)nb * REG_BLOCK) {
         const double p[3] = {(double)P[3 * i], (double)P[3 * i + 1], (double)P[3 * i + 2]};
         double w[3], pl[4];
-        reg_world(T, p, w);
+        pose_apply(T, p[0], p[1], p[2], w);
         if (vox_find_plane(w, map.vs, r0, r1, map.root_key, map.mask, map.rootinfo, map.plane_first, map.plane, pl))
             reg_point(T, p, w, pl, o, s);
     }
@@ -179,9 +179,9 @@ int32_t reg_run(lvba_voxmap_t map, lvba_scans_t sc, int32_t n, const int32_t *fr
         max_blocks = std::max(max_blocks, reg_blocks(sc->frame_off[frames[k] + 1] - sc->frame_off[frames[k]]));
     }
     HIPCHK(hipSetDevice(device));
-    hipStream_t s = nullptr;
-    HIPCHK(StreamCache::get().acquire(&s));
-    struct SG { hipStream_t s; ~SG() { StreamCache::get().release(s); } } sg{s};
+    ScopedStream sg;
+    HIPCHK(sg.acquire());
+    const hipStream_t s = sg.s;
     const int max_it = sums_only ? 1 : o.max_iterations;
     PinnedWords words;
     HIPCHK(PinnedCache::get().acquire((void **)&words.p, 4096)); // (>= 1000 words; one size for the cache's sake)

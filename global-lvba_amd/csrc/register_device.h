@@ -2,7 +2,7 @@
 // rule and the per-job Gauss-Newton step.  Also compiles as plain C++ (tests/register_check.cpp).  All arithmetic is fp64; the
 // including file is built without floating-point contraction (the inlier gate is a discrete decision on a residual).
 //   A job is a cloud of body-frame points p (fp32, promoted once) and a pose T = (R row-major | t).  Per point
-//     w = (R00 px + R01 py) + R02 pz + tx, ...                         the world point
+//     w = (R00 px + R01 py) + R02 pz + tx, ...                         the world point (pose_apply, scan_points.h)
 //     (n, d)                                                            its plane (voxel_lookup.h), if any
 //     r = (n0 w0 + n1 w1) + n2 w2 + d                                   inlier iff a plane was found and |r| <= max_distance
 //     J = [ p x (R^T n) ; n ]                                           d r / d(theta, t) under R <- R Exp(theta), t <- t + delta
@@ -16,6 +16,7 @@
 #include <stdint.h>
 #include "visual_loss.h"
 #include "prior_device.h"
+#include "scan_points.h"
 
 namespace lvba {
 
@@ -31,12 +32,8 @@ struct RegParams { // lvba_register_opts on the device
     int32_t loss_kind;
 };
 
-LVBA_HD void reg_world(const double *T, const double p[3], double w[3])
-{
-    w[0] = (T[0] * p[0] + T[1] * p[1]) + T[2] * p[2] + T[9];
-    w[1] = (T[3] * p[0] + T[4] * p[1]) + T[5] * p[2] + T[10];
-    w[2] = (T[6] * p[0] + T[7] * p[1]) + T[8] * p[2] + T[11];
-}
+// pose_apply (scan_points.h) under the name tests/register_check.cpp binds; new code calls pose_apply
+LVBA_HD void reg_world(const double *T, const double p[3], double w[3]) { pose_apply(T, p[0], p[1], p[2], w); }
 
 LVBA_HD double reg_residual(const double w[3], const double pl[4]) { return (pl[0] * w[0] + pl[1] * w[1]) + pl[2] * w[2] + pl[3]; }
 

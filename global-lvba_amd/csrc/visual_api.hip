@@ -118,10 +118,7 @@ extern "C" int32_t lvba_visual_create(int32_t n_cams, int64_t n_tracks, const in
     const int64_t base = obs_off[0];
     const int64_t Oall = obs_off[n_tracks] - base;
     if (Oall > 0 && (!obs_cam || !obs_uv)) return fail(LVBA_ERR_ARG, "observation arrays are NULL");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return fail(LVBA_ERR_DEVICE, "no HIP device available (liblvba_hip has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(LVBA_ERR_ARG, "device %d out of range [0,%d)", device, ndev);
+    TRY(lvba::check_device(device));
     lvba_visual_s *h = new (std::nothrow) lvba_visual_s();
     if (!h) return fail(LVBA_ERR_NOMEM, "host allocation failed");
     h->M = n_cams; h->T = n_tracks; h->sig_px = sigma_px; h->sig_pl = sigma_plane;

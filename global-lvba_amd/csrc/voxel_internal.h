@@ -1,5 +1,7 @@
-// voxel_internal.h -- pieces shared by the voxel front-end (voxelize.hip) and the window-BA driver (window_ba.hip):
-// the device-resident scan set, rocPRIM wrappers on the caching pool, small utilities.
+// voxel_internal.h -- pieces shared by the front ends that work on the device-resident scan set (voxelize.hip, window_ba.hip,
+// fusion.hip, colorize.hip, map_quality.hip, register.hip, ...): the scan set itself, rocPRIM wrappers on the caching pool, the
+// root key of cut_voxel, the key-range reduction.  The per-point rules (frame of a point, pose, leaf key, key packing) are
+// scan_points.h.
 #pragma once
 #include "host_arena.h"
 #include <cstring>
@@ -10,6 +12,7 @@
 #include "lvba_common.h"
 #include "mempool.h"
 #include "key_pack.h"
+#include "scan_points.h"
 #include "wave_ops.h"
 
 struct lvba_scans_s {
@@ -92,10 +95,21 @@ inline int32_t scan_excl(hipStream_t s, const T *in, T *out, size_t n)
     HIPCHK(hipStreamSynchronize(s));
     return LVBA_OK;
 }
+// exclusive scan of n >= 1 0/1 flags and their number: one stream-ordered read of the last excl and the last flag
+// (scan_excl waits for the stream itself: a count costs two synchronisations, as the open-coded form did)
+inline int32_t count_flags(hipStream_t s, const uint32_t *flag, uint32_t *excl, size_t n, int64_t *count)
+{
+    TRY(scan_excl<uint32_t>(s, flag, excl, n));
+    uint32_t last[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(&last[0], excl + (n - 1), 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&last[1], flag + (n - 1), 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *count = (int64_t)last[0] + last[1];
+    return LVBA_OK;
+}
 
 
-// ---- voxel keys shared by the plane map (voxelize.hip) and the depth grid map (fusion.hip) --------------------------
-constexpr int KEY_BIAS = 1 << 20; // key components must lie in [-2^20, 2^20)
+// ---- root key shared by the plane map (voxelize.hip) and the depth grid map (fusion.hip); packed by pack_key (scan_points.h)
 // (int64)(float)(p / vs), minus one for negatives (cut_voxel, bavoxel.hpp:809-815; the same rule at src/lvba_system.cpp:1289-1293
 // and :1539-1544)
 __device__ __forceinline__ bool root_key_of(const double pw[3], double vs, int64_t k[3])
@@ -109,10 +123,6 @@ __device__ __forceinline__ bool root_key_of(const double pw[3], double vs, int64
         k[j] = ok ? (int64_t)loc : 0;
     }
     return ok;
-}
-__device__ __forceinline__ uint64_t pack_key(const int64_t k[3])
-{
-    return ((uint64_t)(k[0] + KEY_BIAS) << 42) | ((uint64_t)(k[1] + KEY_BIAS) << 21) | (uint64_t)(k[2] + KEY_BIAS);
 }
 
 // ---- sorting on the bits that vary --------------------------------------------------------------------------------

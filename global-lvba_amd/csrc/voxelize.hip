@@ -52,19 +52,10 @@ __global__ void vox_key_kernel(int64_t P, const float *__restrict__ pts, const i
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     int kb[3] = {0, 0, 0};
     if (i < P) {
-    const int64_t base = frame_off[0];
-    int lo = 0, hi = n_frames; // frame f with frame_off[f] <= base + i < frame_off[f+1]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (frame_off[mid] - base <= i) lo = mid; else hi = mid;
-    }
-    const double *T = poses + 12 * (int64_t)lo;
+    const int lo = frame_of_point(frame_off, n_frames, i);
     const float fx = pts[3 * i], fy = pts[3 * i + 1], fz = pts[3 * i + 2];
-    const double p0 = fx, p1 = fy, p2 = fz;
     double pw[3];
-    pw[0] = T[0] * p0 + T[1] * p1 + T[2] * p2 + T[9];
-    pw[1] = T[3] * p0 + T[4] * p1 + T[5] * p2 + T[10];
-    pw[2] = T[6] * p0 + T[7] * p1 + T[8] * p2 + T[11];
+    pose_apply(poses + 12 * (int64_t)lo, fx, fy, fz, pw);
     int64_t k[3];
     if (!root_key_of(pw, vs, k)) { *err = 1; k[0] = k[1] = k[2] = 0; }
     int o1, o2;
@@ -80,19 +71,9 @@ __global__ void vox_key_kernel(int64_t P, const float *__restrict__ pts, const i
 // records into sorted order, the sorted keys back in their 3 x 21-bit form, and the head flags of the sorted sequence in the same
 // pass: heads[i] = (first record of a root) << 32 | (first record of a (root, frame) segment) -- one 64-bit word, so that ONE
 // inclusive scan numbers roots and segments together.  The frame of a record is found from its index in the window's points (a
-// search over <= 2^25 frame offsets that sit in the scalar cache): the flags need no second gather.
+// search over <= 2^25 frame offsets that sit in the scalar cache, frame_of_point of scan_points.h): the flags need no second gather.
 // (ws > 0, joint map of several windows: a root is (window, key), window = frame / ws -- the window index sits above the key bits
 // of the compressed key, so "the compressed key changed" covers it)
-__device__ __forceinline__ int frame_of_point(const int64_t *__restrict__ frame_off, int n_frames, int64_t i)
-{
-    const int64_t base = frame_off[0];
-    int lo = 0, hi = n_frames; // frame f with frame_off[f] <= base + i < frame_off[f+1]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (frame_off[mid] - base <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
 template <class K>
 __global__ void vox_gather_kernel(int64_t n, const float4 *__restrict__ rec, const uint32_t *__restrict__ order,
                                   float4 *__restrict__ out, const K *__restrict__ ckey_s, const KeyPack kp, uint64_t *__restrict__ key_s,
@@ -729,10 +710,7 @@ extern "C" int32_t lvba_scans_create(int32_t device, int32_t n_frames, const voi
     if (n_frames < 1 || !frame_points || !frame_count) return lvba_fail(LVBA_ERR_ARG, "n_frames < 1 or a null argument");
     if (point_stride_bytes < 12 || point_stride_bytes % 4)
         return lvba_fail(LVBA_ERR_ARG, "point_stride_bytes must be a multiple of 4 and >= 12 (got %d)", point_stride_bytes);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return lvba_fail(LVBA_ERR_DEVICE, "no HIP device available (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return lvba_fail(LVBA_ERR_ARG, "device %d out of range [0,%d)", device, ndev);
+    TRY(lvba::check_device(device));
     HIPCHK(hipSetDevice(device));
     for (int f = 0; f < n_frames; ++f)
         if (frame_count[f] < 0 || (frame_count[f] > 0 && !frame_points[f]))

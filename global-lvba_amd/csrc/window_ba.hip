@@ -23,8 +23,6 @@ using namespace lvba;
 
 namespace {
 
-constexpr int KEY_BIAS = 1 << 20;
-
 // merged cloud of one window: every point moved into the anchor frame with its frame's relative pose and rounded to fp32
 // (pl_transform); plus the leaf-voxel key and squared distance to the voxel centre of down_sampling_voxel2.
 __global__ void wba_merge_kernel(int64_t P, const float *__restrict__ pts, const int64_t *__restrict__ frame_off, int n_frames,
@@ -35,33 +33,14 @@ __global__ void wba_merge_kernel(int64_t P, const float *__restrict__ pts, const
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     int kb[3] = {0, 0, 0};
     if (i < P) {
-    const int64_t base = frame_off[0];
-    int lo = 0, hi = n_frames;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (frame_off[mid] - base <= i) lo = mid; else hi = mid;
-    }
-    const double *T = rel + 12 * (int64_t)lo;
-    const double p0 = pts[3 * i], p1 = pts[3 * i + 1], p2 = pts[3 * i + 2];
-    const float q[3] = {(float)(T[0] * p0 + T[1] * p1 + T[2] * p2 + T[9]), (float)(T[3] * p0 + T[4] * p1 + T[5] * p2 + T[10]),
-                        (float)(T[6] * p0 + T[7] * p1 + T[8] * p2 + T[11])};
+    float q[3];
+    pose_apply_f32(rel + 12 * (int64_t)frame_of_point(frame_off, n_frames, i), pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], q);
     out[3 * i] = q[0]; out[3 * i + 1] = q[1]; out[3 * i + 2] = q[2];
     if (key) {
     int64_t k[3];
-    double dd = 0.0;
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        float loc = (float)((double)q[j] / leaf);
-        if (loc < 0.f) loc -= 1.f;
-        ok = ok && (fabsf(loc) < (float)KEY_BIAS);
-        k[j] = ok ? (int64_t)loc : 0;
-        const double c = ((double)k[j] + 0.5) * leaf;
-        const double d = (double)q[j] - c;
-        dd = __dadd_rn(dd, __dmul_rn(d, d)); // dx*dx + dy*dy + dz*dz, left to right, no contraction
-    }
-    if (!ok) *err = 1;
-    key[i] = ((uint64_t)(k[0] + KEY_BIAS) << 42) | ((uint64_t)(k[1] + KEY_BIAS) << 21) | (uint64_t)(k[2] + KEY_BIAS);
+    double dd;
+    if (!leaf_key_of(q, leaf, k, dd)) *err = 1;
+    key[i] = pack_key(k);
     d2[i] = dd;
     idx[i] = (uint32_t)i;
 #pragma unroll
@@ -111,13 +90,7 @@ __global__ void wba_compress_win_kernel(int64_t P, const uint64_t *key, const in
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= P) return;
-    const int64_t base = frame_off[0];
-    int lo = 0, hi = n_frames;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (frame_off[mid] - base <= i) lo = mid; else hi = mid;
-    }
-    const uint64_t c = code[lo / ws];
+    const uint64_t c = code[frame_of_point(frame_off, n_frames, i) / ws];
     out[i] = (K)((c << kp.total) | key_compress<uint64_t>(key[i], kp)); // (in 64 bits, narrowed afterwards: key_pack.h)
 }
 // anchor points of every window: the scan of the leader flags read at the windows' bounds in the sorted sequence

@@ -90,3 +90,14 @@ def test_key_repacking_keeps_order_and_round_trips(tmp_path):
     subprocess.check_call(["g++", "-O2", "-std=c++17", os.path.join(ROOT, "tests", "key_pack_check.cpp"), "-o", exe])
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 0 and "key pack ok" in out.stdout, out.stdout[-2000:]
+
+
+def test_scan_point_rules(tmp_path):
+    """csrc/scan_points.h: the frame of a point against a linear scan (empty frames, offsets that start at 0 or not), the leaf
+    key, its squared distance and the 3 x 21-bit packing against the literal expressions of down_sampling_voxel2 at the edges
+    of the rule (+-0, +-leaf and its neighbours, the ends of the packable range, NaN), the pose rows (tests/scan_points_check.cpp)."""
+    exe = str(tmp_path / "scan_points_check")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror",
+                           os.path.join(ROOT, "tests", "scan_points_check.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and "scan points ok" in out.stdout, out.stdout[-3000:]
