@@ -33,6 +33,7 @@ SYMBOLS = [
     "lvba_submaps_build", "lvba_submaps_count", "lvba_submaps_find_planes", "lvba_register_linearize_submaps",
     "lvba_register_scans_submaps", "lvba_loop_default_opts", "lvba_loop_candidates",
     "lvba_place_default_opts", "lvba_place_descriptors", "lvba_place_search", "lvba_place_candidates",
+    "lvba_closure_default_opts", "lvba_closure_consistency",
 ]
 
 OK, ERR_ARG, ERR_DEVICE, ERR_NOMEM, ERR_UNSUPPORTED, ERR_DIST, ERR_STATE = 0, -1, -2, -3, -4, -5, -6
@@ -177,6 +178,11 @@ class PlaceOpts(C.Structure):
 class PlaceCandidate(C.Structure):
     _fields_ = [("query", C.c_int32), ("submap", C.c_int32), ("ref", C.c_int32), ("shift", C.c_int32), ("distance", C.c_double),
                 ("yaw", C.c_double)]
+
+
+class ClosureOpts(C.Structure):
+    _fields_ = [("rot_tol", C.c_double), ("rot_rate", C.c_double), ("trans_tol", C.c_double), ("trans_rate", C.c_double),
+                ("n_seeds", C.c_int32), ("min_set", C.c_int32)]
 
 
 class VoxelOpts(C.Structure):
@@ -388,6 +394,10 @@ def load():
     lib.lvba_place_descriptors.argtypes = [H, C.c_int32, C.c_int32, C.POINTER(PlaceOpts), C.c_void_p, C.c_void_p]
     lib.lvba_place_search.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.POINTER(PlaceOpts), C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]
     lib.lvba_place_candidates.argtypes = [H, C.POINTER(PlaceOpts), C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]
+    lib.lvba_closure_default_opts.argtypes = [C.POINTER(ClosureOpts)]
+    lib.lvba_closure_default_opts.restype = None
+    lib.lvba_closure_consistency.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.POINTER(ClosureOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
     lib.lvba_scans_info.argtypes = [H, C.POINTER(C.c_int32), C.c_void_p]
     lib.lvba_scans_download.argtypes = [H, C.c_int32, np.ctypeslib.ndpointer(np.float32, flags="C")]
     for name in SYMBOLS:

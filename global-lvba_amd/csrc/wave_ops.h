@@ -50,6 +50,10 @@ struct MaxStepI32 { // of values >= 0
     template <int CTRL, int ROW_MASK>
     static __device__ __forceinline__ int step(int v) { return max(v, dpp_i32<CTRL, ROW_MASK>(0, v)); }
 };
+struct SumStepI32 { // integers add exactly: the order is of no account
+    template <int CTRL, int ROW_MASK>
+    static __device__ __forceinline__ int step(int v) { return v + dpp_i32<CTRL, ROW_MASK>(0, v); }
+};
 struct SumStepF64 {
     template <int CTRL, int ROW_MASK>
     static __device__ __forceinline__ double step(double v) { return v + dpp_f64<CTRL, ROW_MASK>(0.0, v); }

@@ -381,7 +381,7 @@ def loop_acceptance(status, inliers, points, rmse, rot, trans, min_inlier_frac=0
 
 def find_loop_closures(scans, poses, submap_size=10, voxel_size=1.0, eigen_ratio_array=None, radius=5.0, min_gap=50, max_per_frame=2,
                        query_stride=1, min_inlier_frac=0.3, max_rmse=None, max_rot=None, max_trans=None, sigma=None, method="pose",
-                       place=None, **register_opts):
+                       place=None, consistency=None, **register_opts):
     """Loop closures of a trajectory, found and verified on the GPU: the submap set of all frames of `scans` at their current
     `poses` [n,12] is built in one pass (Scans.submaps, eigen ratios register.STRICT_RATIO by default: DESIGN.md §10c), the
     candidates (query frame, submap, reference frame ref) are found, and ALL candidates are registered in one call, each query
@@ -405,7 +405,12 @@ def find_loop_closures(scans, poses, submap_size=10, voxel_size=1.0, eigen_ratio
     ref, method ("pose", "descriptor", or "both" for a pair that both found), distance and distance_kind ("metres" between the
     positions for a pose candidate, "descriptor" for the shift distance in [0, 1]), shift and yaw (None for a pose candidate),
     start, the registration's fields (pose, information, status, status_name, iterations, inliers, points, cost_first,
-    cost_last, rmse, min_eigenvalue), rot / trans (the correction), accepted and reason (None when accepted)."""
+    cost_last, rmse, min_eigenvalue), rot / trans (the correction), accepted and reason (None when accepted).
+    consistency: None (default: off, nothing more is launched and the report is as above), True, or a dict of
+    register.closure_consistency's options: the candidates that loop_acceptance accepted are tested pairwise against the relative
+    motion of `poses` between them and only the largest mutually consistent set found yields priors (consistent_closures,
+    DESIGN.md §10f).  A candidate outside it gets accepted=False, reason="consistency"; every report entry gains `consistent`:
+    True, False, or None for a candidate that was not accepted in the first place."""
     from .register import STRICT_RATIO, loop_candidates, place_candidates
     if method not in ("pose", "descriptor", "both"):
         raise ValueError(f"method {method!r}: one of 'pose', 'descriptor', 'both'")
@@ -434,6 +439,8 @@ def find_loop_closures(scans, poses, submap_size=10, voxel_size=1.0, eigen_ratio
             key = (int(cand["query"][k]), int(cand["submap"][k]))
             found[key] = dict(ref=int(cand["ref"][k]), method="both" if key in found else "pose", distance=float(cand["distance"][k]),
                               distance_kind="metres", shift=None, yaw=None, start=x[key[0]].copy())
+    if consistency is not None and consistency is not True and not isinstance(consistency, dict):
+        raise TypeError("consistency: None, True or a dict of closure_consistency's options")
     priors, report = [], []
     if not found:
         return priors, report
@@ -455,7 +462,45 @@ def find_loop_closures(scans, poses, submap_size=10, voxel_size=1.0, eigen_ratio
         report.append(r)
         if ok:
             priors.append(registration_prior(r["ref"], r["query"], x[r["ref"]], r["pose"], r["information"], r["rmse"], r["status"], sigma))
+    if consistency is not None:
+        priors, keep = consistent_closures(x, priors, device=getattr(scans, "device", 0), **(consistency if isinstance(consistency, dict) else {}))
+        verdict = iter(keep)
+        for r in report:
+            r["consistent"] = bool(next(verdict)) if r["accepted"] else None
+            if r["consistent"] is False:
+                r["accepted"], r["reason"] = False, "consistency"
     return priors, report
+
+
+def consistent_closures(poses, priors, device=0, **opts):
+    """The loop closures among `priors` that agree with one another over the relative motion of the current `poses` [n,12]
+    between them (register.closure_consistency; opts: its options): (kept priors, keep mask [len(priors)] of
+    bool).  priors: balm.Prior.relative objects with identity offsets, as find_loop_closures returns them -- ValueError for any
+    other.  A closure is tested with its earlier frame as ref, whichever way the prior names the two.  A per-candidate check
+    (loop_acceptance) cannot tell a registration that converged well on the wrong place; a closure
+    that contradicts the largest mutually consistent set can, and is voted out here."""
+    from . import _lib as L
+    from .register import closure_consistency
+    identity = [1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0]
+    priors = list(priors)
+    for k, p in enumerate(priors):
+        if getattr(p, "kind", None) != L.PRIOR_KINDS["relative"]:
+            raise ValueError(f"prior {k} is not a relative prior")
+        for off in (p.offset_i, p.offset_j):
+            if any(v != 0.0 for v in off) and list(off) != identity:
+                raise ValueError(f"prior {k} has a body-frame offset: the cycle is between the frames themselves")
+    # The cycle of two closures runs over the odometry from ref to ref and from query to query, so two closures that say the same
+    # must name their frames in the same order: every closure goes in with its earlier frame as ref, (j, i, Z^-1) for (i, j, Z).
+    ref, query, meas = [], [], np.zeros((len(priors), 12))
+    for k, p in enumerate(priors):
+        z = np.array(list(p.meas), np.float64)
+        if p.i > p.j:
+            R = z[:9].reshape(3, 3)
+            z = np.r_[R.T.reshape(9), -(R.T @ z[9:])]
+        ref.append(min(p.i, p.j)); query.append(max(p.i, p.j))
+        meas[k] = z
+    got = closure_consistency(poses, ref, query, meas, device=device, **opts)
+    return [p for p, k in zip(priors, got["keep"]) if k], got["keep"]
 
 
 _map_quality = map_quality   # run_full_pipeline / run_dataset have a keyword of that name
@@ -524,7 +569,8 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
     mean plane variance of the scans at the refined and at the original poses (off by default: nothing is launched).
     loop_closures: None (off: nothing is launched), True, or a dict of find_loop_closures' keywords: loop closures are detected on
     the input poses before the LiDAR stage, the accepted priors are appended to lidar_priors and the output holds
-    loop_closures = the report."""
+    loop_closures = the report.  With consistency=True (or a dict of options) among the keywords the accepted closures are vetted
+    against one another first (consistent_closures) and only the mutually consistent ones become priors."""
     if images is not None and not enable_visual_ba:
         raise ValueError("colouring the map needs the cameras of the visual stage (enable_visual_ba=True)")
     c = dict(DEFAULTS); c.update(cfg)
@@ -599,7 +645,7 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
     map_quality (True or a dict of keywords, as for run_full_pipeline): the output gains map_quality and out_dir gets
     map_quality.json, the two summaries.
     loop_closures (True or a dict of keywords, as for run_full_pipeline): the output gains loop_closures and out_dir gets
-    loop_closures.json, the report without its arrays.
+    loop_closures.json, the report without its arrays; dict(consistency=True, ...) vets the closures against one another.
     cfg as for run_full_pipeline, e.g. visual_loss=REFERENCE_HUBER, window_loss=("cauchy", 0.1), stage_loss=("huber", 0.05),
     camera_priors=lambda cams: lidar_camera_priors(cams, Rci, tci, 1e-3, 0.02)."""
     import os

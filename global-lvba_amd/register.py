@@ -185,3 +185,40 @@ def place_candidates(scans, capacity=None, **opts):
     o = _place_opts(opts)
     lib = L.load()
     return _place_result(lambda po, cap, out, cnt: lib.lvba_place_candidates(scans._h, po, cap, out, cnt), scans.n_frames, o, capacity)
+
+
+CLOSURE_OPTS = ("rot_tol", "rot_rate", "trans_tol", "trans_rate", "n_seeds", "min_set")
+
+
+def closure_consistency(poses, ref, query, meas, device=0, diagnostics=False, **opts):
+    """Pairwise consistency of loop closures (lvba_closure_consistency; include/lvba_hip.h has the exact rule, after Mangelson et
+    al., PCM, ICRA 2018): closure k measures meas[k] = T_ref^-1 T_query (12 numbers, R row-major | t); every pair of closures is
+    tested against the relative motion of the current `poses` [n_frames,12] between them, and a large mutually consistent set is
+    kept by a greedy search from n_seeds seeds (not guaranteed to be the largest).  opts: rot_tol [rad], rot_rate [rad per frame],
+    trans_tol [m], trans_rate [m per frame], n_seeds, min_set.  Returns dict(keep bool [n], n_keep, adjacency bool [n,n], words
+    uint64 [n, ceil(n/64)] as the library lays the adjacency out) and, with diagnostics=True, rot / trans [n,n] (the two measures
+    of every cycle; n * n doubles each)."""
+    x = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
+    z = np.ascontiguousarray(meas, np.float64).reshape(-1, 12)
+    i, j = np.ascontiguousarray(ref, np.int32).reshape(-1), np.ascontiguousarray(query, np.int32).reshape(-1)
+    n = len(z)
+    if len(i) != n or len(j) != n:
+        raise ValueError(f"{n} measurements for {len(i)} ref and {len(j)} query frames")
+    o = L.ClosureOpts()
+    lib = L.load()
+    lib.lvba_closure_default_opts(C.byref(o))
+    for k, v in opts.items():
+        if k not in CLOSURE_OPTS:
+            raise TypeError(f"unknown closure option {k!r}; one of {CLOSURE_OPTS}")
+        setattr(o, k, type(getattr(o, k))(v))
+    W = (n + 63) // 64
+    words, keep, n_keep = np.zeros((n, W), np.uint64), np.zeros(n, np.uint8), C.c_int32()
+    rot, trans = (np.zeros((n, n)), np.zeros((n, n))) if diagnostics else (None, None)
+    L.check(lib.lvba_closure_consistency(int(device), len(x), x.ctypes.data, n, i.ctypes.data, j.ctypes.data, z.ctypes.data, C.byref(o),
+                                         words.ctypes.data, rot.ctypes.data if diagnostics else None,
+                                         trans.ctypes.data if diagnostics else None, keep.ctypes.data, C.byref(n_keep)))
+    adj = np.unpackbits(words.view(np.uint8).reshape(n, 8 * W), axis=1, bitorder="little")[:, :n].astype(bool) if n else np.zeros((0, 0), bool)
+    d = dict(keep=keep.astype(bool), n_keep=int(n_keep.value), adjacency=adj, words=words)
+    if diagnostics:
+        d.update(rot=rot, trans=trans)
+    return d

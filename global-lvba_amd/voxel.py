@@ -77,6 +77,7 @@ class Scans:
             ptrs[f] = c.ctypes.data if c.shape[0] else None
             counts[f] = c.shape[0]
         self.n_frames = n
+        self.device = int(device)
         self.counts = counts[:n].copy()
         self._h = C.c_void_p()
         L.check(self.lib.lvba_scans_create(int(device), n, ptrs, counts, int(stride or 12), C.byref(self._h)))

@@ -936,6 +936,50 @@ int32_t lvba_place_search(int32_t device, int32_t n_frames, const float *desc, c
 int32_t lvba_place_candidates(lvba_scans_t scans, const lvba_place_opts *o, int64_t capacity, lvba_place_candidate *out,
                               int64_t *count);
 
+/* ---- pairwise consistency of loop closures: voting out a closure that contradicts the others -----------------
+ *   After Mangelson et al., "Pairwise Consistent Measurement Set Maximization", ICRA 2018, with fixed tolerances in place of the
+ *   Mahalanobis test (the project has no odometry covariance to put in one).
+ *   A closure k = (i_k = ref[k], j_k = query[k], Z_k = meas[k]): Z_k is the measured T_i^-1 T_j, 12 doubles, R row-major then t --
+ *   the `meas` of an LVBA_PRIOR_RELATIVE prior between ref and query.  poses [n_frames][12] are the current (possibly drifted)
+ *   poses X; their local relative motion is trusted.  X_pq = X_p^-1 X_q.
+ *   Cycle of two closures a < b (positions in the caller's list):
+ *     E_ab = Z_a . X_{j_a j_b} . Z_b^-1 . X_{i_b i_a}        the identity if both closures and the odometry agree; in the frame of i_a
+ *     rot_ab = |Log(R_E)|, the angle atan2(|vee(R_E - R_E^T)| / 2, (tr R_E - 1) / 2);   trans_ab = |t_E|
+ *     L_ab = |j_a - j_b| + |i_a - i_b|                          the odometry steps in the cycle
+ *   The pair is consistent iff rot_ab <= rot_tol + rot_rate L_ab and trans_ab <= trans_tol + trans_rate L_ab (the right-hand sides
+ *   in fp64, rounded as written).  The pair (b, a) takes the decision and the two values of (a, b): the matrix is exactly
+ *   symmetric.  A closure is consistent with itself; rot_aa = trans_aa = 0.  The odometry legs run from ref to ref and from query
+ *   to query: closures that are to agree must name their frames in the same order (the earlier frame as ref, say), and (j, i,
+ *   Z^-1) is to be given for (i, j, Z) where they do not.  The values are computed from the prepared form
+ *   P_k = X_j Z_k^-1 X_i^-1, E_ab = X_{i_a}^-1 P_a^-1 P_b X_{i_a}, and agree with the six compositions above to rounding.
+ *   adjacency [n][W] of uint64_t, W = ceil(n / 64): bit (b mod 64) of word adjacency[a][b / 64] is the decision; the diagonal is
+ *   set; bits at positions >= n are zero.
+ *   The set: deg(v) = popcount(A[v]) - 1.  The seeds are the first min(n_seeds, n) closures by (deg descending, index ascending).
+ *   For seed s: K = {s}, C = A[s] \ {s}; while C is not empty, pick the v in C with the largest |A[v] & C|, the lowest v on a tie,
+ *   and set K <- K + {v}, C <- (C & A[v]) \ {v}.  The result is the largest K, on a tie the one of the seed that comes first in
+ *   seed order; keep[k] = 1 for its members and *n_keep their number.  If it has fewer than min_set members nothing is kept.
+ *   Every K is a clique by construction.  The search is a greedy heuristic: it is NOT guaranteed to find the maximum clique.
+ *   (A seed stops early when every vertex of C has |A[v] & C| = |C|: C is then a clique and the rule would take all of it.  This
+ *   does not change the result.)
+ *   No atomics, every maximum lexicographic with a fixed tie rule: two calls give the same bytes.  n = 0 gives *n_keep = 0.
+ *   Options: NULL takes the defaults, which are a judgement and not a measurement on real data.  adjacency, rot, trans may be
+ *   NULL; rot and trans are diagnostics of n * n doubles each.
+ *   LVBA_ERR_ARG: a null required pointer, n < 0 or n > 16384 (the adjacency is then 32 MB, a candidate set 2 KB of LDS),
+ *   n_frames < 1 with n > 0, an index outside the frames, ref == query, a non-finite pose or measurement, a measurement rotation
+ *   that is not orthonormal within 1e-6, an option outside its range.  A refused call writes nothing. */
+typedef struct lvba_closure_opts {
+    double rot_tol;     /* rad, finite and >= 0 (default 0.035) */
+    double rot_rate;    /* rad per frame, finite and >= 0 (default 0.001) */
+    double trans_tol;   /* metres, finite and >= 0 (default 0.2) */
+    double trans_rate;  /* metres per frame, finite and >= 0 (default 0.01) */
+    int32_t n_seeds;    /* >= 1 (default 32), clamped to n */
+    int32_t min_set;    /* >= 1 (default 2) */
+} lvba_closure_opts;
+void lvba_closure_default_opts(lvba_closure_opts *o);
+int32_t lvba_closure_consistency(int32_t device, int32_t n_frames, const double *poses, int32_t n, const int32_t *ref,
+                                 const int32_t *query, const double *meas, const lvba_closure_opts *o, uint64_t *adjacency,
+                                 double *rot, double *trans, uint8_t *keep, int32_t *n_keep);
+
 #ifdef __cplusplus
 }
 #endif
