@@ -34,6 +34,7 @@ SYMBOLS = [
     "lvba_register_scans_submaps", "lvba_loop_default_opts", "lvba_loop_candidates",
     "lvba_place_default_opts", "lvba_place_descriptors", "lvba_place_search", "lvba_place_candidates",
     "lvba_closure_default_opts", "lvba_closure_consistency",
+    "lvba_posegraph_default_opts", "lvba_posegraph_relax",
 ]
 
 OK, ERR_ARG, ERR_DEVICE, ERR_NOMEM, ERR_UNSUPPORTED, ERR_DIST, ERR_STATE = 0, -1, -2, -3, -4, -5, -6
@@ -111,6 +112,25 @@ LOSS_KINDS = {"trivial": 0, "huber": 1, "softlone": 2, "cauchy": 3, "arctan": 4,
 class Loss(C.Structure):
     """lvba_loss: kind (LVBA_LOSS_*), scale a (visual stage: whitened residual units; LiDAR stage: metres)."""
     _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("scale", C.c_double)]
+
+
+class PosegraphOpts(C.Structure):
+    """lvba_posegraph_opts (include/lvba_hip.h)"""
+    _fields_ = [("anchor", C.c_int32), ("max_iter", C.c_int32), ("odom_sigma_rot", C.c_double), ("odom_sigma_pos", C.c_double),
+                ("anchor_sigma_rot", C.c_double), ("anchor_sigma_pos", C.c_double), ("rel_tol", C.c_double), ("closure_loss", Loss)]
+
+
+class PosegraphReport(C.Structure):
+    """lvba_posegraph_report"""
+    _fields_ = [("iterations", C.c_int32), ("accepted", C.c_int32), ("status", C.c_int32), ("solver_kind", C.c_int32),
+                ("cost_first", C.c_double), ("cost_last", C.c_double), ("odom_cost_last", C.c_double),
+                ("closure_cost_last", C.c_double), ("max_step_last", C.c_double)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+PG_SOLVER_KINDS = {-1: "none", 0: "band", 1: "dissected", 2: "dense"}
 
 
 def loss_struct(loss):
@@ -398,6 +418,10 @@ def load():
     lib.lvba_closure_default_opts.restype = None
     lib.lvba_closure_consistency.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.POINTER(ClosureOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
+    lib.lvba_posegraph_default_opts.argtypes = [C.POINTER(PosegraphOpts)]
+    lib.lvba_posegraph_default_opts.restype = None
+    lib.lvba_posegraph_relax.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(PosegraphOpts), C.c_int32, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PosegraphReport)]
     lib.lvba_scans_info.argtypes = [H, C.POINTER(C.c_int32), C.c_void_p]
     lib.lvba_scans_download.argtypes = [H, C.c_int32, np.ctypeslib.ndpointer(np.float32, flags="C")]
     for name in SYMBOLS:

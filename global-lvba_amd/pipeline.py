@@ -503,6 +503,28 @@ def consistent_closures(poses, priors, device=0, **opts):
     return [p for p, k in zip(priors, got["keep"]) if k], got["keep"]
 
 
+def relax_trajectory(poses, priors, device=0, **opts):
+    """Pose-graph relaxation of the trajectory `poses` [n,12] over its own odometry and the loop closures `priors`
+    (posegraph.relax_pose_graph; opts: its options -- odom_sigma_rot / odom_sigma_pos per frame step, anchor,
+    closure_loss, max_iter, rel_tol, ...).  The closures go in as they are: nothing is re-oriented, and nothing is refused that
+    the library call accepts.  Returns relax_pose_graph's dict plus max_pose_change = (largest rotation [rad], largest position
+    change [m]) of a pose.  A closure whose query has drifted by more than the voxel size couples no planes in the bundle
+    adjustment; relaxed first, the two passes share voxels again and the same closures then serve as its priors."""
+    from .posegraph import relax_pose_graph
+    x = np.asarray(poses, np.float64).reshape(-1, 12)
+    got = relax_pose_graph(x, priors, device=device, **opts)
+    change = [pose_correction(a, b) for a, b in zip(x, got["poses"])]
+    got["max_pose_change"] = (max(c[0] for c in change), max(c[1] for c in change))
+    return got
+
+
+def _relax_over(poses, closures, relax, device=0):
+    """run_lidar_ba / run_full_pipeline: relax=True or a dict of relax_trajectory's options -> (poses, summary dict)"""
+    got = relax_trajectory(poses, closures, device=device, **(dict(relax) if isinstance(relax, dict) else {}))
+    return got["poses"], dict(report=got["report"], weights=[float(w) for w in got["weights"]],
+                              max_pose_change=[float(v) for v in got["max_pose_change"]])
+
+
 _map_quality = map_quality   # run_full_pipeline / run_dataset have a keyword of that name
 
 
@@ -512,15 +534,25 @@ def _lidar_cfg(cfg):
                 stage1_enable=c["stage1_enable"], stage_voxel_size=c["stage_voxel_size"], stage_eigen_ratio=c["stage_eigen_ratio"])
 
 
-def run_lidar_ba(scans, poses, priors=None, window_loss=None, stage_loss=None, host_driven=False, **cfg):
+def run_lidar_ba(scans, poses, priors=None, window_loss=None, stage_loss=None, host_driven=False, relax=None, **cfg):
     """LvbaSystem::runLidarBA (src/lvba_system.cpp:312-410) on resident scans: (poses [n,12], report dict).  cfg: the LiDAR keys of
     DEFAULTS.  window_loss / stage_loss: robust losses (BalmProblem.set_loss arguments) of every window problem / of both global
     stages; None: the plain sum of lambda_min.
     host_driven=False: the library's whole-stage entry (Scans.lidar_ba -> lvba_lidar_ba / _priors / _robust).
     host_driven=True: the same flow driven from here, stage by stage -- window BA, then per global stage a voxel map of the anchor
     clouds at the current anchor poses, its problem (tras_opt), set_loss, refine -- and the composition anchor o rel.  It takes a
-    stage loss only (the window stage is one library call) and no priors."""
+    stage loss only (the window stage is one library call) and no priors.
+    relax: None (default: nothing more is launched), True, or a dict of relax_trajectory's options: the trajectory is first relaxed
+    over the relative priors among `priors` (the loop closures), the stages start from the relaxed poses with the same priors, and
+    the report gains pose_graph.  Without a relative prior it does nothing."""
     k = _lidar_cfg(cfg)
+    closures = [p for p in (priors or []) if getattr(p, "kind", None) == 2] if relax else []
+    if closures:
+        poses, summary = _relax_over(poses, closures, relax, device=getattr(scans, "device", 0))
+        out, report = run_lidar_ba(scans, poses, priors=priors, window_loss=window_loss, stage_loss=stage_loss, host_driven=host_driven, **cfg)
+        report = dict(report)
+        report["pose_graph"] = summary
+        return out, report
     if not host_driven:
         return scans.lidar_ba(poses, priors=priors, window_loss=window_loss, stage_loss=stage_loss, **k)
     if priors or window_loss is not None or not k["window_enable"]:
@@ -556,7 +588,8 @@ def run_lidar_ba(scans, poses, priors=None, window_loss=None, stage_loss=None, h
 
 def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, tci, intr, width, height, keypoints, pairs,
                       matches, enable_lidar_ba=True, enable_visual_ba=True, device=0, images=None, lidar_priors=None,
-                      window_loss=None, stage_loss=None, camera_priors=None, map_quality=False, loop_closures=None, **cfg):
+                      window_loss=None, stage_loss=None, camera_priors=None, map_quality=False, loop_closures=None, relax=None,
+                      **cfg):
     """LvbaSystem::runFullPipeline (src/lvba_system.cpp:136-142) on in-memory data: clouds = body-frame [n_i, >=3] float32
     arrays, poses [n,12] = x_buf_ (T_world<-imu), image_poses [m,12] the image poses from the odometry.  cfg: DEFAULTS' keys
     (visual_loss, colorize_leaf among them).  images: None, or the images ([m,H,W,3] BGR uint8 or a callable k -> [H,W,3]):
@@ -570,7 +603,10 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
     loop_closures: None (off: nothing is launched), True, or a dict of find_loop_closures' keywords: loop closures are detected on
     the input poses before the LiDAR stage, the accepted priors are appended to lidar_priors and the output holds
     loop_closures = the report.  With consistency=True (or a dict of options) among the keywords the accepted closures are vetted
-    against one another first (consistent_closures) and only the mutually consistent ones become priors."""
+    against one another first (consistent_closures) and only the mutually consistent ones become priors.
+    relax: None (off), True, or a dict of relax_trajectory's options; honoured only together with loop_closures: after the closures
+    are found (and vetted), the trajectory is relaxed over them, the LiDAR stage starts from the relaxed poses with the same
+    closures as priors, and the output holds pose_graph = dict(report, weights, max_pose_change).  poses_before stays the input."""
     if images is not None and not enable_visual_ba:
         raise ValueError("colouring the map needs the cameras of the visual stage (enable_visual_ba=True)")
     c = dict(DEFAULTS); c.update(cfg)
@@ -581,8 +617,10 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
         if loop_closures:
             found, out["loop_closures"] = find_loop_closures(scans, x_orig, **(dict(loop_closures) if isinstance(loop_closures, dict) else {}))
             lidar_priors = list(lidar_priors or []) + found if found or lidar_priors is not None else None
+            if relax and found:
+                x_opt, out["pose_graph"] = _relax_over(x_orig, found, relax, device=device)
         if enable_lidar_ba:
-            x_opt, report = run_lidar_ba(scans, x_orig, priors=lidar_priors, window_loss=window_loss, stage_loss=stage_loss, **c)
+            x_opt, report = run_lidar_ba(scans, x_opt, priors=lidar_priors, window_loss=window_loss, stage_loss=stage_loss, **c)
             out["lidar_report"] = report
         out["poses"] = np.asarray(x_opt).reshape(-1, 12)
         if enable_visual_ba:
@@ -632,7 +670,7 @@ def extrinsics_from_config(Rcl, Pcl, extrinsic_R, extrinsic_T):
 
 
 def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrinsic_R=np.eye(3), extrinsic_T=np.zeros(3),
-                image_sample_step=1, out_dir=None, device=0, colorize=False, map_quality=False, loop_closures=None, **cfg):
+                image_sample_step=1, out_dir=None, device=0, colorize=False, map_quality=False, loop_closures=None, relax=None, **cfg):
     """initFromDatasetIO + runFullPipeline on a dataset directory; with out_dir, the refined LiDAR poses (TUM) and the COLMAP
     text files images.txt / points3D.txt the reference writes (src/lvba_system.cpp:2018-2137) are saved there.  images.txt is
     the reference's, character for character (tests/test_ref_system.py).
@@ -646,6 +684,8 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
     map_quality.json, the two summaries.
     loop_closures (True or a dict of keywords, as for run_full_pipeline): the output gains loop_closures and out_dir gets
     loop_closures.json, the report without its arrays; dict(consistency=True, ...) vets the closures against one another.
+    relax (True or a dict, as for run_full_pipeline; only with loop_closures): the output gains pose_graph and out_dir gets
+    pose_graph.json (the report, the closures' weights, the largest pose change).
     cfg as for run_full_pipeline, e.g. visual_loss=REFERENCE_HUBER, window_loss=("cauchy", 0.1), stage_loss=("huber", 0.05),
     camera_priors=lambda cams: lidar_camera_priors(cams, Rci, tci, 1e-3, 0.02)."""
     import os
@@ -666,7 +706,8 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
                             width, height, [k[:, :2] for k in kps], [pairs[k] for k in keep], [matches[k] for k in keep],
                             device=device, images=(lambda k: D.read_image_bgr(os.path.join(img_dir, names[k]), width, height))
                             if colorize else None, **({"map_quality": map_quality} if map_quality else {}),
-                            **({"loop_closures": loop_closures} if loop_closures else {}), **cfg)
+                            **({"loop_closures": loop_closures} if loop_closures else {}),
+                            **({"relax": relax} if relax and loop_closures else {}), **cfg)
     out.update(image_ids=image_ids, scan_times=ds["timestamps"])
     if out_dir is not None:
         os.makedirs(out_dir, exist_ok=True)
@@ -690,4 +731,8 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
             import json
             with open(os.path.join(out_dir, "loop_closures.json"), "w") as f:
                 json.dump([{a: b for a, b in r.items() if not isinstance(b, np.ndarray)} for r in out["loop_closures"]], f, indent=1)
+        if "pose_graph" in out:
+            import json
+            with open(os.path.join(out_dir, "pose_graph.json"), "w") as f:
+                json.dump(out["pose_graph"], f, indent=1)
     return out

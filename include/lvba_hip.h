@@ -980,6 +980,58 @@ int32_t lvba_closure_consistency(int32_t device, int32_t n_frames, const double 
                                  const int32_t *query, const double *meas, const lvba_closure_opts *o, uint64_t *adjacency,
                                  double *rot, double *trans, uint8_t *keep, int32_t *n_keep);
 
+/* Pose-graph relaxation over odometry and loop closures (opt-in).  One call, no handle.
+ *   Poses X [n_poses][12] (R row-major | p) move under BALM's retraction R <- R Exp(dphi), p <- p + dp, d = [phi; p].  Minimised:
+ *     C(x) = sum_{i=0..N-2} 1/2 |L_o r(X_i, X_{i+1}; Z0_i)|^2 + sum_k 1/2 rho(|L_k r_k(x)|^2) + 1/2 |L_a r_pose(X_a; X0_a)|^2
+ *   r       the LVBA_PRIOR_RELATIVE residual above (rotation first, offsets honoured), r_pose the LVBA_PRIOR_POSE residual.
+ *   odometry  edge i keeps the relative motion of the INPUT poses, Z0_i = X0_i^-1 X0_{i+1}, with L_o = diag(1/odom_sigma_rot x 3,
+ *           1/odom_sigma_pos x 3).  The sigmas are per frame step and a judgement (a trajectory file has no covariances); only their
+ *           ratio to the closures' information moves the result.
+ *   closures  the `edges` array: LVBA_PRIOR_RELATIVE only, as find_loop_closures builds them.
+ *   anchor  pose `anchor` is held at its input value by L_a = diag(1/anchor_sigma_rot x 3, 1/anchor_sigma_pos x 3).  The rest of C is
+ *           gauge-invariant, so at the minimum this residual is zero and the solution does not depend on L_a (finite, > 0).  The
+ *           default, 1e-4 rad / 1e-4 m, is stiff: the covariance call's convention is an anchor that does not move, and a stiff
+ *           prior keeps the anchor in place during the damped steps too, not only at the minimum.
+ *   rho     closure_loss, one of LVBA_LOSS_* with s = |L_k r_k|^2 dimensionless, on the closure edges only; gradient and
+ *           Gauss-Newton block are scaled by rho'(s), the rho'' term is left out (as lvba_balm_set_loss).  Default TRIVIAL.
+ *   The LM rule (the numpy oracle of the tests and the device driver follow this text):
+ *     u = 0.01, v = 2.  H, g, C1 <- the Gauss-Newton system and cost at x ("evaluated").  If the first C1 == 0: stop, no iteration.
+ *     Iteration it = 0 .. max_iter - 1:
+ *       dx = -(H + u diag(H))^-1 g;  x' = x [+] dx;  q1 = 1/2 dx^T (u diag(H) dx - g);  C2 = C(x');  q = C1 - C2.
+ *       A flagged pivot makes q NaN (status LVBA_NUM_FACTORIZATION), a non-finite C2 gives status LVBA_NUM_NONFINITE.
+ *       q > 0 (accepted):  x <- x';  t = 1 - (2 q / q1 - 1)^3;  u <- u * max(1/3, t);  v <- 2;  H, g, C1 are evaluated again at
+ *                          the new x;  if q / C1(old) < rel_tol: stop after this iteration.
+ *       else (rejected):   u <- u v;  v <- 2 v;  H, g, C1 are kept.
+ *     The trace row of an iteration holds residual1 = C1, residual2 = C2 (sums, not averages), u, v as used, q, q1.
+ *   poses_out [n_poses][12] receives the result; edge_weight [n_edges] (may be NULL) rho'(s_k) at the result; trace (may be NULL)
+ *   needs room for max_iter rows, *n_trace (may be NULL) their number; report is required.  report.solver_kind: LVBA_PG_SOLVER_*,
+ *   which form of the damped solve the graph was given (-1: nothing was solved); cost_last = C at the result, odom_cost_last and
+ *   closure_cost_last its first two sums; max_step_last = max |dx| of the last accepted step (0 if none).
+ *   n_edges = 0 is legal: the cost is 0, nothing is launched, poses_out equals poses byte for byte.
+ *   LVBA_ERR_ARG (every output untouched): a null required pointer, n_poses < 2, n_edges < 0, an edge that is not RELATIVE, an index
+ *   out of range, i == j, a non-finite value or a rotation (pose, measurement, offset) that is not orthonormal within 1e-6, a sigma
+ *   or rel_tol that is not finite and > 0, max_iter < 0, a bad loss, an anchor outside the poses.
+ *   LVBA_NUM_FACTORIZATION / LVBA_NUM_NONFINITE: as lvba_balm_refine -- the iteration is a rejected step, the loop goes on, the
+ *   worst status is returned at the end and the outputs are written.  lvba_version() is unchanged; look the symbols up. */
+#define LVBA_PG_SOLVER_BAND 0
+#define LVBA_PG_SOLVER_DISSECTED 1
+#define LVBA_PG_SOLVER_DENSE 2
+typedef struct lvba_posegraph_opts {
+    int32_t anchor, max_iter;           /* 0, 50 */
+    double odom_sigma_rot, odom_sigma_pos, anchor_sigma_rot, anchor_sigma_pos, rel_tol; /* 0.01 rad, 0.05 m, 1e-4, 1e-4, 1e-6 */
+    lvba_loss closure_loss;             /* TRIVIAL */
+} lvba_posegraph_opts;
+typedef struct lvba_posegraph_report {
+    int32_t iterations, accepted, status, solver_kind /* band / dissected / dense, as lvba_balm_info names them */;
+    double cost_first, cost_last, odom_cost_last, closure_cost_last, max_step_last;
+} lvba_posegraph_report;
+void    lvba_posegraph_default_opts(lvba_posegraph_opts *);
+int32_t lvba_posegraph_relax(int32_t n_poses, const double *poses, int32_t n_edges, const lvba_prior *edges,
+                             const lvba_posegraph_opts *opts, int32_t device, double *poses_out,
+                             double *edge_weight /* [n_edges] rho'(s) at the result, may be NULL */,
+                             lvba_lm_trace *trace, int32_t *n_trace /* may be NULL */,
+                             lvba_posegraph_report *report);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,176 @@
+"""CPU tests of the pose-graph relaxation: the numpy oracle against finite differences and its own properties
+(gauge, a closed ring, a false closure under CAUCHY), the decision margins of the shared cases, the solver-rounding bound behind
+the GPU tolerance, csrc/posegraph_device.h compiled for the host against the oracle, and the struct sizes."""
+import ctypes
+import importlib
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import closure_oracle as co
+import posegraph_cases as pgc
+import posegraph_oracle as pg
+import prior_oracle as po
+from robust_visual_oracle import KINDS
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FAST = [n for n in pgc.names() if not n.startswith("lot320")]
+
+
+@pytest.fixture(scope="module")
+def emul(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("emul_posegraph") / "libposegraph_check.so")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Werror", "-Wno-unknown-pragmas",
+                           os.path.join(ROOT, "tests", "posegraph_check.cpp"), "-o", so])
+    lib = ctypes.CDLL(so)
+    f64 = np.ctypeslib.ndpointer(np.float64, flags="C")
+    lib.pgc_odometry.argtypes = [f64, f64, ctypes.c_double, ctypes.c_double, f64]
+    lib.pgc_lin.argtypes = [ctypes.c_int, f64, f64, f64, ctypes.c_int, ctypes.c_int, ctypes.c_double, f64, f64]
+    lib.pgc_cost.argtypes = [ctypes.c_int, f64, f64, f64, ctypes.c_int, ctypes.c_double, f64]
+    lib.pgc_retract.argtypes = [f64, f64, f64]
+    for f in (lib.pgc_odometry, lib.pgc_lin, lib.pgc_cost, lib.pgc_retract):
+        f.restype = None
+    return lib
+
+
+def test_gradient_matches_central_differences():
+    """g of assemble() against central differences of cost() along every tangent direction, with a loss on the closures."""
+    c = pgc.named("cauchy")
+    G = pg.Graph(c["X"][:16], [p for p in c["closures"] if p["i"] < 16 and p["j"] < 16] +
+                 [pg.closure(2, 13, co.rigid((0.01, 0.02, -0.03), (0.3, -0.2, 0.1)), pgc.WEAK)], closure_loss=("cauchy", 3.0), anchor=3)
+    rng = np.random.default_rng(1)
+    x = po.retract(G.X0, 0.02 * rng.standard_normal(6 * G.N))
+    _, g, C = G.assemble(x)
+    # central differences at h: rounding of the two costs, ~eps C / h each (taken 10 times), and truncation, ~h^2 relative to g
+    h = 1e-6
+    noise = 10.0 * np.finfo(np.float64).eps * C / h
+    worst = 0.0
+    for a in range(6 * G.N):
+        d = np.zeros(6 * G.N); d[a] = h
+        fd = (G.cost(po.retract(x, d)) - G.cost(po.retract(x, -d))) / (2 * h)
+        worst = max(worst, abs(fd - g[a]) / (noise + 1e-9 * abs(g[a])))
+    print(f"C = {C:.4g}, rounding floor {noise:.2e}; largest |fd - g| / (floor + 1e-9 |g|): {worst:.2f}")
+    assert worst < 1.0
+
+
+def test_gauge_anchor_residual_and_anchor_information():
+    """At convergence the anchor residual is below 1e-12 and the poses do not depend on L_a."""
+    c = pgc.named("ring64")
+    a = pgc.graph(c, rel_tol=1e-14, max_iter=60).relax()
+    b = pgc.graph(c, rel_tol=1e-14, max_iter=60, anchor_sigma_rot=1e-6, anchor_sigma_pos=1e-6).relax()     # L_a x 100
+    r = a["report"]
+    anchor_cost = r["cost_last"] - r["odom_cost_last"] - r["closure_cost_last"]
+    rot, pos = pg.pose_errors(a["poses"][:1], c["X"][:1])
+    d = pg.pose_errors(a["poses"], b["poses"])
+    print(f"anchor pose moved {rot:.2e} rad {pos:.2e} m, anchor cost {anchor_cost:.2e}; L_a x 100 moves the poses by {d[0]:.2e} rad {d[1]:.2e} m")
+    assert rot < 1e-12 and pos < 1e-12
+    assert d[0] < 1e-9 and d[1] < 1e-8      # both runs stop within rel_tol of the same minimum, not at it
+
+
+def test_ring_closure_removes_the_accumulated_bias():
+    c = pgc.named("ring64")
+    P = pgc.ring(64)
+    z = c["closures"][0]["meas"]
+    gap = lambda X: pg.pose_errors([pg.relative(X[63], X[0])], [z])
+    before, after = gap(c["X"]), gap(pgc.oracle("ring64")["poses"])
+    print(f"closing error {before[0]:.4f} rad {before[1]:.4f} m -> {after[0]:.5f} rad {after[1]:.5f} m")
+    assert after[0] < 0.05 * before[0] and after[1] < 0.05 * before[1]
+    assert np.allclose(pg.relative(P[63], P[0]), z)
+
+
+def test_cauchy_separates_the_false_closure():
+    """Recorded margin: the false closure ends at weight 0.023, the true ones at >= 0.992."""
+    w = pgc.oracle("cauchy")["weights"]
+    print("weights:", np.round(w, 4))
+    assert w[-1] < 0.05 and w[:-1].min() > 0.95
+
+
+@pytest.mark.parametrize("name", [n for n in pgc.names() if n != "lot320 nd"])
+def test_cases_keep_their_decision_margins(name):
+    """No accept decision (q > 0) and no stop decision (q / C1 < rel_tol) of the oracle lies within 1e-6 of its threshold."""
+    acc, stop = pgc.decision_margins(name)
+    t = pgc.oracle(name)["trace"]
+    print(f"{name}: {len(t)} iterations, {''.join('A' if r['accepted'] else 'r' for r in t)}, margins {acc:.2e} / {stop:.2e}")
+    assert acc >= pgc.MARGIN and stop >= pgc.MARGIN and len(t) >= 1
+
+
+def test_solver_rounding_bound():
+    """How far the oracle moves when numpy's solve is replaced by a band LDL^T: the figure behind posegraph_cases.POSE_TOL."""
+    worst = [0.0, 0.0]
+    for name in FAST + ["lot320"]:
+        a, b = pgc.oracle(name), pgc.oracle_band(name)
+        d = pg.pose_errors(a["poses"], b["poses"])
+        print(f"{name}: {d[0]:.2e} rad {d[1]:.2e} m")
+        assert [r["accepted"] for r in a["trace"]] == [r["accepted"] for r in b["trace"]]
+        worst = [max(worst[0], d[0]), max(worst[1], d[1])]
+    assert worst[0] <= pgc.SOLVER_SPREAD["rot"] * 1.05 and worst[1] <= pgc.SOLVER_SPREAD["pos"] * 1.05
+    assert pgc.POSE_TOL == dict(rot=10 * pgc.SOLVER_SPREAD["rot"], pos=10 * pgc.SOLVER_SPREAD["pos"])
+
+
+def _rec(pr):
+    return np.ascontiguousarray(np.r_[pr["meas"], pr["oi"], pr["oj"], np.asarray(pr["L"]).reshape(36)])
+
+
+def _close(a, b, what):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    scale = max(1.0, float(np.abs(b).max(initial=0.0)))
+    assert np.abs(a - b).max(initial=0.0) <= 1e-12 * scale, what
+
+
+@pytest.mark.parametrize("name", ["lever", "cauchy", "anchor 40"])
+def test_device_header_equals_the_oracle(emul, name):
+    """Odometry records, weighted lin records, costs and the retraction of posegraph_device.h, to 1e-12 relative to each block's
+    largest entry."""
+    c = pgc.named(name)
+    G = pgc.graph(c)
+    rng = np.random.default_rng(3)
+    x = po.retract(G.X0, 0.01 * rng.standard_normal(6 * G.N))
+    o = G.o
+    for i in (0, 7, G.N - 2):
+        rec = np.zeros(72)
+        emul.pgc_odometry(G.X0[i], G.X0[i + 1], o["odom_sigma_rot"], o["odom_sigma_pos"], rec)
+        _close(rec, _rec(G.odo[i]), "odometry record")
+    loss = o["closure_loss"]
+    for pr, cls in G.edges()[::7] + G.edges()[-3:]:
+        lk, ls = (KINDS[loss[0]], loss[1]) if cls == 1 and loss else (0, 1.0)
+        cost, w, e, Wi, Wj = G.edge(pr, cls, x)
+        Ti, Tj = np.ascontiguousarray(x[pr["i"]]), np.ascontiguousarray(x[pr["j"]])
+        for flip in (0, 1):
+            lin, out = np.zeros(128), np.zeros(2)
+            emul.pgc_lin(pr["kind"], _rec(pr), Ti, Tj, flip, lk, ls, lin, out)
+            _close(out, [cost, w], "cost, weight")
+            _close(lin[1:7], w * (Wi.T @ e), "J_i^T e")
+            _close(lin[13:49].reshape(6, 6).T, w * (Wi.T @ Wi), "J_i^T J_i")
+            if pr["kind"] == 2:
+                _close(lin[7:13], w * (Wj.T @ e), "J_j^T e")
+                _close(lin[49:85].reshape(6, 6).T, w * (Wj.T @ Wj), "J_j^T J_j")
+                X = w * (Wi.T @ Wj)
+                _close(lin[85:121].reshape(6, 6).T, X.T if flip else X, "cross block")
+        out = np.zeros(2)
+        emul.pgc_cost(pr["kind"], _rec(pr), Ti, Tj, lk, ls, out)
+        _close(out, [cost, w], "cost kernel")
+    d = 0.1 * rng.standard_normal(6)
+    got = np.zeros(12)
+    emul.pgc_retract(np.ascontiguousarray(x[5]), d, got)
+    _close(got, po.retract(x[5:6], d)[0], "retraction")
+
+
+def test_struct_sizes_match_the_header(tmp_path):
+    L = importlib.import_module("global-lvba_amd._lib")
+    src = tmp_path / "sz.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "lvba_hip.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu\\n",'
+                   'sizeof(lvba_posegraph_opts),offsetof(lvba_posegraph_opts,rel_tol),offsetof(lvba_posegraph_opts,closure_loss),'
+                   'sizeof(lvba_posegraph_report),offsetof(lvba_posegraph_report,solver_kind),offsetof(lvba_posegraph_report,max_step_last));return 0;}\n')
+    exe = str(tmp_path / "sz")
+    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe])
+    got = [int(t) for t in subprocess.check_output([exe]).split()]
+    O, R = L.PosegraphOpts, L.PosegraphReport
+    assert got == [ctypes.sizeof(O), O.rel_tol.offset, O.closure_loss.offset, ctypes.sizeof(R), R.solver_kind.offset, R.max_step_last.offset]
+    assert got == [64, 40, 48, 56, 12, 48]
+
+
+def test_relax_trajectory_rejects_unknown_options():
+    pgm = importlib.import_module("global-lvba_amd.posegraph")
+    assert set(pgm.POSEGRAPH_OPTS) == set(pg.DEFAULTS)
