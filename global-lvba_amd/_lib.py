@@ -35,6 +35,8 @@ SYMBOLS = [
     "lvba_place_default_opts", "lvba_place_descriptors", "lvba_place_search", "lvba_place_candidates",
     "lvba_closure_default_opts", "lvba_closure_consistency",
     "lvba_posegraph_default_opts", "lvba_posegraph_relax",
+    "lvba_match_default_opts", "lvba_match_create", "lvba_match_destroy", "lvba_match_set_geometry", "lvba_match_pairs",
+    "lvba_match_scan",
 ]
 
 OK, ERR_ARG, ERR_DEVICE, ERR_NOMEM, ERR_UNSUPPORTED, ERR_DIST, ERR_STATE = 0, -1, -2, -3, -4, -5, -6
@@ -203,6 +205,12 @@ class PlaceCandidate(C.Structure):
 class ClosureOpts(C.Structure):
     _fields_ = [("rot_tol", C.c_double), ("rot_rate", C.c_double), ("trans_tol", C.c_double), ("trans_rate", C.c_double),
                 ("n_seeds", C.c_int32), ("min_set", C.c_int32)]
+
+
+class MatchOpts(C.Structure):
+    """lvba_match_opts"""
+    _fields_ = [("max_distance", C.c_double), ("max_ratio", C.c_double), ("mutual", C.c_int32), ("guided", C.c_int32),
+                ("max_epipolar_px", C.c_double)]
 
 
 class VoxelOpts(C.Structure):
@@ -422,6 +430,14 @@ def load():
     lib.lvba_posegraph_default_opts.restype = None
     lib.lvba_posegraph_relax.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(PosegraphOpts), C.c_int32, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PosegraphReport)]
+    lib.lvba_match_default_opts.argtypes = [C.POINTER(MatchOpts)]
+    lib.lvba_match_default_opts.restype = None
+    lib.lvba_match_create.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(H)]
+    lib.lvba_match_destroy.argtypes = [H]
+    lib.lvba_match_set_geometry.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.lvba_match_pairs.argtypes = [H, C.c_int64, C.c_void_p, C.POINTER(MatchOpts), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]
+    lib.lvba_match_scan.argtypes = [H, C.c_int32, C.c_int32, C.POINTER(MatchOpts), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.lvba_scans_info.argtypes = [H, C.POINTER(C.c_int32), C.c_void_p]
     lib.lvba_scans_download.argtypes = [H, C.c_int32, np.ctypeslib.ndpointer(np.float32, flags="C")]
     for name in SYMBOLS:

@@ -1,0 +1,504 @@
+// match.hip -- descriptor matching of image pairs with an optional pose-guided epipolar gate (lvba_match_*; the rule is in
+// include/lvba_hip.h, its scalar pieces in match_device.h).
+//
+// Device design:
+//   match_undistort_kernel  a thread per keypoint: trk_undistort once per lvba_match_set_geometry, NaN where it fails.
+//   match_scan_kernel       the top two of every row of an ordered pair (a, b), for a whole list of ordered pairs in one grid.  A
+//                           workgroup is four wavefronts, each with 32 rows of image a; its A fragments of all four k-steps stay in
+//                           registers.  Column tiles of 32 descriptors of b stream through v_mfma_i32_32x32x32_i8; the accumulator
+//                           starts at the column's bias 128 sum b', so that the biased score sum a'b' + 128 sum b' orders the columns
+//                           of a row as the true score does (the rest of the identity is a per-row constant, added once at the end).
+//                           Each lane keeps (s1, best, s2) for its 16 rows over the columns it sees -- a lane sees ascending columns,
+//                           so a strict > keeps the lowest column of a tie -- and the 32 lanes of a row merge once at the end.  The
+//                           n_a x n_b scores never leave the registers.  Under the gate a lane holds the epipolar line (or the
+//                           point) of its 16 rows from the prologue on, computes its column's once per tile, and a candidate that
+//                           fails is replaced by "none" before the update.
+//   match_decide_kernel     a thread per forward row: the fp64 acos clauses and the mutual clause -> a flag.
+//   match_write_kernel      after an exclusive prefix sum of the flags: the matches in (pair, row) order, and match_off.
+// The byte k of a descriptor that a lane feeds into a k-step is the same for the A and the B operand (bytes 64 h + 16 ks .. + 15 of
+// lane half h), so the sum over k is complete whatever order the instruction takes them in.
+// No atomics of any kind: two calls give the same bytes.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <algorithm>
+#include <cmath>
+#include <vector>
+#include "lvba_common.h"
+#include "mempool.h"
+#include "voxel_internal.h"
+#include "match_device.h"
+#include "../../include/lvba_hip.h"
+
+using namespace lvba;
+
+struct lvba_match_s {
+    int device = 0;
+    int32_t n_images = 0;
+    std::vector<int64_t> off;      // [n_images + 1]
+    uint8_t *d_desc = nullptr;     // [total][128], top bit flipped: a' = a - 128 as a signed byte
+    int32_t *d_bias = nullptr;     // [total] 128 sum a'
+    double *d_xy = nullptr;        // [total][2] undistorted normalised keypoints, NaN where the undistortion fails
+    bool has_geometry = false;
+    std::vector<double> R, t;      // [n_images][9], [n_images][3]
+    double focal_sum = 0.0;        // fx + fy
+};
+
+namespace {
+
+constexpr int SCAN_BLOCK = 256;             // four wavefronts, 32 rows each
+constexpr int SCAN_ROWS = 32 * (SCAN_BLOCK / 64);
+constexpr int64_t MATCH_MAX_PER_IMAGE = 1 << 20;
+constexpr int64_t CHUNK_ROWS = (int64_t)1 << 23; // scanned rows per grid: 96 MB of top-two results
+
+typedef int v4i __attribute__((ext_vector_type(4)));
+typedef int v16i __attribute__((ext_vector_type(16)));
+
+struct MatchTask {
+    int64_t a_off, b_off, out_off;  // first descriptor of a and of b, first result row
+    int32_t n_a, n_b;
+    int32_t rows_lo, pad;           // 1: image a is the "lo" image of the gate
+    double E[9];                    // lo -> hi
+};
+
+__global__ __launch_bounds__(256) void match_undistort_kernel(int64_t n, const float *__restrict__ uv, const TrkIntr cam, double *__restrict__ xy)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double x, y;
+    if (!trk_undistort(cam, (double)uv[2 * i], (double)uv[2 * i + 1], x, y)) x = y = NAN;
+    xy[2 * i] = x; xy[2 * i + 1] = y;
+}
+
+// row of accumulator register i in lane half h (the C/D map of the 32x32 shapes)
+__device__ __forceinline__ int acc_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
+
+template <bool ROWS_LO>
+__device__ __forceinline__ void gate_tile(v16i &acc, const MatchLine (&P)[16], const double *E, double cx, double cy, double tau2)
+{
+    if (ROWS_LO) {
+        const double n_hi = match_norm_hi(E, cx, cy);
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+            if (!match_gate(P[i], cx, cy, n_hi, tau2)) acc[i] = MATCH_NONE;
+    } else {
+        const MatchLine lo = match_line_lo(E, cx, cy);
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+            if (!match_gate(lo, P[i].l0, P[i].l1, P[i].n, tau2)) acc[i] = MATCH_NONE;
+    }
+}
+
+// tiles [n_tiles] = (task, first row); best, s1, s2 [rows of all tasks]
+template <bool GUIDED>
+__global__ __launch_bounds__(SCAN_BLOCK) void match_scan_kernel(const MatchTask *__restrict__ tasks, const int2 *__restrict__ tiles,
+                                                                const uint8_t *__restrict__ desc, const int32_t *__restrict__ bias,
+                                                                const double *__restrict__ xy, double tau2, int32_t *__restrict__ best,
+                                                                int32_t *__restrict__ s1, int32_t *__restrict__ s2)
+{
+    const int2 tl = tiles[blockIdx.x];
+    const MatchTask &t = tasks[tl.x];
+    const int lane = threadIdx.x & 63, cl = lane & 31, h = lane >> 5;
+    const int n_a = t.n_a, n_b = t.n_b;
+    const int row0 = tl.y + 32 * (threadIdx.x >> 6);
+    if (row0 >= n_a) return; // the whole wavefront; nothing below synchronises the workgroup
+    v4i A[4];
+    {
+        const int r = min(row0 + cl, n_a - 1);
+        const v4i *p = reinterpret_cast<const v4i *>(desc + (t.a_off + r) * MATCH_DIM + 64 * h);
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) A[ks] = p[ks];
+    }
+    MatchLine P[GUIDED ? 16 : 1];
+    double E[9];
+    const bool rows_lo = t.rows_lo != 0;
+    if constexpr (GUIDED) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) E[k] = t.E[k];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int r = min(row0 + acc_row(i, h), n_a - 1);
+            const double x = xy[2 * (t.a_off + r)], y = xy[2 * (t.a_off + r) + 1];
+            if (rows_lo) P[i] = match_line_lo(E, x, y);
+            else { MatchLine m; m.l0 = x; m.l1 = y; m.l2 = 0.0; m.n = match_norm_hi(E, x, y); P[i] = m; }
+        }
+    }
+    MatchTop top[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) top[i] = match_top_none();
+
+    // the next tile's fragments are asked for before the current tile's products and epilogue, which hide the load
+    v4i Bn[4] = {};
+    int32_t bn = 0;
+    if (n_b > 0) {
+        const int64_t cb = t.b_off + min(cl, n_b - 1);
+        const v4i *p = reinterpret_cast<const v4i *>(desc + cb * MATCH_DIM + 64 * h);
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) Bn[ks] = p[ks];
+        bn = bias[cb];
+    }
+    for (int c0 = 0; c0 < n_b; c0 += 32) {
+        const int col = c0 + cl;
+        const int64_t cb = t.b_off + min(col, n_b - 1);
+        v4i B[4];
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) B[ks] = Bn[ks];
+        const int32_t bc = bn;
+        if (c0 + 32 < n_b) {
+            const int64_t cn = t.b_off + min(col + 32, n_b - 1);
+            const v4i *p = reinterpret_cast<const v4i *>(desc + cn * MATCH_DIM + 64 * h);
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) Bn[ks] = p[ks];
+            bn = bias[cn];
+        }
+        v16i acc;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[i] = bc;
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(A[ks], B[ks], acc, 0, 0, 0);
+        if constexpr (GUIDED) {
+            const double cx = xy[2 * cb], cy = xy[2 * cb + 1];
+            if (rows_lo) gate_tile<true>(acc, P, E, cx, cy, tau2);
+            else gate_tile<false>(acc, P, E, cx, cy, tau2);
+        }
+        if (c0 + 32 > n_b) { // the last, partial tile: the clamped columns are nobody's
+            const bool live = col < n_b;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[i] = live ? acc[i] : MATCH_NONE;
+        }
+#pragma unroll
+        for (int i = 0; i < 16; ++i) match_top_update(top[i], acc[i], col);
+    }
+    // once: the 32 lanes of a half hold the same 16 rows (xor butterflies stay inside the half, which wave_ops.h' whole-wave folds
+    // do not)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+#pragma unroll
+        for (int m = 1; m < 32; m <<= 1) {
+            MatchTop o;
+            o.s1 = __shfl_xor(top[i].s1, m, 64); o.best = __shfl_xor(top[i].best, m, 64); o.s2 = __shfl_xor(top[i].s2, m, 64);
+            top[i] = match_top_merge(top[i], o);
+        }
+    }
+    if (cl != 0) return;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int r = row0 + acc_row(i, h);
+        if (r >= n_a) continue;
+        const int32_t rc = bias[t.a_off + r] + MATCH_BIAS_CONST;
+        const int64_t o = t.out_off + r;
+        best[o] = top[i].best;
+        s1[o] = top[i].best >= 0 ? top[i].s1 + rc : 0;
+        s2[o] = top[i].s2 != MATCH_NONE ? top[i].s2 + rc : 0;
+    }
+}
+
+struct MatchPairOut { int64_t fwd, rev; }; // first result row of (a, b) and of (b, a)
+
+// flag [n_rows + 1] (the last is 0): forward row i of the chunk is a match
+__global__ __launch_bounds__(256) void match_decide_kernel(int64_t n_rows, int n_pairs, const int64_t *__restrict__ row_off,
+                                                           const MatchPairOut *__restrict__ po, const int32_t *__restrict__ best,
+                                                           const int32_t *__restrict__ s1, const int32_t *__restrict__ s2,
+                                                           double max_distance, double max_ratio, int mutual, uint32_t *__restrict__ flag)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i > n_rows) return;
+    if (i == n_rows) { flag[i] = 0; return; }
+    int lo = 0, hi = n_pairs; // the last pair with row_off <= i
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (row_off[mid] <= i) lo = mid; else hi = mid;
+    }
+    const int64_t r = i - row_off[lo], f = po[lo].fwd + r;
+    const int32_t c = best[f];
+    bool ok = match_accept(c, s1[f], s2[f], max_distance, max_ratio);
+    if (ok && mutual) ok = best[po[lo].rev + c] == (int32_t)r;
+    flag[i] = ok ? 1u : 0u;
+}
+
+// matches / scores [n_out] from position `base` of the whole list on; off [n_pairs] the chunk's part of match_off
+__global__ __launch_bounds__(256) void match_write_kernel(int64_t n_rows, int n_pairs, const int64_t *__restrict__ row_off,
+                                                          const MatchPairOut *__restrict__ po, const int32_t *__restrict__ best,
+                                                          const int32_t *__restrict__ s1, const uint32_t *__restrict__ flag,
+                                                          const uint32_t *__restrict__ excl, int64_t base, int64_t n_out,
+                                                          int32_t *__restrict__ matches, int32_t *__restrict__ scores, int64_t *__restrict__ off)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n_pairs) off[i] = base + excl[row_off[i]];
+    if (i >= n_rows || !flag[i]) return;
+    const int64_t pos = excl[i];
+    if (pos >= n_out) return;
+    int lo = 0, hi = n_pairs;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (row_off[mid] <= i) lo = mid; else hi = mid;
+    }
+    const int64_t r = i - row_off[lo], f = po[lo].fwd + r;
+    matches[2 * pos] = (int32_t)r; matches[2 * pos + 1] = best[f];
+    scores[pos] = s1[f];
+}
+
+int32_t check_opts(const lvba_match_opts *opts, lvba_match_opts &o)
+{
+    lvba_match_default_opts(&o);
+    if (opts) o = *opts;
+    const bool ok = std::isfinite(o.max_distance) && o.max_distance > 0.0 && std::isfinite(o.max_ratio) && o.max_ratio > 0.0 &&
+                    o.max_ratio <= 1.0 && (o.mutual == 0 || o.mutual == 1) && (o.guided == 0 || o.guided == 1) &&
+                    std::isfinite(o.max_epipolar_px) && o.max_epipolar_px > 0.0;
+    if (!ok)
+        return lvba_fail(LVBA_ERR_ARG, "options: max_distance %g (finite, > 0), max_ratio %g (in (0, 1]), mutual %d (0 or 1), guided %d (0 or "
+                         "1), max_epipolar_px %g (finite, > 0)", o.max_distance, o.max_ratio, o.mutual, o.guided, o.max_epipolar_px);
+    return LVBA_OK;
+}
+
+int32_t check_pair(const lvba_match_s *m, int64_t a, int64_t b, const lvba_match_opts &o)
+{
+    if (a < 0 || a >= m->n_images || b < 0 || b >= m->n_images || a == b)
+        return lvba_fail(LVBA_ERR_ARG, "pair (%lld, %lld) of %d images (two different images)", (long long)a, (long long)b, m->n_images);
+    if (o.guided && !m->has_geometry) return lvba_fail(LVBA_ERR_ARG, "guided matching needs lvba_match_set_geometry first");
+    return LVBA_OK;
+}
+
+MatchTask make_task(const lvba_match_s *m, int a, int b, int64_t out_off, bool guided)
+{
+    MatchTask t{};
+    t.a_off = m->off[a]; t.b_off = m->off[b]; t.out_off = out_off;
+    t.n_a = (int32_t)(m->off[a + 1] - m->off[a]); t.n_b = (int32_t)(m->off[b + 1] - m->off[b]);
+    t.rows_lo = a < b ? 1 : 0;
+    if (guided) {
+        const int lo = std::min(a, b), hi = std::max(a, b);
+        match_essential(&m->R[9 * (size_t)lo], &m->t[3 * (size_t)lo], &m->R[9 * (size_t)hi], &m->t[3 * (size_t)hi], t.E);
+    }
+    return t;
+}
+
+double gate_tau2(const lvba_match_s *m, const lvba_match_opts &o)
+{
+    const double tau = (2.0 * o.max_epipolar_px) / m->focal_sum;
+    return tau * tau;
+}
+
+// the scan of `tasks` (results at their out_off in d_best / d_s1 / d_s2), one grid
+int32_t scan_tasks(hipStream_t s, const lvba_match_s *m, const std::vector<MatchTask> &tasks, const lvba_match_opts &o, int32_t *d_best,
+                   int32_t *d_s1, int32_t *d_s2)
+{
+    std::vector<int2> tiles;
+    for (size_t k = 0; k < tasks.size(); ++k)
+        for (int r = 0; r < tasks[k].n_a; r += SCAN_ROWS) tiles.push_back(make_int2((int)k, r));
+    if (tiles.empty()) return LVBA_OK;
+    DevBuf d_tasks(s), d_tiles(s);
+    HIPCHK(d_tasks.alloc(sizeof(MatchTask) * tasks.size())); HIPCHK(d_tiles.alloc(sizeof(int2) * tiles.size()));
+    HIPCHK(lvba::copy_h2d(d_tasks.p, tasks.data(), sizeof(MatchTask) * tasks.size()));
+    HIPCHK(lvba::copy_h2d(d_tiles.p, tiles.data(), sizeof(int2) * tiles.size()));
+    if (o.guided)
+        match_scan_kernel<true><<<(unsigned)tiles.size(), SCAN_BLOCK, 0, s>>>(d_tasks.as<MatchTask>(), d_tiles.as<int2>(), m->d_desc, m->d_bias,
+                                                                            m->d_xy, gate_tau2(m, o), d_best, d_s1, d_s2);
+    else
+        match_scan_kernel<false><<<(unsigned)tiles.size(), SCAN_BLOCK, 0, s>>>(d_tasks.as<MatchTask>(), d_tiles.as<int2>(), m->d_desc, m->d_bias,
+                                                                             nullptr, 0.0, d_best, d_s1, d_s2);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s)); // the task and tile lists go with this scope
+    return LVBA_OK;
+}
+
+} // namespace
+
+extern "C" void lvba_match_default_opts(lvba_match_opts *o)
+{
+    if (!o) return;
+    *o = lvba_match_opts{};
+    o->max_distance = 0.7; o->max_ratio = 0.8; o->mutual = 1; o->guided = 0; o->max_epipolar_px = 4.0;
+}
+
+extern "C" int32_t lvba_match_create(int32_t device, int32_t n_images, const int64_t *desc_off, const uint8_t *desc, lvba_match_t *out)
+{
+    if (!out || n_images < 0 || !desc_off) return lvba_fail(LVBA_ERR_ARG, "null argument or n_images < 0");
+    if (desc_off[0] != 0) return lvba_fail(LVBA_ERR_ARG, "desc_off[0] = %lld (0)", (long long)desc_off[0]);
+    for (int i = 0; i < n_images; ++i) {
+        const int64_t n = desc_off[i + 1] - desc_off[i];
+        if (n < 0) return lvba_fail(LVBA_ERR_ARG, "desc_off decreases at image %d", i);
+        if (n > MATCH_MAX_PER_IMAGE)
+            return lvba_fail(LVBA_ERR_ARG, "image %d has %lld descriptors (at most %lld)", i, (long long)n, (long long)MATCH_MAX_PER_IMAGE);
+    }
+    const int64_t total = desc_off[n_images];
+    if (total > 0 && !desc) return lvba_fail(LVBA_ERR_ARG, "null descriptors");
+    TRY(check_device(device));
+    HIPCHK(hipSetDevice(device));
+    lvba_match_s *m = new lvba_match_s;
+    m->device = device; m->n_images = n_images;
+    m->off.assign(desc_off, desc_off + n_images + 1);
+    if (total > 0) {
+        std::vector<uint8_t> biased((size_t)total * MATCH_DIM);
+        std::vector<int32_t> bias((size_t)total);
+        for (int64_t i = 0; i < total; ++i) {
+            int32_t sum = 0;
+            for (int k = 0; k < MATCH_DIM; ++k) {
+                const uint8_t v = desc[i * MATCH_DIM + k];
+                biased[(size_t)i * MATCH_DIM + k] = v ^ 0x80;
+                sum += (int32_t)v - 128;
+            }
+            bias[(size_t)i] = 128 * sum;
+        }
+        hipError_t e = DevicePool::get().alloc((void **)&m->d_desc, biased.size());
+        if (e == hipSuccess) e = DevicePool::get().alloc((void **)&m->d_bias, 4 * bias.size());
+        if (e == hipSuccess) e = lvba::copy_h2d(m->d_desc, biased.data(), biased.size());
+        if (e == hipSuccess) e = lvba::copy_h2d(m->d_bias, bias.data(), 4 * bias.size());
+        if (e != hipSuccess) {
+            lvba_match_destroy(m);
+            return lvba_fail(e == hipErrorOutOfMemory ? LVBA_ERR_NOMEM : LVBA_ERR_DEVICE, "descriptor upload: %s", hipGetErrorString(e));
+        }
+    }
+    *out = m;
+    return LVBA_OK;
+}
+
+extern "C" int32_t lvba_match_destroy(lvba_match_t m)
+{
+    if (!m) return LVBA_OK;
+    (void)hipSetDevice(m->device);
+    (void)hipDeviceSynchronize();
+    if (m->d_desc) DevicePool::get().free(m->d_desc);
+    if (m->d_bias) DevicePool::get().free(m->d_bias);
+    if (m->d_xy) DevicePool::get().free(m->d_xy);
+    delete m;
+    return LVBA_OK;
+}
+
+extern "C" int32_t lvba_match_set_geometry(lvba_match_t m, const float *keypoints_uv, const double *intr, const double *Rcw, const double *tcw)
+{
+    if (!m || !intr || (m->n_images > 0 && (!Rcw || !tcw))) return lvba_fail(LVBA_ERR_ARG, "null argument");
+    const int64_t total = m->off[m->n_images];
+    if (total > 0 && !keypoints_uv) return lvba_fail(LVBA_ERR_ARG, "null keypoints");
+    for (int k = 0; k < 8; ++k)
+        if (!std::isfinite(intr[k])) return lvba_fail(LVBA_ERR_ARG, "intrinsic %d is not finite", k);
+    if (!(intr[0] > 0.0 && intr[1] > 0.0)) return lvba_fail(LVBA_ERR_ARG, "focal lengths %g, %g (> 0)", intr[0], intr[1]);
+    for (int i = 0; i < m->n_images; ++i) {
+        const double *R = Rcw + 9 * (size_t)i, *t = tcw + 3 * (size_t)i;
+        for (int k = 0; k < 9; ++k)
+            if (!std::isfinite(R[k])) return lvba_fail(LVBA_ERR_ARG, "camera %d: non-finite rotation", i);
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(t[k])) return lvba_fail(LVBA_ERR_ARG, "camera %d: non-finite translation", i);
+        for (int a = 0; a < 3; ++a)
+            for (int b = 0; b < 3; ++b) {
+                const double d = R[3 * a] * R[3 * b] + R[3 * a + 1] * R[3 * b + 1] + R[3 * a + 2] * R[3 * b + 2] - (a == b ? 1.0 : 0.0);
+                if (!(std::fabs(d) <= 1e-6)) return lvba_fail(LVBA_ERR_ARG, "camera %d: rotation not orthonormal within 1e-6", i);
+            }
+        const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
+        if (!(det > 0.0)) return lvba_fail(LVBA_ERR_ARG, "camera %d: rotation with determinant %g", i, det);
+    }
+    HIPCHK(hipSetDevice(m->device));
+    if (total > 0) {
+        if (!m->d_xy) HIPCHK(DevicePool::get().alloc((void **)&m->d_xy, 16 * (size_t)total));
+        ScopedStream sg;
+        HIPCHK(sg.acquire());
+        DevBuf d_uv(sg.s);
+        HIPCHK(d_uv.alloc(8 * (size_t)total));
+        HIPCHK(lvba::copy_h2d(d_uv.p, keypoints_uv, 8 * (size_t)total));
+        TrkIntr cam{intr[0], intr[1], intr[2], intr[3], intr[4], intr[5], intr[6], intr[7]};
+        match_undistort_kernel<<<grid_for(total, 256), 256, 0, sg.s>>>(total, d_uv.as<float>(), cam, m->d_xy);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(sg.s));
+    }
+    m->R.assign(Rcw, Rcw + 9 * (size_t)m->n_images);
+    m->t.assign(tcw, tcw + 3 * (size_t)m->n_images);
+    m->focal_sum = intr[0] + intr[1];
+    m->has_geometry = true;
+    return LVBA_OK;
+}
+
+extern "C" int32_t lvba_match_scan(lvba_match_t m, int32_t a, int32_t b, const lvba_match_opts *opts, int32_t *best, int32_t *s1, int32_t *s2)
+{
+    if (!m) return lvba_fail(LVBA_ERR_ARG, "null handle");
+    lvba_match_opts o;
+    TRY(check_opts(opts, o));
+    TRY(check_pair(m, a, b, o));
+    const size_t n_a = (size_t)(m->off[a + 1] - m->off[a]);
+    if (n_a > 0 && (!best || !s1 || !s2)) return lvba_fail(LVBA_ERR_ARG, "null output");
+    if (n_a == 0) return LVBA_OK;
+    HIPCHK(hipSetDevice(m->device));
+    ScopedStream sg;
+    HIPCHK(sg.acquire());
+    DevBuf d_out(sg.s);
+    HIPCHK(d_out.alloc(12 * n_a));
+    int32_t *d = d_out.as<int32_t>();
+    std::vector<MatchTask> tasks{make_task(m, a, b, 0, o.guided != 0)};
+    TRY(scan_tasks(sg.s, m, tasks, o, d, d + n_a, d + 2 * n_a));
+    HIPCHK(lvba::copy_d2h(best, d, 4 * n_a));
+    HIPCHK(lvba::copy_d2h(s1, d + n_a, 4 * n_a));
+    HIPCHK(lvba::copy_d2h(s2, d + 2 * n_a, 4 * n_a));
+    return LVBA_OK;
+}
+
+extern "C" int32_t lvba_match_pairs(lvba_match_t m, int64_t n_pairs, const int32_t *pairs, const lvba_match_opts *opts, int64_t capacity,
+                                    int32_t *matches, int32_t *scores, int64_t *match_off, int64_t *count)
+{
+    if (!m || !count || !match_off || n_pairs < 0 || capacity < 0 || (n_pairs > 0 && !pairs) || (capacity > 0 && !matches))
+        return lvba_fail(LVBA_ERR_ARG, "null argument, n_pairs < 0 or capacity < 0");
+    lvba_match_opts o;
+    TRY(check_opts(opts, o));
+    for (int64_t p = 0; p < n_pairs; ++p) TRY(check_pair(m, pairs[2 * p], pairs[2 * p + 1], o));
+    *count = 0;
+    match_off[0] = 0;
+    if (n_pairs == 0) return LVBA_OK;
+    HIPCHK(hipSetDevice(m->device));
+    ScopedStream sg;
+    HIPCHK(sg.acquire());
+    hipStream_t s = sg.s;
+    int64_t base = 0; // matches before the current chunk
+    for (int64_t p0 = 0; p0 < n_pairs;) {
+        // a chunk: as many pairs as keep the scanned rows of one grid under CHUNK_ROWS (a single pair may exceed it)
+        std::vector<MatchTask> tasks;
+        std::vector<int64_t> row_off;
+        std::vector<MatchPairOut> po;
+        int64_t rows = 0, fwd_rows = 0, p1 = p0;
+        for (; p1 < n_pairs && p1 - p0 < INT32_MAX / 4; ++p1) {
+            const int a = pairs[2 * p1], b = pairs[2 * p1 + 1];
+            const int64_t n_a = m->off[a + 1] - m->off[a], n_b = m->off[b + 1] - m->off[b];
+            const int64_t need = n_a + (o.mutual ? n_b : 0);
+            if (p1 > p0 && rows + need > CHUNK_ROWS) break;
+            MatchPairOut q; q.fwd = rows; q.rev = rows + n_a;
+            tasks.push_back(make_task(m, a, b, q.fwd, o.guided != 0));
+            if (o.mutual) tasks.push_back(make_task(m, b, a, q.rev, o.guided != 0));
+            row_off.push_back(fwd_rows); po.push_back(q);
+            rows += need; fwd_rows += n_a;
+        }
+        const int np = (int)(p1 - p0);
+        row_off.push_back(fwd_rows);
+        if (fwd_rows > 0) {
+            DevBuf d_res(s), d_row_off(s), d_po(s), d_flag(s), d_excl(s), d_off(s), d_m(s), d_sc(s);
+            HIPCHK(d_res.alloc(12 * (size_t)rows));
+            int32_t *d_best = d_res.as<int32_t>(), *d_s1 = d_best + rows, *d_s2 = d_s1 + rows;
+            TRY(scan_tasks(s, m, tasks, o, d_best, d_s1, d_s2));
+            HIPCHK(d_row_off.alloc(8 * row_off.size())); HIPCHK(d_po.alloc(sizeof(MatchPairOut) * po.size()));
+            HIPCHK(d_flag.alloc(4 * ((size_t)fwd_rows + 1))); HIPCHK(d_excl.alloc(4 * ((size_t)fwd_rows + 1))); HIPCHK(d_off.alloc(8 * (size_t)np));
+            HIPCHK(lvba::copy_h2d(d_row_off.p, row_off.data(), 8 * row_off.size()));
+            HIPCHK(lvba::copy_h2d(d_po.p, po.data(), sizeof(MatchPairOut) * po.size()));
+            match_decide_kernel<<<grid_for(fwd_rows + 1, 256), 256, 0, s>>>(fwd_rows, np, d_row_off.as<int64_t>(), d_po.as<MatchPairOut>(), d_best,
+                                                                          d_s1, d_s2, o.max_distance, o.max_ratio, o.mutual, d_flag.as<uint32_t>());
+            HIPCHK(hipGetLastError());
+            TRY(scan_excl<uint32_t>(s, d_flag.as<uint32_t>(), d_excl.as<uint32_t>(), (size_t)fwd_rows + 1));
+            uint32_t found = 0;
+            HIPCHK(hipStreamSynchronize(s));
+            HIPCHK(lvba::copy_d2h(&found, d_excl.as<uint32_t>() + fwd_rows, 4));
+            const int64_t n_out = std::max<int64_t>(0, std::min<int64_t>(found, capacity - base));
+            HIPCHK(d_m.alloc(8 * (size_t)n_out)); HIPCHK(d_sc.alloc(4 * (size_t)n_out));
+            match_write_kernel<<<grid_for(std::max<int64_t>(fwd_rows, np), 256), 256, 0, s>>>(
+                fwd_rows, np, d_row_off.as<int64_t>(), d_po.as<MatchPairOut>(), d_best, d_s1, d_flag.as<uint32_t>(), d_excl.as<uint32_t>(), base,
+                n_out, d_m.as<int32_t>(), d_sc.as<int32_t>(), d_off.as<int64_t>());
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipStreamSynchronize(s));
+            HIPCHK(lvba::copy_d2h(match_off + p0, d_off.p, 8 * (size_t)np));
+            if (n_out > 0) {
+                HIPCHK(lvba::copy_d2h(matches + 2 * base, d_m.p, 8 * (size_t)n_out));
+                if (scores) HIPCHK(lvba::copy_d2h(scores + base, d_sc.p, 4 * (size_t)n_out));
+            }
+            base += found;
+        } else {
+            for (int64_t p = p0; p < p1; ++p) match_off[p] = base;
+        }
+        p0 = p1;
+    }
+    match_off[n_pairs] = base;
+    *count = base;
+    return LVBA_OK;
+}

@@ -1,0 +1,101 @@
+// match_device.h -- scalar pieces of the descriptor matcher (match.hip; the rule is in include/lvba_hip.h):
+// the running top two of a row, their merge, the epipolar gate and the fp64 decision.  Host/device-neutral, like tracks_device.h.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+#include "tracks_device.h"
+
+namespace lvba {
+
+constexpr int MATCH_DIM = 128;                    // bytes per descriptor
+constexpr int32_t MATCH_NONE = INT32_MIN;         // "no column yet": below every biased score
+// sum a b = sum a'b' + 128 (sum a' + sum b') + 128 * 128 * 128 with a' = a - 128: the last term
+constexpr int32_t MATCH_BIAS_CONST = 128 * 128 * 128;
+constexpr double MATCH_SCORE_SCALE = 262144.0;    // 512^2
+constexpr double MATCH_BASELINE_REL2 = 1e-20;     // |t_ab|^2 <= this (|t_a|^2 + |t_b|^2): no epipolar geometry
+
+// Running (s1, best, s2) of one row over the columns one lane sees, in ascending column order: a strict > keeps the lowest column
+// of a tie.  The scores are biased by a per-row constant, which no comparison within a row sees.
+struct MatchTop { int32_t s1, best, s2; };
+
+LVBA_TRK_FN MatchTop match_top_none() { MatchTop t; t.s1 = MATCH_NONE; t.best = -1; t.s2 = MATCH_NONE; return t; }
+
+LVBA_TRK_FN void match_top_update(MatchTop &t, int32_t v, int32_t col)
+{
+    const int32_t lo = v < t.s1 ? v : t.s1;       // s2 <= s1 always: the median of (v, s1, s2)
+    t.s2 = t.s2 > lo ? t.s2 : lo;
+    t.best = v > t.s1 ? col : t.best;
+    t.s1 = v > t.s1 ? v : t.s1;
+}
+
+// the top two of the union of two disjoint column sets
+LVBA_TRK_FN MatchTop match_top_merge(const MatchTop &a, const MatchTop &b)
+{
+    const bool a_wins = a.s1 > b.s1 || (a.s1 == b.s1 && (uint32_t)a.best < (uint32_t)b.best); // -1 (none) loses every tie
+    MatchTop t;
+    t.s1 = a_wins ? a.s1 : b.s1;
+    t.best = a_wins ? a.best : b.best;
+    const int32_t other = a_wins ? b.s1 : a.s1, own = a_wins ? a.s2 : b.s2;
+    t.s2 = own > other ? own : other;
+    return t;
+}
+
+// Epipolar gate.  "lo" is the image of the pair with the smaller index, "hi" the other; E maps lo to hi.  Both orientations of a
+// pair evaluate these same expressions on the same operands, so the decision for (r, c) and for (c, r) is one bit.
+struct MatchLine { double l0, l1, l2, n; };
+
+LVBA_TRK_FN MatchLine match_line_lo(const double *E, double x, double y)   // l = E x, n = l0^2 + l1^2
+{
+    MatchLine m;
+    m.l0 = (E[0] * x + E[1] * y) + E[2];
+    m.l1 = (E[3] * x + E[4] * y) + E[5];
+    m.l2 = (E[6] * x + E[7] * y) + E[8];
+    m.n = m.l0 * m.l0 + m.l1 * m.l1;
+    return m;
+}
+LVBA_TRK_FN double match_norm_hi(const double *E, double x, double y)       // l' = E^T x, l'0^2 + l'1^2
+{
+    const double m0 = (E[0] * x + E[3] * y) + E[6];
+    const double m1 = (E[1] * x + E[4] * y) + E[7];
+    return m0 * m0 + m1 * m1;
+}
+LVBA_TRK_FN bool match_gate(const MatchLine &lo, double hx, double hy, double n_hi, double tau2)
+{
+    const double e = (hx * lo.l0 + hy * lo.l1) + lo.l2;
+    return e * e <= tau2 * (lo.n + n_hi);          // false when a NaN (failed undistortion) is in it
+}
+
+// E of the ordered pair (lo, hi) from T_cam<-world of both; all zero when the centres coincide
+LVBA_TRK_FN void match_essential(const double *Rlo, const double *tlo, const double *Rhi, const double *thi, double *E)
+{
+    double R[9], t[3];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) R[3 * i + j] = (Rhi[3 * i] * Rlo[3 * j] + Rhi[3 * i + 1] * Rlo[3 * j + 1]) + Rhi[3 * i + 2] * Rlo[3 * j + 2];
+    for (int i = 0; i < 3; ++i) t[i] = thi[i] - ((R[3 * i] * tlo[0] + R[3 * i + 1] * tlo[1]) + R[3 * i + 2] * tlo[2]);
+    const double tt = (t[0] * t[0] + t[1] * t[1]) + t[2] * t[2];
+    const double ref = ((tlo[0] * tlo[0] + tlo[1] * tlo[1]) + tlo[2] * tlo[2]) + ((thi[0] * thi[0] + thi[1] * thi[1]) + thi[2] * thi[2]);
+    if (tt <= MATCH_BASELINE_REL2 * ref) {
+        for (int k = 0; k < 9; ++k) E[k] = 0.0;
+        return;
+    }
+    for (int j = 0; j < 3; ++j) {
+        E[j] = t[1] * R[6 + j] - t[2] * R[3 + j];
+        E[3 + j] = t[2] * R[j] - t[0] * R[6 + j];
+        E[6 + j] = t[0] * R[3 + j] - t[1] * R[j];
+    }
+}
+
+LVBA_TRK_FN double match_distance(int32_t s)
+{
+    const double c = (double)s / MATCH_SCORE_SCALE;
+    return acos(c < 1.0 ? c : 1.0);
+}
+// the one-sided clauses of a match (the mutual clause is the caller's)
+LVBA_TRK_FN bool match_accept(int32_t best, int32_t s1, int32_t s2, double max_distance, double max_ratio)
+{
+    if (best < 0) return false;
+    const double d1 = match_distance(s1), d2 = match_distance(s2);
+    return d1 < max_distance && d1 < max_ratio * d2;
+}
+
+} // namespace lvba

@@ -327,3 +327,27 @@ def load_colmap_db(path, image_names, pairs):
         return kps, out
     finally:
         con.close()
+
+
+def load_colmap_descriptors(path, image_names):
+    """The `descriptors` table of a COLMAP database (rows, cols = 128, data as uint8) for image_names in the caller's order:
+    descriptors[i] = uint8 [n_i, 128], an empty array where the image, the table or the blob is missing or malformed (the
+    leniency of load_colmap_db).  Row k belongs to key point k of the `keypoints` table."""
+    import sqlite3
+    con = sqlite3.connect(path)
+    try:
+        name2id = {name: int(iid) for iid, name in con.execute("SELECT image_id, name FROM images")}
+        out = []
+        for n in image_names:
+            iid = name2id.get(n, -1)
+            try:
+                row = con.execute("SELECT rows, cols, data FROM descriptors WHERE image_id=?", (iid,)).fetchone() if iid >= 0 else None
+            except sqlite3.Error:
+                row = None
+            if row is None or row[2] is None or row[1] != 128 or row[0] <= 0 or len(row[2]) != row[0] * 128:
+                out.append(np.zeros((0, 128), np.uint8))
+            else:
+                out.append(np.frombuffer(row[2], np.uint8).reshape(row[0], 128).copy())
+        return out
+    finally:
+        con.close()

@@ -586,10 +586,21 @@ def run_lidar_ba(scans, poses, priors=None, window_loss=None, stage_loss=None, h
     return out, report
 
 
+def match_image_pairs(descriptors, pairs, keypoints=None, Rcw=None, tcw=None, intr=None, device=0, **opts):
+    """Feature matches of image pairs from their descriptors (match.Matcher), in the form build_tracks and
+    run_full_pipeline take: one int32 [m, 2] array per pair, in the order of `pairs`; a pair without matches gives an empty
+    array, it is not dropped.  descriptors[i] = uint8 [n_i, 128].  Without geometry the matching is unguided (the reference's
+    fallback, src/lvba_system.cpp:697-833: distance bound, ratio test, mutual best match); with keypoints, Rcw, tcw
+    (T_cam<-world) and intr a candidate must also lie within max_epipolar_px of the epipolar line the poses give.  opts:
+    max_distance, max_ratio, mutual, max_epipolar_px."""
+    from . import match as M
+    return M.match_pairs(descriptors, pairs, keypoints=keypoints, intr=intr, Rcw=Rcw, tcw=tcw, device=device, **opts)
+
+
 def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, tci, intr, width, height, keypoints, pairs,
                       matches, enable_lidar_ba=True, enable_visual_ba=True, device=0, images=None, lidar_priors=None,
                       window_loss=None, stage_loss=None, camera_priors=None, map_quality=False, loop_closures=None, relax=None,
-                      **cfg):
+                      match_fn=None, **cfg):
     """LvbaSystem::runFullPipeline (src/lvba_system.cpp:136-142) on in-memory data: clouds = body-frame [n_i, >=3] float32
     arrays, poses [n,12] = x_buf_ (T_world<-imu), image_poses [m,12] the image poses from the odometry.  cfg: DEFAULTS' keys
     (visual_loss, colorize_leaf among them).  images: None, or the images ([m,H,W,3] BGR uint8 or a callable k -> [H,W,3]):
@@ -606,7 +617,10 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
     against one another first (consistent_closures) and only the mutually consistent ones become priors.
     relax: None (off), True, or a dict of relax_trajectory's options; honoured only together with loop_closures: after the closures
     are found (and vetted), the trajectory is relaxed over them, the LiDAR stage starts from the relaxed poses with the same
-    closures as priors, and the output holds pose_graph = dict(report, weights, max_pose_change).  poses_before stays the input."""
+    closures as priors, and the output holds pose_graph = dict(report, weights, max_pose_change).  poses_before stays the input.
+    match_fn: None (pairs and matches are the caller's), or a callable cam_poses -> (pairs, matches), called after the LiDAR stage
+    with the LiDAR-derived image poses [m,12] (T_world<-imu): the matches are then made against the refined poses (guided
+    matching, match_image_pairs) and replace the arguments; the output holds pairs / matches as used."""
     if images is not None and not enable_visual_ba:
         raise ValueError("colouring the map needs the cameras of the visual stage (enable_visual_ba=True)")
     c = dict(DEFAULTS); c.update(cfg)
@@ -623,6 +637,9 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
             x_opt, report = run_lidar_ba(scans, x_opt, priors=lidar_priors, window_loss=window_loss, stage_loss=stage_loss, **c)
             out["lidar_report"] = report
         out["poses"] = np.asarray(x_opt).reshape(-1, 12)
+        if enable_visual_ba and match_fn is not None:
+            pairs, matches = match_fn(update_camera_poses_from_lidar(out["poses"], x_orig, scan_times, image_times, image_poses))
+            out["pairs"], out["matches"] = pairs, matches
         if enable_visual_ba:
             out["visual"] = run_visual_ba_with_lidar_assist(scans, out["poses"], x_orig, scan_times, image_times, image_poses, Rci,
                                                             tci, intr, width, height, keypoints, pairs, matches,
@@ -670,7 +687,8 @@ def extrinsics_from_config(Rcl, Pcl, extrinsic_R, extrinsic_T):
 
 
 def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrinsic_R=np.eye(3), extrinsic_T=np.zeros(3),
-                image_sample_step=1, out_dir=None, device=0, colorize=False, map_quality=False, loop_closures=None, relax=None, **cfg):
+                image_sample_step=1, out_dir=None, device=0, colorize=False, map_quality=False, loop_closures=None, relax=None,
+                matching="db", match_opts=None, **cfg):
     """initFromDatasetIO + runFullPipeline on a dataset directory; with out_dir, the refined LiDAR poses (TUM) and the COLMAP
     text files images.txt / points3D.txt the reference writes (src/lvba_system.cpp:2018-2137) are saved there.  images.txt is
     the reference's, character for character (tests/test_ref_system.py).
@@ -686,6 +704,11 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
     loop_closures.json, the report without its arrays; dict(consistency=True, ...) vets the closures against one another.
     relax (True or a dict, as for run_full_pipeline; only with loop_closures): the output gains pose_graph and out_dir gets
     pose_graph.json (the report, the closures' weights, the largest pose change).
+    matching: where the feature matches come from.  "db" (default): two_view_geometries of the database (loadFromColmapDB).
+    "descriptors": every image pair is matched from the database's descriptors table, unguided, as the reference's fallback does
+    when the database holds no verified matches (src/lvba_system.cpp:697-833; match_image_pairs).  "guided": the same, but after
+    the LiDAR stage and against the refined, LiDAR-derived camera poses, a candidate having to lie near its epipolar line -- the
+    one place where the order differs from the reference's.  match_opts: match_image_pairs' options for the last two.
     cfg as for run_full_pipeline, e.g. visual_loss=REFERENCE_HUBER, window_loss=("cauchy", 0.1), stage_loss=("huber", 0.05),
     camera_priors=lambda cams: lidar_camera_priors(cams, Rci, tci, 1e-3, 0.02)."""
     import os
@@ -700,11 +723,28 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
     pairs = [(i, j) for i in range(len(image_ids)) for j in range(i + 1, len(image_ids))]        # image_pairs_, :462-466
     kps, matches = D.load_colmap_db(colmap_db_path if os.path.isabs(colmap_db_path) else os.path.join(data_path, colmap_db_path),
                                     names, pairs)
-    keep = [k for k, m in enumerate(matches) if len(m)]
+    if matching not in ("db", "descriptors", "guided"):
+        raise ValueError(f"matching={matching!r}: one of 'db', 'descriptors', 'guided'")
     Rci, tci = extrinsics_from_config(Rcl, Pcl, extrinsic_R, extrinsic_T)
+    match_fn = None
+    if matching != "db":
+        descs = D.load_colmap_descriptors(colmap_db_path if os.path.isabs(colmap_db_path) else os.path.join(data_path, colmap_db_path),
+                                          names)
+        descs = [d if len(d) == len(k) else np.zeros((0, 128), np.uint8) for d, k in zip(descs, kps)]   # rows are key points
+        kps = [k if len(d) else k[:0] for d, k in zip(descs, kps)]
+        if matching == "descriptors":
+            matches = match_image_pairs(descs, pairs, device=device, **(match_opts or {}))
+        else:
+            def match_fn(cam_poses):
+                Rcw, tcw = camera_from_imu(cam_poses, Rci, tci)
+                m = match_image_pairs(descs, pairs, keypoints=[k[:, :2] for k in kps], Rcw=Rcw, tcw=tcw, intr=intr, device=device,
+                                      **(match_opts or {}))
+                kept = [k for k, mm in enumerate(m) if len(mm)]
+                return [pairs[k] for k in kept], [m[k] for k in kept]
+    keep = [k for k, m in enumerate(matches) if len(m)]
     out = run_full_pipeline([c[:, :3] for c in ds["clouds"]], ds["poses"], ds["timestamps"], image_ids, image_poses, Rci, tci, intr,
                             width, height, [k[:, :2] for k in kps], [pairs[k] for k in keep], [matches[k] for k in keep],
-                            device=device, images=(lambda k: D.read_image_bgr(os.path.join(img_dir, names[k]), width, height))
+                            device=device, **({"match_fn": match_fn} if match_fn is not None else {}), images=(lambda k: D.read_image_bgr(os.path.join(img_dir, names[k]), width, height))
                             if colorize else None, **({"map_quality": map_quality} if map_quality else {}),
                             **({"loop_closures": loop_closures} if loop_closures else {}),
                             **({"relax": relax} if relax and loop_closures else {}), **cfg)

@@ -1032,6 +1032,64 @@ int32_t lvba_posegraph_relax(int32_t n_poses, const double *poses, int32_t n_edg
                              lvba_lm_trace *trace, int32_t *n_trace /* may be NULL */,
                              lvba_posegraph_report *report);
 
+/* ---- descriptor matching of image pairs, with an optional pose-guided epipolar gate (opt-in) -------------------
+ *   The reference's fallback when its COLMAP database holds no verified matches (src/lvba_system.cpp:697-833) matches every image
+ *   pair with SiftMatchGPU::GetSiftMatch(n, buf, 0.7f, 0.8f, 1).  SiftGPU's source is not part of the reference tree: the rule
+ *   below is this project's own definition of those three documented parameters, restated by a numpy oracle and NOT pinned against
+ *   SiftGPU.
+ *   Descriptor: 128 uint8 values (nominal norm 512, as SiftGPU and COLMAP store them; nothing is assumed about the actual norm).
+ *   Image i has n_i >= 0 of them, at most 1 048 576.
+ *   Score  s(r, c) = sum_k a_r[k] b_c[k], an exact integer (< 2^23).   Distance  d = acos(min(s / 262144, 1)), in fp64.
+ *   Top two of row r of the ORDERED pair (a, b), over the columns that take part (all of b; under the gate those that pass it):
+ *     best(r) = the column of the largest score, the lowest column on a tie;  s1 = that score;
+ *     s2 = the largest score over the other columns, 0 when there is no other column (d2 = pi / 2).  A duplicate of the best column
+ *     gives s2 = s1.  A row with no column at all has best = -1, s1 = s2 = 0.
+ *   (r, c) is a match of the pair (a, b) iff  c = best_ab(r) >= 0,  d1 < max_distance,  d1 < max_ratio * d2 (the product in fp64,
+ *   rounded as written)  and, if mutual, best_ba(c) = r -- the same rule with the images swapped, under the gate with the same gate.
+ *   The distance and the mutual clause are symmetric in the two images, the ratio clause is not (d2 is the second best of the
+ *   row's own image): the matches of (b, a) are the transposed matches of (a, b) only where the ratio clause passes on both sides.
+ *   The matches of a pair are listed by ascending r, the pairs in the caller's order.  acos is the device's fp64 acos: a d1 within
+ *   an ulp or two of a bound may fall either side.
+ *   Guided gate (guided = 1, needs lvba_match_set_geometry).  Keypoints (u, v) are fp32 pixels; x^ = (x, y, 1) is the undistorted
+ *   normalised point (the reference's undistortPixelToNormalized, include/utils.hpp, fp64).  A keypoint whose undistortion fails
+ *   matches nothing under the gate, in any pair.  Cameras are T_cam<-world = (R, t), the visual stage's convention.  With lo the
+ *   image of the pair with the smaller index and hi the other:
+ *     R_lh = R_hi R_lo^T,  t_lh = t_hi - R_lh t_lo,  E = [t_lh]x R_lh               every sum left to right, no fused multiply-add
+ *     for a keypoint p of lo and a keypoint q of hi:
+ *       l = E x^_p,  n_lo = l0 l0 + l1 l1;    l' = E^T x^_q,  n_hi = l'0 l'0 + l'1 l'1;    e = (x_q l0 + y_q l1) + l2
+ *       the candidate passes iff  e e <= tau^2 (n_lo + n_hi)   (the Sampson distance),  tau = (2 max_epipolar_px) / (fx + fy)
+ *   The ordered pairs (lo, hi) and (hi, lo) evaluate these same expressions on the same operands (E of (hi, lo) is E^T): the
+ *   decision for (r, c) in one is bit for bit the decision for (c, r) in the other.  A pair whose centres coincide,
+ *   |t_lh|^2 <= 1e-20 (|t_lo|^2 + |t_hi|^2), has no epipolar geometry: E is taken as zero and every candidate (of keypoints whose
+ *   undistortion succeeded) passes.
+ *   lvba_match_create: desc_off [n_images + 1] (desc_off[0] = 0), desc [sum n][128]; the descriptors go to the device once.
+ *   lvba_match_set_geometry: keypoints_uv [sum n][2] in descriptor order, intr = (fx, fy, cx, cy, k1, k2, p1, p2), Rcw [n_images][9]
+ *   row-major, tcw [n_images][3]; undistorts on the device once; may be called again (new poses replace the old).
+ *   lvba_match_pairs: all pairs in one call, their work tiled over one grid per 2^23 scanned rows.  matches [capacity][2] = (r, c),
+ *   scores [capacity] (may be NULL) = s1 of each match, match_off [n_pairs + 1] the first match of each pair.  *count is the true
+ *   number of matches and match_off the true offsets even when they exceed capacity; only the first `capacity` matches are
+ *   written.  lvba_match_scan: best, s1, s2 [n_a] of the ordered pair (a, b) before any threshold (it reads only guided and
+ *   max_epipolar_px of the options).  No atomics: two calls give the same bytes.  Options: NULL takes the defaults.
+ *   LVBA_ERR_ARG: a null required pointer, a negative count, desc_off that does not start at 0 or decreases, an image above the
+ *   per-image limit, a pair index outside the images, a == b, an option outside its range below (non-finite included), guided
+ *   without geometry, non-finite intrinsics or poses, fx or fy <= 0, a rotation that is not orthonormal within 1e-6 with
+ *   determinant > 0.  A refused call writes nothing (a refused set_geometry keeps the geometry it had). */
+typedef struct lvba_match_s *lvba_match_t;
+typedef struct lvba_match_opts {
+    double max_distance;     /* rad, finite and > 0 (default 0.7) */
+    double max_ratio;        /* in (0, 1] (default 0.8) */
+    int32_t mutual;          /* 0 or 1 (default 1) */
+    int32_t guided;          /* 0 or 1 (default 0) */
+    double max_epipolar_px;  /* pixels, finite and > 0 (default 4) */
+} lvba_match_opts;
+void    lvba_match_default_opts(lvba_match_opts *o);
+int32_t lvba_match_create(int32_t device, int32_t n_images, const int64_t *desc_off, const uint8_t *desc, lvba_match_t *out);
+int32_t lvba_match_destroy(lvba_match_t m);
+int32_t lvba_match_set_geometry(lvba_match_t m, const float *keypoints_uv, const double *intr, const double *Rcw, const double *tcw);
+int32_t lvba_match_pairs(lvba_match_t m, int64_t n_pairs, const int32_t *pairs, const lvba_match_opts *o, int64_t capacity,
+                         int32_t *matches, int32_t *scores, int64_t *match_off, int64_t *count);
+int32_t lvba_match_scan(lvba_match_t m, int32_t a, int32_t b, const lvba_match_opts *o, int32_t *best, int32_t *s1, int32_t *s2);
+
 #ifdef __cplusplus
 }
 #endif
