@@ -1,6 +1,6 @@
 // lvba_api.hip -- BALM half of the C-ABI (include/lvba_hip.h): problem packing and the Nielsen-LM driver of
-// BALM2::damping_iter (reference include/BALM/bavoxel.hpp:662-767).  Host logic only; all arithmetic on problem
-// data runs in the kernels of balm_kernels.hip / ldlt.hip.  Shared machinery (ordering, assembly lists, solver,
+// BALM2::damping_iter (reference include/BALM/bavoxel.hpp:662-767; its damping rule is lm_rule.h).  Host logic only; all arithmetic on
+// problem data runs in the kernels of balm_kernels.hip / ldlt.hip.  Shared machinery (ordering, assembly lists, solver,
 // RCCL) lives in block_system.hip.  No CPU fallback.
 #include <math.h>
 #include <stdio.h>
@@ -14,6 +14,7 @@
 #include "block_system.h"
 #include "host_tables.h"
 #include "prior_tables.h"
+#include "lm_rule.h"
 
 using namespace lvba;
 
@@ -54,11 +55,11 @@ struct lvba_balm_s {
     double *d_gscal = nullptr;         // [3][n_groups]: cost at the current poses, cost at the trial poses, q1 numerator
     double *h_gpin = nullptr;          // pinned, [3][n_groups]
     int32_t *h_gacc = nullptr;         // pinned, [n_groups]
-    // LM state (bavoxel.hpp:664-671)
-    bool lm_active = false, lm_done = false, is_calc_hess = true;
+    // LM state (bavoxel.hpp:664-671): u, v, is_calc_hess, the iteration count and the stop flag are the rule's (lm_rule.h)
+    bool lm_active = false;
     lvba_balm_opts lm_opts{};
-    double u = 0.01, v = 2.0, residual1 = 0.0;
-    int iter = 0;
+    LmRule lm;
+    double residual1 = 0.0;
     bool have_eval = false;
     // the voxel records (d_vrec) and chunk costs belong to the poses in d_pose_cur: the LM loop costs its trial point with the
     // voxel pass of the evaluation, and an accepted trial point is where the next evaluation happens
@@ -802,11 +803,10 @@ extern "C" int32_t lvba_balm_lm_begin(lvba_balm_t h, const double *poses, const 
     if (opts) h->lm_opts = *opts; else lvba_balm_default_opts(&h->lm_opts);
     if (h->lm_opts.max_iter < 0) return fail(LVBA_ERR_ARG, "max_iter < 0");
     TRY(upload_poses(h, poses, h->d_pose_cur));
-    h->u = h->lm_opts.u0; h->v = h->lm_opts.v0;
-    h->is_calc_hess = true; h->iter = 0; h->residual1 = 0.0;
+    h->lm.begin(h->lm_opts.u0, h->lm_opts.v0, h->lm_opts.max_iter);
+    h->residual1 = 0.0;
     h->lin_at_cur = false;
     h->lm_active = true;
-    h->lm_done = h->lm_opts.max_iter == 0;
     return LVBA_OK;
 }
 
@@ -815,62 +815,38 @@ extern "C" int32_t lvba_balm_lm_step(lvba_balm_t h, lvba_lm_trace *row, int32_t 
 {
     if (!h) return fail(LVBA_ERR_ARG, "handle is NULL");
     if (!h->lm_active) return fail(LVBA_ERR_STATE, "lm_step without lm_begin");
-    if (h->lm_done) { if (done) *done = 1; return fail(LVBA_ERR_STATE, "LM loop already finished"); }
+    LmRule &lm = h->lm;
+    if (lm.done) { if (done) *done = 1; return fail(LVBA_ERR_STATE, "LM loop already finished"); }
     HIPCHK(hipSetDevice(h->bs.device));
-    const bool evaluated = h->is_calc_hess;
+    const bool evaluated = lm.evaluate;
     // The trial point is costed by the VOXEL PASS of the evaluation (cost + voxel records): an accepted trial point is where the
     // next evaluation happens, and that evaluation then starts from the records (factor pass, pair pass) instead of reading
     // and eigen-decomposing every voxel again.  A rejected step wastes the difference to the cost-only kernel (C3: 0.04 ms).
     // Also on voxel shards (the records are local).
-    const bool with_lin = true;
-    if (evaluated) TRY(enqueue_eval(h, h->d_pose_cur, with_lin && h->lin_at_cur));         // :688-689
-    TRY(enqueue_solve(h, h->u));                                                           // :692-710
-    const int n_q1 = launch_retract_q1(h->d_pose_cur, h->bs.d_dx, h->d_pose_trial, h->N, h->bs.Hblk(), h->bs.Bb, h->bs.g(), h->u, h->d_q1part,
+    if (evaluated) TRY(enqueue_eval(h, h->d_pose_cur, h->lin_at_cur));                     // :688-689
+    TRY(enqueue_solve(h, lm.u));                                                           // :692-710
+    const int n_q1 = launch_retract_q1(h->d_pose_cur, h->bs.d_dx, h->d_pose_trial, h->N, h->bs.Hblk(), h->bs.Bb, h->bs.g(), lm.u, h->d_q1part,
                                        h->stream());                                       // :722-729 (retraction + the q1 numerator's shares)
-    TRY(enqueue_cost(h, h->d_pose_trial, h->d_scal2, with_lin));                           // :731 (+ the linearisation at the trial point)
+    TRY(enqueue_cost(h, h->d_pose_trial, h->d_scal2, true));                               // :731 (+ the linearisation at the trial point)
     h->lin_at_cur = false; // it belongs to the trial point now
     launch_lm_report(h->d_scal2, h->d_q1part, n_q1, h->bs.scal(), h->bs.d_status, h->h_pin, h->stream()); // -> pinned host memory, zero-copy
     HIPCHK(hipStreamSynchronize(h->stream()));
     ev_collect(h);
     const double Vg = (double)h->Vglobal;
     if (evaluated) h->residual1 = h->h_pin[2] / Vg;                                        // AVG_THR :634-635
-    const double residual1 = h->residual1;
-    const double residual2 = h->h_pin[0] / Vg;
-    const double q1 = h->h_pin[1] / Vg;                                                    // :732
-    int st = 0;
-    { long long stl; memcpy(&stl, h->h_pin + 4, sizeof stl); st = (int)stl; }
-    double q = residual1 - residual2;                                                      // :736
-    int32_t status = LVBA_OK;
-    if (st) status = LVBA_NUM_FACTORIZATION;
-    else if (!isfinite(residual2) || !isfinite(residual1)) status = LVBA_NUM_NONFINITE;
-    // The reference checks neither the LDLT's info() nor the cost (:706-710, :731): a broken factorisation yields a non-finite
-    // step, hence a NaN residual2, `q > 0` is false, the step is rejected, u *= v, and the loop goes on with more damping
-    // (it can recover).  Same here: a flagged solve counts as a rejected step whatever the kernels left in dx.
-    if (st) q = NAN;
-    if (row) {
-        row->iter = h->iter; row->accepted = q > 0; row->evaluated = evaluated; row->status = status;
-        row->residual1 = residual1; row->residual2 = residual2; row->u = h->u; row->v = h->v; row->q = q; row->q1 = q1;
-    }
-    if (q > 0) {                                                                           // :744-752
+    long long st = 0;
+    memcpy(&st, h->h_pin + 4, sizeof st);
+    // :732-760, the costs averaged over the voxels; a flagged solve counts as a rejected step whatever the kernels left in dx
+    const lvba_lm_trace r = lm.step(h->residual1, h->h_pin[0] / Vg, h->h_pin[1] / Vg, (int)st != 0, h->lm_opts.rel_tol, h->lm_opts.max_iter, true);
+    if (row) *row = r;
+    if (r.accepted) {
         std::swap(h->d_pose_cur, h->d_pose_trial);
-        h->lin_at_cur = with_lin; // the trial point is the current point now
-        q = q / q1;
-        h->v = 2.0;
-        q = 1.0 - pow(2.0 * q - 1.0, 3.0);
-        h->u *= (q < (1.0 / 3.0) ? (1.0 / 3.0) : q);
-        h->is_calc_hess = true;
-    } else {                                                                               // :753-758
-        h->u = h->u * h->v;
-        h->v = 2.0 * h->v;
-        h->is_calc_hess = false;
+        h->lin_at_cur = true; // the trial point is the current point now
     }
-    h->iter += 1;
-    if (fabs(residual1 - residual2) / residual1 < h->lm_opts.rel_tol) h->lm_done = true;   // :760
-    if (h->iter >= h->lm_opts.max_iter) h->lm_done = true;                                 // :686
-    if (done) *done = h->lm_done ? 1 : 0;
+    if (done) *done = lm.done ? 1 : 0;
     // numerical statuses (> 0) are reported, not fatal: the caller may keep stepping, as BALM2::damping_iter does
-    if (status == LVBA_NUM_FACTORIZATION) return fail(status, "zero or non-finite pivot in LDL^T (iteration %d)", h->iter - 1);
-    if (status == LVBA_NUM_NONFINITE) return fail(status, "non-finite cost (iteration %d)", h->iter - 1);
+    if (r.status == LVBA_NUM_FACTORIZATION) return fail(r.status, "zero or non-finite pivot in LDL^T (iteration %d)", r.iter);
+    if (r.status == LVBA_NUM_NONFINITE) return fail(r.status, "non-finite cost (iteration %d)", r.iter);
     return LVBA_OK;
 }
 
@@ -892,7 +868,7 @@ extern "C" int32_t lvba_balm_refine(lvba_balm_t h, double *poses_inout, const lv
     if (!h || !poses_inout) return fail(LVBA_ERR_ARG, "NULL argument");
     if (n_trace) *n_trace = 0;
     TRY(lvba_balm_lm_begin(h, poses_inout, opts));
-    int32_t rows = 0, done = h->lm_done ? 1 : 0, rc = LVBA_OK, worst = LVBA_OK;
+    int32_t rows = 0, done = h->lm.done ? 1 : 0, rc = LVBA_OK, worst = LVBA_OK;
     char worst_msg[512] = "";
     while (!done) {
         lvba_lm_trace row;
@@ -996,29 +972,29 @@ extern "C" int32_t lvba_balm_refine_groups(lvba_balm_t h, double *poses_inout, c
     if (opts) o = *opts; else lvba_balm_default_opts(&o);
     if (o.max_iter < 0) return fail(LVBA_ERR_ARG, "max_iter < 0");
     const int32_t G = h->n_groups;
-    const int64_t n = 6 * (int64_t)h->N;
-    (void)n;
     BlockSys &bs = h->bs;
     hipStream_t s = h->stream();
     TRY(upload_poses(h, poses_inout, h->d_pose_cur));
-    struct St { double u, v, r1; bool calc, done; int iter; int32_t status; double first, last; };
+    struct St { LmRule lm; double r1; int32_t status; double first, last; };
     lvba::hvec<St> st((size_t)G);
-    for (auto &q : st) q = St{o.u0, o.v0, 0.0, true, o.max_iter == 0, 0, LVBA_OK, 0.0, 0.0};
+    for (auto &q : st) {
+        q = St{LmRule{}, 0.0, LVBA_OK, 0.0, 0.0};
+        q.lm.begin(o.u0, o.v0, o.max_iter);
+    }
     lvba::hvec<double> u((size_t)G);
     double *c1 = h->d_gscal, *c2 = h->d_gscal + G, *q1d = h->d_gscal + 2 * (int64_t)G;
     int32_t worst = LVBA_OK;
     for (;;) {
         bool any = false, need_eval = false;
-        for (const auto &q : st) { any = any || !q.done; need_eval = need_eval || (!q.done && q.calc); }
+        for (const auto &q : st) { any = any || !q.lm.done; need_eval = need_eval || (!q.lm.done && q.lm.evaluate); }
         if (!any) break;
         if (need_eval) { // :688-689 (groups whose last step was rejected get the same H, g, cost again: the kernels are deterministic)
             TRY(enqueue_eval(h, h->d_pose_cur));
-
             launch_reduce_chunks_groups(h->d_chunk_cost, h->d_gco, G, c1, s);
         }
         // finished groups stay in the joint system as identity blocks (negative damping: ldlt_prepare_kernel): they cost
         // nothing to factorise and cannot raise the pivot flag for the groups that are still running
-        for (int32_t k = 0; k < G; ++k) u[(size_t)k] = st[(size_t)k].done ? -1.0 : st[(size_t)k].u;
+        for (int32_t k = 0; k < G; ++k) u[(size_t)k] = st[(size_t)k].lm.done ? -1.0 : st[(size_t)k].lm.u;
         ev_begin(h, EV_SOLVE);
         TRY(bs_enqueue_solve_groups(bs, u.data()));                                            // :692-710
         ev_end(h, EV_SOLVE);
@@ -1037,29 +1013,15 @@ extern "C" int32_t lvba_balm_refine_groups(lvba_balm_t h, double *poses_inout, c
         for (int32_t k = 0; k < G; ++k) {
             St &q = st[(size_t)k];
             h->h_gacc[k] = 0;
-            if (q.done) continue;
+            if (q.lm.done) continue;
             const double Vg = (double)(h->g_vox_off[(size_t)k + 1] - h->g_vox_off[(size_t)k]);
-            if (need_eval && q.calc) q.r1 = h->h_gpin[k] / Vg;                                 // AVG_THR :634-635
-            const double r1 = q.r1, r2 = h->h_gpin[G + k] / Vg, q1 = h->h_gpin[2 * G + k] / Vg; // :732
-            double dq = r1 - r2;                                                               // :736
-            if (!isfinite(r1) || !isfinite(r2)) q.status = LVBA_NUM_NONFINITE;
-            if (q.iter == 0) q.first = r1;
-            q.last = dq > 0 ? r2 : r1;
-            if (dq > 0) {                                                                      // :744-752
-                h->h_gacc[k] = 1;
-                dq = dq / q1;
-                q.v = 2.0;
-                dq = 1.0 - pow(2.0 * dq - 1.0, 3.0);
-                q.u *= (dq < (1.0 / 3.0) ? (1.0 / 3.0) : dq);
-                q.calc = true;
-            } else {                                                                           // :753-758
-                q.u = q.u * q.v;
-                q.v = 2.0 * q.v;
-                q.calc = false;
-            }
-            q.iter += 1;
-            if (fabs(r1 - r2) / r1 < o.rel_tol) q.done = true;                                 // :760
-            if (q.iter >= o.max_iter) q.done = true;                                           // :686
+            if (need_eval && q.lm.evaluate) q.r1 = h->h_gpin[k] / Vg;                          // AVG_THR :634-635
+            if (q.lm.iter == 0) q.first = q.r1;
+            // :732-760, the costs averaged over the group's voxels
+            const lvba_lm_trace r = q.lm.step(q.r1, h->h_gpin[G + k] / Vg, h->h_gpin[2 * G + k] / Vg, false, o.rel_tol, o.max_iter, true);
+            h->h_gacc[k] = r.accepted;
+            q.last = r.accepted ? r.residual2 : r.residual1;
+            if (r.status > q.status) q.status = r.status;
             if (q.status > worst) worst = q.status;
         }
         HIPCHK(hipMemcpyAsync(h->d_gaccept, h->h_gacc, (size_t)G * sizeof(int32_t), hipMemcpyHostToDevice, s));
@@ -1068,7 +1030,7 @@ extern "C" int32_t lvba_balm_refine_groups(lvba_balm_t h, double *poses_inout, c
     }
     TRY(download_poses(h, h->d_pose_cur, poses_inout));
     for (int32_t k = 0; k < G; ++k) {
-        if (n_iter) n_iter[k] = st[(size_t)k].iter;
+        if (n_iter) n_iter[k] = st[(size_t)k].lm.iter;
         if (status) status[k] = st[(size_t)k].status;
         if (cost_first) cost_first[k] = st[(size_t)k].first;
         if (cost_last) cost_last[k] = st[(size_t)k].last;

@@ -6,6 +6,7 @@
 #include <string.h>
 #include <vector>
 #include "../../include/lvba_hip.h"
+#include "prior_device.h" // PL_*: the layout of a prior's lin record (PriorDev::lin)
 
 #define LVBA_CF 256   // max factors per chunk == workgroup size of the BALM kernels
 #define LVBA_CV 128   // max voxels per chunk (every voxel has >= 2 factors)
@@ -96,7 +97,7 @@ struct PriorRec {
 struct PriorDev {
     int32_t n = 0;
     const PriorRec *pr = nullptr;
-    double *lin = nullptr;     // [n][128] linearisation records
+    double *lin = nullptr;     // [n][PL_LIN] linearisation records
     double *part = nullptr;    // [(n + 63) / 64] per-workgroup shares of the cost
     unsigned *ticket = nullptr; // workgroups done (0 between launches)
     int64_t n_hblk = 0;
@@ -105,10 +106,6 @@ struct PriorDev {
     int32_t n_g = 0;
     const int32_t *gpose = nullptr, *goff = nullptr, *gsrc = nullptr;
 };
-
-// lin record of prior k (priors.hip, visual_priors.hip): [0] unused, [1..6] J_i^T e, [7..12] J_j^T e, [13..48] J_i^T J_i,
-// [49..84] J_j^T J_j, [85..120] cross block, 6 x 6 blocks in the store's element order (column-major: [c * 6 + r])
-enum { PL_GI = 1, PL_GJ = 7, PL_HII = 13, PL_HJJ = 49, PL_HX = 85 };
 
 // Device view of a visual handle's camera priors (lvba_visual_set_priors; visual_priors.hip).  Records and scatter tables are
 // those of the LiDAR stage (tab: pr, lin, part, ticket, tables), cameras in solver order; `active`: this rank adds them (rank 0

@@ -1,5 +1,6 @@
 // pose_graph.hip -- pose-graph relaxation over odometry and loop closures (lvba_posegraph_relax; the problem and the LM rule are in
-// include/lvba_hip.h, the per-edge arithmetic in posegraph_device.h, also compiled for the host by the tests).
+// include/lvba_hip.h, the rule's code in lm_rule.h, the per-edge arithmetic in posegraph_device.h, both also compiled for the host
+// by the tests).
 //
 // The edges are priors: N - 1 odometry steps, the caller's closures, one POSE prior on the anchor, in that order.  The assembly is
 // the prior tables' (PriorTables::bind with all_add = false and no other slots: every off-diagonal block is written by edges
@@ -23,12 +24,11 @@
 #include "block_system.h"
 #include "prior_tables.h"
 #include "posegraph_device.h"
+#include "lm_rule.h"
 
 using namespace lvba;
 
 namespace {
-
-static_assert(PG_GI == PL_GI && PG_GJ == PL_GJ && PG_HII == PL_HII && PG_HJJ == PL_HJJ && PG_HX == PL_HX, "lin record layout");
 
 // edge classes by index: [0, n_odom) odometry, [n_odom, n_odom + n_clos) closures, then the anchor
 struct PgEdges {
@@ -44,8 +44,8 @@ __global__ __launch_bounds__(256) void pg_odometry_kernel(PgEdges ed, const doub
     if (k >= ed.n_odom) return;
     PriorRec &p = ed.pr[k];
     double Xi[12], Xj[12], meas[12], oi[12], oj[12], L[36];
-#pragma unroll
-    for (int a = 0; a < 12; ++a) { Xi[a] = x0[12 * (int64_t)p.I + a]; Xj[a] = x0[12 * (int64_t)p.J + a]; }
+    prior_load_pose(x0, p.I, Xi);
+    prior_load_pose(x0, p.J, Xj);
     pg_odometry_record(Xi, Xj, inv_sigma_rot, inv_sigma_pos, meas, oi, oj, L);
 #pragma unroll
     for (int a = 0; a < 12; ++a) { p.meas[a] = meas[a]; p.oi[a] = oi[a]; p.oj[a] = oj[a]; }
@@ -65,12 +65,8 @@ __device__ __forceinline__ double pg_lin_one(const PriorRec &p, const double *__
                                              double *__restrict__ o, double *w)
 {
     double Ti[12], Tj[12];
-#pragma unroll
-    for (int a = 0; a < 12; ++a) Ti[a] = poses[12 * (int64_t)p.I + a];
-    if (KIND == PRIOR_RELATIVE) {
-#pragma unroll
-        for (int a = 0; a < 12; ++a) Tj[a] = poses[12 * (int64_t)p.J + a];
-    }
+    prior_load_pose(poses, p.I, Ti);
+    if (KIND == PRIOR_RELATIVE) prior_load_pose(poses, p.J, Tj);
     return pg_edge_lin(KIND, p.meas, p.oi, p.oj, p.L, Ti, Tj, p.flip != 0, loss_kind, loss_scale, o, w);
 }
 
@@ -82,7 +78,7 @@ __global__ __launch_bounds__(64) void pg_lin_kernel(PgEdges ed, const double *__
     double c = 0.0, co = 0.0, cc = 0.0, w;
     if (k < ed.n) {
         const PriorRec &p = ed.pr[k];
-        double *o = lin + PG_LIN * (int64_t)k;
+        double *o = lin + PL_LIN * (int64_t)k;
         if (k < ed.n_odom) c = co = pg_lin_one<PRIOR_RELATIVE>(p, poses, VLOSS_TRIVIAL, 0.0, o, &w);
         else if (k < ed.n_odom + ed.n_clos) c = cc = pg_lin_one<PRIOR_RELATIVE>(p, poses, ed.loss_kind, ed.loss_scale, o, &w);
         else c = pg_lin_one<PRIOR_POSE>(p, poses, VLOSS_TRIVIAL, 0.0, o, &w);
@@ -100,12 +96,8 @@ __global__ __launch_bounds__(64) void pg_cost_kernel(PgEdges ed, const double *_
         const PriorRec &p = ed.pr[k];
         const bool clos = k >= ed.n_odom && k < ed.n_odom + ed.n_clos;
         double Ti[12], Tj[12], w;
-#pragma unroll
-        for (int a = 0; a < 12; ++a) Ti[a] = poses[12 * (int64_t)p.I + a];
-        if (p.kind == PRIOR_RELATIVE) {
-#pragma unroll
-            for (int a = 0; a < 12; ++a) Tj[a] = poses[12 * (int64_t)p.J + a];
-        }
+        prior_load_pose(poses, p.I, Ti);
+        if (p.kind == PRIOR_RELATIVE) prior_load_pose(poses, p.J, Tj);
         c = pg_edge_cost(p.kind, p.meas, p.oi, p.oj, p.L, Ti, Tj, clos ? ed.loss_kind : VLOSS_TRIVIAL, ed.loss_scale, &w);
         if (k < ed.n_odom) co = c;
         if (clos) {
@@ -261,18 +253,18 @@ extern "C" int32_t lvba_posegraph_relax(int32_t n_poses, const double *poses, in
 
     const unsigned egrid = (unsigned)((E + 63) / 64);
     const int64_t Bb1 = (int64_t)bs.Bb + 1, n6 = 6 * (int64_t)N;
-    double u = 0.01, v = 2.0, cost_first = 0.0, max_step = 0.0;
-    bool evaluate = true;
-    int32_t rows = 0, accepted = 0, worst = LVBA_OK;
+    double cost_first = 0.0, max_step = 0.0;
+    int32_t accepted = 0, worst = LVBA_OK;
+    LmRule lm;
+    lm.begin(0.01, 2.0, o.max_iter);
     std::vector<lvba_lm_trace> tr;
-    for (int32_t it = 0; it < o.max_iter; ++it) {
-        const bool evaluated = evaluate;
-        if (evaluate) {
+    while (!lm.done) {
+        if (lm.evaluate) {
             pg_zero_kernel<<<(unsigned)((42 * (int64_t)N + 255) / 256), 256, 0, s>>>(bs.Hblk(), bs.g(), N, Bb1);
             pg_lin_kernel<<<egrid, 64, 0, s>>>(ed, d_cur, pd.lin, pd.part, pd.ticket, d_sc);
             launch_prior_scatter(pd, bs.Hblk(), bs.g(), s);
             HIPCHK(hipGetLastError());
-            if (it == 0) { // the first cost decides whether anything runs at all
+            if (lm.iter == 0) { // the first cost decides whether anything runs at all
                 HIPCHK(hipMemcpyAsync(pin + 4, d_sc, sizeof(double), hipMemcpyDeviceToHost, s));
                 HIPCHK(hipStreamSynchronize(s));
                 cost_first = pin[4];
@@ -280,42 +272,24 @@ extern "C" int32_t lvba_posegraph_relax(int32_t n_poses, const double *poses, in
                 if (cost_first == 0.0) break;
             }
         }
-        TRY(bs_enqueue_solve(bs, u));
+        TRY(bs_enqueue_solve(bs, lm.u));
         launch_retract(d_cur, bs.d_dx, d_trial, N, s);
-        launch_predicted_decrease(bs.Hblk(), bs.Bb, bs.g(), bs.d_dx, u, n6, d_sc + 6, s);
+        launch_predicted_decrease(bs.Hblk(), bs.Bb, bs.g(), bs.d_dx, lm.u, n6, d_sc + 6, s);
         pg_cost_kernel<<<egrid, 64, 0, s>>>(ed, d_trial, pd.part, pd.ticket, d_sc + 3, nullptr);
         pg_report_kernel<<<1, 256, 0, s>>>(d_sc, bs.d_dx, n6, bs.d_status, pin);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(s));
-        const double C1 = pin[4], C2 = pin[0], q1 = pin[3];
-        const bool flagged = pin[7] != 0.0;
-        double q = flagged ? NAN : C1 - C2;
-        int32_t status = LVBA_OK;
-        if (flagged) status = LVBA_NUM_FACTORIZATION;
-        else if (!std::isfinite(C2) || !std::isfinite(C1)) status = LVBA_NUM_NONFINITE;
-        worst = std::max(worst, status);
-        lvba_lm_trace row{};
-        row.iter = it; row.accepted = q > 0; row.evaluated = evaluated; row.status = status;
-        row.residual1 = C1; row.residual2 = C2; row.u = u; row.v = v; row.q = q; row.q1 = q1;
+        // the plain sums; a rejected row does not stop the loop (the header's rule: q / C1 < rel_tol on acceptance)
+        const lvba_lm_trace row = lm.step(pin[4], pin[0], pin[3], pin[7] != 0.0, o.rel_tol, o.max_iter, false);
         tr.push_back(row);
-        ++rows;
-        bool stop = false;
-        if (q > 0) {
+        worst = std::max(worst, row.status);
+        if (row.accepted) {
             std::swap(d_cur, d_trial);
             ++accepted;
             max_step = pin[8];
-            const double t = 1.0 - pow(2.0 * (q / q1) - 1.0, 3.0);
-            u *= t < 1.0 / 3.0 ? 1.0 / 3.0 : t;
-            v = 2.0;
-            evaluate = true;
-            stop = q / C1 < o.rel_tol;
-        } else {
-            u *= v;
-            v *= 2.0;
-            evaluate = false;
         }
-        if (stop) break;
     }
+    const int32_t rows = (int32_t)tr.size();
     // ---- the result: the sums and the closures' weights at it, the poses in the caller's order
     pg_cost_kernel<<<egrid, 64, 0, s>>>(ed, d_cur, pd.part, pd.ticket, d_sc + 3, d_w);
     launch_export_poses(d_cur, bs.d_perm, N, d_io, s);

@@ -1,8 +1,8 @@
 // posegraph_device.h -- per-edge arithmetic of the pose-graph relaxation (lvba_posegraph_relax; pose_graph.hip; the problem and the
 // LM rule are in include/lvba_hip.h).  Also compiles as plain C++ (tests/posegraph_check.cpp).
 //   An edge is a prior of prior_device.h (RELATIVE: odometry steps and closures; POSE: the anchor) with the record layout of the
-//   prior tables (meas | oi | oj | L).  The residual, the Jacobians and the products of a lin record are prior_device.h's; what is
-//   added here is the odometry measurement Z0_i = X_i^-1 X_{i+1}, and the robust weight of a closure: with e = L r, s = |e|^2,
+//   prior tables (meas | oi | oj | L).  The residual, the whitened blocks (prior_eval) and the lin record (prior_record, layout
+//   PL_*) are prior_device.h's; what is added here is the odometry measurement Z0_i = X_i^-1 X_{i+1}, and the robust weight of a closure: with e = L r, s = |e|^2,
 //   an edge under a loss rho (visual_loss.h) costs 1/2 rho(s) and its J^T e and 6 x 6 products carry the factor rho'(s) -- applied
 //   as sqrt(rho') on e and on the whitened blocks before the products are formed (Ceres' corrector, scaling branch: the rho'' term
 //   is left out as everywhere in this project).
@@ -11,9 +11,6 @@
 #include "visual_loss.h"
 
 namespace lvba {
-
-// lin record offsets (PL_* of lvba_internal.h, restated for the host check, which cannot include HIP headers)
-enum { PG_GI = 1, PG_GJ = 7, PG_HII = 13, PG_HJJ = 49, PG_HX = 85, PG_LIN = 128 };
 
 // Z = X_i^-1 X_j (poses as R row-major | p)
 LVBA_HD void pg_relative(const double *Xi, const double *Xj, double *Z)
@@ -40,9 +37,8 @@ LVBA_PRIOR_UNROLL
 LVBA_HD double pg_edge_cost(int kind, const double *meas, const double *oi, const double *oj, const double *L, const double *Ti, const double *Tj,
                             int loss_kind, double loss_scale, double *weight)
 {
-    double r[6], e[6];
-    prior_raw(kind, meas, Ti, oi, Tj, oj, r, false, nullptr, nullptr);
-    const double half = prior_whiten(kind, L, r, e);
+    double e[6];
+    const double half = prior_eval(kind, meas, oi, oj, L, Ti, Tj, e, false, nullptr, nullptr);
     if (loss_kind == VLOSS_TRIVIAL) { *weight = 1.0; return half; }
     double rho[3];
     loss_eval(loss_kind, loss_scale, 2.0 * half, rho);
@@ -50,38 +46,30 @@ LVBA_HD double pg_edge_cost(int kind, const double *meas, const double *oi, cons
     return 0.5 * rho[0];
 }
 
-// The weighted lin record o [PG_LIN] of an edge (kind is a constant at each call site: every array stays in registers); returns the
-// cost, *weight = rho'
+// The weighted lin record o [PL_LIN] of an edge (kind is a constant at each call site: every array stays in registers); returns the
+// cost, *weight = rho'.  Between prior_eval and prior_record, e and the whitened blocks take the factor sqrt(rho').
 LVBA_HD double pg_edge_lin(const int kind, const double *meas, const double *oi, const double *oj, const double *L, const double *Ti,
                            const double *Tj, bool flip, int loss_kind, double loss_scale, double *o, double *weight)
 {
-    double r[6], Ji[36], Jj[36], e[6], Wi[36], Wj[36];
-    prior_raw(kind, meas, Ti, oi, Tj, oj, r, true, Ji, Jj);
-    double cost = prior_whiten(kind, L, r, e), sw = 1.0;
+    double e[6], Wi[36], Wj[36];
+    double cost = prior_eval(kind, meas, oi, oj, L, Ti, Tj, e, true, Wi, Wj);
     *weight = 1.0;
     if (loss_kind != VLOSS_TRIVIAL) {
         double rho[3];
         loss_eval(loss_kind, loss_scale, 2.0 * cost, rho);
         cost = 0.5 * rho[0];
         *weight = rho[1];
-        sw = sqrt(rho[1]);
+        const double sw = sqrt(rho[1]);
 LVBA_PRIOR_UNROLL
         for (int a = 0; a < 6; ++a) e[a] *= sw;
-    }
-    prior_whiten_jac(kind, L, Ji, Wi);
-    if (loss_kind != VLOSS_TRIVIAL) {
 LVBA_PRIOR_UNROLL
         for (int a = 0; a < 36; ++a) Wi[a] *= sw;
-    }
-    prior_products(Wi, e, o, PG_GI, PG_HII);
-    if (kind != PRIOR_RELATIVE) return cost;
-    prior_whiten_jac(kind, L, Jj, Wj);
-    if (loss_kind != VLOSS_TRIVIAL) {
+        if (kind == PRIOR_RELATIVE) {
 LVBA_PRIOR_UNROLL
-        for (int a = 0; a < 36; ++a) Wj[a] *= sw;
+            for (int a = 0; a < 36; ++a) Wj[a] *= sw;
+        }
     }
-    prior_products(Wj, e, o, PG_GJ, PG_HJJ);
-    prior_cross(Wi, Wj, flip, o, PG_HX);
+    prior_record(kind, e, Wi, Wj, flip, o);
     return cost;
 }
 

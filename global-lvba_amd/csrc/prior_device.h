@@ -7,10 +7,12 @@
 //     RELATIVE  r = [Log(Rm^T R_A^T R_B); R_A^T (p_B - p_A) - pm]          (6 rows)
 //   and adds 1/2 |L r|^2 to the cost.  prior_raw gives r and the Jacobian blocks dr/dd_i, dr/dd_j (row-major 6 x 6; POSITION:
 //   rows 3..5 zero); prior_whiten / prior_whiten_jac apply L.
-//   Shared with the visual stage's priors (visual_prior_device.h, visual_priors.hip): the model above, the products of a whitened
-//   block that a lin record keeps (prior_products, prior_cross) and, device only, the fixed-order grid sum (prior_grid_sum).
+//   One edge is prior_eval (e, 1/2 |e|^2, the whitened blocks) and then prior_record (the lin record PL_*): the LiDAR priors
+//   (priors.hip) and the pose graph's edges (posegraph_device.h: its loss scales in between).  The visual stage's priors
+//   (visual_prior_device.h, visual_priors.hip) share the model above, prior_record and, device only, prior_grid_sum.
 #pragma once
 #include <math.h>
+#include <stdint.h>
 
 #if defined(__HIPCC__)
 #define LVBA_HD __host__ __device__ __forceinline__
@@ -278,7 +280,11 @@ LVBA_PRIOR_UNROLL
         }
 }
 
-// The products of a whitened block W (row-major 6 x 6) that a lin record keeps (PL_* in lvba_internal.h):
+// lin record of an edge, PL_LIN doubles: [0] unused, [1..6] W_i^T e, [7..12] W_j^T e, [13..48] W_i^T W_i, [49..84] W_j^T W_j,
+// [85..120] cross block, 6 x 6 blocks in the store's element order (column-major: [c * 6 + r])
+enum { PL_GI = 1, PL_GJ = 7, PL_HII = 13, PL_HJJ = 49, PL_HX = 85, PL_LIN = 128 };
+
+// The products of a whitened block W (row-major 6 x 6) that a lin record keeps:
 // o[g0 + c] = (W^T e)(c), o[h0 + 6 c + r] = (W^T W)(r, c).  Every element is its own sum over a = 0..5, from 0.0.
 LVBA_HD void prior_products(const double *W, const double *e, double *o, int g0, int h0)
 {
@@ -313,6 +319,38 @@ LVBA_PRIOR_UNROLL
             for (int a = 0; a < 6; ++a) x += Wi[6 * a + r] * Wj[6 * a + c];
             o[x0 + (flip ? 6 * r + c : 6 * c + r)] = x;
         }
+}
+
+// T [12] = pose I of poses [n][12]
+LVBA_HD void prior_load_pose(const double *poses, int32_t I, double *T)
+{
+LVBA_PRIOR_UNROLL
+    for (int a = 0; a < 12; ++a) T[a] = poses[12 * (int64_t)I + a];
+}
+
+// One edge (record fields meas, oi, oj, L) at the poses Ti, Tj (Tj unused unless RELATIVE): e = L r (6; POSITION: e[3..5] = 0),
+// returns 1/2 |e|^2; if jac, Wi / Wj = L dr/dd_i, L dr/dd_j, row-major 6 x 6 (Wj: RELATIVE only).  (jac is a flag, not a test
+// of Wi against NULL, for prior_raw's reason.)
+LVBA_HD double prior_eval(int kind, const double *meas, const double *oi, const double *oj, const double *L, const double *Ti,
+                          const double *Tj, double *e, bool jac, double *Wi, double *Wj)
+{
+    double r[6], Ji[36], Jj[36];
+    prior_raw(kind, meas, Ti, oi, Tj, oj, r, jac, Ji, Jj);
+    const double cost = prior_whiten(kind, L, r, e);
+    if (jac) {
+        prior_whiten_jac(kind, L, Ji, Wi);
+        if (kind == PRIOR_RELATIVE) prior_whiten_jac(kind, L, Jj, Wj);
+    }
+    return cost;
+}
+
+// The lin record o [PL_LIN] of an edge from e and its whitened blocks (Wj, flip: RELATIVE only; no other kind writes the j ranges)
+LVBA_HD void prior_record(int kind, const double *e, const double *Wi, const double *Wj, bool flip, double *o)
+{
+    prior_products(Wi, e, o, PL_GI, PL_HII);
+    if (kind != PRIOR_RELATIVE) return;
+    prior_products(Wj, e, o, PL_GJ, PL_HJJ);
+    prior_cross(Wi, Wj, flip, o, PL_HX);
 }
 
 #if defined(__HIPCC__)

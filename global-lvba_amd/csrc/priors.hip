@@ -1,41 +1,30 @@
 // priors.hip -- the pose priors of the LiDAR bundle adjustment (lvba_balm_set_priors; the model is in prior_device.h).
-//   prior_lin_kernel      one lane per prior: e = L r and the whitened Jacobian blocks at the solver-order poses; writes per prior
+//   prior_lin_kernel      one lane per prior: e = L r and the whitened Jacobian blocks at the solver-order poses (prior_eval), and
+//                         their lin record (prior_record), both of prior_device.h; writes per prior
 //                         J_i^T e, J_j^T e and the 6 x 6 products J_i^T J_i, J_j^T J_j, J_i^T J_j (the last oriented for the lower
 //                         block store: transposed when the solver puts i before j), and adds the prior cost to the evaluation's
 //   prior_scatter_kernel  every target element of the block store and of g sums its contributions in the fixed order of a CSR table
 //                         built on the host.  No atomics on data: the bytes do not change run to run.
-//   prior_cost_kernel     the cost alone (the LM's trial point), one lane per prior, summed like the evaluation's
+//   prior_cost_kernel     the cost alone (the LM's trial point; prior_eval without Jacobians), one lane per prior, summed like
+//                         the evaluation's
 // Both sums run in the fixed order of prior_grid_sum (prior_device.h).
 // An evaluation is 2 launches, a trial cost 1; a handle without priors launches none of them.
 #include <hip/hip_runtime.h>
 
 #include "lvba_internal.h"
-#include "prior_device.h"
 
 namespace lvba {
 
 #define PRIOR_WG 256
 
-// (the lin record of prior k: PL_* in lvba_internal.h)
-
-// (kind is a constant at each call site: every array stays in registers)
+// prior k's lin record (PL_*), returns its cost.  (kind is a constant at each call site: every array stays in registers)
 __device__ __forceinline__ double prior_lin_one(const int kind, const PriorRec &p, const double *__restrict__ poses, double *__restrict__ o)
 {
-    double Ti[12], Tj[12], r[6], Ji[36], Jj[36], e[6], Wi[36], Wj[36];
-#pragma unroll
-    for (int a = 0; a < 12; ++a) Ti[a] = poses[12 * (int64_t)p.I + a];
-    if (kind == PRIOR_RELATIVE) {
-#pragma unroll
-        for (int a = 0; a < 12; ++a) Tj[a] = poses[12 * (int64_t)p.J + a];
-    }
-    prior_raw(kind, p.meas, Ti, p.oi, Tj, p.oj, r, true, Ji, Jj);
-    const double cost = prior_whiten(kind, p.L, r, e);
-    prior_whiten_jac(kind, p.L, Ji, Wi);
-    prior_products(Wi, e, o, PL_GI, PL_HII);
-    if (kind != PRIOR_RELATIVE) return cost;
-    prior_whiten_jac(kind, p.L, Jj, Wj);
-    prior_products(Wj, e, o, PL_GJ, PL_HJJ);
-    prior_cross(Wi, Wj, p.flip, o, PL_HX);
+    double Ti[12], Tj[12], e[6], Wi[36], Wj[36];
+    prior_load_pose(poses, p.I, Ti);
+    if (kind == PRIOR_RELATIVE) prior_load_pose(poses, p.J, Tj);
+    const double cost = prior_eval(kind, p.meas, p.oi, p.oj, p.L, Ti, Tj, e, true, Wi, Wj);
+    prior_record(kind, e, Wi, Wj, p.flip, o);
     return cost;
 }
 
@@ -47,7 +36,7 @@ __global__ __launch_bounds__(64) void prior_lin_kernel(const PriorRec *__restric
     double c = 0.0;
     if (k < n) {
         const PriorRec &p = pr[k];
-        double *o = lin + 128 * (int64_t)k;
+        double *o = lin + PL_LIN * (int64_t)k;
         if (p.kind == PRIOR_POSE) c = prior_lin_one(PRIOR_POSE, p, poses, o);
         else if (p.kind == PRIOR_POSITION) c = prior_lin_one(PRIOR_POSITION, p, poses, o);
         else c = prior_lin_one(PRIOR_RELATIVE, p, poses, o);
@@ -63,15 +52,10 @@ __global__ __launch_bounds__(64) void prior_cost_kernel(const PriorRec *__restri
     double c = 0.0;
     if (k < n) {
         const PriorRec &p = pr[k];
-        double Ti[12], Tj[12], r[6], e[6];
-LVBA_PRIOR_UNROLL
-        for (int a = 0; a < 12; ++a) Ti[a] = poses[12 * (int64_t)p.I + a];
-        if (p.kind == PRIOR_RELATIVE) {
-LVBA_PRIOR_UNROLL
-            for (int a = 0; a < 12; ++a) Tj[a] = poses[12 * (int64_t)p.J + a];
-        }
-        prior_raw(p.kind, p.meas, Ti, p.oi, Tj, p.oj, r, false, nullptr, nullptr);
-        c = prior_whiten(p.kind, p.L, r, e);
+        double Ti[12], Tj[12], e[6];
+        prior_load_pose(poses, p.I, Ti);
+        if (p.kind == PRIOR_RELATIVE) prior_load_pose(poses, p.J, Tj);
+        c = prior_eval(p.kind, p.meas, p.oi, p.oj, p.L, Ti, Tj, e, false, nullptr, nullptr);
         if (e_out) {
 LVBA_PRIOR_UNROLL
             for (int a = 0; a < 6; ++a) e_out[6 * (int64_t)k + a] = e[a];
@@ -92,7 +76,7 @@ __global__ __launch_bounds__(PRIOR_WG) void prior_scatter_kernel(PriorDev d, dou
         double s = (mode & 1) ? 0.0 : *dst;
         for (int32_t q = d.hoff[b]; q < d.hoff[b + 1]; ++q) {
             const int32_t src = d.hsrc[q], k = src >> 2, piece = src & 3;
-            s += d.lin[128 * (int64_t)k + (piece == 0 ? PL_HII : piece == 1 ? PL_HJJ : PL_HX) + el];
+            s += d.lin[PL_LIN * (int64_t)k + (piece == 0 ? PL_HII : piece == 1 ? PL_HJJ : PL_HX) + el];
         }
         *dst = s;
         return;
@@ -105,7 +89,7 @@ __global__ __launch_bounds__(PRIOR_WG) void prior_scatter_kernel(PriorDev d, dou
     double s = *dst;
     for (int32_t q = d.goff[b]; q < d.goff[b + 1]; ++q) {
         const int32_t src = d.gsrc[q], k = src >> 2, piece = src & 3;
-        s += d.lin[128 * (int64_t)k + (piece == 0 ? PL_GI : PL_GJ) + el];
+        s += d.lin[PL_LIN * (int64_t)k + (piece == 0 ? PL_GI : PL_GJ) + el];
     }
     *dst = s;
 }

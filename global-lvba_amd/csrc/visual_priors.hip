@@ -2,8 +2,9 @@
 // visual_prior_device.h).  A prior is one more residual block on one or two cameras, outside the losses:
 //   vprior_lin_kernel     one lane per prior: e = L r and the whitened Jacobian blocks W_i, W_j in the visual tangent at the
 //                         solver-order cameras, columns scaled by the Jacobi scaling (or not: iteration 0, which derives it);
-//                         writes the LiDAR stage's lin record -- W_i^T e, W_j^T e, W_i^T W_i, W_j^T W_j, the cross block oriented
-//                         for the lower block store; the diagonals of the two squares are the squared column norms -- and
+//                         writes the LiDAR stage's lin record (prior_record, prior_device.h) -- W_i^T e, W_j^T e, W_i^T W_i,
+//                         W_j^T W_j, the cross block oriented for the lower block store; the diagonals of the two squares are the
+//                         squared column norms -- and
 //                         adds sum |e|^2 to the evaluation's.  The constant camera's columns are zero.
 //   prior_scatter_kernel  (priors.hip, shared) the records into the block store and the reduced right-hand side
 //   vprior_cam_kernel     the records into the per-camera sums the LM diagonal, the gradient max and the Jacobi scaling are
@@ -41,16 +42,15 @@ __device__ __forceinline__ double vprior_lin_one(const int kind, const PriorRec 
     vprior_load_cam(qc, tc, p.I, qi, ti);
     vprior_load_cam(qc, tc, kind == PRIOR_RELATIVE ? p.J : p.I, qj, tj);
     const double c2 = 2.0 * vprior_eval(kind, p.meas, p.oi, p.oj, p.L, qi, ti, qj, tj, e, true, Wi, Wj);
+    if (kind == PRIOR_RELATIVE) { // (j before i: the order that needs the fewest registers)
+        vprior_scales(sc_cam, p.J, fixed_cam, sc);
+#pragma unroll
+        for (int a = 0; a < 36; ++a) Wj[a] *= sc[a % 6];
+    }
     vprior_scales(sc_cam, p.I, fixed_cam, sc);
 #pragma unroll
     for (int a = 0; a < 36; ++a) Wi[a] *= sc[a % 6];
-    prior_products(Wi, e, o, PL_GI, PL_HII);
-    if (kind != PRIOR_RELATIVE) return c2;
-    vprior_scales(sc_cam, p.J, fixed_cam, sc);
-#pragma unroll
-    for (int a = 0; a < 36; ++a) Wj[a] *= sc[a % 6];
-    prior_products(Wj, e, o, PL_GJ, PL_HJJ);
-    prior_cross(Wi, Wj, p.flip, o, PL_HX);
+    prior_record(kind, e, Wi, Wj, p.flip, o);
     return c2;
 }
 
@@ -63,7 +63,7 @@ __global__ __launch_bounds__(64) void vprior_lin_kernel(const PriorRec *__restri
     double c2 = 0.0;
     if (k < n) {
         const PriorRec &p = pr[k];
-        double *o = lin + 128 * (int64_t)k;
+        double *o = lin + PL_LIN * (int64_t)k;
         if (p.kind == PRIOR_POSE) c2 = vprior_lin_one(PRIOR_POSE, p, fixed_cam, qc, tc, sc_cam, o);
         else if (p.kind == PRIOR_POSITION) c2 = vprior_lin_one(PRIOR_POSITION, p, fixed_cam, qc, tc, sc_cam, o);
         else c2 = vprior_lin_one(PRIOR_RELATIVE, p, fixed_cam, qc, tc, sc_cam, o);
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(256) void vprior_cam_kernel(PriorDev d, double *__r
     double sd = diag[dst], sg = grad ? grad[dst] : 0.0;
     for (int32_t q = d.goff[b]; q < d.goff[b + 1]; ++q) {
         const int32_t src = d.gsrc[q], k = src >> 2, piece = src & 3;
-        const double *o = d.lin + 128 * (int64_t)k;
+        const double *o = d.lin + PL_LIN * (int64_t)k;
         sd += o[(piece == 0 ? PL_HII : PL_HJJ) + 7 * el];
         sg += o[(piece == 0 ? PL_GI : PL_GJ) + el];
     }

@@ -16,7 +16,7 @@ void pgc_odometry(const double *Xi, const double *Xj, double sigma_rot, double s
 // lin [128], out [2] = cost | weight
 void pgc_lin(int kind, const double *rec, const double *Ti, const double *Tj, int flip, int loss_kind, double loss_scale, double *lin, double *out)
 {
-    for (int a = 0; a < PG_LIN; ++a) lin[a] = 0.0;
+    for (int a = 0; a < PL_LIN; ++a) lin[a] = 0.0;
     if (kind == PRIOR_POSE) out[0] = pg_edge_lin(PRIOR_POSE, rec, rec + 12, rec + 24, rec + 36, Ti, Tj, flip != 0, loss_kind, loss_scale, lin, out + 1);
     else out[0] = pg_edge_lin(PRIOR_RELATIVE, rec, rec + 12, rec + 24, rec + 36, Ti, Tj, flip != 0, loss_kind, loss_scale, lin, out + 1);
 }

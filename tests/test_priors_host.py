@@ -82,10 +82,10 @@ def _checker(tmp_path):
     return exe
 
 
-def test_device_header_agrees_with_the_oracle(tmp_path):
-    """csrc/prior_device.h (host build) vs the numpy model: residual, whitened residual, whitened Jacobians and cost agree to a
-    few ulp of each quantity's scale (the two sum the same products in different orders)."""
-    exe = _checker(tmp_path)
+@pytest.fixture(scope="module")
+def checked(tmp_path_factory):
+    """[(prior, poses, the checker's output line as doubles)] of the cases, four draws each"""
+    exe = _checker(tmp_path_factory.mktemp("prior_check"))
     rng = np.random.default_rng(11)
     lines, cases = [], []
     for kind, off, reg in CASES * 4:
@@ -94,16 +94,56 @@ def test_device_header_agrees_with_the_oracle(tmp_path):
         vals = np.r_[x[0], x[1], pr["oi"], pr["oj"], pr["meas"], pr["L"].reshape(-1)]
         lines.append(f"{pr['kind']} " + " ".join(float(v).hex() for v in vals))
     out = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, check=True).stdout.split("\n")
+    got = [(pr, x, np.array([float.fromhex(t) for t in ln.split()])) for (pr, x), ln in zip(cases, out)]
+    assert len(got) == len(cases) and all(v.size == 6 + 6 + 36 + 36 + 1 + 2 * 128 for _, _, v in got)
+    return got
+
+
+def test_device_header_agrees_with_the_oracle(checked):
+    """csrc/prior_device.h (host build) vs the numpy model: residual, whitened residual, whitened Jacobians and cost agree to a
+    few ulp of each quantity's scale (the two sum the same products in different orders)."""
     eps = np.finfo(np.float64).eps
-    for (pr, x), ln in zip(cases, out):
-        v = np.array([float.fromhex(t) for t in ln.split()])
-        assert v.size == 6 + 6 + 36 + 36 + 1
+    for pr, x, v in checked:
         r, Ji, Jj = po.raw(pr, x[0], x[1])
         e, Wi, Wj = po.whiten(pr, r, Ji, Jj)
         for got, ref in ((v[:6], r), (v[6:12], e), (v[12:48], Wi.reshape(-1)), (v[48:84], Wj.reshape(-1)), (v[84:85], [0.5 * e @ e])):
             ref = np.asarray(ref)
             scale = max(np.abs(ref).max(), 1e-300)
             assert np.abs(got - ref).max() <= 64 * eps * scale, (pr["kind"], got - ref)
+
+
+def _close(a, b, what):
+    """tests/test_posegraph_host.py's tolerance for a lin record against its oracle"""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    scale = max(1.0, float(np.abs(b).max(initial=0.0)))
+    assert np.abs(a - b).max(initial=0.0) <= 1e-12 * scale, what
+
+
+def test_lin_record_holds_the_products_of_the_whitened_blocks(checked):
+    """prior_eval + prior_record (what prior_lin_kernel runs per prior), all three kinds: the record's W^T e and W^T W against numpy's
+    from the same program's e, W_i, W_j, the cross block in both orientations; what a POSE / POSITION record does not own -- the
+    j ranges, the cross block -- and the unused slots keep the sentinel the checker pre-filled."""
+    SENTINEL = -777.0
+    seen = set()
+    for pr, x, v in checked:
+        e, Wi, Wj = v[6:12], v[12:48].reshape(6, 6), v[48:84].reshape(6, 6)
+        seen.add(pr["kind"])
+        for flip in (0, 1):
+            o = v[85 + 128 * flip:85 + 128 * (flip + 1)]
+            what = (pr["kind"], flip)
+            _close(o[1:7], Wi.T @ e, what)
+            _close(o[13:49].reshape(6, 6).T, Wi.T @ Wi, what)
+            assert o[0] == SENTINEL and (o[121:] == SENTINEL).all(), what
+            if pr["kind"] == po.KINDS["relative"]:
+                _close(o[7:13], Wj.T @ e, what)
+                _close(o[49:85].reshape(6, 6).T, Wj.T @ Wj, what)
+                X = Wi.T @ Wj
+                _close(o[85:121].reshape(6, 6).T, X.T if flip else X, what)
+            else:
+                assert (o[7:13] == SENTINEL).all() and (o[49:121] == SENTINEL).all(), what
+        if pr["kind"] == po.KINDS["position"]:          # rows 3..5 of a POSITION block are zero: nothing of L beyond 3 x 3 enters
+            assert not Wi[3:].any() and not e[3:].any()
+    assert seen == set(po.KINDS.values())
 
 
 def test_prior_struct_and_kinds_match_the_c_header(pkg, tmp_path):
