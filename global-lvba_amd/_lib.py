@@ -36,7 +36,7 @@ SYMBOLS = [
     "lvba_closure_default_opts", "lvba_closure_consistency",
     "lvba_posegraph_default_opts", "lvba_posegraph_relax",
     "lvba_match_default_opts", "lvba_match_create", "lvba_match_destroy", "lvba_match_set_geometry", "lvba_match_pairs",
-    "lvba_match_scan",
+    "lvba_match_scan", "lvba_match_set_depth", "lvba_match_points",
 ]
 
 OK, ERR_ARG, ERR_DEVICE, ERR_NOMEM, ERR_UNSUPPORTED, ERR_DIST, ERR_STATE = 0, -1, -2, -3, -4, -5, -6
@@ -210,7 +210,7 @@ class ClosureOpts(C.Structure):
 class MatchOpts(C.Structure):
     """lvba_match_opts"""
     _fields_ = [("max_distance", C.c_double), ("max_ratio", C.c_double), ("mutual", C.c_int32), ("guided", C.c_int32),
-                ("max_epipolar_px", C.c_double)]
+                ("max_epipolar_px", C.c_double), ("max_reproj_px", C.c_double)]
 
 
 class VoxelOpts(C.Structure):
@@ -438,6 +438,8 @@ def load():
     lib.lvba_match_pairs.argtypes = [H, C.c_int64, C.c_void_p, C.POINTER(MatchOpts), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p]
     lib.lvba_match_scan.argtypes = [H, C.c_int32, C.c_int32, C.POINTER(MatchOpts), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.lvba_match_set_depth.argtypes = [H, C.c_void_p]
+    lib.lvba_match_points.argtypes = [H, C.c_void_p]
     lib.lvba_scans_info.argtypes = [H, C.POINTER(C.c_int32), C.c_void_p]
     lib.lvba_scans_download.argtypes = [H, C.c_int32, np.ctypeslib.ndpointer(np.float32, flags="C")]
     for name in SYMBOLS:

@@ -18,7 +18,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-ato
 # Kernels that take DISCRETE decisions on floating-point values (voxel keys, pixel indices, depth / angle / reprojection
 # thresholds, fp32 write-backs, neighbourhood membership: the depth renderer, the colouriser, the track fusion, the triangulation, the anchor
 # merge and down-sampling, the map-quality metrics, the registration's inlier gate, the loop-closure candidates' radius gate, the scan descriptors' bins,
-# the place search's orderings, the closure consistency's two clauses and the descriptor matcher's epipolar gate)
+# the place search's orderings, the closure consistency's two clauses and the descriptor matcher's epipolar and depth gates)
 # must round like the reference's plain x86-64 build, expression by expression: no contraction of a*b+c into FMAs there.
 # The LM kernels (smooth arithmetic, compared at 1e-8) keep the FMAs.
 NO_CONTRACT = {"fusion.hip", "tracks.hip", "window_ba.hip", "colorize.hip", "map_quality.hip", "register.hip", "loop_candidates.hip", "place.hip", "closures.hip", "match.hip"}

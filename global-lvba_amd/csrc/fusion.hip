@@ -33,12 +33,6 @@
 
 using namespace lvba;
 
-struct lvba_depth_s {
-    int device = 0;
-    int n_images = 0, width = 0, height = 0;
-    float *d_depth = nullptr; // [n_images][height][width], 0 = no return
-};
-
 namespace {
 
 __global__ void gm_world_kernel(int64_t P, const float *__restrict__ pts, const int64_t *__restrict__ frame_off, int n_frames,

@@ -32,6 +32,27 @@ LVBA_TRK_FN bool fetch_depth_bilinear(const float *__restrict__ depth, int w, in
     return d > 0.0f;
 }
 
+// The world point of a pixel with a depth return: fetch_depth_bilinear at (u, v), X^c = (x d, y d, d) with (x, y) the pixel's
+// undistorted normalised point (trk_undistort; NaN where it failed), then camToWorld (utils.hpp:277-284): Rwc Xc + twc with
+// twc = -(Rwc tcw), (R, tc) = T_cam<-world of the image.  Every sum left to right.  false (p untouched): no depth at the pixel, a
+// non-finite pixel or undistorted point, or a non-finite camera-frame point.  Shared by fuse_track and the descriptor matcher's
+// depth gate (match.hip).
+LVBA_TRK_FN bool depth_world_point(const float *__restrict__ depth, int w, int h, float u, float v, double x, double y,
+                                   const double *__restrict__ R, const double *__restrict__ tc, double *__restrict__ p)
+{
+    if (!(isfinite(u) && isfinite(v))) return false; // a NaN pixel passes every comparison of the fetch's range check
+    float d;
+    if (!fetch_depth_bilinear(depth, w, h, u, v, d)) return false;
+    const double dd = (double)d;
+    const double Xc[3] = {x * dd, y * dd, dd};
+    if (!(isfinite(Xc[0]) && isfinite(Xc[1]) && isfinite(Xc[2]))) return false;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const double twc = -(R[r] * tc[0] + R[3 + r] * tc[1] + R[6 + r] * tc[2]);
+        p[r] = (R[r] * Xc[0] + R[3 + r] * Xc[1] + R[6 + r] * Xc[2]) + twc;
+    }
+    return true;
+}
 
 // The greedy view-angle filter of :1052-1080 / :1124-1150 over the observations base + ord[i], i < m, in that order: an
 // observation is kept when its ray makes at least the minimum angle with one ray already kept (or is the first).  point: the
@@ -125,21 +146,11 @@ LVBA_TRK_FN void fuse_track(int64_t t, const int64_t *__restrict__ obs_off, cons
             const int32_t im = obs_img[o];
             if (im < 0 || im >= n_images) continue;
             const float u = obs_uv[2 * o], v = obs_uv[2 * o + 1];
-            float d;
-            if (!fetch_depth_bilinear(depth + (int64_t)im * width * height, width, height, u, v, d)) continue;
             double x, y;
             if (!trk_undistort(cam, (double)u, (double)v, x, y)) continue;
-            const double dd = (double)d;
-            const double Xc[3] = {x * dd, y * dd, dd};
-            if (!(isfinite(Xc[0]) && isfinite(Xc[1]) && isfinite(Xc[2]))) continue;
-            const double *R = Rcw + 9 * (int64_t)im, *tc = tcw + 3 * (int64_t)im;
-            // camToWorld (utils.hpp:277-284): Rwc Xc + twc with twc = -(Rwc tcw)
-            double *p = pts + 3 * o;
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                const double twc = -(R[r] * tc[0] + R[3 + r] * tc[1] + R[6 + r] * tc[2]);
-                p[r] = (R[r] * Xc[0] + R[3 + r] * Xc[1] + R[6 + r] * Xc[2]) + twc;
-            }
+            if (!depth_world_point(depth + (int64_t)im * width * height, width, height, u, v, x, y, Rcw + 9 * (int64_t)im,
+                                   tcw + 3 * (int64_t)im, pts + 3 * o))
+                continue;
             flag[o] |= 2;
             if (first_valid < 0) first_valid = o;
             ++n_valid;

@@ -1,8 +1,14 @@
-// match.hip -- descriptor matching of image pairs with an optional pose-guided epipolar gate (lvba_match_*; the rule is in
-// include/lvba_hip.h, its scalar pieces in match_device.h).
+// match.hip -- descriptor matching of image pairs with an optional pose-guided gate, on the epipolar line or at the point a LiDAR
+// depth image predicts (lvba_match_*; the rule is in include/lvba_hip.h, its scalar pieces in match_device.h).
 //
 // Device design:
 //   match_undistort_kernel  a thread per keypoint: trk_undistort once per lvba_match_set_geometry, NaN where it fails.
+//   match_lift_kernel       a thread per keypoint: its 3-D point through the depth image, once per lvba_match_set_depth, NaN where
+//                           it has none.
+//   match_predict_kernel    depth gate only, before the scan: a thread per (ordered pair, keypoint of its first image) projects the
+//                           keypoint's point into the second image -- for both orientations of every pair of the grid, since the scan
+//                           of (a, b) needs a's keypoints in b for its rows and b's in a for its columns.  NaN: no point; +inf: the
+//                           point does not project.
 //   match_scan_kernel       the top two of every row of an ordered pair (a, b), for a whole list of ordered pairs in one grid.  A
 //                           workgroup is four wavefronts, each with 32 rows of image a; its A fragments of all four k-steps stay in
 //                           registers.  Column tiles of 32 descriptors of b stream through v_mfma_i32_32x32x32_i8; the accumulator
@@ -12,7 +18,8 @@
 //                           so a strict > keeps the lowest column of a tie -- and the 32 lanes of a row merge once at the end.  The
 //                           n_a x n_b scores never leave the registers.  Under the gate a lane holds the epipolar line (or the
 //                           point) of its 16 rows from the prologue on, computes its column's once per tile, and a candidate that
-//                           fails is replaced by "none" before the update.
+//                           fails is replaced by "none" before the update.  Under the depth gate it holds each row's pixel and
+//                           prediction instead and loads its column's pixel and prediction once per tile.
 //   match_decide_kernel     a thread per forward row: the fp64 acos clauses and the mutual clause -> a flag.
 //   match_write_kernel      after an exclusive prefix sum of the flags: the matches in (pair, row) order, and match_off.
 // The byte k of a descriptor that a lane feeds into a k-step is the same for the A and the B operand (bytes 64 h + 16 ks .. + 15 of
@@ -38,8 +45,11 @@ struct lvba_match_s {
     std::vector<int64_t> off;      // [n_images + 1]
     uint8_t *d_desc = nullptr;     // [total][128], top bit flipped: a' = a - 128 as a signed byte
     int32_t *d_bias = nullptr;     // [total] 128 sum a'
+    float *d_uv = nullptr;         // [total][2] the keypoints' pixels
     double *d_xy = nullptr;        // [total][2] undistorted normalised keypoints, NaN where the undistortion fails
-    bool has_geometry = false;
+    double *d_pts = nullptr;       // [total][3] the keypoints' points through the depth images, NaN rows where there is none
+    bool has_geometry = false, has_points = false;
+    TrkIntr cam{};
     std::vector<double> R, t;      // [n_images][9], [n_images][3]
     double focal_sum = 0.0;        // fx + fy
 };
@@ -58,7 +68,16 @@ struct MatchTask {
     int64_t a_off, b_off, out_off;  // first descriptor of a and of b, first result row
     int32_t n_a, n_b;
     int32_t rows_lo, pad;           // 1: image a is the "lo" image of the gate
-    double E[9];                    // lo -> hi
+    union {
+        double E[9];                // epipolar gate: lo -> hi
+        struct { int64_t rows, cols; } pred; // depth gate: the first prediction of a's keypoints in b and of b's in a
+    };
+};
+
+// keypoints [src_off, src_off + n) (one image) projected into the image with pose (R, t); predictions [first, first + n)
+struct MatchPredJob {
+    int64_t src_off, first;
+    double R[9], t[3];
 };
 
 __global__ __launch_bounds__(256) void match_undistort_kernel(int64_t n, const float *__restrict__ uv, const TrkIntr cam, double *__restrict__ xy)
@@ -68,6 +87,39 @@ __global__ __launch_bounds__(256) void match_undistort_kernel(int64_t n, const f
     double x, y;
     if (!trk_undistort(cam, (double)uv[2 * i], (double)uv[2 * i + 1], x, y)) x = y = NAN;
     xy[2 * i] = x; xy[2 * i + 1] = y;
+}
+
+// world [n][3]; img_off [n_images + 1] = the matcher's desc_off
+__global__ __launch_bounds__(256) void match_lift_kernel(int64_t n, int n_images, const int64_t *__restrict__ img_off,
+                                                         const float *__restrict__ uv, const double *__restrict__ xy,
+                                                         const float *__restrict__ depth, int width, int height,
+                                                         const double *__restrict__ Rcw, const double *__restrict__ tcw,
+                                                         double *__restrict__ world)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    int lo = 0, hi = n_images; // the last image with img_off <= i (empty images share an offset with their successor)
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (img_off[mid] <= i) lo = mid; else hi = mid;
+    }
+    match_lift(depth + (int64_t)lo * width * height, width, height, uv[2 * i], uv[2 * i + 1], xy[2 * i], xy[2 * i + 1], Rcw + 9 * (int64_t)lo,
+               tcw + 3 * (int64_t)lo, world + 3 * i);
+}
+
+// pred [n][2]; jobs by ascending `first`, none empty
+__global__ __launch_bounds__(256) void match_predict_kernel(int64_t n, int n_jobs, const MatchPredJob *__restrict__ jobs, const TrkIntr cam,
+                                                            const double *__restrict__ world, double *__restrict__ pred)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    int lo = 0, hi = n_jobs; // the last job with first <= i
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (jobs[mid].first <= i) lo = mid; else hi = mid;
+    }
+    const MatchPredJob &j = jobs[lo];
+    match_predict(cam, j.R, j.t, world + 3 * (j.src_off + (i - j.first)), pred[2 * i], pred[2 * i + 1]);
 }
 
 // row of accumulator register i in lane half h (the C/D map of the 32x32 shapes)
@@ -89,13 +141,16 @@ __device__ __forceinline__ void gate_tile(v16i &acc, const MatchLine (&P)[16], c
     }
 }
 
-// tiles [n_tiles] = (task, first row); best, s1, s2 [rows of all tasks]
-template <bool GUIDED>
+// tiles [n_tiles] = (task, first row); best, s1, s2 [rows of all tasks]; tau2: the gate's squared bound (rho^2 under the depth gate);
+// uv, pred: the keypoints' pixels and the grid's predictions (depth gate only)
+template <int MODE>
 __global__ __launch_bounds__(SCAN_BLOCK) void match_scan_kernel(const MatchTask *__restrict__ tasks, const int2 *__restrict__ tiles,
                                                                 const uint8_t *__restrict__ desc, const int32_t *__restrict__ bias,
                                                                 const double *__restrict__ xy, double tau2, int32_t *__restrict__ best,
-                                                                int32_t *__restrict__ s1, int32_t *__restrict__ s2)
+                                                                int32_t *__restrict__ s1, int32_t *__restrict__ s2,
+                                                                const float *__restrict__ uv, const double *__restrict__ pred)
 {
+    constexpr bool GUIDED = MODE == MATCH_EPIPOLAR;
     const int2 tl = tiles[blockIdx.x];
     const MatchTask &t = tasks[tl.x];
     const int lane = threadIdx.x & 63, cl = lane & 31, h = lane >> 5;
@@ -121,6 +176,15 @@ __global__ __launch_bounds__(SCAN_BLOCK) void match_scan_kernel(const MatchTask 
             const double x = xy[2 * (t.a_off + r)], y = xy[2 * (t.a_off + r) + 1];
             if (rows_lo) P[i] = match_line_lo(E, x, y);
             else { MatchLine m; m.l0 = x; m.l1 = y; m.l2 = 0.0; m.n = match_norm_hi(E, x, y); P[i] = m; }
+        }
+    }
+    MatchReproj Q[MODE == MATCH_DEPTH ? 16 : 1];
+    if constexpr (MODE == MATCH_DEPTH) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int r = min(row0 + acc_row(i, h), n_a - 1);
+            Q[i].u = (double)uv[2 * (t.a_off + r)]; Q[i].v = (double)uv[2 * (t.a_off + r) + 1];
+            Q[i].pu = pred[2 * (t.pred.rows + r)]; Q[i].pv = pred[2 * (t.pred.rows + r) + 1];
         }
     }
     MatchTop top[16];
@@ -160,6 +224,14 @@ __global__ __launch_bounds__(SCAN_BLOCK) void match_scan_kernel(const MatchTask 
             const double cx = xy[2 * cb], cy = xy[2 * cb + 1];
             if (rows_lo) gate_tile<true>(acc, P, E, cx, cy, tau2);
             else gate_tile<false>(acc, P, E, cx, cy, tau2);
+        }
+        if constexpr (MODE == MATCH_DEPTH) {
+            const int64_t pc = t.pred.cols + min(col, n_b - 1);
+            MatchReproj c;
+            c.u = (double)uv[2 * cb]; c.v = (double)uv[2 * cb + 1]; c.pu = pred[2 * pc]; c.pv = pred[2 * pc + 1];
+#pragma unroll
+            for (int i = 0; i < 16; ++i)
+                if (!match_depth_gate(Q[i], c, tau2)) acc[i] = MATCH_NONE;
         }
         if (c0 + 32 > n_b) { // the last, partial tile: the clamped columns are nobody's
             const bool live = col < n_b;
@@ -243,11 +315,12 @@ int32_t check_opts(const lvba_match_opts *opts, lvba_match_opts &o)
     lvba_match_default_opts(&o);
     if (opts) o = *opts;
     const bool ok = std::isfinite(o.max_distance) && o.max_distance > 0.0 && std::isfinite(o.max_ratio) && o.max_ratio > 0.0 &&
-                    o.max_ratio <= 1.0 && (o.mutual == 0 || o.mutual == 1) && (o.guided == 0 || o.guided == 1) &&
-                    std::isfinite(o.max_epipolar_px) && o.max_epipolar_px > 0.0;
+                    o.max_ratio <= 1.0 && (o.mutual == 0 || o.mutual == 1) && o.guided >= MATCH_UNGUIDED && o.guided <= MATCH_DEPTH &&
+                    std::isfinite(o.max_epipolar_px) && o.max_epipolar_px > 0.0 && std::isfinite(o.max_reproj_px) && o.max_reproj_px > 0.0;
     if (!ok)
-        return lvba_fail(LVBA_ERR_ARG, "options: max_distance %g (finite, > 0), max_ratio %g (in (0, 1]), mutual %d (0 or 1), guided %d (0 or "
-                         "1), max_epipolar_px %g (finite, > 0)", o.max_distance, o.max_ratio, o.mutual, o.guided, o.max_epipolar_px);
+        return lvba_fail(LVBA_ERR_ARG, "options: max_distance %g (finite, > 0), max_ratio %g (in (0, 1]), mutual %d (0 or 1), guided %d (0, 1 "
+                         "or 2), max_epipolar_px %g (finite, > 0), max_reproj_px %g (finite, > 0)", o.max_distance, o.max_ratio, o.mutual,
+                         o.guided, o.max_epipolar_px, o.max_reproj_px);
     return LVBA_OK;
 }
 
@@ -255,21 +328,43 @@ int32_t check_pair(const lvba_match_s *m, int64_t a, int64_t b, const lvba_match
 {
     if (a < 0 || a >= m->n_images || b < 0 || b >= m->n_images || a == b)
         return lvba_fail(LVBA_ERR_ARG, "pair (%lld, %lld) of %d images (two different images)", (long long)a, (long long)b, m->n_images);
+    if (o.guided == MATCH_DEPTH && !m->has_points)
+        return lvba_fail(LVBA_ERR_ARG, "depth-guided matching (guided = 2) needs lvba_match_set_geometry and then lvba_match_set_depth first");
     if (o.guided && !m->has_geometry) return lvba_fail(LVBA_ERR_ARG, "guided matching needs lvba_match_set_geometry first");
     return LVBA_OK;
 }
 
-MatchTask make_task(const lvba_match_s *m, int a, int b, int64_t out_off, bool guided)
+// pred_rows / pred_cols: depth gate only, where the predictions of a's keypoints in b and of b's in a stand (predict_jobs)
+MatchTask make_task(const lvba_match_s *m, int a, int b, int64_t out_off, int guided, int64_t pred_rows = 0, int64_t pred_cols = 0)
 {
     MatchTask t{};
     t.a_off = m->off[a]; t.b_off = m->off[b]; t.out_off = out_off;
     t.n_a = (int32_t)(m->off[a + 1] - m->off[a]); t.n_b = (int32_t)(m->off[b + 1] - m->off[b]);
     t.rows_lo = a < b ? 1 : 0;
-    if (guided) {
+    if (guided == MATCH_EPIPOLAR) {
         const int lo = std::min(a, b), hi = std::max(a, b);
         match_essential(&m->R[9 * (size_t)lo], &m->t[3 * (size_t)lo], &m->R[9 * (size_t)hi], &m->t[3 * (size_t)hi], t.E);
+    } else if (guided == MATCH_DEPTH) {
+        t.pred.rows = pred_rows; t.pred.cols = pred_cols;
     }
     return t;
+}
+
+// The prediction jobs of the unordered pair {a, b}, both orientations: a's keypoints in b at `first`, b's in a behind them.
+// Returns the position behind both.
+int64_t predict_jobs(const lvba_match_s *m, int a, int b, int64_t first, std::vector<MatchPredJob> &jobs)
+{
+    const int src[2] = {a, b}, dst[2] = {b, a};
+    for (int k = 0; k < 2; ++k) {
+        const int64_t n = m->off[src[k] + 1] - m->off[src[k]];
+        if (n == 0) continue;
+        MatchPredJob j{};
+        j.src_off = m->off[src[k]]; j.first = first;
+        std::copy_n(&m->R[9 * (size_t)dst[k]], 9, j.R); std::copy_n(&m->t[3 * (size_t)dst[k]], 3, j.t);
+        jobs.push_back(j);
+        first += n;
+    }
+    return first;
 }
 
 double gate_tau2(const lvba_match_s *m, const lvba_match_opts &o)
@@ -278,9 +373,10 @@ double gate_tau2(const lvba_match_s *m, const lvba_match_opts &o)
     return tau * tau;
 }
 
-// the scan of `tasks` (results at their out_off in d_best / d_s1 / d_s2), one grid
-int32_t scan_tasks(hipStream_t s, const lvba_match_s *m, const std::vector<MatchTask> &tasks, const lvba_match_opts &o, int32_t *d_best,
-                   int32_t *d_s1, int32_t *d_s2)
+// the scan of `tasks` (results at their out_off in d_best / d_s1 / d_s2), one grid; under the depth gate after the predictions of
+// `jobs` (n_pred in all), which the tasks refer to
+int32_t scan_tasks(hipStream_t s, const lvba_match_s *m, const std::vector<MatchTask> &tasks, const std::vector<MatchPredJob> &jobs,
+                   int64_t n_pred, const lvba_match_opts &o, int32_t *d_best, int32_t *d_s1, int32_t *d_s2)
 {
     std::vector<int2> tiles;
     for (size_t k = 0; k < tasks.size(); ++k)
@@ -290,15 +386,40 @@ int32_t scan_tasks(hipStream_t s, const lvba_match_s *m, const std::vector<Match
     HIPCHK(d_tasks.alloc(sizeof(MatchTask) * tasks.size())); HIPCHK(d_tiles.alloc(sizeof(int2) * tiles.size()));
     HIPCHK(lvba::copy_h2d(d_tasks.p, tasks.data(), sizeof(MatchTask) * tasks.size()));
     HIPCHK(lvba::copy_h2d(d_tiles.p, tiles.data(), sizeof(int2) * tiles.size()));
-    if (o.guided)
-        match_scan_kernel<true><<<(unsigned)tiles.size(), SCAN_BLOCK, 0, s>>>(d_tasks.as<MatchTask>(), d_tiles.as<int2>(), m->d_desc, m->d_bias,
-                                                                            m->d_xy, gate_tau2(m, o), d_best, d_s1, d_s2);
+    DevBuf d_jobs(s), d_pred(s);
+    if (o.guided == MATCH_DEPTH) {
+        HIPCHK(d_pred.alloc(16 * (size_t)n_pred));
+        if (n_pred > 0) {
+            HIPCHK(d_jobs.alloc(sizeof(MatchPredJob) * jobs.size()));
+            HIPCHK(lvba::copy_h2d(d_jobs.p, jobs.data(), sizeof(MatchPredJob) * jobs.size()));
+            match_predict_kernel<<<grid_for(n_pred, 256), 256, 0, s>>>(n_pred, (int)jobs.size(), d_jobs.as<MatchPredJob>(), m->cam, m->d_pts,
+                                                                     d_pred.as<double>());
+            HIPCHK(hipGetLastError());
+        }
+        match_scan_kernel<MATCH_DEPTH><<<(unsigned)tiles.size(), SCAN_BLOCK, 0, s>>>(d_tasks.as<MatchTask>(), d_tiles.as<int2>(), m->d_desc,
+                                                                                   m->d_bias, nullptr, o.max_reproj_px * o.max_reproj_px, d_best,
+                                                                                   d_s1, d_s2, m->d_uv, d_pred.as<double>());
+    } else if (o.guided == MATCH_EPIPOLAR)
+        match_scan_kernel<MATCH_EPIPOLAR><<<(unsigned)tiles.size(), SCAN_BLOCK, 0, s>>>(d_tasks.as<MatchTask>(), d_tiles.as<int2>(), m->d_desc,
+                                                                                      m->d_bias, m->d_xy, gate_tau2(m, o), d_best, d_s1, d_s2,
+                                                                                      nullptr, nullptr);
     else
-        match_scan_kernel<false><<<(unsigned)tiles.size(), SCAN_BLOCK, 0, s>>>(d_tasks.as<MatchTask>(), d_tiles.as<int2>(), m->d_desc, m->d_bias,
-                                                                             nullptr, 0.0, d_best, d_s1, d_s2);
+        match_scan_kernel<MATCH_UNGUIDED><<<(unsigned)tiles.size(), SCAN_BLOCK, 0, s>>>(d_tasks.as<MatchTask>(), d_tiles.as<int2>(), m->d_desc,
+                                                                                      m->d_bias, nullptr, 0.0, d_best, d_s1, d_s2, nullptr,
+                                                                                      nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s)); // the task and tile lists go with this scope
     return LVBA_OK;
+}
+
+void drop_points(lvba_match_s *m)
+{
+    if (m->d_pts) {
+        (void)hipDeviceSynchronize();
+        DevicePool::get().free(m->d_pts);
+    }
+    m->d_pts = nullptr;
+    m->has_points = false;
 }
 
 } // namespace
@@ -307,7 +428,7 @@ extern "C" void lvba_match_default_opts(lvba_match_opts *o)
 {
     if (!o) return;
     *o = lvba_match_opts{};
-    o->max_distance = 0.7; o->max_ratio = 0.8; o->mutual = 1; o->guided = 0; o->max_epipolar_px = 4.0;
+    o->max_distance = 0.7; o->max_ratio = 0.8; o->mutual = 1; o->guided = 0; o->max_epipolar_px = 4.0; o->max_reproj_px = 8.0;
 }
 
 extern "C" int32_t lvba_match_create(int32_t device, int32_t n_images, const int64_t *desc_off, const uint8_t *desc, lvba_match_t *out)
@@ -359,7 +480,9 @@ extern "C" int32_t lvba_match_destroy(lvba_match_t m)
     (void)hipDeviceSynchronize();
     if (m->d_desc) DevicePool::get().free(m->d_desc);
     if (m->d_bias) DevicePool::get().free(m->d_bias);
+    if (m->d_uv) DevicePool::get().free(m->d_uv);
     if (m->d_xy) DevicePool::get().free(m->d_xy);
+    if (m->d_pts) DevicePool::get().free(m->d_pts);
     delete m;
     return LVBA_OK;
 }
@@ -387,18 +510,19 @@ extern "C" int32_t lvba_match_set_geometry(lvba_match_t m, const float *keypoint
         if (!(det > 0.0)) return lvba_fail(LVBA_ERR_ARG, "camera %d: rotation with determinant %g", i, det);
     }
     HIPCHK(hipSetDevice(m->device));
+    const TrkIntr cam{intr[0], intr[1], intr[2], intr[3], intr[4], intr[5], intr[6], intr[7]};
     if (total > 0) {
         if (!m->d_xy) HIPCHK(DevicePool::get().alloc((void **)&m->d_xy, 16 * (size_t)total));
+        if (!m->d_uv) HIPCHK(DevicePool::get().alloc((void **)&m->d_uv, 8 * (size_t)total));
         ScopedStream sg;
         HIPCHK(sg.acquire());
-        DevBuf d_uv(sg.s);
-        HIPCHK(d_uv.alloc(8 * (size_t)total));
-        HIPCHK(lvba::copy_h2d(d_uv.p, keypoints_uv, 8 * (size_t)total));
-        TrkIntr cam{intr[0], intr[1], intr[2], intr[3], intr[4], intr[5], intr[6], intr[7]};
-        match_undistort_kernel<<<grid_for(total, 256), 256, 0, sg.s>>>(total, d_uv.as<float>(), cam, m->d_xy);
+        HIPCHK(lvba::copy_h2d(m->d_uv, keypoints_uv, 8 * (size_t)total));
+        match_undistort_kernel<<<grid_for(total, 256), 256, 0, sg.s>>>(total, m->d_uv, cam, m->d_xy);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(sg.s));
     }
+    drop_points(m); // they were lifted with the poses these replace
+    m->cam = cam;
     m->R.assign(Rcw, Rcw + 9 * (size_t)m->n_images);
     m->t.assign(tcw, tcw + 3 * (size_t)m->n_images);
     m->focal_sum = intr[0] + intr[1];
@@ -421,8 +545,10 @@ extern "C" int32_t lvba_match_scan(lvba_match_t m, int32_t a, int32_t b, const l
     DevBuf d_out(sg.s);
     HIPCHK(d_out.alloc(12 * n_a));
     int32_t *d = d_out.as<int32_t>();
-    std::vector<MatchTask> tasks{make_task(m, a, b, 0, o.guided != 0)};
-    TRY(scan_tasks(sg.s, m, tasks, o, d, d + n_a, d + 2 * n_a));
+    std::vector<MatchPredJob> jobs;
+    const int64_t n_pred = o.guided == MATCH_DEPTH ? predict_jobs(m, a, b, 0, jobs) : 0;
+    std::vector<MatchTask> tasks{make_task(m, a, b, 0, o.guided, 0, (int64_t)n_a)};
+    TRY(scan_tasks(sg.s, m, tasks, jobs, n_pred, o, d, d + n_a, d + 2 * n_a));
     HIPCHK(lvba::copy_d2h(best, d, 4 * n_a));
     HIPCHK(lvba::copy_d2h(s1, d + n_a, 4 * n_a));
     HIPCHK(lvba::copy_d2h(s2, d + 2 * n_a, 4 * n_a));
@@ -450,15 +576,20 @@ extern "C" int32_t lvba_match_pairs(lvba_match_t m, int64_t n_pairs, const int32
         std::vector<MatchTask> tasks;
         std::vector<int64_t> row_off;
         std::vector<MatchPairOut> po;
-        int64_t rows = 0, fwd_rows = 0, p1 = p0;
+        std::vector<MatchPredJob> jobs;
+        int64_t rows = 0, fwd_rows = 0, n_pred = 0, p1 = p0;
         for (; p1 < n_pairs && p1 - p0 < INT32_MAX / 4; ++p1) {
             const int a = pairs[2 * p1], b = pairs[2 * p1 + 1];
             const int64_t n_a = m->off[a + 1] - m->off[a], n_b = m->off[b + 1] - m->off[b];
             const int64_t need = n_a + (o.mutual ? n_b : 0);
             if (p1 > p0 && rows + need > CHUNK_ROWS) break;
+            // the depth gate's predictions cover both images of a pair whatever `mutual` is: they bound the chunk as well
+            if (p1 > p0 && o.guided == MATCH_DEPTH && n_pred + n_a + n_b > CHUNK_ROWS) break;
             MatchPairOut q; q.fwd = rows; q.rev = rows + n_a;
-            tasks.push_back(make_task(m, a, b, q.fwd, o.guided != 0));
-            if (o.mutual) tasks.push_back(make_task(m, b, a, q.rev, o.guided != 0));
+            const int64_t pa = n_pred, pb = n_pred + n_a; // a's keypoints in b, b's in a
+            if (o.guided == MATCH_DEPTH) n_pred = predict_jobs(m, a, b, n_pred, jobs);
+            tasks.push_back(make_task(m, a, b, q.fwd, o.guided, pa, pb));
+            if (o.mutual) tasks.push_back(make_task(m, b, a, q.rev, o.guided, pb, pa));
             row_off.push_back(fwd_rows); po.push_back(q);
             rows += need; fwd_rows += n_a;
         }
@@ -468,7 +599,7 @@ extern "C" int32_t lvba_match_pairs(lvba_match_t m, int64_t n_pairs, const int32
             DevBuf d_res(s), d_row_off(s), d_po(s), d_flag(s), d_excl(s), d_off(s), d_m(s), d_sc(s);
             HIPCHK(d_res.alloc(12 * (size_t)rows));
             int32_t *d_best = d_res.as<int32_t>(), *d_s1 = d_best + rows, *d_s2 = d_s1 + rows;
-            TRY(scan_tasks(s, m, tasks, o, d_best, d_s1, d_s2));
+            TRY(scan_tasks(s, m, tasks, jobs, n_pred, o, d_best, d_s1, d_s2));
             HIPCHK(d_row_off.alloc(8 * row_off.size())); HIPCHK(d_po.alloc(sizeof(MatchPairOut) * po.size()));
             HIPCHK(d_flag.alloc(4 * ((size_t)fwd_rows + 1))); HIPCHK(d_excl.alloc(4 * ((size_t)fwd_rows + 1))); HIPCHK(d_off.alloc(8 * (size_t)np));
             HIPCHK(lvba::copy_h2d(d_row_off.p, row_off.data(), 8 * row_off.size()));
@@ -500,5 +631,53 @@ extern "C" int32_t lvba_match_pairs(lvba_match_t m, int64_t n_pairs, const int32
     }
     match_off[n_pairs] = base;
     *count = base;
+    return LVBA_OK;
+}
+
+extern "C" int32_t lvba_match_set_depth(lvba_match_t m, lvba_depth_t depth)
+{
+    if (!m) return lvba_fail(LVBA_ERR_ARG, "null handle");
+    HIPCHK(hipSetDevice(m->device));
+    if (!depth) {
+        drop_points(m);
+        return LVBA_OK;
+    }
+    if (!m->has_geometry) return lvba_fail(LVBA_ERR_ARG, "lvba_match_set_depth needs lvba_match_set_geometry first");
+    if (depth->n_images != m->n_images)
+        return lvba_fail(LVBA_ERR_ARG, "the depth set holds %d images, the matcher %d", depth->n_images, m->n_images);
+    if (depth->device != m->device)
+        return lvba_fail(LVBA_ERR_ARG, "the depth set lives on device %d, the matcher on device %d", depth->device, m->device);
+    const int64_t total = m->off[m->n_images];
+    if (total > 0) {
+        ScopedStream sg;
+        HIPCHK(sg.acquire());
+        DevBuf d_new(sg.s), d_off(sg.s), d_R(sg.s), d_t(sg.s); // the old table stays until the new one stands
+        HIPCHK(d_new.alloc(24 * (size_t)total)); HIPCHK(d_off.alloc(8 * m->off.size()));
+        HIPCHK(d_R.alloc(8 * m->R.size())); HIPCHK(d_t.alloc(8 * m->t.size()));
+        HIPCHK(lvba::copy_h2d(d_off.p, m->off.data(), 8 * m->off.size()));
+        HIPCHK(lvba::copy_h2d(d_R.p, m->R.data(), 8 * m->R.size()));
+        HIPCHK(lvba::copy_h2d(d_t.p, m->t.data(), 8 * m->t.size()));
+        match_lift_kernel<<<grid_for(total, 256), 256, 0, sg.s>>>(total, m->n_images, d_off.as<int64_t>(), m->d_uv, m->d_xy, depth->d_depth,
+                                                                depth->width, depth->height, d_R.as<double>(), d_t.as<double>(),
+                                                                d_new.as<double>());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(sg.s));
+        drop_points(m);
+        m->d_pts = (double *)d_new.release();
+    }
+    m->has_points = true;
+    return LVBA_OK;
+}
+
+extern "C" int32_t lvba_match_points(lvba_match_t m, double *world)
+{
+    if (!m) return lvba_fail(LVBA_ERR_ARG, "null handle");
+    if (!m->has_points) return lvba_fail(LVBA_ERR_ARG, "no lifted points: lvba_match_set_depth first");
+    const int64_t total = m->off[m->n_images];
+    if (total == 0) return LVBA_OK;
+    if (!world) return lvba_fail(LVBA_ERR_ARG, "null output");
+    HIPCHK(hipSetDevice(m->device));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(lvba::copy_d2h(world, m->d_pts, 24 * (size_t)total));
     return LVBA_OK;
 }

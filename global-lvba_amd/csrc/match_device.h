@@ -1,9 +1,11 @@
 // match_device.h -- scalar pieces of the descriptor matcher (match.hip; the rule is in include/lvba_hip.h):
-// the running top two of a row, their merge, the epipolar gate and the fp64 decision.  Host/device-neutral, like tracks_device.h.
+// the running top two of a row, their merge, the epipolar gate, the depth gate and the fp64 decision.  Host/device-neutral, like
+// tracks_device.h.
 #pragma once
 #include <math.h>
 #include <stdint.h>
 #include "tracks_device.h"
+#include "fusion_device.h"
 
 namespace lvba {
 
@@ -13,6 +15,7 @@ constexpr int32_t MATCH_NONE = INT32_MIN;         // "no column yet": below ever
 constexpr int32_t MATCH_BIAS_CONST = 128 * 128 * 128;
 constexpr double MATCH_SCORE_SCALE = 262144.0;    // 512^2
 constexpr double MATCH_BASELINE_REL2 = 1e-20;     // |t_ab|^2 <= this (|t_a|^2 + |t_b|^2): no epipolar geometry
+enum MatchMode : int { MATCH_UNGUIDED = 0, MATCH_EPIPOLAR = 1, MATCH_DEPTH = 2 }; // lvba_match_opts::guided
 
 // Running (s1, best, s2) of one row over the columns one lane sees, in ascending column order: a strict > keeps the lowest column
 // of a tie.  The scores are biased by a per-row constant, which no comparison within a row sees.
@@ -83,6 +86,36 @@ LVBA_TRK_FN void match_essential(const double *Rlo, const double *tlo, const dou
         E[3 + j] = t[2] * R[j] - t[0] * R[6 + j];
         E[6 + j] = t[0] * R[3 + j] - t[1] * R[j];
     }
+}
+
+// Depth gate.  A keypoint with a depth return is a 3-D point (match_lift: NaN where it has none); its prediction in another
+// image is a pixel (match_predict): NaN for a keypoint without a point, +inf for a point that does not project ("nowhere"), so
+// that neither needs a branch below -- a NaN or an infinite distance fails the comparison, and "has a point" is "the prediction
+// is not NaN" (a projection that succeeds is finite).  Both orientations of a pair evaluate these same expressions on the same
+// operands, so the decision for (r, c) and for (c, r) is one bit.
+LVBA_TRK_FN void match_lift(const float *__restrict__ depth, int w, int h, float u, float v, double x, double y,
+                            const double *__restrict__ R, const double *__restrict__ tc, double *__restrict__ X)
+{
+    double p[3];
+    const bool ok = depth_world_point(depth, w, h, u, v, x, y, R, tc, p) && isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]);
+    X[0] = ok ? p[0] : NAN; X[1] = ok ? p[1] : NAN; X[2] = ok ? p[2] : NAN;
+}
+LVBA_TRK_FN void match_predict(const TrkIntr &cam, const double *R, const double *t, const double *X, double &pu, double &pv)
+{
+    if (X[0] != X[0]) { pu = pv = NAN; return; }
+    if (!trk_project(cam, R, t, X, pu, pv)) pu = pv = INFINITY;
+}
+struct MatchReproj { double u, v, pu, pv; };      // a keypoint's own pixel and its prediction in the other image of the pair
+LVBA_TRK_FN bool match_reproj_near(double u, double v, double pu, double pv, double rho2)   // d^2 <= rho^2
+{
+    const double du = u - pu, dv = v - pv;
+    return du * du + dv * dv <= rho2;
+}
+LVBA_TRK_FN bool match_depth_gate(const MatchReproj &p, const MatchReproj &q, double rho2)
+{
+    const bool hp = p.pu == p.pu, hq = q.pu == q.pu;
+    const bool near_q = match_reproj_near(q.u, q.v, p.pu, p.pv, rho2), near_p = match_reproj_near(p.u, p.v, q.pu, q.pv, rho2);
+    return (hp | hq) & (near_q | !hp) & (near_p | !hq);
 }
 
 LVBA_TRK_FN double match_distance(int32_t s)

@@ -23,6 +23,13 @@ struct lvba_scans_s {
     int64_t *d_frame_off = nullptr;
 };
 
+// depth images on a device (fusion.hip renders or uploads them; match.hip reads them)
+struct lvba_depth_s {
+    int device = 0;
+    int n_images = 0, width = 0, height = 0;
+    float *d_depth = nullptr; // [n_images][height][width], 0 = no return
+};
+
 namespace lvba {
 struct DevCloud { float *d; int64_t n; }; // n points [n][3] on a device
 // A scan set of n_frames frames of count[f] points on `device`, allocated with hipMalloc as lvba_scans_destroy frees it

@@ -1,5 +1,5 @@
-"""Descriptor matching of image pairs on the GPU, with an optional pose-guided epipolar gate (lvba_match_*; the rule is in
-include/lvba_hip.h).  Opt-in: nothing imports this module unless matching is asked for."""
+"""Descriptor matching of image pairs on the GPU, with an optional pose-guided gate -- on the epipolar line, or at the point a
+LiDAR depth image predicts (lvba_match_*; the rule is in include/lvba_hip.h).  Opt-in: nothing imports this module unless matching is asked for."""
 from __future__ import annotations
 
 import ctypes as C
@@ -8,11 +8,11 @@ import numpy as np
 
 from . import _lib as L
 
-OPTION_NAMES = ("max_distance", "max_ratio", "mutual", "guided", "max_epipolar_px")
+OPTION_NAMES = ("max_distance", "max_ratio", "mutual", "guided", "max_epipolar_px", "max_reproj_px")
 
 
 def match_opts(lib=None, **kw):
-    """lvba_match_opts: the defaults (0.7, 0.8, mutual, unguided, 4 px) with `kw` over them."""
+    """lvba_match_opts: the defaults (0.7, 0.8, mutual, unguided, 4 px, 8 px) with `kw` over them."""
     o = L.MatchOpts()
     (lib or L.load()).lvba_match_default_opts(C.byref(o))
     for k, v in kw.items():
@@ -42,6 +42,7 @@ class Matcher:
         flat = np.concatenate(descs) if descs else np.zeros((0, 128), np.uint8)
         self.device = int(device)
         self.has_geometry = False
+        self.has_depth = False
         self._h = C.c_void_p()
         L.check(self.lib.lvba_match_create(self.device, self.n_images, self.off.ctypes.data, flat.ctypes.data, C.byref(self._h)))
 
@@ -64,7 +65,8 @@ class Matcher:
 
     def set_geometry(self, keypoints, intr, Rcw, tcw):
         """keypoints: per image [n_i, 2] pixels (rounded to fp32), in descriptor order; intr (fx, fy, cx, cy, k1, k2, p1, p2);
-        Rcw [M, 3, 3], tcw [M, 3] = T_cam<-world.  May be called again with new poses."""
+        Rcw [M, 3, 3], tcw [M, 3] = T_cam<-world.  May be called again with new poses; the points of set_depth are dropped then
+        (they were lifted with the old poses)."""
         kps = [np.asarray(k, np.float32).reshape(-1, 2) for k in keypoints]
         if len(kps) != self.n_images or any(len(k) != n for k, n in zip(kps, self.counts)):
             raise ValueError("keypoints must give one [n_i, 2] array per image, a row per descriptor")
@@ -74,6 +76,21 @@ class Matcher:
         t = np.ascontiguousarray(tcw, np.float64).reshape(self.n_images, 3)
         L.check(self.lib.lvba_match_set_geometry(self._h, uv.ctypes.data, intr.ctypes.data, R.ctypes.data, t.ctypes.data))
         self.has_geometry = True
+        self.has_depth = False
+
+    def set_depth(self, depth):
+        """depth: a visual.DepthImages with one image per image of the matcher, on its device (rendered at the poses of
+        set_geometry), or None to drop the points.  Every keypoint with a depth return is lifted to its 3-D point once, on the
+        device; guided=2 then gates a candidate at the point's image in the other view.  The depth set is only read during the
+        call."""
+        L.check(self.lib.lvba_match_set_depth(self._h, depth._h if depth is not None else None))
+        self.has_depth = depth is not None
+
+    def points(self):
+        """float64 [total, 3]: the lifted point of every keypoint, image after image; NaN rows have none."""
+        out = np.zeros((int(self.off[-1]), 3))
+        L.check(self.lib.lvba_match_points(self._h, out.ctypes.data))
+        return out
 
     def match_pairs_csr(self, pairs, capacity=None, **opts):
         """(matches int32 [m, 2], scores int32 [m], match_off int64 [n_pairs + 1], count): the C call as it is.  `capacity`
@@ -110,10 +127,15 @@ class Matcher:
         return best, s1, s2
 
 
-def match_pairs(descriptors, pairs, keypoints=None, intr=None, Rcw=None, tcw=None, device=0, **opts):
-    """Matcher(descriptors).match_pairs(pairs) in one call; guided when the geometry is given (unless guided=0 is passed)."""
+def match_pairs(descriptors, pairs, keypoints=None, intr=None, Rcw=None, tcw=None, device=0, depth=None, **opts):
+    """Matcher(descriptors).match_pairs(pairs) in one call; guided when the geometry is given, depth-guided when a
+    visual.DepthImages comes with it (unless guided is passed)."""
     with Matcher(descriptors, device=device) as m:
         if Rcw is not None:
             m.set_geometry(keypoints, intr, Rcw, tcw)
-            opts.setdefault("guided", 1)
+            opts.setdefault("guided", 1 if depth is None else 2)
+            if depth is not None:
+                m.set_depth(depth)
+        elif depth is not None:
+            raise ValueError("depth-guided matching needs the geometry (keypoints, intr, Rcw, tcw)")
         return m.match_pairs(pairs, **opts)

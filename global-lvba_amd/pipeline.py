@@ -213,20 +213,24 @@ def build_tracks_and_fuse(keypoints, pairs, matches, fuse_fn, obser_thr=3):
 
 
 def run_visual_ba_with_lidar_assist(scans, x_opt, x_orig, scan_times, image_times, image_poses, Rci, tci, intr, width, height,
-                                    keypoints, pairs, matches, camera_priors=None, **cfg):
+                                    keypoints, pairs, matches, camera_priors=None, depth=None, **cfg):
     """LvbaSystem::runVisualBAWithLidarAssist (src/lvba_system.cpp:144-154) from the refined LiDAR poses to the refined
     cameras.  scans: a voxel.Scans holding the raw clouds; keypoints[i] = [n_i, 2] float pixel coordinates; pairs / matches as
     build_tracks takes them.  cfg["visual_loss"]: see DEFAULTS.  camera_priors: None (the reference's problem), a list of
     balm.Prior objects on cameras, or a callable cam_poses -> list, called with the LiDAR-derived image poses [m,12]
     (T_world<-imu) that only exist inside this call (e.g. lambda cams: lidar_camera_priors(cams, Rci, tci, 1e-3, 0.02)).
+    depth: None (the depth images are rendered here), or a visual.DepthImages already rendered with these arguments
+    (as run_full_pipeline does under match_depth): it is used as it is and stays the caller's to close.
     Returns a dict (cameras before / after, tracks, landmarks, planes, traces)."""
     c = dict(DEFAULTS); c.update(cfg)
     cam_new = update_camera_poses_from_lidar(x_opt, x_orig, scan_times, image_times, image_poses)      # poses_
     Rcw, tcw = camera_from_imu(cam_new, Rci, tci)                                                      # Rcw_all_optimized_
     Rcw0, tcw0 = camera_from_imu(image_poses, Rci, tci)                                                # Rcw_all_ (before)
     # generateDepthWithVoxel (+ buildGridMapFromOptimized)
-    depth = V.DepthImages.render(scans, x_opt, scan_times, image_times, Rcw, tcw, intr, width, height,
-                                 half_window_s=c["depth_half_window_s"], voxel_size=c["depth_voxel"])
+    own_depth = depth is None
+    if own_depth:
+        depth = V.DepthImages.render(scans, x_opt, scan_times, image_times, Rcw, tcw, intr, width, height,
+                                     half_window_s=c["depth_half_window_s"], voxel_size=c["depth_voxel"])
     try:
         # BuildTracksAndFuse3D
         T = build_tracks_and_fuse(keypoints, pairs, matches,
@@ -234,7 +238,8 @@ def run_visual_ba_with_lidar_assist(scans, x_opt, x_orig, scan_times, image_time
                                                                 min_view_angle_deg=c["min_view_angle_deg"],
                                                                 reproj_mean_thr_px=c["reproj_mean_thr_px"]), c["obser_thr"])
     finally:
-        depth.close()
+        if own_depth:
+            depth.close()
     off, img, uv, kept, X, err = T["obs_off"], T["obs_img"], T["obs_uv"], T["kept"], T["X"], T["err"]
     status = T["component_status"]
     tr = np.arange(len(X))                                                   # tracks_: every one is usable (:1436-1441)
@@ -586,21 +591,24 @@ def run_lidar_ba(scans, poses, priors=None, window_loss=None, stage_loss=None, h
     return out, report
 
 
-def match_image_pairs(descriptors, pairs, keypoints=None, Rcw=None, tcw=None, intr=None, device=0, **opts):
+def match_image_pairs(descriptors, pairs, keypoints=None, Rcw=None, tcw=None, intr=None, device=0, depth=None, **opts):
     """Feature matches of image pairs from their descriptors (match.Matcher), in the form build_tracks and
     run_full_pipeline take: one int32 [m, 2] array per pair, in the order of `pairs`; a pair without matches gives an empty
     array, it is not dropped.  descriptors[i] = uint8 [n_i, 128].  Without geometry the matching is unguided (the reference's
     fallback, src/lvba_system.cpp:697-833: distance bound, ratio test, mutual best match); with keypoints, Rcw, tcw
-    (T_cam<-world) and intr a candidate must also lie within max_epipolar_px of the epipolar line the poses give.  opts:
-    max_distance, max_ratio, mutual, max_epipolar_px."""
+    (T_cam<-world) and intr a candidate must also lie within max_epipolar_px of the epipolar line the poses give.  With depth (a
+    visual.DepthImages rendered at those poses, one image per image) on top, the gate is a point instead of a line (guided=2): a
+    keypoint with a depth return is a 3-D point, and a candidate must lie within max_reproj_px of its image in the other view
+    -- which separates copies of a texture that lie along the epipolar line.  opts: max_distance, max_ratio, mutual, guided,
+    max_epipolar_px, max_reproj_px."""
     from . import match as M
-    return M.match_pairs(descriptors, pairs, keypoints=keypoints, intr=intr, Rcw=Rcw, tcw=tcw, device=device, **opts)
+    return M.match_pairs(descriptors, pairs, keypoints=keypoints, intr=intr, Rcw=Rcw, tcw=tcw, device=device, depth=depth, **opts)
 
 
 def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, tci, intr, width, height, keypoints, pairs,
                       matches, enable_lidar_ba=True, enable_visual_ba=True, device=0, images=None, lidar_priors=None,
                       window_loss=None, stage_loss=None, camera_priors=None, map_quality=False, loop_closures=None, relax=None,
-                      match_fn=None, **cfg):
+                      match_fn=None, match_depth=False, **cfg):
     """LvbaSystem::runFullPipeline (src/lvba_system.cpp:136-142) on in-memory data: clouds = body-frame [n_i, >=3] float32
     arrays, poses [n,12] = x_buf_ (T_world<-imu), image_poses [m,12] the image poses from the odometry.  cfg: DEFAULTS' keys
     (visual_loss, colorize_leaf among them).  images: None, or the images ([m,H,W,3] BGR uint8 or a callable k -> [H,W,3]):
@@ -620,7 +628,10 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
     closures as priors, and the output holds pose_graph = dict(report, weights, max_pose_change).  poses_before stays the input.
     match_fn: None (pairs and matches are the caller's), or a callable cam_poses -> (pairs, matches), called after the LiDAR stage
     with the LiDAR-derived image poses [m,12] (T_world<-imu): the matches are then made against the refined poses (guided
-    matching, match_image_pairs) and replace the arguments; the output holds pairs / matches as used."""
+    matching, match_image_pairs) and replace the arguments; the output holds pairs / matches as used.
+    match_depth: False, or True (only with match_fn): the depth images of the visual stage are rendered once, at the LiDAR-refined
+    poses, before the matching; match_fn is called as match_fn(cam_poses, depth=depth) (depth-guided matching: hand it on to
+    match_image_pairs) and the visual stage uses the same images, which are closed here."""
     if images is not None and not enable_visual_ba:
         raise ValueError("colouring the map needs the cameras of the visual stage (enable_visual_ba=True)")
     c = dict(DEFAULTS); c.update(cfg)
@@ -637,13 +648,26 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
             x_opt, report = run_lidar_ba(scans, x_opt, priors=lidar_priors, window_loss=window_loss, stage_loss=stage_loss, **c)
             out["lidar_report"] = report
         out["poses"] = np.asarray(x_opt).reshape(-1, 12)
-        if enable_visual_ba and match_fn is not None:
-            pairs, matches = match_fn(update_camera_poses_from_lidar(out["poses"], x_orig, scan_times, image_times, image_poses))
-            out["pairs"], out["matches"] = pairs, matches
-        if enable_visual_ba:
-            out["visual"] = run_visual_ba_with_lidar_assist(scans, out["poses"], x_orig, scan_times, image_times, image_poses, Rci,
-                                                            tci, intr, width, height, keypoints, pairs, matches,
-                                                            camera_priors=camera_priors, **c)
+        depth = None
+        try:
+            if enable_visual_ba and match_fn is not None:
+                cam_poses = update_camera_poses_from_lidar(out["poses"], x_orig, scan_times, image_times, image_poses)
+                if match_depth:
+                    Rcw, tcw = camera_from_imu(cam_poses, Rci, tci)
+                    depth = V.DepthImages.render(scans, out["poses"], scan_times, image_times, Rcw, tcw, intr, width, height,
+                                                 half_window_s=c["depth_half_window_s"], voxel_size=c["depth_voxel"])
+                    pairs, matches = match_fn(cam_poses, depth=depth)
+                else:
+                    pairs, matches = match_fn(cam_poses)
+                out["pairs"], out["matches"] = pairs, matches
+            if enable_visual_ba:
+                out["visual"] = run_visual_ba_with_lidar_assist(scans, out["poses"], x_orig, scan_times, image_times, image_poses, Rci,
+                                                                tci, intr, width, height, keypoints, pairs, matches,
+                                                                camera_priors=camera_priors, **({"depth": depth} if depth is not None else {}),
+                                                                **c)
+        finally:
+            if depth is not None:
+                depth.close()
         if images is not None:
             v = out["visual"]
             col = colorize_maps(scans, image_times, images, intr, width, height, after=(out["poses"], v["Rcw"], v["tcw"]),
@@ -708,7 +732,9 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
     "descriptors": every image pair is matched from the database's descriptors table, unguided, as the reference's fallback does
     when the database holds no verified matches (src/lvba_system.cpp:697-833; match_image_pairs).  "guided": the same, but after
     the LiDAR stage and against the refined, LiDAR-derived camera poses, a candidate having to lie near its epipolar line -- the
-    one place where the order differs from the reference's.  match_opts: match_image_pairs' options for the last two.
+    one place where the order differs from the reference's.  "depth": as "guided", but the gate is the point the LiDAR depth image
+    of the keypoint's own view predicts in the other view (match_image_pairs' depth; run_full_pipeline's match_depth): it also
+    separates copies of a texture along the epipolar line.  match_opts: match_image_pairs' options for the last three.
     cfg as for run_full_pipeline, e.g. visual_loss=REFERENCE_HUBER, window_loss=("cauchy", 0.1), stage_loss=("huber", 0.05),
     camera_priors=lambda cams: lidar_camera_priors(cams, Rci, tci, 1e-3, 0.02)."""
     import os
@@ -723,8 +749,8 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
     pairs = [(i, j) for i in range(len(image_ids)) for j in range(i + 1, len(image_ids))]        # image_pairs_, :462-466
     kps, matches = D.load_colmap_db(colmap_db_path if os.path.isabs(colmap_db_path) else os.path.join(data_path, colmap_db_path),
                                     names, pairs)
-    if matching not in ("db", "descriptors", "guided"):
-        raise ValueError(f"matching={matching!r}: one of 'db', 'descriptors', 'guided'")
+    if matching not in ("db", "descriptors", "guided", "depth"):
+        raise ValueError(f"matching={matching!r}: one of 'db', 'descriptors', 'guided', 'depth'")
     Rci, tci = extrinsics_from_config(Rcl, Pcl, extrinsic_R, extrinsic_T)
     match_fn = None
     if matching != "db":
@@ -735,16 +761,17 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
         if matching == "descriptors":
             matches = match_image_pairs(descs, pairs, device=device, **(match_opts or {}))
         else:
-            def match_fn(cam_poses):
+            def match_fn(cam_poses, depth=None):
                 Rcw, tcw = camera_from_imu(cam_poses, Rci, tci)
                 m = match_image_pairs(descs, pairs, keypoints=[k[:, :2] for k in kps], Rcw=Rcw, tcw=tcw, intr=intr, device=device,
-                                      **(match_opts or {}))
+                                      depth=depth, **(match_opts or {}))
                 kept = [k for k, mm in enumerate(m) if len(mm)]
                 return [pairs[k] for k in kept], [m[k] for k in kept]
     keep = [k for k, m in enumerate(matches) if len(m)]
     out = run_full_pipeline([c[:, :3] for c in ds["clouds"]], ds["poses"], ds["timestamps"], image_ids, image_poses, Rci, tci, intr,
                             width, height, [k[:, :2] for k in kps], [pairs[k] for k in keep], [matches[k] for k in keep],
-                            device=device, **({"match_fn": match_fn} if match_fn is not None else {}), images=(lambda k: D.read_image_bgr(os.path.join(img_dir, names[k]), width, height))
+                            device=device, **({"match_fn": match_fn} if match_fn is not None else {}),
+                            **({"match_depth": True} if matching == "depth" else {}), images=(lambda k: D.read_image_bgr(os.path.join(img_dir, names[k]), width, height))
                             if colorize else None, **({"map_quality": map_quality} if map_quality else {}),
                             **({"loop_closures": loop_closures} if loop_closures else {}),
                             **({"relax": relax} if relax and loop_closures else {}), **cfg)

@@ -1032,7 +1032,7 @@ int32_t lvba_posegraph_relax(int32_t n_poses, const double *poses, int32_t n_edg
                              lvba_lm_trace *trace, int32_t *n_trace /* may be NULL */,
                              lvba_posegraph_report *report);
 
-/* ---- descriptor matching of image pairs, with an optional pose-guided epipolar gate (opt-in) -------------------
+/* ---- descriptor matching of image pairs, with an optional pose-guided gate: epipolar or through LiDAR depth (opt-in)
  *   The reference's fallback when its COLMAP database holds no verified matches (src/lvba_system.cpp:697-833) matches every image
  *   pair with SiftMatchGPU::GetSiftMatch(n, buf, 0.7f, 0.8f, 1).  SiftGPU's source is not part of the reference tree: the rule
  *   below is this project's own definition of those three documented parameters, restated by a numpy oracle and NOT pinned against
@@ -1062,25 +1062,50 @@ int32_t lvba_posegraph_relax(int32_t n_poses, const double *poses, int32_t n_edg
  *   decision for (r, c) in one is bit for bit the decision for (c, r) in the other.  A pair whose centres coincide,
  *   |t_lh|^2 <= 1e-20 (|t_lo|^2 + |t_hi|^2), has no epipolar geometry: E is taken as zero and every candidate (of keypoints whose
  *   undistortion succeeded) passes.
+ *   Depth-guided gate (guided = 2, needs lvba_match_set_geometry and then lvba_match_set_depth).  An epipolar gate cannot separate
+ *   copies of a texture that lie along the epipolar line; a keypoint with a LiDAR depth return is a 3-D point, and its image in
+ *   the other view is a point, not a line.
+ *     The point of keypoint p of image i, fp32 pixel (u, v):  d = fetchDepthBilinear(depth_i, u, v)  (float arithmetic, all four
+ *       neighbours > 0, exactly as lvba_fuse_tracks samples it);  X^c = (x d, y d, d) with (x, y) the undistorted normalised point
+ *       above;  X_p = camToWorld(X^c) = R_i^T X^c + (-(R_i^T t_i)), every sum left to right, no fused multiply-add (the expressions
+ *       of the track fusion).  p HAS A POINT iff the fetch and the undistortion succeed and X^c and X_p are finite.
+ *     The prediction of p in image j:  (u^, v^) = the distorted pixel of X_p under (R_j, t_j) (the reference's
+ *       projectCameraToPixel).  When the projection fails (Z <= 1e-12 or a non-finite value) the prediction is NOWHERE.
+ *     For a keypoint q of image j with pixel (u_q, v_q) widened to fp64:  d2(p -> q) = (u_q - u^)(u_q - u^) + (v_q - v^)(v_q - v^).
+ *     The candidate (p, q) passes iff  at least one of p, q has a point,  and for each of the two that has a point
+ *       d2 <= rho rho,  rho = max_reproj_px  -- false for a NaN pixel and for a prediction that is nowhere.
+ *   If neither keypoint has a point the candidate fails: a caller who wants those keypoints matched runs guided = 1 on them.
+ *   There is no occlusion test (the point of p may be hidden in j): the descriptor decides.  As under the epipolar gate, both
+ *   orientations of a pair evaluate these same expressions on the same operands: the decision for (r, c) in (a, b) is bit for bit
+ *   the decision for (c, r) in (b, a), as the mutual clause requires.  max_reproj_px defaults to 8, twice the epipolar default; no
+ *   real dataset was at hand to choose it on.
  *   lvba_match_create: desc_off [n_images + 1] (desc_off[0] = 0), desc [sum n][128]; the descriptors go to the device once.
  *   lvba_match_set_geometry: keypoints_uv [sum n][2] in descriptor order, intr = (fx, fy, cx, cy, k1, k2, p1, p2), Rcw [n_images][9]
- *   row-major, tcw [n_images][3]; undistorts on the device once; may be called again (new poses replace the old).
+ *   row-major, tcw [n_images][3]; undistorts on the device once; may be called again (new poses replace the old, and the lifted
+ *   points are dropped: they were lifted with the old poses).
+ *   lvba_match_set_depth: lifts every keypoint of every image once, on the device, into a resident [sum n][3] fp64 table (NaN rows:
+ *   no point).  depth: one image per image of the matcher (lvba_depth_render / lvba_depth_upload), on the matcher's device; it is
+ *   only read during the call.  depth = NULL drops the table.  lvba_match_points downloads the table, world [sum n][3].
  *   lvba_match_pairs: all pairs in one call, their work tiled over one grid per 2^23 scanned rows.  matches [capacity][2] = (r, c),
  *   scores [capacity] (may be NULL) = s1 of each match, match_off [n_pairs + 1] the first match of each pair.  *count is the true
  *   number of matches and match_off the true offsets even when they exceed capacity; only the first `capacity` matches are
- *   written.  lvba_match_scan: best, s1, s2 [n_a] of the ordered pair (a, b) before any threshold (it reads only guided and
- *   max_epipolar_px of the options).  No atomics: two calls give the same bytes.  Options: NULL takes the defaults.
+ *   written.  lvba_match_scan: best, s1, s2 [n_a] of the ordered pair (a, b) before any threshold (it reads only guided,
+ *   max_epipolar_px and max_reproj_px of the options).  No atomics: two calls give the same bytes.  Options: NULL takes the defaults.
  *   LVBA_ERR_ARG: a null required pointer, a negative count, desc_off that does not start at 0 or decreases, an image above the
  *   per-image limit, a pair index outside the images, a == b, an option outside its range below (non-finite included), guided
- *   without geometry, non-finite intrinsics or poses, fx or fy <= 0, a rotation that is not orthonormal within 1e-6 with
- *   determinant > 0.  A refused call writes nothing (a refused set_geometry keeps the geometry it had). */
+ *   without geometry, guided = 2 or lvba_match_points without lifted points, lvba_match_set_depth without geometry or with a depth
+ *   set of another image count or on another device, non-finite intrinsics or poses, fx or fy <= 0, a rotation that is not orthonormal within 1e-6 with
+ *   determinant > 0.  A refused call writes nothing (a refused set_geometry keeps the geometry and the points it had, a refused set_depth the
+ *   points).  lvba_match_opts grew by max_reproj_px (32 -> 40 bytes) with these two calls; lvba_version() is unchanged, a client
+ *   detects the larger struct by looking lvba_match_set_depth up. */
 typedef struct lvba_match_s *lvba_match_t;
 typedef struct lvba_match_opts {
     double max_distance;     /* rad, finite and > 0 (default 0.7) */
     double max_ratio;        /* in (0, 1] (default 0.8) */
     int32_t mutual;          /* 0 or 1 (default 1) */
-    int32_t guided;          /* 0 or 1 (default 0) */
+    int32_t guided;          /* 0 none, 1 epipolar, 2 depth (default 0) */
     double max_epipolar_px;  /* pixels, finite and > 0 (default 4) */
+    double max_reproj_px;    /* pixels, finite and > 0 (default 8); checked always, used by guided = 2 */
 } lvba_match_opts;
 void    lvba_match_default_opts(lvba_match_opts *o);
 int32_t lvba_match_create(int32_t device, int32_t n_images, const int64_t *desc_off, const uint8_t *desc, lvba_match_t *out);
@@ -1089,6 +1114,8 @@ int32_t lvba_match_set_geometry(lvba_match_t m, const float *keypoints_uv, const
 int32_t lvba_match_pairs(lvba_match_t m, int64_t n_pairs, const int32_t *pairs, const lvba_match_opts *o, int64_t capacity,
                          int32_t *matches, int32_t *scores, int64_t *match_off, int64_t *count);
 int32_t lvba_match_scan(lvba_match_t m, int32_t a, int32_t b, const lvba_match_opts *o, int32_t *best, int32_t *s1, int32_t *s2);
+int32_t lvba_match_set_depth(lvba_match_t m, lvba_depth_t depth);
+int32_t lvba_match_points(lvba_match_t m, double *world);
 
 #ifdef __cplusplus
 }

@@ -1,12 +1,14 @@
 """Descriptor-matching timings: lvba_match_pairs on synthetic SIFT-like descriptors, few large pairs against many small ones,
-unguided and guided, beside the numpy restatement on a pair of the same size.
+unguided, guided by the epipolar line and guided by LiDAR depth, beside the numpy restatement on a pair of the same size.
 
     python tools/match_bench.py [--sizes 2048 8192 32768] [--small 256] [--small-pairs 2000] [--repeat 3] [--oracle-size 2048]
 
 Prints one JSON line.  Times are the host clock around calls that end in a device synchronise and include the copy of the matches
 to the host (best of --repeat, after a warm-up call).  "tmacs" counts n_a n_b 128 integer multiply-adds per ordered scan, two
 scans per pair when mutual.  "oracle_ms" is tests/match_oracle.py on one pair: a single-threaded numpy int64 matrix product and
-its arg-max, a restatement of the rule and not a tuned CPU matcher.  Needs a HIP device."""
+its arg-max, a restatement of the rule and not a tuned CPU matcher.  The depth images of the depth-guided column are synthetic: a
+plane 8 m before every camera, uploaded with lvba_depth_upload; "set_depth_ms" is the lifting of all keypoints through them
+(lvba_match_set_depth, once per pose set), which the column's own time does not include.  Needs a HIP device."""
 import argparse
 import importlib
 import json
@@ -54,15 +56,17 @@ def images(n_images, n, seed):
     Rcw = np.tile(np.eye(3), (n_images, 1, 1))
     tcw = np.array([[-0.4 * v, 0, 0] for v in range(n_images)], np.float64)
     intr = intr.copy(); intr[4:] = 0.0
-    return descs, kps, intr, Rcw, tcw
+    return descs, kps, intr, Rcw, tcw, np.full((n_images, H, W), 8.0, np.float32)
 
 
 def run(M, n_images, n, pairs, repeat, seed):
-    descs, kps, intr, Rcw, tcw = images(n_images, n, seed)
+    V = importlib.import_module("global-lvba_amd.visual")
+    descs, kps, intr, Rcw, tcw, planes = images(n_images, n, seed)
     out = {"n_images": n_images, "descriptors_per_image": n, "n_pairs": len(pairs)}
-    with M.Matcher(descs) as m:
+    with M.Matcher(descs) as m, V.DepthImages.upload(planes) as depth:
         m.set_geometry(kps, intr, Rcw, tcw)
-        for name, kw in (("unguided", {}), ("guided", {"guided": 1}), ("unguided_one_sided", {"mutual": 0})):
+        out["set_depth_ms"] = best_ms(lambda: m.set_depth(depth), repeat)
+        for name, kw in (("unguided", {}), ("guided", {"guided": 1}), ("depth_guided", {"guided": 2}), ("unguided_one_sided", {"mutual": 0})):
             count = [0]
 
             def call():
