@@ -37,6 +37,7 @@ SYMBOLS = [
     "lvba_posegraph_default_opts", "lvba_posegraph_relax",
     "lvba_match_default_opts", "lvba_match_create", "lvba_match_destroy", "lvba_match_set_geometry", "lvba_match_pairs",
     "lvba_match_scan", "lvba_match_set_depth", "lvba_match_points",
+    "lvba_covis_default_opts", "lvba_covis_samples", "lvba_covis_counts", "lvba_covis_pairs",
 ]
 
 OK, ERR_ARG, ERR_DEVICE, ERR_NOMEM, ERR_UNSUPPORTED, ERR_DIST, ERR_STATE = 0, -1, -2, -3, -4, -5, -6
@@ -211,6 +212,13 @@ class MatchOpts(C.Structure):
     """lvba_match_opts"""
     _fields_ = [("max_distance", C.c_double), ("max_ratio", C.c_double), ("mutual", C.c_int32), ("guided", C.c_int32),
                 ("max_epipolar_px", C.c_double), ("max_reproj_px", C.c_double)]
+
+
+class CovisOpts(C.Structure):
+    """lvba_covis_opts"""
+    _fields_ = [("grid_x", C.c_int32), ("grid_y", C.c_int32), ("search_radius", C.c_int32), ("occlusion", C.c_int32),
+                ("both_ways", C.c_int32), ("max_per_image", C.c_int32), ("min_shared", C.c_int32), ("reserved", C.c_int32),
+                ("min_overlap", C.c_double), ("occlusion_rel", C.c_double), ("occlusion_abs", C.c_double)]
 
 
 class VoxelOpts(C.Structure):
@@ -440,6 +448,12 @@ def load():
     lib.lvba_match_scan.argtypes = [H, C.c_int32, C.c_int32, C.POINTER(MatchOpts), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.lvba_match_set_depth.argtypes = [H, C.c_void_p]
     lib.lvba_match_points.argtypes = [H, C.c_void_p]
+    lib.lvba_covis_default_opts.argtypes = [C.POINTER(CovisOpts)]
+    lib.lvba_covis_default_opts.restype = None
+    lib.lvba_covis_samples.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CovisOpts), C.c_void_p]
+    lib.lvba_covis_counts.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CovisOpts), C.c_void_p, C.c_void_p]
+    lib.lvba_covis_pairs.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CovisOpts), C.c_int64, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]
     lib.lvba_scans_info.argtypes = [H, C.POINTER(C.c_int32), C.c_void_p]
     lib.lvba_scans_download.argtypes = [H, C.c_int32, np.ctypeslib.ndpointer(np.float32, flags="C")]
     for name in SYMBOLS:

@@ -605,10 +605,31 @@ def match_image_pairs(descriptors, pairs, keypoints=None, Rcw=None, tcw=None, in
     return M.match_pairs(descriptors, pairs, keypoints=keypoints, intr=intr, Rcw=Rcw, tcw=tcw, device=device, depth=depth, **opts)
 
 
+def select_image_pairs(depth, Rcw, tcw, intr, sequential=0, **opts):
+    """Which image pairs to match (covis.select_pairs) instead of all M (M - 1) / 2: the pairs in which one image
+    sees enough of what the other sees, judged on a grid of samples lifted through the LiDAR depth images (a visual.DepthImages
+    rendered at the poses Rcw, tcw = T_cam<-world), occlusion by the other view's depth image included.  sequential = k > 0 adds,
+    on the host, every pair with |i - j| <= k: the neighbours in time of an image whose depth image is empty have no other way
+    in.  opts: covis.covis_opts' (grid_x, grid_y, search_radius, occlusion, both_ways, max_per_image, min_shared, min_overlap,
+    occlusion_rel, occlusion_abs).  Returns (pairs: a list of (i, j) with i < j, sorted; report: n_images, all_pairs, selected,
+    covisible -- the selection before the sequential pairs --, and empty_images, those without a single sample)."""
+    from . import covis as CV
+    M = depth.n_images
+    pairs, _, _ = CV.select_pairs(depth, Rcw, tcw, intr, **opts)
+    # the images without a sample, from the lifted table alone: the lift kernel and M G 24 bytes back, a third of what a second
+    # pass of the count kernel for n_points would take
+    no_sample = np.isnan(CV.samples(depth, Rcw, tcw, intr, **opts)[:, :, 0]).all(axis=1)
+    chosen = {(int(i), int(j)) for i, j in pairs}
+    chosen |= {(i, j) for i in range(M) for j in range(i + 1, min(M, i + int(sequential) + 1))}
+    report = dict(n_images=M, all_pairs=M * (M - 1) // 2, selected=len(chosen), covisible=len(pairs),
+                  empty_images=[int(i) for i in np.flatnonzero(no_sample)])
+    return sorted(chosen), report
+
+
 def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, tci, intr, width, height, keypoints, pairs,
                       matches, enable_lidar_ba=True, enable_visual_ba=True, device=0, images=None, lidar_priors=None,
                       window_loss=None, stage_loss=None, camera_priors=None, map_quality=False, loop_closures=None, relax=None,
-                      match_fn=None, match_depth=False, **cfg):
+                      match_fn=None, match_depth=False, match_select=None, **cfg):
     """LvbaSystem::runFullPipeline (src/lvba_system.cpp:136-142) on in-memory data: clouds = body-frame [n_i, >=3] float32
     arrays, poses [n,12] = x_buf_ (T_world<-imu), image_poses [m,12] the image poses from the odometry.  cfg: DEFAULTS' keys
     (visual_loss, colorize_leaf among them).  images: None, or the images ([m,H,W,3] BGR uint8 or a callable k -> [H,W,3]):
@@ -631,9 +652,15 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
     matching, match_image_pairs) and replace the arguments; the output holds pairs / matches as used.
     match_depth: False, or True (only with match_fn): the depth images of the visual stage are rendered once, at the LiDAR-refined
     poses, before the matching; match_fn is called as match_fn(cam_poses, depth=depth) (depth-guided matching: hand it on to
-    match_image_pairs) and the visual stage uses the same images, which are closed here."""
+    match_image_pairs) and the visual stage uses the same images, which are closed here.
+    match_select: None (off), True, or a dict of select_image_pairs' keywords (only with match_fn): the depth images are rendered
+    once as under match_depth, the image pairs to match are selected from them (select_image_pairs), match_fn is called with
+    pairs=selected (and depth=depth when match_depth is set), and the output holds pair_selection, the report."""
     if images is not None and not enable_visual_ba:
         raise ValueError("colouring the map needs the cameras of the visual stage (enable_visual_ba=True)")
+    if match_select and (match_fn is None or not enable_visual_ba):
+        raise ValueError("match_select selects the pairs that match_fn is handed before the visual stage: it needs match_fn and "
+                         "enable_visual_ba=True")
     c = dict(DEFAULTS); c.update(cfg)
     x_orig = np.asarray(poses, np.float64).reshape(-1, 12).copy()
     out = dict(poses_before=x_orig)
@@ -652,13 +679,17 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
         try:
             if enable_visual_ba and match_fn is not None:
                 cam_poses = update_camera_poses_from_lidar(out["poses"], x_orig, scan_times, image_times, image_poses)
-                if match_depth:
+                kw = {}
+                if match_depth or match_select:
                     Rcw, tcw = camera_from_imu(cam_poses, Rci, tci)
                     depth = V.DepthImages.render(scans, out["poses"], scan_times, image_times, Rcw, tcw, intr, width, height,
                                                  half_window_s=c["depth_half_window_s"], voxel_size=c["depth_voxel"])
-                    pairs, matches = match_fn(cam_poses, depth=depth)
-                else:
-                    pairs, matches = match_fn(cam_poses)
+                    if match_select:
+                        kw["pairs"], out["pair_selection"] = select_image_pairs(
+                            depth, Rcw, tcw, intr, **(dict(match_select) if isinstance(match_select, dict) else {}))
+                    if match_depth:
+                        kw["depth"] = depth
+                pairs, matches = match_fn(cam_poses, **kw)
                 out["pairs"], out["matches"] = pairs, matches
             if enable_visual_ba:
                 out["visual"] = run_visual_ba_with_lidar_assist(scans, out["poses"], x_orig, scan_times, image_times, image_poses, Rci,
@@ -712,7 +743,7 @@ def extrinsics_from_config(Rcl, Pcl, extrinsic_R, extrinsic_T):
 
 def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrinsic_R=np.eye(3), extrinsic_T=np.zeros(3),
                 image_sample_step=1, out_dir=None, device=0, colorize=False, map_quality=False, loop_closures=None, relax=None,
-                matching="db", match_opts=None, **cfg):
+                matching="db", match_opts=None, pair_selection=None, **cfg):
     """initFromDatasetIO + runFullPipeline on a dataset directory; with out_dir, the refined LiDAR poses (TUM) and the COLMAP
     text files images.txt / points3D.txt the reference writes (src/lvba_system.cpp:2018-2137) are saved there.  images.txt is
     the reference's, character for character (tests/test_ref_system.py).
@@ -735,10 +766,15 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
     one place where the order differs from the reference's.  "depth": as "guided", but the gate is the point the LiDAR depth image
     of the keypoint's own view predicts in the other view (match_image_pairs' depth; run_full_pipeline's match_depth): it also
     separates copies of a texture along the epipolar line.  match_opts: match_image_pairs' options for the last three.
+    pair_selection: None (all pairs, as the reference), True, or a dict of select_image_pairs' keywords; only with "guided" or
+    "depth", where refined poses and depth images exist before the matching (run_full_pipeline's match_select): only the pairs
+    selected from LiDAR co-visibility are matched; the output gains pair_selection and out_dir gets pair_selection.json.
     cfg as for run_full_pipeline, e.g. visual_loss=REFERENCE_HUBER, window_loss=("cauchy", 0.1), stage_loss=("huber", 0.05),
     camera_priors=lambda cams: lidar_camera_priors(cams, Rci, tci, 1e-3, 0.02)."""
     import os
     from . import dataset as D
+    if pair_selection and matching not in ("guided", "depth"):
+        raise ValueError(f"pair_selection needs matching='guided' or 'depth' (refined poses and depth images before the matching), not {matching!r}")
     ds = D.load_dataset(data_path)
     img_dir = os.path.join(data_path, "all_image")
     image_ids = list_image_ids(img_dir, image_sample_step)
@@ -752,7 +788,7 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
     if matching not in ("db", "descriptors", "guided", "depth"):
         raise ValueError(f"matching={matching!r}: one of 'db', 'descriptors', 'guided', 'depth'")
     Rci, tci = extrinsics_from_config(Rcl, Pcl, extrinsic_R, extrinsic_T)
-    match_fn = None
+    match_fn, all_pairs = None, pairs
     if matching != "db":
         descs = D.load_colmap_descriptors(colmap_db_path if os.path.isabs(colmap_db_path) else os.path.join(data_path, colmap_db_path),
                                           names)
@@ -761,17 +797,19 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
         if matching == "descriptors":
             matches = match_image_pairs(descs, pairs, device=device, **(match_opts or {}))
         else:
-            def match_fn(cam_poses, depth=None):
+            def match_fn(cam_poses, depth=None, pairs=None):
+                use = all_pairs if pairs is None else pairs
                 Rcw, tcw = camera_from_imu(cam_poses, Rci, tci)
-                m = match_image_pairs(descs, pairs, keypoints=[k[:, :2] for k in kps], Rcw=Rcw, tcw=tcw, intr=intr, device=device,
+                m = match_image_pairs(descs, use, keypoints=[k[:, :2] for k in kps], Rcw=Rcw, tcw=tcw, intr=intr, device=device,
                                       depth=depth, **(match_opts or {}))
                 kept = [k for k, mm in enumerate(m) if len(mm)]
-                return [pairs[k] for k in kept], [m[k] for k in kept]
+                return [use[k] for k in kept], [m[k] for k in kept]
     keep = [k for k, m in enumerate(matches) if len(m)]
     out = run_full_pipeline([c[:, :3] for c in ds["clouds"]], ds["poses"], ds["timestamps"], image_ids, image_poses, Rci, tci, intr,
                             width, height, [k[:, :2] for k in kps], [pairs[k] for k in keep], [matches[k] for k in keep],
                             device=device, **({"match_fn": match_fn} if match_fn is not None else {}),
-                            **({"match_depth": True} if matching == "depth" else {}), images=(lambda k: D.read_image_bgr(os.path.join(img_dir, names[k]), width, height))
+                            **({"match_depth": True} if matching == "depth" else {}),
+                            **({"match_select": pair_selection} if pair_selection else {}), images=(lambda k: D.read_image_bgr(os.path.join(img_dir, names[k]), width, height))
                             if colorize else None, **({"map_quality": map_quality} if map_quality else {}),
                             **({"loop_closures": loop_closures} if loop_closures else {}),
                             **({"relax": relax} if relax and loop_closures else {}), **cfg)
@@ -798,6 +836,10 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
             import json
             with open(os.path.join(out_dir, "loop_closures.json"), "w") as f:
                 json.dump([{a: b for a, b in r.items() if not isinstance(b, np.ndarray)} for r in out["loop_closures"]], f, indent=1)
+        if "pair_selection" in out:
+            import json
+            with open(os.path.join(out_dir, "pair_selection.json"), "w") as f:
+                json.dump(out["pair_selection"], f, indent=1)
         if "pose_graph" in out:
             import json
             with open(os.path.join(out_dir, "pose_graph.json"), "w") as f:

@@ -1117,6 +1117,59 @@ int32_t lvba_match_scan(lvba_match_t m, int32_t a, int32_t b, const lvba_match_o
 int32_t lvba_match_set_depth(lvba_match_t m, lvba_depth_t depth);
 int32_t lvba_match_points(lvba_match_t m, double *world);
 
+/* ---- which image pairs to match, from LiDAR co-visibility (opt-in)
+ *   The reference matches all M (M - 1) / 2 image pairs (image_pairs_, src/lvba_system.cpp:462-466).  After the LiDAR stage the
+ *   camera poses and one LiDAR depth image per camera are on the device, so "does image j see what image i sees" is a question
+ *   about geometry that is already there, occlusion included.  The rule is this project's own; a numpy oracle restates it.
+ *   Inputs: a depth set of M images of W x H pixels, Rcw [M][9] row-major and tcw [M][3] (T_cam<-world), intr = (fx, fy, cx, cy,
+ *   k1, k2, p1, p2).  Every expression in fp64 unless it says float, every sum left to right, no fused multiply-add.
+ *   Samples.  Image i gets G = grid_x grid_y cells, sample s = gy grid_x + gx.  The cell's centre pixel is
+ *     px = ((2 gx + 1) (W - 1)) / (2 grid_x),  py = ((2 gy + 1) (H - 1)) / (2 grid_y)   in integer division, so 0 <= px <= W - 2.
+ *     Candidates: the centre, then the Chebyshev rings r = 1 .. search_radius around it, each ring walked dy = -r .. r and inside
+ *     that dx = -r .. r, keeping only |dx| = r or |dy| = r.  A candidate outside [0, W - 2] x [0, H - 2] is skipped.  The first
+ *     candidate (u, v) for which the undistortion of the pixel ((double)(float)u, (double)(float)v) succeeds, the depth image of i
+ *     has a return there (fetchDepthBilinear at the float pixel: all four neighbours > 0) and the world point
+ *     X = camToWorld((x d, y d, d)) is finite -- the expressions of lvba_fuse_tracks and of the matcher's depth gate -- is the
+ *     cell's sample.  If no candidate succeeds the cell HAS NO POINT (a NaN row).  n_i = the cells of image i with a point.  The
+ *     search exists because rendered LiDAR depth images have holes.
+ *   Seen.  For an ordered pair (i, j), i != j, sample s of i is SEEN IN j iff it has a point, the projection of X under (R_j, t_j)
+ *     (projectCameraToPixel: Z > 1e-12, all finite) succeeds, its pixel (u^, v^) has 0 <= u^ < W - 1 and 0 <= v^ < H - 1, and,
+ *     with occlusion on, it is not HIDDEN: hidden iff fetchDepthBilinear of depth image j at ((float)u^, (float)v^) succeeds with
+ *     depth d and  Z > (double)d * (1.0 + occlusion_rel) + occlusion_abs,  Z = R_j[6] X[0] + R_j[7] X[1] + R_j[8] X[2] + t_j[2].
+ *     A fetch that fails is a hole in j: no evidence of occlusion, the sample counts as seen.
+ *     c_ij = the samples of i seen in j;  c_ii = 0.
+ *   Score.  r_ij = c_ij / n_i (0 when n_i = 0).  For i < j: score = max(r_ij, r_ji), shared = max(c_ij, c_ji); with both_ways
+ *     both take the min.  The pair is ELIGIBLE iff shared >= min_shared and score >= min_overlap.
+ *   Cap.  With max_per_image = K > 0 the partners of image i among its eligible pairs are ranked by (score descending, partner
+ *     index ascending); an eligible pair is kept iff its partner rank is < K for i or for j.  K = 0 keeps every eligible pair.
+ *   Output: the kept pairs (i, j), i < j, sorted by (i, j); score [capacity] and shared [capacity][2] = (c_ij, c_ji) may be NULL.
+ *   *count is the true number even above capacity; only the first `capacity` entries are written.  No atomics: two calls give the
+ *   same bytes.  The three calls run on the depth set's device and only read it; each lifts the samples itself.
+ *   The samples call gives world [M][G][3], the counts call n_points [M] and counts [M][M].  Options: NULL takes the defaults.
+ *   LVBA_ERR_ARG: a null required pointer, a non-finite pose or intrinsic, an option outside its range below, grid_x > W - 1 or
+ *   grid_y > H - 1, capacity < 0, capacity > 0 with pairs NULL.  LVBA_ERR_UNSUPPORTED: M > 8192 (the count matrix would pass
+ *   256 MB).  M = 0 and M = 1 give *count = 0.  A refused call writes nothing.  The defaults were chosen on synthetic scenes only.
+ *   lvba_version() is unchanged; a client detects these calls by looking lvba_covis_pairs up. */
+typedef struct lvba_covis_opts {
+    int32_t grid_x, grid_y;      /* 1 .. 64 each, <= W - 1 / H - 1 (defaults 16, 12) */
+    int32_t search_radius;       /* 0 .. 16 (default 4) */
+    int32_t occlusion;           /* 0 or 1 (default 1) */
+    int32_t both_ways;           /* 0 or 1 (default 0) */
+    int32_t max_per_image;       /* 0 = no cap, else 1 .. 1024 (default 0) */
+    int32_t min_shared;          /* samples, >= 0 (default 8) */
+    int32_t reserved;
+    double min_overlap;          /* finite, 0 .. 1 (default 0.1) */
+    double occlusion_rel, occlusion_abs;  /* finite, >= 0 (defaults 0.05, 0.1 m) */
+} lvba_covis_opts;               /* 56 bytes */
+void    lvba_covis_default_opts(lvba_covis_opts *o);
+int32_t lvba_covis_samples(lvba_depth_t depth, const double *Rcw, const double *tcw, const double intr[8],
+                           const lvba_covis_opts *o, double *world /* [M][G][3], NaN = none */);
+int32_t lvba_covis_counts(lvba_depth_t depth, const double *Rcw, const double *tcw, const double intr[8],
+                          const lvba_covis_opts *o, int32_t *n_points /* [M] */, int32_t *counts /* [M][M] */);
+int32_t lvba_covis_pairs(lvba_depth_t depth, const double *Rcw, const double *tcw, const double intr[8],
+                         const lvba_covis_opts *o, int64_t capacity, int32_t *pairs, double *score, int32_t *shared,
+                         int64_t *count);
+
 #ifdef __cplusplus
 }
 #endif
