@@ -38,6 +38,7 @@ SYMBOLS = [
     "lvba_match_default_opts", "lvba_match_create", "lvba_match_destroy", "lvba_match_set_geometry", "lvba_match_pairs",
     "lvba_match_scan", "lvba_match_set_depth", "lvba_match_points",
     "lvba_covis_default_opts", "lvba_covis_samples", "lvba_covis_counts", "lvba_covis_pairs",
+    "lvba_trackgraph_create", "lvba_trackgraph_components", "lvba_trackgraph_orders", "lvba_trackgraph_destroy",
 ]
 
 OK, ERR_ARG, ERR_DEVICE, ERR_NOMEM, ERR_UNSUPPORTED, ERR_DIST, ERR_STATE = 0, -1, -2, -3, -4, -5, -6
@@ -219,6 +220,16 @@ class CovisOpts(C.Structure):
     _fields_ = [("grid_x", C.c_int32), ("grid_y", C.c_int32), ("search_radius", C.c_int32), ("occlusion", C.c_int32),
                 ("both_ways", C.c_int32), ("max_per_image", C.c_int32), ("min_shared", C.c_int32), ("reserved", C.c_int32),
                 ("min_overlap", C.c_double), ("occlusion_rel", C.c_double), ("occlusion_abs", C.c_double)]
+
+
+class TrackGraphInfo(C.Structure):
+    """lvba_trackgraph_info"""
+    _fields_ = [("n_nodes", C.c_int64), ("n_edges", C.c_int64), ("n_skipped", C.c_int64), ("n_components_all", C.c_int64),
+                ("n_components", C.c_int64), ("n_observations", C.c_int64), ("largest_component", C.c_int64),
+                ("cc_rounds", C.c_int32), ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_ if f != "reserved"}
 
 
 class VoxelOpts(C.Structure):
@@ -454,6 +465,11 @@ def load():
     lib.lvba_covis_counts.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CovisOpts), C.c_void_p, C.c_void_p]
     lib.lvba_covis_pairs.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CovisOpts), C.c_int64, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p]
+    lib.lvba_trackgraph_create.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                           C.POINTER(H), C.POINTER(TrackGraphInfo)]
+    lib.lvba_trackgraph_components.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.lvba_trackgraph_orders.argtypes = [H, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.lvba_trackgraph_destroy.argtypes = [H]
     lib.lvba_scans_info.argtypes = [H, C.POINTER(C.c_int32), C.c_void_p]
     lib.lvba_scans_download.argtypes = [H, C.c_int32, np.ctypeslib.ndpointer(np.float32, flags="C")]
     for name in SYMBOLS:

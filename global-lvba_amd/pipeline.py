@@ -170,14 +170,70 @@ def build_components(n_keypoints, pairs, matches, obser_thr=3):
     return np.asarray(off, np.int64), np.asarray(img, np.int32), np.asarray(kp, np.int32)
 
 
-def build_tracks_and_fuse(keypoints, pairs, matches, fuse_fn, obser_thr=3):
+def build_components_device(n_keypoints, pairs, matches, obser_thr=3, device=0):
+    """build_components with the graph, its components and the BFS orders made on the GPU (trackgraph.TrackGraph; DESIGN.md
+    §10j): the same three arrays."""
+    from . import trackgraph as TG
+    with TG.TrackGraph([int(n) for n in n_keypoints], pairs, matches, obser_thr, device=device) as g:
+        return g.orders()
+
+
+def _csr_take(off, which):
+    """positions of the entries of the CSR rows `which`, row after row, and the rows' lengths"""
+    lens = (off[1:] - off[:-1])[which]
+    first = np.repeat(off[:-1][which] - (np.cumsum(lens) - lens), lens)
+    return first + np.arange(int(lens.sum()), dtype=np.int64), lens
+
+
+def _tracks_on_device(keypoints, pairs, matches, fuse_fn, obser_thr, device=0):
+    """build_tracks_and_fuse(device_tracks=True): the graph is built once on the device, every round's orders come from
+    TrackGraph.orders(pending, attempt, uv=True); the bookkeeping is numpy on whole arrays."""
+    from . import trackgraph as TG
+    rounds = []                                     # per round, of its accepted components: dict of arrays
+    with TG.TrackGraph(keypoints, pairs, matches, obser_thr, device=device) as g:
+        sizes = np.diff(g.components()[0])
+        comp_status = np.zeros(len(sizes), np.uint8)
+        pending, attempt = np.arange(len(sizes), dtype=np.int64), 0
+        while len(pending):
+            off, img, kp, uv = g.orders(pending, attempt, uv=True)
+            status, X, err, kept = fuse_fn(off, img, uv)
+            status = np.asarray(status)
+            ok = status != 0
+            comp_status[pending[ok]] = status[ok]
+            if ok.any():
+                won = np.flatnonzero(ok)
+                obs, lens = _csr_take(off, won)
+                rounds.append(dict(start_img=img[off[:-1][won]], start_kp=kp[off[:-1][won]], lens=lens, img=img[obs], kp=kp[obs], uv=uv[obs],
+                                   kept=np.asarray(kept)[obs], X=np.asarray(X, np.float64).reshape(-1, 3)[won], err=np.asarray(err, np.float64)[won],
+                                   status=status[won], attempts=np.full(len(won), attempt, np.int32)))
+            pending = pending[~ok & (attempt + 1 < sizes[pending])]
+            attempt += 1
+
+    def cat(key, empty):
+        return np.concatenate([r[key] for r in rounds]) if rounds else empty
+    lens = cat("lens", np.zeros(0, np.int64))
+    by_start = np.lexsort((cat("start_kp", np.zeros(0, np.int32)), cat("start_img", np.zeros(0, np.int32))))   # the reference's order
+    off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    obs, lens = _csr_take(off, by_start)
+    return dict(obs_off=np.concatenate([[0], np.cumsum(lens)]).astype(np.int64), obs_img=cat("img", np.zeros(0, np.int32))[obs],
+                obs_kp=cat("kp", np.zeros(0, np.int32))[obs], obs_uv=cat("uv", np.zeros((0, 2), np.float32))[obs],
+                kept=cat("kept", np.zeros(0, np.uint8))[obs].astype(np.uint8), X=cat("X", np.zeros((0, 3)))[by_start],
+                err=cat("err", np.zeros(0))[by_start], status=cat("status", np.zeros(0, np.uint8))[by_start].astype(np.uint8),
+                attempts=cat("attempts", np.zeros(0, np.int32))[by_start], component_status=comp_status)
+
+
+def build_tracks_and_fuse(keypoints, pairs, matches, fuse_fn, obser_thr=3, device_tracks=False):
     """The track loop of BuildTracksAndFuse3D (src/lvba_system.cpp:954-1246) with the per-component fusion batched:
     fuse_fn(obs_off, obs_img, obs_uv) -> (status, X, err, kept) is lvba_fuse_tracks on the GPU.  A component the fusion drops is
     released by the reference (:1197, :1203) and met again at its next member in scan order, i.e. fused again in another BFS
     order; round r of the loop below fuses, in one batch, the r-th attempt of every component that is still dropped.  Tracks
     come out in the reference's order (by the key point their successful BFS started from).
     Returns dict(obs_off, obs_img, obs_kp, obs_uv, kept: CSR arrays of the tracks; X, err, status: per track; component_status:
-    per component (0 = dropped after all attempts), attempts: per track, 0-based)."""
+    per component (0 = dropped after all attempts), attempts: per track, 0-based).
+    device_tracks=True: the match graph, its components and every round's BFS orders are made on the GPU instead
+    of by the Python mirror below; the returned dict is the same, key for key."""
+    if device_tracks:
+        return _tracks_on_device(keypoints, pairs, matches, fuse_fn, obser_thr)
     nk = [len(k) for k in keypoints]
     adj, comps = match_components(nk, pairs, matches, obser_thr)
     comp_status = np.zeros(len(comps), np.uint8)
@@ -213,7 +269,7 @@ def build_tracks_and_fuse(keypoints, pairs, matches, fuse_fn, obser_thr=3):
 
 
 def run_visual_ba_with_lidar_assist(scans, x_opt, x_orig, scan_times, image_times, image_poses, Rci, tci, intr, width, height,
-                                    keypoints, pairs, matches, camera_priors=None, depth=None, **cfg):
+                                    keypoints, pairs, matches, camera_priors=None, depth=None, device_tracks=False, **cfg):
     """LvbaSystem::runVisualBAWithLidarAssist (src/lvba_system.cpp:144-154) from the refined LiDAR poses to the refined
     cameras.  scans: a voxel.Scans holding the raw clouds; keypoints[i] = [n_i, 2] float pixel coordinates; pairs / matches as
     build_tracks takes them.  cfg["visual_loss"]: see DEFAULTS.  camera_priors: None (the reference's problem), a list of
@@ -221,6 +277,7 @@ def run_visual_ba_with_lidar_assist(scans, x_opt, x_orig, scan_times, image_time
     (T_world<-imu) that only exist inside this call (e.g. lambda cams: lidar_camera_priors(cams, Rci, tci, 1e-3, 0.02)).
     depth: None (the depth images are rendered here), or a visual.DepthImages already rendered with these arguments
     (as run_full_pipeline does under match_depth): it is used as it is and stays the caller's to close.
+    device_tracks: build_tracks_and_fuse's (the track graph on the GPU; off by default).
     Returns a dict (cameras before / after, tracks, landmarks, planes, traces)."""
     c = dict(DEFAULTS); c.update(cfg)
     cam_new = update_camera_poses_from_lidar(x_opt, x_orig, scan_times, image_times, image_poses)      # poses_
@@ -236,7 +293,8 @@ def run_visual_ba_with_lidar_assist(scans, x_opt, x_orig, scan_times, image_time
         T = build_tracks_and_fuse(keypoints, pairs, matches,
                                   lambda o, i, u: V.fuse_tracks(o, i, u, Rcw, tcw, intr, depth=depth, obser_thr=c["obser_thr"],
                                                                 min_view_angle_deg=c["min_view_angle_deg"],
-                                                                reproj_mean_thr_px=c["reproj_mean_thr_px"]), c["obser_thr"])
+                                                                reproj_mean_thr_px=c["reproj_mean_thr_px"]), c["obser_thr"],
+                                  device_tracks=device_tracks)
     finally:
         if own_depth:
             depth.close()
@@ -629,7 +687,7 @@ def select_image_pairs(depth, Rcw, tcw, intr, sequential=0, **opts):
 def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, tci, intr, width, height, keypoints, pairs,
                       matches, enable_lidar_ba=True, enable_visual_ba=True, device=0, images=None, lidar_priors=None,
                       window_loss=None, stage_loss=None, camera_priors=None, map_quality=False, loop_closures=None, relax=None,
-                      match_fn=None, match_depth=False, match_select=None, **cfg):
+                      match_fn=None, match_depth=False, match_select=None, device_tracks=False, **cfg):
     """LvbaSystem::runFullPipeline (src/lvba_system.cpp:136-142) on in-memory data: clouds = body-frame [n_i, >=3] float32
     arrays, poses [n,12] = x_buf_ (T_world<-imu), image_poses [m,12] the image poses from the odometry.  cfg: DEFAULTS' keys
     (visual_loss, colorize_leaf among them).  images: None, or the images ([m,H,W,3] BGR uint8 or a callable k -> [H,W,3]):
@@ -655,7 +713,8 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
     match_image_pairs) and the visual stage uses the same images, which are closed here.
     match_select: None (off), True, or a dict of select_image_pairs' keywords (only with match_fn): the depth images are rendered
     once as under match_depth, the image pairs to match are selected from them (select_image_pairs), match_fn is called with
-    pairs=selected (and depth=depth when match_depth is set), and the output holds pair_selection, the report."""
+    pairs=selected (and depth=depth when match_depth is set), and the output holds pair_selection, the report.
+    device_tracks: False, or True: the visual stage builds its tracks on the GPU (run_visual_ba_with_lidar_assist's device_tracks)."""
     if images is not None and not enable_visual_ba:
         raise ValueError("colouring the map needs the cameras of the visual stage (enable_visual_ba=True)")
     if match_select and (match_fn is None or not enable_visual_ba):
@@ -695,7 +754,7 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
                 out["visual"] = run_visual_ba_with_lidar_assist(scans, out["poses"], x_orig, scan_times, image_times, image_poses, Rci,
                                                                 tci, intr, width, height, keypoints, pairs, matches,
                                                                 camera_priors=camera_priors, **({"depth": depth} if depth is not None else {}),
-                                                                **c)
+                                                                **({"device_tracks": True} if device_tracks else {}), **c)
         finally:
             if depth is not None:
                 depth.close()
@@ -743,7 +802,7 @@ def extrinsics_from_config(Rcl, Pcl, extrinsic_R, extrinsic_T):
 
 def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrinsic_R=np.eye(3), extrinsic_T=np.zeros(3),
                 image_sample_step=1, out_dir=None, device=0, colorize=False, map_quality=False, loop_closures=None, relax=None,
-                matching="db", match_opts=None, pair_selection=None, **cfg):
+                matching="db", match_opts=None, pair_selection=None, device_tracks=False, **cfg):
     """initFromDatasetIO + runFullPipeline on a dataset directory; with out_dir, the refined LiDAR poses (TUM) and the COLMAP
     text files images.txt / points3D.txt the reference writes (src/lvba_system.cpp:2018-2137) are saved there.  images.txt is
     the reference's, character for character (tests/test_ref_system.py).
@@ -769,6 +828,8 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
     pair_selection: None (all pairs, as the reference), True, or a dict of select_image_pairs' keywords; only with "guided" or
     "depth", where refined poses and depth images exist before the matching (run_full_pipeline's match_select): only the pairs
     selected from LiDAR co-visibility are matched; the output gains pair_selection and out_dir gets pair_selection.json.
+    device_tracks: False, or True: the feature tracks are built on the GPU (run_full_pipeline's device_tracks) -- worth it where
+    the matcher delivers matches by the million.
     cfg as for run_full_pipeline, e.g. visual_loss=REFERENCE_HUBER, window_loss=("cauchy", 0.1), stage_loss=("huber", 0.05),
     camera_priors=lambda cams: lidar_camera_priors(cams, Rci, tci, 1e-3, 0.02)."""
     import os
@@ -809,7 +870,8 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
                             width, height, [k[:, :2] for k in kps], [pairs[k] for k in keep], [matches[k] for k in keep],
                             device=device, **({"match_fn": match_fn} if match_fn is not None else {}),
                             **({"match_depth": True} if matching == "depth" else {}),
-                            **({"match_select": pair_selection} if pair_selection else {}), images=(lambda k: D.read_image_bgr(os.path.join(img_dir, names[k]), width, height))
+                            **({"match_select": pair_selection} if pair_selection else {}),
+                            **({"device_tracks": True} if device_tracks else {}), images=(lambda k: D.read_image_bgr(os.path.join(img_dir, names[k]), width, height))
                             if colorize else None, **({"map_quality": map_quality} if map_quality else {}),
                             **({"loop_closures": loop_closures} if loop_closures else {}),
                             **({"relax": relax} if relax and loop_closures else {}), **cfg)

@@ -1170,6 +1170,63 @@ int32_t lvba_covis_pairs(lvba_depth_t depth, const double *Rcw, const double *tc
                          const lvba_covis_opts *o, int64_t capacity, int32_t *pairs, double *score, int32_t *shared,
                          int64_t *count);
 
+/* ---- feature tracks on the device: match-graph components in BFS order (opt-in)
+ *   The adjacency and BFS part of BuildTracksAndFuse3D (src/lvba_system.cpp:932-1014): what feeds lvba_fuse_tracks.  Every output
+ *   is a discrete structure with one right answer; the host mirror (pipeline.match_graph / match_components / bfs_order, pinned to
+ *   the reference by the tests) is the specification.
+ *   Nodes.  Images 0 .. M - 1, image i has n_i = kp_off[i + 1] - kp_off[i] key points; key point k of image i is node
+ *     v = kp_off[i] + k: node order is scan order (image, key point).
+ *   Pairs and matches.  pairs [n_pairs][2] = (a, b) in any order and either orientation; the matches of pair p are the rows
+ *     match_off[p] .. match_off[p + 1] of matches [][2] = (r in a, c in b) -- the arrays lvba_match_pairs writes.  A pair with
+ *     a > b is read with its columns swapped, as (lo, hi).  The pairs are ranked by a STABLE sort on (lo, hi): a pair listed twice
+ *     keeps the caller's order.
+ *   Edge sequence.  The sequence number of an edge is (rank of its pair, position inside the pair).  A match with an index < 0 or
+ *     >= the image's key point count is skipped and counted in n_skipped.
+ *   Adjacency.  The neighbours of a node are listed by ascending edge sequence, duplicates kept.
+ *   Components.  Connected components over the nodes with at least one edge.  A component QUALIFIES iff it has >= obser_thr members
+ *     and they lie in >= obser_thr distinct images.  Qualifying components are numbered by ascending smallest member; members(c)
+ *     are its nodes in ascending order.
+ *   Order.  order(c, attempt) is the FIFO BFS from members(c)[attempt]: a popped node's neighbours are visited in adjacency order,
+ *     a node is appended at its first visit.  attempt = 0 is the reference's first try; a component the fusion drops is met again
+ *     at its next member (:1197, :1203), i.e. attempt + 1.
+ *   lvba_trackgraph_create uploads once, builds everything up to the component table and leaves the adjacency and the tables
+ *   resident.  keypoints_uv [kp_off[M]][2] may be NULL (then no call may ask for obs_uv).  info may be NULL.
+ *   lvba_trackgraph_components: comp_off [n_components + 1], (mem_img, mem_kp) [n_observations] = members(c) of every component,
+ *   comp_images [n_components] (may be NULL) the distinct images of each.
+ *   lvba_trackgraph_orders: the orders of the n components comp[] (strictly ascending; NULL: all of them, n = n_components) for one
+ *   attempt, obs_off [n + 1] and (obs_img, obs_kp, obs_uv) sized by the caller from comp_off; obs_uv may be NULL.  May be called any
+ *   number of times; calls on one handle must not overlap (the visited marks are the handle's).
+ *   The component labels are found with atomicMin; their fixed point is unique (the smallest node of each component), so every
+ *   output is the same bytes on every call -- cc_rounds alone, the number of label rounds, is a diagnostic that may differ.
+ *   LVBA_ERR_ARG, with nothing written: a null required pointer, a negative count, kp_off or match_off that does not start at 0 or
+ *   decreases, a pair index outside the images, a == b, obser_thr < 1, comp not strictly ascending or out of range, attempt < 0 or
+ *   >= the size of a requested component, obs_uv of a graph created without key points.  LVBA_ERR_UNSUPPORTED: kp_off[M] >= 2^31 or
+ *   match_off[n_pairs] >= 2^30 (node and half-edge ids are 32 bits; checked before anything is read or allocated).
+ *   LVBA_ERR_STATE: the label rounds passed their cap of 64, or a walk did not end at its component's size (neither can happen
+ *   unless the library is wrong; every device loop is bounded, so such a fault is a code, not a hang).  M = 0, no pairs, no matches or
+ *   all matches skipped give a valid empty graph.  lvba_version() is unchanged; a client detects these calls by looking
+ *   lvba_trackgraph_create up. */
+typedef struct lvba_trackgraph_s *lvba_trackgraph_t;
+typedef struct lvba_trackgraph_info {
+    int64_t n_nodes;          /* nodes with at least one edge */
+    int64_t n_edges, n_skipped;
+    int64_t n_components_all; /* before the two size checks */
+    int64_t n_components, n_observations;   /* qualifying, and the sum of their sizes */
+    int64_t largest_component;              /* the size of the largest qualifying one */
+    int32_t cc_rounds, reserved;
+} lvba_trackgraph_info;          /* 64 bytes */
+int32_t lvba_trackgraph_create(int32_t device, int32_t n_images, const int64_t *kp_off /* [M+1], from 0 */,
+                               const float *keypoints_uv /* [kp_off[M]][2], may be NULL */,
+                               int64_t n_pairs, const int32_t *pairs, const int64_t *match_off, const int32_t *matches,
+                               int32_t obser_thr, lvba_trackgraph_t *out, lvba_trackgraph_info *info);
+int32_t lvba_trackgraph_components(lvba_trackgraph_t g, int64_t *comp_off /* [n_components+1] */,
+                                   int32_t *mem_img, int32_t *mem_kp /* [n_observations] */,
+                                   int32_t *comp_images /* [n_components] distinct images, may be NULL */);
+int32_t lvba_trackgraph_orders(lvba_trackgraph_t g, int64_t n, const int64_t *comp /* strictly ascending; NULL: all, n = n_components */,
+                               int32_t attempt, int64_t *obs_off /* [n+1] */, int32_t *obs_img, int32_t *obs_kp,
+                               float *obs_uv /* [.][2]; may be NULL; needs keypoints_uv */);
+int32_t lvba_trackgraph_destroy(lvba_trackgraph_t g);
+
 #ifdef __cplusplus
 }
 #endif
