@@ -702,6 +702,8 @@ bool bcr_applicable(int n_poses, int band_blocks)
     return n_poses >= 8 * bcr_block_cams(band_blocks);
 }
 
+int bcr_block_scalars(int band_blocks) { return bcr_pad(bcr_block_cams(band_blocks)); }
+
 int64_t bcr_workspace_doubles(int n_poses, int band_blocks)
 {
     if (!bcr_applicable(n_poses, band_blocks)) return 0;

@@ -323,6 +323,7 @@ void ldlt_cov_gather(const double *z, int64_t ld, int band_blocks, const int32_t
 
 // bcr.hip: block cyclic reduction for narrow-band SPD systems (the visual stage's reduced camera system)
 bool bcr_applicable(int n_poses, int band_blocks);
+int bcr_block_scalars(int band_blocks); // 32 or 64: the padded size of a block row (which kernel family solves)
 int64_t bcr_workspace_doubles(int n_poses, int band_blocks);
 void bcr_solve(const double *Hblk, int band_blocks, int n_poses, const double *g, const double *u_dev, double *x, double *work,
                int *status, hipStream_t s);

@@ -39,6 +39,7 @@ struct lvba_visual_s {
     int32_t loss_kind[2] = {0, 0}; // [0] reprojection, [1] plane: LVBA_LOSS_*; scale 0 on TRIVIAL
     double loss_scale[2] = {0.0, 0.0};
     bool finalized = false;
+    bool have_lin = false;         // bs holds the reduced system of an lvba_visual_linearize (lvba_visual_solve); a refine replaces it
     double intr[8] = {}, sig_px = 0.5, sig_pl = 0.01;
     // camera pose priors (lvba_visual_set_priors): as the caller gave them, and bound to the solver order (bind_priors)
     std::vector<lvba_prior> priors;
@@ -509,6 +510,26 @@ extern "C" int32_t lvba_visual_linearize(lvba_visual_t h, const double *q, const
     HIPCHK(hipStreamSynchronize(bs.stream));
     HIPCHK(hipGetLastError());
     if (cost) *cost = 0.5 * h->h_pin[0];
+    h->have_lin = true;
+    return LVBA_OK;
+}
+
+extern "C" int32_t lvba_visual_solve(lvba_visual_t h, double *x, int32_t *solver)
+{
+    if (!h || !x) return fail(LVBA_ERR_ARG, "NULL argument");
+    if (!h->finalized || !h->have_lin) return fail(LVBA_ERR_STATE, "lvba_visual_solve needs a prior lvba_visual_linearize");
+    BlockSys &bs = h->bs;
+    if (bs.distributed()) return fail(LVBA_ERR_STATE, "lvba_visual_solve is not available on a sharded handle");
+    HIPCHK(hipSetDevice(bs.device));
+    TRY(bs_enqueue_solve(bs, 0.0)); // the damping is in the system (the LM diagonal of the linearisation)
+    launch_export_vec(bs.d_dx, bs.d_perm, h->M, h->d_out, bs.stream);
+    HIPCHK(hipMemcpyAsync(x, h->d_out, (size_t)6 * h->M * sizeof(double), hipMemcpyDeviceToHost, bs.stream));
+    int st = 0;
+    HIPCHK(hipMemcpyAsync(&st, bs.d_status, sizeof(int), hipMemcpyDeviceToHost, bs.stream));
+    HIPCHK(hipStreamSynchronize(bs.stream));
+    HIPCHK(hipGetLastError());
+    if (solver) *solver = !bs.d_bcr ? 0 : bcr_block_scalars(bs.Bb) == 32 ? 1 : 2;
+    if (st) return fail(LVBA_NUM_FACTORIZATION, "zero or non-positive pivot in the reduced camera solve");
     return LVBA_OK;
 }
 
@@ -517,6 +538,7 @@ extern "C" int32_t lvba_visual_refine(lvba_visual_t h, double *q, double *t, dou
 {
     if (!h || !q || !t || !X) return fail(LVBA_ERR_ARG, "NULL argument");
     if (n_trace) *n_trace = 0;
+    h->have_lin = false;
     TRY(finalize(h));
     BlockSys &bs = h->bs;
     HIPCHK(hipSetDevice(bs.device));

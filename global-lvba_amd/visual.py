@@ -104,6 +104,13 @@ class VisualProblem:
                                                C.byref(c)))
         return S, rhs, c.value
 
+    def solve(self):
+        """(x [6M], solver): x = -S^-1 rhs of the last linearize() on this handle, solved with the kernels refine() would use;
+        solver 0 = LDL^T, 1 / 2 = block cyclic reduction with block rows of 32 / 64 scalars (lvba_visual_solve)."""
+        x, solver = np.empty(6 * self.n_cams), C.c_int32(-1)
+        L.check(self.lib.lvba_visual_solve(self._h, x, C.byref(solver)))
+        return x, solver.value
+
     def dist_init(self, n_ranks, rank, uid):
         """Track shards over several ranks (lvba_visual_dist_init): this handle holds the rank's own tracks."""
         L.check(self.lib.lvba_visual_dist_init(self._h, int(n_ranks), int(rank), bytes(uid)))

@@ -423,6 +423,13 @@ int32_t lvba_visual_cost(lvba_visual_t h, const double *q, const double *t, cons
 int32_t lvba_visual_linearize(lvba_visual_t h, const double *q, const double *t, const double *X, double radius,
                               double *S, double *rhs, double *cost);
 
+/* Solve the reduced camera system the last lvba_visual_linearize left on this handle, with the kernels a refinement would use:
+ * x [6M] = -S^-1 rhs in the scaled tangent variables, caller camera order (camera 0: zeros).  *solver (may be NULL) tells
+ * which kernels ran: 0 = LDL^T, 1 = block cyclic reduction with block rows of 32 scalars, 2 = with block rows of 64.
+ * LVBA_NUM_FACTORIZATION on a pivot <= 0; LVBA_ERR_STATE without a prior lvba_visual_linearize on the handle (an
+ * lvba_visual_refine in between replaces the system) and on a sharded handle.  For tests / inspection. */
+int32_t lvba_visual_solve(lvba_visual_t h, double *x, int32_t *solver);
+
 /* Robust losses, Ceres 2.1 semantics (loss_function.cc, corrector.cc): a residual block with squared norm s = |f|^2
  * contributes 1/2 rho(s) to the cost, and its residual and Jacobian enter the linearisation as sqrt(rho'(s)) f,
  * sqrt(rho'(s)) J (every kind here has rho'' <= 0).  `scale` = a, in whitened residual units:

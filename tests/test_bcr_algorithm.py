@@ -1,57 +1,14 @@
-"""The block cyclic reduction of csrc/bcr.hip as an algorithm, on the CPU (numpy): the one-launch-per-level form -- every even block
-row's update computed from the level's INPUT coupling blocks (two L arrays, read one / write the other), both odd neighbours
-inverted by the even row itself, T1 / T2 / t of an odd row kept for the back substitution, the levels from stride 1 up to the
-last one that leaves row 0 alone, then the back substitution from the largest stride down -- against a dense solve.  What the GPU
-tests hold the kernels to (tests/test_gpu_visual.py) is this scheme; here its index arithmetic is checked for block-row counts
-that are not powers of two, including the ones with a missing right neighbour at several levels."""
+"""The block cyclic reduction of csrc/bcr.hip as an algorithm, on the CPU (numpy; tests/bcr_reference.py::bcr_solve): the
+one-launch-per-level form -- every even block row's update computed from the level's INPUT coupling blocks (two L arrays, read
+one / write the other), both odd neighbours inverted by the even row itself, T1 / T2 / t of an odd row kept for the back
+substitution, the levels from stride 1 up to the last one that leaves row 0 alone, then the back substitution from the largest
+stride down -- against a dense solve.  What the GPU tests hold the kernels to (tests/test_gpu_visual.py,
+tests/test_gpu_reduced_solver.py) is this scheme; here its index arithmetic is checked for block-row counts that are not powers
+of two, including the ones with a missing right neighbour at several levels."""
 import numpy as np
 import pytest
 
-
-def bcr_solve(D, L, rhs):
-    """D [nb, b, b] diagonal blocks, L [nb, b, b] with L[r] = S[r, r - 1] (L[0] unused), rhs [nb, b].  Returns x [nb, b]."""
-    nb, b = rhs.shape
-    D = D.copy(); rhs = rhs.copy()
-    Lbuf = [L.copy(), np.zeros_like(L)]
-    cur = 0
-    T1 = np.zeros_like(L); T2 = np.zeros_like(L); t = np.zeros_like(rhs)
-    s, top = 1, 0
-    while s < nb:
-        Ls, Ld = Lbuf[cur], Lbuf[cur ^ 1]
-        newD, newrhs = {}, {}
-        for r in range(0, nb, 2 * s):                       # one "workgroup" per even row; reads only level inputs
-            il, ir, q = r - s, r + s, r + 2 * s
-            dD = np.zeros((b, b)); dL = np.zeros((b, b)); dr = np.zeros(b)
-            if il >= 0:
-                inv = np.linalg.inv(D[il])
-                t1l, t2l, tl = inv @ Ls[il], inv @ Ls[r].T, inv @ rhs[il]
-                dD += Ls[r] @ t2l
-                dL = Ls[r] @ t1l
-                dr += Ls[r] @ tl
-            if ir < nb:
-                inv = np.linalg.inv(D[ir])
-                t1r = inv @ Ls[ir]
-                t2r = inv @ Ls[q].T if q < nb else np.zeros((b, b))
-                tr = inv @ rhs[ir]
-                T1[ir], T2[ir], t[ir] = t1r, t2r, tr        # stored by the LEFT even neighbour
-                dD += Ls[ir].T @ t1r
-                dr += Ls[ir].T @ tr
-            newD[r] = D[r] - dD
-            newrhs[r] = rhs[r] - dr
-            Ld[r] = -dL if (il >= 0 and r - 2 * s >= 0) else 0.0
-        for r in newD:                                       # the even rows' own blocks: nobody else reads them at this level
-            D[r], rhs[r] = newD[r], newrhs[r]
-        cur ^= 1
-        top = s
-        s *= 2
-    x = np.zeros_like(rhs)
-    x[0] = np.linalg.solve(D[0], rhs[0])
-    s = top
-    while s >= 1:
-        for i in range(s, nb, 2 * s):
-            x[i] = t[i] - T1[i] @ x[i - s] - (T2[i] @ x[i + s] if i + s < nb else 0.0)
-        s //= 2
-    return x
+from bcr_reference import bcr_solve
 
 
 @pytest.mark.parametrize("nb", [2, 3, 5, 8, 13, 16, 37, 100, 400])
