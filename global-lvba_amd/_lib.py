@@ -39,6 +39,8 @@ SYMBOLS = [
     "lvba_match_scan", "lvba_match_set_depth", "lvba_match_points",
     "lvba_covis_default_opts", "lvba_covis_samples", "lvba_covis_counts", "lvba_covis_pairs",
     "lvba_trackgraph_create", "lvba_trackgraph_components", "lvba_trackgraph_orders", "lvba_trackgraph_destroy",
+    "lvba_verify_default_opts", "lvba_verify_create", "lvba_verify_destroy", "lvba_verify_pairs", "lvba_verify_hypotheses",
+    "lvba_verify_score",
 ]
 
 OK, ERR_ARG, ERR_DEVICE, ERR_NOMEM, ERR_UNSUPPORTED, ERR_DIST, ERR_STATE = 0, -1, -2, -3, -4, -5, -6
@@ -213,6 +215,12 @@ class MatchOpts(C.Structure):
     """lvba_match_opts"""
     _fields_ = [("max_distance", C.c_double), ("max_ratio", C.c_double), ("mutual", C.c_int32), ("guided", C.c_int32),
                 ("max_epipolar_px", C.c_double), ("max_reproj_px", C.c_double)]
+
+
+class VerifyOpts(C.Structure):
+    """lvba_verify_opts"""
+    _fields_ = [("method", C.c_int32), ("hypotheses", C.c_int32), ("refine_rounds", C.c_int32), ("min_inliers", C.c_int32),
+                ("max_error_px", C.c_double), ("seed", C.c_uint64)]
 
 
 class CovisOpts(C.Structure):
@@ -471,6 +479,14 @@ def load():
     lib.lvba_trackgraph_components.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.lvba_trackgraph_orders.argtypes = [H, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.lvba_trackgraph_destroy.argtypes = [H]
+    lib.lvba_verify_default_opts.argtypes = [C.POINTER(VerifyOpts)]
+    lib.lvba_verify_default_opts.restype = None
+    lib.lvba_verify_create.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(H)]
+    lib.lvba_verify_destroy.argtypes = [H]
+    lib.lvba_verify_pairs.argtypes = [H, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(VerifyOpts), C.c_int64, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.lvba_verify_hypotheses.argtypes = [H, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(VerifyOpts), C.c_void_p, C.c_void_p]
+    lib.lvba_verify_score.argtypes = [H, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
     lib.lvba_scans_info.argtypes = [H, C.POINTER(C.c_int32), C.c_void_p]
     lib.lvba_scans_download.argtypes = [H, C.c_int32, np.ctypeslib.ndpointer(np.float32, flags="C")]
     for name in SYMBOLS:

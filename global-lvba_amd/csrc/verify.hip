@@ -1,0 +1,576 @@
+// verify.hip -- two-view RANSAC over the putative matches of many image pairs at once (lvba_verify_*; the rule is in
+// include/lvba_hip.h, its scalar pieces in verify_device.h).
+//
+// Device design:
+//   verify_undistort_kernel   a thread per keypoint: trk_undistort once per handle, NaN where it fails.
+//   verify_hypothesis_kernel  generates and scores in one launch.  The grid is the list of (pair, block of VERIFY_HB hypotheses) of
+//                             every pair of the call; a workgroup is one wavefront and a lane owns one hypothesis.  In its prologue
+//                             the lane draws its sample, reads those matches and solves; under the eight-point method the 8 x 9
+//                             system (72 doubles) lives in LDS, lane-interleaved, where the pivot search may index it at run time
+//                             -- in registers that would be scratch memory or a select chain per access.  E then stays in nine
+//                             register pairs.  The same LDS is reused to stage the pair's undistorted match coordinates, 32 bytes
+//                             per match, in chunks of VERIFY_CHUNK; every lane walks the staged matches, all lanes read the same
+//                             address (a broadcast: no bank conflict), and counts its inliers with match_device.h' gate.  The
+//                             block's best (count, lowest h) and that lane's E go to one record per block: the per-hypothesis E
+//                             never reaches global memory, except through lvba_verify_hypotheses (one pair, the diagnostic call).
+//   verify_pick_kernel        a thread per pair: the integer maximum over the pair's block records.
+//   verify_refine_kernel      a workgroup per pair: the sums over the winner's inliers (per-thread strides, then wave_ops.h' fixed
+//                             trees), the refit in one lane (Jacobi on LDS), a rescore, kept only if the count grows; status.
+//   verify_mask_kernel        a thread per match: inlier of its pair's final E, and the pair OK -> a flag.
+//   verify_write_kernel       after an exclusive prefix sum of the flags: the inlier matches in (pair, original order), inlier_off.
+// No atomics of any kind, every choice an integer comparison: two calls give the same bytes, and so does a pair verified alone or
+// in a batch in any order (the generator does not know the pair's position, the grid or the lane).
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <algorithm>
+#include <cmath>
+#include <vector>
+#include "lvba_common.h"
+#include "mempool.h"
+#include "voxel_internal.h"
+#include "verify_device.h"
+#include "wave_ops.h"
+#include "../../include/lvba_hip.h"
+
+using namespace lvba;
+
+struct lvba_verify_s {
+    int device = 0;
+    int32_t n_images = 0;
+    std::vector<int64_t> off;      // [n_images + 1]
+    double *d_xy = nullptr;        // [total][2] undistorted normalised keypoints, NaN where the undistortion fails
+    bool has_R = false;
+    std::vector<double> R;         // [n_images][9]
+    double focal_sum = 0.0;        // fx + fy
+};
+
+namespace {
+
+constexpr int VERIFY_HB = 64;               // hypotheses per workgroup: one wavefront, a lane each
+constexpr int VERIFY_CHUNK = 1024;          // matches staged in LDS at a time, 32 bytes each
+constexpr int VERIFY_LDS_DOUBLES = 72 * VERIFY_HB > 4 * VERIFY_CHUNK ? 72 * VERIFY_HB : 4 * VERIFY_CHUNK;   // 36 864 bytes
+constexpr int REFINE_BLOCK = 256;
+constexpr int64_t VERIFY_MAX_MATCHES = (int64_t)1 << 31;   // the flags' prefix sum is 32 bits wide
+
+struct VerifyTask {
+    int64_t lo_off, hi_off, m_off;  // first keypoint of lo and of hi, first match of the pair
+    int32_t m, lo, hi, swap;        // swap: the pair was given as (hi, lo), column 1 of its matches is the lo image
+    int32_t blk0, n_blk;            // the pair's block records
+    double R[9];                    // R_hi R_lo^T (method 1)
+};
+struct VerifyBest { int32_t count, h; double E[9]; };   // count -1: no valid hypothesis
+
+__global__ __launch_bounds__(256) void verify_undistort_kernel(int64_t n, const float *__restrict__ uv, const TrkIntr cam, double *__restrict__ xy)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double x, y;
+    if (!trk_undistort(cam, (double)uv[2 * i], (double)uv[2 * i + 1], x, y)) x = y = NAN;
+    xy[2 * i] = x; xy[2 * i + 1] = y;
+}
+
+// the undistorted coordinates (x_lo, y_lo, x_hi, y_hi) of match i of the task
+__device__ __forceinline__ void load_match(const VerifyTask &t, const int32_t *__restrict__ matches, const double *__restrict__ xy, int i,
+                                           double &xl, double &yl, double &xh, double &yh)
+{
+    const int2 mm = reinterpret_cast<const int2 *>(matches)[t.m_off + i];
+    const int64_t kl = t.lo_off + (t.swap ? mm.y : mm.x), kh = t.hi_off + (t.swap ? mm.x : mm.y);
+    const double2 pl = reinterpret_cast<const double2 *>(xy)[kl], ph = reinterpret_cast<const double2 *>(xy)[kh];
+    xl = pl.x; yl = pl.y; xh = ph.x; yh = ph.y;
+}
+
+// tiles [n_tiles] = (task, first hypothesis); blk [n_tiles]; diag_E [H][9], diag_count [H]: null, or every hypothesis of the one task
+template <int METHOD>
+__global__ __launch_bounds__(VERIFY_HB) void verify_hypothesis_kernel(const VerifyTask *__restrict__ tasks, const int2 *__restrict__ tiles,
+                                                                      const int32_t *__restrict__ matches, const double *__restrict__ xy,
+                                                                      uint64_t seed, int H, double tau2, VerifyBest *__restrict__ blk,
+                                                                      double *__restrict__ diag_E, int32_t *__restrict__ diag_count)
+{
+    constexpr int K = METHOD == VERIFY_KNOWN_ROTATION ? 2 : 8;
+    __shared__ __attribute__((aligned(16))) double lds[METHOD == VERIFY_EIGHT_POINT ? VERIFY_LDS_DOUBLES : 4 * VERIFY_CHUNK];
+    const int2 tl = tiles[blockIdx.x];
+    const VerifyTask &t = tasks[tl.x];
+    const int lane = threadIdx.x, h = tl.y + lane, m = t.m;
+    const bool live = h < H;
+    double E[9];
+    bool valid = false;
+    verify_zero(E);
+    if (live) {
+        int32_t idx[K];
+        verify_sample<K>(verify_key(seed, t.lo, t.hi, h), m, idx);
+        if constexpr (METHOD == VERIFY_EIGHT_POINT) {
+            bool clean = true;
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                double xl, yl, xh, yh;
+                load_match(t, matches, xy, idx[j], xl, yl, xh, yh);
+                clean &= verify_eight_row(lds + lane, VERIFY_HB, j, xl, yl, xh, yh);
+            }
+            valid = clean && verify_eight_solve(lds + lane, VERIFY_HB, E);
+        } else {
+            double p[8], R[9];
+            load_match(t, matches, xy, idx[0], p[0], p[1], p[2], p[3]);
+            load_match(t, matches, xy, idx[1], p[4], p[5], p[6], p[7]);
+#pragma unroll
+            for (int k = 0; k < 9; ++k) R[k] = t.R[k];
+            valid = verify_known_rotation(p, R, E);
+        }
+    }
+    __syncthreads(); // the systems are done with: the same LDS now stages the matches
+    int32_t count = 0;
+    for (int c0 = 0; c0 < m; c0 += VERIFY_CHUNK) {
+        const int n = min(VERIFY_CHUNK, m - c0);
+        for (int i = lane; i < n; i += VERIFY_HB) {
+            double xl, yl, xh, yh;
+            load_match(t, matches, xy, c0 + i, xl, yl, xh, yh);
+            lds[4 * i] = xl; lds[4 * i + 1] = yl; lds[4 * i + 2] = xh; lds[4 * i + 3] = yh;
+        }
+        __syncthreads();
+#pragma unroll 4
+        for (int i = 0; i < n; ++i) {
+            const double2 pl = reinterpret_cast<const double2 *>(lds)[2 * i], ph = reinterpret_cast<const double2 *>(lds)[2 * i + 1];
+            count += verify_inlier(E, pl.x, pl.y, ph.x, ph.y, tau2) ? 1 : 0;
+        }
+        __syncthreads();
+    }
+    if (!valid) count = -1;
+    if (diag_E && live) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) diag_E[9 * (int64_t)h + k] = E[k];
+        diag_count[h] = count;
+    }
+    const int64_t own = live ? verify_rank(count, h) : (int64_t)-1;
+    int64_t top = own;
+#pragma unroll
+    for (int w = 1; w < 64; w <<= 1) {
+        const int64_t o = __shfl_xor(top, w, 64);
+        top = o > top ? o : top;
+    }
+    if (live && own == top) { // one lane: h is part of the rank
+        VerifyBest &b = blk[blockIdx.x];
+        b.count = count; b.h = h;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) b.E[k] = E[k];
+    }
+}
+
+__global__ __launch_bounds__(256) void verify_pick_kernel(int n_tasks, const VerifyTask *__restrict__ tasks, const VerifyBest *__restrict__ blk,
+                                                          VerifyBest *__restrict__ res)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= n_tasks) return;
+    const VerifyTask &t = tasks[p];
+    int win = -1;
+    int64_t top = -1;
+    for (int k = 0; k < t.n_blk; ++k) {
+        const int64_t r = verify_rank(blk[t.blk0 + k].count, blk[t.blk0 + k].h);
+        if (r > top) { top = r; win = t.blk0 + k; }
+    }
+    VerifyBest b;
+    b.count = -1; b.h = -1;
+    verify_zero(b.E);
+    if (win >= 0 && blk[win].count >= 0) b = blk[win];
+    res[p] = b;
+}
+
+// E [P][9], status, n_inliers, best_h [P]: the pair's result after `rounds` refits
+template <int METHOD>
+__global__ __launch_bounds__(REFINE_BLOCK) void verify_refine_kernel(const VerifyTask *__restrict__ tasks, const int32_t *__restrict__ matches,
+                                                                     const double *__restrict__ xy, double tau2, int rounds, int min_inliers,
+                                                                     const VerifyBest *__restrict__ res, double *__restrict__ E_out,
+                                                                     int32_t *__restrict__ status, int32_t *__restrict__ n_inliers,
+                                                                     int32_t *__restrict__ best_h)
+{
+    constexpr int NS = METHOD == VERIFY_EIGHT_POINT ? 45 : 6;
+    constexpr int WAVES = REFINE_BLOCK / 64;
+    __shared__ double red[WAVES];
+    __shared__ double sT[NS], sN[81], sV[81], sE[9];
+    __shared__ int s_ok;
+    const int p = blockIdx.x, tid = threadIdx.x;
+    const VerifyTask &t = tasks[p];
+    const int m = t.m;
+    const VerifyBest b = res[p];
+    double E[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) E[k] = b.E[k];
+    int32_t count = b.count;
+    double R[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R[k] = t.R[k];
+    for (int round = 0; round < rounds && count > 0; ++round) { // every condition below is the same in all threads
+        double acc[NS];
+#pragma unroll
+        for (int k = 0; k < NS; ++k) acc[k] = 0.0;
+        for (int i = tid; i < m; i += REFINE_BLOCK) {
+            double xl, yl, xh, yh;
+            load_match(t, matches, xy, i, xl, yl, xh, yh);
+            if (!verify_inlier(E, xl, yl, xh, yh, tau2)) continue;
+            if constexpr (METHOD == VERIFY_EIGHT_POINT) {
+                const double a[9] = {xh * xl, xh * yl, xh, yh * xl, yh * yl, yh, xl, yl, 1.0};
+                int k = 0;
+#pragma unroll
+                for (int r = 0; r < 9; ++r)
+#pragma unroll
+                    for (int c = r; c < 9; ++c) acc[k++] += a[r] * a[c];
+            } else {
+                double c[3];
+                verify_constraint(R, xl, yl, xh, yh, c);
+                acc[0] += c[0] * c[0]; acc[1] += c[0] * c[1]; acc[2] += c[0] * c[2];
+                acc[3] += c[1] * c[1]; acc[4] += c[1] * c[2]; acc[5] += c[2] * c[2];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < NS; ++k) {
+            const double sum = block_sum_all<WAVES>(acc[k], red);
+            if (tid == 0) sT[k] = sum;
+        }
+        if (tid == 0) {
+            double F[9];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) F[k] = E[k];
+            bool ok;
+            if constexpr (METHOD == VERIFY_EIGHT_POINT) {
+                int k = 0;
+#pragma unroll
+                for (int r = 0; r < 9; ++r)
+#pragma unroll
+                    for (int c = r; c < 9; ++c) { sN[9 * r + c] = sT[k]; sN[9 * c + r] = sT[k]; ++k; }
+                ok = verify_refit_eight(sN, sV, F);
+            } else {
+                double C[6];
+#pragma unroll
+                for (int k = 0; k < 6; ++k) C[k] = sT[k];
+                ok = verify_refit_rotation(C, R, F);
+            }
+#pragma unroll
+            for (int k = 0; k < 9; ++k) sE[k] = F[k];
+            s_ok = ok ? 1 : 0;
+        }
+        __syncthreads();
+        const bool ok = s_ok != 0;
+        double F[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) F[k] = sE[k];
+        __syncthreads(); // sE and s_ok are free again
+        if (!ok) break;
+        int32_t c = 0;
+        for (int i = tid; i < m; i += REFINE_BLOCK) {
+            double xl, yl, xh, yh;
+            load_match(t, matches, xy, i, xl, yl, xh, yh);
+            c += verify_inlier(F, xl, yl, xh, yh, tau2) ? 1 : 0;
+        }
+        const int32_t cn = (int32_t)block_sum_all<WAVES>((double)c, red); // integers below 2^31: exact in fp64 in any order
+        if (cn <= count) break;                                           // kept only if strictly better
+        count = cn;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) E[k] = F[k];
+    }
+    if (tid != 0) return;
+    const int st = verify_status(m, verify_sample_size(METHOD), min_inliers, count);
+    status[p] = st;
+    n_inliers[p] = count > 0 ? count : 0;
+    best_h[p] = b.h;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) E_out[9 * (int64_t)p + k] = E[k];
+}
+
+// flag [n + 1] (the last is 0): match i of the call is an inlier of its pair's E and the pair is OK
+__global__ __launch_bounds__(256) void verify_mask_kernel(int64_t n, int n_tasks, const VerifyTask *__restrict__ tasks,
+                                                          const int32_t *__restrict__ matches, const double *__restrict__ xy, double tau2,
+                                                          const double *__restrict__ E, const int32_t *__restrict__ status,
+                                                          uint32_t *__restrict__ flag)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i > n) return;
+    if (i == n) { flag[i] = 0; return; }
+    int lo = 0, hi = n_tasks; // the last pair with m_off <= i (empty pairs share an offset with their successor)
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (tasks[mid].m_off <= i) lo = mid; else hi = mid;
+    }
+    const VerifyTask &t = tasks[lo];
+    bool ok = status[lo] == VERIFY_OK;
+    if (ok) {
+        double xl, yl, xh, yh, e[9];
+        load_match(t, matches, xy, (int)(i - t.m_off), xl, yl, xh, yh);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) e[k] = E[9 * (int64_t)lo + k];
+        ok = verify_inlier(e, xl, yl, xh, yh, tau2);
+    }
+    flag[i] = ok ? 1u : 0u;
+}
+
+// inliers [n_out][2] in (pair, original order), the caller's columns; off [n_tasks + 1]
+__global__ __launch_bounds__(256) void verify_write_kernel(int64_t n, int n_tasks, const VerifyTask *__restrict__ tasks,
+                                                           const int32_t *__restrict__ matches, const uint32_t *__restrict__ flag,
+                                                           const uint32_t *__restrict__ excl, int64_t n_out, int32_t *__restrict__ inliers,
+                                                           int64_t *__restrict__ off)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n_tasks) off[i] = excl[tasks[i].m_off];
+    if (i == n_tasks) off[i] = excl[n];
+    if (i >= n || !flag[i]) return;
+    const int64_t pos = excl[i];
+    if (pos >= n_out) return;
+    inliers[2 * pos] = matches[2 * i]; inliers[2 * pos + 1] = matches[2 * i + 1];
+}
+
+int32_t check_opts(const lvba_verify_s *v, const lvba_verify_opts *opts, lvba_verify_opts &o)
+{
+    lvba_verify_default_opts(&o);
+    if (opts) o = *opts;
+    if (o.method != VERIFY_EIGHT_POINT && o.method != VERIFY_KNOWN_ROTATION) return lvba_fail(LVBA_ERR_ARG, "method %d (0 or 1)", o.method);
+    if (o.hypotheses < 1) return lvba_fail(LVBA_ERR_ARG, "hypotheses %d (>= 1)", o.hypotheses);
+    if (o.refine_rounds < 0 || o.min_inliers < 0 || !(std::isfinite(o.max_error_px) && o.max_error_px > 0.0))
+        return lvba_fail(LVBA_ERR_ARG, "options: refine_rounds %d (>= 0), min_inliers %d (>= 0), max_error_px %g (finite, > 0)", o.refine_rounds,
+                         o.min_inliers, o.max_error_px);
+    if (o.method == VERIFY_KNOWN_ROTATION && !v->has_R)
+        return lvba_fail(LVBA_ERR_ARG, "the rotation-aided method (method = 1) needs the rotations Rcw at lvba_verify_create");
+    return LVBA_OK;
+}
+
+double gate_tau2(const lvba_verify_s *v, double max_error_px)
+{
+    const double tau = (2.0 * max_error_px) / v->focal_sum;
+    return tau * tau;
+}
+
+// the task of pair (a, b) with matches [m_off, m_off + m) of `matches`, every index checked
+int32_t make_task(const lvba_verify_s *v, int64_t a, int64_t b, int64_t m_off, int64_t m, const int32_t *matches, int method, VerifyTask &t)
+{
+    if (a < 0 || a >= v->n_images || b < 0 || b >= v->n_images || a == b)
+        return lvba_fail(LVBA_ERR_ARG, "pair (%lld, %lld) of %d images (two different images)", (long long)a, (long long)b, v->n_images);
+    if (m < 0 || m >= INT32_MAX) return lvba_fail(LVBA_ERR_ARG, "pair (%lld, %lld) with %lld matches", (long long)a, (long long)b, (long long)m);
+    const int64_t n_a = v->off[a + 1] - v->off[a], n_b = v->off[b + 1] - v->off[b];
+    for (int64_t i = m_off; i < m_off + m; ++i)
+        if (matches[2 * i] < 0 || matches[2 * i] >= n_a || matches[2 * i + 1] < 0 || matches[2 * i + 1] >= n_b)
+            return lvba_fail(LVBA_ERR_ARG, "match %lld = (%d, %d) of pair (%lld, %lld) with %lld and %lld keypoints", (long long)i, matches[2 * i],
+                             matches[2 * i + 1], (long long)a, (long long)b, (long long)n_a, (long long)n_b);
+    t = VerifyTask{};
+    t.lo = (int32_t)std::min(a, b); t.hi = (int32_t)std::max(a, b); t.swap = a > b ? 1 : 0;
+    t.lo_off = v->off[t.lo]; t.hi_off = v->off[t.hi]; t.m_off = m_off; t.m = (int32_t)m;
+    if (method == VERIFY_KNOWN_ROTATION) verify_relative_rotation(&v->R[9 * (size_t)t.lo], &v->R[9 * (size_t)t.hi], t.R);
+    return LVBA_OK;
+}
+
+// The hypotheses of every task with enough matches, one grid; blk0 / n_blk of the tasks are set here.  d_blk: the block records.
+int32_t run_hypotheses(hipStream_t s, const lvba_verify_s *v, std::vector<VerifyTask> &tasks, const lvba_verify_opts &o, const int32_t *d_matches,
+                       DevBuf &d_tasks, DevBuf &d_blk, double *diag_E, int32_t *diag_count)
+{
+    const int k = verify_sample_size(o.method), need = std::max(k, o.min_inliers);
+    std::vector<int2> tiles;
+    for (size_t p = 0; p < tasks.size(); ++p) {
+        tasks[p].blk0 = (int32_t)tiles.size();
+        if (tasks[p].m >= (diag_E ? k : need))
+            for (int h0 = 0; h0 < o.hypotheses; h0 += VERIFY_HB) tiles.push_back(make_int2((int)p, h0));
+        tasks[p].n_blk = (int32_t)tiles.size() - tasks[p].blk0;
+        if (tiles.size() > (size_t)INT32_MAX / 2) return lvba_fail(LVBA_ERR_UNSUPPORTED, "more than 2^30 hypothesis blocks in one call");
+    }
+    HIPCHK(d_tasks.alloc(sizeof(VerifyTask) * tasks.size()));
+    HIPCHK(lvba::copy_h2d(d_tasks.p, tasks.data(), sizeof(VerifyTask) * tasks.size()));
+    HIPCHK(d_blk.alloc(sizeof(VerifyBest) * tiles.size()));
+    if (tiles.empty()) return LVBA_OK;
+    DevBuf d_tiles(s);
+    HIPCHK(d_tiles.alloc(sizeof(int2) * tiles.size()));
+    HIPCHK(lvba::copy_h2d(d_tiles.p, tiles.data(), sizeof(int2) * tiles.size()));
+    const double tau2 = gate_tau2(v, o.max_error_px);
+    if (o.method == VERIFY_EIGHT_POINT)
+        verify_hypothesis_kernel<VERIFY_EIGHT_POINT><<<(unsigned)tiles.size(), VERIFY_HB, 0, s>>>(
+            d_tasks.as<VerifyTask>(), d_tiles.as<int2>(), d_matches, v->d_xy, o.seed, o.hypotheses, tau2, d_blk.as<VerifyBest>(), diag_E, diag_count);
+    else
+        verify_hypothesis_kernel<VERIFY_KNOWN_ROTATION><<<(unsigned)tiles.size(), VERIFY_HB, 0, s>>>(
+            d_tasks.as<VerifyTask>(), d_tiles.as<int2>(), d_matches, v->d_xy, o.seed, o.hypotheses, tau2, d_blk.as<VerifyBest>(), diag_E, diag_count);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s)); // the tile list goes with this scope
+    return LVBA_OK;
+}
+
+} // namespace
+
+extern "C" void lvba_verify_default_opts(lvba_verify_opts *o)
+{
+    if (!o) return;
+    *o = lvba_verify_opts{};
+    o->method = VERIFY_EIGHT_POINT; o->hypotheses = 1024; o->refine_rounds = 2; o->min_inliers = 15; o->max_error_px = 4.0; o->seed = 0;
+}
+
+extern "C" int32_t lvba_verify_create(int32_t device, int32_t n_images, const int64_t *kp_off, const float *keypoints_uv, const double *intr,
+                                      const double *Rcw, lvba_verify_t *out)
+{
+    if (!out || n_images < 0 || !kp_off || !intr) return lvba_fail(LVBA_ERR_ARG, "null argument or n_images < 0");
+    if (kp_off[0] != 0) return lvba_fail(LVBA_ERR_ARG, "kp_off[0] = %lld (0)", (long long)kp_off[0]);
+    for (int i = 0; i < n_images; ++i)
+        if (kp_off[i + 1] < kp_off[i]) return lvba_fail(LVBA_ERR_ARG, "kp_off decreases at image %d", i);
+    const int64_t total = kp_off[n_images];
+    if (total > 0 && !keypoints_uv) return lvba_fail(LVBA_ERR_ARG, "null keypoints");
+    for (int k = 0; k < 8; ++k)
+        if (!std::isfinite(intr[k])) return lvba_fail(LVBA_ERR_ARG, "intrinsic %d is not finite", k);
+    if (!(intr[0] > 0.0 && intr[1] > 0.0)) return lvba_fail(LVBA_ERR_ARG, "focal lengths %g, %g (> 0)", intr[0], intr[1]);
+    if (Rcw)
+        for (int64_t k = 0; k < 9 * (int64_t)n_images; ++k)
+            if (!std::isfinite(Rcw[k])) return lvba_fail(LVBA_ERR_ARG, "camera %lld: non-finite rotation", (long long)(k / 9));
+    TRY(check_device(device));
+    HIPCHK(hipSetDevice(device));
+    lvba_verify_s *v = new lvba_verify_s;
+    v->device = device; v->n_images = n_images;
+    v->off.assign(kp_off, kp_off + n_images + 1);
+    v->focal_sum = intr[0] + intr[1];
+    if (Rcw) { v->R.assign(Rcw, Rcw + 9 * (size_t)n_images); v->has_R = true; }
+    if (total > 0) {
+        const TrkIntr cam{intr[0], intr[1], intr[2], intr[3], intr[4], intr[5], intr[6], intr[7]};
+        hipError_t e = DevicePool::get().alloc((void **)&v->d_xy, 16 * (size_t)total);
+        if (e == hipSuccess) {
+            ScopedStream sg;
+            DevBuf d_uv;
+            e = sg.acquire();
+            d_uv.stream = sg.s;
+            if (e == hipSuccess) e = d_uv.alloc(8 * (size_t)total);
+            if (e == hipSuccess) e = lvba::copy_h2d(d_uv.p, keypoints_uv, 8 * (size_t)total);
+            if (e == hipSuccess) {
+                verify_undistort_kernel<<<grid_for(total, 256), 256, 0, sg.s>>>(total, d_uv.as<float>(), cam, v->d_xy);
+                e = hipGetLastError();
+            }
+            if (e == hipSuccess) e = hipStreamSynchronize(sg.s);
+        }
+        if (e != hipSuccess) {
+            lvba_verify_destroy(v);
+            return lvba_fail(e == hipErrorOutOfMemory ? LVBA_ERR_NOMEM : LVBA_ERR_DEVICE, "keypoint upload: %s", hipGetErrorString(e));
+        }
+    }
+    *out = v;
+    return LVBA_OK;
+}
+
+extern "C" int32_t lvba_verify_destroy(lvba_verify_t v)
+{
+    if (!v) return LVBA_OK;
+    (void)hipSetDevice(v->device);
+    (void)hipDeviceSynchronize();
+    if (v->d_xy) DevicePool::get().free(v->d_xy);
+    delete v;
+    return LVBA_OK;
+}
+
+extern "C" int32_t lvba_verify_pairs(lvba_verify_t v, int64_t n_pairs, const int32_t *pairs, const int64_t *match_off, const int32_t *matches,
+                                     const lvba_verify_opts *opts, int64_t capacity, int64_t *inlier_off, int32_t *inliers, double *E,
+                                     int32_t *status, int32_t *n_inliers, int32_t *best_h)
+{
+    if (!v || !match_off || !inlier_off || n_pairs < 0 || capacity < 0 || (n_pairs > 0 && (!pairs || !E || !status || !n_inliers || !best_h)) ||
+        (capacity > 0 && !inliers))
+        return lvba_fail(LVBA_ERR_ARG, "null argument, n_pairs < 0 or capacity < 0");
+    lvba_verify_opts o;
+    TRY(check_opts(v, opts, o));
+    if (n_pairs >= INT32_MAX / 2) return lvba_fail(LVBA_ERR_UNSUPPORTED, "%lld pairs in one call", (long long)n_pairs);
+    if (match_off[0] != 0) return lvba_fail(LVBA_ERR_ARG, "match_off[0] = %lld (0)", (long long)match_off[0]);
+    for (int64_t p = 0; p < n_pairs; ++p)
+        if (match_off[p + 1] < match_off[p]) return lvba_fail(LVBA_ERR_ARG, "match_off decreases at pair %lld", (long long)p);
+    const int64_t total = match_off[n_pairs];
+    if (total >= VERIFY_MAX_MATCHES) return lvba_fail(LVBA_ERR_UNSUPPORTED, "%lld matches in one call (below 2^31)", (long long)total);
+    if (total > 0 && !matches) return lvba_fail(LVBA_ERR_ARG, "null matches");
+    std::vector<VerifyTask> tasks((size_t)n_pairs);
+    for (int64_t p = 0; p < n_pairs; ++p)
+        TRY(make_task(v, pairs[2 * p], pairs[2 * p + 1], match_off[p], match_off[p + 1] - match_off[p], matches, o.method, tasks[(size_t)p]));
+    inlier_off[0] = 0;
+    if (n_pairs == 0) return LVBA_OK;
+    HIPCHK(hipSetDevice(v->device));
+    ScopedStream sg;
+    HIPCHK(sg.acquire());
+    hipStream_t s = sg.s;
+    const int np = (int)n_pairs;
+    const double tau2 = gate_tau2(v, o.max_error_px);
+    DevBuf d_m(s), d_tasks(s), d_blk(s), d_res(s), d_E(s), d_int(s), d_flag(s), d_excl(s), d_off(s), d_out(s);
+    HIPCHK(d_m.alloc(8 * (size_t)total));
+    if (total > 0) HIPCHK(lvba::copy_h2d(d_m.p, matches, 8 * (size_t)total));
+    TRY(run_hypotheses(s, v, tasks, o, d_m.as<int32_t>(), d_tasks, d_blk, nullptr, nullptr));
+    HIPCHK(d_res.alloc(sizeof(VerifyBest) * (size_t)np)); HIPCHK(d_E.alloc(72 * (size_t)np)); HIPCHK(d_int.alloc(12 * (size_t)np));
+    HIPCHK(d_flag.alloc(4 * ((size_t)total + 1))); HIPCHK(d_excl.alloc(4 * ((size_t)total + 1))); HIPCHK(d_off.alloc(8 * ((size_t)np + 1)));
+    int32_t *d_status = d_int.as<int32_t>(), *d_cnt = d_status + np, *d_h = d_cnt + np;
+    verify_pick_kernel<<<grid_for(np, 256), 256, 0, s>>>(np, d_tasks.as<VerifyTask>(), d_blk.as<VerifyBest>(), d_res.as<VerifyBest>());
+    HIPCHK(hipGetLastError());
+    if (o.method == VERIFY_EIGHT_POINT)
+        verify_refine_kernel<VERIFY_EIGHT_POINT><<<(unsigned)np, REFINE_BLOCK, 0, s>>>(d_tasks.as<VerifyTask>(), d_m.as<int32_t>(), v->d_xy, tau2,
+                                                                                      o.refine_rounds, o.min_inliers, d_res.as<VerifyBest>(),
+                                                                                      d_E.as<double>(), d_status, d_cnt, d_h);
+    else
+        verify_refine_kernel<VERIFY_KNOWN_ROTATION><<<(unsigned)np, REFINE_BLOCK, 0, s>>>(d_tasks.as<VerifyTask>(), d_m.as<int32_t>(), v->d_xy, tau2,
+                                                                                         o.refine_rounds, o.min_inliers, d_res.as<VerifyBest>(),
+                                                                                         d_E.as<double>(), d_status, d_cnt, d_h);
+    HIPCHK(hipGetLastError());
+    verify_mask_kernel<<<grid_for(total + 1, 256), 256, 0, s>>>(total, np, d_tasks.as<VerifyTask>(), d_m.as<int32_t>(), v->d_xy, tau2,
+                                                                d_E.as<double>(), d_status, d_flag.as<uint32_t>());
+    HIPCHK(hipGetLastError());
+    TRY(scan_excl<uint32_t>(s, d_flag.as<uint32_t>(), d_excl.as<uint32_t>(), (size_t)total + 1));
+    uint32_t found = 0;
+    HIPCHK(lvba::copy_d2h(&found, d_excl.as<uint32_t>() + total, 4));
+    const int64_t n_out = std::min<int64_t>(found, capacity);
+    HIPCHK(d_out.alloc(8 * (size_t)n_out));
+    verify_write_kernel<<<grid_for(std::max<int64_t>(total, np + 1), 256), 256, 0, s>>>(total, np, d_tasks.as<VerifyTask>(), d_m.as<int32_t>(),
+                                                                                       d_flag.as<uint32_t>(), d_excl.as<uint32_t>(), n_out,
+                                                                                       d_out.as<int32_t>(), d_off.as<int64_t>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(lvba::copy_d2h(inlier_off, d_off.p, 8 * ((size_t)np + 1)));
+    if (n_out > 0) HIPCHK(lvba::copy_d2h(inliers, d_out.p, 8 * (size_t)n_out));
+    HIPCHK(lvba::copy_d2h(E, d_E.p, 72 * (size_t)np));
+    HIPCHK(lvba::copy_d2h(status, d_status, 4 * (size_t)np));
+    HIPCHK(lvba::copy_d2h(n_inliers, d_cnt, 4 * (size_t)np));
+    HIPCHK(lvba::copy_d2h(best_h, d_h, 4 * (size_t)np));
+    return LVBA_OK;
+}
+
+extern "C" int32_t lvba_verify_hypotheses(lvba_verify_t v, int32_t a, int32_t b, int64_t n_matches, const int32_t *matches,
+                                          const lvba_verify_opts *opts, double *E, int32_t *count)
+{
+    if (!v || !E || !count || n_matches < 0 || (n_matches > 0 && !matches)) return lvba_fail(LVBA_ERR_ARG, "null argument or n_matches < 0");
+    lvba_verify_opts o;
+    TRY(check_opts(v, opts, o));
+    std::vector<VerifyTask> tasks(1);
+    TRY(make_task(v, a, b, 0, n_matches, matches, o.method, tasks[0]));
+    const size_t H = (size_t)o.hypotheses;
+    if (n_matches < verify_sample_size(o.method)) { // no sample can be drawn: every hypothesis is invalid
+        std::fill(E, E + 9 * H, 0.0);
+        std::fill(count, count + H, -1);
+        return LVBA_OK;
+    }
+    HIPCHK(hipSetDevice(v->device));
+    ScopedStream sg;
+    HIPCHK(sg.acquire());
+    DevBuf d_m(sg.s), d_tasks(sg.s), d_blk(sg.s), d_E(sg.s), d_c(sg.s);
+    HIPCHK(d_m.alloc(8 * (size_t)n_matches)); HIPCHK(d_E.alloc(72 * H)); HIPCHK(d_c.alloc(4 * H));
+    HIPCHK(lvba::copy_h2d(d_m.p, matches, 8 * (size_t)n_matches));
+    TRY(run_hypotheses(sg.s, v, tasks, o, d_m.as<int32_t>(), d_tasks, d_blk, d_E.as<double>(), d_c.as<int32_t>()));
+    HIPCHK(lvba::copy_d2h(E, d_E.p, 72 * H));
+    HIPCHK(lvba::copy_d2h(count, d_c.p, 4 * H));
+    return LVBA_OK;
+}
+
+extern "C" int32_t lvba_verify_score(lvba_verify_t v, int32_t a, int32_t b, int64_t n_matches, const int32_t *matches, const double *E,
+                                     double max_error_px, uint8_t *mask)
+{
+    if (!v || !E || n_matches < 0 || (n_matches > 0 && (!matches || !mask))) return lvba_fail(LVBA_ERR_ARG, "null argument or n_matches < 0");
+    if (!(std::isfinite(max_error_px) && max_error_px > 0.0)) return lvba_fail(LVBA_ERR_ARG, "max_error_px %g (finite, > 0)", max_error_px);
+    std::vector<VerifyTask> tasks(1);
+    TRY(make_task(v, a, b, 0, n_matches, matches, VERIFY_EIGHT_POINT, tasks[0]));
+    if (n_matches == 0) return LVBA_OK;
+    HIPCHK(hipSetDevice(v->device));
+    ScopedStream sg;
+    HIPCHK(sg.acquire());
+    const size_t n = (size_t)n_matches;
+    DevBuf d_m(sg.s), d_tasks(sg.s), d_E(sg.s), d_st(sg.s), d_flag(sg.s);
+    HIPCHK(d_m.alloc(8 * n)); HIPCHK(d_tasks.alloc(sizeof(VerifyTask))); HIPCHK(d_E.alloc(72)); HIPCHK(d_st.alloc(4)); HIPCHK(d_flag.alloc(4 * (n + 1)));
+    const int32_t ok = VERIFY_OK;
+    HIPCHK(lvba::copy_h2d(d_m.p, matches, 8 * n));
+    HIPCHK(lvba::copy_h2d(d_tasks.p, tasks.data(), sizeof(VerifyTask)));
+    HIPCHK(lvba::copy_h2d(d_E.p, E, 72));
+    HIPCHK(lvba::copy_h2d(d_st.p, &ok, 4));
+    verify_mask_kernel<<<grid_for(n_matches + 1, 256), 256, 0, sg.s>>>(n_matches, 1, d_tasks.as<VerifyTask>(), d_m.as<int32_t>(), v->d_xy,
+                                                                      gate_tau2(v, max_error_px), d_E.as<double>(), d_st.as<int32_t>(),
+                                                                      d_flag.as<uint32_t>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(sg.s));
+    std::vector<uint32_t> flag(n);
+    HIPCHK(lvba::copy_d2h(flag.data(), d_flag.p, 4 * n));
+    for (size_t i = 0; i < n; ++i) mask[i] = flag[i] ? 1 : 0;
+    return LVBA_OK;
+}

@@ -663,6 +663,18 @@ def match_image_pairs(descriptors, pairs, keypoints=None, Rcw=None, tcw=None, in
     return M.match_pairs(descriptors, pairs, keypoints=keypoints, intr=intr, Rcw=Rcw, tcw=tcw, device=device, depth=depth, **opts)
 
 
+def verify_image_pairs(keypoints, pairs, matches, intr, Rcw=None, device=0, **opts):
+    """Geometric verification of putative matches (verify.Verifier): per image pair an essential matrix by RANSAC
+    on the GPU, all pairs in one grid, and the matches that agree with it.  matches: one [m, 2] array per pair, as
+    match_image_pairs returns them.  Without Rcw the pose-free eight-point method (method=0; degenerate where the scene is one
+    plane); with Rcw [M, 3, 3] (T_cam<-world rotations) and method=1 the rotation-aided two-point method, which trusts the relative
+    rotation and nothing else.  opts: method, hypotheses, refine_rounds, min_inliers, max_error_px, seed.  Returns
+    (inlier_matches, report): one int32 [m, 2] array per pair in the order of `pairs` -- empty for a pair that fails, which is not
+    dropped -- and a dict of arrays E, status, n_inliers, n_matches, best_h."""
+    from . import verify as VF
+    return VF.verify_pairs(keypoints, pairs, matches, intr, Rcw=Rcw, device=device, **opts)
+
+
 def select_image_pairs(depth, Rcw, tcw, intr, sequential=0, **opts):
     """Which image pairs to match (covis.select_pairs) instead of all M (M - 1) / 2: the pairs in which one image
     sees enough of what the other sees, judged on a grid of samples lifted through the LiDAR depth images (a visual.DepthImages
@@ -687,7 +699,7 @@ def select_image_pairs(depth, Rcw, tcw, intr, sequential=0, **opts):
 def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, tci, intr, width, height, keypoints, pairs,
                       matches, enable_lidar_ba=True, enable_visual_ba=True, device=0, images=None, lidar_priors=None,
                       window_loss=None, stage_loss=None, camera_priors=None, map_quality=False, loop_closures=None, relax=None,
-                      match_fn=None, match_depth=False, match_select=None, device_tracks=False, **cfg):
+                      match_fn=None, match_depth=False, match_select=None, device_tracks=False, verify_matches=None, **cfg):
     """LvbaSystem::runFullPipeline (src/lvba_system.cpp:136-142) on in-memory data: clouds = body-frame [n_i, >=3] float32
     arrays, poses [n,12] = x_buf_ (T_world<-imu), image_poses [m,12] the image poses from the odometry.  cfg: DEFAULTS' keys
     (visual_loss, colorize_leaf among them).  images: None, or the images ([m,H,W,3] BGR uint8 or a callable k -> [H,W,3]):
@@ -714,7 +726,15 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
     match_select: None (off), True, or a dict of select_image_pairs' keywords (only with match_fn): the depth images are rendered
     once as under match_depth, the image pairs to match are selected from them (select_image_pairs), match_fn is called with
     pairs=selected (and depth=depth when match_depth is set), and the output holds pair_selection, the report.
-    device_tracks: False, or True: the visual stage builds its tracks on the GPU (run_visual_ba_with_lidar_assist's device_tracks)."""
+    device_tracks: False, or True: the visual stage builds its tracks on the GPU (run_visual_ba_with_lidar_assist's device_tracks).
+    verify_matches: None (off: nothing is launched), True, or a dict of verify_image_pairs' options: the matches actually used --
+    the caller's or match_fn's -- are verified geometrically immediately before the visual stage and only the inliers go on (a
+    pair that fails keeps its place with no matches).  Here the method defaults to 1, the rotation-aided one: the rotations are
+    those of camera_from_imu of the camera poses in force at that point (the LiDAR-derived ones), and the scenes a LiDAR sees are
+    mostly walls and floors, where the pose-free eight-point method (method=0, which uses no pose at all) is degenerate.  The output holds pairs / matches as used and match_verification: per pair
+    the status and the counts, plus the totals."""
+    if verify_matches and not enable_visual_ba:
+        raise ValueError("verify_matches verifies the matches of the visual stage (enable_visual_ba=True)")
     if images is not None and not enable_visual_ba:
         raise ValueError("colouring the map needs the cameras of the visual stage (enable_visual_ba=True)")
     if match_select and (match_fn is None or not enable_visual_ba):
@@ -750,6 +770,17 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
                         kw["depth"] = depth
                 pairs, matches = match_fn(cam_poses, **kw)
                 out["pairs"], out["matches"] = pairs, matches
+            if enable_visual_ba and verify_matches:
+                from . import verify as VF
+                vo = dict(verify_matches) if isinstance(verify_matches, dict) else {}
+                vo.setdefault("method", VF.KNOWN_ROTATION)   # here the rotations exist, and LiDAR scenes are walls and floors
+                Rv = None
+                if int(vo["method"]) == VF.KNOWN_ROTATION:
+                    Rv, _ = camera_from_imu(update_camera_poses_from_lidar(out["poses"], x_orig, scan_times, image_times, image_poses),
+                                            Rci, tci)
+                matches, vrep = verify_image_pairs(keypoints, pairs, matches, intr, Rcw=Rv, device=device, **vo)
+                out["pairs"], out["matches"] = pairs, matches
+                out["match_verification"] = VF.summary(pairs, vrep)
             if enable_visual_ba:
                 out["visual"] = run_visual_ba_with_lidar_assist(scans, out["poses"], x_orig, scan_times, image_times, image_poses, Rci,
                                                                 tci, intr, width, height, keypoints, pairs, matches,
@@ -802,7 +833,7 @@ def extrinsics_from_config(Rcl, Pcl, extrinsic_R, extrinsic_T):
 
 def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrinsic_R=np.eye(3), extrinsic_T=np.zeros(3),
                 image_sample_step=1, out_dir=None, device=0, colorize=False, map_quality=False, loop_closures=None, relax=None,
-                matching="db", match_opts=None, pair_selection=None, device_tracks=False, **cfg):
+                matching="db", match_opts=None, pair_selection=None, device_tracks=False, verify=None, **cfg):
     """initFromDatasetIO + runFullPipeline on a dataset directory; with out_dir, the refined LiDAR poses (TUM) and the COLMAP
     text files images.txt / points3D.txt the reference writes (src/lvba_system.cpp:2018-2137) are saved there.  images.txt is
     the reference's, character for character (tests/test_ref_system.py).
@@ -830,6 +861,9 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
     selected from LiDAR co-visibility are matched; the output gains pair_selection and out_dir gets pair_selection.json.
     device_tracks: False, or True: the feature tracks are built on the GPU (run_full_pipeline's device_tracks) -- worth it where
     the matcher delivers matches by the million.
+    verify: None (off), True, or a dict of verify_image_pairs' options, with every `matching` value: the matches are verified
+    geometrically before the visual stage (run_full_pipeline's verify_matches); the output gains match_verification and out_dir
+    gets match_verification.json.
     cfg as for run_full_pipeline, e.g. visual_loss=REFERENCE_HUBER, window_loss=("cauchy", 0.1), stage_loss=("huber", 0.05),
     camera_priors=lambda cams: lidar_camera_priors(cams, Rci, tci, 1e-3, 0.02)."""
     import os
@@ -871,7 +905,8 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
                             device=device, **({"match_fn": match_fn} if match_fn is not None else {}),
                             **({"match_depth": True} if matching == "depth" else {}),
                             **({"match_select": pair_selection} if pair_selection else {}),
-                            **({"device_tracks": True} if device_tracks else {}), images=(lambda k: D.read_image_bgr(os.path.join(img_dir, names[k]), width, height))
+                            **({"device_tracks": True} if device_tracks else {}), **({"verify_matches": verify} if verify else {}),
+                            images=(lambda k: D.read_image_bgr(os.path.join(img_dir, names[k]), width, height))
                             if colorize else None, **({"map_quality": map_quality} if map_quality else {}),
                             **({"loop_closures": loop_closures} if loop_closures else {}),
                             **({"relax": relax} if relax and loop_closures else {}), **cfg)
@@ -902,6 +937,10 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
             import json
             with open(os.path.join(out_dir, "pair_selection.json"), "w") as f:
                 json.dump(out["pair_selection"], f, indent=1)
+        if "match_verification" in out:
+            import json
+            with open(os.path.join(out_dir, "match_verification.json"), "w") as f:
+                json.dump(out["match_verification"], f, indent=1)
         if "pose_graph" in out:
             import json
             with open(os.path.join(out_dir, "pose_graph.json"), "w") as f:

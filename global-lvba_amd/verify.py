@@ -1,0 +1,133 @@
+"""Two-view verification of putative matches on the GPU: batched RANSAC over many image pairs at once (lvba_verify_*; the rule is
+in include/lvba_hip.h).  Opt-in: nothing imports this module unless verification is asked for."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib as L
+
+OPTION_NAMES = ("method", "hypotheses", "refine_rounds", "min_inliers", "max_error_px", "seed")
+EIGHT_POINT, KNOWN_ROTATION = 0, 1
+OK, TOO_FEW_MATCHES, NO_MODEL, TOO_FEW_INLIERS = 0, 1, 2, 3
+STATUS_NAMES = ("ok", "too_few_matches", "no_model", "too_few_inliers")
+
+
+def verify_opts(lib=None, **kw):
+    """lvba_verify_opts: the defaults (eight-point, 1024 hypotheses, 2 refits, 15 inliers, 4 px, seed 0) with `kw` over them."""
+    o = L.VerifyOpts()
+    (lib or L.load()).lvba_verify_default_opts(C.byref(o))
+    for k, v in kw.items():
+        if k not in OPTION_NAMES:
+            raise TypeError(f"unknown verification option {k!r}; one of {OPTION_NAMES}")
+        setattr(o, k, float(v) if k == "max_error_px" else int(v))
+    return o
+
+
+def _csr(matches):
+    ms = [np.asarray(m, np.int32).reshape(-1, 2) for m in matches]
+    off = np.zeros(len(ms) + 1, np.int64)
+    np.cumsum([len(m) for m in ms], out=off[1:])
+    flat = np.ascontiguousarray(np.concatenate(ms)) if ms else np.zeros((0, 2), np.int32)
+    return flat, off
+
+
+class Verifier:
+    """The undistorted keypoints of a set of images resident on a GPU.  keypoints: a sequence of [n_i, 2] pixel arrays (rounded to
+    fp32); intr (fx, fy, cx, cy, k1, k2, p1, p2); Rcw [M, 3, 3] = the rotations of T_cam<-world, or None (then only the pose-free
+    eight-point method is available)."""
+
+    def __init__(self, keypoints, intr, Rcw=None, device=0):
+        self.lib = L.load()
+        kps = [np.asarray(k, np.float32).reshape(-1, 2) for k in keypoints]
+        self.n_images = len(kps)
+        self.counts = np.array([len(k) for k in kps], np.int64)
+        self.off = np.zeros(self.n_images + 1, np.int64)
+        np.cumsum(self.counts, out=self.off[1:])
+        uv = np.ascontiguousarray(np.concatenate(kps)) if kps else np.zeros((0, 2), np.float32)
+        intr = np.ascontiguousarray(intr, np.float64).reshape(8)
+        R = None if Rcw is None else np.ascontiguousarray(Rcw, np.float64).reshape(self.n_images, 9)
+        self.has_rotations = R is not None
+        self.device = int(device)
+        self._h = C.c_void_p()
+        L.check(self.lib.lvba_verify_create(self.device, self.n_images, self.off.ctypes.data, uv.ctypes.data, intr.ctypes.data,
+                                            R.ctypes.data if R is not None else None, C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self.lib.lvba_verify_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def pairs_csr(self, pairs, matches, match_off, capacity=None, **opts):
+        """(inliers int32 [n, 2], inlier_off int64 [P + 1], report): the C call as it is.  `capacity` defaults to the number of
+        matches, which no result can exceed; inlier_off holds the true offsets also where they pass a smaller capacity."""
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        matches = np.ascontiguousarray(matches, np.int32).reshape(-1, 2)
+        match_off = np.ascontiguousarray(match_off, np.int64)
+        P = len(pairs)
+        if len(match_off) != P + 1:
+            raise ValueError("match_off must hold one offset per pair and the total")
+        o = verify_opts(self.lib, **opts)
+        cap = int(len(matches) if capacity is None else capacity)
+        inliers = np.zeros((max(cap, 0), 2), np.int32)
+        off = np.zeros(P + 1, np.int64)
+        E = np.zeros((P, 9))
+        status, n_inl, best_h = (np.zeros(P, np.int32) for _ in range(3))
+        L.check(self.lib.lvba_verify_pairs(self._h, P, pairs.ctypes.data, match_off.ctypes.data, matches.ctypes.data, C.byref(o), cap,
+                                           off.ctypes.data, inliers.ctypes.data, E.ctypes.data, status.ctypes.data, n_inl.ctypes.data,
+                                           best_h.ctypes.data))
+        report = dict(E=E.reshape(P, 3, 3), status=status, n_inliers=n_inl, n_matches=np.diff(match_off).astype(np.int64), best_h=best_h)
+        return inliers[:min(int(off[-1]), cap)], off, report
+
+    def pairs(self, pairs, matches, **opts):
+        """(inlier_matches, report): one int32 [m, 2] array per pair in the order of `pairs` (empty arrays are kept), and a dict
+        of arrays E [P, 3, 3], status, n_inliers, n_matches, best_h."""
+        flat, off = _csr(matches)
+        inl, ioff, report = self.pairs_csr(pairs, flat, off, **opts)
+        return [inl[ioff[p]:ioff[p + 1]] for p in range(len(ioff) - 1)], report
+
+    def hypotheses(self, a, b, matches, **opts):
+        """(E float64 [H, 3, 3], count int32 [H]): every hypothesis of the pair before the choice, without refinement; an
+        invalid one has E = 0 and count = -1."""
+        o = verify_opts(self.lib, **opts)
+        m = np.ascontiguousarray(matches, np.int32).reshape(-1, 2)
+        H = max(int(o.hypotheses), 0)
+        E, count = np.zeros((H, 9)), np.zeros(H, np.int32)
+        L.check(self.lib.lvba_verify_hypotheses(self._h, int(a), int(b), len(m), m.ctypes.data, C.byref(o), E.ctypes.data, count.ctypes.data))
+        return E.reshape(H, 3, 3), count
+
+    def score(self, a, b, matches, E, max_error_px=4.0):
+        """bool [m]: which matches of the pair (a, b) are inliers of E (lo -> hi)."""
+        m = np.ascontiguousarray(matches, np.int32).reshape(-1, 2)
+        E = np.ascontiguousarray(E, np.float64).reshape(9)
+        mask = np.zeros(len(m), np.uint8)
+        L.check(self.lib.lvba_verify_score(self._h, int(a), int(b), len(m), m.ctypes.data, E.ctypes.data, float(max_error_px), mask.ctypes.data))
+        return mask.astype(bool)
+
+
+def verify_pairs(keypoints, pairs, matches, intr, Rcw=None, device=0, **opts):
+    """Verifier(keypoints, intr, Rcw).pairs(pairs, matches) in one call."""
+    with Verifier(keypoints, intr, Rcw=Rcw, device=device) as v:
+        return v.pairs(pairs, matches, **opts)
+
+
+def summary(pairs, report):
+    """The report as plain Python, for a JSON file: per pair the status and the counts, plus the totals."""
+    per = [dict(pair=[int(a), int(b)], status=STATUS_NAMES[int(s)], n_matches=int(m), n_inliers=int(n))
+           for (a, b), s, m, n in zip(np.asarray(pairs).reshape(-1, 2), report["status"], report["n_matches"], report["n_inliers"])]
+    ok = np.asarray(report["status"]) == OK
+    return dict(pairs=per, n_pairs=len(per), n_pairs_ok=int(ok.sum()), n_matches=int(np.sum(report["n_matches"])),
+                n_inliers=int(np.asarray(report["n_inliers"])[ok].sum()))

@@ -1234,6 +1234,86 @@ int32_t lvba_trackgraph_orders(lvba_trackgraph_t g, int64_t n, const int64_t *co
                                float *obs_uv /* [.][2]; may be NULL; needs keypoints_uv */);
 int32_t lvba_trackgraph_destroy(lvba_trackgraph_t g);
 
+/* ---- two-view verification of putative matches: batched RANSAC (opt-in)
+ *   The reference reads geometrically verified inlier matches from its COLMAP database (loadFromColmapDB); matches that come from
+ *   lvba_match_pairs, or from anywhere else, have seen no geometry, or only the geometry of poses that may themselves be in doubt.
+ *   This stage estimates an essential matrix per image pair from the matches alone (method 0) or from the matches and the relative
+ *   ROTATION of the two cameras (method 1) and keeps the matches that agree with it.  The rule below is this project's own
+ *   definition, restated in numpy in tests/verify_oracle.py; it is NOT pinned against COLMAP's estimators.
+ *   Inputs.  Keypoints (u, v) are fp32 pixels, undistorted once on the device (trk_undistort with intr; x^ = (x, y, 1), NaN where it
+ *     fails).  pairs [P][2] = (a, b), a != b, either orientation; the matches of pair p are rows match_off[p] .. match_off[p + 1] of
+ *     matches [][2] = (keypoint of a, keypoint of b), the arrays lvba_match_pairs writes.  "lo" is the image with the smaller index,
+ *     "hi" the other; E maps lo to hi, x^_hi^T E x^_lo = 0 (the guided matcher's convention).  A pair given as (hi, lo) gives the
+ *     same E and the same inliers as (lo, hi), in the caller's column order.
+ *   Inlier test.  Match i is an inlier of E iff the guided matcher's gate passes it: with l = E x^_lo, l' = E^T x^_hi and
+ *     tau = 2 max_error_px / (fx + fy),  (x^_hi . l)^2 <= tau^2 (l0^2 + l1^2 + l'0^2 + l'1^2)  (match_line_lo, match_norm_hi,
+ *     match_gate of csrc/match_device.h, evaluated without contraction).  A NaN point is never an inlier.
+ *   Sampling.  Hypothesis h of the pair draws k distinct positions of the pair's match list.  Draw j is r_j = mix(key + G (j + 1)),
+ *     key = mix(mix(mix(seed + G) ^ (lo << 32 | hi)) + G (h + 1)), mix = splitmix64's finaliser, G = 0x9E3779B97F4A7C15: a
+ *     function of (seed, lo, hi, h, j) alone -- not of the pair's place in the call, the grid or the lane.  r is mapped onto [0, n)
+ *     as the high half of r n.  Draw j is taken from [0, m - j) and stepped past the positions already chosen, in ascending order
+ *     (a partial Fisher-Yates shuffle without its array).  A pair verified alone, in a batch, or in a batch in another order
+ *     gives the same bytes.
+ *   Method 0, LVBA_VERIFY_EIGHT_POINT (pose-free), k = 8.  Row i of the 8 x 9 system is x^_hi (x) x^_lo.  vec(E) is its null vector
+ *     by Gauss-Jordan elimination with full pivoting in the order of operations of verify_eight_solve (csrc/verify_device.h): the
+ *     pivot of step s is the largest |entry| of rows s.. and columns s.., the lowest (row, column) of a tie; row exchange, column
+ *     exchange, the pivot row divided, every other row reduced.  E is scaled to unit Frobenius norm.  The hypothesis is INVALID
+ *     if a pivot is <= VERIFY_PIVOT_REL (1e-10) times the system's largest entry (repeated matches, collinear or otherwise
+ *     degenerate samples) or a sample point is NaN.  Hypotheses are not projected onto the essential manifold; the test above
+ *     does not need it.  THIS SOLVER IS DEGENERATE ON A SCENE THAT IS ONE PLANE (the system has rank 6 there): use method 1.
+ *   Method 1, LVBA_VERIFY_KNOWN_ROTATION (rotation-aided), k = 2, needs Rcw at lvba_verify_create.  R = R_hi R_lo^T is trusted
+ *     (odometry and the IMU give relative rotation to a fraction of a degree), the translation is not (position is what drifts).
+ *     c_i = x^_hi,i x (R x^_lo,i), t = c_1 x c_2, E = [t]x R scaled to unit norm; INVALID if |t|^2 <= VERIFY_T_REL2 (1e-20)
+ *     |c_1|^2 |c_2|^2 or a sample point is NaN.  Not degenerate on planes, and two-point samples survive low inlier ratios.
+ *   Choice.  A hypothesis scores its inlier count, an invalid one -1; the highest count wins, the lowest h of a tie.  Integers
+ *     only.  hypotheses (default 1024) is fixed, there is no early exit: 1 - (1 - w^k)^H at H = 1024 is 0.98 for method 0 at an
+ *     inlier ratio w = 0.5 and above 0.9999 from w = 0.6; for method 1 it is above 0.9999 already at w = 0.2.
+ *   Local refinement (refine_rounds, default 2, 0 = off).  The winner is refitted over its inliers and the refit kept only if its
+ *     count is strictly larger.  Method 0: the eigenvector of the smallest eigenvalue of N = sum a a^T (9 x 9, cyclic Jacobi, 12
+ *     sweeps), projected onto the essential manifold through the eigenvectors of E^T E.  Method 1: t = the smallest eigenvector
+ *     of sum c c^T.  The refits go through libm; they are held to a measured tolerance, not to the bit.
+ *   Status per pair.  LVBA_VERIFY_OK; LVBA_VERIFY_TOO_FEW_MATCHES: m < max(k, min_inliers) (no hypothesis is formed, E = 0,
+ *     best_h = -1); LVBA_VERIFY_NO_MODEL: every hypothesis invalid (E = 0, best_h = -1); LVBA_VERIFY_TOO_FEW_INLIERS: count <
+ *     min_inliers (default 15, the bound COLMAP's two-view geometry uses by default; E, count and best_h are reported).  A pair
+ *     that is not OK contributes no inlier matches; it keeps its place in every output array.
+ *   lvba_verify_create: kp_off [n_images + 1] from 0, keypoints_uv [kp_off[n_images]][2], intr = (fx, fy, cx, cy, k1, k2, p1, p2),
+ *   Rcw [n_images][9] (T_cam<-world rotations) or NULL (method 0 only).
+ *   lvba_verify_pairs: all pairs of the call in one grid.  inliers [capacity][2] in (pair, original order), inlier_off [n_pairs + 1]
+ *   the first inlier of each pair and, last, the true number of inliers -- also where it exceeds capacity; only the first
+ *   `capacity` are written (the convention of lvba_match_pairs).  E [n_pairs][9], status, n_inliers, best_h [n_pairs].
+ *   lvba_verify_hypotheses: the diagnostic call, one pair: E [hypotheses][9] and count [hypotheses] of every hypothesis before the
+ *   choice, without refinement (invalid: E = 0, count = -1).  It reads method, hypotheses, max_error_px and seed only.
+ *   lvba_verify_score: mask [n_matches] (0 / 1) of the inlier test under a given E (lo -> hi).
+ *   LVBA_ERR_ARG: method 1 on a handle without rotations, a == b or an image out of range, a match index outside its image,
+ *   hypotheses < 1, a null required pointer or an option out of range.  lvba_version() is unchanged; a client detects these calls
+ *   by looking lvba_verify_create up. */
+#define LVBA_VERIFY_EIGHT_POINT 0
+#define LVBA_VERIFY_KNOWN_ROTATION 1
+#define LVBA_VERIFY_OK 0
+#define LVBA_VERIFY_TOO_FEW_MATCHES 1
+#define LVBA_VERIFY_NO_MODEL 2
+#define LVBA_VERIFY_TOO_FEW_INLIERS 3
+typedef struct lvba_verify_s *lvba_verify_t;
+typedef struct lvba_verify_opts {
+    int32_t method;        /* LVBA_VERIFY_EIGHT_POINT (default) or LVBA_VERIFY_KNOWN_ROTATION */
+    int32_t hypotheses;    /* 1024 */
+    int32_t refine_rounds; /* 2; 0 = off */
+    int32_t min_inliers;   /* 15 */
+    double max_error_px;   /* 4.0, the guided matcher's max_epipolar_px */
+    uint64_t seed;         /* 0 */
+} lvba_verify_opts;        /* 32 bytes */
+void    lvba_verify_default_opts(lvba_verify_opts *o);
+int32_t lvba_verify_create(int32_t device, int32_t n_images, const int64_t *kp_off, const float *keypoints_uv, const double *intr,
+                           const double *Rcw_or_null, lvba_verify_t *out);
+int32_t lvba_verify_destroy(lvba_verify_t v);
+int32_t lvba_verify_pairs(lvba_verify_t v, int64_t n_pairs, const int32_t *pairs, const int64_t *match_off, const int32_t *matches,
+                          const lvba_verify_opts *o, int64_t capacity, int64_t *inlier_off, int32_t *inliers, double *E,
+                          int32_t *status, int32_t *n_inliers, int32_t *best_h);
+int32_t lvba_verify_hypotheses(lvba_verify_t v, int32_t a, int32_t b, int64_t n_matches, const int32_t *matches,
+                               const lvba_verify_opts *o, double *E, int32_t *count);
+int32_t lvba_verify_score(lvba_verify_t v, int32_t a, int32_t b, int64_t n_matches, const int32_t *matches, const double *E,
+                          double max_error_px, uint8_t *mask);
+
 #ifdef __cplusplus
 }
 #endif
