@@ -14,11 +14,11 @@ SYMBOLS = [
     "lvba_version", "lvba_last_error", "lvba_device_count", "lvba_balm_default_opts", "lvba_shard_range",
     "lvba_balm_create", "lvba_balm_create_dev", "lvba_balm_destroy", "lvba_balm_configure", "lvba_balm_info", "lvba_balm_cost",
     "lvba_balm_eval", "lvba_balm_eval_blocks", "lvba_balm_solve", "lvba_balm_refine", "lvba_balm_lm_begin", "lvba_balm_lm_step",
-    "lvba_balm_lm_end", "lvba_balm_set_groups", "lvba_balm_refine_groups", "lvba_balm_set_profiling", "lvba_balm_get_profile", "lvba_balm_get_ordering", "lvba_balm_nd_model",
+    "lvba_balm_lm_end", "lvba_balm_set_groups", "lvba_balm_refine_groups", "lvba_balm_set_profiling", "lvba_balm_get_profile", "lvba_balm_get_ordering", "lvba_balm_nd_model", "lvba_balm_pair_layout",
     "lvba_balm_set_priors", "lvba_balm_prior_residuals", "lvba_cov_default_opts", "lvba_balm_covariance",
     "lvba_balm_set_loss", "lvba_balm_voxel_residuals",
     "lvba_dist_unique_id", "lvba_balm_dist_init", "lvba_balm_dist_init_external", "lvba_visual_dist_init_external",
-    "lvba_visual_default_opts", "lvba_visual_create", "lvba_visual_destroy", "lvba_visual_cost", "lvba_visual_linearize", "lvba_visual_solve", "lvba_visual_info", "lvba_visual_dist_init",
+    "lvba_visual_default_opts", "lvba_visual_create", "lvba_visual_destroy", "lvba_visual_cost", "lvba_visual_linearize", "lvba_visual_solve", "lvba_visual_info", "lvba_visual_pair_layout", "lvba_visual_dist_init",
     "lvba_visual_refine", "lvba_visual_set_loss", "lvba_visual_residual_sq", "lvba_visual_set_priors", "lvba_visual_prior_residuals",
     "lvba_voxel_default_opts", "lvba_voxmap_build", "lvba_voxmap_destroy", "lvba_voxmap_info", "lvba_voxmap_export",
     "lvba_voxmap_to_balm", "lvba_voxmap_find_planes", "lvba_scans_create", "lvba_scans_destroy", "lvba_voxmap_build_scans",
@@ -73,6 +73,24 @@ class BalmInfo(C.Structure):
                 ("twist_panels", C.c_int32), ("solve_ranks", C.c_int32), ("trial_linearised", C.c_int32), ("y_fp32", C.c_int32),
                 ("nd_kind", C.c_int32), ("nd_arcs", C.c_int32), ("nd_sep_poses", C.c_int32), ("nd_sep_band_blocks", C.c_int32),
                 ("nd_model_band_ms", C.c_double), ("nd_model_nd_ms", C.c_double)]
+
+
+class PairLayout(C.Structure):
+    _fields_ = [("form", C.c_int32), ("cut", C.c_int32), ("n_items", C.c_int64), ("n_multi", C.c_int64), ("n_partial", C.c_int64),
+                ("window_voxels", C.c_int64), ("longest_item", C.c_int64), ("longest_multi", C.c_int64)]
+
+
+def pair_layout(fn, handle):
+    """lvba_balm_pair_layout / lvba_visual_pair_layout: the struct's fields plus item_len / item_slot [n_items] (int64)."""
+    o = PairLayout()
+    check(fn(handle, C.byref(o), None, None, 0))
+    n = int(o.n_items)
+    item_len, item_slot = np.zeros(n, np.int64), np.zeros(n, np.int64)
+    if n:
+        check(fn(handle, C.byref(o), item_len.ctypes.data, item_slot.ctypes.data, n))
+    d = {f: getattr(o, f) for f, _ in o._fields_}
+    d["item_len"], d["item_slot"] = item_len, item_slot
+    return d
 
 
 class NdModel(C.Structure):
@@ -339,6 +357,8 @@ def load():
     lib.lvba_balm_get_profile.argtypes = [H, C.POINTER(Prof), C.c_int32]
     lib.lvba_balm_get_ordering.argtypes = [H, i32p]
     lib.lvba_balm_nd_model.argtypes = [H, C.c_int32, C.POINTER(NdModel)]
+    lib.lvba_balm_pair_layout.argtypes = [H, C.POINTER(PairLayout), C.c_void_p, C.c_void_p, C.c_int64]
+    lib.lvba_visual_pair_layout.argtypes = [H, C.POINTER(PairLayout), C.c_void_p, C.c_void_p, C.c_int64]
     lib.lvba_balm_set_priors.argtypes = [H, C.c_int32, C.c_void_p]
     lib.lvba_balm_prior_residuals.argtypes = [H, f64p, C.c_void_p, C.POINTER(C.c_double)]
     lib.lvba_cov_default_opts.argtypes = [C.POINTER(CovOpts)]

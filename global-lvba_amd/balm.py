@@ -162,6 +162,11 @@ class BalmProblem:
         L.check(self.lib.lvba_balm_info(self._h, C.byref(i)))
         return {f: getattr(i, f) for f, _ in i._fields_}
 
+    def pair_layout(self):
+        """how the pair pass was laid out (lvba_balm_pair_layout): form, cut, n_items, n_multi, n_partial, window_voxels,
+        longest_item, longest_multi, and per item item_len / item_slot (-1 - k: partial block k)"""
+        return L.pair_layout(self.lib.lvba_balm_pair_layout, self._h)
+
     def nd_model(self, n_ranks):
         """the nested-dissection plan of this problem's graph on n_ranks ranks and its cost model (lvba_balm_nd_model)"""
         m = L.NdModel()

@@ -36,6 +36,9 @@ struct BlockSys {
     bool pair_col = false;            // which pair kernel the item lists were cut for
     bool y32 = false;                 // LVBA_Y32=1 on a LiDAR handle whose lists use the column kernel: fp32 Y records (experiment)
     int64_t n_items = 0, n_multi = 0; // work items of the pair pass (>= nnzb), blocks cut into several items
+    // what bs_pair_layout reports of the lists (set by bs_build): the cut the items were made with, voxels per window (0: not
+    // windowed), partial blocks, the longest item and the most partial blocks summed into one block
+    int64_t pair_cut = 0, pair_window = 0, n_partial = 0, longest_item = 0, longest_multi = 0;
     int64_t *d_multi_off = nullptr, *d_multi_slot = nullptr, *d_multi_idx = nullptr;
     double *d_partial = nullptr;
     int32_t *d_group_of_pos = nullptr, *d_csc_f = nullptr, *d_pos_of = nullptr;
@@ -128,6 +131,8 @@ int32_t bs_ranks_agree(BlockSys &bs, const int64_t *v, int n, bool *same);
 // slots of the structurally non-zero blocks of the block-band store (ascending, diagonal included); their download [n][36]
 int32_t bs_pattern_slots(BlockSys &bs, lvba::hvec<int64_t> &slots);
 int32_t bs_download_blocks(BlockSys &bs, const int64_t *slots, int64_t n, double *out);
+// read-only view of the pair-pass layout (lvba_balm_pair_layout / lvba_visual_pair_layout, include/lvba_hip.h); the system is built
+int32_t bs_pair_layout(BlockSys &bs, lvba_pair_layout_t *out, int64_t *item_len, int64_t *item_slot, int64_t cap);
 int32_t bs_dist_init(BlockSys &bs, int32_t n_ranks, int32_t rank, const char uid[128], int64_t *group_count_inout);
 int32_t bs_dist_init_external(BlockSys &bs, int32_t n_ranks, int32_t rank, lvba_allreduce_fn fn, void *ctx, int64_t *group_count_inout);
 int32_t bs_nd_model(BlockSys &bs, int32_t n_ranks, double *t_band, double *t_nd, int32_t *arcs, int32_t *sep_poses, int32_t *sep_bb,

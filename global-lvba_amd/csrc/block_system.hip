@@ -280,6 +280,29 @@ int32_t bs_download_blocks(BlockSys &bs, const int64_t *slots, int64_t n, double
     return rc;
 }
 
+int32_t bs_pair_layout(BlockSys &bs, lvba_pair_layout_t *out, int64_t *item_len, int64_t *item_slot, int64_t cap)
+{
+    if (!bs.built) return lvba_fail(LVBA_ERR_STATE, "the block system is not built");
+    if (out) {
+        memset(out, 0, sizeof *out);
+        out->form = bs.pair_col ? (bs.y32 ? 2 : 1) : 0;
+        out->cut = (int32_t)bs.pair_cut;
+        out->n_items = bs.n_items; out->n_multi = bs.n_multi; out->n_partial = bs.n_partial;
+        out->window_voxels = bs.pair_window; out->longest_item = bs.longest_item; out->longest_multi = bs.longest_multi;
+    }
+    if (!item_len && !item_slot) return LVBA_OK;
+    if (cap < bs.n_items) return lvba_fail(LVBA_ERR_ARG, "capacity %lld for %lld pair items", (long long)cap, (long long)bs.n_items);
+    HIPCHK(hipSetDevice(bs.device));
+    HIPCHK(hipStreamSynchronize(bs.stream));
+    if (item_len && bs.n_items) {
+        lvba::hvec<int64_t> off((size_t)bs.n_items + 1);
+        HIPCHK(hipMemcpy(off.data(), bs.d_blk_off, (size_t)(bs.n_items + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+        for (int64_t i = 0; i < bs.n_items; ++i) item_len[i] = off[(size_t)i + 1] - off[(size_t)i];
+    }
+    if (item_slot && bs.n_items) HIPCHK(hipMemcpy(item_slot, bs.d_blk_slot, (size_t)bs.n_items * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return LVBA_OK;
+}
+
 static double bs_now_ms()
 {
     struct timespec ts;
@@ -563,6 +586,21 @@ int32_t bs_build(BlockSys &bs, int32_t N, int64_t G, const int64_t *voff, const 
                              multi_off, multi_slot, multi_idx, n_partial); // host_tables.h
             bs.n_items = (int64_t)item_dst.size();
             bs.n_multi = (int64_t)multi_slot.size();
+            bs.pair_cut = bs.pair_col ? LVBA_PAIR_CUT : pair_cut_length(Q);
+            bs.pair_window = window_groups > 0 ? window_groups : 0;
+            bs.n_partial = n_partial;
+            bs.longest_item = bs.longest_multi = 0;
+            for (int64_t i = 0; i < bs.n_items; ++i) bs.longest_item = std::max(bs.longest_item, item_off[(size_t)i + 1] - item_off[(size_t)i]);
+            for (int64_t m = 0; m < bs.n_multi; ++m) bs.longest_multi = std::max(bs.longest_multi, multi_off[(size_t)m + 1] - multi_off[(size_t)m]);
+            // balm_pair_col_kernel fetches a wavefront's lists in one fixed batch of LVBA_PC_ITEMS * LVBA_PAIR_CUT pairs and clamps its
+            // re-reads to the last pair of an item: every item it is given has 1 .. LVBA_PAIR_CUT pairs
+            if (bs.pair_col)
+                for (int64_t i = 0; i < bs.n_items; ++i) {
+                    const int64_t len = item_off[(size_t)i + 1] - item_off[(size_t)i];
+                    if (len < 1 || len > LVBA_PAIR_CUT)
+                        return lvba_fail(LVBA_ERR_STATE, "pair item %lld has %lld pairs: the column kernel takes 1 .. %d", (long long)i,
+                                         (long long)len, LVBA_PAIR_CUT);
+                }
             if (n_partial) TRY(bs_dmalloc(bs, &bs.d_partial, 36 * n_partial));
             if (bs.n_multi) {
                 TRY(bs_dmalloc(bs, &bs.d_multi_off, bs.n_multi + 1));

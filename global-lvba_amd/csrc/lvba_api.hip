@@ -400,6 +400,13 @@ extern "C" int32_t lvba_balm_info(lvba_balm_t h, lvba_balm_info_t *info)
     return LVBA_OK;
 }
 
+extern "C" int32_t lvba_balm_pair_layout(lvba_balm_t h, lvba_pair_layout_t *out, int64_t *item_len, int64_t *item_slot, int64_t cap)
+{
+    if (!h || !out) return fail(LVBA_ERR_ARG, "NULL argument");
+    TRY(finalize(h));
+    return bs_pair_layout(h->bs, out, item_len, item_slot, cap);
+}
+
 extern "C" int32_t lvba_balm_get_ordering(lvba_balm_t h, int32_t *perm)
 {
     if (!h || !perm) return fail(LVBA_ERR_ARG, "NULL argument");

@@ -452,6 +452,13 @@ extern "C" int32_t lvba_visual_info(lvba_visual_t h, lvba_balm_info_t *info)
     return LVBA_OK;
 }
 
+extern "C" int32_t lvba_visual_pair_layout(lvba_visual_t h, lvba_pair_layout_t *out, int64_t *item_len, int64_t *item_slot, int64_t cap)
+{
+    if (!h || !out) return fail(LVBA_ERR_ARG, "NULL argument");
+    TRY(finalize(h));
+    return bs_pair_layout(h->bs, out, item_len, item_slot, cap);
+}
+
 extern "C" int32_t lvba_visual_residual_sq(lvba_visual_t h, const double *q, const double *t, const double *X, double *obs_sq,
                                            double *plane_sq)
 {

@@ -131,6 +131,10 @@ class VisualProblem:
         L.check(self.lib.lvba_visual_info(self._h, C.byref(i)))
         return {f: getattr(i, f) for f, _ in i._fields_}
 
+    def pair_layout(self):
+        """the pair-pass layout of the reduced camera system (lvba_visual_pair_layout; fields as BalmProblem.pair_layout)"""
+        return L.pair_layout(self.lib.lvba_visual_pair_layout, self._h)
+
     @staticmethod
     def default_opts(**kw):
         o = L.VisualOpts()

@@ -150,6 +150,24 @@ int32_t lvba_balm_destroy(lvba_balm_t h);
 int32_t lvba_balm_configure(lvba_balm_t h, int32_t ordering, double band_frac);
 int32_t lvba_balm_info(lvba_balm_t h, lvba_balm_info_t *info);
 
+/* Read-only view of how the pair pass (the off-diagonal pose blocks -sum Y_i Y_j^T) was laid out for this handle: which kernel
+ * runs and the work items it walks.  An item is a run of pairs of one block (of one voxel window, when the lists are windowed),
+ * cut at `cut` pairs; a block made of several items is summed from partial blocks afterwards. */
+typedef struct {
+    int32_t form;           /* 0: 16-lane kernel, 1: column-per-lane kernel, 2: column-per-lane kernel on fp32 records (LVBA_Y32=1) */
+    int32_t cut;            /* longest item the lists were cut for, pairs */
+    int64_t n_items;        /* work items */
+    int64_t n_multi;        /* blocks summed from several partial blocks */
+    int64_t n_partial;      /* partial blocks (= items that do not write their block directly) */
+    int64_t window_voxels;  /* voxels per window of the lists; 0: not windowed */
+    int64_t longest_item;   /* pairs */
+    int64_t longest_multi;  /* most partial blocks summed into one block */
+} lvba_pair_layout_t;
+/* item_len / item_slot (both or either may be NULL; capacity `cap` >= n_items entries otherwise -- size them with a first call):
+ * every item's pair count and destination in item order, a slot J * (band_blocks + 1) + (I - J) of the block-band store in the
+ * SOLVER's pose order (I > J), or -1 - k for partial block k. */
+int32_t lvba_balm_pair_layout(lvba_balm_t h, lvba_pair_layout_t *out, int64_t *item_len, int64_t *item_slot, int64_t cap);
+
 /* only_residual: cost at `poses` [N][12]; is_avg divides by the (global) voxel count. */
 int32_t lvba_balm_cost(lvba_balm_t h, const double *poses, int32_t is_avg, double *cost);
 
@@ -404,6 +422,8 @@ int32_t lvba_visual_destroy(lvba_visual_t h);
  * plane (the active ones), n_factors = their observations, n_pairs, n_blocks (off-diagonal camera blocks of the reduced
  * system), band_blocks, use_band, hess_bytes, device_bytes. */
 int32_t lvba_visual_info(lvba_visual_t h, lvba_balm_info_t *info);
+/* The pair-pass layout of the reduced camera system (as lvba_balm_pair_layout: items are runs of camera pairs of one block). */
+int32_t lvba_visual_pair_layout(lvba_visual_t h, lvba_pair_layout_t *out, int64_t *item_len, int64_t *item_slot, int64_t cap);
 
 /* Multi-GPU: landmark tracks are sharded over the ranks (any partition; contiguous ranges as for the voxels), the cameras are
  * replicated.  Every rank creates its handle from ITS tracks (X, plane, valid and the observation arrays of that shard) and

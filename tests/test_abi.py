@@ -30,6 +30,7 @@ def test_struct_layouts_match_header(pkg):
     L = pkg._lib
     assert ctypes.sizeof(L.BalmOpts) == 32 and ctypes.sizeof(L.LmTrace) == 64
     assert ctypes.sizeof(L.BalmInfo) == 136 and ctypes.sizeof(L.Prof) == 80 and ctypes.sizeof(L.NdModel) == 40
+    assert ctypes.sizeof(L.PairLayout) == 56          # a struct of its own: lvba_balm_info_t did not grow
     o = pkg.BalmProblem.default_opts()
     assert (o.max_iter, o.u0, o.v0, o.rel_tol) == (10, 0.01, 2.0, 1e-6)      # bavoxel.hpp:664,686,760
 
@@ -42,7 +43,7 @@ def test_every_struct_has_the_size_the_c_compiler_gives_it(pkg, tmp_path):
              ("lvba_prof_t", L.Prof), ("lvba_visual_opts", L.VisualOpts), ("lvba_visual_trace", L.VisualTrace),
              ("lvba_voxel_opts", L.VoxelOpts), ("lvba_voxmap_info_t", L.VoxmapInfo), ("lvba_window_opts", L.WindowOpts),
              ("lvba_window_info", L.WindowInfo), ("lvba_lidar_ba_opts", L.LidarBaOpts), ("lvba_lidar_ba_report", L.LidarBaReport),
-             ("lvba_fuse_opts", L.FuseOpts), ("lvba_nd_model_t", L.NdModel)]
+             ("lvba_fuse_opts", L.FuseOpts), ("lvba_nd_model_t", L.NdModel), ("lvba_pair_layout_t", L.PairLayout)]
     src = tmp_path / "sizes.c"
     src.write_text('#include <stdio.h>\n#include "lvba_hip.h"\nint main(void){' +
                    "".join(f'printf("%zu\\n", sizeof({n}));' for n, _ in pairs) + "return 0;}\n")
@@ -51,6 +52,20 @@ def test_every_struct_has_the_size_the_c_compiler_gives_it(pkg, tmp_path):
     sizes = [int(v) for v in subprocess.check_output([exe]).split()]
     for (name, cls), sz in zip(pairs, sizes):
         assert ctypes.sizeof(cls) == sz, (name, ctypes.sizeof(cls), sz)
+
+
+def test_pair_layout_entry_points(lib, pkg):
+    """lvba_balm_pair_layout / lvba_visual_pair_layout: exported, declared in the header with one signature, mirrored by the package,
+    and they refuse NULL arguments before anything touches a device."""
+    hdr = open(os.path.join(ROOT, "include", "lvba_hip.h")).read()
+    for name, handle in (("lvba_balm_pair_layout", "lvba_balm_t"), ("lvba_visual_pair_layout", "lvba_visual_t")):
+        assert name in pkg._lib.SYMBOLS and hasattr(lib, name)
+        assert re.search(name + r"\(" + handle + r" h, lvba_pair_layout_t \*out, int64_t \*item_len, int64_t \*item_slot, int64_t cap\);", hdr)
+        out = pkg._lib.PairLayout()
+        assert getattr(lib, name)(None, ctypes.byref(out), None, None, 0) == pkg._lib.ERR_ARG
+    assert [f for f, _ in pkg._lib.PairLayout._fields_] == ["form", "cut", "n_items", "n_multi", "n_partial", "window_voxels",
+                                                            "longest_item", "longest_multi"]
+    assert hasattr(pkg.BalmProblem, "pair_layout") and hasattr(pkg.VisualProblem, "pair_layout")
 
 
 def test_shard_range_matches_reference_slicing(pkg):
