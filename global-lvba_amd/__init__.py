@@ -9,6 +9,9 @@ from .visual import DepthImages, VisualProblem, fuse_tracks, optimize_camera_pos
 from .voxel import Scans, VoxelMap
 from .mapq import map_quality_points, map_quality_scans
 from . import register
+from . import features
+from .features import extract as extract_features, sift_opts
 
 __all__ = ["BALM2", "IMUST", "VOX_HESS", "BalmProblem", "Prior", "shard_range", "VisualProblem", "optimize_camera_poses", "VoxelMap", "Scans",
-           "map_quality_scans", "map_quality_points", "register", "_lib"]
+           "map_quality_scans", "map_quality_points", "register", "features", "extract_features", "sift_opts",
+           "_lib"]

@@ -41,6 +41,8 @@ SYMBOLS = [
     "lvba_trackgraph_create", "lvba_trackgraph_components", "lvba_trackgraph_orders", "lvba_trackgraph_destroy",
     "lvba_verify_default_opts", "lvba_verify_create", "lvba_verify_destroy", "lvba_verify_pairs", "lvba_verify_hypotheses",
     "lvba_verify_score",
+    "lvba_sift_default_opts", "lvba_sift_tile_width", "lvba_sift_blur_taps", "lvba_sift_extract", "lvba_sift_profile", "lvba_sift_pyramid",
+    "lvba_sift_candidates",
 ]
 
 OK, ERR_ARG, ERR_DEVICE, ERR_NOMEM, ERR_UNSUPPORTED, ERR_DIST, ERR_STATE = 0, -1, -2, -3, -4, -5, -6
@@ -239,6 +241,13 @@ class VerifyOpts(C.Structure):
     """lvba_verify_opts"""
     _fields_ = [("method", C.c_int32), ("hypotheses", C.c_int32), ("refine_rounds", C.c_int32), ("min_inliers", C.c_int32),
                 ("max_error_px", C.c_double), ("seed", C.c_uint64)]
+
+
+class SiftOpts(C.Structure):
+    """lvba_sift_opts"""
+    _fields_ = [("first_octave", C.c_int32), ("n_intervals", C.c_int32), ("sigma0", C.c_double), ("dog_threshold", C.c_double),
+                ("edge_threshold", C.c_double), ("orientation_window", C.c_double), ("max_orientations", C.c_int32),
+                ("max_features", C.c_int32), ("chunk_images", C.c_int32), ("reserved", C.c_int32)]
 
 
 class CovisOpts(C.Structure):
@@ -507,6 +516,17 @@ def load():
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.lvba_verify_hypotheses.argtypes = [H, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(VerifyOpts), C.c_void_p, C.c_void_p]
     lib.lvba_verify_score.argtypes = [H, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
+    lib.lvba_sift_default_opts.argtypes = [C.POINTER(SiftOpts)]
+    lib.lvba_sift_default_opts.restype = None
+    lib.lvba_sift_tile_width.argtypes = []
+    lib.lvba_sift_blur_taps.argtypes = [C.POINTER(SiftOpts), C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]
+    lib.lvba_sift_extract.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(SiftOpts), C.c_int64,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.lvba_sift_profile.argtypes = [C.c_void_p]
+    lib.lvba_sift_pyramid.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(SiftOpts), C.c_int32, C.c_void_p,
+                                      C.c_void_p]
+    lib.lvba_sift_candidates.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(SiftOpts), C.c_int64, C.c_void_p,
+                                         C.c_void_p, C.POINTER(C.c_int64)]
     lib.lvba_scans_info.argtypes = [H, C.POINTER(C.c_int32), C.c_void_p]
     lib.lvba_scans_download.argtypes = [H, C.c_int32, np.ctypeslib.ndpointer(np.float32, flags="C")]
     for name in SYMBOLS:

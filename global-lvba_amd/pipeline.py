@@ -13,9 +13,10 @@ LiDAR poses, camera poses and landmarks", with every compute step in liblvba_hip
     LvbaSystem::VisualizeOptComparison        src/lvba_system.cpp:1932-2144 the LiDAR map coloured from the images, after and
                                                                             before the refinement (colorize_maps)
 
-Out of scope, as in DESIGN.md: SIFT extraction / matching (SiftGPU, `extractAndMatchFeaturesGPU`) -- keypoints and inlier
-matches are inputs here, e.g. from a COLMAP database through dataset.load_colmap_db, which is the reference's own alternative
-(`loadFromColmapDB`); ROS publishing and the OpenCV overlays.
+Key points and matches are inputs of run_full_pipeline -- from a COLMAP database through dataset.load_colmap_db, the reference's own
+alternative (`loadFromColmapDB`), or from the images themselves through extract_image_features and match_image_pairs, this
+project's reading of `extractAndMatchFeaturesGPU` (features.py, match.py; not pinned against SiftGPU).  Out of scope, as in
+DESIGN.md: writing a COLMAP database, ROS publishing and the OpenCV overlays.
 """
 from __future__ import annotations
 
@@ -663,6 +664,21 @@ def match_image_pairs(descriptors, pairs, keypoints=None, Rcw=None, tcw=None, in
     return M.match_pairs(descriptors, pairs, keypoints=keypoints, intr=intr, Rcw=Rcw, tcw=tcw, device=device, depth=depth, **opts)
 
 
+def extract_image_features(read_image, n_images, device=0, batch=32, **opts):
+    """SIFT features of images 0 .. n_images - 1 on the GPU (features.extract; the rule is in include/lvba_hip.h):
+    read_image(k) -> uint8 [h, w, 3] in B, G, R order or [h, w] grey, all of one size; `batch` images are read and handed to the
+    device at a time.  Returns (keypoints, descriptors): per image float32 [n_i, 4] = (x, y, sigma, theta) and uint8 [n_i, 128],
+    the form match_image_pairs takes.  opts: features.sift_opts' keywords."""
+    from . import features as F
+    kps, descs = [], []
+    for k0 in range(0, int(n_images), max(1, int(batch))):
+        imgs = [read_image(k) for k in range(k0, min(int(n_images), k0 + max(1, int(batch))))]
+        kp, ds, _ = F.extract(imgs, device=device, **opts)
+        kps += kp
+        descs += ds
+    return kps, descs
+
+
 def verify_image_pairs(keypoints, pairs, matches, intr, Rcw=None, device=0, **opts):
     """Geometric verification of putative matches (verify.Verifier): per image pair an essential matrix by RANSAC
     on the GPU, all pairs in one grid, and the matches that agree with it.  matches: one [m, 2] array per pair, as
@@ -833,7 +849,8 @@ def extrinsics_from_config(Rcl, Pcl, extrinsic_R, extrinsic_T):
 
 def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrinsic_R=np.eye(3), extrinsic_T=np.zeros(3),
                 image_sample_step=1, out_dir=None, device=0, colorize=False, map_quality=False, loop_closures=None, relax=None,
-                matching="db", match_opts=None, pair_selection=None, device_tracks=False, verify=None, **cfg):
+                matching="db", match_opts=None, pair_selection=None, device_tracks=False, verify=None, features="db",
+                feature_opts=None, **cfg):
     """initFromDatasetIO + runFullPipeline on a dataset directory; with out_dir, the refined LiDAR poses (TUM) and the COLMAP
     text files images.txt / points3D.txt the reference writes (src/lvba_system.cpp:2018-2137) are saved there.  images.txt is
     the reference's, character for character (tests/test_ref_system.py).
@@ -864,10 +881,20 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
     verify: None (off), True, or a dict of verify_image_pairs' options, with every `matching` value: the matches are verified
     geometrically before the visual stage (run_full_pipeline's verify_matches); the output gains match_verification and out_dir
     gets match_verification.json.
+    features: where the key points and descriptors come from.  "db" (default): the database.  "images": every all_image/<t>.png
+    is read (dataset.read_image_bgr at the camera's width and height) and its SIFT features are extracted on the GPU
+    (extract_image_features, feature_opts its options) -- the reference's path without a database
+    (extractAndMatchFeaturesGPU, src/lvba_system.cpp:687-778); the database file is not opened.  Then `matching` must be
+    "descriptors", "guided" or "depth": the database's matches index the database's key points.
     cfg as for run_full_pipeline, e.g. visual_loss=REFERENCE_HUBER, window_loss=("cauchy", 0.1), stage_loss=("huber", 0.05),
     camera_priors=lambda cams: lidar_camera_priors(cams, Rci, tci, 1e-3, 0.02)."""
     import os
     from . import dataset as D
+    if features not in ("db", "images"):
+        raise ValueError(f"features={features!r}: one of 'db', 'images'")
+    if features == "images" and matching not in ("descriptors", "guided", "depth"):
+        raise ValueError(f"features='images' needs matching='descriptors', 'guided' or 'depth', not {matching!r}: the database's matches "
+                         "index the database's key points")
     if pair_selection and matching not in ("guided", "depth"):
         raise ValueError(f"pair_selection needs matching='guided' or 'depth' (refined poses and depth images before the matching), not {matching!r}")
     ds = D.load_dataset(data_path)
@@ -878,17 +905,23 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
         raise ValueError(f"{len(image_ids)} images but {len(image_poses)} image poses")          # :457-460
     names = [f"{t:.6f}.png" for t in image_ids]                                                   # getImagePath: std::to_string
     pairs = [(i, j) for i in range(len(image_ids)) for j in range(i + 1, len(image_ids))]        # image_pairs_, :462-466
-    kps, matches = D.load_colmap_db(colmap_db_path if os.path.isabs(colmap_db_path) else os.path.join(data_path, colmap_db_path),
-                                    names, pairs)
+    if features == "images":
+        kps, descs = extract_image_features(lambda k: D.read_image_bgr(os.path.join(img_dir, names[k]), width, height), len(names),
+                                            device=device, **(feature_opts or {}))
+        matches = [np.zeros((0, 2), np.int64) for _ in pairs]
+    else:
+        kps, matches = D.load_colmap_db(colmap_db_path if os.path.isabs(colmap_db_path) else os.path.join(data_path, colmap_db_path),
+                                        names, pairs)
     if matching not in ("db", "descriptors", "guided", "depth"):
         raise ValueError(f"matching={matching!r}: one of 'db', 'descriptors', 'guided', 'depth'")
     Rci, tci = extrinsics_from_config(Rcl, Pcl, extrinsic_R, extrinsic_T)
     match_fn, all_pairs = None, pairs
     if matching != "db":
-        descs = D.load_colmap_descriptors(colmap_db_path if os.path.isabs(colmap_db_path) else os.path.join(data_path, colmap_db_path),
-                                          names)
-        descs = [d if len(d) == len(k) else np.zeros((0, 128), np.uint8) for d, k in zip(descs, kps)]   # rows are key points
-        kps = [k if len(d) else k[:0] for d, k in zip(descs, kps)]
+        if features == "db":
+            descs = D.load_colmap_descriptors(colmap_db_path if os.path.isabs(colmap_db_path) else os.path.join(data_path, colmap_db_path),
+                                              names)
+            descs = [d if len(d) == len(k) else np.zeros((0, 128), np.uint8) for d, k in zip(descs, kps)]   # rows are key points
+            kps = [k if len(d) else k[:0] for d, k in zip(descs, kps)]
         if matching == "descriptors":
             matches = match_image_pairs(descs, pairs, device=device, **(match_opts or {}))
         else:

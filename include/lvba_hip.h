@@ -1334,6 +1334,102 @@ int32_t lvba_verify_hypotheses(lvba_verify_t v, int32_t a, int32_t b, int64_t n_
 int32_t lvba_verify_score(lvba_verify_t v, int32_t a, int32_t b, int64_t n_matches, const int32_t *matches, const double *E,
                           double max_error_px, uint8_t *mask);
 
+/* ---- SIFT key points and descriptors of a batch of images (opt-in)
+ *   The reference extracts its features with SiftGPU, "-fo -1 -loweo -w 3 -t 0.01 -e 12" (extractAndMatchFeaturesGPU,
+ *   src/lvba_system.cpp:687-778).  The rule below is this project's own reading of Lowe 2004 under those five parameters; it is NOT
+ *   pinned against SiftGPU, whose key points it will not reproduce one for one.  A numpy oracle restates it (tests/sift_oracle.py).
+ *   The descriptors have the form lvba_match_create takes: uint8 [n][128], a unit vector times 512.
+ *   Every product and sum below is evaluated as written, left to right inside its brackets, without fused multiply-add.
+ *   Grey (fp32).  From uint8 B, G, R:  g = ((0.299f R + 0.587f G) + 0.114f B) / 255.0f;  from a grey byte v:  g = v / 255.0f.
+ *   Base image (fp32).  first_octave = -1 doubles the image, first along the rows,
+ *       H(y, 2 x) = g(y, x),   H(y, 2 x + 1) = 0.5f (g(y, x) + g(y, min(x + 1, w - 1))),
+ *     then along the columns,  B(2 y, X) = H(y, X),   B(2 y + 1, X) = 0.5f (H(y, X) + H(min(y + 1, h - 1), X));
+ *     its assumed blur is 1.0 (0.5 before the doubling).  first_octave = 0 takes B = g with assumed blur 0.5.
+ *     Level 0 of the first octave is B blurred with sigma = sqrt(sigma0^2 - assumed^2).
+ *   Pyramid (fp32).  S = n_intervals; an octave has the Gaussian levels 0 .. S + 2, level l from level l - 1 by a blur with
+ *       sigma_inc(l) = sigma0 2^((l - 1) / S) sqrt(2^(2 / S) - 1).
+ *     A blur is separable, rows first, then columns.  Radius r = ceil(4 sigma); taps t[k], k = -r .. r: exp(-k^2 / (2 sigma^2)) in
+ *     fp64 on the host, divided by their sum (ascending k), rounded to fp32 -- computed once per call (lvba_sift_blur_taps hands
+ *     them out; level 0 is the base blur).  out(x) = t[-r] in(c(x - r)), then + t[k] in(c(x + k)) for k = -r + 1 .. r in this order,
+ *     every product and sum rounded to fp32; c clamps an index into the image, and r may exceed the image.
+ *     Level 0 of the next octave is level S at every second pixel, (2 x, 2 y), with w' = w / 2, h' = h / 2 in integer division; the
+ *     octaves o = first_octave, first_octave + 1, ... go on while min(w', h') >= 8.
+ *   Extrema.  DoG level l = Gaussian level l + 1 minus level l in fp32, l = 0 .. S + 1.  The sample (l, y, x), 1 <= l <= S,
+ *     1 <= x <= w - 2, 1 <= y <= h - 2, is a candidate iff  (double)|D| > (0.5 t) / S  and D is strictly greater than all of its 26
+ *     neighbours or strictly less than all of them  (t = dog_threshold).
+ *   Refinement (fp64 on the fp32 DoG values, only + - * /; csrc/sift_device.h, sift_refine, is the text).  At the sample:
+ *       g = 0.5 (D(+1) - D(-1)) per axis;  H_aa = (D(+1) + D(-1)) - 2 D;  H_ab = 0.25 ((D(+a+b) - D(+a-b)) - (D(-a+b) - D(-a-b)))
+ *       with the later axis of (x, y, l) as a;  the offset (ox, oy, ol) = -(adj(H) g) / det(H) by the explicit cofactors, the three
+ *       products of a row summed left to right.  det = 0: dropped.
+ *     While a component exceeds 0.5 in magnitude the sample moves by +-1 along every such axis, at most 5 moves; the key point is
+ *     dropped when it leaves 1 <= x <= w - 2, 1 <= y <= h - 2, 1 <= l <= S, when an offset still exceeds 0.5 after the fifth move,
+ *     when |D + 0.5 ((gx ox + gy oy) + gl ol)| < t / S, when Hxx Hyy - Hxy Hxy <= 0 or when
+ *     (Hxx + Hyy)^2 / (Hxx Hyy - Hxy Hxy) >= (e + 1)^2 / e  (e = edge_threshold).
+ *     sigma_o = sigma0 2^((l + ol) / S) with 2^z from sift_pow2 of sift_device.h (+ * / only, so host and device agree);
+ *     x = (x_s + ox) 2^o, y = (y_s + oy) 2^o, sigma = sigma_o 2^o, rounded to float: input pixels, (0, 0) the centre of the first
+ *     pixel.  Two candidates may end on the same sample; both are kept.
+ *   Orientation (fp64 on the fp32 pixels of Gaussian level l of the octave -- the level nearest the refined scale, |ol| <= 0.5).
+ *     R = floor(w_f 1.5 sigma_o + 0.5)  (w_f = orientation_window).  For j = -R .. R and inside that i = -R .. R with
+ *     i i + j j <= R R and (x_s + i, y_s + j) in [1, w - 2] x [1, h - 2]:  gx = L(+1, 0) - L(-1, 0), gy = L(0, +1) - L(0, -1),
+ *       weight = exp(-((i - ox)^2 + (j - oy)^2) / (2 (1.5 sigma_o)^2)),  a = atan2(gy, gx) (+ 2 pi if negative),
+ *       bin = min(35, (int)(a (36 / 2 pi))),  hist[bin] += sqrt(gx gx + gy gy) weight   -- every bin summed in this sample order.
+ *     Twice: hist[k] = ((hist[k - 1] + hist[k]) + hist[k + 1]) / 3 around the circle.  A bin strictly above both neighbours and
+ *     >= 0.8 max is a peak;  theta = ((k + 0.5) + (0.5 (h[k-1] - h[k+1])) / ((h[k-1] - 2 h[k]) + h[k+1])) (2 pi / 36), wrapped into
+ *     [0, 2 pi), rounded to float.  At most max_orientations are kept, the larger peak first (a tie: the lower bin); a key point
+ *     without a peak is dropped.  The angle runs from +x towards +y (y points down the image).
+ *   Descriptor (fp64; the float theta widened again).  Bin width 3 sigma_o, 4 x 4 cells of 8 directions, window radius
+ *     R = floor(((3 sigma_o) sqrt(2)) 2.5 + 0.5).  For j, i = -R .. R as above, with dx = i - ox, dy = j - oy:
+ *       rx = (cos dx + sin dy) / (3 sigma_o),  ry = (cos dy - sin dx) / (3 sigma_o),  cb = rx + 1.5,  rb = ry + 1.5,
+ *       used iff -1 < rb < 4 and -1 < cb < 4;  a = atan2(gy, gx) - theta wrapped into [0, 2 pi),  ob = a (8 / 2 pi),
+ *       v = sqrt(gx gx + gy gy) exp(-(rx rx + ry ry) / 8)   (a Gaussian window of two cells),
+ *       shared trilinearly: ((v w_r) w_c) w_o to the cells floor(rb), floor(rb) + 1 (inside 0 .. 3), likewise the columns, and the
+ *       directions floor(ob), floor(ob) + 1 modulo 8; every bin summed in this sample order.  Byte (4 r + c) 8 + o.
+ *     Then: divided by the L2 norm (sum of squares in byte order), clamped at 0.2, divided by the norm again,
+ *       byte = min(255, floor(512 v + 0.5)).
+ *   Output.  Per image in the canonical order: (octave, level and y, x of the sample the candidate was FOUND at, orientation rank).
+ *     With more than max_features features an image keeps the max_features of largest float sigma (a tie: the earlier in the
+ *     canonical order), still in canonical order.  count[i] is the number before that cap.  feat_off [n_images + 1] are the true
+ *     offsets of the kept features, also where they exceed capacity; only the first `capacity` rows of keypoints [.][4] =
+ *     (x, y, sigma, theta) and descriptors [.][128] are written.  Images: uint8 [n_images][height][width][channels], channels 3
+ *     (B, G, R) or 1, all of one size.  chunk_images images share a pyramid on the device at a time (0: as many as half of the
+ *     free memory holds, at most 64).  No floating-point atomics and no atomics at all: a pair of calls, a batch, a batch reversed
+ *     and any chunk size give the same bytes per image.
+ *   lvba_sift_blur_taps (host only, touches no device): taps [2 r + 1] (room for 65) and r of level 0 .. S + 2.
+ *   lvba_sift_tile_width (host only): the pixels of a row one workgroup of the blur covers -- where a test puts its widths.
+ *   lvba_sift_profile (host only): ms [6] of the calling thread's last lvba_sift_extract by the host's clock -- pyramid (upload, base
+ *     image, blurs), detection (DoG, flags, scan, refinement), orientation, descriptor (with the download), assembly on the host,
+ *     the whole call.
+ *   lvba_sift_pyramid: a diagnostic; gauss [S + 3][h_o][w_o] and dog [S + 2][h_o][w_o] of one image's octave o.
+ *   lvba_sift_candidates: a diagnostic; the refined key points of one image before the orientation: xys [capacity][3] =
+ *     (x, y, sigma), where [capacity][2] = (octave, level of the sample the fit ended on), *count the true number.
+ *   LVBA_ERR_ARG: a null required pointer, a negative count, width or height outside 8 .. 16384, channels not 1 or 3, an octave
+ *   the image does not have, an option outside the range noted below, or a blur radius above 32.  A refused call writes nothing,
+ *   and these refusals come before a device is touched.  lvba_version() is unchanged; a client detects these calls by looking
+ *   lvba_sift_extract up. */
+typedef struct lvba_sift_opts {
+    int32_t first_octave;       /* -1 (default) or 0 */
+    int32_t n_intervals;        /* S, 2 .. 5 (default 3) */
+    double sigma0;              /* in [1.1, 4] (default 1.6) */
+    double dog_threshold;       /* t, in (0, 1] (default 0.01) */
+    double edge_threshold;      /* e, in [1, 1000] (default 12) */
+    double orientation_window;  /* w_f, in [0.5, 6] (default 3) */
+    int32_t max_orientations;   /* 1 .. 4 (default 2) */
+    int32_t max_features;       /* >= 1 (default 8192) */
+    int32_t chunk_images;       /* >= 0 (default 0: from the free memory) */
+    int32_t reserved;           /* 0 */
+} lvba_sift_opts;               /* 56 bytes */
+void    lvba_sift_default_opts(lvba_sift_opts *o);
+int32_t lvba_sift_tile_width(void);
+int32_t lvba_sift_blur_taps(const lvba_sift_opts *o, int32_t level, float *taps, int32_t *radius);
+int32_t lvba_sift_extract(int32_t device, int32_t n_images, int32_t width, int32_t height, int32_t channels, const uint8_t *images,
+                          const lvba_sift_opts *o, int64_t capacity, int64_t *feat_off, float *keypoints, uint8_t *descriptors,
+                          int64_t *count);
+int32_t lvba_sift_profile(double *ms);
+int32_t lvba_sift_pyramid(int32_t device, int32_t width, int32_t height, int32_t channels, const uint8_t *image,
+                          const lvba_sift_opts *o, int32_t octave, float *gauss, float *dog);
+int32_t lvba_sift_candidates(int32_t device, int32_t width, int32_t height, int32_t channels, const uint8_t *image,
+                             const lvba_sift_opts *o, int64_t capacity, float *xys, int32_t *where, int64_t *count);
+
 #ifdef __cplusplus
 }
 #endif
