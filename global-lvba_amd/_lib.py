@@ -537,6 +537,14 @@ def load():
     return lib
 
 
+def flatten_rows(arrays, dtype, width):
+    """(flat [total, width] of `dtype`, off int64 [n + 1]): per-image or per-pair arrays, each [n_i, width], back to back"""
+    rows = [np.asarray(a, dtype).reshape(-1, width) for a in arrays]
+    off = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64)
+    flat = np.ascontiguousarray(np.concatenate(rows)) if rows else np.zeros((0, width), dtype)
+    return flat, off
+
+
 def check(rc, allow_numeric=False):
     if rc == OK or (allow_numeric and rc > 0):
         return rc

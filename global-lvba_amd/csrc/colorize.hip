@@ -342,7 +342,7 @@ extern "C" int32_t lvba_colorize_create(lvba_scans_t sc, const double *scan_pose
     if (!h) return lvba_fail(LVBA_ERR_NOMEM, "host allocation failed");
     struct Guard { lvba_colorize_s *h; ~Guard() { delete h; } } guard{h};
     h->device = sc->device; h->n_frames = nf; h->width = width; h->height = height;
-    h->cam = TrkIntr{intr[0], intr[1], intr[2], intr[3], intr[4], intr[5], intr[6], intr[7]};
+    h->cam = trk_intr_of(intr);
     h->half = o.half_window_s; h->leaf = o.leaf_size; h->max_batch = o.max_batch_images;
     h->thin = !(o.leaf_size < 0.001); // down_sampling_voxel2: a leaf below 1 mm means no thinning
     h->frame_off.assign(sc->frame_off.begin(), sc->frame_off.begin() + nf + 1);

@@ -25,6 +25,7 @@
 #include "lvba_common.h"
 #include "mempool.h"
 #include "voxel_internal.h"
+#include "image_set.h"
 #include "covis_device.h"
 #include "../../include/lvba_hip.h"
 
@@ -188,15 +189,12 @@ int32_t check_call(lvba_depth_t depth, const double *Rcw, const double *tcw, con
                          o.min_overlap, o.occlusion_rel, o.occlusion_abs);
     if (o.grid_x > W - 1 || o.grid_y > H - 1)
         return lvba_fail(LVBA_ERR_ARG, "a grid of %d x %d cells on images of %d x %d (at most width - 1, height - 1)", o.grid_x, o.grid_y, W, H);
-    for (int k = 0; k < 8; ++k)
-        if (!std::isfinite(intr[k])) return lvba_fail(LVBA_ERR_ARG, "intrinsic %d is not finite", k);
-    for (int64_t k = 0; k < 9 * (int64_t)M; ++k)
-        if (!std::isfinite(Rcw[k])) return lvba_fail(LVBA_ERR_ARG, "camera %d: non-finite rotation", (int)(k / 9));
-    for (int64_t k = 0; k < 3 * (int64_t)M; ++k)
-        if (!std::isfinite(tcw[k])) return lvba_fail(LVBA_ERR_ARG, "camera %d: non-finite translation", (int)(k / 3));
+    TRY(check_intrinsics_finite(intr));
+    TRY(check_rotations_finite(Rcw, 0, M));
+    TRY(check_translations_finite(tcw, 0, M));
     c.sh = CovisShape{M, W, H, o.grid_x, o.grid_y, o.grid_x * o.grid_y, o.search_radius};
     c.rule = CovisRule{o.occlusion, o.both_ways, o.max_per_image, o.min_shared, o.min_overlap, o.occlusion_rel, o.occlusion_abs};
-    c.cam = TrkIntr{intr[0], intr[1], intr[2], intr[3], intr[4], intr[5], intr[6], intr[7]};
+    c.cam = trk_intr_of(intr);
     return LVBA_OK;
 }
 

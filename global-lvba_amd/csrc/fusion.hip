@@ -27,6 +27,7 @@
 #include "lvba_common.h"
 #include "mempool.h"
 #include "voxel_internal.h"
+#include "segments.h"
 #include "tracks_device.h"
 #include "fusion_device.h"
 #include "../../include/lvba_hip.h"
@@ -86,11 +87,7 @@ __global__ void gm_render_kernel(int64_t M, int64_t V, const int64_t *__restrict
 {
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= M) return;
-    int64_t lo = 0, hi = V; // last v with start[v] <= j (empty voxels have start[v] == start[v+1] and are skipped by "last")
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (start[mid] <= j) lo = mid; else hi = mid;
-    }
+    const int64_t lo = segment_of(start, V, j);
     const int64_t pos = voff[lo] + (j - start[lo]);
     const double *pw = world + 3 * (int64_t)order[pos];
     const double X0 = Rcw[0] * pw[0] + Rcw[1] * pw[1] + Rcw[2] * pw[2] + tcw[0];
@@ -184,7 +181,7 @@ extern "C" int32_t lvba_depth_render(lvba_scans_t sc, const double *scan_poses, 
         HIPCHK(hipGetLastError());
         DevBuf mark(s), cnt(s), start(s);
         HIPCHK(mark.alloc(4 * (size_t)V)); HIPCHK(cnt.alloc(8 * ((size_t)V + 1))); HIPCHK(start.alloc(8 * ((size_t)V + 1)));
-        const TrkIntr cam{intr[0], intr[1], intr[2], intr[3], intr[4], intr[5], intr[6], intr[7]};
+        const TrkIntr cam = trk_intr_of(intr);
         for (int m = 0; m < n_images; ++m) {
             // scans with t_img - half <= t <= t_img + half: std::lower_bound / std::upper_bound on the (sorted) scan times
             const double t0 = image_times[m] - half_window_s, t1 = image_times[m] + half_window_s;
@@ -309,7 +306,7 @@ extern "C" int32_t lvba_fuse_tracks(int32_t device, lvba_depth_t depth, int32_t 
     }
     HIPCHK(hipMemcpyAsync(d_R.p, Rcw, 72 * (size_t)n_images, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(d_t.p, tcw, 24 * (size_t)n_images, hipMemcpyHostToDevice, s));
-    const TrkIntr cam{intr[0], intr[1], intr[2], intr[3], intr[4], intr[5], intr[6], intr[7]};
+    const TrkIntr cam = trk_intr_of(intr);
     const double cos_min = cos(o.min_view_angle_deg * M_PI / 180.0);
     fuse_kernel<<<(unsigned)((n_tracks + 63) / 64), 64, 0, s>>>(
         n_tracks, d_off.as<int64_t>(), d_img.as<int32_t>(), d_uv.as<float>(), depth ? depth->d_depth : nullptr,

@@ -2,7 +2,7 @@
 // depth image predicts (lvba_match_*; the rule is in include/lvba_hip.h, its scalar pieces in match_device.h).
 //
 // Device design:
-//   match_undistort_kernel  a thread per keypoint: trk_undistort once per lvba_match_set_geometry, NaN where it fails.
+//   (image_set.hip)         pixels, offsets, undistorted points: the handle's ImageSet, image_set_undistort per set_geometry.
 //   match_lift_kernel       a thread per keypoint: its 3-D point through the depth image, once per lvba_match_set_depth, NaN where
 //                           it has none.
 //   match_predict_kernel    depth gate only, before the scan: a thread per (ordered pair, keypoint of its first image) projects the
@@ -26,7 +26,6 @@
 // lane half h), so the sum over k is complete whatever order the instruction takes them in.
 // No atomics of any kind: two calls give the same bytes.
 #include <hip/hip_runtime.h>
-#include <math.h>
 #include <stdint.h>
 #include <algorithm>
 #include <cmath>
@@ -34,19 +33,17 @@
 #include "lvba_common.h"
 #include "mempool.h"
 #include "voxel_internal.h"
+#include "segments.h"
+#include "image_set.h"
 #include "match_device.h"
 #include "../../include/lvba_hip.h"
 
 using namespace lvba;
 
 struct lvba_match_s {
-    int device = 0;
-    int32_t n_images = 0;
-    std::vector<int64_t> off;      // [n_images + 1]
+    ImageSet kp;                   // offsets (on the device for the lift), pixels, undistorted points
     uint8_t *d_desc = nullptr;     // [total][128], top bit flipped: a' = a - 128 as a signed byte
     int32_t *d_bias = nullptr;     // [total] 128 sum a'
-    float *d_uv = nullptr;         // [total][2] the keypoints' pixels
-    double *d_xy = nullptr;        // [total][2] undistorted normalised keypoints, NaN where the undistortion fails
     double *d_pts = nullptr;       // [total][3] the keypoints' points through the depth images, NaN rows where there is none
     bool has_geometry = false, has_points = false;
     TrkIntr cam{};
@@ -80,15 +77,6 @@ struct MatchPredJob {
     double R[9], t[3];
 };
 
-__global__ __launch_bounds__(256) void match_undistort_kernel(int64_t n, const float *__restrict__ uv, const TrkIntr cam, double *__restrict__ xy)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    double x, y;
-    if (!trk_undistort(cam, (double)uv[2 * i], (double)uv[2 * i + 1], x, y)) x = y = NAN;
-    xy[2 * i] = x; xy[2 * i + 1] = y;
-}
-
 // world [n][3]; img_off [n_images + 1] = the matcher's desc_off
 __global__ __launch_bounds__(256) void match_lift_kernel(int64_t n, int n_images, const int64_t *__restrict__ img_off,
                                                          const float *__restrict__ uv, const double *__restrict__ xy,
@@ -98,11 +86,7 @@ __global__ __launch_bounds__(256) void match_lift_kernel(int64_t n, int n_images
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    int lo = 0, hi = n_images; // the last image with img_off <= i (empty images share an offset with their successor)
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (img_off[mid] <= i) lo = mid; else hi = mid;
-    }
+    const int lo = segment_of(img_off, n_images, i);
     match_lift(depth + (int64_t)lo * width * height, width, height, uv[2 * i], uv[2 * i + 1], xy[2 * i], xy[2 * i + 1], Rcw + 9 * (int64_t)lo,
                tcw + 3 * (int64_t)lo, world + 3 * i);
 }
@@ -113,12 +97,7 @@ __global__ __launch_bounds__(256) void match_predict_kernel(int64_t n, int n_job
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    int lo = 0, hi = n_jobs; // the last job with first <= i
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (jobs[mid].first <= i) lo = mid; else hi = mid;
-    }
-    const MatchPredJob &j = jobs[lo];
+    const MatchPredJob &j = jobs[segment_of([=](int k) { return jobs[k].first; }, n_jobs, i)];
     match_predict(cam, j.R, j.t, world + 3 * (j.src_off + (i - j.first)), pred[2 * i], pred[2 * i + 1]);
 }
 
@@ -276,11 +255,7 @@ __global__ __launch_bounds__(256) void match_decide_kernel(int64_t n_rows, int n
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i > n_rows) return;
     if (i == n_rows) { flag[i] = 0; return; }
-    int lo = 0, hi = n_pairs; // the last pair with row_off <= i
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (row_off[mid] <= i) lo = mid; else hi = mid;
-    }
+    const int lo = segment_of(row_off, n_pairs, i);
     const int64_t r = i - row_off[lo], f = po[lo].fwd + r;
     const int32_t c = best[f];
     bool ok = match_accept(c, s1[f], s2[f], max_distance, max_ratio);
@@ -300,11 +275,7 @@ __global__ __launch_bounds__(256) void match_write_kernel(int64_t n_rows, int n_
     if (i >= n_rows || !flag[i]) return;
     const int64_t pos = excl[i];
     if (pos >= n_out) return;
-    int lo = 0, hi = n_pairs;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (row_off[mid] <= i) lo = mid; else hi = mid;
-    }
+    const int lo = segment_of(row_off, n_pairs, i);
     const int64_t r = i - row_off[lo], f = po[lo].fwd + r;
     matches[2 * pos] = (int32_t)r; matches[2 * pos + 1] = best[f];
     scores[pos] = s1[f];
@@ -326,8 +297,7 @@ int32_t check_opts(const lvba_match_opts *opts, lvba_match_opts &o)
 
 int32_t check_pair(const lvba_match_s *m, int64_t a, int64_t b, const lvba_match_opts &o)
 {
-    if (a < 0 || a >= m->n_images || b < 0 || b >= m->n_images || a == b)
-        return lvba_fail(LVBA_ERR_ARG, "pair (%lld, %lld) of %d images (two different images)", (long long)a, (long long)b, m->n_images);
+    TRY(check_image_pair(a, b, m->kp.n_images));
     if (o.guided == MATCH_DEPTH && !m->has_points)
         return lvba_fail(LVBA_ERR_ARG, "depth-guided matching (guided = 2) needs lvba_match_set_geometry and then lvba_match_set_depth first");
     if (o.guided && !m->has_geometry) return lvba_fail(LVBA_ERR_ARG, "guided matching needs lvba_match_set_geometry first");
@@ -338,8 +308,8 @@ int32_t check_pair(const lvba_match_s *m, int64_t a, int64_t b, const lvba_match
 MatchTask make_task(const lvba_match_s *m, int a, int b, int64_t out_off, int guided, int64_t pred_rows = 0, int64_t pred_cols = 0)
 {
     MatchTask t{};
-    t.a_off = m->off[a]; t.b_off = m->off[b]; t.out_off = out_off;
-    t.n_a = (int32_t)(m->off[a + 1] - m->off[a]); t.n_b = (int32_t)(m->off[b + 1] - m->off[b]);
+    t.a_off = m->kp.off[a]; t.b_off = m->kp.off[b]; t.out_off = out_off;
+    t.n_a = (int32_t)(m->kp.off[a + 1] - m->kp.off[a]); t.n_b = (int32_t)(m->kp.off[b + 1] - m->kp.off[b]);
     t.rows_lo = a < b ? 1 : 0;
     if (guided == MATCH_EPIPOLAR) {
         const int lo = std::min(a, b), hi = std::max(a, b);
@@ -356,21 +326,15 @@ int64_t predict_jobs(const lvba_match_s *m, int a, int b, int64_t first, std::ve
 {
     const int src[2] = {a, b}, dst[2] = {b, a};
     for (int k = 0; k < 2; ++k) {
-        const int64_t n = m->off[src[k] + 1] - m->off[src[k]];
+        const int64_t n = m->kp.off[src[k] + 1] - m->kp.off[src[k]];
         if (n == 0) continue;
         MatchPredJob j{};
-        j.src_off = m->off[src[k]]; j.first = first;
+        j.src_off = m->kp.off[src[k]]; j.first = first;
         std::copy_n(&m->R[9 * (size_t)dst[k]], 9, j.R); std::copy_n(&m->t[3 * (size_t)dst[k]], 3, j.t);
         jobs.push_back(j);
         first += n;
     }
     return first;
-}
-
-double gate_tau2(const lvba_match_s *m, const lvba_match_opts &o)
-{
-    const double tau = (2.0 * o.max_epipolar_px) / m->focal_sum;
-    return tau * tau;
 }
 
 // the scan of `tasks` (results at their out_off in d_best / d_s1 / d_s2), one grid; under the depth gate after the predictions of
@@ -398,10 +362,10 @@ int32_t scan_tasks(hipStream_t s, const lvba_match_s *m, const std::vector<Match
         }
         match_scan_kernel<MATCH_DEPTH><<<(unsigned)tiles.size(), SCAN_BLOCK, 0, s>>>(d_tasks.as<MatchTask>(), d_tiles.as<int2>(), m->d_desc,
                                                                                    m->d_bias, nullptr, o.max_reproj_px * o.max_reproj_px, d_best,
-                                                                                   d_s1, d_s2, m->d_uv, d_pred.as<double>());
+                                                                                   d_s1, d_s2, m->kp.d_uv, d_pred.as<double>());
     } else if (o.guided == MATCH_EPIPOLAR)
         match_scan_kernel<MATCH_EPIPOLAR><<<(unsigned)tiles.size(), SCAN_BLOCK, 0, s>>>(d_tasks.as<MatchTask>(), d_tiles.as<int2>(), m->d_desc,
-                                                                                      m->d_bias, m->d_xy, gate_tau2(m, o), d_best, d_s1, d_s2,
+                                                                                      m->d_bias, m->kp.d_xy, match_tau2(m->focal_sum, o.max_epipolar_px), d_best, d_s1, d_s2,
                                                                                       nullptr, nullptr);
     else
         match_scan_kernel<MATCH_UNGUIDED><<<(unsigned)tiles.size(), SCAN_BLOCK, 0, s>>>(d_tasks.as<MatchTask>(), d_tiles.as<int2>(), m->d_desc,
@@ -434,20 +398,13 @@ extern "C" void lvba_match_default_opts(lvba_match_opts *o)
 extern "C" int32_t lvba_match_create(int32_t device, int32_t n_images, const int64_t *desc_off, const uint8_t *desc, lvba_match_t *out)
 {
     if (!out || n_images < 0 || !desc_off) return lvba_fail(LVBA_ERR_ARG, "null argument or n_images < 0");
-    if (desc_off[0] != 0) return lvba_fail(LVBA_ERR_ARG, "desc_off[0] = %lld (0)", (long long)desc_off[0]);
-    for (int i = 0; i < n_images; ++i) {
-        const int64_t n = desc_off[i + 1] - desc_off[i];
-        if (n < 0) return lvba_fail(LVBA_ERR_ARG, "desc_off decreases at image %d", i);
-        if (n > MATCH_MAX_PER_IMAGE)
-            return lvba_fail(LVBA_ERR_ARG, "image %d has %lld descriptors (at most %lld)", i, (long long)n, (long long)MATCH_MAX_PER_IMAGE);
-    }
+    TRY(check_offsets("desc_off", "image", n_images, desc_off, MATCH_MAX_PER_IMAGE));
     const int64_t total = desc_off[n_images];
     if (total > 0 && !desc) return lvba_fail(LVBA_ERR_ARG, "null descriptors");
     TRY(check_device(device));
     HIPCHK(hipSetDevice(device));
     lvba_match_s *m = new lvba_match_s;
-    m->device = device; m->n_images = n_images;
-    m->off.assign(desc_off, desc_off + n_images + 1);
+    m->kp = ImageSet{device, n_images, std::vector<int64_t>(desc_off, desc_off + n_images + 1)};
     if (total > 0) {
         std::vector<uint8_t> biased((size_t)total * MATCH_DIM);
         std::vector<int32_t> bias((size_t)total);
@@ -476,12 +433,11 @@ extern "C" int32_t lvba_match_create(int32_t device, int32_t n_images, const int
 extern "C" int32_t lvba_match_destroy(lvba_match_t m)
 {
     if (!m) return LVBA_OK;
-    (void)hipSetDevice(m->device);
+    (void)hipSetDevice(m->kp.device);
     (void)hipDeviceSynchronize();
     if (m->d_desc) DevicePool::get().free(m->d_desc);
     if (m->d_bias) DevicePool::get().free(m->d_bias);
-    if (m->d_uv) DevicePool::get().free(m->d_uv);
-    if (m->d_xy) DevicePool::get().free(m->d_xy);
+    image_set_free(m->kp);
     if (m->d_pts) DevicePool::get().free(m->d_pts);
     delete m;
     return LVBA_OK;
@@ -489,18 +445,15 @@ extern "C" int32_t lvba_match_destroy(lvba_match_t m)
 
 extern "C" int32_t lvba_match_set_geometry(lvba_match_t m, const float *keypoints_uv, const double *intr, const double *Rcw, const double *tcw)
 {
-    if (!m || !intr || (m->n_images > 0 && (!Rcw || !tcw))) return lvba_fail(LVBA_ERR_ARG, "null argument");
-    const int64_t total = m->off[m->n_images];
+    if (!m || !intr || (m->kp.n_images > 0 && (!Rcw || !tcw))) return lvba_fail(LVBA_ERR_ARG, "null argument");
+    const int64_t total = m->kp.off[m->kp.n_images];
     if (total > 0 && !keypoints_uv) return lvba_fail(LVBA_ERR_ARG, "null keypoints");
-    for (int k = 0; k < 8; ++k)
-        if (!std::isfinite(intr[k])) return lvba_fail(LVBA_ERR_ARG, "intrinsic %d is not finite", k);
-    if (!(intr[0] > 0.0 && intr[1] > 0.0)) return lvba_fail(LVBA_ERR_ARG, "focal lengths %g, %g (> 0)", intr[0], intr[1]);
-    for (int i = 0; i < m->n_images; ++i) {
-        const double *R = Rcw + 9 * (size_t)i, *t = tcw + 3 * (size_t)i;
-        for (int k = 0; k < 9; ++k)
-            if (!std::isfinite(R[k])) return lvba_fail(LVBA_ERR_ARG, "camera %d: non-finite rotation", i);
-        for (int k = 0; k < 3; ++k)
-            if (!std::isfinite(t[k])) return lvba_fail(LVBA_ERR_ARG, "camera %d: non-finite translation", i);
+    TRY(check_intrinsics_finite(intr));
+    TRY(check_focal_lengths(intr));
+    for (int i = 0; i < m->kp.n_images; ++i) {
+        const double *R = Rcw + 9 * (size_t)i;
+        TRY(check_rotations_finite(Rcw, i, 1));
+        TRY(check_translations_finite(tcw, i, 1));
         for (int a = 0; a < 3; ++a)
             for (int b = 0; b < 3; ++b) {
                 const double d = R[3 * a] * R[3 * b] + R[3 * a + 1] * R[3 * b + 1] + R[3 * a + 2] * R[3 * b + 2] - (a == b ? 1.0 : 0.0);
@@ -509,22 +462,12 @@ extern "C" int32_t lvba_match_set_geometry(lvba_match_t m, const float *keypoint
         const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
         if (!(det > 0.0)) return lvba_fail(LVBA_ERR_ARG, "camera %d: rotation with determinant %g", i, det);
     }
-    HIPCHK(hipSetDevice(m->device));
-    const TrkIntr cam{intr[0], intr[1], intr[2], intr[3], intr[4], intr[5], intr[6], intr[7]};
-    if (total > 0) {
-        if (!m->d_xy) HIPCHK(DevicePool::get().alloc((void **)&m->d_xy, 16 * (size_t)total));
-        if (!m->d_uv) HIPCHK(DevicePool::get().alloc((void **)&m->d_uv, 8 * (size_t)total));
-        ScopedStream sg;
-        HIPCHK(sg.acquire());
-        HIPCHK(lvba::copy_h2d(m->d_uv, keypoints_uv, 8 * (size_t)total));
-        match_undistort_kernel<<<grid_for(total, 256), 256, 0, sg.s>>>(total, m->d_uv, cam, m->d_xy);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(sg.s));
-    }
+    HIPCHK(hipSetDevice(m->kp.device));
+    TRY(image_set_undistort(m->kp, trk_intr_of(intr), keypoints_uv, true));
     drop_points(m); // they were lifted with the poses these replace
-    m->cam = cam;
-    m->R.assign(Rcw, Rcw + 9 * (size_t)m->n_images);
-    m->t.assign(tcw, tcw + 3 * (size_t)m->n_images);
+    m->cam = trk_intr_of(intr);
+    m->R.assign(Rcw, Rcw + 9 * (size_t)m->kp.n_images);
+    m->t.assign(tcw, tcw + 3 * (size_t)m->kp.n_images);
     m->focal_sum = intr[0] + intr[1];
     m->has_geometry = true;
     return LVBA_OK;
@@ -536,10 +479,10 @@ extern "C" int32_t lvba_match_scan(lvba_match_t m, int32_t a, int32_t b, const l
     lvba_match_opts o;
     TRY(check_opts(opts, o));
     TRY(check_pair(m, a, b, o));
-    const size_t n_a = (size_t)(m->off[a + 1] - m->off[a]);
+    const size_t n_a = (size_t)(m->kp.off[a + 1] - m->kp.off[a]);
     if (n_a > 0 && (!best || !s1 || !s2)) return lvba_fail(LVBA_ERR_ARG, "null output");
     if (n_a == 0) return LVBA_OK;
-    HIPCHK(hipSetDevice(m->device));
+    HIPCHK(hipSetDevice(m->kp.device));
     ScopedStream sg;
     HIPCHK(sg.acquire());
     DevBuf d_out(sg.s);
@@ -566,7 +509,7 @@ extern "C" int32_t lvba_match_pairs(lvba_match_t m, int64_t n_pairs, const int32
     *count = 0;
     match_off[0] = 0;
     if (n_pairs == 0) return LVBA_OK;
-    HIPCHK(hipSetDevice(m->device));
+    HIPCHK(hipSetDevice(m->kp.device));
     ScopedStream sg;
     HIPCHK(sg.acquire());
     hipStream_t s = sg.s;
@@ -580,7 +523,7 @@ extern "C" int32_t lvba_match_pairs(lvba_match_t m, int64_t n_pairs, const int32
         int64_t rows = 0, fwd_rows = 0, n_pred = 0, p1 = p0;
         for (; p1 < n_pairs && p1 - p0 < INT32_MAX / 4; ++p1) {
             const int a = pairs[2 * p1], b = pairs[2 * p1 + 1];
-            const int64_t n_a = m->off[a + 1] - m->off[a], n_b = m->off[b + 1] - m->off[b];
+            const int64_t n_a = m->kp.off[a + 1] - m->kp.off[a], n_b = m->kp.off[b + 1] - m->kp.off[b];
             const int64_t need = n_a + (o.mutual ? n_b : 0);
             if (p1 > p0 && rows + need > CHUNK_ROWS) break;
             // the depth gate's predictions cover both images of a pair whatever `mutual` is: they bound the chunk as well
@@ -637,27 +580,27 @@ extern "C" int32_t lvba_match_pairs(lvba_match_t m, int64_t n_pairs, const int32
 extern "C" int32_t lvba_match_set_depth(lvba_match_t m, lvba_depth_t depth)
 {
     if (!m) return lvba_fail(LVBA_ERR_ARG, "null handle");
-    HIPCHK(hipSetDevice(m->device));
+    HIPCHK(hipSetDevice(m->kp.device));
     if (!depth) {
         drop_points(m);
         return LVBA_OK;
     }
     if (!m->has_geometry) return lvba_fail(LVBA_ERR_ARG, "lvba_match_set_depth needs lvba_match_set_geometry first");
-    if (depth->n_images != m->n_images)
-        return lvba_fail(LVBA_ERR_ARG, "the depth set holds %d images, the matcher %d", depth->n_images, m->n_images);
-    if (depth->device != m->device)
-        return lvba_fail(LVBA_ERR_ARG, "the depth set lives on device %d, the matcher on device %d", depth->device, m->device);
-    const int64_t total = m->off[m->n_images];
+    if (depth->n_images != m->kp.n_images)
+        return lvba_fail(LVBA_ERR_ARG, "the depth set holds %d images, the matcher %d", depth->n_images, m->kp.n_images);
+    if (depth->device != m->kp.device)
+        return lvba_fail(LVBA_ERR_ARG, "the depth set lives on device %d, the matcher on device %d", depth->device, m->kp.device);
+    const int64_t total = m->kp.off[m->kp.n_images];
     if (total > 0) {
         ScopedStream sg;
         HIPCHK(sg.acquire());
-        DevBuf d_new(sg.s), d_off(sg.s), d_R(sg.s), d_t(sg.s); // the old table stays until the new one stands
-        HIPCHK(d_new.alloc(24 * (size_t)total)); HIPCHK(d_off.alloc(8 * m->off.size()));
+        DevBuf d_new(sg.s), d_R(sg.s), d_t(sg.s); // the old table stays until the new one stands
+        HIPCHK(d_new.alloc(24 * (size_t)total));
         HIPCHK(d_R.alloc(8 * m->R.size())); HIPCHK(d_t.alloc(8 * m->t.size()));
-        HIPCHK(lvba::copy_h2d(d_off.p, m->off.data(), 8 * m->off.size()));
+        TRY(image_set_upload(m->kp, true, nullptr)); // the offsets go up with the first lift and stay
         HIPCHK(lvba::copy_h2d(d_R.p, m->R.data(), 8 * m->R.size()));
         HIPCHK(lvba::copy_h2d(d_t.p, m->t.data(), 8 * m->t.size()));
-        match_lift_kernel<<<grid_for(total, 256), 256, 0, sg.s>>>(total, m->n_images, d_off.as<int64_t>(), m->d_uv, m->d_xy, depth->d_depth,
+        match_lift_kernel<<<grid_for(total, 256), 256, 0, sg.s>>>(total, m->kp.n_images, m->kp.d_off, m->kp.d_uv, m->kp.d_xy, depth->d_depth,
                                                                 depth->width, depth->height, d_R.as<double>(), d_t.as<double>(),
                                                                 d_new.as<double>());
         HIPCHK(hipGetLastError());
@@ -673,10 +616,10 @@ extern "C" int32_t lvba_match_points(lvba_match_t m, double *world)
 {
     if (!m) return lvba_fail(LVBA_ERR_ARG, "null handle");
     if (!m->has_points) return lvba_fail(LVBA_ERR_ARG, "no lifted points: lvba_match_set_depth first");
-    const int64_t total = m->off[m->n_images];
+    const int64_t total = m->kp.off[m->kp.n_images];
     if (total == 0) return LVBA_OK;
     if (!world) return lvba_fail(LVBA_ERR_ARG, "null output");
-    HIPCHK(hipSetDevice(m->device));
+    HIPCHK(hipSetDevice(m->kp.device));
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(lvba::copy_d2h(world, m->d_pts, 24 * (size_t)total));
     return LVBA_OK;

@@ -62,6 +62,8 @@ LVBA_TRK_FN double match_norm_hi(const double *E, double x, double y)       // l
     const double m1 = (E[1] * x + E[4] * y) + E[7];
     return m0 * m0 + m1 * m1;
 }
+// the gate's bound for max_px pixels in normalised units, squared: tau = 2 max_px / (fx + fy) (match.hip and verify.hip, on the host)
+inline double match_tau2(double focal_sum, double max_px) { const double tau = (2.0 * max_px) / focal_sum; return tau * tau; }
 LVBA_TRK_FN bool match_gate(const MatchLine &lo, double hx, double hy, double n_hi, double tau2)
 {
     const double e = (hx * lo.l0 + hy * lo.l1) + lo.l2;

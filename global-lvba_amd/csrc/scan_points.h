@@ -10,6 +10,7 @@
 #pragma once
 #include <math.h>
 #include <stdint.h>
+#include "segments.h"
 
 #if defined(__HIPCC__)
 #define LVBA_SP_HD __host__ __device__ __forceinline__
@@ -21,17 +22,12 @@ namespace lvba {
 
 // The frame f of point i of a set, frame_off[f] - frame_off[0] <= i < frame_off[f + 1] - frame_off[0]: frame_off [n_frames + 1]
 // may be a slice of a longer offset array (a window of the set, i counted from the window's first point) or start at 0.
-// Empty frames share their offset with the next one; the search returns the LAST frame whose offset is <= i, which is the
-// one that holds the point.  n_frames >= 1 and 0 <= i < frame_off[n_frames] - frame_off[0].
+// The search is segment_of (segments.h) over the offsets counted from the first.  n_frames >= 1 and
+// 0 <= i < frame_off[n_frames] - frame_off[0].
 LVBA_SP_HD int frame_of_point(const int64_t *__restrict__ frame_off, int n_frames, int64_t i)
 {
     const int64_t base = frame_off[0];
-    int lo = 0, hi = n_frames;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (frame_off[mid] - base <= i) lo = mid; else hi = mid;
-    }
-    return lo;
+    return segment_of([=](int f) { return frame_off[f] - base; }, n_frames, i);
 }
 
 // pose T = R (row-major) | t, 12 doubles: out = R p + t in double, each row summed from left to right

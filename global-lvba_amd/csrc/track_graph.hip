@@ -29,21 +29,20 @@
 #include "lvba_common.h"
 #include "mempool.h"
 #include "voxel_internal.h"
+#include "segments.h"
+#include "image_set.h"
 #include "track_graph_device.h"
 #include "../../include/lvba_hip.h"
 
 using namespace lvba;
 
 struct lvba_trackgraph_s {
-    int device = 0;
-    int32_t M = 0, obser_thr = 0;
-    int64_t N = 0;                       // kp_off[M]
+    ImageSet kp;                         // the images' offsets on the device (kp.off.back() nodes), their pixels where given
+    int32_t obser_thr = 0;
     bool has_uv = false;
     uint32_t epoch = 0;
     lvba_trackgraph_info info{};
     std::vector<uint32_t> comp_size, comp_images; // [n_components]
-    int64_t *d_kp_off = nullptr;         // [M + 1]
-    float *d_uv = nullptr;               // [N][2]
     uint32_t *d_adj_off = nullptr;       // [N + 1]
     uint32_t *d_adj = nullptr;           // [2 n_edges (+ 2 n_skipped behind them)]
     uint32_t *d_members = nullptr;       // [n_nodes] the nodes with an edge, by (label, node)
@@ -181,12 +180,7 @@ __global__ __launch_bounds__(TG_BLOCK) void trackgraph_members_kernel(int64_t n_
 {
     const int64_t j = (int64_t)blockIdx.x * TG_BLOCK + threadIdx.x;
     if (j >= n_obs) return;
-    uint32_t lo = 0, hi = n_comp - 1; // the last c with comp_obs[c] <= j
-    while (lo < hi) {
-        const uint32_t mid = lo + (hi - lo + 1) / 2;
-        if (comp_obs[mid] <= (uint32_t)j) lo = mid;
-        else hi = mid - 1;
-    }
+    const uint32_t lo = segment_of(comp_obs, n_comp, (uint32_t)j);
     const uint32_t node = members[comp_first[lo] + ((uint32_t)j - comp_obs[lo])];
     const int64_t i = tg_owner(kp_off, M - 1, (int64_t)node);
     mem_img[j] = (int32_t)i;
@@ -269,21 +263,9 @@ inline unsigned bits_for(uint64_t largest) { unsigned b = 1; while (b < 64 && (l
 
 hipError_t keep_alloc(void **p, size_t bytes) { return DevicePool::get().alloc(p, bytes ? bytes : 8); }
 
-// the resident tables of a valid empty graph, and of every other one
-int32_t alloc_resident(lvba_trackgraph_s *g, const int64_t *kp_off, const float *uv)
-{
-    HIPCHK(keep_alloc((void **)&g->d_kp_off, 8 * ((size_t)g->M + 1)));
-    HIPCHK(lvba::copy_h2d(g->d_kp_off, kp_off, 8 * ((size_t)g->M + 1)));
-    if (uv && g->N > 0) {
-        HIPCHK(keep_alloc((void **)&g->d_uv, 8 * (size_t)g->N));
-        HIPCHK(lvba::copy_h2d(g->d_uv, uv, 8 * (size_t)g->N));
-    }
-    return LVBA_OK;
-}
-
 int32_t build_graph(lvba_trackgraph_s *g, int64_t n_pairs, const int32_t *pairs, const int64_t *match_off, const int32_t *matches)
 {
-    const int64_t N = g->N, n_matches = n_pairs > 0 ? match_off[n_pairs] : 0;
+    const int64_t N = g->kp.off.back(), n_matches = n_pairs > 0 ? match_off[n_pairs] : 0;
     lvba_trackgraph_info &info = g->info;
     info.n_skipped = n_matches;
     if (N == 0 || n_matches == 0) return LVBA_OK;
@@ -307,7 +289,7 @@ int32_t build_graph(lvba_trackgraph_s *g, int64_t n_pairs, const int32_t *pairs,
     HIPCHK(lvba::copy_h2d(d_first.p, first_seq.data(), 8 * (size_t)n_pairs));
     HIPCHK(lvba::copy_h2d(d_matches.p, matches, 8 * (size_t)n_matches));
     trackgraph_edge_kernel<<<grid_for(n_matches, TG_BLOCK), TG_BLOCK, 0, s>>>(n_matches, n_pairs, d_pairs.as<int32_t>(), d_moff.as<int64_t>(),
-                                                                            d_first.as<int64_t>(), d_matches.as<int32_t>(), g->d_kp_off, no_node,
+                                                                            d_first.as<int64_t>(), d_matches.as<int32_t>(), g->kp.d_off, no_node,
                                                                             d_src.as<uint32_t>(), d_dst.as<uint32_t>());
     HIPCHK(hipGetLastError());
     TRY(sort_pairs<uint32_t>(s, d_src.as<uint32_t>(), d_key.as<uint32_t>(), d_dst.as<uint32_t>(), g->d_adj, H2, node_bits));
@@ -361,7 +343,7 @@ int32_t build_graph(lvba_trackgraph_s *g, int64_t n_pairs, const int32_t *pairs,
     HIPCHK(d_img.alloc(4 * (size_t)n_nodes));
     HIPCHK(d_head.alloc(4 * ((size_t)n_nodes + 1))); HIPCHK(d_change.alloc(4 * ((size_t)n_nodes + 1)));
     HIPCHK(d_run_of.alloc(4 * ((size_t)n_nodes + 1))); HIPCHK(d_change_x.alloc(4 * ((size_t)n_nodes + 1)));
-    trackgraph_image_kernel<<<grid_for(n_nodes, TG_BLOCK), TG_BLOCK, 0, s>>>(n_nodes, g->d_members, g->d_kp_off, g->M, d_img.as<int32_t>());
+    trackgraph_image_kernel<<<grid_for(n_nodes, TG_BLOCK), TG_BLOCK, 0, s>>>(n_nodes, g->d_members, g->kp.d_off, g->kp.n_images, d_img.as<int32_t>());
     HIPCHK(hipGetLastError());
     trackgraph_runs_kernel<<<grid_for(n_nodes + 1, TG_BLOCK), TG_BLOCK, 0, s>>>(n_nodes, d_lab.as<uint32_t>(), d_img.as<int32_t>(),
                                                                               d_head.as<uint32_t>(), d_change.as<uint32_t>());
@@ -415,9 +397,10 @@ int32_t build_graph(lvba_trackgraph_s *g, int64_t n_pairs, const int32_t *pairs,
 extern "C" int32_t lvba_trackgraph_destroy(lvba_trackgraph_t g)
 {
     if (!g) return LVBA_OK;
-    (void)hipSetDevice(g->device);
+    (void)hipSetDevice(g->kp.device);
     (void)hipDeviceSynchronize();
-    for (void *p : {(void *)g->d_kp_off, (void *)g->d_uv, (void *)g->d_adj_off, (void *)g->d_adj, (void *)g->d_members, (void *)g->d_stamp,
+    image_set_free(g->kp);
+    for (void *p : {(void *)g->d_adj_off, (void *)g->d_adj, (void *)g->d_members, (void *)g->d_stamp,
                     (void *)g->d_comp_first, (void *)g->d_comp_size, (void *)g->d_comp_obs})
         if (p) DevicePool::get().free(p);
     delete g;
@@ -431,30 +414,23 @@ extern "C" int32_t lvba_trackgraph_create(int32_t device, int32_t n_images, cons
     if (!out || !kp_off || n_images < 0 || n_pairs < 0) return lvba_fail(LVBA_ERR_ARG, "null argument or a negative count");
     if (n_pairs > 0 && (!pairs || !match_off)) return lvba_fail(LVBA_ERR_ARG, "null pairs or match_off");
     if (obser_thr < 1) return lvba_fail(LVBA_ERR_ARG, "obser_thr = %d (>= 1)", obser_thr);
-    if (kp_off[0] != 0) return lvba_fail(LVBA_ERR_ARG, "kp_off[0] = %lld (0)", (long long)kp_off[0]);
-    for (int32_t i = 0; i < n_images; ++i)
-        if (kp_off[i + 1] < kp_off[i]) return lvba_fail(LVBA_ERR_ARG, "kp_off decreases at image %d", i);
+    TRY(check_offsets("kp_off", "image", n_images, kp_off));
     if (kp_off[n_images] >= TG_MAX_NODES)
         return lvba_fail(LVBA_ERR_UNSUPPORTED, "%lld key points (fewer than 2^31: node ids are 32 bits)", (long long)kp_off[n_images]);
     const int64_t n_matches = n_pairs > 0 ? match_off[n_pairs] : 0;
     if (n_pairs > 0) {
-        if (match_off[0] != 0) return lvba_fail(LVBA_ERR_ARG, "match_off[0] = %lld (0)", (long long)match_off[0]);
-        for (int64_t p = 0; p < n_pairs; ++p)
-            if (match_off[p + 1] < match_off[p]) return lvba_fail(LVBA_ERR_ARG, "match_off decreases at pair %lld", (long long)p);
+        TRY(check_offsets("match_off", "pair", n_pairs, match_off));
         if (n_matches >= TG_MAX_MATCHES)
             return lvba_fail(LVBA_ERR_UNSUPPORTED, "%lld matches (fewer than 2^30: half-edge ids are 32 bits)", (long long)n_matches);
-        for (int64_t p = 0; p < n_pairs; ++p) {
-            const int32_t a = pairs[2 * p], b = pairs[2 * p + 1];
-            if (a < 0 || b < 0 || a >= n_images || b >= n_images || a == b)
-                return lvba_fail(LVBA_ERR_ARG, "pair %lld = (%d, %d): two different images of %d", (long long)p, a, b, n_images);
-        }
+        for (int64_t p = 0; p < n_pairs; ++p) TRY(check_image_pair(pairs[2 * p], pairs[2 * p + 1], n_images));
         if (n_matches > 0 && !matches) return lvba_fail(LVBA_ERR_ARG, "null matches");
     }
     TRY(check_device(device));
     HIPCHK(hipSetDevice(device));
     lvba_trackgraph_s *g = new lvba_trackgraph_s;
-    g->device = device; g->M = n_images; g->obser_thr = obser_thr; g->N = kp_off[n_images]; g->has_uv = keypoints_uv != nullptr;
-    int32_t rc = alloc_resident(g, kp_off, keypoints_uv);
+    g->kp = ImageSet{device, n_images, std::vector<int64_t>(kp_off, kp_off + n_images + 1)};
+    g->obser_thr = obser_thr; g->has_uv = keypoints_uv != nullptr;
+    int32_t rc = image_set_upload(g->kp, true, keypoints_uv);
     if (rc == LVBA_OK) rc = build_graph(g, n_pairs, pairs, match_off, matches);
     if (rc != LVBA_OK) { lvba_trackgraph_destroy(g); return rc; }
     if (info) *info = g->info;
@@ -468,13 +444,13 @@ extern "C" int32_t lvba_trackgraph_components(lvba_trackgraph_t g, int64_t *comp
     const int64_t n_obs = g->info.n_observations, n_comp = g->info.n_components;
     if (n_obs > 0 && (!mem_img || !mem_kp)) return lvba_fail(LVBA_ERR_ARG, "null mem_img or mem_kp");
     if (n_obs > 0) {
-        HIPCHK(hipSetDevice(g->device));
+        HIPCHK(hipSetDevice(g->kp.device));
         ScopedStream sg;
         HIPCHK(sg.acquire());
         DevBuf d_img(sg.s), d_kp(sg.s);
         HIPCHK(d_img.alloc(4 * (size_t)n_obs)); HIPCHK(d_kp.alloc(4 * (size_t)n_obs));
         trackgraph_members_kernel<<<grid_for(n_obs, TG_BLOCK), TG_BLOCK, 0, sg.s>>>(n_obs, (uint32_t)n_comp, g->d_comp_obs, g->d_comp_first, g->d_members,
-                                                                                 g->d_kp_off, g->M, d_img.as<int32_t>(), d_kp.as<int32_t>());
+                                                                                 g->kp.d_off, g->kp.n_images, d_img.as<int32_t>(), d_kp.as<int32_t>());
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(sg.s));
         HIPCHK(lvba::copy_d2h(mem_img, d_img.p, 4 * (size_t)n_obs));
@@ -508,12 +484,12 @@ extern "C" int32_t lvba_trackgraph_orders(lvba_trackgraph_t g, int64_t n, const 
     const size_t total = off[(size_t)n];
     if (total > 0 && (!obs_img || !obs_kp)) return lvba_fail(LVBA_ERR_ARG, "null obs_img or obs_kp");
     if (total > 0) {
-        HIPCHK(hipSetDevice(g->device));
+        HIPCHK(hipSetDevice(g->kp.device));
         ScopedStream sg;
         HIPCHK(sg.acquire());
         hipStream_t s = sg.s;
         if (++g->epoch == 0) { // every stamp of 2^32 calls ago is stale by now
-            HIPCHK(hipMemsetAsync(g->d_stamp, 0, 4 * (size_t)g->N, s));
+            HIPCHK(hipMemsetAsync(g->d_stamp, 0, 4 * (size_t)g->kp.off.back(), s));
             g->epoch = 1;
         }
         DevBuf d_sel(s), d_off(s), d_queue(s), d_img(s), d_kp(s), d_uv(s), d_err(s);
@@ -525,7 +501,7 @@ extern "C" int32_t lvba_trackgraph_orders(lvba_trackgraph_t g, int64_t n, const 
         HIPCHK(hipMemsetAsync(d_err.p, 0, 4, s));
         trackgraph_bfs_kernel<TG_BFS_LANES><<<grid_for(n * TG_BFS_LANES, TG_BLOCK), TG_BLOCK, 0, s>>>(
             n, d_sel.as<uint32_t>(), (uint32_t)attempt, g->d_comp_first, g->d_comp_size, d_off.as<uint32_t>(), g->d_members, g->d_adj_off, g->d_adj,
-            g->d_stamp, g->epoch, g->d_kp_off, g->M, g->d_uv, d_queue.as<uint32_t>(), d_img.as<int32_t>(), d_kp.as<int32_t>(),
+            g->d_stamp, g->epoch, g->kp.d_off, g->kp.n_images, g->kp.d_uv, d_queue.as<uint32_t>(), d_img.as<int32_t>(), d_kp.as<int32_t>(),
             obs_uv ? d_uv.as<float>() : nullptr, d_err.as<uint32_t>());
         HIPCHK(hipGetLastError());
         uint32_t err = 0;

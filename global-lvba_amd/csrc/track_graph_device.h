@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <numeric>
 #include <vector>
+#include "segments.h"
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define LVBA_TG_FN __host__ __device__ __forceinline__
@@ -31,19 +32,8 @@ static_assert(TG_BFS_LANES == 64 || TG_BFS_LANES == 32 || TG_BFS_LANES == 16 || 
 
 enum TgError : uint32_t { TG_OK = 0, TG_ERR_OVERRUN = 1, TG_ERR_SHORT = 2 };
 
-// the last index i in [0, n] with off[i] <= x, for a non-decreasing off [n + 1] with off[0] <= x: the image of a node in kp_off
-// (n = M - 1), the pair of a match row in match_off (n = n_pairs - 1).  Taking the LAST such index steps over images without
-// keypoints and pairs without matches.
-LVBA_TG_FN int64_t tg_owner(const int64_t *__restrict__ off, int64_t n, int64_t x)
-{
-    int64_t lo = 0, hi = n; // invariant: off[lo] <= x, and off[hi + 1] > x where hi < n
-    while (lo < hi) {
-        const int64_t mid = lo + (hi - lo + 1) / 2;
-        if (off[mid] <= x) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
+// the last index i in [0, n] with off[i] <= x, segment_of over the n + 1 entries of off: a node's image (n = M - 1), a row's pair
+LVBA_TG_FN int64_t tg_owner(const int64_t *__restrict__ off, int64_t n, int64_t x) { return segment_of(off, n + 1, x); }
 
 // Host: the pairs ranked by a stable sort on (lo, hi); first_seq [n_pairs] = the sequence number of each pair's first match.
 inline void tg_rank_pairs(int64_t n_pairs, const int32_t *pairs, const int64_t *match_off, std::vector<int64_t> &first_seq)

@@ -71,7 +71,7 @@ extern "C" int32_t lvba_triangulate_tracks(int32_t device, int32_t n_cams, int64
     }
     HIPCHK(hipMemcpyAsync(d_R.p, Rcw, 72 * (size_t)n_cams, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(d_t.p, tcw, 24 * (size_t)n_cams, hipMemcpyHostToDevice, s));
-    Intr c{intr[0], intr[1], intr[2], intr[3], intr[4], intr[5], intr[6], intr[7]};
+    const Intr c = trk_intr_of(intr);
     tri_kernel<<<(unsigned)((n_tracks + 127) / 128), 128, 0, s>>>(n_tracks, d_off.as<int64_t>(), d_cam.as<int32_t>(), d_uv.as<double>(),
                                                                   d_R.as<double>(), d_t.as<double>(), n_cams, c, d_X.as<double>(),
                                                                   d_err.as<double>(), d_cnt.as<int32_t>(), d_ok.as<uint8_t>());

@@ -21,6 +21,8 @@
 namespace lvba {
 
 struct TrkIntr { double fx, fy, cx, cy, k1, k2, p1, p2; };
+// the API's intrinsics array (fx, fy, cx, cy, k1, k2, p1, p2)
+LVBA_TRK_FN TrkIntr trk_intr_of(const double intr[8]) { return TrkIntr{intr[0], intr[1], intr[2], intr[3], intr[4], intr[5], intr[6], intr[7]}; }
 
 LVBA_TRK_FN bool trk_undistort(const TrkIntr &c, double u, double v, double &x, double &y)
 {

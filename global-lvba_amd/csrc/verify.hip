@@ -2,7 +2,7 @@
 // include/lvba_hip.h, its scalar pieces in verify_device.h).
 //
 // Device design:
-//   verify_undistort_kernel   a thread per keypoint: trk_undistort once per handle, NaN where it fails.
+//   (image_set.hip)           the undistorted keypoints: the handle's ImageSet, image_set_undistort once per handle.
 //   verify_hypothesis_kernel  generates and scores in one launch.  The grid is the list of (pair, block of VERIFY_HB hypotheses) of
 //                             every pair of the call; a workgroup is one wavefront and a lane owns one hypothesis.  In its prologue
 //                             the lane draws its sample, reads those matches and solves; under the eight-point method the 8 x 9
@@ -21,7 +21,6 @@
 // No atomics of any kind, every choice an integer comparison: two calls give the same bytes, and so does a pair verified alone or
 // in a batch in any order (the generator does not know the pair's position, the grid or the lane).
 #include <hip/hip_runtime.h>
-#include <math.h>
 #include <stdint.h>
 #include <algorithm>
 #include <cmath>
@@ -29,6 +28,8 @@
 #include "lvba_common.h"
 #include "mempool.h"
 #include "voxel_internal.h"
+#include "segments.h"
+#include "image_set.h"
 #include "verify_device.h"
 #include "wave_ops.h"
 #include "../../include/lvba_hip.h"
@@ -36,10 +37,7 @@
 using namespace lvba;
 
 struct lvba_verify_s {
-    int device = 0;
-    int32_t n_images = 0;
-    std::vector<int64_t> off;      // [n_images + 1]
-    double *d_xy = nullptr;        // [total][2] undistorted normalised keypoints, NaN where the undistortion fails
+    ImageSet kp;                   // offsets on the host, undistorted points on the device
     bool has_R = false;
     std::vector<double> R;         // [n_images][9]
     double focal_sum = 0.0;        // fx + fy
@@ -60,15 +58,6 @@ struct VerifyTask {
     double R[9];                    // R_hi R_lo^T (method 1)
 };
 struct VerifyBest { int32_t count, h; double E[9]; };   // count -1: no valid hypothesis
-
-__global__ __launch_bounds__(256) void verify_undistort_kernel(int64_t n, const float *__restrict__ uv, const TrkIntr cam, double *__restrict__ xy)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    double x, y;
-    if (!trk_undistort(cam, (double)uv[2 * i], (double)uv[2 * i + 1], x, y)) x = y = NAN;
-    xy[2 * i] = x; xy[2 * i + 1] = y;
-}
 
 // the undistorted coordinates (x_lo, y_lo, x_hi, y_hi) of match i of the task
 __device__ __forceinline__ void load_match(const VerifyTask &t, const int32_t *__restrict__ matches, const double *__restrict__ xy, int i,
@@ -284,11 +273,7 @@ __global__ __launch_bounds__(256) void verify_mask_kernel(int64_t n, int n_tasks
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i > n) return;
     if (i == n) { flag[i] = 0; return; }
-    int lo = 0, hi = n_tasks; // the last pair with m_off <= i (empty pairs share an offset with their successor)
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (tasks[mid].m_off <= i) lo = mid; else hi = mid;
-    }
+    const int lo = segment_of([=](int k) { return tasks[k].m_off; }, n_tasks, i);
     const VerifyTask &t = tasks[lo];
     bool ok = status[lo] == VERIFY_OK;
     if (ok) {
@@ -330,26 +315,19 @@ int32_t check_opts(const lvba_verify_s *v, const lvba_verify_opts *opts, lvba_ve
     return LVBA_OK;
 }
 
-double gate_tau2(const lvba_verify_s *v, double max_error_px)
-{
-    const double tau = (2.0 * max_error_px) / v->focal_sum;
-    return tau * tau;
-}
-
 // the task of pair (a, b) with matches [m_off, m_off + m) of `matches`, every index checked
 int32_t make_task(const lvba_verify_s *v, int64_t a, int64_t b, int64_t m_off, int64_t m, const int32_t *matches, int method, VerifyTask &t)
 {
-    if (a < 0 || a >= v->n_images || b < 0 || b >= v->n_images || a == b)
-        return lvba_fail(LVBA_ERR_ARG, "pair (%lld, %lld) of %d images (two different images)", (long long)a, (long long)b, v->n_images);
+    TRY(check_image_pair(a, b, v->kp.n_images));
     if (m < 0 || m >= INT32_MAX) return lvba_fail(LVBA_ERR_ARG, "pair (%lld, %lld) with %lld matches", (long long)a, (long long)b, (long long)m);
-    const int64_t n_a = v->off[a + 1] - v->off[a], n_b = v->off[b + 1] - v->off[b];
+    const int64_t n_a = v->kp.off[a + 1] - v->kp.off[a], n_b = v->kp.off[b + 1] - v->kp.off[b];
     for (int64_t i = m_off; i < m_off + m; ++i)
         if (matches[2 * i] < 0 || matches[2 * i] >= n_a || matches[2 * i + 1] < 0 || matches[2 * i + 1] >= n_b)
             return lvba_fail(LVBA_ERR_ARG, "match %lld = (%d, %d) of pair (%lld, %lld) with %lld and %lld keypoints", (long long)i, matches[2 * i],
                              matches[2 * i + 1], (long long)a, (long long)b, (long long)n_a, (long long)n_b);
     t = VerifyTask{};
     t.lo = (int32_t)std::min(a, b); t.hi = (int32_t)std::max(a, b); t.swap = a > b ? 1 : 0;
-    t.lo_off = v->off[t.lo]; t.hi_off = v->off[t.hi]; t.m_off = m_off; t.m = (int32_t)m;
+    t.lo_off = v->kp.off[t.lo]; t.hi_off = v->kp.off[t.hi]; t.m_off = m_off; t.m = (int32_t)m;
     if (method == VERIFY_KNOWN_ROTATION) verify_relative_rotation(&v->R[9 * (size_t)t.lo], &v->R[9 * (size_t)t.hi], t.R);
     return LVBA_OK;
 }
@@ -374,13 +352,13 @@ int32_t run_hypotheses(hipStream_t s, const lvba_verify_s *v, std::vector<Verify
     DevBuf d_tiles(s);
     HIPCHK(d_tiles.alloc(sizeof(int2) * tiles.size()));
     HIPCHK(lvba::copy_h2d(d_tiles.p, tiles.data(), sizeof(int2) * tiles.size()));
-    const double tau2 = gate_tau2(v, o.max_error_px);
+    const double tau2 = match_tau2(v->focal_sum, o.max_error_px);
     if (o.method == VERIFY_EIGHT_POINT)
         verify_hypothesis_kernel<VERIFY_EIGHT_POINT><<<(unsigned)tiles.size(), VERIFY_HB, 0, s>>>(
-            d_tasks.as<VerifyTask>(), d_tiles.as<int2>(), d_matches, v->d_xy, o.seed, o.hypotheses, tau2, d_blk.as<VerifyBest>(), diag_E, diag_count);
+            d_tasks.as<VerifyTask>(), d_tiles.as<int2>(), d_matches, v->kp.d_xy, o.seed, o.hypotheses, tau2, d_blk.as<VerifyBest>(), diag_E, diag_count);
     else
         verify_hypothesis_kernel<VERIFY_KNOWN_ROTATION><<<(unsigned)tiles.size(), VERIFY_HB, 0, s>>>(
-            d_tasks.as<VerifyTask>(), d_tiles.as<int2>(), d_matches, v->d_xy, o.seed, o.hypotheses, tau2, d_blk.as<VerifyBest>(), diag_E, diag_count);
+            d_tasks.as<VerifyTask>(), d_tiles.as<int2>(), d_matches, v->kp.d_xy, o.seed, o.hypotheses, tau2, d_blk.as<VerifyBest>(), diag_E, diag_count);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s)); // the tile list goes with this scope
     return LVBA_OK;
@@ -399,45 +377,20 @@ extern "C" int32_t lvba_verify_create(int32_t device, int32_t n_images, const in
                                       const double *Rcw, lvba_verify_t *out)
 {
     if (!out || n_images < 0 || !kp_off || !intr) return lvba_fail(LVBA_ERR_ARG, "null argument or n_images < 0");
-    if (kp_off[0] != 0) return lvba_fail(LVBA_ERR_ARG, "kp_off[0] = %lld (0)", (long long)kp_off[0]);
-    for (int i = 0; i < n_images; ++i)
-        if (kp_off[i + 1] < kp_off[i]) return lvba_fail(LVBA_ERR_ARG, "kp_off decreases at image %d", i);
+    TRY(check_offsets("kp_off", "image", n_images, kp_off));
     const int64_t total = kp_off[n_images];
     if (total > 0 && !keypoints_uv) return lvba_fail(LVBA_ERR_ARG, "null keypoints");
-    for (int k = 0; k < 8; ++k)
-        if (!std::isfinite(intr[k])) return lvba_fail(LVBA_ERR_ARG, "intrinsic %d is not finite", k);
-    if (!(intr[0] > 0.0 && intr[1] > 0.0)) return lvba_fail(LVBA_ERR_ARG, "focal lengths %g, %g (> 0)", intr[0], intr[1]);
-    if (Rcw)
-        for (int64_t k = 0; k < 9 * (int64_t)n_images; ++k)
-            if (!std::isfinite(Rcw[k])) return lvba_fail(LVBA_ERR_ARG, "camera %lld: non-finite rotation", (long long)(k / 9));
+    TRY(check_intrinsics_finite(intr));
+    TRY(check_focal_lengths(intr));
+    if (Rcw) TRY(check_rotations_finite(Rcw, 0, n_images));
     TRY(check_device(device));
     HIPCHK(hipSetDevice(device));
     lvba_verify_s *v = new lvba_verify_s;
-    v->device = device; v->n_images = n_images;
-    v->off.assign(kp_off, kp_off + n_images + 1);
+    v->kp = ImageSet{device, n_images, std::vector<int64_t>(kp_off, kp_off + n_images + 1)};
     v->focal_sum = intr[0] + intr[1];
     if (Rcw) { v->R.assign(Rcw, Rcw + 9 * (size_t)n_images); v->has_R = true; }
-    if (total > 0) {
-        const TrkIntr cam{intr[0], intr[1], intr[2], intr[3], intr[4], intr[5], intr[6], intr[7]};
-        hipError_t e = DevicePool::get().alloc((void **)&v->d_xy, 16 * (size_t)total);
-        if (e == hipSuccess) {
-            ScopedStream sg;
-            DevBuf d_uv;
-            e = sg.acquire();
-            d_uv.stream = sg.s;
-            if (e == hipSuccess) e = d_uv.alloc(8 * (size_t)total);
-            if (e == hipSuccess) e = lvba::copy_h2d(d_uv.p, keypoints_uv, 8 * (size_t)total);
-            if (e == hipSuccess) {
-                verify_undistort_kernel<<<grid_for(total, 256), 256, 0, sg.s>>>(total, d_uv.as<float>(), cam, v->d_xy);
-                e = hipGetLastError();
-            }
-            if (e == hipSuccess) e = hipStreamSynchronize(sg.s);
-        }
-        if (e != hipSuccess) {
-            lvba_verify_destroy(v);
-            return lvba_fail(e == hipErrorOutOfMemory ? LVBA_ERR_NOMEM : LVBA_ERR_DEVICE, "keypoint upload: %s", hipGetErrorString(e));
-        }
-    }
+    const int32_t rc = image_set_undistort(v->kp, trk_intr_of(intr), keypoints_uv, false); // the pixels: on the device for this call only
+    if (rc != LVBA_OK) { lvba_verify_destroy(v); return rc; }
     *out = v;
     return LVBA_OK;
 }
@@ -445,9 +398,9 @@ extern "C" int32_t lvba_verify_create(int32_t device, int32_t n_images, const in
 extern "C" int32_t lvba_verify_destroy(lvba_verify_t v)
 {
     if (!v) return LVBA_OK;
-    (void)hipSetDevice(v->device);
+    (void)hipSetDevice(v->kp.device);
     (void)hipDeviceSynchronize();
-    if (v->d_xy) DevicePool::get().free(v->d_xy);
+    image_set_free(v->kp);
     delete v;
     return LVBA_OK;
 }
@@ -462,9 +415,7 @@ extern "C" int32_t lvba_verify_pairs(lvba_verify_t v, int64_t n_pairs, const int
     lvba_verify_opts o;
     TRY(check_opts(v, opts, o));
     if (n_pairs >= INT32_MAX / 2) return lvba_fail(LVBA_ERR_UNSUPPORTED, "%lld pairs in one call", (long long)n_pairs);
-    if (match_off[0] != 0) return lvba_fail(LVBA_ERR_ARG, "match_off[0] = %lld (0)", (long long)match_off[0]);
-    for (int64_t p = 0; p < n_pairs; ++p)
-        if (match_off[p + 1] < match_off[p]) return lvba_fail(LVBA_ERR_ARG, "match_off decreases at pair %lld", (long long)p);
+    TRY(check_offsets("match_off", "pair", n_pairs, match_off));
     const int64_t total = match_off[n_pairs];
     if (total >= VERIFY_MAX_MATCHES) return lvba_fail(LVBA_ERR_UNSUPPORTED, "%lld matches in one call (below 2^31)", (long long)total);
     if (total > 0 && !matches) return lvba_fail(LVBA_ERR_ARG, "null matches");
@@ -473,12 +424,12 @@ extern "C" int32_t lvba_verify_pairs(lvba_verify_t v, int64_t n_pairs, const int
         TRY(make_task(v, pairs[2 * p], pairs[2 * p + 1], match_off[p], match_off[p + 1] - match_off[p], matches, o.method, tasks[(size_t)p]));
     inlier_off[0] = 0;
     if (n_pairs == 0) return LVBA_OK;
-    HIPCHK(hipSetDevice(v->device));
+    HIPCHK(hipSetDevice(v->kp.device));
     ScopedStream sg;
     HIPCHK(sg.acquire());
     hipStream_t s = sg.s;
     const int np = (int)n_pairs;
-    const double tau2 = gate_tau2(v, o.max_error_px);
+    const double tau2 = match_tau2(v->focal_sum, o.max_error_px);
     DevBuf d_m(s), d_tasks(s), d_blk(s), d_res(s), d_E(s), d_int(s), d_flag(s), d_excl(s), d_off(s), d_out(s);
     HIPCHK(d_m.alloc(8 * (size_t)total));
     if (total > 0) HIPCHK(lvba::copy_h2d(d_m.p, matches, 8 * (size_t)total));
@@ -489,15 +440,15 @@ extern "C" int32_t lvba_verify_pairs(lvba_verify_t v, int64_t n_pairs, const int
     verify_pick_kernel<<<grid_for(np, 256), 256, 0, s>>>(np, d_tasks.as<VerifyTask>(), d_blk.as<VerifyBest>(), d_res.as<VerifyBest>());
     HIPCHK(hipGetLastError());
     if (o.method == VERIFY_EIGHT_POINT)
-        verify_refine_kernel<VERIFY_EIGHT_POINT><<<(unsigned)np, REFINE_BLOCK, 0, s>>>(d_tasks.as<VerifyTask>(), d_m.as<int32_t>(), v->d_xy, tau2,
+        verify_refine_kernel<VERIFY_EIGHT_POINT><<<(unsigned)np, REFINE_BLOCK, 0, s>>>(d_tasks.as<VerifyTask>(), d_m.as<int32_t>(), v->kp.d_xy, tau2,
                                                                                       o.refine_rounds, o.min_inliers, d_res.as<VerifyBest>(),
                                                                                       d_E.as<double>(), d_status, d_cnt, d_h);
     else
-        verify_refine_kernel<VERIFY_KNOWN_ROTATION><<<(unsigned)np, REFINE_BLOCK, 0, s>>>(d_tasks.as<VerifyTask>(), d_m.as<int32_t>(), v->d_xy, tau2,
+        verify_refine_kernel<VERIFY_KNOWN_ROTATION><<<(unsigned)np, REFINE_BLOCK, 0, s>>>(d_tasks.as<VerifyTask>(), d_m.as<int32_t>(), v->kp.d_xy, tau2,
                                                                                          o.refine_rounds, o.min_inliers, d_res.as<VerifyBest>(),
                                                                                          d_E.as<double>(), d_status, d_cnt, d_h);
     HIPCHK(hipGetLastError());
-    verify_mask_kernel<<<grid_for(total + 1, 256), 256, 0, s>>>(total, np, d_tasks.as<VerifyTask>(), d_m.as<int32_t>(), v->d_xy, tau2,
+    verify_mask_kernel<<<grid_for(total + 1, 256), 256, 0, s>>>(total, np, d_tasks.as<VerifyTask>(), d_m.as<int32_t>(), v->kp.d_xy, tau2,
                                                                 d_E.as<double>(), d_status, d_flag.as<uint32_t>());
     HIPCHK(hipGetLastError());
     TRY(scan_excl<uint32_t>(s, d_flag.as<uint32_t>(), d_excl.as<uint32_t>(), (size_t)total + 1));
@@ -533,7 +484,7 @@ extern "C" int32_t lvba_verify_hypotheses(lvba_verify_t v, int32_t a, int32_t b,
         std::fill(count, count + H, -1);
         return LVBA_OK;
     }
-    HIPCHK(hipSetDevice(v->device));
+    HIPCHK(hipSetDevice(v->kp.device));
     ScopedStream sg;
     HIPCHK(sg.acquire());
     DevBuf d_m(sg.s), d_tasks(sg.s), d_blk(sg.s), d_E(sg.s), d_c(sg.s);
@@ -553,7 +504,7 @@ extern "C" int32_t lvba_verify_score(lvba_verify_t v, int32_t a, int32_t b, int6
     std::vector<VerifyTask> tasks(1);
     TRY(make_task(v, a, b, 0, n_matches, matches, VERIFY_EIGHT_POINT, tasks[0]));
     if (n_matches == 0) return LVBA_OK;
-    HIPCHK(hipSetDevice(v->device));
+    HIPCHK(hipSetDevice(v->kp.device));
     ScopedStream sg;
     HIPCHK(sg.acquire());
     const size_t n = (size_t)n_matches;
@@ -564,8 +515,8 @@ extern "C" int32_t lvba_verify_score(lvba_verify_t v, int32_t a, int32_t b, int6
     HIPCHK(lvba::copy_h2d(d_tasks.p, tasks.data(), sizeof(VerifyTask)));
     HIPCHK(lvba::copy_h2d(d_E.p, E, 72));
     HIPCHK(lvba::copy_h2d(d_st.p, &ok, 4));
-    verify_mask_kernel<<<grid_for(n_matches + 1, 256), 256, 0, sg.s>>>(n_matches, 1, d_tasks.as<VerifyTask>(), d_m.as<int32_t>(), v->d_xy,
-                                                                      gate_tau2(v, max_error_px), d_E.as<double>(), d_st.as<int32_t>(),
+    verify_mask_kernel<<<grid_for(n_matches + 1, 256), 256, 0, sg.s>>>(n_matches, 1, d_tasks.as<VerifyTask>(), d_m.as<int32_t>(), v->kp.d_xy,
+                                                                      match_tau2(v->focal_sum, max_error_px), d_E.as<double>(), d_st.as<int32_t>(),
                                                                       d_flag.as<uint32_t>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(sg.s));

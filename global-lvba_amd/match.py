@@ -34,12 +34,10 @@ class Matcher:
                 d = np.zeros((0, 128), np.uint8)
             if d.dtype != np.uint8 or d.ndim != 2 or d.shape[1] != 128:
                 raise ValueError("each image's descriptors must be uint8 [n, 128]")
-            descs.append(np.ascontiguousarray(d))
+            descs.append(d)
+        flat, self.off = L.flatten_rows(descs, np.uint8, 128)
         self.n_images = len(descs)
-        self.counts = np.array([len(d) for d in descs], np.int64)
-        self.off = np.zeros(self.n_images + 1, np.int64)
-        np.cumsum(self.counts, out=self.off[1:])
-        flat = np.concatenate(descs) if descs else np.zeros((0, 128), np.uint8)
+        self.counts = np.diff(self.off)
         self.device = int(device)
         self.has_geometry = False
         self.has_depth = False
@@ -67,10 +65,9 @@ class Matcher:
         """keypoints: per image [n_i, 2] pixels (rounded to fp32), in descriptor order; intr (fx, fy, cx, cy, k1, k2, p1, p2);
         Rcw [M, 3, 3], tcw [M, 3] = T_cam<-world.  May be called again with new poses; the points of set_depth are dropped then
         (they were lifted with the old poses)."""
-        kps = [np.asarray(k, np.float32).reshape(-1, 2) for k in keypoints]
-        if len(kps) != self.n_images or any(len(k) != n for k, n in zip(kps, self.counts)):
+        uv, off = L.flatten_rows(keypoints, np.float32, 2)
+        if not np.array_equal(off, self.off):
             raise ValueError("keypoints must give one [n_i, 2] array per image, a row per descriptor")
-        uv = np.ascontiguousarray(np.concatenate(kps)) if kps else np.zeros((0, 2), np.float32)
         intr = np.ascontiguousarray(intr, np.float64).reshape(8)
         R = np.ascontiguousarray(Rcw, np.float64).reshape(self.n_images, 9)
         t = np.ascontiguousarray(tcw, np.float64).reshape(self.n_images, 3)

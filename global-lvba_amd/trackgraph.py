@@ -23,21 +23,17 @@ class TrackGraph:
     def __init__(self, keypoints, pairs, matches, obser_thr=3, device=0):
         self._h = None
         lib = L.load()
-        counts = len(keypoints) > 0 and np.ndim(keypoints[0]) == 0
-        n = [int(k) for k in keypoints] if counts else [len(k) for k in keypoints]
-        kp_off = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
-        uv = None
-        if not counts and len(keypoints):
-            uv = np.ascontiguousarray(np.concatenate([np.asarray(k, np.float32).reshape(len(k), -1)[:, :2] if len(k) else np.zeros((0, 2), np.float32)
-                                                      for k in keypoints]), np.float32)
+        counts = len(keypoints) == 0 or np.ndim(keypoints[0]) == 0
+        if counts:
+            uv, kp_off = None, np.concatenate([[0], np.cumsum([int(k) for k in keypoints])]).astype(np.int64)
+        else:
+            uv, kp_off = L.flatten_rows([np.asarray(k, np.float32).reshape(len(k), -1)[:, :2] if len(k) else [] for k in keypoints], np.float32, 2)
         pr = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
-        ms = [np.asarray(m, np.int32).reshape(-1, 2) for m in matches]
-        if len(ms) != len(pr):
-            raise ValueError(f"{len(pr)} pairs but {len(ms)} match arrays")
-        match_off = np.concatenate([[0], np.cumsum([len(m) for m in ms])]).astype(np.int64)
-        flat = np.ascontiguousarray(np.concatenate(ms)) if ms else np.zeros((0, 2), np.int32)
+        flat, match_off = L.flatten_rows(matches, np.int32, 2)
+        if len(match_off) - 1 != len(pr):
+            raise ValueError(f"{len(pr)} pairs but {len(match_off) - 1} match arrays")
         h, info = C.c_void_p(), L.TrackGraphInfo()
-        L.check(lib.lvba_trackgraph_create(device, len(n), kp_off.ctypes.data, None if uv is None else _ptr(uv), len(pr), _ptr(pr),
+        L.check(lib.lvba_trackgraph_create(device, len(kp_off) - 1, kp_off.ctypes.data, None if uv is None else _ptr(uv), len(pr), _ptr(pr),
                                            match_off.ctypes.data, _ptr(flat), int(obser_thr), C.byref(h), C.byref(info)))
         self._h, self._lib, self.has_uv = h, lib, uv is not None
         self.info = info.as_dict()

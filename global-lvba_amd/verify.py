@@ -25,14 +25,6 @@ def verify_opts(lib=None, **kw):
     return o
 
 
-def _csr(matches):
-    ms = [np.asarray(m, np.int32).reshape(-1, 2) for m in matches]
-    off = np.zeros(len(ms) + 1, np.int64)
-    np.cumsum([len(m) for m in ms], out=off[1:])
-    flat = np.ascontiguousarray(np.concatenate(ms)) if ms else np.zeros((0, 2), np.int32)
-    return flat, off
-
-
 class Verifier:
     """The undistorted keypoints of a set of images resident on a GPU.  keypoints: a sequence of [n_i, 2] pixel arrays (rounded to
     fp32); intr (fx, fy, cx, cy, k1, k2, p1, p2); Rcw [M, 3, 3] = the rotations of T_cam<-world, or None (then only the pose-free
@@ -40,12 +32,9 @@ class Verifier:
 
     def __init__(self, keypoints, intr, Rcw=None, device=0):
         self.lib = L.load()
-        kps = [np.asarray(k, np.float32).reshape(-1, 2) for k in keypoints]
-        self.n_images = len(kps)
-        self.counts = np.array([len(k) for k in kps], np.int64)
-        self.off = np.zeros(self.n_images + 1, np.int64)
-        np.cumsum(self.counts, out=self.off[1:])
-        uv = np.ascontiguousarray(np.concatenate(kps)) if kps else np.zeros((0, 2), np.float32)
+        uv, self.off = L.flatten_rows(keypoints, np.float32, 2)
+        self.n_images = len(self.off) - 1
+        self.counts = np.diff(self.off)
         intr = np.ascontiguousarray(intr, np.float64).reshape(8)
         R = None if Rcw is None else np.ascontiguousarray(Rcw, np.float64).reshape(self.n_images, 9)
         self.has_rotations = R is not None
@@ -95,7 +84,7 @@ class Verifier:
     def pairs(self, pairs, matches, **opts):
         """(inlier_matches, report): one int32 [m, 2] array per pair in the order of `pairs` (empty arrays are kept), and a dict
         of arrays E [P, 3, 3], status, n_inliers, n_matches, best_h."""
-        flat, off = _csr(matches)
+        flat, off = L.flatten_rows(matches, np.int32, 2)
         inl, ioff, report = self.pairs_csr(pairs, flat, off, **opts)
         return [inl[ioff[p]:ioff[p + 1]] for p in range(len(ioff) - 1)], report
 

@@ -1,7 +1,7 @@
-// scan_points_check.cpp -- csrc/scan_points.h compiled for the host (tests/test_ordering.py): the frame search against a linear
-// scan over sets with empty frames, in both offset dialects; the leaf key, its squared distance and the key packing against
-// the expressions of down_sampling_voxel2 written out literally, at the edges of the rule; pose_apply against the written-out
-// rows.  Built with -ffp-contract=off like the files that call leaf_key_of.
+// scan_points_check.cpp -- csrc/scan_points.h compiled for the host (tests/test_ordering.py): the leaf key, its squared distance
+// and the key packing against the expressions of down_sampling_voxel2 written out literally, at the edges of the rule;
+// pose_apply against the written-out rows.  Built with -ffp-contract=off like the files that call leaf_key_of.  (The frame
+// search against a linear scan, in both offset dialects: tests/segments_check.cpp, with the search it forwards to.)
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -18,22 +18,6 @@ static int fails = 0;
             if (++fails <= 20) { std::printf("FAILED %s:%d %s: ", __FILE__, __LINE__, #cond); std::printf(__VA_ARGS__); std::printf("\n"); } \
         }                                                                                                                   \
     } while (0)
-
-static void check_frames(const std::vector<int> &count, int64_t first)
-{
-    const int nf = (int)count.size();
-    std::vector<int64_t> off(nf + 1);
-    off[0] = first;
-    for (int f = 0; f < nf; ++f) off[f + 1] = off[f] + count[f];
-    const int64_t P = off[nf] - off[0];
-    for (int64_t i = 0; i < P; ++i) {
-        int want = -1;
-        for (int f = 0; f < nf; ++f)
-            if (off[f] - off[0] <= i && i < off[f + 1] - off[0]) want = f;
-        const int got = frame_of_point(off.data(), nf, i);
-        CHECK(got == want, "frames=%d first=%lld i=%lld: frame %d, linear scan %d", nf, (long long)first, (long long)i, got, want);
-    }
-}
 
 // one point against the literal rule: tools.hpp:318-341, and the range clause of the packing
 static void check_leaf(const float q[3], double leaf)
@@ -69,13 +53,6 @@ static void check_leaf(const float q[3], double leaf)
 int main()
 {
     static_assert(KEY_BIAS == 1 << 20, "3 x 21 bits");
-    for (const int64_t first : {(int64_t)0, (int64_t)1000}) {
-        check_frames({0, 1, 0, 0, 65, 3, 0}, first);
-        check_frames({5}, first);
-        check_frames({0, 0, 4}, first);
-        check_frames({4, 0, 0}, first);
-    }
-
     const float eps = 1.0f / 8388608.0f; // 2^-23
     for (const double leaf : {0.01, 0.1, 0.5, 1.0}) {
         const float l = (float)leaf;

@@ -93,11 +93,21 @@ def test_key_repacking_keeps_order_and_round_trips(tmp_path):
 
 
 def test_scan_point_rules(tmp_path):
-    """csrc/scan_points.h: the frame of a point against a linear scan (empty frames, offsets that start at 0 or not), the leaf
-    key, its squared distance and the 3 x 21-bit packing against the literal expressions of down_sampling_voxel2 at the edges
-    of the rule (+-0, +-leaf and its neighbours, the ends of the packable range, NaN), the pose rows (tests/scan_points_check.cpp)."""
+    """csrc/scan_points.h: the leaf key, its squared distance and the 3 x 21-bit packing against the literal expressions of
+    down_sampling_voxel2 at the edges of the rule (+-0, +-leaf and its neighbours, the ends of the packable range, NaN), the
+    pose rows (tests/scan_points_check.cpp).  The frame of a point: test_segment_search."""
     exe = str(tmp_path / "scan_points_check")
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror",
                            os.path.join(ROOT, "tests", "scan_points_check.cpp"), "-o", exe])
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 0 and "scan points ok" in out.stdout, out.stdout[-3000:]
+
+
+def test_segment_search(tmp_path):
+    """csrc/segments.h: the last segment whose offset is <= i against a linear scan -- pointer and callable form, 32- and 64-bit
+    indices, one segment, empty segments at the start, at the end and three in a row, elements equal to an offset, the last
+    element -- and its two forwards, frame_of_point (offsets that start at 0 or not) and tg_owner (tests/segments_check.cpp)."""
+    exe = str(tmp_path / "segments_check")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", os.path.join(ROOT, "tests", "segments_check.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and "segments ok" in out.stdout, out.stdout[-3000:]
