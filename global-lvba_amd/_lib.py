@@ -14,11 +14,11 @@ SYMBOLS = [
     "lvba_version", "lvba_last_error", "lvba_device_count", "lvba_balm_default_opts", "lvba_shard_range",
     "lvba_balm_create", "lvba_balm_create_dev", "lvba_balm_destroy", "lvba_balm_configure", "lvba_balm_info", "lvba_balm_cost",
     "lvba_balm_eval", "lvba_balm_eval_blocks", "lvba_balm_solve", "lvba_balm_refine", "lvba_balm_lm_begin", "lvba_balm_lm_step",
-    "lvba_balm_lm_end", "lvba_balm_set_groups", "lvba_balm_refine_groups", "lvba_balm_set_profiling", "lvba_balm_get_profile", "lvba_balm_get_ordering", "lvba_balm_nd_model", "lvba_balm_pair_layout",
+    "lvba_balm_lm_end", "lvba_balm_set_groups", "lvba_balm_refine_groups", "lvba_balm_set_profiling", "lvba_balm_get_profile", "lvba_balm_get_ordering", "lvba_balm_nd_model", "lvba_balm_pair_layout", "lvba_balm_eval_layout",
     "lvba_balm_set_priors", "lvba_balm_prior_residuals", "lvba_cov_default_opts", "lvba_balm_covariance",
     "lvba_balm_set_loss", "lvba_balm_voxel_residuals",
     "lvba_dist_unique_id", "lvba_balm_dist_init", "lvba_balm_dist_init_external", "lvba_visual_dist_init_external",
-    "lvba_visual_default_opts", "lvba_visual_create", "lvba_visual_destroy", "lvba_visual_cost", "lvba_visual_linearize", "lvba_visual_solve", "lvba_visual_info", "lvba_visual_pair_layout", "lvba_visual_dist_init",
+    "lvba_visual_default_opts", "lvba_visual_create", "lvba_visual_destroy", "lvba_visual_cost", "lvba_visual_linearize", "lvba_visual_solve", "lvba_visual_info", "lvba_visual_pair_layout", "lvba_visual_eval_layout", "lvba_visual_dist_init",
     "lvba_visual_refine", "lvba_visual_set_loss", "lvba_visual_residual_sq", "lvba_visual_set_priors", "lvba_visual_prior_residuals",
     "lvba_voxel_default_opts", "lvba_voxmap_build", "lvba_voxmap_destroy", "lvba_voxmap_info", "lvba_voxmap_export",
     "lvba_voxmap_to_balm", "lvba_voxmap_find_planes", "lvba_scans_create", "lvba_scans_destroy", "lvba_voxmap_build_scans",
@@ -93,6 +93,19 @@ def pair_layout(fn, handle):
     d = {f: getattr(o, f) for f, _ in o._fields_}
     d["item_len"], d["item_slot"] = item_len, item_slot
     return d
+
+
+class EvalLayout(C.Structure):
+    _fields_ = [("slices", C.c_int32), ("unit_form", C.c_int32), ("units", C.c_int64), ("unit_grid", C.c_int64),
+                ("point_groups", C.c_int32), ("back_groups", C.c_int32), ("point_grid", C.c_int64), ("back_grid", C.c_int64),
+                ("n_groups", C.c_int64), ("n_factors", C.c_int64), ("n_chunks", C.c_int64)]
+
+
+def eval_layout(fn, handle):
+    """lvba_balm_eval_layout / lvba_visual_eval_layout: the struct's fields."""
+    o = EvalLayout()
+    check(fn(handle, C.byref(o)))
+    return {f: getattr(o, f) for f, _ in o._fields_}
 
 
 class NdModel(C.Structure):
@@ -368,6 +381,8 @@ def load():
     lib.lvba_balm_nd_model.argtypes = [H, C.c_int32, C.POINTER(NdModel)]
     lib.lvba_balm_pair_layout.argtypes = [H, C.POINTER(PairLayout), C.c_void_p, C.c_void_p, C.c_int64]
     lib.lvba_visual_pair_layout.argtypes = [H, C.POINTER(PairLayout), C.c_void_p, C.c_void_p, C.c_int64]
+    lib.lvba_balm_eval_layout.argtypes = [H, C.POINTER(EvalLayout)]
+    lib.lvba_visual_eval_layout.argtypes = [H, C.POINTER(EvalLayout)]
     lib.lvba_balm_set_priors.argtypes = [H, C.c_int32, C.c_void_p]
     lib.lvba_balm_prior_residuals.argtypes = [H, f64p, C.c_void_p, C.POINTER(C.c_double)]
     lib.lvba_cov_default_opts.argtypes = [C.POINTER(CovOpts)]

@@ -167,6 +167,11 @@ class BalmProblem:
         longest_item, longest_multi, and per item item_len / item_slot (-1 - k: partial block k)"""
         return L.pair_layout(self.lib.lvba_balm_pair_layout, self._h)
 
+    def eval_layout(self):
+        """how the factor pass is launched (lvba_balm_eval_layout): slices per pose, units = unit_grid = its (pose, slice)
+        workgroups, n_groups = voxels, n_factors, n_chunks of the voxel pass"""
+        return L.eval_layout(self.lib.lvba_balm_eval_layout, self._h)
+
     def nd_model(self, n_ranks):
         """the nested-dissection plan of this problem's graph on n_ranks ranks and its cost model (lvba_balm_nd_model)"""
         m = L.NdModel()

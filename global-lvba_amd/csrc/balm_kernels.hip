@@ -958,7 +958,7 @@ void launch_eval(const BalmDev &d, const PairDev &pd, const double *poses, doubl
     if (zero_first) hipMemsetAsync(Hblk, 0, (size_t)hblk_doubles * sizeof(double), s);
     if (k0) hipEventRecord(k0, s);
     if (!skip_voxel_pass) launch_voxel_pass(d, poses, chunk_cost, s);
-    const dim3 fgrid((unsigned)(d.n_poses * d.S));
+    const dim3 fgrid((unsigned)balm_factor_grid(d));
     if (d.loss_kind) {
         if (pd.col_form == 2) hipLaunchKernelGGL((balm_factor_kernel<true, true>), fgrid, dim3(256), 0, s, d, poses);
         else hipLaunchKernelGGL((balm_factor_kernel<false, true>), fgrid, dim3(256), 0, s, d, poses);

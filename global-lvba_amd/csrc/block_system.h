@@ -133,6 +133,9 @@ int32_t bs_pattern_slots(BlockSys &bs, lvba::hvec<int64_t> &slots);
 int32_t bs_download_blocks(BlockSys &bs, const int64_t *slots, int64_t n, double *out);
 // read-only view of the pair-pass layout (lvba_balm_pair_layout / lvba_visual_pair_layout, include/lvba_hip.h); the system is built
 int32_t bs_pair_layout(BlockSys &bs, lvba_pair_layout_t *out, int64_t *item_len, int64_t *item_slot, int64_t cap);
+// A test switch read from the environment: unset leaves *out alone; an integer in [lo, hi] replaces it; anything else (empty, not
+// a number, out of range) is refused with LVBA_ERR_ARG -- never a silent fall-back.  (LVBA_SLICES, LVBA_VIS_CAM_FORM)
+int32_t env_int_in_range(const char *name, int32_t lo, int32_t hi, int32_t *out);
 int32_t bs_dist_init(BlockSys &bs, int32_t n_ranks, int32_t rank, const char uid[128], int64_t *group_count_inout);
 int32_t bs_dist_init_external(BlockSys &bs, int32_t n_ranks, int32_t rank, lvba_allreduce_fn fn, void *ctx, int64_t *group_count_inout);
 int32_t bs_nd_model(BlockSys &bs, int32_t n_ranks, double *t_band, double *t_nd, int32_t *arcs, int32_t *sep_poses, int32_t *sep_bb,

@@ -303,6 +303,18 @@ int32_t bs_pair_layout(BlockSys &bs, lvba_pair_layout_t *out, int64_t *item_len,
     return LVBA_OK;
 }
 
+int32_t env_int_in_range(const char *name, int32_t lo, int32_t hi, int32_t *out)
+{
+    const char *e = getenv(name);
+    if (!e) return LVBA_OK;
+    char *end = nullptr;
+    const long v = strtol(e, &end, 10);
+    if (end == e || *end != '\0' || v < lo || v > hi)
+        return lvba_fail(LVBA_ERR_ARG, "%s=\"%s\": an integer in %d .. %d expected", name, e, lo, hi);
+    *out = (int32_t)v;
+    return LVBA_OK;
+}
+
 static double bs_now_ms()
 {
     struct timespec ts;
@@ -385,6 +397,10 @@ static int32_t nd_alloc(BlockSys &bs, const NdPlan &pl)
 int32_t bs_build(BlockSys &bs, int32_t N, int64_t G, const int64_t *voff, const int32_t *pidx)
 {
     if (bs.built) return LVBA_OK;
+    // LVBA_SLICES=1..64 replaces the slice rule's count below (0: the rule).  Read here, before anything is allocated, so that a
+    // refused value leaves the handle as it was
+    int32_t slices_env = 0;
+    TRY(env_int_in_range("LVBA_SLICES", 1, 64, &slices_env));
     const bool timing = timing_on("build");
     double tmark = bs_now_ms();
     HIPCHK(hipSetDevice(bs.device));
@@ -616,6 +632,9 @@ int32_t bs_build(BlockSys &bs, int32_t N, int64_t G, const int64_t *voff, const 
         const int64_t avg = F / N;
         Ssz = std::min<int64_t>(Ssz, std::max<int64_t>(1, avg / 256));
         bs.S = (int32_t)std::max<int64_t>(1, std::min<int64_t>(Ssz, 64));
+        // (both stages size their slice partials from bs.S after this call; the switch is how the tests reach S > 1, S > a list's
+        // length and empty slices at test sizes)
+        if (slices_env) bs.S = slices_env;
         TRY(bs_dmalloc(bs, &bs.d_Y, 18 * F));
         TRY(bs_dmalloc(bs, &bs.d_blk_off, bs.n_items + 1));
         TRY(bs_dmalloc(bs, &bs.d_blk_slot, bs.n_items));

@@ -407,6 +407,17 @@ extern "C" int32_t lvba_balm_pair_layout(lvba_balm_t h, lvba_pair_layout_t *out,
     return bs_pair_layout(h->bs, out, item_len, item_slot, cap);
 }
 
+extern "C" int32_t lvba_balm_eval_layout(lvba_balm_t h, lvba_eval_layout_t *out)
+{
+    if (!h || !out) return fail(LVBA_ERR_ARG, "NULL argument");
+    TRY(finalize(h));
+    const BalmDev d = h->dev();
+    memset(out, 0, sizeof *out);
+    out->slices = d.S; out->unit_form = 0; out->units = (int64_t)d.n_poses * d.S; out->unit_grid = balm_factor_grid(d);
+    out->n_groups = d.V; out->n_factors = d.F; out->n_chunks = d.n_chunks;
+    return LVBA_OK;
+}
+
 extern "C" int32_t lvba_balm_get_ordering(lvba_balm_t h, int32_t *perm)
 {
     if (!h || !perm) return fail(LVBA_ERR_ARG, "NULL argument");

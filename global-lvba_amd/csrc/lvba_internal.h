@@ -82,7 +82,20 @@ struct VisDev {
     // robust losses (visual_loss.h), [0] reprojection blocks, [1] plane blocks; robust = 0: both TRIVIAL, the ROBUST=false kernels run
     int32_t robust, loss_kind[2];
     double loss_scale[2];
+    int32_t cam_form;              // vis_cam_kernel: -1 the rule of vis_eval_layout, 0 / 1 that form (LVBA_VIS_CAM_FORM, read at finalize)
 };
+
+// How the kernels that form the reduced camera system and back-substitute are launched for d (visual_kernels.hip): the launchers
+// and lvba_visual_eval_layout both take it from vis_eval_layout.
+struct VisEvalLayout {
+    int32_t cam_form;              // 0: a workgroup per (camera, slice) unit, 1: a wavefront per unit (four units per workgroup)
+    int64_t cam_units;             // M * S
+    unsigned cam_grid, point_grid, back_grid;
+    int32_t point_groups, back_groups; // groups of 64 landmarks a workgroup of vis_point_kernel / vis_back_kernel walks
+};
+VisEvalLayout vis_eval_layout(const VisDev &d);
+// workgroups of balm_factor_kernel: one per (pose, slice) (launch_eval and lvba_balm_eval_layout)
+inline int64_t balm_factor_grid(const BalmDev &d) { return (int64_t)d.n_poses * d.S; }
 
 
 // One pose prior (lvba_balm_set_priors) bound to the solver order: I, J solver pose indices; flip: I < J (the cross block is stored

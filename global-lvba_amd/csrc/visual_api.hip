@@ -39,6 +39,7 @@ struct lvba_visual_s {
     int32_t loss_kind[2] = {0, 0}; // [0] reprojection, [1] plane: LVBA_LOSS_*; scale 0 on TRIVIAL
     double loss_scale[2] = {0.0, 0.0};
     bool finalized = false;
+    int32_t cam_form = -1;         // LVBA_VIS_CAM_FORM=0|1 as read at finalize; -1: the rule (vis_eval_layout)
     bool have_lin = false;         // bs holds the reduced system of an lvba_visual_linearize (lvba_visual_solve); a refine replaces it
     double intr[8] = {}, sig_px = 0.5, sig_pl = 0.01;
     // camera pose priors (lvba_visual_set_priors): as the caller gave them, and bound to the solver order (bind_priors)
@@ -78,6 +79,7 @@ struct lvba_visual_s {
         d.dist = (bs.distributed() || vp.tab.n > 0) ? 1 : 0; d.count_cams = bs.rank == 0 ? 1 : 0; d.camsum = d_camsum; d.colsum = d_colsum;
         d.robust = (loss_kind[0] != LVBA_LOSS_TRIVIAL || loss_kind[1] != LVBA_LOSS_TRIVIAL) ? 1 : 0;
         for (int f = 0; f < 2; ++f) { d.loss_kind[f] = loss_kind[f]; d.loss_scale[f] = loss_scale[f]; }
+        d.cam_form = cam_form;
         return d;
     }
 };
@@ -191,8 +193,12 @@ static int32_t finalize(lvba_visual_s *h)
     if (h->finalized) return LVBA_OK;
     BlockSys &bs = h->bs;
     HIPCHK(hipSetDevice(bs.device));
+    // read once, here: a launch never looks at the environment; a refused value leaves the handle as it was
+    int32_t form_env = -1;
+    TRY(env_int_in_range("LVBA_VIS_CAM_FORM", 0, 1, &form_env));
     bs.spd = true; // S = sum Jc^T Jc + D^2 - sum Y Y^T is the Schur complement of a positive definite matrix
     TRY(bs_build(bs, h->M, h->Ta, h->h_off.data(), h->h_cam.data()));
+    h->cam_form = form_env;
     {
         lvba::hvec<int32_t> cam((size_t)h->O);
         for (int64_t o = 0; o < h->O; ++o) cam[o] = bs.iperm[h->h_cam[o]];
@@ -457,6 +463,19 @@ extern "C" int32_t lvba_visual_pair_layout(lvba_visual_t h, lvba_pair_layout_t *
     if (!h || !out) return fail(LVBA_ERR_ARG, "NULL argument");
     TRY(finalize(h));
     return bs_pair_layout(h->bs, out, item_len, item_slot, cap);
+}
+
+extern "C" int32_t lvba_visual_eval_layout(lvba_visual_t h, lvba_eval_layout_t *out)
+{
+    if (!h || !out) return fail(LVBA_ERR_ARG, "NULL argument");
+    TRY(finalize(h));
+    const VisDev d = h->dev();
+    const VisEvalLayout l = vis_eval_layout(d);
+    memset(out, 0, sizeof *out);
+    out->slices = d.S; out->unit_form = l.cam_form; out->units = l.cam_units; out->unit_grid = l.cam_grid;
+    out->point_groups = l.point_groups; out->back_groups = l.back_groups; out->point_grid = l.point_grid; out->back_grid = l.back_grid;
+    out->n_groups = d.Ta; out->n_factors = d.O;
+    return LVBA_OK;
 }
 
 extern "C" int32_t lvba_visual_residual_sq(lvba_visual_t h, const double *q, const double *t, const double *X, double *obs_sq,

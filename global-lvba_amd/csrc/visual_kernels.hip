@@ -663,6 +663,22 @@ static inline unsigned vis_quad_grid(int64_t Ta)
     return (n + 3) / 4;
 }
 
+// The one place the camera kernel's form and the three grids come from.
+// One wavefront per (camera, slice) while a slice is short: its 39 sums cost one 64-lane reduction per WAVEFRONT, which at ~250
+// observations per camera was most of the kernel with four wavefronts of one observation per lane each.  The other form first
+// pays at 2 048 cameras of more than 1 024 observations each; LVBA_VIS_CAM_FORM (d.cam_form) is how the tests reach it.
+VisEvalLayout vis_eval_layout(const VisDev &d)
+{
+    VisEvalLayout l;
+    l.cam_units = (int64_t)d.M * d.S;
+    const int64_t per_slice = d.O / (l.cam_units > 0 ? l.cam_units : 1);
+    l.cam_form = d.cam_form >= 0 ? d.cam_form : per_slice <= 1024 ? 1 : 0;
+    l.cam_grid = (unsigned)(l.cam_form ? (l.cam_units + 3) / 4 : l.cam_units);
+    l.point_groups = 4; l.point_grid = vis_quad_grid(d.Ta);
+    l.back_groups = 1; l.back_grid = vis_back_grid(d.Ta);
+    return l;
+}
+
 void vis_launch_residuals(const VisDev &d, bool jac, const double *qc, const double *tc, const double *Xp, double *part,
                           double *cost_out, hipStream_t s)
 {
@@ -680,7 +696,7 @@ void vis_launch_step_and_trial(const VisDev &d, const double *step_c, const doub
                                double *tc2, double *Xp2, double *part, double *scal, const unsigned long long *gmax, const int *status,
                                double *host_pin, hipStream_t s, const VisPriorDev *vp)
 {
-    const unsigned nb_back = vis_back_grid(d.Ta), nb_apply = nblk(d.M + d.Ta, 256), nb_res = nblk(d.O + d.Ta, 256);
+    const unsigned nb_back = vis_eval_layout(d).back_grid, nb_apply = nblk(d.M + d.Ta, 256), nb_res = nblk(d.O + d.Ta, 256);
     double *pa = part + nb_back, *pr = pa + 2 * (int64_t)nb_apply;
     if (d.robust) hipLaunchKernelGGL(vis_back_kernel<true>, dim3(nb_back), dim3(256), 0, s, d, step_c, qc, tc, Xp, part);
     else hipLaunchKernelGGL(vis_back_kernel<false>, dim3(nb_back), dim3(256), 0, s, d, step_c, qc, tc, Xp, part);
@@ -729,15 +745,12 @@ void vis_launch_reduced_system(const VisDev &d, const PairDev &pd, const double 
 {
     if (zero_first) hipMemsetAsync(Hblk, 0, (size_t)hblk_doubles * sizeof(double), s);
     hipMemsetAsync(gmax, 0, sizeof(unsigned long long), s);
-    if (d.robust) hipLaunchKernelGGL(vis_point_kernel<true>, dim3(vis_quad_grid(d.Ta)), dim3(256), 0, s, d, qc, tc, Xp, radius, min_diag, max_diag, gmax);
-    else hipLaunchKernelGGL(vis_point_kernel<false>, dim3(vis_quad_grid(d.Ta)), dim3(256), 0, s, d, qc, tc, Xp, radius, min_diag, max_diag, gmax);
-    // one wavefront per (camera, slice) while a slice is short: its 39 sums cost one 64-lane reduction per WAVEFRONT, which at ~250
-    // observations per camera was most of the kernel with four wavefronts of one observation per lane each
-    const int64_t per_slice = d.O / ((int64_t)d.M * d.S > 0 ? (int64_t)d.M * d.S : 1);
-    const int wave_units = per_slice <= 1024 ? 1 : 0;
-    const unsigned ncam_wg = (unsigned)(wave_units ? (d.M * d.S + 3) / 4 : d.M * d.S);
-    if (d.robust) hipLaunchKernelGGL(vis_cam_kernel<true>, dim3(ncam_wg), dim3(256), 0, s, d, qc, tc, Xp, wave_units);
-    else hipLaunchKernelGGL(vis_cam_kernel<false>, dim3(ncam_wg), dim3(256), 0, s, d, qc, tc, Xp, wave_units);
+    const VisEvalLayout l = vis_eval_layout(d);
+    if (d.robust) hipLaunchKernelGGL(vis_point_kernel<true>, dim3(l.point_grid), dim3(256), 0, s, d, qc, tc, Xp, radius, min_diag, max_diag, gmax);
+    else hipLaunchKernelGGL(vis_point_kernel<false>, dim3(l.point_grid), dim3(256), 0, s, d, qc, tc, Xp, radius, min_diag, max_diag, gmax);
+    const int wave_units = l.cam_form;
+    if (d.robust) hipLaunchKernelGGL(vis_cam_kernel<true>, dim3(l.cam_grid), dim3(256), 0, s, d, qc, tc, Xp, wave_units);
+    else hipLaunchKernelGGL(vis_cam_kernel<false>, dim3(l.cam_grid), dim3(256), 0, s, d, qc, tc, Xp, wave_units);
     hipLaunchKernelGGL(vis_cam_reduce_kernel, dim3(nblk(d.M, 64)), dim3(64), 0, s, d, radius, min_diag, max_diag, Hblk, g, qc, gmax);
     launch_pairs(pd, Hblk, s);
 }
@@ -745,7 +758,7 @@ void vis_launch_reduced_system(const VisDev &d, const PairDev &pd, const double 
 void vis_launch_back(const VisDev &d, const double *step_c, const double *qc, const double *tc, const double *Xp, double *part,
                      double *model_out, hipStream_t s)
 {
-    const unsigned nb = vis_back_grid(d.Ta);
+    const unsigned nb = vis_eval_layout(d).back_grid;
     if (d.robust) hipLaunchKernelGGL(vis_back_kernel<true>, dim3(nb), dim3(256), 0, s, d, step_c, qc, tc, Xp, part);
     else hipLaunchKernelGGL(vis_back_kernel<false>, dim3(nb), dim3(256), 0, s, d, step_c, qc, tc, Xp, part);
     hipLaunchKernelGGL(vis_reduce_kernel, dim3(1), dim3(1024), 0, s, part, (int64_t)nb, 1, model_out);

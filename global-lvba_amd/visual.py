@@ -135,6 +135,13 @@ class VisualProblem:
         """the pair-pass layout of the reduced camera system (lvba_visual_pair_layout; fields as BalmProblem.pair_layout)"""
         return L.pair_layout(self.lib.lvba_visual_pair_layout, self._h)
 
+    def eval_layout(self):
+        """how the kernels that form the reduced camera system and back-substitute are launched (lvba_visual_eval_layout): slices
+        per camera, unit_form (0 a workgroup, 1 a wavefront per (camera, slice) unit), units, unit_grid, point_groups / point_grid
+        and back_groups / back_grid of the two quad-per-landmark kernels, n_groups = active landmarks, n_factors = their
+        observations"""
+        return L.eval_layout(self.lib.lvba_visual_eval_layout, self._h)
+
     @staticmethod
     def default_opts(**kw):
         o = L.VisualOpts()

@@ -168,6 +168,26 @@ typedef struct {
  * SOLVER's pose order (I > J), or -1 - k for partial block k. */
 int32_t lvba_balm_pair_layout(lvba_balm_t h, lvba_pair_layout_t *out, int64_t *item_len, int64_t *item_slot, int64_t cap);
 
+/* Read-only view of how the evaluation kernels in front of the pair pass are launched for this handle: what the launchers use,
+ * taken from the place they take it from.  A unit is one (pose or camera, slice) pair: every pose's / camera's list of factors /
+ * observations is cut into `slices` pieces (LVBA_SLICES=1..64 replaces the rule's count).  Fields that do not apply to a stage
+ * are 0. */
+typedef struct {
+    int32_t slices;         /* S: slices per pose (LiDAR) or camera (visual) */
+    int32_t unit_form;      /* 0: one workgroup per unit; 1: one wavefront per unit, four units per workgroup (visual stage, short
+                               slices; LVBA_VIS_CAM_FORM=0|1 replaces the rule's choice) */
+    int64_t units;          /* n_poses * slices */
+    int64_t unit_grid;      /* workgroups of the factor pass (LiDAR) / the camera kernel (visual) */
+    int32_t point_groups;   /* visual: groups of 64 landmarks a workgroup of the landmark kernel walks, ... */
+    int32_t back_groups;    /* ... and of the back-substitution */
+    int64_t point_grid;     /* visual: workgroups of the landmark kernel, ... */
+    int64_t back_grid;      /* ... and of the back-substitution */
+    int64_t n_groups;       /* voxels (LiDAR) / landmarks with a plane (visual) */
+    int64_t n_factors;      /* factors (LiDAR) / observations of those landmarks (visual) */
+    int64_t n_chunks;       /* LiDAR: chunks of the voxel pass */
+} lvba_eval_layout_t;
+int32_t lvba_balm_eval_layout(lvba_balm_t h, lvba_eval_layout_t *out);
+
 /* only_residual: cost at `poses` [N][12]; is_avg divides by the (global) voxel count. */
 int32_t lvba_balm_cost(lvba_balm_t h, const double *poses, int32_t is_avg, double *cost);
 
@@ -424,6 +444,8 @@ int32_t lvba_visual_destroy(lvba_visual_t h);
 int32_t lvba_visual_info(lvba_visual_t h, lvba_balm_info_t *info);
 /* The pair-pass layout of the reduced camera system (as lvba_balm_pair_layout: items are runs of camera pairs of one block). */
 int32_t lvba_visual_pair_layout(lvba_visual_t h, lvba_pair_layout_t *out, int64_t *item_len, int64_t *item_slot, int64_t cap);
+/* The launch layout of the kernels that form the reduced camera system and back-substitute (as lvba_balm_eval_layout). */
+int32_t lvba_visual_eval_layout(lvba_visual_t h, lvba_eval_layout_t *out);
 
 /* Multi-GPU: landmark tracks are sharded over the ranks (any partition; contiguous ranges as for the voxels), the cameras are
  * replicated.  Every rank creates its handle from ITS tracks (X, plane, valid and the observation arrays of that shard) and

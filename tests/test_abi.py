@@ -43,7 +43,8 @@ def test_every_struct_has_the_size_the_c_compiler_gives_it(pkg, tmp_path):
              ("lvba_prof_t", L.Prof), ("lvba_visual_opts", L.VisualOpts), ("lvba_visual_trace", L.VisualTrace),
              ("lvba_voxel_opts", L.VoxelOpts), ("lvba_voxmap_info_t", L.VoxmapInfo), ("lvba_window_opts", L.WindowOpts),
              ("lvba_window_info", L.WindowInfo), ("lvba_lidar_ba_opts", L.LidarBaOpts), ("lvba_lidar_ba_report", L.LidarBaReport),
-             ("lvba_fuse_opts", L.FuseOpts), ("lvba_nd_model_t", L.NdModel), ("lvba_pair_layout_t", L.PairLayout)]
+             ("lvba_fuse_opts", L.FuseOpts), ("lvba_nd_model_t", L.NdModel), ("lvba_pair_layout_t", L.PairLayout),
+             ("lvba_eval_layout_t", L.EvalLayout)]
     src = tmp_path / "sizes.c"
     src.write_text('#include <stdio.h>\n#include "lvba_hip.h"\nint main(void){' +
                    "".join(f'printf("%zu\\n", sizeof({n}));' for n, _ in pairs) + "return 0;}\n")
@@ -66,6 +67,24 @@ def test_pair_layout_entry_points(lib, pkg):
     assert [f for f, _ in pkg._lib.PairLayout._fields_] == ["form", "cut", "n_items", "n_multi", "n_partial", "window_voxels",
                                                             "longest_item", "longest_multi"]
     assert hasattr(pkg.BalmProblem, "pair_layout") and hasattr(pkg.VisualProblem, "pair_layout")
+
+
+def test_eval_layout_entry_points(lib, pkg):
+    """lvba_balm_eval_layout / lvba_visual_eval_layout: exported, declared with one signature, mirrored field for field by the
+    package, and they refuse NULL arguments before anything touches a device."""
+    hdr = open(os.path.join(ROOT, "include", "lvba_hip.h")).read()
+    for name, handle in (("lvba_balm_eval_layout", "lvba_balm_t"), ("lvba_visual_eval_layout", "lvba_visual_t")):
+        assert name in pkg._lib.SYMBOLS and hasattr(lib, name)
+        assert re.search(name + r"\(" + handle + r" h, lvba_eval_layout_t \*out\);", hdr)
+        out = pkg._lib.EvalLayout()
+        assert getattr(lib, name)(None, ctypes.byref(out)) == pkg._lib.ERR_ARG
+    struct = re.search(r"typedef struct \{([^}]*)\} lvba_eval_layout_t;", hdr).group(1)
+    declared = re.findall(r"^\s*int(?:32|64)_t (\w+);", struct, re.M)
+    assert [f for f, _ in pkg._lib.EvalLayout._fields_] == declared == [
+        "slices", "unit_form", "units", "unit_grid", "point_groups", "back_groups", "point_grid", "back_grid", "n_groups",
+        "n_factors", "n_chunks"]
+    assert ctypes.sizeof(pkg._lib.EvalLayout) == 72
+    assert hasattr(pkg.BalmProblem, "eval_layout") and hasattr(pkg.VisualProblem, "eval_layout")
 
 
 def test_shard_range_matches_reference_slicing(pkg):
