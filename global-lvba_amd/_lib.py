@@ -29,6 +29,7 @@ SYMBOLS = [
     "lvba_colorize_default_opts", "lvba_colorize_create", "lvba_colorize_add_images", "lvba_colorize_count",
     "lvba_colorize_download", "lvba_colorize_profile", "lvba_colorize_destroy",
     "lvba_mapq_default_opts", "lvba_mapq_scans", "lvba_mapq_points",
+    "lvba_dynamic_default_opts", "lvba_dynamic_labels", "lvba_scans_select",
     "lvba_register_default_opts", "lvba_register_linearize", "lvba_register_scans",
     "lvba_submaps_build", "lvba_submaps_count", "lvba_submaps_find_planes", "lvba_register_linearize_submaps",
     "lvba_register_scans_submaps", "lvba_loop_default_opts", "lvba_loop_candidates",
@@ -201,6 +202,16 @@ class MapqOpts(C.Structure):
 class MapqSummary(C.Structure):
     _fields_ = [("n_points", C.c_int64), ("n_queries", C.c_int64), ("n_valid", C.c_int64), ("mme", C.c_double), ("mpv", C.c_double),
                 ("mean_neighbors", C.c_double), ("ms", C.c_double * 4)]
+
+
+class DynamicOpts(C.Structure):
+    _fields_ = [("n_rows", C.c_int32), ("n_cols", C.c_int32), ("halo", C.c_int32), ("window", C.c_int32), ("min_free", C.c_int32),
+                ("batch_frames", C.c_int32), ("el_min", C.c_double), ("el_max", C.c_double), ("min_range", C.c_double),
+                ("max_range", C.c_double), ("abs_tol", C.c_double), ("rel_tol", C.c_double), ("free_ratio", C.c_double)]
+
+
+class DynamicSummary(C.Structure):
+    _fields_ = [("n_points", C.c_int64), ("n_judged", C.c_int64), ("n_dynamic", C.c_int64), ("ms", C.c_double * 4)]
 
 
 REG_STATUS = {0: "converged", 1: "max_iterations", 2: "too_few_inliers", 3: "degenerate"}
@@ -542,6 +553,11 @@ def load():
                                       C.c_void_p]
     lib.lvba_sift_candidates.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(SiftOpts), C.c_int64, C.c_void_p,
                                          C.c_void_p, C.POINTER(C.c_int64)]
+    lib.lvba_dynamic_default_opts.argtypes = [C.POINTER(DynamicOpts)]
+    lib.lvba_dynamic_default_opts.restype = None
+    lib.lvba_dynamic_labels.argtypes = [C.c_void_p, f64p, C.c_int32, C.c_int32, C.POINTER(DynamicOpts), C.POINTER(DynamicSummary),
+                                        C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.lvba_scans_select.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(H)]
     lib.lvba_scans_info.argtypes = [H, C.POINTER(C.c_int32), C.c_void_p]
     lib.lvba_scans_download.argtypes = [H, C.c_int32, np.ctypeslib.ndpointer(np.float32, flags="C")]
     for name in SYMBOLS:

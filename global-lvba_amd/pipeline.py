@@ -372,6 +372,18 @@ def map_quality(scans, after, before=None, **kw):
             "before": None if before is None else map_quality_scans(scans, before, **kw)}
 
 
+def remove_dynamic(scans, poses, **opts):
+    """The scans without their moving objects: the points that other frames saw through at `poses` [n,12] are labelled
+    (dynamic.dynamic_labels, opts its options) and dropped.  Returns (static Scans -- the caller closes it --, report): the report
+    holds the summary (n_points, n_judged, n_dynamic, ms), per_frame = the dynamic points of every frame, and label, n_free,
+    n_support per point in cloud order."""
+    from .dynamic import dynamic_labels, static_scans
+    report = dynamic_labels(scans, poses, **opts)
+    frame = np.repeat(np.arange(scans.n_frames), np.asarray(scans.counts, np.int64))
+    report["per_frame"] = np.bincount(frame[report["label"] != 0], minlength=scans.n_frames).astype(np.int64)
+    return static_scans(scans, report["label"]), report
+
+
 def registration_prior(i, j, pose_i, pose_j, information, rmse, status, sigma=None):
     """The balm.Prior.relative(i, j) a registration of frame j gives against reference frame i (loop_closure_prior has the
     derivation): measurement T_i^-1 T_j(registered), sqrt_info the upper Cholesky factor of M H M^T / sigma^2 with
@@ -590,6 +602,7 @@ def _relax_over(poses, closures, relax, device=0):
 
 
 _map_quality = map_quality   # run_full_pipeline / run_dataset have a keyword of that name
+_remove_dynamic = remove_dynamic
 
 
 def _lidar_cfg(cfg):
@@ -715,7 +728,8 @@ def select_image_pairs(depth, Rcw, tcw, intr, sequential=0, **opts):
 def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, tci, intr, width, height, keypoints, pairs,
                       matches, enable_lidar_ba=True, enable_visual_ba=True, device=0, images=None, lidar_priors=None,
                       window_loss=None, stage_loss=None, camera_priors=None, map_quality=False, loop_closures=None, relax=None,
-                      match_fn=None, match_depth=False, match_select=None, device_tracks=False, verify_matches=None, **cfg):
+                      match_fn=None, match_depth=False, match_select=None, device_tracks=False, verify_matches=None,
+                      remove_dynamic=None, **cfg):
     """LvbaSystem::runFullPipeline (src/lvba_system.cpp:136-142) on in-memory data: clouds = body-frame [n_i, >=3] float32
     arrays, poses [n,12] = x_buf_ (T_world<-imu), image_poses [m,12] the image poses from the odometry.  cfg: DEFAULTS' keys
     (visual_loss, colorize_leaf among them).  images: None, or the images ([m,H,W,3] BGR uint8 or a callable k -> [H,W,3]):
@@ -748,7 +762,12 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
     pair that fails keeps its place with no matches).  Here the method defaults to 1, the rotation-aided one: the rotations are
     those of camera_from_imu of the camera poses in force at that point (the LiDAR-derived ones), and the scenes a LiDAR sees are
     mostly walls and floors, where the pose-free eight-point method (method=0, which uses no pose at all) is degenerate.  The output holds pairs / matches as used and match_verification: per pair
-    the status and the counts, plus the totals."""
+    the status and the counts, plus the totals.
+    remove_dynamic: None (off: nothing is launched), True, or a dict of dynamic.dynamic_labels' options: after the LiDAR stage the
+    points that other frames saw through at the refined poses -- whatever moved while the data was recorded -- are labelled
+    (pipeline.remove_dynamic) and the coloured maps and the map quality are made from the static scans, `before` as well as `after`,
+    so that the two compare the same points; the output holds dynamic = the report.  The LiDAR stage, the depth images and the
+    visual stage keep using the full scans."""
     if verify_matches and not enable_visual_ba:
         raise ValueError("verify_matches verifies the matches of the visual stage (enable_visual_ba=True)")
     if images is not None and not enable_visual_ba:
@@ -805,16 +824,29 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
         finally:
             if depth is not None:
                 depth.close()
-        if images is not None:
-            v = out["visual"]
-            col = colorize_maps(scans, image_times, images, intr, width, height, after=(out["poses"], v["Rcw"], v["tcw"]),
-                                before=(x_orig, v["Rcw_before"], v["tcw_before"]), scan_times=scan_times,
-                                half_window_s=c["colorize_half_window_s"], leaf_size=c["colorize_leaf"])
-            out["colored_after"], out["colored_before"] = col["after"], col["before"]
-        if map_quality:
-            kw = dict(map_quality) if isinstance(map_quality, dict) else {}
-            out["map_quality"] = _map_quality(scans, out["poses"], x_orig, **kw)
+        static = None
+        if remove_dynamic:
+            static, out["dynamic"] = _remove_dynamic(scans, out["poses"], **(dict(remove_dynamic) if isinstance(remove_dynamic, dict) else {}))
+        try:
+            _map_products(static if static is not None else scans, out, x_orig, scan_times, image_times, images, intr, width, height,
+                          map_quality, c)
+        finally:
+            if static is not None:
+                static.close()
     return out
+
+
+def _map_products(scans, out, x_orig, scan_times, image_times, images, intr, width, height, map_quality, c):
+    """run_full_pipeline's products made from every point of `scans`: the coloured maps and the map quality"""
+    if images is not None:
+        v = out["visual"]
+        col = colorize_maps(scans, image_times, images, intr, width, height, after=(out["poses"], v["Rcw"], v["tcw"]),
+                            before=(x_orig, v["Rcw_before"], v["tcw_before"]), scan_times=scan_times,
+                            half_window_s=c["colorize_half_window_s"], leaf_size=c["colorize_leaf"])
+        out["colored_after"], out["colored_before"] = col["after"], col["before"]
+    if map_quality:
+        kw = dict(map_quality) if isinstance(map_quality, dict) else {}
+        out["map_quality"] = _map_quality(scans, out["poses"], x_orig, **kw)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -850,7 +882,7 @@ def extrinsics_from_config(Rcl, Pcl, extrinsic_R, extrinsic_T):
 def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrinsic_R=np.eye(3), extrinsic_T=np.zeros(3),
                 image_sample_step=1, out_dir=None, device=0, colorize=False, map_quality=False, loop_closures=None, relax=None,
                 matching="db", match_opts=None, pair_selection=None, device_tracks=False, verify=None, features="db",
-                feature_opts=None, **cfg):
+                feature_opts=None, remove_dynamic=None, **cfg):
     """initFromDatasetIO + runFullPipeline on a dataset directory; with out_dir, the refined LiDAR poses (TUM) and the COLMAP
     text files images.txt / points3D.txt the reference writes (src/lvba_system.cpp:2018-2137) are saved there.  images.txt is
     the reference's, character for character (tests/test_ref_system.py).
@@ -886,6 +918,8 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
     (extract_image_features, feature_opts its options) -- the reference's path without a database
     (extractAndMatchFeaturesGPU, src/lvba_system.cpp:687-778); the database file is not opened.  Then `matching` must be
     "descriptors", "guided" or "depth": the database's matches index the database's key points.
+    remove_dynamic (True or a dict of options, as for run_full_pipeline): the coloured maps and the map quality are made without
+    the points of moving objects; the output gains dynamic and out_dir gets dynamic.json, the summary and the per-frame counts.
     cfg as for run_full_pipeline, e.g. visual_loss=REFERENCE_HUBER, window_loss=("cauchy", 0.1), stage_loss=("huber", 0.05),
     camera_priors=lambda cams: lidar_camera_priors(cams, Rci, tci, 1e-3, 0.02)."""
     import os
@@ -942,7 +976,8 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
                             images=(lambda k: D.read_image_bgr(os.path.join(img_dir, names[k]), width, height))
                             if colorize else None, **({"map_quality": map_quality} if map_quality else {}),
                             **({"loop_closures": loop_closures} if loop_closures else {}),
-                            **({"relax": relax} if relax and loop_closures else {}), **cfg)
+                            **({"relax": relax} if relax and loop_closures else {}),
+                            **({"remove_dynamic": remove_dynamic} if remove_dynamic else {}), **cfg)
     out.update(image_ids=image_ids, scan_times=ds["timestamps"])
     if out_dir is not None:
         os.makedirs(out_dir, exist_ok=True)
@@ -962,6 +997,11 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
             with open(os.path.join(out_dir, "map_quality.json"), "w") as f:
                 json.dump({k: None if q is None else {a: b for a, b in q.items() if not isinstance(b, np.ndarray)}
                            for k, q in out["map_quality"].items()}, f, indent=1)
+        if "dynamic" in out:
+            import json
+            with open(os.path.join(out_dir, "dynamic.json"), "w") as f:
+                json.dump({a: b.tolist() if a == "per_frame" else b for a, b in out["dynamic"].items()
+                           if a == "per_frame" or not isinstance(b, np.ndarray)}, f, indent=1)
         if loop_closures:
             import json
             with open(os.path.join(out_dir, "loop_closures.json"), "w") as f:

@@ -1452,6 +1452,66 @@ int32_t lvba_sift_pyramid(int32_t device, int32_t width, int32_t height, int32_t
 int32_t lvba_sift_candidates(int32_t device, int32_t width, int32_t height, int32_t channels, const uint8_t *image,
                              const lvba_sift_opts *o, int64_t capacity, float *xys, int32_t *where, int64_t *count);
 
+/* ---- Moving objects in the LiDAR map, by range-image visibility ------------------------------------------
+ *   Every scan is a record of free space along its rays.  A point of frame f is not part of the static scene when some other
+ *   frames measured a clearly longer range in the point's direction and in all neighbouring directions: they saw through it.
+ *   This is the visibility test of Removert (Kim & Kim, IROS 2020), stated here as this library's own rule.  Everything is fp64 on
+ *   the fp32 points promoted once, every expression rounded as written (no fused multiply-add).
+ *   Frames [frame_begin, frame_begin + n_frames) of scans at scan_poses [n_frames][12] (R row-major | t, T_world<-body, relative
+ *   to frame_begin as for the map quality); P = their number of points, in cloud order (frames in order, points in scan order).
+ *   Cell of a body-frame point (x, y, z) in a range image of n_rows x n_cols:
+ *     rho = sqrt(x x + y y),  r = sqrt((x x + y y) + z z);  no cell unless r is finite, min_range <= r < max_range and rho > 0;
+ *     col = (int)floor((atan2(y, x) + pi) n_cols / (2 pi)), at most n_cols - 1;
+ *     e = atan2(z, rho);  no cell unless el_min <= e < el_max;
+ *     row = (int)floor((e - el_min) n_rows / (el_max - el_min)), at most n_rows - 1.
+ *   Range image of frame g:  I_g[row][col] = the smallest (float)r of the frame's points with that cell, +inf without one.
+ *   Dilated image:  M_g[row][col] = the smallest I_g over rows row - halo .. row + halo (those outside the image skipped) and
+ *     columns col - halo .. col + halo (modulo n_cols).  A neighbouring direction that hits something nearer vetoes a
+ *     see-through: grazing floor and wall points stay static at this angular resolution.
+ *   Votes of point p of frame f:  w = R_f p + t_f (each row summed from left to right, kept in double).  For every frame g != f
+ *     of the range with |g - f| <= window (window <= 0: every frame):  d = w - t_g,
+ *     q_j = (R_g[0][j] d_0 + R_g[1][j] d_1) + R_g[2][j] d_2;  the cell of q and r_q by the rule above -- no cell, no evidence;
+ *     m = M_g[cell] -- +inf, no evidence;  tol = abs_tol + rel_tol r_q;
+ *     (double)m > r_q + tol: a FREE vote (g saw through the point);  else (double)m >= r_q - tol: a SUPPORT vote;  else the
+ *     point is occluded in g: no evidence.  A non-finite point has no cell in its own image and collects no votes.
+ *   Label:  1 (dynamic) iff n_free >= min_free and (double)n_free >= free_ratio (double)(n_free + n_support);  else 0.
+ *   The defaults below are this library's choice; they are NOT tuned on real data.
+ *   Outputs, each may be NULL: label [P] uint8, n_free [P], n_support [P].  Summary: n_judged = the points with at least one vote;
+ *   ms = device time of the images, the dilation, the votes (with the labels), and the host's time of the download.
+ *   The images of batch_frames frames are on the device at a time (0: as many as the free memory holds); votes are integer
+ *   counts, so the outputs do not depend on the batching, and two calls give the same bytes.  No floating-point atomics.
+ *   Options: NULL takes the defaults.
+ *   LVBA_ERR_ARG: a null scans, scan_poses or summary pointer; a frame range outside the scans or n_frames < 1; a non-finite pose;
+ *   n_rows outside 1 .. 1024, n_cols outside 1 .. 4096, halo outside 0 .. 3; el_min >= el_max or either outside [-pi/2, pi/2];
+ *   min_range not in [0, max_range); a negative or non-finite tolerance; min_free < 1; free_ratio outside (0, 1];
+ *   batch_frames < 0.  LVBA_ERR_NOMEM: the per-point counters and the images of one frame (or of batch_frames > 0 frames) do not
+ *   fit into the free device memory.
+ *   lvba_scans_select: a new scan set on the same device with the same number of frames, each frame keeping its points with
+ *   keep != 0 in scan order (keep: host memory, one byte per point of the WHOLE set in cloud order; a frame may come out empty;
+ *   the compaction runs on the device).  The result is a scan set like any other and is destroyed like any other.
+ *   LVBA_ERR_ARG: a null scans or out pointer, a null mask for a set with points, 2^32 - 1 points or more.
+ *   lvba_version() is unchanged; a client detects these calls by looking lvba_dynamic_labels up. */
+typedef struct lvba_dynamic_opts {
+    int32_t n_rows, n_cols;      /* the range image: 240 x 720 (0.5 degrees a cell) */
+    int32_t halo;                /* 0 .. 3 (default 1) */
+    int32_t window;              /* frames on either side that vote (default 20; <= 0: all) */
+    int32_t min_free;            /* >= 1 (default 3) */
+    int32_t batch_frames;        /* >= 0 (default 0: from the free memory) */
+    double el_min, el_max;       /* elevation range in radians (default -pi/3, +pi/3) */
+    double min_range, max_range; /* metres (default 0.5, 80) */
+    double abs_tol, rel_tol;     /* tol = abs_tol + rel_tol r (default 0.2 m, 0.02) */
+    double free_ratio;           /* in (0, 1] (default 0.5) */
+} lvba_dynamic_opts;             /* 80 bytes */
+typedef struct lvba_dynamic_summary {
+    int64_t n_points, n_judged, n_dynamic;
+    double ms[4];
+} lvba_dynamic_summary;          /* 56 bytes */
+void    lvba_dynamic_default_opts(lvba_dynamic_opts *o);
+int32_t lvba_dynamic_labels(lvba_scans_t scans, const double *scan_poses, int32_t frame_begin, int32_t n_frames,
+                            const lvba_dynamic_opts *o, lvba_dynamic_summary *summary, uint8_t *label, int32_t *n_free,
+                            int32_t *n_support);
+int32_t lvba_scans_select(lvba_scans_t scans, const uint8_t *keep, lvba_scans_t *out);
+
 #ifdef __cplusplus
 }
 #endif
