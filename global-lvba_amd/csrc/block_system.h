@@ -49,7 +49,8 @@ struct BlockSys {
     int64_t hblk_doubles = 0;
     // solver
     LdltMat A{};
-    NdSys nd;                // one level of nested dissection, when that is the solver (nd_plan.h / ldlt_nd.h)
+    LdltRoom room{};         // doubles behind d_A and d_work (ldlt_layout.h)
+    NdSys nd;               // one level of nested dissection, when that is the solver (nd_plan.h / ldlt_nd.h)
     std::vector<void *> nd_allocs;
     // what nd_plan.h was given (kept for lvba_balm_nd_model: "what would n ranks do with this graph"); empty for small systems
     lvba::hvec<uint8_t> adj_keep;

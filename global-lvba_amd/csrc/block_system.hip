@@ -323,24 +323,25 @@ static double bs_now_ms()
 }
 #define BS_MARK(tag) do { if (timing) { const double t_ = bs_now_ms(); fprintf(stderr, "[bs_build] %-12s %.3f ms\n", tag, t_ - tmark); tmark = t_; } } while (0)
 
-// band or dense storage of an n x n system for ldlt_solve (the allocation rules of the whole-system path)
-static int32_t nd_alloc_mat(BlockSys &bs, int64_t n, int64_t bw, LdltMat &A, double **d_A, double **work, bool no_twist)
+// band or dense store of an n x n system for ldlt_solve and its workspace, sized by ldlt_layout.h; room: what was allocated
+static int32_t ldlt_alloc(BlockSys &bs, int64_t n, int64_t bw, bool band, LdltMat &A, double **d_A, double **work, LdltRoom &room)
+{
+    const LdltGeom g = ldlt_geometry(n, bw, band);
+    A.n = n; A.ld = g.ld; A.bw = g.bw;
+    room.store = ldlt_store_doubles(n, g.ld);
+    room.work = ldlt_workspace_doubles(n, g.bw);
+    TRY(bs_dmalloc(bs, d_A, room.store));
+    // a band store is zeroed ONCE: every solve rewrites the columns its two matrices use (ldlt_prepare_band_kernel); the rest must read as zero
+    if (band) HIPCHK(hipMemsetAsync(*d_A, 0, (size_t)room.store * sizeof(double), bs.stream));
+    A.a = *d_A;
+    TRY(bs_dmalloc(bs, work, room.work));
+    return LVBA_OK;
+}
+static int32_t nd_alloc_mat(BlockSys &bs, int64_t n, int64_t bw, LdltMat &A, double **d_A, double **work, LdltRoom &room, bool no_twist)
 {
     A = LdltMat{};
-    A.n = n;
     A.no_twist = no_twist ? 1 : 0;
-    if ((double)(bw + LVBA_NB + 64) < bs.band_frac * (double)n) {
-        const int64_t ldab = bw + LVBA_NB + 64;
-        A.ld = ldab - 1; A.bw = bw;
-        const int64_t cnt = 2 * (ldab * (n + 1)) + 65 * ldab;
-        TRY(bs_dmalloc(bs, d_A, cnt));
-        HIPCHK(hipMemsetAsync(*d_A, 0, (size_t)cnt * sizeof(double), bs.stream)); // zeroed ONCE (ldlt_prepare_band_kernel)
-    } else {
-        A.ld = n; A.bw = n - 1;
-        TRY(bs_dmalloc(bs, d_A, n * n + 64 * n + 128));
-    }
-    A.a = *d_A;
-    TRY(bs_dmalloc(bs, work, ldlt_workspace_doubles(n, A.bw)));
+    TRY(ldlt_alloc(bs, n, bw, ldlt_use_band(n, bw, bs.band_frac), A, d_A, work, room));
     bs.nd_allocs.push_back(*d_A);
     bs.nd_allocs.push_back(*work);
     return LVBA_OK;
@@ -371,7 +372,7 @@ static int32_t nd_alloc(BlockSys &bs, const NdPlan &pl)
         A.status = stat + a;
         if (bs.distributed() && bs.n_ranks >= 2 && A.owner != bs.rank) continue; // another rank's arc: only its ranges are needed here
         if (!(bs.distributed() && bs.n_ranks >= 2)) A.owner = 0;
-        TRY(nd_alloc_mat(bs, A.n, 6 * (int64_t)pa.Bb + 5, A.A, &A.d_A, &A.work, true));
+        TRY(nd_alloc_mat(bs, A.n, 6 * (int64_t)pa.Bb + 5, A.A, &A.d_A, &A.work, A.room, true));
         if (A.nsep > 0) {
             TRY(dm(&A.B, A.n * A.ldb)); TRY(dm(&A.Y, A.n * A.ldb)); TRY(dm(&A.Sa, A.ldb * A.ldb));
             TRY(dm(&A.wv, 2 * A.n)); TRY(dm(&A.gpart, ND_GS_SLICES * A.ldb));
@@ -384,7 +385,7 @@ static int32_t nd_alloc(BlockSys &bs, const NdPlan &pl)
         HIPCHK(lvba::StreamCache::get().acquire(&A.stream));
         HIPCHK(hipEventCreateWithFlags(&A.done, hipEventDisableTiming));
     }
-    TRY(nd_alloc_mat(bs, 6 * (int64_t)nd.Ns, 6 * (int64_t)nd.BbS + 5, nd.AS, &nd.d_AS, &nd.workS, false));
+    TRY(nd_alloc_mat(bs, 6 * (int64_t)nd.Ns, 6 * (int64_t)nd.BbS + 5, nd.AS, &nd.d_AS, &nd.workS, nd.roomS, false));
     TRY(dm(&nd.Sblk, (int64_t)nd.Ns * (nd.BbS + 1) * 36 + 6 * (int64_t)nd.Ns + 8));
     TRY(dm(&nd.d_zero, 8));
     HIPCHK(hipMemsetAsync(nd.d_zero, 0, 8 * sizeof(double), bs.stream));
@@ -505,7 +506,7 @@ int32_t bs_build(BlockSys &bs, int32_t N, int64_t G, const int64_t *voff, const 
     }
     BS_MARK("ordering");
     const int64_t bw = 6 * (int64_t)bs.Bb + 5;
-    bs.use_band = !plan.active && (double)(bw + LVBA_NB + 64) < bs.band_frac * (double)n;
+    bs.use_band = !plan.active && ldlt_use_band(n, bw, bs.band_frac);
     if (!bs.use_band) bs.Bb = N - 1; // full lower block triangle
     const int64_t Bb1 = (int64_t)bs.Bb + 1;
     bs.hblk_doubles = (int64_t)N * Bb1 * 36;
@@ -654,20 +655,8 @@ int32_t bs_build(BlockSys &bs, int32_t N, int64_t G, const int64_t *voff, const 
     }
     TRY(bs_dmalloc(bs, &bs.d_status, 4));
     bs.A.n = n;
-    if (plan.active) {
-        TRY(nd_alloc(bs, plan));
-    } else if (bs.use_band) {
-        const int64_t ldab = bw + LVBA_NB + 64;
-        bs.A.ld = ldab - 1; bs.A.bw = bw;
-        TRY(bs_dmalloc(bs, &bs.d_A, 2 * (ldab * (n + 1)) + 65 * ldab)); // room for the second matrix of the twisted factorisation (+ slack: edge tiles read past the window, ldlt.hip)
-        // zero ONCE: every solve rewrites the columns its two matrices use (ldlt_prepare_band_kernel); the rest must read as zero
-        HIPCHK(hipMemsetAsync(bs.d_A, 0, (size_t)(2 * (ldab * (n + 1)) + 65 * ldab) * sizeof(double), bs.stream));
-    } else {
-        bs.A.ld = n; bs.A.bw = n - 1;
-        TRY(bs_dmalloc(bs, &bs.d_A, n * n + 64 * n + 128)); // (+ slack: edge tiles read past the window, ldlt.hip)
-    }
-    bs.A.a = bs.d_A;
-    if (!plan.active) TRY(bs_dmalloc(bs, &bs.d_work, ldlt_workspace_doubles(n, bs.A.bw)));
+    if (plan.active) TRY(nd_alloc(bs, plan));
+    else TRY(ldlt_alloc(bs, n, bw, bs.use_band, bs.A, &bs.d_A, &bs.d_work, bs.room));
     {
         const char *e = getenv("LVBA_BCR");
         if (bs.spd && bs.use_band && bcr_applicable(N, bs.Bb) && !(e && !strcmp(e, "0")))
@@ -692,7 +681,7 @@ static int32_t solve_launches(BlockSys &bs)
     if (bs.d_bcr) { bcr_solve(bs.Hblk(), bs.Bb, bs.N, bs.g(), bs.d_u, bs.d_dx, bs.d_bcr, bs.d_status, bs.stream); return LVBA_OK; }
     // multi-rank: the two ends of the band factorisation on ranks 0 and 1
     LdltDist dd{bs.rank, bs.n_ranks, &bs, dist_sum_cb, dist_max_cb};
-    return ldlt_solve(bs.A, bs.Hblk(), bs.Bb, bs.N, bs.g(), bs.d_u, bs.d_dx, bs.d_work, bs.d_status, bs.stream,
+    return ldlt_solve(bs.A, bs.Hblk(), bs.Bb, bs.N, bs.g(), bs.d_u, bs.d_dx, bs.d_work, bs.room, bs.d_status, bs.stream,
                       bs.distributed() && bs.n_ranks >= 2 ? &dd : nullptr, bs.n_groups > 0 ? bs.d_grp_of_pose : nullptr);
 }
 

@@ -13,6 +13,8 @@
 //   ldlt_lookahead.h  ONE launch per panel: chain role (the next diagonal block), row roles (L21, Z, the next block column),
 //                     bulk tiles of earlier panels' rank-128 updates; which launch carries what: ldlt_schedule.h (host)
 //   ldlt_back.h       the backward substitution as one chained launch
+//   ldlt_layout.h     sizes and offsets of the store and the workspace, and how far the tile loads reach (host-only; checked on the
+//                     CPU by tests/ldlt_layout_check.cpp)
 //   ldlt_nd.h         graphs that are not a narrow band: one level of nested dissection over arcs solved by this very file
 //   this file         the launch sequence of one solve (captured once into a hipGraph by block_system.hip)
 //
@@ -29,7 +31,9 @@
 #include <vector>
 #include <thread>
 #include "lvba_internal.h"
+#include "lvba_common.h" // lvba_fail
 #include "ldlt_schedule.h"
+#include "ldlt_layout.h"
 #include "wave_ops.h"
 #include "../../include/lvba_hip.h" // status codes
 
@@ -46,22 +50,8 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 #include "ldlt_selinv.h"
 
 // ------------------------------------------------------------------------------------------- driver
-static inline int64_t ldz_for(int64_t n, int64_t bw)
-{
-    int64_t w = bw + LVBA_NB + 64;
-    return w < n ? w : n;
-}
-
-static inline int64_t ldlt_ws_one(int64_t n, int64_t bw)
-{
-    const int64_t nsteps = (n + LVBA_NB - 1) / LVBA_NB;
-    return nsteps * 4096 /*G*/ + 3 * n /*d, b, bacc*/ + 4 * ldz_for(n, bw) * LVBA_NB /*Z, four buffers (st % 4)*/ + 64 +
-           2 * 4096 /*side copies of A(p+1, p), look-ahead schedule*/ + 2 * 4096 /*panel q's share of the next diagonal block, ditto*/;
-}
-// two problems' workspaces + matrix 2's solution vector (twisted factorisation)
-// + the exchange buffer of the multi-rank form: |S| <= bw + 2 * 64 columns of bw + 1 entries, and the S part of the rhs
-static inline int64_t ldlt_exchange_doubles(int64_t n, int64_t bw) { return std::min<int64_t>(n, bw + 2 * LVBA_NB) * (bw + 2) + 64; }
-int64_t ldlt_workspace_doubles(int64_t n, int64_t bw) { return 2 * ldlt_ws_one(n, bw) + n + 64 + ldlt_exchange_doubles(n, bw) + 8 /* LVBA_CHECK_BAND's counter */; }
+static_assert(LDLT_NB == LVBA_NB && LDLT_TILE == LVBA_NB * LVBA_NB, "ldlt_layout.h states the panel width on its own");
+int64_t ldlt_workspace_doubles(int64_t n, int64_t bw) { return ldlt_work_layout(n, bw).total; } // (the layout: ldlt_layout.h)
 
 int64_t ldlt_num_panels(int64_t n) { return (n + LVBA_NB - 1) / LVBA_NB; }
 
@@ -87,28 +77,29 @@ int64_t ldlt_twist_panels(int64_t n, int64_t ld, int64_t bw)
 // rank 0 back-substitutes T and rank 1 B, and the solution is all-reduced.  Per rank the end phase is as long as the
 // single-GPU one but moves one window per launch instead of two; what is replicated is the S phase only.
 int32_t ldlt_solve(const LdltMat &A, const double *Hblk, int band_blocks, int n_poses, const double *g,
-                   const double *u_dev, double *x, double *work, int *status, hipStream_t s, const LdltDist *dist, const int32_t *grp,
+                   const double *u_dev, double *x, double *work, const LdltRoom &room, int *status, hipStream_t s, const LdltDist *dist, const int32_t *grp,
                    int phase, const LdltBorder *border, int64_t anchor_col)
 {
     const int64_t n = A.n, bw = A.bw;
     const int64_t P1 = twist_panels_of(A);
     if (phase != LDLT_ALL && (P1 > 0 || dist)) return LVBA_ERR_STATE; // the halves exist for plain single-rank factorisations
     if (anchor_col >= 0 && P1 > 0) return LVBA_ERR_STATE;
+    if (const char *why = ldlt_solve_fit(n, A.ld, bw, P1, room)) // (ldlt_layout.h: the tile loads are unconditional)
+        return lvba_fail(LVBA_ERR_STATE, "ldlt_solve (n %lld, ld %lld, bw %lld; store %lld, workspace %lld doubles): %s", (long long)n,
+                         (long long)A.ld, (long long)bw, (long long)room.store, (long long)room.work, why);
+    const LdltWork W = ldlt_work_layout(n, bw);
     LdltTwist tw;
     tw.m = P1 * LVBA_NB; tw.n1 = n - tw.m;
-    tw.sA = (A.ld + 1) * (n + 1); tw.sW = ldlt_ws_one(n, bw);
-    tw.x2 = reinterpret_cast<unsigned long long *>(work + 2 * tw.sW);
-    double *Ebuf = work + 2 * tw.sW + n + 64;
+    tw.sA = ldlt_mat2_offset(n, A.ld); tw.sW = W.sW;
+    tw.x2 = reinterpret_cast<unsigned long long *>(work + W.x2);
+    double *Ebuf = work + W.E;
     // side: -1 = both ends here (one rank); 0 / 1 = this rank eliminates T / B; 2 = neither (it only takes part in the exchanges)
     const int side = (dist && dist->n_ranks >= 2 && P1 > 0) ? (dist->rank < 2 ? dist->rank : 2) : -1;
     const int64_t nf = tw.n1; // columns the top-down problem factorises (all of them without the twist)
     const int64_t nsteps = (nf + LVBA_NB - 1) / LVBA_NB;
-    double *Gall = work;
-    double *dvec = Gall + ((n + LVBA_NB - 1) / LVBA_NB) * 4096;
-    double *b = dvec + n;
-    double *bacc = b + n;
-    const int64_t ldz = ldz_for(n, bw);
-    double *Zbuf[4] = {bacc + n, bacc + n + ldz * LVBA_NB, bacc + n + 2 * ldz * LVBA_NB, bacc + n + 3 * ldz * LVBA_NB};
+    double *Gall = work + W.G, *dvec = work + W.d, *b = work + W.b;
+    const int64_t ldz = W.ldz;
+    double *Zbuf[4] = {work + W.Z[0], work + W.Z[1], work + W.Z[2], work + W.Z[3]};
     LdltMat M = A; // the problem the launches see: matrix 1 (and matrix 2 through the block index)
     M.n = nf;
     const size_t abytes = (size_t)((A.ld == n) ? n * n : (A.ld + 1) * n) * sizeof(double);
@@ -121,11 +112,11 @@ int32_t ldlt_solve(const LdltMat &A, const double *Hblk, int band_blocks, int n_
     if (phase != LDLT_BACKWARD) { // ---- fill, factorisation, forward substitution
     if (fill) {
         static const bool check_band = [] { const char *e = getenv("LVBA_CHECK_BAND"); return e && !strcmp(e, "1"); }();
-        const int64_t ldab = A.ld + 1, total = 2 * (ldab * (n + 1)) + 65 * ldab; // = block_system.hip's allocation
+        const int64_t ldab = A.ld + 1, total = room.store;
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         (void)hipStreamIsCapturing(s, &cap);
         if (check_band && cap == hipStreamCaptureStatusNone) {
-            unsigned long long *cnt = reinterpret_cast<unsigned long long *>(work + ldlt_workspace_doubles(n, bw) - 8), hc = 0;
+            unsigned long long *cnt = reinterpret_cast<unsigned long long *>(work + W.counter), hc = 0;
             hipMemsetAsync(cnt, 0, sizeof hc, s);
             hipLaunchKernelGGL(ldlt_check_untouched_kernel, dim3(2048), dim3(256), 0, s, (const double *)A.a, ldab, n, tw.n1, tw.sA, total,
                                P1 > 0 ? 1 : 0, cnt);
@@ -156,8 +147,8 @@ int32_t ldlt_solve(const LdltMat &A, const double *Hblk, int band_blocks, int n_
         q.T = q.w0 < q.rend ? (q.rend - q.w0 + 63) / 64 : 0;
         return q;
     };
-    double *side_buf[2] = {Zbuf[3] + ldz * LVBA_NB + 64, Zbuf[3] + ldz * LVBA_NB + 64 + 4096};
-    double *dq_buf[2] = {side_buf[1] + 4096, side_buf[1] + 2 * 4096};
+    double *side_buf[2] = {work + W.side[0], work + W.side[1]};
+    double *dq_buf[2] = {work + W.dq[0], work + W.dq[1]};
     static const int n_cus = [] {
         int dev = 0, n = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0;
@@ -167,7 +158,7 @@ int32_t ldlt_solve(const LdltMat &A, const double *Hblk, int band_blocks, int n_
     // LVBA_SOLVER=bulk64 forces the 64 x 64 bulk tiles (64-bit pointers) that matrices of 4 GB and more take anyway -- the 128 x 64
     // tiles address one problem's storage with 32-bit byte offsets (buffer instructions) -- so that the tests reach that path at test sizes
     static const bool big_env = !solver_form("bulk64");
-    const bool big = big_env && ((uint64_t)A.ld * (uint64_t)(n + 128) + (uint64_t)n + 256) * 8 < 0xFFFF0000ull;
+    const bool big = big_env && ldlt_offsets_fit_32bit(n, A.ld);
     // Panels [sa, sb) of one problem (or of both, ny = 2).  Consecutive panels are PAIRED (e, o = e + 1): e leaves the bulk of its
     // trailing update to its partner's launches, where every C tile is read and written once for both (rank 128).
     // the border's forward substitution (LdltBorder), two panels behind the roles: stage q = [Y role of panel q - 1, U role of panel
@@ -331,25 +322,24 @@ int32_t ldlt_solve(const LdltMat &A, const double *Hblk, int band_blocks, int n_
 }
 
 // ---- the covariance (lvba_balm_covariance): pivot test, selected inversion, gather (ldlt_selinv.h)
-static inline int64_t selinv_tiles(int64_t n, int64_t bw) { return (std::min(bw, n) + 63) / 64 + 1; }
-int64_t ldlt_selinv_scratch_doubles(int64_t n, int64_t bw)
-{
-    return selinv_tiles(n, bw) * (LVBA_SI_KSMAX + 1) * 4096 + 64;
-}
+int64_t ldlt_selinv_scratch_doubles(int64_t n, int64_t bw) { return ldlt_selinv_scratch(n, bw, LVBA_SI_KSMAX).total; }
 void ldlt_cov_pivot_check(const LdltMat &A, const double *Hblk, int band_blocks, const double *work, int64_t anchor_col, double ratio,
                           const int *status, int *flag, hipStream_t s)
 {
     hipLaunchKernelGGL(ldlt_cov_pivot_kernel, dim3((unsigned)((A.n + 255) / 256)), dim3(256), 0, s, Hblk, band_blocks, A.n,
-                       (const double *)ldlt_work_d(A.n, const_cast<double *>(work)), anchor_col, ratio, status, flag);
+                       ldlt_work_d(A, work), anchor_col, ratio, status, flag);
 }
 // Three launches per panel, last panel to first (each panel reads the Z entries of the panels after it).
-void ldlt_selinv(const LdltMat &A, double *z, const double *work, double *scratch, hipStream_t s)
+int32_t ldlt_selinv(const LdltMat &A, double *z, const double *work, double *scratch, const LdltSelinvRoom &room, hipStream_t s)
 {
-    const int64_t n = A.n, bw = A.bw, nsteps = (n + LVBA_NB - 1) / LVBA_NB, Tm = selinv_tiles(n, bw);
+    const int64_t n = A.n, bw = A.bw, nsteps = (n + LVBA_NB - 1) / LVBA_NB;
+    if (const char *why = ldlt_selinv_fit(n, A.ld, bw, LVBA_SI_KSMAX, room))
+        return lvba_fail(LVBA_ERR_STATE, "ldlt_selinv (n %lld, ld %lld, bw %lld): %s", (long long)n, (long long)A.ld, (long long)bw, why);
+    const LdltSelinvScratch S = ldlt_selinv_scratch(n, bw, LVBA_SI_KSMAX);
     SelinvPanel p{};
     p.z = z; p.a = A.a; p.ld = A.ld; p.n = n;
-    p.xpart = scratch; p.qpart = scratch + Tm * LVBA_SI_KSMAX * 4096;
-    const double *G = ldlt_work_G(const_cast<double *>(work)), *d = ldlt_work_d(n, const_cast<double *>(work));
+    p.xpart = scratch + S.xpart; p.qpart = scratch + S.qpart;
+    const double *G = ldlt_work_G(A, work), *d = ldlt_work_d(A, work);
     for (int64_t st = nsteps - 1; st >= 0; --st) {
         p.k = st * LVBA_NB;
         p.nbe = (int)std::min<int64_t>(LVBA_NB, n - p.k);
@@ -373,6 +363,7 @@ void ldlt_selinv(const LdltMat &A, double *z, const double *work, double *scratc
         p.stage = 2;
         hipLaunchKernelGGL(ldlt_selinv_panel_kernel, dim3(1), dim3(256), 0, s, p);
     }
+    return LVBA_OK;
 }
 void ldlt_cov_gather(const double *z, int64_t ld, int band_blocks, const int32_t *iperm, int N, int anchor, int64_t n_pairs,
                      const int32_t *pi, const int32_t *pj, double *diag, double *blk, uint8_t *avail, hipStream_t s)

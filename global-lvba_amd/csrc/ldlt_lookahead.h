@@ -168,8 +168,8 @@ __device__ __forceinline__ void put_acc(double *T, const d4 (&acc)[4], int w, in
     }
 }
 // tile rows [r0, r0 + 64) x the 64 columns of a panel (column kc + m), rows >= rlim and columns >= nbe read as zero.
-// The loads are UNCONDITIONAL -- what lies past the window or the panel's last column is inside the allocation (block_system.hip
-// leaves the slack; ldlt.hip's workspace likewise) -- and edge tiles are masked afterwards: written as `cond ? load : 0` every one of
+// The loads are UNCONDITIONAL -- what lies past the window or the panel's last column is inside the allocation (ldlt_layout.h states
+// the reach and sizes, tests/ldlt_layout_check.cpp holds them together) -- and edge tiles are masked afterwards: written as `cond ? load : 0` every one of
 // a role's 64 first loads sat behind its own exec-mask branch and 64-bit multiply, and a row workgroup spent 4.8 us REQUESTING them
 // (stamps, round 6: start 0.6 us, last request 5.4 us, data there 5.6 us).
 __device__ __forceinline__ void mask_tile(double (&v)[16], bool whole, bool rok, int nbe, int w)

@@ -244,14 +244,14 @@ int32_t nd_solve(NdSys &nd, const double *Hblk, int32_t N, const double *g, cons
                                nd.ps, A.sep, A.nsep, A.B, A.ldb);
         }
         const int32_t rc = ldlt_solve(A.A, Hblk + (int64_t)A.p0 * Bb1 * 36, (int)(Bb1 - 1), A.Na, g + 6 * (int64_t)A.p0, u_dev,
-                                      x + 6 * (int64_t)A.p0, A.work, A.status, as, nullptr, nullptr, LDLT_FACTOR,
+                                      x + 6 * (int64_t)A.p0, A.work, A.room, A.status, as, nullptr, nullptr, LDLT_FACTOR,
                                       A.nsep > 0 ? &border : nullptr);
         if (rc != LVBA_OK) return bail(rc);
         if (A.nsep > 0) {
-            const double *Gall = ldlt_work_G(A.work), *dvec = ldlt_work_d(A.n, A.work);
+            const double *Gall = ldlt_work_G(A.A, A.work), *dvec = ldlt_work_d(A.A, A.work);
             const unsigned nct = (unsigned)(A.ldb / 64);
             const unsigned np = (unsigned)((A.n + LVBA_NB - 1) / LVBA_NB);
-            hipLaunchKernelGGL(nd_w_kernel, dim3(np), dim3(256), 0, as, Gall, (const double *)ldlt_work_b(A.n, A.work), dvec, A.n, A.wv, A.wv + A.n);
+            hipLaunchKernelGGL(nd_w_kernel, dim3(np), dim3(256), 0, as, Gall, (const double *)ldlt_work_b(A.A, A.work), dvec, A.n, A.wv, A.wv + A.n);
             hipLaunchKernelGGL(nd_gs_kernel, dim3(nct, ND_GS_SLICES), dim3(256), 0, as, (const double *)A.Y, (const double *)A.wv, A.n,
                                A.ldb, A.gpart);
             hipLaunchKernelGGL(nd_schur_kernel, dim3(nct * (nct + 1) / 2), dim3(256), 0, as, (const double *)A.Y, (const double *)(A.wv + A.n), A.n, A.ldb,
@@ -278,7 +278,7 @@ int32_t nd_solve(NdSys &nd, const double *Hblk, int32_t N, const double *g, cons
     if (dist && dist->n_ranks >= 2 && dist->allreduce_sum(dist->ctx, nd.Sblk, (size_t)(sep_doubles + 6 * (int64_t)nd.Ns))) return bail(LVBA_ERR_DIST);
     double *xS = x + 6 * (int64_t)nd.ps;
     {
-        const int32_t rc = ldlt_solve(nd.AS, nd.Sblk, nd.BbS, nd.Ns, nd.Sblk + sep_doubles, nd.d_zero, xS, nd.workS, nd.statusS, s, dist, nullptr,
+        const int32_t rc = ldlt_solve(nd.AS, nd.Sblk, nd.BbS, nd.Ns, nd.Sblk + sep_doubles, nd.d_zero, xS, nd.workS, nd.roomS, nd.statusS, s, dist, nullptr,
                                       LDLT_ALL);
         if (rc != LVBA_OK) return bail(rc);
     }
@@ -295,9 +295,9 @@ int32_t nd_solve(NdSys &nd, const double *Hblk, int32_t N, const double *g, cons
         hipStreamWaitEvent(as, nd.mid, 0);
         if (A.nsep > 0)
             hipLaunchKernelGGL(nd_zstep_kernel, dim3((unsigned)((A.n + 3) / 4)), dim3(256), 0, as, (const double *)A.B, A.n, A.ldb,
-                               (const double *)xS, A.sep, A.nsep, ldlt_work_b(A.n, A.work));
+                               (const double *)xS, A.sep, A.nsep, ldlt_work_b(A.A, A.work));
         const int32_t rc = ldlt_solve(A.A, Hblk + (int64_t)A.p0 * Bb1 * 36, (int)(Bb1 - 1), A.Na, g + 6 * (int64_t)A.p0, u_dev, xa, A.work,
-                                      A.status, as, nullptr, nullptr, LDLT_BACKWARD);
+                                      A.room, A.status, as, nullptr, nullptr, LDLT_BACKWARD);
         if (rc != LVBA_OK) return bail(rc);
         hipEventRecord(A.done, as);
     }

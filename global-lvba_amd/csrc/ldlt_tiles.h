@@ -229,7 +229,7 @@ __device__ __forceinline__ void bulk_tile_128(double *lds, LdltMat M, const Pane
         const unsigned m0 = 32u * (unsigned)(ch & 1);
         const unsigned lsoff = 8u * ((unsigned)r0 + (qk + m0 + w) * ld), zsoff = 8u * (zr + (m0 + 2u * w) * ldz);
         // unconditional: what lies outside the window is masked when it is stored to LDS (the band storage's columns overlap
-        // their neighbours', and block_system.hip leaves slack behind the last one)
+        // their neighbours'; the slack behind the last one: ldlt_layout.h, checked by tests/ldlt_layout_check.cpp)
 #pragma unroll
         for (int it = 0; it < 8; ++it) {
             const double2 v = buf_ld2(rA, lvoff, lsoff + (unsigned)it * (32u * ld));
@@ -312,7 +312,7 @@ __device__ __forceinline__ void bulk_tile_128(double *lds, LdltMat M, const Pane
     // then has the products of two chunks to arrive in.  After the last even chunk, set A takes the C entries instead.
     // (fully unrolled: inside a loop the compiler's wait counts at the back edge drain every load in flight)
     auto load_c = [&]() { // Unmasked: entries outside the window or above the diagonal are read (inside the allocation, see
-                          // block_system.hip) but never stored
+                          // ldlt_layout.h) but never stored
 #pragma unroll
         for (int cq = 0; cq < 4; ++cq)
 #pragma unroll

@@ -756,13 +756,14 @@ extern "C" int32_t lvba_balm_covariance(lvba_balm_t h, const double *poses, cons
     }
     // Z: the second-matrix slot of the band store (unused by a one-ended factorisation); its own buffer for dense storage
     double *z = nullptr;
-    if (band) z = bs.d_A + (A.ld + 1) * (n + 1);
+    const LdltSelinvRoom sroom{bs.room.store, band ? ldlt_store_room(bs.room.store, n, A.ld, true) : ldlt_cov_z_dense_doubles(n), bs.room.work, ns};
+    if (band) z = bs.d_A + ldlt_mat2_offset(n, A.ld);
     else {
-        HIPCHK(zd.alloc((size_t)(n * n + 64) * sizeof(double)));
+        HIPCHK(zd.alloc((size_t)sroom.z * sizeof(double)));
         z = zd.as<double>();
     }
     // the band store must read as zero outside what the damped solve rewrites (block_system.hip): zeroed again on every way out
-    const size_t band_bytes = band ? (size_t)(2 * ((A.ld + 1) * (n + 1)) + 65 * (A.ld + 1)) * sizeof(double) : 0;
+    const size_t band_bytes = band ? (size_t)bs.room.store * sizeof(double) : 0;
     struct BandGuard { double *p; size_t b; hipStream_t s; ~BandGuard() { if (p) (void)hipMemsetAsync(p, 0, b, s); } } bandg{band ? bs.d_A : nullptr, band_bytes, bs.stream};
     mark(0);
     TRY(upload_poses(h, poses, h->d_pose_cur));
@@ -770,7 +771,7 @@ extern "C" int32_t lvba_balm_covariance(lvba_balm_t h, const double *poses, cons
     TRY(enqueue_eval(h, h->d_pose_cur));
     h->have_eval = false; // the solver's workspace now holds the covariance's factor: a later solve needs a fresh evaluation
     mark(1);
-    TRY(ldlt_solve(A, bs.Hblk(), bs.Bb, N, bs.g(), d_zero, bs.d_dx, bs.d_work, bs.d_status, bs.stream, nullptr, nullptr, LDLT_FACTOR,
+    TRY(ldlt_solve(A, bs.Hblk(), bs.Bb, N, bs.g(), d_zero, bs.d_dx, bs.d_work, bs.room, bs.d_status, bs.stream, nullptr, nullptr, LDLT_FACTOR,
                    nullptr, anchor_col));
     ldlt_cov_pivot_check(A, bs.Hblk(), bs.Bb, bs.d_work, anchor_col, o.min_pivot_ratio, bs.d_status, d_flag, bs.stream);
     mark(2);
@@ -782,7 +783,7 @@ extern "C" int32_t lvba_balm_covariance(lvba_balm_t h, const double *poses, cons
     if (*h_flag) return fail(LVBA_NUM_FACTORIZATION, "lvba_balm_covariance: H is not positive definite at these poses (pivot test "
                                                      "failed; no anchor and no priors that fix the frame, or not at a minimum)");
     mark(3);
-    ldlt_selinv(A, z, bs.d_work, d_sc, bs.stream);
+    TRY(ldlt_selinv(A, z, bs.d_work, d_sc, sroom, bs.stream));
     mark(4);
     ldlt_cov_gather(z, A.ld, band ? bs.Bb : -1, d_iperm, N, o.anchor, n_pairs, d_pi, d_pj, d_out, d_out + (int64_t)N * 36, d_av, bs.stream);
     HIPCHK(hipGetLastError());

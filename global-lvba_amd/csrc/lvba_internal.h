@@ -7,6 +7,7 @@
 #include <vector>
 #include "../../include/lvba_hip.h"
 #include "prior_device.h" // PL_*: the layout of a prior's lin record (PriorDev::lin)
+#include "ldlt_layout.h"  // sizes, offsets and reach of the LDL^T's store and workspace
 
 #define LVBA_CF 256   // max factors per chunk == workgroup size of the BALM kernels
 #define LVBA_CV 128   // max voxels per chunk (every voxel has >= 2 factors)
@@ -183,7 +184,8 @@ struct NdArc {
     LdltMat A;          // its band (or dense) matrix, no_twist
     double *d_A;        // (allocation behind A.a)
     double *work;       // ldlt_solve's workspace: G, d, b
-    double *B, *Y;      // [n][ldb] row-major: E_a^T as the forward substitution leaves it / L^-1 E_a^T
+    LdltRoom room;      // doubles behind d_A and work
+    double *B, *Y;     // [n][ldb] row-major: E_a^T as the forward substitution leaves it / L^-1 E_a^T
     double *Sa;         // [ldb][ldb], column j at Sa + j ldb: lower tiles of Y^T D^-1 Y
     double *wv;         // [2][n] G^T b, panel by panel (= D^-1 L^-1 b); 1 / d
     double *gpart;      // [ND_GS_SLICES][ldb] partial sums of Y^T wv
@@ -198,6 +200,7 @@ struct NdSys {
     std::vector<NdArc> arcs;
     LdltMat AS{};                    // the separator system
     double *d_AS = nullptr, *workS = nullptr;
+    LdltRoom roomS{};                // doubles behind them
     double *Sblk = nullptr;          // [Ns (BbS + 1) 36 | 6 Ns]: its block store and gradient (one all-reduce covers both)
     double *d_zero = nullptr;        // a zero on the device: the separator system is damped when it is built
     int *d_stat = nullptr, *statusS = nullptr; // [arcs + 1]
@@ -288,12 +291,12 @@ int64_t ldlt_workspace_doubles(int64_t n, int64_t bw);
 int64_t ldlt_num_panels(int64_t n);
 // panels each end of the two-ended ("twisted") band factorisation eliminates; 0: plain top-down
 int64_t ldlt_twist_panels(int64_t n, int64_t ld, int64_t bw);
-// where ldlt_solve keeps the pieces of a (plain top-down) factorisation in its workspace: G [panels][64 x 64] (G = L11^-T D^-1 of
-// every diagonal block, [m][c] row-major), d [n], and the right-hand side b [n] -- after the forward substitution b holds, panel
-// by panel, the rows as the earlier panels' updates left them (L11^-1 not yet applied: c_k = D_k G_k^T b_k)
-inline double *ldlt_work_G(double *work) { return work; }
-inline double *ldlt_work_d(int64_t n, double *work) { return work + ((n + LVBA_NB - 1) / LVBA_NB) * 4096; }
-inline double *ldlt_work_b(int64_t n, double *work) { return ldlt_work_d(n, work) + n; }
+// where ldlt_solve keeps the pieces of a (plain top-down) factorisation in its workspace (ldlt_layout.h: LdltWork): G [panels][64 x 64]
+// (G = L11^-T D^-1 of every diagonal block, [m][c] row-major), d [n], and the right-hand side b [n] -- after the forward substitution
+// b holds, panel by panel, the rows as the earlier panels' updates left them (L11^-1 not yet applied: c_k = D_k G_k^T b_k)
+template <class D> inline D *ldlt_work_G(const LdltMat &A, D *work) { return work + ldlt_work_layout(A.n, A.bw).G; }
+template <class D> inline D *ldlt_work_d(const LdltMat &A, D *work) { return work + ldlt_work_layout(A.n, A.bw).d; }
+template <class D> inline D *ldlt_work_b(const LdltMat &A, D *work) { return work + ldlt_work_layout(A.n, A.bw).b; }
 enum { LDLT_ALL = 0, LDLT_FACTOR = 1, LDLT_BACKWARD = 2 }; // ldlt_solve's `phase`: everything / fill + factorise + forward / backward only
 // A <- H + u*diag(H) from the block-band store, b <- -g; then unpivoted blocked LDL^T of the lower
 // triangle and the two triangular solves.  x (length n) receives the solution; status[0] != 0 on a
@@ -317,8 +320,10 @@ struct LdltDist {
 struct LdltDist;
 int32_t nd_solve(NdSys &nd, const double *Hblk, int32_t N, const double *g, const double *u_dev, double *x, int *status, hipStream_t s,
                  const LdltDist *dist);
+// room: what A.a's store and `work` were ALLOCATED with, in doubles -- the tile loads of the factorisation are unconditional, so a
+// store or workspace smaller than ldlt_layout.h's reach bounds is refused with LVBA_ERR_STATE before anything is launched
 int32_t ldlt_solve(const LdltMat &A, const double *Hblk, int band_blocks, int n_poses, const double *g,
-                   const double *u_dev, double *x, double *work, int *status, hipStream_t s, const LdltDist *dist = nullptr,
+                   const double *u_dev, double *x, double *work, const LdltRoom &room, int *status, hipStream_t s, const LdltDist *dist = nullptr,
                    const int32_t *grp = nullptr, // grp: pose block -> entry of u_dev (grouped refinement)
                    int phase = LDLT_ALL,         // LDLT_FACTOR / LDLT_BACKWARD: the two halves of a solve (single rank, A.no_twist)
                    const LdltBorder *border = nullptr,
@@ -326,11 +331,12 @@ int32_t ldlt_solve(const LdltMat &A, const double *Hblk, int band_blocks, int n_
                                                   // (lvba_balm_covariance; plain top-down factorisations only)
 // lvba_balm_covariance (ldlt_selinv.h): after ldlt_solve(no_twist A, u = 0, LDLT_FACTOR, anchor_col) -- the pivot test (flag[0] |= 1 on
 // a failure; flag zeroed by the caller), the selected inverse Z of the factor into z (a store of A's shape; scratch of
-// ldlt_selinv_scratch_doubles), and the blocks of the caller's pose pairs from it
+// ldlt_selinv_scratch_doubles; LVBA_ERR_STATE if one of the four buffers is smaller than ldlt_layout.h says), and the blocks of the
+// caller's pose pairs from it
 int64_t ldlt_selinv_scratch_doubles(int64_t n, int64_t bw);
 void ldlt_cov_pivot_check(const LdltMat &A, const double *Hblk, int band_blocks, const double *work, int64_t anchor_col, double ratio,
                           const int *status, int *flag, hipStream_t s);
-void ldlt_selinv(const LdltMat &A, double *z, const double *work, double *scratch, hipStream_t s);
+int32_t ldlt_selinv(const LdltMat &A, double *z, const double *work, double *scratch, const LdltSelinvRoom &room, hipStream_t s);
 void ldlt_cov_gather(const double *z, int64_t ld, int band_blocks, const int32_t *iperm, int N, int anchor, int64_t n_pairs,
                      const int32_t *pi, const int32_t *pj, double *diag, double *blk, uint8_t *avail, hipStream_t s);
 

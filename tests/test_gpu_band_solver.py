@@ -186,6 +186,36 @@ def test_repeated_solves_on_one_handle(rows, oracle_mod):
     _hold("400/27 band u=0.01 (third solve)", A, b, third, x_ref, yard)
 
 
+def _pinned_solver_doubles(n, bw, band):
+    """The LDL^T's store + workspace in doubles as every handle has had them (the literal rules that
+    tests/ldlt_layout_check.cpp pins csrc/ldlt_layout.h to); bw: the half-bandwidth in scalars, band: the storage form."""
+    if band:
+        ldab = bw + NB + 64
+        store = 2 * (ldab * (n + 1)) + 65 * ldab
+    else:
+        store, bw = n * n + 64 * n + 128, n - 1
+    ldz = min(bw + NB + 64, n)
+    one = -(-n // NB) * 4096 + 3 * n + 4 * ldz * NB + 64 + 2 * 4096 + 2 * 4096
+    return store + 2 * one + n + 64 + (min(n, bw + 2 * NB) * (bw + 2) + 64) + 8
+
+
+def test_handle_memory_is_the_pinned_layout(rows):
+    """The smallest row (110/12) in band and in dense storage: the two handles are built from the same problem in the same
+    pose order (n <= 1024: no reordering) and differ in the Hessian store (hess_bytes) and in the solver's store and
+    workspace only, so the difference of their device_bytes must be exactly what the pinned size rules give.  That holds
+    only if every allocation site goes through the layout header and a handle takes the memory it always took."""
+    N, band, _ = ROWS[0]
+    assert (N, band) == min((r[0], r[1]) for r in ROWS)
+    b, d = rows(N, band, "band"), rows(N, band, "dense")
+    n, bw = 6 * N, 6 * (2 * band) + 5
+    assert (b.info["use_band"], b.info["band_blocks"]) == (1, 2 * band) and (d.info["use_band"], d.info["band_blocks"]) == (0, N - 1)
+    assert b.info["hess_bytes"] == 8 * N * (2 * band + 1) * 36 and d.info["hess_bytes"] == 8 * N * N * 36
+    want = b.info["hess_bytes"] - d.info["hess_bytes"] + 8 * (_pinned_solver_doubles(n, bw, True) - _pinned_solver_doubles(n, bw, False))
+    got = b.info["device_bytes"] - d.info["device_bytes"]
+    print(f"band_solver memory {N}/{band}: band {b.info['device_bytes']} dense {d.info['device_bytes']} difference {got} pinned {want}")
+    assert got == want
+
+
 _CHILD = r"""
 import importlib, sys
 import numpy as np

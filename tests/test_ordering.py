@@ -83,6 +83,25 @@ def test_ldlt_lookahead_schedule(tmp_path):
     assert r3.returncode != 0 and "ring slot" in r3.stdout, r3.stdout[-2000:]
 
 
+def test_ldlt_layout_holds_every_tile_reach(tmp_path):
+    """global-lvba_amd/csrc/ldlt_layout.h: the look-ahead LDL^T loads whole tiles unconditionally, so every offset its launch
+    list forms must lie inside the store and workspace the header sizes.  tests/ldlt_layout_check.cpp replays the list
+    (both ends with their close, plain top-down, deferred and full row roles, 64 x 64 and 128 x 64 bulk tiles, forward
+    passengers) for the schedule check's geometries and the smallest shapes at which the reach can go wrong: every offset <=
+    the closed-form bound < the capacity, 32-bit byte offsets where the predicate admits them, the workspace's regions in
+    order, and the sizes every handle has had so far."""
+    exe = str(tmp_path / "ldlt_layout_check")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", os.path.join(ROOT, "tests", "ldlt_layout_check.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0 and "ldlt layout ok" in r.stdout, r.stdout[-3000:]
+    # with the store one ldab (band) / 64 doubles (dense) smaller -- or as small as the tightest geometry's reach, where that
+    # is less -- the same replay must be refused, by the bound-against-capacity check and in both storage forms
+    exe2 = str(tmp_path / "ldlt_layout_check_slack_less")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-DLVBA_LAYOUT_SLACK_LESS", os.path.join(ROOT, "tests", "ldlt_layout_check.cpp"), "-o", exe2])
+    r2 = subprocess.run([exe2], capture_output=True, text=True)
+    assert r2.returncode == 1 and "ld=132 P1=0: reach bound" in r2.stdout and "ld=65 P1=0: reach bound" in r2.stdout, r2.stdout[-2000:]
+
+
 def test_key_repacking_keeps_order_and_round_trips(tmp_path):
     """csrc/key_pack.h: the voxel map's root sort and the anchor down-sampling sort run on keys re-packed onto the bits that
     vary; the re-packed keys must order exactly like the 3 x 21-bit ones and expand back to them (tests/key_pack_check.cpp)."""
