@@ -226,6 +226,13 @@ def test_golden_fixture(pkg):
     np.testing.assert_array_equal(w["anchor_poses"], z["win_anchor_poses"])
     got = w["anchor_scans"].counts.tolist()
     assert all(abs(a - b) <= max(2, 0.002 * b) for a, b in zip(got, z["win_anchor_counts"].tolist()))
+    # the merge itself is exact: the anchor clouds are the replay of the merge from the relative poses the call returned
+    import window_merge_cases as wc
+    replay = wc.replay_anchor_clouds(clouds, w["rel_poses"], w["windows"], 3, 0.05)
+    asc = w["anchor_scans"]
+    assert asc.n_frames == len(replay)
+    for a in range(asc.n_frames):
+        np.testing.assert_array_equal(asc.download(a), replay[a])
     w["anchor_scans"].close()
 
 
@@ -302,10 +309,21 @@ def test_wide_map_sorts_on_64_bit_repacked_keys(pkg, synth):
 
 
 _SORT_SCRIPT = r"""
-import importlib, sys, numpy as np
+import importlib, os, sys, numpy as np
 sys.path.insert(0, sys.argv[1])
 pkg = importlib.import_module("global-lvba_amd")
 synth = importlib.import_module("global-lvba_amd.synth")
+if sys.argv[3] == "j33":                 # merge only, 32 key bits + 1 bit of window code: the joint pass sorts 64-bit keys
+    sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
+    import window_merge_cases as wc
+    case = wc.width_case("J33")
+    with pkg.Scans(case["clouds"]) as scans:
+        w = scans.window_ba(case["poses"], window_size=case["window_size"], anchor_leaf=case["leaf"], merge_only=True)
+        anchors = [w["anchor_scans"].download(k) for k in range(w["anchor_scans"].n_frames)]
+        w["anchor_scans"].close()
+    np.savez(sys.argv[2], n=np.array([len(a) for a in anchors]), pts=np.concatenate(anchors), rel=w["rel_poses"],
+             ai=w["anchor_index"], ap=w["anchor_poses"], skipped=np.array([x["skipped"] for x in w["windows"]]))
+    sys.exit(0)
 s = synth.make_scans(8, 20000, room=(20, 14, 5), origin=(-12.5, 33.1, 1.2), n_panels=8, seed=31)
 clouds = list(s["clouds"])
 if sys.argv[3].startswith("skip"):       # the middle window sees volume noise only: no plane voxels, no anchor
@@ -325,13 +343,15 @@ np.savez(sys.argv[2], off=off, idx=idx, cl=cl, key=key, wp=w["window_poses"], n=
 """
 
 
-@pytest.mark.parametrize("mode", ["plain", "skip", "skip_leaf0"])
+@pytest.mark.parametrize("mode", ["plain", "skip", "skip_leaf0", "j33"])
 def test_joint_window_map_changes_no_byte(tmp_path, mode):
     """LVBA_WINDOW_JOINT_MAP=0 builds one voxel map per window (what a scan set too large for one joint map falls back to); the
     default builds ONE map whose roots are (window, key) and hands the windows views into it, and merges + down-samples the anchor
     clouds of all windows in one pass sorted by (window, leaf key) (window_ba.hip: merge_run over all windows, against one run per
     window).  Same order, same sums either way, on one host thread or several: the map and the whole window stage (refined window
-    poses, anchor clouds point for point) are identical byte for byte."""
+    poses, anchor clouds point for point) are identical byte for byte.
+    j33: tests/window_merge_cases.py's J33 with merge_only -- 32 key bits plus one bit of window code in the joint pass (64-bit
+    sort keys, compressed in place), 32 bits in the per-window pass (32-bit keys): the same bytes, and those of the oracle."""
     import os
     import subprocess
     import sys
@@ -339,15 +359,26 @@ def test_joint_window_map_changes_no_byte(tmp_path, mode):
     script = tmp_path / "run.py"
     script.write_text(_SORT_SCRIPT)
     out = []
-    for i, v in enumerate([{}, {"LVBA_WINDOW_JOINT_MAP": "0"}, {"LVBA_WINDOW_THREADS": "1"},
-                           {"LVBA_WINDOW_JOINT_MAP": "0", "LVBA_WINDOW_THREADS": "1"}]):
+    variants = [{}, {"LVBA_WINDOW_JOINT_MAP": "0"}, {"LVBA_WINDOW_THREADS": "1"}, {"LVBA_WINDOW_JOINT_MAP": "0", "LVBA_WINDOW_THREADS": "1"}]
+    if mode == "j33":     # joint pass against per-window pass (each process start costs seconds; the threads are the other modes' matter)
+        variants = variants[:2]
+    for i, v in enumerate(variants):
         f = tmp_path / f"o_{i}.npz"
         r = subprocess.run([sys.executable, str(script), root, str(f), mode], env=dict(os.environ, **v), capture_output=True, text=True,
                            timeout=600)
         assert r.returncode == 0, (v, r.stderr[-2000:])
         out.append(np.load(f))
-    assert len(out[0]["off"]) > 100 and out[0]["n"].sum() > 1000
-    assert out[0]["skipped"].tolist() == ([0, 1, 0] if mode.startswith("skip") else [0, 0, 0])   # (skipped windows' points sort behind the others')
+    if mode == "j33":
+        import window_merge_cases as wc
+        ap, ac, ai = wc.expected(wc.width_case("J33"))
+        np.testing.assert_array_equal(out[0]["n"], [len(a) for a in ac])
+        np.testing.assert_array_equal(out[0]["pts"], np.concatenate(ac))
+        np.testing.assert_array_equal(out[0]["ap"], ap)
+        np.testing.assert_array_equal(out[0]["ai"], ai)
+        assert out[0]["skipped"].tolist() == [0, 0]
+    else:
+        assert len(out[0]["off"]) > 100 and out[0]["n"].sum() > 1000
+        assert out[0]["skipped"].tolist() == ([0, 1, 0] if mode.startswith("skip") else [0, 0, 0])   # (skipped windows' points sort behind the others')
     for o in out[1:]:
         for k in out[0].files:
             np.testing.assert_array_equal(out[0][k], o[k], err_msg=k)

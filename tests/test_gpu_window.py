@@ -8,7 +8,10 @@ a re-ordered restatement, and anchor clouds as point SETS -- hence the names.
 Per window: voxel counts and skip decisions exact; optimised poses / relative poses to 1e-7 (they inherit the LM parity
 of tests/test_gpu_balm.py); anchor clouds: the fp32 points that survive down_sampling_voxel2.  A relative pose that differs
 by 1e-9 can move a transformed coordinate across an fp32 rounding boundary, so clouds are compared as point sets with a
-1e-5 m tolerance and a 0.2 % budget for flipped survivors."""
+1e-5 m tolerance and a 0.2 % budget for flipped survivors.
+That budget is for the poses alone.  The merge itself is deterministic given the relative poses a call returns, so beside the
+comparison with the oracle every test holds the anchor clouds, point for point and in order, to the replay of the merge from
+the call's own rel_poses (_assert_replay; tests/test_gpu_window_merge.py holds the merge to the oracle itself on exact inputs)."""
 import numpy as np
 import pytest
 
@@ -21,6 +24,19 @@ def _compare_clouds(a, b):
     from scipy.spatial import cKDTree
     d, _ = cKDTree(b).query(a, k=1)
     assert np.mean(d > 1e-5) <= 0.002, float(np.mean(d > 1e-5))
+
+
+def _assert_replay(clouds, got, window_size, leaf, pts=None):
+    """The merge stage is deterministic given the relative poses the call returned (pose_apply_f32 and leaf_key_of are compiled
+    without contraction, tests/window_merge_cases.py restates them): the anchor clouds equal the replay point for point, in
+    order, whatever the LM did to the poses and whichever windows were skipped.  pts: the clouds, if already downloaded."""
+    import window_merge_cases as wc
+    replay = wc.replay_anchor_clouds(clouds, got["rel_poses"], got["windows"], window_size, leaf)
+    if pts is None:
+        pts = [got["anchor_scans"].download(a) for a in range(got["anchor_scans"].n_frames)]
+    assert len(pts) == len(replay) == sum(not w["skipped"] for w in got["windows"])
+    for a, (p, r) in enumerate(zip(pts, replay)):
+        np.testing.assert_array_equal(p, r, err_msg=f"anchor {a}")
 
 
 @pytest.mark.parametrize("use_rel", [True, False])
@@ -47,6 +63,7 @@ def test_window_ba_matches_key_ordered_oracle_clouds_as_point_sets(pkg, synth, u
     assert asc.n_frames == len(ref["anchor_clouds"])
     for a in range(asc.n_frames):
         _compare_clouds(asc.download(a), ref["anchor_clouds"][a])
+    _assert_replay(s["clouds"], got, 4, leaf)
     # the LM did something: the optimised windows moved away from the odometry
     assert np.abs(got["window_poses"] - s["poses"]).max() > 1e-4
     # the anchors feed the global stage directly: a map over the anchor clouds builds and refines
@@ -71,7 +88,38 @@ def test_window_skip_rule_and_identity_rel(pkg, synth):
     np.testing.assert_array_equal(got["rel_poses"][2:], np.tile(I12, (2, 1)))
     np.testing.assert_array_equal(got["window_poses"][2:], s["poses"][2:])
     assert got["anchor_scans"].n_frames == 1
+    _assert_replay(clouds, got, 2, 0.05)
     got["anchor_scans"].close()
+
+
+def test_skipped_window_after_four_merged_takes_the_code_of_a_third_bit(pkg, synth):
+    """20 frames, windows of 4: four windows merge and the last one is skipped.  In the joint pass the skipped window's points
+    get the code G = 4, a power of two, above the codes 0 .. 3 of the merged ones: the window code needs three bits, not the two
+    that G - 1 has (merge_run: cbits).  With a bit too few the code 4 would alias window 0's, and the skipped window's points
+    would sort into its leaves.  Held to the oracle as the neighbouring tests are, and to the replay point for point."""
+    from oracle import window_oracle as wo
+    s = synth.make_scans(20, 6000, room=(10, 8, 4), origin=(2.0, -1.0, 0.4), n_panels=8, seed=45, rot_sigma_deg=0.1,
+                         trans_sigma=0.03)
+    clouds = [c.copy() for c in s["clouds"]]
+    for f in range(16, 20):
+        clouds[f] = clouds[f][:40]                                          # window 4 (frames 16..19) has too few planes: skipped
+    ratio = np.float32([0.3, 0.1, 0.06, 0.03])
+    ref = wo.run_window_ba(clouds, s["poses"], 4, 1.0, ratio, 0.05)
+    with pkg.Scans(clouds) as scans:
+        got = scans.window_ba(s["poses"], window_size=4, voxel_size=1.0, eigen_ratio_array=ratio, anchor_leaf=0.05)
+    asc = got["anchor_scans"]
+    try:
+        assert [w["skipped"] for w in got["windows"]] == [int(w["skipped"]) for w in ref["windows"]] == [0, 0, 0, 0, 1]
+        assert [w["anchor"] for w in got["windows"]] == [0, 1, 2, 3, -1]
+        np.testing.assert_array_equal(got["anchor_index"], ref["anchor_index"])
+        np.testing.assert_array_equal(got["anchor_poses"], ref["anchor_poses"])
+        assert np.abs(got["rel_poses"] - ref["rel_poses"]).max() < 1e-7
+        assert asc.n_frames == len(ref["anchor_clouds"]) == 4
+        for a in range(4):
+            _compare_clouds(asc.download(a), ref["anchor_clouds"][a])
+        _assert_replay(clouds, got, 4, 0.05)
+    finally:
+        asc.close()
 
 
 @pytest.mark.parametrize("window_enable", [True, False])
@@ -128,6 +176,7 @@ def test_window_threads_give_identical_results(pkg, synth, monkeypatch):
     assert len(a[1]) == len(b[1]) == 5
     for p, q in zip(a[1], b[1]):
         np.testing.assert_array_equal(p, q)
+    _assert_replay(clouds, a[0], 4, 0.05, a[1])
 
 
 def test_windows_in_lock_step_equal_one_at_a_time(pkg, synth):
@@ -162,6 +211,8 @@ def test_windows_in_lock_step_equal_one_at_a_time(pkg, synth):
     np.testing.assert_array_equal(a["anchor_poses"], b["anchor_poses"])
     for p, q in zip(pa, pb):
         assert abs(len(p) - len(q)) <= 0.002 * len(q)
+    _assert_replay(clouds, a, 4, 0.05, pa)
+    _assert_replay(clouds, b, 4, 0.05, pb)
 
 
 def test_merge_only_matches_the_anchor_merge_of_the_visual_stage(pkg, synth):
@@ -182,6 +233,7 @@ def test_merge_only_matches_the_anchor_merge_of_the_visual_stage(pkg, synth):
         assert asc.n_frames == len(ac) == 3
         for a in range(3):
             _compare_clouds(asc.download(a), ac[a])
+        _assert_replay(s["clouds"], got, 4, 0.05)
     finally:
         asc.close()
 
@@ -227,6 +279,8 @@ def test_window_stage_over_several_shares_equals_one_device(pkg, synth, devices)
             assert np.abs(got["rel_poses"] - one["rel_poses"]).max() <= 1e-9
             for p, q in zip(pm, p1):
                 assert abs(len(p) - len(q)) <= 0.002 * len(q)
+        _assert_replay(clouds, one, 4, 0.05, p1)
+        _assert_replay(clouds, got, 4, 0.05, pm)
 
 
 def test_lidar_stage_with_the_windows_over_several_shares(pkg, synth):

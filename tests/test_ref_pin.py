@@ -211,6 +211,19 @@ def test_down_sampling_voxel2_and_pl_transform(ref):
         a = got[np.lexsort(got.T[::-1])]
         b = want[np.lexsort(want.T[::-1])]
         assert np.array_equal(a, b)                                         # original points, bit for bit
+    # a merged cloud of lattice points (tests/window_merge_cases.py): hundreds of leaves whose minimum d2 is attained by several
+    # different points, thousands of negative coordinates exactly on a leaf face.  tests/test_gpu_window_merge.py trusts the
+    # oracle on the first-minimum rule and on `loc < 0 -> loc - 1`: here the reference's own function decides both.
+    import window_merge_cases as wc
+    case = wc.lattice_case(0.125)
+    lat = wc.merged_clouds(case["clouds"], wc.exact_rel_poses(case["poses"], 3), None, 3)[0]
+    tied, distinct, on_face = wc.tie_stats(lat, 0.125)
+    assert distinct >= 30 and on_face >= 300
+    for leaf in wc.LATTICE_LEAVES:
+        got = ref.down_sampling_voxel2(lat, leaf)
+        want = lat[wo.down_sampling_voxel2(lat, leaf)]
+        assert len(got) == len(want) < len(lat)
+        assert np.array_equal(got[np.lexsort(got.T[::-1])], want[np.lexsort(want.T[::-1])])
     assert np.array_equal(ref.down_sampling_voxel2(pts, 0.0005), pts)       # leaf < 0.001: untouched (tools.hpp:262)
     pose = np.concatenate([bo.exp_so3([0.1, -0.2, 0.3]).reshape(-1), [1.5, -2.0, 0.25]])
     got = ref.pl_transform(pts[:1000], pose)
