@@ -44,6 +44,7 @@ SYMBOLS = [
     "lvba_verify_score",
     "lvba_sift_default_opts", "lvba_sift_tile_width", "lvba_sift_blur_taps", "lvba_sift_extract", "lvba_sift_profile", "lvba_sift_pyramid",
     "lvba_sift_candidates",
+    "lvba_resect_default_opts", "lvba_resect_images", "lvba_resect_hypotheses", "lvba_resect_score", "lvba_resect_lift",
 ]
 
 OK, ERR_ARG, ERR_DEVICE, ERR_NOMEM, ERR_UNSUPPORTED, ERR_DIST, ERR_STATE = 0, -1, -2, -3, -4, -5, -6
@@ -264,6 +265,12 @@ class MatchOpts(C.Structure):
 class VerifyOpts(C.Structure):
     """lvba_verify_opts"""
     _fields_ = [("method", C.c_int32), ("hypotheses", C.c_int32), ("refine_rounds", C.c_int32), ("min_inliers", C.c_int32),
+                ("max_error_px", C.c_double), ("seed", C.c_uint64)]
+
+
+class ResectOpts(C.Structure):
+    """lvba_resect_opts"""
+    _fields_ = [("hypotheses", C.c_int32), ("refine_rounds", C.c_int32), ("min_inliers", C.c_int32), ("reserved", C.c_int32),
                 ("max_error_px", C.c_double), ("seed", C.c_uint64)]
 
 
@@ -560,6 +567,14 @@ def load():
     lib.lvba_scans_select.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(H)]
     lib.lvba_scans_info.argtypes = [H, C.POINTER(C.c_int32), C.c_void_p]
     lib.lvba_scans_download.argtypes = [H, C.c_int32, np.ctypeslib.ndpointer(np.float32, flags="C")]
+    lib.lvba_resect_default_opts.argtypes = [C.POINTER(ResectOpts)]
+    lib.lvba_resect_default_opts.restype = None
+    lib.lvba_resect_images.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ResectOpts),
+                                       C.c_int64] + [C.c_void_p] * 9
+    lib.lvba_resect_hypotheses.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ResectOpts), C.c_void_p,
+                                           C.c_void_p, C.c_void_p]
+    lib.lvba_resect_score.argtypes = [C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
+    lib.lvba_resect_lift.argtypes = [H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default

@@ -1,4 +1,4 @@
-// image_set.h -- what the image front ends (match.hip, verify.hip, track_graph.hip, covis.hip) share on the host: the resident
+// image_set.h -- what the image front ends (match.hip, verify.hip, track_graph.hip, covis.hip, resect.hip) share on the host: the resident
 // key-point table of a set of images, and the argument checks of their entry points, one wording each; an entry point composes
 // the checks it applies, in its own order.  The undistortion is image_set.hip, built without floating-point contraction; here
 // is integer code, comparisons and copies only, so a translation unit that contracts (track_graph.hip) may include this.

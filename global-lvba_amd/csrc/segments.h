@@ -1,6 +1,6 @@
 // segments.h -- which segment an element belongs to: the image of a key point, the pair of a match row, the voxel of a map point,
 // the component of an observation, the frame of a scan point.  The one search of the front ends over ascending segment offsets
-// (match.hip, verify.hip, fusion.hip, track_graph.hip; scan_points.h and track_graph_device.h forward to it).  Host/device-neutral,
+// (match.hip, verify.hip, resect.hip, fusion.hip, track_graph.hip; scan_points.h and track_graph_device.h forward to it).  Host/device-neutral,
 // integer-only, no HIP includes: also compiled by g++ (tests/segments_check.cpp).  The lower-bound searches for a KEY
 // (voxel_lookup.h, tg_lower_bound, ...) are a different primitive.
 #pragma once

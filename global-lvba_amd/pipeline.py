@@ -704,6 +704,85 @@ def verify_image_pairs(keypoints, pairs, matches, intr, Rcw=None, device=0, **op
     return VF.verify_pairs(keypoints, pairs, matches, intr, Rcw=Rcw, device=device, **opts)
 
 
+def correspondences_from_matches(pairs, matches, points):
+    """The 2-D to 3-D correspondences the matches hold: for every image the (own keypoint, partner's lifted point) of every match
+    whose partner has a point.  points: one [n_i, 3] array per image, NaN rows where a keypoint has no point (Matcher.points,
+    resect.lift_keypoints).  Both directions of a pair are used; the order is the order of `pairs` -- within a pair its first
+    image's side, then its second's -- then match order.  Returns (keypoint, world): per image an int32 [c_i] and a float64
+    [c_i, 3] array."""
+    M = len(points)
+    kp, X = [[] for _ in range(M)], [[] for _ in range(M)]
+    for (a, b), m in zip(pairs, matches):
+        m = np.asarray(m, np.int64).reshape(-1, 2)
+        for own, other, co, cp in ((int(a), int(b), 0, 1), (int(b), int(a), 1, 0)):
+            P = np.asarray(points[other], np.float64).reshape(-1, 3)[m[:, cp]]
+            has = ~np.isnan(P[:, 0])
+            kp[own].append(m[has, co])
+            X[own].append(P[has])
+    return ([np.concatenate(k).astype(np.int32) if k else np.zeros(0, np.int32) for k in kp],
+            [np.concatenate(x).reshape(-1, 3) if x else np.zeros((0, 3)) for x in X])
+
+
+def check_cameras(keypoints, pairs, matches, depth, Rcw, tcw, intr, device=0, **opts):
+    """Where the images say the cameras are (resect.resect_images): every keypoint with a depth return is lifted
+    through its image's depth image (depth: a visual.DepthImages at the poses Rcw, tcw = T_cam<-world), the matches turn the
+    lifted points of an image's partners into its 2-D to 3-D correspondences, and every image is resected from them alone, all
+    in one grid.  Returns the report as plain Python: per image the status, the counts, the rmse and -- for an image that comes
+    back OK -- the rotation angle (degrees) and the distance of the camera centres between the resected and the given pose; the
+    medians of both; and poses = the resected [M, 12] (R row-major, t), zeros where not OK.  opts: resect.resect_opts'."""
+    from . import resect as RS
+    uv = [np.asarray(k, np.float32).reshape(-1, 2) for k in keypoints]
+    points = RS.lift_keypoints(depth, uv, intr, Rcw, tcw)
+    kp, world = correspondences_from_matches(pairs, matches, points)
+    _, report = RS.resect_images([u[k] for u, k in zip(uv, kp)], world, intr, device=device, **opts)
+    out = RS.summary(report, Rcw, tcw)
+    out["poses"] = np.concatenate([report["Rcw"].reshape(-1, 9), report["tcw"]], 1).tolist()
+    return out
+
+
+_check_cameras = check_cameras    # run_full_pipeline's keyword of the same name shadows the function there
+
+
+def localize_images(query_keypoints, query_descriptors, map_keypoints, map_descriptors, map_points, intr, candidates=None, device=0,
+                    match_opts=None, **opts):
+    """Places images that were not part of the run into the map: each query image is matched unguided against its candidate map
+    images (match.Matcher), a match whose map keypoint has a point (map_points: per map image [n_i, 3], NaN rows without one) is a
+    2-D to 3-D correspondence, and every query image is resected from its correspondences (resect.resect_images).  candidates:
+    per query image the map images to match against (None: all).  Returns (Rcw [Q, 3, 3], tcw [Q, 3], report): T_cam<-world of
+    every query image (zeros where the status is not OK), and the report of resect.summary with, under "correspondences", per
+    query image a dict of arrays keypoint, map_image, map_keypoint and inlier."""
+    from . import match as M
+    from . import resect as RS
+    Q, n_map = len(query_descriptors), len(map_descriptors)
+    cand = [list(range(n_map)) if candidates is None else [int(c) for c in candidates[q]] for q in range(Q)]
+    pairs = [(n_map + q, c) for q in range(Q) for c in cand[q]]
+    with M.Matcher(list(map_descriptors) + list(query_descriptors), device=device) as matcher:
+        matches = matcher.match_pairs(pairs, **dict(match_opts or {}, guided=0)) if pairs else []
+    uv, world, corr = [], [], []
+    k = 0
+    for q in range(Q):
+        kq = np.asarray(query_keypoints[q], np.float32).reshape(-1, 2)
+        rows = dict(keypoint=[], map_image=[], map_keypoint=[], world=[])
+        for c in cand[q]:
+            m = np.asarray(matches[k], np.int64).reshape(-1, 2)
+            k += 1
+            P = np.asarray(map_points[c], np.float64).reshape(-1, 3)[m[:, 1]]
+            has = ~np.isnan(P[:, 0])
+            rows["keypoint"].append(m[has, 0]); rows["map_keypoint"].append(m[has, 1]); rows["world"].append(P[has])
+            rows["map_image"].append(np.full(int(has.sum()), c, np.int64))
+        cat = {a: (np.concatenate(b) if b else np.zeros((0, 3) if a == "world" else 0, np.float64 if a == "world" else np.int64))
+               for a, b in rows.items()}
+        uv.append(kq[cat["keypoint"]]); world.append(cat["world"].reshape(-1, 3)); corr.append(cat)
+    inliers, rep = RS.resect_images(uv, world, intr, device=device, **opts)
+    report = RS.summary(rep)
+    for q in range(Q):
+        mask = np.zeros(len(uv[q]), bool)
+        mask[inliers[q]] = True
+        corr[q]["inlier"] = mask
+    report["correspondences"] = corr
+    return rep["Rcw"], rep["tcw"], report
+
+
 def select_image_pairs(depth, Rcw, tcw, intr, sequential=0, **opts):
     """Which image pairs to match (covis.select_pairs) instead of all M (M - 1) / 2: the pairs in which one image
     sees enough of what the other sees, judged on a grid of samples lifted through the LiDAR depth images (a visual.DepthImages
@@ -729,7 +808,7 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
                       matches, enable_lidar_ba=True, enable_visual_ba=True, device=0, images=None, lidar_priors=None,
                       window_loss=None, stage_loss=None, camera_priors=None, map_quality=False, loop_closures=None, relax=None,
                       match_fn=None, match_depth=False, match_select=None, device_tracks=False, verify_matches=None,
-                      remove_dynamic=None, **cfg):
+                      remove_dynamic=None, check_cameras=None, **cfg):
     """LvbaSystem::runFullPipeline (src/lvba_system.cpp:136-142) on in-memory data: clouds = body-frame [n_i, >=3] float32
     arrays, poses [n,12] = x_buf_ (T_world<-imu), image_poses [m,12] the image poses from the odometry.  cfg: DEFAULTS' keys
     (visual_loss, colorize_leaf among them).  images: None, or the images ([m,H,W,3] BGR uint8 or a callable k -> [H,W,3]):
@@ -767,7 +846,12 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
     points that other frames saw through at the refined poses -- whatever moved while the data was recorded -- are labelled
     (pipeline.remove_dynamic) and the coloured maps and the map quality are made from the static scans, `before` as well as `after`,
     so that the two compare the same points; the output holds dynamic = the report.  The LiDAR stage, the depth images and the
-    visual stage keep using the full scans."""
+    visual stage keep using the full scans.
+    check_cameras: None (off: nothing is launched and no entry point of the stage is called), True, or a dict of resect.resect_opts' options: once
+    the matches in force are final -- after the verification where that is on -- every image is resected from the LiDAR points its
+    matches reach (pipeline.check_cameras) at the LiDAR-derived camera poses, through the depth images of match_depth /
+    match_select or images rendered the same way; the output holds camera_check, per image how far the pose the images ask for
+    lies from the one the trajectory and the extrinsic give.  Nothing downstream reads it."""
     if verify_matches and not enable_visual_ba:
         raise ValueError("verify_matches verifies the matches of the visual stage (enable_visual_ba=True)")
     if images is not None and not enable_visual_ba:
@@ -816,6 +900,17 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
                 matches, vrep = verify_image_pairs(keypoints, pairs, matches, intr, Rcw=Rv, device=device, **vo)
                 out["pairs"], out["matches"] = pairs, matches
                 out["match_verification"] = VF.summary(pairs, vrep)
+            if check_cameras:
+                Rk, tk = camera_from_imu(update_camera_poses_from_lidar(out["poses"], x_orig, scan_times, image_times, image_poses), Rci, tci)
+                dk = depth if depth is not None else V.DepthImages.render(scans, out["poses"], scan_times, image_times, Rk, tk, intr, width,
+                                                                          height, half_window_s=c["depth_half_window_s"],
+                                                                          voxel_size=c["depth_voxel"])
+                try:
+                    out["camera_check"] = _check_cameras(keypoints, pairs, matches, dk, Rk, tk, intr, device=device,
+                                                         **(dict(check_cameras) if isinstance(check_cameras, dict) else {}))
+                finally:
+                    if dk is not depth:
+                        dk.close()
             if enable_visual_ba:
                 out["visual"] = run_visual_ba_with_lidar_assist(scans, out["poses"], x_orig, scan_times, image_times, image_poses, Rci,
                                                                 tci, intr, width, height, keypoints, pairs, matches,
@@ -882,7 +977,7 @@ def extrinsics_from_config(Rcl, Pcl, extrinsic_R, extrinsic_T):
 def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrinsic_R=np.eye(3), extrinsic_T=np.zeros(3),
                 image_sample_step=1, out_dir=None, device=0, colorize=False, map_quality=False, loop_closures=None, relax=None,
                 matching="db", match_opts=None, pair_selection=None, device_tracks=False, verify=None, features="db",
-                feature_opts=None, remove_dynamic=None, **cfg):
+                feature_opts=None, remove_dynamic=None, check_cameras=None, **cfg):
     """initFromDatasetIO + runFullPipeline on a dataset directory; with out_dir, the refined LiDAR poses (TUM) and the COLMAP
     text files images.txt / points3D.txt the reference writes (src/lvba_system.cpp:2018-2137) are saved there.  images.txt is
     the reference's, character for character (tests/test_ref_system.py).
@@ -920,6 +1015,8 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
     "descriptors", "guided" or "depth": the database's matches index the database's key points.
     remove_dynamic (True or a dict of options, as for run_full_pipeline): the coloured maps and the map quality are made without
     the points of moving objects; the output gains dynamic and out_dir gets dynamic.json, the summary and the per-frame counts.
+    check_cameras (True or a dict of options, as for run_full_pipeline): every image is resected from the LiDAR points its matches
+    reach; the output gains camera_check and out_dir gets camera_check.json.
     cfg as for run_full_pipeline, e.g. visual_loss=REFERENCE_HUBER, window_loss=("cauchy", 0.1), stage_loss=("huber", 0.05),
     camera_priors=lambda cams: lidar_camera_priors(cams, Rci, tci, 1e-3, 0.02)."""
     import os
@@ -977,7 +1074,8 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
                             if colorize else None, **({"map_quality": map_quality} if map_quality else {}),
                             **({"loop_closures": loop_closures} if loop_closures else {}),
                             **({"relax": relax} if relax and loop_closures else {}),
-                            **({"remove_dynamic": remove_dynamic} if remove_dynamic else {}), **cfg)
+                            **({"remove_dynamic": remove_dynamic} if remove_dynamic else {}),
+                            **({"check_cameras": check_cameras} if check_cameras else {}), **cfg)
     out.update(image_ids=image_ids, scan_times=ds["timestamps"])
     if out_dir is not None:
         os.makedirs(out_dir, exist_ok=True)
@@ -1014,6 +1112,10 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
             import json
             with open(os.path.join(out_dir, "match_verification.json"), "w") as f:
                 json.dump(out["match_verification"], f, indent=1)
+        if "camera_check" in out:
+            import json
+            with open(os.path.join(out_dir, "camera_check.json"), "w") as f:
+                json.dump(out["camera_check"], f, indent=1)
         if "pose_graph" in out:
             import json
             with open(os.path.join(out_dir, "pose_graph.json"), "w") as f:

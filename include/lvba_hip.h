@@ -1512,6 +1512,89 @@ int32_t lvba_dynamic_labels(lvba_scans_t scans, const double *scan_poses, int32_
                             int32_t *n_support);
 int32_t lvba_scans_select(lvba_scans_t scans, const uint8_t *keep, lvba_scans_t *out);
 
+/* ---- camera resectioning from 2-D to 3-D matches: batched P3P RANSAC (opt-in)
+ *   Every camera pose of the pipeline is derived (the LiDAR trajectory interpolated at the image time, times the extrinsic).  A
+ *   matched keypoint whose partner has a LiDAR depth return is a 2-D to 3-D correspondence (lvba_match_set_depth lifts such points,
+ *   lvba_resect_lift does the same for a batch of images without a matcher); three of them give the absolute pose of an image, of
+ *   the run or foreign to it.  The rule below is this project's own definition, restated in numpy in tests/resect_oracle.py; it is
+ *   NOT pinned against COLMAP's absolute-pose estimator.  fp64 throughout, every sum left to right, no contraction.
+ *   Job.  One image: id (int32 >= 0, distinct within a call), m correspondences = rows corr_off[j] .. corr_off[j + 1] of uv [][2]
+ *     (fp32 pixels) and world [][3] (fp64), and the call's intrinsics intr = (fx, fy, cx, cy, k1, k2, p1, p2).  Pixels are
+ *     undistorted once on the device (trk_undistort; (x, y), NaN where it fails).  A correspondence with a NaN (x, y) or a
+ *     non-finite X is UNUSABLE: never an inlier, and a sample that draws it is invalid.
+ *   Inlier test of (R, t) = T_cam<-world.  Xc = R X + t, each row ((r0 X0 + r1 X1) + r2 X2) + t;  a = fx (Xc_x - x Xc_z),
+ *     b = fy (Xc_y - y Xc_z);  inlier iff Xc_z > 1e-12 and a a + b b <= (rho Xc_z)(rho Xc_z), rho = max_error_px; false for any NaN.
+ *     The reprojection error in undistorted pixels, division-free, with the cheirality bound of projectCameraToPixel.
+ *   Sampling.  Hypothesis h draws k = 4 distinct positions with the two-view verification's sampler (above), its key formed with
+ *     lo = id, hi = -1: a function of (seed, id, h, draw) alone, and apart from every image pair's stream (a pair has hi >= 1).
+ *   Minimal solver (resect_p3p of csrc/resect_device.h, whose comment gives every expression in order) on the first three draws.
+ *     Unit bearings f_i = (x_i, y_i, 1) / |.|; the depths s_i satisfy s_i^2 + s_j^2 - 2 s_i s_j (f_i . f_j) = a_ij = |X_i - X_j|^2,
+ *     s^T M_ij s = a_ij.  D1 = a23 M12 - a12 M23 and D2 = a23 M13 - a13 M23 are zero on the solution (Persson and Nordberg, Lambda
+ *     twist, ECCV 2018).  INVALID: |(X1 - X2) x (X1 - X3)|^2 <= 1e-12 a12 a13 (degenerate triangle).  One real root g of the cubic
+ *     det(D1 + g D2), made monic (leading coefficient 0: INVALID), by 16 Newton steps, all taken (a step with a zero derivative is
+ *     left out): with disc = b^2 - 3 c > 0 and the stationary points t1 < t2 = (-b -+ sqrt(disc)) / 3, from t1 - sqrt(p(t1) /
+ *     sqrt(disc)) where p(t1) > 0 and from t2 + sqrt(-p(t2) / sqrt(disc)) otherwise; disc <= 0: from -b / 3.  D0 = D1 + g D2 has
+ *     rank 2: B = -adj(D0), i its largest diagonal entry (lowest of a tie; <= 1e-14 max|D0|^2: INVALID -- no pair of real planes),
+ *     p = B[:, i] / sqrt(B_ii), N = D0 + [p]x has rank 1, and with (r, c) its entry of largest magnitude (row by row, lowest of a
+ *     tie) the planes are row r and column c of N.  Per plane n, with k its largest |n_k|, two vectors u, v of the plane; s = al u
+ *     + be v in D1 is A al^2 + 2 B al be + C be^2 = 0; B^2 - A C < 0: no solution of that plane; q = -(B + sign(B) sqrt(B^2 - A C)),
+ *     (al, be) = (q, A) and (C, q).  Up to four depth triples, number 2 plane + root.  Scale: lam^2 = (a12 + a13 + a23) / (the
+ *     three left sides at s, summed), signed so that s1 > 0.  Three Gauss-Newton steps on (s1, s2, s3) against the three equations.
+ *     A depth that is not finite or not > 0: no solution.  R = Y X^-1 with X = [X1 - X2, X1 - X3, (X1 - X2) x (X1 - X3)] and Y the
+ *     same of s_i f_i (inverse by cofactors), t = s1 f1 - R X1.  +, -, *, / and sqrt only: the same sample gives the same bits
+ *     under g++, numpy and gfx950.  The hypothesis is the solution with the smallest squared undistorted-pixel error (fx (Xc_x /
+ *     Xc_z - x))^2 + (fy (Xc_y / Xc_z - y))^2 on the FOURTH draw, which must lie in front (Xc_z > 1e-12); lowest number of a tie.
+ *     No such solution: the hypothesis is INVALID and counts -1.  Not degenerate on planes.
+ *   Choice.  The highest inlier count wins, the lowest h of a tie; integers only.  hypotheses (default 1024) is fixed, no early
+ *     exit: 1 - (1 - w^4)^H at H = 1024 is 0.9998 at an inlier ratio w = 0.3 and 1 - 2e-29 at w = 0.5.
+ *   Refinement (refine_rounds, default 2, 0 = off).  A round takes 4 Gauss-Newton steps on the six pose parameters over the
+ *     inliers of the round's starting pose: residual (fx (Xc_x / Xc_z - x), fy (Xc_y / Xc_z - y)), left perturbation Xc <- Xc +
+ *     om x Xc + up in the order (om, up), the 6 x 6 normal equations by Cholesky column after column, R <- (I + [om]x) R
+ *     re-orthonormalised through a unit quaternion (sqrt only), t <- t + om x t + up.  Then it rescores; the refit is kept iff its
+ *     count is not smaller than before, and a round that is not kept ends the refinement.  The sums are a tree on the device:
+ *     the refit is held to a measured tolerance, not to the bit.
+ *   Status per job.  LVBA_RESECT_OK; LVBA_RESECT_TOO_FEW_MATCHES: m < max(4, min_inliers) (no hypothesis, pose 0, best_h = -1);
+ *     LVBA_RESECT_NO_MODEL: every hypothesis invalid; LVBA_RESECT_TOO_FEW_INLIERS: count < min_inliers (pose, count and best_h are
+ *     reported).  A job that is not OK keeps its place in every output and contributes no inliers.  min_inliers defaults to 30,
+ *     the bound COLMAP uses to register an image as this project remembers it -- its own rule, not pinned; max_error_px defaults
+ *     to 8, the depth gate's max_reproj_px (the same quantity).
+ *   lvba_resect_images: all jobs of the call in one grid.  Rcw [n_jobs][9], tcw [n_jobs][3], status, n_inliers, best_h [n_jobs],
+ *     rmse_px [n_jobs] over the final inliers, information [n_jobs][36] = sum J^T J at the final pose over the final inliers in
+ *     px^-2 (order (om, up)), inliers [capacity] = positions within the job in (job, original order), inlier_off [n_jobs + 1] with
+ *     the capacity convention of lvba_verify_pairs.
+ *   lvba_resect_hypotheses: the diagnostic call, one job: R [hypotheses][9], t [hypotheses][3], count [hypotheses] of every
+ *     hypothesis before the choice (invalid: zeros and -1).  lvba_resect_score: mask [m] of the inlier test under a given pose.
+ *   lvba_resect_lift: the keypoints uv of the depth set's images (rows kp_off[i] .. kp_off[i + 1] belong to image i) through
+ *     their depth images into world [kp_off[n_images]][3] -- match_lift, as lvba_match_set_depth does it -- NaN rows where a
+ *     keypoint has no point.
+ *   LVBA_ERR_ARG (nothing written): a null required pointer, a negative or repeated id, corr_off that does not start at 0 or
+ *   decreases, non-finite intrinsics or focal lengths <= 0, hypotheses < 1, refine_rounds < 0, min_inliers < 0, max_error_px not
+ *   finite or <= 0, a depth set of another image count, non-finite poses at the lift.  lvba_version() is unchanged; a client
+ *   detects these calls by looking lvba_resect_images up. */
+#define LVBA_RESECT_OK 0
+#define LVBA_RESECT_TOO_FEW_MATCHES 1
+#define LVBA_RESECT_NO_MODEL 2
+#define LVBA_RESECT_TOO_FEW_INLIERS 3
+typedef struct lvba_resect_opts {
+    int32_t hypotheses;    /* 1024 */
+    int32_t refine_rounds; /* 2; 0 = off */
+    int32_t min_inliers;   /* 30 */
+    int32_t reserved;      /* 0 */
+    double max_error_px;   /* 8.0, the depth gate's max_reproj_px */
+    uint64_t seed;         /* 0 */
+} lvba_resect_opts;        /* 32 bytes */
+void    lvba_resect_default_opts(lvba_resect_opts *o);
+int32_t lvba_resect_images(int32_t device, int32_t n_jobs, const int32_t *ids, const int64_t *corr_off, const float *uv,
+                           const double *world, const double *intr, const lvba_resect_opts *o, int64_t capacity, int64_t *inlier_off,
+                           int32_t *inliers, double *Rcw, double *tcw, int32_t *status, int32_t *n_inliers, int32_t *best_h,
+                           double *rmse_px, double *information);
+int32_t lvba_resect_hypotheses(int32_t device, int32_t id, int64_t n_corr, const float *uv, const double *world, const double *intr,
+                               const lvba_resect_opts *o, double *R, double *t, int32_t *count);
+int32_t lvba_resect_score(int32_t device, int64_t n_corr, const float *uv, const double *world, const double *intr, const double *Rcw,
+                          const double *tcw, double max_error_px, uint8_t *mask);
+int32_t lvba_resect_lift(lvba_depth_t depth, int32_t n_images, const int64_t *kp_off, const float *uv, const double *intr,
+                         const double *Rcw, const double *tcw, double *world);
+
 #ifdef __cplusplus
 }
 #endif
