@@ -1,31 +1,18 @@
 // resect.hip -- camera resectioning: P3P RANSAC over the 2-D to 3-D correspondences of many images at once (lvba_resect_*; the rule
 // is in include/lvba_hip.h, its scalar pieces in resect_device.h).
 //
-// Device design (after verify.hip):
+// What is this stage's own, on the skeleton of ransac_batch.h (DESIGN.md §10k says which piece is whose; §10n why 40-byte records):
 //   (image_set.hip)           the pixels undistorted once per call: an ImageSet whose "images" are the jobs.
-//   resect_pack_kernel        a thread per correspondence: its record (x, y, X), an unusable one marked by NaN.  RESECT_REC = 5
-//                             doubles, 40 bytes, the payload and no more: a chunk of RESECT_CHUNK records is then 40 KiB of LDS and
-//                             four workgroups fit the 160 KiB of a compute unit, one wavefront per SIMD; padded to 48 bytes (three
-//                             aligned 16-byte reads) only three would, and the scoring loop is bound by fp64 arithmetic, not by
-//                             LDS reads -- five 8-byte broadcast reads per record against about thirty fp64 operations.
-//   resect_hypothesis_kernel  generates and scores in one launch.  The grid is the list of (job, block of RESECT_HB hypotheses) of
-//                             every job of the call; a workgroup is one wavefront and a lane owns one hypothesis.  The lane draws
-//                             its four positions, reads those records from global memory and solves in registers (the solver's
-//                             3 x 3 matrices are indexed by compile-time constants only, its choices are select chains: no scratch
-//                             memory).  (R, t) stay in twelve register pairs.  The job's records are staged in LDS in chunks of
-//                             RESECT_CHUNK; every lane walks them, all lanes read the same address (a broadcast: no bank
-//                             conflict), and counts its inliers.  The block's best (count, lowest h) and that lane's pose go to
-//                             one record per block: the per-hypothesis pose never reaches global memory, except through
-//                             lvba_resect_hypotheses (one job, the diagnostic call).
-//   resect_pick_kernel        a thread per job: the integer maximum over the job's block records.
+//   resect_pack_kernel        a thread per correspondence: its record (x, y, X) of RESECT_REC = 5 doubles, an unusable one marked by NaN.
+//   resect_hypothesis_kernel  a lane draws its four positions, reads those records from global memory and solves in registers (the
+//                             solver's 3 x 3 matrices are indexed by compile-time constants only, its choices are select chains: no
+//                             scratch memory).  The pose stays in twelve register pairs; the job's records are staged in LDS in
+//                             chunks of RESECT_CHUNK, which every lane walks (a broadcast read).
 //   resect_refine_kernel      a workgroup per job: per Gauss-Newton step the 27 sums over the inliers (per-thread strides, then
-//                             wave_ops.h' fixed trees), the 6 x 6 solve in one lane (its loops have constant trip counts and unroll:
-//                             the matrix stays in registers, no scratch), after a round the rescore; then status, rmse and information at the final pose.
-//   resect_mask_kernel        a thread per correspondence: inlier of its job's final pose, and the job OK -> a flag.
-//   resect_write_kernel       after an exclusive prefix sum of the flags: the inlier positions in (job, original order), inlier_off.
+//                             wave_ops.h' fixed trees), the 6 x 6 solve in one lane (constant trip counts: the matrix stays in
+//                             registers), after a round the rescore; then status, rmse and information at the final pose.
+//   ResectInlier, ResectEmit  the inlier test of the mask kernel; an inlier is written as its position within its job.
 //   resect_lift_kernel        a thread per keypoint: match_device.h' match_lift through the image's depth image.
-// No atomics of any kind, every choice an integer comparison: two calls give the same bytes, and so does a job resected alone or
-// in a batch in any order (the generator does not know the job's position, the grid or the lane).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <algorithm>
@@ -38,6 +25,7 @@
 #include "image_set.h"
 #include "match_device.h"
 #include "resect_device.h"
+#include "ransac_batch.h"
 #include "wave_ops.h"
 #include "../../include/lvba_hip.h"
 
@@ -45,24 +33,14 @@ using namespace lvba;
 
 namespace {
 
-constexpr int RESECT_HB = 64;               // hypotheses per workgroup: one wavefront, a lane each
 constexpr int RESECT_CHUNK = 1024;          // correspondences staged in LDS at a time, 40 bytes each
 constexpr int REFINE_BLOCK = 256;
-constexpr int64_t RESECT_MAX_CORR = (int64_t)1 << 31;   // the flags' prefix sum is 32 bits wide
 
 struct ResectTask {
-    int64_t off;                    // first correspondence of the job
-    int32_t m, id;
-    int32_t blk0, n_blk;            // the job's block records
+    RansacSpan span;                // the job's correspondences in the call's list, its block records
+    int32_t id;
 };
-struct ResectBest { int32_t count, h; double R[9], t[3]; };   // count -1: no valid hypothesis
-
-LVBA_TRK_FN void pose_zero(double *R, double *t)
-{
-#pragma unroll
-    for (int k = 0; k < 9; ++k) R[k] = 0.0;
-    t[0] = t[1] = t[2] = 0.0;
-}
+typedef RansacBest<12> ResectBest;  // the model is the pose: R [9], then t [3]
 
 // rec [n][RESECT_REC]
 __global__ __launch_bounds__(256) void resect_pack_kernel(int64_t n, const double *__restrict__ xy, const double *__restrict__ world,
@@ -77,26 +55,23 @@ __global__ __launch_bounds__(256) void resect_pack_kernel(int64_t n, const doubl
     for (int k = 0; k < RESECT_REC; ++k) rec[RESECT_REC * i + k] = r[k];
 }
 
-// tiles [n_tiles] = (task, first hypothesis); blk [n_tiles]; diag_R [H][9], diag_t [H][3], diag_count [H]: null, or every
-// hypothesis of the one task
-__global__ __launch_bounds__(RESECT_HB) void resect_hypothesis_kernel(const ResectTask *__restrict__ tasks, const int2 *__restrict__ tiles,
+// tiles [n_tiles]; blk, diag_pose, diag_count: see ransac_block_best
+__global__ __launch_bounds__(RANSAC_HB) void resect_hypothesis_kernel(const ResectTask *__restrict__ tasks, const RansacTile *__restrict__ tiles,
                                                                       const double *__restrict__ rec, uint64_t seed, int H, double fx,
                                                                       double fy, double rho, ResectBest *__restrict__ blk,
-                                                                      double *__restrict__ diag_R, double *__restrict__ diag_t,
-                                                                      int32_t *__restrict__ diag_count)
+                                                                      double *__restrict__ diag_pose, int32_t *__restrict__ diag_count)
 {
     __shared__ double lds[RESECT_REC * RESECT_CHUNK];
-    const int2 tl = tiles[blockIdx.x];
-    const ResectTask &task = tasks[tl.x];
-    const int lane = threadIdx.x, h = tl.y + lane, m = task.m;
-    const double *__restrict__ jr = rec + RESECT_REC * task.off;
-    const bool live = h < H;
-    double R[9], t[3];
+    const RansacLane ln = ransac_lane(tiles, H);
+    const ResectTask &task = tasks[ln.task];
+    const int lane = threadIdx.x, m = task.span.m;
+    const double *__restrict__ jr = rec + RESECT_REC * task.span.off;
+    double P[12] = {};              // R, then t
+    double *const R = P, *const t = P + 9;
     bool valid = false;
-    pose_zero(R, t);
-    if (live) {
+    if (ln.live) {
         int32_t idx[RESECT_K];
-        verify_sample<RESECT_K>(verify_key(seed, task.id, -1, h), m, idx);
+        ransac_sample<RESECT_K>(ransac_key(seed, task.id, -1, ln.h), m, idx);
         double c[RESECT_K][RESECT_REC];
 #pragma unroll
         for (int j = 0; j < RESECT_K; ++j)
@@ -107,7 +82,7 @@ __global__ __launch_bounds__(RESECT_HB) void resect_hypothesis_kernel(const Rese
     int32_t count = 0;
     for (int c0 = 0; c0 < m; c0 += RESECT_CHUNK) {
         const int n = min(RESECT_CHUNK, m - c0);
-        for (int i = lane; i < RESECT_REC * n; i += RESECT_HB) lds[i] = jr[RESECT_REC * (int64_t)c0 + i];
+        for (int i = lane; i < RESECT_REC * n; i += RANSAC_HB) lds[i] = jr[RESECT_REC * (int64_t)c0 + i];
         __syncthreads();
 #pragma unroll 4
         for (int i = 0; i < n; ++i) {
@@ -117,47 +92,7 @@ __global__ __launch_bounds__(RESECT_HB) void resect_hypothesis_kernel(const Rese
         __syncthreads();
     }
     if (!valid) count = -1;
-    if (diag_R && live) {
-#pragma unroll
-        for (int k = 0; k < 9; ++k) diag_R[9 * (int64_t)h + k] = R[k];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) diag_t[3 * (int64_t)h + k] = t[k];
-        diag_count[h] = count;
-    }
-    const int64_t own = live ? verify_rank(count, h) : (int64_t)-1;
-    int64_t top = own;
-#pragma unroll
-    for (int w = 1; w < 64; w <<= 1) {
-        const int64_t o = __shfl_xor(top, w, 64);
-        top = o > top ? o : top;
-    }
-    if (live && own == top) { // one lane: h is part of the rank
-        ResectBest &b = blk[blockIdx.x];
-        b.count = count; b.h = h;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) b.R[k] = R[k];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) b.t[k] = t[k];
-    }
-}
-
-__global__ __launch_bounds__(256) void resect_pick_kernel(int n_tasks, const ResectTask *__restrict__ tasks, const ResectBest *__restrict__ blk,
-                                                          ResectBest *__restrict__ res)
-{
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= n_tasks) return;
-    const ResectTask &t = tasks[p];
-    int win = -1;
-    int64_t top = -1;
-    for (int k = 0; k < t.n_blk; ++k) {
-        const int64_t r = verify_rank(blk[t.blk0 + k].count, blk[t.blk0 + k].h);
-        if (r > top) { top = r; win = t.blk0 + k; }
-    }
-    ResectBest b;
-    b.count = -1; b.h = -1;
-    pose_zero(b.R, b.t);
-    if (win >= 0 && blk[win].count >= 0) b = blk[win];
-    res[p] = b;
+    ransac_block_best<12>(ln, count, P, blk, diag_pose, diag_count);
 }
 
 // the number of inliers of (R, t) among the job's records, in every thread
@@ -202,14 +137,14 @@ __global__ __launch_bounds__(REFINE_BLOCK) void resect_refine_kernel(const Resec
     __shared__ int s_ok;
     const int j = blockIdx.x, tid = threadIdx.x;
     const ResectTask &task = tasks[j];
-    const int m = task.m;
-    const double *__restrict__ jr = rec + RESECT_REC * task.off;
+    const int m = task.span.m;
+    const double *__restrict__ jr = rec + RESECT_REC * task.span.off;
     const ResectBest b = res[j];
     double R[9], t[3];
 #pragma unroll
-    for (int k = 0; k < 9; ++k) R[k] = b.R[k];
+    for (int k = 0; k < 9; ++k) R[k] = b.model[k];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) t[k] = b.t[k];
+    for (int k = 0; k < 3; ++k) t[k] = b.model[9 + k];
     int32_t count = b.count;
     for (int round = 0; round < rounds && count > 0; ++round) { // every condition below is the same in all threads
         double P[9], q[3];
@@ -251,7 +186,7 @@ __global__ __launch_bounds__(REFINE_BLOCK) void resect_refine_kernel(const Resec
     }
     if (count > 0) block_sums(jr, m, R, t, R, t, fx, fy, rho, red, sT);
     if (tid != 0) return;
-    status[j] = resect_status(m, min_inliers, count);
+    status[j] = ransac_status(m, RESECT_K, min_inliers, count);
     n_inliers[j] = count > 0 ? count : 0;
     best_h[j] = b.h;
 #pragma unroll
@@ -269,43 +204,27 @@ __global__ __launch_bounds__(REFINE_BLOCK) void resect_refine_kernel(const Resec
     rmse[j] = count > 0 ? sqrt(sT[27] / (double)count) : 0.0;
 }
 
-// flag [n + 1] (the last is 0): correspondence i of the call is an inlier of its job's pose and the job is OK
-__global__ __launch_bounds__(256) void resect_mask_kernel(int64_t n, int n_tasks, const ResectTask *__restrict__ tasks,
-                                                          const double *__restrict__ rec, double fx, double fy, double rho,
-                                                          const double *__restrict__ R, const double *__restrict__ t,
-                                                          const int32_t *__restrict__ status, uint32_t *__restrict__ flag)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i > n) return;
-    if (i == n) { flag[i] = 0; return; }
-    const int j = segment_of([=](int k) { return tasks[k].off; }, n_tasks, i);
-    bool ok = status[j] == RESECT_OK;
-    if (ok) {
-        double r[9], tt[3];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) r[k] = R[9 * (int64_t)j + k];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) tt[k] = t[3 * (int64_t)j + k];
+// correspondence i of the call, of job j, is an inlier of the pose (R [j], t [j])
+struct ResectInlier {
+    const double *rec, *R, *t;
+    double fx, fy, rho;
+    __device__ bool operator()(const ResectTask &, int j, int64_t i) const
+    {
         const double *p = rec + RESECT_REC * i;
-        ok = resect_inlier(r, tt, fx, fy, rho, p[0], p[1], p[2], p[3], p[4]);
+        return resect_inlier(R + 9 * (int64_t)j, t + 3 * (int64_t)j, fx, fy, rho, p[0], p[1], p[2], p[3], p[4]);
     }
-    flag[i] = ok ? 1u : 0u;
-}
-
-// inliers [n_out] = positions within the job, in (job, original order); off [n_tasks + 1]
-__global__ __launch_bounds__(256) void resect_write_kernel(int64_t n, int n_tasks, const ResectTask *__restrict__ tasks,
-                                                           const uint32_t *__restrict__ flag, const uint32_t *__restrict__ excl, int64_t n_out,
-                                                           int32_t *__restrict__ inliers, int64_t *__restrict__ off)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n_tasks) off[i] = excl[tasks[i].off];
-    if (i == n_tasks) off[i] = excl[n];
-    if (i >= n || !flag[i]) return;
-    const int64_t pos = excl[i];
-    if (pos >= n_out) return;
-    const int j = segment_of([=](int k) { return tasks[k].off; }, n_tasks, i);
-    inliers[pos] = (int32_t)(i - tasks[j].off);
-}
+};
+// an inlier is its position within its job
+struct ResectEmit {
+    static constexpr int WIDTH = 1;
+    const ResectTask *tasks;
+    int n_tasks;
+    __device__ void operator()(int32_t *out, int64_t pos, int64_t i) const
+    {
+        const ResectTask *tk = tasks;
+        out[pos] = (int32_t)(i - tk[segment_of([=](int k) { return tk[k].span.off; }, n_tasks, i)].span.off);
+    }
+};
 
 // world [n][3]; img_off [n_images + 1]
 __global__ __launch_bounds__(256) void resect_lift_kernel(int64_t n, int n_images, const int64_t *__restrict__ img_off,
@@ -362,32 +281,16 @@ int32_t make_records(hipStream_t s, int device, int32_t n_jobs, const int64_t *c
     return LVBA_OK;
 }
 
-// The hypotheses of every task with enough correspondences, one grid; blk0 / n_blk of the tasks are set here.
+// The hypotheses of every job with enough correspondences (ransac_run_hypotheses).  diag_pose [H][12], diag_count: null, or the
+// diagnostic call's outputs.
 int32_t run_hypotheses(hipStream_t s, std::vector<ResectTask> &tasks, const lvba_resect_opts &o, const double *intr, const double *d_rec,
-                       DevBuf &d_tasks, DevBuf &d_blk, double *diag_R, double *diag_t, int32_t *diag_count)
+                       DevBuf &d_tasks, DevBuf &d_blk, double *diag_pose, int32_t *diag_count)
 {
-    const int need = std::max(RESECT_K, o.min_inliers);
-    std::vector<int2> tiles;
-    for (size_t p = 0; p < tasks.size(); ++p) {
-        tasks[p].blk0 = (int32_t)tiles.size();
-        if (tasks[p].m >= (diag_R ? RESECT_K : need))
-            for (int h0 = 0; h0 < o.hypotheses; h0 += RESECT_HB) tiles.push_back(make_int2((int)p, h0));
-        tasks[p].n_blk = (int32_t)tiles.size() - tasks[p].blk0;
-        if (tiles.size() > (size_t)INT32_MAX / 2) return lvba_fail(LVBA_ERR_UNSUPPORTED, "more than 2^30 hypothesis blocks in one call");
-    }
-    HIPCHK(d_tasks.alloc(sizeof(ResectTask) * tasks.size()));
-    HIPCHK(lvba::copy_h2d(d_tasks.p, tasks.data(), sizeof(ResectTask) * tasks.size()));
-    HIPCHK(d_blk.alloc(sizeof(ResectBest) * tiles.size()));
-    if (tiles.empty()) return LVBA_OK;
-    DevBuf d_tiles(s);
-    HIPCHK(d_tiles.alloc(sizeof(int2) * tiles.size()));
-    HIPCHK(lvba::copy_h2d(d_tiles.p, tiles.data(), sizeof(int2) * tiles.size()));
-    resect_hypothesis_kernel<<<(unsigned)tiles.size(), RESECT_HB, 0, s>>>(d_tasks.as<ResectTask>(), d_tiles.as<int2>(), d_rec, o.seed, o.hypotheses,
-                                                                          intr[0], intr[1], o.max_error_px, d_blk.as<ResectBest>(), diag_R, diag_t,
-                                                                          diag_count);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s)); // the tile list goes with this scope
-    return LVBA_OK;
+    return ransac_run_hypotheses<12>(s, tasks, o.hypotheses, diag_pose ? RESECT_K : std::max(RESECT_K, o.min_inliers), d_tasks, d_blk,
+                                     [&](unsigned grid, const RansacTile *tiles) {
+        resect_hypothesis_kernel<<<grid, RANSAC_HB, 0, s>>>(d_tasks.as<ResectTask>(), tiles, d_rec, o.seed, o.hypotheses, intr[0], intr[1],
+                                                            o.max_error_px, d_blk.as<ResectBest>(), diag_pose, diag_count);
+    });
 }
 
 } // namespace
@@ -413,7 +316,7 @@ extern "C" int32_t lvba_resect_images(int32_t device, int32_t n_jobs, const int3
     if (n_jobs >= INT32_MAX / 2) return lvba_fail(LVBA_ERR_UNSUPPORTED, "%d jobs in one call", n_jobs);
     TRY(check_offsets("corr_off", "job", n_jobs, corr_off, INT32_MAX - 1));
     const int64_t total = corr_off[n_jobs];
-    if (total >= RESECT_MAX_CORR) return lvba_fail(LVBA_ERR_UNSUPPORTED, "%lld correspondences in one call (below 2^31)", (long long)total);
+    if (total >= RANSAC_MAX_ELEMENTS) return lvba_fail(LVBA_ERR_UNSUPPORTED, "%lld correspondences in one call (below 2^31)", (long long)total);
     if (total > 0 && (!uv || !world)) return lvba_fail(LVBA_ERR_ARG, "null correspondences");
     {
         std::vector<int32_t> seen(ids, ids + n_jobs);
@@ -426,7 +329,7 @@ extern "C" int32_t lvba_resect_images(int32_t device, int32_t n_jobs, const int3
     std::vector<ResectTask> tasks((size_t)n_jobs);
     for (int32_t j = 0; j < n_jobs; ++j) {
         tasks[j] = ResectTask{};
-        tasks[j].off = corr_off[j]; tasks[j].m = (int32_t)(corr_off[j + 1] - corr_off[j]); tasks[j].id = ids[j];
+        tasks[j].span.off = corr_off[j]; tasks[j].span.m = (int32_t)(corr_off[j + 1] - corr_off[j]); tasks[j].id = ids[j];
     }
     if (n_jobs == 0) { inlier_off[0] = 0; return LVBA_OK; }
     HIPCHK(hipSetDevice(device));
@@ -437,34 +340,20 @@ extern "C" int32_t lvba_resect_images(int32_t device, int32_t n_jobs, const int3
     Records recs(s);
     TRY(make_records(s, device, n_jobs, corr_off, uv, world, intr, recs));
     const double *d_rec = recs.rec.as<double>();
-    DevBuf d_tasks(s), d_blk(s), d_res(s), d_pose(s), d_int(s), d_real(s), d_flag(s), d_excl(s), d_off(s), d_out(s);
-    TRY(run_hypotheses(s, tasks, o, intr, d_rec, d_tasks, d_blk, nullptr, nullptr, nullptr));
+    DevBuf d_tasks(s), d_blk(s), d_res(s), d_pose(s), d_int(s), d_real(s);
+    TRY(run_hypotheses(s, tasks, o, intr, d_rec, d_tasks, d_blk, nullptr, nullptr));
     HIPCHK(d_res.alloc(sizeof(ResectBest) * (size_t)nj)); HIPCHK(d_pose.alloc(96 * (size_t)nj)); HIPCHK(d_int.alloc(12 * (size_t)nj));
     HIPCHK(d_real.alloc(8 * 37 * (size_t)nj));
-    HIPCHK(d_flag.alloc(4 * ((size_t)total + 1))); HIPCHK(d_excl.alloc(4 * ((size_t)total + 1))); HIPCHK(d_off.alloc(8 * ((size_t)nj + 1)));
     double *d_R = d_pose.as<double>(), *d_t = d_R + 9 * (size_t)nj;
     double *d_info = d_real.as<double>(), *d_rmse = d_info + 36 * (size_t)nj;
     int32_t *d_status = d_int.as<int32_t>(), *d_cnt = d_status + nj, *d_h = d_cnt + nj;
-    resect_pick_kernel<<<grid_for(nj, 256), 256, 0, s>>>(nj, d_tasks.as<ResectTask>(), d_blk.as<ResectBest>(), d_res.as<ResectBest>());
+    ransac_pick_kernel<<<grid_for(nj, 256), 256, 0, s>>>(nj, d_tasks.as<ResectTask>(), d_blk.as<ResectBest>(), d_res.as<ResectBest>());
     HIPCHK(hipGetLastError());
     resect_refine_kernel<<<(unsigned)nj, REFINE_BLOCK, 0, s>>>(d_tasks.as<ResectTask>(), d_rec, intr[0], intr[1], o.max_error_px, o.refine_rounds,
                                                               o.min_inliers, d_res.as<ResectBest>(), d_R, d_t, d_status, d_cnt, d_h, d_rmse, d_info);
     HIPCHK(hipGetLastError());
-    resect_mask_kernel<<<grid_for(total + 1, 256), 256, 0, s>>>(total, nj, d_tasks.as<ResectTask>(), d_rec, intr[0], intr[1], o.max_error_px, d_R,
-                                                                d_t, d_status, d_flag.as<uint32_t>());
-    HIPCHK(hipGetLastError());
-    TRY(scan_excl<uint32_t>(s, d_flag.as<uint32_t>(), d_excl.as<uint32_t>(), (size_t)total + 1));
-    uint32_t found = 0;
-    HIPCHK(lvba::copy_d2h(&found, d_excl.as<uint32_t>() + total, 4));
-    const int64_t n_out = std::min<int64_t>(found, capacity);
-    HIPCHK(d_out.alloc(4 * (size_t)n_out));
-    resect_write_kernel<<<grid_for(std::max<int64_t>(total, nj + 1), 256), 256, 0, s>>>(total, nj, d_tasks.as<ResectTask>(), d_flag.as<uint32_t>(),
-                                                                                       d_excl.as<uint32_t>(), n_out, d_out.as<int32_t>(),
-                                                                                       d_off.as<int64_t>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(lvba::copy_d2h(inlier_off, d_off.p, 8 * ((size_t)nj + 1)));
-    if (n_out > 0) HIPCHK(lvba::copy_d2h(inliers, d_out.p, 4 * (size_t)n_out));
+    TRY(ransac_inlier_lists(s, total, nj, d_tasks.as<ResectTask>(), d_status, ResectInlier{d_rec, d_R, d_t, intr[0], intr[1], o.max_error_px},
+                            ResectEmit{d_tasks.as<ResectTask>(), nj}, capacity, inlier_off, inliers));
     HIPCHK(lvba::copy_d2h(Rcw, d_R, 72 * (size_t)nj));
     HIPCHK(lvba::copy_d2h(tcw, d_t, 24 * (size_t)nj));
     HIPCHK(lvba::copy_d2h(status, d_status, 4 * (size_t)nj));
@@ -500,12 +389,13 @@ extern "C" int32_t lvba_resect_hypotheses(int32_t device, int32_t id, int64_t n_
     TRY(make_records(sg.s, device, 1, off, uv, world, intr, recs));
     std::vector<ResectTask> tasks(1);
     tasks[0] = ResectTask{};
-    tasks[0].m = (int32_t)n_corr; tasks[0].id = id;
-    DevBuf d_tasks(sg.s), d_blk(sg.s), d_R(sg.s), d_t(sg.s), d_c(sg.s);
-    HIPCHK(d_R.alloc(72 * H)); HIPCHK(d_t.alloc(24 * H)); HIPCHK(d_c.alloc(4 * H));
-    TRY(run_hypotheses(sg.s, tasks, o, intr, recs.rec.as<double>(), d_tasks, d_blk, d_R.as<double>(), d_t.as<double>(), d_c.as<int32_t>()));
-    HIPCHK(lvba::copy_d2h(R, d_R.p, 72 * H));
-    HIPCHK(lvba::copy_d2h(t, d_t.p, 24 * H));
+    tasks[0].span.m = (int32_t)n_corr; tasks[0].id = id;
+    DevBuf d_tasks(sg.s), d_blk(sg.s), d_pose(sg.s), d_c(sg.s);
+    HIPCHK(d_pose.alloc(96 * H)); HIPCHK(d_c.alloc(4 * H));
+    TRY(run_hypotheses(sg.s, tasks, o, intr, recs.rec.as<double>(), d_tasks, d_blk, d_pose.as<double>(), d_c.as<int32_t>()));
+    std::vector<double> pose(12 * H);
+    HIPCHK(lvba::copy_d2h(pose.data(), d_pose.p, 96 * H));
+    for (size_t h = 0; h < H; ++h) { std::copy_n(&pose[12 * h], 9, R + 9 * h); std::copy_n(&pose[12 * h + 9], 3, t + 3 * h); }
     HIPCHK(lvba::copy_d2h(count, d_c.p, 4 * H));
     return LVBA_OK;
 }
@@ -523,27 +413,16 @@ extern "C" int32_t lvba_resect_score(int32_t device, int64_t n_corr, const float
     ScopedStream sg;
     HIPCHK(sg.acquire());
     const int64_t off[2] = {0, n_corr};
-    const size_t n = (size_t)n_corr;
     Records recs(sg.s);
     TRY(make_records(sg.s, device, 1, off, uv, world, intr, recs));
     ResectTask task{};
-    task.m = (int32_t)n_corr;
-    DevBuf d_tasks(sg.s), d_pose(sg.s), d_st(sg.s), d_flag(sg.s);
-    HIPCHK(d_tasks.alloc(sizeof(ResectTask))); HIPCHK(d_pose.alloc(96)); HIPCHK(d_st.alloc(4)); HIPCHK(d_flag.alloc(4 * (n + 1)));
-    const int32_t ok = RESECT_OK;
-    HIPCHK(lvba::copy_h2d(d_tasks.p, &task, sizeof(ResectTask)));
+    task.span.m = (int32_t)n_corr;
+    DevBuf d_pose(sg.s);
+    HIPCHK(d_pose.alloc(96));
     HIPCHK(lvba::copy_h2d(d_pose.p, Rcw, 72));
     HIPCHK(lvba::copy_h2d(d_pose.as<double>() + 9, tcw, 24));
-    HIPCHK(lvba::copy_h2d(d_st.p, &ok, 4));
-    resect_mask_kernel<<<grid_for(n_corr + 1, 256), 256, 0, sg.s>>>(n_corr, 1, d_tasks.as<ResectTask>(), recs.rec.as<double>(), intr[0], intr[1],
-                                                                   max_error_px, d_pose.as<double>(), d_pose.as<double>() + 9, d_st.as<int32_t>(),
-                                                                   d_flag.as<uint32_t>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(sg.s));
-    std::vector<uint32_t> flag(n);
-    HIPCHK(lvba::copy_d2h(flag.data(), d_flag.p, 4 * n));
-    for (size_t i = 0; i < n; ++i) mask[i] = flag[i] ? 1 : 0;
-    return LVBA_OK;
+    return ransac_score_mask(sg.s, task, ResectInlier{recs.rec.as<double>(), d_pose.as<double>(), d_pose.as<double>() + 9, intr[0], intr[1], max_error_px},
+                             mask);
 }
 
 extern "C" int32_t lvba_resect_lift(lvba_depth_t depth, int32_t n_images, const int64_t *kp_off, const float *uv, const double *intr,

@@ -1,17 +1,18 @@
 // resect_device.h -- scalar pieces of the camera resectioning (resect.hip; the rule is in include/lvba_hip.h): the
 // correspondence record, the inlier test, the three-point minimal solver with its fourth-point choice, the Gauss-Newton refit on
-// the six pose parameters and the re-orthonormalisation through a unit quaternion.  Host/device-neutral, like verify_device.h,
-// whose generator, sampler and rank it uses as they stand.  The hypothesis stage uses +, -, *, / and sqrt only, in the order
+// the six pose parameters and the re-orthonormalisation through a unit quaternion.  Host/device-neutral; the generator, the sampler,
+// the rank and the status are ransac_device.h'.  The hypothesis stage uses +, -, *, / and sqrt only, in the order
 // written here, and resect.hip is built without contraction: a hypothesis is the same bits on the host and on the device.  The
 // refit's sums are taken in another order on the device (a tree) and it is held to a measured tolerance instead.
 #pragma once
 #include <math.h>
 #include <stdint.h>
-#include "verify_device.h"
+#include "ransac_device.h"
 
 namespace lvba {
 
-enum ResectStatus : int { RESECT_OK = 0, RESECT_TOO_FEW_MATCHES = 1, RESECT_NO_MODEL = 2, RESECT_TOO_FEW_INLIERS = 3 };
+constexpr int RESECT_OK = RANSAC_OK, RESECT_TOO_FEW_MATCHES = RANSAC_TOO_FEW_MATCHES, RESECT_NO_MODEL = RANSAC_NO_MODEL,
+              RESECT_TOO_FEW_INLIERS = RANSAC_TOO_FEW_INLIERS;
 constexpr int RESECT_K = 4;                       // draws per hypothesis: three for the solver, one to choose among its solutions
 constexpr int RESECT_REC = 5;                     // doubles per correspondence record: x, y, X0, X1, X2 (40 bytes; resect.hip says why)
 constexpr double RESECT_MIN_DEPTH = 1e-12;        // projectCameraToPixel's cheirality bound
@@ -265,8 +266,6 @@ LVBA_TRK_FN bool resect_p3p(const double *c0, const double *c1, const double *c2
     }
     return found;
 }
-
-LVBA_TRK_FN int resect_status(int32_t m, int32_t min_inliers, int32_t count) { return verify_status(m, RESECT_K, min_inliers, count); }
 
 // ---- the refit -----------------------------------------------------------------------------------------------------------------------
 // One correspondence's share of the normal equations at (R, t): r = (fx (Xc_x / Xc_z - x), fy (Xc_y / Xc_z - y)), J its derivative

@@ -1,25 +1,15 @@
 // verify.hip -- two-view RANSAC over the putative matches of many image pairs at once (lvba_verify_*; the rule is in
 // include/lvba_hip.h, its scalar pieces in verify_device.h).
 //
-// Device design:
+// What is this stage's own, on the skeleton of ransac_batch.h (DESIGN.md §10k says which piece is whose):
 //   (image_set.hip)           the undistorted keypoints: the handle's ImageSet, image_set_undistort once per handle.
-//   verify_hypothesis_kernel  generates and scores in one launch.  The grid is the list of (pair, block of VERIFY_HB hypotheses) of
-//                             every pair of the call; a workgroup is one wavefront and a lane owns one hypothesis.  In its prologue
-//                             the lane draws its sample, reads those matches and solves; under the eight-point method the 8 x 9
-//                             system (72 doubles) lives in LDS, lane-interleaved, where the pivot search may index it at run time
-//                             -- in registers that would be scratch memory or a select chain per access.  E then stays in nine
-//                             register pairs.  The same LDS is reused to stage the pair's undistorted match coordinates, 32 bytes
-//                             per match, in chunks of VERIFY_CHUNK; every lane walks the staged matches, all lanes read the same
-//                             address (a broadcast: no bank conflict), and counts its inliers with match_device.h' gate.  The
-//                             block's best (count, lowest h) and that lane's E go to one record per block: the per-hypothesis E
-//                             never reaches global memory, except through lvba_verify_hypotheses (one pair, the diagnostic call).
-//   verify_pick_kernel        a thread per pair: the integer maximum over the pair's block records.
+//   verify_hypothesis_kernel  a lane draws its sample, reads those matches and solves; the eight-point method's 8 x 9 system lives in
+//                             LDS, lane-interleaved, where the pivot search may index it at run time.  E then stays in nine register
+//                             pairs; the same LDS stages the pair's match coordinates, 32 bytes each, in chunks of VERIFY_CHUNK,
+//                             which every lane walks (a broadcast read) with match_device.h' gate.
 //   verify_refine_kernel      a workgroup per pair: the sums over the winner's inliers (per-thread strides, then wave_ops.h' fixed
 //                             trees), the refit in one lane (Jacobi on LDS), a rescore, kept only if the count grows; status.
-//   verify_mask_kernel        a thread per match: inlier of its pair's final E, and the pair OK -> a flag.
-//   verify_write_kernel       after an exclusive prefix sum of the flags: the inlier matches in (pair, original order), inlier_off.
-// No atomics of any kind, every choice an integer comparison: two calls give the same bytes, and so does a pair verified alone or
-// in a batch in any order (the generator does not know the pair's position, the grid or the lane).
+//   VerifyInlier, VerifyEmit  the inlier test of the mask kernel; an inlier is written as its match, the caller's columns.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <algorithm>
@@ -28,9 +18,9 @@
 #include "lvba_common.h"
 #include "mempool.h"
 #include "voxel_internal.h"
-#include "segments.h"
 #include "image_set.h"
 #include "verify_device.h"
+#include "ransac_batch.h"
 #include "wave_ops.h"
 #include "../../include/lvba_hip.h"
 
@@ -45,58 +35,55 @@ struct lvba_verify_s {
 
 namespace {
 
-constexpr int VERIFY_HB = 64;               // hypotheses per workgroup: one wavefront, a lane each
 constexpr int VERIFY_CHUNK = 1024;          // matches staged in LDS at a time, 32 bytes each
-constexpr int VERIFY_LDS_DOUBLES = 72 * VERIFY_HB > 4 * VERIFY_CHUNK ? 72 * VERIFY_HB : 4 * VERIFY_CHUNK;   // 36 864 bytes
+constexpr int VERIFY_LDS_DOUBLES = 72 * RANSAC_HB > 4 * VERIFY_CHUNK ? 72 * RANSAC_HB : 4 * VERIFY_CHUNK;   // 36 864 bytes
 constexpr int REFINE_BLOCK = 256;
-constexpr int64_t VERIFY_MAX_MATCHES = (int64_t)1 << 31;   // the flags' prefix sum is 32 bits wide
 
 struct VerifyTask {
-    int64_t lo_off, hi_off, m_off;  // first keypoint of lo and of hi, first match of the pair
-    int32_t m, lo, hi, swap;        // swap: the pair was given as (hi, lo), column 1 of its matches is the lo image
-    int32_t blk0, n_blk;            // the pair's block records
+    RansacSpan span;                // the pair's matches in the call's list, its block records
+    int64_t lo_off, hi_off;         // first keypoint of lo and of hi
+    int32_t lo, hi, swap;           // swap: the pair was given as (hi, lo), column 1 of its matches is the lo image
     double R[9];                    // R_hi R_lo^T (method 1)
 };
-struct VerifyBest { int32_t count, h; double E[9]; };   // count -1: no valid hypothesis
+typedef RansacBest<9> VerifyBest;   // the model is E
 
 // the undistorted coordinates (x_lo, y_lo, x_hi, y_hi) of match i of the task
 __device__ __forceinline__ void load_match(const VerifyTask &t, const int32_t *__restrict__ matches, const double *__restrict__ xy, int i,
                                            double &xl, double &yl, double &xh, double &yh)
 {
-    const int2 mm = reinterpret_cast<const int2 *>(matches)[t.m_off + i];
+    const int2 mm = reinterpret_cast<const int2 *>(matches)[t.span.off + i];
     const int64_t kl = t.lo_off + (t.swap ? mm.y : mm.x), kh = t.hi_off + (t.swap ? mm.x : mm.y);
     const double2 pl = reinterpret_cast<const double2 *>(xy)[kl], ph = reinterpret_cast<const double2 *>(xy)[kh];
     xl = pl.x; yl = pl.y; xh = ph.x; yh = ph.y;
 }
 
-// tiles [n_tiles] = (task, first hypothesis); blk [n_tiles]; diag_E [H][9], diag_count [H]: null, or every hypothesis of the one task
+// tiles [n_tiles]; blk, diag_E, diag_count: see ransac_block_best
 template <int METHOD>
-__global__ __launch_bounds__(VERIFY_HB) void verify_hypothesis_kernel(const VerifyTask *__restrict__ tasks, const int2 *__restrict__ tiles,
+__global__ __launch_bounds__(RANSAC_HB) void verify_hypothesis_kernel(const VerifyTask *__restrict__ tasks, const RansacTile *__restrict__ tiles,
                                                                       const int32_t *__restrict__ matches, const double *__restrict__ xy,
                                                                       uint64_t seed, int H, double tau2, VerifyBest *__restrict__ blk,
                                                                       double *__restrict__ diag_E, int32_t *__restrict__ diag_count)
 {
     constexpr int K = METHOD == VERIFY_KNOWN_ROTATION ? 2 : 8;
     __shared__ __attribute__((aligned(16))) double lds[METHOD == VERIFY_EIGHT_POINT ? VERIFY_LDS_DOUBLES : 4 * VERIFY_CHUNK];
-    const int2 tl = tiles[blockIdx.x];
-    const VerifyTask &t = tasks[tl.x];
-    const int lane = threadIdx.x, h = tl.y + lane, m = t.m;
-    const bool live = h < H;
+    const RansacLane ln = ransac_lane(tiles, H);
+    const VerifyTask &t = tasks[ln.task];
+    const int lane = threadIdx.x, m = t.span.m;
     double E[9];
     bool valid = false;
     verify_zero(E);
-    if (live) {
+    if (ln.live) {
         int32_t idx[K];
-        verify_sample<K>(verify_key(seed, t.lo, t.hi, h), m, idx);
+        ransac_sample<K>(ransac_key(seed, t.lo, t.hi, ln.h), m, idx);
         if constexpr (METHOD == VERIFY_EIGHT_POINT) {
             bool clean = true;
 #pragma unroll
             for (int j = 0; j < K; ++j) {
                 double xl, yl, xh, yh;
                 load_match(t, matches, xy, idx[j], xl, yl, xh, yh);
-                clean &= verify_eight_row(lds + lane, VERIFY_HB, j, xl, yl, xh, yh);
+                clean &= verify_eight_row(lds + lane, RANSAC_HB, j, xl, yl, xh, yh);
             }
-            valid = clean && verify_eight_solve(lds + lane, VERIFY_HB, E);
+            valid = clean && verify_eight_solve(lds + lane, RANSAC_HB, E);
         } else {
             double p[8], R[9];
             load_match(t, matches, xy, idx[0], p[0], p[1], p[2], p[3]);
@@ -110,7 +97,7 @@ __global__ __launch_bounds__(VERIFY_HB) void verify_hypothesis_kernel(const Veri
     int32_t count = 0;
     for (int c0 = 0; c0 < m; c0 += VERIFY_CHUNK) {
         const int n = min(VERIFY_CHUNK, m - c0);
-        for (int i = lane; i < n; i += VERIFY_HB) {
+        for (int i = lane; i < n; i += RANSAC_HB) {
             double xl, yl, xh, yh;
             load_match(t, matches, xy, c0 + i, xl, yl, xh, yh);
             lds[4 * i] = xl; lds[4 * i + 1] = yl; lds[4 * i + 2] = xh; lds[4 * i + 3] = yh;
@@ -124,43 +111,7 @@ __global__ __launch_bounds__(VERIFY_HB) void verify_hypothesis_kernel(const Veri
         __syncthreads();
     }
     if (!valid) count = -1;
-    if (diag_E && live) {
-#pragma unroll
-        for (int k = 0; k < 9; ++k) diag_E[9 * (int64_t)h + k] = E[k];
-        diag_count[h] = count;
-    }
-    const int64_t own = live ? verify_rank(count, h) : (int64_t)-1;
-    int64_t top = own;
-#pragma unroll
-    for (int w = 1; w < 64; w <<= 1) {
-        const int64_t o = __shfl_xor(top, w, 64);
-        top = o > top ? o : top;
-    }
-    if (live && own == top) { // one lane: h is part of the rank
-        VerifyBest &b = blk[blockIdx.x];
-        b.count = count; b.h = h;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) b.E[k] = E[k];
-    }
-}
-
-__global__ __launch_bounds__(256) void verify_pick_kernel(int n_tasks, const VerifyTask *__restrict__ tasks, const VerifyBest *__restrict__ blk,
-                                                          VerifyBest *__restrict__ res)
-{
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= n_tasks) return;
-    const VerifyTask &t = tasks[p];
-    int win = -1;
-    int64_t top = -1;
-    for (int k = 0; k < t.n_blk; ++k) {
-        const int64_t r = verify_rank(blk[t.blk0 + k].count, blk[t.blk0 + k].h);
-        if (r > top) { top = r; win = t.blk0 + k; }
-    }
-    VerifyBest b;
-    b.count = -1; b.h = -1;
-    verify_zero(b.E);
-    if (win >= 0 && blk[win].count >= 0) b = blk[win];
-    res[p] = b;
+    ransac_block_best<9>(ln, count, E, blk, diag_E, diag_count);
 }
 
 // E [P][9], status, n_inliers, best_h [P]: the pair's result after `rounds` refits
@@ -178,11 +129,11 @@ __global__ __launch_bounds__(REFINE_BLOCK) void verify_refine_kernel(const Verif
     __shared__ int s_ok;
     const int p = blockIdx.x, tid = threadIdx.x;
     const VerifyTask &t = tasks[p];
-    const int m = t.m;
+    const int m = t.span.m;
     const VerifyBest b = res[p];
     double E[9];
 #pragma unroll
-    for (int k = 0; k < 9; ++k) E[k] = b.E[k];
+    for (int k = 0; k < 9; ++k) E[k] = b.model[k];
     int32_t count = b.count;
     double R[9];
 #pragma unroll
@@ -256,50 +207,31 @@ __global__ __launch_bounds__(REFINE_BLOCK) void verify_refine_kernel(const Verif
         for (int k = 0; k < 9; ++k) E[k] = F[k];
     }
     if (tid != 0) return;
-    const int st = verify_status(m, verify_sample_size(METHOD), min_inliers, count);
-    status[p] = st;
+    status[p] = ransac_status(m, verify_sample_size(METHOD), min_inliers, count);
     n_inliers[p] = count > 0 ? count : 0;
     best_h[p] = b.h;
 #pragma unroll
     for (int k = 0; k < 9; ++k) E_out[9 * (int64_t)p + k] = E[k];
 }
 
-// flag [n + 1] (the last is 0): match i of the call is an inlier of its pair's E and the pair is OK
-__global__ __launch_bounds__(256) void verify_mask_kernel(int64_t n, int n_tasks, const VerifyTask *__restrict__ tasks,
-                                                          const int32_t *__restrict__ matches, const double *__restrict__ xy, double tau2,
-                                                          const double *__restrict__ E, const int32_t *__restrict__ status,
-                                                          uint32_t *__restrict__ flag)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i > n) return;
-    if (i == n) { flag[i] = 0; return; }
-    const int lo = segment_of([=](int k) { return tasks[k].m_off; }, n_tasks, i);
-    const VerifyTask &t = tasks[lo];
-    bool ok = status[lo] == VERIFY_OK;
-    if (ok) {
-        double xl, yl, xh, yh, e[9];
-        load_match(t, matches, xy, (int)(i - t.m_off), xl, yl, xh, yh);
-#pragma unroll
-        for (int k = 0; k < 9; ++k) e[k] = E[9 * (int64_t)lo + k];
-        ok = verify_inlier(e, xl, yl, xh, yh, tau2);
+// match i of the call, of pair j, is an inlier of E [j]
+struct VerifyInlier {
+    const int32_t *matches;
+    const double *xy, *E;
+    double tau2;
+    __device__ bool operator()(const VerifyTask &t, int j, int64_t i) const
+    {
+        double xl, yl, xh, yh;
+        load_match(t, matches, xy, (int)(i - t.span.off), xl, yl, xh, yh);
+        return verify_inlier(E + 9 * (int64_t)j, xl, yl, xh, yh, tau2);
     }
-    flag[i] = ok ? 1u : 0u;
-}
-
-// inliers [n_out][2] in (pair, original order), the caller's columns; off [n_tasks + 1]
-__global__ __launch_bounds__(256) void verify_write_kernel(int64_t n, int n_tasks, const VerifyTask *__restrict__ tasks,
-                                                           const int32_t *__restrict__ matches, const uint32_t *__restrict__ flag,
-                                                           const uint32_t *__restrict__ excl, int64_t n_out, int32_t *__restrict__ inliers,
-                                                           int64_t *__restrict__ off)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n_tasks) off[i] = excl[tasks[i].m_off];
-    if (i == n_tasks) off[i] = excl[n];
-    if (i >= n || !flag[i]) return;
-    const int64_t pos = excl[i];
-    if (pos >= n_out) return;
-    inliers[2 * pos] = matches[2 * i]; inliers[2 * pos + 1] = matches[2 * i + 1];
-}
+};
+// an inlier is its match, the caller's columns
+struct VerifyEmit {
+    static constexpr int WIDTH = 2;
+    const int32_t *matches;
+    __device__ void operator()(int32_t *out, int64_t pos, int64_t i) const { out[2 * pos] = matches[2 * i]; out[2 * pos + 1] = matches[2 * i + 1]; }
+};
 
 int32_t check_opts(const lvba_verify_s *v, const lvba_verify_opts *opts, lvba_verify_opts &o)
 {
@@ -327,41 +259,22 @@ int32_t make_task(const lvba_verify_s *v, int64_t a, int64_t b, int64_t m_off, i
                              matches[2 * i + 1], (long long)a, (long long)b, (long long)n_a, (long long)n_b);
     t = VerifyTask{};
     t.lo = (int32_t)std::min(a, b); t.hi = (int32_t)std::max(a, b); t.swap = a > b ? 1 : 0;
-    t.lo_off = v->kp.off[t.lo]; t.hi_off = v->kp.off[t.hi]; t.m_off = m_off; t.m = (int32_t)m;
+    t.lo_off = v->kp.off[t.lo]; t.hi_off = v->kp.off[t.hi]; t.span.off = m_off; t.span.m = (int32_t)m;
     if (method == VERIFY_KNOWN_ROTATION) verify_relative_rotation(&v->R[9 * (size_t)t.lo], &v->R[9 * (size_t)t.hi], t.R);
     return LVBA_OK;
 }
 
-// The hypotheses of every task with enough matches, one grid; blk0 / n_blk of the tasks are set here.  d_blk: the block records.
+// The hypotheses of every pair with enough matches (ransac_run_hypotheses).  diag_E, diag_count: null, or the diagnostic call's outputs.
 int32_t run_hypotheses(hipStream_t s, const lvba_verify_s *v, std::vector<VerifyTask> &tasks, const lvba_verify_opts &o, const int32_t *d_matches,
                        DevBuf &d_tasks, DevBuf &d_blk, double *diag_E, int32_t *diag_count)
 {
-    const int k = verify_sample_size(o.method), need = std::max(k, o.min_inliers);
-    std::vector<int2> tiles;
-    for (size_t p = 0; p < tasks.size(); ++p) {
-        tasks[p].blk0 = (int32_t)tiles.size();
-        if (tasks[p].m >= (diag_E ? k : need))
-            for (int h0 = 0; h0 < o.hypotheses; h0 += VERIFY_HB) tiles.push_back(make_int2((int)p, h0));
-        tasks[p].n_blk = (int32_t)tiles.size() - tasks[p].blk0;
-        if (tiles.size() > (size_t)INT32_MAX / 2) return lvba_fail(LVBA_ERR_UNSUPPORTED, "more than 2^30 hypothesis blocks in one call");
-    }
-    HIPCHK(d_tasks.alloc(sizeof(VerifyTask) * tasks.size()));
-    HIPCHK(lvba::copy_h2d(d_tasks.p, tasks.data(), sizeof(VerifyTask) * tasks.size()));
-    HIPCHK(d_blk.alloc(sizeof(VerifyBest) * tiles.size()));
-    if (tiles.empty()) return LVBA_OK;
-    DevBuf d_tiles(s);
-    HIPCHK(d_tiles.alloc(sizeof(int2) * tiles.size()));
-    HIPCHK(lvba::copy_h2d(d_tiles.p, tiles.data(), sizeof(int2) * tiles.size()));
+    const int k = verify_sample_size(o.method);
     const double tau2 = match_tau2(v->focal_sum, o.max_error_px);
-    if (o.method == VERIFY_EIGHT_POINT)
-        verify_hypothesis_kernel<VERIFY_EIGHT_POINT><<<(unsigned)tiles.size(), VERIFY_HB, 0, s>>>(
-            d_tasks.as<VerifyTask>(), d_tiles.as<int2>(), d_matches, v->kp.d_xy, o.seed, o.hypotheses, tau2, d_blk.as<VerifyBest>(), diag_E, diag_count);
-    else
-        verify_hypothesis_kernel<VERIFY_KNOWN_ROTATION><<<(unsigned)tiles.size(), VERIFY_HB, 0, s>>>(
-            d_tasks.as<VerifyTask>(), d_tiles.as<int2>(), d_matches, v->kp.d_xy, o.seed, o.hypotheses, tau2, d_blk.as<VerifyBest>(), diag_E, diag_count);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s)); // the tile list goes with this scope
-    return LVBA_OK;
+    const auto kernel = o.method == VERIFY_EIGHT_POINT ? verify_hypothesis_kernel<VERIFY_EIGHT_POINT> : verify_hypothesis_kernel<VERIFY_KNOWN_ROTATION>;
+    return ransac_run_hypotheses<9>(s, tasks, o.hypotheses, diag_E ? k : std::max(k, o.min_inliers), d_tasks, d_blk, [&](unsigned grid, const RansacTile *tiles) {
+        kernel<<<grid, RANSAC_HB, 0, s>>>(d_tasks.as<VerifyTask>(), tiles, d_matches, v->kp.d_xy, o.seed, o.hypotheses, tau2, d_blk.as<VerifyBest>(), diag_E,
+                                          diag_count);
+    });
 }
 
 } // namespace
@@ -417,7 +330,7 @@ extern "C" int32_t lvba_verify_pairs(lvba_verify_t v, int64_t n_pairs, const int
     if (n_pairs >= INT32_MAX / 2) return lvba_fail(LVBA_ERR_UNSUPPORTED, "%lld pairs in one call", (long long)n_pairs);
     TRY(check_offsets("match_off", "pair", n_pairs, match_off));
     const int64_t total = match_off[n_pairs];
-    if (total >= VERIFY_MAX_MATCHES) return lvba_fail(LVBA_ERR_UNSUPPORTED, "%lld matches in one call (below 2^31)", (long long)total);
+    if (total >= RANSAC_MAX_ELEMENTS) return lvba_fail(LVBA_ERR_UNSUPPORTED, "%lld matches in one call (below 2^31)", (long long)total);
     if (total > 0 && !matches) return lvba_fail(LVBA_ERR_ARG, "null matches");
     std::vector<VerifyTask> tasks((size_t)n_pairs);
     for (int64_t p = 0; p < n_pairs; ++p)
@@ -430,39 +343,20 @@ extern "C" int32_t lvba_verify_pairs(lvba_verify_t v, int64_t n_pairs, const int
     hipStream_t s = sg.s;
     const int np = (int)n_pairs;
     const double tau2 = match_tau2(v->focal_sum, o.max_error_px);
-    DevBuf d_m(s), d_tasks(s), d_blk(s), d_res(s), d_E(s), d_int(s), d_flag(s), d_excl(s), d_off(s), d_out(s);
+    DevBuf d_m(s), d_tasks(s), d_blk(s), d_res(s), d_E(s), d_int(s);
     HIPCHK(d_m.alloc(8 * (size_t)total));
     if (total > 0) HIPCHK(lvba::copy_h2d(d_m.p, matches, 8 * (size_t)total));
     TRY(run_hypotheses(s, v, tasks, o, d_m.as<int32_t>(), d_tasks, d_blk, nullptr, nullptr));
     HIPCHK(d_res.alloc(sizeof(VerifyBest) * (size_t)np)); HIPCHK(d_E.alloc(72 * (size_t)np)); HIPCHK(d_int.alloc(12 * (size_t)np));
-    HIPCHK(d_flag.alloc(4 * ((size_t)total + 1))); HIPCHK(d_excl.alloc(4 * ((size_t)total + 1))); HIPCHK(d_off.alloc(8 * ((size_t)np + 1)));
     int32_t *d_status = d_int.as<int32_t>(), *d_cnt = d_status + np, *d_h = d_cnt + np;
-    verify_pick_kernel<<<grid_for(np, 256), 256, 0, s>>>(np, d_tasks.as<VerifyTask>(), d_blk.as<VerifyBest>(), d_res.as<VerifyBest>());
+    ransac_pick_kernel<<<grid_for(np, 256), 256, 0, s>>>(np, d_tasks.as<VerifyTask>(), d_blk.as<VerifyBest>(), d_res.as<VerifyBest>());
     HIPCHK(hipGetLastError());
-    if (o.method == VERIFY_EIGHT_POINT)
-        verify_refine_kernel<VERIFY_EIGHT_POINT><<<(unsigned)np, REFINE_BLOCK, 0, s>>>(d_tasks.as<VerifyTask>(), d_m.as<int32_t>(), v->kp.d_xy, tau2,
-                                                                                      o.refine_rounds, o.min_inliers, d_res.as<VerifyBest>(),
-                                                                                      d_E.as<double>(), d_status, d_cnt, d_h);
-    else
-        verify_refine_kernel<VERIFY_KNOWN_ROTATION><<<(unsigned)np, REFINE_BLOCK, 0, s>>>(d_tasks.as<VerifyTask>(), d_m.as<int32_t>(), v->kp.d_xy, tau2,
-                                                                                         o.refine_rounds, o.min_inliers, d_res.as<VerifyBest>(),
-                                                                                         d_E.as<double>(), d_status, d_cnt, d_h);
+    const auto refine = o.method == VERIFY_EIGHT_POINT ? verify_refine_kernel<VERIFY_EIGHT_POINT> : verify_refine_kernel<VERIFY_KNOWN_ROTATION>;
+    refine<<<(unsigned)np, REFINE_BLOCK, 0, s>>>(d_tasks.as<VerifyTask>(), d_m.as<int32_t>(), v->kp.d_xy, tau2, o.refine_rounds, o.min_inliers,
+                                                 d_res.as<VerifyBest>(), d_E.as<double>(), d_status, d_cnt, d_h);
     HIPCHK(hipGetLastError());
-    verify_mask_kernel<<<grid_for(total + 1, 256), 256, 0, s>>>(total, np, d_tasks.as<VerifyTask>(), d_m.as<int32_t>(), v->kp.d_xy, tau2,
-                                                                d_E.as<double>(), d_status, d_flag.as<uint32_t>());
-    HIPCHK(hipGetLastError());
-    TRY(scan_excl<uint32_t>(s, d_flag.as<uint32_t>(), d_excl.as<uint32_t>(), (size_t)total + 1));
-    uint32_t found = 0;
-    HIPCHK(lvba::copy_d2h(&found, d_excl.as<uint32_t>() + total, 4));
-    const int64_t n_out = std::min<int64_t>(found, capacity);
-    HIPCHK(d_out.alloc(8 * (size_t)n_out));
-    verify_write_kernel<<<grid_for(std::max<int64_t>(total, np + 1), 256), 256, 0, s>>>(total, np, d_tasks.as<VerifyTask>(), d_m.as<int32_t>(),
-                                                                                       d_flag.as<uint32_t>(), d_excl.as<uint32_t>(), n_out,
-                                                                                       d_out.as<int32_t>(), d_off.as<int64_t>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(lvba::copy_d2h(inlier_off, d_off.p, 8 * ((size_t)np + 1)));
-    if (n_out > 0) HIPCHK(lvba::copy_d2h(inliers, d_out.p, 8 * (size_t)n_out));
+    TRY(ransac_inlier_lists(s, total, np, d_tasks.as<VerifyTask>(), d_status, VerifyInlier{d_m.as<int32_t>(), v->kp.d_xy, d_E.as<double>(), tau2},
+                            VerifyEmit{d_m.as<int32_t>()}, capacity, inlier_off, inliers));
     HIPCHK(lvba::copy_d2h(E, d_E.p, 72 * (size_t)np));
     HIPCHK(lvba::copy_d2h(status, d_status, 4 * (size_t)np));
     HIPCHK(lvba::copy_d2h(n_inliers, d_cnt, 4 * (size_t)np));
@@ -507,21 +401,9 @@ extern "C" int32_t lvba_verify_score(lvba_verify_t v, int32_t a, int32_t b, int6
     HIPCHK(hipSetDevice(v->kp.device));
     ScopedStream sg;
     HIPCHK(sg.acquire());
-    const size_t n = (size_t)n_matches;
-    DevBuf d_m(sg.s), d_tasks(sg.s), d_E(sg.s), d_st(sg.s), d_flag(sg.s);
-    HIPCHK(d_m.alloc(8 * n)); HIPCHK(d_tasks.alloc(sizeof(VerifyTask))); HIPCHK(d_E.alloc(72)); HIPCHK(d_st.alloc(4)); HIPCHK(d_flag.alloc(4 * (n + 1)));
-    const int32_t ok = VERIFY_OK;
-    HIPCHK(lvba::copy_h2d(d_m.p, matches, 8 * n));
-    HIPCHK(lvba::copy_h2d(d_tasks.p, tasks.data(), sizeof(VerifyTask)));
+    DevBuf d_m(sg.s), d_E(sg.s);
+    HIPCHK(d_m.alloc(8 * (size_t)n_matches)); HIPCHK(d_E.alloc(72));
+    HIPCHK(lvba::copy_h2d(d_m.p, matches, 8 * (size_t)n_matches));
     HIPCHK(lvba::copy_h2d(d_E.p, E, 72));
-    HIPCHK(lvba::copy_h2d(d_st.p, &ok, 4));
-    verify_mask_kernel<<<grid_for(n_matches + 1, 256), 256, 0, sg.s>>>(n_matches, 1, d_tasks.as<VerifyTask>(), d_m.as<int32_t>(), v->kp.d_xy,
-                                                                      match_tau2(v->focal_sum, max_error_px), d_E.as<double>(), d_st.as<int32_t>(),
-                                                                      d_flag.as<uint32_t>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(sg.s));
-    std::vector<uint32_t> flag(n);
-    HIPCHK(lvba::copy_d2h(flag.data(), d_flag.p, 4 * n));
-    for (size_t i = 0; i < n; ++i) mask[i] = flag[i] ? 1 : 0;
-    return LVBA_OK;
+    return ransac_score_mask(sg.s, tasks[0], VerifyInlier{d_m.as<int32_t>(), v->kp.d_xy, d_E.as<double>(), match_tau2(v->focal_sum, max_error_px)}, mask);
 }

@@ -1,7 +1,7 @@
-// verify_device.h -- scalar pieces of the two-view verification of putative matches (verify.hip; the rule is in include/lvba_hip.h,
-// DESIGN.md §10k): the counter-based generator, the sampler of k distinct indices, the two minimal solvers, the refits over the
-// inliers (cyclic Jacobi, projection onto the essential manifold) and the decision.  Host/device-neutral, like match_device.h,
-// whose gate it uses as it stands: a match is an inlier of E exactly where the guided matcher would pass it for the same E.
+// verify_device.h -- the two-view pieces of the verification of putative matches (verify.hip; the rule is in include/lvba_hip.h,
+// DESIGN.md §10k): the inlier test, the two minimal solvers and the refits over the inliers (cyclic Jacobi, projection onto the
+// essential manifold).  The generator, the sampler, the rank and the status are ransac_device.h'.  Host/device-neutral, like
+// match_device.h, whose gate it uses as it stands: a match is an inlier of E exactly where the guided matcher would pass it.
 // The solvers use +, -, *, / and sqrt only, in the order written here, and verify.hip is built without contraction: a hypothesis
 // is the same bits on the host and on the device.  The refits go through eig3 and long rotation chains and are held to a
 // measured tolerance instead.
@@ -10,61 +10,21 @@
 #include <stdint.h>
 #include "match_device.h"
 #include "balm_math.h"
+#include "ransac_device.h"
 
 namespace lvba {
 
 enum VerifyMethod : int { VERIFY_EIGHT_POINT = 0, VERIFY_KNOWN_ROTATION = 1 };                       // lvba_verify_opts::method
-enum VerifyStatus : int { VERIFY_OK = 0, VERIFY_TOO_FEW_MATCHES = 1, VERIFY_NO_MODEL = 2, VERIFY_TOO_FEW_INLIERS = 3 };
+constexpr int VERIFY_OK = RANSAC_OK, VERIFY_TOO_FEW_MATCHES = RANSAC_TOO_FEW_MATCHES, VERIFY_NO_MODEL = RANSAC_NO_MODEL,
+              VERIFY_TOO_FEW_INLIERS = RANSAC_TOO_FEW_INLIERS;
 // A pivot at or below this share of the system's largest entry is "no pivot".  The rounding of an eight-step elimination of
 // entries of order 1 is ~1e-15 and a usable sample's last pivot is above ~1e-6: five decades of room on either side.
 constexpr double VERIFY_PIVOT_REL = 1e-10;
 // |c1 x c2|^2 <= this |c1|^2 |c2|^2 (sin^2 of the angle between the two constraints): no direction.  As MATCH_BASELINE_REL2.
 constexpr double VERIFY_T_REL2 = 1e-20;
 constexpr int VERIFY_JACOBI_SWEEPS = 12;          // cyclic Jacobi on the 9 x 9 normal matrix: converged after 7 or 8 on every fixture
-constexpr uint64_t VERIFY_GOLDEN = 0x9E3779B97F4A7C15ull;
 
 LVBA_TRK_FN int verify_sample_size(int method) { return method == VERIFY_KNOWN_ROTATION ? 2 : 8; }
-
-// ---- the generator: a function of (seed, lo, hi, h, draw) alone ------------------------------------------------------------
-LVBA_TRK_FN uint64_t verify_mix(uint64_t z)        // splitmix64's finaliser
-{
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-LVBA_TRK_FN uint64_t verify_key(uint64_t seed, int32_t lo, int32_t hi, int32_t h)
-{
-    uint64_t k = verify_mix(seed + VERIFY_GOLDEN);
-    k = verify_mix(k ^ (((uint64_t)(uint32_t)lo << 32) | (uint64_t)(uint32_t)hi));
-    return verify_mix(k + VERIFY_GOLDEN * ((uint64_t)(uint32_t)h + 1));
-}
-LVBA_TRK_FN uint64_t verify_draw(uint64_t key, int j) { return verify_mix(key + VERIFY_GOLDEN * ((uint64_t)j + 1)); }
-LVBA_TRK_FN uint32_t verify_below(uint64_t r, uint32_t n)   // the high half of r n: r mapped onto [0, n)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return (uint32_t)__umul64hi(r, (uint64_t)n);
-#else
-    return (uint32_t)(((unsigned __int128)r * n) >> 64);
-#endif
-}
-// K distinct indices of [0, m), m >= K, in draw order: draw j is taken from [0, m - j) and stepped past the indices already
-// chosen, which `sorted` keeps in ascending order (a partial Fisher-Yates shuffle without its array).
-template <int K>
-LVBA_TRK_FN void verify_sample(uint64_t key, int32_t m, int32_t *idx)
-{
-    int32_t sorted[K];
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-        int32_t v = (int32_t)verify_below(verify_draw(key, j), (uint32_t)(m - j));
-#pragma unroll
-        for (int i = 0; i < j; ++i) v += v >= sorted[i] ? 1 : 0;
-        idx[j] = v;
-        sorted[j] = v;
-#pragma unroll
-        for (int i = j; i > 0; --i)
-            if (sorted[i - 1] > sorted[i]) { const int32_t s = sorted[i - 1]; sorted[i - 1] = sorted[i]; sorted[i] = s; }
-    }
-}
 
 // ---- the inlier test: the guided matcher's gate -------------------------------------------------------------------------------
 // p = (x_lo, y_lo, x_hi, y_hi); false when a NaN (failed undistortion) is in it
@@ -196,16 +156,6 @@ LVBA_TRK_FN bool verify_known_rotation(const double *p, const double *R, double 
     const double n1 = (c1[0] * c1[0] + c1[1] * c1[1]) + c1[2] * c1[2], n2 = (c2[0] * c2[0] + c2[1] * c2[1]) + c2[2] * c2[2];
     if (!(tt > VERIFY_T_REL2 * (n1 * n2))) { verify_zero(E); return false; }   // also when a NaN is in it
     return verify_essential_from(t, R, E);
-}
-
-// ---- the choice ------------------------------------------------------------------------------------------------------------------
-// The highest count wins, the lowest h among equals; an invalid hypothesis counts -1.  Integers only: no reduction order matters.
-LVBA_TRK_FN int64_t verify_rank(int32_t count, int32_t h) { return ((int64_t)(count + 1) << 32) | (int64_t)(uint32_t)(INT32_MAX - h); }
-LVBA_TRK_FN int verify_status(int32_t m, int32_t k, int32_t min_inliers, int32_t count)
-{
-    if (m < (k > min_inliers ? k : min_inliers)) return VERIFY_TOO_FEW_MATCHES;
-    if (count < 0) return VERIFY_NO_MODEL;
-    return count < min_inliers ? VERIFY_TOO_FEW_INLIERS : VERIFY_OK;
 }
 
 // ---- local refinement --------------------------------------------------------------------------------------------------------------

@@ -184,7 +184,26 @@ def main_ref_system():
     shutil.rmtree(os.path.dirname(root), ignore_errors=True)
 
 
+def main_ransac():
+    """What lvba_verify_pairs / lvba_verify_hypotheses and lvba_resect_images / lvba_resect_hypotheses return on the mixed batches
+    of tests/verify_cases.py and tests/resect_cases.py (tests/test_gpu_ransac.py collect()), from the library the package loads --
+    LVBA_HIP_LIB names another build.  ransac_parent.npz was recorded on an MI355X from a build of the commit before the two
+    stages' common skeleton moved into csrc/ransac_batch.h; needs a GPU, so it runs only when asked for:
+
+        LVBA_HIP_LIB=<that build's liblvba_hip.so> python tests/golden/make_golden.py ransac
+    """
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_gpu_ransac as T
+    out = T.collect()
+    np.savez_compressed(T.GOLDEN, **out)
+    print("ransac_parent", len(out), "arrays,", sum(a.nbytes for a in out.values()), "bytes from",
+          importlib.import_module("global-lvba_amd._lib").LIB_PATH)
+
+
 if __name__ == "__main__":
+    if "ransac" in sys.argv[1:]:
+        main_ransac()
+        sys.exit(0)
     main()
     main_visual()
     main_voxel()

@@ -21,7 +21,7 @@ from match_cases import _rot
 
 MIN_MARGIN = 1e-9
 CHUNK = 1024                      # resect.hip's RESECT_CHUNK
-HB = 64                           # resect.hip's RESECT_HB
+HB = 64                           # ransac_batch.h's RANSAC_HB
 SIZES = (0, 3, 4, 5, 29, 30, 31, 63, 64, 65, CHUNK - 1, CHUNK, CHUNK + 1)
 H_SMALL = 200                     # not a multiple of HB: the last block of a job is partly idle
 H_EDGES = (1, 63, 64, 65)

@@ -1,6 +1,6 @@
 // resect_check.cpp -- csrc/resect_device.h compiled for the host (tests/test_resect_host.py): the hypotheses of one job formed the
-// way resect_hypothesis_kernel forms them -- the sampler of verify_device.h keyed on (seed, id, -1, h), the minimal solver, the
-// inlier test, one hypothesis after the other -- the choice, and the refinement rounds with their sums taken in correspondence
+// way resect_hypothesis_kernel forms them -- the sampler of ransac_device.h keyed on (seed, id, -1, h), the minimal solver, the
+// inlier test, one hypothesis after the other -- ransac_device.h' choice, and the refinement rounds with their sums taken in correspondence
 // order.  TEST INFRASTRUCTURE ONLY.
 #include <cstdint>
 #include <vector>
@@ -19,7 +19,7 @@ void emul_pack(int32_t m, const double *xy, const double *world, double *rec)
 // idx [H][4]
 void emul_sample(uint64_t seed, int32_t id, int32_t H, int32_t m, int32_t *idx)
 {
-    for (int h = 0; h < H; ++h) verify_sample<RESECT_K>(verify_key(seed, id, -1, h), m, idx + RESECT_K * (int64_t)h);
+    for (int h = 0; h < H; ++h) ransac_sample<RESECT_K>(ransac_key(seed, id, -1, h), m, idx + RESECT_K * (int64_t)h);
 }
 
 // the minimal solver on four records given directly; returns 1 and (R, t), or 0
@@ -40,11 +40,9 @@ void emul_score(int32_t m, const double *rec, const double *R, const double *t, 
 int32_t emul_hypotheses(uint64_t seed, int32_t id, int32_t H, int32_t m, const double *rec, double fx, double fy, double rho, double *R, double *t,
                         int32_t *count)
 {
-    int64_t top = -1;
-    int32_t win = -1;
     for (int h = 0; h < H; ++h) {
         int32_t idx[RESECT_K];
-        verify_sample<RESECT_K>(verify_key(seed, id, -1, h), m, idx);
+        ransac_sample<RESECT_K>(ransac_key(seed, id, -1, h), m, idx);
         double *r = R + 9 * (int64_t)h, *tt = t + 3 * (int64_t)h;
         const bool valid = resect_p3p(rec + RESECT_REC * (int64_t)idx[0], rec + RESECT_REC * (int64_t)idx[1], rec + RESECT_REC * (int64_t)idx[2],
                                       rec + RESECT_REC * (int64_t)idx[3], fx, fy, r, tt);
@@ -54,10 +52,8 @@ int32_t emul_hypotheses(uint64_t seed, int32_t id, int32_t H, int32_t m, const d
             c += resect_inlier(r, tt, fx, fy, rho, p[0], p[1], p[2], p[3], p[4]) ? 1 : 0;
         }
         count[h] = valid ? c : -1;
-        const int64_t rk = verify_rank(count[h], h);
-        if (rk > top) { top = rk; win = h; }
     }
-    return win >= 0 && count[win] >= 0 ? win : -1;
+    return ransac_winner(H, [=](int32_t h) { return count[h]; }, [](int32_t h) { return h; });
 }
 
 static int32_t count_inliers(int32_t m, const double *rec, const double *R, const double *t, double fx, double fy, double rho)
@@ -121,6 +117,6 @@ int32_t emul_refine(int32_t m, const double *rec, double fx, double fy, double r
     return count;
 }
 
-int32_t emul_status(int32_t m, int32_t min_inliers, int32_t count) { return resect_status(m, min_inliers, count); }
+int32_t emul_status(int32_t m, int32_t min_inliers, int32_t count) { return ransac_status(m, RESECT_K, min_inliers, count); }
 
 } // extern "C"

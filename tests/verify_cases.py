@@ -17,7 +17,7 @@ from match_cases import _rot
 
 MIN_MARGIN = 1e-9
 CHUNK = 1024                      # verify.hip's VERIFY_CHUNK
-HB = 64                           # verify.hip's VERIFY_HB
+HB = 64                           # ransac_batch.h's RANSAC_HB
 SIZES0 = (0, 7, 8, 9, 63, 64, 65, CHUNK - 1, CHUNK, CHUNK + 1)
 SIZES1 = (0, 1, 2, 3, 63, 64, 65, CHUNK - 1, CHUNK, CHUNK + 1)
 H_SMALL = 200                     # not a multiple of HB: the last block of a pair is partly idle

@@ -1,6 +1,6 @@
 // verify_check.cpp -- csrc/verify_device.h compiled for the host (tests/test_verify_host.py): the hypotheses of one pair formed the
-// way verify_hypothesis_kernel forms them -- the header's generator, sampler, solvers and gate, one hypothesis after the other --
-// the choice, and the refits with their sums taken in match order.  TEST INFRASTRUCTURE ONLY.
+// way verify_hypothesis_kernel forms them -- ransac_device.h' generator and sampler, the header's solvers and gate, one hypothesis
+// after the other -- ransac_device.h' choice, and the refits with their sums taken in match order.  TEST INFRASTRUCTURE ONLY.
 #include <cstdint>
 #include <vector>
 #include "../global-lvba_amd/csrc/verify_device.h"
@@ -13,9 +13,9 @@ extern "C" {
 void emul_sample(uint64_t seed, int32_t lo, int32_t hi, int32_t H, int32_t m, int32_t k, int32_t *idx)
 {
     for (int h = 0; h < H; ++h) {
-        const uint64_t key = verify_key(seed, lo, hi, h);
-        if (k == 8) verify_sample<8>(key, m, idx + 8 * (int64_t)h);
-        else verify_sample<2>(key, m, idx + 2 * (int64_t)h);
+        const uint64_t key = ransac_key(seed, lo, hi, h);
+        if (k == 8) ransac_sample<8>(key, m, idx + 8 * (int64_t)h);
+        else ransac_sample<2>(key, m, idx + 2 * (int64_t)h);
     }
 }
 
@@ -32,7 +32,7 @@ static bool hypothesis(int method, uint64_t key, int32_t m, const double *P, con
     if (method == VERIFY_EIGHT_POINT) {
         int32_t idx[8];
         double A[72];
-        verify_sample<8>(key, m, idx);
+        ransac_sample<8>(key, m, idx);
         bool clean = true;
         for (int j = 0; j < 8; ++j) {
             const double *p = P + 4 * (int64_t)idx[j];
@@ -43,7 +43,7 @@ static bool hypothesis(int method, uint64_t key, int32_t m, const double *P, con
     }
     int32_t idx[2];
     double p[8];
-    verify_sample<2>(key, m, idx);
+    ransac_sample<2>(key, m, idx);
     for (int j = 0; j < 2; ++j)
         for (int c = 0; c < 4; ++c) p[4 * j + c] = P[4 * (int64_t)idx[j] + c];
     return verify_known_rotation(p, R, E);
@@ -53,18 +53,14 @@ static bool hypothesis(int method, uint64_t key, int32_t m, const double *P, con
 int32_t emul_hypotheses(int32_t method, uint64_t seed, int32_t lo, int32_t hi, int32_t H, int32_t m, const double *P, const double *R,
                         double tau2, double *E, int32_t *count)
 {
-    int64_t top = -1;
-    int32_t win = -1;
     for (int h = 0; h < H; ++h) {
         double *e = E + 9 * (int64_t)h;
-        const bool valid = hypothesis(method, verify_key(seed, lo, hi, h), m, P, R, e);
+        const bool valid = hypothesis(method, ransac_key(seed, lo, hi, h), m, P, R, e);
         int32_t c = 0;
         for (int i = 0; i < m; ++i) c += verify_inlier(e, P[4 * i], P[4 * i + 1], P[4 * i + 2], P[4 * i + 3], tau2) ? 1 : 0;
         count[h] = valid ? c : -1;
-        const int64_t r = verify_rank(count[h], h);
-        if (r > top) { top = r; win = h; }
     }
-    return win >= 0 && count[win] >= 0 ? win : -1;
+    return ransac_winner(H, [=](int32_t h) { return count[h]; }, [](int32_t h) { return h; });
 }
 
 // one refit of E over its inliers; returns 1 and the refit in F, or 0
@@ -95,7 +91,7 @@ int32_t emul_refit(int32_t method, int32_t m, const double *P, const double *R, 
 
 int32_t emul_status(int32_t m, int32_t method, int32_t min_inliers, int32_t count)
 {
-    return verify_status(m, verify_sample_size(method), min_inliers, count);
+    return ransac_status(m, verify_sample_size(method), min_inliers, count);
 }
 
 } // extern "C"
