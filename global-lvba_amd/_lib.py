@@ -41,7 +41,7 @@ SYMBOLS = [
     "lvba_covis_default_opts", "lvba_covis_samples", "lvba_covis_counts", "lvba_covis_pairs",
     "lvba_trackgraph_create", "lvba_trackgraph_components", "lvba_trackgraph_orders", "lvba_trackgraph_destroy",
     "lvba_verify_default_opts", "lvba_verify_create", "lvba_verify_destroy", "lvba_verify_pairs", "lvba_verify_hypotheses",
-    "lvba_verify_score",
+    "lvba_verify_score", "lvba_verify_pairs_model", "lvba_verify_hypotheses_homography", "lvba_verify_score_homography",
     "lvba_sift_default_opts", "lvba_sift_tile_width", "lvba_sift_blur_taps", "lvba_sift_extract", "lvba_sift_profile", "lvba_sift_pyramid",
     "lvba_sift_candidates",
     "lvba_resect_default_opts", "lvba_resect_images", "lvba_resect_hypotheses", "lvba_resect_score", "lvba_resect_lift",
@@ -549,6 +549,10 @@ def load():
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.lvba_verify_hypotheses.argtypes = [H, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(VerifyOpts), C.c_void_p, C.c_void_p]
     lib.lvba_verify_score.argtypes = [H, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
+    lib.lvba_verify_pairs_model.argtypes = [H, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(VerifyOpts), C.c_int32, C.c_double,
+                                            C.c_int64] + [C.c_void_p] * 9
+    lib.lvba_verify_hypotheses_homography.argtypes = lib.lvba_verify_hypotheses.argtypes
+    lib.lvba_verify_score_homography.argtypes = lib.lvba_verify_score.argtypes
     lib.lvba_sift_default_opts.argtypes = [C.POINTER(SiftOpts)]
     lib.lvba_sift_default_opts.restype = None
     lib.lvba_sift_tile_width.argtypes = []

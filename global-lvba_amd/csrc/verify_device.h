@@ -1,7 +1,7 @@
 // verify_device.h -- the two-view pieces of the verification of putative matches (verify.hip; the rule is in include/lvba_hip.h,
-// DESIGN.md §10k): the inlier test, the two minimal solvers and the refits over the inliers (cyclic Jacobi, projection onto the
-// essential manifold).  The generator, the sampler, the rank and the status are ransac_device.h'.  Host/device-neutral, like
-// match_device.h, whose gate it uses as it stands: a match is an inlier of E exactly where the guided matcher would pass it.
+// DESIGN.md §10k): the inlier tests, the minimal solvers (eight points, two points with the rotation, four points for the
+// homography) and the refits over the inliers (cyclic Jacobi, projection onto the essential manifold).  The generator, the
+// sampler, the rank and the status are ransac_device.h'.  Host/device-neutral, like match_device.h, whose gate it uses as it stands: a match is an inlier of E exactly where the guided matcher would pass it.
 // The solvers use +, -, *, / and sqrt only, in the order written here, and verify.hip is built without contraction: a hypothesis
 // is the same bits on the host and on the device.  The refits go through eig3 and long rotation chains and are held to a
 // measured tolerance instead.
@@ -15,6 +15,11 @@
 namespace lvba {
 
 enum VerifyMethod : int { VERIFY_EIGHT_POINT = 0, VERIFY_KNOWN_ROTATION = 1 };                       // lvba_verify_opts::method
+// The homography is no lvba_verify_opts::method (lvba_verify_pairs refuses 2): it is what the kernels of verify.hip are
+// instantiated with for LVBA_VERIFY_MODEL_HOMOGRAPHY.
+constexpr int VERIFY_HOMOGRAPHY = 2;
+enum VerifyModel : int { VERIFY_MODEL_ESSENTIAL = 0, VERIFY_MODEL_HOMOGRAPHY = 1, VERIFY_MODEL_AUTO = 2 };   // lvba_verify_pairs_model
+constexpr double VERIFY_PLANAR_RATIO = 0.8;       // the default of planar_ratio: COLMAP's max_H_inlier_ratio
 constexpr int VERIFY_OK = RANSAC_OK, VERIFY_TOO_FEW_MATCHES = RANSAC_TOO_FEW_MATCHES, VERIFY_NO_MODEL = RANSAC_NO_MODEL,
               VERIFY_TOO_FEW_INLIERS = RANSAC_TOO_FEW_INLIERS;
 // A pivot at or below this share of the system's largest entry is "no pivot".  The rounding of an eight-step elimination of
@@ -24,7 +29,14 @@ constexpr double VERIFY_PIVOT_REL = 1e-10;
 constexpr double VERIFY_T_REL2 = 1e-20;
 constexpr int VERIFY_JACOBI_SWEEPS = 12;          // cyclic Jacobi on the 9 x 9 normal matrix: converged after 7 or 8 on every fixture
 
-LVBA_TRK_FN int verify_sample_size(int method) { return method == VERIFY_KNOWN_ROTATION ? 2 : 8; }
+LVBA_TRK_FN int verify_sample_size(int method) { return method == VERIFY_KNOWN_ROTATION ? 2 : method == VERIFY_HOMOGRAPHY ? 4 : 8; }
+// The E-or-H choice of one pair from its two finished runs: HOMOGRAPHY iff the H run is OK and either the E run is not, or
+// n_H >= planar_ratio n_E in fp64.
+LVBA_TRK_FN int verify_choose_model(int status_E, int32_t n_E, int status_H, int32_t n_H, double planar_ratio)
+{
+    return status_H == RANSAC_OK && (status_E != RANSAC_OK || (double)n_H >= planar_ratio * (double)n_E) ? VERIFY_MODEL_HOMOGRAPHY
+                                                                                                           : VERIFY_MODEL_ESSENTIAL;
+}
 
 // ---- the inlier test: the guided matcher's gate -------------------------------------------------------------------------------
 // p = (x_lo, y_lo, x_hi, y_hi); false when a NaN (failed undistortion) is in it
@@ -158,6 +170,70 @@ LVBA_TRK_FN bool verify_known_rotation(const double *p, const double *R, double 
     return verify_essential_from(t, R, E);
 }
 
+// ---- the homography: four points, no pose, for a scene that is one plane ------------------------------------------------------
+// H maps lo to hi, p = H x^_lo ~ x^_hi.  Sample point i fills rows 2 i and 2 i + 1 of the 8 x 9 system of verify_eight_solve
+// (same layout, same st): p0 - x_hi p2 = 0 and p1 - y_hi p2 = 0.  Returns false when the point holds a NaN.
+LVBA_TRK_FN bool verify_homography_rows(double *A, int st, int i, double xl, double yl, double xh, double yh)
+{
+    double *a = A + 18 * i * st, *b = a + 9 * st;
+    a[0] = xl; a[st] = yl; a[2 * st] = 1.0; a[3 * st] = 0.0; a[4 * st] = 0.0; a[5 * st] = 0.0;
+    a[6 * st] = -xh * xl; a[7 * st] = -xh * yl; a[8 * st] = -xh;
+    b[0] = 0.0; b[st] = 0.0; b[2 * st] = 0.0; b[3 * st] = xl; b[4 * st] = yl; b[5 * st] = 1.0;
+    b[6 * st] = -yh * xl; b[7 * st] = -yh * yl; b[8 * st] = -yh;
+    return xl == xl && yl == yl && xh == xh && yh == yh;
+}
+// The sign of H: negated if the third coordinate of H x^_lo is negative at (xl, yl), the first sample point.  false (H = 0)
+// when it is zero or a NaN there.
+LVBA_TRK_FN bool verify_homography_sign(double *H, double xl, double yl)
+{
+    const double p2 = (H[6] * xl + H[7] * yl) + H[8];
+    if (!(p2 > 0.0) && !(p2 < 0.0)) { verify_zero(H); return false; }
+    if (p2 < 0.0) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) H[k] = -H[k];
+    }
+    return true;
+}
+// G = adj(H), negated if det H < 0: a positive multiple of H^-1.  det H = (H0 G0 + H1 G3) + H2 G6, the first row of H on the
+// first column of adj(H).  false (G = 0) when det H is zero or not finite.
+LVBA_TRK_FN bool verify_homography_inverse(const double *H, double *G)
+{
+    G[0] = H[4] * H[8] - H[5] * H[7]; G[1] = H[2] * H[7] - H[1] * H[8]; G[2] = H[1] * H[5] - H[2] * H[4];
+    G[3] = H[5] * H[6] - H[3] * H[8]; G[4] = H[0] * H[8] - H[2] * H[6]; G[5] = H[2] * H[3] - H[0] * H[5];
+    G[6] = H[3] * H[7] - H[4] * H[6]; G[7] = H[1] * H[6] - H[0] * H[7]; G[8] = H[0] * H[4] - H[1] * H[3];
+    const double det = (H[0] * G[0] + H[1] * G[3]) + H[2] * G[6];
+    if (!isfinite(det) || det == 0.0) { verify_zero(G); return false; }
+    if (det < 0.0) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) G[k] = -G[k];
+    }
+    return true;
+}
+// one direction of the transfer test: x^ = (x, y, 1) carried by M lands within tau of (u, v), in front of the camera
+LVBA_TRK_FN bool verify_transfer(const double *M, double x, double y, double u, double v, double tau2)
+{
+    const double p0 = (M[0] * x + M[1] * y) + M[2], p1 = (M[3] * x + M[4] * y) + M[5], p2 = (M[6] * x + M[7] * y) + M[8];
+    const double d0 = p0 - u * p2, d1 = p1 - v * p2;
+    const bool near = d0 * d0 + d1 * d1 <= tau2 * (p2 * p2), front = p2 > 0.0;
+    return near & front;            // no branch: the scoring loop stays one block
+}
+// the symmetric transfer test: lo carried to hi by H and hi carried to lo by G, both within tau; false when a NaN is in it
+LVBA_TRK_FN bool verify_inlier_h(const double *H, const double *G, double xl, double yl, double xh, double yh, double tau2)
+{
+    const bool there = verify_transfer(H, xl, yl, xh, yh, tau2), back = verify_transfer(G, xh, yh, xl, yl, tau2);
+    return there & back;
+}
+// H and G of the four sample points whose rows are in A (verify_homography_rows); (xl, yl) is the first of them.
+// false: invalid, H = G = 0.
+LVBA_TRK_FN bool verify_homography_solve(double *A, int st, double xl, double yl, double *H, double *G)
+{
+    verify_zero(G);
+    if (!verify_eight_solve(A, st, H)) return false;
+    if (!verify_homography_sign(H, xl, yl)) return false;
+    if (!verify_homography_inverse(H, G)) { verify_zero(H); return false; }
+    return true;
+}
+
 // ---- local refinement --------------------------------------------------------------------------------------------------------------
 // Cyclic Jacobi on the symmetric n x n matrix A (full storage, row-major; plain memory, LDS on the device, so that p and q may
 // be run-time indices): VERIFY_JACOBI_SWEEPS sweeps over (p, q), p < q, in row order, tracks_device.h' rotation with IEEE
@@ -243,6 +319,34 @@ LVBA_TRK_FN bool verify_refit_rotation(const double *C, const double *R, double 
     const double t[3] = {U[0], U[3], U[6]};
     if (!verify_essential_from(t, R, F)) return false;
     for (int r = 0; r < 9; ++r) E[r] = F[r];
+    return true;
+}
+// The two rows of one match in the homography's system, as verify_homography_rows writes them.
+LVBA_TRK_FN void verify_homography_row_pair(double xl, double yl, double xh, double yh, double *r1, double *r2)
+{
+    r1[0] = xl; r1[1] = yl; r1[2] = 1.0; r1[3] = 0.0; r1[4] = 0.0; r1[5] = 0.0; r1[6] = -xh * xl; r1[7] = -xh * yl; r1[8] = -xh;
+    r2[0] = 0.0; r2[1] = 0.0; r2[2] = 0.0; r2[3] = xl; r2[4] = yl; r2[5] = 1.0; r2[6] = -yh * xl; r2[7] = -yh * yl; r2[8] = -yh;
+}
+// The refit of the homography: N = sum (r1 r1^T + r2 r2^T) over the inliers (9 x 9, full storage; destroyed), V [81] workspace.
+// H = the eigenvector of N's smallest eigenvalue (the lowest column of a tie), unit norm, negated if its inner product with the
+// current H is negative; not projected.  G = its inverse direction.  false: no refit, H and G untouched.
+LVBA_TRK_FN bool verify_refit_homography(double *N, double *V, double *H, double *G)
+{
+    verify_jacobi(N, V, 9);
+    int mn = 0;
+    for (int c = 1; c < 9; ++c)
+        if (N[10 * c] < N[10 * mn]) mn = c;
+    double F[9], Gn[9];
+    for (int r = 0; r < 9; ++r) F[r] = V[9 * r + mn];
+    for (int r = 0; r < 9; ++r)
+        if (!isfinite(F[r])) return false;
+    if (!verify_unit(F)) return false;
+    double dot = F[0] * H[0];
+    for (int r = 1; r < 9; ++r) dot = dot + F[r] * H[r];
+    if (dot < 0.0)
+        for (int r = 0; r < 9; ++r) F[r] = -F[r];
+    if (!verify_homography_inverse(F, Gn)) return false;
+    for (int r = 0; r < 9; ++r) { H[r] = F[r]; G[r] = Gn[r]; }
     return true;
 }
 

@@ -697,9 +697,12 @@ def verify_image_pairs(keypoints, pairs, matches, intr, Rcw=None, device=0, **op
     on the GPU, all pairs in one grid, and the matches that agree with it.  matches: one [m, 2] array per pair, as
     match_image_pairs returns them.  Without Rcw the pose-free eight-point method (method=0; degenerate where the scene is one
     plane); with Rcw [M, 3, 3] (T_cam<-world rotations) and method=1 the rotation-aided two-point method, which trusts the relative
-    rotation and nothing else.  opts: method, hypotheses, refine_rounds, min_inliers, max_error_px, seed.  Returns
-    (inlier_matches, report): one int32 [m, 2] array per pair in the order of `pairs` -- empty for a pair that fails, which is not
-    dropped -- and a dict of arrays E, status, n_inliers, n_matches, best_h."""
+    rotation and nothing else.  opts: method, hypotheses, refine_rounds, min_inliers, max_error_px, seed, and model =
+    "essential" (the default: the call as it was) | "homography" (four-point homography with a symmetric transfer test, the model
+    of a scene that is one plane) | "auto" (both, per pair the homography where its count reaches planar_ratio, default 0.8, of
+    the essential matrix's).  Returns (inlier_matches, report): one int32 [m, 2] array per pair in the order of `pairs` -- empty
+    for a pair that fails, which is not dropped -- and a dict of arrays E, status, n_inliers, n_matches, best_h, and with a model
+    other than "essential" kind, n_inliers_E, n_inliers_H."""
     from . import verify as VF
     return VF.verify_pairs(keypoints, pairs, matches, intr, Rcw=Rcw, device=device, **opts)
 
@@ -841,7 +844,8 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
     pair that fails keeps its place with no matches).  Here the method defaults to 1, the rotation-aided one: the rotations are
     those of camera_from_imu of the camera poses in force at that point (the LiDAR-derived ones), and the scenes a LiDAR sees are
     mostly walls and floors, where the pose-free eight-point method (method=0, which uses no pose at all) is degenerate.  The output holds pairs / matches as used and match_verification: per pair
-    the status and the counts, plus the totals.
+    the status and the counts, plus the totals.  dict(model="auto") or dict(model="homography") (verify_image_pairs) adds each
+    pair's model and the two models' counts to it, and n_pairs_planar; without `model` none of these fields appear.
     remove_dynamic: None (off: nothing is launched), True, or a dict of dynamic.dynamic_labels' options: after the LiDAR stage the
     points that other frames saw through at the refined poses -- whatever moved while the data was recorded -- are labelled
     (pipeline.remove_dynamic) and the coloured maps and the map quality are made from the static scans, `before` as well as `after`,

@@ -1328,7 +1328,42 @@ int32_t lvba_trackgraph_destroy(lvba_trackgraph_t g);
  *   lvba_verify_score: mask [n_matches] (0 / 1) of the inlier test under a given E (lo -> hi).
  *   LVBA_ERR_ARG: method 1 on a handle without rotations, a == b or an image out of range, a match index outside its image,
  *   hypotheses < 1, a null required pointer or an option out of range.  lvba_version() is unchanged; a client detects these calls
- *   by looking lvba_verify_create up. */
+ *   by looking lvba_verify_create up.
+ *
+ *   The homography model and the E-or-H choice (opt-in; lvba_verify_pairs_model, lvba_verify_hypotheses_homography,
+ *   lvba_verify_score_homography; the calls above are untouched and lvba_verify_opts::method takes 0 and 1 only).  On a scene that
+ *   is one plane a family of essential matrices takes every true match in and RANSAC picks the member that scoops up the most wrong
+ *   ones; a point-to-line test cannot tell.  The model for a plane is point-to-point.  This rule, too, is the project's own
+ *   (tests/verify_h_oracle.py) and is NOT pinned against COLMAP.
+ *   Model.  H maps lo to hi in undistorted normalised coordinates: p = H x^_lo ~ x^_hi.
+ *   Sample and system.  k = 4, the sampler and key above.  Sample point i fills rows 2 i and 2 i + 1 of an 8 x 9 system:
+ *     (x_l, y_l, 1, 0, 0, 0, -x_h x_l, -x_h y_l, -x_h) and (0, 0, 0, x_l, y_l, 1, -y_h x_l, -y_h y_l, -y_h).
+ *   Solve.  vec(H) is the null vector by verify_eight_solve as it stands: the pivot order, VERIFY_PIVOT_REL and the unit Frobenius
+ *     norm of method 0.  Three collinear sample points lose a pivot: INVALID, as is a NaN sample point.
+ *   Sign.  H is negated if p2 < 0 at the first sample point; p2 == 0 there is INVALID.
+ *   Inverse direction.  G = adj(H), negated if det H < 0: a positive multiple of H^-1.  det H = (H0 G0 + H1 G3) + H2 G6 (the first
+ *     row of H on the first column of adj(H)) must be finite and non-zero, else INVALID.  +, -, *, / and sqrt only, each sum in
+ *     the order of verify_homography_inverse: a hypothesis is the same bits under g++, numpy and gfx950.
+ *   Inlier test.  tau as above.  Match i is an inlier iff (p0 - x_h p2)^2 + (p1 - y_h p2)^2 <= tau^2 p2^2 and p2 > 0 with
+ *     p = H x^_lo, and (q0 - x_l q2)^2 + (q1 - y_l q2)^2 <= tau^2 q2^2 and q2 > 0 with q = G x^_hi.  A NaN point fails.
+ *   Choice, status.  As above, with k = 4.
+ *   Local refinement.  N = sum (r1 r1^T + r2 r2^T) over the inliers, r1 and r2 the match's two rows; the eigenvector of its
+ *     smallest eigenvalue by the same Jacobi (the lowest column of a tie), unit norm, negated if its Frobenius inner product with
+ *     the current H is negative; no projection; G from it as above (no G: no refit).  Kept only if strictly more inliers.
+ *   E-or-H choice, LVBA_VERIFY_MODEL_AUTO.  Each pair is run to completion under E (o->method, 0 or 1) and under H.  The pair is
+ *     HOMOGRAPHY iff the H run is OK and either the E run is not OK or (double)n_H >= planar_ratio * (double)n_E; otherwise
+ *     ESSENTIAL.  Every output of the pair is the chosen run's, byte for byte.  planar_ratio: finite and > 0;
+ *     LVBA_VERIFY_PLANAR_RATIO (0.8, the value of COLMAP's max_H_inlier_ratio) sits in the middle of the gap the fixtures show
+ *     between a plane (>= 0.89) and general position (<= 0.28).
+ *   lvba_verify_pairs_model: lvba_verify_pairs with `model`; M [n_pairs][9] is E or H by kind [n_pairs] (LVBA_VERIFY_MODEL_ESSENTIAL
+ *   or _HOMOGRAPHY).  n_inliers_E, n_inliers_H [n_pairs], either may be NULL: the inlier count of that model's run of the pair, -1
+ *   where the model was not run.  LVBA_VERIFY_MODEL_ESSENTIAL gives the bytes of lvba_verify_pairs.  Under _HOMOGRAPHY o->method is
+ *   not read.  AUTO adds no kernel: two runs, the decision on the host.
+ *   lvba_verify_hypotheses_homography: the diagnostic call, H [hypotheses][9] and count; reads hypotheses, max_error_px, seed.
+ *   lvba_verify_score_homography: the mask of the inlier test under a given H (lo -> hi); all 0 where det H is 0 or not finite.
+ *   LVBA_ERR_ARG: an unknown model, a planar_ratio that is not finite or not > 0, and the refusals above.  lvba_version() is
+ *   unchanged; a client detects these calls by looking lvba_verify_pairs_model up.
+ *   Not built: several planes per pair (peeling the inliers and repeating), a pose from H, a path in lvba_adapter.hpp. */
 #define LVBA_VERIFY_EIGHT_POINT 0
 #define LVBA_VERIFY_KNOWN_ROTATION 1
 #define LVBA_VERIFY_OK 0
@@ -1355,6 +1390,18 @@ int32_t lvba_verify_hypotheses(lvba_verify_t v, int32_t a, int32_t b, int64_t n_
                                const lvba_verify_opts *o, double *E, int32_t *count);
 int32_t lvba_verify_score(lvba_verify_t v, int32_t a, int32_t b, int64_t n_matches, const int32_t *matches, const double *E,
                           double max_error_px, uint8_t *mask);
+#define LVBA_VERIFY_MODEL_ESSENTIAL 0
+#define LVBA_VERIFY_MODEL_HOMOGRAPHY 1
+#define LVBA_VERIFY_MODEL_AUTO 2
+#define LVBA_VERIFY_PLANAR_RATIO 0.8
+int32_t lvba_verify_pairs_model(lvba_verify_t v, int64_t n_pairs, const int32_t *pairs, const int64_t *match_off, const int32_t *matches,
+                                const lvba_verify_opts *o, int32_t model, double planar_ratio, int64_t capacity, int64_t *inlier_off,
+                                int32_t *inliers, double *M, int32_t *kind, int32_t *status, int32_t *n_inliers, int32_t *best_h,
+                                int32_t *n_inliers_E_or_null, int32_t *n_inliers_H_or_null);
+int32_t lvba_verify_hypotheses_homography(lvba_verify_t v, int32_t a, int32_t b, int64_t n_matches, const int32_t *matches,
+                                          const lvba_verify_opts *o, double *Hm, int32_t *count);
+int32_t lvba_verify_score_homography(lvba_verify_t v, int32_t a, int32_t b, int64_t n_matches, const int32_t *matches, const double *Hm,
+                                     double max_error_px, uint8_t *mask);
 
 /* ---- SIFT key points and descriptors of a batch of images (opt-in)
  *   The reference extracts its features with SiftGPU, "-fo -1 -loweo -w 3 -t 0.01 -e 12" (extractAndMatchFeaturesGPU,

@@ -1,9 +1,9 @@
-"""Times lvba_verify_pairs: 10^3 and 10^4 image pairs at 100, 500 and 2 000 putative matches each, both methods,
-1024 hypotheses, best of 3 with the host clock around the call (upload, all kernels and download included).  For context, the
+"""Times lvba_verify_pairs and lvba_verify_pairs_model: 10^3 and 10^4 image pairs at 100, 500 and 2 000 putative
+matches each, both methods, the homography and the E-or-H choice (over method 0), 1024 hypotheses, best of 3 with the host clock around the call (upload, all kernels and download included).  For context, the
 same host's time for the host emulation of the hypothesis stage (tests/verify_check.cpp) on a sample of pairs, scaled to the
 batch.  No test runs this.
 
-    python tools/verify_bench.py [--pairs 1000 10000] [--matches 100 500 2000] [--json out.json]
+    python tools/verify_bench.py [--pairs 1000 10000] [--matches 100 500 2000] [--models essential homography auto] [--json out.json]
 """
 import argparse
 import ctypes
@@ -24,6 +24,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 # fp64 instructions per (hypothesis, match) in the scoring loop of verify_hypothesis_kernel, counted in the gfx950 disassembly
 # (18 v_mul_f64, 15 v_add_f64, 1 v_cmp); 256 CUs x 4 SIMDs x 16 fp64 lanes per clock at 2.4 GHz
 FP64_PER_EVAL = 34
+# the same count for the homography's loop (24 v_mul_f64, 18 v_add_f64, 4 v_cmp: two transfers); "auto" is a run of each
+FP64_PER_EVAL_H = 46
 FP64_LANE_RATE = 256 * 4 * 16 * 2.4e9
 
 
@@ -66,6 +68,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, nargs="+", default=[1000, 10000])
     ap.add_argument("--matches", type=int, nargs="+", default=[100, 500, 2000])
+    ap.add_argument("--models", nargs="+", default=["essential", "homography", "auto"])
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     import verify_cases as vc
@@ -78,16 +81,18 @@ def main():
         for n_pairs in a.pairs:
             for m in a.matches:
                 pairs, flat, off = batch(sc, n_pairs, m, rng)
-                for method in (0, 1):
+                runs = [("essential", 0), ("essential", 1), ("homography", 0), ("auto", 0)]
+                for model, method in (r for r in runs if r[0] in a.models):
                     best = np.inf
                     for _ in range(3):
                         t0 = time.perf_counter()
-                        _, ioff, rep = v.pairs_csr(pairs, flat, off, method=method)
+                        _, ioff, rep = v.pairs_csr(pairs, flat, off, method=method, model=model)
                         best = min(best, time.perf_counter() - t0)
                     evals = n_pairs * 1024.0 * m
-                    bound = evals * FP64_PER_EVAL / FP64_LANE_RATE
-                    host = host_emulation(sc, pairs, flat, off, method) * n_pairs
-                    row = dict(pairs=n_pairs, matches=m, method=method, seconds=best, bound_seconds=bound, share_of_bound=bound / best,
+                    per = {"essential": FP64_PER_EVAL, "homography": FP64_PER_EVAL_H, "auto": FP64_PER_EVAL + FP64_PER_EVAL_H}[model]
+                    bound = evals * per / FP64_LANE_RATE
+                    host = host_emulation(sc, pairs, flat, off, method) * n_pairs if model == "essential" else None
+                    row = dict(pairs=n_pairs, matches=m, model=model, method=method, seconds=best, bound_seconds=bound, share_of_bound=bound / best,
                                host_emulation_seconds=host, ok_pairs=int((rep["status"] == 0).sum()), inliers=int(ioff[-1]))
                     rows.append(row)
                     print(json.dumps(row), flush=True)
