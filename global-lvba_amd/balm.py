@@ -88,8 +88,9 @@ class Prior:
         return Prior._make("relative", i, j, _pose12(T_ij), _sqrt_info(sqrt_info, sigma_rot, sigma_pos), offset_i, offset_j)
 
 
-class BalmProblem:
+class BalmProblem(L.Handle):
     """One packed LiDAR-BA problem (or one rank's voxel shard) resident on a GPU."""
+    _destroy = "lvba_balm_destroy"
 
     def __init__(self, n_poses, voxel_off, pose_idx, clusters, device=0, ordering=None, band_frac=None):
         self.lib = L.load()
@@ -117,24 +118,6 @@ class BalmProblem:
                                                  0.6 if band_frac is None else float(band_frac)))
         return self
 
-    # -- lifetime ---------------------------------------------------------------------------------
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self.lib.lvba_balm_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
     def _poses(self, poses):
         x = np.ascontiguousarray(poses, np.float64).reshape(-1)
         if x.size != 12 * self.n_poses:
@@ -160,7 +143,7 @@ class BalmProblem:
     def info(self):
         i = L.BalmInfo()
         L.check(self.lib.lvba_balm_info(self._h, C.byref(i)))
-        return {f: getattr(i, f) for f, _ in i._fields_}
+        return i.as_dict()
 
     def pair_layout(self):
         """how the pair pass was laid out (lvba_balm_pair_layout): form, cut, n_items, n_multi, n_partial, window_voxels,
@@ -176,7 +159,7 @@ class BalmProblem:
         """the nested-dissection plan of this problem's graph on n_ranks ranks and its cost model (lvba_balm_nd_model)"""
         m = L.NdModel()
         L.check(self.lib.lvba_balm_nd_model(self._h, int(n_ranks), C.byref(m)))
-        return {f: getattr(m, f) for f, _ in m._fields_}
+        return m.as_dict()
 
     def ordering(self):
         perm = np.empty(self.n_poses, np.int32)
@@ -189,7 +172,7 @@ class BalmProblem:
     def profile(self, reset=False):
         p = L.Prof()
         L.check(self.lib.lvba_balm_get_profile(self._h, C.byref(p), 1 if reset else 0))
-        return {f: getattr(p, f) for f, _ in p._fields_}
+        return p.as_dict()
 
     # -- the hot path ---------------------------------------------------------------------------------
     def cost(self, poses, is_avg=False):
@@ -228,11 +211,7 @@ class BalmProblem:
 
     @staticmethod
     def default_opts(**kw):
-        o = L.BalmOpts()
-        L.load().lvba_balm_default_opts(C.byref(o))
-        for k, v in kw.items():
-            setattr(o, k, v)
-        return o
+        return L.make_opts(L.BalmOpts, "LM", **kw)
 
     def refine(self, poses, **opts):
         o = self.default_opts(**opts)
@@ -279,10 +258,7 @@ class BalmProblem:
         units; a noise variance turns it into a metric covariance).  Returns (diag [N, 6, 6], pair_blocks [K, 6, 6], avail [K]):
         avail[k] is False for a pair outside the solver's band, whose block is NaN."""
         x = self._poses(poses)
-        o = L.CovOpts()
-        self.lib.lvba_cov_default_opts(C.byref(o))
-        o.anchor = -1 if anchor is None else int(anchor)
-        o.min_pivot_ratio = float(min_pivot_ratio)
+        o = L.make_opts(L.CovOpts, "covariance", anchor=-1 if anchor is None else anchor, min_pivot_ratio=min_pivot_ratio)
         pr = np.ascontiguousarray(np.zeros((0, 2)) if pairs is None else pairs, np.int32).reshape(-1, 2)
         K = pr.shape[0]
         pi, pj = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])

@@ -18,20 +18,18 @@ from . import _lib as L
 
 
 def default_opts():
-    o = L.ColorizeOpts()
-    L.load().lvba_colorize_default_opts(C.byref(o))
-    return o
+    return L.make_opts(L.ColorizeOpts, "colourisation")
 
 
-class ColorMap:
+class ColorMap(L.Handle):
     """One coloured cloud: scans (a voxel.Scans) seen from their poses scan_poses [n,12] (R row-major | t, T_world<-body),
     scan_times ascending; images of width x height through intr = fx fy cx cy k1 k2 p1 p2."""
+    _destroy = "lvba_colorize_destroy"
 
     def __init__(self, scans, scan_poses, scan_times, intr, width, height, half_window_s=0.5, leaf_size=0.01, max_batch_images=0):
         self.lib = L.load()
         self.width, self.height = int(width), int(height)
-        o = default_opts()
-        o.half_window_s, o.leaf_size, o.max_batch_images = float(half_window_s), float(leaf_size), int(max_batch_images)
+        o = L.make_opts(L.ColorizeOpts, "colourisation", half_window_s=half_window_s, leaf_size=leaf_size, max_batch_images=max_batch_images)
         self._h = C.c_void_p()
         L.check(self.lib.lvba_colorize_create(scans._h, np.ascontiguousarray(scan_poses, np.float64).reshape(-1),
                                               np.ascontiguousarray(scan_times, np.float64).reshape(-1),
@@ -67,20 +65,3 @@ class ColorMap:
         ms = np.zeros(6)
         L.check(self.lib.lvba_colorize_profile(self._h, ms.ctypes.data))
         return dict(zip(("upload", "project", "sort", "walk", "compact", "thin"), ms.tolist()))
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self.lib.lvba_colorize_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()

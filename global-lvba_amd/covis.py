@@ -9,21 +9,15 @@ import numpy as np
 
 from . import _lib as L
 
-INT_OPTIONS = ("grid_x", "grid_y", "search_radius", "occlusion", "both_ways", "max_per_image", "min_shared")
-FLOAT_OPTIONS = ("min_overlap", "occlusion_rel", "occlusion_abs")
-OPTION_NAMES = INT_OPTIONS + FLOAT_OPTIONS
+OPTION_NAMES = L.option_names(L.CovisOpts)
+INT_OPTIONS = tuple(f for f, t in L.CovisOpts._fields_ if f in OPTION_NAMES and t is C.c_int32)
+FLOAT_OPTIONS = tuple(f for f in OPTION_NAMES if f not in INT_OPTIONS)
 
 
 def covis_opts(lib=None, **kw):
     """lvba_covis_opts: the defaults (a 16 x 12 grid, radius 4, occlusion on at 5 % + 0.1 m, either way, no cap, 8 samples,
     overlap 0.1) with `kw` over them."""
-    o = L.CovisOpts()
-    (lib or L.load()).lvba_covis_default_opts(C.byref(o))
-    for k, v in kw.items():
-        if k not in OPTION_NAMES:
-            raise TypeError(f"unknown pair selection option {k!r}; one of {OPTION_NAMES}")
-        setattr(o, k, int(v) if k in INT_OPTIONS else float(v))
-    return o
+    return L.make_opts(L.CovisOpts, "pair selection", **kw)
 
 
 def _geometry(depth, Rcw, tcw, intr):

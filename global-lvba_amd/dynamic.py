@@ -15,24 +15,16 @@ import numpy as np
 
 from . import _lib as L
 
-OPTIONS = ("n_rows", "n_cols", "halo", "window", "min_free", "batch_frames", "el_min", "el_max", "min_range", "max_range", "abs_tol",
-           "rel_tol", "free_ratio")
+OPTIONS = L.option_names(L.DynamicOpts)
 SUMMARY = ("n_points", "n_judged", "n_dynamic")
 
 
 def default_opts():
-    o = L.DynamicOpts()
-    L.load().lvba_dynamic_default_opts(C.byref(o))
-    return o
+    return L.make_opts(L.DynamicOpts, "dynamic")
 
 
 def _opts(opts):
-    o = default_opts()
-    for k, v in opts.items():
-        if k not in OPTIONS:
-            raise TypeError(f"unknown option {k!r}: one of {OPTIONS}")
-        setattr(o, k, type(getattr(o, k))(v))
-    return o
+    return L.make_opts(L.DynamicOpts, "dynamic", **opts)
 
 
 def dynamic_labels(scans, poses, frame_begin=0, n_frames=None, per_point=True, **opts):

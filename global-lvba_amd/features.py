@@ -9,21 +9,13 @@ import numpy as np
 
 from . import _lib as L
 
-OPTION_NAMES = ("first_octave", "n_intervals", "sigma0", "dog_threshold", "edge_threshold", "orientation_window",
-                "max_orientations", "max_features", "chunk_images")
-_INT = ("first_octave", "n_intervals", "max_orientations", "max_features", "chunk_images")
+OPTION_NAMES = L.option_names(L.SiftOpts)
 
 
 def sift_opts(lib=None, **kw):
     """lvba_sift_opts: the defaults (SiftGPU's -fo -1 -w 3 -t 0.01 -e 12; 3 intervals, sigma0 1.6, 2 orientations, 8192 features)
     with `kw` over them."""
-    o = L.SiftOpts()
-    (lib or L.load()).lvba_sift_default_opts(C.byref(o))
-    for k, v in kw.items():
-        if k not in OPTION_NAMES:
-            raise TypeError(f"unknown feature option {k!r}; one of {OPTION_NAMES}")
-        setattr(o, k, int(v) if k in _INT else float(v))
-    return o
+    return L.make_opts(L.SiftOpts, "feature", **kw)
 
 
 def tile_width():

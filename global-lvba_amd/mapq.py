@@ -17,10 +17,7 @@ from . import _lib as L
 
 
 def _opts(radius, min_neighbors, query_stride):
-    o = L.MapqOpts()
-    L.load().lvba_mapq_default_opts(C.byref(o))
-    o.radius, o.min_neighbors, o.query_stride = float(radius), int(min_neighbors), int(query_stride)
-    return o
+    return L.make_opts(L.MapqOpts, "map quality", radius=radius, min_neighbors=min_neighbors, query_stride=query_stride)
 
 
 def _call(fn, head, n_points, o, per_point):

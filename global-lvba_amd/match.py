@@ -8,22 +8,17 @@ import numpy as np
 
 from . import _lib as L
 
-OPTION_NAMES = ("max_distance", "max_ratio", "mutual", "guided", "max_epipolar_px", "max_reproj_px")
+OPTION_NAMES = L.option_names(L.MatchOpts)
 
 
 def match_opts(lib=None, **kw):
     """lvba_match_opts: the defaults (0.7, 0.8, mutual, unguided, 4 px, 8 px) with `kw` over them."""
-    o = L.MatchOpts()
-    (lib or L.load()).lvba_match_default_opts(C.byref(o))
-    for k, v in kw.items():
-        if k not in OPTION_NAMES:
-            raise TypeError(f"unknown matching option {k!r}; one of {OPTION_NAMES}")
-        setattr(o, k, int(v) if k in ("mutual", "guided") else float(v))
-    return o
+    return L.make_opts(L.MatchOpts, "matching", **kw)
 
 
-class Matcher:
+class Matcher(L.Handle):
     """The descriptors of a set of images resident on a GPU.  descriptors: a sequence of uint8 [n_i, 128] arrays."""
+    _destroy = "lvba_match_destroy"
 
     def __init__(self, descriptors, device=0):
         self.lib = L.load()
@@ -43,23 +38,6 @@ class Matcher:
         self.has_depth = False
         self._h = C.c_void_p()
         L.check(self.lib.lvba_match_create(self.device, self.n_images, self.off.ctypes.data, flat.ctypes.data, C.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self.lib.lvba_match_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     def set_geometry(self, keypoints, intr, Rcw, tcw):
         """keypoints: per image [n_i, 2] pixels (rounded to fp32), in descriptor order; intr (fx, fy, cx, cy, k1, k2, p1, p2);

@@ -8,21 +8,16 @@ import numpy as np
 
 from . import _lib as L
 
-POSEGRAPH_OPTS = ("anchor", "max_iter", "odom_sigma_rot", "odom_sigma_pos", "anchor_sigma_rot", "anchor_sigma_pos", "rel_tol",
-                  "closure_loss")
+POSEGRAPH_OPTS = L.option_names(L.PosegraphOpts) + ("closure_loss",)
 
 
 def posegraph_opts(**opts):
     """An lvba_posegraph_opts with the library's defaults and `opts` on top; closure_loss is a (kind, scale) pair or None."""
-    o = L.PosegraphOpts()
-    L.load().lvba_posegraph_default_opts(C.byref(o))
-    for k, v in opts.items():
-        if k not in POSEGRAPH_OPTS:
-            raise TypeError(f"unknown pose-graph option {k!r}; one of {POSEGRAPH_OPTS}")
-        if k == "closure_loss":
-            o.closure_loss = L.Loss(0, 0, 0.0) if v is None else L.loss_struct(v).contents
-        else:
-            setattr(o, k, type(getattr(o, k))(v))
+    opts = dict(opts)
+    given, loss = "closure_loss" in opts, opts.pop("closure_loss", None)
+    o = L.make_opts(L.PosegraphOpts, "pose-graph", ("closure_loss",), **opts)
+    if given:                               # None here means TRIVIAL, not "keep the default" (register's loss differs)
+        o.closure_loss = L.Loss(0, 0, 0.0) if loss is None else L.loss_struct(loss).contents
     return o
 
 

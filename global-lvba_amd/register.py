@@ -20,24 +20,18 @@ import numpy as np
 from . import _lib as L
 
 STRICT_RATIO = (0.02, 0.02, 0.02, 0.02)   # eigen ratios of a registration map
-OPTS = ("max_iterations", "max_distance", "min_inliers", "min_eigenvalue", "tol_rot", "tol_pos")
+OPTS = L.option_names(L.RegisterOpts)          # `loss` is an option too: a (kind, scale) pair, see _opts
 
 
 def default_opts():
-    o = L.RegisterOpts()
-    L.load().lvba_register_default_opts(C.byref(o))
-    return o
+    return L.make_opts(L.RegisterOpts, "registration")
 
 
 def _opts(kw):
-    o = default_opts()
     kw = dict(kw)
     loss = kw.pop("loss", None)
-    for k, v in kw.items():
-        if k not in OPTS:
-            raise TypeError(f"unknown registration option {k!r}; one of {OPTS + ('loss',)}")
-        setattr(o, k, type(getattr(o, k))(v))
-    if loss is not None:
+    o = L.make_opts(L.RegisterOpts, "registration", ("loss",), **kw)
+    if loss is not None:                    # None leaves the library's default
         o.loss = L.loss_struct(loss).contents
     return o
 
@@ -99,7 +93,7 @@ def register(vmap, scans, frames, poses, submap=None, **opts):
     return d
 
 
-LOOP_OPTS = ("submap_size", "min_gap", "max_per_frame", "query_stride", "radius")
+LOOP_OPTS = L.option_names(L.LoopOpts)
 
 
 def loop_candidates(poses, device=0, capacity=None, **opts):
@@ -109,13 +103,8 @@ def loop_candidates(poses, device=0, capacity=None, **opts):
     frame), distance [m], count), sorted by (query, submap).  capacity: None (all of them), or the number of entries to fetch;
     count is the true number either way."""
     x = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
-    o = L.LoopOpts()
+    o = L.make_opts(L.LoopOpts, "candidate", **opts)
     lib = L.load()
-    lib.lvba_loop_default_opts(C.byref(o))
-    for k, v in opts.items():
-        if k not in LOOP_OPTS:
-            raise TypeError(f"unknown candidate option {k!r}; one of {LOOP_OPTS}")
-        setattr(o, k, type(getattr(o, k))(v))
     count = C.c_int64()
     cap = len(x) * max(1, min(32, o.max_per_frame)) if capacity is None else int(capacity)
     buf = np.zeros(max(cap, 1), np.dtype([("query", "<i4"), ("submap", "<i4"), ("ref", "<i4"), ("pad", "<i4"), ("distance", "<f8")]))
@@ -125,19 +114,12 @@ def loop_candidates(poses, device=0, capacity=None, **opts):
                 count=count.value, raw=got.copy())
 
 
-PLACE_OPTS = ("n_rings", "n_sectors", "min_range", "max_range", "z_offset", "submap_size", "min_gap", "n_key_candidates", "max_per_frame",
-              "query_stride", "max_distance")
+PLACE_OPTS = L.option_names(L.PlaceOpts)
 PLACE_DTYPE = np.dtype([("query", "<i4"), ("submap", "<i4"), ("ref", "<i4"), ("shift", "<i4"), ("distance", "<f8"), ("yaw", "<f8")])
 
 
 def _place_opts(opts):
-    o = L.PlaceOpts()
-    L.load().lvba_place_default_opts(C.byref(o))
-    for k, v in opts.items():
-        if k not in PLACE_OPTS:
-            raise TypeError(f"unknown place option {k!r}; one of {PLACE_OPTS}")
-        setattr(o, k, type(getattr(o, k))(v))
-    return o
+    return L.make_opts(L.PlaceOpts, "place", **opts)
 
 
 def _place_result(call, n, o, capacity):
@@ -187,7 +169,7 @@ def place_candidates(scans, capacity=None, **opts):
     return _place_result(lambda po, cap, out, cnt: lib.lvba_place_candidates(scans._h, po, cap, out, cnt), scans.n_frames, o, capacity)
 
 
-CLOSURE_OPTS = ("rot_tol", "rot_rate", "trans_tol", "trans_rate", "n_seeds", "min_set")
+CLOSURE_OPTS = L.option_names(L.ClosureOpts)
 
 
 def closure_consistency(poses, ref, query, meas, device=0, diagnostics=False, **opts):
@@ -204,13 +186,8 @@ def closure_consistency(poses, ref, query, meas, device=0, diagnostics=False, **
     n = len(z)
     if len(i) != n or len(j) != n:
         raise ValueError(f"{n} measurements for {len(i)} ref and {len(j)} query frames")
-    o = L.ClosureOpts()
+    o = L.make_opts(L.ClosureOpts, "closure", **opts)
     lib = L.load()
-    lib.lvba_closure_default_opts(C.byref(o))
-    for k, v in opts.items():
-        if k not in CLOSURE_OPTS:
-            raise TypeError(f"unknown closure option {k!r}; one of {CLOSURE_OPTS}")
-        setattr(o, k, type(getattr(o, k))(v))
     W = (n + 63) // 64
     words, keep, n_keep = np.zeros((n, W), np.uint64), np.zeros(n, np.uint8), C.c_int32()
     rot, trans = (np.zeros((n, n)), np.zeros((n, n))) if diagnostics else (None, None)

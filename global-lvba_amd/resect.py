@@ -9,20 +9,14 @@ import numpy as np
 
 from . import _lib as L
 
-OPTION_NAMES = ("hypotheses", "refine_rounds", "min_inliers", "max_error_px", "seed")
+OPTION_NAMES = L.option_names(L.ResectOpts)
 OK, TOO_FEW_MATCHES, NO_MODEL, TOO_FEW_INLIERS = 0, 1, 2, 3
 STATUS_NAMES = ("ok", "too_few_matches", "no_model", "too_few_inliers")
 
 
 def resect_opts(lib=None, **kw):
     """lvba_resect_opts: the defaults (1024 hypotheses, 2 refinement rounds, 30 inliers, 8 px, seed 0) with `kw` over them."""
-    o = L.ResectOpts()
-    (lib or L.load()).lvba_resect_default_opts(C.byref(o))
-    for k, v in kw.items():
-        if k not in OPTION_NAMES:
-            raise TypeError(f"unknown resectioning option {k!r}; one of {OPTION_NAMES}")
-        setattr(o, k, float(v) if k == "max_error_px" else int(v))
-    return o
+    return L.make_opts(L.ResectOpts, "resectioning", **kw)
 
 
 def _intr(intr):

@@ -14,14 +14,14 @@ def _ptr(a):
     return a.ctypes.data if a.size else None
 
 
-class TrackGraph:
+class TrackGraph(L.Handle):
     """TrackGraph(n_keypoints | keypoints, pairs, matches, obser_thr=3, device=0).  The first argument is either the key point
     count of every image or the key points themselves ([n_i, >= 2] per image; their first two columns go to the device and
     orders(uv=True) gathers them).  pairs / matches as pipeline.build_components takes them: one int [m, 2] array per pair.
     The graph, its component table and the adjacency stay on the device until close()."""
+    _destroy = "lvba_trackgraph_destroy"
 
     def __init__(self, keypoints, pairs, matches, obser_thr=3, device=0):
-        self._h = None
         lib = L.load()
         counts = len(keypoints) == 0 or np.ndim(keypoints[0]) == 0
         if counts:
@@ -35,7 +35,7 @@ class TrackGraph:
         h, info = C.c_void_p(), L.TrackGraphInfo()
         L.check(lib.lvba_trackgraph_create(device, len(kp_off) - 1, kp_off.ctypes.data, None if uv is None else _ptr(uv), len(pr), _ptr(pr),
                                            match_off.ctypes.data, _ptr(flat), int(obser_thr), C.byref(h), C.byref(info)))
-        self._h, self._lib, self.has_uv = h, lib, uv is not None
+        self._h, self.lib, self.has_uv = h, lib, uv is not None
         self.info = info.as_dict()
         self._sizes = None
 
@@ -44,7 +44,7 @@ class TrackGraph:
         scan order, the components by their smallest member."""
         nc, no = self.info["n_components"], self.info["n_observations"]
         off, img, kp, images = np.zeros(nc + 1, np.int64), np.zeros(no, np.int32), np.zeros(no, np.int32), np.zeros(nc, np.int32)
-        L.check(self._lib.lvba_trackgraph_components(self._h, off.ctypes.data, _ptr(img), _ptr(kp), _ptr(images)))
+        L.check(self.lib.lvba_trackgraph_components(self._h, off.ctypes.data, _ptr(img), _ptr(kp), _ptr(images)))
         self._sizes = np.diff(off)
         return off, img, kp, images
 
@@ -64,23 +64,6 @@ class TrackGraph:
         total = int((self._sizes if sel is None else self._sizes[sel]).sum()) if inside else 0       # a refusal writes nothing
         off, img, kp = np.zeros(n + 1, np.int64), np.zeros(total, np.int32), np.zeros(total, np.int32)
         puv = np.zeros((total, 2), np.float32) if uv else None
-        L.check(self._lib.lvba_trackgraph_orders(self._h, n, None if sel is None else sel.ctypes.data, int(attempt),
+        L.check(self.lib.lvba_trackgraph_orders(self._h, n, None if sel is None else sel.ctypes.data, int(attempt),
                                                  off.ctypes.data, _ptr(img), _ptr(kp), None if puv is None else (puv.ctypes.data if total else None)))
         return (off, img, kp, puv) if uv else (off, img, kp)
-
-    def close(self):
-        if self._h is not None:
-            self._lib.lvba_trackgraph_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

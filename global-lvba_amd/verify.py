@@ -8,7 +8,7 @@ import numpy as np
 
 from . import _lib as L
 
-OPTION_NAMES = ("method", "hypotheses", "refine_rounds", "min_inliers", "max_error_px", "seed")
+OPTION_NAMES = L.option_names(L.VerifyOpts)
 EIGHT_POINT, KNOWN_ROTATION = 0, 1
 OK, TOO_FEW_MATCHES, NO_MODEL, TOO_FEW_INLIERS = 0, 1, 2, 3
 STATUS_NAMES = ("ok", "too_few_matches", "no_model", "too_few_inliers")
@@ -28,19 +28,14 @@ def model_code(model):
 
 def verify_opts(lib=None, **kw):
     """lvba_verify_opts: the defaults (eight-point, 1024 hypotheses, 2 refits, 15 inliers, 4 px, seed 0) with `kw` over them."""
-    o = L.VerifyOpts()
-    (lib or L.load()).lvba_verify_default_opts(C.byref(o))
-    for k, v in kw.items():
-        if k not in OPTION_NAMES:
-            raise TypeError(f"unknown verification option {k!r}; one of {OPTION_NAMES}")
-        setattr(o, k, float(v) if k == "max_error_px" else int(v))
-    return o
+    return L.make_opts(L.VerifyOpts, "verification", **kw)
 
 
-class Verifier:
+class Verifier(L.Handle):
     """The undistorted keypoints of a set of images resident on a GPU.  keypoints: a sequence of [n_i, 2] pixel arrays (rounded to
     fp32); intr (fx, fy, cx, cy, k1, k2, p1, p2); Rcw [M, 3, 3] = the rotations of T_cam<-world, or None (then only the pose-free
     eight-point method is available)."""
+    _destroy = "lvba_verify_destroy"
 
     def __init__(self, keypoints, intr, Rcw=None, device=0):
         self.lib = L.load()
@@ -54,23 +49,6 @@ class Verifier:
         self._h = C.c_void_p()
         L.check(self.lib.lvba_verify_create(self.device, self.n_images, self.off.ctypes.data, uv.ctypes.data, intr.ctypes.data,
                                             R.ctypes.data if R is not None else None, C.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self.lib.lvba_verify_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     def pairs_csr(self, pairs, matches, match_off, capacity=None, model="essential", planar_ratio=PLANAR_RATIO, **opts):
         """(inliers int32 [n, 2], inlier_off int64 [P + 1], report): the C call as it is.  `capacity` defaults to the number of

@@ -15,7 +15,9 @@ import numpy as np
 from . import _lib as L
 
 
-class VisualProblem:
+class VisualProblem(L.Handle):
+    _destroy = "lvba_visual_destroy"
+
     def __init__(self, n_cams, obs_off, obs_cam, obs_uv, plane, valid, intr, sigma_px=0.5, sigma_plane=0.01, device=0):
         self.lib = L.load()
         self.n_cams = int(n_cams)
@@ -34,17 +36,6 @@ class VisualProblem:
                                             C.byref(self._h)))
         self._keep = (obs_cam, obs_uv)
         self.n_obs = int(obs_off[-1] - obs_off[0])
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self.lib.lvba_visual_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _state(self, q, t, X):
         q = np.ascontiguousarray(q, np.float64).reshape(-1)
@@ -129,7 +120,7 @@ class VisualProblem:
     def info(self):
         i = L.BalmInfo()
         L.check(self.lib.lvba_visual_info(self._h, C.byref(i)))
-        return {f: getattr(i, f) for f, _ in i._fields_}
+        return i.as_dict()
 
     def pair_layout(self):
         """the pair-pass layout of the reduced camera system (lvba_visual_pair_layout; fields as BalmProblem.pair_layout)"""
@@ -144,11 +135,7 @@ class VisualProblem:
 
     @staticmethod
     def default_opts(**kw):
-        o = L.VisualOpts()
-        L.load().lvba_visual_default_opts(C.byref(o))
-        for k, v in kw.items():
-            setattr(o, k, v)
-        return o
+        return L.make_opts(L.VisualOpts, "visual LM", **kw)
 
     def refine(self, q, t, X, **opts):
         o = self.default_opts(**opts)
@@ -275,9 +262,10 @@ def triangulate_and_filter(Rcw, tcw, keypoints, obs_off, obs_img, obs_kp, intr, 
     return status == 1, X, err, koff, obs_img[sel], obs_kp[sel]
 
 
-class DepthImages:
+class DepthImages(L.Handle):
     """Device-resident depth images (lvba_depth_t): rendered from the refined LiDAR map
     (LvbaSystem::buildGridMapFromOptimized + generateDepthWithVoxel, src/lvba_system.cpp:835-919, 1266-1338) or uploaded."""
+    _destroy = "lvba_depth_destroy"
 
     def __init__(self, handle):
         self._h = handle
@@ -314,23 +302,6 @@ class DepthImages:
         L.check(self.lib.lvba_depth_download(self._h, int(image), out))
         return out.reshape(self.height, self.width)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self.lib.lvba_depth_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
 
 def fuse_tracks(obs_off, obs_img, obs_uv, Rcw, tcw, intr, depth=None, obser_thr=3, min_view_angle_deg=8.0,
                 reproj_mean_thr_px=3.0, device=0):
@@ -349,9 +320,7 @@ def fuse_tracks(obs_off, obs_img, obs_uv, Rcw, tcw, intr, depth=None, obser_thr=
     X = np.zeros((max(n, 1), 3))
     err = np.zeros(max(n, 1))
     kept = np.zeros(max(O, 1), np.uint8)
-    o = L.FuseOpts()
-    lib.lvba_fuse_default_opts(C.byref(o))
-    o.obser_thr, o.min_view_angle_deg, o.reproj_mean_thr_px = int(obser_thr), float(min_view_angle_deg), float(reproj_mean_thr_px)
+    o = L.make_opts(L.FuseOpts, "fusion", obser_thr=obser_thr, min_view_angle_deg=min_view_angle_deg, reproj_mean_thr_px=reproj_mean_thr_px)
     L.check(lib.lvba_fuse_tracks(int(device), depth._h if depth is not None else None, len(Rcw), Rcw.reshape(-1), tcw.reshape(-1),
                                  np.ascontiguousarray(intr, np.float64), n, obs_off, obs_img.ctypes.data, obs_uv.ctypes.data,
                                  C.byref(o), status.ctypes.data, X.reshape(-1), err, kept.ctypes.data))

@@ -19,14 +19,11 @@ from .balm import BalmProblem
 
 
 def default_opts():
-    o = L.VoxelOpts()
-    L.load().lvba_voxel_default_opts(C.byref(o))
-    return o
+    return L.make_opts(L.VoxelOpts, "voxel")
 
 
 def _opts(voxel_size, eigen_ratio_array, min_points):
-    o = default_opts()
-    o.voxel_size = float(voxel_size)
+    o = L.make_opts(L.VoxelOpts, "voxel", voxel_size=voxel_size)
     if eigen_ratio_array is not None:
         er = np.asarray(eigen_ratio_array, np.float32)
         for i in range(min(4, len(er))):
@@ -49,8 +46,9 @@ def _prior_report(rep, ap, used, dropped):
     return d
 
 
-class Scans:
+class Scans(L.Handle):
     """A set of LiDAR clouds resident on a GPU (fp32 x, y, z per point)."""
+    _destroy = "lvba_scans_destroy"
 
     def __init__(self, clouds, device=0):
         """clouds: sequence of [n_i, >=3] float32 arrays (x, y, z first; row stride = the array's, so PCL-style padded
@@ -82,23 +80,6 @@ class Scans:
         self._h = C.c_void_p()
         L.check(self.lib.lvba_scans_create(int(device), n, ptrs, counts, int(stride or 12), C.byref(self._h)))
 
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self.lib.lvba_scans_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
     @classmethod
     def _from_handle(cls, handle):
         self = cls.__new__(cls)
@@ -126,14 +107,11 @@ class Scans:
         poses = np.ascontiguousarray(poses, np.float64).reshape(-1)
         if poses.size != 12 * n:
             raise ValueError(f"poses must hold {n} x 12 doubles")
-        o = L.WindowOpts()
-        self.lib.lvba_window_default_opts(C.byref(o))
-        o.window_size, o.use_rel, o.anchor_leaf = int(window_size), 1 if use_rel else 0, float(anchor_leaf)
+        # lm_mode 0: all windows' LM in lock-step as one grouped problem, 1: one window at a time
+        o = L.make_opts(L.WindowOpts, "window", window_size=window_size, use_rel=bool(use_rel), anchor_leaf=anchor_leaf,
+                        merge_only=bool(merge_only), lm_mode=lm_mode)
         o.voxel = _opts(voxel_size, eigen_ratio_array, min_points)
-        o.merge_only = 1 if merge_only else 0
-        o.lm_mode = int(lm_mode)   # 0: all windows' LM in lock-step as one grouped problem, 1: one window at a time
-        for k, v in lm.items():
-            setattr(o.lm, k, v)
+        L.set_opts(o.lm, "LM", **lm)
         nw = (n + o.window_size - 1) // o.window_size
         window_poses = np.zeros((n, 12))
         rel = np.zeros((n, 12))
@@ -162,13 +140,9 @@ class Scans:
         fb = np.zeros(D + 1, np.int32)
         L.check(lib.lvba_window_split(n, int(window_size), D, fb))
         shares = [Scans(clouds[fb[k]:fb[k + 1]], device=int(devices[k])) for k in range(D) if fb[k + 1] > fb[k]]
-        o = L.WindowOpts()
-        lib.lvba_window_default_opts(C.byref(o))
-        o.window_size, o.use_rel, o.anchor_leaf = int(window_size), 1 if use_rel else 0, float(anchor_leaf)
+        o = L.make_opts(L.WindowOpts, "window", window_size=window_size, use_rel=bool(use_rel), anchor_leaf=anchor_leaf, lm_mode=lm_mode)
         o.voxel = _opts(voxel_size, eigen_ratio_array, min_points)
-        o.lm_mode = int(lm_mode)
-        for k, v in lm.items():
-            setattr(o.lm, k, v)
+        L.set_opts(o.lm, "LM", **lm)
         nw = (n + o.window_size - 1) // o.window_size
         window_poses, rel = np.zeros((n, 12)), np.zeros((n, 12))
         aidx = np.zeros(n, np.int32)
@@ -198,10 +172,8 @@ class Scans:
         poses = np.ascontiguousarray(poses, np.float64).reshape(-1)
         if poses.size != 12 * n:
             raise ValueError(f"poses must hold {n} x 12 doubles")
-        o = L.LidarBaOpts()
-        self.lib.lvba_lidar_ba_default_opts(C.byref(o))
-        o.window_enable, o.stage1_enable = int(bool(window_enable)), int(bool(stage1_enable))
-        o.window.window_size, o.window.use_rel, o.window.anchor_leaf = int(window_size), int(bool(use_rel)), float(anchor_leaf)
+        o = L.make_opts(L.LidarBaOpts, "LiDAR BA", window_enable=bool(window_enable), stage1_enable=bool(stage1_enable))
+        L.set_opts(o.window, "window", window_size=window_size, use_rel=bool(use_rel), anchor_leaf=anchor_leaf)
         o.window.voxel = _opts(stage_voxel_size[0], window_eigen_ratio, None)   # stage1_root_voxel_size_, ratios in effect
         for i in range(2):
             o.stage_voxel_size[i] = float(stage_voxel_size[i])
@@ -240,10 +212,8 @@ class Scans:
         fb = np.zeros(D + 1, np.int32)
         L.check(lib.lvba_window_split(n, int(window_size), D, fb))
         shares = [Scans(clouds[fb[k]:fb[k + 1]], device=int(devices[k])) for k in range(D) if fb[k + 1] > fb[k]]
-        o = L.LidarBaOpts()
-        lib.lvba_lidar_ba_default_opts(C.byref(o))
-        o.window_enable, o.stage1_enable = 1, int(bool(stage1_enable))
-        o.window.window_size, o.window.use_rel, o.window.anchor_leaf = int(window_size), int(bool(use_rel)), float(anchor_leaf)
+        o = L.make_opts(L.LidarBaOpts, "LiDAR BA", window_enable=1, stage1_enable=bool(stage1_enable))
+        L.set_opts(o.window, "window", window_size=window_size, use_rel=bool(use_rel), anchor_leaf=anchor_leaf)
         o.window.voxel = _opts(stage_voxel_size[0], window_eigen_ratio, None)
         for i in range(2):
             o.stage_voxel_size[i] = float(stage_voxel_size[i])
@@ -284,8 +254,9 @@ class Scans:
         return SubmapSet(self, poses, submap_size, voxel_size, eigen_ratio_array, min_points, int(frame_begin), n)
 
 
-class VoxelMap:
+class VoxelMap(L.Handle):
     """Adaptive-voxel plane map of a window of scans, resident on a GPU."""
+    _destroy = "lvba_voxmap_destroy"
 
     def __init__(self, clouds, poses, voxel_size=1.0, eigen_ratio_array=None, min_points=None, device=0, _scans=None):
         self.lib = L.load()
@@ -324,24 +295,7 @@ class VoxelMap:
         self.n_frames = n
         info = L.VoxmapInfo()
         L.check(self.lib.lvba_voxmap_info(self._h, C.byref(info)))
-        self.info = {f: getattr(info, f) for f, _ in info._fields_}
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self.lib.lvba_voxmap_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
+        self.info = info.as_dict()
 
     def export(self):
         """(voxel_off [V+1], pose_idx [F], clusters [F,10], voxel_key [V,4]) of the admitted voxels."""
@@ -396,7 +350,7 @@ class SubmapSet(VoxelMap):
         self.n_frames = n
         info = L.VoxmapInfo()
         L.check(self.lib.lvba_voxmap_info(self._h, C.byref(info)))
-        self.info = {f: getattr(info, f) for f, _ in info._fields_}
+        self.info = info.as_dict()
         ns, ss = C.c_int32(), C.c_int32()
         L.check(self.lib.lvba_submaps_count(self._h, C.byref(ns), C.byref(ss)))
         self.n_submaps, self.submap_size = ns.value, ss.value

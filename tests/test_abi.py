@@ -35,24 +35,72 @@ def test_struct_layouts_match_header(pkg):
     assert (o.max_iter, o.u0, o.v0, o.rel_tol) == (10, 0.01, 2.0, 1e-6)      # bavoxel.hpp:664,686,760
 
 
-def test_every_struct_has_the_size_the_c_compiler_gives_it(pkg, tmp_path):
-    """ctypes mirrors vs `sizeof` from the header itself (compiled as C: the header must stay plain C)."""
+def header_structs():
+    """[(C type name, [(base type, field name, array dimensions)])] of every struct typedef of include/lvba_hip.h, in declaration order"""
+    hdr = open(os.path.join(ROOT, "include", "lvba_hip.h")).read()
+    out = []
+    for body, name in re.findall(r"typedef struct\s*\w*\s*\{(.*?)\}\s*(\w+);", hdr, re.S):
+        body = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", body, flags=re.S))
+        fields = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            base, declarators = decl.split(None, 1)
+            for d in declarators.split(","):
+                m = re.fullmatch(r"\s*(\w+)((?:\[\d+\])*)\s*", d)
+                assert m, (name, decl)
+                fields.append((base, m.group(1), [int(n) for n in re.findall(r"\d+", m.group(2))]))
+        out.append((name, fields))
+    return out
+
+
+# sizeof, and the offsetof of the fields a stage's test used to pin by number: they guard against header and mirror drifting together
+PINNED_SIZES = {
+    "lvba_balm_opts": 32, "lvba_lm_trace": 64, "lvba_balm_info_t": 136, "lvba_prof_t": 80, "lvba_nd_model_t": 40,
+    "lvba_pair_layout_t": 56, "lvba_eval_layout_t": 72, "lvba_loss": 16, "lvba_loop_opts": 24, "lvba_loop_candidate": 24,
+    "lvba_place_opts": 64, "lvba_place_candidate": 32, "lvba_register_opts": 64, "lvba_register_result": 56,
+    "lvba_closure_opts": 40, "lvba_posegraph_opts": 64, "lvba_posegraph_report": 56, "lvba_covis_opts": 56,
+    "lvba_dynamic_opts": 80, "lvba_dynamic_summary": 56, "lvba_mapq_opts": 16, "lvba_mapq_summary": 80, "lvba_sift_opts": 56,
+    "lvba_trackgraph_info": 64,
+}
+PINNED_OFFSETS = {
+    ("lvba_loss", "scale"): 8, ("lvba_closure_opts", "trans_tol"): 16, ("lvba_closure_opts", "n_seeds"): 32,
+    ("lvba_closure_opts", "min_set"): 36, ("lvba_posegraph_opts", "rel_tol"): 40, ("lvba_posegraph_opts", "closure_loss"): 48,
+    ("lvba_posegraph_report", "solver_kind"): 12, ("lvba_posegraph_report", "max_step_last"): 48,
+}
+
+
+def test_every_struct_matches_the_header_field_for_field(pkg, tmp_path):
+    """Every struct typedef of the header has a mirror in _lib.STRUCTS and the reverse; for each, from the header compiled as C99
+    (it must stay plain C): sizeof, the names of the fields in declaration order, and every field's offsetof, sizeof and type."""
     import subprocess
     L = pkg._lib
-    pairs = [("lvba_balm_opts", L.BalmOpts), ("lvba_lm_trace", L.LmTrace), ("lvba_balm_info_t", L.BalmInfo),
-             ("lvba_prof_t", L.Prof), ("lvba_visual_opts", L.VisualOpts), ("lvba_visual_trace", L.VisualTrace),
-             ("lvba_voxel_opts", L.VoxelOpts), ("lvba_voxmap_info_t", L.VoxmapInfo), ("lvba_window_opts", L.WindowOpts),
-             ("lvba_window_info", L.WindowInfo), ("lvba_lidar_ba_opts", L.LidarBaOpts), ("lvba_lidar_ba_report", L.LidarBaReport),
-             ("lvba_fuse_opts", L.FuseOpts), ("lvba_nd_model_t", L.NdModel), ("lvba_pair_layout_t", L.PairLayout),
-             ("lvba_eval_layout_t", L.EvalLayout)]
-    src = tmp_path / "sizes.c"
-    src.write_text('#include <stdio.h>\n#include "lvba_hip.h"\nint main(void){' +
-                   "".join(f'printf("%zu\\n", sizeof({n}));' for n, _ in pairs) + "return 0;}\n")
-    exe = str(tmp_path / "sizes")
+    structs = header_structs()
+    assert [n for n, _ in structs if n not in L.STRUCTS] == [] and set(L.STRUCTS) == {n for n, _ in structs}
+    rows = "".join(f'printf("%zu", sizeof({n}));' +
+                   "".join(f'printf(" %zu %zu", offsetof({n}, {f}), sizeof((({n} *)0)->{f}));' for _, f, _ in fields) + 'printf("\\n");'
+                   for n, fields in structs)
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "lvba_hip.h"\nint main(void){' + rows + "return 0;}\n")
+    exe = str(tmp_path / "layout")
     subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe])
-    sizes = [int(v) for v in subprocess.check_output([exe]).split()]
-    for (name, cls), sz in zip(pairs, sizes):
-        assert ctypes.sizeof(cls) == sz, (name, ctypes.sizeof(cls), sz)
+    scalars = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "double": ctypes.c_double,
+               "float": ctypes.c_float}
+    n_fields, sizes, offsets = 0, {}, {}
+    for (name, fields), line in zip(structs, subprocess.check_output([exe]).decode().splitlines()):
+        cls, got = L.STRUCTS[name], [int(v) for v in line.split()]
+        assert ctypes.sizeof(cls) == got[0], (name, ctypes.sizeof(cls), got[0])
+        assert [f for f, _ in cls._fields_] == [f for _, f, _ in fields], name
+        for k, ((f, ctype), (base, _, dims)) in enumerate(zip(cls._fields_, fields)):
+            want = scalars.get(base) or L.STRUCTS[base]
+            for d in reversed(dims):
+                want = want * d
+            assert ctype == want, (name, f, ctype, want)            # ctypes caches array types: equal means the same type
+            assert (getattr(cls, f).offset, getattr(cls, f).size) == (got[1 + 2 * k], got[2 + 2 * k]), (name, f)
+            offsets[name, f] = got[1 + 2 * k]
+        sizes[name] = got[0]
+        n_fields += len(fields)
+    print(f"{len(structs)} structs, {n_fields} fields, no mismatch")
+    assert {n: sizes[n] for n in PINNED_SIZES} == PINNED_SIZES
+    assert {k: offsets[k] for k in PINNED_OFFSETS} == PINNED_OFFSETS
 
 
 def test_pair_layout_entry_points(lib, pkg):

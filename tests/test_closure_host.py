@@ -3,13 +3,11 @@ against the numpy restatement (tests/closure_oracle.py), the conditions on the s
 §10f), the argument checks of pipeline.consistent_closures and the struct layout."""
 import ctypes
 import importlib
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from host_build import build_check
 
 import closure_cases as cc
 import closure_oracle as co
@@ -20,10 +18,7 @@ IDS = [c["name"] for c in cc.cases()]
 
 @pytest.fixture(scope="module")
 def emul(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("emul_closure") / "libclosure_check.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Werror", "-Wno-unknown-pragmas",
-                           os.path.join(ROOT, "tests", "closure_check.cpp"), "-o", so])
-    lib = ctypes.CDLL(so)
+    lib = ctypes.CDLL(build_check("closure_check", tmp_path_factory.mktemp("emul_closure")))
     f64, i32, u64, u8 = (np.ctypeslib.ndpointer(t, flags="C") for t in (np.float64, np.int32, np.uint64, np.uint8))
     lib.emul_adjacency.argtypes = [f64, ctypes.c_int, i32, i32, f64, f64, u64, f64, f64]
     lib.emul_adjacency.restype = None
@@ -181,17 +176,9 @@ def test_consistent_closures_refuses_what_it_cannot_check():
     assert inspect.signature(pl.find_loop_closures).parameters["consistency"].default is None
 
 
-def test_closure_struct_size_matches_the_header(tmp_path):
+def test_closure_struct_size_matches_the_header():
     L = importlib.import_module("global-lvba_amd._lib")
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "lvba_hip.h"\nint main(void){printf("%zu %zu %zu %zu\\n", '
-                   'sizeof(lvba_closure_opts), offsetof(lvba_closure_opts, trans_tol), offsetof(lvba_closure_opts, n_seeds), '
-                   'offsetof(lvba_closure_opts, min_set));return 0;}\n')
-    exe = str(tmp_path / "sz")
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe])
-    got = [int(t) for t in subprocess.check_output([exe]).split()]
-    assert got == [ctypes.sizeof(L.ClosureOpts), L.ClosureOpts.trans_tol.offset, L.ClosureOpts.n_seeds.offset, L.ClosureOpts.min_set.offset]
-    assert got == [40, 16, 32, 36]
+    # the layout of lvba_closure_opts against the header: tests/test_abi.py, every struct at once
     assert all(s in L.SYMBOLS for s in ("lvba_closure_default_opts", "lvba_closure_consistency"))
 
 

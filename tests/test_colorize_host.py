@@ -4,13 +4,13 @@ walk and the restatement, and the Python layer around it (image decoding, the PC
 import ctypes
 import importlib
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
+from host_build import build_check
 
 import colorize_oracle as co
 
@@ -46,10 +46,7 @@ def test_oracle_matches_reference_visualize_opt_comparison(tmp_path):
 # ------------------------------------------------------------------------------------------------------- (b) host-built header
 @pytest.fixture(scope="module")
 def emul(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("emul_colorize") / "libcolorize_check.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Werror", "-Wno-unknown-pragmas",
-                           os.path.join(ROOT, "tests", "colorize_check.cpp"), "-o", so])
-    lib = ctypes.CDLL(so)
+    lib = ctypes.CDLL(build_check("colorize_check", tmp_path_factory.mktemp("emul_colorize")))
     f64 = np.ctypeslib.ndpointer(np.float64, flags="C")
     f32 = np.ctypeslib.ndpointer(np.float32, flags="C")
     i64 = np.ctypeslib.ndpointer(np.int64, flags="C")

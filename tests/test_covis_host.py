@@ -5,9 +5,7 @@ that shares nothing is selected and no pair that shares much is missed, without 
 import ctypes
 import importlib
 import json
-import os
 import sqlite3
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,7 +13,7 @@ import pytest
 import covis_cases as cc
 import covis_oracle as co
 import match_cases as mc
-from conftest import ROOT
+from host_build import build_check
 
 # The largest number of planted points (of cc.N_PLANTED) that a pair NOT selected at the defaults shares is 63, measured on this
 # fixture by the oracle at 160 x 128 with the 16 x 12 grid: no pair sharing this many may be missed.
@@ -25,10 +23,7 @@ T_SHARED = 64
 @pytest.fixture(scope="module")
 def emul(tmp_path_factory):
     """csrc/covis_device.h compiled for the host, without contraction (tests/covis_check.cpp)"""
-    so = str(tmp_path_factory.mktemp("emul_covis") / "libcovis_check.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Werror", "-Wno-unknown-pragmas",
-                           os.path.join(ROOT, "tests", "covis_check.cpp"), "-o", so])
-    lib = ctypes.CDLL(so)
+    lib = ctypes.CDLL(build_check("covis_check", tmp_path_factory.mktemp("emul_covis")))
     P, I = ctypes.c_void_p, ctypes.c_int
     lib.emul_samples.argtypes = [I, I, I, I, I, I, P, P, P, P, P, P]
     lib.emul_counts.argtypes = [I, I, I, I, P, P, P, P, P, P, P, P, P, P]
@@ -136,14 +131,6 @@ def test_fixture_conditions():
     # the option sets do select different things
     sets = [frozenset(map(tuple, cc.selected(0, 0, **kw)[0].tolist())) for kw in cc.OPTION_SETS]
     assert len(set(sets)) == len(sets) and all(sets)
-
-
-def test_options_struct_has_the_size_the_c_compiler_gives_it(pkg, tmp_path):
-    src = tmp_path / "size.c"
-    src.write_text('#include <stdio.h>\n#include "lvba_hip.h"\nint main(void){printf("%zu\\n", sizeof(lvba_covis_opts));return 0;}\n')
-    exe = str(tmp_path / "size")
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe])
-    assert int(subprocess.check_output([exe])) == 56 == ctypes.sizeof(pkg._lib.CovisOpts)
 
 
 def test_occlusion_keeps_out_the_pairs_that_share_nothing():

@@ -3,13 +3,11 @@ restatement (tests/dynamic_oracle.py) on every shared fixture and option set (te
 fixtures and the struct layouts."""
 import ctypes
 import importlib
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from host_build import build_check
 
 import dynamic_cases as dc
 import dynamic_oracle as do
@@ -24,10 +22,7 @@ class EmulOpts(ctypes.Structure):
 
 @pytest.fixture(scope="module")
 def emul(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("emul_dynamic") / "libdynamic_check.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Werror", "-Wno-unknown-pragmas",
-                           os.path.join(ROOT, "tests", "dynamic_check.cpp"), "-o", so])
-    lib = ctypes.CDLL(so)
+    lib = ctypes.CDLL(build_check("dynamic_check", tmp_path_factory.mktemp("emul_dynamic")))
     f32, f64, i32, i64, u8 = (np.ctypeslib.ndpointer(t, flags="C") for t in (np.float32, np.float64, np.int32, np.int64, np.uint8))
     lib.emul_image.argtypes = [ctypes.c_int64, f32, ctypes.POINTER(EmulOpts), i32, f32, f32]
     lib.emul_image.restype = None
@@ -130,19 +125,10 @@ def test_selection_equals_boolean_indexing():
             at += len(c)
 
 
-def test_dynamic_struct_sizes_match_the_header(tmp_path):
+def test_dynamic_struct_sizes_match_the_header():
     L = importlib.import_module("global-lvba_amd._lib")
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "lvba_hip.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu\\n", '
-                   'sizeof(lvba_dynamic_opts), sizeof(lvba_dynamic_summary), offsetof(lvba_dynamic_opts, batch_frames), '
-                   'offsetof(lvba_dynamic_opts, el_min), offsetof(lvba_dynamic_opts, free_ratio), offsetof(lvba_dynamic_summary, ms));'
-                   'return 0;}\n')
-    exe = str(tmp_path / "sz")
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe])
-    got = [int(t) for t in subprocess.check_output([exe]).split()]
-    assert got == [ctypes.sizeof(L.DynamicOpts), ctypes.sizeof(L.DynamicSummary), L.DynamicOpts.batch_frames.offset,
-                   L.DynamicOpts.el_min.offset, L.DynamicOpts.free_ratio.offset, L.DynamicSummary.ms.offset]
-    assert got[0] == 80 == ctypes.sizeof(EmulOpts) and got[1] == 56
+    # the mirrors against the header: tests/test_abi.py, every struct at once; here the check program's own copy of the options
+    assert ctypes.sizeof(L.DynamicOpts) == 80 == ctypes.sizeof(EmulOpts) and ctypes.sizeof(L.DynamicSummary) == 56
     assert [f for f, _ in L.DynamicOpts._fields_] == [f for f, _ in EmulOpts._fields_]
     assert all(s in L.SYMBOLS for s in ("lvba_dynamic_default_opts", "lvba_dynamic_labels", "lvba_scans_select"))
     dyn = importlib.import_module("global-lvba_amd.dynamic")

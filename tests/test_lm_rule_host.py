@@ -4,7 +4,6 @@ max_iter = 0."""
 import ctypes
 import math
 import os
-import subprocess
 from types import SimpleNamespace
 
 import numpy as np
@@ -12,6 +11,7 @@ import pytest
 
 import posegraph_cases as pgc
 import posegraph_oracle as pg
+from host_build import build_check
 from oracle import balm_oracle as bo
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,10 +20,7 @@ OK, FACTORIZATION, NONFINITE = 0, 1, 2      # LVBA_OK, LVBA_NUM_* of include/lvb
 
 @pytest.fixture(scope="module")
 def rule(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("lm_rule") / "liblm_rule_check.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Werror", os.path.join(ROOT, "tests", "lm_rule_check.cpp"),
-                           "-o", so])
-    lib = ctypes.CDLL(so)
+    lib = ctypes.CDLL(build_check("lm_rule_check", tmp_path_factory.mktemp("lm_rule"), flags=("-O2", "-std=c++17", "-Wall", "-Werror")))
     lib.lmr_replay.argtypes = [ctypes.c_int, np.ctypeslib.ndpointer(np.float64, flags="C"), ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                ctypes.c_int, ctypes.c_int, np.ctypeslib.ndpointer(np.int32, flags="C"), np.ctypeslib.ndpointer(np.float64, flags="C")]
     lib.lmr_replay.restype = ctypes.c_int

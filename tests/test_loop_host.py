@@ -3,13 +3,11 @@ against the numpy restatement (tests/loop_oracle.py), the conditions on the shar
 §10d), the acceptance rule, the shared prior helper and the struct layouts."""
 import ctypes
 import importlib
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from host_build import build_check
 
 import loop_cases as lc
 import loop_oracle as lo
@@ -18,10 +16,7 @@ import register_oracle as ro
 
 @pytest.fixture(scope="module")
 def emul(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("emul_loop") / "libloop_check.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Werror", "-Wno-unknown-pragmas",
-                           os.path.join(ROOT, "tests", "loop_check.cpp"), "-o", so])
-    lib = ctypes.CDLL(so)
+    lib = ctypes.CDLL(build_check("loop_check", tmp_path_factory.mktemp("emul_loop")))
     f64 = np.ctypeslib.ndpointer(np.float64, flags="C")
     i32 = np.ctypeslib.ndpointer(np.int32, flags="C")
     lib.emul_candidates.argtypes = [ctypes.c_int, f64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
@@ -149,18 +144,9 @@ def test_shared_prior_helper_is_loop_closure_priors_arithmetic():
     assert not np.any(np.array(dead.sqrt_info[:]))
 
 
-def test_loop_struct_sizes_match_the_header(tmp_path):
+def test_loop_struct_sizes_match_the_header():
     L = importlib.import_module("global-lvba_amd._lib")
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "lvba_hip.h"\nint main(void){printf("%zu %zu %zu %zu %zu\\n", '
-                   'sizeof(lvba_loop_opts), sizeof(lvba_loop_candidate), offsetof(lvba_loop_opts, radius), '
-                   'offsetof(lvba_loop_candidate, ref), offsetof(lvba_loop_candidate, distance));return 0;}\n')
-    exe = str(tmp_path / "sz")
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe])
-    got = [int(t) for t in subprocess.check_output([exe]).split()]
-    assert got == [ctypes.sizeof(L.LoopOpts), ctypes.sizeof(L.LoopCandidate), L.LoopOpts.radius.offset, L.LoopCandidate.ref.offset,
-                   L.LoopCandidate.distance.offset]
-    assert got[0] == 24 and got[1] == 24
+    # the layout of lvba_loop_opts / lvba_loop_candidate against the header: tests/test_abi.py, every struct at once
     new = ("lvba_submaps_build", "lvba_submaps_count", "lvba_submaps_find_planes", "lvba_register_linearize_submaps",
            "lvba_register_scans_submaps", "lvba_loop_default_opts", "lvba_loop_candidates")
     assert all(s in L.SYMBOLS for s in new)

@@ -2,24 +2,18 @@
 against the brute-force restatement (tests/mapq_oracle.py), the lattice against its closed form, the struct layouts, and the
 restatement's own sanity: a map at the true poses is sharper than at the noisy ones."""
 import ctypes
-import importlib
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from host_build import build_check
 
 import mapq_oracle as mo
 
 
 @pytest.fixture(scope="module")
 def emul(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("emul_mapq") / "libmapq_check.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Werror", "-Wno-unknown-pragmas",
-                           os.path.join(ROOT, "tests", "mapq_check.cpp"), "-o", so])
-    lib = ctypes.CDLL(so)
+    lib = ctypes.CDLL(build_check("mapq_check", tmp_path_factory.mktemp("emul_mapq")))
     f64 = np.ctypeslib.ndpointer(np.float64, flags="C")
     f32 = np.ctypeslib.ndpointer(np.float32, flags="C")
     i64 = np.ctypeslib.ndpointer(np.int64, flags="C")
@@ -99,18 +93,6 @@ def test_lattice_against_closed_form(emul):
         assert np.abs(got["entropy"][inner] - mo.LATTICE_INTERIOR_ENTROPY).max() <= 1e-12
         assert abs(mo.LATTICE_INTERIOR_ENTROPY - (-1.781211936)) < 1e-9
         assert np.abs(got["plane_var"][inner] - 2 * 0.0625 / 7).max() <= 1e-15
-
-
-def test_struct_sizes_match_the_header(tmp_path):
-    L = importlib.import_module("global-lvba_amd._lib")
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "lvba_hip.h"\nint main(void){printf("%zu %zu %zu %zu\\n", '
-                   'sizeof(lvba_mapq_opts), sizeof(lvba_mapq_summary), offsetof(lvba_mapq_summary, mme), offsetof(lvba_mapq_summary, ms));return 0;}\n')
-    exe = str(tmp_path / "sz")
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe])
-    got = [int(t) for t in subprocess.check_output([exe]).split()]
-    assert got == [ctypes.sizeof(L.MapqOpts), ctypes.sizeof(L.MapqSummary), L.MapqSummary.mme.offset, L.MapqSummary.ms.offset]
-    assert got[0] == 16 and got[1] == 80
 
 
 def test_oracle_true_poses_give_the_sharper_map(emul):

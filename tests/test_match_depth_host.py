@@ -3,8 +3,6 @@ oracle against the rule as plain loops, the symmetry of the two orientations, th
 the oracle bit for bit, the fixture's conditions (margins, branches, special keypoints), and the claim -- textures that repeat
 along the epipolar line defeat the epipolar gate and come back under the depth gate."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,16 +10,13 @@ import pytest
 import match_cases as mc
 import match_depth_cases as mdc
 import match_depth_oracle as mdo
-from conftest import ROOT
+from host_build import build_check
 
 
 @pytest.fixture(scope="module")
 def emul(tmp_path_factory):
     """csrc/match_device.h compiled for the host, without contraction (tests/match_depth_check.cpp)"""
-    so = str(tmp_path_factory.mktemp("emul_match_depth") / "libmatch_depth_check.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Werror", "-Wno-unknown-pragmas",
-                           os.path.join(ROOT, "tests", "match_depth_check.cpp"), "-o", so])
-    lib = ctypes.CDLL(so)
+    lib = ctypes.CDLL(build_check("match_depth_check", tmp_path_factory.mktemp("emul_match_depth")))
     P = ctypes.c_void_p
     lib.emul_lift.argtypes = [ctypes.c_int64, P, P, P, ctypes.c_int, ctypes.c_int, P, P, P]
     lib.emul_predict.argtypes = [ctypes.c_int64, P, P, P, P, P]

@@ -3,9 +3,7 @@ the numpy oracle against the definition as plain loops, the signed-byte identity
 fixtures, the repeated-texture claim of the guided gate, the descriptor loader, and run_dataset's default path."""
 import ctypes
 import importlib
-import os
 import sqlite3
-import subprocess
 import sys
 
 import numpy as np
@@ -13,16 +11,13 @@ import pytest
 
 import match_cases as mc
 import match_oracle as mo
-from conftest import ROOT
+from host_build import build_check
 
 
 @pytest.fixture(scope="module")
 def emul(tmp_path_factory):
     """csrc/match_device.h compiled for the host, without contraction, walked as the kernel walks it (tests/match_check.cpp)"""
-    so = str(tmp_path_factory.mktemp("emul_match") / "libmatch_check.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Werror", "-Wno-unknown-pragmas",
-                           os.path.join(ROOT, "tests", "match_check.cpp"), "-o", so])
-    lib = ctypes.CDLL(so)
+    lib = ctypes.CDLL(build_check("match_check", tmp_path_factory.mktemp("emul_match")))
     for f in (lib.emul_essential, lib.emul_undistort, lib.emul_scan):
         f.restype = None
     lib.emul_scan.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,

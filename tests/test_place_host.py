@@ -3,13 +3,11 @@ numpy restatement (tests/place_oracle.py), the conditions on the shared fixtures
 struct layouts."""
 import ctypes
 import importlib
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from host_build import build_check
 
 import place_cases as pc
 import place_oracle as po
@@ -25,10 +23,7 @@ class EmulOpts(ctypes.Structure):
 
 @pytest.fixture(scope="module")
 def emul(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("emul_place") / "libplace_check.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Werror", "-Wno-unknown-pragmas",
-                           os.path.join(ROOT, "tests", "place_check.cpp"), "-o", so])
-    lib = ctypes.CDLL(so)
+    lib = ctypes.CDLL(build_check("place_check", tmp_path_factory.mktemp("emul_place")))
     f32, f64, i32 = (np.ctypeslib.ndpointer(t, flags="C") for t in (np.float32, np.float64, np.int32))
     lib.emul_descriptor.argtypes = [ctypes.c_int64, f32, ctypes.POINTER(EmulOpts), i32, f32, f32, f32]
     lib.emul_descriptor.restype = None
@@ -171,17 +166,8 @@ def test_two_lap_fixture_meets_its_conditions():
     assert accepted >= 8
 
 
-def test_place_struct_sizes_match_the_header(tmp_path):
+def test_place_struct_sizes_match_the_header():
     L = importlib.import_module("global-lvba_amd._lib")
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "lvba_hip.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu\\n", '
-                   'sizeof(lvba_place_opts), sizeof(lvba_place_candidate), offsetof(lvba_place_opts, submap_size), '
-                   'offsetof(lvba_place_opts, max_distance), offsetof(lvba_place_candidate, shift), offsetof(lvba_place_candidate, yaw));'
-                   'return 0;}\n')
-    exe = str(tmp_path / "sz")
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe])
-    got = [int(t) for t in subprocess.check_output([exe]).split()]
-    assert got == [ctypes.sizeof(L.PlaceOpts), ctypes.sizeof(L.PlaceCandidate), L.PlaceOpts.submap_size.offset, L.PlaceOpts.max_distance.offset,
-                   L.PlaceCandidate.shift.offset, L.PlaceCandidate.yaw.offset]
-    assert got[0] == 64 == ctypes.sizeof(EmulOpts) and got[1] == 32
+    # the mirrors against the header: tests/test_abi.py, every struct at once; here the check program's own copy of the options
+    assert ctypes.sizeof(L.PlaceOpts) == 64 == ctypes.sizeof(EmulOpts) and ctypes.sizeof(L.PlaceCandidate) == 32
     assert all(s in L.SYMBOLS for s in ("lvba_place_default_opts", "lvba_place_descriptors", "lvba_place_search", "lvba_place_candidates"))

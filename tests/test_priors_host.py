@@ -1,6 +1,5 @@
 """CPU tests of the LiDAR stage's pose priors: the numpy model (tests/prior_oracle.py) against central finite differences, the
 device header csrc/prior_device.h compiled for the host against the model, and the C-ABI / Python surface."""
-import ctypes
 import math
 import os
 import subprocess
@@ -149,16 +148,12 @@ def test_lin_record_holds_the_products_of_the_whitened_blocks(checked):
 def test_prior_struct_and_kinds_match_the_c_header(pkg, tmp_path):
     L = pkg._lib
     src = tmp_path / "prior.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "lvba_hip.h"\n'
-                   'int main(void){printf("%zu %zu %zu %zu %d %d %d\\n", sizeof(lvba_prior), offsetof(lvba_prior, meas), '
-                   'offsetof(lvba_prior, offset_j), offsetof(lvba_prior, sqrt_info), LVBA_PRIOR_POSE, LVBA_PRIOR_POSITION, '
-                   'LVBA_PRIOR_RELATIVE); return 0;}\n')
+    src.write_text('#include <stdio.h>\n#include "lvba_hip.h"\n'
+                   'int main(void){printf("%d %d %d\\n", LVBA_PRIOR_POSE, LVBA_PRIOR_POSITION, LVBA_PRIOR_RELATIVE); return 0;}\n')
     exe = str(tmp_path / "prior")
     subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe])
     v = [int(x) for x in subprocess.check_output([exe]).split()]
-    assert v[0] == ctypes.sizeof(L.Prior) and v[1] == L.Prior.meas.offset and v[2] == L.Prior.offset_j.offset
-    assert v[3] == L.Prior.sqrt_info.offset
-    assert v[4:] == [L.PRIOR_KINDS[k] for k in KINDS] == [po.KINDS[k] for k in KINDS]
+    assert v == [L.PRIOR_KINDS[k] for k in KINDS] == [po.KINDS[k] for k in KINDS]      # lvba_prior's layout: tests/test_abi.py
     assert {"lvba_balm_set_priors", "lvba_balm_prior_residuals"} <= set(L.SYMBOLS)
 
 

@@ -2,14 +2,12 @@
 which tasks get hypothesis blocks, where their block records start, the (task, first hypothesis) list that is the hypothesis
 kernel's grid, and the refusal above 2^30 - 1 blocks, which is decided in 64 bits before anything is built."""
 import ctypes
-import os
-import subprocess
 import time
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from host_build import build_check
 
 HB = 64                       # RANSAC_HB
 MAX_BLOCKS = 2 ** 30 - 1      # RANSAC_MAX_BLOCKS = INT32_MAX / 2, the bound the two stages had
@@ -20,10 +18,7 @@ UNTOUCHED = -7
 @pytest.fixture(scope="module")
 def emul(tmp_path_factory):
     """csrc/ransac_device.h compiled for the host (tests/ransac_check.cpp)"""
-    so = str(tmp_path_factory.mktemp("emul_ransac") / "libransac_check.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Werror", "-Wno-unknown-pragmas",
-                           os.path.join(ROOT, "tests", "ransac_check.cpp"), "-o", so])
-    lib = ctypes.CDLL(so)
+    lib = ctypes.CDLL(build_check("ransac_check", tmp_path_factory.mktemp("emul_ransac")))
     P, I, L = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
     lib.emul_plan.argtypes = [L, P, I, I, I, I, P, P, L, P, P]
     lib.emul_plan.restype = L

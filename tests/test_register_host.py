@@ -3,13 +3,11 @@ host against the numpy restatement (tests/register_oracle.py), the restatement's
 residual along the retraction, the conditions on the shared fixture, and the struct layouts."""
 import ctypes
 import importlib
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from host_build import build_check
 
 import register_cases as rc
 import register_oracle as ro
@@ -17,10 +15,7 @@ import register_oracle as ro
 
 @pytest.fixture(scope="module")
 def emul(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("emul_register") / "libregister_check.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Werror", "-Wno-unknown-pragmas",
-                           os.path.join(ROOT, "tests", "register_check.cpp"), "-o", so])
-    lib = ctypes.CDLL(so)
+    lib = ctypes.CDLL(build_check("register_check", tmp_path_factory.mktemp("emul_register")))
     f64 = np.ctypeslib.ndpointer(np.float64, flags="C")
     f32 = np.ctypeslib.ndpointer(np.float32, flags="C")
     u8 = np.ctypeslib.ndpointer(np.uint8, flags="C")
@@ -138,16 +133,7 @@ def test_fixture_meets_its_conditions():
     assert min(t["margin"] for t in res["trace"]) > 1e-9                     # every iteration is comparable across summation orders
 
 
-def test_struct_sizes_match_the_header(tmp_path):
+def test_struct_sizes_match_the_header():
     L = importlib.import_module("global-lvba_amd._lib")
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "lvba_hip.h"\nint main(void){printf("%zu %zu %zu %zu %zu\\n", '
-                   'sizeof(lvba_register_opts), sizeof(lvba_register_result), offsetof(lvba_register_opts, loss), '
-                   'offsetof(lvba_register_result, points), offsetof(lvba_register_result, min_eigenvalue));return 0;}\n')
-    exe = str(tmp_path / "sz")
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe])
-    got = [int(t) for t in subprocess.check_output([exe]).split()]
-    assert got == [ctypes.sizeof(L.RegisterOpts), ctypes.sizeof(L.RegisterResult), L.RegisterOpts.loss.offset,
-                   L.RegisterResult.points.offset, L.RegisterResult.min_eigenvalue.offset]
-    assert got[0] == 64 and got[1] == 56
+    # the layout of lvba_register_opts / lvba_register_result against the header: tests/test_abi.py, every struct at once
     assert all(s in L.SYMBOLS for s in ("lvba_register_default_opts", "lvba_register_linearize", "lvba_register_scans"))

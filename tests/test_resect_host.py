@@ -4,8 +4,6 @@ noise-free samples, the refits and the information matrix under measured toleran
 the fixtures claim, and the default paths of run_full_pipeline and run_dataset."""
 import ctypes
 import importlib
-import os
-import subprocess
 import sys
 
 import numpy as np
@@ -14,7 +12,7 @@ import pytest
 import resect_cases as rc
 import resect_oracle as ro
 import verify_oracle as vo
-from conftest import ROOT
+from host_build import build_check
 
 # The largest difference between the pose after the host emulation's refinement rounds (4 Gauss-Newton steps a round, Cholesky,
 # quaternion) and the oracle's (the same residual minimised to convergence with lstsq) over all fixtures that reach the refinement
@@ -43,10 +41,7 @@ INFO_D = 3.5e-11
 @pytest.fixture(scope="module")
 def emul(tmp_path_factory):
     """csrc/resect_device.h compiled for the host, without contraction (tests/resect_check.cpp)"""
-    so = str(tmp_path_factory.mktemp("emul_resect") / "libresect_check.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Werror", "-Wno-unknown-pragmas",
-                           os.path.join(ROOT, "tests", "resect_check.cpp"), "-o", so])
-    lib = ctypes.CDLL(so)
+    lib = ctypes.CDLL(build_check("resect_check", tmp_path_factory.mktemp("emul_resect")))
     P, D, I = ctypes.c_void_p, ctypes.c_double, ctypes.c_int32
     lib.emul_pack.argtypes = [I, P, P, P]
     lib.emul_pack.restype = None

@@ -5,8 +5,6 @@ argument checks."""
 import ctypes
 import importlib
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,7 +12,7 @@ import pytest
 import match_oracle as mo
 import sift_cases as sc
 import sift_oracle as so
-from conftest import ROOT
+from host_build import build_check
 
 # The fragile share a fixture may have (the condition of the issue), and what this file measures for the GPU tests:
 MAX_FRAGILE_SHARE = 0.02
@@ -42,10 +40,7 @@ def ft():
 @pytest.fixture(scope="module")
 def emul(tmp_path_factory):
     """csrc/sift_device.h compiled for the host, without contraction, walked as the kernels walk it (tests/sift_check.cpp)"""
-    so_path = str(tmp_path_factory.mktemp("emul_sift") / "libsift_check.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Werror", "-Wno-unknown-pragmas",
-                           os.path.join(ROOT, "tests", "sift_check.cpp"), "-o", so_path])
-    lib = ctypes.CDLL(so_path)
+    lib = ctypes.CDLL(build_check("sift_check", tmp_path_factory.mktemp("emul_sift")))
     V, I, D = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
     lib.emul_pow2.restype = D
     lib.emul_pow2.argtypes = [D]
@@ -78,14 +73,10 @@ def test_blur_taps_against_numpy(ft):
         assert e.value.code == L.ERR_ARG
 
 
-def test_options_struct_matches_the_header(tmp_path):
-    """lvba_sift_opts: ctypes' size is the C compiler's (the header compiled as C), the defaults are SiftGPU's five parameters."""
+def test_options_struct_matches_the_header():
+    """lvba_sift_opts: the defaults are SiftGPU's five parameters (the layout against the header: tests/test_abi.py)."""
     L = importlib.import_module("global-lvba_amd._lib")
-    src = tmp_path / "size.c"
-    src.write_text('#include <stdio.h>\n#include "lvba_hip.h"\nint main(void){printf("%zu\\n", sizeof(lvba_sift_opts));return 0;}\n')
-    exe = str(tmp_path / "size")
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe])
-    assert int(subprocess.check_output([exe])) == ctypes.sizeof(L.SiftOpts) == 56
+    assert ctypes.sizeof(L.SiftOpts) == 56
     o = importlib.import_module("global-lvba_amd.features").sift_opts()
     assert (o.first_octave, o.n_intervals, o.sigma0, o.dog_threshold, o.edge_threshold, o.orientation_window, o.max_orientations,
             o.max_features, o.chunk_images, o.reserved) == (-1, 3, 1.6, 0.01, 12.0, 3.0, 2, 8192, 0, 0)

@@ -124,12 +124,8 @@ def test_driver_under_the_sanitizers(sanitized_driver, tmp_path, name):
         check_against_the_mirror(run_driver(sanitized_driver, tmp_path, name, thr, lanes, attempts), name, thr, attempts)
 
 
-def test_info_struct_has_the_size_the_c_compiler_gives_it(pkg, tmp_path):
-    src = tmp_path / "size.c"
-    src.write_text('#include <stdio.h>\n#include "lvba_hip.h"\nint main(void){printf("%zu\\n", sizeof(lvba_trackgraph_info));return 0;}\n')
-    exe = str(tmp_path / "size")
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe])
-    assert int(subprocess.check_output([exe])) == 64 == ctypes.sizeof(pkg._lib.TrackGraphInfo)
+def test_info_struct_has_the_size_the_c_compiler_gives_it(pkg):
+    assert ctypes.sizeof(pkg._lib.TrackGraphInfo) == 64            # against the header: tests/test_abi.py, every struct at once
     assert {"lvba_trackgraph_create", "lvba_trackgraph_components", "lvba_trackgraph_orders", "lvba_trackgraph_destroy"} <= set(pkg._lib.SYMBOLS)
 
 

@@ -17,7 +17,7 @@ import match_oracle as mo
 import verify_h_cases as hc
 import verify_h_oracle as ho
 import verify_oracle as vo
-from conftest import ROOT
+from host_build import build_check
 
 # The largest difference between a refit of the host emulation (cyclic Jacobi) and the oracle's (LAPACK eigh) over all fixtures,
 # entry by entry, both of unit norm and of the sign the rule fixes, measured on the CPU: 1.16e-13
@@ -26,16 +26,12 @@ from conftest import ROOT
 REFIT_D = 1.2e-13
 REFIT_TOL = 10 * REFIT_D
 NEW_SYMBOLS = ("lvba_verify_pairs_model", "lvba_verify_hypotheses_homography", "lvba_verify_score_homography")
-SRC = os.path.join(ROOT, "tests", "verify_h_check.cpp")
-CXX = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", "-Wno-unknown-pragmas"]
 
 
 @pytest.fixture(scope="module")
 def emul(tmp_path_factory):
     """csrc/verify_device.h compiled for the host, without contraction (tests/verify_h_check.cpp)"""
-    so = str(tmp_path_factory.mktemp("emul_verify_h") / "libverify_h_check.so")
-    subprocess.check_call(CXX + ["-fPIC", "-shared", SRC, "-o", so])
-    lib = ctypes.CDLL(so)
+    lib = ctypes.CDLL(build_check("verify_h_check", tmp_path_factory.mktemp("emul_verify_h")))
     P = ctypes.c_void_p
     lib.emul_h_score.argtypes = [ctypes.c_int32, P, P, ctypes.c_double, P]
     lib.emul_h_score.restype = None
@@ -340,9 +336,9 @@ def test_run_dataset_hands_the_model_on(tmp_path, monkeypatch):
 def test_the_header_is_clean_under_the_host_sanitizers(tmp_path):
     """tests/verify_h_check.cpp as a stand-alone program (its own main: hypotheses, refit, score and choice on a synthetic plane
     with wrong matches and a NaN point) built with -fsanitize=address,undefined: it runs clean and finds the planted set."""
-    exe = str(tmp_path / "verify_h_main")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", "-Wno-unknown-pragmas", "-DVERIFY_H_MAIN",
-                           "-fsanitize=address,undefined", "-fno-sanitize-recover=all", SRC, "-o", exe])
+    exe = build_check("verify_h_check", tmp_path, shared=False,
+                      flags=("-O1", "-g", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", "-Wno-unknown-pragmas"),
+                      extra=("-DVERIFY_H_MAIN", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"))
     r = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))     # the leak checker needs ptrace, which a sandbox may deny
     print(r.stdout, r.stderr)
     assert r.returncode == 0 and "inliers 30 wrong 0" in r.stdout and "runtime error" not in r.stderr

@@ -3,8 +3,6 @@ DESIGN.md §10k): csrc/verify_device.h on the host against the numpy oracle to t
 tolerance, the margin condition of the fixtures, what the fixtures claim, and run_full_pipeline's default path."""
 import ctypes
 import importlib
-import os
-import subprocess
 import sys
 
 import numpy as np
@@ -13,7 +11,7 @@ import pytest
 import match_oracle as mo
 import verify_cases as vc
 import verify_oracle as vo
-from conftest import ROOT
+from host_build import build_check
 
 # The largest difference between a refit of the host emulation (Jacobi, eig3) and the oracle's (LAPACK eigh, svd) over all
 # fixtures, sign fixed and unit norm, measured on the CPU: 7.1e-12 (the eigen-gap of N is ~1e-6 of its norm) (test_refits_agree_within_the_measured_tolerance prints it).  The
@@ -25,10 +23,7 @@ REFIT_TOL = 10 * REFIT_D
 @pytest.fixture(scope="module")
 def emul(tmp_path_factory):
     """csrc/verify_device.h compiled for the host, without contraction (tests/verify_check.cpp)"""
-    so = str(tmp_path_factory.mktemp("emul_verify") / "libverify_check.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Werror", "-Wno-unknown-pragmas",
-                           os.path.join(ROOT, "tests", "verify_check.cpp"), "-o", so])
-    lib = ctypes.CDLL(so)
+    lib = ctypes.CDLL(build_check("verify_check", tmp_path_factory.mktemp("emul_verify")))
     P = ctypes.c_void_p
     lib.emul_sample.argtypes = [ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, P]
     lib.emul_sample.restype = None

@@ -1,7 +1,6 @@
 """CPU tests of the visual stage's robust losses (lvba_visual_set_loss): the reference model (tests/robust_visual_oracle.py)
 against calculus and against the plain oracle, the device header compiled for the host against the model, and the C-ABI
 additions compiled as C99 and through the adapter."""
-import ctypes
 import os
 import subprocess
 
@@ -133,18 +132,18 @@ def test_outlier_helper_leaves_synth_untouched(synth):
 
 
 def test_loss_struct_layout_and_c99_header(pkg, tmp_path):
-    """sizeof(lvba_loss) from gcc equals the ctypes mirror; the header (with its LVBA_LOSS_* kinds) stays plain C99."""
+    """The LVBA_LOSS_* kinds of the header, which stays plain C99, are the package's and the oracle's (lvba_loss's layout:
+    tests/test_abi.py)."""
     L = pkg._lib
     src = tmp_path / "loss.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "lvba_hip.h"\n'
-                   'int main(void){printf("%zu %zu %d %d %d %d %d %d\\n", sizeof(lvba_loss), offsetof(lvba_loss, scale), '
+    src.write_text('#include <stdio.h>\n#include "lvba_hip.h"\n'
+                   'int main(void){printf("%d %d %d %d %d %d\\n", '
                    'LVBA_LOSS_TRIVIAL, LVBA_LOSS_HUBER, LVBA_LOSS_SOFTLONE, LVBA_LOSS_CAUCHY, LVBA_LOSS_ARCTAN, LVBA_LOSS_TUKEY);'
                    'return 0;}\n')
     exe = str(tmp_path / "loss")
     subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe])
     v = [int(x) for x in subprocess.check_output([exe]).split()]
-    assert v[0] == ctypes.sizeof(L.Loss) == 16 and v[1] == L.Loss.scale.offset == 8
-    assert v[2:] == [L.LOSS_KINDS[k] for k in ["trivial"] + KINDS] == [rvo.KINDS[k] for k in ["trivial"] + KINDS]
+    assert v == [L.LOSS_KINDS[k] for k in ["trivial"] + KINDS] == [rvo.KINDS[k] for k in ["trivial"] + KINDS]
     assert {"lvba_visual_set_loss", "lvba_visual_residual_sq"} <= set(L.SYMBOLS)
 
 
