@@ -94,12 +94,10 @@ int32_t bs_ranks_agree(BlockSys &bs, const int64_t *v, int n, bool *same)
     if (n > 8) return lvba_fail(LVBA_ERR_ARG, "bs_ranks_agree: more than 8 values");
     int64_t buf[16];
     for (int e = 0; e < n; ++e) { buf[e] = v[e]; buf[n + e] = -v[e]; }
-    const size_t bytes = 2 * (size_t)n * sizeof(int64_t);
-    DevBuf d(bs.stream);
-    HIPCHK(d.alloc(bytes));
-    HIPCHK(hipMemcpyAsync(d.p, buf, bytes, hipMemcpyHostToDevice, bs.stream));
-    TRY(bs_comm_allreduce(bs, d.p, 2 * (size_t)n, ncclInt64, ncclMax));
-    HIPCHK(hipMemcpyAsync(buf, d.p, bytes, hipMemcpyDeviceToHost, bs.stream));
+    DevArr<int64_t> d(bs.stream);
+    HIPCHK(d.alloc(2 * (size_t)n)); HIPCHK(hipMemcpyAsync(d, buf, d.bytes(2 * (size_t)n), hipMemcpyHostToDevice, bs.stream));
+    TRY(bs_comm_allreduce(bs, d, 2 * (size_t)n, ncclInt64, ncclMax));
+    HIPCHK(hipMemcpyAsync(buf, d, d.bytes(2 * (size_t)n), hipMemcpyDeviceToHost, bs.stream));
     HIPCHK(hipStreamSynchronize(bs.stream));
     for (int e = 0; e < n; ++e) same[e] = buf[e] == -buf[n + e];
     return LVBA_OK;
@@ -257,12 +255,10 @@ int32_t bs_pattern_slots(BlockSys &bs, lvba::hvec<int64_t> &slots)
 int32_t bs_download_blocks(BlockSys &bs, const int64_t *slots, int64_t n, double *out)
 {
     if (n <= 0) return LVBA_OK;
-    DevBuf d_slots(bs.stream), d_buf(bs.stream);
-    HIPCHK(d_slots.alloc((size_t)n * sizeof(int64_t)));
-    HIPCHK(d_buf.alloc((size_t)n * 36 * sizeof(double)));
-    HIPCHK(lvba::copy_h2d(d_slots.as<int64_t>(), slots, (size_t)n * sizeof(int64_t)));
-    hipLaunchKernelGGL(hg_pack_kernel, dim3((unsigned)((36 * n + 255) / 256)), dim3(256), 0, bs.stream, bs.d_hg, d_slots.as<int64_t>(), n,
-                       bs.hblk_doubles, (int64_t)0, d_buf.as<double>());
+    DevArr<int64_t> d_slots(bs.stream); DevArr<double> d_buf(bs.stream);
+    HIPCHK(d_slots.alloc((size_t)n)); HIPCHK(d_buf.alloc((size_t)n * 36)); HIPCHK(d_slots.upload(slots, (size_t)n));
+    hipLaunchKernelGGL(hg_pack_kernel, dim3((unsigned)((36 * n + 255) / 256)), dim3(256), 0, bs.stream, bs.d_hg, d_slots, n,
+                       bs.hblk_doubles, (int64_t)0, d_buf);
     HIPCHK(hipGetLastError());
     const size_t total = (size_t)n * 36 * sizeof(double), slab = std::min<size_t>(total, (size_t)64 << 20);
     void *pin = nullptr;
@@ -270,7 +266,7 @@ int32_t bs_download_blocks(BlockSys &bs, const int64_t *slots, int64_t n, double
     int32_t rc = LVBA_OK;
     for (size_t o = 0; o < total && rc == LVBA_OK; o += slab) {
         const size_t nb = std::min(slab, total - o);
-        if (hipMemcpyAsync(pin, reinterpret_cast<const char *>(d_buf.as<double>()) + o, nb, hipMemcpyDeviceToHost, bs.stream) != hipSuccess ||
+        if (hipMemcpyAsync(pin, reinterpret_cast<const char *>(d_buf.p) + o, nb, hipMemcpyDeviceToHost, bs.stream) != hipSuccess ||
             hipStreamSynchronize(bs.stream) != hipSuccess)
             rc = LVBA_ERR_DEVICE;
         else
@@ -538,10 +534,10 @@ int32_t bs_build(BlockSys &bs, int32_t N, int64_t G, const int64_t *voff, const 
         TRY(bs_dmalloc(bs, &bs.d_csc_f, F));
         TRY(bs_dmalloc(bs, &bs.d_pos_of, F));
         TRY(bs_dmalloc(bs, &bs.d_pairs, Q));
-        DevBuf d_blk_of(bs.stream);
-        HIPCHK(d_blk_of.alloc(4 * (size_t)std::max<int64_t>(F, 1)));
+        DevArr<int32_t> d_blk_of(bs.stream);
+        HIPCHK(d_blk_of.alloc((size_t)std::max<int64_t>(F, 1)));
         TRY(csc_build(bs.stream, G, voff, F, pidx, N, bs.iperm.data(), bs.d_csc_f, bs.d_group_of_pos, bs.d_pos_of, bs.d_csc_off,
-                      d_blk_of.as<int32_t>()));
+                      d_blk_of));
         BS_MARK("csc");
         // Non-empty blocks, visited in 2-D TILES of the block matrix (8 x 8 poses): a tile's pairs touch only a slice of
         // 8 + 8 poses' Y segments (factors are sorted by voxel inside a segment), which stays L2-resident, whereas a
@@ -564,8 +560,8 @@ int32_t bs_build(BlockSys &bs, int32_t N, int64_t G, const int64_t *voff, const 
         if (bs.n_groups > 0) window_groups = 0;
         if (const char *e = getenv("LVBA_PAIR_WINDOW")) window_groups = atoll(e);
         // (the items of a window are laid out by length: a wavefront's ten items finish together)
-        TRY(pair_lists_build(bs.stream, G, voff, F, d_blk_of.as<int32_t>(), bs.d_pos_of, N, (int32_t)Bb1, Q, window_groups,
-                             LVBA_PAIR_CUT, bs.d_pairs, blk_slot, blk_off));
+        TRY(pair_lists_build(bs.stream, G, voff, F, d_blk_of, bs.d_pos_of, N, (int32_t)Bb1, Q, window_groups, LVBA_PAIR_CUT,
+                             bs.d_pairs, blk_slot, blk_off));
         BS_MARK("pairs");
         bs.nnzb = (int64_t)blk_slot.size();
         if (window_groups > 0) {
@@ -580,8 +576,8 @@ int32_t bs_build(BlockSys &bs, int32_t N, int64_t G, const int64_t *voff, const 
             const int64_t distinct = (int64_t)(std::unique(u.begin(), u.end()) - u.begin());
             if ((int64_t)blk_slot.size() > 24 * std::max<int64_t>(distinct, 1)) {
                 window_groups = 0;
-                TRY(pair_lists_build(bs.stream, G, voff, F, d_blk_of.as<int32_t>(), bs.d_pos_of, N, (int32_t)Bb1, Q, 0, 0,
-                                     bs.d_pairs, blk_slot, blk_off));
+                TRY(pair_lists_build(bs.stream, G, voff, F, d_blk_of, bs.d_pos_of, N, (int32_t)Bb1, Q, 0, 0, bs.d_pairs, blk_slot,
+                                     blk_off));
             }
         }
         { // distinct blocks, not runs

@@ -268,45 +268,41 @@ extern "C" int32_t lvba_closure_consistency(int32_t device, int32_t n_frames, co
     ScopedStream sg;
     HIPCHK(sg.acquire());
     const hipStream_t s = sg.s;
-    DevBuf d_X(s), d_ref(s), d_query(s), d_Z(s), d_prep(s), d_adj(s), d_rot(s), d_trans(s), d_deg(s), d_seeds(s), d_sets(s), d_size(s),
-        d_keep(s), d_nkeep(s);
-    HIPCHK(d_X.alloc(96 * (size_t)n_frames)); HIPCHK(d_ref.alloc(4 * (size_t)M)); HIPCHK(d_query.alloc(4 * (size_t)M));
-    HIPCHK(d_Z.alloc(96 * (size_t)M)); HIPCHK(d_prep.alloc(8 * (size_t)CLOSURE_PREP * M)); HIPCHK(d_adj.alloc(8 * (size_t)M * W));
-    if (rot) HIPCHK(d_rot.alloc(8 * MM));
-    if (trans) HIPCHK(d_trans.alloc(8 * MM));
-    HIPCHK(d_deg.alloc(4 * (size_t)M)); HIPCHK(d_seeds.alloc(4 * (size_t)n_seeds)); HIPCHK(d_sets.alloc(8 * (size_t)n_seeds * W));
-    HIPCHK(d_size.alloc(4 * (size_t)n_seeds)); HIPCHK(d_keep.alloc((size_t)M)); HIPCHK(d_nkeep.alloc(4));
-    HIPCHK(lvba::copy_h2d(d_X.p, poses, 96 * (size_t)n_frames));
-    HIPCHK(lvba::copy_h2d(d_ref.p, ref, 4 * (size_t)M));
-    HIPCHK(lvba::copy_h2d(d_query.p, query, 4 * (size_t)M));
-    HIPCHK(lvba::copy_h2d(d_Z.p, meas, 96 * (size_t)M));
-    closure_prepare_kernel<<<grid_for(M, PREP_BLOCK), PREP_BLOCK, 0, s>>>(M, d_X.as<double>(), d_ref.as<int32_t>(), d_query.as<int32_t>(),
-                                                                         d_Z.as<double>(), d_prep.as<double>());
+    DevArr<double> d_X(s); DevArr<int32_t> d_ref(s), d_query(s); DevArr<double> d_Z(s), d_prep(s); DevArr<uint64_t> d_adj(s);
+    DevArr<double> d_rot(s), d_trans(s); DevArr<int32_t> d_deg(s), d_seeds(s); DevArr<uint64_t> d_sets(s);
+    DevArr<int32_t> d_size(s); DevArr<uint8_t> d_keep(s); DevArr<int32_t> d_nkeep(s);
+    HIPCHK(d_X.alloc(12 * (size_t)n_frames)); HIPCHK(d_ref.alloc((size_t)M)); HIPCHK(d_query.alloc((size_t)M));
+    HIPCHK(d_Z.alloc(12 * (size_t)M)); HIPCHK(d_prep.alloc((size_t)CLOSURE_PREP * M)); HIPCHK(d_adj.alloc((size_t)M * W));
+    if (rot) HIPCHK(d_rot.alloc(MM));
+    if (trans) HIPCHK(d_trans.alloc(MM));
+    HIPCHK(d_deg.alloc((size_t)M)); HIPCHK(d_seeds.alloc((size_t)n_seeds)); HIPCHK(d_sets.alloc((size_t)n_seeds * W));
+    HIPCHK(d_size.alloc((size_t)n_seeds)); HIPCHK(d_keep.alloc((size_t)M)); HIPCHK(d_nkeep.alloc(1));
+    HIPCHK(d_X.upload(poses, 12 * (size_t)n_frames)); HIPCHK(d_ref.upload(ref, (size_t)M));
+    HIPCHK(d_query.upload(query, (size_t)M)); HIPCHK(d_Z.upload(meas, 12 * (size_t)M));
+    closure_prepare_kernel<<<grid_for(M, PREP_BLOCK), PREP_BLOCK, 0, s>>>(M, d_X, d_ref, d_query,
+                                                                         d_Z, d_prep);
     HIPCHK(hipGetLastError());
-    closure_pair_kernel<<<dim3(grid_for(W, PAIR_BLOCK / 64), M), PAIR_BLOCK, 0, s>>>(M, W, d_prep.as<double>(), d_ref.as<int32_t>(),
-                                                                                    d_query.as<int32_t>(), par, d_adj.as<uint64_t>(),
-                                                                                    rot ? d_rot.as<double>() : nullptr,
-                                                                                    trans ? d_trans.as<double>() : nullptr);
+    closure_pair_kernel<<<dim3(grid_for(W, PAIR_BLOCK / 64), M), PAIR_BLOCK, 0, s>>>(M, W, d_prep, d_ref,
+                                                                                    d_query, par, d_adj,
+                                                                                    rot ? d_rot : nullptr,
+                                                                                    trans ? d_trans : nullptr);
     HIPCHK(hipGetLastError());
-    closure_degree_kernel<<<grid_for(M, DEG_BLOCK / 64), DEG_BLOCK, 0, s>>>(M, W, d_adj.as<uint64_t>(), d_deg.as<int32_t>());
+    closure_degree_kernel<<<grid_for(M, DEG_BLOCK / 64), DEG_BLOCK, 0, s>>>(M, W, d_adj, d_deg);
     HIPCHK(hipGetLastError());
-    closure_seed_kernel<<<grid_for(M, SEED_BLOCK), SEED_BLOCK, 0, s>>>(M, n_seeds, d_deg.as<int32_t>(), d_seeds.as<int32_t>());
+    closure_seed_kernel<<<grid_for(M, SEED_BLOCK), SEED_BLOCK, 0, s>>>(M, n_seeds, d_deg, d_seeds);
     HIPCHK(hipGetLastError());
-    closure_set_kernel<<<n_seeds, SET_BLOCK, 0, s>>>(M, W, d_adj.as<uint64_t>(), d_deg.as<int32_t>(), d_seeds.as<int32_t>(),
-                                                     d_sets.as<uint64_t>(), d_size.as<int32_t>());
+    closure_set_kernel<<<n_seeds, SET_BLOCK, 0, s>>>(M, W, d_adj, d_deg, d_seeds, d_sets, d_size);
     HIPCHK(hipGetLastError());
-    closure_select_kernel<<<1, SEL_BLOCK, 0, s>>>(M, W, n_seeds, o.min_set, d_sets.as<uint64_t>(), d_size.as<int32_t>(), d_keep.as<uint8_t>(),
-                                                  d_nkeep.as<int32_t>());
+    closure_select_kernel<<<1, SEL_BLOCK, 0, s>>>(M, W, n_seeds, o.min_set, d_sets, d_size, d_keep, d_nkeep);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
     // everything has run: only now is anything of the caller's written
     std::vector<uint8_t> h_keep((size_t)M);
     int32_t h_nkeep = 0;
-    HIPCHK(lvba::copy_d2h(h_keep.data(), d_keep.p, (size_t)M));
-    HIPCHK(lvba::copy_d2h(&h_nkeep, d_nkeep.p, 4));
-    if (adjacency) HIPCHK(lvba::copy_d2h(adjacency, d_adj.p, 8 * (size_t)M * W));
-    if (rot) HIPCHK(lvba::copy_d2h(rot, d_rot.p, 8 * MM));
-    if (trans) HIPCHK(lvba::copy_d2h(trans, d_trans.p, 8 * MM));
+    HIPCHK(d_keep.download(h_keep.data(), (size_t)M)); HIPCHK(d_nkeep.download(&h_nkeep, 1));
+    if (adjacency) HIPCHK(d_adj.download(adjacency, (size_t)M * W));
+    if (rot) HIPCHK(d_rot.download(rot, MM));
+    if (trans) HIPCHK(d_trans.download(trans, MM));
     std::copy(h_keep.begin(), h_keep.end(), keep);
     *n_keep = h_nkeep;
     return LVBA_OK;

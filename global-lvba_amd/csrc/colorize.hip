@@ -38,14 +38,6 @@ namespace {
 
 constexpr uint32_t COL_SENT = 0xFFFFFFFFu; // key of a work item whose point is skipped (sorts after every pixel)
 
-// handle-owned device array (pool memory; the owner synchronises before it frees)
-struct Owned {
-    void *p = nullptr;
-    hipError_t alloc(size_t bytes) { return DevicePool::get().alloc(&p, bytes ? bytes : 8); }
-    void reset() { if (p) DevicePool::get().free(p); p = nullptr; }
-    template <class T> T *as() const { return (T *)p; }
-};
-
 } // namespace
 
 struct lvba_colorize_s {
@@ -57,13 +49,18 @@ struct lvba_colorize_s {
     bool thin = true;
     std::vector<int64_t> frame_off;
     std::vector<double> scan_times;
-    Owned world;      // [P][3] float
+    // handle-owned device arrays (no stream: every call has drained its own before it returned)
+    DevArr<float> world; // [P][3]
     int64_t n_merged = 0; // points emitted so far (merged position of the next one)
     // the running set: n points (key-sorted and one per leaf when thinning, else in merged order), capacity cap
     int64_t n = 0, cap = 0;
-    Owned xyz, rgb, key, d2, pos;
+    DevArr<float> xyz;   // [cap][3]
+    DevArr<uint8_t> rgb; // [cap][3]
+    DevArr<uint64_t> key;
+    DevArr<double> d2;
+    DevArr<int64_t> pos;
     double prof[6] = {0, 0, 0, 0, 0, 0}; // upload, projection, sort, walk, compaction, thinning (ms, accumulated)
-    ~lvba_colorize_s() // every call has drained its stream before it returned
+    ~lvba_colorize_s()
     {
         (void)hipSetDevice(device);
         world.reset(); xyz.reset(); rgb.reset(); key.reset(); d2.reset(); pos.reset();
@@ -179,25 +176,44 @@ __global__ void col_gather_kernel(int64_t n, const uint32_t *__restrict__ flag, 
     key2[o] = key[s]; d22[o] = d2[s]; pos2[o] = pos[s];
 }
 
+// the running set's five arrays for `cap` points, not yet the handle's; adopt() hands them over once the stream has drained, what is
+// not adopted drains the stream and goes back to the pool
+struct RunningSet {
+    DevArr<float> xyz; DevArr<uint8_t> rgb; DevArr<uint64_t> key; DevArr<double> d2; DevArr<int64_t> pos;
+    explicit RunningSet(hipStream_t s) : xyz(s), rgb(s), key(s), d2(s), pos(s) {}
+    int32_t alloc(size_t cap)
+    {
+        hipError_t e = xyz.alloc(3 * cap);
+        if (e == hipSuccess) e = rgb.alloc(3 * cap);
+        if (e == hipSuccess) e = key.alloc(cap);
+        if (e == hipSuccess) e = d2.alloc(cap);
+        if (e == hipSuccess) e = pos.alloc(cap);
+        return e == hipSuccess ? LVBA_OK : lvba_fail(e == hipErrorOutOfMemory ? LVBA_ERR_NOMEM : LVBA_ERR_DEVICE, "colour map: %s", hipGetErrorString(e));
+    }
+    void adopt(lvba_colorize_s *h, int64_t cap)
+    {
+        h->xyz.reset(xyz.release()); h->rgb.reset(rgb.release()); h->key.reset(key.release()); h->d2.reset(d2.release()); h->pos.reset(pos.release());
+        h->cap = cap;
+    }
+};
+
 // grow the running set to hold `need` points, keeping its first h->n
 int32_t ensure_capacity(lvba_colorize_s *h, int64_t need, hipStream_t s)
 {
     if (need <= h->cap) return LVBA_OK;
     const int64_t cap = std::max<int64_t>(need, h->cap + h->cap / 2);
-    Owned a[5];
-    const size_t sz[5] = {12, 3, 8, 8, 8};
-    Owned *cur[5] = {&h->xyz, &h->rgb, &h->key, &h->d2, &h->pos};
-    for (int f = 0; f < 5; ++f) {
-        const hipError_t e = a[f].alloc(sz[f] * (size_t)cap);
-        if (e != hipSuccess) {
-            for (int g = 0; g < f; ++g) a[g].reset();
-            return lvba_fail(e == hipErrorOutOfMemory ? LVBA_ERR_NOMEM : LVBA_ERR_DEVICE, "colour map: %s", hipGetErrorString(e));
-        }
-        if (h->n > 0) HIPCHK(hipMemcpyAsync(a[f].p, cur[f]->p, sz[f] * (size_t)h->n, hipMemcpyDeviceToDevice, s));
+    RunningSet a(s);
+    TRY(a.alloc((size_t)cap));
+    const size_t n = (size_t)h->n;
+    if (n > 0) {
+        HIPCHK(hipMemcpyAsync(a.xyz, h->xyz, a.xyz.bytes(3 * n), hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(a.rgb, h->rgb, a.rgb.bytes(3 * n), hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(a.key, h->key, a.key.bytes(n), hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(a.d2, h->d2, a.d2.bytes(n), hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(a.pos, h->pos, a.pos.bytes(n), hipMemcpyDeviceToDevice, s));
     }
     HIPCHK(hipStreamSynchronize(s));
-    for (int f = 0; f < 5; ++f) { cur[f]->reset(); *cur[f] = a[f]; }
-    h->cap = cap;
+    a.adopt(h, cap);
     return LVBA_OK;
 }
 
@@ -206,37 +222,27 @@ int32_t thin_running(lvba_colorize_s *h, hipStream_t s)
 {
     const int64_t n = h->n;
     if (n == 0) return LVBA_OK;
-    DevBuf idx(s), key_s(s), idx_s(s), flag(s), excl(s), pick(s);
-    HIPCHK(idx.alloc(4 * (size_t)n)); HIPCHK(key_s.alloc(8 * (size_t)n)); HIPCHK(idx_s.alloc(4 * (size_t)n));
-    HIPCHK(flag.alloc(4 * (size_t)n)); HIPCHK(excl.alloc(4 * (size_t)n)); HIPCHK(pick.alloc(4 * (size_t)n));
-    col_iota_kernel<<<grid_for(n, 256), 256, 0, s>>>(n, idx.as<uint32_t>());
+    DevArr<uint32_t> idx(s);
+    DevArr<uint64_t> key_s(s);
+    DevArr<uint32_t> idx_s(s), flag(s), excl(s), pick(s);
+    HIPCHK(idx.alloc((size_t)n)); HIPCHK(key_s.alloc((size_t)n)); HIPCHK(idx_s.alloc((size_t)n));
+    HIPCHK(flag.alloc((size_t)n)); HIPCHK(excl.alloc((size_t)n)); HIPCHK(pick.alloc((size_t)n));
+    col_iota_kernel<<<grid_for(n, 256), 256, 0, s>>>(n, idx);
     HIPCHK(hipGetLastError());
-    TRY(sort_pairs(s, h->key.as<uint64_t>(), key_s.as<uint64_t>(), idx.as<uint32_t>(), idx_s.as<uint32_t>(), (size_t)n, 63));
-    col_pick_kernel<<<grid_for(n, 256), 256, 0, s>>>(n, key_s.as<uint64_t>(), idx_s.as<uint32_t>(), h->d2.as<double>(),
-                                                     h->pos.as<int64_t>(), flag.as<uint32_t>(), pick.as<uint32_t>());
+    TRY(sort_pairs<uint64_t>(s, h->key, key_s, idx, idx_s, (size_t)n, 63));
+    col_pick_kernel<<<grid_for(n, 256), 256, 0, s>>>(n, key_s, idx_s, h->d2, h->pos, flag, pick);
     HIPCHK(hipGetLastError());
     int64_t N = 0;
-    TRY(count_flags(s, flag.as<uint32_t>(), excl.as<uint32_t>(), (size_t)n, &N));
-    Owned a[5];
-    const size_t sz[5] = {12, 3, 8, 8, 8};
+    TRY(count_flags(s, flag, excl, (size_t)n, &N));
+    RunningSet a(s);
     const int64_t cap = std::max<int64_t>(N, 1);
-    for (int f = 0; f < 5; ++f) {
-        const hipError_t e = a[f].alloc(sz[f] * (size_t)cap);
-        if (e != hipSuccess) {
-            for (int g = 0; g < f; ++g) a[g].reset();
-            return lvba_fail(e == hipErrorOutOfMemory ? LVBA_ERR_NOMEM : LVBA_ERR_DEVICE, "colour map: %s", hipGetErrorString(e));
-        }
-    }
-    col_gather_kernel<<<grid_for(n, 256), 256, 0, s>>>(n, flag.as<uint32_t>(), excl.as<uint32_t>(), pick.as<uint32_t>(),
-                                                       h->xyz.as<float>(), h->rgb.as<uint8_t>(), h->key.as<uint64_t>(),
-                                                       h->d2.as<double>(), h->pos.as<int64_t>(), a[0].as<float>(), a[1].as<uint8_t>(),
-                                                       a[2].as<uint64_t>(), a[3].as<double>(), a[4].as<int64_t>());
+    TRY(a.alloc((size_t)cap));
+    col_gather_kernel<<<grid_for(n, 256), 256, 0, s>>>(n, flag, excl, pick, h->xyz, h->rgb, h->key, h->d2, h->pos, a.xyz, a.rgb,
+                                                       a.key, a.d2, a.pos);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
-    Owned *cur[5] = {&h->xyz, &h->rgb, &h->key, &h->d2, &h->pos};
-    for (int f = 0; f < 5; ++f) { cur[f]->reset(); *cur[f] = a[f]; }
+    a.adopt(h, cap);
     h->n = N;
-    h->cap = cap;
     return LVBA_OK;
 }
 
@@ -248,47 +254,47 @@ int32_t run_batch(lvba_colorize_s *h, hipStream_t s, const std::vector<BatchImag
     const int64_t npix = (int64_t)h->width * h->height;
     EventTimer<7> ev;
     ev.rec(0, s);
-    DevBuf d_tab(s), d_R(s), d_t(s), d_img(s), key(s), val(s), key_s(s), val_s(s), zc(s), flag(s), excl(s), win(s);
-    HIPCHK(d_tab.alloc(sizeof(BatchImage) * B)); HIPCHK(d_R.alloc(72 * (size_t)B)); HIPCHK(d_t.alloc(24 * (size_t)B));
+    DevArr<BatchImage> d_tab(s);
+    DevArr<double> d_R(s), d_t(s);
+    DevArr<uint8_t> d_img(s);
+    DevArr<uint32_t> key(s), val(s), key_s(s), val_s(s);
+    DevArr<double> zc(s);
+    DevArr<uint32_t> flag(s), excl(s), win(s);
+    HIPCHK(d_tab.alloc((size_t)B)); HIPCHK(d_R.alloc(9 * (size_t)B)); HIPCHK(d_t.alloc(3 * (size_t)B));
     HIPCHK(d_img.alloc(3 * (size_t)npix * B));
     std::vector<double> R(9 * (size_t)B), t(3 * (size_t)B);
     for (int b = 0; b < B; ++b) {
         const int64_t k = img_of[b];
         std::copy(Rcw + 9 * k, Rcw + 9 * k + 9, R.begin() + 9 * b);
         std::copy(tcw + 3 * k, tcw + 3 * k + 3, t.begin() + 3 * b);
-        HIPCHK(hipMemcpyAsync(d_img.as<uint8_t>() + 3 * npix * b, bgr + 3 * npix * k, 3 * (size_t)npix, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d_img + 3 * npix * b, bgr + 3 * npix * k, 3 * (size_t)npix, hipMemcpyHostToDevice, s));
     }
-    HIPCHK(hipMemcpyAsync(d_tab.p, tab.data(), sizeof(BatchImage) * B, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_R.p, R.data(), 72 * (size_t)B, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_t.p, t.data(), 24 * (size_t)B, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_tab, tab.data(), d_tab.bytes(B), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_R, R.data(), d_R.bytes(R.size()), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_t, t.data(), d_t.bytes(t.size()), hipMemcpyHostToDevice, s));
     ev.rec(1, s);
-    HIPCHK(key.alloc(4 * (size_t)M)); HIPCHK(val.alloc(4 * (size_t)M)); HIPCHK(key_s.alloc(4 * (size_t)M));
-    HIPCHK(val_s.alloc(4 * (size_t)M)); HIPCHK(zc.alloc(8 * (size_t)M)); HIPCHK(flag.alloc(4 * (size_t)M));
-    HIPCHK(excl.alloc(4 * (size_t)M)); HIPCHK(win.alloc(4 * (size_t)M));
+    HIPCHK(key.alloc((size_t)M)); HIPCHK(val.alloc((size_t)M)); HIPCHK(key_s.alloc((size_t)M));
+    HIPCHK(val_s.alloc((size_t)M)); HIPCHK(zc.alloc((size_t)M)); HIPCHK(flag.alloc((size_t)M));
+    HIPCHK(excl.alloc((size_t)M)); HIPCHK(win.alloc((size_t)M));
     int64_t max_np = 0;
     for (const auto &x : tab) max_np = std::max(max_np, x.np);
-    col_project_kernel<<<dim3(grid_for(max_np, 256), B), 256, 0, s>>>(d_tab.as<BatchImage>(), h->world.as<float>(), d_R.as<double>(),
-                                                                      d_t.as<double>(), h->cam, h->width, h->height,
-                                                                      key.as<uint32_t>(), val.as<uint32_t>(), zc.as<double>());
+    col_project_kernel<<<dim3(grid_for(max_np, 256), B), 256, 0, s>>>(d_tab, h->world, d_R, d_t, h->cam, h->width, h->height, key,
+                                                                      val, zc);
     HIPCHK(hipGetLastError());
     ev.rec(2, s);
     unsigned bits = 1; // keys < B * npix, and the sentinel's low bits (all ones) above every one of them
     while (bits < 32 && ((uint64_t)1 << bits) - 1 < (uint64_t)B * npix) ++bits;
-    TRY(sort_pairs(s, key.as<uint32_t>(), key_s.as<uint32_t>(), val.as<uint32_t>(), val_s.as<uint32_t>(), (size_t)M, bits));
+    TRY(sort_pairs<uint32_t>(s, key, key_s, val, val_s, (size_t)M, bits));
     ev.rec(3, s);
-    col_walk_kernel<<<grid_for(M, 256), 256, 0, s>>>(M, key_s.as<uint32_t>(), val_s.as<uint32_t>(), zc.as<double>(), flag.as<uint32_t>(),
-                                                     win.as<uint32_t>());
+    col_walk_kernel<<<grid_for(M, 256), 256, 0, s>>>(M, key_s, val_s, zc, flag, win);
     HIPCHK(hipGetLastError());
     ev.rec(4, s);
     int64_t S = 0;
-    TRY(count_flags(s, flag.as<uint32_t>(), excl.as<uint32_t>(), (size_t)M, &S));
+    TRY(count_flags(s, flag, excl, (size_t)M, &S));
     if (S > 0) {
         TRY(ensure_capacity(h, h->n + S, s));
-        col_emit_kernel<<<grid_for(M, 256), 256, 0, s>>>(M, flag.as<uint32_t>(), excl.as<uint32_t>(), key_s.as<uint32_t>(),
-                                                         win.as<uint32_t>(), d_tab.as<BatchImage>(), npix, h->world.as<float>(),
-                                                         d_img.as<uint8_t>(), h->leaf, h->thin ? 1 : 0, h->n, h->n_merged,
-                                                         h->xyz.as<float>(), h->rgb.as<uint8_t>(), h->key.as<uint64_t>(),
-                                                         h->d2.as<double>(), h->pos.as<int64_t>());
+        col_emit_kernel<<<grid_for(M, 256), 256, 0, s>>>(M, flag, excl, key_s, win, d_tab, npix, h->world, d_img, h->leaf,
+                                                         h->thin ? 1 : 0, h->n, h->n_merged, h->xyz, h->rgb, h->key, h->d2, h->pos);
         HIPCHK(hipGetLastError());
     }
     ev.rec(5, s);
@@ -349,20 +355,21 @@ extern "C" int32_t lvba_colorize_create(lvba_scans_t sc, const double *scan_pose
     h->scan_times.assign(scan_times, scan_times + nf);
     const int64_t P = h->frame_off[nf];
     if (P >= ((int64_t)1 << 32)) return lvba_fail(LVBA_ERR_ARG, "%lld points (at most 2^32 - 1)", (long long)P);
-    HIPCHK(h->world.alloc(12 * (size_t)std::max<int64_t>(P, 1)));
+    HIPCHK(h->world.alloc(3 * (size_t)std::max<int64_t>(P, 1)));
     if (P > 0) {
         ScopedStream sg;
         HIPCHK(sg.acquire());
         const hipStream_t s = sg.s;
-        DevBuf d_poses(s), d_err(s);
-        HIPCHK(d_poses.alloc(96 * (size_t)nf)); HIPCHK(d_err.alloc(4));
-        HIPCHK(hipMemcpyAsync(d_poses.p, scan_poses, 96 * (size_t)nf, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemsetAsync(d_err.p, 0, 4, s));
-        col_world_kernel<<<grid_for(P, 256), 256, 0, s>>>(P, sc->d_pts, sc->d_frame_off, nf, d_poses.as<double>(), h->leaf,
-                                                          h->thin ? 1 : 0, h->world.as<float>(), d_err.as<int>());
+        DevArr<double> d_poses(s);
+        DevArr<int> d_err(s);
+        HIPCHK(d_poses.alloc(12 * (size_t)nf)); HIPCHK(d_err.alloc(1));
+        HIPCHK(hipMemcpyAsync(d_poses, scan_poses, d_poses.bytes(12 * (size_t)nf), hipMemcpyHostToDevice, s));
+        HIPCHK(d_err.zero_async(1));
+        col_world_kernel<<<grid_for(P, 256), 256, 0, s>>>(P, sc->d_pts, sc->d_frame_off, nf, d_poses, h->leaf, h->thin ? 1 : 0,
+                                                          h->world, d_err);
         HIPCHK(hipGetLastError());
         int err = 0;
-        HIPCHK(hipMemcpyAsync(&err, d_err.p, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&err, d_err, d_err.bytes(1), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         if (err) return lvba_fail(LVBA_ERR_ARG, "a world point lies outside +-2^20 leaves of %g m", h->leaf);
     }
@@ -427,8 +434,8 @@ extern "C" int32_t lvba_colorize_download(lvba_colorize_t h, float *xyz, uint8_t
     if (!h || (h->n > 0 && (!xyz || !rgb))) return lvba_fail(LVBA_ERR_ARG, "null argument");
     if (h->n == 0) return LVBA_OK;
     HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipMemcpy(xyz, h->xyz.p, 12 * (size_t)h->n, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(rgb, h->rgb.p, 3 * (size_t)h->n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(xyz, h->xyz, h->xyz.bytes(3 * (size_t)h->n), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(rgb, h->rgb, h->rgb.bytes(3 * (size_t)h->n), hipMemcpyDeviceToHost));
     return LVBA_OK;
 }
 

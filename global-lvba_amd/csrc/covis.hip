@@ -200,18 +200,17 @@ int32_t check_call(lvba_depth_t depth, const double *Rcw, const double *tcw, con
 
 // the device side of a call (M >= 1): the poses and the sample table; with counts, n_points [M] and counts [M][M] behind it
 struct CovisWork {
-    DevBuf R, t, world, n_points, counts;
+    DevArr<double> R, t, world; DevArr<int32_t> n_points, counts;
     explicit CovisWork(hipStream_t s) : R(s), t(s), world(s), n_points(s), counts(s) {}
 };
 
 int32_t run_lift(hipStream_t s, lvba_depth_t depth, const double *Rcw, const double *tcw, const CovisCall &c, CovisWork &w)
 {
     const size_t M = (size_t)c.sh.M;
-    HIPCHK(w.R.alloc(72 * M)); HIPCHK(w.t.alloc(24 * M)); HIPCHK(w.world.alloc(24 * M * (size_t)c.sh.G));
-    HIPCHK(lvba::copy_h2d(w.R.p, Rcw, 72 * M));
-    HIPCHK(lvba::copy_h2d(w.t.p, tcw, 24 * M));
-    covis_lift_kernel<<<grid_for((int64_t)M * c.sh.G, COVIS_BLOCK), COVIS_BLOCK, 0, s>>>(c.sh, depth->d_depth, w.R.as<double>(), w.t.as<double>(),
-                                                                                      c.cam, w.world.as<double>());
+    HIPCHK(w.R.alloc(9 * M)); HIPCHK(w.t.alloc(3 * M)); HIPCHK(w.world.alloc(3 * M * (size_t)c.sh.G));
+    HIPCHK(w.R.upload(Rcw, 9 * M)); HIPCHK(w.t.upload(tcw, 3 * M));
+    covis_lift_kernel<<<grid_for((int64_t)M * c.sh.G, COVIS_BLOCK), COVIS_BLOCK, 0, s>>>(c.sh, depth->d_depth, w.R, w.t,
+                                                                                      c.cam, w.world);
     HIPCHK(hipGetLastError());
     return LVBA_OK;
 }
@@ -220,10 +219,10 @@ int32_t run_counts(hipStream_t s, lvba_depth_t depth, const double *Rcw, const d
 {
     TRY(run_lift(s, depth, Rcw, tcw, c, w));
     const int M = c.sh.M, groups = (M + COVIS_WAVES - 1) / COVIS_WAVES;
-    HIPCHK(w.n_points.alloc(4 * (size_t)M)); HIPCHK(w.counts.alloc(4 * (size_t)M * M));
-    covis_count_kernel<<<(unsigned)((int64_t)M * groups), COVIS_BLOCK, 0, s>>>(c.sh, groups, w.world.as<double>(), depth->d_depth,
-                                                                              w.R.as<double>(), w.t.as<double>(), c.cam, c.rule,
-                                                                              w.n_points.as<int32_t>(), w.counts.as<int32_t>());
+    HIPCHK(w.n_points.alloc((size_t)M)); HIPCHK(w.counts.alloc((size_t)M * M));
+    covis_count_kernel<<<(unsigned)((int64_t)M * groups), COVIS_BLOCK, 0, s>>>(c.sh, groups, w.world, depth->d_depth,
+                                                                              w.R, w.t, c.cam, c.rule,
+                                                                              w.n_points, w.counts);
     HIPCHK(hipGetLastError());
     return LVBA_OK;
 }
@@ -251,7 +250,7 @@ extern "C" int32_t lvba_covis_samples(lvba_depth_t depth, const double *Rcw, con
     CovisWork w(sg.s);
     TRY(run_lift(sg.s, depth, Rcw, tcw, c, w));
     HIPCHK(hipStreamSynchronize(sg.s));
-    HIPCHK(lvba::copy_d2h(world, w.world.p, 24 * (size_t)c.sh.M * c.sh.G));
+    HIPCHK(w.world.download(world, 3 * (size_t)c.sh.M * c.sh.G));
     return LVBA_OK;
 }
 
@@ -268,8 +267,7 @@ extern "C" int32_t lvba_covis_counts(lvba_depth_t depth, const double *Rcw, cons
     CovisWork w(sg.s);
     TRY(run_counts(sg.s, depth, Rcw, tcw, c, w));
     HIPCHK(hipStreamSynchronize(sg.s));
-    HIPCHK(lvba::copy_d2h(n_points, w.n_points.p, 4 * (size_t)c.sh.M));
-    HIPCHK(lvba::copy_d2h(counts, w.counts.p, 4 * (size_t)c.sh.M * c.sh.M));
+    HIPCHK(w.n_points.download(n_points, (size_t)c.sh.M)); HIPCHK(w.counts.download(counts, (size_t)c.sh.M * c.sh.M));
     return LVBA_OK;
 }
 
@@ -288,32 +286,33 @@ extern "C" int32_t lvba_covis_pairs(lvba_depth_t depth, const double *Rcw, const
     hipStream_t s = sg.s;
     CovisWork w(s);
     TRY(run_counts(s, depth, Rcw, tcw, c, w));
-    const int32_t *d_n = w.n_points.as<int32_t>(), *d_c = w.counts.as<int32_t>();
-    DevBuf d_kth(s), d_row(s), d_first(s), d_pairs(s), d_score(s), d_shared(s);
+    const int32_t *d_n = w.n_points, *d_c = w.counts;
+    DevArr<CovisRank> d_kth(s); DevArr<uint32_t> d_row(s), d_first(s); DevArr<int32_t> d_pairs(s); DevArr<double> d_score(s);
+    DevArr<int32_t> d_shared(s);
     const CovisRank *kth = nullptr;
     const int K = c.rule.max_per_image;
     if (K > 0 && K < M - 1) { // with K >= M - 1 every partner is within the cap
-        HIPCHK(d_kth.alloc(sizeof(CovisRank) * (size_t)M));
-        covis_select_kernel<<<grid_for(M, COVIS_WAVES), COVIS_BLOCK, 0, s>>>(M, K, d_n, d_c, c.rule, d_kth.as<CovisRank>());
+        HIPCHK(d_kth.alloc((size_t)M));
+        covis_select_kernel<<<grid_for(M, COVIS_WAVES), COVIS_BLOCK, 0, s>>>(M, K, d_n, d_c, c.rule, d_kth);
         HIPCHK(hipGetLastError());
-        kth = d_kth.as<CovisRank>();
+        kth = d_kth;
     }
-    HIPCHK(d_row.alloc(4 * ((size_t)M + 1))); HIPCHK(d_first.alloc(4 * ((size_t)M + 1)));
-    covis_flag_kernel<<<grid_for(M + 1, COVIS_WAVES), COVIS_BLOCK, 0, s>>>(M, d_n, d_c, c.rule, kth, d_row.as<uint32_t>());
+    HIPCHK(d_row.alloc((size_t)M + 1)); HIPCHK(d_first.alloc((size_t)M + 1));
+    covis_flag_kernel<<<grid_for(M + 1, COVIS_WAVES), COVIS_BLOCK, 0, s>>>(M, d_n, d_c, c.rule, kth, d_row);
     HIPCHK(hipGetLastError());
-    TRY(scan_excl<uint32_t>(s, d_row.as<uint32_t>(), d_first.as<uint32_t>(), (size_t)M + 1));
+    TRY(scan_excl<uint32_t>(s, d_row, d_first, (size_t)M + 1));
     uint32_t found = 0;
-    HIPCHK(lvba::copy_d2h(&found, d_first.as<uint32_t>() + M, 4));
+    HIPCHK(copy_d2h(&found, d_first + M, d_first.bytes(1)));
     const int64_t n_out = std::min<int64_t>(found, capacity);
     if (n_out > 0) {
-        HIPCHK(d_pairs.alloc(8 * (size_t)n_out)); HIPCHK(d_score.alloc(8 * (size_t)n_out)); HIPCHK(d_shared.alloc(8 * (size_t)n_out));
-        covis_write_kernel<<<grid_for(M, COVIS_WAVES), COVIS_BLOCK, 0, s>>>(M, d_n, d_c, c.rule, kth, d_first.as<uint32_t>(), n_out,
-                                                                          d_pairs.as<int32_t>(), d_score.as<double>(), d_shared.as<int32_t>());
+        HIPCHK(d_pairs.alloc(2 * (size_t)n_out)); HIPCHK(d_score.alloc((size_t)n_out)); HIPCHK(d_shared.alloc(2 * (size_t)n_out));
+        covis_write_kernel<<<grid_for(M, COVIS_WAVES), COVIS_BLOCK, 0, s>>>(M, d_n, d_c, c.rule, kth, d_first, n_out,
+                                                                          d_pairs, d_score, d_shared);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(s));
-        HIPCHK(lvba::copy_d2h(pairs, d_pairs.p, 8 * (size_t)n_out));
-        if (score) HIPCHK(lvba::copy_d2h(score, d_score.p, 8 * (size_t)n_out));
-        if (shared) HIPCHK(lvba::copy_d2h(shared, d_shared.p, 8 * (size_t)n_out));
+        HIPCHK(d_pairs.download(pairs, 2 * (size_t)n_out));
+        if (score) HIPCHK(d_score.download(score, (size_t)n_out));
+        if (shared) HIPCHK(d_shared.download(shared, 2 * (size_t)n_out));
     }
     *count = found;
     return LVBA_OK;

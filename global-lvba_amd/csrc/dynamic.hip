@@ -200,38 +200,38 @@ extern "C" int32_t lvba_dynamic_labels(lvba_scans_t sc, const double *scan_poses
     HIPCHK(sg.acquire());
     const hipStream_t s = sg.s;
     EventTimer<4> ev;
-    DevBuf d_poses(s), d_chunk(s), d_img(s), d_dil(s), d_nf(s), d_ns(s), d_label(s), d_part(s);
+    DevArr<double> d_poses(s); DevArr<int64_t> d_chunk(s); DevArr<uint32_t> d_img(s), d_dil(s);
+    DevArr<int32_t> d_nf(s), d_ns(s); DevArr<uint8_t> d_label(s); DevArr<int32_t> d_part(s);
     const unsigned label_grid = grid_for(P, 256);
-    HIPCHK(d_poses.alloc(96 * (size_t)n_frames)); HIPCHK(d_chunk.alloc(8 * ((size_t)n_frames + 1)));
-    HIPCHK(d_img.alloc(4 * (size_t)cells * B)); HIPCHK(d_dil.alloc(4 * (size_t)cells * B));
-    HIPCHK(d_nf.alloc(4 * (size_t)P)); HIPCHK(d_ns.alloc(4 * (size_t)P)); HIPCHK(d_label.alloc((size_t)P));
-    HIPCHK(d_part.alloc(8 * (size_t)label_grid));
-    HIPCHK(hipMemcpyAsync(d_poses.p, scan_poses, 96 * (size_t)n_frames, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_chunk.p, chunk.data(), 8 * ((size_t)n_frames + 1), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(d_nf.p, 0, 4 * (size_t)P, s));
-    HIPCHK(hipMemsetAsync(d_ns.p, 0, 4 * (size_t)P, s));
+    HIPCHK(d_poses.alloc(12 * (size_t)n_frames)); HIPCHK(d_chunk.alloc((size_t)n_frames + 1));
+    HIPCHK(d_img.alloc((size_t)cells * B)); HIPCHK(d_dil.alloc((size_t)cells * B));
+    HIPCHK(d_nf.alloc((size_t)P)); HIPCHK(d_ns.alloc((size_t)P)); HIPCHK(d_label.alloc((size_t)P));
+    HIPCHK(d_part.alloc(2 * (size_t)label_grid));
+    HIPCHK(hipMemcpyAsync(d_poses, scan_poses, d_poses.bytes(12 * (size_t)n_frames), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_chunk, chunk.data(), d_chunk.bytes((size_t)n_frames + 1), hipMemcpyHostToDevice, s));
+    HIPCHK(d_nf.zero_async((size_t)P)); HIPCHK(d_ns.zero_async((size_t)P));
     const float *d_pts = sc->d_pts + 3 * off[0];
     const int64_t *d_off = sc->d_frame_off + frame_begin;
     for (int b0 = 0; b0 < n_frames; b0 += B) {
         const int b1 = std::min(n_frames, b0 + B), nb = b1 - b0;
         const int64_t np = off[b1] - off[b0], nc = cells * nb;
         ev.rec(0, s);
-        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)d_img.p, (int)DYN_EMPTY_BITS, (size_t)nc, s));
+        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)d_img, (int)DYN_EMPTY_BITS, (size_t)nc, s));
         if (np > 0) {
-            dyn_image_kernel<<<grid_for(np, 256), 256, 0, s>>>(np, d_pts + 3 * (off[b0] - off[0]), d_off + b0, nb, p, d_img.as<uint32_t>());
+            dyn_image_kernel<<<grid_for(np, 256), 256, 0, s>>>(np, d_pts + 3 * (off[b0] - off[0]), d_off + b0, nb, p, d_img);
             HIPCHK(hipGetLastError());
         }
         ev.rec(1, s);
-        dyn_dilate_kernel<<<grid_for(nc, 256), 256, 0, s>>>(nc, p, d_img.as<uint32_t>(), d_dil.as<uint32_t>());
+        dyn_dilate_kernel<<<grid_for(nc, 256), 256, 0, s>>>(nc, p, d_img, d_dil);
         HIPCHK(hipGetLastError());
         ev.rec(2, s);
         // the frames whose window reaches into the batch
         const int fa = p.window <= 0 ? 0 : std::max(0, b0 - p.window), fb = p.window <= 0 ? n_frames : std::min(n_frames, b1 + p.window);
         const int64_t blocks = chunk[(size_t)fb] - chunk[(size_t)fa];
         if (blocks > 0) {
-            dyn_vote_kernel<<<(unsigned)blocks, DYN_BLOCK, 0, s>>>(d_pts, d_off, d_chunk.as<int64_t>(), chunk[(size_t)fa], n_frames,
-                                                                   d_poses.as<double>(), d_dil.as<float>(), b0, b1, p, d_nf.as<int32_t>(),
-                                                                   d_ns.as<int32_t>());
+            // d_dil.as<float>(): the range images are written as ordered bit patterns and read as floats
+            dyn_vote_kernel<<<(unsigned)blocks, DYN_BLOCK, 0, s>>>(d_pts, d_off, d_chunk, chunk[(size_t)fa], n_frames, d_poses,
+                                                                   d_dil.as<float>(), b0, b1, p, d_nf, d_ns);
             HIPCHK(hipGetLastError());
         }
         ev.rec(3, s);
@@ -239,18 +239,18 @@ extern "C" int32_t lvba_dynamic_labels(lvba_scans_t sc, const double *scan_poses
         summary->ms[0] += ev.ms(0, 1); summary->ms[1] += ev.ms(1, 2); summary->ms[2] += ev.ms(2, 3);
     }
     ev.rec(0, s);
-    dyn_label_kernel<<<label_grid, 256, 0, s>>>(P, d_nf.as<int32_t>(), d_ns.as<int32_t>(), p, d_label.as<uint8_t>(), d_part.as<int32_t>());
+    dyn_label_kernel<<<label_grid, 256, 0, s>>>(P, d_nf, d_ns, p, d_label, d_part);
     HIPCHK(hipGetLastError());
     ev.rec(1, s);
     HIPCHK(hipStreamSynchronize(s));
     summary->ms[2] += ev.ms(0, 1);
     const double t0 = now_ms();
     std::vector<int32_t> part(2 * (size_t)label_grid);
-    HIPCHK(copy_d2h(part.data(), d_part.p, 8 * (size_t)label_grid));
+    HIPCHK(d_part.download(part.data(), 2 * (size_t)label_grid));
     for (size_t k = 0; k < (size_t)label_grid; ++k) { summary->n_judged += part[2 * k]; summary->n_dynamic += part[2 * k + 1]; }
-    if (label) HIPCHK(copy_d2h(label, d_label.p, (size_t)P));
-    if (n_free) HIPCHK(copy_d2h(n_free, d_nf.p, 4 * (size_t)P));
-    if (n_support) HIPCHK(copy_d2h(n_support, d_ns.p, 4 * (size_t)P));
+    if (label) HIPCHK(d_label.download(label, (size_t)P));
+    if (n_free) HIPCHK(d_nf.download(n_free, (size_t)P));
+    if (n_support) HIPCHK(d_ns.download(n_support, (size_t)P));
     summary->ms[3] = now_ms() - t0;
     return LVBA_OK;
 }
@@ -274,21 +274,20 @@ extern "C" int32_t lvba_scans_select(lvba_scans_t sc, const uint8_t *keep, lvba_
     ScopedStream sg;
     HIPCHK(sg.acquire());
     const hipStream_t s = sg.s;
-    DevBuf d_keep(s), d_flag(s), d_excl(s), d_new(s);
-    HIPCHK(d_keep.alloc((size_t)P)); HIPCHK(d_flag.alloc(4 * ((size_t)P + 1))); HIPCHK(d_excl.alloc(4 * ((size_t)P + 1)));
-    HIPCHK(d_new.alloc(8 * ((size_t)nf + 1)));
-    HIPCHK(copy_h2d(d_keep.p, keep, (size_t)P));
-    sel_flag_kernel<<<grid_for(P + 1, 256), 256, 0, s>>>(P, d_keep.as<uint8_t>(), d_flag.as<uint32_t>());
+    DevArr<uint8_t> d_keep(s); DevArr<uint32_t> d_flag(s), d_excl(s); DevArr<int64_t> d_new(s);
+    HIPCHK(d_keep.alloc((size_t)P)); HIPCHK(d_flag.alloc((size_t)P + 1)); HIPCHK(d_excl.alloc((size_t)P + 1));
+    HIPCHK(d_new.alloc((size_t)nf + 1)); HIPCHK(d_keep.upload(keep, (size_t)P));
+    sel_flag_kernel<<<grid_for(P + 1, 256), 256, 0, s>>>(P, d_keep, d_flag);
     HIPCHK(hipGetLastError());
-    TRY(scan_excl<uint32_t>(s, d_flag.as<uint32_t>(), d_excl.as<uint32_t>(), (size_t)P + 1));
-    sel_offsets_kernel<<<grid_for((int64_t)nf + 1, 256), 256, 0, s>>>(nf, sc->d_frame_off, d_excl.as<uint32_t>(), d_new.as<int64_t>());
+    TRY(scan_excl<uint32_t>(s, d_flag, d_excl, (size_t)P + 1));
+    sel_offsets_kernel<<<grid_for((int64_t)nf + 1, 256), 256, 0, s>>>(nf, sc->d_frame_off, d_excl, d_new);
     HIPCHK(hipGetLastError());
     std::vector<int64_t> new_off((size_t)nf + 1, 0);
-    HIPCHK(hipMemcpyAsync(new_off.data(), d_new.p, 8 * ((size_t)nf + 1), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(new_off.data(), d_new, d_new.bytes((size_t)nf + 1), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     for (int f = 0; f < nf; ++f) count[(size_t)f] = new_off[(size_t)f + 1] - new_off[(size_t)f];
     TRY(scans_build(sc->device, nf, count.data(), nullptr, nullptr, 0, &res));
-    sel_scatter_kernel<<<grid_for(P, 256), 256, 0, s>>>(P, sc->d_pts, d_flag.as<uint32_t>(), d_excl.as<uint32_t>(), res->d_pts);
+    sel_scatter_kernel<<<grid_for(P, 256), 256, 0, s>>>(P, sc->d_pts, d_flag, d_excl, res->d_pts);
     const hipError_t e = hipGetLastError() == hipSuccess ? hipStreamSynchronize(s) : hipErrorUnknown;
     if (e != hipSuccess) {
         lvba_scans_destroy(res);

@@ -153,34 +153,34 @@ extern "C" int32_t lvba_depth_render(lvba_scans_t sc, const double *scan_poses, 
     // every pixel starts at +inf
     HIPCHK(hipMemsetD32Async((hipDeviceptr_t)h->d_depth, 0x7f800000, (size_t)(n_images * npix), s));
     if (P > 0) {
-        DevBuf d_poses(s), world(s), key(s), idx(s), key_s(s), order(s), head(s), incl(s), vop(s), voff(s), d_err(s), d_R(s), d_t(s);
-        HIPCHK(d_poses.alloc(96 * (size_t)nf)); HIPCHK(world.alloc(24 * (size_t)P)); HIPCHK(key.alloc(8 * (size_t)P));
-        HIPCHK(idx.alloc(4 * (size_t)P)); HIPCHK(key_s.alloc(8 * (size_t)P)); HIPCHK(order.alloc(4 * (size_t)P));
-        HIPCHK(head.alloc(4 * (size_t)P)); HIPCHK(incl.alloc(4 * (size_t)P)); HIPCHK(vop.alloc(4 * (size_t)P)); HIPCHK(d_err.alloc(4));
-        HIPCHK(d_R.alloc(72 * (size_t)n_images)); HIPCHK(d_t.alloc(24 * (size_t)n_images));
-        HIPCHK(hipMemcpyAsync(d_poses.p, scan_poses, 96 * (size_t)nf, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(d_R.p, Rcw, 72 * (size_t)n_images, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(d_t.p, tcw, 24 * (size_t)n_images, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemsetAsync(d_err.p, 0, 4, s));
-        gm_world_kernel<<<grid_for(P, 256), 256, 0, s>>>(P, sc->d_pts, sc->d_frame_off, nf, d_poses.as<double>(), voxel_size,
-                                                         world.as<double>(), key.as<uint64_t>(), idx.as<uint32_t>(), d_err.as<int>());
+        DevArr<double> d_poses(s), world(s); DevArr<uint64_t> key(s); DevArr<uint32_t> idx(s); DevArr<uint64_t> key_s(s);
+        DevArr<uint32_t> order(s), head(s), incl(s), vop(s); DevArr<int64_t> voff(s); DevArr<int> d_err(s);
+        DevArr<double> d_R(s), d_t(s);
+        HIPCHK(d_poses.alloc(12 * (size_t)nf)); HIPCHK(world.alloc(3 * (size_t)P)); HIPCHK(key.alloc((size_t)P));
+        HIPCHK(idx.alloc((size_t)P)); HIPCHK(key_s.alloc((size_t)P)); HIPCHK(order.alloc((size_t)P));
+        HIPCHK(head.alloc((size_t)P)); HIPCHK(incl.alloc((size_t)P)); HIPCHK(vop.alloc((size_t)P)); HIPCHK(d_err.alloc(1));
+        HIPCHK(d_R.alloc(9 * (size_t)n_images)); HIPCHK(d_t.alloc(3 * (size_t)n_images));
+        HIPCHK(hipMemcpyAsync(d_poses, scan_poses, d_poses.bytes(12 * (size_t)nf), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d_R, Rcw, d_R.bytes(9 * (size_t)n_images), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d_t, tcw, d_t.bytes(3 * (size_t)n_images), hipMemcpyHostToDevice, s)); HIPCHK(d_err.zero_async(1));
+        gm_world_kernel<<<grid_for(P, 256), 256, 0, s>>>(P, sc->d_pts, sc->d_frame_off, nf, d_poses, voxel_size, world, key, idx,
+                                                         d_err);
         HIPCHK(hipGetLastError());
         int err = 0;
-        HIPCHK(hipMemcpyAsync(&err, d_err.p, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&err, d_err, d_err.bytes(1), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         if (err) return lvba_fail(LVBA_ERR_ARG, "a scan point is non-finite or outside +-2^20 grid voxels");
-        TRY(sort_pairs(s, key.as<uint64_t>(), key_s.as<uint64_t>(), idx.as<uint32_t>(), order.as<uint32_t>(), (size_t)P, 63));
-        gm_heads_kernel<<<grid_for(P, 256), 256, 0, s>>>(P, key_s.as<uint64_t>(), head.as<uint32_t>());
-        TRY(scan_incl<uint32_t>(s, head.as<uint32_t>(), incl.as<uint32_t>(), (size_t)P));
+        TRY(sort_pairs<uint64_t>(s, key, key_s, idx, order, (size_t)P, 63));
+        gm_heads_kernel<<<grid_for(P, 256), 256, 0, s>>>(P, key_s, head);
+        TRY(scan_incl<uint32_t>(s, head, incl, (size_t)P));
         uint32_t V32 = 0;
-        HIPCHK(hipMemcpy(&V32, incl.as<uint32_t>() + (P - 1), 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(&V32, incl + (P - 1), incl.bytes(1), hipMemcpyDeviceToHost));
         const int64_t V = V32;
-        HIPCHK(voff.alloc(8 * ((size_t)V + 1)));
-        gm_tables_kernel<<<grid_for(P, 256), 256, 0, s>>>(P, head.as<uint32_t>(), incl.as<uint32_t>(), order.as<uint32_t>(),
-                                                          vop.as<uint32_t>(), voff.as<int64_t>(), V);
+        HIPCHK(voff.alloc((size_t)V + 1));
+        gm_tables_kernel<<<grid_for(P, 256), 256, 0, s>>>(P, head, incl, order, vop, voff, V);
         HIPCHK(hipGetLastError());
-        DevBuf mark(s), cnt(s), start(s);
-        HIPCHK(mark.alloc(4 * (size_t)V)); HIPCHK(cnt.alloc(8 * ((size_t)V + 1))); HIPCHK(start.alloc(8 * ((size_t)V + 1)));
+        DevArr<uint32_t> mark(s); DevArr<int64_t> cnt(s), start(s);
+        HIPCHK(mark.alloc((size_t)V)); HIPCHK(cnt.alloc((size_t)V + 1)); HIPCHK(start.alloc((size_t)V + 1));
         const TrkIntr cam = trk_intr_of(intr);
         for (int m = 0; m < n_images; ++m) {
             // scans with t_img - half <= t <= t_img + half: std::lower_bound / std::upper_bound on the (sorted) scan times
@@ -190,17 +190,16 @@ extern "C" int32_t lvba_depth_render(lvba_scans_t sc, const double *scan_poses, 
             if (fhi <= flo) continue;
             const int64_t p0 = sc->frame_off[flo], np = sc->frame_off[fhi] - p0;
             if (np <= 0) continue;
-            HIPCHK(hipMemsetAsync(mark.p, 0, 4 * (size_t)V, s));
-            gm_mark_kernel<<<grid_for(np, 256), 256, 0, s>>>(np, vop.as<uint32_t>() + p0, mark.as<uint32_t>());
-            gm_count_kernel<<<grid_for(V + 1, 256), 256, 0, s>>>(V, mark.as<uint32_t>(), voff.as<int64_t>(), cnt.as<int64_t>());
+            HIPCHK(mark.zero_async((size_t)V));
+            gm_mark_kernel<<<grid_for(np, 256), 256, 0, s>>>(np, vop + p0, mark);
+            gm_count_kernel<<<grid_for(V + 1, 256), 256, 0, s>>>(V, mark, voff, cnt);
             HIPCHK(hipGetLastError());
-            TRY(scan_excl<int64_t>(s, cnt.as<int64_t>(), start.as<int64_t>(), (size_t)V + 1));
+            TRY(scan_excl<int64_t>(s, cnt, start, (size_t)V + 1));
             int64_t M = 0;
-            HIPCHK(hipMemcpy(&M, start.as<int64_t>() + V, 8, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(&M, start + V, start.bytes(1), hipMemcpyDeviceToHost));
             if (M <= 0) continue;
-            gm_render_kernel<<<grid_for(M, 256), 256, 0, s>>>(M, V, start.as<int64_t>(), voff.as<int64_t>(), order.as<uint32_t>(),
-                                                              world.as<double>(), d_R.as<double>() + 9 * (int64_t)m,
-                                                              d_t.as<double>() + 3 * (int64_t)m, cam, width, height,
+            gm_render_kernel<<<grid_for(M, 256), 256, 0, s>>>(M, V, start, voff, order, world, d_R + 9 * (int64_t)m,
+                                                              d_t + 3 * (int64_t)m, cam, width, height,
                                                               reinterpret_cast<unsigned int *>(h->d_depth) + (int64_t)m * npix);
             HIPCHK(hipGetLastError());
         }
@@ -292,32 +291,34 @@ extern "C" int32_t lvba_fuse_tracks(int32_t device, lvba_depth_t depth, int32_t 
     ScopedStream sg;
     HIPCHK(sg.acquire());
     const hipStream_t s = sg.s;
-    DevBuf d_off(s), d_img(s), d_uv(s), d_R(s), d_t(s), d_pts(s), d_dirs(s), d_flag(s), d_idx(s), d_st(s), d_X(s), d_err(s), d_kept(s);
+    DevArr<int64_t> d_off(s); DevArr<int32_t> d_img(s); DevArr<float> d_uv(s); DevArr<double> d_R(s), d_t(s), d_pts(s), d_dirs(s);
+    DevArr<uint8_t> d_flag(s); DevArr<int32_t> d_idx(s); DevArr<uint8_t> d_st(s); DevArr<double> d_X(s), d_err(s);
+    DevArr<uint8_t> d_kept(s);
     const size_t O1 = (size_t)std::max<int64_t>(O, 1);
-    HIPCHK(d_off.alloc(8 * ((size_t)n_tracks + 1))); HIPCHK(d_img.alloc(4 * O1)); HIPCHK(d_uv.alloc(8 * O1));
-    HIPCHK(d_R.alloc(72 * (size_t)n_images)); HIPCHK(d_t.alloc(24 * (size_t)n_images));
-    HIPCHK(d_pts.alloc(24 * O1)); HIPCHK(d_dirs.alloc(24 * O1)); HIPCHK(d_flag.alloc(O1)); HIPCHK(d_idx.alloc(8 * O1));
-    HIPCHK(d_st.alloc((size_t)n_tracks)); HIPCHK(d_X.alloc(24 * (size_t)n_tracks)); HIPCHK(d_err.alloc(8 * (size_t)n_tracks));
+    HIPCHK(d_off.alloc((size_t)n_tracks + 1)); HIPCHK(d_img.alloc(O1)); HIPCHK(d_uv.alloc(2 * O1));
+    HIPCHK(d_R.alloc(9 * (size_t)n_images)); HIPCHK(d_t.alloc(3 * (size_t)n_images));
+    HIPCHK(d_pts.alloc(3 * O1)); HIPCHK(d_dirs.alloc(3 * O1)); HIPCHK(d_flag.alloc(O1)); HIPCHK(d_idx.alloc(2 * O1));
+    HIPCHK(d_st.alloc((size_t)n_tracks)); HIPCHK(d_X.alloc(3 * (size_t)n_tracks)); HIPCHK(d_err.alloc((size_t)n_tracks));
     HIPCHK(d_kept.alloc(O1));
-    HIPCHK(hipMemcpyAsync(d_off.p, obs_off, 8 * ((size_t)n_tracks + 1), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_off, obs_off, d_off.bytes((size_t)n_tracks + 1), hipMemcpyHostToDevice, s));
     if (O > 0) {
-        HIPCHK(hipMemcpyAsync(d_img.p, obs_img, 4 * (size_t)O, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(d_uv.p, obs_uv, 8 * (size_t)O, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d_img, obs_img, d_img.bytes((size_t)O), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d_uv, obs_uv, d_uv.bytes(2 * (size_t)O), hipMemcpyHostToDevice, s));
     }
-    HIPCHK(hipMemcpyAsync(d_R.p, Rcw, 72 * (size_t)n_images, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_t.p, tcw, 24 * (size_t)n_images, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_R, Rcw, d_R.bytes(9 * (size_t)n_images), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_t, tcw, d_t.bytes(3 * (size_t)n_images), hipMemcpyHostToDevice, s));
     const TrkIntr cam = trk_intr_of(intr);
     const double cos_min = cos(o.min_view_angle_deg * M_PI / 180.0);
     fuse_kernel<<<(unsigned)((n_tracks + 63) / 64), 64, 0, s>>>(
-        n_tracks, d_off.as<int64_t>(), d_img.as<int32_t>(), d_uv.as<float>(), depth ? depth->d_depth : nullptr,
-        depth ? depth->width : 0, depth ? depth->height : 0, d_R.as<double>(), d_t.as<double>(), n_images, cam, o.obser_thr, cos_min,
-        o.reproj_mean_thr_px, d_pts.as<double>(), d_dirs.as<double>(), d_flag.as<uint8_t>(), d_idx.as<int32_t>(), d_st.as<uint8_t>(), d_X.as<double>(),
-        d_err.as<double>(), d_kept.as<uint8_t>());
+        n_tracks, d_off, d_img, d_uv, depth ? depth->d_depth : nullptr,
+        depth ? depth->width : 0, depth ? depth->height : 0, d_R, d_t, n_images, cam, o.obser_thr, cos_min,
+        o.reproj_mean_thr_px, d_pts, d_dirs, d_flag, d_idx, d_st, d_X,
+        d_err, d_kept);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(status, d_st.p, (size_t)n_tracks, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(X, d_X.p, 24 * (size_t)n_tracks, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(mean_reproj, d_err.p, 8 * (size_t)n_tracks, hipMemcpyDeviceToHost, s));
-    if (O > 0) HIPCHK(hipMemcpyAsync(kept, d_kept.p, (size_t)O, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(status, d_st, d_st.bytes((size_t)n_tracks), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(X, d_X, d_X.bytes(3 * (size_t)n_tracks), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(mean_reproj, d_err, d_err.bytes((size_t)n_tracks), hipMemcpyDeviceToHost, s));
+    if (O > 0) HIPCHK(hipMemcpyAsync(kept, d_kept, d_kept.bytes((size_t)O), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return LVBA_OK;
 }

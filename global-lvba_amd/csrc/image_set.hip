@@ -20,10 +20,10 @@ int32_t image_set_upload(ImageSet &t, bool offsets, const float *uv)
 {
     const size_t total = (size_t)t.off.back();
     if (offsets && !t.d_off) {
-        HIPCHK(DevicePool::get().alloc((void **)&t.d_off, 8 * t.off.size())); HIPCHK(copy_h2d(t.d_off, t.off.data(), 8 * t.off.size()));
+        HIPCHK(pool_alloc(&t.d_off, t.off.size())); HIPCHK(copy_h2d(t.d_off, t.off.data(), 8 * t.off.size()));
     }
     if (uv && total > 0) {
-        if (!t.d_uv) HIPCHK(DevicePool::get().alloc((void **)&t.d_uv, 8 * total));
+        if (!t.d_uv) HIPCHK(pool_alloc(&t.d_uv, 2 * total));
         HIPCHK(copy_h2d(t.d_uv, uv, 8 * total));
     }
     return LVBA_OK;
@@ -35,11 +35,11 @@ int32_t image_set_undistort(ImageSet &t, const TrkIntr &cam, const float *uv, bo
     if (total == 0) return LVBA_OK;
     ScopedStream sg;
     HIPCHK(sg.acquire());
-    DevBuf tmp(sg.s);
+    DevArr<float> tmp(sg.s);
     if (keep_uv) TRY(image_set_upload(t, false, uv));
-    else { HIPCHK(tmp.alloc(8 * total)); HIPCHK(copy_h2d(tmp.p, uv, 8 * total)); }
-    if (!t.d_xy) HIPCHK(DevicePool::get().alloc((void **)&t.d_xy, 16 * total));
-    image_set_undistort_kernel<<<(unsigned)((total + 255) / 256), 256, 0, sg.s>>>((int64_t)total, keep_uv ? t.d_uv : tmp.as<float>(), cam, t.d_xy);
+    else { HIPCHK(tmp.alloc(2 * total)); HIPCHK(tmp.upload(uv, 2 * total)); }
+    if (!t.d_xy) HIPCHK(pool_alloc(&t.d_xy, 2 * total));
+    image_set_undistort_kernel<<<(unsigned)((total + 255) / 256), 256, 0, sg.s>>>((int64_t)total, keep_uv ? t.d_uv : tmp, cam, t.d_xy);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(sg.s));
     return LVBA_OK;

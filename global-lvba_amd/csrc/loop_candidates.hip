@@ -114,25 +114,24 @@ extern "C" int32_t lvba_loop_candidates(int32_t device, int32_t n_frames, const 
     ScopedStream sg;
     HIPCHK(sg.acquire());
     const hipStream_t s = sg.s;
-    DevBuf d_pos(s), d_count(s), d_first(s), d_stage(s), d_out(s);
-    HIPCHK(d_pos.alloc(24 * (size_t)n)); HIPCHK(d_count.alloc(8 * ((size_t)nq + 1))); HIPCHK(d_first.alloc(8 * ((size_t)nq + 1)));
-    HIPCHK(d_stage.alloc(sizeof(lvba_loop_candidate) * (size_t)nq * (size_t)o.max_per_frame));
-    HIPCHK(lvba::copy_h2d(d_pos.p, pos.data(), 24 * (size_t)n));
-    HIPCHK(hipMemsetAsync(d_count.as<int64_t>() + nq, 0, 8, s));
-    loop_search_kernel<<<grid_for(nq, LOOP_BLOCK / 64), LOOP_BLOCK, 0, s>>>(n, nq, d_pos.as<double>(), par, d_count.as<int64_t>(),
-                                                                           d_stage.as<lvba_loop_candidate>());
+    DevArr<double> d_pos(s); DevArr<int64_t> d_count(s), d_first(s); DevArr<lvba_loop_candidate> d_stage(s), d_out(s);
+    HIPCHK(d_pos.alloc(3 * (size_t)n)); HIPCHK(d_count.alloc((size_t)nq + 1)); HIPCHK(d_first.alloc((size_t)nq + 1));
+    HIPCHK(d_stage.alloc((size_t)nq * (size_t)o.max_per_frame)); HIPCHK(d_pos.upload(pos.data(), 3 * (size_t)n));
+    HIPCHK(d_count.zero_async(1, nq));
+    loop_search_kernel<<<grid_for(nq, LOOP_BLOCK / 64), LOOP_BLOCK, 0, s>>>(n, nq, d_pos, par, d_count,
+                                                                           d_stage);
     HIPCHK(hipGetLastError());
-    TRY(scan_excl<int64_t>(s, d_count.as<int64_t>(), d_first.as<int64_t>(), (size_t)nq + 1));
+    TRY(scan_excl<int64_t>(s, d_count, d_first, (size_t)nq + 1));
     int64_t total = 0;
-    HIPCHK(lvba::copy_d2h(&total, d_first.as<int64_t>() + nq, 8));
+    HIPCHK(copy_d2h(&total, d_first + nq, d_first.bytes(1)));
     *count = total;
     const int64_t n_out = std::min(total, capacity);
     if (n_out == 0) return LVBA_OK;
-    HIPCHK(d_out.alloc(sizeof(lvba_loop_candidate) * (size_t)n_out));
-    loop_write_kernel<<<grid_for(nq, 256), 256, 0, s>>>(nq, o.max_per_frame, d_count.as<int64_t>(), d_first.as<int64_t>(),
-                                                        d_stage.as<lvba_loop_candidate>(), n_out, d_out.as<lvba_loop_candidate>());
+    HIPCHK(d_out.alloc((size_t)n_out));
+    loop_write_kernel<lvba_loop_candidate><<<grid_for(nq, 256), 256, 0, s>>>(nq, o.max_per_frame, d_count, d_first,
+                                                        d_stage, n_out, d_out);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(lvba::copy_d2h(out, d_out.p, sizeof(lvba_loop_candidate) * (size_t)n_out));
+    HIPCHK(d_out.download(out, (size_t)n_out));
     return LVBA_OK;
 }

@@ -606,11 +606,11 @@ extern "C" int32_t lvba_balm_eval(lvba_balm_t h, const double *poses, double *H,
         launch_export_vec(bs.g(), bs.d_perm, h->N, h->d_out, bs.stream);
         HIPCHK(hipMemcpyAsync(g, h->d_out, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, bs.stream));
     }
-    DevBuf dH(bs.stream); // freed on every path, error returns included
+    DevArr<double> dH(bs.stream); // freed on every path, error returns included
     if (H) {
-        HIPCHK(dH.alloc((size_t)(n * n) * sizeof(double)));
-        launch_export_dense(bs.Hblk(), bs.Bb, h->N, bs.d_perm, dH.as<double>(), bs.stream);
-        HIPCHK(hipMemcpyAsync(H, dH.as<double>(), (size_t)(n * n) * sizeof(double), hipMemcpyDeviceToHost, bs.stream));
+        HIPCHK(dH.alloc((size_t)(n * n)));
+        launch_export_dense(bs.Hblk(), bs.Bb, h->N, bs.d_perm, dH, bs.stream);
+        HIPCHK(hipMemcpyAsync(H, dH, dH.bytes((size_t)(n * n)), hipMemcpyDeviceToHost, bs.stream));
     }
     HIPCHK(hipStreamSynchronize(bs.stream));
     ev_collect(h);
@@ -741,7 +741,8 @@ extern "C" int32_t lvba_balm_covariance(lvba_balm_t h, const double *poses, cons
     const int64_t ns = ldlt_selinv_scratch_doubles(n, A.bw);
     const int64_t nout = ((int64_t)N + n_pairs) * 36;
     const int64_t nint = (int64_t)N + 2 * n_pairs + 2 * 64, nbytes8 = (n_pairs + 7) / 8 + 8;
-    DevBuf scr(bs.stream), zd(bs.stream);
+    DevBuf scr(bs.stream); // raw scratch, carved into doubles, bytes and int32s below
+    DevArr<double> zd(bs.stream);
     HIPCHK(scr.alloc((size_t)(ns + 8 + nout + nbytes8) * sizeof(double) + (size_t)nint * sizeof(int32_t)));
     double *d_sc = scr.as<double>(), *d_zero = d_sc + ns, *d_out = d_zero + 8;
     uint8_t *d_av = reinterpret_cast<uint8_t *>(d_out + nout);
@@ -759,8 +760,8 @@ extern "C" int32_t lvba_balm_covariance(lvba_balm_t h, const double *poses, cons
     const LdltSelinvRoom sroom{bs.room.store, band ? ldlt_store_room(bs.room.store, n, A.ld, true) : ldlt_cov_z_dense_doubles(n), bs.room.work, ns};
     if (band) z = bs.d_A + ldlt_mat2_offset(n, A.ld);
     else {
-        HIPCHK(zd.alloc((size_t)sroom.z * sizeof(double)));
-        z = zd.as<double>();
+        HIPCHK(zd.alloc((size_t)sroom.z));
+        z = zd;
     }
     // the band store must read as zero outside what the damped solve rewrites (block_system.hip): zeroed again on every way out
     const size_t band_bytes = band ? (size_t)bs.room.store * sizeof(double) : 0;
@@ -1132,9 +1133,9 @@ extern "C" int32_t lvba_balm_prior_residuals(lvba_balm_t h, const double *poses,
     const int64_t n = h->pt.dev.n;
     if (n == 0) { if (cost) *cost = 0.0; return LVBA_OK; }
     TRY(upload_poses(h, poses, h->d_pose_trial));
-    DevBuf d(bs.stream);
-    HIPCHK(d.alloc((size_t)(6 * n + 1) * sizeof(double)));
-    double *de = d.as<double>();
+    DevArr<double> d(bs.stream);
+    HIPCHK(d.alloc((size_t)(6 * n + 1)));
+    double *de = d;
     HIPCHK(hipMemsetAsync(de + 6 * n, 0, sizeof(double), bs.stream));
     launch_prior_cost(h->pt.dev, h->d_pose_trial, de + 6 * n, de, bs.stream);
     HIPCHK(hipGetLastError());
@@ -1199,9 +1200,9 @@ extern "C" int32_t lvba_balm_voxel_residuals(lvba_balm_t h, const double *poses,
     if (!lambda_min && !weight) return LVBA_OK;
     TRY(upload_poses(h, poses, h->d_pose_trial));
     const int64_t V = h->V;
-    DevBuf d(bs.stream);
-    HIPCHK(d.alloc((size_t)((lambda_min ? V : 0) + (weight ? V : 0)) * sizeof(double)));
-    double *dl = d.as<double>(), *dw = dl + (lambda_min ? V : 0);
+    DevArr<double> d(bs.stream);
+    HIPCHK(d.alloc((size_t)((lambda_min ? V : 0) + (weight ? V : 0))));
+    double *dl = d, *dw = dl + (lambda_min ? V : 0);
     launch_voxel_residuals(h->dev(), h->d_pose_trial, h->d_vox_order, lambda_min ? dl : nullptr, weight ? dw : nullptr, bs.stream);
     HIPCHK(hipGetLastError());
     if (lambda_min) HIPCHK(hipMemcpyAsync(lambda_min, dl, (size_t)V * sizeof(double), hipMemcpyDeviceToHost, bs.stream));

@@ -226,15 +226,16 @@ int32_t mapq_run(hipStream_t s, const float *d_world, int64_t n, const lvba_mapq
     if (n == 0) return LVBA_OK;
     const double edge = mapq_cell_edge(o.radius), r2 = o.radius * o.radius;
     // 1. keys
-    DevBuf key(s), partial(s), small(s), ckey(s), idx(s), ckey_s(s), idx_s(s);
+    DevArr<uint64_t> key(s); DevArr<int> partial(s), small(s); DevArr<uint64_t> ckey(s); DevArr<uint32_t> idx(s);
+    DevArr<uint64_t> ckey_s(s); DevArr<uint32_t> idx_s(s);
     const int64_t slots = key_range_slots(n, 256);
-    HIPCHK(key.alloc(8 * (size_t)n)); HIPCHK(partial.alloc(24 * (size_t)slots)); HIPCHK(small.alloc(64));
-    HIPCHK(hipMemsetAsync(small.p, 0, 64, s)); // rng[6], err, ticket
-    int *d_rng = small.as<int>(), *d_err = d_rng + 6;
+    HIPCHK(key.alloc((size_t)n)); HIPCHK(partial.alloc(6 * (size_t)slots)); HIPCHK(small.alloc(16));
+    HIPCHK(small.zero_async(16)); // rng[6], err, ticket
+    int *d_rng = small, *d_err = d_rng + 6;
     unsigned *d_ticket = (unsigned *)(d_rng + 7);
-    mapq_key_kernel<<<grid_for(n, 256), 256, 0, s>>>(n, d_world, edge, key.as<uint64_t>(), partial.as<int>(), d_err);
+    mapq_key_kernel<<<grid_for(n, 256), 256, 0, s>>>(n, d_world, edge, key, partial, d_err);
     HIPCHK(hipGetLastError());
-    key_range_reduce_kernel<<<key_range_reduce_grid(slots), 256, 0, s>>>(slots, partial.as<int>(), d_rng);
+    key_range_reduce_kernel<<<key_range_reduce_grid(slots), 256, 0, s>>>(slots, partial, d_rng);
     HIPCHK(hipGetLastError());
     int host[7] = {0, 0, 0, 0, 0, 0, 0};
     HIPCHK(hipMemcpyAsync(host, d_rng, sizeof(host), hipMemcpyDeviceToHost, s));
@@ -243,46 +244,43 @@ int32_t mapq_run(hipStream_t s, const float *d_world, int64_t n, const lvba_mapq
         return lvba_fail(LVBA_ERR_ARG, "map quality: a point lies 2^20 - 1 or more cells of %g m from the origin", edge);
     const KeyPack kp = key_pack_of(host);
     // 2. sort, records, tables
-    HIPCHK(ckey.alloc(8 * (size_t)n)); HIPCHK(idx.alloc(4 * (size_t)n)); HIPCHK(ckey_s.alloc(8 * (size_t)n)); HIPCHK(idx_s.alloc(4 * (size_t)n));
-    mapq_compress_kernel<<<grid_for(n, 256), 256, 0, s>>>(n, key.as<uint64_t>(), kp, ckey.as<uint64_t>(), idx.as<uint32_t>());
+    HIPCHK(ckey.alloc((size_t)n)); HIPCHK(idx.alloc((size_t)n)); HIPCHK(ckey_s.alloc((size_t)n)); HIPCHK(idx_s.alloc((size_t)n));
+    mapq_compress_kernel<<<grid_for(n, 256), 256, 0, s>>>(n, key, kp, ckey, idx);
     HIPCHK(hipGetLastError());
-    TRY(sort_pairs(s, ckey.as<uint64_t>(), ckey_s.as<uint64_t>(), idx.as<uint32_t>(), idx_s.as<uint32_t>(), (size_t)n, (unsigned)kp.total + 1));
-    DevBuf rec(s), head(s), head_x(s), qflag(s), q_x(s), ukey(s), ustart(s), qlist(s);
-    HIPCHK(rec.alloc(16 * (size_t)n)); HIPCHK(head.alloc(4 * (size_t)n)); HIPCHK(head_x.alloc(4 * (size_t)n));
-    HIPCHK(qflag.alloc(4 * (size_t)n)); HIPCHK(q_x.alloc(4 * (size_t)n));
-    mapq_gather_kernel<<<grid_for(n, 256), 256, 0, s>>>(n, ckey_s.as<uint64_t>(), idx_s.as<uint32_t>(), d_world, (uint32_t)stride,
-                                                        rec.as<float4>(), head.as<uint32_t>(), qflag.as<uint32_t>());
+    TRY(sort_pairs<uint64_t>(s, ckey, ckey_s, idx, idx_s, (size_t)n, (unsigned)kp.total + 1));
+    DevArr<float4> rec(s); DevArr<uint32_t> head(s), head_x(s), qflag(s), q_x(s); DevArr<uint64_t> ukey(s);
+    DevArr<uint32_t> ustart(s), qlist(s);
+    HIPCHK(rec.alloc((size_t)n)); HIPCHK(head.alloc((size_t)n)); HIPCHK(head_x.alloc((size_t)n));
+    HIPCHK(qflag.alloc((size_t)n)); HIPCHK(q_x.alloc((size_t)n));
+    mapq_gather_kernel<<<grid_for(n, 256), 256, 0, s>>>(n, ckey_s, idx_s, d_world, (uint32_t)stride, rec, head, qflag);
     HIPCHK(hipGetLastError());
-    TRY(scan_excl<uint32_t>(s, qflag.as<uint32_t>(), q_x.as<uint32_t>(), (size_t)n));
+    TRY(scan_excl<uint32_t>(s, qflag, q_x, (size_t)n));
     int64_t n_cells = 0;
-    TRY(count_flags(s, head.as<uint32_t>(), head_x.as<uint32_t>(), (size_t)n, &n_cells));
-    HIPCHK(ukey.alloc(8 * (size_t)n_cells)); HIPCHK(ustart.alloc(4 * (size_t)(n_cells + 1))); HIPCHK(qlist.alloc(4 * (size_t)nq));
-    mapq_table_kernel<<<grid_for(n, 256), 256, 0, s>>>(n, ckey_s.as<uint64_t>(), head.as<uint32_t>(), head_x.as<uint32_t>(),
-                                                       qflag.as<uint32_t>(), q_x.as<uint32_t>(), kp, n_cells, ukey.as<uint64_t>(),
-                                                       ustart.as<uint32_t>(), qlist.as<uint32_t>());
+    TRY(count_flags(s, head, head_x, (size_t)n, &n_cells));
+    HIPCHK(ukey.alloc((size_t)n_cells)); HIPCHK(ustart.alloc((size_t)(n_cells + 1))); HIPCHK(qlist.alloc((size_t)nq));
+    mapq_table_kernel<<<grid_for(n, 256), 256, 0, s>>>(n, ckey_s, head, head_x, qflag, q_x, kp, n_cells, ukey, ustart, qlist);
     HIPCHK(hipGetLastError());
     ev.rec(2, s);
     // 3. reduction
     const unsigned grid = grid_for(nq, 64);
-    DevBuf d_ent(s), d_pv(s), d_nrm(s), d_cnt(s), part(s), sums(s);
-    HIPCHK(d_ent.alloc(8 * (size_t)nq)); HIPCHK(d_pv.alloc(8 * (size_t)nq)); HIPCHK(d_nrm.alloc(12 * (size_t)nq));
-    HIPCHK(d_cnt.alloc(4 * (size_t)nq)); HIPCHK(part.alloc(40 * (size_t)grid)); HIPCHK(sums.alloc(40));
-    mapq_reduce_kernel<<<grid, 64, 0, s>>>(nq, qlist.as<uint32_t>(), rec.as<float4>(), ukey.as<uint64_t>(), ustart.as<uint32_t>(), n_cells,
-                                           edge, r2, o.min_neighbors, (uint32_t)stride, d_ent.as<double>(), d_pv.as<double>(),
-                                           d_nrm.as<float>(), d_cnt.as<int32_t>(), part.as<double>(), d_ticket, sums.as<double>());
+    DevArr<double> d_ent(s), d_pv(s); DevArr<float> d_nrm(s); DevArr<int32_t> d_cnt(s); DevArr<double> part(s), sums(s);
+    HIPCHK(d_ent.alloc((size_t)nq)); HIPCHK(d_pv.alloc((size_t)nq)); HIPCHK(d_nrm.alloc(3 * (size_t)nq));
+    HIPCHK(d_cnt.alloc((size_t)nq)); HIPCHK(part.alloc(5 * (size_t)grid)); HIPCHK(sums.alloc(5));
+    mapq_reduce_kernel<<<grid, 64, 0, s>>>(nq, qlist, rec, ukey, ustart, n_cells, edge, r2, o.min_neighbors, (uint32_t)stride,
+                                           d_ent, d_pv, d_nrm, d_cnt, part, d_ticket, sums);
     HIPCHK(hipGetLastError());
     ev.rec(3, s);
     double h_sums[5] = {0, 0, 0, 0, 0};
-    HIPCHK(hipMemcpyAsync(h_sums, sums.p, sizeof(h_sums), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h_sums, sums, sizeof(h_sums), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     sum->ms[1] = ev.ms(1, 2);
     sum->ms[2] = ev.ms(2, 3);
     // 4. download
     const double t0 = now_ms();
-    if (entropy) HIPCHK(copy_d2h(entropy, d_ent.p, 8 * (size_t)nq));
-    if (plane_var) HIPCHK(copy_d2h(plane_var, d_pv.p, 8 * (size_t)nq));
-    if (normal) HIPCHK(copy_d2h(normal, d_nrm.p, 12 * (size_t)nq));
-    if (count) HIPCHK(copy_d2h(count, d_cnt.p, 4 * (size_t)nq));
+    if (entropy) HIPCHK(d_ent.download(entropy, (size_t)nq));
+    if (plane_var) HIPCHK(d_pv.download(plane_var, (size_t)nq));
+    if (normal) HIPCHK(d_nrm.download(normal, 3 * (size_t)nq));
+    if (count) HIPCHK(d_cnt.download(count, (size_t)nq));
     sum->ms[3] = now_ms() - t0;
     sum->n_valid = (int64_t)h_sums[2];
     if (h_sums[2] > 0.0) { sum->mme = h_sums[0] / h_sums[2]; sum->mpv = h_sums[1] / h_sums[2]; }
@@ -320,17 +318,17 @@ extern "C" int32_t lvba_mapq_scans(lvba_scans_t sc, const double *scan_poses, in
     HIPCHK(sg.acquire());
     const hipStream_t s = sg.s;
     EventTimer<4> ev;
-    DevBuf world(s), d_poses(s);
-    HIPCHK(world.alloc(12 * (size_t)std::max<int64_t>(P, 1))); HIPCHK(d_poses.alloc(96 * (size_t)n_frames));
-    HIPCHK(hipMemcpyAsync(d_poses.p, scan_poses, 96 * (size_t)n_frames, hipMemcpyHostToDevice, s));
+    DevArr<float> world(s); DevArr<double> d_poses(s);
+    HIPCHK(world.alloc(3 * (size_t)std::max<int64_t>(P, 1))); HIPCHK(d_poses.alloc(12 * (size_t)n_frames));
+    HIPCHK(hipMemcpyAsync(d_poses, scan_poses, d_poses.bytes(12 * (size_t)n_frames), hipMemcpyHostToDevice, s));
     ev.rec(0, s);
     if (P > 0) {
-        col_world_kernel<<<grid_for(P, 256), 256, 0, s>>>(P, sc->d_pts + 3 * sc->frame_off[frame_begin], sc->d_frame_off + frame_begin, n_frames,
-                                                          d_poses.as<double>(), 0.0, 0, world.as<float>(), nullptr);
+        col_world_kernel<<<grid_for(P, 256), 256, 0, s>>>(P, sc->d_pts + 3 * sc->frame_off[frame_begin],
+                                                          sc->d_frame_off + frame_begin, n_frames, d_poses, 0.0, 0, world, nullptr);
         HIPCHK(hipGetLastError());
     }
     ev.rec(1, s);
-    const int32_t rc = mapq_run(s, world.as<float>(), P, o, summary, entropy, plane_var, normal, count, ev);
+    const int32_t rc = mapq_run(s, world, P, o, summary, entropy, plane_var, normal, count, ev);
     HIPCHK(hipStreamSynchronize(s)); // scan_poses was read by now
     if (rc == LVBA_OK) summary->ms[0] = ev.ms(0, 1);
     return rc;
@@ -350,13 +348,13 @@ extern "C" int32_t lvba_mapq_points(int32_t device, int64_t n, const float *xyz,
     HIPCHK(sg.acquire());
     const hipStream_t s = sg.s;
     EventTimer<4> ev;
-    DevBuf world(s);
-    HIPCHK(world.alloc(12 * (size_t)std::max<int64_t>(n, 1)));
+    DevArr<float> world(s);
+    HIPCHK(world.alloc(3 * (size_t)std::max<int64_t>(n, 1)));
     const double t0 = now_ms();
-    if (n > 0) HIPCHK(copy_h2d(world.p, xyz, 12 * (size_t)n));
+    if (n > 0) HIPCHK(world.upload(xyz, 3 * (size_t)n));
     const double up = now_ms() - t0;
     ev.rec(1, s);
-    const int32_t rc = mapq_run(s, world.as<float>(), n, o, summary, entropy, plane_var, normal, count, ev);
+    const int32_t rc = mapq_run(s, world, n, o, summary, entropy, plane_var, normal, count, ev);
     if (rc == LVBA_OK) summary->ms[0] = up;
     return rc;
 }

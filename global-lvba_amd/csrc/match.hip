@@ -346,29 +346,26 @@ int32_t scan_tasks(hipStream_t s, const lvba_match_s *m, const std::vector<Match
     for (size_t k = 0; k < tasks.size(); ++k)
         for (int r = 0; r < tasks[k].n_a; r += SCAN_ROWS) tiles.push_back(make_int2((int)k, r));
     if (tiles.empty()) return LVBA_OK;
-    DevBuf d_tasks(s), d_tiles(s);
-    HIPCHK(d_tasks.alloc(sizeof(MatchTask) * tasks.size())); HIPCHK(d_tiles.alloc(sizeof(int2) * tiles.size()));
-    HIPCHK(lvba::copy_h2d(d_tasks.p, tasks.data(), sizeof(MatchTask) * tasks.size()));
-    HIPCHK(lvba::copy_h2d(d_tiles.p, tiles.data(), sizeof(int2) * tiles.size()));
-    DevBuf d_jobs(s), d_pred(s);
+    DevArr<MatchTask> d_tasks(s); DevArr<int2> d_tiles(s);
+    HIPCHK(d_tasks.alloc_upload(tasks)); HIPCHK(d_tiles.alloc_upload(tiles));
+    DevArr<MatchPredJob> d_jobs(s); DevArr<double> d_pred(s);
     if (o.guided == MATCH_DEPTH) {
-        HIPCHK(d_pred.alloc(16 * (size_t)n_pred));
+        HIPCHK(d_pred.alloc(2 * (size_t)n_pred));
         if (n_pred > 0) {
-            HIPCHK(d_jobs.alloc(sizeof(MatchPredJob) * jobs.size()));
-            HIPCHK(lvba::copy_h2d(d_jobs.p, jobs.data(), sizeof(MatchPredJob) * jobs.size()));
-            match_predict_kernel<<<grid_for(n_pred, 256), 256, 0, s>>>(n_pred, (int)jobs.size(), d_jobs.as<MatchPredJob>(), m->cam, m->d_pts,
-                                                                     d_pred.as<double>());
+            HIPCHK(d_jobs.alloc_upload(jobs));
+            match_predict_kernel<<<grid_for(n_pred, 256), 256, 0, s>>>(n_pred, (int)jobs.size(), d_jobs, m->cam, m->d_pts,
+                                                                     d_pred);
             HIPCHK(hipGetLastError());
         }
-        match_scan_kernel<MATCH_DEPTH><<<(unsigned)tiles.size(), SCAN_BLOCK, 0, s>>>(d_tasks.as<MatchTask>(), d_tiles.as<int2>(), m->d_desc,
+        match_scan_kernel<MATCH_DEPTH><<<(unsigned)tiles.size(), SCAN_BLOCK, 0, s>>>(d_tasks, d_tiles, m->d_desc,
                                                                                    m->d_bias, nullptr, o.max_reproj_px * o.max_reproj_px, d_best,
-                                                                                   d_s1, d_s2, m->kp.d_uv, d_pred.as<double>());
+                                                                                   d_s1, d_s2, m->kp.d_uv, d_pred);
     } else if (o.guided == MATCH_EPIPOLAR)
-        match_scan_kernel<MATCH_EPIPOLAR><<<(unsigned)tiles.size(), SCAN_BLOCK, 0, s>>>(d_tasks.as<MatchTask>(), d_tiles.as<int2>(), m->d_desc,
+        match_scan_kernel<MATCH_EPIPOLAR><<<(unsigned)tiles.size(), SCAN_BLOCK, 0, s>>>(d_tasks, d_tiles, m->d_desc,
                                                                                       m->d_bias, m->kp.d_xy, match_tau2(m->focal_sum, o.max_epipolar_px), d_best, d_s1, d_s2,
                                                                                       nullptr, nullptr);
     else
-        match_scan_kernel<MATCH_UNGUIDED><<<(unsigned)tiles.size(), SCAN_BLOCK, 0, s>>>(d_tasks.as<MatchTask>(), d_tiles.as<int2>(), m->d_desc,
+        match_scan_kernel<MATCH_UNGUIDED><<<(unsigned)tiles.size(), SCAN_BLOCK, 0, s>>>(d_tasks, d_tiles, m->d_desc,
                                                                                       m->d_bias, nullptr, 0.0, d_best, d_s1, d_s2, nullptr,
                                                                                       nullptr);
     HIPCHK(hipGetLastError());
@@ -417,8 +414,8 @@ extern "C" int32_t lvba_match_create(int32_t device, int32_t n_images, const int
             }
             bias[(size_t)i] = 128 * sum;
         }
-        hipError_t e = DevicePool::get().alloc((void **)&m->d_desc, biased.size());
-        if (e == hipSuccess) e = DevicePool::get().alloc((void **)&m->d_bias, 4 * bias.size());
+        hipError_t e = pool_alloc(&m->d_desc, biased.size());
+        if (e == hipSuccess) e = pool_alloc(&m->d_bias, bias.size());
         if (e == hipSuccess) e = lvba::copy_h2d(m->d_desc, biased.data(), biased.size());
         if (e == hipSuccess) e = lvba::copy_h2d(m->d_bias, bias.data(), 4 * bias.size());
         if (e != hipSuccess) {
@@ -485,9 +482,9 @@ extern "C" int32_t lvba_match_scan(lvba_match_t m, int32_t a, int32_t b, const l
     HIPCHK(hipSetDevice(m->kp.device));
     ScopedStream sg;
     HIPCHK(sg.acquire());
-    DevBuf d_out(sg.s);
-    HIPCHK(d_out.alloc(12 * n_a));
-    int32_t *d = d_out.as<int32_t>();
+    DevArr<int32_t> d_out(sg.s);
+    HIPCHK(d_out.alloc(3 * n_a));
+    int32_t *d = d_out;
     std::vector<MatchPredJob> jobs;
     const int64_t n_pred = o.guided == MATCH_DEPTH ? predict_jobs(m, a, b, 0, jobs) : 0;
     std::vector<MatchTask> tasks{make_task(m, a, b, 0, o.guided, 0, (int64_t)n_a)};
@@ -539,32 +536,31 @@ extern "C" int32_t lvba_match_pairs(lvba_match_t m, int64_t n_pairs, const int32
         const int np = (int)(p1 - p0);
         row_off.push_back(fwd_rows);
         if (fwd_rows > 0) {
-            DevBuf d_res(s), d_row_off(s), d_po(s), d_flag(s), d_excl(s), d_off(s), d_m(s), d_sc(s);
-            HIPCHK(d_res.alloc(12 * (size_t)rows));
-            int32_t *d_best = d_res.as<int32_t>(), *d_s1 = d_best + rows, *d_s2 = d_s1 + rows;
+            DevArr<int32_t> d_res(s); DevArr<int64_t> d_row_off(s); DevArr<MatchPairOut> d_po(s);
+            DevArr<uint32_t> d_flag(s), d_excl(s); DevArr<int64_t> d_off(s); DevArr<int32_t> d_m(s), d_sc(s);
+            HIPCHK(d_res.alloc(3 * (size_t)rows));
+            int32_t *d_best = d_res, *d_s1 = d_best + rows, *d_s2 = d_s1 + rows;
             TRY(scan_tasks(s, m, tasks, jobs, n_pred, o, d_best, d_s1, d_s2));
-            HIPCHK(d_row_off.alloc(8 * row_off.size())); HIPCHK(d_po.alloc(sizeof(MatchPairOut) * po.size()));
-            HIPCHK(d_flag.alloc(4 * ((size_t)fwd_rows + 1))); HIPCHK(d_excl.alloc(4 * ((size_t)fwd_rows + 1))); HIPCHK(d_off.alloc(8 * (size_t)np));
-            HIPCHK(lvba::copy_h2d(d_row_off.p, row_off.data(), 8 * row_off.size()));
-            HIPCHK(lvba::copy_h2d(d_po.p, po.data(), sizeof(MatchPairOut) * po.size()));
-            match_decide_kernel<<<grid_for(fwd_rows + 1, 256), 256, 0, s>>>(fwd_rows, np, d_row_off.as<int64_t>(), d_po.as<MatchPairOut>(), d_best,
-                                                                          d_s1, d_s2, o.max_distance, o.max_ratio, o.mutual, d_flag.as<uint32_t>());
+            HIPCHK(d_flag.alloc((size_t)fwd_rows + 1)); HIPCHK(d_excl.alloc((size_t)fwd_rows + 1)); HIPCHK(d_off.alloc((size_t)np));
+            HIPCHK(d_row_off.alloc_upload(row_off)); HIPCHK(d_po.alloc_upload(po));
+            match_decide_kernel<<<grid_for(fwd_rows + 1, 256), 256, 0, s>>>(fwd_rows, np, d_row_off, d_po, d_best,
+                                                                          d_s1, d_s2, o.max_distance, o.max_ratio, o.mutual, d_flag);
             HIPCHK(hipGetLastError());
-            TRY(scan_excl<uint32_t>(s, d_flag.as<uint32_t>(), d_excl.as<uint32_t>(), (size_t)fwd_rows + 1));
+            TRY(scan_excl<uint32_t>(s, d_flag, d_excl, (size_t)fwd_rows + 1));
             uint32_t found = 0;
             HIPCHK(hipStreamSynchronize(s));
-            HIPCHK(lvba::copy_d2h(&found, d_excl.as<uint32_t>() + fwd_rows, 4));
+            HIPCHK(copy_d2h(&found, d_excl + fwd_rows, d_excl.bytes(1)));
             const int64_t n_out = std::max<int64_t>(0, std::min<int64_t>(found, capacity - base));
-            HIPCHK(d_m.alloc(8 * (size_t)n_out)); HIPCHK(d_sc.alloc(4 * (size_t)n_out));
+            HIPCHK(d_m.alloc(2 * (size_t)n_out)); HIPCHK(d_sc.alloc((size_t)n_out));
             match_write_kernel<<<grid_for(std::max<int64_t>(fwd_rows, np), 256), 256, 0, s>>>(
-                fwd_rows, np, d_row_off.as<int64_t>(), d_po.as<MatchPairOut>(), d_best, d_s1, d_flag.as<uint32_t>(), d_excl.as<uint32_t>(), base,
-                n_out, d_m.as<int32_t>(), d_sc.as<int32_t>(), d_off.as<int64_t>());
+                fwd_rows, np, d_row_off, d_po, d_best, d_s1, d_flag, d_excl, base,
+                n_out, d_m, d_sc, d_off);
             HIPCHK(hipGetLastError());
             HIPCHK(hipStreamSynchronize(s));
-            HIPCHK(lvba::copy_d2h(match_off + p0, d_off.p, 8 * (size_t)np));
+            HIPCHK(d_off.download(match_off + p0, (size_t)np));
             if (n_out > 0) {
-                HIPCHK(lvba::copy_d2h(matches + 2 * base, d_m.p, 8 * (size_t)n_out));
-                if (scores) HIPCHK(lvba::copy_d2h(scores + base, d_sc.p, 4 * (size_t)n_out));
+                HIPCHK(d_m.download(matches + 2 * base, 2 * (size_t)n_out));
+                if (scores) HIPCHK(d_sc.download(scores + base, (size_t)n_out));
             }
             base += found;
         } else {
@@ -594,15 +590,13 @@ extern "C" int32_t lvba_match_set_depth(lvba_match_t m, lvba_depth_t depth)
     if (total > 0) {
         ScopedStream sg;
         HIPCHK(sg.acquire());
-        DevBuf d_new(sg.s), d_R(sg.s), d_t(sg.s); // the old table stays until the new one stands
-        HIPCHK(d_new.alloc(24 * (size_t)total));
-        HIPCHK(d_R.alloc(8 * m->R.size())); HIPCHK(d_t.alloc(8 * m->t.size()));
+        DevArr<double> d_new(sg.s), d_R(sg.s), d_t(sg.s); // the old table stays until the new one stands
+        HIPCHK(d_new.alloc(3 * (size_t)total));
         TRY(image_set_upload(m->kp, true, nullptr)); // the offsets go up with the first lift and stay
-        HIPCHK(lvba::copy_h2d(d_R.p, m->R.data(), 8 * m->R.size()));
-        HIPCHK(lvba::copy_h2d(d_t.p, m->t.data(), 8 * m->t.size()));
+        HIPCHK(d_R.alloc_upload(m->R)); HIPCHK(d_t.alloc_upload(m->t));
         match_lift_kernel<<<grid_for(total, 256), 256, 0, sg.s>>>(total, m->kp.n_images, m->kp.d_off, m->kp.d_uv, m->kp.d_xy, depth->d_depth,
-                                                                depth->width, depth->height, d_R.as<double>(), d_t.as<double>(),
-                                                                d_new.as<double>());
+                                                                depth->width, depth->height, d_R, d_t,
+                                                                d_new);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(sg.s));
         drop_points(m);

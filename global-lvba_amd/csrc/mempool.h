@@ -335,4 +335,49 @@ struct DevBuf {
     void *release() { void *q = p; p = nullptr; return q; }
 };
 
+// DevBuf with its element type and counts in elements: the type is stated once, at the declaration, and the compiler holds every
+// launch, sort / scan call and copy to it.  DevBuf stays for raw-byte workspaces (rocPRIM's temporary storage, scratch carved
+// into several types).  Bound to a stream it drains the stream before the block goes back to the pool, like DevBuf; without one
+// (a handle's member, whose owner has synchronised) it only gives the block back.  The conversion to T * is not seen by template
+// argument deduction: a template callee names its type (sort_pairs<uint64_t>(...), loop_write_kernel<Cand><<<...>>>(...)).
+template <class T> struct DevArr {
+    T *p = nullptr;
+    hipStream_t stream = nullptr;
+    DevArr() {}
+    explicit DevArr(hipStream_t s) : stream(s) {}
+    DevArr(const DevArr &) = delete;
+    DevArr &operator=(const DevArr &) = delete;
+    ~DevArr() { reset(); }
+    static constexpr size_t bytes(size_t count) { return count * sizeof(T); }
+    static constexpr size_t bytes_for(size_t count) { return count ? bytes(count) : 8; } // what alloc(count) asks the pool for
+    hipError_t alloc(size_t count) { return DevicePool::get().alloc((void **)&p, bytes_for(count)); }
+    operator T *() const { return p; }
+    T *release() { T *q = p; p = nullptr; return q; }
+    // give the block back (after draining the stream) and hold q instead
+    void reset(T *q = nullptr)
+    {
+        if (p) {
+            if (stream) (void)hipStreamSynchronize(stream);
+            DevicePool::get().free(p);
+        }
+        p = q;
+    }
+    // a spelled-out reinterpretation, for a buffer that holds two types in turn (say why at each use)
+    template <class U> U *as() const { return (U *)p; }
+    // synchronous chunked copies of pageable host tables (copy_chunked above), an asynchronous zero-fill on the array's own
+    // stream (stream-bound arrays only); counts in elements
+    hipError_t upload(const T *src, size_t count) { return copy_h2d(p, src, bytes(count)); }
+    hipError_t download(T *dst, size_t count) const { return copy_d2h(dst, p, bytes(count)); }
+    template <class V> hipError_t alloc_upload(const V &v) // std::vector<T> / hvec<T>
+    {
+        const hipError_t e = alloc(v.size());
+        return e != hipSuccess ? e : upload(v.data(), v.size());
+    }
+    hipError_t zero_async(size_t count, size_t first = 0) { return hipMemsetAsync(p + first, 0, bytes(count), stream); }
+};
+
+// A handle-owned device pointer from the pool: typed and counted like bs_dmalloc (block_system.h), without its accounting.  The
+// handle's destroy list gives it back with DevicePool::free.
+template <class T> inline hipError_t pool_alloc(T **p, size_t count) { return DevicePool::get().alloc((void **)p, DevArr<T>::bytes_for(count)); }
+
 } // namespace lvba

@@ -138,9 +138,9 @@ int32_t adjacency_build(hipStream_t s, int64_t G, const int64_t *h_voff, int64_t
                         uint8_t *h_adj)
 {
     const size_t nn = (size_t)N * N;
-    DevBuf d_adj(s), d_voff(s), d_poff(s), d_pidx(s);
+    DevArr<uint8_t> d_adj(s); DevArr<int64_t> d_voff(s), d_poff(s); DevArr<int32_t> d_pidx(s);
     HIPCHK(d_adj.alloc(nn));
-    HIPCHK(hipMemsetAsync(d_adj.p, 0, nn, s));
+    HIPCHK(d_adj.zero_async(nn));
     if (Q > 0) {
         lvba::hvec<int64_t> poff((size_t)G + 1, 0);
         for (int64_t a = 0; a < G; ++a) {
@@ -148,16 +148,14 @@ int32_t adjacency_build(hipStream_t s, int64_t G, const int64_t *h_voff, int64_t
             poff[a + 1] = poff[a] + k * (k - 1) / 2;
         }
         if (poff[G] != Q) return LVBA_ERR_STATE;
-        HIPCHK(d_voff.alloc(8 * ((size_t)G + 1))); HIPCHK(d_poff.alloc(8 * ((size_t)G + 1))); HIPCHK(d_pidx.alloc(4 * (size_t)F));
-        HIPCHK(lvba::copy_h2d(d_voff.p, h_voff, 8 * ((size_t)G + 1)));
-        HIPCHK(lvba::copy_h2d(d_poff.p, poff.data(), 8 * ((size_t)G + 1)));
-        HIPCHK(lvba::copy_h2d(d_pidx.p, h_pidx, 4 * (size_t)F)); // (pieces below the pinning threshold: mempool.h)
-        adj_kernel<<<(unsigned)((Q + 255) / 256), 256, 0, s>>>((const int64_t *)d_voff.p, (const int64_t *)d_poff.p,
-                                                               (const int32_t *)d_pidx.p, G, Q, N, (uint8_t *)d_adj.p);
+        HIPCHK(d_voff.alloc((size_t)G + 1)); HIPCHK(d_poff.alloc((size_t)G + 1)); HIPCHK(d_pidx.alloc((size_t)F));
+        HIPCHK(d_voff.upload(h_voff, (size_t)G + 1)); HIPCHK(d_poff.upload(poff.data(), (size_t)G + 1));
+        HIPCHK(d_pidx.upload(h_pidx, (size_t)F)); // (pieces below the pinning threshold: mempool.h)
+        adj_kernel<<<(unsigned)((Q + 255) / 256), 256, 0, s>>>(d_voff, d_poff, d_pidx, G, Q, N, d_adj);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(s)); // poff is a local
     }
-    HIPCHK(hipMemcpyAsync(h_adj, d_adj.p, nn, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h_adj, d_adj, d_adj.bytes(nn), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return LVBA_OK;
 }
@@ -170,30 +168,27 @@ int32_t csc_build(hipStream_t s, int64_t G, const int64_t *h_voff, int64_t F, co
                   const int32_t *h_iperm, int32_t *d_csc_f, int32_t *d_group_of_pos, int32_t *d_pos_of, int64_t *d_csc_off,
                   int32_t *d_blk_of)
 {
-    DevBuf d_pidx(s), d_iperm(s), d_voff(s), key(s), val(s), key_s(s), val_s(s), tmp(s);
-    HIPCHK(d_iperm.alloc(4 * (size_t)std::max(N, 1)));
-    HIPCHK(hipMemcpyAsync(d_iperm.p, h_iperm, 4 * (size_t)N, hipMemcpyHostToDevice, s));
+    DevArr<int32_t> d_pidx(s), d_iperm(s); DevArr<int64_t> d_voff(s); DevArr<uint32_t> key(s), val(s), key_s(s), val_s(s);
+    DevBuf tmp(s);
+    HIPCHK(d_iperm.alloc((size_t)std::max(N, 1)));
+    HIPCHK(hipMemcpyAsync(d_iperm, h_iperm, d_iperm.bytes((size_t)N), hipMemcpyHostToDevice, s));
     if (F > 0) {
-        HIPCHK(d_pidx.alloc(4 * (size_t)F)); HIPCHK(d_voff.alloc(8 * ((size_t)G + 1)));
-        HIPCHK(key.alloc(4 * (size_t)F)); HIPCHK(val.alloc(4 * (size_t)F)); HIPCHK(key_s.alloc(4 * (size_t)F)); HIPCHK(val_s.alloc(4 * (size_t)F));
-        HIPCHK(lvba::copy_h2d(d_pidx.p, h_pidx, 4 * (size_t)F)); // (pieces below the pinning threshold: mempool.h)
-        HIPCHK(lvba::copy_h2d(d_voff.p, h_voff, 8 * ((size_t)G + 1)));
-        csc_key_kernel<<<(unsigned)((F + 255) / 256), 256, 0, s>>>(F, (const int32_t *)d_pidx.p, (const int32_t *)d_iperm.p,
-                                                                   (uint32_t *)key.p, (uint32_t *)val.p, d_blk_of);
+        HIPCHK(d_pidx.alloc((size_t)F)); HIPCHK(d_voff.alloc((size_t)G + 1));
+        HIPCHK(key.alloc((size_t)F)); HIPCHK(val.alloc((size_t)F)); HIPCHK(key_s.alloc((size_t)F)); HIPCHK(val_s.alloc((size_t)F));
+        HIPCHK(d_pidx.upload(h_pidx, (size_t)F)); // (pieces below the pinning threshold: mempool.h)
+        HIPCHK(d_voff.upload(h_voff, (size_t)G + 1));
+        csc_key_kernel<<<(unsigned)((F + 255) / 256), 256, 0, s>>>(F, d_pidx, d_iperm, key, val, d_blk_of);
         HIPCHK(hipGetLastError());
         unsigned end_bit = 1;
         while (end_bit < 32 && ((uint32_t)N >> end_bit) != 0) ++end_bit;
         size_t bytes = 0;
-        HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes, (const uint32_t *)key.p, (uint32_t *)key_s.p, (const uint32_t *)val.p,
-                                         (uint32_t *)val_s.p, (size_t)F, 0u, end_bit, s));
+        HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes, (const uint32_t *)key, key_s.p, (const uint32_t *)val, val_s.p, (size_t)F, 0u, end_bit, s));
         HIPCHK(tmp.alloc(bytes));
-        HIPCHK(rocprim::radix_sort_pairs(tmp.p, bytes, (const uint32_t *)key.p, (uint32_t *)key_s.p, (const uint32_t *)val.p,
-                                         (uint32_t *)val_s.p, (size_t)F, 0u, end_bit, s));
-        csc_tables_kernel<<<(unsigned)((F + 255) / 256), 256, 0, s>>>(F, G, (const uint32_t *)val_s.p, (const int64_t *)d_voff.p, d_csc_f,
-                                                                      d_group_of_pos, d_pos_of);
+        HIPCHK(rocprim::radix_sort_pairs(tmp.p, bytes, (const uint32_t *)key, key_s.p, (const uint32_t *)val, val_s.p, (size_t)F, 0u, end_bit, s));
+        csc_tables_kernel<<<(unsigned)((F + 255) / 256), 256, 0, s>>>(F, G, val_s, d_voff, d_csc_f, d_group_of_pos, d_pos_of);
         HIPCHK(hipGetLastError());
     }
-    csc_off_kernel<<<(unsigned)((N + 1 + 255) / 256), 256, 0, s>>>(N, F, (const uint32_t *)key_s.p, d_csc_off);
+    csc_off_kernel<<<(unsigned)((N + 1 + 255) / 256), 256, 0, s>>>(N, F, key_s, d_csc_off);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
     return LVBA_OK;
@@ -226,48 +221,37 @@ int32_t pair_lists_build(hipStream_t s, int64_t G, const int64_t *h_voff, int64_
     }
     const uint64_t block_mask = (block_bits >= 64) ? ~0ull : (((uint64_t)1 << block_bits) - 1);
 
-    DevBuf d_voff(s), d_poff(s), k_in(s), k_out(s), v_in(s), uniq(s), cnt(s), nruns(s), tmp(s);
-    HIPCHK(d_voff.alloc((size_t)(G + 1) * 8));
-    HIPCHK(d_poff.alloc((size_t)(G + 1) * 8));
-    HIPCHK(k_in.alloc((size_t)Q * 8));
-    HIPCHK(k_out.alloc((size_t)Q * 8));
-    HIPCHK(v_in.alloc((size_t)Q * 8));
-    HIPCHK(lvba::copy_h2d(d_voff.p, h_voff, (size_t)(G + 1) * 8));
-    HIPCHK(lvba::copy_h2d(d_poff.p, poff.data(), (size_t)(G + 1) * 8));
-    pair_gen_kernel<<<(unsigned)((Q + 255) / 256), 256, 0, s>>>((const int64_t *)d_voff.p, (const int64_t *)d_poff.p,
-                                                                d_blk_of, d_pos_of, G, Q, tiles_per_row, window_groups,
-                                                                block_bits, (uint64_t *)k_in.p, (uint64_t *)v_in.p);
+    DevArr<int64_t> d_voff(s), d_poff(s); DevArr<uint64_t> k_in(s), k_out(s), v_in(s), uniq(s); DevArr<uint32_t> cnt(s);
+    DevArr<uint64_t> nruns(s); DevBuf tmp(s);
+    HIPCHK(d_voff.alloc((size_t)(G + 1))); HIPCHK(d_poff.alloc((size_t)(G + 1))); HIPCHK(k_in.alloc((size_t)Q));
+    HIPCHK(k_out.alloc((size_t)Q)); HIPCHK(v_in.alloc((size_t)Q)); HIPCHK(d_voff.upload(h_voff, (size_t)(G + 1)));
+    HIPCHK(d_poff.upload(poff.data(), (size_t)(G + 1)));
+    pair_gen_kernel<<<(unsigned)((Q + 255) / 256), 256, 0, s>>>(d_voff, d_poff, d_blk_of, d_pos_of, G, Q, tiles_per_row,
+                                                                window_groups, block_bits, k_in, v_in);
     HIPCHK(hipGetLastError());
     {
         size_t bytes = 0;
-        HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes, (const uint64_t *)k_in.p, (uint64_t *)k_out.p, (const uint64_t *)v_in.p,
-                                         (uint64_t *)d_pairs, (size_t)Q, 0u, end_bit, s));
+        HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes, (const uint64_t *)k_in, k_out.p, (const uint64_t *)v_in, (uint64_t *)d_pairs, (size_t)Q, 0u, end_bit, s));
         HIPCHK(tmp.alloc(bytes));
-        HIPCHK(rocprim::radix_sort_pairs(tmp.p, bytes, (const uint64_t *)k_in.p, (uint64_t *)k_out.p, (const uint64_t *)v_in.p,
-                                         (uint64_t *)d_pairs, (size_t)Q, 0u, end_bit, s));
+        HIPCHK(rocprim::radix_sort_pairs(tmp.p, bytes, (const uint64_t *)k_in, k_out.p, (const uint64_t *)v_in, (uint64_t *)d_pairs, (size_t)Q, 0u, end_bit, s));
     }
     // non-empty blocks and their list lengths; the number of runs is bounded by the band profile N * Bb1 and by Q
     const int64_t max_runs = window_groups > 0 ? Q : std::min<int64_t>(Q, (int64_t)N * Bb1);
-    HIPCHK(uniq.alloc((size_t)max_runs * 8));
-    HIPCHK(cnt.alloc((size_t)max_runs * 4));
-    HIPCHK(nruns.alloc(8));
+    HIPCHK(uniq.alloc((size_t)max_runs)); HIPCHK(cnt.alloc((size_t)max_runs)); HIPCHK(nruns.alloc(1));
     {
         size_t bytes = 0;
-        HIPCHK(rocprim::run_length_encode(nullptr, bytes, (const uint64_t *)k_out.p, (size_t)Q, (uint64_t *)uniq.p,
-                                          (uint32_t *)cnt.p, (uint64_t *)nruns.p, s));
+        HIPCHK(rocprim::run_length_encode(nullptr, bytes, (const uint64_t *)k_out, (size_t)Q, uniq.p, cnt.p, nruns.p, s));
         DevBuf tmp2(s);
         HIPCHK(tmp2.alloc(bytes));
-        HIPCHK(rocprim::run_length_encode(tmp2.p, bytes, (const uint64_t *)k_out.p, (size_t)Q, (uint64_t *)uniq.p,
-                                          (uint32_t *)cnt.p, (uint64_t *)nruns.p, s));
+        HIPCHK(rocprim::run_length_encode(tmp2.p, bytes, (const uint64_t *)k_out, (size_t)Q, uniq.p, cnt.p, nruns.p, s));
         HIPCHK(hipStreamSynchronize(s));
     }
     uint64_t n_runs = 0;
-    HIPCHK(lvba::copy_d2h(&n_runs, nruns.p, 8));
+    HIPCHK(nruns.download(&n_runs, 1));
     lvba::hvec<uint64_t> h_uniq((size_t)n_runs);
     lvba::hvec<uint32_t> h_cnt((size_t)n_runs);
     if (n_runs) {
-        HIPCHK(lvba::copy_d2h(h_uniq.data(), uniq.p, (size_t)n_runs * 8));
-        HIPCHK(lvba::copy_d2h(h_cnt.data(), cnt.p, (size_t)n_runs * 4));
+        HIPCHK(uniq.download(h_uniq.data(), (size_t)n_runs)); HIPCHK(cnt.download(h_cnt.data(), (size_t)n_runs));
     }
     auto slot_of_key = [&](uint64_t k64) {
         const uint64_t key = k64 & block_mask, tile = key >> 6;
@@ -303,16 +287,14 @@ int32_t pair_lists_build(hipStream_t s, int64_t G, const int64_t *h_voff, int64_
             new_off[i + 1] = new_off[i] + pc[i].len;
         }
         blk_off = new_off;
-        DevBuf d_new(s), d_old(s);
-        HIPCHK(d_new.alloc((np + 1) * 8));
-        HIPCHK(d_old.alloc(np * 8));
-        HIPCHK(lvba::copy_h2d(d_new.p, new_off.data(), (np + 1) * 8));
-        HIPCHK(lvba::copy_h2d(d_old.p, old_off.data(), np * 8));
+        DevArr<int64_t> d_new(s), d_old(s);
+        HIPCHK(d_new.alloc(np + 1)); HIPCHK(d_old.alloc(np)); HIPCHK(d_new.upload(new_off.data(), np + 1));
+        HIPCHK(d_old.upload(old_off.data(), np));
         // v_in (the unsorted values) is free: gather into it, then back into the caller's array
-        pair_permute_kernel<<<(unsigned)((Q + 255) / 256), 256, 0, s>>>(Q, (int64_t)np, (const int64_t *)d_new.p, (const int64_t *)d_old.p,
-                                                                        (const uint64_t *)d_pairs, (uint64_t *)v_in.p);
+        pair_permute_kernel<<<(unsigned)((Q + 255) / 256), 256, 0, s>>>(Q, (int64_t)np, d_new, d_old, (const uint64_t *)d_pairs,
+                                                                        v_in);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(d_pairs, v_in.p, (size_t)Q * 8, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(d_pairs, v_in, v_in.bytes((size_t)Q), hipMemcpyDeviceToDevice, s));
         HIPCHK(hipStreamSynchronize(s));
         return LVBA_OK;
     }

@@ -231,34 +231,34 @@ int32_t search_dev(hipStream_t s, int n, const float *d_desc, const PlaceParams 
     const size_t cells = (size_t)p.n_rings * p.n_sectors, K = (size_t)p.n_key;
     const int nq = (int)(((int64_t)n + p.query_stride - 1) / p.query_stride);
     if ((int64_t)nq * p.n_key > INT32_MAX) return lvba_fail(LVBA_ERR_ARG, "%d queries x %d key candidates: more than 2^31 - 1 pairs", nq, p.n_key);
-    DevBuf d_key(s), d_U(s), d_mask(s), d_pick(s), d_dist(s), d_shift(s), d_count(s), d_first(s), d_stage(s), d_out(s);
-    HIPCHK(d_key.alloc(4 * (size_t)n * p.n_rings)); HIPCHK(d_U.alloc(8 * (size_t)n * cells)); HIPCHK(d_mask.alloc(16 * (size_t)n));
-    HIPCHK(d_pick.alloc(4 * (size_t)nq * K)); HIPCHK(d_dist.alloc(8 * (size_t)nq * K)); HIPCHK(d_shift.alloc(4 * (size_t)nq * K));
-    HIPCHK(d_count.alloc(8 * ((size_t)nq + 1))); HIPCHK(d_first.alloc(8 * ((size_t)nq + 1)));
-    HIPCHK(d_stage.alloc(sizeof(lvba_place_candidate) * (size_t)nq * (size_t)p.max_per_frame));
-    place_finish_kernel<<<n, FIN_BLOCK, 0, s>>>(d_desc, p, d_key.as<float>(), d_U.as<double>(), d_mask.as<uint64_t>());
+    DevArr<float> d_key(s); DevArr<double> d_U(s); DevArr<uint64_t> d_mask(s); DevArr<int32_t> d_pick(s); DevArr<double> d_dist(s);
+    DevArr<int32_t> d_shift(s); DevArr<int64_t> d_count(s), d_first(s); DevArr<lvba_place_candidate> d_stage(s), d_out(s);
+    HIPCHK(d_key.alloc((size_t)n * p.n_rings)); HIPCHK(d_U.alloc((size_t)n * cells)); HIPCHK(d_mask.alloc(2 * (size_t)n));
+    HIPCHK(d_pick.alloc((size_t)nq * K)); HIPCHK(d_dist.alloc((size_t)nq * K)); HIPCHK(d_shift.alloc((size_t)nq * K));
+    HIPCHK(d_count.alloc((size_t)nq + 1)); HIPCHK(d_first.alloc((size_t)nq + 1));
+    HIPCHK(d_stage.alloc((size_t)nq * (size_t)p.max_per_frame));
+    place_finish_kernel<<<n, FIN_BLOCK, 0, s>>>(d_desc, p, d_key, d_U, d_mask);
     HIPCHK(hipGetLastError());
-    place_key_kernel<<<grid_for(nq, KEY_BLOCK / 64), KEY_BLOCK, 0, s>>>(n, nq, d_key.as<float>(), p, d_pick.as<int32_t>());
+    place_key_kernel<<<grid_for(nq, KEY_BLOCK / 64), KEY_BLOCK, 0, s>>>(n, nq, d_key, p, d_pick);
     HIPCHK(hipGetLastError());
-    place_shift_kernel<<<(unsigned)((size_t)nq * K), 64, 16 * cells, s>>>(d_pick.as<int32_t>(), d_U.as<double>(), d_mask.as<uint64_t>(), p,
-                                                                        d_dist.as<double>(), d_shift.as<int32_t>());
+    place_shift_kernel<<<(unsigned)((size_t)nq * K), 64, 16 * cells, s>>>(d_pick, d_U, d_mask, p,
+                                                                        d_dist, d_shift);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemsetAsync(d_count.as<int64_t>() + nq, 0, 8, s));
-    place_select_kernel<<<nq, 64, 0, s>>>(d_pick.as<int32_t>(), d_dist.as<double>(), d_shift.as<int32_t>(), p, d_count.as<int64_t>(),
-                                          d_stage.as<lvba_place_candidate>());
+    HIPCHK(d_count.zero_async(1, nq));
+    place_select_kernel<<<nq, 64, 0, s>>>(d_pick, d_dist, d_shift, p, d_count, d_stage);
     HIPCHK(hipGetLastError());
-    TRY(scan_excl<int64_t>(s, d_count.as<int64_t>(), d_first.as<int64_t>(), (size_t)nq + 1));
+    TRY(scan_excl<int64_t>(s, d_count, d_first, (size_t)nq + 1));
     int64_t total = 0;
-    HIPCHK(lvba::copy_d2h(&total, d_first.as<int64_t>() + nq, 8));
+    HIPCHK(copy_d2h(&total, d_first + nq, d_first.bytes(1)));
     *count = total;
     const int64_t n_out = std::min(total, capacity);
     if (n_out == 0) return LVBA_OK;
-    HIPCHK(d_out.alloc(sizeof(lvba_place_candidate) * (size_t)n_out));
-    loop_write_kernel<<<grid_for(nq, 256), 256, 0, s>>>(nq, p.max_per_frame, d_count.as<int64_t>(), d_first.as<int64_t>(),
-                                                        d_stage.as<lvba_place_candidate>(), n_out, d_out.as<lvba_place_candidate>());
+    HIPCHK(d_out.alloc((size_t)n_out));
+    loop_write_kernel<lvba_place_candidate><<<grid_for(nq, 256), 256, 0, s>>>(nq, p.max_per_frame, d_count, d_first,
+                                                        d_stage, n_out, d_out);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(lvba::copy_d2h(out, d_out.p, sizeof(lvba_place_candidate) * (size_t)n_out));
+    HIPCHK(d_out.download(out, (size_t)n_out));
     return LVBA_OK;
 }
 
@@ -288,14 +288,13 @@ extern "C" int32_t lvba_place_descriptors(lvba_scans_t sc, int32_t frame_begin, 
     HIPCHK(hipSetDevice(sc->device));
     ScopedStream sg;
     HIPCHK(sg.acquire());
-    DevBuf d_desc(sg.s), d_key(sg.s);
-    HIPCHK(d_desc.alloc(4 * n * cells)); HIPCHK(d_key.alloc(4 * n * p.n_rings));
-    TRY(describe_dev(sg.s, sc, frame_begin, n_frames, p, d_desc.as<float>()));
-    place_finish_kernel<<<n_frames, FIN_BLOCK, 0, sg.s>>>(d_desc.as<float>(), p, d_key.as<float>(), nullptr, nullptr);
+    DevArr<float> d_desc(sg.s), d_key(sg.s);
+    HIPCHK(d_desc.alloc(n * cells)); HIPCHK(d_key.alloc(n * p.n_rings));
+    TRY(describe_dev(sg.s, sc, frame_begin, n_frames, p, d_desc));
+    place_finish_kernel<<<n_frames, FIN_BLOCK, 0, sg.s>>>(d_desc, p, d_key, nullptr, nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(sg.s));
-    HIPCHK(lvba::copy_d2h(desc, d_desc.p, 4 * n * cells));
-    HIPCHK(lvba::copy_d2h(ring_key, d_key.p, 4 * n * p.n_rings));
+    HIPCHK(d_desc.download(desc, n * cells)); HIPCHK(d_key.download(ring_key, n * p.n_rings));
     return LVBA_OK;
 }
 
@@ -316,10 +315,9 @@ extern "C" int32_t lvba_place_search(int32_t device, int32_t n_frames, const flo
     HIPCHK(hipSetDevice(device));
     ScopedStream sg;
     HIPCHK(sg.acquire());
-    DevBuf d_desc(sg.s);
-    HIPCHK(d_desc.alloc(4 * n * cells));
-    HIPCHK(lvba::copy_h2d(d_desc.p, desc, 4 * n * cells));
-    return search_dev(sg.s, n_frames, d_desc.as<float>(), p, capacity, out, count);
+    DevArr<float> d_desc(sg.s);
+    HIPCHK(d_desc.alloc(n * cells)); HIPCHK(d_desc.upload(desc, n * cells));
+    return search_dev(sg.s, n_frames, d_desc, p, capacity, out, count);
 }
 
 extern "C" int32_t lvba_place_candidates(lvba_scans_t sc, const lvba_place_opts *opts, int64_t capacity, lvba_place_candidate *out,
@@ -335,8 +333,7 @@ extern "C" int32_t lvba_place_candidates(lvba_scans_t sc, const lvba_place_opts 
     HIPCHK(hipSetDevice(sc->device));
     ScopedStream sg;
     HIPCHK(sg.acquire());
-    DevBuf d_desc(sg.s);
-    HIPCHK(d_desc.alloc(4 * (size_t)n * p.n_rings * p.n_sectors));
-    TRY(describe_dev(sg.s, sc, 0, n, p, d_desc.as<float>()));
-    return search_dev(sg.s, n, d_desc.as<float>(), p, capacity, out, count);
+    DevArr<float> d_desc(sg.s);
+    HIPCHK(d_desc.alloc((size_t)n * p.n_rings * p.n_sectors)); TRY(describe_dev(sg.s, sc, 0, n, p, d_desc));
+    return search_dev(sg.s, n, d_desc, p, capacity, out, count);
 }

@@ -61,19 +61,17 @@ __device__ __forceinline__ void ransac_block_best(const RansacLane &ln, int32_t 
 // The hypotheses of every task with at least `need` elements, one grid: launch(n_tiles, tiles) starts the stage's kernel on s.
 // blk0 / n_blk of the tasks are set here, before they go up.  d_blk: the block records.
 template <int NM, class Task, class Launch>
-int32_t ransac_run_hypotheses(hipStream_t s, std::vector<Task> &tasks, int32_t H, int32_t need, DevBuf &d_tasks, DevBuf &d_blk, const Launch &launch)
+int32_t ransac_run_hypotheses(hipStream_t s, std::vector<Task> &tasks, int32_t H, int32_t need, DevArr<Task> &d_tasks,
+                              DevArr<RansacBest<NM>> &d_blk, const Launch &launch)
 {
     std::vector<RansacTile> tiles;
     if (ransac_plan(tasks.data(), tasks.size(), H, RANSAC_HB, need, &tiles) < 0)
         return lvba_fail(LVBA_ERR_UNSUPPORTED, "more than 2^30 hypothesis blocks in one call");
-    HIPCHK(d_tasks.alloc(sizeof(Task) * tasks.size()));
-    HIPCHK(lvba::copy_h2d(d_tasks.p, tasks.data(), sizeof(Task) * tasks.size()));
-    HIPCHK(d_blk.alloc(sizeof(RansacBest<NM>) * tiles.size()));
+    HIPCHK(d_tasks.alloc_upload(tasks)); HIPCHK(d_blk.alloc(tiles.size()));
     if (tiles.empty()) return LVBA_OK;
-    DevBuf d_tiles(s);
-    HIPCHK(d_tiles.alloc(sizeof(RansacTile) * tiles.size()));
-    HIPCHK(lvba::copy_h2d(d_tiles.p, tiles.data(), sizeof(RansacTile) * tiles.size()));
-    launch((unsigned)tiles.size(), d_tiles.as<RansacTile>());
+    DevArr<RansacTile> d_tiles(s);
+    HIPCHK(d_tiles.alloc_upload(tiles));
+    launch((unsigned)tiles.size(), d_tiles);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s)); // the tile list goes with this scope
     return LVBA_OK;
@@ -129,21 +127,21 @@ template <class Task, class Inlier, class Emit>
 int32_t ransac_inlier_lists(hipStream_t s, int64_t total, int n_tasks, const Task *d_tasks, const int32_t *d_status, const Inlier &inlier,
                             const Emit &emit, int64_t capacity, int64_t *inlier_off, int32_t *inliers)
 {
-    DevBuf d_flag(s), d_excl(s), d_off(s), d_out(s);
-    HIPCHK(d_flag.alloc(4 * ((size_t)total + 1))); HIPCHK(d_excl.alloc(4 * ((size_t)total + 1))); HIPCHK(d_off.alloc(8 * ((size_t)n_tasks + 1)));
-    ransac_mask_kernel<<<grid_for(total + 1, 256), 256, 0, s>>>(total, n_tasks, d_tasks, d_status, inlier, d_flag.as<uint32_t>());
+    DevArr<uint32_t> d_flag(s), d_excl(s); DevArr<int64_t> d_off(s); DevArr<int32_t> d_out(s);
+    HIPCHK(d_flag.alloc((size_t)total + 1)); HIPCHK(d_excl.alloc((size_t)total + 1)); HIPCHK(d_off.alloc((size_t)n_tasks + 1));
+    ransac_mask_kernel<<<grid_for(total + 1, 256), 256, 0, s>>>(total, n_tasks, d_tasks, d_status, inlier, d_flag);
     HIPCHK(hipGetLastError());
-    TRY(scan_excl<uint32_t>(s, d_flag.as<uint32_t>(), d_excl.as<uint32_t>(), (size_t)total + 1));
+    TRY(scan_excl<uint32_t>(s, d_flag, d_excl, (size_t)total + 1));
     uint32_t found = 0;
-    HIPCHK(lvba::copy_d2h(&found, d_excl.as<uint32_t>() + total, 4));
+    HIPCHK(copy_d2h(&found, d_excl + total, d_excl.bytes(1)));
     const int64_t n_out = std::min<int64_t>(found, capacity);
-    HIPCHK(d_out.alloc(4 * Emit::WIDTH * (size_t)n_out));
+    HIPCHK(d_out.alloc(Emit::WIDTH * (size_t)n_out));
     ransac_write_kernel<<<grid_for(std::max<int64_t>(total, n_tasks + 1), 256), 256, 0, s>>>(
-        total, n_tasks, d_tasks, d_flag.as<uint32_t>(), d_excl.as<uint32_t>(), n_out, emit, d_out.as<int32_t>(), d_off.as<int64_t>());
+        total, n_tasks, d_tasks, d_flag, d_excl, n_out, emit, d_out, d_off);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(lvba::copy_d2h(inlier_off, d_off.p, 8 * ((size_t)n_tasks + 1)));
-    if (n_out > 0) HIPCHK(lvba::copy_d2h(inliers, d_out.p, 4 * Emit::WIDTH * (size_t)n_out));
+    HIPCHK(d_off.download(inlier_off, (size_t)n_tasks + 1));
+    if (n_out > 0) HIPCHK(d_out.download(inliers, Emit::WIDTH * (size_t)n_out));
     return LVBA_OK;
 }
 
@@ -153,16 +151,15 @@ int32_t ransac_score_mask(hipStream_t s, const Task &task, const Inlier &inlier,
 {
     const size_t n = (size_t)task.span.m;
     const int32_t ok = RANSAC_OK;
-    DevBuf d_tasks(s), d_st(s), d_flag(s);
-    HIPCHK(d_tasks.alloc(sizeof(Task))); HIPCHK(d_st.alloc(4)); HIPCHK(d_flag.alloc(4 * (n + 1)));
-    HIPCHK(lvba::copy_h2d(d_tasks.p, &task, sizeof(Task)));
-    HIPCHK(lvba::copy_h2d(d_st.p, &ok, 4));
-    ransac_mask_kernel<<<grid_for((int64_t)n + 1, 256), 256, 0, s>>>((int64_t)n, 1, d_tasks.as<Task>(), d_st.as<int32_t>(), inlier,
-                                                                    d_flag.as<uint32_t>());
+    DevArr<Task> d_tasks(s); DevArr<int32_t> d_st(s); DevArr<uint32_t> d_flag(s);
+    HIPCHK(d_tasks.alloc(1)); HIPCHK(d_st.alloc(1)); HIPCHK(d_flag.alloc(n + 1)); HIPCHK(d_tasks.upload(&task, 1));
+    HIPCHK(d_st.upload(&ok, 1));
+    ransac_mask_kernel<Task><<<grid_for((int64_t)n + 1, 256), 256, 0, s>>>((int64_t)n, 1, d_tasks, d_st, inlier,
+                                                                    d_flag);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
     std::vector<uint32_t> flag(n);
-    HIPCHK(lvba::copy_d2h(flag.data(), d_flag.p, 4 * n));
+    HIPCHK(d_flag.download(flag.data(), n));
     for (size_t i = 0; i < n; ++i) mask[i] = flag[i] ? 1 : 0;
     return LVBA_OK;
 }

@@ -194,34 +194,34 @@ int32_t reg_run(lvba_voxmap_t map, lvba_scans_t sc, int32_t n, const int32_t *fr
         hres[k].status = REG_RUNNING;
         hres[k].points = sc->frame_off[frames[k] + 1] - sc->frame_off[frames[k]];
     }
-    DevBuf d_frames(s), d_poses(s), d_res(s), d_part(s), d_sums(s), d_submap(s);
+    DevArr<int32_t> d_frames(s); DevArr<double> d_poses(s); DevArr<lvba_register_result> d_res(s);
+    DevArr<double> d_part(s), d_sums(s); DevArr<int32_t> d_submap(s);
     if (submaps) {
-        HIPCHK(d_submap.alloc(4 * (size_t)n));
-        HIPCHK(hipMemcpyAsync(d_submap.p, submap, 4 * (size_t)n, hipMemcpyHostToDevice, s));
+        HIPCHK(d_submap.alloc((size_t)n));
+        HIPCHK(hipMemcpyAsync(d_submap, submap, d_submap.bytes((size_t)n), hipMemcpyHostToDevice, s));
     }
-    HIPCHK(d_frames.alloc(4 * (size_t)n)); HIPCHK(d_poses.alloc(96 * (size_t)n)); HIPCHK(d_res.alloc(sizeof(lvba_register_result) * (size_t)n));
-    HIPCHK(d_part.alloc(8 * (size_t)REG_NS * (size_t)max_blocks * (size_t)n)); HIPCHK(d_sums.alloc(8 * (size_t)REG_NS * (size_t)n));
-    HIPCHK(hipMemcpyAsync(d_frames.p, frames, 4 * (size_t)n, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_poses.p, poses, 96 * (size_t)n, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_res.p, hres.data(), sizeof(lvba_register_result) * (size_t)n, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(d_sums.p, 0, 8 * (size_t)REG_NS * (size_t)n, s));
+    HIPCHK(d_frames.alloc((size_t)n)); HIPCHK(d_poses.alloc(12 * (size_t)n)); HIPCHK(d_res.alloc((size_t)n));
+    HIPCHK(d_part.alloc((size_t)REG_NS * (size_t)max_blocks * (size_t)n)); HIPCHK(d_sums.alloc((size_t)REG_NS * (size_t)n));
+    HIPCHK(hipMemcpyAsync(d_frames, frames, d_frames.bytes((size_t)n), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_poses, poses, d_poses.bytes(12 * (size_t)n), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_res, hres.data(), d_res.bytes((size_t)n), hipMemcpyHostToDevice, s));
+    HIPCHK(d_sums.zero_async((size_t)REG_NS * (size_t)n));
     for (int it = 0; it < max_it; ++it) {
         (submaps ? reg_linearize_kernel<true> : reg_linearize_kernel<false>)<<<dim3((unsigned)max_blocks, (unsigned)n), REG_BLOCK, 0, s>>>(
-            tab, sc->d_pts, sc->d_frame_off, d_frames.as<int32_t>(), d_submap.as<int32_t>(), d_poses.as<double>(), d_res.as<lvba_register_result>(), par,
-            d_part.as<double>());
+            tab, sc->d_pts, sc->d_frame_off, d_frames, d_submap, d_poses, d_res, par,
+            d_part);
         HIPCHK(hipGetLastError());
-        reg_step_kernel<<<(unsigned)n, 64, 0, s>>>(max_blocks, sc->d_frame_off, d_frames.as<int32_t>(), d_part.as<double>(), par,
-                                                   sums_only ? 1 : 0, it, max_it, d_poses.as<double>(), d_res.as<lvba_register_result>(),
-                                                   d_sums.as<double>(), d_words + it);
+        reg_step_kernel<<<(unsigned)n, 64, 0, s>>>(max_blocks, sc->d_frame_off, d_frames, d_part, par, sums_only ? 1 : 0, it,
+                                                   max_it, d_poses, d_res, d_sums, d_words + it);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(s));
         if (!words.p[it]) break; // every job has finished
     }
     std::vector<double> hsums((size_t)REG_NS * (size_t)n);
-    HIPCHK(hipMemcpyAsync(hsums.data(), d_sums.p, 8 * hsums.size(), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(hsums.data(), d_sums, d_sums.bytes(hsums.size()), hipMemcpyDeviceToHost, s));
     if (!sums_only) {
-        HIPCHK(hipMemcpyAsync(poses_out, d_poses.p, 96 * (size_t)n, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(results, d_res.p, sizeof(lvba_register_result) * (size_t)n, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(poses_out, d_poses, d_poses.bytes(12 * (size_t)n), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(results, d_res, d_res.bytes((size_t)n), hipMemcpyDeviceToHost, s));
     }
     HIPCHK(hipStreamSynchronize(s));
     for (int32_t k = 0; k < n; ++k) {

@@ -260,7 +260,7 @@ int32_t check_camera(const double *intr)
 // The records of the call's correspondences on the device: the pixels undistorted (image_set.hip), then packed with the world points.
 struct Records {
     ImageSet set;
-    DevBuf rec;
+    DevArr<double> rec;
     explicit Records(hipStream_t s) : rec(s) {}
     ~Records() { image_set_free(set); }
 };
@@ -269,13 +269,12 @@ int32_t make_records(hipStream_t s, int device, int32_t n_jobs, const int64_t *c
 {
     r.set = ImageSet{device, n_jobs, std::vector<int64_t>(corr_off, corr_off + n_jobs + 1)};
     const int64_t total = corr_off[n_jobs];
-    HIPCHK(r.rec.alloc(8 * (size_t)RESECT_REC * (size_t)total));
+    HIPCHK(r.rec.alloc((size_t)RESECT_REC * (size_t)total));
     if (total == 0) return LVBA_OK;
     TRY(image_set_undistort(r.set, trk_intr_of(intr), uv, false));
-    DevBuf d_w(s);
-    HIPCHK(d_w.alloc(24 * (size_t)total));
-    HIPCHK(lvba::copy_h2d(d_w.p, world, 24 * (size_t)total));
-    resect_pack_kernel<<<grid_for(total, 256), 256, 0, s>>>(total, r.set.d_xy, d_w.as<double>(), r.rec.as<double>());
+    DevArr<double> d_w(s);
+    HIPCHK(d_w.alloc(3 * (size_t)total)); HIPCHK(d_w.upload(world, 3 * (size_t)total));
+    resect_pack_kernel<<<grid_for(total, 256), 256, 0, s>>>(total, r.set.d_xy, d_w, r.rec);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s)); // the world points go with this scope
     return LVBA_OK;
@@ -284,12 +283,12 @@ int32_t make_records(hipStream_t s, int device, int32_t n_jobs, const int64_t *c
 // The hypotheses of every job with enough correspondences (ransac_run_hypotheses).  diag_pose [H][12], diag_count: null, or the
 // diagnostic call's outputs.
 int32_t run_hypotheses(hipStream_t s, std::vector<ResectTask> &tasks, const lvba_resect_opts &o, const double *intr, const double *d_rec,
-                       DevBuf &d_tasks, DevBuf &d_blk, double *diag_pose, int32_t *diag_count)
+                       DevArr<ResectTask> &d_tasks, DevArr<ResectBest> &d_blk, double *diag_pose, int32_t *diag_count)
 {
     return ransac_run_hypotheses<12>(s, tasks, o.hypotheses, diag_pose ? RESECT_K : std::max(RESECT_K, o.min_inliers), d_tasks, d_blk,
                                      [&](unsigned grid, const RansacTile *tiles) {
-        resect_hypothesis_kernel<<<grid, RANSAC_HB, 0, s>>>(d_tasks.as<ResectTask>(), tiles, d_rec, o.seed, o.hypotheses, intr[0], intr[1],
-                                                            o.max_error_px, d_blk.as<ResectBest>(), diag_pose, diag_count);
+        resect_hypothesis_kernel<<<grid, RANSAC_HB, 0, s>>>(d_tasks, tiles, d_rec, o.seed, o.hypotheses, intr[0], intr[1],
+                                                            o.max_error_px, d_blk, diag_pose, diag_count);
     });
 }
 
@@ -339,21 +338,22 @@ extern "C" int32_t lvba_resect_images(int32_t device, int32_t n_jobs, const int3
     const int nj = n_jobs;
     Records recs(s);
     TRY(make_records(s, device, n_jobs, corr_off, uv, world, intr, recs));
-    const double *d_rec = recs.rec.as<double>();
-    DevBuf d_tasks(s), d_blk(s), d_res(s), d_pose(s), d_int(s), d_real(s);
+    const double *d_rec = recs.rec;
+    DevArr<ResectTask> d_tasks(s); DevArr<ResectBest> d_blk(s), d_res(s); DevArr<double> d_pose(s); DevArr<int32_t> d_int(s);
+    DevArr<double> d_real(s);
     TRY(run_hypotheses(s, tasks, o, intr, d_rec, d_tasks, d_blk, nullptr, nullptr));
-    HIPCHK(d_res.alloc(sizeof(ResectBest) * (size_t)nj)); HIPCHK(d_pose.alloc(96 * (size_t)nj)); HIPCHK(d_int.alloc(12 * (size_t)nj));
-    HIPCHK(d_real.alloc(8 * 37 * (size_t)nj));
-    double *d_R = d_pose.as<double>(), *d_t = d_R + 9 * (size_t)nj;
-    double *d_info = d_real.as<double>(), *d_rmse = d_info + 36 * (size_t)nj;
-    int32_t *d_status = d_int.as<int32_t>(), *d_cnt = d_status + nj, *d_h = d_cnt + nj;
-    ransac_pick_kernel<<<grid_for(nj, 256), 256, 0, s>>>(nj, d_tasks.as<ResectTask>(), d_blk.as<ResectBest>(), d_res.as<ResectBest>());
+    HIPCHK(d_res.alloc((size_t)nj)); HIPCHK(d_pose.alloc(12 * (size_t)nj)); HIPCHK(d_int.alloc(3 * (size_t)nj));
+    HIPCHK(d_real.alloc(37 * (size_t)nj));
+    double *d_R = d_pose, *d_t = d_R + 9 * (size_t)nj;
+    double *d_info = d_real, *d_rmse = d_info + 36 * (size_t)nj;
+    int32_t *d_status = d_int, *d_cnt = d_status + nj, *d_h = d_cnt + nj;
+    ransac_pick_kernel<12, ResectTask><<<grid_for(nj, 256), 256, 0, s>>>(nj, d_tasks, d_blk, d_res);
     HIPCHK(hipGetLastError());
-    resect_refine_kernel<<<(unsigned)nj, REFINE_BLOCK, 0, s>>>(d_tasks.as<ResectTask>(), d_rec, intr[0], intr[1], o.max_error_px, o.refine_rounds,
-                                                              o.min_inliers, d_res.as<ResectBest>(), d_R, d_t, d_status, d_cnt, d_h, d_rmse, d_info);
+    resect_refine_kernel<<<(unsigned)nj, REFINE_BLOCK, 0, s>>>(d_tasks, d_rec, intr[0], intr[1], o.max_error_px, o.refine_rounds,
+                                                              o.min_inliers, d_res, d_R, d_t, d_status, d_cnt, d_h, d_rmse, d_info);
     HIPCHK(hipGetLastError());
-    TRY(ransac_inlier_lists(s, total, nj, d_tasks.as<ResectTask>(), d_status, ResectInlier{d_rec, d_R, d_t, intr[0], intr[1], o.max_error_px},
-                            ResectEmit{d_tasks.as<ResectTask>(), nj}, capacity, inlier_off, inliers));
+    TRY(ransac_inlier_lists<ResectTask>(s, total, nj, d_tasks, d_status, ResectInlier{d_rec, d_R, d_t, intr[0], intr[1], o.max_error_px},
+                            ResectEmit{d_tasks, nj}, capacity, inlier_off, inliers));
     HIPCHK(lvba::copy_d2h(Rcw, d_R, 72 * (size_t)nj));
     HIPCHK(lvba::copy_d2h(tcw, d_t, 24 * (size_t)nj));
     HIPCHK(lvba::copy_d2h(status, d_status, 4 * (size_t)nj));
@@ -390,13 +390,13 @@ extern "C" int32_t lvba_resect_hypotheses(int32_t device, int32_t id, int64_t n_
     std::vector<ResectTask> tasks(1);
     tasks[0] = ResectTask{};
     tasks[0].span.m = (int32_t)n_corr; tasks[0].id = id;
-    DevBuf d_tasks(sg.s), d_blk(sg.s), d_pose(sg.s), d_c(sg.s);
-    HIPCHK(d_pose.alloc(96 * H)); HIPCHK(d_c.alloc(4 * H));
-    TRY(run_hypotheses(sg.s, tasks, o, intr, recs.rec.as<double>(), d_tasks, d_blk, d_pose.as<double>(), d_c.as<int32_t>()));
+    DevArr<ResectTask> d_tasks(sg.s); DevArr<ResectBest> d_blk(sg.s); DevArr<double> d_pose(sg.s); DevArr<int32_t> d_c(sg.s);
+    HIPCHK(d_pose.alloc(12 * H)); HIPCHK(d_c.alloc(H));
+    TRY(run_hypotheses(sg.s, tasks, o, intr, recs.rec, d_tasks, d_blk, d_pose, d_c));
     std::vector<double> pose(12 * H);
-    HIPCHK(lvba::copy_d2h(pose.data(), d_pose.p, 96 * H));
+    HIPCHK(d_pose.download(pose.data(), 12 * H));
     for (size_t h = 0; h < H; ++h) { std::copy_n(&pose[12 * h], 9, R + 9 * h); std::copy_n(&pose[12 * h + 9], 3, t + 3 * h); }
-    HIPCHK(lvba::copy_d2h(count, d_c.p, 4 * H));
+    HIPCHK(d_c.download(count, H));
     return LVBA_OK;
 }
 
@@ -417,11 +417,9 @@ extern "C" int32_t lvba_resect_score(int32_t device, int64_t n_corr, const float
     TRY(make_records(sg.s, device, 1, off, uv, world, intr, recs));
     ResectTask task{};
     task.span.m = (int32_t)n_corr;
-    DevBuf d_pose(sg.s);
-    HIPCHK(d_pose.alloc(96));
-    HIPCHK(lvba::copy_h2d(d_pose.p, Rcw, 72));
-    HIPCHK(lvba::copy_h2d(d_pose.as<double>() + 9, tcw, 24));
-    return ransac_score_mask(sg.s, task, ResectInlier{recs.rec.as<double>(), d_pose.as<double>(), d_pose.as<double>() + 9, intr[0], intr[1], max_error_px},
+    DevArr<double> d_pose(sg.s);
+    HIPCHK(d_pose.alloc(12)); HIPCHK(d_pose.upload(Rcw, 9)); HIPCHK(copy_h2d(d_pose + 9, tcw, d_pose.bytes(3)));
+    return ransac_score_mask(sg.s, task, ResectInlier{recs.rec, d_pose, d_pose + 9, intr[0], intr[1], max_error_px},
                              mask);
 }
 
@@ -444,14 +442,13 @@ extern "C" int32_t lvba_resect_lift(lvba_depth_t depth, int32_t n_images, const 
     g.set = ImageSet{depth->device, n_images, std::vector<int64_t>(kp_off, kp_off + n_images + 1)};
     TRY(image_set_undistort(g.set, trk_intr_of(intr), uv, true));
     TRY(image_set_upload(g.set, true, nullptr));
-    DevBuf d_w(sg.s), d_R(sg.s), d_t(sg.s);
-    HIPCHK(d_w.alloc(24 * (size_t)total)); HIPCHK(d_R.alloc(72 * (size_t)n_images)); HIPCHK(d_t.alloc(24 * (size_t)n_images));
-    HIPCHK(lvba::copy_h2d(d_R.p, Rcw, 72 * (size_t)n_images));
-    HIPCHK(lvba::copy_h2d(d_t.p, tcw, 24 * (size_t)n_images));
+    DevArr<double> d_w(sg.s), d_R(sg.s), d_t(sg.s);
+    HIPCHK(d_w.alloc(3 * (size_t)total)); HIPCHK(d_R.alloc(9 * (size_t)n_images)); HIPCHK(d_t.alloc(3 * (size_t)n_images));
+    HIPCHK(d_R.upload(Rcw, 9 * (size_t)n_images)); HIPCHK(d_t.upload(tcw, 3 * (size_t)n_images));
     resect_lift_kernel<<<grid_for(total, 256), 256, 0, sg.s>>>(total, n_images, g.set.d_off, g.set.d_uv, g.set.d_xy, depth->d_depth, depth->width,
-                                                              depth->height, d_R.as<double>(), d_t.as<double>(), d_w.as<double>());
+                                                              depth->height, d_R, d_t, d_w);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(sg.s));
-    HIPCHK(lvba::copy_d2h(world, d_w.p, 24 * (size_t)total));
+    HIPCHK(d_w.download(world, 3 * (size_t)total));
     return LVBA_OK;
 }

@@ -376,7 +376,8 @@ struct SiftChunk {
     int w_in, h_in, ch, C = 0, S;
     std::vector<int> ow, oh;         // octave sizes
     int oct = -1;                    // the octave the buffers hold
-    DevBuf d_img, d_gauss, d_dog, d_tmp, d_flag, d_excl, d_taps, d_cand_idx, d_cand;
+    DevArr<uint8_t> d_img; DevArr<float> d_gauss, d_dog, d_tmp; DevArr<uint32_t> d_flag, d_excl; DevArr<float> d_taps;
+    DevArr<int64_t> d_cand_idx; DevArr<SiftCand> d_cand;
     int radius[SIFT_MAX_INTERVALS + 3];
     int64_t n_cand = 0;
 
@@ -402,22 +403,21 @@ struct SiftChunk {
         C = chunk;
         const size_t n0 = (size_t)npx0() * C;
         HIPCHK(d_img.alloc((size_t)w_in * h_in * ch * C));
-        HIPCHK(d_gauss.alloc(4 * n0 * (S + 3))); HIPCHK(d_dog.alloc(4 * n0 * (S + 2))); HIPCHK(d_tmp.alloc(4 * n0));
-        HIPCHK(d_flag.alloc(4 * (n0 * S + 1))); HIPCHK(d_excl.alloc(4 * (n0 * S + 1)));
+        HIPCHK(d_gauss.alloc(n0 * (S + 3))); HIPCHK(d_dog.alloc(n0 * (S + 2))); HIPCHK(d_tmp.alloc(n0));
+        HIPCHK(d_flag.alloc(n0 * S + 1)); HIPCHK(d_excl.alloc(n0 * S + 1));
         std::vector<float> taps((size_t)TAPS_STRIDE * (S + 3), 0.f);
         for (int l = 0; l <= S + 2; ++l) radius[l] = taps_for(o, l, &taps[(size_t)TAPS_STRIDE * l]);
-        HIPCHK(d_taps.alloc(4 * taps.size()));
-        HIPCHK(lvba::copy_h2d(d_taps.p, taps.data(), 4 * taps.size()));
+        HIPCHK(d_taps.alloc_upload(taps));
         return LVBA_OK;
     }
     dim3 grid(int w, int h, int rows, int n) const { return dim3((unsigned)((w + 63) / 64), (unsigned)((h + rows - 1) / rows), (unsigned)n); }
     int32_t blur(const float *src, int64_t src_stride, float *dst, int64_t dst_stride, int w, int h, int level, int n)
     {
-        const float *taps = d_taps.as<float>() + (size_t)TAPS_STRIDE * level;
-        sift_blur_rows_kernel<<<grid(w, h, 4, n), dim3(64, 4), 0, s>>>(src, src_stride, d_tmp.as<float>(), (int64_t)w * h, w, h, taps,
+        const float *taps = d_taps + (size_t)TAPS_STRIDE * level;
+        sift_blur_rows_kernel<<<grid(w, h, 4, n), dim3(64, 4), 0, s>>>(src, src_stride, d_tmp, (int64_t)w * h, w, h, taps,
                                                                       radius[level]);
         HIPCHK(hipGetLastError());
-        sift_blur_cols_kernel<<<grid(w, h, SIFT_TILE_ROWS, n), dim3(64, 4), 0, s>>>(d_tmp.as<float>(), (int64_t)w * h, dst, dst_stride, w, h,
+        sift_blur_cols_kernel<<<grid(w, h, SIFT_TILE_ROWS, n), dim3(64, 4), 0, s>>>(d_tmp, (int64_t)w * h, dst, dst_stride, w, h,
                                                                                    taps, radius[level]);
         HIPCHK(hipGetLastError());
         return LVBA_OK;
@@ -426,13 +426,13 @@ struct SiftChunk {
     int32_t begin(const uint8_t *images, int n)
     {
         C = n;
-        HIPCHK(lvba::copy_h2d(d_img.p, images, (size_t)w_in * h_in * ch * n));
+        HIPCHK(d_img.upload(images, (size_t)w_in * h_in * ch * n));
         const int w = ow[0], h = oh[0];
         const int64_t npx = (int64_t)w * h;
-        sift_base_kernel<<<grid(w, h, 4, n), dim3(64, 4), 0, s>>>(d_img.as<uint8_t>(), w_in, h_in, ch, o.first_octave < 0 ? 1 : 0,
-                                                                 d_dog.as<float>());
+        sift_base_kernel<<<grid(w, h, 4, n), dim3(64, 4), 0, s>>>(d_img, w_in, h_in, ch, o.first_octave < 0 ? 1 : 0,
+                                                                 d_dog);
         HIPCHK(hipGetLastError());
-        TRY(blur(d_dog.as<float>(), npx, d_gauss.as<float>(), (S + 3) * npx, w, h, 0, n));
+        TRY(blur(d_dog, npx, d_gauss, (S + 3) * npx, w, h, 0, n));
         oct = 0;
         return levels();
     }
@@ -442,17 +442,17 @@ struct SiftChunk {
         const int w = ow[oct], h = oh[oct];
         const int64_t npx = (int64_t)w * h, stride = (S + 3) * npx;
         for (int l = 1; l <= S + 2; ++l)
-            TRY(blur(d_gauss.as<float>() + (l - 1) * npx, stride, d_gauss.as<float>() + l * npx, stride, w, h, l, C));
+            TRY(blur(d_gauss + (l - 1) * npx, stride, d_gauss + l * npx, stride, w, h, l, C));
         return LVBA_OK;
     }
     int32_t next_octave()
     {
         const int w = ow[oct], h = oh[oct], w2 = ow[oct + 1], h2 = oh[oct + 1];
         const int64_t npx = (int64_t)w * h, npx2 = (int64_t)w2 * h2;
-        sift_decimate_kernel<<<grid(w2, h2, 4, C), dim3(64, 4), 0, s>>>(d_gauss.as<float>() + S * npx, (S + 3) * npx, w, d_tmp.as<float>(), npx2,
+        sift_decimate_kernel<<<grid(w2, h2, 4, C), dim3(64, 4), 0, s>>>(d_gauss + S * npx, (S + 3) * npx, w, d_tmp, npx2,
                                                                        w2, h2);
         HIPCHK(hipGetLastError());
-        sift_copy_kernel<<<dim3(grid_for(npx2, 256), 1, (unsigned)C), 256, 0, s>>>(d_tmp.as<float>(), npx2, d_gauss.as<float>(), (S + 3) * npx2,
+        sift_copy_kernel<<<dim3(grid_for(npx2, 256), 1, (unsigned)C), 256, 0, s>>>(d_tmp, npx2, d_gauss, (S + 3) * npx2,
                                                                                   npx2);
         HIPCHK(hipGetLastError());
         ++oct;
@@ -463,18 +463,17 @@ struct SiftChunk {
     {
         const int w = ow[oct], h = oh[oct];
         const int64_t n = (int64_t)w * h * S * C;
-        sift_detect_kernel<<<grid(w, h, 4, C), dim3(64, 4), 0, s>>>(d_gauss.as<float>(), d_dog.as<float>(), d_flag.as<uint32_t>(), w, h, S,
+        sift_detect_kernel<<<grid(w, h, 4, C), dim3(64, 4), 0, s>>>(d_gauss, d_dog, d_flag, w, h, S,
                                                                    (0.5 * o.dog_threshold) / (double)S);
         HIPCHK(hipGetLastError());
-        TRY(count_flags(s, d_flag.as<uint32_t>(), d_excl.as<uint32_t>(), (size_t)n, &n_cand));
+        TRY(count_flags(s, d_flag, d_excl, (size_t)n, &n_cand));
         if (n_cand == 0) return LVBA_OK;
-        if (d_cand_idx.p) { HIPCHK(hipStreamSynchronize(s)); DevicePool::get().free(d_cand_idx.release()); }
-        if (d_cand.p) { HIPCHK(hipStreamSynchronize(s)); DevicePool::get().free(d_cand.release()); }
-        HIPCHK(d_cand_idx.alloc(8 * (size_t)n_cand)); HIPCHK(d_cand.alloc(sizeof(SiftCand) * (size_t)n_cand));
-        sift_gather_kernel<<<grid_for(n, 256), 256, 0, s>>>(n, d_flag.as<uint32_t>(), d_excl.as<uint32_t>(), d_cand_idx.as<int64_t>());
+        d_cand_idx.reset(); d_cand.reset(); // (each drains the stream before its block goes back)
+        HIPCHK(d_cand_idx.alloc((size_t)n_cand)); HIPCHK(d_cand.alloc((size_t)n_cand));
+        sift_gather_kernel<<<grid_for(n, 256), 256, 0, s>>>(n, d_flag, d_excl, d_cand_idx);
         HIPCHK(hipGetLastError());
-        sift_refine_kernel<<<grid_for(n_cand, 256), 256, 0, s>>>(n_cand, d_cand_idx.as<int64_t>(), d_dog.as<float>(), w, h, S, o.sigma0,
-                                                               o.dog_threshold, o.edge_threshold, d_cand.as<SiftCand>());
+        sift_refine_kernel<<<grid_for(n_cand, 256), 256, 0, s>>>(n_cand, d_cand_idx, d_dog, w, h, S, o.sigma0,
+                                                               o.dog_threshold, o.edge_threshold, d_cand);
         HIPCHK(hipGetLastError());
         return LVBA_OK;
     }
@@ -485,9 +484,9 @@ struct SiftChunk {
         if (n_cand == 0) return LVBA_OK;
         const int w = ow[oct], h = oh[oct];
         // d_flag / d_excl are free again: the orientation counts and their scan
-        uint32_t *d_n = d_flag.as<uint32_t>(), *d_first = d_excl.as<uint32_t>();
+        uint32_t *d_n = d_flag, *d_first = d_excl;
         const double t0 = now_ms();
-        sift_orient_kernel<<<(unsigned)n_cand, 64, 0, s>>>(n_cand, d_cand.as<SiftCand>(), d_gauss.as<float>(), w, h, S, o.orientation_window,
+        sift_orient_kernel<<<(unsigned)n_cand, 64, 0, s>>>(n_cand, d_cand, d_gauss, w, h, S, o.orientation_window,
                                                          o.max_orientations, d_n);
         HIPCHK(hipGetLastError());
         int64_t n_feat = 0;
@@ -495,18 +494,17 @@ struct SiftChunk {
         const double t1 = now_ms();
         g_sift_ms[2] += t1 - t0;
         if (n_feat == 0) return LVBA_OK;
-        DevBuf d_kp(s), d_desc(s), d_im(s);
-        HIPCHK(d_kp.alloc(16 * (size_t)n_feat)); HIPCHK(d_desc.alloc((size_t)SIFT_DESC * n_feat)); HIPCHK(d_im.alloc(4 * (size_t)n_feat));
-        sift_describe_kernel<<<(unsigned)n_cand, 64, 0, s>>>(n_cand, d_cand.as<SiftCand>(), d_first, d_gauss.as<float>(), w, h, S, scale(),
-                                                           d_kp.as<float>(), d_desc.as<uint8_t>(), d_im.as<int32_t>());
+        DevArr<float> d_kp(s); DevArr<uint8_t> d_desc(s); DevArr<int32_t> d_im(s);
+        HIPCHK(d_kp.alloc(4 * (size_t)n_feat)); HIPCHK(d_desc.alloc((size_t)SIFT_DESC * n_feat)); HIPCHK(d_im.alloc((size_t)n_feat));
+        sift_describe_kernel<<<(unsigned)n_cand, 64, 0, s>>>(n_cand, d_cand, d_first, d_gauss, w, h, S, scale(),
+                                                           d_kp, d_desc, d_im);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(s));
         std::vector<float> kp(4 * (size_t)n_feat);
         std::vector<uint8_t> desc((size_t)SIFT_DESC * n_feat);
         std::vector<int32_t> im((size_t)n_feat);
-        HIPCHK(lvba::copy_d2h(kp.data(), d_kp.p, 16 * (size_t)n_feat));
-        HIPCHK(lvba::copy_d2h(desc.data(), d_desc.p, desc.size()));
-        HIPCHK(lvba::copy_d2h(im.data(), d_im.p, 4 * (size_t)n_feat));
+        HIPCHK(d_kp.download(kp.data(), 4 * (size_t)n_feat)); HIPCHK(d_desc.download(desc.data(), desc.size()));
+        HIPCHK(d_im.download(im.data(), (size_t)n_feat));
         for (int64_t f = 0; f < n_feat; ++f) {
             Feature ft;
             std::copy_n(&kp[4 * (size_t)f], 4, ft.kp);
@@ -654,8 +652,7 @@ extern "C" int32_t lvba_sift_pyramid(int32_t device, int32_t width, int32_t heig
     TRY(ck.detect());
     HIPCHK(hipStreamSynchronize(sg.s));
     const size_t npx = (size_t)ck.ow[(size_t)k] * ck.oh[(size_t)k];
-    HIPCHK(lvba::copy_d2h(gauss, ck.d_gauss.p, 4 * npx * (o.n_intervals + 3)));
-    HIPCHK(lvba::copy_d2h(dog, ck.d_dog.p, 4 * npx * (o.n_intervals + 2)));
+    HIPCHK(ck.d_gauss.download(gauss, npx * (o.n_intervals + 3))); HIPCHK(ck.d_dog.download(dog, npx * (o.n_intervals + 2)));
     return LVBA_OK;
 }
 
@@ -679,7 +676,7 @@ extern "C" int32_t lvba_sift_candidates(int32_t device, int32_t width, int32_t h
         if (ck.n_cand > 0) {
             std::vector<SiftCand> c((size_t)ck.n_cand);
             HIPCHK(hipStreamSynchronize(sg.s));
-            HIPCHK(lvba::copy_d2h(c.data(), ck.d_cand.p, sizeof(SiftCand) * c.size()));
+            HIPCHK(ck.d_cand.download(c.data(), c.size()));
             const double sc = ck.scale();
             for (const SiftCand &q : c) {
                 if (!q.ok) continue;

@@ -261,7 +261,6 @@ __global__ __launch_bounds__(TG_BLOCK) void trackgraph_bfs_kernel(int64_t n, con
 
 inline unsigned bits_for(uint64_t largest) { unsigned b = 1; while (b < 64 && (largest >> b)) ++b; return b; }
 
-hipError_t keep_alloc(void **p, size_t bytes) { return DevicePool::get().alloc(p, bytes ? bytes : 8); }
 
 int32_t build_graph(lvba_trackgraph_s *g, int64_t n_pairs, const int32_t *pairs, const int64_t *match_off, const int32_t *matches)
 {
@@ -279,22 +278,19 @@ int32_t build_graph(lvba_trackgraph_s *g, int64_t n_pairs, const int32_t *pairs,
     const size_t H2 = 2 * (size_t)n_matches;
     const uint32_t no_node = (uint32_t)N;
     const unsigned node_bits = bits_for((uint64_t)N);
-    DevBuf d_pairs(s), d_moff(s), d_first(s), d_matches(s), d_src(s), d_dst(s), d_key(s);
-    HIPCHK(d_pairs.alloc(8 * (size_t)n_pairs)); HIPCHK(d_moff.alloc(8 * ((size_t)n_pairs + 1))); HIPCHK(d_first.alloc(8 * (size_t)n_pairs));
-    HIPCHK(d_matches.alloc(8 * (size_t)n_matches));
-    HIPCHK(d_src.alloc(4 * H2)); HIPCHK(d_dst.alloc(4 * H2)); HIPCHK(d_key.alloc(4 * H2));
-    HIPCHK(keep_alloc((void **)&g->d_adj, 4 * H2));
-    HIPCHK(lvba::copy_h2d(d_pairs.p, pairs, 8 * (size_t)n_pairs));
-    HIPCHK(lvba::copy_h2d(d_moff.p, match_off, 8 * ((size_t)n_pairs + 1)));
-    HIPCHK(lvba::copy_h2d(d_first.p, first_seq.data(), 8 * (size_t)n_pairs));
-    HIPCHK(lvba::copy_h2d(d_matches.p, matches, 8 * (size_t)n_matches));
-    trackgraph_edge_kernel<<<grid_for(n_matches, TG_BLOCK), TG_BLOCK, 0, s>>>(n_matches, n_pairs, d_pairs.as<int32_t>(), d_moff.as<int64_t>(),
-                                                                            d_first.as<int64_t>(), d_matches.as<int32_t>(), g->kp.d_off, no_node,
-                                                                            d_src.as<uint32_t>(), d_dst.as<uint32_t>());
+    DevArr<int32_t> d_pairs(s); DevArr<int64_t> d_moff(s), d_first(s); DevArr<int32_t> d_matches(s);
+    DevArr<uint32_t> d_src(s), d_dst(s), d_key(s);
+    HIPCHK(d_pairs.alloc(2 * (size_t)n_pairs)); HIPCHK(d_moff.alloc((size_t)n_pairs + 1)); HIPCHK(d_first.alloc((size_t)n_pairs));
+    HIPCHK(d_matches.alloc(2 * (size_t)n_matches)); HIPCHK(d_src.alloc(H2)); HIPCHK(d_dst.alloc(H2)); HIPCHK(d_key.alloc(H2));
+    HIPCHK(pool_alloc(&g->d_adj, H2)); HIPCHK(d_pairs.upload(pairs, 2 * (size_t)n_pairs));
+    HIPCHK(d_moff.upload(match_off, (size_t)n_pairs + 1)); HIPCHK(d_first.upload(first_seq.data(), (size_t)n_pairs));
+    HIPCHK(d_matches.upload(matches, 2 * (size_t)n_matches));
+    trackgraph_edge_kernel<<<grid_for(n_matches, TG_BLOCK), TG_BLOCK, 0, s>>>(n_matches, n_pairs, d_pairs, d_moff,
+                                                                            d_first, d_matches, g->kp.d_off, no_node,
+                                                                            d_src, d_dst);
     HIPCHK(hipGetLastError());
-    TRY(sort_pairs<uint32_t>(s, d_src.as<uint32_t>(), d_key.as<uint32_t>(), d_dst.as<uint32_t>(), g->d_adj, H2, node_bits));
-    HIPCHK(keep_alloc((void **)&g->d_adj_off, 4 * ((size_t)N + 1)));
-    trackgraph_offsets_kernel<<<grid_for(N + 1, TG_BLOCK), TG_BLOCK, 0, s>>>(N, d_key.as<uint32_t>(), (uint32_t)H2, g->d_adj_off);
+    TRY(sort_pairs<uint32_t>(s, d_src, d_key, d_dst, g->d_adj, H2, node_bits)); HIPCHK(pool_alloc(&g->d_adj_off, ((size_t)N + 1)));
+    trackgraph_offsets_kernel<<<grid_for(N + 1, TG_BLOCK), TG_BLOCK, 0, s>>>(N, d_key, (uint32_t)H2, g->d_adj_off);
     HIPCHK(hipGetLastError());
     uint32_t n_half = 0;
     HIPCHK(hipMemcpyAsync(&n_half, g->d_adj_off + N, 4, hipMemcpyDeviceToHost, s));
@@ -304,89 +300,87 @@ int32_t build_graph(lvba_trackgraph_s *g, int64_t n_pairs, const int32_t *pairs,
     if (n_half == 0) return LVBA_OK;
 
     // ---- labels
-    DevBuf d_label(s), d_changed(s);
-    HIPCHK(d_label.alloc(4 * (size_t)N)); HIPCHK(d_changed.alloc(4));
-    trackgraph_iota_kernel<<<grid_for(N, TG_BLOCK), TG_BLOCK, 0, s>>>(N, d_label.as<uint32_t>());
+    DevArr<uint32_t> d_label(s), d_changed(s);
+    HIPCHK(d_label.alloc((size_t)N)); HIPCHK(d_changed.alloc(1));
+    trackgraph_iota_kernel<<<grid_for(N, TG_BLOCK), TG_BLOCK, 0, s>>>(N, d_label);
     HIPCHK(hipGetLastError());
     int rounds = 0;
     for (uint32_t changed = 1; changed;) {
         if (rounds == TG_MAX_ROUNDS) return lvba_fail(LVBA_ERR_STATE, "the component labels did not settle in %d rounds", TG_MAX_ROUNDS);
         ++rounds;
-        HIPCHK(hipMemsetAsync(d_changed.p, 0, 4, s));
-        trackgraph_hook_kernel<<<grid_for(n_half, TG_BLOCK), TG_BLOCK, 0, s>>>(n_half, d_key.as<uint32_t>(), g->d_adj, d_label.as<uint32_t>(),
-                                                                             d_changed.as<uint32_t>());
+        HIPCHK(d_changed.zero_async(1));
+        trackgraph_hook_kernel<<<grid_for(n_half, TG_BLOCK), TG_BLOCK, 0, s>>>(n_half, d_key, g->d_adj, d_label,
+                                                                             d_changed);
         HIPCHK(hipGetLastError());
-        trackgraph_jump_kernel<<<grid_for(N, TG_BLOCK), TG_BLOCK, 0, s>>>(N, d_label.as<uint32_t>(), d_changed.as<uint32_t>());
+        trackgraph_jump_kernel<<<grid_for(N, TG_BLOCK), TG_BLOCK, 0, s>>>(N, d_label, d_changed);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(&changed, d_changed.p, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&changed, d_changed, d_changed.bytes(1), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
     }
     info.cc_rounds = rounds;
 
     // ---- the nodes with an edge, by (label, node)
-    DevBuf d_flag(s), d_excl(s), d_node(s), d_node_label(s), d_lab(s);
-    HIPCHK(d_flag.alloc(4 * ((size_t)N + 1))); HIPCHK(d_excl.alloc(4 * ((size_t)N + 1)));
-    trackgraph_degree_kernel<<<grid_for(N + 1, TG_BLOCK), TG_BLOCK, 0, s>>>(N, g->d_adj_off, d_flag.as<uint32_t>());
+    DevArr<uint32_t> d_flag(s), d_excl(s), d_node(s), d_node_label(s), d_lab(s);
+    HIPCHK(d_flag.alloc((size_t)N + 1)); HIPCHK(d_excl.alloc((size_t)N + 1));
+    trackgraph_degree_kernel<<<grid_for(N + 1, TG_BLOCK), TG_BLOCK, 0, s>>>(N, g->d_adj_off, d_flag);
     HIPCHK(hipGetLastError());
     int64_t n_nodes = 0;
-    TRY(count_flags(s, d_flag.as<uint32_t>(), d_excl.as<uint32_t>(), (size_t)N + 1, &n_nodes));
+    TRY(count_flags(s, d_flag, d_excl, (size_t)N + 1, &n_nodes));
     info.n_nodes = n_nodes;
-    HIPCHK(d_node.alloc(4 * (size_t)n_nodes)); HIPCHK(d_node_label.alloc(4 * (size_t)n_nodes)); HIPCHK(d_lab.alloc(4 * (size_t)n_nodes));
-    HIPCHK(keep_alloc((void **)&g->d_members, 4 * (size_t)n_nodes));
-    trackgraph_nodes_kernel<<<grid_for(N, TG_BLOCK), TG_BLOCK, 0, s>>>(N, d_flag.as<uint32_t>(), d_excl.as<uint32_t>(), d_label.as<uint32_t>(),
-                                                                     d_node.as<uint32_t>(), d_node_label.as<uint32_t>());
+    HIPCHK(d_node.alloc((size_t)n_nodes)); HIPCHK(d_node_label.alloc((size_t)n_nodes)); HIPCHK(d_lab.alloc((size_t)n_nodes));
+    HIPCHK(pool_alloc(&g->d_members, (size_t)n_nodes));
+    trackgraph_nodes_kernel<<<grid_for(N, TG_BLOCK), TG_BLOCK, 0, s>>>(N, d_flag, d_excl, d_label,
+                                                                     d_node, d_node_label);
     HIPCHK(hipGetLastError());
-    TRY(sort_pairs<uint32_t>(s, d_node_label.as<uint32_t>(), d_lab.as<uint32_t>(), d_node.as<uint32_t>(), g->d_members, (size_t)n_nodes, node_bits));
+    TRY(sort_pairs<uint32_t>(s, d_node_label, d_lab, d_node, g->d_members, (size_t)n_nodes, node_bits));
 
     // ---- runs, sizes, distinct images, the two checks, the table
-    DevBuf d_img(s), d_head(s), d_change(s), d_run_of(s), d_change_x(s), d_run_first(s);
-    HIPCHK(d_img.alloc(4 * (size_t)n_nodes));
-    HIPCHK(d_head.alloc(4 * ((size_t)n_nodes + 1))); HIPCHK(d_change.alloc(4 * ((size_t)n_nodes + 1)));
-    HIPCHK(d_run_of.alloc(4 * ((size_t)n_nodes + 1))); HIPCHK(d_change_x.alloc(4 * ((size_t)n_nodes + 1)));
-    trackgraph_image_kernel<<<grid_for(n_nodes, TG_BLOCK), TG_BLOCK, 0, s>>>(n_nodes, g->d_members, g->kp.d_off, g->kp.n_images, d_img.as<int32_t>());
+    DevArr<int32_t> d_img(s); DevArr<uint32_t> d_head(s), d_change(s), d_run_of(s), d_change_x(s), d_run_first(s);
+    HIPCHK(d_img.alloc((size_t)n_nodes)); HIPCHK(d_head.alloc((size_t)n_nodes + 1)); HIPCHK(d_change.alloc((size_t)n_nodes + 1));
+    HIPCHK(d_run_of.alloc((size_t)n_nodes + 1)); HIPCHK(d_change_x.alloc((size_t)n_nodes + 1));
+    trackgraph_image_kernel<<<grid_for(n_nodes, TG_BLOCK), TG_BLOCK, 0, s>>>(n_nodes, g->d_members, g->kp.d_off, g->kp.n_images, d_img);
     HIPCHK(hipGetLastError());
-    trackgraph_runs_kernel<<<grid_for(n_nodes + 1, TG_BLOCK), TG_BLOCK, 0, s>>>(n_nodes, d_lab.as<uint32_t>(), d_img.as<int32_t>(),
-                                                                              d_head.as<uint32_t>(), d_change.as<uint32_t>());
+    trackgraph_runs_kernel<<<grid_for(n_nodes + 1, TG_BLOCK), TG_BLOCK, 0, s>>>(n_nodes, d_lab, d_img,
+                                                                              d_head, d_change);
     HIPCHK(hipGetLastError());
-    TRY(scan_excl<uint32_t>(s, d_head.as<uint32_t>(), d_run_of.as<uint32_t>(), (size_t)n_nodes + 1));
-    TRY(scan_excl<uint32_t>(s, d_change.as<uint32_t>(), d_change_x.as<uint32_t>(), (size_t)n_nodes + 1));
+    TRY(scan_excl<uint32_t>(s, d_head, d_run_of, (size_t)n_nodes + 1));
+    TRY(scan_excl<uint32_t>(s, d_change, d_change_x, (size_t)n_nodes + 1));
     uint32_t n_all = 0;
-    HIPCHK(lvba::copy_d2h(&n_all, d_run_of.as<uint32_t>() + n_nodes, 4));
+    HIPCHK(copy_d2h(&n_all, d_run_of + n_nodes, d_run_of.bytes(1)));
     info.n_components_all = n_all;
-    HIPCHK(d_run_first.alloc(4 * ((size_t)n_all + 1)));
-    trackgraph_heads_kernel<<<grid_for(n_nodes + 1, TG_BLOCK), TG_BLOCK, 0, s>>>(n_nodes, d_head.as<uint32_t>(), d_run_of.as<uint32_t>(),
-                                                                               d_run_first.as<uint32_t>());
+    HIPCHK(d_run_first.alloc((size_t)n_all + 1));
+    trackgraph_heads_kernel<<<grid_for(n_nodes + 1, TG_BLOCK), TG_BLOCK, 0, s>>>(n_nodes, d_head, d_run_of,
+                                                                               d_run_first);
     HIPCHK(hipGetLastError());
-    DevBuf d_keep(s), d_kept_size(s), d_comp_of(s), d_obs_x(s), d_comp_images(s);
-    HIPCHK(d_keep.alloc(4 * ((size_t)n_all + 1))); HIPCHK(d_kept_size.alloc(4 * ((size_t)n_all + 1)));
-    HIPCHK(d_comp_of.alloc(4 * ((size_t)n_all + 1))); HIPCHK(d_obs_x.alloc(4 * ((size_t)n_all + 1)));
-    trackgraph_check_kernel<<<grid_for((int64_t)n_all + 1, TG_BLOCK), TG_BLOCK, 0, s>>>(n_all, d_run_first.as<uint32_t>(), d_change_x.as<uint32_t>(),
-                                                                                      g->obser_thr, d_keep.as<uint32_t>(), d_kept_size.as<uint32_t>());
+    DevArr<uint32_t> d_keep(s), d_kept_size(s), d_comp_of(s), d_obs_x(s), d_comp_images(s);
+    HIPCHK(d_keep.alloc((size_t)n_all + 1)); HIPCHK(d_kept_size.alloc((size_t)n_all + 1));
+    HIPCHK(d_comp_of.alloc((size_t)n_all + 1)); HIPCHK(d_obs_x.alloc((size_t)n_all + 1));
+    trackgraph_check_kernel<<<grid_for((int64_t)n_all + 1, TG_BLOCK), TG_BLOCK, 0, s>>>(n_all, d_run_first, d_change_x,
+                                                                                      g->obser_thr, d_keep, d_kept_size);
     HIPCHK(hipGetLastError());
-    TRY(scan_excl<uint32_t>(s, d_keep.as<uint32_t>(), d_comp_of.as<uint32_t>(), (size_t)n_all + 1));
-    TRY(scan_excl<uint32_t>(s, d_kept_size.as<uint32_t>(), d_obs_x.as<uint32_t>(), (size_t)n_all + 1));
+    TRY(scan_excl<uint32_t>(s, d_keep, d_comp_of, (size_t)n_all + 1));
+    TRY(scan_excl<uint32_t>(s, d_kept_size, d_obs_x, (size_t)n_all + 1));
     uint32_t n_comp = 0;
-    HIPCHK(lvba::copy_d2h(&n_comp, d_comp_of.as<uint32_t>() + n_all, 4));
+    HIPCHK(copy_d2h(&n_comp, d_comp_of + n_all, d_comp_of.bytes(1)));
     info.n_components = n_comp;
-    HIPCHK(keep_alloc((void **)&g->d_comp_first, 4 * (size_t)n_comp)); HIPCHK(keep_alloc((void **)&g->d_comp_size, 4 * (size_t)n_comp));
-    HIPCHK(keep_alloc((void **)&g->d_comp_obs, 4 * ((size_t)n_comp + 1)));
-    HIPCHK(d_comp_images.alloc(4 * (size_t)n_comp));
-    trackgraph_table_kernel<<<grid_for((int64_t)n_all + 1, TG_BLOCK), TG_BLOCK, 0, s>>>(n_all, d_run_first.as<uint32_t>(), d_change_x.as<uint32_t>(),
-                                                                                      d_keep.as<uint32_t>(), d_comp_of.as<uint32_t>(), d_obs_x.as<uint32_t>(),
-                                                                                      g->d_comp_first, g->d_comp_size, d_comp_images.as<uint32_t>(),
+    HIPCHK(pool_alloc(&g->d_comp_first, (size_t)n_comp)); HIPCHK(pool_alloc(&g->d_comp_size, (size_t)n_comp));
+    HIPCHK(pool_alloc(&g->d_comp_obs, ((size_t)n_comp + 1))); HIPCHK(d_comp_images.alloc((size_t)n_comp));
+    trackgraph_table_kernel<<<grid_for((int64_t)n_all + 1, TG_BLOCK), TG_BLOCK, 0, s>>>(n_all, d_run_first, d_change_x,
+                                                                                      d_keep, d_comp_of, d_obs_x,
+                                                                                      g->d_comp_first, g->d_comp_size, d_comp_images,
                                                                                       g->d_comp_obs);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
     g->comp_size.resize(n_comp); g->comp_images.resize(n_comp);
     if (n_comp > 0) {
         HIPCHK(lvba::copy_d2h(g->comp_size.data(), g->d_comp_size, 4 * (size_t)n_comp));
-        HIPCHK(lvba::copy_d2h(g->comp_images.data(), d_comp_images.p, 4 * (size_t)n_comp));
+        HIPCHK(d_comp_images.download(g->comp_images.data(), (size_t)n_comp));
     }
     for (uint32_t sz : g->comp_size) {
         info.n_observations += sz;
         info.largest_component = std::max<int64_t>(info.largest_component, sz);
     }
-    HIPCHK(keep_alloc((void **)&g->d_stamp, 4 * (size_t)N));
+    HIPCHK(pool_alloc(&g->d_stamp, (size_t)N));
     HIPCHK(hipMemsetAsync(g->d_stamp, 0, 4 * (size_t)N, s));
     HIPCHK(hipStreamSynchronize(s));
     return LVBA_OK;
@@ -447,14 +441,13 @@ extern "C" int32_t lvba_trackgraph_components(lvba_trackgraph_t g, int64_t *comp
         HIPCHK(hipSetDevice(g->kp.device));
         ScopedStream sg;
         HIPCHK(sg.acquire());
-        DevBuf d_img(sg.s), d_kp(sg.s);
-        HIPCHK(d_img.alloc(4 * (size_t)n_obs)); HIPCHK(d_kp.alloc(4 * (size_t)n_obs));
+        DevArr<int32_t> d_img(sg.s), d_kp(sg.s);
+        HIPCHK(d_img.alloc((size_t)n_obs)); HIPCHK(d_kp.alloc((size_t)n_obs));
         trackgraph_members_kernel<<<grid_for(n_obs, TG_BLOCK), TG_BLOCK, 0, sg.s>>>(n_obs, (uint32_t)n_comp, g->d_comp_obs, g->d_comp_first, g->d_members,
-                                                                                 g->kp.d_off, g->kp.n_images, d_img.as<int32_t>(), d_kp.as<int32_t>());
+                                                                                 g->kp.d_off, g->kp.n_images, d_img, d_kp);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(sg.s));
-        HIPCHK(lvba::copy_d2h(mem_img, d_img.p, 4 * (size_t)n_obs));
-        HIPCHK(lvba::copy_d2h(mem_kp, d_kp.p, 4 * (size_t)n_obs));
+        HIPCHK(d_img.download(mem_img, (size_t)n_obs)); HIPCHK(d_kp.download(mem_kp, (size_t)n_obs));
     }
     comp_off[0] = 0;
     for (int64_t c = 0; c < n_comp; ++c) {
@@ -492,25 +485,23 @@ extern "C" int32_t lvba_trackgraph_orders(lvba_trackgraph_t g, int64_t n, const 
             HIPCHK(hipMemsetAsync(g->d_stamp, 0, 4 * (size_t)g->kp.off.back(), s));
             g->epoch = 1;
         }
-        DevBuf d_sel(s), d_off(s), d_queue(s), d_img(s), d_kp(s), d_uv(s), d_err(s);
-        HIPCHK(d_sel.alloc(4 * (size_t)n)); HIPCHK(d_off.alloc(4 * ((size_t)n + 1))); HIPCHK(d_queue.alloc(4 * total));
-        HIPCHK(d_img.alloc(4 * total)); HIPCHK(d_kp.alloc(4 * total)); HIPCHK(d_err.alloc(4));
-        if (obs_uv) HIPCHK(d_uv.alloc(8 * total));
-        HIPCHK(lvba::copy_h2d(d_sel.p, sel.data(), 4 * (size_t)n));
-        HIPCHK(lvba::copy_h2d(d_off.p, off.data(), 4 * ((size_t)n + 1)));
-        HIPCHK(hipMemsetAsync(d_err.p, 0, 4, s));
+        DevArr<uint32_t> d_sel(s), d_off(s), d_queue(s); DevArr<int32_t> d_img(s), d_kp(s); DevArr<float> d_uv(s);
+        DevArr<uint32_t> d_err(s);
+        HIPCHK(d_sel.alloc((size_t)n)); HIPCHK(d_off.alloc((size_t)n + 1)); HIPCHK(d_queue.alloc(total));
+        HIPCHK(d_img.alloc(total)); HIPCHK(d_kp.alloc(total)); HIPCHK(d_err.alloc(1));
+        if (obs_uv) HIPCHK(d_uv.alloc(2 * total));
+        HIPCHK(d_sel.upload(sel.data(), (size_t)n)); HIPCHK(d_off.upload(off.data(), (size_t)n + 1)); HIPCHK(d_err.zero_async(1));
         trackgraph_bfs_kernel<TG_BFS_LANES><<<grid_for(n * TG_BFS_LANES, TG_BLOCK), TG_BLOCK, 0, s>>>(
-            n, d_sel.as<uint32_t>(), (uint32_t)attempt, g->d_comp_first, g->d_comp_size, d_off.as<uint32_t>(), g->d_members, g->d_adj_off, g->d_adj,
-            g->d_stamp, g->epoch, g->kp.d_off, g->kp.n_images, g->kp.d_uv, d_queue.as<uint32_t>(), d_img.as<int32_t>(), d_kp.as<int32_t>(),
-            obs_uv ? d_uv.as<float>() : nullptr, d_err.as<uint32_t>());
+            n, d_sel, (uint32_t)attempt, g->d_comp_first, g->d_comp_size, d_off, g->d_members, g->d_adj_off, g->d_adj,
+            g->d_stamp, g->epoch, g->kp.d_off, g->kp.n_images, g->kp.d_uv, d_queue, d_img, d_kp,
+            obs_uv ? d_uv : nullptr, d_err);
         HIPCHK(hipGetLastError());
         uint32_t err = 0;
-        HIPCHK(hipMemcpyAsync(&err, d_err.p, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&err, d_err, d_err.bytes(1), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         if (err) return lvba_fail(LVBA_ERR_STATE, "a breadth-first walk ended %s its component's size", err & TG_ERR_OVERRUN ? "beyond" : "short of");
-        HIPCHK(lvba::copy_d2h(obs_img, d_img.p, 4 * total));
-        HIPCHK(lvba::copy_d2h(obs_kp, d_kp.p, 4 * total));
-        if (obs_uv) HIPCHK(lvba::copy_d2h(obs_uv, d_uv.p, 8 * total));
+        HIPCHK(d_img.download(obs_img, total)); HIPCHK(d_kp.download(obs_kp, total));
+        if (obs_uv) HIPCHK(d_uv.download(obs_uv, 2 * total));
     }
     for (int64_t k = 0; k <= n; ++k) obs_off[k] = off[(size_t)k];
     return LVBA_OK;

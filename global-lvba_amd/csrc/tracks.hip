@@ -59,27 +59,27 @@ extern "C" int32_t lvba_triangulate_tracks(int32_t device, int32_t n_cams, int64
     ScopedStream sg;
     HIPCHK(sg.acquire());
     const hipStream_t s = sg.s;
-    DevBuf d_off(s), d_cam(s), d_uv(s), d_R(s), d_t(s), d_X(s), d_err(s), d_cnt(s), d_ok(s);
-    HIPCHK(d_off.alloc(8 * ((size_t)n_tracks + 1))); HIPCHK(d_cam.alloc(4 * (size_t)O)); HIPCHK(d_uv.alloc(16 * (size_t)O));
-    HIPCHK(d_R.alloc(72 * (size_t)n_cams)); HIPCHK(d_t.alloc(24 * (size_t)n_cams));
-    HIPCHK(d_X.alloc(24 * (size_t)n_tracks)); HIPCHK(d_err.alloc(8 * (size_t)n_tracks));
-    HIPCHK(d_cnt.alloc(4 * (size_t)n_tracks)); HIPCHK(d_ok.alloc((size_t)n_tracks));
-    HIPCHK(hipMemcpyAsync(d_off.p, obs_off, 8 * ((size_t)n_tracks + 1), hipMemcpyHostToDevice, s));
+    DevArr<int64_t> d_off(s); DevArr<int32_t> d_cam(s); DevArr<double> d_uv(s), d_R(s), d_t(s), d_X(s), d_err(s);
+    DevArr<int32_t> d_cnt(s); DevArr<uint8_t> d_ok(s);
+    HIPCHK(d_off.alloc((size_t)n_tracks + 1)); HIPCHK(d_cam.alloc((size_t)O)); HIPCHK(d_uv.alloc(2 * (size_t)O));
+    HIPCHK(d_R.alloc(9 * (size_t)n_cams)); HIPCHK(d_t.alloc(3 * (size_t)n_cams));
+    HIPCHK(d_X.alloc(3 * (size_t)n_tracks)); HIPCHK(d_err.alloc((size_t)n_tracks));
+    HIPCHK(d_cnt.alloc((size_t)n_tracks)); HIPCHK(d_ok.alloc((size_t)n_tracks));
+    HIPCHK(hipMemcpyAsync(d_off, obs_off, d_off.bytes((size_t)n_tracks + 1), hipMemcpyHostToDevice, s));
     if (O > 0) {
-        HIPCHK(hipMemcpyAsync(d_cam.p, obs_cam, 4 * (size_t)O, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(d_uv.p, obs_uv, 16 * (size_t)O, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d_cam, obs_cam, d_cam.bytes((size_t)O), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d_uv, obs_uv, d_uv.bytes(2 * (size_t)O), hipMemcpyHostToDevice, s));
     }
-    HIPCHK(hipMemcpyAsync(d_R.p, Rcw, 72 * (size_t)n_cams, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_t.p, tcw, 24 * (size_t)n_cams, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_R, Rcw, d_R.bytes(9 * (size_t)n_cams), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_t, tcw, d_t.bytes(3 * (size_t)n_cams), hipMemcpyHostToDevice, s));
     const Intr c = trk_intr_of(intr);
-    tri_kernel<<<(unsigned)((n_tracks + 127) / 128), 128, 0, s>>>(n_tracks, d_off.as<int64_t>(), d_cam.as<int32_t>(), d_uv.as<double>(),
-                                                                  d_R.as<double>(), d_t.as<double>(), n_cams, c, d_X.as<double>(),
-                                                                  d_err.as<double>(), d_cnt.as<int32_t>(), d_ok.as<uint8_t>());
+    tri_kernel<<<(unsigned)((n_tracks + 127) / 128), 128, 0, s>>>(n_tracks, d_off, d_cam, d_uv, d_R, d_t, n_cams, c, d_X, d_err,
+                                                                  d_cnt, d_ok);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(X, d_X.p, 24 * (size_t)n_tracks, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(mean_reproj, d_err.p, 8 * (size_t)n_tracks, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(count, d_cnt.p, 4 * (size_t)n_tracks, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(ok, d_ok.p, (size_t)n_tracks, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(X, d_X, d_X.bytes(3 * (size_t)n_tracks), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(mean_reproj, d_err, d_err.bytes((size_t)n_tracks), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(count, d_cnt, d_cnt.bytes((size_t)n_tracks), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(ok, d_ok, d_ok.bytes((size_t)n_tracks), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return LVBA_OK;
 }

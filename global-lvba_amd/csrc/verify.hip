@@ -333,7 +333,7 @@ int32_t make_task(const lvba_verify_s *v, int64_t a, int64_t b, int64_t m_off, i
 // The hypotheses of every pair with enough matches (ransac_run_hypotheses).  diag_E, diag_count: null, or the diagnostic call's outputs.
 // method: o.method, or VERIFY_HOMOGRAPHY.
 int32_t run_hypotheses(hipStream_t s, const lvba_verify_s *v, std::vector<VerifyTask> &tasks, const lvba_verify_opts &o, int method,
-                       const int32_t *d_matches, DevBuf &d_tasks, DevBuf &d_blk, double *diag_E, int32_t *diag_count)
+                       const int32_t *d_matches, DevArr<VerifyTask> &d_tasks, DevArr<VerifyBest> &d_blk, double *diag_E, int32_t *diag_count)
 {
     const int k = verify_sample_size(method);
     const double tau2 = match_tau2(v->focal_sum, o.max_error_px);
@@ -341,7 +341,7 @@ int32_t run_hypotheses(hipStream_t s, const lvba_verify_s *v, std::vector<Verify
                         : method == VERIFY_HOMOGRAPHY ? verify_hypothesis_kernel<VERIFY_HOMOGRAPHY>
                                                       : verify_hypothesis_kernel<VERIFY_KNOWN_ROTATION>;
     return ransac_run_hypotheses<9>(s, tasks, o.hypotheses, diag_E ? k : std::max(k, o.min_inliers), d_tasks, d_blk, [&](unsigned grid, const RansacTile *tiles) {
-        kernel<<<grid, RANSAC_HB, 0, s>>>(d_tasks.as<VerifyTask>(), tiles, d_matches, v->kp.d_xy, o.seed, o.hypotheses, tau2, d_blk.as<VerifyBest>(), diag_E,
+        kernel<<<grid, RANSAC_HB, 0, s>>>(d_tasks, tiles, d_matches, v->kp.d_xy, o.seed, o.hypotheses, tau2, d_blk, diag_E,
                                           diag_count);
     });
 }
@@ -419,27 +419,28 @@ int32_t run_pairs(lvba_verify_t v, int64_t n_pairs, const int32_t *pairs, const 
     hipStream_t s = sg.s;
     const int np = (int)n_pairs;
     const double tau2 = match_tau2(v->focal_sum, o.max_error_px);
-    DevBuf d_m(s), d_tasks(s), d_blk(s), d_res(s), d_E(s), d_int(s);
-    HIPCHK(d_m.alloc(8 * (size_t)total));
-    if (total > 0) HIPCHK(lvba::copy_h2d(d_m.p, matches, 8 * (size_t)total));
-    TRY(run_hypotheses(s, v, tasks, o, method, d_m.as<int32_t>(), d_tasks, d_blk, nullptr, nullptr));
-    HIPCHK(d_res.alloc(sizeof(VerifyBest) * (size_t)np)); HIPCHK(d_E.alloc(72 * (size_t)np)); HIPCHK(d_int.alloc(12 * (size_t)np));
-    int32_t *d_status = d_int.as<int32_t>(), *d_cnt = d_status + np, *d_h = d_cnt + np;
-    ransac_pick_kernel<<<grid_for(np, 256), 256, 0, s>>>(np, d_tasks.as<VerifyTask>(), d_blk.as<VerifyBest>(), d_res.as<VerifyBest>());
+    DevArr<int32_t> d_m(s); DevArr<VerifyTask> d_tasks(s); DevArr<VerifyBest> d_blk(s), d_res(s); DevArr<double> d_E(s);
+    DevArr<int32_t> d_int(s);
+    HIPCHK(d_m.alloc(2 * (size_t)total));
+    if (total > 0) HIPCHK(d_m.upload(matches, 2 * (size_t)total));
+    TRY(run_hypotheses(s, v, tasks, o, method, d_m, d_tasks, d_blk, nullptr, nullptr));
+    HIPCHK(d_res.alloc((size_t)np)); HIPCHK(d_E.alloc(9 * (size_t)np)); HIPCHK(d_int.alloc(3 * (size_t)np));
+    int32_t *d_status = d_int, *d_cnt = d_status + np, *d_h = d_cnt + np;
+    ransac_pick_kernel<9, VerifyTask><<<grid_for(np, 256), 256, 0, s>>>(np, d_tasks, d_blk, d_res);
     HIPCHK(hipGetLastError());
     const auto refine = method == VERIFY_EIGHT_POINT    ? verify_refine_kernel<VERIFY_EIGHT_POINT>
                         : method == VERIFY_HOMOGRAPHY ? verify_refine_kernel<VERIFY_HOMOGRAPHY>
                                                       : verify_refine_kernel<VERIFY_KNOWN_ROTATION>;
-    refine<<<(unsigned)np, REFINE_BLOCK, 0, s>>>(d_tasks.as<VerifyTask>(), d_m.as<int32_t>(), v->kp.d_xy, tau2, o.refine_rounds, o.min_inliers,
-                                                 d_res.as<VerifyBest>(), d_E.as<double>(), d_status, d_cnt, d_h);
+    refine<<<(unsigned)np, REFINE_BLOCK, 0, s>>>(d_tasks, d_m, v->kp.d_xy, tau2, o.refine_rounds, o.min_inliers, d_res, d_E,
+                                                 d_status, d_cnt, d_h);
     HIPCHK(hipGetLastError());
     if (method == VERIFY_HOMOGRAPHY)
-        TRY(ransac_inlier_lists(s, total, np, d_tasks.as<VerifyTask>(), d_status, VerifyInlierH{d_m.as<int32_t>(), v->kp.d_xy, d_E.as<double>(), tau2},
-                                VerifyEmit{d_m.as<int32_t>()}, capacity, inlier_off, inliers));
+        TRY(ransac_inlier_lists<VerifyTask>(s, total, np, d_tasks, d_status, VerifyInlierH{d_m, v->kp.d_xy, d_E, tau2},
+                                VerifyEmit{d_m}, capacity, inlier_off, inliers));
     else
-        TRY(ransac_inlier_lists(s, total, np, d_tasks.as<VerifyTask>(), d_status, VerifyInlier{d_m.as<int32_t>(), v->kp.d_xy, d_E.as<double>(), tau2},
-                                VerifyEmit{d_m.as<int32_t>()}, capacity, inlier_off, inliers));
-    HIPCHK(lvba::copy_d2h(E, d_E.p, 72 * (size_t)np));
+        TRY(ransac_inlier_lists<VerifyTask>(s, total, np, d_tasks, d_status, VerifyInlier{d_m, v->kp.d_xy, d_E, tau2},
+                                VerifyEmit{d_m}, capacity, inlier_off, inliers));
+    HIPCHK(d_E.download(E, 9 * (size_t)np));
     HIPCHK(lvba::copy_d2h(status, d_status, 4 * (size_t)np));
     HIPCHK(lvba::copy_d2h(n_inliers, d_cnt, 4 * (size_t)np));
     HIPCHK(lvba::copy_d2h(best_h, d_h, 4 * (size_t)np));
@@ -461,12 +462,11 @@ int32_t run_diagnostic(lvba_verify_t v, int32_t a, int32_t b, int64_t n_matches,
     HIPCHK(hipSetDevice(v->kp.device));
     ScopedStream sg;
     HIPCHK(sg.acquire());
-    DevBuf d_m(sg.s), d_tasks(sg.s), d_blk(sg.s), d_E(sg.s), d_c(sg.s);
-    HIPCHK(d_m.alloc(8 * (size_t)n_matches)); HIPCHK(d_E.alloc(72 * H)); HIPCHK(d_c.alloc(4 * H));
-    HIPCHK(lvba::copy_h2d(d_m.p, matches, 8 * (size_t)n_matches));
-    TRY(run_hypotheses(sg.s, v, tasks, o, method, d_m.as<int32_t>(), d_tasks, d_blk, d_E.as<double>(), d_c.as<int32_t>()));
-    HIPCHK(lvba::copy_d2h(E, d_E.p, 72 * H));
-    HIPCHK(lvba::copy_d2h(count, d_c.p, 4 * H));
+    DevArr<int32_t> d_m(sg.s); DevArr<VerifyTask> d_tasks(sg.s); DevArr<VerifyBest> d_blk(sg.s); DevArr<double> d_E(sg.s); DevArr<int32_t> d_c(sg.s);
+    HIPCHK(d_m.alloc(2 * (size_t)n_matches)); HIPCHK(d_E.alloc(9 * H)); HIPCHK(d_c.alloc(H));
+    HIPCHK(d_m.upload(matches, 2 * (size_t)n_matches));
+    TRY(run_hypotheses(sg.s, v, tasks, o, method, d_m, d_tasks, d_blk, d_E, d_c)); HIPCHK(d_E.download(E, 9 * H));
+    HIPCHK(d_c.download(count, H));
     return LVBA_OK;
 }
 
@@ -482,13 +482,12 @@ int32_t run_score(lvba_verify_t v, int32_t a, int32_t b, int64_t n_matches, cons
     HIPCHK(hipSetDevice(v->kp.device));
     ScopedStream sg;
     HIPCHK(sg.acquire());
-    DevBuf d_m(sg.s), d_E(sg.s);
-    HIPCHK(d_m.alloc(8 * (size_t)n_matches)); HIPCHK(d_E.alloc(72));
-    HIPCHK(lvba::copy_h2d(d_m.p, matches, 8 * (size_t)n_matches));
-    HIPCHK(lvba::copy_h2d(d_E.p, E, 72));
+    DevArr<int32_t> d_m(sg.s); DevArr<double> d_E(sg.s);
+    HIPCHK(d_m.alloc(2 * (size_t)n_matches)); HIPCHK(d_E.alloc(9)); HIPCHK(d_m.upload(matches, 2 * (size_t)n_matches));
+    HIPCHK(d_E.upload(E, 9));
     const double tau2 = match_tau2(v->focal_sum, max_error_px);
-    if (homography) return ransac_score_mask(sg.s, tasks[0], VerifyInlierH{d_m.as<int32_t>(), v->kp.d_xy, d_E.as<double>(), tau2}, mask);
-    return ransac_score_mask(sg.s, tasks[0], VerifyInlier{d_m.as<int32_t>(), v->kp.d_xy, d_E.as<double>(), tau2}, mask);
+    if (homography) return ransac_score_mask(sg.s, tasks[0], VerifyInlierH{d_m, v->kp.d_xy, d_E, tau2}, mask);
+    return ransac_score_mask(sg.s, tasks[0], VerifyInlier{d_m, v->kp.d_xy, d_E, tau2}, mask);
 }
 
 // the options of a call that runs the homography alone: `method` is not read

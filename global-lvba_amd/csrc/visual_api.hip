@@ -393,9 +393,9 @@ extern "C" int32_t lvba_visual_prior_residuals(lvba_visual_t h, const double *q,
     HIPCHK(hipSetDevice(bs.device));
     const int64_t n = h->vp.tab.n;
     if (n == 0) { if (cost) *cost = 0.0; return LVBA_OK; }
-    DevBuf d(bs.stream);
-    HIPCHK(d.alloc((size_t)(6 * n + 1 + 7 * (int64_t)h->M) * sizeof(double)));
-    double *de = d.as<double>(), *dq = de + 6 * n + 1, *dt = dq + 4 * (int64_t)h->M;
+    DevArr<double> d(bs.stream);
+    HIPCHK(d.alloc((size_t)(6 * n + 1 + 7 * (int64_t)h->M)));
+    double *de = d, *dq = de + 6 * n + 1, *dt = dq + 4 * (int64_t)h->M;
     lvba::hvec<double> st(7 * (size_t)h->M);
     for (int c = 0; c < h->M; ++c) {
         const int I = bs.iperm[c];
@@ -490,10 +490,10 @@ extern "C" int32_t lvba_visual_residual_sq(lvba_visual_t h, const double *q, con
     TRY(import_state(h, q, t, X));
     const int64_t n = h->O + h->Ta;
     lvba::hvec<double> hs((size_t)std::max<int64_t>(1, n));
-    DevBuf ds(bs.stream);
-    HIPCHK(ds.alloc((size_t)std::max<int64_t>(1, n) * sizeof(double)));
-    vis_launch_residual_sq(h->dev(), h->d_q, h->d_t, h->d_X, ds.as<double>(), bs.stream);
-    if (n) HIPCHK(hipMemcpyAsync(hs.data(), ds.as<double>(), (size_t)n * sizeof(double), hipMemcpyDeviceToHost, bs.stream));
+    DevArr<double> ds(bs.stream);
+    HIPCHK(ds.alloc((size_t)std::max<int64_t>(1, n)));
+    vis_launch_residual_sq(h->dev(), h->d_q, h->d_t, h->d_X, ds, bs.stream);
+    if (n) HIPCHK(hipMemcpyAsync(hs.data(), ds, ds.bytes((size_t)n), hipMemcpyDeviceToHost, bs.stream));
     HIPCHK(hipStreamSynchronize(bs.stream));
     HIPCHK(hipGetLastError());
     for (int64_t o = 0; o < h->O_all; ++o) obs_sq[o] = NAN;     // observations of inactive landmarks
@@ -522,11 +522,11 @@ extern "C" int32_t lvba_visual_linearize(lvba_visual_t h, const double *q, const
     TRY(enqueue_colnorms(h));
     TRY(enqueue_reduced_system(h, radius, o));
     const int64_t n = 6 * (int64_t)h->M;
-    DevBuf dS(bs.stream); // freed on every path, error returns included
+    DevArr<double> dS(bs.stream); // freed on every path, error returns included
     if (S) {
-        HIPCHK(dS.alloc((size_t)(n * n) * sizeof(double)));
-        launch_export_dense(bs.Hblk(), bs.Bb, h->M, bs.d_perm, dS.as<double>(), bs.stream);
-        HIPCHK(hipMemcpyAsync(S, dS.as<double>(), (size_t)(n * n) * sizeof(double), hipMemcpyDeviceToHost, bs.stream));
+        HIPCHK(dS.alloc((size_t)(n * n)));
+        launch_export_dense(bs.Hblk(), bs.Bb, h->M, bs.d_perm, dS, bs.stream);
+        HIPCHK(hipMemcpyAsync(S, dS, dS.bytes((size_t)(n * n)), hipMemcpyDeviceToHost, bs.stream));
     }
     if (rhs) {
         launch_export_vec(bs.g(), bs.d_perm, h->M, h->d_out, bs.stream);

@@ -148,7 +148,12 @@ __global__ void vox_fetch_kernel(FetchArgs a)
 struct Fetch {
     FetchArgs a{};
     void *host[6];
-    void add(void *h, const void *d, size_t bytes) { host[a.n] = h; a.src[a.n] = (const uint32_t *)d; a.words[a.n] = (int)(bytes / 4); ++a.n; }
+    // count elements of T (whole 32-bit words) from the device pointer or DevArr<T> d
+    template <class T, class D> void add(T *h, const D &d, size_t count)
+    {
+        const T *src = d;
+        host[a.n] = h; a.src[a.n] = (const uint32_t *)src; a.words[a.n] = (int)(count * sizeof(T) / 4); ++a.n;
+    }
     hipError_t run(hipStream_t s)
     {
         size_t total = 0;
@@ -843,173 +848,158 @@ int32_t voxmap_build_impl(lvba_voxmap_s *h, const lvba_scans_s *sc, int frame_be
     const float *pts = sc->d_pts + 3 * p_begin;
     double t0 = now_ms();
 
-    DevBuf d_poses(s);
-    HIPCHK(d_poses.alloc(96 * (size_t)nfr));
+    DevArr<double> d_poses(s);
+    HIPCHK(d_poses.alloc(12 * (size_t)nfr));
     // (small transfers to / from the caller's PAGEABLE memory go through the synchronous copy: the asynchronous one pins the
     // pages on the fly, which was measured at up to 24 ms for 30 KB)
-    HIPCHK(lvba::copy_h2d(d_poses.p, poses, 96 * (size_t)nfr));
+    HIPCHK(d_poses.upload(poses, 12 * (size_t)nfr));
 
     // -- 1./2. keys + records, root sort (stable: inside a root the records stay frame-major, cloud order inside a frame),
     //          root table and (root, frame) segment table
     int64_t R = 0, NS = 0;
-    DevBuf rec_s(s), root_key(s), root_seg(s), seg_start(s), seg_root(s), seg_frame(s);
+    DevArr<float4> rec_s(s); DevArr<uint64_t> root_key(s); DevArr<uint32_t> root_seg(s), seg_start(s), seg_root(s);
+    DevArr<int32_t> seg_frame(s);
     {
-        DevBuf key(s), rec(s), idx(s), key_s(s), idx0(s), d_err(s);
-        HIPCHK(key.alloc(8 * P)); HIPCHK(rec.alloc(16 * P)); HIPCHK(idx.alloc(4 * P));
-        HIPCHK(key_s.alloc(8 * P)); HIPCHK(idx0.alloc(4 * P)); HIPCHK(rec_s.alloc(16 * P)); HIPCHK(d_err.alloc(28));
+        DevArr<uint64_t> key(s); DevArr<float4> rec(s); DevArr<uint32_t> idx(s); DevArr<uint64_t> key_s(s);
+        DevArr<uint32_t> idx0(s); DevArr<int> d_err(s);
+        HIPCHK(key.alloc(P)); HIPCHK(rec.alloc(P)); HIPCHK(idx.alloc(P));
+        HIPCHK(key_s.alloc(P)); HIPCHK(idx0.alloc(P)); HIPCHK(rec_s.alloc(P)); HIPCHK(d_err.alloc(7));
         int h_err[7] = {0}; // [0] error flag, [1..6] range of the biased key components
-        DevBuf d_part(s);
+        DevArr<int> d_part(s);
         const int64_t n_slots = key_range_slots(P, 256);
-        HIPCHK(d_part.alloc(24 * (size_t)n_slots));
-        HIPCHK(hipMemsetAsync(d_err.p, 0, 28, s));
-        vox_key_kernel<<<grid_for(P, 256), 256, 0, s>>>(P, pts, sc->d_frame_off + frame_begin, nfr, d_poses.as<double>(),
-                                                        h->opts.voxel_size, key.as<uint64_t>(), rec.as<float4>(),
-                                                        idx.as<uint32_t>(), d_err.as<int>(), d_part.as<int>());
+        HIPCHK(d_part.alloc(6 * (size_t)n_slots)); HIPCHK(d_err.zero_async(7));
+        vox_key_kernel<<<grid_for(P, 256), 256, 0, s>>>(P, pts, sc->d_frame_off + frame_begin, nfr, d_poses, h->opts.voxel_size,
+                                                        key, rec, idx, d_err, d_part);
         HIPCHK(hipGetLastError());
-        key_range_reduce_kernel<<<key_range_reduce_grid(n_slots), 256, 0, s>>>(n_slots, d_part.as<int>(), d_err.as<int>() + 1);
+        key_range_reduce_kernel<<<key_range_reduce_grid(n_slots), 256, 0, s>>>(n_slots, d_part, d_err + 1);
         HIPCHK(hipGetLastError());
-        { Fetch f; f.add(h_err, d_err.p, 28); HIPCHK(f.run(s)); }
+        { Fetch f; f.add(h_err, d_err, 7); HIPCHK(f.run(s)); }
         if (h_err[0]) return lvba_fail(LVBA_ERR_ARG, "a point is non-finite or its voxel key exceeds +-2^20 after the pose transform");
         h->info.key_ms = now_ms() - t0; t0 = now_ms();
         const KeyPack kp = key_pack_of(h_err + 1);
         // (the gather also writes the head flags of the sorted sequence: vox_gather_kernel)
-        DevBuf heads(s), incl(s);
-        HIPCHK(heads.alloc(8 * P)); HIPCHK(incl.alloc(8 * P));
+        DevArr<uint64_t> heads(s), incl(s);
+        HIPCHK(heads.alloc(P)); HIPCHK(incl.alloc(P));
         const int64_t *foff = sc->d_frame_off + frame_begin;
-        uint64_t *keys_sorted = key_s.as<uint64_t>(); // the sorted keys in their 3 x 21-bit form
+        uint64_t *keys_sorted = key_s; // the sorted keys in their 3 x 21-bit form
         const unsigned sort_bits = (unsigned)(kp.total + (ws ? wbits : 0));
         if (ws && sort_bits > 64) return lvba_fail(LVBA_ERR_UNSUPPORTED, "joint map: %d key bits + %d window bits", kp.total, wbits);
-        DevBuf k32(s), k32s(s); // (live until the block ends: handing them back earlier would cost a stream round trip)
+        DevArr<uint32_t> k32(s), k32s(s); // (live until the block ends: handing them back earlier would cost a stream round trip)
         if (sort_bits <= 32) {
-            HIPCHK(k32.alloc(4 * P)); HIPCHK(k32s.alloc(4 * P));
-            if (ws) key_compress_win_kernel<uint32_t><<<grid_for(P, 256), 256, 0, s>>>(P, key.as<uint64_t>(), rec.as<float4>(), kp, ws, k32.as<uint32_t>());
-            else key_compress_kernel<uint32_t><<<grid_for(P, 256), 256, 0, s>>>(P, key.as<uint64_t>(), kp, k32.as<uint32_t>());
+            HIPCHK(k32.alloc(P)); HIPCHK(k32s.alloc(P));
+            if (ws) key_compress_win_kernel<uint32_t><<<grid_for(P, 256), 256, 0, s>>>(P, key, rec, kp, ws, k32);
+            else key_compress_kernel<uint32_t><<<grid_for(P, 256), 256, 0, s>>>(P, key, kp, k32);
             HIPCHK(hipGetLastError());
-            TRY(sort_pairs(s, k32.as<uint32_t>(), k32s.as<uint32_t>(), idx.as<uint32_t>(), idx0.as<uint32_t>(), (size_t)P, sort_bits));
-            vox_gather_kernel<uint32_t><<<grid_for(P, 256), 256, 0, s>>>(P, rec.as<float4>(), idx0.as<uint32_t>(), rec_s.as<float4>(), k32s.as<uint32_t>(), kp,
-                                                                         keys_sorted, foff, nfr, heads.as<uint64_t>());
+            TRY(sort_pairs<uint32_t>(s, k32, k32s, idx, idx0, (size_t)P, sort_bits));
+            vox_gather_kernel<uint32_t><<<grid_for(P, 256), 256, 0, s>>>(P, rec, idx0, rec_s, k32s, kp, keys_sorted, foff, nfr,
+                                                                         heads);
             HIPCHK(hipGetLastError());
-        } else { // wide maps: 64-bit keys, still only the bits that vary (compressed in place; expanded into the unsorted keys' buffer)
-            if (ws) key_compress_win_kernel<uint64_t><<<grid_for(P, 256), 256, 0, s>>>(P, key.as<uint64_t>(), rec.as<float4>(), kp, ws, key.as<uint64_t>());
-            else key_compress_kernel<uint64_t><<<grid_for(P, 256), 256, 0, s>>>(P, key.as<uint64_t>(), kp, key.as<uint64_t>());
+        } else { // wide maps: 64-bit keys, still only the bits that vary (`key` is rewritten in place; expanded into the unsorted keys' buffer)
+            if (ws) key_compress_win_kernel<uint64_t><<<grid_for(P, 256), 256, 0, s>>>(P, key, rec, kp, ws, key);
+            else key_compress_kernel<uint64_t><<<grid_for(P, 256), 256, 0, s>>>(P, key, kp, key);
             HIPCHK(hipGetLastError());
-            TRY(sort_pairs(s, key.as<uint64_t>(), key_s.as<uint64_t>(), idx.as<uint32_t>(), idx0.as<uint32_t>(), (size_t)P, sort_bits));
-            keys_sorted = key.as<uint64_t>();
-            vox_gather_kernel<uint64_t><<<grid_for(P, 256), 256, 0, s>>>(P, rec.as<float4>(), idx0.as<uint32_t>(), rec_s.as<float4>(), key_s.as<uint64_t>(), kp,
-                                                                         keys_sorted, foff, nfr, heads.as<uint64_t>());
+            TRY(sort_pairs<uint64_t>(s, key, key_s, idx, idx0, (size_t)P, sort_bits));
+            keys_sorted = key;
+            vox_gather_kernel<uint64_t><<<grid_for(P, 256), 256, 0, s>>>(P, rec, idx0, rec_s, key_s, kp, keys_sorted, foff, nfr,
+                                                                         heads);
             HIPCHK(hipGetLastError());
         }
         // ONE inclusive scan numbers roots (high word) and (root, frame) segments (low word)
-        TRY(scan_incl<uint64_t>(s, heads.as<uint64_t>(), incl.as<uint64_t>(), (size_t)P));
+        TRY(scan_incl<uint64_t>(s, heads, incl, (size_t)P));
         uint64_t last = 0;
-        { Fetch f; f.add(&last, incl.as<uint64_t>() + (P - 1), 8); HIPCHK(f.run(s)); }
+        { Fetch f; f.add(&last, incl + (P - 1), 1); HIPCHK(f.run(s)); }
         R = (int64_t)(last >> 32); NS = (int64_t)(last & 0xFFFFFFFFull);
-        HIPCHK(root_key.alloc(8 * (size_t)R)); HIPCHK(root_seg.alloc(4 * ((size_t)R + 1)));
-        HIPCHK(seg_start.alloc(4 * ((size_t)NS + 1))); HIPCHK(seg_root.alloc(4 * (size_t)NS)); HIPCHK(seg_frame.alloc(4 * (size_t)NS));
-        vox_tables_kernel<<<grid_for(P, 256), 256, 0, s>>>(P, keys_sorted, rec_s.as<float4>(), heads.as<uint64_t>(), incl.as<uint64_t>(),
-                                                           root_key.as<uint64_t>(), root_seg.as<uint32_t>(), seg_start.as<uint32_t>(),
-                                                           seg_root.as<uint32_t>(), seg_frame.as<int32_t>());
+        HIPCHK(root_key.alloc((size_t)R)); HIPCHK(root_seg.alloc((size_t)R + 1));
+        HIPCHK(seg_start.alloc((size_t)NS + 1)); HIPCHK(seg_root.alloc((size_t)NS)); HIPCHK(seg_frame.alloc((size_t)NS));
+        vox_tables_kernel<<<grid_for(P, 256), 256, 0, s>>>(P, keys_sorted, rec_s, heads, incl, root_key, root_seg, seg_start,
+                                                           seg_root, seg_frame);
         HIPCHK(hipGetLastError());
     } // (the work buffers' destructors wait for the stream before the pool takes them back)
     h->info.n_roots = R;
     h->info.sort_ms = now_ms() - t0; t0 = now_ms();
 
     // -- 3. octree: root clusters and decisions for every root, children / grandchildren for the roots that split
-    DevBuf segm1(s), segm2(s);
-    HIPCHK(segm1.alloc(4 * (size_t)NS)); HIPCHK(segm2.alloc(8 * (size_t)NS));
-    DevBuf segcl(s), n_plane(s), n_vox(s), n_fac(s), mask(s), rootinfo(s), plane0(s), is_split(s), seg_split(s), split_excl(s), seg_excl(s);
-    HIPCHK(segcl.alloc(80 * (size_t)NS));
-    HIPCHK(n_plane.alloc(4 * (R + 1))); HIPCHK(n_vox.alloc(4 * (R + 1))); HIPCHK(n_fac.alloc(8 * (R + 1)));
-    HIPCHK(mask.alloc(8 * R)); HIPCHK(rootinfo.alloc(4 * R)); HIPCHK(plane0.alloc(48 * R));
-    HIPCHK(is_split.alloc(4 * (R + 1))); HIPCHK(seg_split.alloc(4 * (NS + 1)));
-    HIPCHK(split_excl.alloc(4 * (R + 1))); HIPCHK(seg_excl.alloc(4 * (NS + 1)));
-    HIPCHK(hipMemsetAsync(n_plane.as<int32_t>() + R, 0, 4, s));
-    HIPCHK(hipMemsetAsync(n_vox.as<int32_t>() + R, 0, 4, s));
-    HIPCHK(hipMemsetAsync(n_fac.as<int64_t>() + R, 0, 8, s));
-    HIPCHK(hipMemsetAsync(is_split.as<uint32_t>() + R, 0, 4, s));
-    HIPCHK(hipMemsetAsync(seg_split.as<uint32_t>() + NS, 0, 4, s));
-    vox_seg_small_kernel<<<grid_for(NS, 64), 64, 0, s>>>(NS, seg_start.as<uint32_t>(), rec_s.as<float4>(), segcl.as<double>(),
-                                                         segm1.as<uint32_t>(), segm2.as<uint64_t>());
-    vox_seg_big_kernel<<<(unsigned)NS, 64, 0, s>>>(NS, seg_start.as<uint32_t>(), rec_s.as<float4>(), segcl.as<double>(),
-                                                   segm1.as<uint32_t>(), segm2.as<uint64_t>());
+    DevArr<uint32_t> segm1(s); DevArr<uint64_t> segm2(s);
+    HIPCHK(segm1.alloc((size_t)NS)); HIPCHK(segm2.alloc((size_t)NS));
+    DevArr<double> segcl(s); DevArr<int32_t> n_plane(s), n_vox(s); DevArr<int64_t> n_fac(s); DevArr<uint64_t> mask(s);
+    DevArr<uint32_t> rootinfo(s); DevArr<double> plane0(s); DevArr<uint32_t> is_split(s), seg_split(s), split_excl(s), seg_excl(s);
+    HIPCHK(segcl.alloc(10 * (size_t)NS)); HIPCHK(n_plane.alloc(R + 1)); HIPCHK(n_vox.alloc(R + 1)); HIPCHK(n_fac.alloc(R + 1));
+    HIPCHK(mask.alloc(R)); HIPCHK(rootinfo.alloc(R)); HIPCHK(plane0.alloc(6 * R));
+    HIPCHK(is_split.alloc(R + 1)); HIPCHK(seg_split.alloc(NS + 1)); HIPCHK(split_excl.alloc(R + 1)); HIPCHK(seg_excl.alloc(NS + 1));
+    HIPCHK(n_plane.zero_async(1, R)); HIPCHK(n_vox.zero_async(1, R)); HIPCHK(n_fac.zero_async(1, R));
+    HIPCHK(is_split.zero_async(1, R)); HIPCHK(seg_split.zero_async(1, NS));
+    vox_seg_small_kernel<<<grid_for(NS, 64), 64, 0, s>>>(NS, seg_start, rec_s, segcl, segm1, segm2);
+    vox_seg_big_kernel<<<(unsigned)NS, 64, 0, s>>>(NS, seg_start, rec_s, segcl, segm1, segm2);
     HIPCHK(hipGetLastError());
     RootArgs ra{};
-    ra.R = R; ra.root_seg = root_seg.as<uint32_t>(); ra.seg_frame = seg_frame.as<int32_t>(); ra.segcl = segcl.as<double>();
-    ra.poses = d_poses.as<double>();
+    ra.R = R; ra.root_seg = root_seg; ra.seg_frame = seg_frame; ra.segcl = segcl;
+    ra.poses = d_poses;
     for (int L = 0; L < 3; ++L) ra.ratio[L] = h->opts.eigen_ratio[L];
     ra.min_ps = h->opts.min_points;
-    ra.n_plane = n_plane.as<int32_t>(); ra.n_vox = n_vox.as<int32_t>(); ra.n_fac = n_fac.as<int64_t>();
-    ra.mask = mask.as<uint64_t>(); ra.rootinfo = rootinfo.as<uint32_t>(); ra.plane0 = plane0.as<double>();
-    ra.is_split = is_split.as<uint32_t>(); ra.seg_split = seg_split.as<uint32_t>();
+    ra.n_plane = n_plane; ra.n_vox = n_vox; ra.n_fac = n_fac;
+    ra.mask = mask; ra.rootinfo = rootinfo; ra.plane0 = plane0;
+    ra.is_split = is_split; ra.seg_split = seg_split;
     vox_root_kernel<<<grid_for(R, 64), 64, 0, s>>>(ra);
     HIPCHK(hipGetLastError());
-    TRY(scan_excl<uint32_t>(s, is_split.as<uint32_t>(), split_excl.as<uint32_t>(), (size_t)R + 1));
-    TRY(scan_excl<uint32_t>(s, seg_split.as<uint32_t>(), seg_excl.as<uint32_t>(), (size_t)NS + 1));
+    TRY(scan_excl<uint32_t>(s, is_split, split_excl, (size_t)R + 1));
+    TRY(scan_excl<uint32_t>(s, seg_split, seg_excl, (size_t)NS + 1));
     uint32_t NRS = 0, NSS = 0;
-    { Fetch f; f.add(&NRS, split_excl.as<uint32_t>() + R, 4); f.add(&NSS, seg_excl.as<uint32_t>() + NS, 4); HIPCHK(f.run(s)); }
+    { Fetch f; f.add(&NRS, split_excl + R, 1); f.add(&NSS, seg_excl + NS, 1); HIPCHK(f.run(s)); }
 
-    DevBuf split_roots(s), split_segs(s), m1(s), m2(s), cnt(s), base(s), nodecl(s), tmp_count(s), tmp_base(s), tmp_plane(s), tmp_nf(s);
+    DevArr<uint32_t> split_roots(s), split_segs(s), m1(s); DevArr<uint64_t> m2(s); DevArr<uint32_t> cnt(s), base(s);
+    DevArr<double> nodecl(s); DevArr<unsigned> tmp_count(s); DevArr<int32_t> tmp_base(s); DevArr<double> tmp_plane(s);
+    DevArr<int32_t> tmp_nf(s);
     SplitArgs sa{};
     if (NRS > 0) {
-        HIPCHK(split_roots.alloc(4 * (size_t)NRS)); HIPCHK(split_segs.alloc(4 * (size_t)NSS));
-        vox_compact_kernel<<<grid_for(R, 256), 256, 0, s>>>(R, is_split.as<uint32_t>(), split_excl.as<uint32_t>(), split_roots.as<uint32_t>());
-        vox_compact_kernel<<<grid_for(NS, 256), 256, 0, s>>>(NS, seg_split.as<uint32_t>(), seg_excl.as<uint32_t>(), split_segs.as<uint32_t>());
-        HIPCHK(m1.alloc(4 * (size_t)NSS)); HIPCHK(m2.alloc(8 * (size_t)NSS)); HIPCHK(cnt.alloc(4 * ((size_t)NSS + 1)));
-        HIPCHK(base.alloc(4 * ((size_t)NSS + 1)));
-        vox_split_masks_kernel<<<grid_for((int64_t)NSS + 1, 256), 256, 0, s>>>(NSS, split_segs.as<uint32_t>(), segm1.as<uint32_t>(),
-                                                                               segm2.as<uint64_t>(), m1.as<uint32_t>(), m2.as<uint64_t>(),
-                                                                               cnt.as<uint32_t>());
+        HIPCHK(split_roots.alloc((size_t)NRS)); HIPCHK(split_segs.alloc((size_t)NSS));
+        vox_compact_kernel<<<grid_for(R, 256), 256, 0, s>>>(R, is_split, split_excl, split_roots);
+        vox_compact_kernel<<<grid_for(NS, 256), 256, 0, s>>>(NS, seg_split, seg_excl, split_segs);
+        HIPCHK(m1.alloc((size_t)NSS)); HIPCHK(m2.alloc((size_t)NSS)); HIPCHK(cnt.alloc((size_t)NSS + 1));
+        HIPCHK(base.alloc((size_t)NSS + 1));
+        vox_split_masks_kernel<<<grid_for((int64_t)NSS + 1, 256), 256, 0, s>>>(NSS, split_segs, segm1, segm2, m1, m2, cnt);
         HIPCHK(hipGetLastError());
-        TRY(scan_excl<uint32_t>(s, cnt.as<uint32_t>(), base.as<uint32_t>(), (size_t)NSS + 1));
+        TRY(scan_excl<uint32_t>(s, cnt, base, (size_t)NSS + 1));
         uint32_t NN = 0;
-        { Fetch f; f.add(&NN, base.as<uint32_t>() + NSS, 4); HIPCHK(f.run(s)); }
-        HIPCHK(nodecl.alloc(80 * (size_t)NN));
-        vox_split_cluster_kernel<<<NSS, 64, 0, s>>>(split_segs.as<uint32_t>(), seg_start.as<uint32_t>(), rec_s.as<float4>(),
-                                                    m1.as<uint32_t>(), m2.as<uint64_t>(), base.as<uint32_t>(), nodecl.as<double>());
+        { Fetch f; f.add(&NN, base + NSS, 1); HIPCHK(f.run(s)); }
+        HIPCHK(nodecl.alloc(10 * (size_t)NN));
+        vox_split_cluster_kernel<<<NSS, 64, 0, s>>>(split_segs, seg_start, rec_s, m1, m2, base, nodecl);
         HIPCHK(hipGetLastError());
         const size_t tmp_cap = (size_t)(P / h->opts.min_points) + 1; // a PLANE node holds >= min_points points of its own
-        HIPCHK(tmp_count.alloc(4)); HIPCHK(tmp_base.alloc(4 * (size_t)NRS));
-        HIPCHK(tmp_plane.alloc(48 * tmp_cap)); HIPCHK(tmp_nf.alloc(4 * tmp_cap));
-        HIPCHK(hipMemsetAsync(tmp_count.p, 0, 4, s));
-        sa.split_roots = split_roots.as<uint32_t>(); sa.root_seg = root_seg.as<uint32_t>(); sa.seg_excl = seg_excl.as<uint32_t>();
-        sa.seg_frame = seg_frame.as<int32_t>(); sa.m1 = m1.as<uint32_t>(); sa.m2 = m2.as<uint64_t>(); sa.base = base.as<uint32_t>();
-        sa.nodecl = nodecl.as<double>(); sa.poses = d_poses.as<double>();
+        HIPCHK(tmp_count.alloc(1)); HIPCHK(tmp_base.alloc((size_t)NRS));
+        HIPCHK(tmp_plane.alloc(6 * tmp_cap)); HIPCHK(tmp_nf.alloc(tmp_cap)); HIPCHK(tmp_count.zero_async(1));
+        sa.split_roots = split_roots; sa.root_seg = root_seg; sa.seg_excl = seg_excl;
+        sa.seg_frame = seg_frame; sa.m1 = m1; sa.m2 = m2; sa.base = base;
+        sa.nodecl = nodecl; sa.poses = d_poses;
         for (int L = 0; L < 3; ++L) sa.ratio[L] = h->opts.eigen_ratio[L];
         sa.min_ps = h->opts.min_points;
-        sa.n_plane = n_plane.as<int32_t>(); sa.n_vox = n_vox.as<int32_t>(); sa.n_fac = n_fac.as<int64_t>();
-        sa.mask = mask.as<uint64_t>(); sa.rootinfo = rootinfo.as<uint32_t>();
-        sa.tmp_count = tmp_count.as<unsigned>(); sa.tmp_base = tmp_base.as<int32_t>();
-        sa.tmp_plane = tmp_plane.as<double>(); sa.tmp_nf = tmp_nf.as<int32_t>();
+        sa.n_plane = n_plane; sa.n_vox = n_vox; sa.n_fac = n_fac;
+        sa.mask = mask; sa.rootinfo = rootinfo;
+        sa.tmp_count = tmp_count; sa.tmp_base = tmp_base;
+        sa.tmp_plane = tmp_plane; sa.tmp_nf = tmp_nf;
         vox_split_decide_kernel<<<NRS, 64, 0, s>>>(sa);
         HIPCHK(hipGetLastError());
     }
-    DevBuf plane_first(s), vox_first(s), fac_first(s);
-    HIPCHK(plane_first.alloc(4 * (R + 1))); HIPCHK(vox_first.alloc(4 * (R + 1))); HIPCHK(fac_first.alloc(8 * (R + 1)));
-    TRY(scan_excl<int32_t>(s, n_plane.as<int32_t>(), plane_first.as<int32_t>(), (size_t)R + 1));
-    TRY(scan_excl<int32_t>(s, n_vox.as<int32_t>(), vox_first.as<int32_t>(), (size_t)R + 1));
-    TRY(scan_excl<int64_t>(s, n_fac.as<int64_t>(), fac_first.as<int64_t>(), (size_t)R + 1));
+    DevArr<int32_t> plane_first(s), vox_first(s); DevArr<int64_t> fac_first(s);
+    HIPCHK(plane_first.alloc(R + 1)); HIPCHK(vox_first.alloc(R + 1)); HIPCHK(fac_first.alloc(R + 1));
+    TRY(scan_excl<int32_t>(s, n_plane, plane_first, (size_t)R + 1)); TRY(scan_excl<int32_t>(s, n_vox, vox_first, (size_t)R + 1));
+    TRY(scan_excl<int64_t>(s, n_fac, fac_first, (size_t)R + 1));
     int32_t n_planes = 0, V = 0;
     int64_t F = 0;
     Fetch fc;
-    fc.add(&n_planes, plane_first.as<int32_t>() + R, 4);
-    fc.add(&V, vox_first.as<int32_t>() + R, 4);
-    fc.add(&F, fac_first.as<int64_t>() + R, 8);
-    DevBuf wv(s), wf(s), wr(s);
+    fc.add(&n_planes, plane_first + R, 1); fc.add(&V, vox_first + R, 1); fc.add(&F, fac_first + R, 1);
+    DevArr<int64_t> wv(s), wf(s), wr(s);
     if (ws) { // where every window's voxels, factors and roots begin
-        HIPCHK(wv.alloc(8 * (size_t)n_win)); HIPCHK(wf.alloc(8 * (size_t)n_win));
-        HIPCHK(hipMemsetAsync(wv.p, 0xFF, 8 * (size_t)n_win, s)); HIPCHK(hipMemsetAsync(wf.p, 0xFF, 8 * (size_t)n_win, s));
-        vox_win_first_kernel<<<grid_for(R, 256), 256, 0, s>>>(R, root_seg.as<uint32_t>(), seg_frame.as<int32_t>(), ws, vox_first.as<int32_t>(),
-                                                              fac_first.as<int64_t>(), wv.as<int64_t>(), wf.as<int64_t>());
+        HIPCHK(wv.alloc((size_t)n_win)); HIPCHK(wf.alloc((size_t)n_win));
+        HIPCHK(hipMemsetAsync(wv, 0xFF, wv.bytes(n_win), s)); HIPCHK(hipMemsetAsync(wf, 0xFF, wf.bytes(n_win), s));
+        vox_win_first_kernel<<<grid_for(R, 256), 256, 0, s>>>(R, root_seg, seg_frame, ws, vox_first, fac_first, wv, wf);
         HIPCHK(hipGetLastError());
         h->win_v0.assign((size_t)n_win + 1, 0); h->win_f0.assign((size_t)n_win + 1, 0);
-        fc.add(h->win_v0.data(), wv.p, 8 * (size_t)n_win);
-        fc.add(h->win_f0.data(), wf.p, 8 * (size_t)n_win);
-        HIPCHK(wr.alloc(8 * ((size_t)n_win + 1)));
-        vox_win_roots_kernel<<<grid_for((int64_t)n_win + 1, 256), 256, 0, s>>>(R, n_win, root_seg.as<uint32_t>(), seg_frame.as<int32_t>(), ws,
-                                                                               wr.as<int64_t>());
+        fc.add(h->win_v0.data(), wv, (size_t)n_win); fc.add(h->win_f0.data(), wf, (size_t)n_win);
+        HIPCHK(wr.alloc((size_t)n_win + 1));
+        vox_win_roots_kernel<<<grid_for((int64_t)n_win + 1, 256), 256, 0, s>>>(R, n_win, root_seg, seg_frame, ws, wr);
         HIPCHK(hipGetLastError());
         h->win_r0.assign((size_t)n_win + 1, 0);
-        fc.add(h->win_r0.data(), wr.p, 8 * ((size_t)n_win + 1));
+        fc.add(h->win_r0.data(), wr, (size_t)n_win + 1);
     }
     HIPCHK(fc.run(s)); // the totals and the windows' first voxels / factors in one round trip
     h->info.n_planes = n_planes; h->info.n_voxels = V; h->info.n_factors = F;
@@ -1021,41 +1011,40 @@ int32_t voxmap_build_impl(lvba_voxmap_s *h, const lvba_scans_s *sc, int frame_be
     h->info.count_ms = now_ms() - t0; t0 = now_ms();
 
     // -- emission
-    DevBuf plane(s), vox_off(s), pose_idx(s), clusters(s), vox_label(s);
-    HIPCHK(plane.alloc(48 * (size_t)n_planes)); HIPCHK(vox_off.alloc(8 * ((size_t)V + 1)));
-    HIPCHK(pose_idx.alloc(4 * (size_t)F)); HIPCHK(clusters.alloc(80 * (size_t)F)); HIPCHK(vox_label.alloc(8 * (size_t)V));
-    vox_root_emit_kernel<<<grid_for(NS, 256), 256, 0, s>>>(NS, seg_root.as<uint32_t>(), root_seg.as<uint32_t>(), seg_frame.as<int32_t>(),
-                                                           segcl.as<double>(), rootinfo.as<uint32_t>(), n_vox.as<int32_t>(),
-                                                           plane0.as<double>(), plane_first.as<int32_t>(), vox_first.as<int32_t>(),
-                                                           fac_first.as<int64_t>(), plane.as<double>(), vox_off.as<int64_t>(),
-                                                           pose_idx.as<int32_t>(), clusters.as<double>(), vox_label.as<int32_t>());
+    DevArr<double> plane(s); DevArr<int64_t> vox_off(s); DevArr<int32_t> pose_idx(s); DevArr<double> clusters(s);
+    DevArr<int32_t> vox_label(s);
+    HIPCHK(plane.alloc(6 * (size_t)n_planes)); HIPCHK(vox_off.alloc((size_t)V + 1));
+    HIPCHK(pose_idx.alloc((size_t)F)); HIPCHK(clusters.alloc(10 * (size_t)F)); HIPCHK(vox_label.alloc(2 * (size_t)V));
+    vox_root_emit_kernel<<<grid_for(NS, 256), 256, 0, s>>>(NS, seg_root, root_seg, seg_frame, segcl, rootinfo, n_vox, plane0,
+                                                           plane_first, vox_first, fac_first, plane, vox_off, pose_idx, clusters,
+                                                           vox_label);
     HIPCHK(hipGetLastError());
     if (NRS > 0) {
-        sa.plane_first = plane_first.as<int32_t>(); sa.vox_first = vox_first.as<int32_t>(); sa.fac_first = fac_first.as<int64_t>();
-        sa.plane = plane.as<double>(); sa.vox_off = vox_off.as<int64_t>(); sa.pose_idx = pose_idx.as<int32_t>();
-        sa.clusters = clusters.as<double>(); sa.vox_label = vox_label.as<int32_t>();
+        sa.plane_first = plane_first; sa.vox_first = vox_first; sa.fac_first = fac_first;
+        sa.plane = plane; sa.vox_off = vox_off; sa.pose_idx = pose_idx;
+        sa.clusters = clusters; sa.vox_label = vox_label;
         vox_split_emit_kernel<<<NRS, 64, 0, s>>>(sa);
         HIPCHK(hipGetLastError());
     }
     if (ws && F > 0) { // pose indices relative to the window's first frame, as the window's own map would have them
-        vox_pose_rel_kernel<<<grid_for(F, 256), 256, 0, s>>>(F, pose_idx.as<int32_t>(), ws);
+        vox_pose_rel_kernel<<<grid_for(F, 256), 256, 0, s>>>(F, pose_idx, ws);
         HIPCHK(hipGetLastError());
     }
-    vox_close_offsets_kernel<<<1, 1, 0, s>>>(vox_off.as<int64_t>() + V, fac_first.as<int64_t>() + R);
+    vox_close_offsets_kernel<<<1, 1, 0, s>>>(vox_off + V, fac_first + R);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
     h->info.write_ms = now_ms() - t0;
 
-    h->d_root_key = (uint64_t *)root_key.release();
-    h->d_mask = (uint64_t *)mask.release();
-    h->d_rootinfo = (uint32_t *)rootinfo.release();
-    h->d_plane_first = (int32_t *)plane_first.release();
-    h->d_plane = (double *)plane.release();
-    h->d_vox_off = (int64_t *)vox_off.release();
-    h->d_pose_idx = (int32_t *)pose_idx.release();
-    h->d_vox_label = (int32_t *)vox_label.release();
-    h->d_clusters = (double *)clusters.release();
-    h->d_win_r0 = (int64_t *)wr.release();
+    h->d_root_key = root_key.release();
+    h->d_mask = mask.release();
+    h->d_rootinfo = rootinfo.release();
+    h->d_plane_first = plane_first.release();
+    h->d_plane = plane.release();
+    h->d_vox_off = vox_off.release();
+    h->d_pose_idx = pose_idx.release();
+    h->d_vox_label = vox_label.release();
+    h->d_clusters = clusters.release();
+    h->d_win_r0 = wr.release();
     return LVBA_OK;
 }
 
@@ -1224,21 +1213,19 @@ static int32_t find_planes_impl(lvba_voxmap_t h, int64_t n, const int32_t *subma
         return LVBA_OK;
     }
     HIPCHK(hipSetDevice(h->device));
-    DevBuf dX(h->stream), dpl(h->stream), dval(h->stream), dsub(h->stream);
-    HIPCHK(dX.alloc(24 * (size_t)n)); HIPCHK(dpl.alloc(32 * (size_t)n)); HIPCHK(dval.alloc((size_t)n));
-    HIPCHK(hipMemcpyAsync(dX.p, X, 24 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    DevArr<double> dX(h->stream), dpl(h->stream); DevArr<uint8_t> dval(h->stream); DevArr<int32_t> dsub(h->stream);
+    HIPCHK(dX.alloc(3 * (size_t)n)); HIPCHK(dpl.alloc(4 * (size_t)n)); HIPCHK(dval.alloc((size_t)n));
+    HIPCHK(hipMemcpyAsync(dX, X, dX.bytes(3 * (size_t)n), hipMemcpyHostToDevice, h->stream));
     if (submap) {
-        HIPCHK(dsub.alloc(4 * (size_t)n));
-        HIPCHK(hipMemcpyAsync(dsub.p, submap, 4 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(dsub.alloc((size_t)n));
+        HIPCHK(hipMemcpyAsync(dsub, submap, dsub.bytes((size_t)n), hipMemcpyHostToDevice, h->stream));
     }
-    vox_lookup_kernel<<<grid_for(n, 256), 256, 0, h->stream>>>(n, dX.as<double>(), h->opts.voxel_size, h->info.n_roots,
-                                                               h->d_root_key, h->d_mask, h->d_rootinfo, h->d_plane_first,
-                                                               h->d_plane, submap ? dsub.as<int32_t>() : nullptr,
-                                                               h->window_size > 0 ? h->d_win_r0 : nullptr, h->n_windows,
-                                                               dpl.as<double>(), dval.as<uint8_t>());
+    vox_lookup_kernel<<<grid_for(n, 256), 256, 0, h->stream>>>(n, dX, h->opts.voxel_size, h->info.n_roots, h->d_root_key, h->d_mask,
+                                                               h->d_rootinfo, h->d_plane_first, h->d_plane, submap ? dsub : nullptr,
+                                                               h->window_size > 0 ? h->d_win_r0 : nullptr, h->n_windows, dpl, dval);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(plane, dpl.p, 32 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(valid, dval.p, (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(plane, dpl, dpl.bytes(4 * (size_t)n), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(valid, dval, dval.bytes((size_t)n), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return LVBA_OK;
 }

@@ -313,8 +313,8 @@ int32_t stage_lm_batched(WindowCall &c, bool &done)
     lvba::hvec<int64_t> off((size_t)V + 1, 0);
     lvba::hvec<int32_t> idx((size_t)F);
     lvba::hvec<double> x(12 * (size_t)pose_off[(size_t)G]);
-    DevBuf d_clu(c.s);
-    HIPCHK(d_clu.alloc(80 * (size_t)F));
+    DevArr<double> d_clu(c.s);
+    HIPCHK(d_clu.alloc(10 * (size_t)F));
     lvba::hvec<int64_t> joff; // with a joint map: its whole CSR structure in ONE pair of copies instead of two per window
     lvba::hvec<int32_t> jidx;
     if (c.joint_map) {
@@ -336,7 +336,7 @@ int32_t stage_lm_batched(WindowCall &c, bool &done)
             TRY(lvba_voxmap_export(R.map, o1.data(), idx.data() + f0, nullptr, nullptr)); // CSR structure to the host, clusters stay in HBM
         for (int64_t a = 0; a <= nv; ++a) off[(size_t)(v0 + a)] = f0 + (o1[(size_t)a] - o1[0]);
         for (int64_t f = f0; f < f0 + nf; ++f) idx[(size_t)f] += pose_off[(size_t)k];
-        HIPCHK(hipMemcpyAsync(d_clu.as<double>() + 10 * f0, lvba_voxmap_clusters(R.map), 80 * (size_t)nf, hipMemcpyDeviceToDevice, c.s));
+        HIPCHK(hipMemcpyAsync(d_clu + 10 * f0, lvba_voxmap_clusters(R.map), d_clu.bytes(10 * (size_t)nf), hipMemcpyDeviceToDevice, c.s));
         memcpy(x.data() + 12 * (size_t)pose_off[(size_t)k], R.x.data(), 96 * (size_t)R.info.n_frames);
     }
     HIPCHK(hipStreamSynchronize(c.s));
@@ -345,7 +345,7 @@ int32_t stage_lm_batched(WindowCall &c, bool &done)
     auto mk = [&](const char *what) { if (tm) { const double t = now_ms(); fprintf(stderr, "[window_ba LM] %-16s %.3f ms\n", what, t - tk); tk = t; } };
     if (tm) fprintf(stderr, "[window_ba LM] %-16s %.3f ms\n", "export + concat", tk - t0);
     lvba_balm_t b = nullptr;
-    TRY(balm_create_dev_trusted(pose_off[(size_t)G], V, off.data(), idx.data(), d_clu.as<double>(), c.sc->device, &b));
+    TRY(balm_create_dev_trusted(pose_off[(size_t)G], V, off.data(), idx.data(), d_clu, c.sc->device, &b));
     struct Guard { lvba_balm_t b; ~Guard() { if (b) lvba_balm_destroy(b); } } guard{b};
     mk("create");
     TRY(lvba_balm_set_groups(b, G, pose_off.data(), vox_off.data()));
@@ -448,31 +448,30 @@ int32_t merge_run(const WindowCall &c, int w0, int w1, hipStream_t s, DevCloud *
         fprintf(stderr, "[window_ba merge] %-18s %.3f ms\n", what, t - tj);
         tj = t;
     };
-    DevBuf d_rel(s), d_code(s), d_at(s), d_cnt(s), merged(s), d_err(s), key(s), d2(s), idx(s), d_part(s);
-    DevBuf key_s(s), order(s), flag(s), excl(s), pick(s);
+    DevArr<double> d_rel(s); DevArr<uint32_t> d_code(s); DevArr<int64_t> d_at(s); DevArr<uint32_t> d_cnt(s);
+    DevArr<float> merged(s); DevArr<int> d_err(s); DevArr<uint64_t> key(s); DevArr<double> d2(s); DevArr<uint32_t> idx(s);
+    DevArr<int> d_part(s);
+    DevArr<uint64_t> key_s(s); DevArr<uint32_t> order(s), flag(s), excl(s), pick(s);
     const int64_t n_slots = key_range_slots(P, 256);
-    HIPCHK(d_rel.alloc(96 * (size_t)nf)); HIPCHK(merged.alloc(12 * (size_t)P));
-    HIPCHK(lvba::copy_h2d(d_rel.p, c.rel.data() + 12 * (size_t)f0, 96 * (size_t)nf)); // (pageable sources: synchronous copies)
+    HIPCHK(d_rel.alloc(12 * (size_t)nf)); HIPCHK(merged.alloc(3 * (size_t)P));
+    HIPCHK(d_rel.upload(c.rel.data() + 12 * (size_t)f0, 12 * (size_t)nf)); // (pageable sources: synchronous copies)
     if (down) {
-        HIPCHK(d_code.alloc(4 * (size_t)nw)); HIPCHK(d_at.alloc(8 * ((size_t)G + 1))); HIPCHK(d_cnt.alloc(4 * ((size_t)G + 1)));
-        HIPCHK(d_err.alloc(28)); HIPCHK(key.alloc(8 * (size_t)P)); HIPCHK(d2.alloc(8 * (size_t)P)); HIPCHK(idx.alloc(4 * (size_t)P));
-        HIPCHK(d_part.alloc(24 * (size_t)n_slots));
-        HIPCHK(lvba::copy_h2d(d_code.p, code.data(), 4 * (size_t)nw));
-        HIPCHK(lvba::copy_h2d(d_at.p, at.data(), 8 * ((size_t)G + 1)));
-        HIPCHK(hipMemsetAsync(d_err.p, 0, 28, s));
+        HIPCHK(d_code.alloc((size_t)nw)); HIPCHK(d_at.alloc((size_t)G + 1)); HIPCHK(d_cnt.alloc((size_t)G + 1));
+        HIPCHK(d_err.alloc(7)); HIPCHK(key.alloc((size_t)P)); HIPCHK(d2.alloc((size_t)P)); HIPCHK(idx.alloc((size_t)P));
+        HIPCHK(d_part.alloc(6 * (size_t)n_slots)); HIPCHK(d_code.upload(code.data(), (size_t)nw));
+        HIPCHK(d_at.upload(at.data(), (size_t)G + 1)); HIPCHK(d_err.zero_async(7));
     }
     mark("alloc + tables");
-    wba_merge_kernel<<<grid_for(P, 256), 256, 0, s>>>(P, sc->d_pts + 3 * p_begin, sc->d_frame_off + f0, nf, d_rel.as<double>(),
-                                                      c.o.anchor_leaf, merged.as<float>(), down ? key.as<uint64_t>() : nullptr,
-                                                      d2.as<double>(), idx.as<uint32_t>(), d_err.as<int>(), d_part.as<int>());
+    wba_merge_kernel<<<grid_for(P, 256), 256, 0, s>>>(P, sc->d_pts + 3 * p_begin, sc->d_frame_off + f0, nf, d_rel, c.o.anchor_leaf,
+                                                      merged, down ? key : nullptr, d2, idx, d_err, d_part);
     HIPCHK(hipGetLastError());
     int64_t n_all = P_live;
     if (down) {
-        key_range_reduce_kernel<<<key_range_reduce_grid(n_slots), 256, 0, s>>>(n_slots, d_part.as<int>(), d_err.as<int>() + 1);
+        key_range_reduce_kernel<<<key_range_reduce_grid(n_slots), 256, 0, s>>>(n_slots, d_part, d_err + 1);
         HIPCHK(hipGetLastError());
         int h_err[7] = {0}; // [0] error flag, [1..6] range of the biased key components
         HIPCHK(hipStreamSynchronize(s));
-        HIPCHK(lvba::copy_d2h(h_err, d_err.p, 28));
+        HIPCHK(d_err.download(h_err, 7));
         if (h_err[0]) // (a run of several windows is retried one window at a time, so that the message names the window)
             return lvba_fail(LVBA_ERR_ARG, "window %d: a merged point is non-finite or outside +-2^20 anchor leaves", w0);
         mark("merge + range");
@@ -482,34 +481,32 @@ int32_t merge_run(const WindowCall &c, int w0, int w1, hipStream_t s, DevCloud *
         const int cbits = G < nw ? 32 - __builtin_clz((unsigned)G) : (G > 1 ? 32 - __builtin_clz((unsigned)(G - 1)) : 0);
         const unsigned bits = (unsigned)(kp.total + cbits);
         if (bits > 64) return lvba_fail(LVBA_ERR_UNSUPPORTED, "windows [%d,%d): %u key + window bits", w0, w1, bits);
-        HIPCHK(key_s.alloc(8 * (size_t)P)); HIPCHK(order.alloc(4 * (size_t)P)); HIPCHK(flag.alloc(4 * ((size_t)P_live + 1)));
-        HIPCHK(excl.alloc(4 * ((size_t)P_live + 1))); HIPCHK(pick.alloc(4 * (size_t)P_live));
+        HIPCHK(key_s.alloc((size_t)P)); HIPCHK(order.alloc((size_t)P)); HIPCHK(flag.alloc((size_t)P_live + 1));
+        HIPCHK(excl.alloc((size_t)P_live + 1)); HIPCHK(pick.alloc((size_t)P_live));
         if (bits <= 32) {
-            DevBuf k32(s);
-            HIPCHK(k32.alloc(4 * (size_t)P));
-            wba_compress_win_kernel<uint32_t><<<grid_for(P, 256), 256, 0, s>>>(P, key.as<uint64_t>(), sc->d_frame_off + f0, nf, c.w,
-                                                                               d_code.as<uint32_t>(), kp, k32.as<uint32_t>());
+            DevArr<uint32_t> k32(s);
+            HIPCHK(k32.alloc((size_t)P));
+            wba_compress_win_kernel<uint32_t><<<grid_for(P, 256), 256, 0, s>>>(P, key, sc->d_frame_off + f0, nf, c.w, d_code, kp,
+                                                                               k32);
             HIPCHK(hipGetLastError());
-            TRY(sort_pairs(s, k32.as<uint32_t>(), key_s.as<uint32_t>(), idx.as<uint32_t>(), order.as<uint32_t>(), (size_t)P, bits));
-            wba_pick_kernel<uint32_t><<<grid_for(P_live, 256), 256, 0, s>>>(P_live, key_s.as<uint32_t>(), order.as<uint32_t>(), d2.as<double>(),
-                                                                            flag.as<uint32_t>(), pick.as<uint32_t>());
+            // key_s.as<uint32_t>(): the sorted 32-bit keys lie in the front half of the 64-bit buffer
+            TRY(sort_pairs<uint32_t>(s, k32, key_s.as<uint32_t>(), idx, order, (size_t)P, bits));
+            wba_pick_kernel<uint32_t><<<grid_for(P_live, 256), 256, 0, s>>>(P_live, key_s.as<uint32_t>(), order, d2, flag, pick);
         } else {
-            wba_compress_win_kernel<uint64_t><<<grid_for(P, 256), 256, 0, s>>>(P, key.as<uint64_t>(), sc->d_frame_off + f0, nf, c.w,
-                                                                               d_code.as<uint32_t>(), kp, key.as<uint64_t>());
+            wba_compress_win_kernel<uint64_t><<<grid_for(P, 256), 256, 0, s>>>(P, key, sc->d_frame_off + f0, nf, c.w, d_code, kp,
+                                                                               key);
             HIPCHK(hipGetLastError());
-            TRY(sort_pairs(s, key.as<uint64_t>(), key_s.as<uint64_t>(), idx.as<uint32_t>(), order.as<uint32_t>(), (size_t)P, bits));
-            wba_pick_kernel<uint64_t><<<grid_for(P_live, 256), 256, 0, s>>>(P_live, key_s.as<uint64_t>(), order.as<uint32_t>(), d2.as<double>(),
-                                                                            flag.as<uint32_t>(), pick.as<uint32_t>());
+            TRY(sort_pairs<uint64_t>(s, key, key_s, idx, order, (size_t)P, bits));
+            wba_pick_kernel<uint64_t><<<grid_for(P_live, 256), 256, 0, s>>>(P_live, key_s, order, d2, flag, pick);
         }
         HIPCHK(hipGetLastError());
         mark("sort + pick");
-        HIPCHK(hipMemsetAsync(flag.as<uint32_t>() + P_live, 0, 4, s));
-        TRY(scan_excl<uint32_t>(s, flag.as<uint32_t>(), excl.as<uint32_t>(), (size_t)P_live + 1));
-        wba_bounds_kernel<<<grid_for(G + 1, 256), 256, 0, s>>>(G + 1, d_at.as<int64_t>(), excl.as<uint32_t>(), d_cnt.as<uint32_t>());
+        HIPCHK(flag.zero_async(1, P_live)); TRY(scan_excl<uint32_t>(s, flag, excl, (size_t)P_live + 1));
+        wba_bounds_kernel<<<grid_for(G + 1, 256), 256, 0, s>>>(G + 1, d_at, excl, d_cnt);
         HIPCHK(hipGetLastError());
         lvba::hvec<uint32_t> cnt((size_t)G + 1);
         HIPCHK(hipStreamSynchronize(s));
-        HIPCHK(lvba::copy_d2h(cnt.data(), d_cnt.p, 4 * ((size_t)G + 1)));
+        HIPCHK(d_cnt.download(cnt.data(), (size_t)G + 1));
         mark("scan + counts");
         n_all = cnt[(size_t)G];
         for (int wi = w0, g = 0; wi < w1; ++wi)
@@ -520,14 +517,13 @@ int32_t merge_run(const WindowCall &c, int w0, int w1, hipStream_t s, DevCloud *
     mark("hipMalloc (cloud)");
     hipError_t e = hipSuccess;
     if (down) {
-        wba_compact_kernel<<<grid_for(P_live, 256), 256, 0, s>>>(P_live, flag.as<uint32_t>(), excl.as<uint32_t>(), pick.as<uint32_t>(),
-                                                                 merged.as<float>(), pts);
+        wba_compact_kernel<<<grid_for(P_live, 256), 256, 0, s>>>(P_live, flag, excl, pick, merged, pts);
         e = hipGetLastError();
     } else
         for (int wi = w0, g = 0; wi < w1 && e == hipSuccess; ++wi)
             if (!c.res[(size_t)wi].info.skipped) {
                 const int64_t src = sc->frame_off[(size_t)c.start(wi)] - p_begin;
-                e = hipMemcpyAsync(pts + 3 * at[(size_t)g], merged.as<float>() + 3 * src, 12 * (size_t)count[wi - w0], hipMemcpyDeviceToDevice, s);
+                e = hipMemcpyAsync(pts + 3 * at[(size_t)g], merged + 3 * src, merged.bytes(3 * (size_t)count[wi - w0]), hipMemcpyDeviceToDevice, s);
                 ++g;
             }
     if (e == hipSuccess) e = hipStreamSynchronize(s);
