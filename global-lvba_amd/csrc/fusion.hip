@@ -28,6 +28,7 @@
 #include "mempool.h"
 #include "voxel_internal.h"
 #include "segments.h"
+#include "image_set.h"
 #include "tracks_device.h"
 #include "fusion_device.h"
 #include "../../include/lvba_hip.h"
@@ -277,11 +278,16 @@ extern "C" int32_t lvba_fuse_tracks(int32_t device, lvba_depth_t depth, int32_t 
     if (n_images < 1 || n_tracks < 0 || !Rcw || !tcw || !intr || !obs_off || !status || !X || !mean_reproj)
         return lvba_fail(LVBA_ERR_ARG, "null argument or n_images < 1");
     if (n_tracks == 0) return LVBA_OK;
-    const int64_t O = obs_off[n_tracks] - obs_off[0];
-    if (obs_off[0] != 0 || O < 0 || (O > 0 && (!obs_img || !obs_uv || !kept))) return lvba_fail(LVBA_ERR_ARG, "bad observation arrays");
+    TRY(check_offsets("obs_off", "track", n_tracks, obs_off)); // the kernel walks [obs_off[t], obs_off[t + 1]) of O-element arrays
+    const int64_t O = obs_off[n_tracks];
+    if (O > 0 && (!obs_img || !obs_uv || !kept)) return lvba_fail(LVBA_ERR_ARG, "bad observation arrays");
     lvba_fuse_opts o;
     lvba_fuse_default_opts(&o);
     if (opts) o = *opts;
+    if (o.obser_thr < 1) return lvba_fail(LVBA_ERR_ARG, "obser_thr = %d (>= 1)", o.obser_thr); // fuse_track divides by a count >= obser_thr
+    if (!(o.min_view_angle_deg >= 0.0 && o.min_view_angle_deg <= 180.0))
+        return lvba_fail(LVBA_ERR_ARG, "min_view_angle_deg = %g (0..180)", o.min_view_angle_deg);
+    if (!(o.reproj_mean_thr_px >= 0.0)) return lvba_fail(LVBA_ERR_ARG, "reproj_mean_thr_px = %g (>= 0)", o.reproj_mean_thr_px);
     if (depth) {
         if (depth->n_images != n_images) return lvba_fail(LVBA_ERR_ARG, "depth handle holds %d images, %d cameras given", depth->n_images, n_images);
         device = depth->device;

@@ -13,6 +13,7 @@
 #include <stdint.h>
 #include "lvba_common.h"
 #include "mempool.h"
+#include "image_set.h"
 #include "tracks_device.h"
 
 using namespace lvba;
@@ -52,8 +53,9 @@ extern "C" int32_t lvba_triangulate_tracks(int32_t device, int32_t n_cams, int64
     if (n_cams < 1 || n_tracks < 0 || !obs_off || !Rcw || !tcw || !intr || !X || !mean_reproj || !count || !ok)
         return lvba_fail(LVBA_ERR_ARG, "null argument or n_cams < 1");
     if (n_tracks == 0) return LVBA_OK;
-    const int64_t O = obs_off[n_tracks] - obs_off[0];
-    if (obs_off[0] != 0 || O < 0 || (O > 0 && (!obs_cam || !obs_uv))) return lvba_fail(LVBA_ERR_ARG, "bad observation arrays");
+    TRY(check_offsets("obs_off", "track", n_tracks, obs_off)); // the kernel walks [obs_off[t], obs_off[t + 1]) of O-element arrays
+    const int64_t O = obs_off[n_tracks];
+    if (O > 0 && (!obs_cam || !obs_uv)) return lvba_fail(LVBA_ERR_ARG, "bad observation arrays");
     TRY(lvba::check_device(device));
     HIPCHK(hipSetDevice(device));
     ScopedStream sg;

@@ -596,7 +596,9 @@ int32_t lvba_voxmap_find_planes(lvba_voxmap_t h, int64_t n, const double *X, dou
  *   error of X over the track.  Tracks are CSR (obs_off [n+1] from 0, obs_cam [O], obs_uv [O][2]), one observation per
  *   image as the reference's selected_ids holds them; Rcw [M][9] row-major and tcw [M][3] are T_cam<-world.
  *   ok[i] = 1 iff the track has >= 4 observations, >= 8 DLT rows, |Xh.w| >= 1e-12, finite X and >= 4 valid reprojections
- *   (mean_reproj = +inf otherwise; the caller applies its own reproj_mean_thr_px_ as at :1143-1146). */
+ *   (mean_reproj = +inf otherwise; the caller applies its own reproj_mean_thr_px_ as at :1143-1146).
+ *   LVBA_ERR_ARG, before any device work and with the outputs untouched: obs_off does not start at 0 or decreases somewhere
+ *   (the kernel would walk observations past obs_off[n_tracks]). */
 int32_t lvba_triangulate_tracks(int32_t device, int32_t n_cams, int64_t n_tracks, const int64_t *obs_off,
                                 const int32_t *obs_cam, const double *obs_uv, const double *Rcw, const double *tcw,
                                 const double intr[8], double *X, double *mean_reproj, int32_t *count, uint8_t *ok);
@@ -621,7 +623,13 @@ int32_t lvba_triangulate_tracks(int32_t device, int32_t n_cams, int64_t n_tracks
  *   std::unordered_map<int,int> of images (unique_id :994, best_id :1051, kept_id_depth :1064), images are visited in the order libstdc++ gives that
  *   container for the reference's reserve() and insertion sequence (bucket = key mod the rehash policy's prime, a new node
  *   goes to the front of its bucket and a new bucket to the front of the list: csrc/tracks_device.h umap_order), because
- *   the greedy view-angle filter's survivors depend on it. */
+ *   the greedy view-angle filter's survivors depend on it.
+ *   An observation whose pixel is NaN or +-inf has no depth point (the reference's fetchDepthBilinear would index with it,
+ *   which is undefined; csrc/fusion_device.h depth_world_point) and, having no undistorted point, adds no DLT rows; it still
+ *   counts as the observation of its image.
+ *   LVBA_ERR_ARG, before any device work and with the outputs untouched: obs_off does not start at 0 or decreases somewhere;
+ *   obser_thr < 1; min_view_angle_deg NaN or outside [0, 180]; reproj_mean_thr_px NaN or negative.  Image ids outside
+ *   [0, n_images) are no error: such observations are skipped. */
 typedef struct lvba_depth_s *lvba_depth_t;
 int32_t lvba_depth_render(lvba_scans_t scans, const double *scan_poses, const double *scan_times, int32_t n_images,
                           const double *image_times, const double *Rcw, const double *tcw, const double intr[8],

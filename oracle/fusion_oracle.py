@@ -95,6 +95,8 @@ def fetch_depth_bilinear(depth, u, v):
     """utils.hpp:246-275 for a CV_32FC1 image; u, v are float (the keypoint's fields).  Returns d > 0 or None."""
     u, v = f32(u), f32(v)
     h, w = depth.shape
+    if not (np.isfinite(u) and np.isfinite(v)):     # undefined upstream (a NaN passes the range check and indexes the image);
+        return None                                 # the device rule: no depth point (csrc/fusion_device.h depth_world_point)
     if u < 0 or v < 0 or u >= w - 1 or v >= h - 1:
         return None
     x, y = int(np.floor(u)), int(np.floor(v))
@@ -142,8 +144,9 @@ def umap_order(keys, reserve_n):
     return order
 
 
-def _view_filter(ids, points, Cw, cos_min):
-    """ids: [(img, comp_idx)], points: comp_idx -> 3D point (or one point for all).  Greedy filter of :1052-1080 / :1124-1150."""
+def _view_filter(ids, points, Cw, cos_min, margins=None):
+    """ids: [(img, comp_idx)], points: comp_idx -> 3D point (or one point for all).  Greedy filter of :1052-1080 / :1124-1150.
+    margins: a list that receives every min_dot - cos_min the filter compared."""
     kept, dirs = [], []
     for img, ci in ids:
         d = (points[ci] if isinstance(points, dict) else points) - Cw[img]
@@ -152,16 +155,26 @@ def _view_filter(ids, points, Cw, cos_min):
             continue
         d = d / n
         min_dot = min([float(d @ e) for e in dirs], default=1.0)
+        if dirs and margins is not None:
+            margins.append(min_dot - cos_min)
         if not dirs or min_dot <= cos_min:
             kept.append((img, ci))
             dirs.append(d)
     return kept
 
 
-def fuse_track(component_img, component_uv, depth, Rcw, tcw, intr, obser_thr=3, min_view_angle_deg=8.0, reproj_thr=3.0):
+def fuse_track(component_img, component_uv, depth, Rcw, tcw, intr, obser_thr=3, min_view_angle_deg=8.0, reproj_thr=3.0,
+               trace=None):
     """One BFS component (observations in BFS order; uv float32 keypoint coordinates).
-    Returns (status, X, mean_reproj, kept_mask): status 0 dropped, 1 triangulated, 2 depth-fused."""
+    Returns (status, X, mean_reproj, kept_mask): status 0 dropped, 1 triangulated, 2 depth-fused.
+    trace: a dict that receives how close every decision was -- m_depth / m_tri (the candidates' mean reprojection errors,
+    None where a candidate never got one), n_kept_depth / n_kept_tri (what the two view filters kept), dot_margins (every
+    min_dot - cos_min a view filter compared) and dist_margins (every anchor distance - 0.12).  The results do not depend on it."""
     n = len(component_img)
+    dot_margins, dist_margins = [], []
+    if trace is not None:
+        trace.update(m_depth=None, m_tri=None, n_kept_depth=None, n_kept_tri=None, dot_margins=dot_margins,
+                     dist_margins=dist_margins)
     kept_mask = np.zeros(n, np.uint8)
     none = (0, np.zeros(3), np.inf, kept_mask)
     if n < obser_thr:
@@ -199,7 +212,9 @@ def fuse_track(component_img, component_uv, depth, Rcw, tcw, intr, obser_thr=3, 
         valid = sorted(pts)
         if len(valid) >= obser_thr:
             anchor = pts[valid[0]]
-            inl = [ci for ci in valid if np.linalg.norm(pts[ci] - anchor) < 0.12]
+            dist = [float(np.linalg.norm(pts[ci] - anchor)) for ci in valid]
+            dist_margins.extend(d - 0.12 for d in dist)
+            inl = [ci for ci, d in zip(valid, dist) if d < 0.12]
             best = {}
             for ci in inl:
                 best.setdefault(int(component_img[ci]), ci)
@@ -210,25 +225,33 @@ def fuse_track(component_img, component_uv, depth, Rcw, tcw, intr, obser_thr=3, 
                 for _, ci in best:
                     X_depth = X_depth + pts[ci]
                 X_depth = X_depth / float(len(best))
-                kd = _view_filter(best, pts, Cw, cos_min)
+                kd = _view_filter(best, pts, Cw, cos_min, dot_margins)
+                if trace is not None:
+                    trace["n_kept_depth"] = len(kd)
                 if len(kd) >= obser_thr:
                     kdo = [kd[i] for i in umap_order([im for im, _ in kd], len(best))]   # kept_id_depth.reserve(best_id.size())
                     m, cnt = to.mean_reproj(intr, R3, t3, X_depth, [im for im, _ in kdo], [uv64[ci] for _, ci in kdo], obser_thr)
                     if m is not None:
                         m_depth, kept_depth = m, [ci for _, ci in kd]
+                        if trace is not None:
+                            trace["m_depth"] = m
                         depth_ok = m <= reproj_thr
     # ---- triangulation candidate (:1108-1160)
     tri_ok, X_tri, m_tri, kept_tri = False, np.zeros(3), np.inf, []
     if len(unique) >= 4:
         ok, Xs, _, _ = to.triangulate_track(intr, R3, t3, [im for im, _ in unique], [uv64[ci] for _, ci in unique])
         if ok:
-            kt = _view_filter(unique, Xs, Cw, cos_min)
+            kt = _view_filter(unique, Xs, Cw, cos_min, dot_margins)
             kept_tri = [ci for _, ci in kt]
+            if trace is not None:
+                trace["n_kept_tri"] = len(kt)
             if len(kt) >= 4:
                 kto = [kt[i] for i in umap_order([im for im, _ in kt], len(unique))]     # kept_id_tri.reserve(unique_id.size())
                 ok2, X2, m2, _ = to.triangulate_track(intr, R3, t3, [im for im, _ in kto], [uv64[ci] for _, ci in kto])
                 if ok2:
                     X_tri, m_tri = X2, m2
+                    if trace is not None:
+                        trace["m_tri"] = m2
                     tri_ok = m2 <= reproj_thr
     # ---- selection (:1162-1200)
     if depth_ok and tri_ok:
