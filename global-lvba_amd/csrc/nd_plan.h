@@ -18,7 +18,9 @@
 #include "host_arena.h"
 #include "ordering.h"
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
+#include <cstdlib>
 #include <vector>
 
 namespace lvba {
