@@ -45,6 +45,7 @@ SYMBOLS = [
     "lvba_sift_default_opts", "lvba_sift_tile_width", "lvba_sift_blur_taps", "lvba_sift_extract", "lvba_sift_profile", "lvba_sift_pyramid",
     "lvba_sift_candidates",
     "lvba_resect_default_opts", "lvba_resect_images", "lvba_resect_hypotheses", "lvba_resect_score", "lvba_resect_lift",
+    "lvba_calib_default_opts", "lvba_calib_extrinsic", "lvba_calib_linearize",
 ]
 
 OK, ERR_ARG, ERR_DEVICE, ERR_NOMEM, ERR_UNSUPPORTED, ERR_DIST, ERR_STATE = 0, -1, -2, -3, -4, -5, -6
@@ -277,6 +278,13 @@ class ResectOpts(Struct):
                 ("max_error_px", C.c_double), ("seed", C.c_uint64)]
 
 
+class CalibOpts(Struct):
+    """lvba_calib_opts"""
+    _fields_ = [("max_iterations", C.c_int32), ("loss_kind", C.c_int32), ("min_records", C.c_int64), ("loss_scale_px", C.c_double),
+                ("max_error_px", C.c_double), ("min_eig_ratio", C.c_double), ("eps_rot", C.c_double), ("eps_trans", C.c_double),
+                ("reserved", C.c_int64)]
+
+
 class SiftOpts(Struct):
     """lvba_sift_opts"""
     _fields_ = [("first_octave", C.c_int32), ("n_intervals", C.c_int32), ("sigma0", C.c_double), ("dog_threshold", C.c_double),
@@ -359,6 +367,7 @@ STRUCTS = {
     "lvba_match_opts": MatchOpts, "lvba_covis_opts": CovisOpts, "lvba_trackgraph_info": TrackGraphInfo,
     "lvba_verify_opts": VerifyOpts, "lvba_sift_opts": SiftOpts, "lvba_dynamic_opts": DynamicOpts,
     "lvba_dynamic_summary": DynamicSummary, "lvba_resect_opts": ResectOpts,
+    "lvba_calib_opts": CalibOpts,
 }
 
 _INTS = (C.c_int32, C.c_int64, C.c_uint64)
@@ -619,6 +628,11 @@ def load():
                                            C.c_void_p, C.c_void_p]
     lib.lvba_resect_score.argtypes = [C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
     lib.lvba_resect_lift.argtypes = [H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.lvba_calib_default_opts.argtypes = [C.POINTER(CalibOpts)]
+    _calib = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+              C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(CalibOpts)]
+    lib.lvba_calib_extrinsic.argtypes = _calib + [C.c_void_p] * 11
+    lib.lvba_calib_linearize.argtypes = _calib + [C.c_void_p] * 5
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if name.endswith("_default_opts") or name in ("lvba_depth_destroy", "lvba_colorize_destroy"):     # these return void

@@ -249,6 +249,13 @@ class PinnedCache {
     std::map<void *, size_t> owner_;
 };
 
+// The iteration words of a lock-step solver (register.hip, calib.hip) in the host's pinned memory: acquired from the cache by the
+// caller, given back when the call ends
+struct PinnedWords {
+    int32_t *p = nullptr;
+    ~PinnedWords() { if (p) PinnedCache::get().release(p); }
+};
+
 // Host <-> device copies of set-up tables from / to the caller's or the library's PAGEABLE memory.  The runtime moves small
 // transfers through its own staging buffers, but pins the user pages for transfers from 4 MB up (GPU_PINNED_MIN_XFER_SIZE) and
 // unpins them afterwards; every set-up table is a temporary std::vector that is freed right after.  Unmapping host memory the

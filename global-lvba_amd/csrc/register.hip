@@ -148,11 +148,6 @@ int32_t check_opts(const lvba_register_opts *opts, lvba_register_opts &o, RegPar
     return LVBA_OK;
 }
 
-struct PinnedWords { // the iteration words in the host's pinned memory
-    int32_t *p = nullptr;
-    ~PinnedWords() { if (p) PinnedCache::get().release(p); }
-};
-
 // All entry points.  sums_only: one linearisation, H / g / cost / inliers out; else the iteration, poses_out / information /
 // results out.  submaps: the map is a submap set and job k works against submap[k] (else a map of one window, submap unused).
 int32_t reg_run(lvba_voxmap_t map, lvba_scans_t sc, int32_t n, const int32_t *frames, const int32_t *submap, bool submaps,

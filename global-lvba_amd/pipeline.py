@@ -746,6 +746,82 @@ def check_cameras(keypoints, pairs, matches, depth, Rcw, tcw, intr, device=0, **
 _check_cameras = check_cameras    # run_full_pipeline's keyword of the same name shadows the function there
 
 
+def calibration_records_from_points(keypoints, pairs, matches, points, Rcw, tcw):
+    """The records of calib.refine_extrinsic that the matches hold, from lifted points (one [n_i, 3] array per image, NaN rows
+    where a keypoint has none, lifted at the poses Rcw, tcw = T_cam<-world): every match whose partner keypoint has a point is a
+    record (own pixel, the partner's point in the partner's camera frame).  Both directions of a pair are used, in the order of
+    correspondences_from_matches: the order of `pairs`, within a pair its first image's side, then its second's, then match order;
+    every direction is a row of the directed pair table.  Returns (records, (img_a, img_b)): records = dict(pair int32 [n], uv
+    float32 [n, 2], Xb float64 [n, 3]), img_a the image the pixel is in, img_b the image the point was lifted in."""
+    Rcw, tcw = np.asarray(Rcw, np.float64).reshape(-1, 3, 3), np.asarray(tcw, np.float64).reshape(-1, 3)
+    pr, uv, Xb, ia, ib = [], [], [], [], []
+    for (a, b), m in zip(pairs, matches):
+        m = np.asarray(m, np.int64).reshape(-1, 2)
+        for own, other, co, cp in ((int(a), int(b), 0, 1), (int(b), int(a), 1, 0)):
+            P = np.asarray(points[other], np.float64).reshape(-1, 3)[m[:, cp]]
+            has = ~np.isnan(P[:, 0])
+            pr.append(np.full(int(has.sum()), len(ia), np.int32))
+            uv.append(np.asarray(keypoints[own], np.float32).reshape(-1, 2)[m[has, co]])
+            Xb.append(P[has] @ Rcw[other].T + tcw[other])      # back into its source camera, with the pose it was lifted with
+            ia.append(own); ib.append(other)
+    records = dict(pair=np.concatenate(pr) if pr else np.zeros(0, np.int32),
+                   uv=np.concatenate(uv).reshape(-1, 2) if uv else np.zeros((0, 2), np.float32),
+                   Xb=np.concatenate(Xb).reshape(-1, 3) if Xb else np.zeros((0, 3)))
+    return records, (np.asarray(ia, np.int32), np.asarray(ib, np.int32))
+
+
+def calibration_records(keypoints, pairs, matches, depth, Rcw, tcw, intr):
+    """calibration_records_from_points of the keypoints lifted through their images' depth images (resect.lift_keypoints; depth: a
+    visual.DepthImages at the poses Rcw, tcw = T_cam<-world)."""
+    from . import resect as RS
+    uv = [np.asarray(k, np.float32).reshape(-1, 2) for k in keypoints]
+    points = RS.lift_keypoints(depth, uv, intr, Rcw, tcw)
+    return calibration_records_from_points(uv, pairs, matches, points, Rcw, tcw)
+
+
+def calibrate_extrinsic(keypoints, pairs, matches, body_poses, Rci, tci, intr, depth=None, render=None, rounds=1, starts=None, device=0,
+                        **opts):
+    """What the extrinsic T_cam<-imu should be instead of (Rci, tci), from the matches and the LiDAR depths (calib.refine_extrinsic;
+    DESIGN.md §10o).  body_poses [M, 12]: T_world<-imu at the image times (the LiDAR-derived image poses).  depth: a
+    visual.DepthImages rendered at camera_from_imu(body_poses, Rci, tci), used by the first round and left to the caller; render:
+    a callable (Rcw, tcw) -> visual.DepthImages, called where a round has no depth images (every round after the first: the depth
+    under a keypoint was read through the old extrinsic, and that error is why rounds exist); what it returns is closed here.
+    rounds: how many times records are built and the extrinsic solved, each from the last result; a round that does not come back
+    converged or at its iteration limit ends the loop and its extrinsic is not taken.  starts, opts: calib.refine_extrinsic's.
+    Returns calib.summary of the last round against the given extrinsic (Rci, tci there are the refined ones; rotation_deg and
+    translation_m the total change) plus n_records and rounds = the summary of every round against its own start."""
+    from . import calib as CB
+    R0, t0 = np.asarray(Rci, np.float64).reshape(3, 3), np.asarray(tci, np.float64).reshape(3)
+    R, t = R0, t0
+    per, last = [], None
+    for k in range(max(1, int(rounds))):
+        Rcw, tcw = camera_from_imu(body_poses, R, t)
+        dk = depth if k == 0 and depth is not None else None
+        own = dk is None
+        if own:
+            if render is None:
+                raise ValueError("calibrate_extrinsic needs depth images: depth for the first round, render for every other")
+            dk = render(Rcw, tcw)
+        try:
+            records, table = calibration_records(keypoints, pairs, matches, dk, Rcw, tcw, intr)
+        finally:
+            if own:
+                dk.close()
+        Rn, tn, rep = CB.refine_extrinsic(records, table, body_poses, intr, R, t, starts=starts if k == 0 else None, device=device, **opts)
+        per.append(dict(CB.summary(rep, R, t), n_records=int(len(records["pair"]))))
+        if int(rep["status"]) not in (CB.CONVERGED, CB.MAX_ITERATIONS):
+            if last is None:
+                last = rep
+            break
+        R, t, last = Rn, tn, rep
+    out = CB.summary(dict(last, Rci=R, tci=t), R0, t0)
+    out.update(n_records=per[-1]["n_records"], rounds=per)
+    return out
+
+
+_calibrate_extrinsic = calibrate_extrinsic    # run_full_pipeline's keyword of the same name shadows the function there
+
+
 def localize_images(query_keypoints, query_descriptors, map_keypoints, map_descriptors, map_points, intr, candidates=None, device=0,
                     match_opts=None, **opts):
     """Places images that were not part of the run into the map: each query image is matched unguided against its candidate map
@@ -811,7 +887,7 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
                       matches, enable_lidar_ba=True, enable_visual_ba=True, device=0, images=None, lidar_priors=None,
                       window_loss=None, stage_loss=None, camera_priors=None, map_quality=False, loop_closures=None, relax=None,
                       match_fn=None, match_depth=False, match_select=None, device_tracks=False, verify_matches=None,
-                      remove_dynamic=None, check_cameras=None, **cfg):
+                      remove_dynamic=None, check_cameras=None, calibrate_extrinsic=False, **cfg):
     """LvbaSystem::runFullPipeline (src/lvba_system.cpp:136-142) on in-memory data: clouds = body-frame [n_i, >=3] float32
     arrays, poses [n,12] = x_buf_ (T_world<-imu), image_poses [m,12] the image poses from the odometry.  cfg: DEFAULTS' keys
     (visual_loss, colorize_leaf among them).  images: None, or the images ([m,H,W,3] BGR uint8 or a callable k -> [H,W,3]):
@@ -855,7 +931,14 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
     the matches in force are final -- after the verification where that is on -- every image is resected from the LiDAR points its
     matches reach (pipeline.check_cameras) at the LiDAR-derived camera poses, through the depth images of match_depth /
     match_select or images rendered the same way; the output holds camera_check, per image how far the pose the images ask for
-    lies from the one the trajectory and the extrinsic give.  Nothing downstream reads it."""
+    lies from the one the trajectory and the extrinsic give.  Nothing downstream reads it.
+    calibrate_extrinsic: False (off: nothing is launched and no entry point of the stage is called), True, "apply", or a dict of
+    pipeline.calibrate_extrinsic's keywords (rounds, starts, calib.calib_opts' options) with an optional apply=True: once the
+    matches in force are final, the extrinsic is refined from them and the LiDAR depths (pipeline.calibrate_extrinsic) at the
+    LiDAR-derived image poses, and the output holds extrinsic, the report.  True reports only: nothing downstream reads it.
+    "apply": the visual stage -- camera poses, depth images, track fusion, the start of the BA, the colours -- runs with the
+    refined extrinsic instead of (Rci, tci), when the refinement converged; it needs depth images from the matching stage
+    (match_depth or match_select), which are closed before the visual stage renders its own at the new extrinsic."""
     if verify_matches and not enable_visual_ba:
         raise ValueError("verify_matches verifies the matches of the visual stage (enable_visual_ba=True)")
     if images is not None and not enable_visual_ba:
@@ -915,6 +998,21 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
                 finally:
                     if dk is not depth:
                         dk.close()
+            if calibrate_extrinsic:
+                ce = dict(calibrate_extrinsic) if isinstance(calibrate_extrinsic, dict) else {}
+                apply = bool(ce.pop("apply", False)) or calibrate_extrinsic == "apply"
+                if apply and depth is None:
+                    raise ValueError("calibrate_extrinsic='apply' needs the matches and depth images of match_depth or match_select")
+                cam_k = update_camera_poses_from_lidar(out["poses"], x_orig, scan_times, image_times, image_poses)
+                out["extrinsic"] = _calibrate_extrinsic(
+                    keypoints, pairs, matches, cam_k, Rci, tci, intr, depth=depth, device=device,
+                    render=lambda Rk, tk: V.DepthImages.render(scans, out["poses"], scan_times, image_times, Rk, tk, intr, width, height,
+                                                               half_window_s=c["depth_half_window_s"], voxel_size=c["depth_voxel"]), **ce)
+                out["extrinsic"]["applied"] = bool(apply and out["extrinsic"]["status"] == "converged")
+                if out["extrinsic"]["applied"]:
+                    Rci, tci = np.array(out["extrinsic"]["Rci"]), np.array(out["extrinsic"]["tci"])
+                    depth.close()            # rendered at the old extrinsic: the visual stage renders its own
+                    depth = None
             if enable_visual_ba:
                 out["visual"] = run_visual_ba_with_lidar_assist(scans, out["poses"], x_orig, scan_times, image_times, image_poses, Rci,
                                                                 tci, intr, width, height, keypoints, pairs, matches,
@@ -981,7 +1079,7 @@ def extrinsics_from_config(Rcl, Pcl, extrinsic_R, extrinsic_T):
 def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrinsic_R=np.eye(3), extrinsic_T=np.zeros(3),
                 image_sample_step=1, out_dir=None, device=0, colorize=False, map_quality=False, loop_closures=None, relax=None,
                 matching="db", match_opts=None, pair_selection=None, device_tracks=False, verify=None, features="db",
-                feature_opts=None, remove_dynamic=None, check_cameras=None, **cfg):
+                feature_opts=None, remove_dynamic=None, check_cameras=None, calibrate_extrinsic=False, **cfg):
     """initFromDatasetIO + runFullPipeline on a dataset directory; with out_dir, the refined LiDAR poses (TUM) and the COLMAP
     text files images.txt / points3D.txt the reference writes (src/lvba_system.cpp:2018-2137) are saved there.  images.txt is
     the reference's, character for character (tests/test_ref_system.py).
@@ -1021,6 +1119,8 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
     the points of moving objects; the output gains dynamic and out_dir gets dynamic.json, the summary and the per-frame counts.
     check_cameras (True or a dict of options, as for run_full_pipeline): every image is resected from the LiDAR points its matches
     reach; the output gains camera_check and out_dir gets camera_check.json.
+    calibrate_extrinsic (True, "apply" or a dict, as for run_full_pipeline): the extrinsic is refined from the matches and the LiDAR
+    depths; the output gains extrinsic and out_dir gets extrinsic.json.
     cfg as for run_full_pipeline, e.g. visual_loss=REFERENCE_HUBER, window_loss=("cauchy", 0.1), stage_loss=("huber", 0.05),
     camera_priors=lambda cams: lidar_camera_priors(cams, Rci, tci, 1e-3, 0.02)."""
     import os
@@ -1079,7 +1179,8 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
                             **({"loop_closures": loop_closures} if loop_closures else {}),
                             **({"relax": relax} if relax and loop_closures else {}),
                             **({"remove_dynamic": remove_dynamic} if remove_dynamic else {}),
-                            **({"check_cameras": check_cameras} if check_cameras else {}), **cfg)
+                            **({"check_cameras": check_cameras} if check_cameras else {}),
+                            **({"calibrate_extrinsic": calibrate_extrinsic} if calibrate_extrinsic else {}), **cfg)
     out.update(image_ids=image_ids, scan_times=ds["timestamps"])
     if out_dir is not None:
         os.makedirs(out_dir, exist_ok=True)
@@ -1120,6 +1221,10 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
             import json
             with open(os.path.join(out_dir, "camera_check.json"), "w") as f:
                 json.dump(out["camera_check"], f, indent=1)
+        if "extrinsic" in out:
+            import json
+            with open(os.path.join(out_dir, "extrinsic.json"), "w") as f:
+                json.dump(out["extrinsic"], f, indent=1)
         if "pose_graph" in out:
             import json
             with open(os.path.join(out_dir, "pose_graph.json"), "w") as f:

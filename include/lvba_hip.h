@@ -1650,6 +1650,84 @@ int32_t lvba_resect_score(int32_t device, int64_t n_corr, const float *uv, const
 int32_t lvba_resect_lift(lvba_depth_t depth, int32_t n_images, const int64_t *kp_off, const float *uv, const double *intr,
                          const double *Rcw, const double *tcw, double *world);
 
+/* ---- LiDAR-camera extrinsic refinement from depth-lifted matches (opt-in)
+ *   Every camera pose of the pipeline is the body pose at the image time times ONE configured transform T_cam<-imu = (Rci, tci).
+ *   A match between images a and b whose keypoint in b has a LiDAR depth return constrains that transform through the body's motion
+ *   between the two image times: the hand-eye equation A X = X B, with metric scale from the LiDAR.  These calls minimise the
+ *   reprojection error of all such records over the six parameters of X by Gauss-Newton, hold the directions the trajectory leaves
+ *   unobservable, and say which they are.  The rule below is this project's own definition, restated in numpy in
+ *   tests/calib_oracle.py.  fp64 throughout, every sum left to right within a record, no contraction: a record's residual, Jacobian
+ *   and weight are the same bits under g++, numpy and gfx950; the sums over the records are a tree on the device and are held to the
+ *   summation bound.
+ *   Record.  pair (int32, a row of the pair table), uv_a (fp32 pixel of the keypoint in the TARGET image a), Xb (fp64 [3]: the
+ *     partner keypoint's lifted point in the camera frame of the SOURCE image b, at the pose it was lifted with).  Records arrive
+ *     grouped by pair: all records of a pair in one run.
+ *   Pair table.  img_a, img_b [n_pairs], a directed pair each.  Body poses: T_world<-imu [n_images][12] (R row-major, then P), the
+ *     layout of image_poses.
+ *   Once per call, on the device.  Per pair R_ab = Rwi_a^T Rwi_b, p_ab = Rwi_a^T (P_b - P_a) (T_imu_a<-imu_b); per record (x, y) =
+ *     uv_a undistorted (trk_undistort, intr = (fx, fy, cx, cy, k1, k2, p1, p2)).  A record whose (x, y) is NaN or whose Xb is not
+ *     finite is UNUSABLE: never counted.
+ *   Residual at (R, t) = (Rci, tci).  q = R^T (Xb - t);  w = R_ab q + p_ab;  Xc = R w + t, every row ((m0 v0 + m1 v1) + m2 v2) +
+ *     c;  iz = 1 / Xc_z, r = (fx (Xc_x iz - x), fy (Xc_y iz - y)) (the resection's refit form).  The record COUNTS iff Xc_z > 1e-12
+ *     and, where max_error_px > 0, r0 r0 + r1 r1 <= max_error_px max_error_px -- at the extrinsic the iteration starts from, so
+ *     the counted set may change from one iteration to the next.
+ *   Jacobian under the resection's left perturbation (R <- (I + [om]x) R re-orthonormalised through a unit quaternion, t <- t +
+ *     om x t + up, order (om, up)): with M = R R_ab R^T, dXc/dom = -[Xc]x + M [Xb]x and dXc/dup = I - M, each followed by the 2 x 3
+ *     projection Jacobian.  I - M is why the translation needs rotation about two axes.  csrc/calib_device.h writes every
+ *     expression in order (M is never formed: a Jacobian row is Xc x g + h x Xb, g - h with h = R (R_ab^T (R^T g))).
+ *   Loss.  loss_eval of csrc/visual_loss.h on s = |r|^2 at scale loss_scale_px, kinds LVBA_LOSS_*: weight rho', cost rho / 2.
+ *     Default Huber at 2 px: the value of the numpy prototype this stage started from, not tuned on recorded data.
+ *   Sums.  H = sum rho' J^T J (21), g = sum rho' J^T r (6), cost = sum rho / 2, the count, sum |r|^2, sum rho'.
+ *   Step.  H = V diag(lambda) V^T by cyclic Jacobi, eigenvalues ascending.  Direction k is HELD where not lambda_k > min_eig_ratio
+ *     lambda_max (default 1e-6: between the 1.3e-3 of a trajectory that rotates about three axes and the 1e-15 of one that rotates
+ *     about one, as the prototype saw them; not measured on recorded data).  The step is the Gauss-Newton step in the span of the
+ *     free directions, d = -sum_free v_k (v_k . g) / lambda_k.  CONVERGED where |om| <= eps_rot and |up| <= eps_trans (defaults
+ *     1e-10 rad, 1e-10 m); that step is not applied.  At most max_iterations (default 20) steps, then one more linearisation:
+ *     whatever the status, n_used, rmse_px, cost, the eigen-decomposition and information are of the extrinsic returned.
+ *   Status per job.  LVBA_CALIB_CONVERGED; LVBA_CALIB_MAX_ITERATIONS; LVBA_CALIB_TOO_FEW_RECORDS: fewer than min_records (default
+ *     100) records count (no eigen-decomposition: zeros); LVBA_CALIB_DEGENERATE: lambda_max is not > 0 -- up to rounding: not above
+ *     1e-20 n_used (fx^2 + fy^2), the square of the Jacobian's own rounding being all H holds where the body never moves --,
+ *     every direction is held, or the step is not finite.  n_held (0 .. 6) is an output of its own, not a failure: a body that
+ *     turns about one axis and moves only along it comes back CONVERGED with n_held = 2 (the rotation about that axis and the
+ *     translation along it); a ground vehicle, which also moves across its axis, with n_held = 1 (the translation along it: the
+ *     motion across ties the rotation down through the LiDAR's metric scale).
+ *   Jobs.  n_jobs initial extrinsics over the SAME records (multi-start), iterated in lock-step.  What a job returns depends
+ *     neither on what else is in the batch nor on its place in it.
+ *   lvba_calib_extrinsic: per job Rci_out [9], tci_out [3], status, iterations (steps applied), n_used, rmse_px = sqrt(sum |r|^2 /
+ *     n_used), cost, n_held, eigenvalues [6] ascending, eigenvectors [36] (row k the unit vector of eigenvalue k, order (om, up),
+ *     camera frame), information [36] = H at the returned extrinsic, px^-2.
+ *   lvba_calib_linearize: the diagnostic call, one evaluation per job at the given extrinsic and no step: H [n_jobs][36], g [6],
+ *     cost, n_used, sum_sq = sum |r|^2.
+ *   LVBA_ERR_ARG (nothing written): a null pointer, n_images < 1, n_jobs < 1, a negative count, a pair index outside the table,
+ *   records not grouped by pair, an image index outside [0, n_images) or img_a == img_b, non-finite poses, intrinsics or initial
+ *   extrinsic, focal lengths <= 0, max_iterations < 1 (or > 1000), a negative or NaN threshold, an unknown loss or a loss scale that
+ *   is not > 0.  lvba_version() is unchanged; a client detects these calls by looking lvba_calib_extrinsic up. */
+#define LVBA_CALIB_CONVERGED 0
+#define LVBA_CALIB_MAX_ITERATIONS 1
+#define LVBA_CALIB_TOO_FEW_RECORDS 2
+#define LVBA_CALIB_DEGENERATE 3
+typedef struct lvba_calib_opts {
+    int32_t max_iterations;  /* 20 */
+    int32_t loss_kind;       /* LVBA_LOSS_HUBER */
+    int64_t min_records;     /* 100 */
+    double loss_scale_px;    /* 2.0 */
+    double max_error_px;     /* 0 = no gate */
+    double min_eig_ratio;    /* 1e-6 */
+    double eps_rot;          /* 1e-10 rad */
+    double eps_trans;        /* 1e-10 m */
+    int64_t reserved;        /* 0 */
+} lvba_calib_opts;           /* 64 bytes */
+void    lvba_calib_default_opts(lvba_calib_opts *o);
+int32_t lvba_calib_extrinsic(int32_t device, int32_t n_images, const double *body_poses, const double *intr, int32_t n_pairs,
+                             const int32_t *img_a, const int32_t *img_b, int64_t n_records, const int32_t *pair, const float *uv_a,
+                             const double *Xb, int32_t n_jobs, const double *Rci, const double *tci, const lvba_calib_opts *o,
+                             double *Rci_out, double *tci_out, int32_t *status, int32_t *iterations, int64_t *n_used, double *rmse_px,
+                             double *cost, int32_t *n_held, double *eigenvalues, double *eigenvectors, double *information);
+int32_t lvba_calib_linearize(int32_t device, int32_t n_images, const double *body_poses, const double *intr, int32_t n_pairs,
+                             const int32_t *img_a, const int32_t *img_b, int64_t n_records, const int32_t *pair, const float *uv_a,
+                             const double *Xb, int32_t n_jobs, const double *Rci, const double *tci, const lvba_calib_opts *o, double *H,
+                             double *g, double *cost, int64_t *n_used, double *sum_sq);
+
 #ifdef __cplusplus
 }
 #endif
