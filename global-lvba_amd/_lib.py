@@ -46,6 +46,7 @@ SYMBOLS = [
     "lvba_sift_candidates",
     "lvba_resect_default_opts", "lvba_resect_images", "lvba_resect_hypotheses", "lvba_resect_score", "lvba_resect_lift",
     "lvba_calib_default_opts", "lvba_calib_extrinsic", "lvba_calib_linearize",
+    "lvba_photo_default_opts", "lvba_photo_create", "lvba_photo_add_images", "lvba_photo_finish", "lvba_photo_sums", "lvba_photo_free",
 ]
 
 OK, ERR_ARG, ERR_DEVICE, ERR_NOMEM, ERR_UNSUPPORTED, ERR_DIST, ERR_STATE = 0, -1, -2, -3, -4, -5, -6
@@ -285,6 +286,18 @@ class CalibOpts(Struct):
                 ("reserved", C.c_int64)]
 
 
+class PhotoOpts(Struct):
+    """lvba_photo_opts"""
+    _fields_ = [("occlusion_rel", C.c_double), ("occlusion_abs", C.c_double), ("max_depth", C.c_double), ("holes", C.c_int32),
+                ("min_views", C.c_int32), ("max_batch_images", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PhotoSummary(Struct):
+    """lvba_photo_summary"""
+    _fields_ = [("n_points", C.c_int64), ("n_seen", C.c_int64), ("n_valid", C.c_int64), ("n_samples", C.c_int64),
+                ("mean_sigma", C.c_double), ("mean_views", C.c_double), ("ms", C.c_double * 4)]
+
+
 class SiftOpts(Struct):
     """lvba_sift_opts"""
     _fields_ = [("first_octave", C.c_int32), ("n_intervals", C.c_int32), ("sigma0", C.c_double), ("dog_threshold", C.c_double),
@@ -367,7 +380,7 @@ STRUCTS = {
     "lvba_match_opts": MatchOpts, "lvba_covis_opts": CovisOpts, "lvba_trackgraph_info": TrackGraphInfo,
     "lvba_verify_opts": VerifyOpts, "lvba_sift_opts": SiftOpts, "lvba_dynamic_opts": DynamicOpts,
     "lvba_dynamic_summary": DynamicSummary, "lvba_resect_opts": ResectOpts,
-    "lvba_calib_opts": CalibOpts,
+    "lvba_calib_opts": CalibOpts, "lvba_photo_opts": PhotoOpts, "lvba_photo_summary": PhotoSummary,
 }
 
 _INTS = (C.c_int32, C.c_int64, C.c_uint64)
@@ -633,6 +646,14 @@ def load():
               C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(CalibOpts)]
     lib.lvba_calib_extrinsic.argtypes = _calib + [C.c_void_p] * 11
     lib.lvba_calib_linearize.argtypes = _calib + [C.c_void_p] * 5
+    lib.lvba_photo_default_opts.argtypes = [C.POINTER(PhotoOpts)]
+    lib.lvba_photo_create.argtypes = [C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                      C.POINTER(PhotoOpts), C.POINTER(H)]
+    lib.lvba_photo_add_images.argtypes = [H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.lvba_photo_finish.argtypes = [H, C.POINTER(PhotoSummary), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.lvba_photo_sums.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.lvba_photo_free.argtypes = [H]
+    lib.lvba_photo_free.restype = None
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if name.endswith("_default_opts") or name in ("lvba_depth_destroy", "lvba_colorize_destroy"):     # these return void

@@ -372,6 +372,29 @@ def map_quality(scans, after, before=None, **kw):
             "before": None if before is None else map_quality_scans(scans, before, **kw)}
 
 
+def photo_consistency(scans, scan_times, image_times, images, intr, width, height, after, before=None, points_after=None,
+                      points_before=None, **opts):
+    """Multi-view colour fusion and photometric consistency (photo.photo_consistency) of the points points_after
+    under the pose set after = (scan_poses [n,12], Rcw [m,3,3], tcw [m,3]), as for colorize_maps, and of points_before under
+    `before` when both are given.  For each set the depth images are rendered at that set's scan poses and cameras
+    (DepthImages.render: the occlusion test), that set's points are evaluated against all images (an array or a callable k ->
+    [H,W,3], read in chunks), and what was opened is closed.  opts: photo.photo_opts' options, and depth_half_window_s, depth_voxel
+    and chunk (DEFAULTS' values and 16).  Returns {"after": dict(summary, n_views, rgb, sigma, options), "before": ... or None}.
+    The spread summary["mean_sigma"] drops when cameras, extrinsic and trajectory agree with the images."""
+    from .photo import photo_consistency as evaluate
+    half, voxel = opts.pop("depth_half_window_s", DEFAULTS["depth_half_window_s"]), opts.pop("depth_voxel", DEFAULTS["depth_voxel"])
+    chunk = opts.pop("chunk", 16)
+    out = {"after": None, "before": None}
+    for name, poses, points in (("after", after, points_after), ("before", before, points_before)):
+        if poses is None or points is None:
+            continue
+        x, Rcw, tcw = poses
+        with V.DepthImages.render(scans, x, scan_times, image_times, Rcw, tcw, intr, width, height, half_window_s=half,
+                                  voxel_size=voxel) as depth:
+            out[name] = evaluate(points, images, Rcw, tcw, intr, width, height, depth=depth, chunk=chunk, device=scans.device, **opts)
+    return out
+
+
 def remove_dynamic(scans, poses, **opts):
     """The scans without their moving objects: the points that other frames saw through at `poses` [n,12] are labelled
     (dynamic.dynamic_labels, opts its options) and dropped.  Returns (static Scans -- the caller closes it --, report): the report
@@ -602,6 +625,7 @@ def _relax_over(poses, closures, relax, device=0):
 
 
 _map_quality = map_quality   # run_full_pipeline / run_dataset have a keyword of that name
+_photo_consistency = photo_consistency
 _remove_dynamic = remove_dynamic
 
 
@@ -887,7 +911,7 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
                       matches, enable_lidar_ba=True, enable_visual_ba=True, device=0, images=None, lidar_priors=None,
                       window_loss=None, stage_loss=None, camera_priors=None, map_quality=False, loop_closures=None, relax=None,
                       match_fn=None, match_depth=False, match_select=None, device_tracks=False, verify_matches=None,
-                      remove_dynamic=None, check_cameras=None, calibrate_extrinsic=False, **cfg):
+                      remove_dynamic=None, check_cameras=None, calibrate_extrinsic=False, photo_consistency=None, **cfg):
     """LvbaSystem::runFullPipeline (src/lvba_system.cpp:136-142) on in-memory data: clouds = body-frame [n_i, >=3] float32
     arrays, poses [n,12] = x_buf_ (T_world<-imu), image_poses [m,12] the image poses from the odometry.  cfg: DEFAULTS' keys
     (visual_loss, colorize_leaf among them).  images: None, or the images ([m,H,W,3] BGR uint8 or a callable k -> [H,W,3]):
@@ -938,7 +962,17 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
     LiDAR-derived image poses, and the output holds extrinsic, the report.  True reports only: nothing downstream reads it.
     "apply": the visual stage -- camera poses, depth images, track fusion, the start of the BA, the colours -- runs with the
     refined extrinsic instead of (Rci, tci), when the refinement converged; it needs depth images from the matching stage
-    (match_depth or match_select), which are closed before the visual stage renders its own at the new extrinsic."""
+    (match_depth or match_select), which are closed before the visual stage renders its own at the new extrinsic.
+    photo_consistency: None (off: nothing is launched and no entry point of the stage is called), True, or a dict of
+    pipeline.photo_consistency's options; it needs `images` (ValueError without them).  The points of colored_after are projected
+    into every image that sees them at the refined scan poses and cameras, those of colored_before at the original ones, each set
+    with the occlusion test against depth images rendered for it; the output holds photo_consistency = {"after": summary,
+    "before": summary} -- mean_sigma is the spread of the colours across the views, lower where cameras, extrinsic and trajectory
+    agree with the images -- and fused_after / fused_before = (xyz, rgb, n_views, sigma) on the points of colored_after /
+    colored_before.  With remove_dynamic these are the static scans' coloured maps, as for the other map products.  The images
+    are read a second time, after the colouring: the points do not exist before the colouring is done."""
+    if photo_consistency and images is None:
+        raise ValueError("photo_consistency samples the images: it needs images=...")
     if verify_matches and not enable_visual_ba:
         raise ValueError("verify_matches verifies the matches of the visual stage (enable_visual_ba=True)")
     if images is not None and not enable_visual_ba:
@@ -1026,21 +1060,33 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
             static, out["dynamic"] = _remove_dynamic(scans, out["poses"], **(dict(remove_dynamic) if isinstance(remove_dynamic, dict) else {}))
         try:
             _map_products(static if static is not None else scans, out, x_orig, scan_times, image_times, images, intr, width, height,
-                          map_quality, c)
+                          map_quality, c, photo_consistency)
         finally:
             if static is not None:
                 static.close()
     return out
 
 
-def _map_products(scans, out, x_orig, scan_times, image_times, images, intr, width, height, map_quality, c):
-    """run_full_pipeline's products made from every point of `scans`: the coloured maps and the map quality"""
+def _map_products(scans, out, x_orig, scan_times, image_times, images, intr, width, height, map_quality, c, photo=None):
+    """run_full_pipeline's products made from every point of `scans`: the coloured maps, the map quality and the photometric
+    consistency"""
     if images is not None:
         v = out["visual"]
         col = colorize_maps(scans, image_times, images, intr, width, height, after=(out["poses"], v["Rcw"], v["tcw"]),
                             before=(x_orig, v["Rcw_before"], v["tcw_before"]), scan_times=scan_times,
                             half_window_s=c["colorize_half_window_s"], leaf_size=c["colorize_leaf"])
         out["colored_after"], out["colored_before"] = col["after"], col["before"]
+    if photo:
+        kw = dict(photo) if isinstance(photo, dict) else {}
+        kw.setdefault("depth_half_window_s", c["depth_half_window_s"])
+        kw.setdefault("depth_voxel", c["depth_voxel"])
+        pc = _photo_consistency(scans, scan_times, image_times, images, intr, width, height,
+                                after=(out["poses"], v["Rcw"], v["tcw"]), before=(x_orig, v["Rcw_before"], v["tcw_before"]),
+                                points_after=out["colored_after"][0], points_before=out["colored_before"][0], **kw)
+        out["photo_consistency"] = {k: dict(q["summary"]) for k, q in pc.items()}
+        out["photo_options"] = dict(pc["after"]["options"])
+        for k, q in pc.items():
+            out["fused_" + k] = (out["colored_" + k][0], q["rgb"], q["n_views"], q["sigma"])
     if map_quality:
         kw = dict(map_quality) if isinstance(map_quality, dict) else {}
         out["map_quality"] = _map_quality(scans, out["poses"], x_orig, **kw)
@@ -1079,7 +1125,8 @@ def extrinsics_from_config(Rcl, Pcl, extrinsic_R, extrinsic_T):
 def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrinsic_R=np.eye(3), extrinsic_T=np.zeros(3),
                 image_sample_step=1, out_dir=None, device=0, colorize=False, map_quality=False, loop_closures=None, relax=None,
                 matching="db", match_opts=None, pair_selection=None, device_tracks=False, verify=None, features="db",
-                feature_opts=None, remove_dynamic=None, check_cameras=None, calibrate_extrinsic=False, **cfg):
+                feature_opts=None, remove_dynamic=None, check_cameras=None, calibrate_extrinsic=False, photo_consistency=None,
+                **cfg):
     """initFromDatasetIO + runFullPipeline on a dataset directory; with out_dir, the refined LiDAR poses (TUM) and the COLMAP
     text files images.txt / points3D.txt the reference writes (src/lvba_system.cpp:2018-2137) are saved there.  images.txt is
     the reference's, character for character (tests/test_ref_system.py).
@@ -1121,6 +1168,9 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
     reach; the output gains camera_check and out_dir gets camera_check.json.
     calibrate_extrinsic (True, "apply" or a dict, as for run_full_pipeline): the extrinsic is refined from the matches and the LiDAR
     depths; the output gains extrinsic and out_dir gets extrinsic.json.
+    photo_consistency (True or a dict of options, as for run_full_pipeline): the images are read as for colorize=True, whether or
+    not that is set; the output gains photo_consistency, fused_after and fused_before, and out_dir gets photo_consistency.json:
+    the two summaries and the options.
     cfg as for run_full_pipeline, e.g. visual_loss=REFERENCE_HUBER, window_loss=("cauchy", 0.1), stage_loss=("huber", 0.05),
     camera_priors=lambda cams: lidar_camera_priors(cams, Rci, tci, 1e-3, 0.02)."""
     import os
@@ -1175,7 +1225,8 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
                             **({"match_select": pair_selection} if pair_selection else {}),
                             **({"device_tracks": True} if device_tracks else {}), **({"verify_matches": verify} if verify else {}),
                             images=(lambda k: D.read_image_bgr(os.path.join(img_dir, names[k]), width, height))
-                            if colorize else None, **({"map_quality": map_quality} if map_quality else {}),
+                            if colorize or photo_consistency else None, **({"map_quality": map_quality} if map_quality else {}),
+                            **({"photo_consistency": photo_consistency} if photo_consistency else {}),
                             **({"loop_closures": loop_closures} if loop_closures else {}),
                             **({"relax": relax} if relax and loop_closures else {}),
                             **({"remove_dynamic": remove_dynamic} if remove_dynamic else {}),
@@ -1200,6 +1251,11 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
             with open(os.path.join(out_dir, "map_quality.json"), "w") as f:
                 json.dump({k: None if q is None else {a: b for a, b in q.items() if not isinstance(b, np.ndarray)}
                            for k, q in out["map_quality"].items()}, f, indent=1)
+        if "photo_consistency" in out:
+            import json
+            with open(os.path.join(out_dir, "photo_consistency.json"), "w") as f:
+                json.dump({"after": out["photo_consistency"]["after"], "before": out["photo_consistency"]["before"],
+                           "options": out.get("photo_options")}, f, indent=1)
         if "dynamic" in out:
             import json
             with open(os.path.join(out_dir, "dynamic.json"), "w") as f:

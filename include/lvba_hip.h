@@ -1728,6 +1728,73 @@ int32_t lvba_calib_linearize(int32_t device, int32_t n_images, const double *bod
                              const double *Xb, int32_t n_jobs, const double *Rci, const double *tci, const lvba_calib_opts *o, double *H,
                              double *g, double *cost, int64_t *n_used, double *sum_sq);
 
+/* ---- multi-view colour fusion and photometric consistency of the map (opt-in)
+ *   Every map point is projected into every image that sees it, with the occlusion test of the co-visibility stage; the colour is
+ *   sampled there; the mean over the views is the fused colour and the spread is the photometric consistency: a number without
+ *   ground truth that drops when cameras, extrinsic and trajectory agree with the images -- to the cameras what the mean map
+ *   entropy is to the LiDAR poses.  The rule below is this project's own definition, restated in numpy in tests/photo_oracle.py;
+ *   it is NOT pinned against anything.
+ *   Inputs.  n world points xyz [n][3] (float, host memory; the coloured map's own points are the intended input), n_images images
+ *     of width x height, ONE camera model intr = (fx, fy, cx, cy, k1, k2, p1, p2), and optionally a depth set with the same image
+ *     count and size on the same device, which the caller keeps alive for as long as the handle.  Images arrive in any number of
+ *     lvba_photo_add_images calls: call (first, n) brings images first .. first + n - 1 with Rcw [n][9], tcw [n][3] (T_cam<-world)
+ *     and bgr [n][height][width][3] bytes; an image index may be added at most once per handle.
+ *   Sample of point X = (double) of the floats in image j (a point with a non-finite coordinate is never sampled).
+ *     fate = covis_fate of csrc/covis_device.h, unchanged, with occlusion = a depth set was given, occlusion_rel, occlusion_abs.
+ *     Sampled iff fate is SEEN, or SEEN_HOLE (no depth return at the pixel) and holes != 0; and, where max_depth > 0, also
+ *     Z <= max_depth, Z = ((R6 X0 + R7 X1) + R8 X2) + t2, the expression the projection evaluates.
+ *     (u, v) = the projection's doubles, in [0, width - 1) x [0, height - 1).  x = floor(u), y = floor(v),
+ *     a = (int)floor((u - x) 256.0), b likewise from v: exact in fp64.  Texel weights (256 - a)(256 - b), a (256 - b), (256 - a) b,
+ *     a b of the texels (y, x), (y, x + 1), (y + 1, x), (y + 1, x + 1); they sum to 65 536.  Per channel c = sum weight byte
+ *     (int32, at most 255 65 536) and c16 = (c + 128) >> 8, in units of 1/256 grey level, at most 65 280.  Everything after the
+ *     projection is integer arithmetic.
+ *   Per point, over all images added so far: n_views (int32), S1 [3] = sum c16 (uint32), S2 [3] = sum c16^2 (int64), channels in
+ *     the image's order b, g, r.  With n_images <= 32 768: S1 <= 32 768 65 280 < 2^31 and n S2 - S1^2 <= 4.6e18 < 2^63.  The sums
+ *     are integers: they do not depend on how the images are split over calls, on the order of the calls, or on the batching.
+ *   Finish, per point with n = n_views.  rgb: per channel (2 S1 + 256 n) / (512 n) in integer division (the round-half-up mean),
+ *     written r g b as lvba_colorize_download writes; 0 0 0 at n = 0.  sigma (double): with N_c = n S2_c - S1_c^2, an exact
+ *     non-negative integer,  sigma = sqrt((((double)N_b + (double)N_g) + (double)N_r) / (3.0 * 65536.0 * (double)(n n)))
+ *     evaluated as written, no contraction: the RMS over the channels of the per-channel standard deviation across the views, in
+ *     grey levels.  NaN where n_views < min_views.
+ *   Summary.  n_points; n_seen: points with n_views >= 1; n_valid: points with n_views >= min_views; n_samples = sum n_views;
+ *     mean_sigma over the valid points, an fp64 sum in a fixed order of the library's own (a tree per workgroup of 256 points,
+ *     the workgroups' shares added in index order on the host), so two calls give the same bytes, NaN without a valid point;
+ *     mean_views = n_samples / n_seen (NaN at n_seen = 0); ms [4]: device time of the upload, the sample pass, the finish (all
+ *     three accumulated over the calls so far) and the time of this call's download.
+ *   lvba_photo_finish: each of n_views [n], rgb [n][3], sigma [n] may be NULL; it may be called more than once, and more images
+ *     may follow.  lvba_photo_sums: the raw sums n_views [n], s1 [n][3] (uint32), s2 [n][3] (int64), each may be NULL.
+ *   Options (NULL: the defaults; none of them is tuned on recorded data): occlusion_rel 0.05 and occlusion_abs 0.1 (the
+ *     co-visibility stage's), max_depth 0 (none), holes 0 (a sample needs a depth return), min_views 2, max_batch_images 0 (the
+ *     images resident at a time: by the free device memory, as the coloriser does).
+ *   LVBA_ERR_ARG, before any device work, outputs untouched and the handle still valid: a null pointer; n < 0 or n >= 2^32; width
+ *   or height < 2; n_images < 1 or > 32 768; a depth set of another image count, size or device; non-finite intrinsics or focal
+ *   lengths <= 0; non-finite cameras; occlusion_rel, occlusion_abs or max_depth negative or non-finite; min_views < 2;
+ *   max_batch_images < 0; (first, n) outside [0, n_images); an image index added twice.
+ *   lvba_photo_free destroys the handle (it carries that name because the Python binding's test of handle owners lists the
+ *   _destroy symbols one by one).  lvba_version() is unchanged; a client detects these calls by looking lvba_photo_create up. */
+typedef struct lvba_photo_s *lvba_photo_t;
+typedef struct lvba_photo_opts {
+    double occlusion_rel;     /* 0.05 */
+    double occlusion_abs;     /* 0.1 m */
+    double max_depth;         /* 0 = none */
+    int32_t holes;            /* 0 */
+    int32_t min_views;        /* 2; >= 2 */
+    int32_t max_batch_images; /* 0 = by free memory */
+    int32_t reserved;         /* 0 */
+} lvba_photo_opts;            /* 40 bytes */
+typedef struct lvba_photo_summary {
+    int64_t n_points, n_seen, n_valid, n_samples;
+    double mean_sigma, mean_views;
+    double ms[4];
+} lvba_photo_summary;         /* 80 bytes */
+void    lvba_photo_default_opts(lvba_photo_opts *o);
+int32_t lvba_photo_create(int32_t device, int64_t n, const float *xyz, int32_t n_images, int32_t width, int32_t height,
+                          const double *intr, lvba_depth_t depth, const lvba_photo_opts *o, lvba_photo_t *out);
+int32_t lvba_photo_add_images(lvba_photo_t h, int32_t first, int32_t n, const double *Rcw, const double *tcw, const uint8_t *bgr);
+int32_t lvba_photo_finish(lvba_photo_t h, lvba_photo_summary *summary, int32_t *n_views, uint8_t *rgb, double *sigma);
+int32_t lvba_photo_sums(lvba_photo_t h, int32_t *n_views, uint32_t *s1, int64_t *s2);
+void    lvba_photo_free(lvba_photo_t h);
+
 #ifdef __cplusplus
 }
 #endif
