@@ -47,6 +47,7 @@ SYMBOLS = [
     "lvba_resect_default_opts", "lvba_resect_images", "lvba_resect_hypotheses", "lvba_resect_score", "lvba_resect_lift",
     "lvba_calib_default_opts", "lvba_calib_extrinsic", "lvba_calib_linearize",
     "lvba_photo_default_opts", "lvba_photo_create", "lvba_photo_add_images", "lvba_photo_finish", "lvba_photo_sums", "lvba_photo_free",
+    "lvba_palign_default_opts", "lvba_palign_create", "lvba_palign_linearize", "lvba_palign_align", "lvba_palign_profile", "lvba_palign_free",
 ]
 
 OK, ERR_ARG, ERR_DEVICE, ERR_NOMEM, ERR_UNSUPPORTED, ERR_DIST, ERR_STATE = 0, -1, -2, -3, -4, -5, -6
@@ -298,6 +299,14 @@ class PhotoSummary(Struct):
                 ("mean_sigma", C.c_double), ("mean_views", C.c_double), ("ms", C.c_double * 4)]
 
 
+class PalignOpts(Struct):
+    """lvba_palign_opts"""
+    _fields_ = [("occlusion_rel", C.c_double), ("occlusion_abs", C.c_double), ("max_depth", C.c_double), ("loss_scale", C.c_double),
+                ("eps_rot", C.c_double), ("eps_trans", C.c_double), ("max_rotation_deg", C.c_double), ("max_translation", C.c_double),
+                ("holes", C.c_int32), ("loss_kind", C.c_int32), ("min_samples", C.c_int32), ("max_iterations", C.c_int32),
+                ("max_batch_images", C.c_int32), ("reserved", C.c_int32)]
+
+
 class SiftOpts(Struct):
     """lvba_sift_opts"""
     _fields_ = [("first_octave", C.c_int32), ("n_intervals", C.c_int32), ("sigma0", C.c_double), ("dog_threshold", C.c_double),
@@ -381,6 +390,7 @@ STRUCTS = {
     "lvba_verify_opts": VerifyOpts, "lvba_sift_opts": SiftOpts, "lvba_dynamic_opts": DynamicOpts,
     "lvba_dynamic_summary": DynamicSummary, "lvba_resect_opts": ResectOpts,
     "lvba_calib_opts": CalibOpts, "lvba_photo_opts": PhotoOpts, "lvba_photo_summary": PhotoSummary,
+    "lvba_palign_opts": PalignOpts,
 }
 
 _INTS = (C.c_int32, C.c_int64, C.c_uint64)
@@ -654,6 +664,15 @@ def load():
     lib.lvba_photo_sums.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.lvba_photo_free.argtypes = [H]
     lib.lvba_photo_free.restype = None
+    lib.lvba_palign_default_opts.argtypes = [C.POINTER(PalignOpts)]
+    lib.lvba_palign_create.argtypes = [C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                       C.c_void_p, C.POINTER(PalignOpts), C.POINTER(H)]
+    _palign = [H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.lvba_palign_linearize.argtypes = _palign + [C.c_void_p]
+    lib.lvba_palign_align.argtypes = _palign + [C.c_void_p] * 10
+    lib.lvba_palign_profile.argtypes = [H, C.c_void_p]
+    lib.lvba_palign_free.argtypes = [H]
+    lib.lvba_palign_free.restype = None
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if name.endswith("_default_opts") or name in ("lvba_depth_destroy", "lvba_colorize_destroy"):     # these return void

@@ -395,6 +395,69 @@ def photo_consistency(scans, scan_times, image_times, images, intr, width, heigh
     return out
 
 
+def align_cameras_photometric(points, images, cameras, depth, intr, width, height, rounds=1, min_views=2, render=None, chunk=16,
+                              device=0, **opts):
+    """Photometric camera alignment against the coloured map (palign.PhotoAligner): the colour-map optimisation of
+    Zhou & Koltun in `rounds` rounds.  points [n,3]: the map's points; images: an array [m,H,W,3] or a callable k -> [H,W,3], read
+    `chunk` at a time; cameras = (Rcw [m,3,3], tcw [m,3]); depth: a visual.DepthImages at those cameras (the caller's, left open)
+    or None (no occlusion test).  Per round: (1) the colour fusion at the current cameras gives the integer sums and the spread;
+    (2) the reference colours are the fused ones, points below min_views invalid; (3) every image is aligned against them;
+    (4) the depth images are rendered again at the returned cameras by render(Rcw, tcw) -> DepthImages (None: the depth images
+    stay as they came), closed here.  opts: palign.palign_opts' options.  Returns dict(Rcw, tcw, status [m] and status_names,
+    iterations, accepted, n_samples, rmse_initial (at the cameras given, first round) and rmse (at the cameras returned, last
+    round) [m] in grey levels, mean_sigma: the spread at the start of every round and at the cameras returned [rounds + 1],
+    rounds: per round dict(status, rmse_initial, rmse, n_valid), options).  The reference of a round holds every image's own
+    earlier sample, so a round's step falls short by about 1 / n_views: the rounds make up for it."""
+    from .palign import STATUS, PhotoAligner, reference_from_sums
+    from .photo import PhotoMap
+    R = np.ascontiguousarray(cameras[0], np.float64).reshape(-1, 3, 3).copy()
+    t = np.ascontiguousarray(cameras[1], np.float64).reshape(-1, 3).copy()
+    M, step = len(R), max(int(chunk), 1)
+    read = (lambda a, b: np.stack([np.asarray(images(k), np.uint8) for k in range(a, b)])) if callable(images) else (lambda a, b: images[a:b])
+    occl = {k: opts[k] for k in ("occlusion_rel", "occlusion_abs", "max_depth", "holes") if k in opts}
+
+    def fuse(d):
+        """the fusion at the current cameras: (mean spread, (n_views, s1, s2))"""
+        with PhotoMap(points, M, intr, width, height, depth=d, device=device, min_views=max(int(min_views), 2), **occl) as pm:
+            for k0 in range(0, M, step):
+                k1 = min(M, k0 + step)
+                pm.add_images(k0, R[k0:k1], t[k0:k1], read(k0, k1))
+            return pm.finish()["summary"]["mean_sigma"], pm.sums()
+
+    out = dict(mean_sigma=[], rounds=[])
+    own = None                                   # the depth images rendered here
+    try:
+        for rnd in range(max(int(rounds), 1)):
+            d = own if own is not None else depth
+            spread, sums = fuse(d)
+            out["mean_sigma"].append(spread)
+            ref16, valid = reference_from_sums(sums[0], sums[1], min_views)
+            parts = []
+            with PhotoAligner(points, ref16, valid, M, width, height, intr, depth=d, device=device, **opts) as pa:
+                for k0 in range(0, M, step):
+                    k1 = min(M, k0 + step)
+                    parts.append(pa.align(k0, R[k0:k1], t[k0:k1], read(k0, k1)))
+                out["options"] = dict(pa.options)
+            res = {k: np.concatenate([q[k] for q in parts]) for k in parts[0]}
+            if rnd == 0:
+                out["rmse_initial"] = res["rmse_initial"]
+            R, t = np.ascontiguousarray(res["Rcw"]), np.ascontiguousarray(res["tcw"])
+            out["rounds"].append(dict(status=res["status"], rmse_initial=res["rmse_initial"], rmse=res["rmse"], n_valid=int(valid.sum())))
+            for k in ("status", "iterations", "accepted", "n_samples", "rmse", "cost", "information"):
+                out[k] = res[k]
+            if render is not None:
+                if own is not None:
+                    own.close()
+                own = render(R, t)
+        out["mean_sigma"].append(fuse(own if own is not None else depth)[0])
+    finally:
+        if own is not None:
+            own.close()
+    out["Rcw"], out["tcw"] = R, t
+    out["status_names"] = [STATUS[int(v)] for v in out["status"]]
+    return out
+
+
 def remove_dynamic(scans, poses, **opts):
     """The scans without their moving objects: the points that other frames saw through at `poses` [n,12] are labelled
     (dynamic.dynamic_labels, opts its options) and dropped.  Returns (static Scans -- the caller closes it --, report): the report
@@ -626,6 +689,7 @@ def _relax_over(poses, closures, relax, device=0):
 
 _map_quality = map_quality   # run_full_pipeline / run_dataset have a keyword of that name
 _photo_consistency = photo_consistency
+_align_cameras_photometric = align_cameras_photometric
 _remove_dynamic = remove_dynamic
 
 
@@ -911,7 +975,7 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
                       matches, enable_lidar_ba=True, enable_visual_ba=True, device=0, images=None, lidar_priors=None,
                       window_loss=None, stage_loss=None, camera_priors=None, map_quality=False, loop_closures=None, relax=None,
                       match_fn=None, match_depth=False, match_select=None, device_tracks=False, verify_matches=None,
-                      remove_dynamic=None, check_cameras=None, calibrate_extrinsic=False, photo_consistency=None, **cfg):
+                      remove_dynamic=None, check_cameras=None, calibrate_extrinsic=False, photo_consistency=None, photo_align=None, **cfg):
     """LvbaSystem::runFullPipeline (src/lvba_system.cpp:136-142) on in-memory data: clouds = body-frame [n_i, >=3] float32
     arrays, poses [n,12] = x_buf_ (T_world<-imu), image_poses [m,12] the image poses from the odometry.  cfg: DEFAULTS' keys
     (visual_loss, colorize_leaf among them).  images: None, or the images ([m,H,W,3] BGR uint8 or a callable k -> [H,W,3]):
@@ -970,9 +1034,19 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
     "before": summary} -- mean_sigma is the spread of the colours across the views, lower where cameras, extrinsic and trajectory
     agree with the images -- and fused_after / fused_before = (xyz, rgb, n_views, sigma) on the points of colored_after /
     colored_before.  With remove_dynamic these are the static scans' coloured maps, as for the other map products.  The images
-    are read a second time, after the colouring: the points do not exist before the colouring is done."""
+    are read a second time, after the colouring: the points do not exist before the colouring is done.
+    photo_align: None (off: nothing is launched, no entry point of the stage is called and its module is not imported), True,
+    "apply", or a dict of pipeline.align_cameras_photometric's keywords (rounds, min_views, palign.palign_opts' options) with an
+    optional apply=True; it needs `images`.  The refined cameras are aligned photometrically against the points of colored_after
+    (depth images rendered at the refined scan poses and cameras, and again after every round), and the output holds photo_align,
+    the report (without the per-image information matrices), and photo_align_cameras = (Rcw, tcw).  True reports only.  "apply":
+    the `after` set of photo_consistency -- fused_after and its summary -- is evaluated at the aligned cameras; everything else
+    stays as it is (the coloured maps keep the colours of the refined cameras: their points are what the alignment is made
+    against)."""
     if photo_consistency and images is None:
         raise ValueError("photo_consistency samples the images: it needs images=...")
+    if photo_align and images is None:
+        raise ValueError("photo_align samples the images: it needs images=...")
     if verify_matches and not enable_visual_ba:
         raise ValueError("verify_matches verifies the matches of the visual stage (enable_visual_ba=True)")
     if images is not None and not enable_visual_ba:
@@ -1060,28 +1134,49 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
             static, out["dynamic"] = _remove_dynamic(scans, out["poses"], **(dict(remove_dynamic) if isinstance(remove_dynamic, dict) else {}))
         try:
             _map_products(static if static is not None else scans, out, x_orig, scan_times, image_times, images, intr, width, height,
-                          map_quality, c, photo_consistency)
+                          map_quality, c, photo_consistency, photo_align)
         finally:
             if static is not None:
                 static.close()
     return out
 
 
-def _map_products(scans, out, x_orig, scan_times, image_times, images, intr, width, height, map_quality, c, photo=None):
-    """run_full_pipeline's products made from every point of `scans`: the coloured maps, the map quality and the photometric
-    consistency"""
+def _photo_align(scans, out, scan_times, image_times, images, intr, width, height, c, photo_align):
+    """run_full_pipeline's photo_align: the report into out, and the cameras the `after` set of the photometric consistency uses"""
+    kw = dict(photo_align) if isinstance(photo_align, dict) else {}
+    apply = bool(kw.pop("apply", False)) or photo_align == "apply"
+    v = out["visual"]
+    render = lambda Rk, tk: V.DepthImages.render(scans, out["poses"], scan_times, image_times, Rk, tk, intr, width, height,
+                                                 half_window_s=c["depth_half_window_s"], voxel_size=c["depth_voxel"])
+    with render(v["Rcw"], v["tcw"]) as depth:
+        rep = _align_cameras_photometric(out["colored_after"][0], images, (v["Rcw"], v["tcw"]), depth, intr, width, height, render=render,
+                                         device=scans.device, **kw)
+    out["photo_align_cameras"] = (rep.pop("Rcw"), rep.pop("tcw"))
+    rep.pop("information")
+    rep["applied"] = apply
+    out["photo_align"] = rep
+    return out["photo_align_cameras"] if apply else (v["Rcw"], v["tcw"])
+
+
+def _map_products(scans, out, x_orig, scan_times, image_times, images, intr, width, height, map_quality, c, photo=None, photo_align=None):
+    """run_full_pipeline's products made from every point of `scans`: the coloured maps, the photometric alignment, the photometric
+    consistency and the map quality"""
     if images is not None:
         v = out["visual"]
         col = colorize_maps(scans, image_times, images, intr, width, height, after=(out["poses"], v["Rcw"], v["tcw"]),
                             before=(x_orig, v["Rcw_before"], v["tcw_before"]), scan_times=scan_times,
                             half_window_s=c["colorize_half_window_s"], leaf_size=c["colorize_leaf"])
         out["colored_after"], out["colored_before"] = col["after"], col["before"]
+    if photo_align:
+        Rcw_after, tcw_after = _photo_align(scans, out, scan_times, image_times, images, intr, width, height, c, photo_align)
+    elif images is not None:
+        Rcw_after, tcw_after = v["Rcw"], v["tcw"]
     if photo:
         kw = dict(photo) if isinstance(photo, dict) else {}
         kw.setdefault("depth_half_window_s", c["depth_half_window_s"])
         kw.setdefault("depth_voxel", c["depth_voxel"])
         pc = _photo_consistency(scans, scan_times, image_times, images, intr, width, height,
-                                after=(out["poses"], v["Rcw"], v["tcw"]), before=(x_orig, v["Rcw_before"], v["tcw_before"]),
+                                after=(out["poses"], Rcw_after, tcw_after), before=(x_orig, v["Rcw_before"], v["tcw_before"]),
                                 points_after=out["colored_after"][0], points_before=out["colored_before"][0], **kw)
         out["photo_consistency"] = {k: dict(q["summary"]) for k, q in pc.items()}
         out["photo_options"] = dict(pc["after"]["options"])
@@ -1126,7 +1221,7 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
                 image_sample_step=1, out_dir=None, device=0, colorize=False, map_quality=False, loop_closures=None, relax=None,
                 matching="db", match_opts=None, pair_selection=None, device_tracks=False, verify=None, features="db",
                 feature_opts=None, remove_dynamic=None, check_cameras=None, calibrate_extrinsic=False, photo_consistency=None,
-                **cfg):
+                photo_align=None, **cfg):
     """initFromDatasetIO + runFullPipeline on a dataset directory; with out_dir, the refined LiDAR poses (TUM) and the COLMAP
     text files images.txt / points3D.txt the reference writes (src/lvba_system.cpp:2018-2137) are saved there.  images.txt is
     the reference's, character for character (tests/test_ref_system.py).
@@ -1171,6 +1266,8 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
     photo_consistency (True or a dict of options, as for run_full_pipeline): the images are read as for colorize=True, whether or
     not that is set; the output gains photo_consistency, fused_after and fused_before, and out_dir gets photo_consistency.json:
     the two summaries and the options.
+    photo_align (True, "apply" or a dict, as for run_full_pipeline): the images are read as for colorize=True; the output gains
+    photo_align and photo_align_cameras, and out_dir gets photo_align.json: the report with its per-image arrays as lists.
     cfg as for run_full_pipeline, e.g. visual_loss=REFERENCE_HUBER, window_loss=("cauchy", 0.1), stage_loss=("huber", 0.05),
     camera_priors=lambda cams: lidar_camera_priors(cams, Rci, tci, 1e-3, 0.02)."""
     import os
@@ -1225,8 +1322,9 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
                             **({"match_select": pair_selection} if pair_selection else {}),
                             **({"device_tracks": True} if device_tracks else {}), **({"verify_matches": verify} if verify else {}),
                             images=(lambda k: D.read_image_bgr(os.path.join(img_dir, names[k]), width, height))
-                            if colorize or photo_consistency else None, **({"map_quality": map_quality} if map_quality else {}),
+                            if colorize or photo_consistency or photo_align else None, **({"map_quality": map_quality} if map_quality else {}),
                             **({"photo_consistency": photo_consistency} if photo_consistency else {}),
+                            **({"photo_align": photo_align} if photo_align else {}),
                             **({"loop_closures": loop_closures} if loop_closures else {}),
                             **({"relax": relax} if relax and loop_closures else {}),
                             **({"remove_dynamic": remove_dynamic} if remove_dynamic else {}),
@@ -1256,6 +1354,12 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
             with open(os.path.join(out_dir, "photo_consistency.json"), "w") as f:
                 json.dump({"after": out["photo_consistency"]["after"], "before": out["photo_consistency"]["before"],
                            "options": out.get("photo_options")}, f, indent=1)
+        if "photo_align" in out:
+            import json
+            plain = lambda q: q.tolist() if isinstance(q, np.ndarray) else [plain(e) for e in q] if isinstance(q, list) else \
+                {a: plain(b) for a, b in q.items()} if isinstance(q, dict) else q
+            with open(os.path.join(out_dir, "photo_align.json"), "w") as f:
+                json.dump(plain(out["photo_align"]), f, indent=1)
         if "dynamic" in out:
             import json
             with open(os.path.join(out_dir, "dynamic.json"), "w") as f:

@@ -1795,6 +1795,96 @@ int32_t lvba_photo_finish(lvba_photo_t h, lvba_photo_summary *summary, int32_t *
 int32_t lvba_photo_sums(lvba_photo_t h, int32_t *n_views, uint32_t *s1, int64_t *s2);
 void    lvba_photo_free(lvba_photo_t h);
 
+/* ---- photometric camera alignment against the coloured map (opt-in)
+ *   The direct method: the map's colours are held fixed and each camera is moved until its image agrees with them.  Alternated
+ *   with the colour fusion above it is the colour-map optimisation of Zhou & Koltun (SIGGRAPH 2014); one image against a reference
+ *   it was not fused from is feature-free localisation against the coloured map.  The rule below is this project's own
+ *   definition, restated in numpy in tests/palign_oracle.py; it is NOT pinned against anything.  csrc/palign_device.h writes every
+ *   scalar expression once, in a fixed order and without contraction: a sample's residuals, rows and weights are the same bits
+ *   under g++, numpy and gfx950; the sums over the samples are a tree on the device and are held to the summation bound.
+ *   Inputs.  n world points xyz [n][3] (float), per point a reference colour ref16 [n][3] (uint16; channels b, g, r in 1/256 grey
+ *     level, the fusion's unit: from its sums (2 S1 + n_views) / (2 n_views) in integers) and a validity byte valid [n] (0: the
+ *     point is never sampled); n_images images of width x height as uploaded (bgr, 3 bytes a texel), ONE camera model intr = (fx,
+ *     fy, cx, cy, k1, k2, p1, p2), initial Rcw [9], tcw [3] (T_cam<-world) per image, and optionally a depth set with the same
+ *     image count and size on the same device, kept alive by the caller: the occlusion test.  The depth images are those of the
+ *     INITIAL poses; they are not rendered again inside the iteration.
+ *   Sample of point X in image j at pose (R, t).  Exactly the colour fusion's: the same fate, max_depth and holes, the same (u, v),
+ *     x, y, a, b and c16 [3].  In addition the bilinear gradient from the same four texels t00 = (y, x), t10 = (y, x + 1), t01 =
+ *     (y + 1, x), t11 = (y + 1, x + 1), per channel, in grey levels per pixel:
+ *       gu = ((256 - b)(t10 - t00) + b (t11 - t01)) / 256,  gv = ((256 - a)(t01 - t00) + a (t11 - t10)) / 256
+ *     with integer numerators and one division.
+ *   Residual per channel.  r = (c16 - ref16) / 256, in grey levels.
+ *   Jacobian under the resection's left perturbation (R <- (I + [om]x) R re-orthonormalised through a unit quaternion, t <- t +
+ *     om x t + up, order (om, up)): Xc = R X + t moves by om x Xc + up.  With Jpi the 2 x 3 Jacobian of the projection at Xc, the
+ *     distortion included, and q = gu Jpi[0] + gv Jpi[1], the channel's row is (Xc x q, q).
+ *   Loss.  loss_eval of csrc/visual_loss.h on s = r^2, per channel, at loss_scale grey levels, kinds LVBA_LOSS_*: weight rho', cost
+ *     rho / 2.  Default Huber at 10 grey levels: the value of the numpy prototype this stage started from, not tuned on data.
+ *   Sums per image (LVBA_PALIGN_SUMS = 31 doubles): H = sum rho' J^T J, upper triangle by row (21); g = sum rho' J^T r (6); cost =
+ *     sum rho / 2; n_samples (a sample counts once, its three channels are three terms of the other sums); sum r^2; sum rho'.
+ *   Step: Levenberg-Marquardt per image, all images of a call in lock-step.  (H + lambda diag(max(H_aa, 1e-12))) d = -g by a 6 x 6
+ *     LDL^T; the trial pose is the perturbation d applied to the current pose.  One linearisation at the trial pose gives its mean
+ *     cost m = cost / n_samples; the trial is accepted iff n_samples >= min_samples and m_trial < m_current.  Accepted: the trial
+ *     and its H, g become current and lambda <- max(lambda / 3, 1e-9).  Rejected: lambda <- 4 lambda.  lambda starts at 1e-3.  A
+ *     pass is one linearisation, whatever its outcome: the first is at the initial pose, and an image takes at most
+ *     max_iterations passes (default 15).
+ *   Status per image.  LVBA_PALIGN_CONVERGED: an accepted step with |om| <= eps_rot (1e-7) and |up| <= eps_trans (1e-6 m).
+ *     LVBA_PALIGN_MAX_ITERATIONS: max_iterations passes without converging; the current pose is returned.
+ *     LVBA_PALIGN_TOO_FEW_SAMPLES: fewer than min_samples (default 200) samples at the initial pose.  LVBA_PALIGN_DEGENERATE: a
+ *     diagonal entry of H is not > 0, a pivot of the damped system is not > 0, or the step is not finite.
+ *     LVBA_PALIGN_OUT_OF_BOUNDS: an accepted pose is more than max_rotation_deg (default 5 degrees) or max_translation (default
+ *     0.5 m, of the camera centre) from the initial one.  With the last three the initial pose is returned bit for bit, and rmse,
+ *     cost, n_samples and information are those of the initial pose.  A finished image is skipped by the later passes.  What an
+ *     image returns depends neither on the other images of the call, nor on its place among them, nor on the batching.
+ *   lvba_palign_align, images first .. first + n - 1 (first only selects the depth images): per image Rcw_out [9], tcw_out [3],
+ *     status, iterations (passes), accepted (steps), n_samples, rmse = sqrt(sum r^2 / (3 n_samples)) in grey levels at the initial
+ *     (rmse_initial) and at the returned pose (0 without a sample), cost, information [36] = H at the returned pose.
+ *   lvba_palign_linearize: the diagnostic call, one evaluation per image at the given poses and no step: sums [n][31], the
+ *     per-image photometric residual.  lvba_palign_profile: ms [3], the device time of the uploads, the linearisation passes and
+ *     the steps, accumulated over the handle's calls.
+ *   Options (NULL: the defaults; none is tuned on recorded data): occlusion_rel, occlusion_abs, max_depth, holes and
+ *     max_batch_images as in lvba_photo_opts.
+ *   LVBA_ERR_ARG, before any device work, outputs untouched and the handle still valid: a null pointer; n < 0 or n >= 2^32; width
+ *   or height < 2; n_images < 1 or > 32 768; a depth set of another image count, size or device; non-finite intrinsics or focal
+ *   lengths <= 0; non-finite cameras; (first, n) outside [0, n_images); max_iterations outside 1 .. 1000; a negative or non-finite
+ *   threshold (occlusion_rel, occlusion_abs, max_depth, eps_rot, eps_trans, max_rotation_deg -- also above 180 --,
+ *   max_translation); an unknown loss; a loss scale that is not > 0; min_samples < 6; max_batch_images < 0.
+ *   lvba_palign_free destroys the handle.  lvba_version() is unchanged; a client detects these calls by looking lvba_palign_create
+ *   up. */
+#define LVBA_PALIGN_CONVERGED 0
+#define LVBA_PALIGN_MAX_ITERATIONS 1
+#define LVBA_PALIGN_TOO_FEW_SAMPLES 2
+#define LVBA_PALIGN_DEGENERATE 3
+#define LVBA_PALIGN_OUT_OF_BOUNDS 4
+#define LVBA_PALIGN_SUMS 31
+typedef struct lvba_palign_s *lvba_palign_t;
+typedef struct lvba_palign_opts {
+    double occlusion_rel;     /* 0.05 */
+    double occlusion_abs;     /* 0.1 m */
+    double max_depth;         /* 0 = none */
+    double loss_scale;        /* 10 grey levels */
+    double eps_rot;           /* 1e-7 rad */
+    double eps_trans;         /* 1e-6 m */
+    double max_rotation_deg;  /* 5 */
+    double max_translation;   /* 0.5 m */
+    int32_t holes;            /* 0 */
+    int32_t loss_kind;        /* LVBA_LOSS_HUBER */
+    int32_t min_samples;      /* 200; >= 6 */
+    int32_t max_iterations;   /* 15 */
+    int32_t max_batch_images; /* 0 = by free memory */
+    int32_t reserved;         /* 0 */
+} lvba_palign_opts;           /* 88 bytes */
+void    lvba_palign_default_opts(lvba_palign_opts *o);
+int32_t lvba_palign_create(int32_t device, int64_t n, const float *xyz, const uint16_t *ref16, const uint8_t *valid, int32_t n_images,
+                           int32_t width, int32_t height, const double *intr, lvba_depth_t depth, const lvba_palign_opts *o,
+                           lvba_palign_t *out);
+int32_t lvba_palign_linearize(lvba_palign_t h, int32_t first, int32_t n, const double *Rcw, const double *tcw, const uint8_t *bgr,
+                              double *sums);
+int32_t lvba_palign_align(lvba_palign_t h, int32_t first, int32_t n, const double *Rcw, const double *tcw, const uint8_t *bgr,
+                          double *Rcw_out, double *tcw_out, int32_t *status, int32_t *iterations, int32_t *accepted, int64_t *n_samples,
+                          double *rmse_initial, double *rmse, double *cost, double *information);
+int32_t lvba_palign_profile(lvba_palign_t h, double *ms);
+void    lvba_palign_free(lvba_palign_t h);
+
 #ifdef __cplusplus
 }
 #endif
