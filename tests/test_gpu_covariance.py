@@ -7,6 +7,7 @@ import pytest
 import cov_oracle as co
 import prior_oracle as po
 from conftest import HostTransport, make_problem
+from cov_oracle import worst as _worst
 
 pytestmark = pytest.mark.gpu
 
@@ -65,29 +66,6 @@ def _dense_from_blocks(N, bi, bj, blocks):
         H[6 * i:6 * i + 6, 6 * j:6 * j + 6] = b
         H[6 * j:6 * j + 6, 6 * i:6 * i + 6] = b.T
     return H
-
-
-def _worst(S, diag, pairs, blocks, avail):
-    """max over poses of |dSigma_i|_F / |Sigma_i|_F and over available pairs of |dSigma_ij|_F / sqrt(|Sigma_ii|_F |Sigma_jj|_F)"""
-    N = diag.shape[0]
-    nd = np.array([np.linalg.norm(S[6 * i:6 * i + 6, 6 * i:6 * i + 6]) for i in range(N)])
-    wd = 0.0
-    for i in range(N):
-        if nd[i] > 0:
-            wd = max(wd, np.linalg.norm(diag[i] - S[6 * i:6 * i + 6, 6 * i:6 * i + 6]) / nd[i])
-        else:
-            assert np.all(diag[i] == 0.0)
-    wp = 0.0
-    for (i, j), b, a in zip(pairs, blocks, avail):
-        if not a:
-            continue
-        ref = S[6 * i:6 * i + 6, 6 * j:6 * j + 6]
-        den = np.sqrt(nd[i] * nd[j])
-        if den == 0:
-            assert np.all(b == 0.0)
-        else:
-            wp = max(wp, np.linalg.norm(b - ref) / den)
-    return wd, wp
 
 
 def _refined(p, d, iters=30):
