@@ -46,6 +46,7 @@ SYMBOLS = [
     "lvba_sift_candidates",
     "lvba_resect_default_opts", "lvba_resect_images", "lvba_resect_hypotheses", "lvba_resect_score", "lvba_resect_lift",
     "lvba_calib_default_opts", "lvba_calib_extrinsic", "lvba_calib_linearize",
+    "lvba_calib_td_default_opts", "lvba_calib_extrinsic_td", "lvba_calib_linearize_td",
     "lvba_photo_default_opts", "lvba_photo_create", "lvba_photo_add_images", "lvba_photo_finish", "lvba_photo_sums", "lvba_photo_free",
     "lvba_palign_default_opts", "lvba_palign_create", "lvba_palign_linearize", "lvba_palign_align", "lvba_palign_profile", "lvba_palign_free",
 ]
@@ -287,6 +288,11 @@ class CalibOpts(Struct):
                 ("reserved", C.c_int64)]
 
 
+class CalibTdOpts(Struct):
+    """lvba_calib_td_opts"""
+    _fields_ = [("calib", CalibOpts), ("eps_td_s", C.c_double), ("max_abs_td_s", C.c_double), ("reserved", C.c_int64)]
+
+
 class PhotoOpts(Struct):
     """lvba_photo_opts"""
     _fields_ = [("occlusion_rel", C.c_double), ("occlusion_abs", C.c_double), ("max_depth", C.c_double), ("holes", C.c_int32),
@@ -389,7 +395,7 @@ STRUCTS = {
     "lvba_match_opts": MatchOpts, "lvba_covis_opts": CovisOpts, "lvba_trackgraph_info": TrackGraphInfo,
     "lvba_verify_opts": VerifyOpts, "lvba_sift_opts": SiftOpts, "lvba_dynamic_opts": DynamicOpts,
     "lvba_dynamic_summary": DynamicSummary, "lvba_resect_opts": ResectOpts,
-    "lvba_calib_opts": CalibOpts, "lvba_photo_opts": PhotoOpts, "lvba_photo_summary": PhotoSummary,
+    "lvba_calib_opts": CalibOpts, "lvba_calib_td_opts": CalibTdOpts, "lvba_photo_opts": PhotoOpts, "lvba_photo_summary": PhotoSummary,
     "lvba_palign_opts": PalignOpts,
 }
 
@@ -656,6 +662,11 @@ def load():
               C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(CalibOpts)]
     lib.lvba_calib_extrinsic.argtypes = _calib + [C.c_void_p] * 11
     lib.lvba_calib_linearize.argtypes = _calib + [C.c_void_p] * 5
+    lib.lvba_calib_td_default_opts.argtypes = [C.POINTER(CalibTdOpts)]
+    # lvba_calib_*'s arguments with body_twists after body_poses and td0 after tci
+    _calib_td = _calib[:3] + [C.c_void_p] + _calib[3:14] + [C.c_void_p, C.POINTER(CalibTdOpts)]
+    lib.lvba_calib_extrinsic_td.argtypes = _calib_td + [C.c_void_p] * 12
+    lib.lvba_calib_linearize_td.argtypes = _calib_td + [C.c_void_p] * 5
     lib.lvba_photo_default_opts.argtypes = [C.POINTER(PhotoOpts)]
     lib.lvba_photo_create.argtypes = [C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                       C.POINTER(PhotoOpts), C.POINTER(H)]

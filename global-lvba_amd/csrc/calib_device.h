@@ -78,10 +78,14 @@ LVBA_TRK_FN void cal_target(const TrkIntr &cam, float u, float v, const double *
     if (!(isfinite(Xb[0]) && isfinite(Xb[1]) && isfinite(Xb[2])) || !trk_undistort(cam, (double)u, (double)v, x, y)) x = y = NAN;
 }
 
+// what cal_eval forms on its way and the time-offset column (calib_td_device.h) is made of: q = R^T (Xb - t), w = R_ab q + p_ab and
+// a0, a1 = R^T g of the two residual components' gradients by Xc
+struct CalMid { double q[3], w[3], a0[3], a1[3]; };
+
 // One record at (R, t) with its pair's transform A: false where it does not count (unusable, at or behind the camera, outside the
-// gate); else r [2], the two rows J0, J1 [6] of its Jacobian in the order (om, up) and rho [3] of its loss.
-LVBA_TRK_FN bool cal_eval(const double *R, const double *t, const double *A, double x, double y, const double *Xb, const CalParams &o,
-                          double *r, double *J0, double *J1, double *rho)
+// gate); else r [2], the two rows J0, J1 [6] of its Jacobian in the order (om, up), rho [3] of its loss and m, its intermediates.
+LVBA_TRK_FN bool cal_eval_mid(const double *R, const double *t, const double *A, double x, double y, const double *Xb, const CalParams &o,
+                              double *r, double *J0, double *J1, double *rho, CalMid &m)
 {
     if (!(x == x && y == y)) return false;
     const double d0 = Xb[0] - t[0], d1 = Xb[1] - t[1], d2 = Xb[2] - t[2];
@@ -117,7 +121,17 @@ LVBA_TRK_FN bool cal_eval(const double *R, const double *t, const double *A, dou
     J1[2] = gy * cx + (h10 * Xb[1] - h11 * Xb[0]);
     J1[3] = -h10; J1[4] = gy - h11; J1[5] = gz1 - h12;
     loss_eval(o.loss_kind, o.loss_scale, s, rho);
+    m.q[0] = q0; m.q[1] = q1; m.q[2] = q2; m.w[0] = w0; m.w[1] = w1; m.w[2] = w2;
+    m.a0[0] = a00; m.a0[1] = a01; m.a0[2] = a02; m.a1[0] = a10; m.a1[1] = a11; m.a1[2] = a12;
     return true;
+}
+
+// cal_eval_mid without the intermediates
+LVBA_TRK_FN bool cal_eval(const double *R, const double *t, const double *A, double x, double y, const double *Xb, const CalParams &o,
+                          double *r, double *J0, double *J1, double *rho)
+{
+    CalMid m;
+    return cal_eval_mid(R, t, A, x, y, Xb, o, r, J0, J1, rho, m);
 }
 
 // a counted record's terms into the sums s [CAL_NS] (registers on the device: every index is a constant after unrolling)
@@ -181,66 +195,61 @@ LVBA_TRK_FN void cal_jacobi(double *A, double *V, int n)
     }
 }
 
-// the full symmetric matrix of the 21 upper-triangle sums
-LVBA_TRK_FN void cal_expand(const double *s, double *A)
+// the full symmetric n x n matrix of the n (n + 1) / 2 upper-triangle sums
+LVBA_TRK_FN void cal_expand_n(const double *s, double *A, int n)
 {
     int k = 0;
-    for (int a = 0; a < 6; ++a)
-        for (int b = a; b < 6; ++b) { A[6 * a + b] = A[6 * b + a] = s[k]; ++k; }
+    for (int a = 0; a < n; ++a)
+        for (int b = a; b < n; ++b) { A[n * a + b] = A[n * b + a] = s[k]; ++k; }
 }
 
-// The step of a job from its sums s [CAL_NS] at (R, t).  ws: CAL_WS doubles of workspace.  Fills out (n_used, rmse, cost, the
-// eigenvalues ascending -- the lower index first of a tie --, their vectors, n_held) and returns the job's state:
-//   TOO_FEW: count < min_records (eigenvalues and vectors zero, n_held 0).  DEGENERATE: the largest eigenvalue is not above
-//   CAL_EIG_FLOOR count (fx^2 + fy^2) (not > 0 up to rounding), every direction is held, or the step is not finite.
-//   Direction k is HELD where not eig[k] > min_eig_ratio * eig_max.  The step is d = -sum over the free k of v_k (v_k . g) / eig[k], the sum in ascending k.  CONVERGED where |om| <= eps_rot and |up| <=
-//   eps_trans: the step is not applied, so what is reported is of the final extrinsic.  may_step false (the iteration limit is
-//   reached): RUNNING becomes MAX_ITERATIONS without a step, for the same reason.  On RUNNING (R, t) has been retracted:
-//   R <- (I + [om]x) R through a unit quaternion, t <- t + om x t + up (resect_step's retraction).
-LVBA_TRK_FN int cal_step(const double *s, const CalParams &o, bool may_step, double *R, double *t, double *ws, CalResult &out)
+LVBA_TRK_FN void cal_expand(const double *s, double *A) { cal_expand_n(s, A, 6); }
+
+constexpr int CAL_MAX_N = 7;                        // the largest system cal_free_step takes (calib_td_device.h's)
+
+// The eigen-decomposition, the held set and the step of an n-parameter job from its upper-triangle sums H and its gradient g.
+// ws: 2 n n + 2 n doubles (A, V, the eigenvalues, the step).  Fills eig [n] ascending -- the lower index first of a tie --, vec
+// [n][n] (row k the unit vector of eig[k]) and n_held, and returns the step d [n] = -sum over the free k of v_k (v_k . g) / eig[k],
+// the sum in ascending k -- or nullptr (DEGENERATE): the largest eigenvalue is not above floor, or every direction is held (n_held
+// = n either way).  Direction k is HELD where not eig[k] > min_eig_ratio * eig_max.
+LVBA_TRK_FN const double *cal_free_step(int n, const double *H, const double *g, double min_eig_ratio, double floor, double *ws,
+                                        double *eig, double *vec, int32_t &n_held)
 {
-    const double cnt = s[CAL_CNT];
-    out.n_used = (int64_t)cnt;
-    out.cost = s[CAL_COST];
-    out.rmse = cnt > 0.0 ? sqrt(s[CAL_SSQ] / cnt) : 0.0;
-    out.n_held = 0;
-    for (int k = 0; k < 6; ++k) out.eig[k] = 0.0;
-    for (int k = 0; k < 36; ++k) out.vec[k] = 0.0;
-    if (cnt < (double)o.min_records) return CAL_TOO_FEW;
-    double *A = ws, *V = ws + 36, *lam = ws + 72, *d = ws + 78;
-    cal_expand(s, A);
-    cal_jacobi(A, V, 6);
-    int order[6];
-    for (int k = 0; k < 6; ++k) {   // insertion sort by (eigenvalue, index)
-        const double v = A[7 * k];
+    double *A = ws, *V = ws + n * n, *lam = ws + 2 * n * n, *d = lam + n;
+    cal_expand_n(H, A, n);
+    cal_jacobi(A, V, n);
+    int order[CAL_MAX_N];
+    for (int k = 0; k < n; ++k) {   // insertion sort by (eigenvalue, index)
+        const double v = A[(n + 1) * k];
         int j = k;
-        while (j > 0 && A[7 * order[j - 1]] > v) { order[j] = order[j - 1]; --j; }
+        while (j > 0 && A[(n + 1) * order[j - 1]] > v) { order[j] = order[j - 1]; --j; }
         order[j] = k;
     }
-    for (int k = 0; k < 6; ++k) {
-        lam[k] = out.eig[k] = A[7 * order[k]];
-        for (int a = 0; a < 6; ++a) out.vec[6 * k + a] = V[6 * a + order[k]];
+    for (int k = 0; k < n; ++k) {
+        lam[k] = eig[k] = A[(n + 1) * order[k]];
+        for (int a = 0; a < n; ++a) vec[n * k + a] = V[n * a + order[k]];
     }
     double top = lam[0];
-    for (int k = 1; k < 6; ++k) top = lam[k] > top ? lam[k] : top;
-    if (!(top > CAL_EIG_FLOOR * cnt * (o.fx * o.fx + o.fy * o.fy))) { out.n_held = 6; return CAL_DEGENERATE; }
-    const double bound = o.min_eig_ratio * top;
-    for (int a = 0; a < 6; ++a) d[a] = 0.0;
+    for (int k = 1; k < n; ++k) top = lam[k] > top ? lam[k] : top;
+    if (!(top > floor)) { n_held = n; return nullptr; }
+    const double bound = min_eig_ratio * top;
+    for (int a = 0; a < n; ++a) d[a] = 0.0;
     int held = 0;
-    for (int k = 0; k < 6; ++k) {
+    for (int k = 0; k < n; ++k) {
         if (!(lam[k] > bound)) { ++held; continue; }
-        const double *v = out.vec + 6 * k;
+        const double *v = vec + n * k;
         double vg = 0.0;
-        for (int a = 0; a < 6; ++a) vg += v[a] * s[CAL_G0 + a];
+        for (int a = 0; a < n; ++a) vg += v[a] * g[a];
         const double c = vg / lam[k];
-        for (int a = 0; a < 6; ++a) d[a] -= v[a] * c;
+        for (int a = 0; a < n; ++a) d[a] -= v[a] * c;
     }
-    out.n_held = held;
-    if (held == 6) return CAL_DEGENERATE;
-    const double dr = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]), dt = sqrt((d[3] * d[3] + d[4] * d[4]) + d[5] * d[5]);
-    if (!(isfinite(dr) && isfinite(dt))) return CAL_DEGENERATE;
-    if (dr <= o.eps_rot && dt <= o.eps_trans) return CAL_CONVERGED;
-    if (!may_step) return CAL_MAX_ITERATIONS;
+    n_held = held;
+    return held == n ? nullptr : d;
+}
+
+// R <- (I + [om]x) R through a unit quaternion, t <- t + om x t + up (resect_step's retraction), d = (om, up)
+LVBA_TRK_FN void cal_retract(const double *d, double *R, double *t)
+{
     double Rn[9];
     for (int c = 0; c < 3; ++c) {
         Rn[c] = R[c] + (d[1] * R[6 + c] - d[2] * R[3 + c]);
@@ -252,6 +261,33 @@ LVBA_TRK_FN int cal_step(const double *s, const CalParams &o, bool may_step, dou
     resect_orthonormalise(Rn);
     for (int e = 0; e < 9; ++e) R[e] = Rn[e];
     t[0] = tn[0]; t[1] = tn[1]; t[2] = tn[2];
+}
+
+// The step of a job from its sums s [CAL_NS] at (R, t).  ws: CAL_WS doubles of workspace.  Fills out (n_used, rmse, cost, the
+// eigenvalues ascending -- the lower index first of a tie --, their vectors, n_held) and returns the job's state:
+//   TOO_FEW: count < min_records (eigenvalues and vectors zero, n_held 0).  DEGENERATE: the largest eigenvalue is not above
+//   CAL_EIG_FLOOR count (fx^2 + fy^2) (not > 0 up to rounding), every direction is held, or the step is not finite.
+//   Held set and step: cal_free_step.  CONVERGED where |om| <= eps_rot and |up| <=
+//   eps_trans: the step is not applied, so what is reported is of the final extrinsic.  may_step false (the iteration limit is
+//   reached): RUNNING becomes MAX_ITERATIONS without a step, for the same reason.  On RUNNING (R, t) has been retracted (cal_retract).
+LVBA_TRK_FN int cal_step(const double *s, const CalParams &o, bool may_step, double *R, double *t, double *ws, CalResult &out)
+{
+    const double cnt = s[CAL_CNT];
+    out.n_used = (int64_t)cnt;
+    out.cost = s[CAL_COST];
+    out.rmse = cnt > 0.0 ? sqrt(s[CAL_SSQ] / cnt) : 0.0;
+    out.n_held = 0;
+    for (int k = 0; k < 6; ++k) out.eig[k] = 0.0;
+    for (int k = 0; k < 36; ++k) out.vec[k] = 0.0;
+    if (cnt < (double)o.min_records) return CAL_TOO_FEW;
+    const double *d = cal_free_step(6, s, s + CAL_G0, o.min_eig_ratio, CAL_EIG_FLOOR * cnt * (o.fx * o.fx + o.fy * o.fy), ws, out.eig,
+                                    out.vec, out.n_held);
+    if (!d) return CAL_DEGENERATE;
+    const double dr = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]), dt = sqrt((d[3] * d[3] + d[4] * d[4]) + d[5] * d[5]);
+    if (!(isfinite(dr) && isfinite(dt))) return CAL_DEGENERATE;
+    if (dr <= o.eps_rot && dt <= o.eps_trans) return CAL_CONVERGED;
+    if (!may_step) return CAL_MAX_ITERATIONS;
+    cal_retract(d, R, t);
     return CAL_RUNNING;
 }
 

@@ -867,8 +867,31 @@ def calibration_records(keypoints, pairs, matches, depth, Rcw, tcw, intr):
     return calibration_records_from_points(uv, pairs, matches, points, Rcw, tcw)
 
 
+def body_twists(scan_poses, scan_times, image_times):
+    """The twist of the body at every image time, for calib.refine_extrinsic_td: [M, 6] rows (om, v), om the body-frame angular
+    velocity (rad/s), v the world-frame linear velocity (m/s), from the scan segment [k, k + 1] that brackets the image (the first
+    or the last segment for an image outside the scans): om = log(R_k^T R_k+1) / dt, v = (P_k+1 - P_k) / dt.  scan_poses [n, 12]
+    = T_world<-imu at scan_times (ascending)."""
+    R, p = _mat(scan_poses)
+    ts = np.asarray(scan_times, np.float64).reshape(-1)
+    if len(ts) < 2 or len(ts) != len(R):
+        raise ValueError("body_twists needs at least two scan poses and one time per pose")
+    out = np.zeros((len(np.atleast_1d(image_times)), 6))
+    for i, t in enumerate(np.asarray(image_times, np.float64).reshape(-1)):
+        k = min(max(int(np.searchsorted(ts, t, side="right")) - 1, 0), len(ts) - 2)
+        dt = ts[k + 1] - ts[k]
+        if not dt > 0.0:
+            raise ValueError(f"scan times {k} and {k + 1} do not ascend")
+        E = R[k].T @ R[k + 1]
+        th = np.arccos(np.clip(0.5 * (np.trace(E) - 1.0), -1.0, 1.0))
+        w = 0.5 * np.array([E[2, 1] - E[1, 2], E[0, 2] - E[2, 0], E[1, 0] - E[0, 1]])
+        out[i, :3] = (w if th < 1e-9 else w * th / np.sin(th)) / dt
+        out[i, 3:] = (p[k + 1] - p[k]) / dt
+    return out
+
+
 def calibrate_extrinsic(keypoints, pairs, matches, body_poses, Rci, tci, intr, depth=None, render=None, rounds=1, starts=None, device=0,
-                        **opts):
+                        time_offset=False, twists=None, **opts):
     """What the extrinsic T_cam<-imu should be instead of (Rci, tci), from the matches and the LiDAR depths (calib.refine_extrinsic;
     DESIGN.md §10o).  body_poses [M, 12]: T_world<-imu at the image times (the LiDAR-derived image poses).  depth: a
     visual.DepthImages rendered at camera_from_imu(body_poses, Rci, tci), used by the first round and left to the caller; render:
@@ -877,13 +900,20 @@ def calibrate_extrinsic(keypoints, pairs, matches, body_poses, Rci, tci, intr, d
     rounds: how many times records are built and the extrinsic solved, each from the last result; a round that does not come back
     converged or at its iteration limit ends the loop and its extrinsic is not taken.  starts, opts: calib.refine_extrinsic's.
     Returns calib.summary of the last round against the given extrinsic (Rci, tci there are the refined ones; rotation_deg and
-    translation_m the total change) plus n_records and rounds = the summary of every round against its own start."""
+    translation_m the total change) plus n_records and rounds = the summary of every round against its own start.
+    time_offset=True (needs twists [M, 6], body_twists): the camera-LiDAR time offset td is refined with the extrinsic
+    (calib.refine_extrinsic_td).  Every round lifts its records at camera_from_imu(calib.shift_poses(body_poses, twists, td), R, t)
+    and calls the solver with the ORIGINAL poses and td0 = td, so the offset accumulates across rounds; the report's time_offset_s
+    and std_td_s are then numbers, and time_offset_rounds lists td after every round.  Off (the default), no _td entry point is
+    looked up and the report is what it always was, with time_offset_s = std_td_s = None."""
     from . import calib as CB
+    if time_offset and twists is None:
+        raise ValueError("calibrate_extrinsic(time_offset=True) needs twists (pipeline.body_twists)")
     R0, t0 = np.asarray(Rci, np.float64).reshape(3, 3), np.asarray(tci, np.float64).reshape(3)
-    R, t = R0, t0
-    per, last = [], None
+    R, t, td = R0, t0, 0.0
+    per, last, tds = [], None, []
     for k in range(max(1, int(rounds))):
-        Rcw, tcw = camera_from_imu(body_poses, R, t)
+        Rcw, tcw = camera_from_imu(CB.shift_poses(body_poses, twists, td) if time_offset else body_poses, R, t)
         dk = depth if k == 0 and depth is not None else None
         own = dk is None
         if own:
@@ -895,15 +925,24 @@ def calibrate_extrinsic(keypoints, pairs, matches, body_poses, Rci, tci, intr, d
         finally:
             if own:
                 dk.close()
-        Rn, tn, rep = CB.refine_extrinsic(records, table, body_poses, intr, R, t, starts=starts if k == 0 else None, device=device, **opts)
+        if time_offset:
+            Rn, tn, tdn, rep = CB.refine_extrinsic_td(records, table, body_poses, twists, intr, R, t, td, starts=starts if k == 0 else None,
+                                                      device=device, **opts)
+        else:
+            Rn, tn, rep = CB.refine_extrinsic(records, table, body_poses, intr, R, t, starts=starts if k == 0 else None, device=device, **opts)
         per.append(dict(CB.summary(rep, R, t), n_records=int(len(records["pair"]))))
         if int(rep["status"]) not in (CB.CONVERGED, CB.MAX_ITERATIONS):
             if last is None:
                 last = rep
             break
         R, t, last = Rn, tn, rep
-    out = CB.summary(dict(last, Rci=R, tci=t), R0, t0)
+        if time_offset:
+            td = float(tdn)
+            tds.append(td)
+    out = CB.summary(dict(last, Rci=R, tci=t, **({"td": td} if time_offset else {})), R0, t0)
     out.update(n_records=per[-1]["n_records"], rounds=per)
+    if time_offset:
+        out["time_offset_rounds"] = tds
     return out
 
 
@@ -1021,7 +1060,9 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
     match_select or images rendered the same way; the output holds camera_check, per image how far the pose the images ask for
     lies from the one the trajectory and the extrinsic give.  Nothing downstream reads it.
     calibrate_extrinsic: False (off: nothing is launched and no entry point of the stage is called), True, "apply", or a dict of
-    pipeline.calibrate_extrinsic's keywords (rounds, starts, calib.calib_opts' options) with an optional apply=True: once the
+    pipeline.calibrate_extrinsic's keywords (rounds, starts, calib.calib_opts' options; time_offset=True refines the camera-LiDAR
+    time offset too, with the twists of the refined LiDAR trajectory (body_twists) unless twists are given, and with apply and a
+    converged result the visual stage gets the image poses shifted by it: poses_shifted in the report) with an optional apply=True: once the
     matches in force are final, the extrinsic is refined from them and the LiDAR depths (pipeline.calibrate_extrinsic) at the
     LiDAR-derived image poses, and the output holds extrinsic, the report.  True reports only: nothing downstream reads it.
     "apply": the visual stage -- camera poses, depth images, track fusion, the start of the BA, the colours -- runs with the
@@ -1106,12 +1147,15 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
                 finally:
                     if dk is not depth:
                         dk.close()
+            x_orig_v, image_poses_v = x_orig, image_poses    # what the visual stage derives its image poses from
             if calibrate_extrinsic:
                 ce = dict(calibrate_extrinsic) if isinstance(calibrate_extrinsic, dict) else {}
                 apply = bool(ce.pop("apply", False)) or calibrate_extrinsic == "apply"
                 if apply and depth is None:
                     raise ValueError("calibrate_extrinsic='apply' needs the matches and depth images of match_depth or match_select")
                 cam_k = update_camera_poses_from_lidar(out["poses"], x_orig, scan_times, image_times, image_poses)
+                if ce.get("time_offset") and ce.get("twists") is None:
+                    ce["twists"] = body_twists(out["poses"], scan_times, image_times)   # of the refined LiDAR trajectory
                 out["extrinsic"] = _calibrate_extrinsic(
                     keypoints, pairs, matches, cam_k, Rci, tci, intr, depth=depth, device=device,
                     render=lambda Rk, tk: V.DepthImages.render(scans, out["poses"], scan_times, image_times, Rk, tk, intr, width, height,
@@ -1121,8 +1165,16 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
                     Rci, tci = np.array(out["extrinsic"]["Rci"]), np.array(out["extrinsic"]["tci"])
                     depth.close()            # rendered at the old extrinsic: the visual stage renders its own
                     depth = None
+                if ce.get("time_offset"):
+                    out["extrinsic"]["poses_shifted"] = out["extrinsic"]["applied"]
+                    if out["extrinsic"]["applied"]:
+                        # the image poses the later stages get are the ones at t + td, handed on as they are: x_orig = the refined
+                        # scans makes update_camera_poses_from_lidar the identity
+                        from . import calib as CB
+                        image_poses_v = CB.shift_poses(cam_k, ce["twists"], out["extrinsic"]["time_offset_s"])
+                        x_orig_v = out["poses"]
             if enable_visual_ba:
-                out["visual"] = run_visual_ba_with_lidar_assist(scans, out["poses"], x_orig, scan_times, image_times, image_poses, Rci,
+                out["visual"] = run_visual_ba_with_lidar_assist(scans, out["poses"], x_orig_v, scan_times, image_times, image_poses_v, Rci,
                                                                 tci, intr, width, height, keypoints, pairs, matches,
                                                                 camera_priors=camera_priors, **({"depth": depth} if depth is not None else {}),
                                                                 **({"device_tracks": True} if device_tracks else {}), **c)

@@ -1728,6 +1728,59 @@ int32_t lvba_calib_linearize(int32_t device, int32_t n_images, const double *bod
                              const double *Xb, int32_t n_jobs, const double *Rci, const double *tci, const lvba_calib_opts *o, double *H,
                              double *g, double *cost, int64_t *n_used, double *sum_sq);
 
+/* ---- the camera-LiDAR time offset as a seventh parameter of the extrinsic refinement (opt-in; DESIGN.md §10o "time offset")
+ *   The rule above with one more unknown, td (seconds): the image stamped t was taken at t + td.  Everything not named here is
+ *   the 6-parameter rule's, unchanged; restated in numpy in tests/calib_td_oracle.py.  fp64, no contraction; outside the loss only
+ *   +, -, *, / and sqrt: a record's terms are the same bits under g++, numpy and gfx950.
+ *   New input.  body_twists [n_images][6], a row (om, v) per image: om the body-frame angular velocity (rad/s), v the world-frame
+ *     linear velocity (m/s), each taken as constant around its image.
+ *   Body pose of image j at td.  th = td om, s = 1 + ((th0^2 + th1^2) + th2^2) / 4, C = I + ([th]x + [th]x^2 / 2) / s (the Cayley
+ *     map: an exact rotation about om by 2 atan(td |om| / 2), no sin or cos, whose bits differ between libms); R_j(td) = R_j C,
+ *     P_j(td) = P_j + td v_j.
+ *   Pair table, per job and per iteration, 21 doubles per (job, pair): A(td) = (R_ab | p_ab) of the two poses at td (12);
+ *     om'_a and om'_b with om' = om / (1 + td^2 |om|^2 / 4), the exact rate of the Cayley rotation (dC/dtd = C [om']x); dv =
+ *     R_a(td)^T (v_b - v_a).
+ *   Record.  r, the first six entries of both Jacobian rows and the loss are the 6-parameter rule's at A(td); counting, gate and
+ *     loss are unchanged.  With its q = R^T (Xb - t), w = R_ab q + p_ab and a_k = R^T g_k (g_k the gradient of r_k by Xc):
+ *       dw = (R_ab (om'_b x q) - om'_a x w) + dv,   J_k[6] = (a_k0 dw0 + a_k1 dw1) + a_k2 dw2.
+ *   Sums.  LVBA_CALIB_TD_SUMS = 39: H upper triangle by row (28), g (7), cost, the count, sum |r|^2, sum rho'.
+ *   Step.  The 6-parameter step at n = 7, order (om, up, td): eigenvalues ascending, direction k HELD where not lambda_k >
+ *     min_eig_ratio lambda_max, the step in the free span summed in ascending k, the same retraction and td <- td + d[6].
+ *     CONVERGED also needs |d[6]| <= eps_td_s (default 1e-10 s, on eps_rot's reasoning).  The DEGENERATE floor is unchanged.
+ *     LVBA_CALIB_TD_OUT_OF_RANGE: a step would leave |td| > max_abs_td_s (default 0.2 s: beyond it a constant twist is no
+ *     description of the motion; not tuned on data).  That step is not applied and the job returns its start values (Rci, tci,
+ *     td0) bit for bit; n_used, rmse_px, cost, the eigen-decomposition and information are of the linearisation the step came from.
+ *     Twists that are all zero leave J[6] exactly 0: the job returns the 6-parameter call's extrinsic, status and iterations, td0
+ *     unchanged, and one more held direction.  A body whose twist is the same in its own frame at every image (poses exp(k dt xi))
+ *     has an A(td) that does not depend on td: the td axis is held beside the screw's two.
+ *   Jobs.  Each job has its own (Rci, tci, td0); lock-step over the same records; a job's bytes depend neither on the batch nor
+ *     on its place in it.
+ *   lvba_calib_extrinsic_td: lvba_calib_extrinsic's arguments plus body_twists and td0 [n_jobs]; its outputs plus td_out
+ *     [n_jobs], with eigenvalues [7], eigenvectors [49] (order (om, up, td)) and information [49] per job.
+ *   lvba_calib_linearize_td: H [n_jobs][49], g [7], cost, n_used, sum_sq at (Rci, tci, td0), no step.
+ *   LVBA_ERR_ARG (nothing written): everything lvba_calib_extrinsic refuses; null or non-finite twists; a null, non-finite or
+ *   out-of-range td0 (|td0| > max_abs_td_s); eps_td_s negative or NaN; max_abs_td_s not > 0.  lvba_version() is unchanged; a client
+ *   detects these calls by looking lvba_calib_extrinsic_td up. */
+#define LVBA_CALIB_TD_OUT_OF_RANGE 4
+#define LVBA_CALIB_TD_SUMS 39
+typedef struct lvba_calib_td_opts {
+    lvba_calib_opts calib;   /* lvba_calib_default_opts */
+    double eps_td_s;         /* 1e-10 s */
+    double max_abs_td_s;     /* 0.2 s */
+    int64_t reserved;        /* 0 */
+} lvba_calib_td_opts;        /* 88 bytes */
+void    lvba_calib_td_default_opts(lvba_calib_td_opts *o);
+int32_t lvba_calib_extrinsic_td(int32_t device, int32_t n_images, const double *body_poses, const double *body_twists, const double *intr,
+                                int32_t n_pairs, const int32_t *img_a, const int32_t *img_b, int64_t n_records, const int32_t *pair,
+                                const float *uv_a, const double *Xb, int32_t n_jobs, const double *Rci, const double *tci, const double *td0,
+                                const lvba_calib_td_opts *o, double *Rci_out, double *tci_out, double *td_out, int32_t *status,
+                                int32_t *iterations, int64_t *n_used, double *rmse_px, double *cost, int32_t *n_held, double *eigenvalues,
+                                double *eigenvectors, double *information);
+int32_t lvba_calib_linearize_td(int32_t device, int32_t n_images, const double *body_poses, const double *body_twists, const double *intr,
+                                int32_t n_pairs, const int32_t *img_a, const int32_t *img_b, int64_t n_records, const int32_t *pair,
+                                const float *uv_a, const double *Xb, int32_t n_jobs, const double *Rci, const double *tci, const double *td0,
+                                const lvba_calib_td_opts *o, double *H, double *g, double *cost, int64_t *n_used, double *sum_sq);
+
 /* ---- multi-view colour fusion and photometric consistency of the map (opt-in)
  *   Every map point is projected into every image that sees it, with the occlusion test of the co-visibility stage; the colour is
  *   sampled there; the mean over the views is the fused colour and the spread is the photometric consistency: a number without

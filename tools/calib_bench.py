@@ -2,6 +2,7 @@
 the same bytes in the same run.
 
     python tools/calib_bench.py [--records 100000 1000000 10000000] [--jobs 1 8] [--repeat 5] [--iterations 10 510]
+                                [--time-offset] [--out FILE]
 
 Prints one JSON line.  An iteration is one launch of calib_linearize_kernel (grid (workgroups, jobs)), one of calib_step_kernel and
 one synchronise; it reads 44 bytes per record per job (pair 4, target 16, point 24).  The call also uploads the records and
@@ -12,7 +13,10 @@ call runs to its limit), best of --repeat each after a warm-up, divided by the d
 every job: the rate is what the caches deliver, not HBM traffic).  "copy_gbs": a device-to-device copy (torch, timed by device
 events, best of --repeat after a warm-up) of a buffer of 44 n bytes, counted as read plus write, 88 n bytes.  "share_of_copy" =
 read_gbs / copy_gbs for jobs = 1: the share of the bandwidth a plain copy reaches on this device in this run that the iteration
-reaches.  The kernels' own times come from a run under `rocprofv3 --kernel-trace --stats`.  Needs a HIP device."""
+reaches.  The kernels' own times come from a run under `rocprofv3 --kernel-trace --stats`.  --time-offset: every (records, jobs)
+entry gains "td", the same measurement of lvba_calib_extrinsic_td (calib_td_pairs_kernel, calib_td_linearize_kernel,
+calib_td_step_kernel; 39 sums instead of 31 and one more small launch) over the same records with seeded twists, in the same run,
+and "td_over_6" = its iter_ms over the 6-parameter iter_ms.  --out FILE also writes the JSON there.  Needs a HIP device."""
 import argparse
 import importlib
 import json
@@ -64,6 +68,8 @@ def main():
     ap.add_argument("--jobs", type=int, nargs="+", default=[1, 8])
     ap.add_argument("--repeat", type=int, default=5)
     ap.add_argument("--iterations", type=int, nargs=2, default=[10, 510])
+    ap.add_argument("--time-offset", action="store_true")
+    ap.add_argument("--out")
     args = ap.parse_args()
     import torch                                                                  # first: its HIP runtime must be the process's
     L = importlib.import_module("global-lvba_amd._lib")
@@ -74,6 +80,9 @@ def main():
     import calib_oracle as co
     base = cc.make("general", M=10, per_pair=(min(max(args.records), 1000000) + 33) // 34, span=2, seed=21, noise_px=0.5, outliers=0.2)
     out = dict(bytes_per_record=BYTES_PER_RECORD, iterations=args.iterations, sizes=[])
+    if args.time_offset:
+        import calib_td_cases as tc
+        twists = tc.seeded_twists("general", base["poses"], np.random.default_rng(22))
     k0, k1 = args.iterations
     for n in args.records:
         rep = max(1, (n + len(base["pair"]) - 1) // len(base["pair"]))
@@ -97,9 +106,22 @@ def main():
                      ns_per_record_job=round(1e6 * it / (n * J), 4))
             if J == 1:
                 e["share_of_copy"] = round(read / gbs, 3)
+            if args.time_offset:
+                run_td = lambda k: CB.refine_jobs_td(rec, table, base["poses"], twists, base["intr"], R, t, 0.0, max_iterations=k, eps_rot=0.0,
+                                                     eps_trans=0.0, eps_td_s=0.0)
+                done = run_td(k1)
+                assert (done["iterations"] == k1).all() and (done["status"] == CB.MAX_ITERATIONS).all(), (done["iterations"], done["status"])
+                td0, td1 = best_ms(lambda: run_td(k0), args.repeat), best_ms(lambda: run_td(k1), args.repeat)
+                it_td = (td1 - td0) / (k1 - k0)
+                e["td"] = dict(call_ms=[round(td0, 3), round(td1, 3)], iter_ms=round(it_td, 4),
+                               read_gbs=round(BYTES_PER_RECORD * n * J / (it_td * 1e6), 1), ns_per_record_job=round(1e6 * it_td / (n * J), 4))
+                e["td_over_6"] = round(it_td / it, 3)
             row["jobs"].append(e)
         out["sizes"].append(row)
     print(json.dumps(out))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(out, f, indent=1)
 
 
 if __name__ == "__main__":
