@@ -49,6 +49,8 @@ SYMBOLS = [
     "lvba_calib_td_default_opts", "lvba_calib_extrinsic_td", "lvba_calib_linearize_td",
     "lvba_photo_default_opts", "lvba_photo_create", "lvba_photo_add_images", "lvba_photo_finish", "lvba_photo_sums", "lvba_photo_free",
     "lvba_palign_default_opts", "lvba_palign_create", "lvba_palign_linearize", "lvba_palign_align", "lvba_palign_profile", "lvba_palign_free",
+    "lvba_expo_default_opts", "lvba_expo_create", "lvba_expo_sums", "lvba_expo_solve", "lvba_expo_profile", "lvba_expo_free",
+    "lvba_photo_add_images_gains",
 ]
 
 OK, ERR_ARG, ERR_DEVICE, ERR_NOMEM, ERR_UNSUPPORTED, ERR_DIST, ERR_STATE = 0, -1, -2, -3, -4, -5, -6
@@ -313,6 +315,14 @@ class PalignOpts(Struct):
                 ("max_batch_images", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ExpoOpts(Struct):
+    """lvba_expo_opts"""
+    _fields_ = [("occlusion_rel", C.c_double), ("occlusion_abs", C.c_double), ("max_depth", C.c_double), ("min_gain", C.c_double),
+                ("max_gain", C.c_double), ("max_offset", C.c_double), ("holes", C.c_int32), ("model", C.c_int32), ("sat_lo", C.c_int32),
+                ("sat_hi", C.c_int32), ("gate", C.c_int32), ("min_samples", C.c_int32), ("min_spread", C.c_int32),
+                ("max_batch_images", C.c_int32)]
+
+
 class SiftOpts(Struct):
     """lvba_sift_opts"""
     _fields_ = [("first_octave", C.c_int32), ("n_intervals", C.c_int32), ("sigma0", C.c_double), ("dog_threshold", C.c_double),
@@ -396,7 +406,7 @@ STRUCTS = {
     "lvba_verify_opts": VerifyOpts, "lvba_sift_opts": SiftOpts, "lvba_dynamic_opts": DynamicOpts,
     "lvba_dynamic_summary": DynamicSummary, "lvba_resect_opts": ResectOpts,
     "lvba_calib_opts": CalibOpts, "lvba_calib_td_opts": CalibTdOpts, "lvba_photo_opts": PhotoOpts, "lvba_photo_summary": PhotoSummary,
-    "lvba_palign_opts": PalignOpts,
+    "lvba_palign_opts": PalignOpts, "lvba_expo_opts": ExpoOpts,
 }
 
 _INTS = (C.c_int32, C.c_int64, C.c_uint64)
@@ -684,6 +694,15 @@ def load():
     lib.lvba_palign_profile.argtypes = [H, C.c_void_p]
     lib.lvba_palign_free.argtypes = [H]
     lib.lvba_palign_free.restype = None
+    lib.lvba_expo_default_opts.argtypes = [C.POINTER(ExpoOpts)]
+    lib.lvba_expo_create.argtypes = [C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                     C.c_void_p, C.POINTER(ExpoOpts), C.POINTER(H)]
+    lib.lvba_expo_sums.argtypes = _palign + [C.c_void_p, C.c_void_p]
+    lib.lvba_expo_solve.argtypes = [C.c_int32, C.c_void_p, C.POINTER(ExpoOpts), C.c_void_p, C.c_void_p]
+    lib.lvba_expo_profile.argtypes = [H, C.c_void_p]
+    lib.lvba_expo_free.argtypes = [H]
+    lib.lvba_expo_free.restype = None
+    lib.lvba_photo_add_images_gains.argtypes = _palign + [C.c_void_p]
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if name.endswith("_default_opts") or name in ("lvba_depth_destroy", "lvba_colorize_destroy"):     # these return void

@@ -27,6 +27,7 @@
 #include "voxel_internal.h"
 #include "image_set.h"
 #include "photo_device.h"
+#include "expo_device.h"
 #include "wave_ops.h"
 #include "../../include/lvba_hip.h"
 
@@ -59,13 +60,17 @@ namespace {
 constexpr int PHOTO_BLOCK = 256; // the sample kernel's chunk of points
 
 // images 0 .. B - 1 of the batch: Rcw [B][9], tcw [B][3], bgr [B][H][W][3] as uploaded; depth0 = the depth image of the batch's
-// first image (null: no occlusion test).  The counters of point i are added to n_views [i], s1 [i][3], s2 [i][3].
+// first image (null: no occlusion test).  The counters of point i are added to n_views [i], s1 [i][3], s2 [i][3].  GAINS: the
+// exposure compensation (expo_device.h) -- gains [B][3][2] depend on the loop counter alone, scalar loads like the pose, and
+// every channel of a sample goes through expo_apply before it is added; the plain instantiation never reads `gains` and is the
+// kernel it was (DESIGN.md §10r has the resource figures of both).
+template <bool GAINS>
 __global__ __launch_bounds__(PHOTO_BLOCK) void photo_sample_kernel(int64_t n, const float *__restrict__ xyz, int B,
                                                                    const double *__restrict__ Rcw, const double *__restrict__ tcw,
                                                                    const uint8_t *__restrict__ bgr, const float *__restrict__ depth0,
                                                                    const TrkIntr cam, const PhotoRule o, int W, int H,
                                                                    int32_t *__restrict__ n_views, uint32_t *__restrict__ s1,
-                                                                   int64_t *__restrict__ s2)
+                                                                   int64_t *__restrict__ s2, const int64_t *__restrict__ gains)
 {
     const int64_t i = (int64_t)blockIdx.x * PHOTO_BLOCK + threadIdx.x;
     if (i >= n) return; // nothing below synchronises the workgroup
@@ -80,8 +85,14 @@ __global__ __launch_bounds__(PHOTO_BLOCK) void photo_sample_kernel(int64_t n, co
         const float *__restrict__ db = depth0 ? depth0 + (int64_t)b * npix : nullptr;
         int32_t c16[3];
         if (photo_sample(cam, db, W, H, Rcw + 9 * (int64_t)b, tcw + 3 * (int64_t)b, X, o,
-                         [&](int y, int x) { return photo_texel_of(tb + 3 * ((int64_t)y * W + x)); }, c16))
+                         [&](int y, int x) { return photo_texel_of(tb + 3 * ((int64_t)y * W + x)); }, c16)) {
+            if (GAINS) {
+                const int64_t *__restrict__ g = gains + 6 * (int64_t)b;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) c16[k] = expo_apply(g[2 * k], g[2 * k + 1], c16[k]);
+            }
             photo_add(acc, c16);
+        }
     }
     if (acc.n == 0) return;
     n_views[i] += acc.n;
@@ -186,7 +197,9 @@ extern "C" int32_t lvba_photo_create(int32_t device, int64_t n, const float *xyz
     return LVBA_OK;
 }
 
-extern "C" int32_t lvba_photo_add_images(lvba_photo_t h, int32_t first, int32_t n, const double *Rcw, const double *tcw, const uint8_t *bgr)
+// Both entry points.  gains [n][3][2] or null: the plain kernel.
+static int32_t photo_add_images(lvba_photo_t h, int32_t first, int32_t n, const double *Rcw, const double *tcw, const uint8_t *bgr,
+                                const int64_t *gains)
 {
     if (!h) return lvba_fail(LVBA_ERR_ARG, "null handle");
     if (first < 0 || n < 0 || (int64_t)first + n > h->n_images || (n > 0 && first >= h->n_images))
@@ -197,6 +210,8 @@ extern "C" int32_t lvba_photo_add_images(lvba_photo_t h, int32_t first, int32_t 
     TRY(check_translations_finite(tcw, 0, n));
     for (int k = 0; k < n; ++k)
         if (h->added[(size_t)first + k]) return lvba_fail(LVBA_ERR_ARG, "image %d was added before", first + k);
+    if (gains && !expo_gains_ok(gains, 3 * (int64_t)n))
+        return lvba_fail(LVBA_ERR_ARG, "gains: A outside [2^14, 2^18] or |B| above 2^16 * 65280");
     HIPCHK(hipSetDevice(h->device));
     const int64_t npix = (int64_t)h->width * h->height;
     // the batch: the uploaded bytes of B images
@@ -210,21 +225,24 @@ extern "C" int32_t lvba_photo_add_images(lvba_photo_t h, int32_t first, int32_t 
     HIPCHK(sg.acquire());
     const hipStream_t s = sg.s;
     EventTimer<3> ev;
-    DevArr<uint8_t> d_img(s); DevArr<double> d_R(s), d_t(s);
+    DevArr<uint8_t> d_img(s); DevArr<double> d_R(s), d_t(s); DevArr<int64_t> d_g(s);
     HIPCHK(d_img.alloc(3 * (size_t)npix * (size_t)B));
     HIPCHK(d_R.alloc(9 * (size_t)B)); HIPCHK(d_t.alloc(3 * (size_t)B));
+    if (gains) HIPCHK(d_g.alloc(6 * (size_t)B));
     for (int64_t b0 = 0; b0 < n; b0 += B) {
         const int nb = (int)std::min<int64_t>(B, n - b0);
         ev.rec(0, s);
         HIPCHK(hipMemcpyAsync(d_img, bgr + 3 * npix * b0, 3 * (size_t)npix * nb, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(d_R, Rcw + 9 * b0, d_R.bytes(9 * (size_t)nb), hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(d_t, tcw + 3 * b0, d_t.bytes(3 * (size_t)nb), hipMemcpyHostToDevice, s));
+        if (gains) HIPCHK(hipMemcpyAsync(d_g, gains + 6 * b0, d_g.bytes(6 * (size_t)nb), hipMemcpyHostToDevice, s));
         ev.rec(1, s);
         if (h->n > 0) {
             const float *depth0 = h->depth ? h->depth->d_depth + ((int64_t)first + b0) * npix : nullptr;
-            photo_sample_kernel<<<grid_for(h->n, PHOTO_BLOCK), PHOTO_BLOCK, 0, s>>>(h->n, h->xyz, nb, d_R, d_t, d_img, depth0, h->cam,
-                                                                                    h->rule, h->width, h->height, h->n_views, h->s1,
-                                                                                    h->s2);
+            const auto kernel = gains ? photo_sample_kernel<true> : photo_sample_kernel<false>;
+            kernel<<<grid_for(h->n, PHOTO_BLOCK), PHOTO_BLOCK, 0, s>>>(h->n, h->xyz, nb, d_R, d_t, d_img, depth0, h->cam, h->rule, h->width,
+                                                                       h->height, h->n_views, h->s1, h->s2,
+                                                                       gains ? (const int64_t *)d_g : nullptr);
             HIPCHK(hipGetLastError());
         }
         ev.rec(2, s);
@@ -233,6 +251,17 @@ extern "C" int32_t lvba_photo_add_images(lvba_photo_t h, int32_t first, int32_t 
         for (int k = 0; k < nb; ++k) h->added[(size_t)first + (size_t)b0 + k] = 1;
     }
     return LVBA_OK;
+}
+
+extern "C" int32_t lvba_photo_add_images(lvba_photo_t h, int32_t first, int32_t n, const double *Rcw, const double *tcw, const uint8_t *bgr)
+{
+    return photo_add_images(h, first, n, Rcw, tcw, bgr, nullptr);
+}
+
+extern "C" int32_t lvba_photo_add_images_gains(lvba_photo_t h, int32_t first, int32_t n, const double *Rcw, const double *tcw,
+                                               const uint8_t *bgr, const int64_t *gains)
+{
+    return photo_add_images(h, first, n, Rcw, tcw, bgr, gains);
 }
 
 extern "C" int32_t lvba_photo_finish(lvba_photo_t h, lvba_photo_summary *summary, int32_t *n_views, uint8_t *rgb, double *sigma)

@@ -54,6 +54,15 @@ struct SumStepI32 { // integers add exactly: the order is of no account
     template <int CTRL, int ROW_MASK>
     static __device__ __forceinline__ int step(int v) { return v + dpp_i32<CTRL, ROW_MASK>(0, v); }
 };
+struct SumStepI64 { // the same in 64 bits, as two 32-bit halves through the DPP path and one 64-bit add
+    template <int CTRL, int ROW_MASK>
+    static __device__ __forceinline__ unsigned long long step(unsigned long long v)
+    {
+        const unsigned lo = (unsigned)dpp_i32<CTRL, ROW_MASK>(0, (int)(unsigned)v);
+        const unsigned hi = (unsigned)dpp_i32<CTRL, ROW_MASK>(0, (int)(unsigned)(v >> 32));
+        return v + (((unsigned long long)hi << 32) | lo);
+    }
+};
 struct SumStepF64 {
     template <int CTRL, int ROW_MASK>
     static __device__ __forceinline__ double step(double v) { return v + dpp_f64<CTRL, ROW_MASK>(0.0, v); }

@@ -42,15 +42,22 @@ class PhotoMap(L.Handle):
         L.check(self.lib.lvba_photo_create(int(device), self.n, xyz.ctypes.data, self.n_images, self.width, self.height, intr.ctypes.data,
                                            depth._h if depth is not None else None, C.byref(o), C.byref(self._h)))
 
-    def add_images(self, first, Rcw, tcw, bgr):
-        """images first .. first + m - 1: Rcw [m, 3, 3], tcw [m, 3] (T_cam<-world); bgr [m, height, width, 3] uint8."""
+    def add_images(self, first, Rcw, tcw, bgr, gains=None):
+        """images first .. first + m - 1: Rcw [m, 3, 3], tcw [m, 3] (T_cam<-world); bgr [m, height, width, 3] uint8.  gains: None, or
+        the exposure gains int64 [m, 3, 2] of these images (expo.estimate_exposure), applied to every sample."""
         R = np.ascontiguousarray(Rcw, np.float64).reshape(-1, 9)
         t = np.ascontiguousarray(tcw, np.float64).reshape(-1, 3)
         img = np.ascontiguousarray(bgr, np.uint8)
         m = len(R)
         if len(t) != m or img.shape != (m, self.height, self.width, 3):
             raise ValueError(f"{m} rotations, {len(t)} translations, bgr {img.shape} (want [{m}, {self.height}, {self.width}, 3])")
-        L.check(self.lib.lvba_photo_add_images(self._h, int(first), m, R.ctypes.data, t.ctypes.data, img.ctypes.data))
+        if gains is None:                        # (the plain entry point: lvba_photo_add_images_gains is not looked up)
+            L.check(self.lib.lvba_photo_add_images(self._h, int(first), m, R.ctypes.data, t.ctypes.data, img.ctypes.data))
+            return
+        g = np.ascontiguousarray(gains, np.int64)
+        if g.shape != (m, 3, 2):
+            raise ValueError(f"gains {g.shape} (want [{m}, 3, 2])")
+        L.check(self.lib.lvba_photo_add_images_gains(self._h, int(first), m, R.ctypes.data, t.ctypes.data, img.ctypes.data, g.ctypes.data))
 
     def finish(self):
         """dict(summary, n_views int32 [n], rgb uint8 [n, 3], sigma float64 [n]: NaN below min_views) of the images added so far"""
@@ -66,9 +73,10 @@ class PhotoMap(L.Handle):
         return nv, s1, s2
 
 
-def photo_consistency(points, images, Rcw, tcw, intr, width, height, depth=None, chunk=16, device=0, **opts):
+def photo_consistency(points, images, Rcw, tcw, intr, width, height, depth=None, chunk=16, device=0, gains=None, **opts):
     """PhotoMap over all images, read `chunk` at a time: images is an array [M, height, width, 3] or a callable k -> [height,
-    width, 3].  Returns finish()'s dict, with the options under "options"."""
+    width, 3].  gains: None, or the exposure gains int64 [M, 3, 2] of all images.  Returns finish()'s dict, with the options under
+    "options"."""
     R = np.ascontiguousarray(Rcw, np.float64).reshape(-1, 9)
     t = np.ascontiguousarray(tcw, np.float64).reshape(-1, 3)
     M = len(R)
@@ -76,7 +84,7 @@ def photo_consistency(points, images, Rcw, tcw, intr, width, height, depth=None,
         for k0 in range(0, M, max(int(chunk), 1)):
             k1 = min(M, k0 + max(int(chunk), 1))
             bgr = np.stack([np.asarray(images(k), np.uint8) for k in range(k0, k1)]) if callable(images) else images[k0:k1]
-            pm.add_images(k0, R[k0:k1], t[k0:k1], bgr)
+            pm.add_images(k0, R[k0:k1], t[k0:k1], bgr, **({} if gains is None else dict(gains=np.asarray(gains, np.int64)[k0:k1])))
         out = pm.finish()
         out["options"] = dict(pm.options)
     return out

@@ -373,18 +373,24 @@ def map_quality(scans, after, before=None, **kw):
 
 
 def photo_consistency(scans, scan_times, image_times, images, intr, width, height, after, before=None, points_after=None,
-                      points_before=None, **opts):
+                      points_before=None, exposure=None, **opts):
     """Multi-view colour fusion and photometric consistency (photo.photo_consistency) of the points points_after
     under the pose set after = (scan_poses [n,12], Rcw [m,3,3], tcw [m,3]), as for colorize_maps, and of points_before under
     `before` when both are given.  For each set the depth images are rendered at that set's scan poses and cameras
     (DepthImages.render: the occlusion test), that set's points are evaluated against all images (an array or a callable k ->
     [H,W,3], read in chunks), and what was opened is closed.  opts: photo.photo_opts' options, and depth_half_window_s, depth_voxel
     and chunk (DEFAULTS' values and 16).  Returns {"after": dict(summary, n_views, rgb, sigma, options), "before": ... or None}.
-    The spread summary["mean_sigma"] drops when cameras, extrinsic and trajectory agree with the images."""
+    The spread summary["mean_sigma"] drops when cameras, extrinsic and trajectory agree with the images.
+    exposure: None (off: nothing of the stage is launched, its module is not imported and no entry point of it is called), True,
+    or a dict of expo.estimate_exposure's keywords (rounds, expo.expo_opts' options): per-image exposure gains
+    are estimated on the `after` set and applied to the `after` and the `before` evaluation alike -- a different compensation
+    must not fake a change of spread.  Each set's dict then is the compensated evaluation and also holds "summary_raw", the
+    summary without compensation, and the result holds "exposure", estimate_exposure's report."""
     from .photo import photo_consistency as evaluate
     half, voxel = opts.pop("depth_half_window_s", DEFAULTS["depth_half_window_s"]), opts.pop("depth_voxel", DEFAULTS["depth_voxel"])
     chunk = opts.pop("chunk", 16)
     out = {"after": None, "before": None}
+    gains = None
     for name, poses, points in (("after", after, points_after), ("before", before, points_before)):
         if poses is None or points is None:
             continue
@@ -392,6 +398,22 @@ def photo_consistency(scans, scan_times, image_times, images, intr, width, heigh
         with V.DepthImages.render(scans, x, scan_times, image_times, Rcw, tcw, intr, width, height, half_window_s=half,
                                   voxel_size=voxel) as depth:
             out[name] = evaluate(points, images, Rcw, tcw, intr, width, height, depth=depth, chunk=chunk, device=scans.device, **opts)
+            if not exposure:
+                continue
+            if name == "after":
+                from .expo import estimate_exposure
+                kw = dict(exposure) if isinstance(exposure, dict) else {}
+                for k in ("occlusion_rel", "occlusion_abs", "max_depth", "holes", "min_views"):      # the evaluation's own
+                    if k in opts:
+                        kw.setdefault(k, opts[k])
+                out["exposure"] = estimate_exposure(points, images, Rcw, tcw, intr, width, height, depth=depth, chunk=chunk,
+                                                    device=scans.device, **kw)
+                gains = out["exposure"]["gains"]
+            if gains is not None:
+                raw = out[name]["summary"]
+                out[name] = evaluate(points, images, Rcw, tcw, intr, width, height, depth=depth, chunk=chunk, device=scans.device,
+                                     gains=gains, **opts)
+                out[name]["summary_raw"] = raw
     return out
 
 
@@ -1014,7 +1036,8 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
                       matches, enable_lidar_ba=True, enable_visual_ba=True, device=0, images=None, lidar_priors=None,
                       window_loss=None, stage_loss=None, camera_priors=None, map_quality=False, loop_closures=None, relax=None,
                       match_fn=None, match_depth=False, match_select=None, device_tracks=False, verify_matches=None,
-                      remove_dynamic=None, check_cameras=None, calibrate_extrinsic=False, photo_consistency=None, photo_align=None, **cfg):
+                      remove_dynamic=None, check_cameras=None, calibrate_extrinsic=False, photo_consistency=None, photo_align=None,
+                      exposure=None, **cfg):
     """LvbaSystem::runFullPipeline (src/lvba_system.cpp:136-142) on in-memory data: clouds = body-frame [n_i, >=3] float32
     arrays, poses [n,12] = x_buf_ (T_world<-imu), image_poses [m,12] the image poses from the odometry.  cfg: DEFAULTS' keys
     (visual_loss, colorize_leaf among them).  images: None, or the images ([m,H,W,3] BGR uint8 or a callable k -> [H,W,3]):
@@ -1083,7 +1106,14 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
     the report (without the per-image information matrices), and photo_align_cameras = (Rcw, tcw).  True reports only.  "apply":
     the `after` set of photo_consistency -- fused_after and its summary -- is evaluated at the aligned cameras; everything else
     stays as it is (the coloured maps keep the colours of the refined cameras: their points are what the alignment is made
-    against)."""
+    against).
+    exposure: None (off: nothing is launched, the stage's module is not imported and no lvba_expo_* entry point is called), True,
+    or a dict of expo.estimate_exposure's keywords; only together with photo_consistency (ValueError without it).  Per-image
+    exposure gains are estimated on the `after` set and applied to both evaluations (pipeline.photo_consistency's exposure); the
+    output's photo_consistency and fused_after / fused_before are then the compensated ones, photo_consistency_raw =
+    {"after": summary, "before": summary} are the summaries without compensation, and exposure is the report."""
+    if exposure and not photo_consistency:
+        raise ValueError("exposure compensates the photometric consistency: it needs photo_consistency=...")
     if photo_consistency and images is None:
         raise ValueError("photo_consistency samples the images: it needs images=...")
     if photo_align and images is None:
@@ -1186,7 +1216,7 @@ def run_full_pipeline(clouds, poses, scan_times, image_times, image_poses, Rci, 
             static, out["dynamic"] = _remove_dynamic(scans, out["poses"], **(dict(remove_dynamic) if isinstance(remove_dynamic, dict) else {}))
         try:
             _map_products(static if static is not None else scans, out, x_orig, scan_times, image_times, images, intr, width, height,
-                          map_quality, c, photo_consistency, photo_align)
+                          map_quality, c, photo_consistency, photo_align, exposure)
         finally:
             if static is not None:
                 static.close()
@@ -1210,7 +1240,8 @@ def _photo_align(scans, out, scan_times, image_times, images, intr, width, heigh
     return out["photo_align_cameras"] if apply else (v["Rcw"], v["tcw"])
 
 
-def _map_products(scans, out, x_orig, scan_times, image_times, images, intr, width, height, map_quality, c, photo=None, photo_align=None):
+def _map_products(scans, out, x_orig, scan_times, image_times, images, intr, width, height, map_quality, c, photo=None, photo_align=None,
+                  exposure=None):
     """run_full_pipeline's products made from every point of `scans`: the coloured maps, the photometric alignment, the photometric
     consistency and the map quality"""
     if images is not None:
@@ -1229,7 +1260,11 @@ def _map_products(scans, out, x_orig, scan_times, image_times, images, intr, wid
         kw.setdefault("depth_voxel", c["depth_voxel"])
         pc = _photo_consistency(scans, scan_times, image_times, images, intr, width, height,
                                 after=(out["poses"], Rcw_after, tcw_after), before=(x_orig, v["Rcw_before"], v["tcw_before"]),
-                                points_after=out["colored_after"][0], points_before=out["colored_before"][0], **kw)
+                                points_after=out["colored_after"][0], points_before=out["colored_before"][0],
+                                **({"exposure": exposure} if exposure else {}), **kw)
+        if exposure:
+            out["exposure"] = pc.pop("exposure")
+            out["photo_consistency_raw"] = {k: dict(q["summary_raw"]) for k, q in pc.items()}
         out["photo_consistency"] = {k: dict(q["summary"]) for k, q in pc.items()}
         out["photo_options"] = dict(pc["after"]["options"])
         for k, q in pc.items():
@@ -1273,7 +1308,7 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
                 image_sample_step=1, out_dir=None, device=0, colorize=False, map_quality=False, loop_closures=None, relax=None,
                 matching="db", match_opts=None, pair_selection=None, device_tracks=False, verify=None, features="db",
                 feature_opts=None, remove_dynamic=None, check_cameras=None, calibrate_extrinsic=False, photo_consistency=None,
-                photo_align=None, **cfg):
+                photo_align=None, exposure=None, **cfg):
     """initFromDatasetIO + runFullPipeline on a dataset directory; with out_dir, the refined LiDAR poses (TUM) and the COLMAP
     text files images.txt / points3D.txt the reference writes (src/lvba_system.cpp:2018-2137) are saved there.  images.txt is
     the reference's, character for character (tests/test_ref_system.py).
@@ -1320,6 +1355,9 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
     the two summaries and the options.
     photo_align (True, "apply" or a dict, as for run_full_pipeline): the images are read as for colorize=True; the output gains
     photo_align and photo_align_cameras, and out_dir gets photo_align.json: the report with its per-image arrays as lists.
+    exposure (True or a dict, as for run_full_pipeline; only with photo_consistency): the output gains exposure and
+    photo_consistency_raw, photo_consistency.json also holds "raw", the two summaries without compensation, and out_dir gets
+    exposure.json: the report with its per-image arrays as lists.
     cfg as for run_full_pipeline, e.g. visual_loss=REFERENCE_HUBER, window_loss=("cauchy", 0.1), stage_loss=("huber", 0.05),
     camera_priors=lambda cams: lidar_camera_priors(cams, Rci, tci, 1e-3, 0.02)."""
     import os
@@ -1377,6 +1415,7 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
                             if colorize or photo_consistency or photo_align else None, **({"map_quality": map_quality} if map_quality else {}),
                             **({"photo_consistency": photo_consistency} if photo_consistency else {}),
                             **({"photo_align": photo_align} if photo_align else {}),
+                            **({"exposure": exposure} if exposure else {}),
                             **({"loop_closures": loop_closures} if loop_closures else {}),
                             **({"relax": relax} if relax and loop_closures else {}),
                             **({"remove_dynamic": remove_dynamic} if remove_dynamic else {}),
@@ -1405,11 +1444,16 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
             import json
             with open(os.path.join(out_dir, "photo_consistency.json"), "w") as f:
                 json.dump({"after": out["photo_consistency"]["after"], "before": out["photo_consistency"]["before"],
-                           "options": out.get("photo_options")}, f, indent=1)
+                           "options": out.get("photo_options"),
+                           **({"raw": out["photo_consistency_raw"]} if "photo_consistency_raw" in out else {})}, f, indent=1)
+        plain = lambda q: q.tolist() if isinstance(q, np.ndarray) else [plain(e) for e in q] if isinstance(q, list) else \
+            {a: plain(b) for a, b in q.items()} if isinstance(q, dict) else q
+        if "exposure" in out:
+            import json
+            with open(os.path.join(out_dir, "exposure.json"), "w") as f:
+                json.dump(plain(out["exposure"]), f, indent=1)
         if "photo_align" in out:
             import json
-            plain = lambda q: q.tolist() if isinstance(q, np.ndarray) else [plain(e) for e in q] if isinstance(q, list) else \
-                {a: plain(b) for a, b in q.items()} if isinstance(q, dict) else q
             with open(os.path.join(out_dir, "photo_align.json"), "w") as f:
                 json.dump(plain(out["photo_align"]), f, indent=1)
         if "dynamic" in out:

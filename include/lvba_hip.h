@@ -1938,6 +1938,97 @@ int32_t lvba_palign_align(lvba_palign_t h, int32_t first, int32_t n, const doubl
 int32_t lvba_palign_profile(lvba_palign_t h, double *ms);
 void    lvba_palign_free(lvba_palign_t h);
 
+/* ---- per-image exposure compensation of the colour fusion (opt-in)
+ *   The fusion above assumes that a surface has the same grey level in every image.  A camera with auto-exposure and auto white
+ *   balance breaks that: the spread then measures exposure differences, which no pose change removes, and the fused colour shows
+ *   seams where the set of images that see a point changes.  This stage estimates a gain and an offset per image and channel
+ *   against the fused colours, and the fusion applies them.  The rule below is this project's own definition (the reference takes
+ *   one pixel of one image and has nothing of the kind), restated with Python integers in tests/expo_oracle.py; it is NOT pinned
+ *   against anything.  csrc/expo_device.h writes every scalar piece once.  Everything after the projection is integer arithmetic.
+ *   Gains.  int64_t gains [n_images][3][2] = (A, B) per image and channel, in the image's order b, g, r.  A in units of 2^-16, B
+ *     in units of 2^-16 of 1/256 grey level; the identity is (65536, 0).  The compensated sample of c16 is
+ *       c' = clamp(floor((A c16 + B + 32768) / 65536), 0, 65280)     in int64, floor towards minus infinity.
+ *     The clamp keeps the fusion's bounds on S1, S2 and n S2 - S1^2 as they are.
+ *   Fusion with gains, lvba_photo_add_images_gains: gains [n][3][2] are those of the images of this call; the sample is the
+ *     fusion's, except that c' takes the place of c16 in the sums.  gains == NULL or all identity gives the bytes of
+ *     lvba_photo_add_images.  lvba_photo_add_images, lvba_photo_opts and lvba_photo_summary are unchanged.
+ *   Estimation sums, lvba_expo_sums, per image against a reference ref16 [n][3] / valid [n] -- what lvba_palign_create takes, every
+ *     ref16 at most 65 280 -- under the gains gains_in [n][3][2] (NULL: identity).  A point with valid = 0 is skipped.  A valid point
+ *     is located in image j exactly as the fusion locates it (the same fate, max_depth and holes, the same (u, v), a, b and
+ *     texels).  Channel k of a located sample is USED iff (1) each of the four texel bytes of channel k lies in [sat_lo, sat_hi]
+ *     -- a clipped texel breaks the affine model -- and (2) where gate > 0, |c' - ref| <= gate 256 with c' under gains_in -- a
+ *     point coloured through a wrong occlusion decision or a specular highlight stays out.  Both are integer comparisons.
+ *     LVBA_EXPO_SUMS = 20 values of uint64 per image: per channel k at [6 k]: n, sum c, sum ref, sum c^2, sum c ref,
+ *     sum (c' - ref)^2 over the used terms, c = c16 raw; then [18] n_located, the located samples, and [19] the channel terms
+ *     that passed (1) and that the gate refused.  With fewer than 2^32 points every sum stays below 2^32 65280^2 < 2^64, because
+ *     65280^2 < 2^32.  The sums are integers: nothing depends on the batching or on how the images are split over calls.
+ *   Solve, lvba_expo_solve: host arithmetic only, pure integer arithmetic, in 128 bits where products need it: C++, Python
+ *     integers and any caller give the same bytes.  Per image and channel  D = n sum c^2 - (sum c)^2,  N = n sum c ref - sum c sum ref.
+ *       LVBA_EXPO_AFFINE (default):  A = floor((N 2^16 + D / 2) / D),  B = floor(((sum ref 2^16 - A sum c) 2 + n) / (2 n))
+ *       LVBA_EXPO_GAIN:              A = floor((sum c ref 2^16 + sum c^2 / 2) / sum c^2),  B = 0
+ *     (D / 2 and sum c^2 / 2 in integer division of non-negative numbers).  Per channel, in this order:
+ *       n < min_samples                                              -> LVBA_EXPO_TOO_FEW_SAMPLES
+ *       affine and D <= n^2 (min_spread 256)^2: the view is too flat to tell a gain from an offset
+ *                                                                    -> LVBA_EXPO_FALLBACK_GAIN, the channel takes the gain-only form
+ *       the gain-only form with sum c^2 = 0; A outside [min_gain, max_gain]; |B| above max_offset
+ *                                                                    -> LVBA_EXPO_OUT_OF_BOUNDS
+ *       else LVBA_EXPO_OK.  min_gain and max_gain are compared as floor(x 2^16 + 0.5), max_offset as floor(x 2^24 + 0.5).
+ *     Status per image: the worst of its three channels (the largest value).  With TOO_FEW_SAMPLES or OUT_OF_BOUNDS all three
+ *     channels of the image are the identity.
+ *   Gauge.  Alternating the fusion and the solve fixes the gains only up to one global affine map per channel; it is set so that
+ *     the mean gain is 1 and the mean offset 0, per channel over the n_ok images that are OK or FALLBACK_GAIN:
+ *       S = floor((n_ok 2^32 + sum A / 2) / sum A);  A <- floor((A S + 2^15) / 2^16);  B <- floor((B S + 2^15) / 2^16) - T
+ *     with T = floor((2 sum B + n_ok) / (2 n_ok)) of the scaled B, the round-half-up mean.  The spread then stays in the grey levels
+ *     of the average image and remains comparable with the uncompensated number.  An image whose gauged A is outside
+ *     [2^14, 2^18] or whose |B| is above 2^16 65280 -- gains the fusion would refuse -- becomes OUT_OF_BOUNDS with the identity.
+ *   lvba_expo_profile: ms [2], the device time of the uploads and of the sums passes, accumulated over the handle's calls.
+ *   Options (NULL: the defaults; all of them are this library's choice and none is tuned on recorded data): occlusion_rel,
+ *     occlusion_abs, max_depth, holes and max_batch_images as in lvba_photo_opts; model LVBA_EXPO_AFFINE; sat_lo 4, sat_hi 251;
+ *     gate 30 grey levels (0: off); min_samples 200; min_spread 2 grey levels; min_gain 0.25, max_gain 4, max_offset 64 grey levels.
+ *   LVBA_ERR_ARG, before any device work, outputs untouched and the handle still valid: a null pointer (gains and gains_in may
+ *   be NULL); n < 0 or n >= 2^32; width or height < 2; n_images < 1 or > 32 768 (the solve: < 0); a depth set of another image
+ *   count, size or device; non-finite intrinsics or focal lengths <= 0; non-finite cameras; (first, n) outside [0, n_images); an
+ *   image index added twice (the fusion); occlusion_rel, occlusion_abs or max_depth negative or non-finite; max_batch_images < 0;
+ *   an unknown model; sat_lo < 0, sat_hi > 255 or sat_lo > sat_hi; gate or min_spread outside 0 .. 255; min_samples < 2;
+ *   min_gain outside [0.25, 1]; max_gain outside [1, 4]; max_offset outside [0, 255]; a ref16 above 65 280; an A outside
+ *   [2^14, 2^18] or a |B| above 2^16 65280 in gains or gains_in; sums given to the solve that fewer than 2^32 samples of at most
+ *   65 280 cannot have.
+ *   lvba_expo_free destroys the handle.  lvba_version() is unchanged; a client detects the stage by looking lvba_expo_create up. */
+#define LVBA_EXPO_OK 0
+#define LVBA_EXPO_FALLBACK_GAIN 1
+#define LVBA_EXPO_TOO_FEW_SAMPLES 2
+#define LVBA_EXPO_OUT_OF_BOUNDS 3
+#define LVBA_EXPO_AFFINE 0
+#define LVBA_EXPO_GAIN 1
+#define LVBA_EXPO_SUMS 20
+typedef struct lvba_expo_s *lvba_expo_t;
+typedef struct lvba_expo_opts {
+    double occlusion_rel;     /* 0.05 */
+    double occlusion_abs;     /* 0.1 m */
+    double max_depth;         /* 0 = none */
+    double min_gain;          /* 0.25 */
+    double max_gain;          /* 4 */
+    double max_offset;        /* 64 grey levels */
+    int32_t holes;            /* 0 */
+    int32_t model;            /* LVBA_EXPO_AFFINE */
+    int32_t sat_lo;           /* 4 */
+    int32_t sat_hi;           /* 251 */
+    int32_t gate;             /* 30 grey levels; 0 = off */
+    int32_t min_samples;      /* 200; >= 2 */
+    int32_t min_spread;       /* 2 grey levels */
+    int32_t max_batch_images; /* 0 = by free memory */
+} lvba_expo_opts;             /* 80 bytes */
+void    lvba_expo_default_opts(lvba_expo_opts *o);
+int32_t lvba_expo_create(int32_t device, int64_t n, const float *xyz, const uint16_t *ref16, const uint8_t *valid, int32_t n_images,
+                         int32_t width, int32_t height, const double *intr, lvba_depth_t depth, const lvba_expo_opts *o, lvba_expo_t *out);
+int32_t lvba_expo_sums(lvba_expo_t h, int32_t first, int32_t n, const double *Rcw, const double *tcw, const uint8_t *bgr,
+                       const int64_t *gains_in, uint64_t *sums);
+int32_t lvba_expo_solve(int32_t n_images, const uint64_t *sums, const lvba_expo_opts *o, int64_t *gains, int32_t *status);
+int32_t lvba_expo_profile(lvba_expo_t h, double *ms);
+void    lvba_expo_free(lvba_expo_t h);
+int32_t lvba_photo_add_images_gains(lvba_photo_t h, int32_t first, int32_t n, const double *Rcw, const double *tcw, const uint8_t *bgr,
+                                    const int64_t *gains);
+
 #ifdef __cplusplus
 }
 #endif
