@@ -51,6 +51,8 @@ SYMBOLS = [
     "lvba_palign_default_opts", "lvba_palign_create", "lvba_palign_linearize", "lvba_palign_align", "lvba_palign_profile", "lvba_palign_free",
     "lvba_expo_default_opts", "lvba_expo_create", "lvba_expo_sums", "lvba_expo_solve", "lvba_expo_profile", "lvba_expo_free",
     "lvba_photo_add_images_gains",
+    "lvba_undistort_default_opts", "lvba_undistort_tile", "lvba_undistort_create", "lvba_undistort_info", "lvba_undistort_images",
+    "lvba_undistort_map", "lvba_undistort_profile", "lvba_undistort_free",
 ]
 
 OK, ERR_ARG, ERR_DEVICE, ERR_NOMEM, ERR_UNSUPPORTED, ERR_DIST, ERR_STATE = 0, -1, -2, -3, -4, -5, -6
@@ -323,6 +325,12 @@ class ExpoOpts(Struct):
                 ("max_batch_images", C.c_int32)]
 
 
+class UndistortOpts(Struct):
+    """lvba_undistort_opts"""
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("out_width", C.c_int32),
+                ("out_height", C.c_int32), ("border", C.c_int32), ("max_batch_images", C.c_int32)]
+
+
 class SiftOpts(Struct):
     """lvba_sift_opts"""
     _fields_ = [("first_octave", C.c_int32), ("n_intervals", C.c_int32), ("sigma0", C.c_double), ("dog_threshold", C.c_double),
@@ -406,7 +414,7 @@ STRUCTS = {
     "lvba_verify_opts": VerifyOpts, "lvba_sift_opts": SiftOpts, "lvba_dynamic_opts": DynamicOpts,
     "lvba_dynamic_summary": DynamicSummary, "lvba_resect_opts": ResectOpts,
     "lvba_calib_opts": CalibOpts, "lvba_calib_td_opts": CalibTdOpts, "lvba_photo_opts": PhotoOpts, "lvba_photo_summary": PhotoSummary,
-    "lvba_palign_opts": PalignOpts, "lvba_expo_opts": ExpoOpts,
+    "lvba_palign_opts": PalignOpts, "lvba_expo_opts": ExpoOpts, "lvba_undistort_opts": UndistortOpts,
 }
 
 _INTS = (C.c_int32, C.c_int64, C.c_uint64)
@@ -703,6 +711,15 @@ def load():
     lib.lvba_expo_free.argtypes = [H]
     lib.lvba_expo_free.restype = None
     lib.lvba_photo_add_images_gains.argtypes = _palign + [C.c_void_p]
+    lib.lvba_undistort_default_opts.argtypes = [C.POINTER(UndistortOpts)]
+    lib.lvba_undistort_tile.argtypes = [C.POINTER(C.c_int32)] * 3
+    lib.lvba_undistort_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(UndistortOpts), C.POINTER(H)]
+    lib.lvba_undistort_info.argtypes = [H, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_int64)]
+    lib.lvba_undistort_images.argtypes = [H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.lvba_undistort_map.argtypes = [H, C.c_void_p, C.c_void_p]
+    lib.lvba_undistort_profile.argtypes = [H, C.c_void_p]
+    lib.lvba_undistort_free.argtypes = [H]
+    lib.lvba_undistort_free.restype = None
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if name.endswith("_default_opts") or name in ("lvba_depth_destroy", "lvba_colorize_destroy"):     # these return void

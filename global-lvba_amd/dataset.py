@@ -219,12 +219,32 @@ def load_dataset(dataset_path):
 
 
 # ------------------------------------------------------------------------------------------------------------- COLMAP text
-def write_images_txt(path, q_cw, t_cw):
-    """q_cw [M,4] (w,x,y,z), t_cw [M,3] -> COLMAP images.txt body as the reference writes it (ids = row index)."""
+def write_images_txt(path, q_cw, t_cw, ext="jpg"):
+    """q_cw [M,4] (w,x,y,z), t_cw [M,3] -> COLMAP images.txt body as the reference writes it (ids = row index).  ext: the
+    extension of the image names; the reference's is jpg."""
     with open(path, "w") as f:
         for k, (q, t) in enumerate(zip(np.asarray(q_cw).reshape(-1, 4), np.asarray(t_cw).reshape(-1, 3))):
-            f.write(f"{k} {q[0]:.6f} {q[1]:.6f} {q[2]:.6f} {q[3]:.6f} {t[0]:.6f} {t[1]:.6f} {t[2]:.6f} 1 {k}.jpg\n")
+            f.write(f"{k} {q[0]:.6f} {q[1]:.6f} {q[2]:.6f} {q[3]:.6f} {t[0]:.6f} {t[1]:.6f} {t[2]:.6f} 1 {k}.{ext}\n")
             f.write("0.0 0.0 -1\n")
+
+
+def write_cameras_txt(path, width, height, pinhole):
+    """COLMAP cameras.txt with the one camera images.txt's rows name: `1 PINHOLE w h fx fy cx cy`, pinhole = (fx, fy, cx, cy)."""
+    fx, fy, cx, cy = (float(v) for v in pinhole)
+    with open(path, "w") as f:
+        f.write(f"1 PINHOLE {int(width)} {int(height)} {fx!r} {fy!r} {cx!r} {cy!r}\n")
+
+
+def write_image_bgr(path, bgr, quality=95):
+    """An image [h, w, 3] uint8 in B, G, R order, written with Pillow in the format of the path's extension: JPEG (the
+    reference's, at `quality`) or PNG (lossless).  A mask [h, w] is written as a grey image."""
+    from PIL import Image
+    a = np.asarray(bgr, np.uint8)
+    im = Image.fromarray(np.ascontiguousarray(a[:, :, ::-1]) if a.ndim == 3 else a)
+    if os.path.splitext(path)[1].lower() in (".jpg", ".jpeg"):
+        im.save(path, quality=int(quality))
+    else:
+        im.save(path)
 
 
 def write_points3d_txt(path, xyz, rgb):

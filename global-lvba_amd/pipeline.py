@@ -1280,6 +1280,50 @@ def _map_products(scans, out, x_orig, scan_times, image_times, images, intr, wid
 #     <data_path>/all_image/image_poses.txt + <timestamp>.png         TUM poses of the images + the images (only their names are read)
 #     <data_path>/<colmap_db_path>                                    keypoints + inlier matches (loadFromColmapDB)
 # ---------------------------------------------------------------------------------------------------------------------
+UNDISTORT_FORMATS = ("jpg", "png")
+
+
+def export_undistorted(out_dir, images, n, intr, width, height, gains=None, format="jpg", quality=95, chunk=16, device=0, **opts):
+    """The images the rows of images.txt name (the reference's Colmap/images/k.jpg, src/lvba_system.cpp:2029), undistorted on the
+    GPU (undistort.undistort_images): out_dir/images/<k>.<format> for k < n, out_dir/images_mask.png (255 where a
+    pixel has a source, 0 where it is border) and out_dir/cameras.txt, the pinhole camera those images and the poses of images.txt
+    belong to.  images: an array [n, height, width, 3] BGR uint8 or a callable k -> [height, width, 3].  gains: None, or the
+    exposure gains int64 [n, 3, 2] (§10r), applied on the way out.  format: "jpg" (the reference's) or "png" (lossless).  opts:
+    undistort.undistort_opts' options.  Returns dict(size (w', h'), pinhole, n_valid, profile: the three device times, n_files,
+    format, options)."""
+    import os
+    if format not in UNDISTORT_FORMATS:
+        raise ValueError(f"format={format!r}: one of {UNDISTORT_FORMATS}")
+    from . import dataset as D
+    from .undistort import undistort_images
+    img_dir = os.path.join(out_dir, "images")
+    os.makedirs(img_dir, exist_ok=True)
+    rep, n_files = {}, 0
+    for k, bgr in undistort_images(images, intr, width, height, gains=gains, chunk=chunk, device=device, n=n, report=rep, **opts):
+        D.write_image_bgr(os.path.join(img_dir, f"{k}.{format}"), bgr, quality=quality)
+        n_files += 1
+    D.write_image_bgr(os.path.join(out_dir, "images_mask.png"), rep.pop("mask"))
+    D.write_cameras_txt(os.path.join(out_dir, "cameras.txt"), rep["size"][0], rep["size"][1], rep["pinhole"])
+    return dict(size=list(rep["size"]), pinhole=list(rep["pinhole"]), n_valid=rep["n_valid"], profile=rep["profile"], n_files=n_files,
+                format=format, options=rep["options"])
+
+
+def _undistort_request(undistorted_images, exposure):
+    """run_dataset's undistorted_images as (format, apply_exposure, undistort options), checked without touching a device"""
+    kw = dict(undistorted_images) if isinstance(undistorted_images, dict) else {}
+    fmt, apply_exposure = kw.pop("format", "jpg"), bool(kw.pop("apply_exposure", False))
+    from . import _lib as L
+    names = L.option_names(L.UndistortOpts)              # the struct's mirror: the library is not loaded
+    unknown = sorted(k for k in kw if k not in names + ("quality", "chunk"))
+    if unknown:
+        raise ValueError(f"undistorted_images: unknown keys {unknown}; one of {('format', 'apply_exposure', 'quality', 'chunk') + names}")
+    if fmt not in UNDISTORT_FORMATS:
+        raise ValueError(f"undistorted_images: format={fmt!r}: one of {UNDISTORT_FORMATS}")
+    if apply_exposure and not exposure:
+        raise ValueError("undistorted_images: apply_exposure=True applies the gains of the exposure stage: it needs exposure=...")
+    return fmt, apply_exposure, kw
+
+
 def list_image_ids(image_dir, stride=1):
     """DatasetIO::handleImages (src/dataset_io.cpp:77-131): numeric ids of *.png/.jpg/.jpeg/.bmp, sorted, every stride-th."""
     import os
@@ -1308,7 +1352,7 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
                 image_sample_step=1, out_dir=None, device=0, colorize=False, map_quality=False, loop_closures=None, relax=None,
                 matching="db", match_opts=None, pair_selection=None, device_tracks=False, verify=None, features="db",
                 feature_opts=None, remove_dynamic=None, check_cameras=None, calibrate_extrinsic=False, photo_consistency=None,
-                photo_align=None, exposure=None, **cfg):
+                photo_align=None, exposure=None, undistorted_images=None, **cfg):
     """initFromDatasetIO + runFullPipeline on a dataset directory; with out_dir, the refined LiDAR poses (TUM) and the COLMAP
     text files images.txt / points3D.txt the reference writes (src/lvba_system.cpp:2018-2137) are saved there.  images.txt is
     the reference's, character for character (tests/test_ref_system.py).
@@ -1358,6 +1402,13 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
     exposure (True or a dict, as for run_full_pipeline; only with photo_consistency): the output gains exposure and
     photo_consistency_raw, photo_consistency.json also holds "raw", the two summaries without compensation, and out_dir gets
     exposure.json: the report with its per-image arrays as lists.
+    undistorted_images: None (off: nothing of the stage is launched and its module is not imported), True, or a dict with the keys
+    format ("jpg", the reference's, or "png"), apply_exposure, quality, chunk and undistort.undistort_opts' options; needs out_dir.
+    The images are read as for colorize=True and, after the run, written undistorted (export_undistorted):
+    out_dir/images/<k>.<format>, one per image and per row of images.txt, images_mask.png and cameras.txt, the pinhole camera
+    they belong to.  The output gains undistorted, the exporter's report, and out_dir gets undistorted.json.  With format="png"
+    images.txt names k.png.  apply_exposure=True applies out["exposure"]'s gains on the way out and needs exposure (ValueError
+    without it); unknown keys raise ValueError before any device is touched.
     cfg as for run_full_pipeline, e.g. visual_loss=REFERENCE_HUBER, window_loss=("cauchy", 0.1), stage_loss=("huber", 0.05),
     camera_priors=lambda cams: lidar_camera_priors(cams, Rci, tci, 1e-3, 0.02)."""
     import os
@@ -1367,6 +1418,10 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
     if features == "images" and matching not in ("descriptors", "guided", "depth"):
         raise ValueError(f"features='images' needs matching='descriptors', 'guided' or 'depth', not {matching!r}: the database's matches "
                          "index the database's key points")
+    if undistorted_images:
+        und_format, und_exposure, und_opts = _undistort_request(undistorted_images, exposure)
+        if out_dir is None:
+            raise ValueError("undistorted_images writes files: it needs out_dir")
     if pair_selection and matching not in ("guided", "depth"):
         raise ValueError(f"pair_selection needs matching='guided' or 'depth' (refined poses and depth images before the matching), not {matching!r}")
     ds = D.load_dataset(data_path)
@@ -1427,7 +1482,8 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
         D.write_poses_tum(os.path.join(out_dir, "lidar_poses_refined.txt"), ds["timestamps"], out["poses"])
         v = out.get("visual")
         if v is not None and len(v.get("landmarks", [])):
-            D.write_images_txt(os.path.join(out_dir, "images.txt"), rot_to_quat_wxyz(v["Rcw"]), v["tcw"])
+            D.write_images_txt(os.path.join(out_dir, "images.txt"), rot_to_quat_wxyz(v["Rcw"]), v["tcw"],
+                               **({"ext": und_format} if undistorted_images and und_format != "jpg" else {}))
             if not colorize:
                 ok = v["landmark_valid"] > 0
                 D.write_points3d_txt(os.path.join(out_dir, "points3D.txt"), v["landmarks"][ok], np.full((int(ok.sum()), 3), 255))
@@ -1452,6 +1508,13 @@ def run_dataset(data_path, colmap_db_path, intr, width, height, Rcl, Pcl, extrin
             import json
             with open(os.path.join(out_dir, "exposure.json"), "w") as f:
                 json.dump(plain(out["exposure"]), f, indent=1)
+        if undistorted_images:
+            import json
+            out["undistorted"] = export_undistorted(
+                out_dir, lambda k: D.read_image_bgr(os.path.join(img_dir, names[k]), width, height), len(names), intr, width, height,
+                gains=out["exposure"]["gains"] if und_exposure else None, format=und_format, device=device, **und_opts)
+            with open(os.path.join(out_dir, "undistorted.json"), "w") as f:
+                json.dump(plain(out["undistorted"]), f, indent=1)
         if "photo_align" in out:
             import json
             with open(os.path.join(out_dir, "photo_align.json"), "w") as f:

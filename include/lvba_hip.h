@@ -2029,6 +2029,57 @@ void    lvba_expo_free(lvba_expo_t h);
 int32_t lvba_photo_add_images_gains(lvba_photo_t h, int32_t first, int32_t n, const double *Rcw, const double *tcw, const uint8_t *bgr,
                                     const int64_t *gains);
 
+/* ---- the undistorted images of the COLMAP export (opt-in)
+ *   The reference's end product names an image k.jpg per row of images.txt and writes it undistorted (DatasetIO::undistortImage,
+ *   src/dataset_io.cpp:15-26: initUndistortRectifyMap with newK = K, then remap(INTER_LINEAR)); the poses of images.txt belong to
+ *   that pinhole image, not to the raw Brown-Conrady one.  This stage writes those pixels.  The rule below is this project's own
+ *   definition, restated in numpy in tests/undistort_oracle.py; it is NOT pinned against OpenCV, whose fixed-point map and weight
+ *   table are not restated.  csrc/undistort_device.h writes every scalar piece once.
+ *   Inputs: the source camera intr [8] = fx fy cx cy k1 k2 p1 p2 and size w x h, images BGR uint8 [n][h][w][3]; the target
+ *     pinhole fx' fy' cx' cy' (fx' = 0: all four from the source, the reference's newK = K) and size w' x h' (0: the source's).
+ *   Position.  For target pixel column i, row j:  x = (i - cx') / fx',  y = (j - cy') / fy',  (u, v) = the projection of the
+ *     camera-frame point (x, y, 1) through the source camera -- the fusion's own projection, the same doubles: + - * / in fp64 in
+ *     a file built without contraction.  The pixel is VALID iff the projection succeeds and 0 <= u < w - 1, 0 <= v < h - 1, the
+ *     range the colour fusion samples in.
+ *   Colour.  An invalid pixel is `border` in its three bytes and its mask byte is 0 (a valid one's is 255).  Channel k of a valid
+ *     pixel: c16 = the fusion's sample at (u, v), 1/256-pixel fractions and integer weights, in 1/256 grey level; with gains,
+ *     c16 <- the compensated sample under the image's (A, B) of channel k (§10r above); the byte is (c16 + 128) >> 8, at most 255.
+ *     What a pinhole projection reads from the exported image is therefore byte for byte what the fusion read from the raw one.
+ *   Two differences from OpenCV's remap: no partial blend with the border in the source's last row and column (such a pixel is
+ *     invalid), and fractions of 1/256 pixel, not 1/32.  The polynomial model can fold far outside the image: a target field of
+ *     view much wider than the source's shows mirrored content there, as it does under OpenCV; this is left alone.
+ *   gains: NULL, or int64 [n][3][2] of the images of the call, as lvba_photo_add_images_gains takes them.  The bytes do not depend
+ *     on max_batch_images (default 64, which keeps the stage's device memory small; 0: batches by the free memory, as the
+ *     fusion's) or on how the images are split over calls.
+ *   lvba_undistort_tile: host only; the kernel's pixels per lane and its tile of the target, the sizes a test puts its cases at.
+ *   lvba_undistort_info: each output may be NULL; pinhole [4] = fx' fy' cx' cy' as resolved; n_valid the valid target pixels.
+ *   lvba_undistort_map: uv [h'][w'][2] (NaN where invalid) and mask [h'][w'], either may be NULL; a small kernel of its own over
+ *     the same position function.  lvba_undistort_profile: ms [3], the device time of the uploads, the kernel and the downloads,
+ *     accumulated over the handle's calls.
+ *   LVBA_ERR_ARG, before any device work, outputs untouched and the handle still valid: a null pointer (opts, gains and the
+ *   outputs named above may be NULL); n < 0; a source or target width or height below 2; non-finite intrinsics or source focal
+ *   lengths <= 0; a non-finite target pinhole or a target focal length <= 0 (fx' = 0 alone means the source's); border outside
+ *   0 .. 255; max_batch_images < 0; an A outside [2^14, 2^18] or a |B| above 2^16 65280 in gains.
+ *   lvba_undistort_free destroys the handle.  lvba_version() is unchanged; a client detects the stage by looking
+ *   lvba_undistort_create up. */
+typedef struct lvba_undistort_s *lvba_undistort_t;
+typedef struct lvba_undistort_opts {
+    double fx, fy, cx, cy;    /* the target pinhole; fx = 0: the source's four */
+    int32_t out_width;        /* 0 = the source's */
+    int32_t out_height;       /* 0 = the source's */
+    int32_t border;           /* 0; the grey level of an invalid pixel, 0 .. 255 */
+    int32_t max_batch_images; /* 64; 0 = by free memory */
+} lvba_undistort_opts;        /* 48 bytes */
+void    lvba_undistort_default_opts(lvba_undistort_opts *o);
+int32_t lvba_undistort_tile(int32_t *pixels_per_lane, int32_t *tile_width, int32_t *tile_height);
+int32_t lvba_undistort_create(int32_t device, int32_t width, int32_t height, const double intr[8], const lvba_undistort_opts *o,
+                              lvba_undistort_t *out);
+int32_t lvba_undistort_info(lvba_undistort_t h, int32_t *out_width, int32_t *out_height, double pinhole[4], int64_t *n_valid);
+int32_t lvba_undistort_images(lvba_undistort_t h, int32_t n, const uint8_t *bgr, const int64_t *gains, uint8_t *bgr_out);
+int32_t lvba_undistort_map(lvba_undistort_t h, double *uv, uint8_t *mask);
+int32_t lvba_undistort_profile(lvba_undistort_t h, double ms[3]);
+void    lvba_undistort_free(lvba_undistort_t h);
+
 #ifdef __cplusplus
 }
 #endif
